@@ -7,7 +7,14 @@ interval (0, 0.1775) holding 44 eigenvalues, 16 Gauss quadrature nodes, M0 = 64,
 outer tolerance 1e-12.  A "step" = one complete FEAST solve (all refinement loops until the
 max relative residual of the inside eigenpairs is <= 1e-12) with A and B resident in HBM.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the headline line (with the roofline
+of the timed steps' own sampled timers).  --full adds the secondary measurements after it: the
+complex64-panel run, the reference's default contour and default call, the sparse direct solver,
+the measured CPU baseline and the dense cfg 2 / cfg 5 configurations.  --dump-outputs DIR writes
+the last timed step's result (eigenvalues, eigenvectors, residuals, epsout / M / loop / info) as
+float64 .npy files; the inputs are closed-form or seeded, identical from run to run.
 
 N > 1 without WORLD_SIZE in the environment: bench.py launches its own ranks (a child
 `python -m torch.distributed.run --nproc-per-node N ... bench.py`, started BEFORE this process
@@ -229,6 +236,34 @@ def dense_configs(fk, eng):
     return out
 
 
+DUMP_LIMIT_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(dirname, res, seed=20260515):
+    """The arrays a caller of the timed path receives from its last step, as float64 .npy files: lambda, q (real and
+    imaginary parts when complex), res, and epsout / M / loop / info.  Should q ever exceed the 64 MB budget, a fixed,
+    seeded sample of its rows (sorted, listed in q_rows.npy) is written instead."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {"lambda": np.asarray(res.lambda_), "res": np.asarray(res.res)}
+    q = np.asarray(res.q)
+    other = sum(a.size * (2 if np.iscomplexobj(a) else 1) * 8 for a in arrays.values()) + 4096
+    q_parts = 2 if np.iscomplexobj(q) else 1
+    if q.size * q_parts * 8 > DUMP_LIMIT_BYTES - other:
+        n_rows = max(1, int((DUMP_LIMIT_BYTES - other) // (q_parts * 8 * max(q.shape[1], 1) + 8)))
+        rows = np.sort(np.random.default_rng(seed).choice(q.shape[0], size=min(n_rows, q.shape[0]), replace=False))
+        q = q[rows]
+        arrays["q_rows"] = rows.astype(np.float64)
+    arrays["q"] = q
+    arrays["summary"] = np.array([res.epsout, res.M, res.loop, res.info], dtype=np.float64)   # epsout, M, loop, info
+    for name, a in arrays.items():
+        if np.iscomplexobj(a):
+            np.save(os.path.join(dirname, name + "_real.npy"), np.ascontiguousarray(a.real, dtype=np.float64))
+            np.save(os.path.join(dirname, name + "_imag.npy"), np.ascontiguousarray(a.imag, dtype=np.float64))
+        else:
+            np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def free_port():
     s = socket.socket()
     s.bind(("127.0.0.1", 0))
@@ -247,13 +282,22 @@ def main():
     ap.add_argument("--solver", default="cocg", choices=["cocg", "bicgstab"])
     ap.add_argument("--contour", default="gauss", choices=["gauss", "trapezoid", "zolotarev"], help="fpm[16]")
     ap.add_argument("--aspect", type=int, default=4000, help="fpm[18]: ellipse ratio a/b x 100 (100 = the reference's default circle)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-dense", action="store_true", help="skip the cfg 2 / cfg 5 dense measurements after the headline")
-    ap.add_argument("--no-default-contour", action="store_true", help="skip the secondary run on the reference's default contour")
-    ap.add_argument("--headline-only", action="store_true", help="only the timed headline solve (profiling passes): no mixed-precision, "
-                    "default-contour, CPU or dense measurements")
+    ap.add_argument("--full", action="store_true", help="after the headline: mixed-precision, default-contour, default-call, "
+                    "sparse-direct, CPU-baseline and dense cfg 2 / cfg 5 measurements (a plain run times the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's result arrays to DIR/<name>.npy (float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the measured CPU baseline")
+    ap.add_argument("--no-dense", action="store_true", help="with --full: skip the cfg 2 / cfg 5 dense measurements after the headline")
+    ap.add_argument("--no-default-contour", action="store_true", help="with --full: skip the secondary runs on the reference's "
+                    "default contour and call and the sparse direct run")
+    ap.add_argument("--headline-only", action="store_true", help="only the timed headline solve, even with --full (what a plain "
+                    "run does)")
     ap.add_argument("--reduced-solver", default="host", choices=["host", "device"])
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # launch our own ranks; nothing in this process has touched the GPU yet (no torch import, no HIP call)
@@ -435,7 +479,9 @@ def main():
         "solve_seconds_last_step": round(float(res.stats.get("solve_seconds", 0.0)), 4),
         "roofline": cands[0] if cands else None, "roofline_other": cands[1:], "kernel_classes": classes,
     }
-    if rk == 0 and nr == 1 and not args.headline_only:
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, res)
+    if rk == 0 and nr == 1 and args.full and not args.headline_only:
         # secondary measurements, none of them the headline value
         fence()
         step(32)
