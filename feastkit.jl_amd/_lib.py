@@ -60,6 +60,8 @@ SYMBOLS = {
     "feasthip_rayleigh_ritz_dev": (_i, [_vp, _i64, _vp, _d, _d, _i, _vp, _vp, _vp, _vp]),
     "feasthip_contour_apply": (_i, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _ps]),
     "feasthip_contour_apply_dev": (_i, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _ps]),
+    "feasthip_estimate_count": (_i, [_vp, _i64, C.c_uint64, _pd, _vp, _ps]),
+    "feasthip_random_block_dev": (_i, [_vp, _i64, C.c_uint64, _vp]),
     "feasthip_contour_apply_resident": (_i, [_vp, _i64, _vp, _vp, _vp, _ps]),
     "feasthip_rr_reduce_resident": (_i, [_vp, _i64, _d, _i, _pi, _vp, _vp]),
     "feasthip_rr_ritz_resident": (_i, [_vp, _i64, _vp, _vp, _i64, _i, _i, _vp]),

@@ -11,7 +11,8 @@ import numpy as np
 import scipy.sparse as sp
 
 from .engine import HipEngine
-from .hip_backend import feast_hip_general, feast_hip_hermitian
+from .contour import feast_contour, feast_gcontour
+from .hip_backend import ESTIMATE_SEED, feast_hip_estimate, feast_hip_general, feast_hip_hermitian
 from .parameters import feastdefault, feastinit
 from .types import FEAST_UNINITIALIZED, FeastHipError, FeastResult
 
@@ -168,6 +169,64 @@ def _release_band_factors(eng, keep):
         pass                                   # a poisoned handle reports through the result, not from the clean-up
 
 
+# ---- stochastic eigenvalue-count estimate (fpm[14] = 2) and M0 = "auto" ----------------------------------------------
+ESTIMATE_TOL = 1e-8        # inner tolerance of the estimate's Krylov solves (zero start): loose solves bias every t_j
+AUTO_SAMPLES = 64          # samples of the estimate behind M0 = "auto"
+
+
+def _estimate_solver(eng, A, B, nodes, solver, group, general):
+    """The solver of the estimate's sweep: the caller's when named, else (solver=:direct) the direct solver where it applies
+    -- dense input, or a sparse pattern whose direct factors fit the device (_band_direct_fits) -- and otherwise the Krylov
+    solver for the pencil (COCG for real symmetric input, BiCGStab otherwise)."""
+    if solver == "sparse_direct":
+        return "banded"
+    if solver not in ("direct", "lu", "krylov"):
+        return solver
+    if not sp.issparse(A):
+        return "direct"
+    if solver != "krylov" and _band_direct_fits(eng, A, B, nodes, group, complexify=general):
+        return "banded"
+    real_input = not (np.iscomplexobj(A.data) or (B is not None and np.iscomplexobj(B.data)))
+    return "cocg" if (real_input and not general) else "bicgstab"
+
+
+def _run_estimate(eng, A, B, Zne, Wne, general, m, seed, solver, solver_tol, solver_maxiter, solver_restart, group):
+    """(info, estimate dict or None) of feast_hip_estimate with the solver rule above; the direct factors go afterwards."""
+    use = _estimate_solver(eng, A, B, len(Zne), solver, group, general)
+    if general:                                     # the shifted systems of the full contour are complex (feast_hip_general)
+        A = A.astype(np.complex128) if not np.iscomplexobj(A.data if sp.issparse(A) else A) else A
+        B = None if B is None else (B.astype(np.complex128) if not np.iscomplexobj(B.data if sp.issparse(B) else B) else B)
+    tol = float(solver_tol) if solver_tol and float(solver_tol) > 0.0 else ESTIMATE_TOL
+    try:
+        return feast_hip_estimate(eng, A, B, Zne, Wne, 1.0 if general else 2.0, int(m), general=general,
+                                  seed=ESTIMATE_SEED if seed is None else int(seed), solver=use, solver_tol=tol,
+                                  solver_maxiter=2000 if solver_maxiter is None else int(solver_maxiter),
+                                  solver_restart=solver_restart, group=group)
+    finally:
+        _release_band_factors(eng, False)
+
+
+def _estimate_result(N, info, est, real):
+    """FeastResult of an fpm[14] = 2 call: no eigenpairs, M = max(0, round(Re mean)), the estimate in stats."""
+    M = 0 if est is None else max(0, int(round(float(np.real(est["mean"])))))
+    q = np.zeros((N, 0), dtype=np.float64 if real else np.complex128)
+    lam = np.zeros(0, dtype=np.float64 if real else np.complex128)
+    return FeastResult(lam, q, M, np.zeros(0), int(info), 0.0, 0, {"estimate": est})
+
+
+def auto_M0(est, N):
+    """M0 for a solve after an estimate: 1.5 x (mean + 2 stderr) (FEAST's sizing advice), at least 8, at most N."""
+    return int(min(N, max(8, math.ceil(1.5 * (float(np.real(est["mean"])) + 2.0 * float(est["stderr"]))))))
+
+
+def _estimate_fpm(fpm):
+    """Parameters of the estimate behind M0 = "auto": the caller's, with fpm[14] = 2 and the estimate's own node counts
+    (fpm[2] = 3, fpm[8] = 6) -- the contour shape (fpm[16], fpm[18], fpm[19]) stays the caller's."""
+    e = (feastinit() if fpm is None else np.array(fpm, dtype=np.int64)).copy()
+    e[14], e[2], e[8] = 2, FEAST_UNINITIALIZED, FEAST_UNINITIALIZED
+    return feastdefault(e)
+
+
 def _engine(engine, device):
     return engine if engine is not None else HipEngine(device)
 
@@ -175,7 +234,7 @@ def _engine(engine, device):
 def feast(A, B=None, interval=None, *, M0=10, fpm=None, backend="hip", solver="direct", solver_tol=0.0,
           solver_maxiter=None, solver_restart=30, warm_start=None, inner_rtol=None, real_projection=None,
           inner_precision=64, group=None, engine=None, device=0, Q0=None, contour=None, contour_policy=None,
-          keep_factors=False):
+          keep_factors=False, seed=None):
     """feast(A, [B,] (Emin, Emax); M0, fpm, backend=:hip) for real-symmetric / Hermitian
     dense (numpy) or sparse (scipy) matrices.  Real input is complexified and the result is
     real.(q), exactly as feast_sygv!/feast_scsrgv! do (src/dense/feast_dense.jl:362-387).
@@ -185,7 +244,21 @@ def feast(A, B=None, interval=None, *, M0=10, fpm=None, backend="hip", solver="d
     cached across the refinement loops of ONE call, like the reference's per-call ``lu(zB - A)`` cache
     (src/sparse/feast_sparse.jl:335-341), and released when the call returns; ``True`` leaves them resident on the engine
     for a repeated call on the same contour (``engine.free_factors()`` releases them).
+    ``fpm[14] = 2``: no eigensolve -- a stochastic estimate of the number of eigenvalues in the interval from one contour
+    sweep over M0 Rademacher columns (hip_backend.feast_hip_estimate; ``seed`` picks the block, default the package seed).
+    The result has no eigenpairs, M = round(mean) and ``stats["estimate"]`` = {mean, stderr, samples, nodes, solver, seed,
+    seconds}; a node that fails (status 5 / 8) gives that info and ``stats["estimate"] = None``.
+    ``M0="auto"``: such an estimate with 64 samples first, then the solve with M0 = min(N, max(8, ceil(1.5 (mean +
+    2 stderr)))); the estimate and the chosen M0 are in ``stats["estimate"]`` / ``stats["M0_auto"]``.
     """
+    if isinstance(M0, str):
+        if M0 != "auto":
+            raise ValueError("M0 must be an integer or 'auto'")
+        return _feast_auto(feast, A, B, interval, fpm=fpm, backend=backend, solver=solver, solver_tol=solver_tol,
+                           solver_maxiter=solver_maxiter, solver_restart=solver_restart, warm_start=warm_start,
+                           inner_rtol=inner_rtol, real_projection=real_projection, inner_precision=inner_precision,
+                           group=group, engine=engine, device=device, Q0=Q0, contour=contour, contour_policy=contour_policy,
+                           keep_factors=keep_factors, seed=seed)
     if interval is None and B is not None and isinstance(B, tuple):
         B, interval = None, B              # feast(A, (Emin, Emax)) form
     if backend not in _BACKENDS:
@@ -215,6 +288,15 @@ def feast(A, B=None, interval=None, *, M0=10, fpm=None, backend="hip", solver="d
     M0 = min(int(M0), N)
     real_input = not (np.iscomplexobj(A.data if sp.issparse(A) else A) or
                       (B is not None and np.iscomplexobj(B.data if sp.issparse(B) else B)))
+    if int(fpm[14]) == 2:
+        if M0 <= 0:
+            return FeastResult(np.zeros(0), np.zeros((N, 0)), 0, np.zeros(0), 2, 0.0, 0, {"estimate": None})
+        if not Emin < Emax:
+            return FeastResult(np.zeros(0), np.zeros((N, 0)), 0, np.zeros(0), 3, 0.0, 0, {"estimate": None})
+        Zne, Wne = feast_contour(Emin, Emax, fpm) if contour is None else contour
+        info, est = _run_estimate(eng, A, B, Zne, Wne, False, M0, seed, solver, solver_tol, solver_maxiter, solver_restart,
+                                  group)
+        return _estimate_result(N, info, est, real_input)
     substituted = None
     if sp.issparse(A) and solver in ("direct", "lu"):
         # the reference's sparse default is UMFPACK; the :hip backend has a direct path for band
@@ -326,9 +408,17 @@ def feast(A, B=None, interval=None, *, M0=10, fpm=None, backend="hip", solver="d
 
 def feast_general(A, B=None, center=0.0, radius=1.0, *, M0=10, fpm=None, backend="hip", solver="direct",
                   solver_tol=0.0, solver_maxiter=500, solver_restart=30, group=None, engine=None, device=0, Q0=None,
-                  inner_precision=64, contour=None, keep_factors=False):
+                  inner_precision=64, contour=None, keep_factors=False, seed=None):
     """feast_general(A, [B,] center, radius; M0, fpm): src/interfaces/feast_interfaces.jl:274-379.
-    ``keep_factors``: as in feast()."""
+    ``keep_factors``: as in feast().  ``fpm[14] = 2`` and ``M0="auto"``: as in feast(), on the full contour of the
+    circle (the samples are complex; M = round(Re mean))."""
+    if isinstance(M0, str):
+        if M0 != "auto":
+            raise ValueError("M0 must be an integer or 'auto'")
+        return _feast_auto(feast_general, A, B, center, radius, fpm=fpm, backend=backend, solver=solver, solver_tol=solver_tol,
+                           solver_maxiter=solver_maxiter, solver_restart=solver_restart, group=group, engine=engine,
+                           device=device, Q0=Q0, inner_precision=inner_precision, contour=contour, keep_factors=keep_factors,
+                           seed=seed)
     if backend not in _BACKENDS:
         raise ValueError(f"Unknown backend '{backend}' (this package provides: hip)")
     if A.shape[0] != A.shape[1]:
@@ -341,6 +431,14 @@ def feast_general(A, B=None, center=0.0, radius=1.0, *, M0=10, fpm=None, backend
     fpm = feastinit() if fpm is None else fpm
     feastdefault(fpm)
     M0 = min(int(M0), A.shape[0])
+    if int(fpm[14]) == 2:
+        N = A.shape[0]
+        if M0 <= 0:
+            return FeastResult(np.zeros(0, complex), np.zeros((N, 0), complex), 0, np.zeros(0), 2, 0.0, 0, {"estimate": None})
+        Zne, Wne = feast_gcontour(complex(center), float(radius), fpm) if contour is None else contour
+        info, est = _run_estimate(_engine(engine, device), A, B, Zne, Wne, True, M0, seed, solver, solver_tol,
+                                  solver_maxiter, solver_restart, group)
+        return _estimate_result(N, info, est, False)
     substituted = None
     if sp.issparse(A) and solver in ("direct", "lu"):
         # the reference factors z B - A with UMFPACK (src/sparse/feast_sparse.jl:943); here: banded LU for narrow
@@ -377,4 +475,25 @@ def feast_general(A, B=None, center=0.0, radius=1.0, *, M0=10, fpm=None, backend
     _release_band_factors(eng, keep_factors)
     if single:
         res = _demote(res, cplx_lambda=True)
+    return res
+
+
+def _feast_auto(driver, A, B, *where, fpm=None, engine=None, device=0, solver="direct", solver_tol=0.0,
+                solver_maxiter=None, solver_restart=30, group=None, seed=None, **kw):
+    """M0 = "auto" of feast / feast_general: a 64-sample estimate on the estimate's own contour (_estimate_fpm), then the
+    solve with M0 = auto_M0(estimate) and the caller's parameters.  A failed estimate returns its info and no solve."""
+    eng = _engine(engine, device)
+    common = dict(engine=eng, solver=solver, solver_tol=solver_tol, solver_restart=solver_restart, group=group,
+                  backend=kw.pop("backend", "hip"))
+    if solver_maxiter is not None:
+        common["solver_maxiter"] = solver_maxiter
+    er = driver(A, B, *where, M0=AUTO_SAMPLES, fpm=_estimate_fpm(fpm), seed=seed, **common)
+    est = er.stats.get("estimate")
+    if est is None:
+        return er
+    M0 = auto_M0(est, A.shape[0])
+    res = driver(A, B, *where, M0=M0, fpm=fpm, **common, **kw)
+    if isinstance(res.stats, dict):
+        res.stats["estimate"] = est
+        res.stats["M0_auto"] = M0
     return res

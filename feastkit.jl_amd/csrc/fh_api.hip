@@ -1750,6 +1750,58 @@ extern "C" int feasthip_contour_apply(feasthip_handle h, int64_t m, const void* 
 }
 
 // ---------------------------------------------------------------------------------------
+// stochastic eigenvalue-count estimate (fpm[14] = 2): kernels in fh_estimate.hip
+// ---------------------------------------------------------------------------------------
+static int fh_check_estimate(feasthip_ctx* h, int64_t m) {
+    int rc = fh_check_problem(h, m, 1);
+    if (rc) return rc;
+    if (m > 65535) { h->last_error = "estimate: at most 65535 columns"; return FEASTHIP_ERROR_M0; }
+    return 0;
+}
+
+extern "C" int feasthip_random_block_dev(feasthip_handle h, int64_t m, uint64_t seed, void* dX) {
+    int rc = fh_check_estimate(h, m);
+    if (rc) return rc;
+    if (!dX) { h->last_error = "random_block: null X"; return FEASTHIP_ERROR_INTERNAL; }
+    FH_CHECK(hipSetDevice(h->device));
+    const int64_t N = fh_N(h);
+    fh_launch_rademacher(seed, 0, N, m, (cplx*)dX, N, h->stream);
+    FH_CHECK(hipGetLastError());
+    FH_CHECK(hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+extern "C" int feasthip_estimate_count(feasthip_handle h, int64_t m, uint64_t seed, double* samples, int* node_status,
+                                       feasthip_stats* stats) {
+    int rc = fh_check_estimate(h, m);
+    if (rc) return rc;
+    if (!samples) { h->last_error = "estimate_count: null samples"; return FEASTHIP_ERROR_INTERNAL; }
+    const double t0 = fh_now_s();
+    FH_CHECK(hipSetDevice(h->device));
+    const int64_t N = fh_N(h);
+    const size_t nb = (size_t)N * m * sizeof(cplx);
+    void *dV, *dP, *dW, *dT;
+    if ((rc = fh_get_buf(h, "est_V", nb, &dV))) return rc;
+    if ((rc = fh_get_buf(h, "est_P", nb, &dP))) return rc;
+    if ((rc = fh_get_buf(h, "est_work", fh_trace_work_elems(N, m) * sizeof(cplx), &dW))) return rc;
+    if ((rc = fh_get_buf(h, "est_t", (size_t)m * 2 * sizeof(double), &dT))) return rc;
+    fh_launch_rademacher(seed, 0, N, m, (cplx*)dV, N, h->stream);
+    FH_CHECK(hipGetLastError());
+    // the sweep of feasthip_contour_apply_dev from a zero start: Q_proj = rho V, summed over the ranks of a communicator
+    h->mask_live = 1;
+    rc = fh_contour_apply_impl(h, m, (const cplx*)dV, nullptr, (cplx*)dP, nullptr, nullptr, node_status, stats);
+    h->mask_live = 0;
+    h->col_mask.clear();
+    if (rc) return rc;
+    fh_launch_trace_dots((const cplx*)dP, N, m, N, seed, h->real_projection, (cplx*)dW, (double*)dT, h->stream);
+    FH_CHECK(hipGetLastError());
+    FH_CHECK(hipMemcpyAsync(samples, dT, (size_t)m * 2 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    FH_CHECK(hipStreamSynchronize(h->stream));
+    if (stats) stats->seconds_total = fh_now_s() - t0;
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------
 // small host-side complex Hermitian helpers (m <= 64) for the Cholesky-QR fast path
 // ---------------------------------------------------------------------------------------
 // pivoted Cholesky pivots of a Hermitian PSD matrix (column-major, leading dim ld): returns

@@ -169,6 +169,13 @@ void fh_launch_small_matmul(const cplx* Q, const cplx* V, int N, int ld, cplx* X
 // dst[:,k] = src[:,perm[k]] for k < count else 0
 void fh_launch_gather_cols(const cplx* src, const int* perm, int count, int N, int ld, cplx* dst, hipStream_t st);
 
+// stochastic eigenvalue-count estimate (fh_estimate.hip): Rademacher block X[r, j] = v(row0 + r, j) (column-major, N x m,
+// m <= 65535), and t[2j], t[2j+1] = re, im of sum_i v(i, j) P[i, j] over the column-major N x m block P; work: fh_trace_work_elems
+void fh_launch_rademacher(uint64_t seed, int64_t row0, int64_t nrows, int64_t m, cplx* X, int64_t ldx, hipStream_t st);
+size_t fh_trace_work_elems(int64_t N, int64_t m);
+void fh_launch_trace_dots(const cplx* P, int64_t N, int64_t m, int64_t ldp, uint64_t seed, int real_only, cplx* work, double* t,
+                          hipStream_t st);
+
 // column-pivoted modified Gram-Schmidt with re-orthogonalisation, fully on device.
 // state: int[4 + ld] = {k (steps done), rank, done, pivot, perm[ld]}; dstate: double[2+ld] = {R11, thr, norm2[ld]}
 struct fh_mgs_args {

@@ -314,6 +314,31 @@ class HipEngine:
             return dP, status, self.last_stats, dA.cpu().numpy().T.copy(), dS.cpu().numpy().T.copy()
         return dP, status, self.last_stats
 
+    # -- stochastic eigenvalue-count estimate (fpm[14] = 2) -------------------------------------------------------------
+    def random_block(self, m, seed):
+        """The N x m Rademacher block (+-1, column-major device block: an (m, N) tensor) that estimate_count sweeps for
+        ``seed`` (feasthip_random_block_dev)."""
+        self._sync_stream()
+        out = self.empty(int(m))
+        self._chk(self.lib.feasthip_random_block_dev(self.h, int(m), C.c_uint64(int(seed) & (2 ** 64 - 1)),
+                                                     C.c_void_p(out.data_ptr())))
+        return out
+
+    def estimate_count(self, m, seed):
+        """One contour sweep over m Rademacher columns and their Hutchinson samples t_j = v_j^T Q_proj[:, j]
+        (feasthip_estimate_count) with the problem, contour, projection, solver and nodes set on the engine.
+        Returns (samples: m complex values, status, stats); ``status`` as in contour_apply."""
+        self._sync_stream()
+        m = int(m)
+        samples = np.zeros(2 * m, dtype=np.float64)
+        status = np.zeros(max(1, self.ne), dtype=np.int32)
+        stats = FeastHipStats()
+        self._chk(self.lib.feasthip_estimate_count(self.h, m, C.c_uint64(int(seed) & (2 ** 64 - 1)),
+                                                   samples.ctypes.data_as(C.POINTER(C.c_double)), _np_ptr(status),
+                                                   C.byref(stats)))
+        self.last_stats = stats.asdict()
+        return samples[0::2] + 1j * samples[1::2], status, self.last_stats
+
     # -- the refinement loop with resident panels (feasthip_*_resident: nothing crosses the ABI between the calls of a loop) --
     resident = True
 

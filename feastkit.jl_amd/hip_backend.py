@@ -564,6 +564,49 @@ def feast_hip_hermitian(engine, A, B, Emin, Emax, M0, fpm, *, freeze_guards_afte
     return FeastResult(lam_vec[:M_found].copy(), q, M_found, res_vec[:M_found].copy(), info, epsout, loop_count, stats)
 
 
+ESTIMATE_SEED = 20260515          # default seed of the estimate's Rademacher block (the package seed)
+
+
+def feast_hip_estimate(engine, A, B, Zne, Wne, weight_scale, m, *, general=False, seed=ESTIMATE_SEED, solver="direct",
+                       solver_tol=1e-8, solver_maxiter=2000, solver_restart=30, group=None):
+    """Stochastic estimate of the eigenvalue count inside the contour (Zne, Wne): fpm[14] = 2, which the reference
+    validates (src/core/feast_parameters.jl:69-75) but never computes.  One sweep over m Rademacher columns V generated on
+    the device, then Hutchinson's samples t_j = v_j^T Q_proj[:, j] (engine.estimate_count).
+
+    Hermitian (general=False): half contour with the real projection, Q_proj = Re(sum_e 2 w_e (z_e B - A)^{-1} B) V, so
+      t_j samples sum_i f(lambda_i) with f(x) = Re sum_e 2 w_e / (z_e - x) -- also for complex Hermitian input, since
+      v_j is real and the full contour's trace is the real part of the half contour's.
+    General (general=True): full contour, weight_scale 1, no projection: the t_j are complex and Re mean(t) estimates
+      the count inside the circle.
+    The estimate is of a sum of filter values, not of an integer: eigenvalues near the ends of the interval (or just
+    outside) contribute fractions.  Krylov solves start from zero and stop at ||r|| <= solver_tol ||b||.
+
+    Returns (info, estimate): info 0 with the dict {mean, stderr, samples, nodes, solver, seed, seconds}, or the node
+    status 5 / 8 of a failed node and None."""
+    rank, world = _world(engine, group)
+    t0 = time.perf_counter()
+    engine.set_problem(A, B)
+    engine.set_contour(Zne, Wne, float(weight_scale))
+    engine.set_real_projection(not general)
+    first, count = distribute_contour_points(len(Zne), world)[rank]
+    engine.set_node_range(first, count)
+    iterative = solver not in ("direct", "lu", "banded")
+    engine.set_solver(solver, rtol=float(solver_tol), atol=0.0, maxit=int(solver_maxiter), restart=int(solver_restart),
+                      cache_factors=True)
+    samples, status, _st = engine.estimate_count(m, seed)
+    fail = int(np.max(status)) if (world > 1 or count > 0) else 0
+    if fail:
+        return (int(FeastError.Feast_ERROR_LAPACK) if fail == 8 else int(FeastError.Feast_ERROR_NO_CONVERGENCE)), None
+    t = samples if general else samples.real
+    mean = complex(np.mean(t)) if general else float(np.mean(t))
+    stderr = float(np.std(t, ddof=1) / math.sqrt(m)) if m > 1 else math.inf
+    est = {"mean": mean, "stderr": stderr, "samples": t.copy(), "nodes": len(Zne), "solver": solver, "seed": int(seed),
+           "seconds": time.perf_counter() - t0}
+    if iterative:
+        est["solver_tol"] = float(solver_tol)
+    return 0, est
+
+
 def feast_hip_general(engine, A, B, Emid, r, M0, fpm, *, solver="direct", solver_tol=0.0, solver_maxiter=500,
                       solver_restart=30, group=None, Q0=None, seed=20260515, inner_precision=64, contour=None, eps_floor=0.0):
     """Variant C (general, full contour, no factor 2, no orthonormalisation, residual

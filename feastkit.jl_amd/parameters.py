@@ -22,6 +22,7 @@ _DEFAULTS = {1: 0, 2: 8, 3: 12, 4: 20, 5: 0, 6: 1, 7: 5, 8: 16, 9: 0, 10: 1, 11:
              14: 0, 15: 0, 16: 0, 17: 0, 18: 100, 19: 0, 29: 0, 31: 40, 32: 10, 36: 1, 37: 0,
              38: 1, 39: 0, 40: 0, 41: 1, 42: 1, 43: 0, 44: 0, 45: 1, 46: 40, 47: 0, 48: 0,
              49: 0, 59: 0, 60: 0, 64: 0}
+_ESTIMATE_NODES = {2: 3, 8: 6}     # fpm[14] = 2 (stochastic estimate): node counts when unset
 _ZERO_RANGES = (range(20, 29), range(33, 36), range(50, 59), range(61, 64))   # internal / reserved slots: 0 when unset
 _NONPOSITIVE_RESETS = (2, 4, 8)     # "== -111 || <= 0" in the reference (feast_parameters.jl:103, 130, 161)
 
@@ -29,12 +30,18 @@ _NONPOSITIVE_RESETS = (2, 4, 8)     # "== -111 || <= 0" in the reference (feast_
 def feastdefault(fpm):
     """src/core/feast_parameters.jl:41-386 (feastdefault!): every slot still at -111 gets its default, fpm[2], fpm[4]
     and fpm[8] are also reset when <= 0, fpm[30] is left alone, and out-of-range values raise (ArgumentError there,
-    ValueError here) with the reference's messages."""
+    ValueError here) with the reference's messages.  fpm[14] = 2 (stochastic estimate) gives the unset fpm[2] / fpm[8]
+    the estimate's node counts 3 / 6 and sets fpm[15] = 1, as the reference does."""
     if len(fpm) < 65:
         raise ValueError("fpm array must have at least 64 elements (1-based, slot 0 unused)")
 
     def bad(i, what):
         raise ValueError(f"Invalid fpm[{i}]={int(fpm[i])}: {what}")
+    if fpm[14] == 2:
+        # stochastic estimate: fewer nodes by default (feast_parameters.jl:108-110, 166-168)
+        for i, d in _ESTIMATE_NODES.items():
+            if fpm[i] == FEAST_UNINITIALIZED or fpm[i] <= 0:
+                fpm[i] = d
     for i, d in _DEFAULTS.items():
         if fpm[i] == FEAST_UNINITIALIZED or (i in _NONPOSITIVE_RESETS and fpm[i] <= 0):
             fpm[i] = d
@@ -68,6 +75,8 @@ def feastdefault(fpm):
         bad(13, "must be 0, 1, 2, or 3")
     if fpm[15] < 0 or fpm[15] > 2:
         bad(15, "must be 0, 1, or 2")
+    if fpm[14] == 2:
+        fpm[15] = 1                     # right contour only for the estimate (feast_parameters.jl:223-225)
     if fpm[18] < 0:
         bad(18, "aspect ratio must be non-negative")
     if fpm[19] < -180 or fpm[19] > 180:

@@ -274,6 +274,27 @@ int  feasthip_contour_apply_dev(feasthip_handle h, int64_t m, const void* dQ,
                                 const double* ritz_lambda_host, void* dQproj,
                                 void* dzAq, void* dzSq, int* node_status, feasthip_stats* stats);
 
+/* ---- stochastic estimate of the eigenvalue count (fpm[14] = 2) ------------------------------------------------------
+ * The reference validates fpm[14] in {0,1,2} (src/core/feast_parameters.jl:69-75) and sets the estimate's defaults
+ * fpm[2] = 3 (:108-110), fpm[8] = 6 (:166-168), fpm[15] = 1 (:223-225), but no kernel of it reads the parameter.
+ * feasthip_estimate_count: ONE contour sweep (the sweep of feasthip_contour_apply_dev, zero initial guess) over m
+ *   Rademacher columns V (entries +-1, generated on the device), then t_j = v_j^T Q_proj[:, j] for every column in one
+ *   pass over Q_proj.  Q_proj = rho V with rho = sum_e weight_scale w_e (z_e B - A)^{-1} B (its real part under the real
+ *   projection), so every t_j is an unbiased sample of tr rho = sum_i f(lambda_i), f the rational filter of the contour
+ *   in force: mean(t) estimates the number of eigenvalues inside the contour (a sum of filter values, not an integer),
+ *   std(t)/sqrt(m) its standard error.  Uses the problem, contour, real-projection flag, solver and node range set on the
+ *   handle; with a communicator attached Q_proj is summed by the sweep's all-reduce before the dots, so every rank
+ *   returns the same samples.  samples: 2*m doubles (re, im of t_j; im = 0 under the real projection).  node_status as
+ *   in feasthip_contour_apply_dev (the samples are written whatever the statuses: the caller discards them when a node
+ *   reports 5 or 8).  m > 64 runs in 64-column panels; 1 <= m <= min(N, 65535).
+ * feasthip_random_block_dev: the N x m block V of feasthip_estimate_count for the same seed (c128, column-major, device).
+ *   v_ij is a pure function of (seed, row i, column j) -- the splitmix64 finaliser mix64 applied twice:
+ *   b = mix64(mix64(seed + 0x9E3779B97F4A7C15 (i + 1)) ^ 0xD1B54A32D192ED03 (j + 1)) mod 2^64, v_ij = 1 - 2 (b >> 63) --
+ *   independent of the node range, the rank, the row renumbering of a sparse matrix and the launch geometry.         */
+int  feasthip_estimate_count(feasthip_handle h, int64_t m, uint64_t seed, double* samples /* 2*m: t_j re,im */,
+                             int* node_status, feasthip_stats* stats);
+int  feasthip_random_block_dev(feasthip_handle h, int64_t m, uint64_t seed, void* dX /* N x m c128 col-major */);
+
 /* ---- the refinement loop with resident panels ---------------------------------------------------------------------
  * One loop of variant A -- contour sweep, _feast_qr_compress!, the reduced pencil, Ritz vectors, residuals
  * (src/dense/feast_dense.jl:171-337, src/sparse/feast_sparse.jl:318-478) -- as three calls whose N x m blocks never
