@@ -20,6 +20,7 @@ static inline cplx fh_ing_zero(cplx) { return cmake(0, 0); }
 static inline cplx fh_ing_add(cplx a, cplx b) { return cadd(a, b); }
 #define FH_INGEST_STORAGE_CSR 0
 #include "fh_ingest.hpp"       // fh_rcm, fh_bandwidth
+#include "fh_mf.hpp"           // fh_mf::max_boundary_multiplier
 #include "../../include/feasthip.h"
 
 #define FH_BLOCK 256
@@ -192,6 +193,33 @@ void fh_banded_free(feasthip_ctx* h) {
     fh_mf_free(h);
 }
 
+// Reverse Cuthill-McKee order of the stored pattern if it shortens the elimination (N kl (kl + ku)), else the stored order
+static void band_rcm_order(feasthip_ctx* h, int kl0, int ku0, std::vector<int>& perm, std::vector<int>& iperm, int& kl1, int& ku1) {
+    const int64_t N = h->csr.N;
+    iperm.assign(N, 0);
+    fh_rcm(N, h->host_rowptr, h->host_col, perm);
+    for (int64_t i = 0; i < N; ++i) iperm[perm[i]] = (int)i;
+    fh_bandwidth(N, h->host_rowptr, h->host_col, iperm.data(), kl1, ku1);
+    if ((double)kl1 * (kl1 + ku1) >= (double)kl0 * (kl0 + ku0)) {
+        for (int64_t i = 0; i < N; ++i) { perm[i] = (int)i; iperm[i] = (int)i; }
+        kl1 = kl0; ku1 = ku0;
+    }
+}
+
+// The blocked band plan (band_plan 2) in the order perm / iperm
+static int band_take_band_plan(feasthip_ctx* h, const std::vector<int>& perm, const std::vector<int>& iperm, int kl0, int ku0, int kl1, int ku1) {
+    const int64_t N = h->csr.N;
+    FH_CHECK(hipMalloc((void**)&h->band_perm, N * sizeof(int)));
+    FH_CHECK(hipMalloc((void**)&h->band_iperm, N * sizeof(int)));
+    FH_CHECK(hipMemcpy(h->band_perm, perm.data(), N * sizeof(int), hipMemcpyHostToDevice));
+    FH_CHECK(hipMemcpy(h->band_iperm, iperm.data(), N * sizeof(int), hipMemcpyHostToDevice));
+    h->band_plan = 2; h->band_kl = kl1; h->band_ku = ku1;
+    if (getenv("FH_DEBUG_TIMING"))
+        fprintf(stderr, "[feasthip] band plan: stored order kl %d ku %d, band order kl %d ku %d, %.2f GB per node\n", kl0, ku0, kl1, ku1,
+                (double)fh_wband_elems((int)N, kl1, ku1) * sizeof(cplx) / 1e9);
+    return 0;
+}
+
 static int band_make_plan(feasthip_ctx* h) {
     if (h->band_plan) return 0;
     if (h->kind != 2) { h->last_error = "banded LU needs a CSR matrix (feasthip_set_csr)"; return FEASTHIP_ERROR_FPM; }
@@ -205,16 +233,9 @@ static int band_make_plan(feasthip_ctx* h) {
         h->band_plan = 1; h->band_kl = kl0; h->band_ku = ku0;
         return 0;
     }
-    std::vector<int> perm, iperm(N);
-    fh_rcm(N, h->host_rowptr, h->host_col, perm);
-    for (int64_t i = 0; i < N; ++i) iperm[perm[i]] = (int)i;
+    std::vector<int> perm, iperm;
     int kl1 = 0, ku1 = 0;
-    fh_bandwidth(N, h->host_rowptr, h->host_col, iperm.data(), kl1, ku1);
-    // the elimination costs N kl (kl + ku): compare that, not the plain width
-    if ((double)kl1 * (kl1 + ku1) >= (double)kl0 * (kl0 + ku0)) {
-        for (int64_t i = 0; i < N; ++i) { perm[i] = (int)i; iperm[i] = (int)i; }
-        kl1 = kl0; ku1 = ku0;
-    }
+    band_rcm_order(h, kl0, ku0, perm, iperm, kl1, ku1);
     // Multifrontal plan (fh_mf.hpp, numeric phase in fh_dense.hip): fill confined to the fronts of a nested-dissection tree
     // instead of the band.  Taken when its (padded) work is under half the band elimination's -- the band LU streams one
     // long trailing update per block column, the fronts are many smaller batches.
@@ -239,15 +260,7 @@ static int band_make_plan(feasthip_ctx* h) {
             }
         }
     }
-    FH_CHECK(hipMalloc((void**)&h->band_perm, N * sizeof(int)));
-    FH_CHECK(hipMalloc((void**)&h->band_iperm, N * sizeof(int)));
-    FH_CHECK(hipMemcpy(h->band_perm, perm.data(), N * sizeof(int), hipMemcpyHostToDevice));
-    FH_CHECK(hipMemcpy(h->band_iperm, iperm.data(), N * sizeof(int), hipMemcpyHostToDevice));
-    h->band_plan = 2; h->band_kl = kl1; h->band_ku = ku1;
-    if (getenv("FH_DEBUG_TIMING"))
-        fprintf(stderr, "[feasthip] band plan: stored order kl %d ku %d, band order kl %d ku %d, %.2f GB per node\n", kl0, ku0, kl1, ku1,
-                (double)fh_wband_elems((int)N, kl1, ku1) * sizeof(cplx) / 1e9);
-    return 0;
+    return band_take_band_plan(h, perm, iperm, kl0, ku0, kl1, ku1);
 }
 
 static size_t band_slot_bytes(feasthip_ctx* h) {
@@ -342,6 +355,26 @@ static int mf_nodes_per_call(feasthip_ctx* h) {
     return per;
 }
 
+// The multifrontal plan rejected a factorisation (fh_mf.hpp: a zero pivot, or a boundary multiplier beyond
+// fh_mf::max_boundary_multiplier): this matrix goes to the blocked band plan for good -- reverse Cuthill-McKee, partial
+// pivoting over the whole band.  Every factor slot is re-made (their size changes; band_valid = 0: a cached node is factored
+// again when it is next used), as many as there were.  A band whose factors do not fit fails here with the reason in last_error.
+static int band_fall_back(feasthip_ctx* h) {
+    const int nslots = (int)h->band_factors.size();
+    fh_banded_free(h);
+    fh_mf_free_buffers(h);         // the dead plan's work arena would otherwise count against the band factors' memory check
+    const int64_t N = h->csr.N;
+    int kl0 = 0, ku0 = 0, kl1 = 0, ku1 = 0;
+    fh_bandwidth(N, h->host_rowptr, h->host_col, nullptr, kl0, ku0);
+    std::vector<int> perm, iperm;
+    band_rcm_order(h, kl0, ku0, perm, iperm, kl1, ku1);
+    int rc = band_take_band_plan(h, perm, iperm, kl0, ku0, kl1, ku1);
+    if (!rc) rc = band_check(h);
+    if (!rc) rc = band_ensure_slots(h, nslots);
+    if (rc) h->last_error = "multifrontal LU rejected a pivot; its band LU fallback: " + h->last_error;
+    return rc;
+}
+
 static int band_factor_batch(feasthip_ctx* h, const std::vector<int>& which, const std::vector<cplx>& zlist, std::vector<int>& info_out) {
     const int nf = (int)which.size();
     info_out.assign(nf, 0);
@@ -359,16 +392,27 @@ static int band_factor_batch(feasthip_ctx* h, const std::vector<int>& which, con
         FH_CHECK(hipMemcpyAsync(dz, zlist.data(), nf * sizeof(cplx), hipMemcpyHostToDevice, h->stream));
         // (fronts of a group) x (nodes of a call) is a grid dimension: node batches for long contours
         const int per_call = mf_nodes_per_call(h);
+        const double bound = getenv("FH_MF_MAX_MULTIPLIER") ? atof(getenv("FH_MF_MAX_MULTIPLIER")) : fh_mf::max_boundary_multiplier;
+        double worst = 0.0;
+        bool rejected = false;
         for (int q0 = 0; q0 < nf; q0 += per_call) {
             const int cnt = std::min(per_call, nf - q0);
             std::vector<int> info_part;
-            if ((rc = fh_mf_factor(h, h->band_prec, cnt, stores.data() + q0, pvs.data() + q0, dz + q0, info_part))) return rc;
-            for (int q = 0; q < cnt; ++q) info_out[q0 + q] = info_part[q];
+            std::vector<double> mult_part;
+            if ((rc = fh_mf_factor(h, h->band_prec, cnt, stores.data() + q0, pvs.data() + q0, dz + q0, info_part, mult_part))) return rc;
+            for (int q = 0; q < cnt; ++q) {
+                info_out[q0 + q] = info_part[q];
+                worst = std::max(worst, mult_part[q]);
+                rejected = rejected || info_part[q] != 0 || !(mult_part[q] <= bound);
+            }
         }
         if (getenv("FH_DEBUG_TIMING"))
-            fprintf(stderr, "[feasthip] multifrontal LU: %d factorisations (%d-bit) in %.1f ms\n", nf, h->band_prec,
-                    std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_factor).count());
-        return 0;
+            fprintf(stderr, "[feasthip] multifrontal LU: %d factorisations (%d-bit) in %.1f ms, largest boundary multiplier %.3g%s\n", nf, h->band_prec,
+                    std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_factor).count(), worst,
+                    rejected ? ": rejected, band LU from here" : "");
+        if (!rejected) return 0;
+        if ((rc = band_fall_back(h))) return rc;
+        return band_factor_batch(h, which, zlist, info_out);
     }
     cplx** dabs; int** dpvs; int** dperms;
     if ((rc = band_pointer_arrays(h, which, &dabs, &dpvs, &dperms))) return rc;
@@ -460,7 +504,21 @@ int fh_banded_solve_nodes(feasthip_ctx* h, int ld, int m, int nodes, const std::
         h->band_z[need[q]] = zl[q];
         h->band_valid[need[q]] = info[q] == 0 ? 1 : -1;
     }
-    if (nfact) *nfact = (int64_t)need.size();
+    int64_t done = (int64_t)need.size();
+    // a fallback to the band plan inside the batch re-made every slot: the nodes that were cached are factored again
+    std::vector<int> lost;
+    std::vector<cplx> zlost;
+    for (int e = 0; e < nodes; ++e)
+        if (h->band_valid[e] == 0) { lost.push_back(e); zlost.push_back(z[e]); }
+    if (!lost.empty()) {
+        if ((rc = band_factor_batch(h, lost, zlost, info))) return rc;
+        for (size_t q = 0; q < lost.size(); ++q) {
+            h->band_z[lost[q]] = zlost[q];
+            h->band_valid[lost[q]] = info[q] == 0 ? 1 : -1;
+        }
+        done += (int64_t)lost.size();
+    }
+    if (nfact) *nfact = done;
     std::vector<int> slots(nodes);
     for (int e = 0; e < nodes; ++e) slots[e] = e;
     if ((rc = band_solve_batch(h, ld, m, slots, RHS, rhs_stride, Y, stride))) return rc;

@@ -2284,6 +2284,14 @@ void fh_mf_free(feasthip_ctx* h) {
     h->mf = nullptr;
 }
 
+// the multifrontal solver's transient buffers (work arena, substitution panels: together more than the factors themselves)
+void fh_mf_free_buffers(feasthip_ctx* h) {
+    for (const char* name : {"mf_work", "mf_y", "mf_z", "mf_ptrs", "mf_info", "mf_mult"}) {
+        auto it = h->bufs.find(name);
+        if (it != h->bufs.end()) { (void)hipFree(it->second.first); h->bufs.erase(it); }
+    }
+}
+
 // Builds the plan from the host copy of the stored pattern.  Returns 0 and leaves h->mf set, or an error code (h->mf null).
 int fh_mf_make_plan(feasthip_ctx* h, int leaf) {
     fh_mf_free(h);
@@ -2427,20 +2435,49 @@ __global__ __launch_bounds__(FH_BLOCK) void k_mf_extend_add(const mf_kid* kids, 
     }
 }
 
-// L block column (n x np, contiguous) and U12 (np x nb, leading dimension np) of a factored front -> factor store
+// L block column (n x np, contiguous) and U12 (np x nb, leading dimension np) of a factored front -> factor store.
+// On the way, the largest squared boundary multiplier |l_ik|^2 (rows i >= np of the L block column; non-finite -> +inf) of
+// this workgroup's share goes to part[matrix * MF_MULT_PARTS + blockIdx.x] (k_mf_mult_reduce takes the maximum per matrix):
+// the threshold-pivoting test of the restricted pivots (fh_mf.hpp), without atomics.
+#define MF_MULT_PARTS 64                   // >= gridDim.x of k_mf_store (mf_blocks cap)
 template <typename T>
-__global__ __launch_bounds__(FH_BLOCK) void k_mf_store(T* const* W, T* const* S, int n, int np, int nb, size_t u12_off) {
+__global__ __launch_bounds__(FH_BLOCK) void k_mf_store(T* const* W, T* const* S, int n, int np, int nb, size_t u12_off, float* part) {
     const T* A = W[blockIdx.y];
     T* D = S[blockIdx.y];
     const size_t nl = (size_t)n * np, nu = (size_t)np * nb;
+    float g = 0.0f;
     for (size_t e = (size_t)blockIdx.x * FH_BLOCK + threadIdx.x; e < nl + nu; e += (size_t)gridDim.x * FH_BLOCK) {
-        if (e < nl) D[e] = A[e];
-        else {
+        if (e < nl) {
+            const T v = A[e];
+            D[e] = v;
+            if ((int)e % n >= np) {        // (n x np < 2^31: the panel kernels' front limit)
+                const float a = (float)((double)v.x * v.x + (double)v.y * v.y);
+                g = fmaxf(g, a == a ? a : INFINITY);
+            }
+        } else {
             const size_t u = e - nl;
             const int i = (int)(u % np), j = (int)(u / np);
             D[u12_off + u] = A[(size_t)i + (size_t)(np + j) * n];
         }
     }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) g = fmaxf(g, __shfl_xor(g, off));
+    __shared__ float wmax[FH_BLOCK / 64];
+    if ((threadIdx.x & 63) == 0) wmax[threadIdx.x >> 6] = g;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < FH_BLOCK / 64; ++w) g = fmaxf(g, wmax[w]);
+        part[(size_t)blockIdx.y * MF_MULT_PARTS + blockIdx.x] = g;
+    }
+}
+
+// out[m] = max over the MF_MULT_PARTS partial maxima of matrix m (zeroed before the factorisation: unused parts are 0)
+__global__ __launch_bounds__(FH_BLOCK) void k_mf_mult_reduce(const float* __restrict__ part, float* __restrict__ out, int tot) {
+    const int m = blockIdx.x * FH_BLOCK + threadIdx.x;
+    if (m >= tot) return;
+    float g = 0.0f;
+    for (int k = 0; k < MF_MULT_PARTS; ++k) g = fmaxf(g, part[(size_t)m * MF_MULT_PARTS + k]);
+    out[m] = g;
 }
 
 // ---- substitution: front vectors are row-major n x LD panels; group g's panels start at row rhs_off * nf, matrix m = node * F + slot
@@ -2556,9 +2593,11 @@ static inline unsigned mf_blocks(size_t work, size_t per_block, unsigned cap) {
     return (unsigned)std::max<size_t>(1, std::min<size_t>(cap, (work + per_block - 1) / per_block));
 }
 
-// Factor nf shifted matrices z_q B - A into stores[q] / pivs[q].  info_out[q] != 0: a zero or non-finite pivot in some front.
+// Factor nf shifted matrices z_q B - A into stores[q] / pivs[q].  info_out[q] != 0: a zero or non-finite pivot in some front;
+// mult_out[q]: the largest boundary multiplier |l_ik| over all fronts (the caller's threshold-pivoting test, fh_mf.hpp).
 template <typename T>
-static int mf_factor_t(feasthip_ctx* h, int nf, void* const* stores, int* const* pivs, const cplx* dz, std::vector<int>& info_out) {
+static int mf_factor_t(feasthip_ctx* h, int nf, void* const* stores, int* const* pivs, const cplx* dz, std::vector<int>& info_out,
+                       std::vector<double>& mult_out) {
     fh_mf_state* S = (fh_mf_state*)h->mf;
     if (!S) { h->last_error = "multifrontal LU: no plan"; return FEASTHIP_ERROR_INTERNAL; }
     const fh_mf::plan& P = S->P;
@@ -2580,6 +2619,10 @@ static int mf_factor_t(feasthip_ctx* h, int nf, void* const* stores, int* const*
     if ((rc = fh_get_buf(h, "mf_info", tot * sizeof(int), &p))) return rc;
     int* dinfo = (int*)p;
     FH_CHECK(hipMemsetAsync(dinfo, 0, tot * sizeof(int), h->stream));
+    if ((rc = fh_get_buf(h, "mf_mult", tot * (MF_MULT_PARTS + 1) * sizeof(float), &p))) return rc;
+    float* dpart = (float*)p;
+    float* dmult = dpart + tot * MF_MULT_PARTS;
+    FH_CHECK(hipMemsetAsync(dpart, 0, tot * MF_MULT_PARTS * sizeof(float), h->stream));
     static const bool m3_off = getenv("FH_LU_3M") && atoi(getenv("FH_LU_3M")) == 0;
     const bool bid = h->csr.b_identity != 0, cz = h->csr.is_complex != 0;
     auto factor_group = [&](int g) -> int {
@@ -2677,7 +2720,8 @@ static int mf_factor_t(feasthip_ctx* h, int nf, void* const* stores, int* const*
         // ---- store: L block column + U12, inverted diagonal blocks, row permutation of the pivot block
         fh_prof_begin(h, "mf_store");
         const size_t i32 = fh_mf::inv32_elems(np), u12 = (size_t)n * np + i32 + (G.inv128 ? fh_mf::inv128_elems(np) : 0);
-        hipLaunchKernelGGL((k_mf_store<T>), dim3(mf_blocks((size_t)n * np + (size_t)np * nb, 8 * FH_BLOCK, 64), nmat), dim3(FH_BLOCK), 0, h->stream, W, ST, n, np, nb, u12);
+        hipLaunchKernelGGL((k_mf_store<T>), dim3(mf_blocks((size_t)n * np + (size_t)np * nb, 8 * FH_BLOCK, MF_MULT_PARTS), nmat), dim3(FH_BLOCK), 0, h->stream, W, ST, n, np, nb, u12,
+                           dpart + ptr.off[g] * MF_MULT_PARTS);
         const lu_geom gs{n, np, (size_t)n * np, (size_t)n * np + i32};
         hipLaunchKernelGGL((k_lu_invert_diag<LU_NB, T>), dim3(np / LU_NB, nmat), dim3(64), 0, h->stream, ST, gs);
         if (G.inv128) {
@@ -2690,24 +2734,33 @@ static int mf_factor_t(feasthip_ctx* h, int nf, void* const* stores, int* const*
         return 0;
     };
     if ((rc = mf_for_levels(h, S, true, factor_group))) return rc;
+    hipLaunchKernelGGL(k_mf_mult_reduce, dim3((unsigned)((tot + FH_BLOCK - 1) / FH_BLOCK)), dim3(FH_BLOCK), 0, h->stream, dpart, dmult, (int)tot);
     const double t_launch = since();
     std::vector<int> hinfo(tot);
+    std::vector<float> hmult(tot);
     FH_CHECK(hipMemcpyAsync(hinfo.data(), dinfo, tot * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    FH_CHECK(hipMemcpyAsync(hmult.data(), dmult, tot * sizeof(float), hipMemcpyDeviceToHost, h->stream));
     FH_CHECK(hipStreamSynchronize(h->stream));
     if (dbg) fprintf(stderr, "[feasthip] multifrontal LU: work arena %.1f ms, pointer arrays %.1f ms, launches %.1f ms, drained at %.1f ms\n", t_work, t_ptrs - t_work,
                      t_launch - t_ptrs, since());
     info_out.assign(nf, 0);
+    mult_out.assign(nf, 0.0);
     for (int g = 0; g < ng; ++g) {
         const size_t F = P.groups[g].fronts.size();
         for (int q = 0; q < nf; ++q)
-            for (size_t s = 0; s < F; ++s) if (hinfo[ptr.off[g] + (size_t)q * F + s] && !info_out[q]) info_out[q] = P.fronts[P.groups[g].fronts[s]].piv0 + 1;
+            for (size_t s = 0; s < F; ++s) {
+                const size_t m = ptr.off[g] + (size_t)q * F + s;
+                if (hinfo[m] && !info_out[q]) info_out[q] = P.fronts[P.groups[g].fronts[s]].piv0 + 1;
+                mult_out[q] = std::max(mult_out[q], std::sqrt((double)hmult[m]));
+            }
     }
     return 0;
 }
 // prec: 64 = complex128 factors, 32 = complex64 factors (the caller refines in fp64: fh_dense_lu_refined)
-int fh_mf_factor(feasthip_ctx* h, int prec, int nf, void* const* stores, int* const* pivs, const cplx* dz, std::vector<int>& info_out) {
-    if (prec == 32) return mf_factor_t<cplxf>(h, nf, stores, pivs, dz, info_out);
-    return mf_factor_t<cplx>(h, nf, stores, pivs, dz, info_out);
+int fh_mf_factor(feasthip_ctx* h, int prec, int nf, void* const* stores, int* const* pivs, const cplx* dz, std::vector<int>& info_out,
+                 std::vector<double>& mult_out) {
+    if (prec == 32) return mf_factor_t<cplxf>(h, nf, stores, pivs, dz, info_out, mult_out);
+    return mf_factor_t<cplx>(h, nf, stores, pivs, dz, info_out, mult_out);
 }
 
 template <int LD, typename T>

@@ -21,9 +21,14 @@
 //              entry), extend-add maps (boundary row of a child -> row of its parent's padded front), pivot -> unknown.
 //
 // Pivoting is partial pivoting INSIDE the fully-summed block of a front (rows < np); a pivot is never taken from a boundary
-// row (no delayed pivots).  For z off the real axis and a definite B the leading blocks of z B - A are nonsingular (the
-// field of values of z B - A misses zero), which is the FEAST case; the caller checks the factorisation's info flags and the
-// residual of the solve and falls back to the band LU otherwise.
+// row (no delayed pivots).  For a Hermitian pencil with a definite B and z off the real axis the leading blocks of z B - A
+// are nonsingular (the field of values misses zero), but they can be nearly singular -- a zero-diagonal bipartite H has
+// leaf blocks whose last pivot is ~ Im z -- and saddle-point or zero-diagonal pencils give exactly singular ones.  So the
+// numeric phase applies the threshold-pivoting test after the fact: with pivots restricted to the fully-summed rows, the
+// pivot of column k fails |pivot| >= tau max_{i >= np} |a_ik| exactly when some boundary multiplier |l_ik| exceeds 1 / tau.
+// The factor store kernel measures the largest boundary multiplier of every front; a zero pivot (info != 0) or a multiplier
+// beyond max_boundary_multiplier makes the caller (fh_banded.hip) drop this plan for the matrix and refactor with the band
+// LU, partial pivoting over the whole band.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -70,6 +75,13 @@ struct plan {
     double flops_exact = 0.0;                  // unpadded
     int max_n = 0, max_np = 0;
 };
+
+// 1 / tau of the test above (tau = 1e-3).  The residual of a solve through factors with multipliers up to m grows about
+// like m x eps (measured: 2.2e3 -> 1e-11, 2.2e4 -> 1e-10 relative to the right-hand side on a 2-D bipartite H, where the
+// band LU gives 1e-14; 3-D trees compound it further), and a near-singular leaf at z = i eps gives m ~ 2 / eps.  The benign
+// inputs stay below: <= 0.42 on the cfg 3 Laplacian's contours, <= 304 on the random no-dominance grid pencils of the tests
+// (multifrontal section).  FH_MF_MAX_MULTIPLIER overrides it (measurements).
+constexpr double max_boundary_multiplier = 1e3;
 
 static inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
 static inline double plan_store_slack() { const char* e = getenv("FH_MF_STORE_SLACK"); const double v = e ? atof(e) : 0.0; return v >= 1.0 ? v : 1.25; }

@@ -56,10 +56,12 @@ def test_multifrontal_solve_matches_superlu(engine, force_mf, monkeypatch, shape
     check_solve(engine, A, B, 0.3 + 0.8j, m)
     # a second shift through the cached-slot logic, then identity B
     check_solve(engine, A, B, -0.4 + 0.3j, m, seed=9)
+    assert engine.band_plan()[3] == 2          # no pivot rejected: these solves were the multifrontal plan's
     engine.set_problem(A, None)
     engine.set_solver("banded")
     assert engine.band_plan()[3] == 2
     check_solve(engine, A, None, -0.2 + 0.05j, m)
+    assert engine.band_plan()[3] == 2
 
 
 @pytest.mark.parametrize("n,band,density,m,cplx,sym", [
@@ -77,6 +79,7 @@ def test_multifrontal_random_patterns_match_superlu(engine, force_mf, n, band, d
     engine.set_solver("banded")
     assert engine.band_plan()[3] == 2
     check_solve(engine, A, B, 0.3 + 0.8j, m)
+    assert engine.band_plan()[3] == 2
 
 
 def test_multifrontal_contour_apply_cache_and_reproducibility(engine, force_mf, monkeypatch):
@@ -122,6 +125,7 @@ def test_multifrontal_complex64_factors_refined(engine, force_mf):
     assert blocked == 2
     check_solve(engine, A, B, 0.4 + 0.6j, 48, tol=5e-12)
     assert engine.last_stats["max_rel_residual"] <= 1e-12
+    assert engine.band_plan()[3] == 2
     engine.set_solver("banded", rtol=1.0, factor_precision=32)
     n, m = A.shape[0], 48
     rng = np.random.default_rng(5)
@@ -161,6 +165,7 @@ def test_cfg3_takes_the_multifrontal_plan(engine):
     X = r.q[:, :r.M]
     res = np.linalg.norm(A @ X - (B @ X) * r.lambda_[:r.M], axis=0) / np.linalg.norm(X, axis=0)
     assert res.max() < 1e-10
+    assert engine.band_plan()[3] == 2          # no pivot was rejected: the solve stayed on the multifrontal plan
 
 
 def test_multifrontal_fuzz(engine, force_mf):
