@@ -6,6 +6,7 @@
 #include "fh_banded.hpp"
 #include "fh_eig.hpp"
 #include "fh_comm.hpp"
+#include "fh_cholqr.hpp"
 #include "../../include/feasthip.h"
 
 #include <algorithm>
@@ -473,14 +474,14 @@ extern "C" int feasthip_set_solver(feasthip_handle h, int kind, double rtol, dou
 // ---------------------------------------------------------------------------------------
 
 struct fh_op_call {
-    const void* X; size_t x_stride;
-    void* Y; size_t y_stride;
-    const cplx* coefA; const cplx* coefB;   // device [nodes][ld]
-    const void* Bvec; size_t b_stride;
-    const void* U; size_t u_stride;
-    int dot_mode; cplx* partial1; cplx* partial2;
-    const int* node_active;
-    int nodes;
+    const void* X = nullptr; size_t x_stride = 0;
+    void* Y = nullptr; size_t y_stride = 0;
+    const cplx* coefA = nullptr; const cplx* coefB = nullptr;   // device [nodes][ld]
+    const void* Bvec = nullptr; size_t b_stride = 0;
+    const void* U = nullptr; size_t u_stride = 0;
+    int dot_mode = 0; cplx* partial1 = nullptr; cplx* partial2 = nullptr;
+    const int* node_active = nullptr;
+    int nodes = 1;
     int m = FH_MAX_LD;     // active columns (measurement only)
     int uniform_coef = 0;  // coefA/coefB identical across columns
     int prec = 64;         // panel precision of X/Y/Bvec/U
@@ -560,60 +561,58 @@ static int fh_check_problem(feasthip_ctx* h, int64_t m, int wide = 0) {
     return 0;
 }
 
-// upload per-column coefficient arrays [nodes][ld]
-static int fh_upload_coefs(feasthip_ctx* h, const char* name, const std::vector<cplx>& host, cplx** dev) {
-    void* p = nullptr;
-    int rc = fh_get_buf(h, name, host.size() * sizeof(cplx), &p);
-    if (rc) return rc;
-    const size_t bytes = host.size() * sizeof(cplx);
-    if (h->pin && bytes <= h->pin_cap / 4) {
-        // staged through a pinned ring: the copy is queued and the caller's vector may go out of scope at once -- no
-        // synchronisation per upload (a FEAST loop makes about twenty of these).  The ring wraps behind a stream
-        // synchronisation, so a slot is never rewritten under a copy that is still queued.
-        const size_t need = (bytes + 63) & ~(size_t)63;
-        if (h->pin_off + need > h->pin_cap) {
-            FH_CHECK(hipStreamSynchronize(h->stream));
-            h->pin_off = 0;
-        }
-        memcpy(h->pin + h->pin_off, host.data(), bytes);
-        FH_CHECK(hipMemcpyAsync(p, h->pin + h->pin_off, bytes, hipMemcpyHostToDevice, h->stream));
-        h->pin_off += need;
-    } else {
-        FH_CHECK(hipMemcpyAsync(p, host.data(), bytes, hipMemcpyHostToDevice, h->stream));
-        FH_CHECK(hipStreamSynchronize(h->stream));   // host vector may go out of scope
-    }
-    *dev = (cplx*)p;
+// Reserves a 64-byte aligned slot of `bytes` in the pinned ring, or *slot = null when there is no ring or the copy is too large
+// for it.  Copies through the ring are queued without a synchronisation each (a FEAST loop makes about twenty); the ring
+// wraps behind a stream synchronisation, so a slot is never rewritten under a copy that is still queued.
+static int fh_pin_reserve(feasthip_ctx* h, size_t bytes, char** slot) {
+    *slot = nullptr;
+    if (!h->pin || bytes > h->pin_cap / 4) return 0;
+    const size_t need = (bytes + 63) & ~(size_t)63;
+    if (h->pin_off + need > h->pin_cap) { FH_CHECK(hipStreamSynchronize(h->stream)); h->pin_off = 0; }
+    *slot = h->pin + h->pin_off;
+    h->pin_off += need;
     return 0;
 }
 
-// Small host -> device copy through the pinned ring (queued, no synchronisation; falls back to a synchronous copy)
+// Small host -> device copy through the pinned ring (queued: the source may go out of scope at once; falls back to a
+// synchronous copy)
 static int fh_upload_small(feasthip_ctx* h, void* dst, const void* src, size_t bytes) {
-    if (h->pin && bytes <= h->pin_cap / 4) {
-        const size_t need = (bytes + 63) & ~(size_t)63;
-        if (h->pin_off + need > h->pin_cap) { FH_CHECK(hipStreamSynchronize(h->stream)); h->pin_off = 0; }
-        memcpy(h->pin + h->pin_off, src, bytes);
-        FH_CHECK(hipMemcpyAsync(dst, h->pin + h->pin_off, bytes, hipMemcpyHostToDevice, h->stream));
-        h->pin_off += need;
+    char* pin;
+    int rc = fh_pin_reserve(h, bytes, &pin);
+    if (rc) return rc;
+    if (pin) {
+        memcpy(pin, src, bytes);
+        FH_CHECK(hipMemcpyAsync(dst, pin, bytes, hipMemcpyHostToDevice, h->stream));
         return 0;
     }
     FH_CHECK(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, h->stream));
     FH_CHECK(hipStreamSynchronize(h->stream));
     return 0;
 }
+
+// upload per-column coefficient arrays [nodes][ld]
+static int fh_upload_coefs(feasthip_ctx* h, const char* name, const std::vector<cplx>& host, cplx** dev) {
+    void* p = nullptr;
+    const size_t bytes = host.size() * sizeof(cplx);
+    int rc = fh_get_buf(h, name, bytes, &p);
+    if (rc) return rc;
+    if ((rc = fh_upload_small(h, p, host.data(), bytes))) return rc;
+    *dev = (cplx*)p;
+    return 0;
+}
+
 // Small device -> host copy: lands in the pinned ring (one DMA, no pageable staging), *slot points at it; valid after the
 // caller's next stream synchronisation and until the ring wraps
 static int fh_download_small(feasthip_ctx* h, const void* src, size_t bytes, const void** slot, std::vector<char>& fallback) {
-    if (h->pin && bytes <= h->pin_cap / 4) {
-        const size_t need = (bytes + 63) & ~(size_t)63;
-        if (h->pin_off + need > h->pin_cap) { FH_CHECK(hipStreamSynchronize(h->stream)); h->pin_off = 0; }
-        FH_CHECK(hipMemcpyAsync(h->pin + h->pin_off, src, bytes, hipMemcpyDeviceToHost, h->stream));
-        *slot = h->pin + h->pin_off;
-        h->pin_off += need;
-        return 0;
+    char* pin;
+    int rc = fh_pin_reserve(h, bytes, &pin);
+    if (rc) return rc;
+    if (!pin) {
+        fallback.resize(bytes);
+        pin = fallback.data();
     }
-    fallback.resize(bytes);
-    FH_CHECK(hipMemcpyAsync(fallback.data(), src, bytes, hipMemcpyDeviceToHost, h->stream));
-    *slot = fallback.data();
+    FH_CHECK(hipMemcpyAsync(pin, src, bytes, hipMemcpyDeviceToHost, h->stream));
+    *slot = pin;
     return 0;
 }
 
@@ -715,7 +714,7 @@ static int fh_krylov(feasthip_ctx* h, int method, int prec, int ld, int m, int n
 
     fh_op_call oc;
     oc.m = m; oc.uniform_coef = 1; oc.coefA = dca; oc.coefB = dcb; oc.nodes = nodes;
-    oc.partial1 = part1; oc.partial2 = part2; oc.U = nullptr; oc.u_stride = 0;
+    oc.partial1 = part1; oc.partial2 = part2;
     fh_fin_args fa;
     fa.s = s; fa.partial1 = part1; fa.partial2 = part2; fa.m = m; fa.rtol = h->rtol; fa.atol = h->atol;
     fa.atol_scale = nullptr; fa.mode = method; fa.col_mask = nullptr;
@@ -1030,7 +1029,7 @@ static int fh_gmres(feasthip_ctx* h, int ld, int m, int nodes_all, const std::ve
         cplx* Xb = X + (size_t)e0 * stride;
         fh_op_call oc;
         oc.m = m; oc.uniform_coef = 1; oc.coefA = dca; oc.coefB = dcb; oc.nodes = nodes; oc.prec = 64;
-        oc.partial1 = nullptr; oc.partial2 = npart; oc.U = nullptr; oc.u_stride = 0;
+        oc.partial2 = npart;
 
         int total_it = 0, first = 1;
         unsigned tag = 0;
@@ -1162,8 +1161,7 @@ static int fh_dense_lu_refined(feasthip_ctx* h, int ld, int m, int nodes, const 
         fh_op_call oc;
         oc.m = m; oc.uniform_coef = 1; oc.prec = 64;
         oc.X = Y; oc.x_stride = panel; oc.Y = R; oc.y_stride = panel; oc.coefA = dca; oc.coefB = dcb;
-        oc.Bvec = Rhs; oc.b_stride = 0; oc.U = nullptr; oc.u_stride = 0; oc.dot_mode = 0;
-        oc.partial1 = nullptr; oc.partial2 = nullptr; oc.node_active = nullptr; oc.nodes = nodes;
+        oc.Bvec = Rhs; oc.nodes = nodes;
         fh_apply_operator(h, ld, oc);                               // R = RHS - S Y
         for (int e = 0; e < nodes; ++e)
             fh_launch_dot_cols(R + (size_t)e * panel, R + (size_t)e * panel, N, ld, part, ddots + (size_t)e * ld, h->stream);
@@ -1252,9 +1250,7 @@ static int fh_contour_apply_panel(feasthip_ctx* h, int64_t m64, const cplx* dQ, 
         if ((rc = fh_upload_coefs(h, "ca_coefB", cb, &dcb))) return rc;
         fh_op_call oc;
         oc.m = m;
-        oc.X = Qp; oc.x_stride = 0; oc.Y = Rhs; oc.y_stride = 0; oc.coefA = dca; oc.coefB = dcb;
-        oc.Bvec = nullptr; oc.b_stride = 0; oc.U = nullptr; oc.u_stride = 0; oc.dot_mode = 0;
-        oc.partial1 = nullptr; oc.partial2 = nullptr; oc.node_active = nullptr; oc.nodes = 1;
+        oc.X = Qp; oc.Y = Rhs; oc.coefA = dca; oc.coefB = dcb;
         fh_apply_operator(h, ld, oc);
     }
     std::vector<cplx> z(nodes), w(nodes);
@@ -1328,10 +1324,8 @@ static int fh_contour_apply_panel(feasthip_ctx* h, int64_t m64, const cplx* dQ, 
                 if ((rc = fh_upload_coefs(h, "ca_rcoefB", cb, &dcb))) return rc;
                 if ((rc = fh_get_buf(h, "ca_eigres", panel * sizeof(cplx), &p))) return rc;
                 fh_op_call oc;
-                oc.m = m; oc.uniform_coef = 0;
-                oc.X = Qp; oc.x_stride = 0; oc.Y = p; oc.y_stride = 0; oc.coefA = dca; oc.coefB = dcb;
-                oc.Bvec = nullptr; oc.b_stride = 0; oc.U = nullptr; oc.u_stride = 0; oc.dot_mode = 0;
-                oc.partial1 = nullptr; oc.partial2 = nullptr; oc.node_active = nullptr; oc.nodes = 1;
+                oc.m = m;
+                oc.X = Qp; oc.Y = p; oc.coefA = dca; oc.coefB = dcb;
                 fh_apply_operator(h, ld, oc);                    // A q - lambda B q (B = I handled by the operator kernel)
                 shared_src = (const cplx*)p;
             } else {
@@ -1798,123 +1792,6 @@ extern "C" int feasthip_estimate_count(feasthip_handle h, int64_t m, uint64_t se
 }
 
 // ---------------------------------------------------------------------------------------
-// small host-side complex Hermitian helpers (m <= 64) for the Cholesky-QR fast path
-// ---------------------------------------------------------------------------------------
-// pivoted Cholesky pivots of a Hermitian PSD matrix (column-major, leading dim ld): returns
-// min/max pivot ratio.  In exact arithmetic these pivots are the squares of the diagonal of R
-// in the column-pivoted QR of the panel, so the ratio bounds the rank test of
-// _feast_qr_compress! (src/core/feast_aux.jl:117-124) from the safe side.
-static double fh_pivoted_cholesky_ratio(std::vector<cplx> G, int m, int ld) {
-    std::vector<int> perm(m);
-    for (int i = 0; i < m; ++i) perm[i] = i;
-    double dmax = 0.0, dmin = 0.0;
-    auto at = [&](int i, int j) -> cplx& { return G[(size_t)j * ld + i]; };
-    for (int k = 0; k < m; ++k) {
-        int p = k;
-        for (int j = k + 1; j < m; ++j) if (at(j, j).x > at(p, p).x) p = j;
-        if (p != k) {     // symmetric swap of rows/cols k and p
-            for (int j = 0; j < m; ++j) std::swap(at(k, j), at(p, j));
-            for (int i = 0; i < m; ++i) std::swap(at(i, k), at(i, p));
-        }
-        double d = at(k, k).x;
-        if (k == 0) dmax = d;
-        if (!(d > 0.0) || !std::isfinite(d)) return 0.0;
-        dmin = d;
-        double r = std::sqrt(d);
-        at(k, k) = cmake(r, 0);
-        for (int i = k + 1; i < m; ++i) at(i, k) = cscale(at(i, k), 1.0 / r);
-        for (int j = k + 1; j < m; ++j)
-            for (int i = j; i < m; ++i) {
-                cplx v = csub(at(i, j), cmul(at(i, k), cconj(at(j, k))));
-                at(i, j) = v;
-                at(j, i) = cconj(v);
-            }
-    }
-    return dmax > 0.0 ? dmin / dmax : 0.0;
-}
-
-// Real twins of the two routines for a Gram matrix without imaginary parts (real projection of real-symmetric input:
-// Q_proj is real): the same arithmetic on a quarter of the flops -- the host's share of the orthonormalisation was
-// most of the 0.56 ms the step took per refinement loop on cfg 3.
-static double fh_pivoted_cholesky_ratio_real(std::vector<double> G, int m) {
-    double dmax = 0.0, dmin = 0.0;
-    auto at = [&](int i, int j) -> double& { return G[(size_t)j * m + i]; };
-    for (int k = 0; k < m; ++k) {
-        int p = k;
-        for (int j = k + 1; j < m; ++j) if (at(j, j) > at(p, p)) p = j;
-        if (p != k) {
-            for (int j = 0; j < m; ++j) std::swap(at(k, j), at(p, j));
-            for (int i = 0; i < m; ++i) std::swap(at(i, k), at(i, p));
-        }
-        const double d = at(k, k);
-        if (k == 0) dmax = d;
-        if (!(d > 0.0) || !std::isfinite(d)) return 0.0;
-        dmin = d;
-        const double r = std::sqrt(d);
-        for (int i = k + 1; i < m; ++i) at(i, k) /= r;
-        for (int j = k + 1; j < m; ++j) {
-            const double ajk = at(j, k);
-            for (int i = j; i < m; ++i) { const double v = at(i, j) - at(i, k) * ajk; at(i, j) = v; at(j, i) = v; }
-        }
-    }
-    return dmax > 0.0 ? dmin / dmax : 0.0;
-}
-static bool fh_chol_upper_inverse_real(const std::vector<double>& G, int m, int ld, std::vector<cplx>& Rinv) {
-    std::vector<double> R((size_t)m * m, 0.0), X((size_t)m * m, 0.0);
-    auto r = [&](int i, int j) -> double& { return R[(size_t)j * m + i]; };
-    for (int j = 0; j < m; ++j)
-        for (int i = 0; i <= j; ++i) {
-            double sum = G[(size_t)j * m + i];
-            for (int k = 0; k < i; ++k) sum -= r(k, i) * r(k, j);
-            if (i == j) {
-                if (!(sum > 0.0) || !std::isfinite(sum)) return false;
-                r(i, i) = std::sqrt(sum);
-            } else {
-                r(i, j) = sum / r(i, i);
-            }
-        }
-    Rinv.assign((size_t)ld * ld, cmake(0, 0));
-    for (int j = 0; j < m; ++j) {
-        X[(size_t)j * m + j] = 1.0 / r(j, j);
-        for (int i = j - 1; i >= 0; --i) {
-            double sum = 0.0;
-            for (int k = i + 1; k <= j; ++k) sum += r(i, k) * X[(size_t)j * m + k];
-            X[(size_t)j * m + i] = -sum / r(i, i);
-        }
-        for (int i = 0; i <= j; ++i) Rinv[(size_t)j * ld + i] = cmake(X[(size_t)j * m + i], 0);
-    }
-    return true;
-}
-
-// Rinv (ld x ld, column-major, zero padded) with G = R^H R, R upper triangular; false if not PD
-static bool fh_chol_upper_inverse(const std::vector<cplx>& G, int m, int ld, std::vector<cplx>& Rinv) {
-    std::vector<cplx> R((size_t)m * m, cmake(0, 0));
-    auto r = [&](int i, int j) -> cplx& { return R[(size_t)j * m + i]; };
-    for (int j = 0; j < m; ++j) {
-        for (int i = 0; i <= j; ++i) {
-            cplx sum = G[(size_t)j * ld + i];
-            for (int k = 0; k < i; ++k) sum = csub(sum, cmul(cconj(r(k, i)), r(k, j)));
-            if (i == j) {
-                if (!(sum.x > 0.0) || !std::isfinite(sum.x)) return false;
-                r(i, i) = cmake(std::sqrt(sum.x), 0);
-            } else {
-                r(i, j) = cscale(sum, 1.0 / r(i, i).x);
-            }
-        }
-    }
-    Rinv.assign((size_t)ld * ld, cmake(0, 0));
-    for (int j = 0; j < m; ++j) {          // back substitution, column by column
-        Rinv[(size_t)j * ld + j] = cmake(1.0 / r(j, j).x, 0);
-        for (int i = j - 1; i >= 0; --i) {
-            cplx sum = cmake(0, 0);
-            for (int k = i + 1; k <= j; ++k) sum = cadd(sum, cmul(r(i, k), Rinv[(size_t)j * ld + k]));
-            Rinv[(size_t)j * ld + i] = cscale(sum, -1.0 / r(i, i).x);
-        }
-    }
-    return true;
-}
-
-// ---------------------------------------------------------------------------------------
 // orthonormalisation (a9)
 // ---------------------------------------------------------------------------------------
 // Rank-revealing orthonormalisation of the m (<= ld) columns of panel X.  On success *res is the
@@ -1933,10 +1810,10 @@ static int fh_ortho_panel(feasthip_ctx* h, int m, int ld, cplx* X, cplx* Out, do
     double* dstate = (double*)p;
     if ((rc = fh_get_buf(h, "or_coef", FH_MAX_LD * sizeof(cplx), &p))) return rc;
     cplx* coef = (cplx*)p;
-    // Fast path (Cholesky-QR twice) when the panel is far from rank deficient: the pivoted
-    // Cholesky pivots of the Gram matrix are the squared R_kk of the pivoted QR, so a pivot
-    // ratio above 1e-10 means every |R_kk|/|R_11| > 1e-5 >> rank_tol and the reference rule
-    // keeps all m columns.  Otherwise fall through to the rank-revealing pivoted Gram-Schmidt.
+    // Fast path (Cholesky-QR, one or two passes) when the panel is far from rank deficient (fh_cholqr::accept: the pivoted
+    // Cholesky pivots of the Gram matrix are the squared R_kk of the pivoted QR).  Otherwise fall through to the
+    // rank-revealing pivoted Gram-Schmidt.  The Rayleigh-Ritz step that follows uses Q^H B Q anyway, so one pass suffices
+    // when it is orthonormal to 1e-14.
     if (!getenv("FH_NO_CHOLQR")) {
         if ((rc = fh_get_buf(h, "gram_work", fh_gram_work_elems(ld) * sizeof(cplx), &p))) return rc;
         cplx* gw = (cplx*)p;
@@ -1945,13 +1822,10 @@ static int fh_ortho_panel(feasthip_ctx* h, int m, int ld, cplx* X, cplx* Out, do
         if ((rc = fh_get_buf(h, "or_Rinv", (size_t)ld * ld * sizeof(cplx), &p))) return rc;
         cplx* dR = (cplx*)p;
         std::vector<cplx> Gh((size_t)ld * ld), Rinv;
+        std::vector<double> dcol;
         bool ok = true;
         cplx* src = X;
         cplx* dst = Out;
-        // A second Cholesky-QR pass squares away the orthogonality error of the first, eps / ratio' (ratio' = pivot ratio
-        // of the equilibrated Gram matrix ~ 1 / its condition number).  With ratio' > 1e-2 the first pass is already at
-        // 1e-14 -- the FEAST panel in steady state (B-orthonormal Ritz vectors times filter values, equilibrated) has
-        // ratio' ~ 0.4 -- and the Rayleigh-Ritz step that follows uses Q^H B Q anyway, so the pass is skipped.
         int npass = 2;
         static const bool always_two = getenv("FH_CHOLQR_TWO_PASS") != nullptr;
         for (int pass = 0; pass < npass && ok; ++pass) {
@@ -1960,45 +1834,12 @@ static int fh_ortho_panel(feasthip_ctx* h, int m, int ld, cplx* X, cplx* Out, do
             fh_prof_end(h);
             FH_CHECK(hipMemcpyAsync(Gh.data(), G, Gh.size() * sizeof(cplx), hipMemcpyDeviceToHost, h->stream));
             FH_CHECK(hipStreamSynchronize(h->stream));
-            std::vector<double> dcol;
-            double dmin_eq = 1.0, dmax_eq = 1.0;
-            if (pass == 0) {
-                // Equilibrate: G = D G' D with D = diag(column norms).  Columns of very different
-                // length (e.g. guard columns scaled by a small filter value) make G ill-conditioned
-                // although the directions are fine; Cholesky of G' is as stable as for unit columns.
-                // Full rank in the sense of the reference's pivoted-QR rule is accepted only with a
-                // wide margin: |R_kk|/|R_11| >~ (d_min/d_max) sqrt(ratio') must exceed 1e3 rank_tol.
-                dcol.resize(m);
-                double dmin = 0.0, dmax = ref_scale;
-                for (int j = 0; j < m; ++j) {
-                    const double g = Gh[(size_t)j * ld + j].x;
-                    dcol[j] = g > 0.0 && std::isfinite(g) ? std::sqrt(g) : 0.0;
-                    dmin = j == 0 ? dcol[j] : std::min(dmin, dcol[j]);
-                    dmax = std::max(dmax, dcol[j]);
-                }
-                if (!(dmin > 0.0)) { ok = false; break; }
-                for (int j = 0; j < m; ++j)
-                    for (int i = 0; i < m; ++i) {
-                        cplx& g = Gh[(size_t)j * ld + i];
-                        g = cscale(g, 1.0 / (dcol[i] * dcol[j]));
-                    }
-                dmin_eq = dmin; dmax_eq = dmax;
+            if (pass == 0) {         // equilibrates Gh: G = D G' D, D = diag(dcol)
+                const fh_cholqr::Plan plan = fh_cholqr::accept(Gh, m, ld, ref_scale, rank_tol, always_two, dcol);
+                if (plan == fh_cholqr::Plan::reject) { ok = false; break; }
+                if (plan == fh_cholqr::Plan::one_pass) npass = 1;
             }
-            // a Gram matrix without imaginary parts (real Q_proj) takes the real routines
-            bool is_real = true;
-            for (int j = 0; j < m && is_real; ++j)
-                for (int i = 0; i < m; ++i) if (Gh[(size_t)j * ld + i].y != 0.0) { is_real = false; break; }
-            std::vector<double> Gr;
-            if (is_real) {
-                Gr.resize((size_t)m * m);
-                for (int j = 0; j < m; ++j) for (int i = 0; i < m; ++i) Gr[(size_t)j * m + i] = Gh[(size_t)j * ld + i].x;
-            }
-            if (pass == 0) {
-                const double ratio = is_real ? fh_pivoted_cholesky_ratio_real(Gr, m) : fh_pivoted_cholesky_ratio(Gh, m, ld);
-                if (!(ratio > 1e-10) || !((dmin_eq / dmax_eq) * std::sqrt(ratio) > 1e3 * rank_tol)) { ok = false; break; }
-                if (ratio > 1e-2 && !always_two) npass = 1;
-            }
-            if (!(is_real ? fh_chol_upper_inverse_real(Gr, m, ld, Rinv) : fh_chol_upper_inverse(Gh, m, ld, Rinv))) { ok = false; break; }
+            if (!fh_cholqr::gram_upper_inverse(Gh, m, ld, Rinv)) { ok = false; break; }
             if (pass == 0)       // R = R' D  =>  R^-1 = D^-1 R'^-1: scale row i by 1/d_i
                 for (int j = 0; j < m; ++j)
                     for (int i = 0; i < m; ++i) Rinv[(size_t)j * ld + i] = cscale(Rinv[(size_t)j * ld + i], 1.0 / dcol[i]);
@@ -2148,17 +1989,6 @@ extern "C" int feasthip_orthonormalize(feasthip_handle h, int64_t m, void* Q, do
 // ---------------------------------------------------------------------------------------
 // Rayleigh-Ritz projection (a10)
 // ---------------------------------------------------------------------------------------
-static void fh_hermitize(std::vector<cplx>& G, int r) {
-    // _feast_hermitian_part!  src/core/feast_aux.jl:84-92
-    std::vector<cplx> out((size_t)r * r);
-    for (int j = 0; j < r; ++j)
-        for (int i = 0; i < r; ++i) {
-            cplx a = G[(size_t)j * r + i], b = cconj(G[(size_t)i * r + j]);
-            out[(size_t)j * r + i] = cmake(0.5 * (a.x + b.x), 0.5 * (a.y + b.y));
-        }
-    G.swap(out);
-}
-
 extern "C" int feasthip_project_dev(feasthip_handle h, int64_t r64, const void* dQ, int bilinear, int hermitize,
                                     void* Aq_host, void* Bq_host) {
     if (r64 > FH_MAX_LD) {
@@ -2199,10 +2029,8 @@ extern "C" int feasthip_project_dev(feasthip_handle h, int64_t r64, const void* 
                     fh_launch_to_panel((const cplx*)dQ + (size_t)j * ld * N, N, N, mj, Qj, ld, h->stream, fh_perm(h));
                     fh_op_call oc;
                     oc.m = mj;
-                    oc.X = Qj; oc.x_stride = 0; oc.Y = W; oc.y_stride = 0;
+                    oc.X = Qj; oc.Y = W;
                     oc.coefA = which == 0 ? d1 : d0; oc.coefB = which == 0 ? d0 : d1;
-                    oc.Bvec = nullptr; oc.b_stride = 0; oc.U = nullptr; oc.u_stride = 0; oc.dot_mode = 0;
-                    oc.partial1 = nullptr; oc.partial2 = nullptr; oc.node_active = nullptr; oc.nodes = 1;
                     fh_apply_operator(h, ld, oc);
                     for (int i = 0; i < npan; ++i) {
                         const int mi = std::min(ld, r - i * ld);
@@ -2217,7 +2045,7 @@ extern "C" int feasthip_project_dev(feasthip_handle h, int64_t r64, const void* 
                                 res[(size_t)(j * ld + c2) * r + i * ld + c1] = Gh[(size_t)c2 * ld + c1];
                     }
                 }
-                if (hermitize && !bilinear) fh_hermitize(res, r);
+                if (hermitize && !bilinear) fh_cholqr::hermitian_part(res.data(), r);
             }
             memcpy(out_host, res.data(), res.size() * sizeof(cplx));
         }
@@ -2257,10 +2085,8 @@ extern "C" int feasthip_project_dev(feasthip_handle h, int64_t r64, const void* 
         // (B = I without orthonormal Q, variant C: the operator kernel yields W = Q, so G = Q^H Q)
         fh_op_call oc;
         oc.m = r;
-        oc.X = Qp; oc.x_stride = 0; oc.Y = W; oc.y_stride = 0;
+        oc.X = Qp; oc.Y = W;
         oc.coefA = which == 0 ? d1 : d0; oc.coefB = which == 0 ? d0 : d1;
-        oc.Bvec = nullptr; oc.b_stride = 0; oc.U = nullptr; oc.u_stride = 0; oc.dot_mode = 0;
-        oc.partial1 = nullptr; oc.partial2 = nullptr; oc.node_active = nullptr; oc.nodes = 1;
         fh_apply_operator(h, ld, oc);
         fh_prof_begin(h, "gram");
         fh_launch_gram(Qp, W, N, ld, bilinear, gw, G + (size_t)which * ld * ld, h->stream);
@@ -2280,7 +2106,7 @@ extern "C" int feasthip_project_dev(feasthip_handle h, int64_t r64, const void* 
         } else {
             const cplx* Gw = Gh.data() + (size_t)which * ld * ld;
             for (int j = 0; j < r; ++j) for (int i = 0; i < r; ++i) res[(size_t)j * r + i] = Gw[(size_t)j * ld + i];
-            if (hermitize && !bilinear) fh_hermitize(res, r);
+            if (hermitize && !bilinear) fh_cholqr::hermitian_part(res.data(), r);
         }
         memcpy(out_host, res.data(), res.size() * sizeof(cplx));
     }
@@ -2302,6 +2128,47 @@ extern "C" int feasthip_project(feasthip_handle h, int64_t r, const void* Q, int
 // ---------------------------------------------------------------------------------------
 // Ritz back-transform + residual (a12, a13)
 // ---------------------------------------------------------------------------------------
+// R = A X - B X diag(lambda) on the first ncols columns of an ld-wide panel -- A X - X diag(lambda) when use_B = 0 and B != I
+// (RCI-style residual, src/kernel/feast_kernel.jl:899-906); lambda holds (re, im) pairs.  With dots != null the squared
+// column norms are queued into the pinned ring as well: *dots is valid after the caller's next stream synchronisation
+// (fh_residual_norms).  No synchronisation of its own.
+static int fh_panel_residual(feasthip_ctx* h, int ld, int ncols, const cplx* X, cplx* R, const double* lambda, int use_B,
+                             cplx* part, cplx* ddots, const cplx** dots, std::vector<char>& fallback) {
+    const int N = (int)fh_N(h);
+    const bool lam_in_op = use_B || fh_b_identity(h);
+    std::vector<cplx> ca(ld, cmake(1, 0)), cb(ld, cmake(0, 0));
+    for (int c = 0; c < ncols; ++c) cb[c] = lam_in_op ? cmake(-lambda[2 * c], -lambda[2 * c + 1]) : cmake(0, 0);
+    int rc;
+    cplx *dca, *dcb;
+    if ((rc = fh_upload_coefs(h, "rz_coefA", ca, &dca))) return rc;
+    if ((rc = fh_upload_coefs(h, "rz_coefB", cb, &dcb))) return rc;
+    fh_op_call oc;
+    oc.m = ncols;
+    oc.X = X; oc.Y = R; oc.coefA = dca; oc.coefB = dcb;
+    fh_apply_operator(h, ld, oc);
+    if (!lam_in_op) {
+        std::vector<cplx> lam(ld, cmake(0, 0));
+        for (int c = 0; c < ncols; ++c) lam[c] = cmake(lambda[2 * c], lambda[2 * c + 1]);
+        cplx* dl;
+        if ((rc = fh_upload_coefs(h, "rz_lam", lam, &dl))) return rc;
+        fh_launch_axpy_cols(R, X, dl, N, ld, h->stream);   // R -= X diag(lam)
+    }
+    if (!dots) return 0;
+    fh_launch_dot_cols(R, R, N, ld, part, ddots, h->stream);
+    const void* slot = nullptr;
+    if ((rc = fh_download_small(h, ddots, ld * sizeof(cplx), &slot, fallback))) return rc;
+    *dots = (const cplx*)slot;
+    return 0;
+}
+
+// res_j = ||R_j|| / max(|lambda_j|, 1), j < M, from the squared norms of fh_panel_residual
+static void fh_residual_norms(const cplx* dots, const double* lambda, int M, double* res) {
+    for (int c = 0; c < M; ++c) {
+        const double la = std::hypot(lambda[2 * c], lambda[2 * c + 1]);
+        res[c] = std::sqrt(dots[c].x) / std::max(la, 1.0);
+    }
+}
+
 extern "C" int feasthip_ritz_residual_dev(feasthip_handle h, int64_t r64, const void* dQ, const void* V_host,
                                           const double* lambda_host, int64_t M, int normalize, int use_B, void* dX,
                                           double* res_host) {
@@ -2339,6 +2206,7 @@ extern "C" int feasthip_ritz_residual_dev(feasthip_handle h, int64_t r64, const 
         const cplx* Vh = (const cplx*)V_host;
         const int npan = (r + ld - 1) / ld;
         std::vector<cplx> Vp((size_t)ld * ld), dots(ld);
+        std::vector<char> dots_fb;
         for (int j = 0; j < npan; ++j) {
             const int mj = std::min(ld, r - j * ld);
             for (int i = 0; i < npan; ++i) {
@@ -2375,32 +2243,10 @@ extern "C" int feasthip_ritz_residual_dev(feasthip_handle h, int64_t r64, const 
             fh_launch_from_panel(Xp, ld, N, mj, (cplx*)dX + (size_t)j * ld * N, N, h->stream, fh_perm(h));
             if (Mj > 0 && res_host) {
                 const double* lam = lambda_host + 2 * (size_t)j * ld;
-                std::vector<cplx> ca(ld, cmake(1, 0)), cb(ld, cmake(0, 0));
-                const bool lam_in_op = use_B || fh_b_identity(h);
-                for (int c = 0; c < mj; ++c) cb[c] = lam_in_op ? cmake(-lam[2 * c], -lam[2 * c + 1]) : cmake(0, 0);
-                cplx *dca, *dcb;
-                if ((rc = fh_upload_coefs(h, "rz_coefA", ca, &dca))) return rc;
-                if ((rc = fh_upload_coefs(h, "rz_coefB", cb, &dcb))) return rc;
-                fh_op_call oc;
-                oc.m = mj;
-                oc.X = Xp; oc.x_stride = 0; oc.Y = Rp; oc.y_stride = 0; oc.coefA = dca; oc.coefB = dcb;
-                oc.Bvec = nullptr; oc.b_stride = 0; oc.U = nullptr; oc.u_stride = 0; oc.dot_mode = 0;
-                oc.partial1 = nullptr; oc.partial2 = nullptr; oc.node_active = nullptr; oc.nodes = 1;
-                fh_apply_operator(h, ld, oc);
-                if (!use_B && !fh_b_identity(h)) {
-                    std::vector<cplx> lv(ld, cmake(0, 0));
-                    for (int c = 0; c < mj; ++c) lv[c] = cmake(lam[2 * c], lam[2 * c + 1]);
-                    cplx* dl;
-                    if ((rc = fh_upload_coefs(h, "rz_lam", lv, &dl))) return rc;
-                    fh_launch_axpy_cols(Rp, Xp, dl, N, ld, h->stream);
-                }
-                fh_launch_dot_cols(Rp, Rp, N, ld, part, ddots, h->stream);
-                FH_CHECK(hipMemcpyAsync(dots.data(), ddots, ld * sizeof(cplx), hipMemcpyDeviceToHost, h->stream));
+                const cplx* rdots = nullptr;
+                if ((rc = fh_panel_residual(h, ld, mj, Xp, Rp, lam, use_B, part, ddots, &rdots, dots_fb))) return rc;
                 FH_CHECK(hipStreamSynchronize(h->stream));
-                for (int c = 0; c < Mj; ++c) {
-                    double la = std::hypot(lam[2 * c], lam[2 * c + 1]);
-                    res_host[j * ld + c] = std::sqrt(dots[c].x) / std::max(la, 1.0);
-                }
+                fh_residual_norms(rdots, lam, Mj, res_host + (size_t)j * ld);
             }
         }
         FH_CHECK(hipStreamSynchronize(h->stream));
@@ -2438,7 +2284,6 @@ extern "C" int feasthip_ritz_residual_dev(feasthip_handle h, int64_t r64, const 
     fh_prof_begin(h, "ritz");
     fh_launch_small_matmul(Qp, dV, N, ld, Xp, h->stream);
     fh_prof_end(h);
-    std::vector<cplx> dots(ld);
     if (normalize && M > 0) {
         // normalise the first M columns (src/dense/feast_dense.jl:301-305): norms and scaling stay on the device
         fh_launch_dot_cols(Xp, Xp, N, ld, part, ddots, h->stream);
@@ -2446,34 +2291,11 @@ extern "C" int feasthip_ritz_residual_dev(feasthip_handle h, int64_t r64, const 
     }
     fh_launch_from_panel(Xp, ld, N, r, (cplx*)dX, N, h->stream, fh_perm(h));
     if (M > 0 && res_host) {
-        // R = A X - B X diag(lambda); res_j = ||R_j|| / max(|lambda_j|, 1)
-        std::vector<cplx> ca(ld, cmake(1, 0)), cb(ld, cmake(0, 0));
-        const bool lam_in_op = use_B || fh_b_identity(h);
-        for (int c = 0; c < r; ++c) cb[c] = lam_in_op ? cmake(-lambda_host[2 * c], -lambda_host[2 * c + 1]) : cmake(0, 0);
-        cplx *dca, *dcb;
-        if ((rc = fh_upload_coefs(h, "rz_coefA", ca, &dca))) return rc;
-        if ((rc = fh_upload_coefs(h, "rz_coefB", cb, &dcb))) return rc;
-        fh_op_call oc;
-        oc.m = r;
-        oc.X = Xp; oc.x_stride = 0; oc.Y = Rp; oc.y_stride = 0; oc.coefA = dca; oc.coefB = dcb;
-        oc.Bvec = nullptr; oc.b_stride = 0; oc.U = nullptr; oc.u_stride = 0; oc.dot_mode = 0;
-        oc.partial1 = nullptr; oc.partial2 = nullptr; oc.node_active = nullptr; oc.nodes = 1;
-        fh_apply_operator(h, ld, oc);
-        if (!use_B && !fh_b_identity(h)) {
-            // RCI-style residual without B: R = A X - X diag(lambda)  (src/kernel/feast_kernel.jl:899-906)
-            std::vector<cplx> lam(ld, cmake(0, 0));
-            for (int c = 0; c < r; ++c) lam[c] = cmake(lambda_host[2 * c], lambda_host[2 * c + 1]);
-            cplx* dl;
-            if ((rc = fh_upload_coefs(h, "rz_lam", lam, &dl))) return rc;
-            fh_launch_axpy_cols(Rp, Xp, dl, N, ld, h->stream);   // R -= X diag(lam)
-        }
-        fh_launch_dot_cols(Rp, Rp, N, ld, part, ddots, h->stream);
-        FH_CHECK(hipMemcpyAsync(dots.data(), ddots, ld * sizeof(cplx), hipMemcpyDeviceToHost, h->stream));
+        const cplx* rdots = nullptr;
+        std::vector<char> dots_fb;
+        if ((rc = fh_panel_residual(h, ld, r, Xp, Rp, lambda_host, use_B, part, ddots, &rdots, dots_fb))) return rc;
         FH_CHECK(hipStreamSynchronize(h->stream));
-        for (int c = 0; c < (int)M; ++c) {
-            double la = std::hypot(lambda_host[2 * c], lambda_host[2 * c + 1]);
-            res_host[c] = std::sqrt(dots[c].x) / std::max(la, 1.0);
-        }
+        fh_residual_norms(rdots, lambda_host, (int)M, res_host);
     }
     FH_CHECK(hipStreamSynchronize(h->stream));
     fh_prof_collect(h);
@@ -2512,10 +2334,10 @@ extern "C" int feasthip_ritz_residual(feasthip_handle h, int64_t r, const void* 
 // pairs of a subspace do not depend on the basis, so the reduced pencil is taken on Q_proj with unit columns -- three Gram
 // products (Q^H Q for the test, Q^H A Q, Q^H B Q) queued behind ONE synchronisation, an O(m^2) scaling on the host -- and
 // handed to the host's generalized eigensolver, whose Cholesky factorisation of the B-part does what the Cholesky-QR did;
-// the Ritz vectors are Q_proj (D^-1 V): one tall product instead of two.  The acceptance test is fh_ortho_panel's one-pass
-// condition (equilibrated pivoted-Cholesky ratio > 1e-2, the reference's rank rule with its margin); anything else -- rank
-// deficiency, a ratio that needs the second Cholesky-QR pass -- takes fh_ortho_panel itself on the resident panel, so the
-// rank decisions are the same as the per-primitive path's.
+// the Ritz vectors are Q_proj (D^-1 V): one tall product instead of two.  The acceptance test is fh_ortho_panel's own
+// (fh_cholqr::accept) and the implicit basis is taken when it decides "one pass"; anything else -- rank deficiency, a ratio
+// that needs the second Cholesky-QR pass -- takes fh_ortho_panel itself on the resident panel, so the rank decisions are the
+// same as the per-primitive path's.
 // The eigen-residual panel A X - B X diag(lambda) the Ritz step forms for its norms is the next sweep's shared start
 // residual (fh_contour_apply_panel: shared_src), which saves that sweep's first operator product.
 // ---------------------------------------------------------------------------------------
@@ -2604,10 +2426,8 @@ extern "C" int feasthip_rr_reduce_resident(feasthip_handle h, int64_t m64, doubl
             if (which == 1 && b_id) break;
             fh_op_call oc;
             oc.m = m;
-            oc.X = basis; oc.x_stride = 0; oc.Y = W; oc.y_stride = 0;
+            oc.X = basis; oc.Y = W;
             oc.coefA = which == 0 ? d1 : d0; oc.coefB = which == 0 ? d0 : d1;
-            oc.Bvec = nullptr; oc.b_stride = 0; oc.U = nullptr; oc.u_stride = 0; oc.dot_mode = 0;
-            oc.partial1 = nullptr; oc.partial2 = nullptr; oc.node_active = nullptr; oc.nodes = 1;
             fh_apply_operator(h, ld, oc);
             fh_prof_begin(h, "gram");
             fh_launch_gram(basis, W, N, ld, 0, gw, G + (size_t)(1 + which) * g2, h->stream);
@@ -2629,53 +2449,21 @@ extern "C" int feasthip_rr_reduce_resident(feasthip_handle h, int64_t m64, doubl
                 if (d) g = cscale(g, 1.0 / (d[i] * d[j]));
                 out[(size_t)j * r + i] = g;
             }
-        if (hermitize)
-            for (int j = 0; j < r; ++j)
-                for (int i = 0; i <= j; ++i) {
-                    const cplx a = out[(size_t)j * r + i], b = cconj(out[(size_t)i * r + j]);
-                    const cplx hm = cmake(0.5 * (a.x + b.x), 0.5 * (a.y + b.y));
-                    out[(size_t)j * r + i] = hm; out[(size_t)i * r + j] = cconj(hm);
-                }
+        if (hermitize) fh_cholqr::hermitian_part(out, r);
     };
     auto identity = [&](int r, void* out_host) {
         cplx* out = (cplx*)out_host;
         for (int j = 0; j < r; ++j) for (int i = 0; i < r; ++i) out[(size_t)j * r + i] = cmake(i == j ? 1.0 : 0.0, 0.0);
     };
     if ((rc = grams(P, true))) return rc;
-    // ---- implicit basis: the acceptance test of fh_ortho_panel, on the Gram matrix we already have ----
-    bool fast = !getenv("FH_NO_CHOLQR");
-    std::vector<double> dcol(m, 1.0);
-    if (fast) {
+    // ---- implicit basis: fh_ortho_panel's acceptance test on the Gram matrix we already have; its one-pass decision (the basis
+    //      below is then as good as an orthonormalised one to 1e-14) takes the fast path ----
+    std::vector<double> dcol;
+    bool fast = false;
+    if (!getenv("FH_NO_CHOLQR")) {
+        static const bool always_two = getenv("FH_CHOLQR_TWO_PASS") != nullptr;
         std::vector<cplx> G0(Gh, Gh + g2);
-        double dmin = 0.0, dmax = 0.0;
-        for (int j = 0; j < m; ++j) {
-            const double g = G0[(size_t)j * ld + j].x;
-            dcol[j] = g > 0.0 && std::isfinite(g) ? std::sqrt(g) : 0.0;
-            dmin = j == 0 ? dcol[j] : std::min(dmin, dcol[j]);
-            dmax = std::max(dmax, dcol[j]);
-        }
-        fast = dmin > 0.0;
-        if (fast) {
-            bool is_real = true;
-            for (int j = 0; j < m; ++j)
-                for (int i = 0; i < m; ++i) {
-                    cplx& g = G0[(size_t)j * ld + i];
-                    g = cscale(g, 1.0 / (dcol[i] * dcol[j]));
-                    if (g.y != 0.0) is_real = false;
-                }
-            double ratio;
-            if (is_real) {
-                std::vector<double> Gr((size_t)m * m);
-                for (int j = 0; j < m; ++j) for (int i = 0; i < m; ++i) Gr[(size_t)j * m + i] = G0[(size_t)j * ld + i].x;
-                ratio = fh_pivoted_cholesky_ratio_real(std::move(Gr), m);
-            } else {
-                ratio = fh_pivoted_cholesky_ratio(std::move(G0), m, ld);
-            }
-            static const bool always_two = getenv("FH_CHOLQR_TWO_PASS") != nullptr;
-            // the one-pass condition of fh_ortho_panel (pivot ratio of the equilibrated Gram matrix > 1e-2: the basis below is
-            // then as good as an orthonormalised one to 1e-14) and the reference's rank rule with the same margin as there
-            fast = ratio > 1e-2 && !always_two && (dmin / dmax) * std::sqrt(ratio) > 1e3 * rank_tol;
-        }
+        fast = fh_cholqr::accept(G0, m, ld, 0.0, rank_tol, always_two, dcol) == fh_cholqr::Plan::one_pass;
     }
     if (fast) {
         // basis = Q_proj D^-1 (unit columns): its pencil is the equilibrated Gram pair; the orthonormal basis is never formed
@@ -2746,35 +2534,11 @@ extern "C" int feasthip_rr_ritz_resident(feasthip_handle h, int64_t r64, const v
         fh_launch_dot_cols(Xp, Xp, N, ld, part, ddots, h->stream);
         fh_launch_normalize_cols(Xp, ddots, N, ld, (int)M, h->stream);
     }
-    // R = A X - B X diag(lambda) for all r columns (the next sweep's start residual); res_j = ||R_j|| / max(|lambda_j|, 1), j < M
-    std::vector<cplx> ca(ld, cmake(1, 0)), cb(ld, cmake(0, 0));
-    const bool lam_in_op = use_B || fh_b_identity(h);
-    for (int c = 0; c < r; ++c) cb[c] = lam_in_op ? cmake(-lambda_host[2 * c], -lambda_host[2 * c + 1]) : cmake(0, 0);
-    cplx *dca, *dcb;
-    if ((rc = fh_upload_coefs(h, "rz_coefA", ca, &dca))) return rc;
-    if ((rc = fh_upload_coefs(h, "rz_coefB", cb, &dcb))) return rc;
-    fh_op_call oc;
-    oc.m = r;
-    oc.X = Xp; oc.x_stride = 0; oc.Y = Rp; oc.y_stride = 0; oc.coefA = dca; oc.coefB = dcb;
-    oc.Bvec = nullptr; oc.b_stride = 0; oc.U = nullptr; oc.u_stride = 0; oc.dot_mode = 0;
-    oc.partial1 = nullptr; oc.partial2 = nullptr; oc.node_active = nullptr; oc.nodes = 1;
-    fh_apply_operator(h, ld, oc);
-    if (!lam_in_op) {
-        // RCI-style residual without B: R = A X - X diag(lambda)  (src/kernel/feast_kernel.jl:899-906)
-        std::vector<cplx> lam(ld, cmake(0, 0));
-        for (int c = 0; c < r; ++c) lam[c] = cmake(lambda_host[2 * c], lambda_host[2 * c + 1]);
-        cplx* dl;
-        if ((rc = fh_upload_coefs(h, "rz_lam", lam, &dl))) return rc;
-        fh_launch_axpy_cols(Rp, Xp, dl, N, ld, h->stream);
-    }
+    // R for all r columns (the next sweep's start residual); its column norms only when asked for
     const cplx* dots_h = nullptr;
     std::vector<char> dots_fb;
-    if (M > 0 && res_host) {
-        fh_launch_dot_cols(Rp, Rp, N, ld, part, ddots, h->stream);
-        const void* slot = nullptr;
-        if ((rc = fh_download_small(h, ddots, ld * sizeof(cplx), &slot, dots_fb))) return rc;
-        dots_h = (const cplx*)slot;
-    }
+    const bool want_res = M > 0 && res_host;
+    if ((rc = fh_panel_residual(h, ld, r, Xp, Rp, lambda_host, use_B, part, ddots, want_res ? &dots_h : nullptr, dots_fb))) return rc;
     // the rank dropped below the panel's padded width (64 -> 32 / 16 columns): the next sweep works on the narrower panel
     int ldx = ld;
     if (fh_pick_ld(r) < ld) {
@@ -2787,11 +2551,7 @@ extern "C" int feasthip_rr_ritz_resident(feasthip_handle h, int64_t r64, const v
         }
     }
     FH_CHECK(hipStreamSynchronize(h->stream));
-    if (M > 0 && res_host)
-        for (int c = 0; c < (int)M; ++c) {
-            const double la = std::hypot(lambda_host[2 * c], lambda_host[2 * c + 1]);
-            res_host[c] = std::sqrt(dots_h[c].x) / std::max(la, 1.0);
-        }
+    if (want_res) fh_residual_norms(dots_h, lambda_host, (int)M, res_host);
     h->rs_X = Xp; h->rs_X_m = r; h->rs_X_ld = ldx;
     h->rs_R_lambda.assign(ld, cmake(0, 0));
     if (use_B || fh_b_identity(h)) {                  // the start residual of the sweeps is the one WITH B
@@ -3011,9 +2771,7 @@ extern "C" int feasthip_matmul_dev(feasthip_handle h, int which, int64_t m64, co
     if ((rc = fh_upload_coefs(h, "mm_coefB", cb, &dcb))) return rc;
     fh_op_call oc;
     oc.m = m;
-    oc.X = Xp; oc.x_stride = 0; oc.Y = Yp; oc.y_stride = 0; oc.coefA = dca; oc.coefB = dcb;
-    oc.Bvec = nullptr; oc.b_stride = 0; oc.U = nullptr; oc.u_stride = 0; oc.dot_mode = 0;
-    oc.partial1 = nullptr; oc.partial2 = nullptr; oc.node_active = nullptr; oc.nodes = 1;
+    oc.X = Xp; oc.Y = Yp; oc.coefA = dca; oc.coefB = dcb;
     fh_apply_operator(h, ld, oc);
     fh_launch_from_panel(Yp, ld, N, m, (cplx*)dY, N, h->stream, fh_perm(h));
     FH_CHECK(hipStreamSynchronize(h->stream));
