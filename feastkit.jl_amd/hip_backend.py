@@ -23,6 +23,7 @@ The reduced M0 x M0 eigenproblem stays on host LAPACK (SURVEY.md section 8 row a
 """
 from __future__ import annotations
 
+import ctypes
 import math
 import threading
 import time
@@ -30,12 +31,14 @@ import time
 import numpy as np
 import scipy.linalg as sla
 
+from . import _lib
 from .contour import (balanced_contour_points, cost_balanced_contour_points, distribute_contour_points, feast_contour,
                       feast_gcontour, feast_inside_gcontour, split_balanced_assignment)
 from .parameters import check_feast_srci_input, feast_tolerance, feastdefault
 from .types import FeastError, FeastResult
 
 SQRT_EPS = math.sqrt(np.finfo(np.float64).eps)
+DIRECT_SOLVERS = ("direct", "lu", "banded")        # every other solver name is a Krylov method
 
 try:
     # The reduced M0 x M0 problems are far too small for threaded BLAS, and a BLAS pool that keeps spinning
@@ -151,6 +154,280 @@ def _reduced_hermitian_eig(Sq, Aq):
             return np.real(w).astype(np.float64), V
 
 
+def _empty_result(N, info, loop=0, *, complex_lambda=False, real_q=False, epsout=math.inf, stats=None):
+    """The FeastResult of a call that returns no eigenpair: bad input, a failed sweep or nothing converged."""
+    return FeastResult(np.zeros(0, complex if complex_lambda else float), np.zeros((N, 0), float if real_q else complex), 0,
+                       np.zeros(0), int(info), epsout, loop, {} if stats is None else stats)
+
+
+def _setup_sweep(engine, group, A, B, Zne, Wne, weight, real_projection):
+    """Communicator, pencil, contour (weights weight * Wne[e]), projection and this rank's block of nodes -> (world, count)."""
+    rank, world = _world(engine, group)
+    engine.set_problem(A, B)
+    engine.set_contour(Zne, Wne, weight)
+    engine.set_real_projection(real_projection)
+    first, count = distribute_contour_points(len(Zne), world)[rank]
+    engine.set_node_range(first, count)
+    return world, count
+
+
+def _configure_solver(engine, solver, fpm, solver_tol, solver_maxiter, solver_restart, **extra):
+    """The standard solver setting: tol 10^-fpm[3] unless solver_tol, absolute too for Krylov -> (iterative, tol_value)."""
+    iterative = solver not in DIRECT_SOLVERS
+    tol_value = feast_tolerance(fpm) if solver_tol == 0.0 else float(solver_tol)
+    engine.set_solver(solver, rtol=tol_value, atol=tol_value if iterative else 0.0, maxit=solver_maxiter,
+                      restart=solver_restart, cache_factors=True, **extra)
+    return iterative, tol_value
+
+
+def _failure(status, world, count):
+    """Raw failure code of a sweep (0, 5 = a Krylov solve failed, 8 = singular shift); a lone rank without nodes has none."""
+    return int(np.max(status)) if (world > 1 or count > 0) else 0
+
+
+def _sweep(engine, dQ, m, world, count, stats, lam_guess=None, want_moments=False, resident=False):
+    """One sweep + the solve counters into stats (if kept) -> (raw failure code, the engine's tuple); each driver maps the code."""
+    if resident:
+        out = (None,) + tuple(engine.contour_apply_resident(dQ, m, lam_guess))
+    elif want_moments:
+        out = engine.contour_apply(dQ, m, lam_guess, want_moments=True)
+    else:
+        out = engine.contour_apply(dQ, m, lam_guess)
+    st = out[2]
+    if stats is not None:
+        stats["krylov_iterations"] += st.get("krylov_iterations", 0)
+        stats["factorizations"] += st.get("factorizations", 0)
+        stats["solve_seconds"] += st.get("seconds_solve", 0.0)
+    return _failure(out[1], world, count), out
+
+
+def _check_circle_input(N, M0, r):
+    """Input check of the general and complex-symmetric drivers -> 1 (N), 2 (M0), 4 (radius) or 0."""
+    if N <= 0:
+        return 1
+    if M0 <= 0 or M0 > N:
+        return 2
+    if not r > 0:
+        return 4
+    return 0
+
+
+def _complex_pencil(A, B):
+    """A and B as complex128 (complex input as it is)."""
+    Ac = A.astype(np.complex128) if not np.iscomplexobj(A) else A
+    Bc = None if B is None else (B.astype(np.complex128) if not np.iscomplexobj(B) else B)
+    return Ac, Bc
+
+
+def _reorder_by_contour(lam, Emid, r, fpm, n):
+    """Stable inside-first permutation for the contour of (Emid, r) -> (perm, ninside); cf. _reorder_by_interval."""
+    ins = [i for i in range(n) if feast_inside_gcontour(lam[i], Emid, r, fpm)]
+    inset = set(ins)
+    return np.array(ins + [i for i in range(n) if i not in inset], dtype=np.int64), len(ins)
+
+
+class _NodeLayout:
+    """This rank's quadrature nodes (local_nodes, count) and right-hand-side column group (my_cg of my_cgs) in a Hermitian sweep."""
+
+    def __init__(self, engine, n_nodes, rank, world, M0, column_groups, node_assignment, iterative):
+        if column_groups == "auto":
+            column_groups = 1
+            if iterative and world > 1:
+                for g in range(world, 0, -1):
+                    if world % g == 0 and M0 // g >= 16:
+                        column_groups = g
+                        break
+        column_groups = int(column_groups)
+        if column_groups < 1 or world % column_groups != 0 or (column_groups > 1 and not iterative):
+            raise ValueError("column_groups must divide the world size and needs an iterative solver")
+        self.rank, self.world, self.iterative, self.node_assignment = rank, world, iterative, node_assignment
+        self.node_groups, self.node_rank = world // column_groups, rank // column_groups
+        balanced = node_assignment == "balanced" or callable(node_assignment)
+        if balanced and self.node_groups > 1:
+            nodes_here = balanced_contour_points(n_nodes, self.node_groups)[self.node_rank]
+            engine.set_node_list(nodes_here)
+            self.count, self.local_nodes = len(nodes_here), list(nodes_here)
+        else:
+            first, self.count = distribute_contour_points(n_nodes, self.node_groups)[self.node_rank]
+            engine.set_node_range(first, self.count)
+            self.local_nodes = list(range(first, first + self.count))
+        # this rank's column group: fixed by the grid, or re-derived every loop by split_balanced_assignment, which splits
+        # only the heaviest nodes by columns
+        self.my_cg, self.my_cgs = rank % column_groups, column_groups
+        self.split = balanced and column_groups == 1 and world > 1 and iterative
+        self.node_parts = {}                         # node -> column groups it was swept in (its iteration count arrives summed)
+
+    def column_block(self, ncols):
+        """[c0, c1) of this rank's column group: blocks in multiples of 16, remainder to the last."""
+        if self.my_cgs == 1:
+            return 0, ncols
+        per = max(16, -(-ncols // self.my_cgs // 16) * 16) if ncols >= 16 * self.my_cgs else -(-ncols // self.my_cgs)
+        c0 = min(ncols, self.my_cg * per)
+        c1 = ncols if self.my_cg == self.my_cgs - 1 else min(ncols, c0 + per)
+        return c0, c1
+
+    def rebalance(self, engine, loop_idx, active, stats):
+        """From loop 1 on: re-derive the layout from the iteration counts the sweep just measured (identical on every rank)."""
+        if loop_idx < 1 or not hasattr(engine, "last_global_node_iterations"):
+            return
+        if self.split:
+            # node-only layout asked for: let the heaviest nodes be split by columns over several ranks when that lowers
+            # the largest share (contour.split_balanced_assignment)
+            costs = [float(v) / self.node_parts.get(e, 1) for e, v in enumerate(engine.last_global_node_iterations())]
+            layout = (self.node_assignment(costs, self.world) if callable(self.node_assignment)
+                      else split_balanced_assignment(costs, self.world, ncols=active))
+            nodes_here, self.my_cg, self.my_cgs = layout[self.rank]
+            self.node_parts = {e: k for nodes, _g, k in layout for e in nodes}
+            stats["layout"] = [(list(map(int, nodes)), int(g), int(k)) for nodes, g, k in layout]
+        elif self.node_assignment == "balanced" and self.node_groups > 1 and self.iterative:
+            # re-balance the node groups: the slow near-axis nodes no longer share a group by accident
+            nodes_here = cost_balanced_contour_points(engine.last_global_node_iterations(), self.node_groups)[self.node_rank]
+        else:
+            return
+        if list(nodes_here) != list(self.local_nodes):
+            engine.set_node_list(nodes_here)
+            self.count, self.local_nodes = len(nodes_here), list(nodes_here)
+            stats["local_nodes"] = [int(v) for v in self.local_nodes]
+
+
+class _InexactPolicy(_lib.FeastHipPolicy):
+    """The inexact mode's host policy under the C ABI (feasthip_policy_*, csrc/fh_policy.hpp); fields are the C struct's.
+    hist, reach: fpm[18] and the subspace reach of every loop under contour steering."""
+
+    def init(self, Emin, Emax, fpm, inner_rtol, outer_tol, maxiter, steer):
+        """feasthip_policy_init -> True when the policy is in force."""
+        self.hist, self.reach = [], []
+        return _lib.load_library().feasthip_policy_init(
+            ctypes.byref(self), float(Emin), float(Emax), int(fpm[2]), int(fpm[16]), float(inner_rtol), float(outer_tol),
+            int(maxiter), int(steer), int(fpm[18])) == 0
+
+    def update(self, epsout, M, capped, ritz, rank_q):
+        """feasthip_policy_update after a loop -> (ellipse ratio changed, inner cap or tolerance changed)."""
+        prev = self.aspect, self.inner_cap, self.next_rtol
+        ritz_c = np.ascontiguousarray(ritz[:rank_q], dtype=np.float64)
+        _lib.load_library().feasthip_policy_update(ctypes.byref(self), float(epsout), int(M), int(capped),
+                                                   ritz_c.ctypes.data_as(ctypes.c_void_p), int(rank_q))
+        return self.aspect != prev[0], (self.inner_cap, self.next_rtol) != prev[1:]
+
+    def steer(self, engine, Emin, Emax, fpm, layout):
+        """fpm[18] := the policy's ellipse ratio, the contour re-issued on this rank's nodes (set_contour resets them)."""
+        fpm[18] = self.aspect
+        Zne, Wne = feast_contour(Emin, Emax, fpm)
+        engine.set_contour(Zne, Wne, 2.0)
+        engine.set_node_list(layout.local_nodes)
+
+
+def _policy_set_aside(engine, resident, dP, rank_q, V, lam, M, dX, res):
+    """Inexact inner solves leave solver noise in the guard columns.  Its Ritz values are arbitrary; one that lands inside
+    the interval has an O(1) residual that never contracts and would hold epsout up forever (variant A has no spurious-pair
+    removal; with exact solves the guard columns are true eigen-directions and stay outside).  A pair is set aside when
+    its relative residual is > 0.1 AND > 100x the smallest residual of the pairs inside: a true pair inside the interval
+    sees a filter value >= 1/2 and contracts with the others, it cannot sit at 10 % while another pair is 100x ahead.
+    Set-aside pairs stay in the subspace and are re-examined every loop (measured on a random pencil: the ten true pairs
+    contract by ~1e-2 per loop while one to three noise pairs stay at residual 1).  feasthip_policy_set_aside needs no
+    policy state.  -> (n set aside, dX, lam, M, res): the n pairs moved behind the M - n kept, the Ritz pairs formed again."""
+    resc = np.ascontiguousarray(res, dtype=np.float64)
+    flags = np.zeros(M, dtype=np.int32)
+    n = int(_lib.load_library().feasthip_policy_set_aside(resc.ctypes.data_as(ctypes.c_void_p), int(M),
+                                                          flags.ctypes.data_as(ctypes.c_void_p)))
+    if not 0 < n < M:
+        return 0, dX, lam, M, res
+    flag = flags.astype(bool)
+    order = np.concatenate([np.nonzero(~flag)[0], np.nonzero(flag)[0], np.arange(M, rank_q)])
+    lam = lam[order]
+    dX, res = _ritz_pairs(engine, resident, dP, rank_q, np.asfortranarray(V[:, order]), lam, M - n)
+    return n, dX, lam, M - n, res
+
+
+def _initial_block(engine, Q0, N, M0, seed):
+    """The start block on the device: a device Q0 (data_ptr; only ever read), the seeded block, or the host Q0 uploaded."""
+    if Q0 is not None and hasattr(Q0, "data_ptr"):
+        return Q0
+    if Q0 is not None:
+        return engine.upload(np.asarray(Q0, dtype=np.complex128))
+    # the seeded start block is a function of (N, M0, seed): generating it on the host takes 35 ms at N = 50 000, M0 = 64 --
+    # a sixth of a default feast() call -- so an engine keeps the last one on the device for repeated calls
+    key = (int(N), int(M0), int(seed))
+    cache = getattr(engine, "_seed_cache", None)
+    if cache is not None and cache[0] == key:
+        return cache[1]
+    dQ = engine.upload(seeded_subspace(N, M0, seed))
+    try:
+        engine._seed_cache = (key, dQ)
+    except AttributeError:
+        pass
+    return dQ
+
+
+def _host_reduced_eig(engine, dP, rank_q, SA, Emin, Emax, ph):
+    """The reduced eigenproblem on the host, projected first unless resident panels gave (Sq, Aq) -> (lam, V, M) sorted
+    inside first, or None when LAPACK fails."""
+    tick = time.perf_counter
+    if SA is None:
+        t_ = tick()
+        SA = engine.project(dP, rank_q, bilinear=False, hermitize=True)
+        ph["project"] += tick() - t_
+    t_ = tick()
+    try:
+        lam_red, v_red = _reduced_hermitian_eig(*SA)
+    except Exception:
+        return None
+    ph["eig"] += tick() - t_
+    perm, M = _reorder_by_interval(lam_red, Emin, Emax, rank_q)
+    return lam_red[perm], np.asfortranarray(v_red[:, perm]), M
+
+
+def _ritz_pairs(engine, resident, dP, rank_q, V, lam, M):
+    """Ritz vectors and residuals of the host reduced solution -> (dX, res); resident panels keep the block (dX None)."""
+    if resident:
+        return None, engine.rr_ritz_resident(rank_q, V, lam, M, normalize=True, use_B=True)
+    return engine.ritz_residual(dP, rank_q, V, lam, M, normalize=True, use_B=True)
+
+
+class _LoopRecord:
+    """The Ritz values (lam_vec), residuals of the M_found pairs inside (res_vec) and epsout of the last refinement loop;
+    loops: the stats["loops"] list that gets one entry per loop, if kept."""
+
+    def __init__(self, M0, eps_tol, maxloop, dtype=float, loops=None):
+        self.lam_vec, self.res_vec = np.zeros(M0, dtype=dtype), np.zeros(M0)
+        self.epsout, self.M_found = math.inf, 0
+        self.eps_tol, self.maxloop, self.loops = eps_tol, maxloop, loops
+
+    def record(self, loop_idx, n, lam, M, res, st=None, set_aside=None):
+        """Keep the loop's n Ritz values and its M residuals -> None, or the info to stop with (0, or 5 after the last loop).
+        set_aside: pairs the host reduced solver set aside (its entry also keeps the residuals); None for the device one."""
+        self.lam_vec[:n] = lam
+        if M > 0:
+            self.res_vec[:M] = res[:M]
+            self.epsout = float(res[:M].max())
+        else:
+            self.epsout = math.inf
+        self.M_found = M
+        if self.loops is not None:
+            entry = {"loop": loop_idx, "rank": n, "M": M, "epsout": self.epsout}
+            if set_aside is not None:
+                entry["set_aside"] = set_aside
+            entry["krylov_iterations"] = st.get("krylov_iterations", 0)
+            if set_aside is not None:
+                entry["res_inside"] = np.array(res[:M], dtype=float).copy() if M > 0 else np.zeros(0)
+            self.loops.append(entry)
+        if M > 0 and self.epsout <= self.eps_tol:
+            return 0
+        if loop_idx == self.maxloop:
+            return int(FeastError.Feast_ERROR_NO_CONVERGENCE)
+        return None
+
+    def result(self, q, info, loop, stats=None, order=None):
+        """The FeastResult of the M_found pairs, in ``order`` if given; info 5 when no pair converged and nothing failed."""
+        M = self.M_found
+        if M == 0 and info == 0:
+            info = int(FeastError.Feast_ERROR_NO_CONVERGENCE)
+        lam, res = self.lam_vec[:M], self.res_vec[:M]
+        if order is not None:
+            lam, res, q = lam[order], res[order], q[:, order].copy()
+        return FeastResult(lam.copy(), q, M, res.copy(), info, self.epsout, loop, {} if stats is None else stats)
+
+
 def feast_hip_hermitian(engine, A, B, Emin, Emax, M0, fpm, *, freeze_guards_after=None, reduced_solver="host",
                         solver="direct", solver_tol=0.0,
                         solver_maxiter=500, solver_restart=30, warm_start=True, inner_rtol=None,
@@ -199,18 +476,14 @@ def feast_hip_hermitian(engine, A, B, Emin, Emax, M0, fpm, *, freeze_guards_afte
     feastdefault(fpm)
     info = check_feast_srci_input(N, M0, Emin, Emax)
     if info:
-        return FeastResult(np.zeros(0), np.zeros((N, 0), dtype=np.complex128), 0, np.zeros(0), info, math.inf, 0)
+        return _empty_result(N, info)
     rank, world = _world(engine, group)
-    iterative = solver not in ("direct", "lu", "banded")
-    tol_value = feast_tolerance(fpm) if solver_tol == 0.0 else float(solver_tol)
+    iterative = solver not in DIRECT_SOLVERS
 
     t_setup = time.perf_counter()
     if not preloaded:                            # matrices already resident on the device
         engine.set_problem(A, B)
-    if contour is None:
-        Zne, Wne = feast_contour(Emin, Emax, fpm)
-    else:
-        Zne, Wne = contour
+    Zne, Wne = feast_contour(Emin, Emax, fpm) if contour is None else contour
     engine.set_contour(Zne, Wne, 2.0)            # weight = 2*Wne[e]: src/dense/feast_dense.jl:174
     if real_projection is None:
         import scipy.sparse as _sp
@@ -219,44 +492,8 @@ def feast_hip_hermitian(engine, A, B, Emin, Emax, M0, fpm, *, freeze_guards_afte
             (not hasattr(Q0, "data_ptr") and (not np.iscomplexobj(Q0) or not np.any(np.imag(Q0))))
         real_projection = not (_isc(A) or _isc(B)) and q_real
     engine.set_real_projection(bool(real_projection))
-    if column_groups == "auto":
-        column_groups = 1
-        if iterative and world > 1:
-            for g in range(world, 0, -1):
-                if world % g == 0 and M0 // g >= 16:
-                    column_groups = g
-                    break
-    column_groups = int(column_groups)
-    if column_groups < 1 or world % column_groups != 0 or (column_groups > 1 and not iterative):
-        raise ValueError("column_groups must divide the world size and needs an iterative solver")
-    node_groups = world // column_groups
-    node_rank, col_rank = rank // column_groups, rank % column_groups
-    if (node_assignment == "balanced" or callable(node_assignment)) and node_groups > 1:
-        nodes_here = balanced_contour_points(len(Zne), node_groups)[node_rank]
-        engine.set_node_list(nodes_here)
-        count = len(nodes_here)
-        local_nodes = list(nodes_here)
-    else:
-        first, count = distribute_contour_points(len(Zne), node_groups)[node_rank]
-        engine.set_node_range(first, count)
-        local_nodes = list(range(first, first + count))
-
-    # this rank's column group (my_cg of my_cgs): fixed by the (node groups) x (column groups) grid, or re-derived every
-    # loop by split_balanced_assignment, which splits only the heaviest nodes by columns
-    my_cg, my_cgs = col_rank, column_groups
-    split_layout = (callable(node_assignment) or node_assignment == "balanced") and column_groups == 1 and world > 1 and iterative
-    node_parts = {}                                  # node -> column groups it was swept in (its iteration count arrives summed)
-
-    def column_block(ncols):
-        """[c0, c1) of this rank's column group: blocks in multiples of 16, remainder to the last."""
-        if my_cgs == 1:
-            return 0, ncols
-        per = max(16, -(-ncols // my_cgs // 16) * 16) if ncols >= 16 * my_cgs else -(-ncols // my_cgs)
-        c0 = min(ncols, my_cg * per)
-        c1 = ncols if my_cg == my_cgs - 1 else min(ncols, c0 + per)
-        return c0, c1
-    engine.set_solver(solver, rtol=tol_value, atol=tol_value if iterative else 0.0, maxit=solver_maxiter,
-                      restart=solver_restart, cache_factors=True)
+    layout = _NodeLayout(engine, len(Zne), rank, world, M0, column_groups, node_assignment, iterative)
+    _, tol_value = _configure_solver(engine, solver, fpm, solver_tol, solver_maxiter, solver_restart)
     if inner_precision not in (32, 64):
         raise ValueError("inner_precision must be 32 or 64")
     inexact = bool(iterative and warm_start and inner_rtol is not None and float(inner_rtol) > 10.0 * tol_value)
@@ -268,78 +505,47 @@ def feast_hip_hermitian(engine, A, B, Emin, Emax, M0, fpm, *, freeze_guards_afte
         engine.set_solver(solver, rtol=rt, atol=0.0, maxit=solver_maxiter, restart=solver_restart,
                           factor_precision=inner_precision)
     elif inner_precision == 32:
-        if solver in ("direct", "lu", "banded"):
+        if solver in DIRECT_SOLVERS:
             # dense LU / blocked band LU: complex64 factors + fp64 iterative refinement inside every solve
             engine.set_solver(solver, rtol=tol_value, atol=0.0, maxit=solver_maxiter, restart=solver_restart,
                               factor_precision=32, cache_factors=True)
         else:
             raise ValueError("inner_precision=32 needs a direct solver or the warm-started inexact iterative mode")
-    # -- the host policy of the inexact mode (contour steering, iteration-cap guards, last-loop tolerance) lives under the C
-    #    ABI: feasthip_policy_* (csrc/fh_policy.hpp).  Steering only where the filter is the real-projection filter.
+    eps_tol = max(feast_tolerance(fpm), float(eps_floor))      # eps_floor: sqrt(eps(Float32)) for single-precision callers
+    # -- the host policy of the inexact mode lives under the C ABI.  Steering only where the filter is the real-projection
+    #    filter.  The spurious-pair set-aside needs no policy state.
     auto_contour = bool(contour_policy == "auto" and contour is None and inexact and real_projection and int(fpm[16]) in (0, 1))
-    pol = None
-    policy_hist, policy_reach = [], []
-    if inexact:
-        import ctypes as _C
-        from . import _lib as _libmod
-        _plib = _libmod.load_library()
-        pol = _libmod.FeastHipPolicy()
-        rcp = _plib.feasthip_policy_init(_C.byref(pol), float(Emin), float(Emax), int(fpm[2]), int(fpm[16]), float(inner_rtol),
-                                         float(max(feast_tolerance(fpm), float(eps_floor))), int(solver_maxiter), int(auto_contour), int(fpm[18]))
-        if rcp != 0:
-            pol = None
+    pol = _InexactPolicy() if inexact else None
+    if pol is not None and not pol.init(Emin, Emax, fpm, inner_rtol, eps_tol, solver_maxiter, auto_contour):
+        pol = None
     if auto_contour and pol is not None:
         fpm = fpm.copy()
-        fpm[18] = int(pol.aspect)
-        Zne, Wne = feast_contour(Emin, Emax, fpm)
-        engine.set_contour(Zne, Wne, 2.0)
-        engine.set_node_list(local_nodes)         # set_contour resets the node selection to "all"
-        policy_hist.append(int(pol.aspect))
+        pol.steer(engine, Emin, Emax, fpm, layout)
+        pol.hist.append(pol.aspect)
     t_setup = time.perf_counter() - t_setup
 
-    if Q0 is not None and hasattr(Q0, "data_ptr"):
-        dQ = Q0                                   # initial subspace already resident on the device (M0 x N); only ever read
-    elif Q0 is None:
-        # the seeded start block is a function of (N, M0, seed): generating it on the host takes 35 ms at N = 50 000, M0 = 64 --
-        # a sixth of a default feast() call -- so an engine keeps the last one on the device for repeated calls
-        key = (int(N), int(M0), int(seed))
-        cache = getattr(engine, "_seed_cache", None)
-        if cache is not None and cache[0] == key:
-            dQ = cache[1]
-        else:
-            dQ = engine.upload(seeded_subspace(N, M0, seed))
-            try:
-                engine._seed_cache = (key, dQ)
-            except AttributeError:
-                pass
-    else:
-        dQ = engine.upload(np.asarray(Q0, dtype=np.complex128))
+    dQ = _initial_block(engine, Q0, N, M0, seed)
     maxloop = int(fpm[4])
-    eps_tol = max(feast_tolerance(fpm), float(eps_floor))      # eps_floor: sqrt(eps(Float32)) for single-precision callers
-    epsout, info, loop_count, M_found, active = math.inf, 0, 0, 0, M0
-    lam_vec = np.zeros(M0)
-    res_vec = np.zeros(M0)
-    ritz_lambda = None
-    inner_cap, loop_rtol = int(solver_maxiter), (float(inner_rtol) if inner_rtol is not None else None)
-    dX = None
+    info, loop_count, active, ritz_lambda, dX = 0, 0, M0, None, None
     stats = {"setup_seconds": t_setup, "krylov_iterations": 0, "spmm_calls": 0, "factorizations": 0,
-             "solve_seconds": 0.0, "loops": [], "node_iterations": [], "node_lists": [], "local_nodes": [int(v) for v in local_nodes], "phase_seconds": {"apply": 0.0, "reduce": 0.0, "ortho": 0.0,
-                                                                   "project": 0.0, "eig": 0.0, "ritz": 0.0}}
+             "solve_seconds": 0.0, "loops": [], "node_iterations": [], "node_lists": [],
+             "local_nodes": [int(v) for v in layout.local_nodes],
+             "phase_seconds": {"apply": 0.0, "reduce": 0.0, "ortho": 0.0, "project": 0.0, "eig": 0.0, "ritz": 0.0}}
     ph = stats["phase_seconds"]
     tick = time.perf_counter
+    done = _LoopRecord(M0, eps_tol, maxloop, loops=stats["loops"])
 
-    epsout_mp = math.inf                     # outer residual of the previous loop (refinement tolerance of complex64 factors)
     t_loops = time.perf_counter()
     # The refinement loop with resident panels (engine.contour_apply_resident / rr_reduce_resident / rr_ritz_resident): one
     # 64-column panel, reduced eigenproblem on the host.  The per-primitive calls remain for wide subspaces (M0 > 64), the
     # device eigensolver and engines without the resident entry points.
     resident = bool(getattr(engine, "resident", False)) and M0 <= 64 and reduced_solver != "device" and resident_panels
-    have_ritz = False
     # one BLAS thread for the whole solve; the `with` releases the process-wide limit on every way out, including an
     # exception from the engine inside the loop (FeastHipError, a poisoned handle)
     with small_lapack():
         for loop_idx in range(0, maxloop + 1):
             loop_count = loop_idx
+            # -- sweep
             t_ = tick()
             lam_guess = ritz_lambda if (iterative and warm_start) else None
             col_mask = None
@@ -349,63 +555,36 @@ def feast_hip_hermitian(engine, A, B, Emin, Emax, M0, fpm, *, freeze_guards_afte
                 col_mask = np.array([1 if Emin <= lam_guess[c] <= Emax else 0 for c in range(active)], dtype=np.int32)
             if hasattr(engine, "set_column_mask"):
                 engine.set_column_mask(col_mask)                    # one-shot: consumed by the sweep below
-            if my_cgs > 1:
-                c0, c1 = column_block(active)
+            if layout.my_cgs > 1:
+                c0, c1 = layout.column_block(active)
                 engine.set_column_block(c0, c1 - c0)
             if inner_precision == 32 and not iterative:
                 # inexact FEAST on complex64 factors: the solves are refined only as far as the current outer residual needs
                 # (no refinement in the first loop; the last loops reach the full tolerance)
-                ref_tol = 1.0 if not math.isfinite(epsout_mp) else min(1.0, max(tol_value, 1e-2 * epsout_mp))
+                ref_tol = 1.0 if not math.isfinite(done.epsout) else min(1.0, max(tol_value, 1e-2 * done.epsout))
                 engine.set_solver(solver, rtol=ref_tol, atol=0.0, maxit=solver_maxiter, restart=solver_restart,
                                   factor_precision=32, cache_factors=True)
-            # one call = this rank's (nodes x column block) sweep + the packed all-reduce inside the C ABI:
-            # dP and status come back summed over all ranks (status indexed by contour node when world > 1)
-            if resident:
-                # resident panels: Q_proj stays in the library in the kernels' layout; after the first loop the subspace is
-                # the Ritz block the previous loop left there (dQ is None)
-                dP = None
-                status, st = engine.contour_apply_resident(dQ, active, lam_guess)
-            else:
-                dP, status, st = engine.contour_apply(dQ, active, lam_guess)
-            if my_cgs > 1:
+            # one call = this rank's (nodes x column block) sweep + the packed all-reduce inside the C ABI: dP and status
+            # come back summed over all ranks (status indexed by contour node when world > 1).  Resident panels: Q_proj
+            # stays in the library in the kernels' layout; after the first loop the subspace is the Ritz block the
+            # previous loop left there (dQ is None)
+            fail, (dP, status, st) = _sweep(engine, dQ, active, world, layout.count, stats, lam_guess, resident=resident)
+            if layout.my_cgs > 1:
                 engine.set_column_block(0, -1)
             ph["apply"] += tick() - t_
-            stats["krylov_iterations"] += st.get("krylov_iterations", 0)
             stats["spmm_calls"] += st.get("spmm_calls", 0)
-            stats["factorizations"] += st.get("factorizations", 0)
-            stats["solve_seconds"] += st.get("seconds_solve", 0.0)
             if hasattr(engine, "last_node_iterations"):
-                stats["node_iterations"].append([int(v) for v in engine.last_node_iterations(count)])
-                stats["node_lists"].append([int(v) for v in local_nodes])
-            local_fail = int(np.max(status)) if (world > 1 or count > 0) else 0
-            if split_layout and loop_idx >= 1 and hasattr(engine, "last_global_node_iterations"):
-                # node-only layout asked for: re-derive it from the measured iteration counts and let the heaviest nodes be
-                # split by columns over several ranks when that lowers the largest share (contour.split_balanced_assignment);
-                # the counts arrived in the tail of the packed all-reduce, summed over the ranks that swept a node
-                costs = [float(v) / node_parts.get(e, 1) for e, v in enumerate(engine.last_global_node_iterations())]
-                layout = node_assignment(costs, world) if callable(node_assignment) else split_balanced_assignment(costs, world, ncols=active)
-                nodes_here, my_cg, my_cgs = layout[rank]
-                node_parts = {e: k for nodes, _g, k in layout for e in nodes}
-                stats["layout"] = [(list(map(int, nodes)), int(g), int(k)) for nodes, g, k in layout]
-                if list(nodes_here) != list(local_nodes):
-                    engine.set_node_list(nodes_here)
-                    count, local_nodes = len(nodes_here), list(nodes_here)
-                    stats["local_nodes"] = [int(v) for v in local_nodes]
-            elif (node_assignment == "balanced" and node_groups > 1 and iterative and hasattr(engine, "last_global_node_iterations")
-                    and loop_idx >= 1):
-                # re-balance the node groups from the iteration counts the sweep just measured (they arrived in the tail of the
-                # packed all-reduce and are identical on every rank): the slow near-axis nodes no longer share a group by accident
-                nodes_here = cost_balanced_contour_points(engine.last_global_node_iterations(), node_groups)[node_rank]
-                if list(nodes_here) != list(local_nodes):
-                    engine.set_node_list(nodes_here)
-                    count, local_nodes = len(nodes_here), list(nodes_here)
-                    stats["local_nodes"] = [int(v) for v in local_nodes]
-            if local_fail == 8 or (local_fail == 5 and not warm_start):
-                # direct: singular shift -> info 8 (src/dense/feast_dense.jl:199-203);
-                # reference GMRES failure -> info 5 (src/dense/feast_dense.jl:221-225)
-                info = int(FeastError.Feast_ERROR_LAPACK if local_fail == 8 else FeastError.Feast_ERROR_NO_CONVERGENCE)
+                stats["node_iterations"].append([int(v) for v in engine.last_node_iterations(layout.count)])
+                stats["node_lists"].append([int(v) for v in layout.local_nodes])
+            layout.rebalance(engine, loop_idx, active, stats)
+            # direct: singular shift -> info 8 (src/dense/feast_dense.jl:199-203); reference GMRES failure -> info 5
+            # (src/dense/feast_dense.jl:221-225).  Warm-started solves go on past a Krylov failure (5): the next loop
+            # starts from where this one stopped.
+            if fail == 8 or (fail == 5 and not warm_start):
+                info = int(FeastError.Feast_ERROR_LAPACK if fail == 8 else FeastError.Feast_ERROR_NO_CONVERGENCE)
                 break
 
+            # -- reduce
             t_ = tick()
             if resident:
                 # _feast_qr_compress! and the projections in one call: rank + (Q_o^H A Q_o, Q_o^H B Q_o)
@@ -417,151 +596,87 @@ def feast_hip_hermitian(engine, A, B, Emin, Emax, M0, fpm, *, freeze_guards_afte
             if rank_q == 0:
                 info = int(FeastError.Feast_ERROR_NO_CONVERGENCE)
                 break
+
+            # -- reduced eigenproblem, Ritz pairs and residuals: on the device in one call, or on the host
+            rr = None
             if reduced_solver == "device" and rank_q <= 64 and trace is None and hasattr(engine, "rayleigh_ritz"):
                 # project + reduced eigenproblem (Jacobi in LDS) + reorder + Ritz vectors + residuals in one call;
                 # None: reduced B not positive definite -> the host path below (general fallback of the reference)
                 t_ = tick()
                 rr = engine.rayleigh_ritz(dP, rank_q, Emin, Emax, use_B=True)
                 ph["ritz"] += tick() - t_
-                if rr is not None:
-                    dX, lam_sorted, M, res = rr
-                    if M == 0 and not (iterative and warm_start):
-                        info = int(FeastError.Feast_ERROR_NO_CONVERGENCE)
-                        break
-                    lam_vec[:rank_q] = lam_sorted
-                    if M > 0:
-                        res_vec[:M] = res
-                        epsout = float(res.max())
-                    else:
-                        epsout = math.inf
-                    epsout_mp = epsout
-                    M_found = M
-                    stats["loops"].append({"loop": loop_idx, "rank": rank_q, "M": M, "epsout": epsout,
-                                           "krylov_iterations": st.get("krylov_iterations", 0)})
-                    if M > 0 and epsout <= eps_tol:
-                        break
-                    if loop_idx == maxloop:
-                        info = int(FeastError.Feast_ERROR_NO_CONVERGENCE)
-                        break
-                    active = rank_q
-                    dQ = dX
-                    ritz_lambda = lam_sorted.copy()
-                    continue
-            if not resident:
+            if rr is not None:
+                dX, lam_sorted, M, res = rr
+                if M == 0 and not (iterative and warm_start):
+                    info = int(FeastError.Feast_ERROR_NO_CONVERGENCE)
+                    break
+            else:
+                red = _host_reduced_eig(engine, dP, rank_q, (Sq, Aq) if resident else None, Emin, Emax, ph)
+                if red is None:
+                    info = int(FeastError.Feast_ERROR_LAPACK)
+                    break
+                lam_sorted, V_sorted, M = red
+                if trace is not None:
+                    trace.append({"loop": loop_idx, "rank": rank_q, "M": M, "lambda": lam_sorted.copy(), "status": status.copy(),
+                                  "stats": dict(st),
+                                  "node_iterations": engine.last_node_iterations(layout.count) if hasattr(engine, "last_node_iterations") else None,
+                                  "column_iterations": engine.last_column_iterations(layout.count, active) if hasattr(engine, "last_column_iterations") else None})
+                if M == 0 and not (iterative and warm_start):
+                    info = int(FeastError.Feast_ERROR_NO_CONVERGENCE)
+                    break
                 t_ = tick()
-                Sq, Aq = engine.project(dP, rank_q, bilinear=False, hermitize=True)
-                ph["project"] += tick() - t_
-            t_ = tick()
-            try:
-                lam_red, v_red = _reduced_hermitian_eig(Sq, Aq)
-            except Exception:
-                info = int(FeastError.Feast_ERROR_LAPACK)
+                dX, res = _ritz_pairs(engine, resident, dP, rank_q, V_sorted, lam_sorted, M)
+                n_spurious = 0
+                if inexact and spurious_filter and loop_idx >= 1 and M > 1:      # solver noise inside the interval
+                    n_spurious, dX, lam_sorted, M, res = _policy_set_aside(engine, resident, dP, rank_q, V_sorted, lam_sorted,
+                                                                           M, dX, res)
+                ph["ritz"] += tick() - t_
+
+            # -- stop test
+            # (the device reduced solver sets no pair aside)
+            stop = done.record(loop_idx, rank_q, lam_sorted, M, res, st, set_aside=None if rr is not None else n_spurious)
+            if stop is not None:
+                info = stop
                 break
-            ph["eig"] += tick() - t_
-            perm, M = _reorder_by_interval(lam_red, Emin, Emax, rank_q)
-            lam_sorted = lam_red[perm]
-            V_sorted = np.asfortranarray(v_red[:, perm])
-            if trace is not None:
-                trace.append({"loop": loop_idx, "rank": rank_q, "M": M, "lambda": lam_sorted.copy(), "status": status.copy(),
-                              "stats": dict(st),
-                              "node_iterations": engine.last_node_iterations(count) if hasattr(engine, "last_node_iterations") else None,
-                              "column_iterations": engine.last_column_iterations(count, active) if hasattr(engine, "last_column_iterations") else None})
-            if M == 0 and not (iterative and warm_start):
-                info = int(FeastError.Feast_ERROR_NO_CONVERGENCE)
-                break
-            t_ = tick()
-            if resident:
-                dX, res = None, engine.rr_ritz_resident(rank_q, V_sorted, lam_sorted, M, normalize=True, use_B=True)
-            else:
-                dX, res = engine.ritz_residual(dP, rank_q, V_sorted, lam_sorted, M, normalize=True, use_B=True)
-            n_spurious = 0
-            if inexact and spurious_filter and loop_idx >= 1 and M > 1:
-                # Inexact inner solves leave solver noise in the guard columns.  Its Ritz values are arbitrary; one that
-                # lands inside the interval has an O(1) residual that never contracts and would hold epsout up forever
-                # (variant A has no spurious-pair removal; with exact solves the guard columns are true eigen-directions
-                # and stay outside).  A pair is set aside when its relative residual is > 0.1 AND > 100x the smallest
-                # residual of the pairs inside: a true pair inside the interval sees a filter value >= 1/2 and contracts
-                # with the others, it cannot sit at 10 % while another pair is 100x ahead.  Set-aside pairs stay in the
-                # subspace and are re-examined every loop (measured on a random pencil: the ten true pairs contract by
-                # ~1e-2 per loop while one to three noise pairs stay at residual 1).
-                import ctypes as _C
-                resc = np.ascontiguousarray(res, dtype=np.float64)
-                flags_i = np.zeros(M, dtype=np.int32)
-                n_spurious = int(_plib.feasthip_policy_set_aside(resc.ctypes.data_as(_C.c_void_p), int(M), flags_i.ctypes.data_as(_C.c_void_p)))
-                flag = flags_i.astype(bool)
-                if 0 < n_spurious < M:
-                    order = np.concatenate([np.nonzero(~flag)[0], np.nonzero(flag)[0], np.arange(M, rank_q)])
-                    lam_sorted = lam_sorted[order]
-                    V_sorted = np.asfortranarray(V_sorted[:, order])
-                    M = M - n_spurious
-                    if resident:
-                        res = engine.rr_ritz_resident(rank_q, V_sorted, lam_sorted, M, normalize=True, use_B=True)
-                    else:
-                        dX, res = engine.ritz_residual(dP, rank_q, V_sorted, lam_sorted, M, normalize=True, use_B=True)
-                else:
-                    n_spurious = 0
-            ph["ritz"] += tick() - t_
-            have_ritz = True
-            lam_vec[:rank_q] = lam_sorted
-            if M > 0:
-                res_vec[:M] = res
-                epsout = float(res.max())
-            else:
-                epsout = math.inf
-            epsout_mp = epsout
-            M_found = M
-            stats["loops"].append({"loop": loop_idx, "rank": rank_q, "M": M, "epsout": epsout, "set_aside": n_spurious,
-                                   "krylov_iterations": st.get("krylov_iterations", 0),
-                                   "res_inside": np.array(res[:M], dtype=float).copy() if M > 0 else np.zeros(0)})
-            if M > 0 and epsout <= eps_tol:
-                break
-            if loop_idx == maxloop:
-                info = int(FeastError.Feast_ERROR_NO_CONVERGENCE)
-                break
-            if abort_check is not None and world == 1 and abort_check(loop_idx, [l["epsout"] for l in stats["loops"]],
-                                                                      time.perf_counter() - t_loops):
-                # the caller has a cheaper way to finish (api.feast: the sparse direct solver): stop here
-                info = int(FeastError.Feast_ERROR_NO_CONVERGENCE)
-                stats["aborted"] = True
-                break
-            if pol is not None:
-                # one call decides the next sweep: iteration cap (stagnation guard; capped nodes under the contour policy), inner
-                # tolerance (relaxed when the outer tolerance is within reach), and -- under the contour policy -- fpm[18]
-                import ctypes as _C
-                ritz_c = np.ascontiguousarray(lam_sorted[:rank_q], dtype=np.float64)
-                prev_aspect, prev_cap, prev_rtol = int(pol.aspect), int(pol.inner_cap), float(pol.next_rtol)
-                _plib.feasthip_policy_update(_C.byref(pol), float(epsout), int(M), int(int(np.max(status)) == 5),
-                                             ritz_c.ctypes.data_as(_C.c_void_p), int(rank_q))
-                if int(pol.inner_cap) != prev_cap or float(pol.next_rtol) != prev_rtol:
-                    inner_cap, loop_rtol = int(pol.inner_cap), float(pol.next_rtol)
-                    engine.set_solver(solver, rtol=loop_rtol, atol=0.0, maxit=inner_cap, restart=solver_restart,
-                                      factor_precision=inner_precision)
-                    if inner_cap != int(solver_maxiter):
-                        stats["inner_cap"] = inner_cap
-                if auto_contour:
-                    if int(pol.aspect) != prev_aspect:
-                        fpm[18] = int(pol.aspect)
-                        Zne, Wne = feast_contour(Emin, Emax, fpm)
-                        engine.set_contour(Zne, Wne, 2.0)
-                        engine.set_node_list(local_nodes)
-                    policy_hist.append(int(pol.aspect))
-                    policy_reach.append(None if pol.last_reach < 0 else round(float(pol.last_reach), 3))
+            if rr is None:                          # the device reduced solver has neither the abort test nor the policy
+                if abort_check is not None and world == 1 and abort_check(loop_idx, [l["epsout"] for l in stats["loops"]],
+                                                                          time.perf_counter() - t_loops):
+                    # the caller has a cheaper way to finish (api.feast: the sparse direct solver): stop here
+                    info = int(FeastError.Feast_ERROR_NO_CONVERGENCE)
+                    stats["aborted"] = True
+                    break
+                if pol is not None:
+                    # one call decides the next sweep: iteration cap (stagnation guard; capped nodes under the contour
+                    # policy), inner tolerance (relaxed when the outer tolerance is within reach), and -- under the contour
+                    # policy -- fpm[18]
+                    new_aspect, new_solve = pol.update(done.epsout, M, int(np.max(status)) == 5, lam_sorted, rank_q)
+                    if new_solve:
+                        engine.set_solver(solver, rtol=pol.next_rtol, atol=0.0, maxit=pol.inner_cap, restart=solver_restart,
+                                          factor_precision=inner_precision)
+                        if pol.inner_cap != int(solver_maxiter):
+                            stats["inner_cap"] = pol.inner_cap
+                    if auto_contour:
+                        if new_aspect:
+                            pol.steer(engine, Emin, Emax, fpm, layout)
+                        pol.hist.append(pol.aspect)
+                        pol.reach.append(None if pol.last_reach < 0 else round(pol.last_reach, 3))
+
+            # -- next loop
             active = rank_q
             dQ = dX                                   # Q_basis[:, 1:rank] = solutions[:, 1:rank]
             ritz_lambda = lam_sorted.copy()
 
     if auto_contour and pol is not None:
-        stats["contour_policy"] = {"fpm18_per_loop": policy_hist, "cap": int(pol.cap), "reach": policy_reach}
+        stats["contour_policy"] = {"fpm18_per_loop": pol.hist, "cap": pol.cap, "reach": pol.reach}
     if hasattr(engine, "set_column_mask"):
         engine.set_column_mask(None)
-    if M_found == 0 and info == 0:
-        info = int(FeastError.Feast_ERROR_NO_CONVERGENCE)
+    M_found = done.M_found
     # only the M converged Ritz vectors cross PCIe (the block is column-major: the first M rows of the tensor)
-    if resident and have_ritz and M_found > 0:
+    if resident and M_found > 0:
         q = engine.download(engine.export_resident(M_found), M_found)
     else:
         q = engine.download(dX[:M_found], M_found) if (dX is not None and M_found > 0) else np.zeros((N, 0), dtype=np.complex128)
-    return FeastResult(lam_vec[:M_found].copy(), q, M_found, res_vec[:M_found].copy(), info, epsout, loop_count, stats)
+    return done.result(q, info, loop_count, stats)
 
 
 ESTIMATE_SEED = 20260515          # default seed of the estimate's Rademacher block (the package seed)
@@ -583,18 +698,12 @@ def feast_hip_estimate(engine, A, B, Zne, Wne, weight_scale, m, *, general=False
 
     Returns (info, estimate): info 0 with the dict {mean, stderr, samples, nodes, solver, seed, seconds}, or the node
     status 5 / 8 of a failed node and None."""
-    rank, world = _world(engine, group)
     t0 = time.perf_counter()
-    engine.set_problem(A, B)
-    engine.set_contour(Zne, Wne, float(weight_scale))
-    engine.set_real_projection(not general)
-    first, count = distribute_contour_points(len(Zne), world)[rank]
-    engine.set_node_range(first, count)
-    iterative = solver not in ("direct", "lu", "banded")
+    world, count = _setup_sweep(engine, group, A, B, Zne, Wne, float(weight_scale), not general)
     engine.set_solver(solver, rtol=float(solver_tol), atol=0.0, maxit=int(solver_maxiter), restart=int(solver_restart),
                       cache_factors=True)
     samples, status, _st = engine.estimate_count(m, seed)
-    fail = int(np.max(status)) if (world > 1 or count > 0) else 0
+    fail = _failure(status, world, count)
     if fail:
         return (int(FeastError.Feast_ERROR_LAPACK) if fail == 8 else int(FeastError.Feast_ERROR_NO_CONVERGENCE)), None
     t = samples if general else samples.real
@@ -602,7 +711,7 @@ def feast_hip_estimate(engine, A, B, Zne, Wne, weight_scale, m, *, general=False
     stderr = float(np.std(t, ddof=1) / math.sqrt(m)) if m > 1 else math.inf
     est = {"mean": mean, "stderr": stderr, "samples": t.copy(), "nodes": len(Zne), "solver": solver, "seed": int(seed),
            "seconds": time.perf_counter() - t0}
-    if iterative:
+    if solver not in DIRECT_SOLVERS:
         est["solver_tol"] = float(solver_tol)
     return 0, est
 
@@ -613,28 +722,17 @@ def feast_hip_general(engine, A, B, Emid, r, M0, fpm, *, solver="direct", solver
     without B): src/kernel/feast_kernel.jl:752-950 driven as in src/dense/feast_dense.jl:468-584."""
     N = A.shape[0]
     feastdefault(fpm)
-    if N <= 0:
-        return FeastResult(np.zeros(0, complex), np.zeros((N, 0), complex), 0, np.zeros(0), 1, math.inf, 0)
-    if M0 <= 0 or M0 > N:
-        return FeastResult(np.zeros(0, complex), np.zeros((N, 0), complex), 0, np.zeros(0), 2, math.inf, 0)
-    if not r > 0:
-        return FeastResult(np.zeros(0, complex), np.zeros((N, 0), complex), 0, np.zeros(0), 4, math.inf, 0)
-    rank, world = _world(engine, group)
-    iterative = solver not in ("direct", "lu", "banded")
-    tol_value = feast_tolerance(fpm) if solver_tol == 0.0 else float(solver_tol)
-    Ac = A.astype(np.complex128) if not np.iscomplexobj(A) else A
-    Bc = None if B is None else (B.astype(np.complex128) if not np.iscomplexobj(B) else B)
-    engine.set_problem(Ac, Bc)
+    info = _check_circle_input(N, M0, r)
+    if info:
+        return _empty_result(N, info, complex_lambda=True)
+    Ac, Bc = _complex_pencil(A, B)
     # caller-supplied nodes/weights: the reference's "x" drivers (feast_gcsrgvx!/feast_gegvx!, src/sparse/feast_sparse.jl:1008-)
     Zne, Wne = feast_gcontour(Emid, r, fpm) if contour is None else contour
-    engine.set_contour(Zne, Wne, 1.0)
-    engine.set_real_projection(False)
-    first, count = distribute_contour_points(len(Zne), world)[rank]
-    engine.set_node_range(first, count)
-    if inner_precision == 32 and solver not in ("direct", "lu", "banded"):
+    world, count = _setup_sweep(engine, group, Ac, Bc, Zne, Wne, 1.0, False)
+    if inner_precision == 32 and solver not in DIRECT_SOLVERS:
         raise ValueError("inner_precision=32 (complex64 LU factors + fp64 refinement) needs a direct solver")
-    engine.set_solver(solver, rtol=tol_value, atol=tol_value if iterative else 0.0, maxit=solver_maxiter,
-                      restart=solver_restart, cache_factors=True, factor_precision=32 if inner_precision == 32 else 64)
+    _configure_solver(engine, solver, fpm, solver_tol, solver_maxiter, solver_restart,
+                      factor_precision=32 if inner_precision == 32 else 64)
     Q_host = seeded_subspace(N, M0, seed) if Q0 is None else np.asarray(Q0, dtype=np.complex128)
     dQ = engine.upload(Q_host)
     eps_tol = max(feast_tolerance(fpm), float(eps_floor))
@@ -648,29 +746,19 @@ def feast_hip_general(engine, A, B, Emid, r, M0, fpm, *, solver="direct", solver
             ref_tol = 1.0 if not math.isfinite(epsout) else min(1.0, max(1e-14, 1e-2 * epsout))
             engine.set_solver(solver, rtol=ref_tol, atol=0.0, maxit=solver_maxiter, restart=solver_restart,
                               cache_factors=True, factor_precision=32)
-        dq, status, st = engine.contour_apply(dQ, M0, None)
-        stats["krylov_iterations"] += st.get("krylov_iterations", 0)
-        stats["factorizations"] += st.get("factorizations", 0)
-        stats["solve_seconds"] += st.get("seconds_solve", 0.0)
-        fail = int(np.max(status)) if (world > 1 or count > 0) else 0     # summed over the ranks inside the call
+        fail, (dq, status, st) = _sweep(engine, dQ, M0, world, count, stats)
         if fail:
-            return FeastResult(np.zeros(0, complex), np.zeros((N, 0), complex), 0, np.zeros(0),
-                               int(FeastError.Feast_ERROR_LAPACK if fail == 8 else FeastError.Feast_ERROR_NO_CONVERGENCE),
-                               math.inf, loop, stats)
+            return _empty_result(N, FeastError.Feast_ERROR_LAPACK if fail == 8 else FeastError.Feast_ERROR_NO_CONVERGENCE,
+                                 loop, complex_lambda=True, stats=stats)
         Aq, Sq = engine.project(dq, M0, bilinear=False, hermitize=False)   # Aq = q^H A q, Sq = q^H B q
         try:
             with small_lapack():
                 lam_red, v_red = sla.eig(Aq, Sq)                            # feast_kernel.jl:812
         except Exception:
-            return FeastResult(np.zeros(0, complex), np.zeros((N, 0), complex), 0, np.zeros(0),
-                               int(FeastError.Feast_ERROR_LAPACK), math.inf, loop, stats)
-        ins = [i for i in range(M0) if feast_inside_gcontour(lam_red[i], Emid, r, fpm)]
-        M = len(ins)
+            return _empty_result(N, FeastError.Feast_ERROR_LAPACK, loop, complex_lambda=True, stats=stats)
+        perm, M = _reorder_by_contour(lam_red, Emid, r, fpm, M0)
         if M == 0:
-            return FeastResult(np.zeros(0, complex), np.zeros((N, 0), complex), 0, np.zeros(0),
-                               int(FeastError.Feast_ERROR_NO_CONVERGENCE), math.inf, loop, stats)
-        inset = set(ins)
-        perm = np.array(ins + [i for i in range(M0) if i not in inset], dtype=np.int64)
+            return _empty_result(N, FeastError.Feast_ERROR_NO_CONVERGENCE, loop, complex_lambda=True, stats=stats)
         lam = lam_red[perm]
         V = np.asfortranarray(v_red[:, perm])
         # normalise ALL M0 columns (feast_kernel.jl:864-876); residual WITHOUT B (:899-906)
@@ -698,47 +786,26 @@ def feast_hip_complex_symmetric(engine, A, B, Emid, r, M0, fpm, *, solver="direc
     import scipy.sparse as _sp
     N = A.shape[0]
     feastdefault(fpm)
-    empty = lambda code, loop=0: FeastResult(np.zeros(0, complex), np.zeros((N, 0), complex), 0, np.zeros(0), code, math.inf, loop)
-    if N <= 0:
-        return empty(1)
-    if M0 <= 0 or M0 > N:
-        return empty(2)
-    if not r > 0:
-        return empty(4)
+    info = _check_circle_input(N, M0, r)
+    if info:
+        return _empty_result(N, info, complex_lambda=True)
     for name, Mx in (("A", A), ("B", B)):
         if Mx is None:
             continue
         sym = (abs(Mx - Mx.T).max() == 0) if _sp.issparse(Mx) else np.array_equal(Mx, Mx.T)
         if not sym:                                          # check_complex_symmetric, feast_dense.jl:1038
             raise ValueError(f"Matrix {name} must be complex symmetric ({name} == transpose({name}))")
-    rank_, world = _world(engine, group)
-    iterative = solver not in ("direct", "lu", "banded")
-    tol_value = feast_tolerance(fpm) if solver_tol == 0.0 else float(solver_tol)
-    Ac = A.astype(np.complex128) if not np.iscomplexobj(A) else A
-    Bc = None if B is None else (B.astype(np.complex128) if not np.iscomplexobj(B) else B)
-    engine.set_problem(Ac, Bc)
+    Ac, Bc = _complex_pencil(A, B)
     Zne, Wne = feast_gcontour(Emid, r, fpm)
-    engine.set_contour(Zne, Wne, 1.0)
-    engine.set_real_projection(False)
-    first, count = distribute_contour_points(len(Zne), world)[rank_]
-    engine.set_node_range(first, count)
-    engine.set_solver(solver, rtol=tol_value, atol=tol_value if iterative else 0.0, maxit=solver_maxiter,
-                      restart=solver_restart, cache_factors=True)
+    world, count = _setup_sweep(engine, group, Ac, Bc, Zne, Wne, 1.0, False)
+    _configure_solver(engine, solver, fpm, solver_tol, solver_maxiter, solver_restart)
     dQ = engine.upload(seeded_subspace(N, M0, seed, complex_values=True) if Q0 is None else np.asarray(Q0, dtype=np.complex128))
-    eps_tol = feast_tolerance(fpm)
-    maxloop = int(fpm[4])
-    info, epsout, M_found, active, loop_count = 0, math.inf, 0, M0, 0
-    lam_vec = np.zeros(M0, dtype=np.complex128)
-    res_vec = np.zeros(M0)
-    dX = None
+    done = _LoopRecord(M0, feast_tolerance(fpm), int(fpm[4]), dtype=np.complex128)
+    info, active, loop_count, dX = 0, M0, 0, None
     stats = {"krylov_iterations": 0, "factorizations": 0, "solve_seconds": 0.0}
-    for loop_idx in range(0, maxloop + 1):
+    for loop_idx in range(0, done.maxloop + 1):
         loop_count = loop_idx
-        dP, status, st = engine.contour_apply(dQ, active, None)
-        stats["krylov_iterations"] += st.get("krylov_iterations", 0)
-        stats["factorizations"] += st.get("factorizations", 0)
-        stats["solve_seconds"] += st.get("seconds_solve", 0.0)
-        fail = int(np.max(status)) if (world > 1 or count > 0) else 0
+        fail, (dP, status, st) = _sweep(engine, dQ, active, world, count, stats)
         if fail:
             info = int(FeastError.Feast_ERROR_LAPACK if fail == 8 else FeastError.Feast_ERROR_NO_CONVERGENCE)
             break
@@ -753,35 +820,23 @@ def feast_hip_complex_symmetric(engine, A, B, Emid, r, M0, fpm, *, solver="direc
         except Exception:
             info = int(FeastError.Feast_ERROR_LAPACK)
             break
-        ins = [i for i in range(rank_q) if feast_inside_gcontour(lam_red[i], Emid, r, fpm)]
-        M = len(ins)
+        perm, M = _reorder_by_contour(lam_red, Emid, r, fpm, rank_q)
         if M == 0:
             info = int(FeastError.Feast_ERROR_NO_CONVERGENCE)
             break
-        inset = set(ins)
-        perm = np.array(ins + [i for i in range(rank_q) if i not in inset], dtype=np.int64)
         lam_sorted = lam_red[perm]
         V = np.asfortranarray(v_red[:, perm])
         dX, res = engine.ritz_residual(dP, rank_q, V, lam_sorted, rank_q, normalize=True, use_B=True)
-        lam_vec[:rank_q] = lam_sorted
-        res_vec[:M] = res[:M]
-        epsout = float(res[:M].max())
-        M_found = M
-        if epsout <= eps_tol:
-            break
-        if loop_idx == maxloop:
-            info = int(FeastError.Feast_ERROR_NO_CONVERGENCE)
+        stop = done.record(loop_idx, rank_q, lam_sorted, M, res)
+        if stop is not None:
+            info = stop
             break
         active = rank_q
         dQ = dX
-    if M_found == 0 and info == 0:
-        info = int(FeastError.Feast_ERROR_NO_CONVERGENCE)
-    if dX is None or M_found == 0:
-        return FeastResult(np.zeros(0, complex), np.zeros((N, 0), complex), 0, np.zeros(0), info, epsout, loop_count, stats)
-    X = engine.download(dX, M_found)
-    order = sorted(range(M_found), key=lambda i: abs(lam_vec[i]) ** 2)         # feast_sort_general!
-    return FeastResult(lam_vec[:M_found][order].copy(), X[:, order].copy(), M_found, res_vec[:M_found][order].copy(),
-                       info, epsout, loop_count, stats)
+    M_found = done.M_found
+    X = engine.download(dX, M_found) if M_found > 0 else np.zeros((N, 0), complex)
+    order = sorted(range(M_found), key=lambda i: abs(done.lam_vec[i]) ** 2)         # feast_sort_general!
+    return done.result(X, info, loop_count, stats, order)
 
 
 def pfeast_hip_moments(engine, A, B, Emin, Emax, M0, fpm, *, group=None, Q0=None, seed=20260515):
@@ -801,15 +856,10 @@ def pfeast_hip_moments(engine, A, B, Emin, Emax, M0, fpm, *, group=None, Q0=None
     feastdefault(fpm)
     info = check_feast_srci_input(N, M0, Emin, Emax)
     if info:
-        return FeastResult(np.zeros(0), np.zeros((N, 0)), 0, np.zeros(0), info, math.inf, 0)
-    rank, world = _world(engine, group)
+        return _empty_result(N, info, real_q=True)
     Bm = B if B is not None else (_sp.identity(N, format="csr") if _sp.issparse(A) else np.eye(N))
-    engine.set_problem(A, Bm)
     Zne, Wne = feast_contour(Emin, Emax, fpm)
-    engine.set_contour(Zne, Wne, 2.0)
-    engine.set_real_projection(True)                      # real.(...) of feast_parallel.jl:38-55
-    first, count = distribute_contour_points(len(Zne), world)[rank]
-    engine.set_node_range(first, count)
+    _setup_sweep(engine, group, A, Bm, Zne, Wne, 2.0, True)      # real.(...) of feast_parallel.jl:38-55
     engine.set_solver("direct" if not _sp.issparse(A) else "bicgstab", rtol=1e-13, atol=0.0, maxit=5000)
     work = np.real(seeded_subspace(N, M0, seed)) if Q0 is None else np.real(np.asarray(Q0))
     eps_tol = feast_tolerance(fpm)
@@ -837,7 +887,7 @@ def pfeast_hip_moments(engine, A, B, Emin, Emax, M0, fpm, *, group=None, Q0=None
         lam = np.asarray(lam_red)[perm]
         q = q[:, perm]
         if M == 0:
-            return FeastResult(np.zeros(0), np.zeros((N, 0)), 0, np.zeros(0), int(FeastError.Feast_ERROR_NO_CONVERGENCE), 0.0, loop)
+            return _empty_result(N, FeastError.Feast_ERROR_NO_CONVERGENCE, loop, real_q=True, epsout=0.0)
         for j in range(M):
             nrm = np.linalg.norm(q[:, j])
             if nrm > 0:
@@ -866,23 +916,15 @@ def feast_hip_symmetric_kernel(engine, A, B, Emin, Emax, M0, fpm, *, solver="dir
     with no normalisation (:183-187), stable inside-first reorder (:189-215), residual ||A q - lambda q|| / max(|lambda|, 1)
     WITHOUT B (:244-252: generalized problems therefore run all fpm[4] loops and return info = 0), stop test with
     loop >= fpm[4] (:258), all M0 Ritz vectors carried to the next loop (:269), feast_sort! at the end."""
-    import scipy.sparse as _sp
     N = A.shape[0]
     feastdefault(fpm)
     info = check_feast_srci_input(N, M0, Emin, Emax)
     if info:
-        return FeastResult(np.zeros(0), np.zeros((N, 0)), 0, np.zeros(0), info, 0.0, 0)
-    rank, world = _world(engine, group)
-    engine.set_problem(A, B)
+        return _empty_result(N, info, real_q=True, epsout=0.0)
     Zne, Wne = feast_contour(Emin, Emax, fpm) if contour is None else contour
-    engine.set_contour(Zne, Wne, 2.0)                     # weight = 2 * Wne[e], feast_kernel.jl:150
-    engine.set_real_projection(True)                      # real(...) after the sweep, :166-169
-    first, count = distribute_contour_points(len(Zne), world)[rank]
-    engine.set_node_range(first, count)
-    iterative = solver not in ("direct", "lu", "banded")
-    tol_value = feast_tolerance(fpm) if solver_tol == 0.0 else float(solver_tol)
-    engine.set_solver(solver, rtol=tol_value, atol=tol_value if iterative else 0.0, maxit=solver_maxiter,
-                      restart=solver_restart, cache_factors=True)
+    # weight = 2 * Wne[e] (feast_kernel.jl:150); real(...) after the sweep (:166-169)
+    world, count = _setup_sweep(engine, group, A, B, Zne, Wne, 2.0, True)
+    _configure_solver(engine, solver, fpm, solver_tol, solver_maxiter, solver_restart)
     if Q0 is not None:                                    # fpm[5] = 1: the caller's columns, normalised (:68-80)
         work = np.array(np.real(Q0), dtype=np.float64)
         nrm = np.linalg.norm(work, axis=0)
@@ -893,16 +935,14 @@ def feast_hip_symmetric_kernel(engine, A, B, Emin, Emax, M0, fpm, *, solver="dir
     eps_tol = feast_tolerance(fpm)
     maxloop = int(fpm[4])
     stats = {"krylov_iterations": 0, "factorizations": 0, "solve_seconds": 0.0}
-    empty = lambda code, loop: FeastResult(np.zeros(0), np.zeros((N, 0)), 0, np.zeros(0), int(code), 0.0, loop, stats)
+    empty = lambda code, loop: _empty_result(N, code, loop, real_q=True, epsout=0.0, stats=stats)
     loop = 0
     with small_lapack():
         while True:
             dQ = engine.upload(work)
-            dP, status, st, Aq, Sq = engine.contour_apply(dQ, M0, None, want_moments=True)
-            for k_, s_ in (("krylov_iterations", "krylov_iterations"), ("factorizations", "factorizations"), ("solve_seconds", "seconds_solve")):
-                stats[k_] += st.get(s_, 0)
-            if (int(np.max(status)) if (world > 1 or count > 0) else 0) != 0:
-                return empty(FeastError.Feast_ERROR_LAPACK, loop)           # a failed SOLVE job, feast_banded.jl:137-147
+            fail, (dP, status, st, Aq, Sq) = _sweep(engine, dQ, M0, world, count, stats, want_moments=True)
+            if fail:                                      # any failed SOLVE job, whatever its code: feast_banded.jl:137-147
+                return empty(FeastError.Feast_ERROR_LAPACK, loop)
             try:
                 w, V = sla.eig(np.real(Sq), np.real(Aq))
             except Exception:
@@ -949,43 +989,32 @@ def pfeast_hip_hermitian_moments(engine, A, B, Emin, Emax, M0, fpm, *, solver="d
     feastdefault(fpm)
     info = check_feast_srci_input(N, M0, Emin, Emax)
     if info:
-        return FeastResult(np.zeros(0), np.zeros((N, 0), dtype=np.complex128), 0, np.zeros(0), info, math.inf, 0)
-    rank, world = _world(engine, group)
+        return _empty_result(N, info)
     sparse = _sp.issparse(A)
     Ac = A.astype(np.complex128)
     Bc = B.astype(np.complex128) if B is not None else (_sp.identity(N, dtype=np.complex128, format="csr") if sparse else np.eye(N, dtype=np.complex128))
-    engine.set_problem(Ac, Bc)
     Zne, Wne = feast_contour(Emin, Emax, fpm)
-    engine.set_contour(Zne, Wne, 2.0)                     # weight = 2 * local_Wne[e], feast_mpi.jl:548
-    engine.set_real_projection(False)
-    first, count = distribute_contour_points(len(Zne), world)[rank]
-    engine.set_node_range(first, count)
-    iterative = solver not in ("direct", "lu", "banded")
-    substituted = False
+    world, count = _setup_sweep(engine, group, Ac, Bc, Zne, Wne, 2.0, False)   # weight = 2 * local_Wne[e], feast_mpi.jl:548
     if solver in ("direct", "lu") and sparse:
         # no sparse LU on the device: the reference's own iterative option, restarted GMRES
-        # (solve_shifted_iterative!, feast_sparse.jl:164-203), device resident here
-        solver, iterative, substituted = "gmres", True, True
-    tol_value = feast_tolerance(fpm) if solver_tol == 0.0 else float(solver_tol)
-    if substituted:
-        # standing in for a DIRECT solve: purely relative stop at 1e-13 per column.  (The reference's iterative option
-        # stops at atol + rtol*||b|| with atol = rtol = tol; columns of this un-normalised iteration shrink to 1e-8 and
-        # an absolute 1e-12 then leaves them at 1e-4 relative -- measured: the outer residual grows 3x per loop.)
-        engine.set_solver(solver, rtol=min(tol_value, 1e-13), atol=0.0, maxit=max(solver_maxiter, 2000), restart=solver_restart)
+        # (solve_shifted_iterative!, feast_sparse.jl:164-203), device resident here, standing in for a DIRECT solve:
+        # purely relative stop at 1e-13 per column.  (The reference's iterative option stops at atol + rtol*||b|| with
+        # atol = rtol = tol; columns of this un-normalised iteration shrink to 1e-8 and an absolute 1e-12 then leaves them
+        # at 1e-4 relative -- measured: the outer residual grows 3x per loop.)
+        iterative = True
+        tol_value = feast_tolerance(fpm) if solver_tol == 0.0 else float(solver_tol)
+        engine.set_solver("gmres", rtol=min(tol_value, 1e-13), atol=0.0, maxit=max(solver_maxiter, 2000), restart=solver_restart)
     else:
-        engine.set_solver(solver, rtol=tol_value, atol=tol_value if iterative else 0.0, maxit=solver_maxiter,
-                          restart=solver_restart, cache_factors=True)
+        iterative, _ = _configure_solver(engine, solver, fpm, solver_tol, solver_maxiter, solver_restart)
     Q_basis = seeded_subspace(N, M0, seed, complex_values=True) if Q0 is None else np.asarray(Q0, dtype=np.complex128)
     dQ = engine.upload(Q_basis)
-    eps_tol = feast_tolerance(fpm)
-    lam_vec, res_vec = np.zeros(M0), np.zeros(M0)
-    epsout, info, M_found, loop_count = math.inf, 0, 0, 0
-    dX = None
-    for loop_idx in range(0, int(fpm[4]) + 1):
+    done = _LoopRecord(M0, feast_tolerance(fpm), int(fpm[4]))
+    info, loop_count, dX = 0, 0, None
+    for loop_idx in range(0, done.maxloop + 1):
         loop_count = loop_idx
-        dP, status, st, zAq, zSq = engine.contour_apply(dQ, M0, None, want_moments=True)
-        fail = int(np.max(status)) if (world > 1 or count > 0) else 0
+        fail, (dP, status, st, zAq, zSq) = _sweep(engine, dQ, M0, world, count, None, want_moments=True)
         if fail:                                          # _mpi_success_count(...) != size, feast_mpi.jl:849-852
+            # any failed node: LAPACK for direct solves, NO_CONVERGENCE for Krylov solves, whatever its code
             info = int(FeastError.Feast_ERROR_LAPACK if not iterative else FeastError.Feast_ERROR_NO_CONVERGENCE)
             break
         Aq = 0.5 * (zAq + zAq.conj().T)                   # _feast_hermitian_part!
@@ -1003,20 +1032,12 @@ def pfeast_hip_hermitian_moments(engine, A, B, Emin, Emax, M0, fpm, *, solver="d
         V_sorted = np.asfortranarray(np.asarray(v_red, dtype=np.complex128)[:, perm])
         # X = Q_proj V, the first M columns normalised, residual ||A x - lambda B x|| / max(|lambda|, 1) for them
         dX, res = engine.ritz_residual(dP, M0, V_sorted, lam_sorted, M, normalize=True, use_B=True)
-        lam_vec[:] = lam_sorted
-        res_vec[:M] = res
-        epsout = float(res.max())
-        M_found = M
-        if epsout <= eps_tol:
-            break
-        if loop_idx == int(fpm[4]):
-            info = int(FeastError.Feast_ERROR_NO_CONVERGENCE)
+        stop = done.record(loop_idx, M0, lam_sorted, M, res)
+        if stop is not None:
+            info = stop
             break
         dQ = dX                                           # copyto!(Q_basis, solutions): all M0 columns
-    if dX is None or M_found == 0:
-        return FeastResult(np.zeros(0), np.zeros((N, 0), dtype=np.complex128), 0, np.zeros(0),
-                           info or int(FeastError.Feast_ERROR_NO_CONVERGENCE), epsout, loop_count)
-    X = engine.download(dX, M_found)
-    order = np.argsort(lam_vec[:M_found], kind="stable")  # feast_sort!
-    return FeastResult(lam_vec[:M_found][order].copy(), X[:, order].copy(), M_found, res_vec[:M_found][order].copy(),
-                       info, epsout, loop_count)
+    M_found = done.M_found
+    X = engine.download(dX, M_found) if M_found > 0 else np.zeros((N, 0), complex)
+    order = np.argsort(done.lam_vec[:M_found], kind="stable")  # feast_sort!
+    return done.result(X, info, loop_count, order=order)
