@@ -56,6 +56,8 @@ SYMBOLS = {
     "feasthip_set_node_range": (_i, [_vp, _i, _i]),
     "feasthip_set_node_list": (_i, [_vp, _i, _vp]),
     "feasthip_set_solver": (_i, [_vp, _i, _d, _d, _i, _i, _i, _i]),
+    "feasthip_set_node_solver": (_i, [_vp, _i, _vp]),
+    "feasthip_direct_plan_bytes": (_i, [_vp, _i, _pi64, _pi64]),
     "feasthip_set_column_mask": (_i, [_vp, _i64, _vp]),
     "feasthip_rayleigh_ritz_dev": (_i, [_vp, _i64, _vp, _d, _d, _i, _vp, _vp, _vp, _vp]),
     "feasthip_contour_apply": (_i, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _ps]),
@@ -91,6 +93,7 @@ SYMBOLS = {
     "feasthip_policy_init": (_i, [_vp, _d, _d, _i, _i, _d, _d, _i, _i, _i]),
     "feasthip_policy_update": (_i, [_vp, _d, _i, _i, _vp, _i]),
     "feasthip_policy_set_aside": (_i, [_vp, _i, _vp]),
+    "feasthip_policy_pick_direct_nodes": (_i, [_vp, _i, _i, _d, _d, _d, _i, _vp]),
     "feasthip_policy_filter_ratio": (_d, [_d, _d, _i, _i, _i, _d, _vp, _i]),
     "feasthip_policy_reach": (_d, [_vp, _i, _d, _d, _d]),
 }

@@ -12,7 +12,8 @@ import scipy.sparse as sp
 
 from .engine import HipEngine
 from .contour import feast_contour, feast_gcontour
-from .hip_backend import ESTIMATE_SEED, feast_hip_estimate, feast_hip_general, feast_hip_hermitian
+from .hip_backend import (DIRECT_SOLVERS, ESTIMATE_SEED, check_direct_nodes, feast_hip_estimate, feast_hip_general,
+                          feast_hip_hermitian)
 from .parameters import feastdefault, feastinit
 from .types import FEAST_UNINITIALIZED, FeastHipError, FeastResult
 
@@ -155,6 +156,17 @@ def _warn_substitution(sub):
                   RuntimeWarning, stacklevel=3)
 
 
+def _check_direct_nodes_early(direct_nodes, A, solver, fpm, ne_slot, contour):
+    """The ``direct_nodes`` keyword checked before any device work (ValueError): sparse input, a Krylov solver (or the
+    default, which may resolve to one), indices inside the contour's node count (fpm[ne_slot], or the caller's contour)."""
+    if direct_nodes is None:
+        return
+    f = feastinit() if fpm is None else np.array(fpm).copy()
+    feastdefault(f)
+    ne = len(contour[0]) if contour is not None else int(f[ne_slot])
+    check_direct_nodes(direct_nodes, ne, sp.issparse(A), "cocg" if solver in ("direct", "krylov") else solver)
+
+
 def _release_band_factors(eng, keep):
     """The sparse direct solver's factors stay on the engine across set_contour and across calls (16 x 2.8 GB on cfg 3).
     Inside one call that is the reference's factor cache; beyond it, it is device memory a later Krylov / GMRES call on
@@ -234,7 +246,7 @@ def _engine(engine, device):
 def feast(A, B=None, interval=None, *, M0=10, fpm=None, backend="hip", solver="direct", solver_tol=0.0,
           solver_maxiter=None, solver_restart=30, warm_start=None, inner_rtol=None, real_projection=None,
           inner_precision=64, group=None, engine=None, device=0, Q0=None, contour=None, contour_policy=None,
-          keep_factors=False, seed=None):
+          keep_factors=False, seed=None, direct_nodes=None):
     """feast(A, [B,] (Emin, Emax); M0, fpm, backend=:hip) for real-symmetric / Hermitian
     dense (numpy) or sparse (scipy) matrices.  Real input is complexified and the result is
     real.(q), exactly as feast_sygv!/feast_scsrgv! do (src/dense/feast_dense.jl:362-387).
@@ -250,6 +262,10 @@ def feast(A, B=None, interval=None, *, M0=10, fpm=None, backend="hip", solver="d
     seconds}; a node that fails (status 5 / 8) gives that info and ``stats["estimate"] = None``.
     ``M0="auto"``: such an estimate with 64 samples first, then the solve with M0 = min(N, max(8, ceil(1.5 (mean +
     2 stderr)))); the estimate and the chosen M0 are in ``stats["estimate"]`` / ``stats["M0_auto"]``.
+    ``direct_nodes`` (sparse input on the Krylov path: solver cocg / bicgstab / iterative, or the default when it resolves to
+    them): contour nodes the sweeps solve with the sparse direct solver instead of iterating (per-node solver,
+    feasthip_set_node_solver) -- a list of node indices, an int k (the k slowest nodes of the first loop, from the second
+    on) or "auto" (feasthip_policy_pick_direct_nodes after every loop).  ``stats["direct_nodes"]`` has one entry per loop.
     """
     if isinstance(M0, str):
         if M0 != "auto":
@@ -258,7 +274,7 @@ def feast(A, B=None, interval=None, *, M0=10, fpm=None, backend="hip", solver="d
                            solver_maxiter=solver_maxiter, solver_restart=solver_restart, warm_start=warm_start,
                            inner_rtol=inner_rtol, real_projection=real_projection, inner_precision=inner_precision,
                            group=group, engine=engine, device=device, Q0=Q0, contour=contour, contour_policy=contour_policy,
-                           keep_factors=keep_factors, seed=seed)
+                           keep_factors=keep_factors, seed=seed, direct_nodes=direct_nodes)
     if interval is None and B is not None and isinstance(B, tuple):
         B, interval = None, B              # feast(A, (Emin, Emax)) form
     if backend not in _BACKENDS:
@@ -267,6 +283,7 @@ def feast(A, B=None, interval=None, *, M0=10, fpm=None, backend="hip", solver="d
         raise ValueError("Matrix A must be square")
     if B is not None and B.shape != A.shape:
         raise ValueError("Matrix B must match size of A")
+    _check_direct_nodes_early(direct_nodes, A, solver, fpm, 2, contour)
     eng = _engine(engine, device)
     # input checks and the pattern scan cost tens of milliseconds on a 50 000-unknown CSR pair (sparse transposes): a
     # repeated call with the same matrices (content fingerprint, engine.py) skips them
@@ -376,29 +393,37 @@ def feast(A, B=None, interval=None, *, M0=10, fpm=None, backend="hip", solver="d
             return remaining > 3.0 * plan["t_direct"]
     warm_start = bool(warm_start)                 # an explicitly named iterative solver keeps the reference's zero guess
     solver_maxiter = 500 if solver_maxiter is None else int(solver_maxiter)
-    res = feast_hip_hermitian(eng, A, B, Emin, Emax, M0, fpm, solver=solver, solver_tol=solver_tol,
-                              solver_maxiter=solver_maxiter, solver_restart=solver_restart,
-                              warm_start=warm_start, inner_rtol=inner_rtol, real_projection=real_projection,
-                              inner_precision=inner_precision, group=group, Q0=Q0, contour=contour,
-                              contour_policy=contour_policy, eps_floor=float(np.sqrt(np.finfo(np.float32).eps)) if single else 0.0,
-                              abort_check=abort_check)
-    if (res.info == 5 and substituted is not None and substituted.get("used") in ("cocg", "bicgstab") and group is None
-            and _band_direct_fits(eng, A, B, int(fpm[2]))):
-        # The Krylov sweeps did not converge (typically an interval inside the spectrum: the shifted systems are then
-        # indefinite and badly conditioned).  solver=:direct was what the caller asked for, and the direct solver for general
-        # patterns fits the device: run it, as the reference's default would have from the start.
-        krylov_info, krylov_loops = int(res.info), int(res.loop)
-        # (the direct solver starts from the caller's / the seeded subspace, not from what the Krylov loops left: measured on
-        #  cfg 3's interval around 2.0, the stagnated subspace carries a spurious pair into the direct solve -- M = 41, info 5
-        #  after 20 loops -- where the fresh start converges in two)
-        res = feast_hip_hermitian(eng, A, B, Emin, Emax, M0, fpm, solver="banded", solver_tol=solver_tol,
-                                  real_projection=real_projection, inner_precision=inner_precision, group=group, Q0=Q0,
-                                  contour=contour, eps_floor=float(np.sqrt(np.finfo(np.float32).eps)) if single else 0.0)
-        substituted = dict(substituted, fallback=_direct_label(eng), krylov_info=krylov_info,
-                           krylov_loops=krylov_loops)
-    if substituted is not None and isinstance(res.stats, dict):
-        res.stats["solver_substitution"] = substituted
-    _release_band_factors(eng, keep_factors)
+    dn_ignored = direct_nodes is not None and solver in DIRECT_SOLVERS      # the default resolved to a direct solver outright
+    try:                                          # whatever happens below, the factors it cached go with the call
+        res = feast_hip_hermitian(eng, A, B, Emin, Emax, M0, fpm, solver=solver, solver_tol=solver_tol,
+                                  solver_maxiter=solver_maxiter, solver_restart=solver_restart,
+                                  warm_start=warm_start, inner_rtol=inner_rtol, real_projection=real_projection,
+                                  inner_precision=inner_precision, group=group, Q0=Q0, contour=contour,
+                                  contour_policy=contour_policy, eps_floor=float(np.sqrt(np.finfo(np.float32).eps)) if single else 0.0,
+                                  abort_check=abort_check, direct_nodes=None if dn_ignored else direct_nodes)
+        if dn_ignored and isinstance(res.stats, dict):
+            res.stats["direct_nodes"] = {"ignored": "direct solver in force"}
+        if (res.info == 5 and substituted is not None and substituted.get("used") in ("cocg", "bicgstab") and group is None
+                and _band_direct_fits(eng, A, B, int(fpm[2]))):
+            # The Krylov sweeps did not converge (typically an interval inside the spectrum: the shifted systems are then
+            # indefinite and badly conditioned).  solver=:direct was what the caller asked for, and the direct solver for general
+            # patterns fits the device: run it, as the reference's default would have from the start.
+            krylov_info, krylov_loops = int(res.info), int(res.loop)
+            # (the direct solver starts from the caller's / the seeded subspace, not from what the Krylov loops left: measured on
+            #  cfg 3's interval around 2.0, the stagnated subspace carries a spurious pair into the direct solve -- M = 41, info 5
+            #  after 20 loops -- where the fresh start converges in two)
+            dn_log = res.stats.get("direct_nodes") if isinstance(res.stats, dict) else None
+            res = feast_hip_hermitian(eng, A, B, Emin, Emax, M0, fpm, solver="banded", solver_tol=solver_tol,
+                                      real_projection=real_projection, inner_precision=inner_precision, group=group, Q0=Q0,
+                                      contour=contour, eps_floor=float(np.sqrt(np.finfo(np.float32).eps)) if single else 0.0)
+            if dn_log is not None and isinstance(res.stats, dict):
+                res.stats["direct_nodes"] = dn_log                      # what the Krylov loops did before the hand-over
+            substituted = dict(substituted, fallback=_direct_label(eng), krylov_info=krylov_info,
+                               krylov_loops=krylov_loops)
+        if substituted is not None and isinstance(res.stats, dict):
+            res.stats["solver_substitution"] = substituted
+    finally:
+        _release_band_factors(eng, keep_factors)
     if real_input:
         res = FeastResult(res.lambda_, np.real(res.q), res.M, res.res, res.info, res.epsout, res.loop, res.stats)
     if single:
@@ -408,9 +433,9 @@ def feast(A, B=None, interval=None, *, M0=10, fpm=None, backend="hip", solver="d
 
 def feast_general(A, B=None, center=0.0, radius=1.0, *, M0=10, fpm=None, backend="hip", solver="direct",
                   solver_tol=0.0, solver_maxiter=500, solver_restart=30, group=None, engine=None, device=0, Q0=None,
-                  inner_precision=64, contour=None, keep_factors=False, seed=None):
+                  inner_precision=64, contour=None, keep_factors=False, seed=None, direct_nodes=None):
     """feast_general(A, [B,] center, radius; M0, fpm): src/interfaces/feast_interfaces.jl:274-379.
-    ``keep_factors``: as in feast().  ``fpm[14] = 2`` and ``M0="auto"``: as in feast(), on the full contour of the
+    ``keep_factors``, ``direct_nodes``: as in feast().  ``fpm[14] = 2`` and ``M0="auto"``: as in feast(), on the full contour of the
     circle (the samples are complex; M = round(Re mean))."""
     if isinstance(M0, str):
         if M0 != "auto":
@@ -418,13 +443,14 @@ def feast_general(A, B=None, center=0.0, radius=1.0, *, M0=10, fpm=None, backend
         return _feast_auto(feast_general, A, B, center, radius, fpm=fpm, backend=backend, solver=solver, solver_tol=solver_tol,
                            solver_maxiter=solver_maxiter, solver_restart=solver_restart, group=group, engine=engine,
                            device=device, Q0=Q0, inner_precision=inner_precision, contour=contour, keep_factors=keep_factors,
-                           seed=seed)
+                           seed=seed, direct_nodes=direct_nodes)
     if backend not in _BACKENDS:
         raise ValueError(f"Unknown backend '{backend}' (this package provides: hip)")
     if A.shape[0] != A.shape[1]:
         raise ValueError("Matrix A must be square")
     if not radius > 0:
         raise ValueError("radius must be positive")
+    _check_direct_nodes_early(direct_nodes, A, solver, fpm, 8, contour)
     single = _single_precision(A, B)
     if single:
         A, B = _promote(A), _promote(B)
@@ -466,13 +492,19 @@ def feast_general(A, B=None, center=0.0, radius=1.0, *, M0=10, fpm=None, backend
     elif solver == "sparse_direct":
         solver = "banded"
     eng = _engine(engine, device)
-    res = feast_hip_general(eng, A, B, complex(center), float(radius), M0, fpm, solver=solver, inner_precision=inner_precision,
-                             solver_tol=solver_tol, solver_maxiter=solver_maxiter,
-                             solver_restart=solver_restart, group=group, Q0=Q0, contour=contour,
-                             eps_floor=float(np.sqrt(np.finfo(np.float32).eps)) if single else 0.0)
-    if substituted is not None and isinstance(res.stats, dict):
-        res.stats["solver_substitution"] = substituted
-    _release_band_factors(eng, keep_factors)
+    dn_ignored = direct_nodes is not None and solver in DIRECT_SOLVERS
+    try:
+        res = feast_hip_general(eng, A, B, complex(center), float(radius), M0, fpm, solver=solver, inner_precision=inner_precision,
+                                 solver_tol=solver_tol, solver_maxiter=solver_maxiter,
+                                 solver_restart=solver_restart, group=group, Q0=Q0, contour=contour,
+                                 eps_floor=float(np.sqrt(np.finfo(np.float32).eps)) if single else 0.0,
+                                 direct_nodes=None if dn_ignored else direct_nodes)
+        if dn_ignored and isinstance(res.stats, dict):
+            res.stats["direct_nodes"] = {"ignored": "direct solver in force"}
+        if substituted is not None and isinstance(res.stats, dict):
+            res.stats["solver_substitution"] = substituted
+    finally:
+        _release_band_factors(eng, keep_factors)
     if single:
         res = _demote(res, cplx_lambda=True)
     return res

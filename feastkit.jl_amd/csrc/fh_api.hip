@@ -405,6 +405,7 @@ extern "C" int feasthip_set_contour(feasthip_handle h, int ne, const double* zne
         h->wne[e] = cmake(wne[2 * e], wne[2 * e + 1]);
     }
     h->weight_scale = weight_scale;
+    if ((int)h->node_kinds.size() != ne) h->node_kinds.clear();      // feasthip_set_node_solver: kinds of another contour
     h->node_first = 0;
     h->node_count = ne;
     h->node_ids.resize(ne);
@@ -413,6 +414,30 @@ extern "C" int feasthip_set_contour(feasthip_handle h, int ne, const double* zne
     // fh_banded_solve_nodes), so a repeated solve on the same contour keeps its factorisations and any other contour
     // refactors slot by slot
     return 0;
+}
+
+extern "C" int feasthip_set_node_solver(feasthip_handle h, int count, const int* kinds) {
+    if (!h) return FEASTHIP_ERROR_INTERNAL;
+    if (count == 0 || !kinds) { h->node_kinds.clear(); return 0; }
+    if (count != (int)h->zne.size()) {
+        h->last_error = "feasthip_set_node_solver: count " + std::to_string(count) + " is not the contour's node count " + std::to_string(h->zne.size());
+        return FEASTHIP_ERROR_FPM;
+    }
+    for (int e = 0; e < count; ++e)
+        if (kinds[e] != 0 && kinds[e] != FEASTHIP_SOLVER_BANDED) {
+            h->last_error = "feasthip_set_node_solver: kind " + std::to_string(kinds[e]) + " of node " + std::to_string(e) + " (0 or FEASTHIP_SOLVER_BANDED)";
+            return FEASTHIP_ERROR_FPM;
+        }
+    h->node_kinds.assign(kinds, kinds + count);
+    return 0;
+}
+
+extern "C" int feasthip_direct_plan_bytes(feasthip_handle h, int nodes, int64_t* factor_bytes, int64_t* transient_bytes) {
+    if (!h) return FEASTHIP_ERROR_INTERNAL;
+    if (h->poisoned) { h->last_error = "handle poisoned by an earlier device failure: destroy it"; return FEASTHIP_ERROR_INTERNAL; }
+    if (h->kind != 2 || nodes < 0) { h->last_error = "feasthip_direct_plan_bytes: needs a CSR problem and nodes >= 0"; return FEASTHIP_ERROR_FPM; }
+    FH_CHECK(hipSetDevice(h->device));
+    return fh_banded_plan_bytes(h, nodes, factor_bytes, transient_bytes);
 }
 
 extern "C" int feasthip_set_real_projection(feasthip_handle h, int real_part) {
@@ -1204,6 +1229,30 @@ struct fh_panel_io {
     cplx* out = nullptr;
 };
 
+// Local nodes in sweep order: the Krylov nodes, then the *nd direct ones (feasthip_set_node_solver), each ascending.  With at
+// least one direct node the handle must be able to mix the two families: a CSR problem, COCG or BiCGStab on fp64 panels.
+// A handle whose own solver is the sparse direct one takes every node there anyway, so the kinds change nothing.
+static int fh_split_nodes(feasthip_ctx* h, std::vector<int>& order, int* nd) {
+    const int nodes = h->node_count;
+    order.clear();
+    std::vector<int> direct;
+    const bool mixed = h->node_kinds.size() == h->zne.size() && h->solver != FEASTHIP_SOLVER_BANDED;
+    for (int e = 0; e < nodes; ++e) {
+        if (mixed && h->node_kinds[h->node_ids[e]] == FEASTHIP_SOLVER_BANDED) direct.push_back(e);
+        else order.push_back(e);
+    }
+    *nd = (int)direct.size();
+    order.insert(order.end(), direct.begin(), direct.end());
+    if (!*nd) return 0;
+    const char* why = nullptr;
+    if (h->kind != 2) why = "a dense problem has no sparse direct solver";
+    else if (h->solver != FEASTHIP_SOLVER_COCG && h->solver != FEASTHIP_SOLVER_BICGSTAB) why = "the handle's solver must be COCG or BICGSTAB (GMRES sweeps do not mix)";
+    else if (h->factor_precision != 64) why = "factor_precision = 32 is not supported";
+    else if (*nd > FH_NODE_FINISH_MAX) why = "more than 64 direct nodes on one rank";
+    if (why) { h->last_error = std::string("per-node solver (feasthip_set_node_solver) with direct nodes: ") + why; return FEASTHIP_ERROR_FPM; }
+    return 0;
+}
+
 static int fh_contour_apply_panel(feasthip_ctx* h, int64_t m64, const cplx* dQ, const double* ritz_lambda,
                                   cplx* dQproj, cplx* dzAq, cplx* dzSq, int* node_status, feasthip_stats* stats,
                                   const fh_moment_ctx* mom = nullptr, const fh_panel_io* io = nullptr) {
@@ -1253,11 +1302,19 @@ static int fh_contour_apply_panel(feasthip_ctx* h, int64_t m64, const cplx* dQ, 
         oc.X = Qp; oc.Y = Rhs; oc.coefA = dca; oc.coefB = dcb;
         fh_apply_operator(h, ld, oc);
     }
+    // Per-node solver (feasthip_set_node_solver): the local nodes split into a Krylov set K and a direct set D.  The panels
+    // of Y, and z / w with them, are ordered K first, then D, both in ascending node order (order[i] = local node of panel
+    // i); with no direct node this is the identity and nothing below differs from the one-solver sweep.
+    std::vector<int> order;
+    int nd = 0;
+    if ((rc = fh_split_nodes(h, order, &nd))) return rc;
+    const int nk = nodes - nd;
     std::vector<cplx> z(nodes), w(nodes);
-    for (int e = 0; e < nodes; ++e) {
-        z[e] = h->zne[h->node_ids[e]];
-        w[e] = cscale(h->wne[h->node_ids[e]], h->weight_scale);
+    for (int i = 0; i < nodes; ++i) {
+        z[i] = h->zne[h->node_ids[order[i]]];
+        w[i] = cscale(h->wne[h->node_ids[order[i]]], h->weight_scale);
     }
+    const std::vector<cplx> zk(z.begin(), z.begin() + nk), wk(w.begin(), w.begin() + nk), zd(z.begin() + nk, z.end());
     if ((rc = fh_get_buf(h, "ca_Y", (size_t)nodes * panel * sizeof(cplx), &p))) return rc;
     cplx* Y = (cplx*)p;
     std::vector<int> status(nodes, 0);
@@ -1289,9 +1346,14 @@ static int fh_contour_apply_panel(feasthip_ctx* h, int64_t m64, const cplx* dQ, 
             h->last_error = "solver COCG needs a complex-SYMMETRIC shifted matrix: real-symmetric A and B only";
             return FEASTHIP_ERROR_FPM;
         }
+        // direct nodes first, on the same stream: sparse direct solves of the shared right-hand side into their own panels
+        // (no warm start, no column mask, as the LU path); the factors live in the band / multifrontal cache, matched by z
+        int64_t nfact = 0;
+        std::vector<int> status_d;
+        if (nd && (rc = fh_banded_solve_subset(h, ld, m, zd, Rhs, Y + (size_t)nk * panel, panel, status_d, &nfact))) return rc;
         // initial guess
-        cplx* dz;
-        if ((rc = fh_upload_coefs(h, "ca_z", z, &dz))) return rc;
+        cplx* dz = nullptr;
+        if (nk && (rc = fh_upload_coefs(h, "ca_z", zk, &dz))) return rc;
         double* dlam = nullptr;
         if (ritz_lambda) {
             std::vector<double> lam(ld, 0.0);
@@ -1331,23 +1393,40 @@ static int fh_contour_apply_panel(feasthip_ctx* h, int64_t m64, const cplx* dQ, 
             } else {
                 shared_src = Rhs;
             }
-        } else {
+        } else if (nk) {
             fh_vec_args va;
             memset(&va, 0, sizeof(va));
             va.N = N; va.node_stride = panel; va.X = Y; va.Q = Qp; va.lambda = dlam; va.znode = dz;
-            fh_launch_init_guess(va, ld, fh_vec_nblk(N, ld), nodes, h->stream);
+            fh_launch_init_guess(va, ld, fh_vec_nblk(N, ld), nk, h->stream);
         }
-        rc = fh_krylov(h, h->solver == FEASTHIP_SOLVER_COCG ? 1 : 0, h->factor_precision, ld, m, nodes, z, Rhs, Y, panel, sr,
-                       sum_acc, &w, shared_src, dlam, dz, ritz_lambda);
-        if (rc) return rc;
-        status = sr.status;
-        h->last_node_iters = sr.node_iters;
-        h->last_col_iters = sr.col_iters;
+        if (nk) {
+            rc = fh_krylov(h, h->solver == FEASTHIP_SOLVER_COCG ? 1 : 0, h->factor_precision, ld, m, nk, zk, Rhs, Y, panel, sr,
+                           sum_acc, &wk, shared_src, dlam, dz, ritz_lambda);
+            if (rc) return rc;
+        }
+        if (!nd) {
+            status = sr.status;
+            h->last_node_iters = sr.node_iters;
+            h->last_col_iters = sr.col_iters;
+        } else {
+            // back to local node order; a direct node reports 0 iterations
+            h->last_node_iters.assign(nodes, 0);
+            h->last_col_iters.assign((size_t)nodes * m, 0);
+            for (int i = 0; i < nk; ++i) {
+                const int e = order[i];
+                if (i < (int)sr.status.size()) status[e] = sr.status[i];
+                if (i < (int)sr.node_iters.size()) h->last_node_iters[e] = sr.node_iters[i];
+                for (int c = 0; c < m && (size_t)i * m + c < sr.col_iters.size(); ++c)
+                    h->last_col_iters[(size_t)e * m + c] = sr.col_iters[(size_t)i * m + c];
+            }
+            for (int d = 0; d < nd; ++d) status[order[nk + d]] = status_d[d];
+        }
         h->last_col_m = m;
         if (stats) {
             stats->krylov_iterations = sr.iters_sum;
             stats->spmm_calls = sr.op_calls;
             stats->max_rel_residual = sr.max_rel_res;
+            stats->factorizations = nfact;
         }
     } else {
         // GMRES: zero initial guess like Krylov.jl (or the Ritz warm start when given)
@@ -1383,16 +1462,23 @@ static int fh_contour_apply_panel(feasthip_ctx* h, int64_t m64, const cplx* dQ, 
     // Q_proj = sum_e (scale*w_e) Y_e
     cplx* dw;
     if ((rc = fh_upload_coefs(h, "ca_w", w, &dw))) return rc;
-    fh_prof_begin(h, "accumulate");
+    cplx* dwd = nullptr;
+    if (sum_shared && nd) {
+        const std::vector<cplx> wd(w.begin() + nk, w.end());
+        if ((rc = fh_upload_coefs(h, "ca_wd", wd, &dwd))) return rc;
+    }
+    fh_prof_begin(h, dwd ? "node_finish" : "accumulate");
     if (sum_shared) {
         cplx* drho = nullptr;
         if (ritz_lambda) {
+            // the closed-form sum of the warm starts runs over the Krylov nodes only
             std::vector<cplx> rho(ld, cmake(0, 0));
             for (int c = 0; c < m; ++c)
-                for (int e = 0; e < nodes; ++e) rho[c] = cadd(rho[c], cdiv(w[e], cmake(z[e].x - ritz_lambda[c], z[e].y)));
+                for (int e = 0; e < nk; ++e) rho[c] = cadd(rho[c], cdiv(w[e], cmake(z[e].x - ritz_lambda[c], z[e].y)));
             if ((rc = fh_upload_coefs(h, "ca_rho", rho, &drho))) return rc;
         }
-        fh_launch_sum_finish(Qp, drho, sum_acc, Outp, N, ld, h->real_projection, h->stream);
+        if (dwd) fh_launch_node_finish(Qp, drho, sum_acc, Y + (size_t)nk * panel, panel, dwd, nd, Outp, N, ld, h->real_projection, h->stream);
+        else fh_launch_sum_finish(Qp, drho, sum_acc, Outp, N, ld, h->real_projection, h->stream);
     } else {
         fh_launch_accumulate(Y, panel, dw, nodes, N, ld, sum_acc, Outp, h->real_projection, h->stream);
     }
@@ -2644,6 +2730,11 @@ extern "C" int feasthip_policy_update(feasthip_policy* p, double epsout, int M, 
         p->next_rtol = std::min(0.3, std::max(p->inner_rtol, 0.32 * p->outer_tol / epsout));
     p->eps_prev = epsout;
     return 0;
+}
+
+extern "C" int feasthip_policy_pick_direct_nodes(const int* node_iters, int ne, int max_direct, double t_iter, double t_solve,
+                                                 double t_factor, int loops_left, int* kinds) {
+    return fh_policy::pick_direct_nodes(node_iters, ne, max_direct, t_iter, t_solve, t_factor, loops_left, kinds);
 }
 
 extern "C" int feasthip_policy_set_aside(const double* res, int M, int* flags) {

@@ -283,6 +283,12 @@ static int band_check(feasthip_ctx* h) {
     return 0;
 }
 
+// Buffers that live only while `nslots` nodes are factored and swept (multifrontal plan: the work arena and the substitution
+// panels, about the factors' size again; the band plans have none beyond the sweep's own workspace)
+static double band_transient_bytes(feasthip_ctx* h, int prec, int nslots, size_t slot_bytes) {
+    return h->band_plan == 3 ? (double)nslots * ((double)fh_mf_work_bytes(h, prec) + 0.5 * (double)slot_bytes) : 0.0;
+}
+
 static int band_ensure_slots(feasthip_ctx* h, int nslots) {
     const size_t N = (size_t)h->csr.N;
     // complex64 factors (feasthip_set_solver factor_precision = 32) exist for the blocked plan only; the caller refines in fp64
@@ -297,8 +303,7 @@ static int band_ensure_slots(feasthip_ctx* h, int nslots) {
     const int missing = nslots - (int)h->band_factors.size();
     if (missing > 0) {
         size_t free_b = 0, total_b = 0;
-        // (multifrontal plan: the work arena and the substitution panels are transient buffers of about the factors' size again)
-        const double transient = h->band_plan == 3 ? (double)nslots * ((double)fh_mf_work_bytes(h, prec) + 0.5 * (double)bytes) : 0.0;
+        const double transient = band_transient_bytes(h, prec, nslots, bytes);
         if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && (double)missing * (double)bytes + transient > 0.92 * (double)free_b) {
             h->last_error = "banded LU: " + std::to_string(missing) + " factors of " + std::to_string(bytes >> 20) + " MiB do not fit the free device memory (" +
                             std::to_string(free_b >> 20) + " MiB)";
@@ -487,16 +492,17 @@ static int band_solve_batch(feasthip_ctx* h, int ld, int m, const std::vector<in
     return 0;
 }
 
-int fh_banded_solve_nodes(feasthip_ctx* h, int ld, int m, int nodes, const std::vector<cplx>& z, const cplx* RHS, size_t rhs_stride, cplx* Y,
-                          size_t stride, std::vector<int>& status, int64_t* nfact) {
-    int rc = band_check(h);
-    if (rc) return rc;
-    if ((rc = band_ensure_slots(h, nodes))) return rc;
+// Factor (where the cache does not already hold z[q] in slot slots[q]) and solve the nodes listed in `slots`.
+static int band_solve_slots(feasthip_ctx* h, int ld, int m, const std::vector<int>& slots, const std::vector<cplx>& z, const cplx* RHS,
+                            size_t rhs_stride, cplx* Y, size_t stride, std::vector<int>& status, int64_t* nfact) {
+    const int nodes = (int)slots.size();
+    int rc;
     std::vector<int> need;
     std::vector<cplx> zl;
     for (int e = 0; e < nodes; ++e) {
-        const bool ok = h->cache_factors && h->band_valid[e] == 1 && h->band_z[e].x == z[e].x && h->band_z[e].y == z[e].y;
-        if (!ok) { need.push_back(e); zl.push_back(z[e]); h->band_valid[e] = 0; }
+        const int s = slots[e];
+        const bool ok = h->cache_factors && h->band_valid[s] == 1 && h->band_z[s].x == z[e].x && h->band_z[s].y == z[e].y;
+        if (!ok) { need.push_back(s); zl.push_back(z[e]); h->band_valid[s] = 0; }
     }
     std::vector<int> info;
     if ((rc = band_factor_batch(h, need, zl, info))) return rc;
@@ -509,7 +515,7 @@ int fh_banded_solve_nodes(feasthip_ctx* h, int ld, int m, int nodes, const std::
     std::vector<int> lost;
     std::vector<cplx> zlost;
     for (int e = 0; e < nodes; ++e)
-        if (h->band_valid[e] == 0) { lost.push_back(e); zlost.push_back(z[e]); }
+        if (h->band_valid[slots[e]] == 0) { lost.push_back(slots[e]); zlost.push_back(z[e]); }
     if (!lost.empty()) {
         if ((rc = band_factor_batch(h, lost, zlost, info))) return rc;
         for (size_t q = 0; q < lost.size(); ++q) {
@@ -519,12 +525,55 @@ int fh_banded_solve_nodes(feasthip_ctx* h, int ld, int m, int nodes, const std::
         done += (int64_t)lost.size();
     }
     if (nfact) *nfact = done;
-    std::vector<int> slots(nodes);
-    for (int e = 0; e < nodes; ++e) slots[e] = e;
     if ((rc = band_solve_batch(h, ld, m, slots, RHS, rhs_stride, Y, stride))) return rc;
     status.assign(nodes, 0);
-    for (int e = 0; e < nodes; ++e) if (h->band_valid[e] != 1) status[e] = FEASTHIP_ERROR_LAPACK;
+    for (int e = 0; e < nodes; ++e) if (h->band_valid[slots[e]] != 1) status[e] = FEASTHIP_ERROR_LAPACK;
     return 0;
+}
+
+int fh_banded_solve_nodes(feasthip_ctx* h, int ld, int m, int nodes, const std::vector<cplx>& z, const cplx* RHS, size_t rhs_stride, cplx* Y,
+                          size_t stride, std::vector<int>& status, int64_t* nfact) {
+    int rc = band_check(h);
+    if (rc) return rc;
+    if ((rc = band_ensure_slots(h, nodes))) return rc;
+    std::vector<int> slots(nodes);
+    for (int e = 0; e < nodes; ++e) slots[e] = e;
+    return band_solve_slots(h, ld, m, slots, z, RHS, rhs_stride, Y, stride, status, nfact);
+}
+
+// The direct nodes of a per-node sweep (feasthip_set_node_solver): a subset of the local nodes, so the factor slots are
+// mapped by shift instead of by local node -- a node whose z is cached keeps its slot whatever else joined or left the
+// subset, the others take the slots no node of this call holds.  Only as many slots as the subset needs are allocated.
+int fh_banded_solve_subset(feasthip_ctx* h, int ld, int m, const std::vector<cplx>& z, const cplx* RHS, cplx* Y, size_t stride,
+                           std::vector<int>& status, int64_t* nfact) {
+    int rc = band_check(h);
+    if (rc) return rc;
+    const int nd = (int)z.size();
+    if ((rc = band_ensure_slots(h, std::max(nd, (int)h->band_factors.size())))) return rc;
+    const int nslots = (int)h->band_factors.size();
+    std::vector<int> slots(nd, -1), taken(nslots, 0);
+    for (int d = 0; d < nd; ++d)
+        for (int s = 0; s < nslots && h->cache_factors; ++s)
+            if (!taken[s] && h->band_valid[s] == 1 && h->band_z[s].x == z[d].x && h->band_z[s].y == z[d].y) { slots[d] = s; taken[s] = 1; break; }
+    for (int pass = 0; pass < 2; ++pass)          // free slots first, then the cached ones nobody claimed
+        for (int d = 0; d < nd; ++d)
+            for (int s = 0; s < nslots && slots[d] < 0; ++s)
+                if (!taken[s] && (pass == 1 || h->band_valid[s] != 1)) { slots[d] = s; taken[s] = 1; }
+    return band_solve_slots(h, ld, m, slots, z, RHS, 0, Y, stride, status, nfact);
+}
+
+// Device memory `nodes` direct nodes take under the plan in force: the cached factors and pivots, and the buffers that live
+// only while they are factored and swept (band_transient_bytes, which
+// band_ensure_slots checks its allocations against).
+int fh_banded_plan_bytes(feasthip_ctx* h, int nodes, int64_t* factor_bytes, int64_t* transient_bytes) {
+    int rc = band_check(h);
+    if (rc && !h->band_plan) return rc;
+    const int prec = (h->band_plan >= 2 && h->factor_precision == 32) ? 32 : 64;
+    const double bytes = (double)(h->band_plan == 3 ? fh_mf_store_bytes(h, prec) : band_slot_bytes(h));
+    const double pivots = (double)(h->band_plan == 3 ? fh_mf_pivot_ints(h) : (size_t)h->csr.N) * sizeof(int);
+    if (factor_bytes) *factor_bytes = (int64_t)((double)nodes * (bytes + pivots));
+    if (transient_bytes) *transient_bytes = (int64_t)band_transient_bytes(h, prec, nodes, (size_t)bytes);
+    return rc;
 }
 
 int fh_banded_solve_single(feasthip_ctx* h, int ld, int m, cplx z, const cplx* RHS, cplx* Y, int* status, int64_t* nfact) {

@@ -148,6 +148,7 @@ struct feasthip_ctx {
     int real_projection = 0;
     int node_first = 0, node_count = 0;
     std::vector<int> node_ids;      // local node -> contour index (set by range or list)
+    std::vector<int> node_kinds;    // feasthip_set_node_solver: per CONTOUR node, 0 = the handle's solver, FEASTHIP_SOLVER_BANDED = direct; empty = none
 
     // solver options
     int solver = 1;

@@ -79,6 +79,9 @@ void fh_launch_cocg_init_shared(const fh_vec_args& a, int ld, int nblk, int node
 void fh_launch_cocg_init_lazy(const fh_vec_args& a, int ld, int nblk, int nodes, hipStream_t st);
 // OUT = [Re](SRC * rho_c + ACC)
 void fh_launch_sum_finish(const cplx* src, const cplx* rho, const cplx* acc, cplx* out, int N, int ld, int real_part, hipStream_t st);
+#define FH_NODE_FINISH_MAX 64    // direct nodes one finishing launch sums (their weights sit in LDS); FH_BLOCK >= this
+void fh_launch_node_finish(const cplx* src, const cplx* rho, const cplx* acc, const cplx* Yd, size_t stride, const cplx* wd, int nd,
+                           cplx* out, int N, int ld, int real_part, hipStream_t st);
 void fh_launch_cocg_update(const fh_vec_args& a, int ld, int nblk, int nodes, hipStream_t st);
 void fh_launch_cocg_p(const fh_vec_args& a, int ld, int nblk, int nodes, hipStream_t st);
 void fh_launch_cocg_p_sum(const fh_vec_args& a, int ld, int nodes, hipStream_t st);

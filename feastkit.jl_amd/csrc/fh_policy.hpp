@@ -149,4 +149,27 @@ static inline int pick(double Emin, double Emax, int ne, int quadrature, double 
     return best;
 }
 
+// Which quadrature nodes of a Krylov sweep to hand to the sparse direct solver (feasthip_policy_pick_direct_nodes).  The
+// sweep's serial chain is as long as its slowest node, so with the nodes ordered by node_iters descending (ties to the lower
+// index) the predicted time of one further loop with the first k of them direct is
+//     t_iter * max(node_iters outside the top k) + k * (t_solve + t_factor / max(loops_left, 1)).
+// Takes the smallest k in 0..max_direct that minimises it; kinds[e] = 4 (FEASTHIP_SOLVER_BANDED) for the chosen, else 0.
+static inline int pick_direct_nodes(const int* node_iters, int ne, int max_direct, double t_iter, double t_solve, double t_factor,
+                                    int loops_left, int* kinds) {
+    if (!node_iters || !kinds || ne <= 0) return 0;
+    std::vector<int> idx(ne);
+    for (int e = 0; e < ne; ++e) { idx[e] = e; kinds[e] = 0; }
+    std::stable_sort(idx.begin(), idx.end(), [&](int a, int b) { return node_iters[a] > node_iters[b]; });
+    const double per_node = t_solve + t_factor / (double)std::max(loops_left, 1);
+    const int kmax = std::min(std::max(max_direct, 0), ne);
+    int best = 0;
+    double best_t = 0.0;
+    for (int k = 0; k <= kmax; ++k) {
+        const double t = t_iter * (double)(k < ne ? node_iters[idx[k]] : 0) + (double)k * per_node;
+        if (k == 0 || t < best_t) { best = k; best_t = t; }
+    }
+    for (int k = 0; k < best; ++k) kinds[idx[k]] = 4;
+    return best;
+}
+
 }   // namespace fh_policy

@@ -1241,6 +1241,29 @@ __global__ __launch_bounds__(FH_BLOCK) void k_sum_finish(const cplx* __restrict_
     }
 }
 
+// Q_proj of a per-node sweep in sum mode (feasthip_set_node_solver): the Krylov nodes left ACC (and, with a Ritz warm start,
+// the closed-form SRC * rho_c over the Krylov nodes only), the direct nodes left one solution panel each:
+//     OUT = [Re] ( SRC * rho_c + ACC + sum_d wd[d] Yd[d] ),  d ascending -- a fixed order, so the result is reproducible.
+// One pass: (2 + nd [+ 1]) panels of 16 B per element, each element read or written once, 16-byte accesses, no atomics;
+// the nd weights go through LDS once per workgroup.
+template <int LD>
+__global__ __launch_bounds__(FH_BLOCK) void k_node_finish(const cplx* __restrict__ src, const cplx* __restrict__ rho,
+                                                           const cplx* __restrict__ acc, const cplx* __restrict__ Yd, size_t stride,
+                                                           const cplx* __restrict__ wd, int nd, cplx* __restrict__ out, size_t total,
+                                                           int real_part) {
+    __shared__ cplx sw[FH_NODE_FINISH_MAX];
+    if ((int)threadIdx.x < nd) sw[threadIdx.x] = wd[threadIdx.x];
+    __syncthreads();
+    const cplx rc = rho ? rho[threadIdx.x % LD] : cmake(0, 0);
+    for (size_t e = (size_t)blockIdx.x * FH_BLOCK + threadIdx.x; e < total; e += (size_t)gridDim.x * FH_BLOCK) {
+        cplx v = acc[e];
+        if (rho) cfma(v, rc, src[e]);
+        for (int d = 0; d < nd; ++d) cfma(v, sw[d], Yd[(size_t)d * stride + e]);
+        if (real_part) v.y = 0.0;
+        out[e] = v;
+    }
+}
+
 template <typename CT, int LD>
 __global__ __launch_bounds__(FH_BLOCK) void k_cocg_update(fh_vec_args a) {
     // X += alpha P ; R -= alpha Q (Q stored in V) ; partial1 = sum R*R, partial2 = sum |R|^2
@@ -1680,6 +1703,14 @@ void fh_launch_sum_finish(const cplx* src, const cplx* rho, const cplx* acc, cpl
     if (ld == 16) hipLaunchKernelGGL((k_sum_finish<16>), dim3(nblk), dim3(FH_BLOCK), 0, st, src, rho, acc, out, total, real_part);
     else if (ld == 32) hipLaunchKernelGGL((k_sum_finish<32>), dim3(nblk), dim3(FH_BLOCK), 0, st, src, rho, acc, out, total, real_part);
     else hipLaunchKernelGGL((k_sum_finish<64>), dim3(nblk), dim3(FH_BLOCK), 0, st, src, rho, acc, out, total, real_part);
+}
+void fh_launch_node_finish(const cplx* src, const cplx* rho, const cplx* acc, const cplx* Yd, size_t stride, const cplx* wd, int nd,
+                           cplx* out, int N, int ld, int real_part, hipStream_t st) {
+    const size_t total = (size_t)N * ld;
+    const int nblk = (int)std::min<size_t>((total + FH_BLOCK - 1) / FH_BLOCK, 2048);
+    if (ld == 16) hipLaunchKernelGGL((k_node_finish<16>), dim3(nblk), dim3(FH_BLOCK), 0, st, src, rho, acc, Yd, stride, wd, nd, out, total, real_part);
+    else if (ld == 32) hipLaunchKernelGGL((k_node_finish<32>), dim3(nblk), dim3(FH_BLOCK), 0, st, src, rho, acc, Yd, stride, wd, nd, out, total, real_part);
+    else hipLaunchKernelGGL((k_node_finish<64>), dim3(nblk), dim3(FH_BLOCK), 0, st, src, rho, acc, Yd, stride, wd, nd, out, total, real_part);
 }
 void fh_launch_cocg_update(const fh_vec_args& a, int ld, int nblk, int nodes, hipStream_t st) {
     FH_DISPATCH_VEC(a.prec, ld, k_cocg_update, dim3(nblk, nodes), st, a);

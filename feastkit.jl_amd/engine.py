@@ -254,6 +254,15 @@ class HipEngine:
         self._chk(self.lib.feasthip_set_solver(self.h, _SOLVER_CODES[solver], float(rtol), float(atol), int(maxit),
                                                int(restart), int(factor_precision), int(bool(cache_factors))))
 
+    def set_node_solver(self, kinds):
+        """Per-node solver (feasthip_set_node_solver): ``kinds[e]`` per GLOBAL contour node, 0 = the handle's solver,
+        4 (``banded``) = a sparse direct solve for that node; ``None`` clears the setting."""
+        if kinds is None:
+            self._chk(self.lib.feasthip_set_node_solver(self.h, 0, None))
+            return
+        k = np.ascontiguousarray(kinds, dtype=np.int32)
+        self._chk(self.lib.feasthip_set_node_solver(self.h, len(k), _np_ptr(k)))
+
     # -- device arrays (plumbing) -----------------------------------------------------
     def set_column_mask(self, mask):
         """mask[c] == 0: column c is not iterated by the Krylov solvers (keeps its warm start);
@@ -461,6 +470,12 @@ class HipEngine:
         fl = C.c_double(0.0)
         self._chk(self.lib.feasthip_direct_plan_flops(self.h, C.byref(fl)))
         return fl.value
+
+    def direct_plan_bytes(self, nodes):
+        """(factor bytes, transient bytes) that ``nodes`` direct nodes take on the device (feasthip_direct_plan_bytes)."""
+        fb, tb = C.c_int64(0), C.c_int64(0)
+        self._chk(self.lib.feasthip_direct_plan_bytes(self.h, int(nodes), C.byref(fb), C.byref(tb)))
+        return fb.value, tb.value
 
     def last_node_iterations(self, n):
         out = np.zeros(max(1, n), dtype=np.int32)

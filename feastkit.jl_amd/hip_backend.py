@@ -23,6 +23,7 @@ The reduced M0 x M0 eigenproblem stays on host LAPACK (SURVEY.md section 8 row a
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import math
 import threading
@@ -290,6 +291,179 @@ class _NodeLayout:
             stats["local_nodes"] = [int(v) for v in self.local_nodes]
 
 
+NODE_SOLVER_SOLVERS = ("cocg", "bicgstab", "iterative")     # handle solvers a per-node sweep can mix with direct nodes
+NODE_SOLVER_DIRECT = 4                                      # FEASTHIP_SOLVER_BANDED
+DIRECT_FLOP_RATE = 1.3e13                                   # flop/s of the sparse direct solver (api.feast's hand-over estimate)
+# flop/s of its substitution with 64 right-hand sides inside a sweep, measured on cfg 3 (tools/node_solver_probe.py, DESIGN.md
+# section 6g: a loop that factors nothing spends 14.2 ms per direct node beyond its Krylov chain, for 2.2e10 flop)
+DIRECT_SOLVE_RATE = 1.55e12
+
+
+def check_direct_nodes(direct_nodes, ne, sparse, solver):
+    """Host-only validation of the ``direct_nodes`` keyword (no device work) -> None, "auto", an int k or a sorted index list."""
+    if direct_nodes is None:
+        return None
+    if not sparse:
+        raise ValueError("direct_nodes needs sparse input (the per-node solver mixes Krylov sweeps with sparse direct solves)")
+    if solver not in NODE_SOLVER_SOLVERS:
+        raise ValueError(f"direct_nodes needs solver 'cocg', 'bicgstab' or 'iterative', not '{solver}'")
+    if isinstance(direct_nodes, str):
+        if direct_nodes != "auto":
+            raise ValueError("direct_nodes must be None, a list of node indices, an int or 'auto'")
+        return "auto"
+    if isinstance(direct_nodes, (bool, float, np.floating)):
+        raise ValueError("direct_nodes must be None, a list of node indices, an int or 'auto'")
+    if isinstance(direct_nodes, (int, np.integer)):
+        if not 0 <= int(direct_nodes) <= ne:
+            raise ValueError(f"direct_nodes={int(direct_nodes)}: between 0 and the node count {ne}")
+        return int(direct_nodes)
+    try:
+        idx = [v for v in direct_nodes]
+    except TypeError:
+        raise ValueError("direct_nodes must be None, a list of node indices, an int or 'auto'") from None
+    if any(isinstance(v, (bool, float, str)) or not isinstance(v, (int, np.integer)) for v in idx):
+        raise ValueError("direct_nodes: node indices must be integers")
+    if any(not 0 <= int(v) < ne for v in idx):
+        raise ValueError(f"direct_nodes: node indices must lie in 0..{ne - 1}")
+    return sorted(set(int(v) for v in idx))
+
+
+class _DirectNodes:
+    """The ``direct_nodes`` keyword of the host drivers: which contour nodes (GLOBAL indices) the sweeps solve directly
+    (feasthip_set_node_solver), chosen up front (a list), after the first loop (an int k: the k slowest nodes) or after every
+    loop by feasthip_policy_pick_direct_nodes ("auto").  Every rank derives the same set from the global iteration vector.
+    ``log`` becomes stats["direct_nodes"]: one entry per loop."""
+
+    def __init__(self, engine, spec, ne, m, world):
+        self.engine, self.spec, self.ne, self.m, self.world = engine, spec, ne, m, world
+        self.nodes, self.log, self.note = [], [], None
+        self.t_iter = self.t_solve = self.t_factor = None        # "auto": the measured inputs of the selection rule
+        self.max_fit = self._fit()
+        if isinstance(spec, list):
+            if len(spec) > self.max_fit:
+                raise ValueError(f"direct_nodes: the factors of {len(spec)} nodes do not fit the free device memory "
+                                 f"({self.max_fit} would)")
+            self.nodes = list(spec)
+        elif spec != "auto" and spec > self.max_fit:
+            self.note = f"shrunk from {spec} to {self.max_fit}: device memory"
+        self._apply()
+
+    def _fit(self):
+        """How many direct nodes fit: cached factors plus the transient buffers of their factorisation and sweep
+        (feasthip_direct_plan_bytes, linear in the node count) within the share of the free device memory the library's own
+        slot allocation accepts (0.92, band_ensure_slots); the smallest answer over the ranks."""
+        import torch
+        free, _total = torch.cuda.mem_get_info(self.engine.device)
+        fb, tb = self.engine.direct_plan_bytes(1)
+        k = min(self.ne, int(0.92 * free // max(1, fb + tb)))
+        if self.world > 1:
+            k = int(round(-self.engine.max_over_ranks(-k)))
+        return k
+
+    def _apply(self):
+        kinds = np.zeros(self.ne, dtype=np.int32)
+        kinds[self.nodes] = NODE_SOLVER_DIRECT
+        self.engine.set_node_solver(kinds if self.nodes else None)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.engine.set_node_solver(None)
+        return False
+
+    def record(self, loop_idx, st, local_nodes=None):
+        """One entry for the loop just swept: the nodes in force and what it factored (summed over the ranks).  Everything
+        the choice below rests on is made rank-independent here: the global iteration vector, and -- one small all-reduce
+        -- every rank's sweep seconds, factorisations and local direct nodes, of which the slowest rank's are kept."""
+        eng = self.engine
+        self.iters = np.asarray(eng.last_global_node_iterations() if self.world > 1 else eng.last_node_iterations(self.ne),
+                                dtype=np.int32)
+        if local_nodes is None:                       # the block partition of _setup_sweep
+            first, count = distribute_contour_points(self.ne, self.world)[eng.comm_rank]
+            local_nodes = range(first, first + count)
+        nd = len(set(self.nodes) & set(int(v) for v in local_nodes))
+        mine = [float(st.get("seconds_solve", 0.0)), float(st.get("factorizations", 0)), float(nd)]
+        if self.world > 1:
+            t = eng.torch.zeros((self.world, 3), dtype=eng.torch.float64, device=eng.device)
+            t[eng.comm_rank] = eng.torch.tensor(mine, dtype=eng.torch.float64, device=eng.device)
+            rows = eng.allreduce_sum_(t).cpu().numpy()
+        else:
+            rows = np.array([mine])
+        self.sweep = tuple(float(v) for v in rows[int(np.argmax(rows[:, 0]))])       # (seconds, factorisations, direct nodes)
+        self.log.append({"loop": int(loop_idx), "nodes": list(self.nodes), "factorizations": int(round(rows[:, 1].sum()))})
+        if self.note:
+            self.log[-1]["note"] = self.note
+
+    def _loops_left(self, loop_idx, eps_hist, eps_tol, maxloop):
+        """Loops still to come: from the contraction of the last two outer residuals, at most what fpm[4] leaves."""
+        fin = [e for e in eps_hist if np.isfinite(e) and e > 0]
+        left = maxloop - loop_idx
+        if len(fin) >= 2 and fin[-1] < fin[-2]:
+            left = min(left, int(math.ceil(max(1.0, math.log(eps_tol / fin[-1]) / math.log(fin[-1] / fin[-2])))))
+        return max(1, left)
+
+    def _calibrate(self):
+        """The three times of the selection rule.  t_iter: the last all-Krylov sweep's seconds per iteration of its longest
+        node (a sweep with direct nodes also spends their solves).  t_factor, t_solve: the flop model (feasthip_direct_plan_flops
+        / DIRECT_FLOP_RATE; one complex multiply-add per factor entry and column / DIRECT_SOLVE_RATE), raised to what the sweeps
+        with direct nodes spend beyond their Krylov chain: a sweep that factored nothing gives t_solve, one that factored t_factor."""
+        secs, nfact, nd = self.sweep
+        chain = int(self.iters.max())
+        if nd == 0 or self.t_iter is None:
+            self.t_iter = secs / max(1, chain)
+        if self.t_solve is None:
+            fb, _tb = self.engine.direct_plan_bytes(1)
+            self.t_factor = self.engine.direct_plan_flops() / DIRECT_FLOP_RATE
+            self.t_solve = 8.0 * (fb / 16.0) * self.m / DIRECT_SOLVE_RATE
+        beyond = secs - self.t_iter * chain
+        if nd and nfact == 0:
+            self.t_solve = max(self.t_solve, beyond / nd)
+        elif nd:
+            self.t_factor = max(self.t_factor, (beyond - nd * self.t_solve) / nfact)
+        return self.t_iter, self.t_solve, self.t_factor
+
+    def choose(self, loop_idx, eps_hist, eps_tol, maxloop):
+        """The nodes of the next loop, after a loop that did not converge."""
+        iters, entry = self.iters, self.log[-1]
+        room = self.max_fit - len(self.nodes)
+        if isinstance(self.spec, list) or room <= 0 or not iters.any():
+            return
+        order = sorted(range(self.ne), key=lambda e: (-int(iters[e]), e))
+        new = []
+        if self.spec == "auto":
+            left = self._loops_left(loop_idx, eps_hist, eps_tol, maxloop)
+            t_iter, t_solve, t_factor = self._calibrate()
+            kinds = np.zeros(self.ne, dtype=np.int32)
+            it_c = np.ascontiguousarray(iters, dtype=np.int32)
+            k = _lib.load_library().feasthip_policy_pick_direct_nodes(
+                it_c.ctypes.data_as(ctypes.c_void_p), self.ne, int(room), t_iter, t_solve, t_factor, int(left),
+                kinds.ctypes.data_as(ctypes.c_void_p))
+            new = [int(e) for e in np.nonzero(kinds)[0]]
+            # the rule's own prediction: the all-Krylov loop against the loop with its k nodes direct
+            t_none = t_iter * int(iters[order[0]])
+            t_pick = t_iter * (int(iters[order[k]]) if k < self.ne else 0) + k * (t_solve + t_factor / left)
+            entry.update(t_iter=t_iter, t_solve=t_solve, t_factor=t_factor, loops_left=int(left), predicted_gain=t_none - t_pick)
+        elif loop_idx == 0:
+            new = [e for e in order[:min(int(self.spec), room)] if iters[e] > 0]
+        if new:
+            self.nodes = sorted(set(self.nodes) | set(new))         # a node once chosen stays chosen
+            self._apply()
+
+
+def _direct_nodes_scope(engine, direct_nodes, ne, sparse, solver, m, world, stats, inner_precision=64):
+    """The drivers' ``direct_nodes`` keyword as a context: the kinds are set for the loops inside and cleared on every way
+    out; ``stats["direct_nodes"]`` is the per-loop log.  None: nothing changes."""
+    if direct_nodes is None:
+        return contextlib.nullcontext()
+    spec = check_direct_nodes(direct_nodes, ne, sparse, solver)
+    if inner_precision != 64:
+        raise ValueError("direct_nodes needs inner_precision=64")
+    dn = _DirectNodes(engine, spec, ne, m, world)
+    stats["direct_nodes"] = dn.log
+    return dn
+
+
 class _InexactPolicy(_lib.FeastHipPolicy):
     """The inexact mode's host policy under the C ABI (feasthip_policy_*, csrc/fh_policy.hpp); fields are the C struct's.
     hist, reach: fpm[18] and the subspace reach of every loop under contour steering."""
@@ -433,7 +607,8 @@ def feast_hip_hermitian(engine, A, B, Emin, Emax, M0, fpm, *, freeze_guards_afte
                         solver_maxiter=500, solver_restart=30, warm_start=True, inner_rtol=None,
                         real_projection=None, group=None, Q0=None, seed=20260515, contour=None, trace=None,
                         preloaded=False, node_assignment="block", inner_precision=64, column_groups=1,
-                        spurious_filter=True, contour_policy=None, eps_floor=0.0, abort_check=None, resident_panels=True):
+                        spurious_filter=True, contour_policy=None, eps_floor=0.0, abort_check=None, resident_panels=True,
+                        direct_nodes=None):
     """Variant A on the :hip engine.  Returns FeastResult (complex Ritz vectors, like
     _feast_dense_complex_hermitian; real-symmetric callers take real.(q) as the reference
     does, src/dense/feast_dense.jl:372-387).
@@ -471,6 +646,10 @@ def feast_hip_hermitian(engine, A, B, Emin, Emax, M0, fpm, *, freeze_guards_afte
       the a-priori 1.4 half widths of a subspace 1.5 times the eigenvalue count).  Safeguard: when a loop contracts
       the residual by less than 0.3 although the policy promised better, then -- if inner solves stopped at the iteration
       cap -- the cap is doubled, else the ratio is halved for the next loops, down to the reference's circle.
+    direct_nodes: None | list of GLOBAL node indices | int k | "auto" (sparse input, cocg / bicgstab): those contour nodes are
+      solved by the sparse direct solver inside the Krylov sweep (feasthip_set_node_solver) -- the list in every loop, the k
+      slowest nodes of the first loop from the second on, or what feasthip_policy_pick_direct_nodes picks after every loop.
+      ``stats["direct_nodes"]`` has one entry per loop; ``stats["node_iterations"]`` shows 0 for a direct node.
     """
     N = A.shape[0]
     feastdefault(fpm)
@@ -542,7 +721,9 @@ def feast_hip_hermitian(engine, A, B, Emin, Emax, M0, fpm, *, freeze_guards_afte
     resident = bool(getattr(engine, "resident", False)) and M0 <= 64 and reduced_solver != "device" and resident_panels
     # one BLAS thread for the whole solve; the `with` releases the process-wide limit on every way out, including an
     # exception from the engine inside the loop (FeastHipError, a poisoned handle)
-    with small_lapack():
+    import scipy.sparse as _sp
+    with small_lapack(), _direct_nodes_scope(engine, direct_nodes, len(Zne), _sp.issparse(A), solver, M0, world, stats,
+                                             inner_precision) as dn:
         for loop_idx in range(0, maxloop + 1):
             loop_count = loop_idx
             # -- sweep
@@ -576,6 +757,8 @@ def feast_hip_hermitian(engine, A, B, Emin, Emax, M0, fpm, *, freeze_guards_afte
             if hasattr(engine, "last_node_iterations"):
                 stats["node_iterations"].append([int(v) for v in engine.last_node_iterations(layout.count)])
                 stats["node_lists"].append([int(v) for v in layout.local_nodes])
+            if dn is not None:
+                dn.record(loop_idx, st, layout.local_nodes)
             layout.rebalance(engine, loop_idx, active, stats)
             # direct: singular shift -> info 8 (src/dense/feast_dense.jl:199-203); reference GMRES failure -> info 5
             # (src/dense/feast_dense.jl:221-225).  Warm-started solves go on past a Krylov failure (5): the next loop
@@ -661,6 +844,9 @@ def feast_hip_hermitian(engine, A, B, Emin, Emax, M0, fpm, *, freeze_guards_afte
                         pol.hist.append(pol.aspect)
                         pol.reach.append(None if pol.last_reach < 0 else round(pol.last_reach, 3))
 
+            if dn is not None:
+                dn.choose(loop_idx, [l["epsout"] for l in stats["loops"]], eps_tol, maxloop)
+
             # -- next loop
             active = rank_q
             dQ = dX                                   # Q_basis[:, 1:rank] = solutions[:, 1:rank]
@@ -717,7 +903,8 @@ def feast_hip_estimate(engine, A, B, Zne, Wne, weight_scale, m, *, general=False
 
 
 def feast_hip_general(engine, A, B, Emid, r, M0, fpm, *, solver="direct", solver_tol=0.0, solver_maxiter=500,
-                      solver_restart=30, group=None, Q0=None, seed=20260515, inner_precision=64, contour=None, eps_floor=0.0):
+                      solver_restart=30, group=None, Q0=None, seed=20260515, inner_precision=64, contour=None, eps_floor=0.0,
+                      direct_nodes=None):
     """Variant C (general, full contour, no factor 2, no orthonormalisation, residual
     without B): src/kernel/feast_kernel.jl:752-950 driven as in src/dense/feast_dense.jl:468-584."""
     N = A.shape[0]
@@ -739,42 +926,49 @@ def feast_hip_general(engine, A, B, Emid, r, M0, fpm, *, solver="direct", solver
     maxloop = int(fpm[4])
     loop = 0
     stats = {"krylov_iterations": 0, "factorizations": 0, "solve_seconds": 0.0}
-    epsout = math.inf
-    while True:
-        if inner_precision == 32:
-            # inexact FEAST: the complex64 solves are refined only as far as the current outer residual needs
-            ref_tol = 1.0 if not math.isfinite(epsout) else min(1.0, max(1e-14, 1e-2 * epsout))
-            engine.set_solver(solver, rtol=ref_tol, atol=0.0, maxit=solver_maxiter, restart=solver_restart,
-                              cache_factors=True, factor_precision=32)
-        fail, (dq, status, st) = _sweep(engine, dQ, M0, world, count, stats)
-        if fail:
-            return _empty_result(N, FeastError.Feast_ERROR_LAPACK if fail == 8 else FeastError.Feast_ERROR_NO_CONVERGENCE,
-                                 loop, complex_lambda=True, stats=stats)
-        Aq, Sq = engine.project(dq, M0, bilinear=False, hermitize=False)   # Aq = q^H A q, Sq = q^H B q
-        try:
-            with small_lapack():
-                lam_red, v_red = sla.eig(Aq, Sq)                            # feast_kernel.jl:812
-        except Exception:
-            return _empty_result(N, FeastError.Feast_ERROR_LAPACK, loop, complex_lambda=True, stats=stats)
-        perm, M = _reorder_by_contour(lam_red, Emid, r, fpm, M0)
-        if M == 0:
-            return _empty_result(N, FeastError.Feast_ERROR_NO_CONVERGENCE, loop, complex_lambda=True, stats=stats)
-        lam = lam_red[perm]
-        V = np.asfortranarray(v_red[:, perm])
-        # normalise ALL M0 columns (feast_kernel.jl:864-876); residual WITHOUT B (:899-906)
-        dX, res = engine.ritz_residual(dq, M0, V, lam, M0, normalize=True, use_B=False)
-        res = res[:M]
-        epsout = float(res.max())
-        if epsout <= eps_tol or loop >= maxloop:
-            order = sorted(range(M), key=lambda i: abs(lam[i]) ** 2)         # feast_sort_general!
-            X = engine.download(dX, M0)
-            return FeastResult(lam[:M][order].copy(), X[:, :M][:, order].copy(), M, res[order].copy(), 0, epsout, loop, stats)
-        loop += 1
-        dQ = dX
+    epsout, eps_hist = math.inf, []
+    import scipy.sparse as _sp
+    with _direct_nodes_scope(engine, direct_nodes, len(Zne), _sp.issparse(A), solver, M0, world, stats, inner_precision) as dn:
+        while True:
+            if inner_precision == 32:
+                # inexact FEAST: the complex64 solves are refined only as far as the current outer residual needs
+                ref_tol = 1.0 if not math.isfinite(epsout) else min(1.0, max(1e-14, 1e-2 * epsout))
+                engine.set_solver(solver, rtol=ref_tol, atol=0.0, maxit=solver_maxiter, restart=solver_restart,
+                                  cache_factors=True, factor_precision=32)
+            fail, (dq, status, st) = _sweep(engine, dQ, M0, world, count, stats)
+            if dn is not None:
+                dn.record(loop, st)
+            if fail:
+                return _empty_result(N, FeastError.Feast_ERROR_LAPACK if fail == 8 else FeastError.Feast_ERROR_NO_CONVERGENCE,
+                                     loop, complex_lambda=True, stats=stats)
+            Aq, Sq = engine.project(dq, M0, bilinear=False, hermitize=False)   # Aq = q^H A q, Sq = q^H B q
+            try:
+                with small_lapack():
+                    lam_red, v_red = sla.eig(Aq, Sq)                            # feast_kernel.jl:812
+            except Exception:
+                return _empty_result(N, FeastError.Feast_ERROR_LAPACK, loop, complex_lambda=True, stats=stats)
+            perm, M = _reorder_by_contour(lam_red, Emid, r, fpm, M0)
+            if M == 0:
+                return _empty_result(N, FeastError.Feast_ERROR_NO_CONVERGENCE, loop, complex_lambda=True, stats=stats)
+            lam = lam_red[perm]
+            V = np.asfortranarray(v_red[:, perm])
+            # normalise ALL M0 columns (feast_kernel.jl:864-876); residual WITHOUT B (:899-906)
+            dX, res = engine.ritz_residual(dq, M0, V, lam, M0, normalize=True, use_B=False)
+            res = res[:M]
+            epsout = float(res.max())
+            if epsout <= eps_tol or loop >= maxloop:
+                order = sorted(range(M), key=lambda i: abs(lam[i]) ** 2)         # feast_sort_general!
+                X = engine.download(dX, M0)
+                return FeastResult(lam[:M][order].copy(), X[:, :M][:, order].copy(), M, res[order].copy(), 0, epsout, loop, stats)
+            if dn is not None:
+                eps_hist.append(epsout)
+                dn.choose(loop, eps_hist, eps_tol, maxloop)
+            loop += 1
+            dQ = dX
 
 
 def feast_hip_complex_symmetric(engine, A, B, Emid, r, M0, fpm, *, solver="direct", solver_tol=0.0,
-                                solver_maxiter=500, solver_restart=30, group=None, Q0=None, seed=20260515):
+                                solver_maxiter=500, solver_restart=30, group=None, Q0=None, seed=20260515, direct_nodes=None):
     """Complex-symmetric sibling of variant A (A == A^T, B == B^T, complex): the loop of
     _feast_dense_complex_symmetric / its sparse twin (src/dense/feast_dense.jl:1026-1259,
     src/sparse/feast_sparse.jl:509-711).  Same kernels as the Hermitian path with the full
@@ -801,38 +995,44 @@ def feast_hip_complex_symmetric(engine, A, B, Emid, r, M0, fpm, *, solver="direc
     _configure_solver(engine, solver, fpm, solver_tol, solver_maxiter, solver_restart)
     dQ = engine.upload(seeded_subspace(N, M0, seed, complex_values=True) if Q0 is None else np.asarray(Q0, dtype=np.complex128))
     done = _LoopRecord(M0, feast_tolerance(fpm), int(fpm[4]), dtype=np.complex128)
-    info, active, loop_count, dX = 0, M0, 0, None
+    info, active, loop_count, dX, eps_hist = 0, M0, 0, None, []
     stats = {"krylov_iterations": 0, "factorizations": 0, "solve_seconds": 0.0}
-    for loop_idx in range(0, done.maxloop + 1):
-        loop_count = loop_idx
-        fail, (dP, status, st) = _sweep(engine, dQ, active, world, count, stats)
-        if fail:
-            info = int(FeastError.Feast_ERROR_LAPACK if fail == 8 else FeastError.Feast_ERROR_NO_CONVERGENCE)
-            break
-        rank_q = engine.orthonormalize(dP, active, SQRT_EPS)                  # _feast_qr_compress!, :1163
-        if rank_q == 0:
-            info = int(FeastError.Feast_ERROR_NO_CONVERGENCE)
-            break
-        Ared, Bred = engine.project(dP, rank_q, bilinear=True, hermitize=False)   # q^T A q, q^T B q
-        try:
-            with small_lapack():
-                lam_red, v_red = sla.eig(Ared, Bred)
-        except Exception:
-            info = int(FeastError.Feast_ERROR_LAPACK)
-            break
-        perm, M = _reorder_by_contour(lam_red, Emid, r, fpm, rank_q)
-        if M == 0:
-            info = int(FeastError.Feast_ERROR_NO_CONVERGENCE)
-            break
-        lam_sorted = lam_red[perm]
-        V = np.asfortranarray(v_red[:, perm])
-        dX, res = engine.ritz_residual(dP, rank_q, V, lam_sorted, rank_q, normalize=True, use_B=True)
-        stop = done.record(loop_idx, rank_q, lam_sorted, M, res)
-        if stop is not None:
-            info = stop
-            break
-        active = rank_q
-        dQ = dX
+    with _direct_nodes_scope(engine, direct_nodes, len(Zne), _sp.issparse(A), solver, M0, world, stats) as dn:
+        for loop_idx in range(0, done.maxloop + 1):
+            loop_count = loop_idx
+            fail, (dP, status, st) = _sweep(engine, dQ, active, world, count, stats)
+            if dn is not None:
+                dn.record(loop_idx, st)
+            if fail:
+                info = int(FeastError.Feast_ERROR_LAPACK if fail == 8 else FeastError.Feast_ERROR_NO_CONVERGENCE)
+                break
+            rank_q = engine.orthonormalize(dP, active, SQRT_EPS)                  # _feast_qr_compress!, :1163
+            if rank_q == 0:
+                info = int(FeastError.Feast_ERROR_NO_CONVERGENCE)
+                break
+            Ared, Bred = engine.project(dP, rank_q, bilinear=True, hermitize=False)   # q^T A q, q^T B q
+            try:
+                with small_lapack():
+                    lam_red, v_red = sla.eig(Ared, Bred)
+            except Exception:
+                info = int(FeastError.Feast_ERROR_LAPACK)
+                break
+            perm, M = _reorder_by_contour(lam_red, Emid, r, fpm, rank_q)
+            if M == 0:
+                info = int(FeastError.Feast_ERROR_NO_CONVERGENCE)
+                break
+            lam_sorted = lam_red[perm]
+            V = np.asfortranarray(v_red[:, perm])
+            dX, res = engine.ritz_residual(dP, rank_q, V, lam_sorted, rank_q, normalize=True, use_B=True)
+            stop = done.record(loop_idx, rank_q, lam_sorted, M, res)
+            if stop is not None:
+                info = stop
+                break
+            if dn is not None:
+                eps_hist.append(done.epsout)
+                dn.choose(loop_idx, eps_hist, done.eps_tol, done.maxloop)
+            active = rank_q
+            dQ = dX
     M_found = done.M_found
     X = engine.download(dX, M_found) if M_found > 0 else np.zeros((N, 0), complex)
     order = sorted(range(M_found), key=lambda i: abs(done.lam_vec[i]) ** 2)         # feast_sort_general!

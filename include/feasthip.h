@@ -216,6 +216,26 @@ int  feasthip_direct_plan_flops(feasthip_handle h, double* flops_per_node);
 int  feasthip_set_solver(feasthip_handle h, int kind, double rtol, double atol, int maxit,
                          int restart, int factor_precision, int cache_factors);
 
+/* Per-node solver: a sparse direct solve for chosen quadrature nodes of a Krylov sweep.  The reference picks ONE solver per
+ * driver call by keyword -- the iterative branch src/sparse/feast_sparse.jl:164-203, `lu(zB - A)` per node :334-342 -- so a
+ * sweep whose chain length is set by the one or two nodes nearest the real axis pays their iteration count on every node.
+ * kinds[e], indexed by GLOBAL contour node (like node_status under a communicator): 0 = the handle's solver
+ * (feasthip_set_solver), FEASTHIP_SOLVER_BANDED = factor z_e B - A and solve directly; anything else: FEASTHIP_ERROR_FPM.
+ * count == 0 or kinds == NULL clears the setting; otherwise count must be the contour's node count (FEASTHIP_ERROR_FPM).
+ * Persistent until cleared; feasthip_set_contour with another node count clears it.  Honoured by feasthip_contour_apply,
+ * _dev, _resident and feasthip_estimate_count for a CSR problem whose handle solver is COCG or BICGSTAB with
+ * factor_precision = 64; with GMRES, a dense problem or factor_precision = 32 and at least one local direct node the sweep
+ * returns FEASTHIP_ERROR_FPM (a handle whose own solver is BANDED solves every node directly: the kinds change nothing).
+ * feasthip_shifted_solve ignores it.  Direct nodes share the factor cache of FEASTHIP_SOLVER_BANDED, matched by z_e: a
+ * repeated sweep on the same contour factors nothing (cache_factors), a moved contour factors them again, and
+ * feasthip_stats.factorizations counts what the call factored; feasthip_release_factors frees them.  They ignore the column
+ * mask and the warm start, report node_status 0 or 8, and 0 iterations in feasthip_last_[global_]node_iterations.        */
+int  feasthip_set_node_solver(feasthip_handle h, int count, const int* kinds);
+/* Device memory `nodes` direct nodes take under the plan feasthip_band_plan reports: *factor_bytes for the cached factors and
+ * pivots, *transient_bytes for what lives only while they are factored and swept (multifrontal work arena and substitution
+ * panels).  A host shim sizes the direct subset of feasthip_set_node_solver with it.                                       */
+int  feasthip_direct_plan_bytes(feasthip_handle h, int nodes, int64_t* factor_bytes, int64_t* transient_bytes);
+
 /* ---- host policy of the inexact FEAST mode (no device work; needs no problem and no GPU) -----------------------------
  * What the :hip backend adds to the reference's driver loop when `solver = :direct` on large sparse input is served by the
  * warm-started, inexact Krylov sweeps (not in the reference; DESIGN.md sections 2 and 5): which ellipse ratio fpm[18] to put
@@ -246,6 +266,14 @@ int    feasthip_policy_init(feasthip_policy* p, double Emin, double Emax, int ne
                             double outer_tol, int solver_maxiter, int steer, int fpm18);
 int    feasthip_policy_update(feasthip_policy* p, double epsout, int M, int any_node_capped, const double* ritz, int nritz);
 int    feasthip_policy_set_aside(const double* res, int M, int* flags);
+/* Which nodes feasthip_set_node_solver should make direct (host arithmetic only).  Nodes ordered by node_iters descending,
+ * ties to the lower index; with the first k of them direct one further loop is predicted to take
+ *   t_iter * max(node_iters of the others) + k * (t_solve + t_factor / max(loops_left, 1))   seconds
+ * (t_iter: one Krylov iteration of the sweep, t_solve / t_factor: one node's substitution / factorisation).  Takes the
+ * smallest k in 0..max_direct that minimises it, writes kinds[e] = FEASTHIP_SOLVER_BANDED for the chosen nodes and 0 for the
+ * rest, returns k (0: the all-Krylov sweep is predicted fastest).                                                          */
+int    feasthip_policy_pick_direct_nodes(const int* node_iters, int ne, int max_direct, double t_iter, double t_solve,
+                                         double t_factor, int loops_left, int* kinds);
 double feasthip_policy_filter_ratio(double Emin, double Emax, int ne, int quadrature, int fpm18, double reach,
                                     const double* inside, int n_inside);
 double feasthip_policy_reach(const double* ritz, int n, double Emin, double Emax, double quantile);
