@@ -540,6 +540,23 @@ def test_contour_apply_is_bitwise_reproducible(engine, solver):
     engine.set_real_projection(False)
     assert np.array_equal(outs[0], outs[1]) and np.array_equal(outs[1], outs[2])
     assert np.isfinite(outs[0]).all() and np.abs(outs[0]).max() > 0
+    # ... and those bits are the step-exact restatement's sweep (krylov_reference.py) within 32 x its own fp64 drift.
+    # COCG only: at rtol = 1e-3 / 60 steps the BiCGStab restatement does not agree with itself in fp64 on the node next
+    # to Emax (its drift is O(1) there), so no tolerance could tell a defect from rounding; BiCGStab sweeps are compared
+    # in test_gpu_krylov_steps.py at settings where it does.
+    if solver != "cocg":
+        return
+    import krylov_cases as kc
+    import krylov_reference as kr
+    c = kc.sweep_case("cocg_fused", 1e-3, 60, 24, True)
+    assert np.array_equal(c.Q, fk.seeded_subspace(N, 24)) and np.array_equal(c.ritz, ritz) and np.array_equal(c.Z, Z)
+    assert c.fp64_steps_agree and (~c.decided).sum() <= kc.LEFT_OUT_MAX * c.decided.size
+    assert 32.0 * c.drift[True] <= kc.POWER
+    ok = np.flatnonzero(c.col_ok)
+    assert kr.block_dist(outs[0][:, ok], kc.project(c.ref.out, True)[:, ok]) <= kr.tolerance(c.drift[True])
+    if c.decided.all():
+        assert list(status[:8]) == list(c.ref.status)
+        assert np.array_equal(engine.last_column_iterations(8, 24), c.ref.steps)
 
 
 @pytest.mark.parametrize("N,r,generalized,cplx", [(60, 5, False, False), (300, 17, True, False), (800, 32, True, True),
