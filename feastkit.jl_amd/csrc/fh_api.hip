@@ -484,11 +484,14 @@ extern "C" int feasthip_set_column_mask(feasthip_handle h, int64_t m, const int*
 extern "C" int feasthip_set_solver(feasthip_handle h, int kind, double rtol, double atol, int maxit, int restart,
                                    int factor_precision, int cache_factors) {
     if (!h) return FEASTHIP_ERROR_INTERNAL;
-    if (kind < 0 || kind > 4 || rtol < 0 || atol < 0 || maxit <= 0 || restart < 0 ||
+    if (kind < 0 || kind > FEASTHIP_SOLVER_SHIFTED_COCG || rtol < 0 || atol < 0 || maxit <= 0 || restart < 0 ||
         (factor_precision != 64 && factor_precision != 32)) {
         h->last_error = "feasthip_set_solver: invalid option";
         return FEASTHIP_ERROR_FPM;
     }
+    // SHIFTED_COCG is COCG with the shifted sweep where fh_contour_apply_panel finds it eligible: every other path sees COCG
+    h->shifted = kind == FEASTHIP_SOLVER_SHIFTED_COCG ? 1 : 0;
+    if (h->shifted) kind = FEASTHIP_SOLVER_COCG;
     h->solver = kind; h->rtol = rtol; h->atol = atol; h->maxit = maxit; h->restart = restart;
     h->factor_precision = factor_precision; h->cache_factors = cache_factors;
     return 0;
@@ -660,6 +663,39 @@ struct fh_solve_result {
     std::vector<int> status;    // per node
     double max_rel_res = 0.0;
 };
+
+// Throttle of the Krylov drivers' queueing loops: after chunk `tag` has been queued (with its publish kernel), wait -- by
+// polling the host-mapped progress word -- until the device is at most three chunks behind; *all_done when a published
+// count of active columns is zero.
+static int fh_iter_throttle(feasthip_ctx* h, unsigned tag, std::chrono::steady_clock::time_point t_loop0, int N, int nodes,
+                            bool* all_done) {
+    unsigned st = 0, sc = 0;
+    for (unsigned spins = 1;; ++spins) {
+        const unsigned long long w = *h->h_progress;
+        st = (unsigned)(w >> 32); sc = (unsigned)(w & 0xffffffffull);
+        if (st >= 1 && sc == 0) { *all_done = true; break; }
+        if (tag < 3 || st + 3 > tag) break;      // at most three chunks queued ahead of the device
+        std::this_thread::sleep_for(std::chrono::microseconds(100));   // poll, do not burn the core
+        if ((spins & 2047u) == 0) {              // every ~0.2 s: a faulted queue never publishes; do not wait for it
+            const hipError_t q = hipStreamQuery(h->stream);
+            if (q != hipSuccess && q != hipErrorNotReady) {
+                h->last_error = std::string("device queue failed while iterating: ") + hipGetErrorString(q);
+                h->poisoned = 1;
+                return FEASTHIP_ERROR_INTERNAL;
+            }
+            // a wedged kernel keeps answering "not ready": overall deadline, generous against the slowest
+            // measured iteration (2 ms with 16 nodes x 64 columns at N = 50 000), scaled by the problem size
+            const double waited = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_loop0).count();
+            const double budget = 30.0 + 0.05 * (double)h->maxit * (1.0 + (double)N * nodes / 8.0e5);
+            if (waited > budget) {
+                h->last_error = "device did not make progress on the Krylov iterations within the deadline (" + std::to_string((int)budget) + " s)";
+                fh_poison_unless_drained(h, 2.0);
+                return FEASTHIP_ERROR_INTERNAL;
+            }
+        }
+    }
+    return 0;
+}
 
 // sum_acc != null (COCG only): "sum mode" -- X keeps the initial guess, every step alpha p of every
 // node is added, weighted with wnode[e], to the N x ld accumulator sum_acc (zeroed by the caller), so
@@ -854,10 +890,6 @@ static int fh_krylov(feasthip_ctx* h, int method, int prec, int ld, int m, int n
     unsigned tag = 0;
     bool all_done = false;
     auto t_loop0 = std::chrono::steady_clock::now();
-    auto progress = [&](unsigned& seen_tag, unsigned& seen_cnt) {
-        unsigned long long w = *h->h_progress;
-        seen_tag = (unsigned)(w >> 32); seen_cnt = (unsigned)(w & 0xffffffffull);
-    };
     while (it < h->maxit && !all_done) {
         int chunk = std::min(check_every, h->maxit - it);
         for (int k = 0; k < chunk; ++k) {
@@ -910,31 +942,7 @@ static int fh_krylov(feasthip_ctx* h, int method, int prec, int ld, int m, int n
         it += chunk;
         ++tag;
         fh_launch_publish_progress(s.node_active, nodes, h->d_progress, tag, h->stream);
-        // throttle: wait (by polling host memory) until the device has finished chunk tag-2
-        unsigned st = 0, sc = 0;
-        for (unsigned spins = 1;; ++spins) {
-            progress(st, sc);
-            if (st >= 1 && sc == 0) { all_done = true; break; }
-            if (tag < 3 || st + 3 > tag) break;      // at most three chunks queued ahead of the device
-            std::this_thread::sleep_for(std::chrono::microseconds(100));   // poll, do not burn the core
-            if ((spins & 2047u) == 0) {              // every ~0.2 s: a faulted queue never publishes; do not wait for it
-                const hipError_t q = hipStreamQuery(h->stream);
-                if (q != hipSuccess && q != hipErrorNotReady) {
-                    h->last_error = std::string("device queue failed while iterating: ") + hipGetErrorString(q);
-                    h->poisoned = 1;
-                    return FEASTHIP_ERROR_INTERNAL;
-                }
-                // a wedged kernel keeps answering "not ready": overall deadline, generous against the slowest
-                // measured iteration (2 ms with 16 nodes x 64 columns at N = 50 000), scaled by the problem size
-                const double waited = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_loop0).count();
-                const double budget = 30.0 + 0.05 * (double)h->maxit * (1.0 + (double)N * nodes / 8.0e5);
-                if (waited > budget) {
-                    h->last_error = "device did not make progress on the Krylov iterations within the deadline (" + std::to_string((int)budget) + " s)";
-                    fh_poison_unless_drained(h, 2.0);
-                    return FEASTHIP_ERROR_INTERNAL;
-                }
-            }
-        }
+        if ((rc = fh_iter_throttle(h, tag, t_loop0, N, nodes, &all_done))) return rc;
     }
     if (fused && it > 0) {
         // the stop test of the last step: true norms from the last vector kernel's partials (no SpMM follows it)
@@ -974,6 +982,134 @@ static int fh_krylov(feasthip_ctx* h, int method, int prec, int ld, int m, int n
         res.max_iters = std::max(res.max_iters, mx);
         res.status[e] = st;
     }
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------
+// Shifted COCG sweep in sum mode (fh_sparse.hip, "shifted COCG"): CSR operator with real values, B = I, complex128 panels,
+// shared start r_e^0 = f_e,c * shared_src with f = 1 / (z_e - lambda_c) (lambda_host given) or 1.  One operator product per
+// iteration, on the direction panel of the seed (the node with the smallest |Im z_e|, ties to the lowest index); the other
+// nodes follow by scalar recurrences and one direction panel each.  Work panels: r, q, `nodes` directions (+ the caller's
+// accumulator).  res as fh_krylov fills it: per (node, column) the steps in which that pair still advanced.
+// ---------------------------------------------------------------------------------------
+static int fh_shifted_cocg(feasthip_ctx* h, int ld, int m, int nodes, const std::vector<cplx>& z, fh_solve_result& res,
+                           cplx* sum_acc, const std::vector<cplx>& wnode, const cplx* shared_src, const double* lambda_host,
+                           int* seed_out, int* seed_iters_out) {
+    const int N = (int)fh_N(h);
+    const size_t panel = (size_t)N * ld;
+    const size_t nl = (size_t)nodes * ld;
+    const int ntiles = ld / 16;
+    int rc;
+    void* p;
+    int seed = 0;
+    for (int e = 1; e < nodes; ++e)
+        if (fabs(z[e].y) < fabs(z[seed].y)) seed = e;
+    fh_shift_args a;
+    memset(&a, 0, sizeof(a));
+    a.N = N; a.nodes = nodes; a.seed = seed; a.m = m; a.node_stride = panel;
+    if ((rc = fh_get_buf(h, "shc_vecs", (size_t)(2 + nodes) * panel * sizeof(cplx), &p))) return rc;
+    a.R = (cplx*)p; a.Qv = a.R + panel; a.P = a.Qv + panel;
+    a.sum_acc = sum_acc; a.src = shared_src;
+    if ((rc = fh_get_buf(h, "shc_scal_c", (5 * nl + 2 * (size_t)ld) * sizeof(cplx), &p))) return rc;
+    a.pi = (cplx*)p; a.pi_old = a.pi + nl; a.coef = a.pi_old + nl; a.ipi = a.coef + nl; a.beta_e = a.ipi + nl;
+    a.alpha = a.beta_e + nl; a.beta = a.alpha + ld;
+    if ((rc = fh_get_buf(h, "shc_scal_d", 3 * nl * sizeof(double), &p))) return rc;
+    a.r0norm = (double*)p; a.target = a.r0norm + nl; a.rnorm = a.target + nl;
+    const size_t nint = 4 * nl + (size_t)ld + (size_t)ntiles * nodes + ntiles + 2;
+    if ((rc = fh_get_buf(h, "shc_scal_i", nint * sizeof(int), &p))) return rc;
+    a.active = (int*)p; a.accum = a.active + nl; a.iters = a.accum + nl; a.status = a.iters + nl;
+    a.col_step = a.status + nl; a.node_step = a.col_step + ld;
+    a.tile_alive = a.node_step + (size_t)ntiles * nodes; a.alive_total = a.tile_alive + ntiles; a.passes = a.alive_total + 1;
+    FH_CHECK(hipMemsetAsync(a.active, 0, nint * sizeof(int), h->stream));
+    // start factors, shifts against the seed, weights
+    std::vector<cplx> fs(nl, cmake(1, 0)), sg(nodes), ca(ld, cmake(-1, 0)), cb(ld, z[seed]);
+    if (lambda_host)
+        for (int e = 0; e < nodes; ++e)
+            for (int c = 0; c < m; ++c) fs[(size_t)e * ld + c] = cdiv(cmake(1, 0), cmake(z[e].x - lambda_host[c], z[e].y));
+    for (int e = 0; e < nodes; ++e) sg[e] = csub(z[e], z[seed]);
+    cplx *dfs, *dsg, *dw, *dca, *dcb;
+    if ((rc = fh_upload_coefs(h, "shc_fscale", fs, &dfs))) return rc;
+    if ((rc = fh_upload_coefs(h, "shc_sigma", sg, &dsg))) return rc;
+    if ((rc = fh_upload_coefs(h, "shc_wnode", wnode, &dw))) return rc;
+    if ((rc = fh_upload_coefs(h, "shc_coefA", ca, &dca))) return rc;
+    if ((rc = fh_upload_coefs(h, "shc_coefB", cb, &dcb))) return rc;
+    a.fscale = dfs; a.sigma = dsg; a.wnode = dw;
+    a.rtol = h->rtol; a.atol = h->atol; a.col_mask = nullptr;
+    if (h->mask_live && !h->col_mask.empty()) {
+        std::vector<int> mk(ld, 1);
+        for (int c = 0; c < ld && c < (int)h->col_mask.size(); ++c) mk[c] = h->col_mask[c];
+        if ((rc = fh_get_buf(h, "kry_colmask", ld * sizeof(int), &p))) return rc;
+        FH_CHECK(hipMemcpyAsync(p, mk.data(), ld * sizeof(int), hipMemcpyHostToDevice, h->stream));
+        FH_CHECK(hipStreamSynchronize(h->stream));
+        a.col_mask = (const int*)p;
+    }
+    int fv_blk, fv_seg, fv_per;
+    fh_fused_vec_geometry(N, ld, 1, &fv_blk, &fv_seg, &fv_per);
+    const int nblk_op = fh_op_nblk(h, ld);
+    const int nrow_max = std::max(256, fv_blk * fv_seg);
+    if ((rc = fh_get_buf(h, "shc_partials", 2 * (size_t)(nrow_max + nblk_op) * ld * sizeof(cplx), &p))) return rc;
+    a.rho_part = (cplx*)p; a.rr_part = a.rho_part + (size_t)nrow_max * ld;
+    cplx* sp0 = a.rr_part + (size_t)nrow_max * ld;
+    cplx* sp1 = sp0 + (size_t)nblk_op * ld;
+    a.sig = sp0; a.kap = sp1;
+
+    a.nblk_vec = fh_launch_shift_init(a, ld, h->stream);
+    fh_op_call oc;
+    oc.m = m; oc.uniform_coef = 1; oc.coefA = dca; oc.coefB = dcb; oc.nodes = 1; oc.prec = 64;
+    oc.X = a.P + (size_t)seed * panel; oc.x_stride = panel; oc.Y = a.Qv; oc.y_stride = panel;
+    oc.dot_mode = 6; oc.node_active = a.alive_total; oc.partial1 = sp0; oc.partial2 = sp1;
+    const int check_every = getenv("FH_CHECK_EVERY") ? std::max(1, atoi(getenv("FH_CHECK_EVERY"))) : 16;
+    *h->h_progress = 0ull;
+    int it = 0;
+    unsigned tag = 0;
+    bool all_done = false;
+    auto t_loop0 = std::chrono::steady_clock::now();
+    while (it < h->maxit && !all_done) {
+        const int chunk = std::min(check_every, h->maxit - it);
+        for (int k = 0; k < chunk; ++k) {
+            a.nblk_op = fh_apply_operator(h, ld, oc);
+            if (a.nblk_op < 0) return FEASTHIP_ERROR_INTERNAL;
+            a.phase = (it + k == 0) ? 0 : 1;
+            fh_prof_begin(h, "dot_finalize"); fh_launch_shift_fin(a, ld, h->stream); fh_prof_end(h);
+            fh_prof_begin(h, "shift_vec"); a.nblk_vec = fh_launch_shift_vec(a, ld, h->stream); fh_prof_end(h);
+        }
+        it += chunk;
+        ++tag;
+        fh_launch_publish_progress(a.tile_alive, ntiles, h->d_progress, tag, h->stream);
+        if ((rc = fh_iter_throttle(h, tag, t_loop0, N, nodes, &all_done))) return rc;
+    }
+    if (it > 0) {
+        a.phase = 2;                     // the stop test of the last step, on the true norm the last vector kernel left
+        fh_launch_shift_fin(a, ld, h->stream);
+    }
+    FH_CHECK(hipStreamSynchronize(h->stream));
+
+    std::vector<int> iters(nl), status(nl), active(nl);
+    std::vector<double> rnorm(nl), r0(nl);
+    FH_CHECK(hipMemcpy(iters.data(), a.iters, nl * sizeof(int), hipMemcpyDeviceToHost));
+    FH_CHECK(hipMemcpy(status.data(), a.status, nl * sizeof(int), hipMemcpyDeviceToHost));
+    FH_CHECK(hipMemcpy(active.data(), a.active, nl * sizeof(int), hipMemcpyDeviceToHost));
+    FH_CHECK(hipMemcpy(rnorm.data(), a.rnorm, nl * sizeof(double), hipMemcpyDeviceToHost));
+    FH_CHECK(hipMemcpy(r0.data(), a.r0norm, nl * sizeof(double), hipMemcpyDeviceToHost));
+    res.status.assign(nodes, 0);
+    for (int e = 0; e < nodes; ++e) {
+        int mx = 0, st = 0;
+        for (int c = 0; c < m; ++c) {
+            const int i = e * ld + c;
+            mx = std::max(mx, iters[i]);
+            res.col_iters.push_back(iters[i]);
+            if (active[i] || !std::isfinite(rnorm[i])) st = std::max(st, (int)FEASTHIP_ERROR_NO_CONVERGENCE);
+            else if (status[i] == 8 && !(rnorm[i] <= h->atol + h->rtol * r0[i])) st = std::max(st, (int)FEASTHIP_ERROR_NO_CONVERGENCE);
+            if (r0[i] > 0) res.max_rel_res = std::max(res.max_rel_res, rnorm[i] / r0[i]);
+        }
+        res.iters_sum += mx;
+        res.node_iters.push_back(mx);
+        res.max_iters = std::max(res.max_iters, mx);
+        res.status[e] = st;
+    }
+    *seed_out = seed;
+    FH_CHECK(hipMemcpy(seed_iters_out, a.passes, sizeof(int), hipMemcpyDeviceToHost));
+    res.op_calls = *seed_iters_out;        // the products that ran (those queued behind the last live column return at once)
     return 0;
 }
 
@@ -1399,7 +1535,16 @@ static int fh_contour_apply_panel(feasthip_ctx* h, int64_t m64, const cplx* dQ, 
             va.N = N; va.node_stride = panel; va.X = Y; va.Q = Qp; va.lambda = dlam; va.znode = dz;
             fh_launch_init_guess(va, ld, fh_vec_nblk(N, ld), nk, h->stream);
         }
-        if (nk) {
+        // Shifted COCG (feasthip_set_solver kind SHIFTED_COCG): a CSR operator with real values and B = I, fp64 panels, sum mode
+        // from a shared start, no direct nodes.  Anything else is the per-node sweep below.
+        const bool shifted = h->shifted && sum_shared && shared_src && nk && !nd && h->kind == 2 && h->csr.b_identity &&
+                             !h->csr.is_complex;
+        h->shift_panels += 1;
+        if (shifted) {
+            int seed = 0, seed_its = 0;
+            if ((rc = fh_shifted_cocg(h, ld, m, nk, zk, sr, sum_acc, wk, shared_src, ritz_lambda, &seed, &seed_its))) return rc;
+            h->shift_used += 1; h->shift_seed = h->node_ids[order[seed]]; h->shift_seed_iters += seed_its;
+        } else if (nk) {
             rc = fh_krylov(h, h->solver == FEASTHIP_SOLVER_COCG ? 1 : 0, h->factor_precision, ld, m, nk, zk, Rhs, Y, panel, sr,
                            sum_acc, &wk, shared_src, dlam, dz, ritz_lambda);
             if (rc) return rc;
@@ -1608,6 +1753,7 @@ struct fh_resident_sweep {
 static int fh_contour_apply_impl(feasthip_ctx* h, int64_t m64, const cplx* dQ, const double* ritz_lambda,
                                  cplx* dQproj, cplx* dzAq, cplx* dzSq, int* node_status, feasthip_stats* stats,
                                  const fh_resident_sweep* rs = nullptr) {
+    h->shift_panels = h->shift_used = h->shift_seed_iters = 0; h->shift_seed = -1;      // feasthip_last_shifted_sweep
     const int nr = fh_comm_nranks(h);
     int64_t c0 = 0, c1 = m64;
     if (h->col_block_hi >= 0) { c0 = std::min(h->col_block_lo, m64); c1 = std::min(std::max(h->col_block_hi, c0), m64); }
@@ -2992,6 +3138,16 @@ extern "C" int feasthip_last_node_iterations(feasthip_handle h, int* out, int n)
 extern "C" int feasthip_last_global_node_iterations(feasthip_handle h, int* out, int n) {
     if (!h || !out) return FEASTHIP_ERROR_INTERNAL;
     for (int e = 0; e < n; ++e) out[e] = e < (int)h->global_node_iters.size() ? h->global_node_iters[e] : 0;
+    return 0;
+}
+
+extern "C" int feasthip_last_shifted_sweep(feasthip_handle h, int* used, int* seed_node, int* seed_iterations, int* spmm_node_passes) {
+    if (!h) return FEASTHIP_ERROR_INTERNAL;
+    const bool u = h->shift_panels > 0 && h->shift_used == h->shift_panels;
+    if (used) *used = u ? 1 : 0;
+    if (seed_node) *seed_node = u ? h->shift_seed : -1;
+    if (seed_iterations) *seed_iterations = u ? h->shift_seed_iters : 0;
+    if (spmm_node_passes) *spmm_node_passes = u ? h->shift_seed_iters : 0;
     return 0;
 }
 

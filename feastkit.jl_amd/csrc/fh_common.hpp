@@ -152,6 +152,9 @@ struct feasthip_ctx {
 
     // solver options
     int solver = 1;
+    int shifted = 0;               // FEASTHIP_SOLVER_SHIFTED_COCG was asked for (solver then holds COCG)
+    // the last contour_apply: panels swept, panels that took the shifted sweep, its seed (contour index) and seed iterations
+    int shift_panels = 0, shift_used = 0, shift_seed = -1, shift_seed_iters = 0;
     double rtol = 1e-12, atol = 0.0;
     int maxit = 500, restart = 30, factor_precision = 64, cache_factors = 1;
 

@@ -100,6 +100,38 @@ void fh_launch_fused_fin(const fh_fused_fin_args& a, int ld, int nodes, hipStrea
 void fh_fused_vec_geometry(int N, int ld, int half, int* nblk, int* nseg, int* per_thread);
 // R -= alpha Q, [ACC += w alpha P | X += alpha P], P = R + beta P, partials r^T r and |r|^2 ([nodes][nblk*nseg][LD])
 void fh_launch_fused_vec(const fh_vec_args& a, int ld, hipStream_t st);
+// ---- shifted COCG (fh_sparse.hip, "shifted COCG"): one Krylov space for all nodes of a B = I sweep ------------------------
+// Panels are complex128.  Arrays marked [n][LD] hold one entry per (node, column), [LD] one per column.
+struct fh_shift_args {
+    int N, nodes, seed, m;
+    size_t node_stride;
+    cplx* R; cplx* Qv; cplx* P;               // seed residual, S_seed p_seed, direction panels [nodes] (P + seed * node_stride: the seed's)
+    cplx* sum_acc;                            // N x LD accumulator: ACC += w_e alpha_e p_e
+    const cplx* src;                          // shared start source: r_e^0 = fscale[e][c] * src
+    const cplx* fscale;                       // [n][LD]
+    const cplx* sigma;                        // [nodes] z_e - z_seed
+    const cplx* wnode;                        // [nodes]
+    cplx *pi, *pi_old;                        // [n][LD] pi_e^k, pi_e^(k-1)
+    cplx *coef, *ipi, *beta_e;                // [n][LD] w_e alpha_e, 1 / pi_e^(k+1), beta_e of the step the vector kernel takes
+    double *r0norm, *target, *rnorm;          // [n][LD]
+    int *active, *accum, *iters, *status;     // [n][LD]
+    cplx *alpha, *beta;                       // [LD] the seed's scalars of the last step taken
+    int* col_step;                            // [LD] the column's seed recurrence advances in this iteration
+    int* node_step;                           // [LD / 16][nodes] a column of the tile steps at this node
+    int* tile_alive;                          // [LD / 16] columns of the tile with a node still iterating
+    int* alive_total;                         // [1] their sum (the node_active word of the seed's operator product)
+    int* passes;                              // [1] operator products that found a live column
+    const cplx *sig, *kap; int nblk_op;       // SpMM partials [nblk_op][LD]: p^T q, q^T q
+    cplx *rho_part, *rr_part; int nblk_vec;   // partials of the seed residual [nblk_vec][LD]: r^T r, |r|^2
+    double rtol, atol;
+    const int* col_mask;                      // [LD] or null
+    int phase;                                // finalize: 0 first iteration (sets the start values), 1 iteration, 2 final check
+};
+// R = f_seed src, P_e = f_e src, partial rows of r^T r and |r|^2; returns the number of partial rows
+int fh_launch_shift_init(const fh_shift_args& a, int ld, hipStream_t st);
+void fh_launch_shift_fin(const fh_shift_args& a, int ld, hipStream_t st);
+// r -= alpha q; ACC += sum_e w_e alpha_e p_e; p_e = r / pi_e + beta_e p_e; partial rows of the new r; returns their number
+int fh_launch_shift_vec(const fh_shift_args& a, int ld, hipStream_t st);
 void fh_launch_fin_init(const fh_fin_args& a, int ld, int nodes, hipStream_t st);
 void fh_launch_fin_alpha(const fh_fin_args& a, int ld, int nodes, hipStream_t st);
 void fh_launch_fin_omega(const fh_fin_args& a, int ld, int nodes, hipStream_t st);

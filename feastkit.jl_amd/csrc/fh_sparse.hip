@@ -1648,8 +1648,325 @@ __global__ __launch_bounds__(FH_FV_THREADS, 2) void k_fused_vec(fh_vec_args a, i
 }
 
 // ------------------------------------------------------------------------------------
+// Shifted COCG (Frommer 2003; Takayama, Hoshi, Sogabe, Zhang, Fujiwara 2006): B = I, so S_e = z_e I - A = S_seed + sigma_e I
+// with sigma_e = z_e - z_seed, and the start residuals of a shared start are collinear, r_e^0 = f_e src.  All nodes then
+// share the seed's Krylov space: r_e^k = r^k / pi_e^k (r: the seed's residual), and only the seed needs the operator.
+//
+//   k_spmm (dot_mode 6, one node)   q = S_seed p_seed,  sigma_pq = p^T q,  kappa = q^T q
+//   k_shift_fin      the seed's scalars as in k_fused_fin without the predicted stop: alpha = rho / sigma_pq (true rho),
+//                    rho' = alpha^2 kappa - rho, beta = rho' / rho; then for every node still iterating
+//                        pi' = (1 + alpha sigma_e) pi + (beta_old alpha / alpha_old) (pi - pi_old)
+//                        alpha_e = alpha pi / pi',   beta_e = beta (pi / pi')^2            (seed: pi = 1, alpha, beta)
+//                    after the stop test  |r| / |pi_e| <= rtol |r_e^0| + atol  on the TRUE |r| of the last vector kernel
+//   k_shift_vec      r -= alpha q;  ACC += sum_e w_e alpha_e p_e;  p_e = r (1 / pi_e') + beta_e p_e;  partials of r^T r, |r|^2
+//
+// A (node, column) that met its test is frozen: pi stops, its direction panel is neither read nor written.  The seed's
+// direction goes on for a column as long as any node of that column iterates, also after the seed's own test is met (it
+// then no longer adds to ACC).  A column ends when no node is left, or on a breakdown of the seed recurrence (status 8 for
+// the nodes still iterating).  No atomics: flags are plain stores, counts are sums in a fixed order.
+// ------------------------------------------------------------------------------------
+#define FH_SV_EMAX (FH_FV_EMAX / 2)
+
+template <int LD>
+__global__ __launch_bounds__(FH_BLOCK) void k_shift_init(fh_shift_args a) {
+    const size_t total = (size_t)a.N * LD;
+    const int c = threadIdx.x % LD;
+    const cplx fs = a.fscale[a.seed * LD + c];
+    cplx d1 = cmake(0, 0), d2 = cmake(0, 0);
+    for (size_t e = (size_t)blockIdx.x * FH_BLOCK + threadIdx.x; e < total; e += (size_t)gridDim.x * FH_BLOCK) {
+        const cplx v = a.src[e];
+        const cplx r = cmul(v, fs);
+        a.R[e] = r;
+        for (int n = 0; n < a.nodes; ++n) a.P[(size_t)n * a.node_stride + e] = n == a.seed ? r : cmul(v, a.fscale[n * LD + c]);
+        d1 = cadd(d1, cmul(r, r));
+        d2.x += cabs2(r);
+    }
+    __shared__ cplx red[FH_BLOCK];
+    fh_block_reduce_cols<LD>(d1, red, a.rho_part + (size_t)blockIdx.x * LD);
+    fh_block_reduce_cols<LD>(d2, red, a.rr_part + (size_t)blockIdx.x * LD);
+    if (blockIdx.x == 0 && threadIdx.x == 0) *a.alive_total = 1;       // the first product runs; the first finalize counts
+}
+
+template <int LD>
+__global__ __launch_bounds__(FH_FIN_BLOCK) void k_shift_fin(fh_shift_args a) {
+    // grid (LD / 16): one workgroup per 16-column tile; the partial rows are summed as in k_fused_fin (64 row groups x 16
+    // columns, fixed order), then the threads spread over (node, column of the tile)
+    __shared__ double red[FH_FIN_BLOCK / 64][16][8];
+    __shared__ cplx s_alpha[16], s_beta[16], s_fac[16];
+    __shared__ double s_rn[16];
+    __shared__ int s_flag[16], s_alive[16], s_step[16];
+    const int tile = blockIdx.x, t = threadIdx.x;
+    const int lane = t & 63, wave = t >> 6;
+    const int c16 = lane & 15, g = wave * 4 + (lane >> 4);
+    const bool final_check = a.phase == 2, first = a.phase == 0;
+    double v[8];
+#pragma unroll
+    for (int q = 0; q < 8; ++q) v[q] = 0.0;
+    {
+        const size_t base = (size_t)tile * 16 + c16;
+#pragma unroll 4
+        for (int b = g; b < a.nblk_vec; b += 64) {
+            const cplx r1 = a.rho_part[base + (size_t)b * LD], r2 = a.rr_part[base + (size_t)b * LD];
+            v[0] += r1.x; v[1] += r1.y; v[2] += r2.x;
+        }
+        if (!final_check) {
+#pragma unroll 4
+            for (int b = g; b < a.nblk_op; b += 64) {
+                const cplx s1 = a.sig[base + (size_t)b * LD], s3 = a.kap[base + (size_t)b * LD];
+                v[3] += s1.x; v[4] += s1.y; v[5] += s3.x; v[6] += s3.y;
+            }
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < 7; ++q) {
+        v[q] += __shfl_xor(v[q], 16);
+        v[q] += __shfl_xor(v[q], 32);
+    }
+    if (lane < 16) {
+#pragma unroll
+        for (int q = 0; q < 7; ++q) red[wave][lane][q] = v[q];
+    }
+    __syncthreads();
+    // the seed's scalars of the column.  flag 0: no step (final check), 1: step, 2: breakdown before the step, 3: |r| not
+    // finite, 4: step, then breakdown (beta not finite)
+    if (t < 16) {
+        double w[7];
+#pragma unroll
+        for (int q = 0; q < 7; ++q) {
+            double sacc = red[0][t][q];
+#pragma unroll
+            for (int k = 1; k < FH_FIN_BLOCK / 64; ++k) sacc += red[k][t][q];
+            w[q] = sacc;
+        }
+        const int c = tile * 16 + t;
+        const cplx rho = cmake(w[0], w[1]);
+        const double rn = sqrt(w[2]);
+        int flag = 1;
+        cplx al = cmake(0, 0), beta = cmake(0, 0), fac = cmake(0, 0);
+        if (!isfinite(rn)) flag = 3;
+        else if (final_check) flag = 0;
+        else {
+            const cplx sigma = cmake(w[3], w[4]), kappa = cmake(w[5], w[6]);
+            al = cdiv(rho, sigma);
+            if (cabs2(sigma) == 0.0 || cabs2(rho) == 0.0 || !fh_finite(al)) flag = 2;
+            else {
+                const cplx rho_next = csub(cmul(cmul(al, al), kappa), rho);
+                beta = cdiv(rho_next, rho);
+                if (!fh_finite(beta)) { flag = 4; beta = cmake(0, 0); }
+                if (!first) fac = cdiv(cmul(a.beta[c], al), a.alpha[c]);       // (still the last step's: rewritten below)
+            }
+        }
+        s_alpha[t] = al; s_beta[t] = beta; s_fac[t] = fac; s_rn[t] = rn; s_flag[t] = flag; s_alive[t] = 0; s_step[t] = 0;
+    }
+    __syncthreads();
+    for (int idx = t; idx < a.nodes * 16; idx += FH_FIN_BLOCK) {
+        const int n = idx >> 4, k16 = idx & 15;
+        const int c = tile * 16 + k16, i = n * LD + c;
+        const double rn = s_rn[k16];
+        const int flag = s_flag[k16];
+        cplx pi, pio;
+        int act;
+        if (first) {
+            pi = n == a.seed ? cmake(1, 0) : cdiv(a.fscale[a.seed * LD + c], a.fscale[i]);
+            pio = pi;
+            const double r0 = rn / sqrt(cabs2(pi));
+            const double target = a.rtol * r0 + a.atol;
+            a.r0norm[i] = r0; a.target[i] = target; a.rnorm[i] = r0; a.iters[i] = 0;
+            a.pi[i] = pi; a.pi_old[i] = pio;
+            act = (c < a.m) && (r0 > target) && isfinite(r0) && (!a.col_mask || a.col_mask[c]);
+            a.status[i] = (c < a.m && !isfinite(r0)) ? 8 : 0;
+        } else {
+            act = a.active[i];
+            pi = a.pi[i]; pio = a.pi_old[i];
+        }
+        int stepped = 0;
+        if (act) {
+            const double rne = rn / sqrt(cabs2(pi));
+            a.rnorm[i] = rne;
+            if (flag == 3 || !isfinite(rne)) { act = 0; a.status[i] = 8; }
+            else if (!(rne > a.target[i])) { act = 0; a.status[i] = 0; }
+            else if (flag == 2) { act = 0; a.status[i] = 8; }
+            else if (flag != 0) {
+                const cplx al = s_alpha[k16], beta = s_beta[k16];
+                cplx pin = cmake(1, 0), ae = al, be = beta, ip = cmake(1, 0);
+                if (n != a.seed) {
+                    pin = cadd(cmul(cadd(cmake(1, 0), cmul(al, a.sigma[n])), pi), cmul(s_fac[k16], csub(pi, pio)));
+                    const cplx ratio = cdiv(pi, pin);
+                    ae = cmul(al, ratio);
+                    be = cmul(beta, cmul(ratio, ratio));
+                    ip = cdiv(cmake(1, 0), pin);
+                }
+                if (cabs2(pin) == 0.0 || !fh_finite(ae) || !fh_finite(be) || !fh_finite(ip)) { act = 0; a.status[i] = 8; }
+                else {
+                    a.coef[i] = cmul(a.wnode[n], ae); a.ipi[i] = ip; a.beta_e[i] = be;
+                    a.pi_old[i] = pi; a.pi[i] = pin;
+                    a.iters[i] += 1;
+                    stepped = 1;
+                    if (flag == 4) { act = 0; a.status[i] = 8; }
+                }
+            }
+        }
+        a.active[i] = act;
+        if (!final_check) a.accum[i] = stepped;
+        if (act) s_alive[k16] = 1;             // (every writer stores the same value)
+        if (stepped) s_step[k16] = 1;
+        if (!final_check) {
+            // a column of this tile steps at node n: the 16 lanes of the node vote
+            const unsigned long long bal = __ballot(stepped != 0);
+            if (k16 == 0) a.node_step[tile * a.nodes + n] = ((bal >> (lane & 48)) & 0xFFFFull) != 0ull;
+        }
+    }
+    __syncthreads();
+    if (t < 16 && !final_check) {
+        const int c = tile * 16 + t;
+        a.col_step[c] = s_step[t];
+        if (s_step[t]) {
+            a.alpha[c] = s_alpha[t]; a.beta[c] = s_beta[t];
+        }
+    }
+    if (t == 0) {
+        int alive = 0;
+        for (int k = 0; k < 16; ++k) alive += s_alive[k];
+        a.tile_alive[tile] = alive;
+        // the product this finalize follows did its work (alive_total: what that launch saw; rewritten by the next vector kernel)
+        if (tile == 0 && !final_check && *a.alive_total != 0) a.passes[0] += 1;
+    }
+}
+
+template <int LD>
+__global__ __launch_bounds__(FH_FV_THREADS, 2) void k_shift_vec(fh_shift_args a, int per_thread) {
+    // grid (nblk, nseg), the geometry of k_fused_vec's half launches: a thread OWNS per_thread (<= 14) elements, one column,
+    // for every node.  The new residual of those elements and the weighted steps of all nodes stay in registers (2 x 14
+    // complex128 = 112 VGPRs, what k_fused_vec holds for its 28 accumulators); R, Q are passed once, every stepping
+    // direction panel is read and written once, the accumulator is read and written once per launch.
+    __shared__ double red[FH_FV_THREADS / 64][LD][3];
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int c = t % LD;
+    const size_t total = (size_t)a.N * LD;
+    const size_t stride = (size_t)gridDim.x * FH_FV_THREADS;
+    const size_t e0 = (size_t)blockIdx.y * stride * per_thread + (size_t)blockIdx.x * FH_FV_THREADS + t;
+    const int prow = blockIdx.y * gridDim.x + blockIdx.x;
+    constexpr int GRP = 2;
+    if (prow == 0 && t == 0) {
+        int s = 0;
+        for (int k = 0; k < LD / 16; ++k) s += a.tile_alive[k];
+        *a.alive_total = s;
+    }
+    const bool cstep = a.col_step[c] != 0;
+    cplx rn[FH_SV_EMAX], acc[FH_SV_EMAX];
+#pragma unroll
+    for (int j = 0; j < FH_SV_EMAX; ++j) { rn[j] = cmake(0, 0); acc[j] = cmake(0, 0); }
+    double d1x = 0.0, d1y = 0.0, d2 = 0.0;
+    if (cstep) {
+        const cplx alpha = a.alpha[c];
+#pragma unroll
+        for (int j0 = 0; j0 < FH_SV_EMAX; j0 += GRP) {
+            if (j0 >= per_thread) continue;                      // (no break: the loop must unroll fully -- rn[] lives in registers)
+            cplx qv[GRP], rv[GRP];
+            bool ok[GRP];
+#pragma unroll
+            for (int u = 0; u < GRP; ++u) {
+                const size_t e = e0 + (size_t)(j0 + u) * stride;
+                ok[u] = (j0 + u < per_thread) && e < total;
+                qv[u] = cmake(0, 0); rv[u] = cmake(0, 0);
+                if (ok[u]) { qv[u] = fh_ld_nt(a.Qv + e); rv[u] = a.R[e]; }
+            }
+#pragma unroll
+            for (int u = 0; u < GRP; ++u) {
+                if (!ok[u]) continue;
+                const cplx r = csub(rv[u], cmul(alpha, qv[u]));
+                a.R[e0 + (size_t)(j0 + u) * stride] = r;
+                rn[j0 + u] = r;
+                d1x += r.x * r.x - r.y * r.y; d1y += 2.0 * r.x * r.y; d2 += cabs2(r);
+            }
+        }
+    }
+    if (LD < 64) {
+#pragma unroll
+        for (int off = LD; off < 64; off <<= 1) {
+            d1x += __shfl_xor(d1x, off); d1y += __shfl_xor(d1y, off); d2 += __shfl_xor(d2, off);
+        }
+    }
+    if (lane < LD) { red[wave][lane][0] = d1x; red[wave][lane][1] = d1y; red[wave][lane][2] = d2; }
+    __syncthreads();
+    if (t < LD) {
+        double s0 = 0.0, s1 = 0.0, s2 = 0.0;
+#pragma unroll
+        for (int w = 0; w < FH_FV_THREADS / 64; ++w) { s0 += red[w][t][0]; s1 += red[w][t][1]; s2 += red[w][t][2]; }
+        const size_t o = (size_t)prow * LD + t;
+        a.rho_part[o] = cmake(s0, s1);
+        a.rr_part[o] = cmake(s2, 0.0);
+    }
+    bool any = false;
+    for (int n = 0; n < a.nodes; ++n) {
+        bool nstep = false;                                      // uniform over the grid
+        for (int k = 0; k < LD / 16; ++k) nstep = nstep || a.node_step[k * a.nodes + n] != 0;
+        if (!nstep && n != a.seed) continue;
+        const int i = n * LD + c;
+        const bool step = cstep && a.accum[i] != 0;              // the node takes this step: it adds to ACC
+        if (!step && !(cstep && n == a.seed)) continue;          // (the seed's direction follows its column to the end)
+        cplx coef = cmake(0, 0), ip = cmake(1, 0), be = a.beta[c];
+        if (step) {
+            any = true;
+            coef = a.coef[i];
+            if (n != a.seed) { ip = a.ipi[i]; be = a.beta_e[i]; }
+        }
+        cplx* __restrict__ P = a.P + (size_t)n * a.node_stride;
+#pragma unroll
+        for (int j0 = 0; j0 < FH_SV_EMAX; j0 += GRP) {
+            if (j0 >= per_thread) continue;
+            cplx pv[GRP];
+            bool ok[GRP];
+#pragma unroll
+            for (int u = 0; u < GRP; ++u) {
+                const size_t e = e0 + (size_t)(j0 + u) * stride;
+                ok[u] = (j0 + u < per_thread) && e < total;
+                pv[u] = cmake(0, 0);
+                if (ok[u]) pv[u] = P[e];
+            }
+#pragma unroll
+            for (int u = 0; u < GRP; ++u) {
+                if (!ok[u]) continue;
+                cfma(acc[j0 + u], coef, pv[u]);
+                P[e0 + (size_t)(j0 + u) * stride] = cadd(cmul(rn[j0 + u], ip), cmul(be, pv[u]));
+            }
+        }
+    }
+    if (any) {
+#pragma unroll
+        for (int j = 0; j < FH_SV_EMAX; ++j) {
+            const size_t e = e0 + (size_t)j * stride;
+            if (j < per_thread && e < total) a.sum_acc[e] = cadd(a.sum_acc[e], acc[j]);
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------
 // launchers
 // ------------------------------------------------------------------------------------
+int fh_launch_shift_init(const fh_shift_args& a, int ld, hipStream_t st) {
+    const size_t total = (size_t)a.N * ld;
+    const int nblk = (int)std::min<size_t>((total + FH_BLOCK - 1) / FH_BLOCK, 256);
+    if (ld == 16) hipLaunchKernelGGL((k_shift_init<16>), dim3(nblk), dim3(FH_BLOCK), 0, st, a);
+    else if (ld == 32) hipLaunchKernelGGL((k_shift_init<32>), dim3(nblk), dim3(FH_BLOCK), 0, st, a);
+    else hipLaunchKernelGGL((k_shift_init<64>), dim3(nblk), dim3(FH_BLOCK), 0, st, a);
+    return nblk;
+}
+void fh_launch_shift_fin(const fh_shift_args& a, int ld, hipStream_t st) {
+    if (ld == 16) hipLaunchKernelGGL((k_shift_fin<16>), dim3(1), dim3(FH_FIN_BLOCK), 0, st, a);
+    else if (ld == 32) hipLaunchKernelGGL((k_shift_fin<32>), dim3(2), dim3(FH_FIN_BLOCK), 0, st, a);
+    else hipLaunchKernelGGL((k_shift_fin<64>), dim3(4), dim3(FH_FIN_BLOCK), 0, st, a);
+}
+int fh_launch_shift_vec(const fh_shift_args& a, int ld, hipStream_t st) {
+    int nblk, nseg, per;
+    fh_fused_vec_geometry(a.N, ld, 1, &nblk, &nseg, &per);
+    const dim3 grid(nblk, nseg);
+    if (ld == 16) hipLaunchKernelGGL((k_shift_vec<16>), grid, dim3(FH_FV_THREADS), 0, st, a, per);
+    else if (ld == 32) hipLaunchKernelGGL((k_shift_vec<32>), grid, dim3(FH_FV_THREADS), 0, st, a, per);
+    else hipLaunchKernelGGL((k_shift_vec<64>), grid, dim3(FH_FV_THREADS), 0, st, a, per);
+    return nblk * nseg;
+}
+
 #define FH_DISPATCH_VEC(prec, ld, KERNEL, grid, st, args)                                          \
     do {                                                                                            \
         if ((prec) == 32) {                                                                         \

@@ -18,10 +18,10 @@ from . import _lib
 from ._lib import FeastHipStats, FeastHipUnavailable
 from .types import FeastHipError
 
-SOLVER_LU, SOLVER_BICGSTAB, SOLVER_GMRES, SOLVER_COCG, SOLVER_BANDED = 0, 1, 2, 3, 4
+SOLVER_LU, SOLVER_BICGSTAB, SOLVER_GMRES, SOLVER_COCG, SOLVER_BANDED, SOLVER_SHIFTED_COCG = 0, 1, 2, 3, 4, 5
 _SOLVER_CODES = {"direct": SOLVER_LU, "lu": SOLVER_LU, "bicgstab": SOLVER_BICGSTAB,
                  "iterative": SOLVER_BICGSTAB, "gmres": SOLVER_GMRES, "cocg": SOLVER_COCG,
-                 "banded": SOLVER_BANDED}
+                 "banded": SOLVER_BANDED, "shifted_cocg": SOLVER_SHIFTED_COCG}
 MAX_BLOCK = 64   # FH_MAX_LD: widest panel the kernels take in one call
 
 
@@ -250,7 +250,7 @@ class HipEngine:
     def set_solver(self, solver="direct", rtol=1e-12, atol=0.0, maxit=500, restart=30,
                    factor_precision=64, cache_factors=True):
         if solver not in _SOLVER_CODES:
-            raise ValueError(f"Unsupported solver option '{solver}'. Use :direct, :banded, :bicgstab, :cocg, :gmres, or :iterative.")
+            raise ValueError(f"Unsupported solver option '{solver}'. Use :direct, :banded, :bicgstab, :cocg, :shifted_cocg, :gmres, or :iterative.")
         self._chk(self.lib.feasthip_set_solver(self.h, _SOLVER_CODES[solver], float(rtol), float(atol), int(maxit),
                                                int(restart), int(factor_precision), int(bool(cache_factors))))
 
@@ -481,6 +481,13 @@ class HipEngine:
         out = np.zeros(max(1, n), dtype=np.int32)
         self._chk(self.lib.feasthip_last_node_iterations(self.h, _np_ptr(out), int(n)))
         return out[:n]
+
+    def last_shifted_sweep(self):
+        """(used, seed node, seed iterations, SpMM node-passes) of the last contour_apply: whether it took the shifted COCG
+        sweep (solver "shifted_cocg" on an eligible problem) and what that cost (feasthip_last_shifted_sweep)."""
+        out = [np.zeros(1, dtype=np.int32) for _ in range(4)]
+        self._chk(self.lib.feasthip_last_shifted_sweep(self.h, *[_np_ptr(v) for v in out]))
+        return bool(out[0][0]), int(out[1][0]), int(out[2][0]), int(out[3][0])
 
     def last_global_node_iterations(self):
         """Per contour node, summed over the ranks (multi-rank sweeps only): the cost signal for node re-balancing."""

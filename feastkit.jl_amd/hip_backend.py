@@ -757,6 +757,9 @@ def feast_hip_hermitian(engine, A, B, Emin, Emax, M0, fpm, *, freeze_guards_afte
             if hasattr(engine, "last_node_iterations"):
                 stats["node_iterations"].append([int(v) for v in engine.last_node_iterations(layout.count)])
                 stats["node_lists"].append([int(v) for v in layout.local_nodes])
+            if solver == "shifted_cocg" and hasattr(engine, "last_shifted_sweep"):
+                used, seed_node, seed_its, _ = engine.last_shifted_sweep()
+                stats.setdefault("shifted", []).append({"used": used, "seed_node": seed_node, "seed_iterations": seed_its})
             if dn is not None:
                 dn.record(loop_idx, st, layout.local_nodes)
             layout.rebalance(engine, loop_idx, active, stats)

@@ -31,6 +31,15 @@ def laplacian_3d_pencil(nx=50, ny=40, nz=25, shift=0.1):
     return A, B, np.sort(mu / (1 + shift * mu))
 
 
+def laplacian_3d_standard(nx=50, ny=40, nz=25):
+    """The standard-problem counterpart of laplacian_3d_pencil: the same A, no B (B = I).
+
+    Returns (A, lam) with lam the sorted eigenvalues mu of the 7-point Dirichlet Laplacian.
+    """
+    A, _, lam = laplacian_3d_pencil(nx, ny, nz, shift=0.0)
+    return A, lam
+
+
 def reflected_diagonal(d, seed=SEED, nreflect=2, complex_reflectors=False):
     """cfg 2: A = H2 H1 diag(d) H1 H2 with seeded unit Householder reflectors; eigenvalues = d."""
     n = d.shape[0]

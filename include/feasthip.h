@@ -67,9 +67,15 @@ enum {
                                       LU on the same kernels (fill confined to the band, 16 N (2 kl + ku + 256) bytes
                                       per node).  feasthip_band_plan / feasthip_direct_plan_flops say which, and what
                                       it costs                                                               */
-    FEASTHIP_SOLVER_COCG = 3       /* conjugate-orthogonal CG for the complex-SYMMETRIC shifted
+    FEASTHIP_SOLVER_COCG = 3,      /* conjugate-orthogonal CG for the complex-SYMMETRIC shifted
                                       systems that real-symmetric A, B produce (one operator
                                       application per iteration); not in the reference      */
+    FEASTHIP_SOLVER_SHIFTED_COCG = 5 /* COCG whose contour sweep shares ONE Krylov space among the local nodes when
+                                      B = I (shifted COCG: the matrices z_e I - A differ by multiples of the identity, so
+                                      only a seed node applies the operator, the others follow by scalar recurrences).
+                                      Replaces the solve loop over the nodes, src/sparse/feast_sparse.jl:318-369 and
+                                      :164-203, for real CSR A without B, fp64 panels, feasthip_contour_apply without
+                                      moments; every other case runs exactly as FEASTHIP_SOLVER_COCG                */
 };
 
 enum { FEASTHIP_STORAGE_CSR = 0, FEASTHIP_STORAGE_CSC = 1 };
@@ -425,6 +431,13 @@ int  feasthip_last_node_iterations(feasthip_handle h, int* out, int n);
  * re-balance the node lists between refinement loops deterministically (nodes next to the real axis need 10x the
  * iterations of the others).                                                                              */
 int  feasthip_last_global_node_iterations(feasthip_handle h, int* out, int n);
+/* Whether the last feasthip_contour_apply[_resident] took the shifted COCG sweep (FEASTHIP_SOLVER_SHIFTED_COCG and an
+ * eligible problem) on this rank, and what it cost: the seed's contour node, the iterations of the seed recurrence (one
+ * operator product each; the last one may only find every node converged) and the SpMM node-passes of the sweep -- the
+ * seed's alone, where the solve loop over the nodes (src/sparse/feast_sparse.jl:318-369, :164-203) makes one per node and
+ * iteration.  Sums over the 64-column panels of a wide sweep.  used = 0: seed_node = -1, the counts are 0.  Any pointer
+ * may be null.                                                                                              */
+int  feasthip_last_shifted_sweep(feasthip_handle h, int* used, int* seed_node, int* seed_iterations, int* spmm_node_passes);
 /* [local node][m] iterations per column of the last iterative sweep (row-major, n entries). */
 int  feasthip_last_column_iterations(feasthip_handle h, int* out, int n);
 int  feasthip_profile_enable(feasthip_handle h, int enable);
