@@ -629,6 +629,54 @@ static int fh_upload_coefs(feasthip_ctx* h, const char* name, const std::vector<
     return 0;
 }
 
+// shifted-operator coefficients S_e = z_e B - A as [nodes][ld] arrays: coefA = -1, coefB = z_e in every column of node e
+static int fh_upload_shift_coefs(feasthip_ctx* h, const char* nameA, const char* nameB, const cplx* z, int nodes, int ld,
+                                 cplx** dca, cplx** dcb) {
+    std::vector<cplx> ca((size_t)nodes * ld, cmake(-1, 0)), cb((size_t)nodes * ld);
+    for (int e = 0; e < nodes; ++e)
+        for (int c = 0; c < ld; ++c) cb[(size_t)e * ld + c] = z[e];
+    const int rc = fh_upload_coefs(h, nameA, ca, dca);
+    return rc ? rc : fh_upload_coefs(h, nameB, cb, dcb);
+}
+
+// the column mask of the running sweep, padded with ones to ld, in "kry_colmask"; *mask = null when no mask is live
+static int fh_upload_col_mask(feasthip_ctx* h, int ld, const int** mask) {
+    *mask = nullptr;
+    if (!h->mask_live || h->col_mask.empty()) return 0;
+    std::vector<int> mk(ld, 1);
+    for (int c = 0; c < ld && c < (int)h->col_mask.size(); ++c) mk[c] = h->col_mask[c];
+    void* p;
+    const int rc = fh_get_buf(h, "kry_colmask", ld * sizeof(int), &p);
+    if (rc) return rc;
+    FH_CHECK(hipMemcpyAsync(p, mk.data(), ld * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    FH_CHECK(hipStreamSynchronize(h->stream));
+    *mask = (const int*)p;
+    return 0;
+}
+
+// start factors of a shared start, [nodes][ld]: f[e][c] = 1 / (z_e - lambda_c); 1 without Ritz values and in the padding
+static std::vector<cplx> fh_start_factors(const std::vector<cplx>& z, int nodes, int m, int ld, const double* lambda_host) {
+    std::vector<cplx> fs((size_t)nodes * ld, cmake(1, 0));
+    if (lambda_host)
+        for (int e = 0; e < nodes; ++e)
+            for (int c = 0; c < m; ++c) fs[(size_t)e * ld + c] = cdiv(cmake(1, 0), cmake(z[e].x - lambda_host[c], z[e].y));
+    return fs;
+}
+
+// the Ritz values of a warm start, padded with zeros to ld, in "ca_lam"; *dlam = null without a warm start
+static int fh_upload_ritz_lambda(feasthip_ctx* h, const double* ritz_lambda, int m, int ld, double** dlam) {
+    *dlam = nullptr;
+    if (!ritz_lambda) return 0;
+    std::vector<double> lam(ld, 0.0);
+    for (int c = 0; c < m; ++c) lam[c] = ritz_lambda[c];
+    void* p;
+    const int rc = fh_get_buf(h, "ca_lam", ld * sizeof(double), &p);
+    if (rc) return rc;
+    FH_CHECK(hipMemcpy(p, lam.data(), ld * sizeof(double), hipMemcpyHostToDevice));
+    *dlam = (double*)p;
+    return 0;
+}
+
 // Small device -> host copy: lands in the pinned ring (one DMA, no pageable staging), *slot points at it; valid after the
 // caller's next stream synchronisation and until the ring wraps
 static int fh_download_small(feasthip_ctx* h, const void* src, size_t bytes, const void** slot, std::vector<char>& fallback) {
@@ -697,130 +745,191 @@ static int fh_iter_throttle(feasthip_ctx* h, unsigned tag, std::chrono::steady_c
     return 0;
 }
 
-// sum_acc != null (COCG only): "sum mode" -- X keeps the initial guess, every step alpha p of every
-// node is added, weighted with wnode[e], to the N x ld accumulator sum_acc (zeroed by the caller), so
-// that  sum_e w_e X_e(final) = sum_e w_e X_e(initial) + sum_acc.
-// shared_src != null (sum mode, prec 64): the initial residual of every node is  f_node,c * shared_src  with
-// f = 1/(z_node - shared_lambda[c]) (device array, Ritz warm start) or 1 (shared_lambda == null: zero guess, the source
-// is RHS).  X and RHS are then never read: no warm-start panels, no residual product, no separate P = R pass.
-static int fh_krylov(feasthip_ctx* h, int method, int prec, int ld, int m, int nodes, const std::vector<cplx>& z,
-                     const cplx* RHS, cplx* X, size_t stride, fh_solve_result& res, cplx* sum_acc = nullptr,
-                     const std::vector<cplx>* wnode = nullptr, const cplx* shared_src = nullptr,
-                     const double* shared_lambda = nullptr, const cplx* dznode = nullptr, const double* shared_lambda_host = nullptr) {
-    if (h->kind != 2) prec = 64;          // the dense operator kernel takes complex128 panels only
-    if (method != 1 || !wnode) sum_acc = nullptr;
-    const int N = (int)fh_N(h);
-    const size_t panel = (size_t)N * ld;
-    if (stride != panel) { h->last_error = "internal: solution stride mismatch"; return FEASTHIP_ERROR_INTERNAL; }
+// partial-sum rows that one launch of the fused vector kernels leaves (half = 1: the 8 B/element geometry)
+static int fh_fused_vec_rows(int N, int ld, int half) {
+    int blk, seg, per;
+    fh_fused_vec_geometry(N, ld, half, &blk, &seg, &per);
+    return blk * seg;
+}
+
+// The queueing loop of the Krylov sweeps.  It never blocks in the HIP runtime: chunks of `check_every` steps are queued back
+// to back (body(it) queues step `it`), each chunk followed by a tiny kernel that publishes (chunk tag, sum of live[0 .. nlive))
+// to a host-mapped word.  The host polls that word, stays at most three chunks ahead of the device and stops queueing once a
+// published count is zero.  (A hipStreamSynchronize per chunk idled the GPU for milliseconds each time: 1.1 s -> 0.7 s per
+// cfg-3 solve.)  N and nodes scale the deadline.  Returns the number of steps queued; *rc != 0: a step or the throttle failed.
+template <class Body>
+static int fh_queue_chunks(feasthip_ctx* h, const int* live, int nlive, int N, int nodes, Body body, int* rc) {
+    const int check_every = getenv("FH_CHECK_EVERY") ? std::max(1, atoi(getenv("FH_CHECK_EVERY"))) : 16;
+    *h->h_progress = 0ull;
+    int it = *rc = 0;
+    unsigned tag = 0;
+    bool all_done = false;
+    const auto t_loop0 = std::chrono::steady_clock::now();
+    while (it < h->maxit && !all_done) {
+        const int chunk = std::min(check_every, h->maxit - it);
+        for (int k = 0; k < chunk; ++k)
+            if ((*rc = body(it + k))) return it + k;
+        it += chunk;
+        ++tag;
+        fh_launch_publish_progress(live, nlive, h->d_progress, tag, h->stream);
+        if ((*rc = fh_iter_throttle(h, tag, t_loop0, N, nodes, &all_done))) return it;
+    }
+    return it;
+}
+
+// Per-column bookkeeping of `nodes` nodes ([nodes][ld] device arrays; d_target: FH_FAIL_TARGET only; the rules: fh_policy.hpp, fh_column_failed), folded into res: the
+// iterations per column and per node, the worst relative residual and the status of node node0 + e (the caller sizes
+// res.status).
+static int fh_collect_columns(feasthip_ctx* h, const int* d_iters, const int* d_status, const int* d_active, const double* d_rnorm,
+                              const double* d_r0norm, const double* d_target, int nodes, int m, int ld, int node0,
+                              fh_fail_rule rule, fh_solve_result& res) {
+    const size_t nl = (size_t)nodes * ld;
+    std::vector<int> iters(nl), status(nl), active(nl);
+    std::vector<double> rnorm(nl), r0(nl), target(d_target ? nl : 0);
+    FH_CHECK(hipMemcpy(iters.data(), d_iters, nl * sizeof(int), hipMemcpyDeviceToHost));
+    FH_CHECK(hipMemcpy(status.data(), d_status, nl * sizeof(int), hipMemcpyDeviceToHost));
+    FH_CHECK(hipMemcpy(active.data(), d_active, nl * sizeof(int), hipMemcpyDeviceToHost));
+    FH_CHECK(hipMemcpy(rnorm.data(), d_rnorm, nl * sizeof(double), hipMemcpyDeviceToHost));
+    FH_CHECK(hipMemcpy(r0.data(), d_r0norm, nl * sizeof(double), hipMemcpyDeviceToHost));
+    if (d_target) FH_CHECK(hipMemcpy(target.data(), d_target, nl * sizeof(double), hipMemcpyDeviceToHost));
+    for (int e = 0; e < nodes; ++e) {
+        int mx = 0, st = 0;
+        for (int c = 0; c < m; ++c) {
+            const size_t i = (size_t)e * ld + c;
+            mx = std::max(mx, iters[i]);
+            res.col_iters.push_back(iters[i]);
+            if (fh_column_failed(rule, active[i], status[i], rnorm[i], r0[i], d_target ? target[i] : 0.0, h->atol, h->rtol)) st = FEASTHIP_ERROR_NO_CONVERGENCE;
+            if (r0[i] > 0) res.max_rel_res = std::max(res.max_rel_res, rnorm[i] / r0[i]);
+        }
+        res.iters_sum += mx; res.node_iters.push_back(mx); res.max_iters = std::max(res.max_iters, mx);
+        res.status[node0 + e] = st;
+    }
+    return 0;
+}
+
+// The optional parts of a fh_krylov call; default-constructed: a plain solve from the guess in X.
+// sum_acc and wnode (COCG only): "sum mode" -- X keeps the initial guess, every step alpha p of every node is added, weighted
+// with wnode[e], to the N x ld accumulator sum_acc (zeroed by the caller): sum_e w_e X_e(final) = sum_e w_e X_e(initial) + sum_acc.
+// shared_src (sum mode, prec 64): the initial residual of every node is  f_node,c * shared_src  with f = 1/(z_node -
+// shared_lambda[c]) (Ritz warm start: the values on the device and on the host, dznode: the nodes on the device) or 1 (no
+// shared_lambda: zero guess, the source is RHS).  X and RHS are then never read: no warm-start panels, no residual product.
+struct fh_krylov_opts {
+    cplx* sum_acc = nullptr;
+    const std::vector<cplx>* wnode = nullptr;
+    const cplx *shared_src = nullptr, *dznode = nullptr;
+    const double *shared_lambda = nullptr, *shared_lambda_host = nullptr;
+};
+
+namespace {      // (internal linkage for the member functions, as the static helpers have)
+// What the phases of fh_krylov share: the shape of the call, the work panels and the argument blocks of the kernels
+struct fh_krylov_work {
+    feasthip_ctx* h;
+    fh_solve_result& res;
+    int method, prec, ld, m, nodes, N;
+    size_t panel;
+    bool fused = false, lazy = false;
+    void *R, *Rh, *P, *V, *S, *T, *D = nullptr, *RHS32 = nullptr, *Xk = nullptr;    // Xk: the panel the recurrences update, X or D
+    fh_krylov_scalars s;
+    double *r0_64, *inv_r0;                  // fp64 initial-residual norms and their inverses (mixed precision)
+    cplx *part1, *part2, *sp[2] = {nullptr, nullptr};
+    int nblk_vec, fv_rows = 0, fv1_rows = 0; // partial rows of the vector kernels; fv1: the lazy start's first fused launch
+    cplx *sum_acc = nullptr, *dfs = nullptr; // dfs, lazy_src: start factors and shared source of a lazy start
+    const cplx* lazy_src = nullptr;
+    fh_op_call oc;                           // the argument blocks of the operator, finalize and vector kernels
+    fh_fin_args fa;
+    fh_vec_args va;
+    fh_fused_fin_args ff;                    // (fused iteration; s, rho, rr and tickets are filled once)
+    int alloc(const std::vector<cplx>& z, const std::vector<cplx>* wnode);
+    int start(const std::vector<cplx>& z, const cplx* RHS, cplx* X, const fh_krylov_opts& opt);
+    void bicgstab_step(), cocg_step(), cocg_fused_step(int it);
+};
+
+// allocate: the work panels R, Rhat, P, V, S, T (+ D and RHS32 for the mixed-precision correction), the per-column scalars
+// and the partial sums come from the handle's buffer cache; the shift coefficients, the node weights and the column mask go
+// up; the argument blocks of the operator, finalize and vector kernels are filled.
+int fh_krylov_work::alloc(const std::vector<cplx>& z, const std::vector<cplx>* wnode) {
     const size_t esz = prec == 32 ? sizeof(cplxf) : sizeof(cplx);
     int rc;
     void* p;
-    // work panels R, Rhat, P, V, S, T (+ D and RHS32 for the mixed-precision correction)
     const int nvec = 6 + (prec == 32 ? 2 : 0);
     if ((rc = fh_get_buf(h, "kry_vecs", (size_t)nvec * nodes * panel * esz, &p))) return rc;
     char* base = (char*)p;
-    auto vec = [&](int k) { return (void*)(base + (size_t)k * nodes * panel * esz); };
-    void *R = vec(0), *Rh = vec(1), *P = vec(2), *V = vec(3), *S = vec(4), *T = vec(5);
+    auto vec = [&](int i) { return (void*)(base + (size_t)i * nodes * panel * esz); };
+    R = vec(0); Rh = vec(1); P = vec(2); V = vec(3); S = vec(4); T = vec(5);
+    if (prec == 32) { D = vec(6); RHS32 = vec(7); }
     const size_t nl = (size_t)nodes * ld;
     if ((rc = fh_get_buf(h, "kry_scal_c", 4 * nl * sizeof(cplx), &p))) return rc;
-    fh_krylov_scalars s;
     s.rho = (cplx*)p; s.alpha = s.rho + nl; s.omega = s.alpha + nl; s.beta = s.omega + nl;
     if ((rc = fh_get_buf(h, "kry_scal_d", 5 * nl * sizeof(double), &p))) return rc;
     s.r0norm = (double*)p; s.target = s.r0norm + nl; s.rnorm = s.target + nl;
-    double* r0_64 = s.rnorm + nl;            // fp64 initial-residual norms (mixed precision)
-    double* inv_r0 = r0_64 + nl;
+    r0_64 = s.rnorm + nl; inv_r0 = r0_64 + nl;
     if ((rc = fh_get_buf(h, "kry_scal_i", (4 * nl + 2 * nodes + 4) * sizeof(int), &p))) return rc;
     s.active = (int*)p; s.iters = s.active + nl; s.status = s.iters + nl; s.node_active = s.status + nl;
-    int* d_count = s.node_active + nodes;
-    cplx* d_wnode = nullptr;
     // Fused COCG iteration (fh_sparse.hip): SpMM with five dots -> one finalize -> one vector kernel.  CSR operator through
     // the gather kernel only; FH_COCG_FUSED=0 selects the five-launch form for comparison.
     static const bool fused_off = getenv("FH_COCG_FUSED") && atoi(getenv("FH_COCG_FUSED")) == 0;
-    const bool fused = method == 1 && h->kind == 2 && !fused_off;
+    fused = method == 1 && h->kind == 2 && !fused_off;
     if (sum_acc || fused) {
-        s.accum = d_count + 4; s.node_accum = s.accum + nl;
+        s.accum = s.node_active + nodes + 4; s.node_accum = s.accum + nl;
         FH_CHECK(hipMemsetAsync(s.accum, 0, (nl + nodes) * sizeof(int), h->stream));
     }
-    if (sum_acc) {
-        if ((rc = fh_upload_coefs(h, "kry_wnode", *wnode, &d_wnode))) return rc;
-    }
+    cplx* d_wnode = nullptr;
+    if (sum_acc && (rc = fh_upload_coefs(h, "kry_wnode", *wnode, &d_wnode))) return rc;
     const int nblk_op = fh_op_nblk(h, ld);
-    const int nblk_vec = fh_kry_nblk(N, ld, nodes);
-    int fv_blk = 0, fv_seg = 0, fv_per = 0;
-    int fv1_blk = 0, fv1_seg = 0, fv1_per = 0;        // geometry of the lazy start's first vector launch
-    if (fused) fh_fused_vec_geometry(N, ld, prec == 32, &fv_blk, &fv_seg, &fv_per);
-    if (fused) fh_fused_vec_geometry(N, ld, 1, &fv1_blk, &fv1_seg, &fv1_per);
-    const int nblk_max = std::max(std::max(std::max(nblk_op, nblk_vec), fv_blk * fv_seg), fv1_blk * fv1_seg);
+    nblk_vec = fh_kry_nblk(N, ld, nodes);
+    if (fused) { fv_rows = fh_fused_vec_rows(N, ld, prec == 32); fv1_rows = fh_fused_vec_rows(N, ld, 1); }
+    const int nblk_max = std::max(std::max(std::max(nblk_op, nblk_vec), fv_rows), fv1_rows);
     if ((rc = fh_get_buf(h, "kry_partials", 2 * (size_t)nodes * nblk_max * ld * sizeof(cplx), &p))) return rc;
-    cplx* part1 = (cplx*)p;
-    cplx* part2 = part1 + (size_t)nodes * nblk_max * ld;
-    cplx* sp[2] = {nullptr, nullptr};
-    unsigned long long* d_tickets = nullptr;
+    part1 = (cplx*)p; part2 = part1 + (size_t)nodes * nblk_max * ld;
     if (fused) {
         const size_t one = (size_t)nodes * nblk_op * ld;
         if ((rc = fh_get_buf(h, "kry_partials_op", 2 * one * sizeof(cplx), &p))) return rc;
         for (int q = 0; q < 2; ++q) sp[q] = (cplx*)p + q * one;
         if ((rc = fh_get_buf(h, "kry_tickets", (size_t)nodes * sizeof(unsigned long long), &p))) return rc;
-        d_tickets = (unsigned long long*)p;
-        FH_CHECK(hipMemsetAsync(d_tickets, 0, (size_t)nodes * sizeof(unsigned long long), h->stream));
+        ff.s = s; ff.rho = part1; ff.rr = part2; ff.tickets = (unsigned long long*)p;
+        FH_CHECK(hipMemsetAsync(ff.tickets, 0, (size_t)nodes * sizeof(unsigned long long), h->stream));
     }
-
-    // shifted-operator coefficients: S_e = z_e B - A
-    std::vector<cplx> ca(nl), cb(nl);
-    for (int e = 0; e < nodes; ++e)
-        for (int c = 0; c < ld; ++c) { ca[e * ld + c] = cmake(-1, 0); cb[e * ld + c] = z[e]; }
     cplx *dca, *dcb;
-    if ((rc = fh_upload_coefs(h, "kry_coefA", ca, &dca))) return rc;
-    if ((rc = fh_upload_coefs(h, "kry_coefB", cb, &dcb))) return rc;
-
-    fh_op_call oc;
+    if ((rc = fh_upload_shift_coefs(h, "kry_coefA", "kry_coefB", z.data(), nodes, ld, &dca, &dcb))) return rc;
     oc.m = m; oc.uniform_coef = 1; oc.coefA = dca; oc.coefB = dcb; oc.nodes = nodes;
     oc.partial1 = part1; oc.partial2 = part2;
-    fh_fin_args fa;
     fa.s = s; fa.partial1 = part1; fa.partial2 = part2; fa.m = m; fa.rtol = h->rtol; fa.atol = h->atol;
-    fa.atol_scale = nullptr; fa.mode = method; fa.col_mask = nullptr;
-    if (h->mask_live && !h->col_mask.empty()) {
-        std::vector<int> mk(ld, 1);
-        for (int c = 0; c < ld && c < (int)h->col_mask.size(); ++c) mk[c] = h->col_mask[c];
-        if ((rc = fh_get_buf(h, "kry_colmask", ld * sizeof(int), &p))) return rc;
-        FH_CHECK(hipMemcpyAsync(p, mk.data(), ld * sizeof(int), hipMemcpyHostToDevice, h->stream));
-        FH_CHECK(hipStreamSynchronize(h->stream));
-        fa.col_mask = (const int*)p;
-    }
-    fh_vec_args va;
+    fa.atol_scale = nullptr; fa.mode = method;
+    if ((rc = fh_upload_col_mask(h, ld, &fa.col_mask))) return rc;
     memset(&va, 0, sizeof(va));
     va.N = N; va.node_stride = panel; va.R = R; va.Rhat = Rh; va.P = P; va.V = V; va.S = S; va.T = T;
     va.s = s; va.partial1 = part1; va.partial2 = part2; va.prec = prec;
     va.counters = h->profiling ? h->d_counters : nullptr;
     va.sum_acc = sum_acc; va.wnode = d_wnode; va.sum_scale = (sum_acc && prec == 32) ? r0_64 : nullptr; va.nodes = nodes;
+    return 0;
+}
 
-    void* Xk = X;        // the panel the Krylov recurrences update
-    const bool shared_start = shared_src && sum_acc && method == 1 && prec == 64;
-    if (shared_start) {
-        // nothing to do here: R, P and the norms come from k_cocg_init_shared below
-    } else if (prec == 64) {
+// start: R, P (BiCGStab: Rhat too), rho and the norms of the stop test.  fp64: R = RHS - S X in one operator product, then
+// P = R.  Mixed precision: that residual in fp64, normalised per column and narrowed to complex64; the recurrences then update
+// the correction D from zero instead of X.  Shared start (sum mode, fp64): R = P = f_e,c * shared_src; lazy (fused iteration
+// over a real CSR operator): not even those are written -- the first operator product reads the source itself and the first
+// vector kernel writes them (fh_sparse.hip: k_cocg_init_lazy).
+int fh_krylov_work::start(const std::vector<cplx>& z, const cplx* RHS, cplx* X, const fh_krylov_opts& opt) {
+    const size_t nl = (size_t)nodes * ld;
+    int rc;
+    Xk = X;
+    const bool shared_start = opt.shared_src && sum_acc && method == 1 && prec == 64;
+    void* R64 = R;                               // mixed precision: the fp64 residual goes to a panel set of its own
+    if (!shared_start && prec == 32 && (rc = fh_get_buf(h, "kry_r64", (size_t)nodes * panel * sizeof(cplx), &R64))) return rc;
+    if (!shared_start) {
         // R = RHS - S X0, ||R||^2
-        oc.prec = 64; oc.X = X; oc.x_stride = panel; oc.Y = R; oc.y_stride = panel; oc.Bvec = RHS; oc.b_stride = 0;
+        oc.prec = 64; oc.X = X; oc.x_stride = panel; oc.Y = R64; oc.y_stride = panel; oc.Bvec = RHS; oc.b_stride = 0;
         oc.dot_mode = 3; oc.node_active = nullptr;
         fa.nblk = fh_apply_operator(h, ld, oc);
         res.op_calls += 1;
-    } else {
-        // fp64 residual of the warm start into the (fp64-sized) tail of the work area
-        void* q;
-        if ((rc = fh_get_buf(h, "kry_r64", (size_t)nodes * panel * sizeof(cplx), &q))) return rc;
-        cplx* R64 = (cplx*)q;
-        oc.prec = 64; oc.X = X; oc.x_stride = panel; oc.Y = R64; oc.y_stride = panel; oc.Bvec = RHS; oc.b_stride = 0;
-        oc.dot_mode = 3; oc.node_active = nullptr;
-        int nb = fh_apply_operator(h, ld, oc);
-        res.op_calls += 1;
+    }
+    if (!shared_start && prec == 32) {
         fh_fin_args f0 = fa;                       // only to obtain ||r0|| per column
-        f0.nblk = nb; f0.rtol = 0.0; f0.atol = 0.0; f0.mode = 0;
+        f0.rtol = 0.0; f0.atol = 0.0; f0.mode = 0;
         fh_launch_fin_init(f0, ld, nodes, h->stream);
         FH_CHECK(hipMemcpyAsync(r0_64, s.r0norm, nl * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
         // narrow: RHS32 = R64 / ||r0||, D = 0, R = RHS32
-        cplxf* D = (cplxf*)vec(6);
-        cplxf* RHS32 = (cplxf*)vec(7);
-        fh_launch_narrow_scaled(R64, panel, RHS32, panel, r0_64, N, ld, nblk_vec, nodes, h->stream);
+        fh_launch_narrow_scaled((const cplx*)R64, panel, (cplxf*)RHS32, panel, r0_64, N, ld, nblk_vec, nodes, h->stream);
         FH_CHECK(hipMemsetAsync(D, 0, (size_t)nodes * panel * sizeof(cplxf), h->stream));
         FH_CHECK(hipMemcpyAsync(R, RHS32, (size_t)nodes * panel * sizeof(cplxf), hipMemcpyDeviceToDevice, h->stream));
         Xk = D;
@@ -832,157 +941,121 @@ static int fh_krylov(feasthip_ctx* h, int method, int prec, int ld, int m, int n
         FH_CHECK(hipMemcpyAsync(inv_r0, hinv.data(), nl * sizeof(double), hipMemcpyHostToDevice, h->stream));
         FH_CHECK(hipStreamSynchronize(h->stream));
         fa.atol_scale = inv_r0;
-        // ||R||^2 of the narrowed residual through a zero-cost pass: reuse cocg_init/copy below
     }
     va.X = Xk;
-    const int vprec = prec;
-    // Lazy start (fused iteration over a CSR operator, both gather kernels): residual and direction of every node are the ONE source panel times a
-    // per-node column factor, so neither is written here; the first operator product reads the source itself and the first
-    // vector kernel writes R and P (fh_sparse.hip: k_cocg_init_lazy).  FH_NO_LAZY_START=1: materialise them as before.
-    const bool lazy_off = getenv("FH_NO_LAZY_START") != nullptr;    // read per call (the tests flip it)
-    const bool lazy = shared_start && fused && h->kind == 2 && !h->csr.is_complex && !lazy_off && (!shared_lambda || shared_lambda_host) &&
-                      !(getenv("FH_LDS_SPMM") && atoi(getenv("FH_LDS_SPMM")) != 0);
-    cplx* dfs = nullptr;
+    // FH_NO_LAZY_START=1: materialise R and P of a shared start as before.  Read per call (the tests flip it).
+    lazy = shared_start && fused && h->kind == 2 && !h->csr.is_complex && !getenv("FH_NO_LAZY_START") &&
+           (!opt.shared_lambda || opt.shared_lambda_host) && !(getenv("FH_LDS_SPMM") && atoi(getenv("FH_LDS_SPMM")) != 0);
     if (lazy) {
-        std::vector<cplx> fs(nl, cmake(1, 0));
-        if (shared_lambda_host)
-            for (int e = 0; e < nodes; ++e)
-                for (int c = 0; c < m; ++c) fs[(size_t)e * ld + c] = cdiv(cmake(1, 0), cmake(z[e].x - shared_lambda_host[c], z[e].y));
-        if ((rc = fh_upload_coefs(h, "kry_fscale", fs, &dfs))) return rc;
+        if ((rc = fh_upload_coefs(h, "kry_fscale", fh_start_factors(z, nodes, m, ld, opt.shared_lambda_host), &dfs))) return rc;
+        lazy_src = opt.shared_src;
         fh_vec_args vs = va;
-        vs.Q = shared_src; vs.first_scale = dfs;
+        vs.Q = opt.shared_src; vs.first_scale = dfs;
         fh_launch_cocg_init_lazy(vs, ld, nblk_vec, nodes, h->stream);
-        fa.nblk = nblk_vec;
-        fh_launch_fin_init(fa, ld, nodes, h->stream);
     } else if (shared_start) {
         fh_vec_args vs = va;
-        vs.Q = shared_src; vs.lambda = shared_lambda; vs.znode = dznode;
+        vs.Q = opt.shared_src; vs.lambda = opt.shared_lambda; vs.znode = opt.dznode;
         fh_launch_cocg_init_shared(vs, ld, nblk_vec, nodes, h->stream);
-        fa.nblk = nblk_vec;
-        fh_launch_fin_init(fa, ld, nodes, h->stream);
-    } else if (method == 1) {
-        // COCG: P = R, rho = r^T r, ||r||
+    } else if (method == 1 || prec == 32) {
+        // COCG: P = R, rho = r^T r, ||r||.  BiCGStab needs it for ||R||^2 of the narrowed residual only.
         fh_launch_cocg_init(va, ld, nblk_vec, nodes, h->stream);
-        fa.nblk = nblk_vec;
-        fh_launch_fin_init(fa, ld, nodes, h->stream);
-    } else {
-        if (prec == 32) {
-            // partial2 = ||R||^2 of the narrowed residual (cocg_init also writes P = R)
-            fh_launch_cocg_init(va, ld, nblk_vec, nodes, h->stream);
-            fa.nblk = nblk_vec;
-        }
-        fa.mode = 0;
-        fh_launch_fin_init(fa, ld, nodes, h->stream);
-        fh_launch_copy_r(va, ld, nblk_vec, nodes, h->stream);            // Rhat = R ; P = R
     }
-    (void)vprec;
-
+    if (method == 1 || prec == 32) fa.nblk = nblk_vec;     // else: the partial rows of the residual product
+    fh_launch_fin_init(fa, ld, nodes, h->stream);
+    if (method == 0) fh_launch_copy_r(va, ld, nblk_vec, nodes, h->stream);            // Rhat = R ; P = R
     oc.prec = prec; oc.Bvec = nullptr; oc.b_stride = 0; oc.x_stride = panel; oc.y_stride = panel;
-    // Iterate without ever blocking in the HIP runtime: chunks of `check_every` iterations are
-    // queued back to back, each followed by a tiny kernel that publishes (chunk tag, active
-    // columns) to a host-mapped word.  The host polls that word, stays at most two chunks ahead
-    // of the device and stops queueing once a published count is zero.  (A hipStreamSynchronize
-    // per chunk idled the GPU for milliseconds each time: 1.1 s -> 0.7 s per cfg-3 solve.)
-    const int check_every = getenv("FH_CHECK_EVERY") ? std::max(1, atoi(getenv("FH_CHECK_EVERY"))) : 16;
-    (void)d_count;
-    *h->h_progress = 0ull;
-    int it = 0;
-    unsigned tag = 0;
-    bool all_done = false;
-    auto t_loop0 = std::chrono::steady_clock::now();
-    while (it < h->maxit && !all_done) {
-        int chunk = std::min(check_every, h->maxit - it);
-        for (int k = 0; k < chunk; ++k) {
-            if (method == 0) {
-                // V = S P, sigma = <Rhat, V>
-                oc.X = P; oc.Y = V; oc.U = Rh; oc.u_stride = panel; oc.dot_mode = 1; oc.node_active = s.node_active;
-                fa.nblk = fh_apply_operator(h, ld, oc);
-                fh_prof_begin(h, "dot_finalize"); fh_launch_fin_alpha(fa, ld, nodes, h->stream); fh_prof_end(h);
-                fh_prof_begin(h, "bicg_s"); fh_launch_s_update(va, ld, nblk_vec, nodes, h->stream); fh_prof_end(h);
-                // T = S S, <T,S>, <T,T>
-                oc.X = S; oc.Y = T; oc.U = nullptr; oc.dot_mode = 2;
-                fa.nblk = fh_apply_operator(h, ld, oc);
-                fh_prof_begin(h, "dot_finalize"); fh_launch_fin_omega(fa, ld, nodes, h->stream); fh_prof_end(h);
-                fh_prof_begin(h, "bicg_xr"); fh_launch_xr_update(va, ld, nblk_vec, nodes, h->stream); fh_prof_end(h);
-                fa.nblk = nblk_vec;
-                fh_prof_begin(h, "dot_finalize"); fh_launch_fin_rho(fa, ld, nodes, h->stream); fh_prof_end(h);
-                fh_prof_begin(h, "bicg_p"); fh_launch_p_update(va, ld, nblk_vec, nodes, h->stream); fh_prof_end(h);
-                res.op_calls += 2;
-            } else if (fused) {
-                // Q = S P (stored in V), sigma = p^T q, kappa = q^T q (fh_sparse.hip, fused COCG)
-                const bool first_lazy = lazy && it + k == 0;
-                oc.X = first_lazy ? (const void*)shared_src : P; oc.x_stride = first_lazy ? 0 : panel; oc.colscale = first_lazy ? dfs : nullptr;
-                oc.Y = V; oc.U = nullptr; oc.dot_mode = 6; oc.node_active = s.node_active;
-                oc.partial1 = sp[0]; oc.partial2 = sp[1];
-                va.first_src = first_lazy ? shared_src : nullptr; va.first_scale = first_lazy ? dfs : nullptr;
-                fh_fused_fin_args ff;
-                ff.s = s; ff.sig = sp[0]; ff.kap = sp[1];
-                ff.rho = part1; ff.rr = part2; ff.tickets = d_tickets; ff.final_check = 0;
-                ff.predict_stop = (h->rtol >= 1e-3 && h->atol == 0.0) ? 1 : 0;
-                ff.nblk_op = fh_apply_operator(h, ld, oc);
-                ff.nblk_vec = (it + k == 0) ? fa.nblk : ((lazy && it + k == 1) ? fv1_blk * fv1_seg : fv_blk * fv_seg);      // first iteration: the init kernel's partial rows; second (lazy start): the half-geometry launch's
-                fh_prof_begin(h, "dot_finalize"); fh_launch_fused_fin(ff, ld, nodes, h->stream); fh_prof_end(h);
-                fh_prof_begin(h, "cocg_vec"); fh_launch_fused_vec(va, ld, h->stream); fh_prof_end(h);
-                res.op_calls += 1;
-            } else {
-                // Q = S P (stored in V), sigma = p^T S p
-                oc.X = P; oc.Y = V; oc.U = nullptr; oc.dot_mode = 4; oc.node_active = s.node_active;
-                fa.nblk = fh_apply_operator(h, ld, oc);
-                fh_prof_begin(h, "dot_finalize"); fh_launch_fin_alpha(fa, ld, nodes, h->stream); fh_prof_end(h);
-                fh_prof_begin(h, "cocg_xr"); fh_launch_cocg_update(va, ld, nblk_vec, nodes, h->stream); fh_prof_end(h);
-                fa.nblk = nblk_vec;
-                fh_prof_begin(h, "dot_finalize"); fh_launch_fin_rho(fa, ld, nodes, h->stream); fh_prof_end(h);
-                fh_prof_begin(h, "cocg_p");
-                if (sum_acc) fh_launch_cocg_p_sum(va, ld, nodes, h->stream);
-                else fh_launch_cocg_p(va, ld, nblk_vec, nodes, h->stream);
-                fh_prof_end(h);
-                res.op_calls += 1;
-            }
-        }
-        it += chunk;
-        ++tag;
-        fh_launch_publish_progress(s.node_active, nodes, h->d_progress, tag, h->stream);
-        if ((rc = fh_iter_throttle(h, tag, t_loop0, N, nodes, &all_done))) return rc;
-    }
-    if (fused && it > 0) {
-        // the stop test of the last step: true norms from the last vector kernel's partials (no SpMM follows it)
-        fh_fused_fin_args ff;
-        ff.s = s; ff.sig = ff.kap = nullptr; ff.rho = part1; ff.rr = part2; ff.tickets = d_tickets;
-        ff.nblk_op = 0; ff.nblk_vec = (lazy && it == 1) ? fv1_blk * fv1_seg : fv_blk * fv_seg; ff.final_check = 1; ff.predict_stop = 0;
+    return 0;
+}
+
+// One BiCGStab step: two operator products, each with its finalize and vector update, then rho and the new direction
+void fh_krylov_work::bicgstab_step() {
+    // V = S P, sigma = <Rhat, V>
+    oc.X = P; oc.Y = V; oc.U = Rh; oc.u_stride = panel; oc.dot_mode = 1; oc.node_active = s.node_active;
+    fa.nblk = fh_apply_operator(h, ld, oc);
+    fh_prof_begin(h, "dot_finalize"); fh_launch_fin_alpha(fa, ld, nodes, h->stream); fh_prof_end(h);
+    fh_prof_begin(h, "bicg_s"); fh_launch_s_update(va, ld, nblk_vec, nodes, h->stream); fh_prof_end(h);
+    // T = S S, <T,S>, <T,T>
+    oc.X = S; oc.Y = T; oc.U = nullptr; oc.dot_mode = 2;
+    fa.nblk = fh_apply_operator(h, ld, oc);
+    fh_prof_begin(h, "dot_finalize"); fh_launch_fin_omega(fa, ld, nodes, h->stream); fh_prof_end(h);
+    fh_prof_begin(h, "bicg_xr"); fh_launch_xr_update(va, ld, nblk_vec, nodes, h->stream); fh_prof_end(h);
+    fa.nblk = nblk_vec;
+    fh_prof_begin(h, "dot_finalize"); fh_launch_fin_rho(fa, ld, nodes, h->stream); fh_prof_end(h);
+    fh_prof_begin(h, "bicg_p"); fh_launch_p_update(va, ld, nblk_vec, nodes, h->stream); fh_prof_end(h);
+    res.op_calls += 2;
+}
+
+// One COCG step in five launches: Q = S P with sigma = p^T S p, finalize, x / r update, finalize of rho, new direction
+void fh_krylov_work::cocg_step() {
+    oc.X = P; oc.Y = V; oc.U = nullptr; oc.dot_mode = 4; oc.node_active = s.node_active;     // Q is stored in V
+    fa.nblk = fh_apply_operator(h, ld, oc);
+    fh_prof_begin(h, "dot_finalize"); fh_launch_fin_alpha(fa, ld, nodes, h->stream); fh_prof_end(h);
+    fh_prof_begin(h, "cocg_xr"); fh_launch_cocg_update(va, ld, nblk_vec, nodes, h->stream); fh_prof_end(h);
+    fa.nblk = nblk_vec;
+    fh_prof_begin(h, "dot_finalize"); fh_launch_fin_rho(fa, ld, nodes, h->stream); fh_prof_end(h);
+    fh_prof_begin(h, "cocg_p");
+    if (sum_acc) fh_launch_cocg_p_sum(va, ld, nodes, h->stream);
+    else fh_launch_cocg_p(va, ld, nblk_vec, nodes, h->stream);
+    fh_prof_end(h);
+    res.op_calls += 1;
+}
+
+// Step `it` of the fused COCG iteration (fh_sparse.hip): Q = S P (stored in V) with sigma = p^T q and kappa = q^T q, one
+// finalize, one vector kernel.  Step 0 of a lazy start reads the shared source times the start factors instead of P.
+void fh_krylov_work::cocg_fused_step(int it) {
+    const bool first_lazy = lazy && it == 0;
+    oc.X = first_lazy ? (const void*)lazy_src : P; oc.x_stride = first_lazy ? 0 : panel; oc.colscale = first_lazy ? dfs : nullptr;
+    oc.Y = V; oc.U = nullptr; oc.dot_mode = 6; oc.node_active = s.node_active;
+    oc.partial1 = sp[0]; oc.partial2 = sp[1];
+    va.first_src = first_lazy ? lazy_src : nullptr; va.first_scale = first_lazy ? dfs : nullptr;
+    ff.sig = sp[0]; ff.kap = sp[1]; ff.final_check = 0;
+    ff.predict_stop = (h->rtol >= 1e-3 && h->atol == 0.0) ? 1 : 0;
+    ff.nblk_op = fh_apply_operator(h, ld, oc);
+    // first step: the init kernel's partial rows; second (lazy start): the half-geometry launch's
+    ff.nblk_vec = it == 0 ? fa.nblk : ((lazy && it == 1) ? fv1_rows : fv_rows);
+    fh_prof_begin(h, "dot_finalize"); fh_launch_fused_fin(ff, ld, nodes, h->stream); fh_prof_end(h);
+    fh_prof_begin(h, "cocg_vec"); fh_launch_fused_vec(va, ld, h->stream); fh_prof_end(h);
+    res.op_calls += 1;
+}
+
+}  // namespace
+
+// Batched BiCGStab (method 0) or COCG (method 1) on `nodes` panels, in five phases: allocate, start, iterate, finish, collect.
+static int fh_krylov(feasthip_ctx* h, int method, int prec, int ld, int m, int nodes, const std::vector<cplx>& z,
+                     const cplx* RHS, cplx* X, size_t stride, fh_solve_result& res, const fh_krylov_opts& opt) {
+    if (h->kind != 2) prec = 64;          // the dense operator kernel takes complex128 panels only
+    fh_krylov_work k{h, res};
+    k.method = method; k.prec = prec; k.ld = ld; k.m = m; k.nodes = nodes; k.N = (int)fh_N(h); k.panel = (size_t)k.N * ld;
+    k.sum_acc = (method == 1 && opt.wnode) ? opt.sum_acc : nullptr;
+    if (stride != k.panel) { h->last_error = "internal: solution stride mismatch"; return FEASTHIP_ERROR_INTERNAL; }
+    int rc;
+    if ((rc = k.alloc(z, opt.wnode))) return rc;
+    if ((rc = k.start(z, RHS, X, opt))) return rc;
+    // iterate: the steps go to the stream in chunks; the published count is the number of nodes with a live column
+    const auto t_loop0 = std::chrono::steady_clock::now();
+    const int it = fh_queue_chunks(h, k.s.node_active, nodes, k.N, nodes, [&](int i) {
+        method == 0 ? k.bicgstab_step() : k.fused ? k.cocg_fused_step(i) : k.cocg_step();
+        return 0;
+    }, &rc);
+    if (rc) return rc;
+    // finish: the fused iteration's last stop test (true norms from the last vector kernel's partials: no SpMM follows it),
+    // the one synchronisation of the solve, and X = X0 + ||r0|| D for a mixed-precision solve outside sum mode
+    if (k.fused && it > 0) {
+        fh_fused_fin_args& ff = k.ff;
+        ff.sig = ff.kap = nullptr; ff.nblk_op = 0; ff.final_check = 1; ff.predict_stop = 0;
+        ff.nblk_vec = (k.lazy && it == 1) ? k.fv1_rows : k.fv_rows;
         fh_launch_fused_fin(ff, ld, nodes, h->stream);
     }
     FH_CHECK(hipStreamSynchronize(h->stream));
     if (getenv("FH_DEBUG_TIMING"))
         fprintf(stderr, "[fh_krylov] nodes=%d its queued=%d loop wall %.3f ms\n", nodes, it,
                 1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t_loop0).count());
-    if (prec == 32 && !sum_acc)    // X = X0 + ||r0|| d
-        fh_launch_widen_axpy(X, panel, (const cplxf*)Xk, panel, r0_64, N, ld, nblk_vec, nodes, h->stream);
-
-    // gather per-column bookkeeping
-    std::vector<int> iters(nl), status(nl), active(nl);
-    std::vector<double> rnorm(nl), r0(nl);
-    FH_CHECK(hipMemcpy(iters.data(), s.iters, nl * sizeof(int), hipMemcpyDeviceToHost));
-    FH_CHECK(hipMemcpy(status.data(), s.status, nl * sizeof(int), hipMemcpyDeviceToHost));
-    FH_CHECK(hipMemcpy(active.data(), s.active, nl * sizeof(int), hipMemcpyDeviceToHost));
-    FH_CHECK(hipMemcpy(rnorm.data(), s.rnorm, nl * sizeof(double), hipMemcpyDeviceToHost));
-    FH_CHECK(hipMemcpy(r0.data(), s.r0norm, nl * sizeof(double), hipMemcpyDeviceToHost));
+    if (prec == 32 && !k.sum_acc)
+        fh_launch_widen_axpy(X, k.panel, (const cplxf*)k.Xk, k.panel, k.r0_64, k.N, ld, k.nblk_vec, nodes, h->stream);
+    // collect: the per-column counts, norms and flags come back and fold into res
     res.status.assign(nodes, 0);
-    for (int e = 0; e < nodes; ++e) {
-        int mx = 0, st = 0;
-        for (int c = 0; c < m; ++c) {
-            int i = e * ld + c;
-            mx = std::max(mx, iters[i]);
-            res.col_iters.push_back(iters[i]);
-            if (active[i] || !std::isfinite(rnorm[i])) st = std::max(st, (int)FEASTHIP_ERROR_NO_CONVERGENCE);
-            else if (status[i] == 8 && !(rnorm[i] <= h->atol + h->rtol * r0[i])) st = std::max(st, (int)FEASTHIP_ERROR_NO_CONVERGENCE);
-            if (r0[i] > 0) res.max_rel_res = std::max(res.max_rel_res, rnorm[i] / r0[i]);
-        }
-        res.iters_sum += mx;
-        res.node_iters.push_back(mx);
-        res.max_iters = std::max(res.max_iters, mx);
-        res.status[e] = st;
-    }
-    return 0;
+    return fh_collect_columns(h, k.s.iters, k.s.status, k.s.active, k.s.rnorm, k.s.r0norm, nullptr, nodes, m, ld, 0,
+                              FH_FAIL_STOP_TEST, res);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1021,32 +1094,19 @@ static int fh_shifted_cocg(feasthip_ctx* h, int ld, int m, int nodes, const std:
     a.col_step = a.status + nl; a.node_step = a.col_step + ld;
     a.tile_alive = a.node_step + (size_t)ntiles * nodes; a.alive_total = a.tile_alive + ntiles; a.passes = a.alive_total + 1;
     FH_CHECK(hipMemsetAsync(a.active, 0, nint * sizeof(int), h->stream));
-    // start factors, shifts against the seed, weights
-    std::vector<cplx> fs(nl, cmake(1, 0)), sg(nodes), ca(ld, cmake(-1, 0)), cb(ld, z[seed]);
-    if (lambda_host)
-        for (int e = 0; e < nodes; ++e)
-            for (int c = 0; c < m; ++c) fs[(size_t)e * ld + c] = cdiv(cmake(1, 0), cmake(z[e].x - lambda_host[c], z[e].y));
+    // start factors, shifts against the seed, weights, the seed's operator coefficients
+    std::vector<cplx> sg(nodes);
     for (int e = 0; e < nodes; ++e) sg[e] = csub(z[e], z[seed]);
     cplx *dfs, *dsg, *dw, *dca, *dcb;
-    if ((rc = fh_upload_coefs(h, "shc_fscale", fs, &dfs))) return rc;
+    if ((rc = fh_upload_coefs(h, "shc_fscale", fh_start_factors(z, nodes, m, ld, lambda_host), &dfs))) return rc;
     if ((rc = fh_upload_coefs(h, "shc_sigma", sg, &dsg))) return rc;
     if ((rc = fh_upload_coefs(h, "shc_wnode", wnode, &dw))) return rc;
-    if ((rc = fh_upload_coefs(h, "shc_coefA", ca, &dca))) return rc;
-    if ((rc = fh_upload_coefs(h, "shc_coefB", cb, &dcb))) return rc;
+    if ((rc = fh_upload_shift_coefs(h, "shc_coefA", "shc_coefB", &z[seed], 1, ld, &dca, &dcb))) return rc;
     a.fscale = dfs; a.sigma = dsg; a.wnode = dw;
-    a.rtol = h->rtol; a.atol = h->atol; a.col_mask = nullptr;
-    if (h->mask_live && !h->col_mask.empty()) {
-        std::vector<int> mk(ld, 1);
-        for (int c = 0; c < ld && c < (int)h->col_mask.size(); ++c) mk[c] = h->col_mask[c];
-        if ((rc = fh_get_buf(h, "kry_colmask", ld * sizeof(int), &p))) return rc;
-        FH_CHECK(hipMemcpyAsync(p, mk.data(), ld * sizeof(int), hipMemcpyHostToDevice, h->stream));
-        FH_CHECK(hipStreamSynchronize(h->stream));
-        a.col_mask = (const int*)p;
-    }
-    int fv_blk, fv_seg, fv_per;
-    fh_fused_vec_geometry(N, ld, 1, &fv_blk, &fv_seg, &fv_per);
+    a.rtol = h->rtol; a.atol = h->atol;
+    if ((rc = fh_upload_col_mask(h, ld, &a.col_mask))) return rc;
     const int nblk_op = fh_op_nblk(h, ld);
-    const int nrow_max = std::max(256, fv_blk * fv_seg);
+    const int nrow_max = std::max(256, fh_fused_vec_rows(N, ld, 1));
     if ((rc = fh_get_buf(h, "shc_partials", 2 * (size_t)(nrow_max + nblk_op) * ld * sizeof(cplx), &p))) return rc;
     a.rho_part = (cplx*)p; a.rr_part = a.rho_part + (size_t)nrow_max * ld;
     cplx* sp0 = a.rr_part + (size_t)nrow_max * ld;
@@ -1058,55 +1118,24 @@ static int fh_shifted_cocg(feasthip_ctx* h, int ld, int m, int nodes, const std:
     oc.m = m; oc.uniform_coef = 1; oc.coefA = dca; oc.coefB = dcb; oc.nodes = 1; oc.prec = 64;
     oc.X = a.P + (size_t)seed * panel; oc.x_stride = panel; oc.Y = a.Qv; oc.y_stride = panel;
     oc.dot_mode = 6; oc.node_active = a.alive_total; oc.partial1 = sp0; oc.partial2 = sp1;
-    const int check_every = getenv("FH_CHECK_EVERY") ? std::max(1, atoi(getenv("FH_CHECK_EVERY"))) : 16;
-    *h->h_progress = 0ull;
-    int it = 0;
-    unsigned tag = 0;
-    bool all_done = false;
-    auto t_loop0 = std::chrono::steady_clock::now();
-    while (it < h->maxit && !all_done) {
-        const int chunk = std::min(check_every, h->maxit - it);
-        for (int k = 0; k < chunk; ++k) {
-            a.nblk_op = fh_apply_operator(h, ld, oc);
-            if (a.nblk_op < 0) return FEASTHIP_ERROR_INTERNAL;
-            a.phase = (it + k == 0) ? 0 : 1;
-            fh_prof_begin(h, "dot_finalize"); fh_launch_shift_fin(a, ld, h->stream); fh_prof_end(h);
-            fh_prof_begin(h, "shift_vec"); a.nblk_vec = fh_launch_shift_vec(a, ld, h->stream); fh_prof_end(h);
-        }
-        it += chunk;
-        ++tag;
-        fh_launch_publish_progress(a.tile_alive, ntiles, h->d_progress, tag, h->stream);
-        if ((rc = fh_iter_throttle(h, tag, t_loop0, N, nodes, &all_done))) return rc;
-    }
+    // iterate: the published count is the number of column tiles with a live column
+    const int it = fh_queue_chunks(h, a.tile_alive, ntiles, N, nodes, [&](int i) {
+        a.nblk_op = fh_apply_operator(h, ld, oc);
+        if (a.nblk_op < 0) return (int)FEASTHIP_ERROR_INTERNAL;
+        a.phase = i == 0 ? 0 : 1;
+        fh_prof_begin(h, "dot_finalize"); fh_launch_shift_fin(a, ld, h->stream); fh_prof_end(h);
+        fh_prof_begin(h, "shift_vec"); a.nblk_vec = fh_launch_shift_vec(a, ld, h->stream); fh_prof_end(h);
+        return 0;
+    }, &rc);
+    if (rc) return rc;
     if (it > 0) {
         a.phase = 2;                     // the stop test of the last step, on the true norm the last vector kernel left
         fh_launch_shift_fin(a, ld, h->stream);
     }
     FH_CHECK(hipStreamSynchronize(h->stream));
-
-    std::vector<int> iters(nl), status(nl), active(nl);
-    std::vector<double> rnorm(nl), r0(nl);
-    FH_CHECK(hipMemcpy(iters.data(), a.iters, nl * sizeof(int), hipMemcpyDeviceToHost));
-    FH_CHECK(hipMemcpy(status.data(), a.status, nl * sizeof(int), hipMemcpyDeviceToHost));
-    FH_CHECK(hipMemcpy(active.data(), a.active, nl * sizeof(int), hipMemcpyDeviceToHost));
-    FH_CHECK(hipMemcpy(rnorm.data(), a.rnorm, nl * sizeof(double), hipMemcpyDeviceToHost));
-    FH_CHECK(hipMemcpy(r0.data(), a.r0norm, nl * sizeof(double), hipMemcpyDeviceToHost));
     res.status.assign(nodes, 0);
-    for (int e = 0; e < nodes; ++e) {
-        int mx = 0, st = 0;
-        for (int c = 0; c < m; ++c) {
-            const int i = e * ld + c;
-            mx = std::max(mx, iters[i]);
-            res.col_iters.push_back(iters[i]);
-            if (active[i] || !std::isfinite(rnorm[i])) st = std::max(st, (int)FEASTHIP_ERROR_NO_CONVERGENCE);
-            else if (status[i] == 8 && !(rnorm[i] <= h->atol + h->rtol * r0[i])) st = std::max(st, (int)FEASTHIP_ERROR_NO_CONVERGENCE);
-            if (r0[i] > 0) res.max_rel_res = std::max(res.max_rel_res, rnorm[i] / r0[i]);
-        }
-        res.iters_sum += mx;
-        res.node_iters.push_back(mx);
-        res.max_iters = std::max(res.max_iters, mx);
-        res.status[e] = st;
-    }
+    if ((rc = fh_collect_columns(h, a.iters, a.status, a.active, a.rnorm, a.r0norm, nullptr, nodes, m, ld, 0, FH_FAIL_STOP_TEST, res)))
+        return rc;
     *seed_out = seed;
     FH_CHECK(hipMemcpy(seed_iters_out, a.passes, sizeof(int), hipMemcpyDeviceToHost));
     res.op_calls = *seed_iters_out;        // the products that ran (those queued behind the last live column return at once)
@@ -1182,11 +1211,8 @@ static int fh_gmres(feasthip_ctx* h, int ld, int m, int nodes_all, const std::ve
         ga.active = si; ga.iters = si + nl; ga.status = si + 2 * nl; ga.kdim = si + 3 * nl; ga.node_active = si + 4 * nl;
         FH_CHECK(hipMemsetAsync(sc, 0, hsz * sizeof(cplx), h->stream));
 
-        std::vector<cplx> ca(nl, cmake(-1, 0)), cb(nl);
-        for (int e = 0; e < nodes; ++e) for (int c = 0; c < ld; ++c) cb[(size_t)e * ld + c] = z[e0 + e];
         cplx *dca, *dcb;
-        if ((rc = fh_upload_coefs(h, "gm_coefA", ca, &dca))) return rc;
-        if ((rc = fh_upload_coefs(h, "gm_coefB", cb, &dcb))) return rc;
+        if ((rc = fh_upload_shift_coefs(h, "gm_coefA", "gm_coefB", z.data() + e0, nodes, ld, &dca, &dcb))) return rc;
         cplx* Xb = X + (size_t)e0 * stride;
         fh_op_call oc;
         oc.m = m; oc.uniform_coef = 1; oc.coefA = dca; oc.coefB = dcb; oc.nodes = nodes; oc.prec = 64;
@@ -1246,27 +1272,8 @@ static int fh_gmres(feasthip_ctx* h, int ld, int m, int nodes_all, const std::ve
             }
             fh_launch_gm_finish_cycle(ga, ld, Xb, stride, ksteps, nblk_vec, nodes, h->stream);   // x += V y
         }
-        // bookkeeping
-        std::vector<int> iters(nl), status(nl), active(nl);
-        std::vector<double> rnorm(nl), r0(nl), target(nl);
-        FH_CHECK(hipMemcpy(iters.data(), ga.iters, nl * sizeof(int), hipMemcpyDeviceToHost));
-        FH_CHECK(hipMemcpy(status.data(), ga.status, nl * sizeof(int), hipMemcpyDeviceToHost));
-        FH_CHECK(hipMemcpy(active.data(), ga.active, nl * sizeof(int), hipMemcpyDeviceToHost));
-        FH_CHECK(hipMemcpy(rnorm.data(), ga.rnorm, nl * sizeof(double), hipMemcpyDeviceToHost));
-        FH_CHECK(hipMemcpy(r0.data(), ga.r0norm, nl * sizeof(double), hipMemcpyDeviceToHost));
-        FH_CHECK(hipMemcpy(target.data(), ga.target, nl * sizeof(double), hipMemcpyDeviceToHost));
-        for (int e = 0; e < nodes; ++e) {
-            int mx = 0, stn = 0;
-            for (int c = 0; c < m; ++c) {
-                const size_t i = (size_t)e * ld + c;
-                mx = std::max(mx, iters[i]);
-                res.col_iters.push_back(iters[i]);
-                if (active[i] || !std::isfinite(rnorm[i]) || rnorm[i] > target[i]) stn = FEASTHIP_ERROR_NO_CONVERGENCE;
-                if (r0[i] > 0) res.max_rel_res = std::max(res.max_rel_res, rnorm[i] / r0[i]);
-            }
-            res.iters_sum += mx; res.node_iters.push_back(mx); res.max_iters = std::max(res.max_iters, mx);
-            res.status[e0 + e] = stn;
-        }
+        if ((rc = fh_collect_columns(h, ga.iters, ga.status, ga.active, ga.rnorm, ga.r0norm, ga.target, nodes, m, ld, e0, FH_FAIL_TARGET, res)))
+            return rc;
     }
     return 0;
 }
@@ -1284,7 +1291,7 @@ static bool fh_is_complex_input(feasthip_ctx* h) { return h->kind == 2 ? h->csr.
 // The residual is the fp64 dense operator kernel, so the result has fp64 accuracy as long as
 // cond(z_e B - A) * eps32 < 1.  `single`: one shift through fh_dense_lu_solve_single (nodes == 1).
 static int fh_dense_lu_refined(feasthip_ctx* h, int ld, int m, int nodes, const std::vector<cplx>& z, const cplx* Rhs, cplx* Y,
-                               size_t panel, std::vector<int>& status, int64_t* nfact, bool single, double* worst_out, bool banded = false) {
+                               size_t panel, std::vector<int>& status, int64_t* nfact, bool single, double* worst_out, bool banded) {
     const int N = (int)fh_N(h);
     int rc;
     void* p;
@@ -1308,12 +1315,9 @@ static int fh_dense_lu_refined(feasthip_ctx* h, int ld, int m, int nodes, const 
     cplx* part = (cplx*)p;
     if ((rc = fh_get_buf(h, "lr_dots", (size_t)(nodes + 1) * ld * sizeof(cplx), &p))) return rc;
     cplx* ddots = (cplx*)p;
-    const size_t nl = (size_t)nodes * ld;
-    std::vector<cplx> ca(nl, cmake(-1, 0)), cb(nl), mone(ld, cmake(-1, 0));
-    for (int e = 0; e < nodes; ++e) for (int c = 0; c < ld; ++c) cb[(size_t)e * ld + c] = z[e];
+    const std::vector<cplx> mone(ld, cmake(-1, 0));
     cplx *dca, *dcb, *dmone;
-    if ((rc = fh_upload_coefs(h, "lr_coefA", ca, &dca))) return rc;
-    if ((rc = fh_upload_coefs(h, "lr_coefB", cb, &dcb))) return rc;
+    if ((rc = fh_upload_shift_coefs(h, "lr_coefA", "lr_coefB", z.data(), nodes, ld, &dca, &dcb))) return rc;
     if ((rc = fh_upload_coefs(h, "lr_mone", mone, &dmone))) return rc;
     std::vector<cplx> dots((size_t)(nodes + 1) * ld);
     fh_launch_dot_cols(Rhs, Rhs, N, ld, part, ddots + (size_t)nodes * ld, h->stream);
@@ -1389,6 +1393,180 @@ static int fh_split_nodes(feasthip_ctx* h, std::vector<int>& order, int* nd) {
     return 0;
 }
 
+// What the solver branches of one panel sweep share.  The panels of Y, and z / w with them, are ordered Krylov nodes first,
+// then the direct ones, both in ascending node order (order[i] = local node of panel i).
+struct fh_panel_sweep {
+    int m, ld, N, nodes, nk, nd;
+    size_t panel;
+    cplx *Qp, *Rhs, *Y;
+    std::vector<int> order;
+    std::vector<cplx> z, w;
+    const double* ritz_lambda; const fh_panel_io* io;
+    cplx* sum_acc = nullptr;
+    bool sum_shared = false;          // sum mode started from one shared residual panel: no per-node solution panels exist
+};
+
+// Dense LU or sparse direct solves of every node (the two differ in the solver called only); factor_precision 32 refines
+// complex64 factors.  Y_e = S_e^-1 Rhs, sr.status per node, sr.max_rel_res the worst refined residual.
+static int fh_panel_direct(feasthip_ctx* h, const fh_panel_sweep& g, int64_t* nfact, fh_solve_result& sr) {
+    const bool banded = h->solver == FEASTHIP_SOLVER_BANDED;
+    if (!banded && h->kind != 1) { h->last_error = "solver LU requires a dense matrix (sparse direct factorisation is not provided; use BICGSTAB)"; return FEASTHIP_ERROR_FPM; }
+    sr.status.assign(g.nodes, 0);
+    if (h->factor_precision == 32)
+        return fh_dense_lu_refined(h, g.ld, g.m, g.nodes, g.z, g.Rhs, g.Y, g.panel, sr.status, nfact, false, &sr.max_rel_res, banded);
+    if (banded) return fh_banded_solve_nodes(h, g.ld, g.m, g.nodes, g.z, g.Rhs, 0, g.Y, g.panel, sr.status, nfact);
+    return fh_dense_lu_solve_nodes(h, g.ld, g.m, g.nodes, g.z, g.Rhs, 0, g.Y, g.panel, sr.status, nfact);
+}
+
+// Shared start (sum mode, fp64 panels): the warm start Y0_e = q_c/(z_e - lambda_c) has the residual
+// (A q_c - lambda_c B q_c)/(z_e - lambda_c) -- ONE eigen-residual panel serves every node -- and its weighted
+// sum over the nodes is q_c * sum_e w_e/(z_e - lambda_c): neither the warm-start panels nor their residual
+// products are ever formed.  Zero guess: the residual is RHS for every node.  *src: that one panel.
+static int fh_shared_start_source(feasthip_ctx* h, const fh_panel_sweep& g, const cplx** src) {
+    if (!g.ritz_lambda) { *src = g.Rhs; return 0; }
+    if (g.io && g.io->eigres) { *src = g.io->eigres; return 0; }      // left behind by the Ritz step of the previous loop
+    std::vector<cplx> ca(g.ld, cmake(1, 0)), cb(g.ld, cmake(0, 0));
+    for (int c = 0; c < g.m; ++c) cb[c] = cmake(-g.ritz_lambda[c], 0);
+    cplx *dca, *dcb;
+    void* p; int rc;
+    if ((rc = fh_upload_coefs(h, "ca_rcoefA", ca, &dca))) return rc;
+    if ((rc = fh_upload_coefs(h, "ca_rcoefB", cb, &dcb))) return rc;
+    if ((rc = fh_get_buf(h, "ca_eigres", g.panel * sizeof(cplx), &p))) return rc;
+    fh_op_call oc;
+    oc.m = g.m;
+    oc.X = g.Qp; oc.Y = p; oc.coefA = dca; oc.coefB = dcb;
+    fh_apply_operator(h, g.ld, oc);                    // A q - lambda B q (B = I handled by the operator kernel)
+    *src = (const cplx*)p;
+    return 0;
+}
+
+// COCG / BiCGStab: the direct nodes' solves into their own panels, the initial guess (or the shared start of sum mode), the
+// shifted or the per-node sweep over the Krylov nodes.  sr comes back in local node order.
+static int fh_panel_krylov(feasthip_ctx* h, fh_panel_sweep& g, bool want_moments, int64_t* nfact, fh_solve_result& sr) {
+    const int m = g.m, ld = g.ld, nodes = g.nodes, nk = g.nk, nd = g.nd;
+    const size_t panel = g.panel;
+    int rc;
+    if (h->solver == FEASTHIP_SOLVER_COCG && fh_is_complex_input(h)) {
+        h->last_error = "solver COCG needs a complex-SYMMETRIC shifted matrix: real-symmetric A and B only";
+        return FEASTHIP_ERROR_FPM;
+    }
+    const std::vector<cplx> zk(g.z.begin(), g.z.begin() + nk), wk(g.w.begin(), g.w.begin() + nk), zd(g.z.begin() + nk, g.z.end());
+    // direct nodes first, on the same stream: sparse direct solves of the shared right-hand side into their own panels
+    // (no warm start, no column mask, as the LU path); the factors live in the band / multifrontal cache, matched by z
+    std::vector<int> status_d;
+    if (nd && (rc = fh_banded_solve_subset(h, ld, m, zd, g.Rhs, g.Y + (size_t)nk * panel, panel, status_d, nfact))) return rc;
+    fh_krylov_opts opt;
+    cplx* dz = nullptr; double* dlam = nullptr;
+    if (nk && (rc = fh_upload_coefs(h, "ca_z", zk, &dz))) return rc;
+    if ((rc = fh_upload_ritz_lambda(h, g.ritz_lambda, m, ld, &dlam))) return rc;
+    // sum mode: only Q_proj is wanted (no moments), so the per-node solutions are never formed
+    if (h->solver == FEASTHIP_SOLVER_COCG && !want_moments && h->sum_mode) {
+        if ((rc = fh_get_buf(h, "ca_acc", panel * sizeof(cplx), (void**)&g.sum_acc))) return rc;
+        FH_CHECK(hipMemsetAsync(g.sum_acc, 0, panel * sizeof(cplx), h->stream));
+    }
+    g.sum_shared = g.sum_acc && h->factor_precision == 64 && !getenv("FH_NO_SHARED_START");
+    if (g.sum_shared) {
+        if ((rc = fh_shared_start_source(h, g, &opt.shared_src))) return rc;
+    } else if (nk) {
+        fh_vec_args va;
+        memset(&va, 0, sizeof(va));
+        va.N = g.N; va.node_stride = panel; va.X = g.Y; va.Q = g.Qp; va.lambda = dlam; va.znode = dz;
+        fh_launch_init_guess(va, ld, fh_vec_nblk(g.N, ld), nk, h->stream);
+    }
+    // Shifted COCG (feasthip_set_solver kind SHIFTED_COCG): a CSR operator with real values and B = I, fp64 panels, sum mode
+    // from a shared start, no direct nodes.  Anything else is the per-node sweep.
+    const bool shifted = h->shifted && g.sum_shared && opt.shared_src && nk && !nd && h->kind == 2 && h->csr.b_identity &&
+                         !h->csr.is_complex;
+    h->shift_panels += 1;
+    if (shifted) {
+        int seed = 0, seed_its = 0;
+        if ((rc = fh_shifted_cocg(h, ld, m, nk, zk, sr, g.sum_acc, wk, opt.shared_src, g.ritz_lambda, &seed, &seed_its))) return rc;
+        h->shift_used += 1; h->shift_seed = h->node_ids[g.order[seed]]; h->shift_seed_iters += seed_its;
+    } else if (nk) {
+        opt.sum_acc = g.sum_acc; opt.wnode = &wk; opt.shared_lambda = dlam; opt.dznode = dz; opt.shared_lambda_host = g.ritz_lambda;
+        rc = fh_krylov(h, h->solver == FEASTHIP_SOLVER_COCG ? 1 : 0, h->factor_precision, ld, m, nk, zk, g.Rhs, g.Y, panel, sr, opt);
+        if (rc) return rc;
+    }
+    if (!nd) return 0;
+    // back to local node order; a direct node reports 0 iterations
+    std::vector<int> status(nodes, 0), node_iters(nodes, 0), col_iters((size_t)nodes * m, 0);
+    for (int i = 0; i < nk; ++i) {
+        const int e = g.order[i];
+        status[e] = sr.status[i];
+        node_iters[e] = sr.node_iters[i];
+        std::copy_n(sr.col_iters.begin() + (size_t)i * m, m, col_iters.begin() + (size_t)e * m);
+    }
+    for (int d = 0; d < nd; ++d) status[g.order[nk + d]] = status_d[d];
+    sr.status = status; sr.node_iters = node_iters; sr.col_iters = col_iters;
+    return 0;
+}
+
+// GMRES: zero initial guess like Krylov.jl (or the Ritz warm start when given), then the restarted cycles over every node
+static int fh_panel_gmres(feasthip_ctx* h, const fh_panel_sweep& g, fh_solve_result& sr) {
+    int rc;
+    cplx* dz; double* dlam;
+    if ((rc = fh_upload_coefs(h, "ca_z", g.z, &dz))) return rc;
+    if ((rc = fh_upload_ritz_lambda(h, g.ritz_lambda, g.m, g.ld, &dlam))) return rc;
+    fh_vec_args va;
+    memset(&va, 0, sizeof(va));
+    va.N = g.N; va.node_stride = g.panel; va.X = g.Y; va.Q = g.Qp; va.lambda = dlam; va.znode = dz; va.prec = 64;
+    fh_launch_init_guess(va, g.ld, fh_vec_nblk(g.N, g.ld), g.nodes, h->stream);
+    return fh_gmres(h, g.ld, g.m, g.nodes, g.z, g.Rhs, g.Y, g.panel, sr);
+}
+
+// What an iterative sweep leaves in the handle (feasthip_last_node_iterations / _column_iterations) and in the stats
+static void fh_store_sweep_result(feasthip_ctx* h, const fh_solve_result& sr, int m, feasthip_stats* stats) {
+    h->last_node_iters = sr.node_iters; h->last_col_iters = sr.col_iters; h->last_col_m = m;
+    if (stats) { stats->krylov_iterations = sr.iters_sum; stats->spmm_calls = sr.op_calls; stats->max_rel_residual = sr.max_rel_res; }
+}
+
+// Moments (variant B): zAq += w_e Q^H Y_e ; zSq += w_e z_e Q^H Y_e, one Gram product per node (and per row block of a wide
+// sweep, whose block columns go to mom's host accumulators); the sums of a one-panel sweep are uploaded to dzAq / dzSq.
+static int fh_panel_moments(feasthip_ctx* h, const fh_panel_sweep& g, cplx* dzAq, cplx* dzSq, const fh_moment_ctx* mom) {
+    const int m = g.m, ld = g.ld, N = g.N;
+    int rc;
+    void* p;
+    if ((rc = fh_get_buf(h, "gram_work", fh_gram_work_elems(ld) * sizeof(cplx), &p))) return rc;
+    cplx* gw = (cplx*)p;
+    if ((rc = fh_get_buf(h, "gram_G", (size_t)ld * ld * sizeof(cplx), &p))) return rc;
+    cplx* G = (cplx*)p;
+    const int m_all = mom ? mom->m_all : m, col0 = mom ? mom->col0 : 0;
+    std::vector<cplx> Gh((size_t)ld * ld), aq_local, sq_local;
+    if (!mom) { aq_local.assign((size_t)m * m, cmake(0, 0)); sq_local.assign((size_t)m * m, cmake(0, 0)); }
+    std::vector<cplx>& aq = mom ? *mom->aq : aq_local;
+    std::vector<cplx>& sq = mom ? *mom->sq : sq_local;
+    cplx* Qrow = g.Qp;                     // row block of Q in panel layout (the panel's own columns when not wide)
+    if (mom && (rc = fh_get_buf(h, "ca_Qrow", g.panel * sizeof(cplx), &p))) return rc;
+    if (mom) Qrow = (cplx*)p;
+    for (int r0 = 0; r0 < m_all; r0 += ld) {
+        const int mr_ = std::min(ld, m_all - r0);
+        if (mom) fh_launch_to_panel(mom->dQ_all + (size_t)r0 * N, N, N, mr_, Qrow, ld, h->stream, fh_perm(h));
+        for (int e = 0; e < g.nodes; ++e) {
+            fh_prof_begin(h, "gram");
+            fh_launch_gram(Qrow, g.Y + (size_t)e * g.panel, N, ld, 0, gw, G, h->stream);
+            fh_prof_end(h);
+            FH_CHECK(hipMemcpyAsync(Gh.data(), G, Gh.size() * sizeof(cplx), hipMemcpyDeviceToHost, h->stream));
+            FH_CHECK(hipStreamSynchronize(h->stream));
+            cplx wz = cmul(g.w[e], g.z[e]);
+            for (int c2 = 0; c2 < m; ++c2)
+                for (int c1 = 0; c1 < mr_; ++c1) {
+                    cplx gv = Gh[(size_t)c2 * ld + c1];
+                    cfma(aq[(size_t)(col0 + c2) * m_all + r0 + c1], g.w[e], gv);
+                    cfma(sq[(size_t)(col0 + c2) * m_all + r0 + c1], wz, gv);
+                }
+        }
+        if (!mom) break;
+    }
+    if (!mom) {
+        if (h->real_projection) for (size_t i = 0; i < aq.size(); ++i) { aq[i].y = 0.0; sq[i].y = 0.0; }
+        if (dzAq) FH_CHECK(hipMemcpyAsync(dzAq, aq.data(), aq.size() * sizeof(cplx), hipMemcpyHostToDevice, h->stream));
+        if (dzSq) FH_CHECK(hipMemcpyAsync(dzSq, sq.data(), sq.size() * sizeof(cplx), hipMemcpyHostToDevice, h->stream));
+    }
+    return 0;
+}
+
+// One panel (m <= 64) of the sweep, in phases: import Q, rhs = B Q, split the nodes, solve, sum the weighted solutions
+// into Q_proj, moments, one synchronisation.
 static int fh_contour_apply_panel(feasthip_ctx* h, int64_t m64, const cplx* dQ, const double* ritz_lambda,
                                   cplx* dQproj, cplx* dzAq, cplx* dzSq, int* node_status, feasthip_stats* stats,
                                   const fh_moment_ctx* mom = nullptr, const fh_panel_io* io = nullptr) {
@@ -1397,17 +1575,18 @@ static int fh_contour_apply_panel(feasthip_ctx* h, int64_t m64, const cplx* dQ, 
     if (h->zne.empty()) { h->last_error = "no contour set"; return FEASTHIP_ERROR_FPM; }
     auto t0 = std::chrono::steady_clock::now();
     FH_CHECK(hipSetDevice(h->device));
-    const int m = (int)m64, ld = fh_pick_ld(m), N = (int)fh_N(h);
-    const int nodes = h->node_count;
-    const size_t panel = (size_t)N * ld;
+    fh_panel_sweep g;
+    const int m = g.m = (int)m64, ld = g.ld = fh_pick_ld(m), N = g.N = (int)fh_N(h);
+    const int nodes = g.nodes = h->node_count;
+    const size_t panel = g.panel = (size_t)N * ld;
+    g.ritz_lambda = ritz_lambda; g.io = io;
     void* p;
-    cplx* Qp = nullptr;
     if (io && io->Qp) {
-        Qp = const_cast<cplx*>(io->Qp);          // read only below (the right-hand side when B = I)
+        g.Qp = const_cast<cplx*>(io->Qp);        // read only below (the right-hand side when B = I)
     } else {
         if ((rc = fh_get_buf(h, "ca_Qp", panel * sizeof(cplx), &p))) return rc;
-        Qp = (cplx*)p;
-        fh_launch_to_panel(dQ, N, N, m, Qp, ld, h->stream, fh_perm(h));
+        g.Qp = (cplx*)p;
+        fh_launch_to_panel(dQ, N, N, m, g.Qp, ld, h->stream, fh_perm(h));
     }
     cplx* Outp = io ? io->out : nullptr;
     if (!Outp) {
@@ -1425,195 +1604,61 @@ static int fh_contour_apply_panel(feasthip_ctx* h, int64_t m64, const cplx* dQ, 
     }
     // rhs = B Q  (hoisted out of the node loop; the reference recomputes it per node,
     // src/dense/feast_dense.jl:184 -- it is loop invariant)
-    cplx* Rhs = Qp;
+    g.Rhs = g.Qp;
     if (!fh_b_identity(h)) {
         if ((rc = fh_get_buf(h, "ca_rhs", panel * sizeof(cplx), &p))) return rc;
-        Rhs = (cplx*)p;
+        g.Rhs = (cplx*)p;
         std::vector<cplx> ca(ld, cmake(0, 0)), cb(ld, cmake(1, 0));
         cplx *dca, *dcb;
         if ((rc = fh_upload_coefs(h, "ca_coefA", ca, &dca))) return rc;
         if ((rc = fh_upload_coefs(h, "ca_coefB", cb, &dcb))) return rc;
         fh_op_call oc;
         oc.m = m;
-        oc.X = Qp; oc.Y = Rhs; oc.coefA = dca; oc.coefB = dcb;
+        oc.X = g.Qp; oc.Y = g.Rhs; oc.coefA = dca; oc.coefB = dcb;
         fh_apply_operator(h, ld, oc);
     }
-    // Per-node solver (feasthip_set_node_solver): the local nodes split into a Krylov set K and a direct set D.  The panels
-    // of Y, and z / w with them, are ordered K first, then D, both in ascending node order (order[i] = local node of panel
-    // i); with no direct node this is the identity and nothing below differs from the one-solver sweep.
-    std::vector<int> order;
-    int nd = 0;
-    if ((rc = fh_split_nodes(h, order, &nd))) return rc;
-    const int nk = nodes - nd;
-    std::vector<cplx> z(nodes), w(nodes);
+    // Per-node solver (feasthip_set_node_solver): the local nodes split into a Krylov set and a direct set; with no direct
+    // node the order is the identity and nothing below differs from the one-solver sweep.
+    if ((rc = fh_split_nodes(h, g.order, &g.nd))) return rc;
+    const int nd = g.nd, nk = g.nk = nodes - nd;
+    std::vector<cplx>& z = g.z;
+    std::vector<cplx>& w = g.w;
+    z.resize(nodes); w.resize(nodes);
     for (int i = 0; i < nodes; ++i) {
-        z[i] = h->zne[h->node_ids[order[i]]];
-        w[i] = cscale(h->wne[h->node_ids[order[i]]], h->weight_scale);
+        z[i] = h->zne[h->node_ids[g.order[i]]];
+        w[i] = cscale(h->wne[h->node_ids[g.order[i]]], h->weight_scale);
     }
-    const std::vector<cplx> zk(z.begin(), z.begin() + nk), wk(w.begin(), w.begin() + nk), zd(z.begin() + nk, z.end());
     if ((rc = fh_get_buf(h, "ca_Y", (size_t)nodes * panel * sizeof(cplx), &p))) return rc;
-    cplx* Y = (cplx*)p;
-    std::vector<int> status(nodes, 0);
-    cplx* sum_acc = nullptr;
-    bool sum_shared = false;          // sum mode started from one shared residual panel: no per-node solution panels exist
+    cplx* Y = g.Y = (cplx*)p;
 
     // destroyed on every return path (the solver branches below return early on errors)
     struct ev_guard { hipEvent_t a = nullptr, b = nullptr; ~ev_guard() { if (a) hipEventDestroy(a); if (b) hipEventDestroy(b); } } evg;
     FH_CHECK(hipEventCreate(&evg.a)); FH_CHECK(hipEventCreate(&evg.b));
     const hipEvent_t ev0 = evg.a, ev1 = evg.b;
     FH_CHECK(hipEventRecord(ev0, h->stream));
-    if (h->solver == FEASTHIP_SOLVER_LU) {
-        if (h->kind != 1) { h->last_error = "solver LU requires a dense matrix (sparse direct factorisation is not provided; use BICGSTAB)"; return FEASTHIP_ERROR_FPM; }
-        int64_t nfact = 0;
-        double worst = 0.0;
-        if (h->factor_precision == 32) rc = fh_dense_lu_refined(h, ld, m, nodes, z, Rhs, Y, panel, status, &nfact, false, &worst);
-        else rc = fh_dense_lu_solve_nodes(h, ld, m, nodes, z, Rhs, 0, Y, panel, status, &nfact);
-        if (rc) return rc;
-        if (stats) { stats->factorizations = nfact; stats->max_rel_residual = worst; }
-    } else if (h->solver == FEASTHIP_SOLVER_BANDED) {
-        int64_t nfact = 0;
-        double worst = 0.0;
-        if (h->factor_precision == 32) rc = fh_dense_lu_refined(h, ld, m, nodes, z, Rhs, Y, panel, status, &nfact, false, &worst, true);
-        else rc = fh_banded_solve_nodes(h, ld, m, nodes, z, Rhs, 0, Y, panel, status, &nfact);
-        if (rc) return rc;
-        if (stats) { stats->factorizations = nfact; stats->max_rel_residual = worst; }
-    } else if (h->solver == FEASTHIP_SOLVER_BICGSTAB || h->solver == FEASTHIP_SOLVER_COCG) {
-        if (h->solver == FEASTHIP_SOLVER_COCG && fh_is_complex_input(h)) {
-            h->last_error = "solver COCG needs a complex-SYMMETRIC shifted matrix: real-symmetric A and B only";
-            return FEASTHIP_ERROR_FPM;
-        }
-        // direct nodes first, on the same stream: sparse direct solves of the shared right-hand side into their own panels
-        // (no warm start, no column mask, as the LU path); the factors live in the band / multifrontal cache, matched by z
-        int64_t nfact = 0;
-        std::vector<int> status_d;
-        if (nd && (rc = fh_banded_solve_subset(h, ld, m, zd, Rhs, Y + (size_t)nk * panel, panel, status_d, &nfact))) return rc;
-        // initial guess
-        cplx* dz = nullptr;
-        if (nk && (rc = fh_upload_coefs(h, "ca_z", zk, &dz))) return rc;
-        double* dlam = nullptr;
-        if (ritz_lambda) {
-            std::vector<double> lam(ld, 0.0);
-            for (int c = 0; c < m; ++c) lam[c] = ritz_lambda[c];
-            if ((rc = fh_get_buf(h, "ca_lam", ld * sizeof(double), &p))) return rc;
-            dlam = (double*)p;
-            FH_CHECK(hipMemcpy(dlam, lam.data(), ld * sizeof(double), hipMemcpyHostToDevice));
-        }
-        fh_solve_result sr;
-        // sum mode: only Q_proj is wanted (no moments), so the per-node solutions are never formed
-        if (h->solver == FEASTHIP_SOLVER_COCG && !dzAq && !dzSq && !mom && h->sum_mode) {
-            if ((rc = fh_get_buf(h, "ca_acc", panel * sizeof(cplx), &p))) return rc;
-            sum_acc = (cplx*)p;
-            FH_CHECK(hipMemsetAsync(sum_acc, 0, panel * sizeof(cplx), h->stream));
-        }
-        // Shared start (sum mode, fp64 panels): the warm start Y0_e = q_c/(z_e - lambda_c) has the residual
-        // (A q_c - lambda_c B q_c)/(z_e - lambda_c) -- ONE eigen-residual panel serves every node -- and its weighted
-        // sum over the nodes is q_c * sum_e w_e/(z_e - lambda_c): neither the warm-start panels nor their residual
-        // products are ever formed.  Zero guess: the residual is RHS for every node.
-        const cplx* shared_src = nullptr;
-        sum_shared = sum_acc && h->factor_precision == 64 && !getenv("FH_NO_SHARED_START");
-        if (sum_shared) {
-            if (ritz_lambda && io && io->eigres) {
-                shared_src = io->eigres;                         // left behind by the Ritz step of the previous loop
-            } else if (ritz_lambda) {
-                std::vector<cplx> ca(ld, cmake(1, 0)), cb(ld, cmake(0, 0));
-                for (int c = 0; c < m; ++c) cb[c] = cmake(-ritz_lambda[c], 0);
-                cplx *dca, *dcb;
-                if ((rc = fh_upload_coefs(h, "ca_rcoefA", ca, &dca))) return rc;
-                if ((rc = fh_upload_coefs(h, "ca_rcoefB", cb, &dcb))) return rc;
-                if ((rc = fh_get_buf(h, "ca_eigres", panel * sizeof(cplx), &p))) return rc;
-                fh_op_call oc;
-                oc.m = m;
-                oc.X = Qp; oc.Y = p; oc.coefA = dca; oc.coefB = dcb;
-                fh_apply_operator(h, ld, oc);                    // A q - lambda B q (B = I handled by the operator kernel)
-                shared_src = (const cplx*)p;
-            } else {
-                shared_src = Rhs;
-            }
-        } else if (nk) {
-            fh_vec_args va;
-            memset(&va, 0, sizeof(va));
-            va.N = N; va.node_stride = panel; va.X = Y; va.Q = Qp; va.lambda = dlam; va.znode = dz;
-            fh_launch_init_guess(va, ld, fh_vec_nblk(N, ld), nk, h->stream);
-        }
-        // Shifted COCG (feasthip_set_solver kind SHIFTED_COCG): a CSR operator with real values and B = I, fp64 panels, sum mode
-        // from a shared start, no direct nodes.  Anything else is the per-node sweep below.
-        const bool shifted = h->shifted && sum_shared && shared_src && nk && !nd && h->kind == 2 && h->csr.b_identity &&
-                             !h->csr.is_complex;
-        h->shift_panels += 1;
-        if (shifted) {
-            int seed = 0, seed_its = 0;
-            if ((rc = fh_shifted_cocg(h, ld, m, nk, zk, sr, sum_acc, wk, shared_src, ritz_lambda, &seed, &seed_its))) return rc;
-            h->shift_used += 1; h->shift_seed = h->node_ids[order[seed]]; h->shift_seed_iters += seed_its;
-        } else if (nk) {
-            rc = fh_krylov(h, h->solver == FEASTHIP_SOLVER_COCG ? 1 : 0, h->factor_precision, ld, m, nk, zk, Rhs, Y, panel, sr,
-                           sum_acc, &wk, shared_src, dlam, dz, ritz_lambda);
-            if (rc) return rc;
-        }
-        if (!nd) {
-            status = sr.status;
-            h->last_node_iters = sr.node_iters;
-            h->last_col_iters = sr.col_iters;
-        } else {
-            // back to local node order; a direct node reports 0 iterations
-            h->last_node_iters.assign(nodes, 0);
-            h->last_col_iters.assign((size_t)nodes * m, 0);
-            for (int i = 0; i < nk; ++i) {
-                const int e = order[i];
-                if (i < (int)sr.status.size()) status[e] = sr.status[i];
-                if (i < (int)sr.node_iters.size()) h->last_node_iters[e] = sr.node_iters[i];
-                for (int c = 0; c < m && (size_t)i * m + c < sr.col_iters.size(); ++c)
-                    h->last_col_iters[(size_t)e * m + c] = sr.col_iters[(size_t)i * m + c];
-            }
-            for (int d = 0; d < nd; ++d) status[order[nk + d]] = status_d[d];
-        }
-        h->last_col_m = m;
-        if (stats) {
-            stats->krylov_iterations = sr.iters_sum;
-            stats->spmm_calls = sr.op_calls;
-            stats->max_rel_residual = sr.max_rel_res;
-            stats->factorizations = nfact;
-        }
-    } else {
-        // GMRES: zero initial guess like Krylov.jl (or the Ritz warm start when given)
-        cplx* dz;
-        if ((rc = fh_upload_coefs(h, "ca_z", z, &dz))) return rc;
-        double* dlam = nullptr;
-        if (ritz_lambda) {
-            std::vector<double> lam(ld, 0.0);
-            for (int c = 0; c < m; ++c) lam[c] = ritz_lambda[c];
-            if ((rc = fh_get_buf(h, "ca_lam", ld * sizeof(double), &p))) return rc;
-            dlam = (double*)p;
-            FH_CHECK(hipMemcpy(dlam, lam.data(), ld * sizeof(double), hipMemcpyHostToDevice));
-        }
-        fh_vec_args va;
-        memset(&va, 0, sizeof(va));
-        va.N = N; va.node_stride = panel; va.X = Y; va.Q = Qp; va.lambda = dlam; va.znode = dz; va.prec = 64;
-        fh_launch_init_guess(va, ld, fh_vec_nblk(N, ld), nodes, h->stream);
-        fh_solve_result sr;
-        rc = fh_gmres(h, ld, m, nodes, z, Rhs, Y, panel, sr);
-        if (rc) return rc;
-        status = sr.status;
-        h->last_node_iters = sr.node_iters;
-        h->last_col_iters = sr.col_iters;
-        h->last_col_m = m;
-        if (stats) {
-            stats->krylov_iterations = sr.iters_sum;
-            stats->spmm_calls = sr.op_calls;
-            stats->max_rel_residual = sr.max_rel_res;
-        }
-    }
+    // solve: Y_e = (z_e B - A)^-1 rhs for every local node (sum mode: their weighted sum only, in g.sum_acc)
+    const bool direct = h->solver == FEASTHIP_SOLVER_LU || h->solver == FEASTHIP_SOLVER_BANDED;
+    int64_t nfact = 0;
+    fh_solve_result sr;
+    if (direct) rc = fh_panel_direct(h, g, &nfact, sr);
+    else if (h->solver == FEASTHIP_SOLVER_BICGSTAB || h->solver == FEASTHIP_SOLVER_COCG) rc = fh_panel_krylov(h, g, dzAq || dzSq || mom, &nfact, sr);
+    else rc = fh_panel_gmres(h, g, sr);
+    if (rc) return rc;
+    if (!direct) fh_store_sweep_result(h, sr, m, stats);
+    else if (stats) stats->max_rel_residual = sr.max_rel_res;
+    if (stats) stats->factorizations = nfact;
     FH_CHECK(hipEventRecord(ev1, h->stream));
 
     // Q_proj = sum_e (scale*w_e) Y_e
     cplx* dw;
     if ((rc = fh_upload_coefs(h, "ca_w", w, &dw))) return rc;
     cplx* dwd = nullptr;
-    if (sum_shared && nd) {
+    if (g.sum_shared && nd) {
         const std::vector<cplx> wd(w.begin() + nk, w.end());
         if ((rc = fh_upload_coefs(h, "ca_wd", wd, &dwd))) return rc;
     }
     fh_prof_begin(h, dwd ? "node_finish" : "accumulate");
-    if (sum_shared) {
+    if (g.sum_shared) {
         cplx* drho = nullptr;
         if (ritz_lambda) {
             // the closed-form sum of the warm starts runs over the Krylov nodes only
@@ -1622,57 +1667,16 @@ static int fh_contour_apply_panel(feasthip_ctx* h, int64_t m64, const cplx* dQ, 
                 for (int e = 0; e < nk; ++e) rho[c] = cadd(rho[c], cdiv(w[e], cmake(z[e].x - ritz_lambda[c], z[e].y)));
             if ((rc = fh_upload_coefs(h, "ca_rho", rho, &drho))) return rc;
         }
-        if (dwd) fh_launch_node_finish(Qp, drho, sum_acc, Y + (size_t)nk * panel, panel, dwd, nd, Outp, N, ld, h->real_projection, h->stream);
-        else fh_launch_sum_finish(Qp, drho, sum_acc, Outp, N, ld, h->real_projection, h->stream);
+        if (dwd) fh_launch_node_finish(g.Qp, drho, g.sum_acc, Y + (size_t)nk * panel, panel, dwd, nd, Outp, N, ld, h->real_projection, h->stream);
+        else fh_launch_sum_finish(g.Qp, drho, g.sum_acc, Outp, N, ld, h->real_projection, h->stream);
     } else {
-        fh_launch_accumulate(Y, panel, dw, nodes, N, ld, sum_acc, Outp, h->real_projection, h->stream);
+        fh_launch_accumulate(Y, panel, dw, nodes, N, ld, g.sum_acc, Outp, h->real_projection, h->stream);
     }
     fh_prof_end(h);
     if (dQproj) fh_launch_from_panel(Outp, ld, N, m, dQproj, N, h->stream, fh_perm(h));
-
-    // optional moments (variant B): zAq += w_e Q^H Y_e ; zSq += w_e z_e Q^H Y_e
-    if (dzAq || dzSq || mom) {
-        if ((rc = fh_get_buf(h, "gram_work", fh_gram_work_elems(ld) * sizeof(cplx), &p))) return rc;
-        cplx* gw = (cplx*)p;
-        if ((rc = fh_get_buf(h, "gram_G", (size_t)ld * ld * sizeof(cplx), &p))) return rc;
-        cplx* G = (cplx*)p;
-        const int m_all = mom ? mom->m_all : m, col0 = mom ? mom->col0 : 0;
-        std::vector<cplx> Gh((size_t)ld * ld), aq_local, sq_local;
-        if (!mom) { aq_local.assign((size_t)m * m, cmake(0, 0)); sq_local.assign((size_t)m * m, cmake(0, 0)); }
-        std::vector<cplx>& aq = mom ? *mom->aq : aq_local;
-        std::vector<cplx>& sq = mom ? *mom->sq : sq_local;
-        cplx* Qrow = Qp;                       // row block of Q in panel layout (the panel's own columns when not wide)
-        if (mom && (rc = fh_get_buf(h, "ca_Qrow", panel * sizeof(cplx), &p))) return rc;
-        if (mom) Qrow = (cplx*)p;
-        for (int r0 = 0; r0 < m_all; r0 += ld) {
-            const int mr_ = std::min(ld, m_all - r0);
-            if (mom) {
-                fh_launch_to_panel(mom->dQ_all + (size_t)r0 * N, N, N, mr_, Qrow, ld, h->stream, fh_perm(h));
-            }
-            for (int e = 0; e < nodes; ++e) {
-                fh_prof_begin(h, "gram");
-                fh_launch_gram(Qrow, Y + (size_t)e * panel, N, ld, 0, gw, G, h->stream);
-                fh_prof_end(h);
-                FH_CHECK(hipMemcpyAsync(Gh.data(), G, Gh.size() * sizeof(cplx), hipMemcpyDeviceToHost, h->stream));
-                FH_CHECK(hipStreamSynchronize(h->stream));
-                cplx wz = cmul(w[e], z[e]);
-                for (int c2 = 0; c2 < m; ++c2)
-                    for (int c1 = 0; c1 < mr_; ++c1) {
-                        cplx g = Gh[(size_t)c2 * ld + c1];
-                        cfma(aq[(size_t)(col0 + c2) * m_all + r0 + c1], w[e], g);
-                        cfma(sq[(size_t)(col0 + c2) * m_all + r0 + c1], wz, g);
-                    }
-            }
-            if (!mom) break;
-        }
-        if (!mom) {
-            if (h->real_projection) for (size_t i = 0; i < aq.size(); ++i) { aq[i].y = 0.0; sq[i].y = 0.0; }
-            if (dzAq) FH_CHECK(hipMemcpyAsync(dzAq, aq.data(), aq.size() * sizeof(cplx), hipMemcpyHostToDevice, h->stream));
-            if (dzSq) FH_CHECK(hipMemcpyAsync(dzSq, sq.data(), sq.size() * sizeof(cplx), hipMemcpyHostToDevice, h->stream));
-        }
-    }
+    if ((dzAq || dzSq || mom) && (rc = fh_panel_moments(h, g, dzAq, dzSq, mom))) return rc;
     FH_CHECK(hipStreamSynchronize(h->stream));
-    if (node_status) for (int e = 0; e < nodes; ++e) node_status[e] = status[e];
+    if (node_status) for (int e = 0; e < nodes; ++e) node_status[e] = sr.status[e];
     if (stats) {
         float ms = 0.f;
         hipEventElapsedTime(&ms, ev0, ev1);
@@ -1683,6 +1687,19 @@ static int fh_contour_apply_panel(feasthip_ctx* h, int64_t m64, const cplx* dQ, 
     FH_CHECK(hipGetLastError());       // launch-configuration errors do not surface through the stream sync
     return 0;
 }
+
+// While it lives, the handle's column mask is its slice [c0, c1) (columns past the mask's end count as set); the
+// destructor puts the whole mask back, on every return path.
+struct fh_mask_slice {
+    feasthip_ctx* h;
+    const std::vector<int> whole;
+    fh_mask_slice(feasthip_ctx* h_, int64_t c0, int64_t c1) : h(h_), whole(h_->col_mask) {
+        if (whole.empty()) return;
+        h->col_mask.clear();
+        for (int64_t c = c0; c < c1; ++c) h->col_mask.push_back(c < (int64_t)whole.size() ? whole[c] : 1);
+    }
+    ~fh_mask_slice() { h->col_mask = whole; }
+};
 
 // m > 64: the columns of Q are independent right-hand sides, so the sweep runs panel by panel
 // (64 columns each); LU factors are shared by the panels through the per-node cache.
@@ -1703,17 +1720,16 @@ static int fh_contour_apply_local(feasthip_ctx* h, int64_t m64, const cplx* dQ, 
     if (stats) memset(stats, 0, sizeof(*stats));
     std::vector<int> ns(std::max(nodes, 1), 0), node_it(nodes, 0), col_it((size_t)nodes * m, 0);
     if (node_status) for (int e = 0; e < nodes; ++e) node_status[e] = 0;
-    const std::vector<int> mask = h->col_mask;
     for (int c0 = 0; c0 < m; c0 += FH_MAX_LD) {
         const int mc = std::min(FH_MAX_LD, m - c0);
         feasthip_stats st;
-        h->col_mask.clear();
-        if (!mask.empty()) for (int c = c0; c < c0 + mc; ++c) h->col_mask.push_back(c < (int)mask.size() ? mask[c] : 1);
         h->last_node_iters.clear(); h->last_col_iters.clear();
         mom.col0 = c0;
-        rc = fh_contour_apply_panel(h, mc, dQ + (size_t)c0 * N, ritz_lambda ? ritz_lambda + c0 : nullptr,
-                                    dQproj + (size_t)c0 * N, nullptr, nullptr, ns.data(), &st, want_mom ? &mom : nullptr);
-        h->col_mask = mask;
+        {
+            fh_mask_slice slice(h, c0, c0 + mc);
+            rc = fh_contour_apply_panel(h, mc, dQ + (size_t)c0 * N, ritz_lambda ? ritz_lambda + c0 : nullptr,
+                                        dQproj + (size_t)c0 * N, nullptr, nullptr, ns.data(), &st, want_mom ? &mom : nullptr);
+        }
         if (rc) return rc;
         for (int e = 0; e < nodes; ++e) {
             if (node_status) node_status[e] = std::max(node_status[e], ns[e]);
@@ -1802,7 +1818,9 @@ static int fh_contour_apply_impl(feasthip_ctx* h, int64_t m64, const cplx* dQ, c
     if (!local_rc && !full && !rs) soft(hipMemsetAsync(dQproj, 0, (size_t)N * m * sizeof(cplx), h->stream), "hipMemsetAsync(Q_proj)");
     cplx* rs_out = nullptr;                       // resident form: this rank's block of Q_proj, an N x rs_ldw panel
     int rs_ldw = 0;
-    if (rs && !local_rc && c1 > c0) {
+    if (!local_rc && c1 <= c0) {
+        soft(hipStreamSynchronize(h->stream), "hipStreamSynchronize");
+    } else if (!local_rc && rs) {
         const int w = (int)(c1 - c0);
         rs_ldw = fh_pick_ld(w);
         fh_panel_io io;
@@ -1824,28 +1842,14 @@ static int fh_contour_apply_impl(feasthip_ctx* h, int64_t m64, const cplx* dQ, c
         if (brc) local_rc = brc;
         else {
             io.out = rs_out;
-            const std::vector<int> mask = h->col_mask;
-            if (!mask.empty()) {
-                h->col_mask.clear();
-                for (int64_t c = c0; c < c1; ++c) h->col_mask.push_back(c < (int64_t)mask.size() ? mask[c] : 1);
-            }
+            fh_mask_slice slice(h, c0, c1);
             local_rc = fh_contour_apply_panel(h, w, nullptr, ritz_lambda ? ritz_lambda + c0 : nullptr, nullptr, nullptr, nullptr,
                                               ns.data(), stats, nullptr, &io);
-            h->col_mask = mask;
         }
-    } else if (rs && !local_rc) {
-        soft(hipStreamSynchronize(h->stream), "hipStreamSynchronize");
-    } else if (!local_rc && c1 > c0) {
-        const std::vector<int> mask = h->col_mask;
-        if (!mask.empty()) {
-            h->col_mask.clear();
-            for (int64_t c = c0; c < c1; ++c) h->col_mask.push_back(c < (int64_t)mask.size() ? mask[c] : 1);
-        }
+    } else if (!local_rc) {
+        fh_mask_slice slice(h, c0, c1);
         local_rc = fh_contour_apply_local(h, c1 - c0, dQ + (size_t)c0 * N, ritz_lambda ? ritz_lambda + c0 : nullptr,
                                           dQproj + (size_t)c0 * N, dzAq, dzSq, ns.data(), stats);
-        h->col_mask = mask;
-    } else if (!local_rc) {
-        soft(hipStreamSynchronize(h->stream), "hipStreamSynchronize");
     }
     if (nr == 1) {
         if (local_rc) return local_rc;
@@ -3069,37 +3073,26 @@ extern "C" int feasthip_shifted_solve_dev(feasthip_handle h, double z_re, double
     fh_launch_to_panel((const cplx*)dX, N, N, m, Rhs, ld, h->stream, fh_perm(h));
     std::vector<cplx> z(1, cmake(z_re, z_im));
     std::vector<int> status(1, 0);
-    if (h->solver == FEASTHIP_SOLVER_LU) {
-        if (h->kind != 1) { h->last_error = "solver LU requires a dense matrix"; return FEASTHIP_ERROR_FPM; }
-        int64_t nfact = 0;
-        // cached per quadrature node when z is one, else in one extra slot
+    if (h->solver == FEASTHIP_SOLVER_LU || h->solver == FEASTHIP_SOLVER_BANDED) {
+        const bool banded = h->solver == FEASTHIP_SOLVER_BANDED;
+        if (!banded && h->kind != 1) { h->last_error = "solver LU requires a dense matrix"; return FEASTHIP_ERROR_FPM; }
+        int64_t nfact = 0;          // (the factors are cached per quadrature node when z is one, else in one extra slot)
         double worst = 0.0;
-        if (h->factor_precision == 32) rc = fh_dense_lu_refined(h, ld, m, 1, z, Rhs, Y, panel, status, &nfact, true, &worst);
+        if (h->factor_precision == 32) rc = fh_dense_lu_refined(h, ld, m, 1, z, Rhs, Y, panel, status, &nfact, true, &worst, banded);
+        else if (banded) rc = fh_banded_solve_single(h, ld, m, z[0], Rhs, Y, &status[0], &nfact);
         else rc = fh_dense_lu_solve_single(h, ld, m, z[0], Rhs, Y, &status[0], &nfact);
         if (rc) return rc;
         if (stats) { stats->factorizations = nfact; stats->max_rel_residual = worst; }
-    } else if (h->solver == FEASTHIP_SOLVER_BANDED) {
-        int64_t nfact = 0;
-        double worst = 0.0;
-        if (h->factor_precision == 32) rc = fh_dense_lu_refined(h, ld, m, 1, z, Rhs, Y, panel, status, &nfact, true, &worst, true);
-        else rc = fh_banded_solve_single(h, ld, m, z[0], Rhs, Y, &status[0], &nfact);
-        if (rc) return rc;
-        if (stats) { stats->factorizations = nfact; stats->max_rel_residual = worst; }
-    } else if (h->solver == FEASTHIP_SOLVER_BICGSTAB || h->solver == FEASTHIP_SOLVER_COCG) {
+    } else {
         if (h->solver == FEASTHIP_SOLVER_COCG && fh_is_complex_input(h)) {
             h->last_error = "solver COCG needs real-symmetric A and B";
             return FEASTHIP_ERROR_FPM;
         }
         FH_CHECK(hipMemsetAsync(Y, 0, panel * sizeof(cplx), h->stream));
         fh_solve_result sr;
-        rc = fh_krylov(h, h->solver == FEASTHIP_SOLVER_COCG ? 1 : 0, h->factor_precision, ld, m, 1, z, Rhs, Y, panel, sr);
-        if (rc) return rc;
-        status = sr.status;
-        if (stats) { stats->krylov_iterations = sr.iters_sum; stats->spmm_calls = sr.op_calls; stats->max_rel_residual = sr.max_rel_res; }
-    } else {
-        FH_CHECK(hipMemsetAsync(Y, 0, panel * sizeof(cplx), h->stream));
-        fh_solve_result sr;
-        rc = fh_gmres(h, ld, m, 1, z, Rhs, Y, panel, sr);
+        const int method = h->solver == FEASTHIP_SOLVER_COCG ? 1 : h->solver == FEASTHIP_SOLVER_BICGSTAB ? 0 : -1;      // -1: GMRES
+        if (method >= 0) rc = fh_krylov(h, method, h->factor_precision, ld, m, 1, z, Rhs, Y, panel, sr, fh_krylov_opts());
+        else rc = fh_gmres(h, ld, m, 1, z, Rhs, Y, panel, sr);
         if (rc) return rc;
         status = sr.status;
         if (stats) { stats->krylov_iterations = sr.iters_sum; stats->spmm_calls = sr.op_calls; stats->max_rel_residual = sr.max_rel_res; }

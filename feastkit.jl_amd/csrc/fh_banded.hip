@@ -16,8 +16,6 @@
 #include "fh_banded.hpp"
 #include "fh_dense.hpp"
 #include <string>
-static inline cplx fh_ing_zero(cplx) { return cmake(0, 0); }
-static inline cplx fh_ing_add(cplx a, cplx b) { return cadd(a, b); }
 #define FH_INGEST_STORAGE_CSR 0
 #include "fh_ingest.hpp"       // fh_rcm, fh_bandwidth
 #include "fh_mf.hpp"           // fh_mf::max_boundary_multiplier

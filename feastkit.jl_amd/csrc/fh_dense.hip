@@ -2766,7 +2766,6 @@ int fh_mf_factor(feasthip_ctx* h, int prec, int nf, void* const* stores, int* co
 template <int LD, typename T>
 static int mf_solve_ld(feasthip_ctx* h, fh_mf_state* S, int nf, const mf_ptrs<T>& ptr, const cplx* RHS, size_t rhs_stride, cplx* OUT, size_t out_stride, int m) {
     const fh_mf::plan& P = S->P;
-    const int ng = (int)P.groups.size();
     const int cta = std::max(1, std::min(LD / 16, (m + 15) / 16));
     void* p;
     int rc;

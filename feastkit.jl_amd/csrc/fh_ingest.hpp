@@ -84,7 +84,7 @@ static bool to_csr0(int64_t N, int index_base, int storage, int64_t nnz, const i
 // order independent, results are for the matrix as the caller defined it.  perm[new] = old; blk_start: first row of every
 // block (+ N).
 // ---------------------------------------------------------------------------------------
-static void fh_block_partition(int64_t N, const std::vector<int>& rowptr_in, const std::vector<int>& col_in, int R,
+static inline void fh_block_partition(int64_t N, const std::vector<int>& rowptr_in, const std::vector<int>& col_in, int R,
                                std::vector<int>& perm, std::vector<int>& blk_start) {
     // The traversal needs an UNDIRECTED graph: on a structurally unsymmetric pattern (general pencils) a breadth-first
     // search along the stored direction only reaches part of a component, the level order of a part then listed some
@@ -165,7 +165,7 @@ static void fh_block_partition(int64_t N, const std::vector<int>& rowptr_in, con
 // pseudo-peripheral vertex (the far end of a breadth-first probe), neighbours taken by increasing degree, the whole order
 // reversed.  perm[new] = old.
 // ---------------------------------------------------------------------------------------
-static void fh_bandwidth(int64_t N, const std::vector<int>& rowptr, const std::vector<int>& col, const int* iperm, int& kl, int& ku) {
+static inline void fh_bandwidth(int64_t N, const std::vector<int>& rowptr, const std::vector<int>& col, const int* iperm, int& kl, int& ku) {
     kl = 0; ku = 0;
     for (int64_t i = 0; i < N; ++i) {
         const int bi = iperm ? iperm[i] : (int)i;
@@ -177,7 +177,7 @@ static void fh_bandwidth(int64_t N, const std::vector<int>& rowptr, const std::v
     }
 }
 
-static void fh_rcm(int64_t N, const std::vector<int>& rowptr_in, const std::vector<int>& col_in, std::vector<int>& perm) {
+static inline void fh_rcm(int64_t N, const std::vector<int>& rowptr_in, const std::vector<int>& col_in, std::vector<int>& perm) {
     std::vector<int> rowptr(N + 1, 0), col;
     {
         std::vector<int> deg(N, 0);

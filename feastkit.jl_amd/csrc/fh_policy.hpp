@@ -173,3 +173,12 @@ static inline int pick_direct_nodes(const int* node_iters, int ne, int max_direc
 }
 
 }   // namespace fh_policy
+
+// Which columns of a finished Krylov sweep failed (fh_api.hip: fh_collect_columns): those still active or with a non-finite
+// norm, and by rule STOP_TEST (COCG, BiCGStab, shifted COCG) a predicted stop (status 8) whose norm misses atol + rtol ||r0||,
+// by rule TARGET (GMRES) a norm above the column's target.
+enum fh_fail_rule { FH_FAIL_STOP_TEST, FH_FAIL_TARGET };
+inline bool fh_column_failed(fh_fail_rule rule, int active, int status, double rnorm, double r0, double target, double atol, double rtol) {
+    if (active || !std::isfinite(rnorm)) return true;
+    return rule == FH_FAIL_TARGET ? rnorm > target : status == 8 && !(rnorm <= atol + rtol * r0);
+}

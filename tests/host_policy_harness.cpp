@@ -78,6 +78,16 @@ int main(int argc, char** argv) {
         CHECK(member && (got == 100 || (got <= cap && (limit <= 0 || got <= limit))));
         CHECK(fh_policy::pick(Emin, Emax, ne, quad, 0.9, cap, 1.5, nullptr, 0, 0) == 100);        // nothing contracts below 0.5
     }
+    // the two failure rules of the Krylov bookkeeping (fh_column_failed) agree on active and non-finite columns and differ
+    // exactly on: an inactive column above its target (a failed GMRES column; a masked or capped-by-prediction COCG column is
+    // judged by its own stop test instead) and a predicted stop (status 8) that missed atol + rtol ||r0||
+    for (fh_fail_rule rule : {FH_FAIL_STOP_TEST, FH_FAIL_TARGET}) {
+        CHECK(fh_column_failed(rule, 1, 0, 1e-9, 1.0, 1e-3, 0.0, 1e-3) && fh_column_failed(rule, 0, 0, std::nan(""), 1.0, 1e-3, 0.0, 1e-3));
+        CHECK(!fh_column_failed(rule, 0, 0, 5e-4, 1.0, 1e-3, 0.0, 1e-3));
+    }
+    CHECK(fh_column_failed(FH_FAIL_TARGET, 0, 0, 2e-3, 1.0, 1e-3, 0.0, 1e-3) && !fh_column_failed(FH_FAIL_STOP_TEST, 0, 0, 2e-3, 1.0, 1e-3, 0.0, 1e-3));
+    CHECK(fh_column_failed(FH_FAIL_STOP_TEST, 0, 8, 2e-3, 1.0, 1.0, 0.0, 1e-3) && !fh_column_failed(FH_FAIL_TARGET, 0, 8, 2e-3, 1.0, 1.0, 0.0, 1e-3));
+    CHECK(!fh_column_failed(FH_FAIL_STOP_TEST, 0, 8, 5e-4, 1.0, 1.0, 0.0, 1e-3));
     std::printf("ok %d\n", cases);
     return 0;
 }

@@ -18,7 +18,7 @@ kernels, not of a textbook:
               column whose |rho'| (|r|^2/|r^T r|) is <= target^2 (and >= 1e-12 |r|^2) takes this step and stops: beta = 0,
               the reported norm is the square root of the estimate.
 
-Common (k_fin_init, the gather loop of fh_krylov): target = rtol |r0| + atol; a column with |r0| <= target, a masked
+Common (k_fin_init, fh_collect_columns at the end of fh_krylov): target = rtol |r0| + atol; a column with |r0| <= target, a masked
 column or a non-finite |r0| never iterates; breakdown (sigma == 0, rho == 0, non-finite alpha / beta) ends the column with
 status 8; maxit caps the steps; a node reports 5 when a column is still active, its norm is not finite, or it broke down
 above its target.
@@ -257,7 +257,7 @@ def truncated(col, k):
 
 
 def node_status(cols, rtol, atol):
-    """The per-node status of the gather loop at the end of fh_krylov."""
+    """The per-node status that fh_collect_columns (rule FH_FAIL_STOP_TEST) reports at the end of fh_krylov."""
     st = 0
     for c in cols:
         if c.active or not np.isfinite(c.rnorm):
