@@ -1150,6 +1150,10 @@ static int fh_shifted_cocg(feasthip_ctx* h, int ld, int m, int nodes, const std:
 // columns, Givens rotations and the per-column stop test live on the device.  The host only queues kernels: it
 // looks at the device's published progress word without blocking to stop queueing once every column has converged
 // inside a cycle, and reads the true-residual check once per restart cycle.
+// maxit caps the lock-steps that RAN, and spmm_calls counts them: the host may have queued up to six steps behind the last
+// live column of a cycle (they return at once), so the device leaves the cycle's largest kdim in the second host-mapped word
+// and the host adds it after the synchronisation of the next cycle start.  (Counting queued steps made the budget left for a
+// column that the restart's true residual reactivates, and spmm_calls, depend on host/device timing.)
 // ---------------------------------------------------------------------------------------
 static int fh_gmres(feasthip_ctx* h, int ld, int m, int nodes_all, const std::vector<cplx>& z, const cplx* RHS, cplx* X,
                     size_t stride, fh_solve_result& res) {
@@ -1218,9 +1222,9 @@ static int fh_gmres(feasthip_ctx* h, int ld, int m, int nodes_all, const std::ve
         oc.m = m; oc.uniform_coef = 1; oc.coefA = dca; oc.coefB = dcb; oc.nodes = nodes; oc.prec = 64;
         oc.partial2 = npart;
 
-        int total_it = 0, first = 1;
+        int total_it = 0, first = 1;                             // total_it: the lock-steps that ran
         unsigned tag = 0;
-        *h->h_progress = 0ull;
+        h->h_progress[0] = 0ull; h->h_progress[1] = 0ull;
         auto seen = [&](unsigned& st, unsigned& cnt) { unsigned long long w = *h->h_progress; st = (unsigned)(w >> 32); cnt = (unsigned)(w & 0xffffffffull); };
         while (true) {
             // true residual r = b - S x (into W), ||r|| per column, activity from the stop test
@@ -1232,18 +1236,19 @@ static int fh_gmres(feasthip_ctx* h, int ld, int m, int nodes_all, const std::ve
             ++tag;
             fh_launch_publish_progress(ga.node_active, nodes, h->d_progress, tag, h->stream);
             FH_CHECK(hipStreamSynchronize(h->stream));           // the one host round trip per restart cycle
+            const int ran = (int)h->h_progress[1];               // of the cycle just finished (0 before the first)
+            total_it += ran; res.op_calls += ran;
             unsigned st = 0, cnt = 0;
             seen(st, cnt);
             if (cnt == 0 || total_it >= h->maxit) break;
             fh_launch_gm_scale_store(ga, ld, W, panel, 0, nblk_vec, nodes, h->stream);           // v_0 = r / beta
             int ksteps = 0;
             const unsigned tag0 = tag;
-            for (int k = 0; k < mr && total_it < h->maxit; ++k) {
+            for (int k = 0; k < mr && total_it + k < h->maxit; ++k) {
                 oc.X = V + (size_t)k * panel; oc.x_stride = ga.v_node_stride; oc.Y = W; oc.y_stride = panel; oc.Bvec = nullptr;
                 oc.dot_mode = 0; oc.node_active = ga.node_active; oc.partial2 = nullptr;
                 fh_apply_operator(h, ld, oc);                                                  // w = S v_k
                 oc.partial2 = npart;
-                res.op_calls += 1;
                 fh_prof_begin(h, "gmres_ortho");
                 fh_launch_gm_orthogonalize(ga, ld, k, nblk_vec, nodes, h->stream);             // CGS2 against v_0..v_k
                 fh_launch_gm_givens(ga, ld, k, nblk_vec, nodes, h->stream);
@@ -1251,7 +1256,7 @@ static int fh_gmres(feasthip_ctx* h, int ld, int m, int nodes_all, const std::ve
                 fh_prof_end(h);
                 ++tag;
                 fh_launch_publish_progress(ga.node_active, nodes, h->d_progress, tag, h->stream);
-                ++ksteps; ++total_it;
+                ++ksteps;
                 // non-blocking look at the device's progress: stop queueing steps once every column has converged
                 seen(st, cnt);
                 if (st > tag0 && cnt == 0) break;
@@ -1270,7 +1275,7 @@ static int fh_gmres(feasthip_ctx* h, int ld, int m, int nodes_all, const std::ve
                     if (st > tag0 && cnt == 0) break;
                 }
             }
-            fh_launch_gm_finish_cycle(ga, ld, Xb, stride, ksteps, nblk_vec, nodes, h->stream);   // x += V y
+            fh_launch_gm_finish_cycle(ga, ld, Xb, stride, ksteps, nblk_vec, nodes, h->d_progress + 1, h->stream);   // x += V y
         }
         if ((rc = fh_collect_columns(h, ga.iters, ga.status, ga.active, ga.rnorm, ga.r0norm, ga.target, nodes, m, ld, e0, FH_FAIL_TARGET, res)))
             return rc;

@@ -269,6 +269,21 @@ __global__ __launch_bounds__(GM_BLOCK) void k_gm_xupdate(fh_gmres_args a, cplx* 
     }
 }
 
+// ---- the lock-steps of the cycle that RAN: the largest kdim of the batch (a step queued behind the last live column returns
+// at once and leaves every kdim alone), into a host-mapped word the host reads after its next synchronisation -----------------
+__global__ __launch_bounds__(GM_BLOCK) void k_gm_cycle_steps(const int* kdim, int n, unsigned long long* out) {
+    __shared__ int red[GM_BLOCK];
+    int mx = 0;
+    for (int i = threadIdx.x; i < n; i += GM_BLOCK) mx = max(mx, kdim[i]);
+    red[threadIdx.x] = mx;
+    __syncthreads();
+    for (int s = GM_BLOCK / 2; s > 0; s >>= 1) {
+        if (threadIdx.x < s) red[threadIdx.x] = max(red[threadIdx.x], red[threadIdx.x + s]);
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) __hip_atomic_store(out, (unsigned long long)red[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
 // ---------------------------------------------------------------------------------------------------------------------------
 #define GM_DISPATCH(ld, KERNEL, grid, st, ...)                                                        \
     do {                                                                                               \
@@ -298,7 +313,9 @@ void fh_launch_gm_scale_store(const fh_gmres_args& a, int ld, const cplx* src, s
                               hipStream_t st) {
     GM_DISPATCH(ld, k_gm_scale_store, dim3(nblk, nodes), st, a, src, src_node_stride, dst_index);
 }
-void fh_launch_gm_finish_cycle(const fh_gmres_args& a, int ld, cplx* X, size_t x_node_stride, int kmax, int nblk, int nodes, hipStream_t st) {
+void fh_launch_gm_finish_cycle(const fh_gmres_args& a, int ld, cplx* X, size_t x_node_stride, int kmax, int nblk, int nodes,
+                               unsigned long long* steps_ran, hipStream_t st) {
     GM_DISPATCH(ld, k_gm_solve_y, dim3((nodes * ld + GM_BLOCK - 1) / GM_BLOCK), st, a, nodes);
     GM_DISPATCH(ld, k_gm_xupdate, dim3(nblk, nodes), st, a, X, x_node_stride, kmax);
+    hipLaunchKernelGGL(k_gm_cycle_steps, dim3(1), dim3(GM_BLOCK), 0, st, a.kdim, nodes * ld, steps_ran);
 }

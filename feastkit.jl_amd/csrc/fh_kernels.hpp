@@ -170,7 +170,8 @@ void fh_launch_gm_start(const fh_gmres_args& a, int ld, int nblk_norm, int nodes
 void fh_launch_gm_givens(const fh_gmres_args& a, int ld, int k, int nblk, int nodes, hipStream_t st);
 void fh_launch_gm_scale_store(const fh_gmres_args& a, int ld, const cplx* src, size_t src_node_stride, int dst_index, int nblk, int nodes,
                               hipStream_t st);
-void fh_launch_gm_finish_cycle(const fh_gmres_args& a, int ld, cplx* X, size_t x_node_stride, int kmax, int nblk, int nodes, hipStream_t st);
+void fh_launch_gm_finish_cycle(const fh_gmres_args& a, int ld, cplx* X, size_t x_node_stride, int kmax, int nblk, int nodes,
+                               unsigned long long* steps_ran, hipStream_t st);
 
 // ---- block (panel) operations ------------------------------------------------------------
 // column-major (N x m, leading dim lds) <-> row-major panel (N x ld), zero padded

@@ -201,6 +201,8 @@ int  feasthip_set_column_mask(feasthip_handle h, int64_t m, const int* mask);
  * fp64 operator kernel, stop at 1e-14 relative, <= 8 steps) -- fp64-accurate solves while
  * cond(zB-A)*eps32 < 1 (the reference has no counterpart; BASELINE config 5 asks for it).
  * BiCGStab/COCG: correction solve on complex64 panels around an fp64 residual (inexact-solve mode).
+ * restart: the GMRES restart length (basis panels per cycle); 0 and 1 are taken as 2.  GMRES counts maxit in lock-steps of a
+ * node batch (all columns of the batch's nodes advance together) and spmm_calls in products that ran.
  * cache_factors: keep LU factors per
  * node across calls (src/dense/feast_dense.jl:147,188).                                 */
 /* Free the cached factorisations of the direct solvers (dense LU, band LU): the reference keeps `lu(z B - A)` per node for

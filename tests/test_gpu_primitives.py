@@ -518,7 +518,7 @@ def test_gmres_shifted_solve(engine, N, m, restart, dense):
     engine.set_solver("direct")
 
 
-@pytest.mark.parametrize("solver", ["cocg", "bicgstab"])
+@pytest.mark.parametrize("solver", ["cocg", "bicgstab", "gmres"])
 def test_contour_apply_is_bitwise_reproducible(engine, solver):
     """Two-stage fixed-order reductions and the in-order node sum of the COCG sum mode: the same call
     twice gives the same bits (no float atomics)."""
