@@ -71,6 +71,8 @@ SYMBOLS = {
     "feasthip_resident_import": (_i, [_vp, _i, _i64, _vp]),
     "feasthip_orthonormalize": (_i, [_vp, _i64, _vp, _d, _pi]),
     "feasthip_orthonormalize_dev": (_i, [_vp, _i64, _vp, _d, _pi]),
+    "feasthip_set_ortho_method": (_i, [_vp, _i]),
+    "feasthip_last_ortho": (_i, [_vp, _pi, _pi, _pi, _pi, _vp, _vp, _i]),
     "feasthip_project": (_i, [_vp, _i64, _vp, _i, _i, _vp, _vp]),
     "feasthip_project_dev": (_i, [_vp, _i64, _vp, _i, _i, _vp, _vp]),
     "feasthip_ritz_residual": (_i, [_vp, _i64, _vp, _vp, _vp, _i64, _i, _i, _vp, _vp]),

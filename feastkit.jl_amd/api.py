@@ -12,7 +12,7 @@ import scipy.sparse as sp
 
 from .engine import HipEngine
 from .contour import feast_contour, feast_gcontour
-from .hip_backend import (DIRECT_SOLVERS, ESTIMATE_SEED, check_direct_nodes, feast_hip_estimate, feast_hip_general,
+from .hip_backend import (DIRECT_SOLVERS, ESTIMATE_SEED, check_direct_nodes, check_ortho, feast_hip_estimate, feast_hip_general,
                           feast_hip_hermitian)
 from .parameters import feastdefault, feastinit
 from .types import FEAST_UNINITIALIZED, FeastHipError, FeastResult
@@ -246,7 +246,7 @@ def _engine(engine, device):
 def feast(A, B=None, interval=None, *, M0=10, fpm=None, backend="hip", solver="direct", solver_tol=0.0,
           solver_maxiter=None, solver_restart=30, warm_start=None, inner_rtol=None, real_projection=None,
           inner_precision=64, group=None, engine=None, device=0, Q0=None, contour=None, contour_policy=None,
-          keep_factors=False, seed=None, direct_nodes=None):
+          keep_factors=False, seed=None, direct_nodes=None, ortho="mgs"):
     """feast(A, [B,] (Emin, Emax); M0, fpm, backend=:hip) for real-symmetric / Hermitian
     dense (numpy) or sparse (scipy) matrices.  Real input is complexified and the result is
     real.(q), exactly as feast_sygv!/feast_scsrgv! do (src/dense/feast_dense.jl:362-387).
@@ -266,6 +266,9 @@ def feast(A, B=None, interval=None, *, M0=10, fpm=None, backend="hip", solver="d
     them): contour nodes the sweeps solve with the sparse direct solver instead of iterating (per-node solver,
     feasthip_set_node_solver) -- a list of node indices, an int k (the k slowest nodes of the first loop, from the second
     on) or "auto" (feasthip_policy_pick_direct_nodes after every loop).  ``stats["direct_nodes"]`` has one entry per loop.
+    ``ortho``: what orthonormalises a rank-deficient subspace (every loop of an exact solver): "mgs", the column-pivoted
+    Gram-Schmidt (default), or "cholqr_rr", the staged rank-revealing Cholesky-QR; same rank rule.  ``stats["ortho"]`` has one
+    entry per loop: method used ("cholqr" = the full-rank fast path), stages, fell_back, rank.
     """
     if isinstance(M0, str):
         if M0 != "auto":
@@ -274,7 +277,7 @@ def feast(A, B=None, interval=None, *, M0=10, fpm=None, backend="hip", solver="d
                            solver_maxiter=solver_maxiter, solver_restart=solver_restart, warm_start=warm_start,
                            inner_rtol=inner_rtol, real_projection=real_projection, inner_precision=inner_precision,
                            group=group, engine=engine, device=device, Q0=Q0, contour=contour, contour_policy=contour_policy,
-                           keep_factors=keep_factors, seed=seed, direct_nodes=direct_nodes)
+                           keep_factors=keep_factors, seed=seed, direct_nodes=direct_nodes, ortho=ortho)
     if interval is None and B is not None and isinstance(B, tuple):
         B, interval = None, B              # feast(A, (Emin, Emax)) form
     if backend not in _BACKENDS:
@@ -284,6 +287,7 @@ def feast(A, B=None, interval=None, *, M0=10, fpm=None, backend="hip", solver="d
     if B is not None and B.shape != A.shape:
         raise ValueError("Matrix B must match size of A")
     _check_direct_nodes_early(direct_nodes, A, solver, fpm, 2, contour)
+    check_ortho(ortho)
     eng = _engine(engine, device)
     # input checks and the pattern scan cost tens of milliseconds on a 50 000-unknown CSR pair (sparse transposes): a
     # repeated call with the same matrices (content fingerprint, engine.py) skips them
@@ -400,7 +404,7 @@ def feast(A, B=None, interval=None, *, M0=10, fpm=None, backend="hip", solver="d
                                   warm_start=warm_start, inner_rtol=inner_rtol, real_projection=real_projection,
                                   inner_precision=inner_precision, group=group, Q0=Q0, contour=contour,
                                   contour_policy=contour_policy, eps_floor=float(np.sqrt(np.finfo(np.float32).eps)) if single else 0.0,
-                                  abort_check=abort_check, direct_nodes=None if dn_ignored else direct_nodes)
+                                  abort_check=abort_check, direct_nodes=None if dn_ignored else direct_nodes, ortho=ortho)
         if dn_ignored and isinstance(res.stats, dict):
             res.stats["direct_nodes"] = {"ignored": "direct solver in force"}
         if (res.info == 5 and substituted is not None and substituted.get("used") in ("cocg", "bicgstab") and group is None
@@ -415,7 +419,8 @@ def feast(A, B=None, interval=None, *, M0=10, fpm=None, backend="hip", solver="d
             dn_log = res.stats.get("direct_nodes") if isinstance(res.stats, dict) else None
             res = feast_hip_hermitian(eng, A, B, Emin, Emax, M0, fpm, solver="banded", solver_tol=solver_tol,
                                       real_projection=real_projection, inner_precision=inner_precision, group=group, Q0=Q0,
-                                      contour=contour, eps_floor=float(np.sqrt(np.finfo(np.float32).eps)) if single else 0.0)
+                                      contour=contour, eps_floor=float(np.sqrt(np.finfo(np.float32).eps)) if single else 0.0,
+                                      ortho=ortho)
             if dn_log is not None and isinstance(res.stats, dict):
                 res.stats["direct_nodes"] = dn_log                      # what the Krylov loops did before the hand-over
             substituted = dict(substituted, fallback=_direct_label(eng), krylov_info=krylov_info,
@@ -433,9 +438,10 @@ def feast(A, B=None, interval=None, *, M0=10, fpm=None, backend="hip", solver="d
 
 def feast_general(A, B=None, center=0.0, radius=1.0, *, M0=10, fpm=None, backend="hip", solver="direct",
                   solver_tol=0.0, solver_maxiter=500, solver_restart=30, group=None, engine=None, device=0, Q0=None,
-                  inner_precision=64, contour=None, keep_factors=False, seed=None, direct_nodes=None):
+                  inner_precision=64, contour=None, keep_factors=False, seed=None, direct_nodes=None, ortho="mgs"):
     """feast_general(A, [B,] center, radius; M0, fpm): src/interfaces/feast_interfaces.jl:274-379.
-    ``keep_factors``, ``direct_nodes``: as in feast().  ``fpm[14] = 2`` and ``M0="auto"``: as in feast(), on the full contour of the
+    ``keep_factors``, ``direct_nodes``, ``ortho``: as in feast() (this variant never orthonormalises its subspace, so ``ortho``
+    changes nothing it computes).  ``fpm[14] = 2`` and ``M0="auto"``: as in feast(), on the full contour of the
     circle (the samples are complex; M = round(Re mean))."""
     if isinstance(M0, str):
         if M0 != "auto":
@@ -443,7 +449,7 @@ def feast_general(A, B=None, center=0.0, radius=1.0, *, M0=10, fpm=None, backend
         return _feast_auto(feast_general, A, B, center, radius, fpm=fpm, backend=backend, solver=solver, solver_tol=solver_tol,
                            solver_maxiter=solver_maxiter, solver_restart=solver_restart, group=group, engine=engine,
                            device=device, Q0=Q0, inner_precision=inner_precision, contour=contour, keep_factors=keep_factors,
-                           seed=seed, direct_nodes=direct_nodes)
+                           seed=seed, direct_nodes=direct_nodes, ortho=ortho)
     if backend not in _BACKENDS:
         raise ValueError(f"Unknown backend '{backend}' (this package provides: hip)")
     if A.shape[0] != A.shape[1]:
@@ -451,6 +457,7 @@ def feast_general(A, B=None, center=0.0, radius=1.0, *, M0=10, fpm=None, backend
     if not radius > 0:
         raise ValueError("radius must be positive")
     _check_direct_nodes_early(direct_nodes, A, solver, fpm, 8, contour)
+    check_ortho(ortho)
     single = _single_precision(A, B)
     if single:
         A, B = _promote(A), _promote(B)
@@ -498,7 +505,7 @@ def feast_general(A, B=None, center=0.0, radius=1.0, *, M0=10, fpm=None, backend
                                  solver_tol=solver_tol, solver_maxiter=solver_maxiter,
                                  solver_restart=solver_restart, group=group, Q0=Q0, contour=contour,
                                  eps_floor=float(np.sqrt(np.finfo(np.float32).eps)) if single else 0.0,
-                                 direct_nodes=None if dn_ignored else direct_nodes)
+                                 direct_nodes=None if dn_ignored else direct_nodes, ortho=ortho)
         if dn_ignored and isinstance(res.stats, dict):
             res.stats["direct_nodes"] = {"ignored": "direct solver in force"}
         if substituted is not None and isinstance(res.stats, dict):

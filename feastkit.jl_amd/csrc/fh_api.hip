@@ -2035,6 +2035,118 @@ extern "C" int feasthip_estimate_count(feasthip_handle h, int64_t m, uint64_t se
 // ---------------------------------------------------------------------------------------
 // orthonormalisation (a9)
 // ---------------------------------------------------------------------------------------
+// what the last orthonormalisation did (feasthip_last_ortho).  A call over several panels (fh_ortho_wide) adds up stages,
+// fall-backs and rank; perm / rdiag are the last panel's.  The method reported for such a call is the staged path if any
+// panel took it, else the Gram-Schmidt if any did, else the Cholesky-QR fast path.
+static void fh_ortho_note(feasthip_ctx* h, int used, int stages, int fell_back, int rank, const int* perm, const double* rdiag) {
+    auto& o = h->ortho_last;
+    auto weight = [](int u) { return u == FEASTHIP_ORTHO_CHOLQR_RR ? 2 : u == FEASTHIP_ORTHO_MGS ? 1 : 0; };
+    if (o.panels == 0 || weight(used) > weight(o.used)) o.used = used;
+    o.panels += 1;
+    o.stages += stages; o.fell_back += fell_back; o.rank += rank;
+    o.perm.assign(perm, perm + rank);
+    if (rdiag) o.rdiag.assign(rdiag, rdiag + rank);
+    else o.rdiag.assign(rank, 0.0);
+}
+static void fh_ortho_note_reset(feasthip_ctx* h) {
+    h->ortho_last.panels = h->ortho_last.used = h->ortho_last.stages = h->ortho_last.fell_back = h->ortho_last.rank = 0;
+    h->ortho_last.perm.clear(); h->ortho_last.rdiag.clear();
+}
+
+// The staged rank-revealing Cholesky-QR (FEASTHIP_ORTHO_CHOLQR_RR) on a panel that fh_cholqr::accept rejected.  Per stage:
+//   G = W^H W of the working copy W -> k_pchol_stage: the pivots this stage may judge, R^-1 with the permutation folded in
+//   T = W R^-1 (the accepted columns, first pass); from the second stage on T -= K (K^H T) against the columns K kept so far
+//   G = T^H T -> k_pchol_stage (refine): second pass, T2 = T R2^-1 lands in the columns [rank, rank + accepted) of a zero panel
+//   Out += T2;  twice:  W -= T2 (T2^H W)
+// All of it is queued for a fixed number of stages; the device decides how many run (the launches of a stage past the
+// decision return at once) and the host reads the state once.  The Gram product, the panel product and the column update
+// are the existing kernels (k_gram_mfma, k_small_matmul_mfma, k_axpy_cols) with a skip word: fusing gather, product and
+// subtraction would save two passes over W per stage, which is not where the time of a 2-3 stage call goes (the latency
+// chain of k_pchol_stage and the launch count are).  *staged = false: a non-finite Gram matrix, a stage that accepted
+// nothing, a second pass that broke down, or no decision within FH_RR_MAX_STAGES; X is untouched in every case.
+// colmax: the largest column norm of X (accept() has it).  The working copy is scaled by the power of two that brings it
+// into [1, 2): exact, and the Gram matrices of the later stages -- squares of what is left after the projections -- stay
+// clear of the denormal range for panels of any magnitude.
+#define FH_RR_MAX_STAGES 6
+#define FH_RR_WINDOW 1e-10
+static int fh_ortho_staged(feasthip_ctx* h, int m, int ld, const cplx* X, cplx* Out, double rank_tol, double ref_scale, int big_dim,
+                           double colmax, int* rank, bool* staged) {
+    const int N = (int)fh_N(h);
+    const size_t panel = (size_t)N * ld;
+    int rc;
+    void* p;
+    *staged = false;
+    if ((rc = fh_get_buf(h, "rr_W", panel * sizeof(cplx), &p))) return rc;
+    cplx* W = (cplx*)p;
+    if ((rc = fh_get_buf(h, "rr_T", panel * sizeof(cplx), &p))) return rc;
+    cplx* T = (cplx*)p;
+    if ((rc = fh_get_buf(h, "rr_T2", panel * sizeof(cplx), &p))) return rc;
+    cplx* T2 = (cplx*)p;
+    if ((rc = fh_get_buf(h, "gram_work", fh_gram_work_elems(ld) * sizeof(cplx), &p))) return rc;
+    cplx* gw = (cplx*)p;
+    if ((rc = fh_get_buf(h, "gram_G", (size_t)ld * ld * sizeof(cplx), &p))) return rc;
+    cplx* G = (cplx*)p;
+    if ((rc = fh_get_buf(h, "or_Rinv", (size_t)ld * ld * sizeof(cplx), &p))) return rc;
+    cplx* dR = (cplx*)p;
+    if ((rc = fh_get_buf(h, "rr_C", (size_t)ld * ld * sizeof(cplx), &p))) return rc;
+    cplx* C = (cplx*)p;
+    if ((rc = fh_get_buf(h, "rr_istate", (FH_RR_PERM + FH_MAX_LD) * sizeof(int), &p))) return rc;
+    int* ist = (int*)p;
+    if ((rc = fh_get_buf(h, "rr_dstate", (2 + FH_MAX_LD) * sizeof(double), &p))) return rc;
+    double* dst = (double*)p;
+    std::vector<cplx> ones(ld, cmake(1, 0)), mones(ld, cmake(-1, 0));
+    cplx *done, *dmone;
+    if ((rc = fh_upload_coefs(h, "rr_one", ones, &done))) return rc;
+    if ((rc = fh_upload_coefs(h, "rr_mone", mones, &dmone))) return rc;
+    const double eps = 2.220446049250313e-16;
+    const double big = (double)std::max(N, std::max(big_dim, m));
+    const double thr = std::max(rank_tol, eps * big);                     // the threshold of k_mgs_pick
+    const double scale = colmax > 0.0 && std::isfinite(colmax) ? std::ldexp(1.0, -std::ilogb(colmax)) : 1.0;
+    std::vector<cplx> scl(ld, cmake(scale, 0));
+    cplx* dscale;
+    if ((rc = fh_upload_coefs(h, "rr_scale", scl, &dscale))) return rc;
+    const int* skip = ist + FH_RR_SKIP;
+    const int* decided = ist + FH_RR_DONE;
+    hipStream_t st = h->stream;
+    fh_prof_begin(h, "ortho");
+    FH_CHECK(hipMemcpyAsync(W, X, panel * sizeof(cplx), hipMemcpyDeviceToDevice, st));
+    if (scale != 1.0) fh_launch_scale_cols(W, dscale, N, ld, st);
+    FH_CHECK(hipMemsetAsync(Out, 0, panel * sizeof(cplx), st));
+    fh_launch_rr_init(ist, dst, ld, st);
+    for (int s = 0; s < FH_RR_MAX_STAGES; ++s) {
+        fh_launch_gram(W, W, N, ld, 0, gw, G, st, decided);
+        fh_launch_pchol_stage(G, m, ld, 0, FH_RR_WINDOW, thr, ref_scale * scale, ist, dst, dR, st);
+        fh_launch_small_matmul(W, dR, N, ld, T, st, skip);
+        if (s > 0) {
+            fh_launch_gram(Out, T, N, ld, 0, gw, C, st, skip);
+            fh_launch_small_matmul(Out, C, N, ld, T2, st, skip);
+            fh_launch_axpy_cols(T, T2, done, N, ld, st, skip);              // T -= K (K^H T)
+        }
+        fh_launch_gram(T, T, N, ld, 0, gw, G, st, skip);
+        fh_launch_pchol_stage(G, m, ld, 1, 0.0, thr, ref_scale * scale, ist, dst, dR, st);
+        fh_launch_small_matmul(T, dR, N, ld, T2, st, skip);
+        fh_launch_axpy_cols(Out, T2, dmone, N, ld, st, skip);               // Out += T2
+        for (int pass = 0; pass < 2; ++pass) {
+            fh_launch_gram(T2, W, N, ld, 0, gw, C, st, decided);
+            fh_launch_small_matmul(T2, C, N, ld, T, st, decided);
+            fh_launch_axpy_cols(W, T, done, N, ld, st, decided);            // W -= T2 (T2^H W)
+        }
+    }
+    fh_prof_end(h);
+    int hst[FH_RR_PERM + FH_MAX_LD];
+    double hds[2 + FH_MAX_LD];
+    FH_CHECK(hipMemcpyAsync(hst, ist, (FH_RR_PERM + ld) * sizeof(int), hipMemcpyDeviceToHost, st));
+    FH_CHECK(hipMemcpyAsync(hds, dst, (2 + ld) * sizeof(double), hipMemcpyDeviceToHost, st));
+    FH_CHECK(hipStreamSynchronize(st));
+    const int r = hst[FH_RR_RANK];
+    if (hst[FH_RR_FAIL] || !hst[FH_RR_DONE] || r < 0 || r > m) return 0;
+    *rank = r;
+    *staged = true;
+    for (int k = 0; k < r; ++k) hds[2 + k] /= scale;
+    fh_ortho_note(h, FEASTHIP_ORTHO_CHOLQR_RR, hst[FH_RR_STAGES], 0, r, hst + FH_RR_PERM, hds + 2);
+    return 0;
+}
+
 // Rank-revealing orthonormalisation of the m (<= ld) columns of panel X.  On success *res is the
 // panel (X or Out) whose first *rank columns hold the basis.  ref_scale > 0 / big_dim: X is a
 // block of a wider matrix (see k_mgs_pick).
@@ -2051,6 +2163,7 @@ static int fh_ortho_panel(feasthip_ctx* h, int m, int ld, cplx* X, cplx* Out, do
     double* dstate = (double*)p;
     if ((rc = fh_get_buf(h, "or_coef", FH_MAX_LD * sizeof(cplx), &p))) return rc;
     cplx* coef = (cplx*)p;
+    int fell_back = 0;
     // Fast path (Cholesky-QR, one or two passes) when the panel is far from rank deficient (fh_cholqr::accept: the pivoted
     // Cholesky pivots of the Gram matrix are the squared R_kk of the pivoted QR).  Otherwise fall through to the
     // rank-revealing pivoted Gram-Schmidt.  The Rayleigh-Ritz step that follows uses Q^H B Q anyway, so one pass suffices
@@ -2094,10 +2207,21 @@ static int fh_ortho_panel(feasthip_ctx* h, int m, int ld, cplx* X, cplx* Out, do
         if (ok) {       // src after the swaps: X after two passes, Out after one
             *rank = m;
             *res = src;
+            std::vector<int> ident(m);
+            for (int j = 0; j < m; ++j) ident[j] = j;
+            fh_ortho_note(h, FEASTHIP_ORTHO_USED_CHOLQR, 0, 0, m, ident.data(), nullptr);
             return 0;
         }
         // a failure happens before the pass writes its destination: X still holds the input
         // (pass 0 writes Out, pass 1 would have written X)
+        if (h->ortho_method == FEASTHIP_ORTHO_CHOLQR_RR) {
+            bool staged = false;
+            double colmax = 0.0;
+            for (double dj : dcol) colmax = std::max(colmax, dj);
+            if ((rc = fh_ortho_staged(h, m, ld, X, Out, rank_tol, ref_scale, big_dim, colmax, rank, &staged))) return rc;
+            if (staged) { *res = Out; return 0; }
+            fell_back = 1;                     // X is untouched: the Gram-Schmidt decides as it would have
+        }
     }
     fh_mgs_args a;
     a.X = X; a.N = N; a.ld = ld; a.m = m; a.istate = istate; a.dstate = dstate; a.coef = coef; a.work = work;
@@ -2114,6 +2238,7 @@ static int fh_ortho_panel(feasthip_ctx* h, int m, int ld, cplx* X, cplx* Out, do
     *rank = r;
     fh_launch_gather_cols(X, istate + 4, r, N, ld, Out, h->stream);
     *res = Out;
+    fh_ortho_note(h, FEASTHIP_ORTHO_MGS, 0, fell_back, r, hst + 4, nullptr);
     return 0;
 }
 
@@ -2191,6 +2316,7 @@ extern "C" int feasthip_orthonormalize_dev(feasthip_handle h, int64_t m64, void*
     if (rc) return rc;
     if (!dQ || !rank) { h->last_error = "orthonormalize: null argument"; return FEASTHIP_ERROR_INTERNAL; }
     FH_CHECK(hipSetDevice(h->device));
+    fh_ortho_note_reset(h);
     if (m64 > FH_MAX_LD) {
         rc = fh_ortho_wide(h, (int)m64, (cplx*)dQ, rank_tol, rank);
         fh_prof_collect(h);
@@ -2224,6 +2350,31 @@ extern "C" int feasthip_orthonormalize(feasthip_handle h, int64_t m, void* Q, do
     rc = feasthip_orthonormalize_dev(h, m, dQ, rank_tol, rank);
     if (rc) return rc;
     FH_CHECK(hipMemcpy(Q, dQ, nb, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+extern "C" int feasthip_set_ortho_method(feasthip_handle h, int method) {
+    if (!h) return FEASTHIP_ERROR_INTERNAL;
+    if (method != FEASTHIP_ORTHO_MGS && method != FEASTHIP_ORTHO_CHOLQR_RR) {
+        h->last_error = "set_ortho_method: unknown method";
+        return FEASTHIP_ERROR_FPM;
+    }
+    h->ortho_method = method;
+    return 0;
+}
+
+extern "C" int feasthip_last_ortho(feasthip_handle h, int* method_used, int* stages, int* fell_back, int* rank, int* perm,
+                                   double* rdiag, int n) {
+    if (!h) return FEASTHIP_ERROR_INTERNAL;
+    const auto& o = h->ortho_last;
+    if (method_used) *method_used = o.used;
+    if (stages) *stages = o.stages;
+    if (fell_back) *fell_back = o.fell_back;
+    if (rank) *rank = o.rank;
+    for (int k = 0; k < n; ++k) {
+        if (perm) perm[k] = k < (int)o.perm.size() ? o.perm[k] : -1;
+        if (rdiag) rdiag[k] = k < (int)o.rdiag.size() ? o.rdiag[k] : 0.0;
+    }
     return 0;
 }
 
@@ -2707,6 +2858,10 @@ extern "C" int feasthip_rr_reduce_resident(feasthip_handle h, int64_t m64, doubl
         fast = fh_cholqr::accept(G0, m, ld, 0.0, rank_tol, always_two, dcol) == fh_cholqr::Plan::one_pass;
     }
     if (fast) {
+        fh_ortho_note_reset(h);
+        std::vector<int> ident(m);
+        for (int j = 0; j < m; ++j) ident[j] = j;
+        fh_ortho_note(h, FEASTHIP_ORTHO_USED_CHOLQR, 0, 0, m, ident.data(), nullptr);
         // basis = Q_proj D^-1 (unit columns): its pencil is the equilibrated Gram pair; the orthonormal basis is never formed
         emit(Gh + g2, dcol.data(), m, Aq_host);
         emit(b_id ? Gh : Gh + 2 * g2, dcol.data(), m, Bq_host);
@@ -2723,6 +2878,7 @@ extern "C" int feasthip_rr_reduce_resident(feasthip_handle h, int64_t m64, doubl
     cplx* Out = (cplx*)p;
     cplx* res = nullptr;
     int r = 0;
+    fh_ortho_note_reset(h);
     if ((rc = fh_ortho_panel(h, m, ld, P, Out, rank_tol, 0.0, m, &r, &res))) return rc;
     h->rs_P = nullptr;                            // (the orthonormalisation may have overwritten the projection panel)
     *rank = r;

@@ -8,6 +8,7 @@
 #include <stdlib.h>
 #include "fh_common.hpp"
 #include "fh_kernels.hpp"
+#include "fh_cholqr.hpp"
 
 #define FH_BLOCK 256
 typedef double v4d __attribute__((ext_vector_type(4)));
@@ -244,7 +245,8 @@ void fh_launch_gather_cols(const cplx* src, const int* perm, int count, int N, i
 
 template <int LD>
 __global__ __launch_bounds__(FH_BLOCK) void k_gram_mfma(const cplx* __restrict__ X, const cplx* __restrict__ Y,
-                                                         int N, cplx* __restrict__ partial) {
+                                                         int N, cplx* __restrict__ partial, const int* __restrict__ skip) {
+    if (skip && *skip) return;         // a stage of the staged Cholesky-QR that has nothing left to do
     constexpr int NS = LD / 16;        // stripes (= tiles per stripe)
     constexpr int SUB = 4 / NS;        // row subsets per block (waves per stripe)
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -322,9 +324,9 @@ __global__ __launch_bounds__(FH_BLOCK) void k_gram_mfma(const cplx* __restrict__
 #define FH_GRAM_GROUPS 16
 template <int LD>
 __global__ __launch_bounds__(FH_BLOCK) void k_gram_reduce_groups(const cplx* __restrict__ partial, int nslots,
-                                                                  cplx* __restrict__ gsum) {
+                                                                  cplx* __restrict__ gsum, const int* __restrict__ skip) {
     const int e = blockIdx.x * FH_BLOCK + threadIdx.x;
-    if (e >= LD * LD) return;
+    if (e >= LD * LD || (skip && *skip)) return;
     const int per = (nslots + FH_GRAM_GROUPS - 1) / FH_GRAM_GROUPS;
     const int s0 = blockIdx.y * per, s1 = min(nslots, s0 + per);
     double rr = 0, ii = 0, ri = 0, ir = 0;
@@ -349,9 +351,10 @@ __global__ __launch_bounds__(FH_BLOCK) void k_gram_reduce_groups(const cplx* __r
     o[1] = cmake(ri, ir);
 }
 template <int LD>
-__global__ __launch_bounds__(FH_BLOCK) void k_gram_reduce(const cplx* __restrict__ gsum, int bilinear, cplx* __restrict__ G) {
+__global__ __launch_bounds__(FH_BLOCK) void k_gram_reduce(const cplx* __restrict__ gsum, int bilinear, cplx* __restrict__ G,
+                                                           const int* __restrict__ skip) {
     const int e = blockIdx.x * FH_BLOCK + threadIdx.x;
-    if (e >= LD * LD) return;
+    if (e >= LD * LD || (skip && *skip)) return;
     cplx a[FH_GRAM_GROUPS], b[FH_GRAM_GROUPS];
 #pragma unroll
     for (int g = 0; g < FH_GRAM_GROUPS; ++g) {
@@ -370,19 +373,19 @@ size_t fh_gram_work_elems(int ld) {
 }
 
 template <int LD>
-static void gram_launch(const cplx* X, const cplx* Y, int N, int bilinear, cplx* work, cplx* G, hipStream_t st) {
+static void gram_launch(const cplx* X, const cplx* Y, int N, int bilinear, cplx* work, cplx* G, hipStream_t st, const int* skip) {
     constexpr int sub = 4 / (LD / 16), nslots = FH_GRAM_BLOCKS * sub;
     const int nred = (LD * LD + FH_BLOCK - 1) / FH_BLOCK;
     cplx* gsum = work + (size_t)nslots * LD * LD * 2;
-    hipLaunchKernelGGL((k_gram_mfma<LD>), dim3(FH_GRAM_BLOCKS), dim3(FH_BLOCK), 0, st, X, Y, N, work);
-    hipLaunchKernelGGL((k_gram_reduce_groups<LD>), dim3(nred, FH_GRAM_GROUPS), dim3(FH_BLOCK), 0, st, work, nslots, gsum);
-    hipLaunchKernelGGL((k_gram_reduce<LD>), dim3(nred), dim3(FH_BLOCK), 0, st, gsum, bilinear, G);
+    hipLaunchKernelGGL((k_gram_mfma<LD>), dim3(FH_GRAM_BLOCKS), dim3(FH_BLOCK), 0, st, X, Y, N, work, skip);
+    hipLaunchKernelGGL((k_gram_reduce_groups<LD>), dim3(nred, FH_GRAM_GROUPS), dim3(FH_BLOCK), 0, st, work, nslots, gsum, skip);
+    hipLaunchKernelGGL((k_gram_reduce<LD>), dim3(nred), dim3(FH_BLOCK), 0, st, gsum, bilinear, G, skip);
 }
 void fh_launch_gram(const cplx* X, const cplx* Y, int N, int ld, int bilinear, cplx* work, cplx* G,
-                    hipStream_t st) {
-    if (ld == 16) gram_launch<16>(X, Y, N, bilinear, work, G, st);
-    else if (ld == 32) gram_launch<32>(X, Y, N, bilinear, work, G, st);
-    else gram_launch<64>(X, Y, N, bilinear, work, G, st);
+                    hipStream_t st, const int* skip) {
+    if (ld == 16) gram_launch<16>(X, Y, N, bilinear, work, G, st, skip);
+    else if (ld == 32) gram_launch<32>(X, Y, N, bilinear, work, G, st, skip);
+    else gram_launch<64>(X, Y, N, bilinear, work, G, st, skip);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -390,8 +393,9 @@ void fh_launch_gram(const cplx* X, const cplx* Y, int N, int ld, int bilinear, c
 // ---------------------------------------------------------------------------------------
 template <int LD>
 __global__ __launch_bounds__(FH_BLOCK) void k_small_matmul(const cplx* __restrict__ Q, const cplx* __restrict__ V,
-                                                            int N, cplx* __restrict__ Xout) {
+                                                            int N, cplx* __restrict__ Xout, const int* __restrict__ skip) {
     extern __shared__ cplx sm[];
+    if (skip && *skip) return;
     cplx* Vs = sm;                 // [k][c]  (row k of V contiguous over c) : LD*LD
     cplx* Qs = sm + LD * LD;       // [rows][LD] tile of Q : (256/LD) * LD = 256
     const int t = threadIdx.x;
@@ -419,7 +423,8 @@ __global__ __launch_bounds__(FH_BLOCK) void k_small_matmul(const cplx* __restric
 // FMA and is LDS-bound (85 us for 50 000 x 64 against 25 us of HBM time).
 template <int LD>
 __global__ __launch_bounds__(FH_BLOCK) void k_small_matmul_mfma(const cplx* __restrict__ Q, const cplx* __restrict__ V,
-                                                                 int N, cplx* __restrict__ Xout) {
+                                                                 int N, cplx* __restrict__ Xout, const int* __restrict__ skip) {
+    if (skip && *skip) return;
     constexpr int NS = LD / 16, SUB = 4 / NS, RB = 16 * SUB, KS = LD / 4;
     __shared__ cplx Qs[RB][LD + 1];
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
@@ -465,22 +470,22 @@ __global__ __launch_bounds__(FH_BLOCK) void k_small_matmul_mfma(const cplx* __re
     }
 }
 
-void fh_launch_small_matmul(const cplx* Q, const cplx* V, int N, int ld, cplx* Xout, hipStream_t st) {
+void fh_launch_small_matmul(const cplx* Q, const cplx* V, int N, int ld, cplx* Xout, hipStream_t st, const int* skip) {
     static const bool valu = getenv("FH_SMALL_MATMUL_VALU") != nullptr;
     if (!valu) {
         const int rb = 16 * (4 / (ld / 16));
         const int nb = std::min((N + rb - 1) / rb, 2048);
-        if (ld == 16) hipLaunchKernelGGL((k_small_matmul_mfma<16>), dim3(nb), dim3(FH_BLOCK), 0, st, Q, V, N, Xout);
-        else if (ld == 32) hipLaunchKernelGGL((k_small_matmul_mfma<32>), dim3(nb), dim3(FH_BLOCK), 0, st, Q, V, N, Xout);
-        else hipLaunchKernelGGL((k_small_matmul_mfma<64>), dim3(nb), dim3(FH_BLOCK), 0, st, Q, V, N, Xout);
+        if (ld == 16) hipLaunchKernelGGL((k_small_matmul_mfma<16>), dim3(nb), dim3(FH_BLOCK), 0, st, Q, V, N, Xout, skip);
+        else if (ld == 32) hipLaunchKernelGGL((k_small_matmul_mfma<32>), dim3(nb), dim3(FH_BLOCK), 0, st, Q, V, N, Xout, skip);
+        else hipLaunchKernelGGL((k_small_matmul_mfma<64>), dim3(nb), dim3(FH_BLOCK), 0, st, Q, V, N, Xout, skip);
         return;
     }
     int rpb = FH_BLOCK / ld;
     int nblk = std::min((N + rpb - 1) / rpb, 2048);
     size_t shm = ((size_t)ld * ld + FH_BLOCK) * sizeof(cplx);
-    if (ld == 16) hipLaunchKernelGGL((k_small_matmul<16>), dim3(nblk), dim3(FH_BLOCK), shm, st, Q, V, N, Xout);
-    else if (ld == 32) hipLaunchKernelGGL((k_small_matmul<32>), dim3(nblk), dim3(FH_BLOCK), shm, st, Q, V, N, Xout);
-    else hipLaunchKernelGGL((k_small_matmul<64>), dim3(nblk), dim3(FH_BLOCK), shm, st, Q, V, N, Xout);
+    if (ld == 16) hipLaunchKernelGGL((k_small_matmul<16>), dim3(nblk), dim3(FH_BLOCK), shm, st, Q, V, N, Xout, skip);
+    else if (ld == 32) hipLaunchKernelGGL((k_small_matmul<32>), dim3(nblk), dim3(FH_BLOCK), shm, st, Q, V, N, Xout, skip);
+    else hipLaunchKernelGGL((k_small_matmul<64>), dim3(nblk), dim3(FH_BLOCK), shm, st, Q, V, N, Xout, skip);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -693,4 +698,216 @@ void fh_mgs_run(const fh_mgs_args& a, hipStream_t st) {
     if (a.ld == 16) mgs_run_ld<16>(a, st);
     else if (a.ld == 32) mgs_run_ld<32>(a, st);
     else mgs_run_ld<64>(a, st);
+}
+
+// ---------------------------------------------------------------------------------------
+// Rank-revealing Cholesky-QR (FEASTHIP_ORTHO_CHOLQR_RR): the decision of one stage.  One workgroup holds the ld x ld Gram
+// matrix in LDS (64 KiB of complex128 at ld = 64, half of that when it has no imaginary parts) and runs
+// fh_cholqr::pivoted_stage on it -- equilibration, pivoted Cholesky with the window and the stop rule of k_mgs_pick, inverse
+// of the accepted triangular block -- with every entry's operations in the order of that routine.  A step of the
+// factorisation is a latency chain (pivot search, column scaling, rank-one update: four barriers); the update is spread
+// over the 256 threads with consecutive lanes on consecutive rows of a column, so LDS reads are contiguous 16-byte words
+// plus one broadcast.  Nothing is accumulated across threads: two runs on the same input give the same bits.
+// State words: fh_kernels.hpp (FH_RR_*).  The launches that follow read the flags and R^-1 from device memory; the host
+// reads the state once, after the last queued stage.
+// ---------------------------------------------------------------------------------------
+struct rr_small {            // per-column state in LDS
+    double d[FH_MAX_LD], w[FH_MAX_LD], key[FH_MAX_LD], rd[FH_MAX_LD], rid[FH_MAX_LD];
+    int alive[FH_MAX_LD], picked[FH_MAX_LD], pos[FH_MAX_LD], ord[FH_MAX_LD];
+};
+
+template <class S> __device__ inline S rr_load(cplx v) {
+    if constexpr (std::is_same_v<S, double>) return v.x;
+    else return v;
+}
+template <class S> __device__ inline cplx rr_store(const S& v) {
+    if constexpr (std::is_same_v<S, double>) return cmake(v, 0.0);
+    else return v;
+}
+
+template <int LD, class S>
+__device__ void pchol_body(S* Gs, rr_small& sm, const cplx* __restrict__ G, int m, int refine, double window, double thr,
+                           double ref_scale, int rank, int nfix, int* istate, double* dstate, cplx* __restrict__ Rinv) {
+    using namespace fh_cholqr;
+    const int t = threadIdx.x, lane = t & 63;
+    for (int e = t; e < LD * LD; e += FH_BLOCK) Gs[e] = rr_load<S>(G[e]);
+    if (refine && t < nfix) sm.rd[t] = dstate[2 + rank + t];
+    __syncthreads();
+    double dref = 1.0, r11 = dstate[0];
+    if (!refine) {
+        if (t < LD && sm.alive[t]) {
+            const double g = re(Gs[t * LD + t]);
+            sm.d[t] = g > 0.0 ? sqrt(g) : 0.0;
+        }
+        __syncthreads();
+        dref = 0.0;
+        for (int j = 0; j < LD; ++j) if (sm.alive[j]) dref = fmax(dref, sm.d[j]);
+        for (int e = t; e < LD * LD; e += FH_BLOCK) {
+            const int i = e % LD, j = e / LD;
+            if (sm.alive[i] && sm.alive[j] && sm.d[i] > 0.0 && sm.d[j] > 0.0) Gs[e] = div_re(Gs[e], sm.d[i] * sm.d[j]);
+        }
+        if (t < LD && sm.alive[t]) sm.w[t] = sm.d[t] > 0.0 ? (sm.d[t] / dref) * (sm.d[t] / dref) : 0.0;
+        if (r11 < 0.0) r11 = fmax(dref, ref_scale);
+        __syncthreads();
+    }
+    const double stop = thr * r11;
+    if (t < LD && sm.alive[t]) sm.key[t] = sm.w[t] * re(Gs[t * LD + t]);
+    __syncthreads();
+    double key0 = 0.0;
+    bool done = false, fail = false;
+    int k = 0;
+    for (;; ++k) {
+        int p = -1;
+        double best = 0.0;
+        if (refine) {
+            if (k < nfix) { p = k; best = sm.key[k]; }
+        } else {        // every wave finds the same pivot: largest key, lowest index among equals
+            int cand = lane < LD && sm.alive[lane] && !sm.picked[lane];
+            double v = cand ? sm.key[lane] : 0.0;
+            int idx = lane;
+            for (int off = 32; off >= 1; off >>= 1) {
+                const double v2 = __shfl_xor(v, off);
+                const int i2 = __shfl_xor(idx, off), c2 = __shfl_xor(cand, off);
+                if (c2 && (!cand || v2 > v || (v2 == v && i2 < idx))) { v = v2; idx = i2; cand = 1; }
+            }
+            if (cand) { p = idx; best = v; }
+        }
+        if (p < 0) break;
+        const double rkk = dref * sqrt(best);
+        if (refine) {
+            if (!(best > 0.0)) { fail = true; break; }
+        } else {
+            if (!(rkk > stop) || rkk == 0.0) { done = true; break; }
+            if (k == 0) key0 = best;
+            else if (!(best > window * key0)) break;
+        }
+        const double r = sqrt(re(Gs[p * LD + p]));
+        __syncthreads();                                   // every thread has read the pivot and the keys
+        if (t < LD && t != p && sm.alive[t] && !sm.picked[t]) Gs[p * LD + t] = div_re(Gs[p * LD + t], r);
+        if (t == p) Gs[p * LD + p] = from_re<S>(r);
+        __syncthreads();
+        if (t == 0) { sm.ord[k] = p; sm.rd[k] = refine ? sm.rd[k] * r : rkk; sm.pos[p] = k; }
+        {
+            const int i = t % LD;
+            if (i != p && sm.alive[i] && !sm.picked[i]) {
+                const S li = Gs[p * LD + i];
+                for (int j = t / LD; j < LD; j += FH_BLOCK / LD)
+                    if (j != p && sm.alive[j] && !sm.picked[j]) Gs[j * LD + i] = sub(Gs[j * LD + i], mul(li, conj(Gs[p * LD + j])));
+            }
+        }
+        __syncthreads();
+        if (t == p) sm.picked[p] = 1;
+        if (t < LD && t != p && sm.alive[t] && !sm.picked[t]) sm.key[t] = sm.w[t] * re(Gs[t * LD + t]);
+        __syncthreads();
+    }
+    if (fail || (!refine && !done && k == 0)) {            // a stage that accepts nothing: the caller's Gram-Schmidt decides
+        if (t == 0) { istate[FH_RR_FAIL] = 1; istate[FH_RR_DONE] = 1; istate[FH_RR_SKIP] = 1; }
+        return;
+    }
+    // inverse of the triangular factor, one column per thread: R'[a][c] = conj(Gs(ord[c], ord[a])) for a < c; the inverse
+    // goes to the entries (ord[a], ord[b]), a < b, which the factorisation no longer needs
+    if (t < k) {
+        const int ob = sm.ord[t];
+        sm.rid[t] = 1.0 / re(Gs[ob * LD + ob]);
+        for (int a = t - 1; a >= 0; --a) {
+            const int oa = sm.ord[a];
+            S sum{};
+            for (int c = a + 1; c <= t; ++c) {
+                const S ric = c == t ? from_re<S>(sm.rid[t]) : Gs[ob * LD + sm.ord[c]];
+                sum = add(sum, mul(conj(Gs[oa * LD + sm.ord[c]]), ric));
+            }
+            Gs[ob * LD + oa] = div_re(neg(sum), re(Gs[oa * LD + oa]));
+        }
+    }
+    __syncthreads();
+    const int col0 = refine ? rank : 0;
+    for (int e = t; e < LD * LD; e += FH_BLOCK) {
+        const int i = e % LD, b = e / LD - col0, a = sm.pos[i];
+        cplx val = cmake(0, 0);
+        if (b >= 0 && b < k && a >= 0 && a <= b) {
+            S v = a == b ? from_re<S>(sm.rid[b]) : Gs[sm.ord[b] * LD + i];
+            if (!refine) v = div_re(v, sm.d[i]);
+            val = rr_store<S>(v);
+        }
+        Rinv[e] = val;
+    }
+    if (t < k) {
+        dstate[2 + rank + t] = sm.rd[t];
+        if (!refine) istate[FH_RR_PERM + rank + t] = sm.ord[t];
+    }
+    if (t == 0) {
+        if (!refine) {
+            dstate[0] = r11;
+            istate[FH_RR_NACC] = k;
+            if (done) istate[FH_RR_DONE] = 1;
+        } else {
+            istate[FH_RR_RANK] = rank + k;
+            istate[FH_RR_STAGES] += 1;
+            if (rank + k >= m) istate[FH_RR_DONE] = 1;
+        }
+    }
+}
+
+template <int LD>
+__global__ __launch_bounds__(FH_BLOCK) void k_pchol_stage(const cplx* __restrict__ G, int m, int refine, double window, double thr,
+                                                           double ref_scale, int* istate, double* dstate, cplx* __restrict__ Rinv) {
+    extern __shared__ cplx rr_dyn[];         // LD x LD
+    __shared__ rr_small sm;
+    const int t = threadIdx.x;
+    if (istate[FH_RR_SKIP]) return;
+    if (!refine && istate[FH_RR_DONE]) {     // decided by an earlier stage: everything queued behind this launch returns at once
+        if (t == 0) istate[FH_RR_SKIP] = 1;
+        return;
+    }
+    const int rank = istate[FH_RR_RANK], nfix = istate[FH_RR_NACC];
+    if (t < LD) {
+        sm.alive[t] = refine ? t < nfix : t < m;
+        sm.picked[t] = 0; sm.pos[t] = -1;
+        sm.d[t] = 1.0; sm.w[t] = 1.0; sm.key[t] = -1.0; sm.rd[t] = 0.0; sm.rid[t] = 0.0; sm.ord[t] = 0;
+    }
+    __syncthreads();
+    if (!refine && t < rank && t < LD) sm.alive[istate[FH_RR_PERM + t]] = 0;
+    __syncthreads();
+    int bad = 0, imag = 0;
+    for (int e = t; e < LD * LD; e += FH_BLOCK) {
+        if (!sm.alive[e % LD] || !sm.alive[e / LD]) continue;
+        const cplx v = G[e];
+        bad |= !(isfinite(v.x) && isfinite(v.y));
+        imag |= v.y != 0.0;
+    }
+    bad = __syncthreads_or(bad);
+    imag = __syncthreads_or(imag);
+    if (bad) {
+        if (t == 0) { istate[FH_RR_FAIL] = 1; istate[FH_RR_DONE] = 1; istate[FH_RR_SKIP] = 1; }
+        return;
+    }
+    if (imag) pchol_body<LD, cplx>(rr_dyn, sm, G, m, refine, window, thr, ref_scale, rank, nfix, istate, dstate, Rinv);
+    else pchol_body<LD, double>((double*)rr_dyn, sm, G, m, refine, window, thr, ref_scale, rank, nfix, istate, dstate, Rinv);
+}
+
+__global__ void k_rr_init(int* istate, double* dstate, int ld) {
+    const int t = threadIdx.x;
+    if (t < FH_RR_PERM + ld) istate[t] = t >= FH_RR_PERM ? -1 : 0;
+    if (t < 2 + ld) dstate[t] = t == 0 ? -1.0 : 0.0;
+}
+void fh_launch_rr_init(int* istate, double* dstate, int ld, hipStream_t st) {
+    hipLaunchKernelGGL(k_rr_init, dim3(1), dim3(128), 0, st, istate, dstate, ld);
+}
+
+template <int LD>
+static void pchol_launch(const cplx* G, int m, int refine, double window, double thr, double ref_scale, int* istate, double* dstate,
+                         cplx* Rinv, hipStream_t st) {
+    const size_t dyn = (size_t)LD * LD * sizeof(cplx);
+    static bool asked = false;
+    if (!asked) {        // 64 KiB of dynamic LDS at LD = 64 on top of the static state: above the default limit
+        asked = true;
+        (void)hipFuncSetAttribute((const void*)k_pchol_stage<LD>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);
+    }
+    hipLaunchKernelGGL((k_pchol_stage<LD>), dim3(1), dim3(FH_BLOCK), dyn, st, G, m, refine, window, thr, ref_scale, istate, dstate, Rinv);
+}
+void fh_launch_pchol_stage(const cplx* G, int m, int ld, int refine, double window, double thr, double ref_scale, int* istate,
+                           double* dstate, cplx* Rinv, hipStream_t st) {
+    if (ld == 16) pchol_launch<16>(G, m, refine, window, thr, ref_scale, istate, dstate, Rinv, st);
+    else if (ld == 32) pchol_launch<32>(G, m, refine, window, thr, ref_scale, istate, dstate, Rinv, st);
+    else pchol_launch<64>(G, m, refine, window, thr, ref_scale, istate, dstate, Rinv, st);
 }

@@ -1,6 +1,7 @@
 // fh_cholqr.hpp -- host half of the Cholesky-QR orthonormalisation (pure C++17, no HIP): the small dense maths that decides
 // the rank of every FEAST refinement loop's subspace.  fh_ortho_panel and feasthip_rr_reduce_resident (fh_api.hip) both take
-// their decision from accept() below; tests/host_cholqr_harness.cpp checks this file on the CPU under sanitizers.
+// their decision from accept() below; tests/host_cholqr_harness.cpp and tests/host_cholqr_rr_harness.cpp check this file on
+// the CPU under sanitizers.
 //
 // Every routine is one template instantiated for a real scalar (double) and a complex one (any struct {double x, y}, such as
 // fh_common.hpp's cplx).  A Gram matrix without imaginary parts (the real projection of a real-symmetric pencil) takes the
@@ -13,23 +14,29 @@
 #include <utility>
 #include <vector>
 
+#if defined(__HIPCC__)
+#define FH_CQ_HD __host__ __device__
+#else
+#define FH_CQ_HD
+#endif
+
 namespace fh_cholqr {
 
-inline double re(double a) { return a; }
-inline double conj(double a) { return a; }
-inline double neg(double a) { return -a; }
-inline double add(double a, double b) { return a + b; }
-inline double sub(double a, double b) { return a - b; }
-inline double mul(double a, double b) { return a * b; }
-inline double div_re(double a, double r) { return a / r; }
-template <class C> inline double re(const C& a) { return a.x; }
-template <class C> inline C conj(const C& a) { return C{a.x, -a.y}; }
-template <class C> inline C neg(const C& a) { return C{-a.x, -a.y}; }
-template <class C> inline C add(const C& a, const C& b) { return C{a.x + b.x, a.y + b.y}; }
-template <class C> inline C sub(const C& a, const C& b) { return C{a.x - b.x, a.y - b.y}; }
-template <class C> inline C mul(const C& a, const C& b) { return C{a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x}; }
-template <class C> inline C div_re(const C& a, double r) { const double s = 1.0 / r; return C{a.x * s, a.y * s}; }
-template <class S> inline S from_re(double v) {
+FH_CQ_HD inline double re(double a) { return a; }
+FH_CQ_HD inline double conj(double a) { return a; }
+FH_CQ_HD inline double neg(double a) { return -a; }
+FH_CQ_HD inline double add(double a, double b) { return a + b; }
+FH_CQ_HD inline double sub(double a, double b) { return a - b; }
+FH_CQ_HD inline double mul(double a, double b) { return a * b; }
+FH_CQ_HD inline double div_re(double a, double r) { return a / r; }
+template <class C> FH_CQ_HD inline double re(const C& a) { return a.x; }
+template <class C> FH_CQ_HD inline C conj(const C& a) { return C{a.x, -a.y}; }
+template <class C> FH_CQ_HD inline C neg(const C& a) { return C{-a.x, -a.y}; }
+template <class C> FH_CQ_HD inline C add(const C& a, const C& b) { return C{a.x + b.x, a.y + b.y}; }
+template <class C> FH_CQ_HD inline C sub(const C& a, const C& b) { return C{a.x - b.x, a.y - b.y}; }
+template <class C> FH_CQ_HD inline C mul(const C& a, const C& b) { return C{a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x}; }
+template <class C> FH_CQ_HD inline C div_re(const C& a, double r) { const double s = 1.0 / r; return C{a.x * s, a.y * s}; }
+template <class S> FH_CQ_HD inline S from_re(double v) {
     if constexpr (std::is_same_v<S, double>) return v;
     else return S{v, 0.0};
 }
@@ -143,6 +150,113 @@ template <class C> Plan accept(std::vector<C>& G, int m, int ld, double ref_scal
     const double ratio = gram_ratio(G, m, ld);
     if (!(ratio > 1e-10) || !((dmin / dmax) * std::sqrt(ratio) > 1e3 * rank_tol)) return Plan::reject;
     return ratio > 1e-2 && !always_two ? Plan::one_pass : Plan::two_pass;
+}
+
+// ---- one stage of the rank-revealing Cholesky-QR (FEASTHIP_ORTHO_CHOLQR_RR) ---------------------------------------------------
+// The pivots of a pivoted Cholesky of G = X^H X are the squared R_kk of the column-pivoted QR of X, but the rank threshold of
+// _feast_qr_compress! (rank_tol ~ sqrt(eps), src/core/feast_aux.jl:117-124) sits at pivot ratio 1e-16, where G has no digits
+// left.  So a stage only accepts the leading pivots that stay inside `window` (a ratio of squared pivots) of its first one;
+// the caller orthonormalises those columns, projects them out of the rest and runs the next stage on the Gram matrix of the
+// remainder, which is accurate relative to its own size.  k_pchol_stage (fh_blockops.hip) is this routine on one workgroup:
+// the same operations on every entry in the same order, spread over threads.
+//
+// G (ld x ld, column-major) is overwritten.  decided[j] != 0: column j was accepted by an earlier stage and is ignored.
+//   refine == false  equilibrate the undecided block as accept() does, then pivoted Cholesky: the next pivot is the column
+//                    of largest remaining norm, |R_kk| = d_p sqrt(G'_pp).  Stops for good (done) at the first
+//                    |R_kk| <= stop -- the rule of k_mgs_pick -- and for this stage at the first pivot with
+//                    R_kk^2 <= window * (the stage's first R_kk^2).  *r11 < 0 on entry: first stage, *r11 = max(first |R_kk|,
+//                    ref_scale) and stop = thr * *r11 from here on.
+//   refine == true   the second Cholesky-QR pass of the columns a stage accepted: G is the Gram matrix of those nfix columns
+//                    (already nearly orthonormal), no pivoting, no scaling; rdiag[k] is multiplied by the correction R2_kk.
+// ord[k] / rdiag[k]: column and |R_kk| of the k-th accepted pivot.  Rinv (ld x ld, zero padded): X Rinv has the accepted
+// columns, orthonormalised, at columns col0, col0 + 1, ... (the permutation is folded in: row ord[a] of Rinv holds row a of
+// the inverse of the triangular factor).
+struct Stage { int nacc = 0; bool done = false, fail = false; };
+
+template <class S> inline bool finite_s(const S& a) {
+    if constexpr (std::is_same_v<S, double>) return std::isfinite(a);
+    else return std::isfinite(a.x) && std::isfinite(a.y);
+}
+
+template <class S>
+Stage pivoted_stage(std::vector<S>& G, int m, int ld, double window, double thr, double ref_scale, double* r11,
+                    const int* decided, bool refine, int nfix, int col0, int* ord, double* rdiag, std::vector<S>& Rinv) {
+    Stage out;
+    auto at = [&](int i, int j) -> S& { return G[(size_t)j * ld + i]; };
+    std::vector<int> alive(ld, 0), picked(ld, 0), pos(ld, -1);
+    std::vector<double> d(ld, 1.0), w(ld, 1.0), key(ld, -1.0);
+    for (int j = 0; j < ld; ++j) alive[j] = refine ? j < nfix : (j < m && !decided[j]);
+    Rinv.assign((size_t)ld * ld, S{});
+    for (int j = 0; j < ld; ++j)
+        for (int i = 0; i < ld; ++i)
+            if (alive[i] && alive[j] && !finite_s(at(i, j))) { out.fail = out.done = true; return out; }
+    double dref = 0.0;
+    if (!refine) {
+        for (int j = 0; j < ld; ++j) {
+            if (!alive[j]) continue;
+            const double g = re(at(j, j));
+            d[j] = g > 0.0 ? std::sqrt(g) : 0.0;
+            dref = std::max(dref, d[j]);
+        }
+        for (int j = 0; j < ld; ++j)
+            for (int i = 0; i < ld; ++i)
+                if (alive[i] && alive[j] && d[i] > 0.0 && d[j] > 0.0) at(i, j) = div_re(at(i, j), d[i] * d[j]);
+        for (int j = 0; j < ld; ++j) if (alive[j]) w[j] = d[j] > 0.0 ? (d[j] / dref) * (d[j] / dref) : 0.0;
+        if (*r11 < 0.0) *r11 = std::max(dref, ref_scale);
+    } else {
+        dref = 1.0;
+    }
+    const double stop = thr * *r11;
+    for (int j = 0; j < ld; ++j) if (alive[j]) key[j] = w[j] * re(at(j, j));
+    double key0 = 0.0;
+    int k = 0;
+    for (;; ++k) {
+        int p = -1;
+        for (int j = 0; j < ld; ++j) {
+            if (!alive[j] || picked[j]) continue;
+            if (refine) { p = j; break; }
+            if (p < 0 || key[j] > key[p]) p = j;       // ties: the lowest index
+        }
+        if (p < 0) break;
+        const double best = key[p], rkk = dref * std::sqrt(best);
+        if (refine) {
+            if (!(best > 0.0)) { out.fail = out.done = true; return out; }
+        } else {
+            if (!(rkk > stop) || rkk == 0.0) { out.done = true; break; }
+            if (k == 0) key0 = best;
+            else if (!(best > window * key0)) break;
+        }
+        const double r = std::sqrt(re(at(p, p)));
+        ord[k] = p;
+        rdiag[k] = refine ? rdiag[k] * r : rkk;
+        picked[p] = 1;
+        pos[p] = k;
+        for (int i = 0; i < ld; ++i) if (alive[i] && !picked[i]) at(i, p) = div_re(at(i, p), r);
+        at(p, p) = from_re<S>(r);
+        for (int j = 0; j < ld; ++j) {
+            if (!alive[j] || picked[j]) continue;
+            for (int i = 0; i < ld; ++i)
+                if (alive[i] && !picked[i]) at(i, j) = sub(at(i, j), mul(at(i, p), conj(at(j, p))));
+            key[j] = w[j] * re(at(j, j));
+        }
+    }
+    out.nacc = k;
+    // inverse of the triangular factor R'[a][b] = conj(L_a[ord[b]]) (a < b), R'[a][a] = r_a, column by column
+    std::vector<S> Ri((size_t)k * k, S{});
+    for (int b = 0; b < k; ++b) {
+        Ri[(size_t)b * k + b] = from_re<S>(1.0 / re(at(ord[b], ord[b])));
+        for (int a = b - 1; a >= 0; --a) {
+            S sum{};
+            for (int c = a + 1; c <= b; ++c) sum = add(sum, mul(conj(at(ord[c], ord[a])), Ri[(size_t)b * k + c]));
+            Ri[(size_t)b * k + a] = div_re(neg(sum), re(at(ord[a], ord[a])));
+        }
+    }
+    for (int b = 0; b < k; ++b)
+        for (int a = 0; a <= b; ++a) {
+            if (col0 + b >= ld) continue;
+            Rinv[(size_t)(col0 + b) * ld + ord[a]] = refine ? Ri[(size_t)b * k + a] : div_re(Ri[(size_t)b * k + a], d[ord[a]]);
+        }
+    return out;
 }
 
 // Hermitian part (G + G^H) / 2 in place (r x r, column-major): _feast_hermitian_part!, src/core/feast_aux.jl:84-92

@@ -202,6 +202,9 @@ struct feasthip_ctx {
     std::vector<int> band_valid;
     std::vector<cplx> band_z;
     void* mf = nullptr;           // multifrontal plan of the sparse direct solver (fh_dense.hip: fh_mf_state), band_plan == 3
+    // feasthip_set_ortho_method / feasthip_last_ortho: what rejected panels take, and what the last orthonormalisation did
+    int ortho_method = 0;         // FEASTHIP_ORTHO_MGS | FEASTHIP_ORTHO_CHOLQR_RR
+    struct { int panels = 0, used = 0, stages = 0, fell_back = 0, rank = 0; std::vector<int> perm; std::vector<double> rdiag; } ortho_last;
     std::vector<int> col_mask;    // feasthip_set_column_mask: columns with 0 are not iterated by the Krylov solvers
     int poisoned = 0;             // a Krylov deadline / queue fault returned with kernels possibly still queued: every later call fails fast
     int mask_live = 0;            // set only while a contour_apply call runs: the mask is one-shot and never reaches shifted_solve

@@ -282,13 +282,15 @@ void fh_launch_dense_op(const fh_dense_op_args& a, int ld, int nblk, hipStream_t
 }
 
 __global__ __launch_bounds__(FH_BLOCK) void k_axpy_cols(cplx* __restrict__ R, const cplx* __restrict__ X,
-                                                         const cplx* __restrict__ lam, size_t total, int ld) {
+                                                         const cplx* __restrict__ lam, size_t total, int ld,
+                                                         const int* __restrict__ skip) {
+    if (skip && *skip) return;
     const cplx l = lam[threadIdx.x % ld];
     for (size_t e = (size_t)blockIdx.x * FH_BLOCK + threadIdx.x; e < total; e += (size_t)gridDim.x * FH_BLOCK)
         R[e] = csub(R[e], cmul(l, X[e]));
 }
-void fh_launch_axpy_cols(cplx* R, const cplx* X, const cplx* lam, int N, int ld, hipStream_t st) {
-    hipLaunchKernelGGL(k_axpy_cols, dim3(fh_vec_nblk(N, ld)), dim3(FH_BLOCK), 0, st, R, X, lam, (size_t)N * ld, ld);
+void fh_launch_axpy_cols(cplx* R, const cplx* X, const cplx* lam, int N, int ld, hipStream_t st, const int* skip) {
+    hipLaunchKernelGGL(k_axpy_cols, dim3(fh_vec_nblk(N, ld)), dim3(FH_BLOCK), 0, st, R, X, lam, (size_t)N * ld, ld, skip);
 }
 
 // ---------------------------------------------------------------------------------------

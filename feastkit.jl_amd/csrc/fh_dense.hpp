@@ -19,7 +19,7 @@ int fh_dense_op_nblk(int N);
 void fh_launch_dense_op(const fh_dense_op_args& a, int ld, int nblk, hipStream_t st);
 
 // R -= X diag(lam)
-void fh_launch_axpy_cols(cplx* R, const cplx* X, const cplx* lam, int N, int ld, hipStream_t st);
+void fh_launch_axpy_cols(cplx* R, const cplx* X, const cplx* lam, int N, int ld, hipStream_t st, const int* skip = nullptr);
 
 // Factor (cached per local node when h->cache_factors) and solve all local nodes:
 //   Y[e] = (z_e B - A)^{-1} RHS     RHS: one shared panel; Y: node-strided panels

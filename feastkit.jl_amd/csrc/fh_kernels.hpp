@@ -188,10 +188,11 @@ void fh_launch_to_panel_real(const double* src, int64_t lds, int N, int m, cplx*
 void fh_launch_accumulate(const cplx* X, size_t node_stride, const cplx* w, int nodes, int N, int ld, const cplx* extra,
                           cplx* dst, int real_part, hipStream_t st);
 // G (ld x ld, column-major, ldg = ld) = X^H Y (bilinear=0) or X^T Y (bilinear=1); f64 MFMA.
-// work: at least fh_gram_work_elems(ld) cplx.
+// work: at least fh_gram_work_elems(ld) cplx.  skip (here and below): device word; non-zero = the launch does nothing (the
+// staged Cholesky-QR queues a fixed number of stages and the device decides how many run).
 size_t fh_gram_work_elems(int ld);
 void fh_launch_gram(const cplx* X, const cplx* Y, int N, int ld, int bilinear, cplx* work, cplx* G,
-                    hipStream_t st);
+                    hipStream_t st, const int* skip = nullptr);
 // per-column dots: out[c] = <U[:,c], V[:,c]>; work: nblk*ld cplx
 int fh_vec_nblk(int N, int ld);
 int fh_kry_nblk(int N, int ld, int nodes);
@@ -201,7 +202,7 @@ void fh_launch_scale_cols(cplx* X, const cplx* s, int N, int ld, hipStream_t st)
 // X[:, c] /= sqrt(dots[c].x) for c < M, on the device (dots: per-column <x, x> from fh_launch_dot_cols)
 void fh_launch_normalize_cols(cplx* X, const cplx* dots, int N, int ld, int M, hipStream_t st);
 // Xout = Q * V   (V: ld x ld column-major on device, zero padded)
-void fh_launch_small_matmul(const cplx* Q, const cplx* V, int N, int ld, cplx* Xout, hipStream_t st);
+void fh_launch_small_matmul(const cplx* Q, const cplx* V, int N, int ld, cplx* Xout, hipStream_t st, const int* skip = nullptr);
 // dst[:,k] = src[:,perm[k]] for k < count else 0
 void fh_launch_gather_cols(const cplx* src, const int* perm, int count, int N, int ld, cplx* dst, hipStream_t st);
 
@@ -223,6 +224,15 @@ struct fh_mgs_args {
     int big_dim = 0;                           // total column count of the wider matrix (eps*max(N,M0) term)
 };
 void fh_mgs_run(const fh_mgs_args& a, hipStream_t st);
+
+// Rank-revealing Cholesky-QR, one stage's decision on one workgroup (k_pchol_stage; host restatement: fh_cholqr::pivoted_stage).
+// istate: int[FH_RR_PERM + ld], dstate: double[2 + ld] = {R11 (< 0: not set), -, |R_kk|[ld]}
+enum { FH_RR_RANK = 0, FH_RR_DONE = 1, FH_RR_SKIP = 2, FH_RR_FAIL = 3, FH_RR_NACC = 4, FH_RR_STAGES = 5, FH_RR_PERM = 8 };
+void fh_launch_rr_init(int* istate, double* dstate, int ld, hipStream_t st);
+// refine = 0: Gram matrix of the working panel -> pivots of this stage; refine = 1: Gram matrix of the accepted columns after
+// the first pass -> their second pass.  Rinv: ld x ld, zero padded, permutation (refine = 0) / output column offset (1) folded in.
+void fh_launch_pchol_stage(const cplx* G, int m, int ld, int refine, double window, double thr, double ref_scale, int* istate,
+                           double* dstate, cplx* Rinv, hipStream_t st);
 
 // dense kernels ---------------------------------------------------------------------------
 struct fh_dense;

@@ -397,6 +397,31 @@ class HipEngine:
         self._chk(self.lib.feasthip_resident_export(self.h, int(which), int(ncols), C.c_void_p(out.data_ptr())))
         return out[:int(ncols)]
 
+    ORTHO_METHODS = {"mgs": 0, "cholqr_rr": 1}
+    ORTHO_USED = {0: "mgs", 1: "cholqr_rr", 2: "cholqr"}
+
+    def set_ortho_method(self, method):
+        """What a panel the Cholesky-QR fast path rejects takes: "mgs" (column-pivoted Gram-Schmidt, the default) or
+        "cholqr_rr" (staged rank-revealing Cholesky-QR); feasthip_set_ortho_method.  Persists on the engine."""
+        code = self.ORTHO_METHODS.get(method, method) if isinstance(method, str) else method
+        if isinstance(code, str):
+            raise ValueError(f"ortho must be one of {sorted(self.ORTHO_METHODS)}, not {method!r}")
+        self._chk(self.lib.feasthip_set_ortho_method(self.h, int(code)))
+
+    def last_ortho(self, n=0):
+        """The last orthonormalisation (feasthip_last_ortho): method used ("cholqr" = the fast path), stages, fell_back, rank;
+        with n > 0 also the first n entries of the pivot order and of |R_kk|."""
+        used, stages, fell, rank = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0)
+        perm = np.full(max(1, n), -1, dtype=np.int32)
+        rdiag = np.zeros(max(1, n), dtype=np.float64)
+        self._chk(self.lib.feasthip_last_ortho(self.h, C.byref(used), C.byref(stages), C.byref(fell), C.byref(rank),
+                                               _np_ptr(perm), _np_ptr(rdiag), int(n)))
+        out = {"method": self.ORTHO_USED.get(used.value, used.value), "stages": stages.value, "fell_back": fell.value,
+               "rank": rank.value}
+        if n > 0:
+            out["perm"], out["rdiag"] = perm[:n].copy(), rdiag[:n].copy()
+        return out
+
     def orthonormalize(self, dQ, m, rank_tol):
         self._sync_stream()
         rank = C.c_int(0)

@@ -602,13 +602,46 @@ class _LoopRecord:
         return FeastResult(lam.copy(), q, M, res.copy(), info, self.epsout, loop, {} if stats is None else stats)
 
 
+ORTHO_METHODS = ("mgs", "cholqr_rr")
+
+
+def check_ortho(ortho):
+    """Host-only validation of the ``ortho`` keyword."""
+    if ortho not in ORTHO_METHODS:
+        raise ValueError(f"ortho must be one of {ORTHO_METHODS}, not {ortho!r}")
+    return ortho
+
+
+@contextlib.contextmanager
+def _ortho_scope(engine, ortho, stats):
+    """The drivers' ``ortho`` keyword as a context: the engine orthonormalises rank-deficient panels by that method inside
+    and by the default on every way out.  ``stats["ortho"]`` gets one entry per loop (_note_ortho)."""
+    check_ortho(ortho)
+    if not hasattr(engine, "set_ortho_method"):
+        if ortho != "mgs":
+            raise ValueError(f"ortho={ortho!r}: this engine has no choice of orthonormalisation")
+        yield
+        return
+    stats["ortho"] = []
+    engine.set_ortho_method(ortho)
+    try:
+        yield
+    finally:
+        engine.set_ortho_method("mgs")
+
+
+def _note_ortho(engine, stats):
+    if "ortho" in stats and hasattr(engine, "last_ortho"):
+        stats["ortho"].append(engine.last_ortho())
+
+
 def feast_hip_hermitian(engine, A, B, Emin, Emax, M0, fpm, *, freeze_guards_after=None, reduced_solver="host",
                         solver="direct", solver_tol=0.0,
                         solver_maxiter=500, solver_restart=30, warm_start=True, inner_rtol=None,
                         real_projection=None, group=None, Q0=None, seed=20260515, contour=None, trace=None,
                         preloaded=False, node_assignment="block", inner_precision=64, column_groups=1,
                         spurious_filter=True, contour_policy=None, eps_floor=0.0, abort_check=None, resident_panels=True,
-                        direct_nodes=None):
+                        direct_nodes=None, ortho="mgs"):
     """Variant A on the :hip engine.  Returns FeastResult (complex Ritz vectors, like
     _feast_dense_complex_hermitian; real-symmetric callers take real.(q) as the reference
     does, src/dense/feast_dense.jl:372-387).
@@ -722,8 +755,8 @@ def feast_hip_hermitian(engine, A, B, Emin, Emax, M0, fpm, *, freeze_guards_afte
     # one BLAS thread for the whole solve; the `with` releases the process-wide limit on every way out, including an
     # exception from the engine inside the loop (FeastHipError, a poisoned handle)
     import scipy.sparse as _sp
-    with small_lapack(), _direct_nodes_scope(engine, direct_nodes, len(Zne), _sp.issparse(A), solver, M0, world, stats,
-                                             inner_precision) as dn:
+    with small_lapack(), _ortho_scope(engine, ortho, stats), \
+            _direct_nodes_scope(engine, direct_nodes, len(Zne), _sp.issparse(A), solver, M0, world, stats, inner_precision) as dn:
         for loop_idx in range(0, maxloop + 1):
             loop_count = loop_idx
             # -- sweep
@@ -779,6 +812,7 @@ def feast_hip_hermitian(engine, A, B, Emin, Emax, M0, fpm, *, freeze_guards_afte
             else:
                 rank_q = engine.orthonormalize(dP, active, SQRT_EPS)       # _feast_qr_compress!
                 ph["ortho"] += tick() - t_
+            _note_ortho(engine, stats)
             if rank_q == 0:
                 info = int(FeastError.Feast_ERROR_NO_CONVERGENCE)
                 break
@@ -907,9 +941,11 @@ def feast_hip_estimate(engine, A, B, Zne, Wne, weight_scale, m, *, general=False
 
 def feast_hip_general(engine, A, B, Emid, r, M0, fpm, *, solver="direct", solver_tol=0.0, solver_maxiter=500,
                       solver_restart=30, group=None, Q0=None, seed=20260515, inner_precision=64, contour=None, eps_floor=0.0,
-                      direct_nodes=None):
+                      direct_nodes=None, ortho="mgs"):
     """Variant C (general, full contour, no factor 2, no orthonormalisation, residual
-    without B): src/kernel/feast_kernel.jl:752-950 driven as in src/dense/feast_dense.jl:468-584."""
+    without B): src/kernel/feast_kernel.jl:752-950 driven as in src/dense/feast_dense.jl:468-584.
+    ``ortho`` is checked and set on the engine for the solve like in the other drivers; this variant never orthonormalises
+    its subspace, so ``stats["ortho"]`` stays empty."""
     N = A.shape[0]
     feastdefault(fpm)
     info = _check_circle_input(N, M0, r)
@@ -931,7 +967,8 @@ def feast_hip_general(engine, A, B, Emid, r, M0, fpm, *, solver="direct", solver
     stats = {"krylov_iterations": 0, "factorizations": 0, "solve_seconds": 0.0}
     epsout, eps_hist = math.inf, []
     import scipy.sparse as _sp
-    with _direct_nodes_scope(engine, direct_nodes, len(Zne), _sp.issparse(A), solver, M0, world, stats, inner_precision) as dn:
+    with _ortho_scope(engine, ortho, stats), \
+            _direct_nodes_scope(engine, direct_nodes, len(Zne), _sp.issparse(A), solver, M0, world, stats, inner_precision) as dn:
         while True:
             if inner_precision == 32:
                 # inexact FEAST: the complex64 solves are refined only as far as the current outer residual needs
@@ -971,7 +1008,8 @@ def feast_hip_general(engine, A, B, Emid, r, M0, fpm, *, solver="direct", solver
 
 
 def feast_hip_complex_symmetric(engine, A, B, Emid, r, M0, fpm, *, solver="direct", solver_tol=0.0,
-                                solver_maxiter=500, solver_restart=30, group=None, Q0=None, seed=20260515, direct_nodes=None):
+                                solver_maxiter=500, solver_restart=30, group=None, Q0=None, seed=20260515, direct_nodes=None,
+                                ortho="mgs"):
     """Complex-symmetric sibling of variant A (A == A^T, B == B^T, complex): the loop of
     _feast_dense_complex_symmetric / its sparse twin (src/dense/feast_dense.jl:1026-1259,
     src/sparse/feast_sparse.jl:509-711).  Same kernels as the Hermitian path with the full
@@ -1000,7 +1038,8 @@ def feast_hip_complex_symmetric(engine, A, B, Emid, r, M0, fpm, *, solver="direc
     done = _LoopRecord(M0, feast_tolerance(fpm), int(fpm[4]), dtype=np.complex128)
     info, active, loop_count, dX, eps_hist = 0, M0, 0, None, []
     stats = {"krylov_iterations": 0, "factorizations": 0, "solve_seconds": 0.0}
-    with _direct_nodes_scope(engine, direct_nodes, len(Zne), _sp.issparse(A), solver, M0, world, stats) as dn:
+    with _ortho_scope(engine, ortho, stats), \
+            _direct_nodes_scope(engine, direct_nodes, len(Zne), _sp.issparse(A), solver, M0, world, stats) as dn:
         for loop_idx in range(0, done.maxloop + 1):
             loop_count = loop_idx
             fail, (dP, status, st) = _sweep(engine, dQ, active, world, count, stats)
@@ -1010,6 +1049,7 @@ def feast_hip_complex_symmetric(engine, A, B, Emid, r, M0, fpm, *, solver="direc
                 info = int(FeastError.Feast_ERROR_LAPACK if fail == 8 else FeastError.Feast_ERROR_NO_CONVERGENCE)
                 break
             rank_q = engine.orthonormalize(dP, active, SQRT_EPS)                  # _feast_qr_compress!, :1163
+            _note_ortho(engine, stats)
             if rank_q == 0:
                 info = int(FeastError.Feast_ERROR_NO_CONVERGENCE)
                 break

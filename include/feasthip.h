@@ -376,6 +376,30 @@ int  feasthip_resident_import(feasthip_handle h, int which, int64_t ncols, const
 int  feasthip_orthonormalize(feasthip_handle h, int64_t m, void* Q, double rank_tol, int* rank);
 int  feasthip_orthonormalize_dev(feasthip_handle h, int64_t m, void* dQ, double rank_tol, int* rank);
 
+/* What a panel takes when the Cholesky-QR fast path rejects it as (nearly) rank deficient -- every refinement loop of an
+ * exact solver, where Q_proj has more columns than eigenvalues inside the contour.  The rank rule is the same for both, that
+ * of _feast_qr_compress! (src/core/feast_aux.jl:101-131).
+ *   FEASTHIP_ORTHO_MGS        the column-pivoted Gram-Schmidt, one chain of launches per column (default)
+ *   FEASTHIP_ORTHO_CHOLQR_RR  staged rank-revealing Cholesky-QR: a pivoted Cholesky of the Gram matrix decides the columns
+ *                             whose pivots it still resolves, they are orthonormalised and projected out, the remainder is
+ *                             judged by the next stage.  Falls back to the Gram-Schmidt on the untouched input when a Gram
+ *                             matrix is not finite or the stage budget runs out.
+ * Applies to feasthip_orthonormalize[_dev] and feasthip_rr_reduce_resident, at every width; the setting persists on the
+ * handle.  Any other value: FEASTHIP_ERROR_FPM.  Full-rank panels take the fast path under either setting.                 */
+enum {
+    FEASTHIP_ORTHO_MGS = 0,
+    FEASTHIP_ORTHO_CHOLQR_RR = 1,
+    FEASTHIP_ORTHO_USED_CHOLQR = 2     /* reported by feasthip_last_ortho only: the Cholesky-QR fast path */
+};
+int  feasthip_set_ortho_method(feasthip_handle h, int method);
+/* The last orthonormalisation on this handle: the path taken (one of the three values above), the stages the staged path
+ * ran, whether it gave up and the Gram-Schmidt decided (fell_back), the rank, and the first n entries of the pivot order
+ * (columns of the panel; -1 past the rank) and of |R_kk| (staged path only, else 0).  A call wider than 64 columns reports
+ * sums over its 64-column panels, perm / rdiag of the last panel, and the staged path if any panel took it.  Any pointer
+ * may be NULL.                                                                                                            */
+int  feasthip_last_ortho(feasthip_handle h, int* method_used, int* stages, int* fell_back, int* rank, int* perm,
+                         double* rdiag, int n);
+
 /* Rayleigh-Ritz projection: Aq = herm(Q^H A Q), Bq = herm(Q^H B Q) (Bq = I when
  * B is the identity).  bilinear=1 uses Q^T (complex-symmetric siblings) and skips the
  * Hermitian symmetrisation.  hermitize=0 returns the raw products, Bq = Q^H Q for B = I (variant C,
