@@ -7,6 +7,7 @@
 #include "fh_eig.hpp"
 #include "fh_comm.hpp"
 #include "fh_cholqr.hpp"
+#include "fh_knobs.hpp"
 #include "../../include/feasthip.h"
 
 #include <algorithm>
@@ -69,10 +70,6 @@ void fh_free_bufs(feasthip_ctx* h) {
 // on the launch stream; the class average is (sum of sampled durations)/(samples).
 #define FH_PROF_PERIOD 13
 static thread_local int fh_prof_open = 0;
-static int fh_prof_period() {
-    static const int period = getenv("FH_PROF_PERIOD") ? std::max(1, atoi(getenv("FH_PROF_PERIOD"))) : FH_PROF_PERIOD;
-    return period;
-}
 static inline double fh_now_s() {
     return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
@@ -81,8 +78,7 @@ void fh_prof_begin(feasthip_ctx* h, const char* cls) {
     if (!h->profiling) return;
     fh_prof_class& pc = h->prof[cls];
     pc.launches += 1;
-    const int period = h->prof_period > 0 ? h->prof_period : fh_prof_period();
-    static const bool nopool = getenv("FH_PROF_NOPOOL") != nullptr;
+    const int period = h->prof_period > 0 ? h->prof_period : fh_knob::prof_period(FH_PROF_PERIOD);
     const long eff = (long)period * h->prof_mult;
     if (eff > 1 && (pc.launches % eff) != 1) return;
     if (h->pending_events.size() > 60000) return;
@@ -90,7 +86,7 @@ void fh_prof_begin(feasthip_ctx* h, const char* cls) {
     fh_event_pair ep;
     ep.cls = cls;
     // events are recycled through a pool: creating and destroying a pair per sample cost more than recording it
-    if (!nopool && h->event_pool.size() >= 2) {
+    if (!fh_knob::prof_nopool() && h->event_pool.size() >= 2) {
         ep.a = h->event_pool.back(); h->event_pool.pop_back();
         ep.b = h->event_pool.back(); h->event_pool.pop_back();
     } else {
@@ -129,7 +125,7 @@ void fh_prof_collect(feasthip_ctx* h) {
     // less often (91 stays coprime to the iteration caps), up to 1 launch in 637.
     h->prof_host_s += fh_now_s() - t_in;
     const double wall = fh_now_s() - h->prof_t0;
-    if ((h->prof_period > 0 ? h->prof_period : fh_prof_period()) > 1 && wall > 0.05 && h->prof_host_s > 0.01 * wall && h->prof_mult < 49) {   // period 1 = exact timing requested
+    if ((h->prof_period > 0 ? h->prof_period : fh_knob::prof_period(FH_PROF_PERIOD)) > 1 && wall > 0.05 && h->prof_host_s > 0.01 * wall && h->prof_mult < 49) {   // period 1 = exact timing requested
         h->prof_mult *= 7;
         h->prof_host_s = 0.0;
         h->prof_t0 = fh_now_s();
@@ -154,12 +150,12 @@ extern "C" int feasthip_create(feasthip_handle* out, int device_id) {
     feasthip_ctx* h = new (std::nothrow) feasthip_ctx();
     if (!h) return FEASTHIP_ERROR_MEMORY;
     h->device = device_id;
-    if (getenv("FH_LU_KB")) h->lu_outer_block = std::max(32, (atoi(getenv("FH_LU_KB")) / 32) * 32);
-    h->lu_solve_legacy = getenv("FH_LU_SOLVE_32") != nullptr;
-    h->lu_gemm_staged = getenv("FH_LU_GEMM_STAGED") != nullptr;
-    if (getenv("FH_LU_LOOKAHEAD")) h->lu_lookahead = atoi(getenv("FH_LU_LOOKAHEAD"));
-    h->sum_mode = getenv("FH_NO_SUM_MODE") ? 0 : 1;
-    h->lu_panel_legacy = getenv("FH_LU_PANEL_LEGACY") ? atoi(getenv("FH_LU_PANEL_LEGACY")) : 0;
+    h->lu_outer_block = fh_knob::lu_kb(h->lu_outer_block);
+    h->lu_solve_legacy = fh_knob::lu_solve_32();
+    h->lu_gemm_staged = fh_knob::lu_gemm_staged();
+    h->lu_lookahead = fh_knob::lu_lookahead();
+    h->sum_mode = fh_knob::no_sum_mode() ? 0 : 1;
+    h->lu_panel_legacy = fh_knob::lu_panel_legacy();
     if (hipSetDevice(device_id) != hipSuccess) { delete h; return FEASTHIP_ERROR_INTERNAL; }
     if (hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking) != hipSuccess) { delete h; return FEASTHIP_ERROR_INTERNAL; }
     h->stream = h->own_stream;
@@ -275,10 +271,9 @@ static int set_csr_typed(feasthip_ctx* h, int64_t N, int index_base, int storage
     // launch, 163 -> 159 ms per solve.  (k_spmm, with its 256-B tiles, never cared: round 2.)  FH_REORDER=0 keeps the caller's
     // order, FH_REORDER=2 renumbers whenever there are at least two blocks (test rigs push small problems through it).  The
     // LDS-window kernel the renumbering was built for stays opt-in (FH_LDS_SPMM=1): 57 vs 33 us per node on cfg 3.
-    static const int reorder_mode = getenv("FH_REORDER") ? atoi(getenv("FH_REORDER")) : 1;
     fh_prepared<VT> P;
     std::string err;
-    const int prc = fh_prepare_csr<VT>(N, index_base, storage, nnzA, ptrA, idxA, valA, nnzB, ptrB, idxB, valB, reorder_mode,
+    const int prc = fh_prepare_csr<VT>(N, index_base, storage, nnzA, ptrA, idxA, valA, nnzB, ptrB, idxB, valB, fh_knob::reorder(),
                                        FH_SPMM_R, FH_SPMM_EXT, sizeof(VT) == sizeof(double), P, err);
     if (prc) { h->last_error = "feasthip_set_csr: " + err; return prc == 3 ? FEASTHIP_ERROR_MEMORY : FEASTHIP_ERROR_N; }
     const bool hasB = ptrB != nullptr;
@@ -324,7 +319,7 @@ static int set_csr_typed(feasthip_ctx* h, int64_t N, int index_base, int storage
         FH_CHECK(hipMemcpy(d.ext_ptr, P.ext_ptr.data(), (nb + 1) * sizeof(int), hipMemcpyHostToDevice));
         FH_CHECK(hipMemcpy(d.ext_idx, P.ext_idx.data(), P.ext_idx.size() * sizeof(int), hipMemcpyHostToDevice));
         FH_CHECK(hipMemcpy(d.lcol, P.lcol.data(), P.lcol.size() * sizeof(unsigned short), hipMemcpyHostToDevice));
-        if (getenv("FH_DEBUG_TIMING"))
+        if (fh_knob::debug_timing())
             fprintf(stderr, "[feasthip] renumbered into %d row blocks, %.1f outside rows per block on average\n", nb, nb ? (double)P.ext_idx.size() / nb : 0.0);
     }
     h->kind = 2;
@@ -518,8 +513,7 @@ struct fh_op_call {
 
 // full-width panels over a real matrix go through the row-per-wave kernel (FH_SPMM_ROW=0: the 4-rows-per-wave gather kernel)
 static bool fh_row_kernel_ok(feasthip_ctx* h, int ld) {
-    static const bool row_off = getenv("FH_SPMM_ROW") && atoi(getenv("FH_SPMM_ROW")) == 0;
-    return h->kind == 2 && ld == 64 && !h->csr.is_complex && h->csr.rp8 && !row_off;
+    return h->kind == 2 && ld == 64 && !h->csr.is_complex && h->csr.rp8 && fh_knob::spmm_row();
 }
 
 // returns number of blocks used in x (needed to size / read partials)
@@ -533,10 +527,9 @@ static int fh_apply_operator(feasthip_ctx* h, int ld, const fh_op_call& c) {
         a.U = c.U; a.u_node_stride = c.u_stride; a.dot_mode = c.dot_mode;
         a.partial1 = c.partial1; a.partial2 = c.partial2; a.node_active = c.node_active;
         a.counters = h->profiling ? h->d_counters : nullptr; a.m = c.m; a.uniform_coef = c.uniform_coef; a.prec = c.prec;
-        static const bool no_lds = !(getenv("FH_LDS_SPMM") && atoi(getenv("FH_LDS_SPMM")) != 0);      // opt-in
         // (the LDS-window kernel keeps its active-node list in a 64-entry LDS array: wider node batches -- trapezoid
         //  contours put no bound on fpm[2] -- take the gather kernel, which has no such limit)
-        const bool lds_kernel = h->csr.lcol && c.prec == 64 && !no_lds && c.nodes <= 64 && c.dot_mode != 6;   // (fused-COCG dots: gather kernel only)
+        const bool lds_kernel = h->csr.lcol && c.prec == 64 && fh_knob::lds_spmm() && c.nodes <= 64 && c.dot_mode != 6;   // (fused-COCG dots: gather kernel only)
         a.nblk_rows = h->csr.nblk; a.blk_start = h->csr.blk_start; a.ext_ptr = h->csr.ext_ptr; a.ext_idx = h->csr.ext_idx;
         a.lcol = lds_kernel ? h->csr.lcol : nullptr;
         // full-width panels over a real matrix: the row-per-wave kernel (FH_SPMM_ROW=0: the 4-rows-per-wave gather kernel)
@@ -759,7 +752,7 @@ static int fh_fused_vec_rows(int N, int ld, int half) {
 // cfg-3 solve.)  N and nodes scale the deadline.  Returns the number of steps queued; *rc != 0: a step or the throttle failed.
 template <class Body>
 static int fh_queue_chunks(feasthip_ctx* h, const int* live, int nlive, int N, int nodes, Body body, int* rc) {
-    const int check_every = getenv("FH_CHECK_EVERY") ? std::max(1, atoi(getenv("FH_CHECK_EVERY"))) : 16;
+    const int check_every = fh_knob::check_every();
     *h->h_progress = 0ull;
     int it = *rc = 0;
     unsigned tag = 0;
@@ -867,8 +860,7 @@ int fh_krylov_work::alloc(const std::vector<cplx>& z, const std::vector<cplx>* w
     s.active = (int*)p; s.iters = s.active + nl; s.status = s.iters + nl; s.node_active = s.status + nl;
     // Fused COCG iteration (fh_sparse.hip): SpMM with five dots -> one finalize -> one vector kernel.  CSR operator through
     // the gather kernel only; FH_COCG_FUSED=0 selects the five-launch form for comparison.
-    static const bool fused_off = getenv("FH_COCG_FUSED") && atoi(getenv("FH_COCG_FUSED")) == 0;
-    fused = method == 1 && h->kind == 2 && !fused_off;
+    fused = method == 1 && h->kind == 2 && fh_knob::cocg_fused();
     if (sum_acc || fused) {
         s.accum = s.node_active + nodes + 4; s.node_accum = s.accum + nl;
         FH_CHECK(hipMemsetAsync(s.accum, 0, (nl + nodes) * sizeof(int), h->stream));
@@ -944,8 +936,8 @@ int fh_krylov_work::start(const std::vector<cplx>& z, const cplx* RHS, cplx* X, 
     }
     va.X = Xk;
     // FH_NO_LAZY_START=1: materialise R and P of a shared start as before.  Read per call (the tests flip it).
-    lazy = shared_start && fused && h->kind == 2 && !h->csr.is_complex && !getenv("FH_NO_LAZY_START") &&
-           (!opt.shared_lambda || opt.shared_lambda_host) && !(getenv("FH_LDS_SPMM") && atoi(getenv("FH_LDS_SPMM")) != 0);
+    lazy = shared_start && fused && h->kind == 2 && !h->csr.is_complex && !fh_knob::no_lazy_start() &&
+           (!opt.shared_lambda || opt.shared_lambda_host) && !fh_knob::lds_spmm();
     if (lazy) {
         if ((rc = fh_upload_coefs(h, "kry_fscale", fh_start_factors(z, nodes, m, ld, opt.shared_lambda_host), &dfs))) return rc;
         lazy_src = opt.shared_src;
@@ -1047,7 +1039,7 @@ static int fh_krylov(feasthip_ctx* h, int method, int prec, int ld, int m, int n
         fh_launch_fused_fin(ff, ld, nodes, h->stream);
     }
     FH_CHECK(hipStreamSynchronize(h->stream));
-    if (getenv("FH_DEBUG_TIMING"))
+    if (fh_knob::debug_timing())
         fprintf(stderr, "[fh_krylov] nodes=%d its queued=%d loop wall %.3f ms\n", nodes, it,
                 1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t_loop0).count());
     if (prec == 32 && !k.sum_acc)
@@ -1176,7 +1168,7 @@ static int fh_gmres(feasthip_ctx* h, int ld, int m, int nodes_all, const std::ve
             budget = std::min(budget, std::max(avail, per_node));
         }
     }
-    if (getenv("FH_GMRES_BUDGET_MB")) budget = (size_t)std::max(1, atoi(getenv("FH_GMRES_BUDGET_MB"))) << 20;
+    budget = fh_knob::gmres_budget_bytes(budget);
     int nbatch = (int)std::max<size_t>(1, std::min<size_t>((size_t)nodes_all, budget / std::max<size_t>(per_node, 1)));
     // an allocation failure halves the batch before it becomes an error
     for (;;) {
@@ -1469,7 +1461,7 @@ static int fh_panel_krylov(feasthip_ctx* h, fh_panel_sweep& g, bool want_moments
         if ((rc = fh_get_buf(h, "ca_acc", panel * sizeof(cplx), (void**)&g.sum_acc))) return rc;
         FH_CHECK(hipMemsetAsync(g.sum_acc, 0, panel * sizeof(cplx), h->stream));
     }
-    g.sum_shared = g.sum_acc && h->factor_precision == 64 && !getenv("FH_NO_SHARED_START");
+    g.sum_shared = g.sum_acc && h->factor_precision == 64 && !fh_knob::no_shared_start();
     if (g.sum_shared) {
         if ((rc = fh_shared_start_source(h, g, &opt.shared_src))) return rc;
     } else if (nk) {
@@ -2168,7 +2160,7 @@ static int fh_ortho_panel(feasthip_ctx* h, int m, int ld, cplx* X, cplx* Out, do
     // Cholesky pivots of the Gram matrix are the squared R_kk of the pivoted QR).  Otherwise fall through to the
     // rank-revealing pivoted Gram-Schmidt.  The Rayleigh-Ritz step that follows uses Q^H B Q anyway, so one pass suffices
     // when it is orthonormal to 1e-14.
-    if (!getenv("FH_NO_CHOLQR")) {
+    if (!fh_knob::no_cholqr()) {
         if ((rc = fh_get_buf(h, "gram_work", fh_gram_work_elems(ld) * sizeof(cplx), &p))) return rc;
         cplx* gw = (cplx*)p;
         if ((rc = fh_get_buf(h, "gram_G", (size_t)ld * ld * sizeof(cplx), &p))) return rc;
@@ -2181,7 +2173,7 @@ static int fh_ortho_panel(feasthip_ctx* h, int m, int ld, cplx* X, cplx* Out, do
         cplx* src = X;
         cplx* dst = Out;
         int npass = 2;
-        static const bool always_two = getenv("FH_CHOLQR_TWO_PASS") != nullptr;
+        const bool always_two = fh_knob::cholqr_two_pass();
         for (int pass = 0; pass < npass && ok; ++pass) {
             fh_prof_begin(h, "gram");
             fh_launch_gram(src, src, N, ld, 0, gw, G, h->stream);
@@ -2852,10 +2844,9 @@ extern "C" int feasthip_rr_reduce_resident(feasthip_handle h, int64_t m64, doubl
     //      below is then as good as an orthonormalised one to 1e-14) takes the fast path ----
     std::vector<double> dcol;
     bool fast = false;
-    if (!getenv("FH_NO_CHOLQR")) {
-        static const bool always_two = getenv("FH_CHOLQR_TWO_PASS") != nullptr;
+    if (!fh_knob::no_cholqr()) {
         std::vector<cplx> G0(Gh, Gh + g2);
-        fast = fh_cholqr::accept(G0, m, ld, 0.0, rank_tol, always_two, dcol) == fh_cholqr::Plan::one_pass;
+        fast = fh_cholqr::accept(G0, m, ld, 0.0, rank_tol, fh_knob::cholqr_two_pass(), dcol) == fh_cholqr::Plan::one_pass;
     }
     if (fast) {
         fh_ortho_note_reset(h);
@@ -3124,7 +3115,7 @@ extern "C" int feasthip_rayleigh_ritz_dev(feasthip_handle h, int64_t r64, const 
     FH_CHECK(hipMemcpyAsync(lam.data(), dlam, r * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     FH_CHECK(hipMemcpyAsync(V.data(), dV, V.size() * sizeof(cplx), hipMemcpyDeviceToHost, h->stream));
     FH_CHECK(hipStreamSynchronize(h->stream));
-    if (getenv("FH_DEBUG_TIMING")) fprintf(stderr, "[rayleigh_ritz] r=%d jacobi sweeps=%d\n", r, flags[3]);
+    if (fh_knob::debug_timing()) fprintf(stderr, "[rayleigh_ritz] r=%d jacobi sweeps=%d\n", r, flags[3]);
     if (flags[0] || flags[2]) { h->last_error = "rayleigh_ritz: reduced B matrix not positive definite"; return FEASTHIP_ERROR_LAPACK; }
     // stable inside-first permutation
     std::vector<int> perm;

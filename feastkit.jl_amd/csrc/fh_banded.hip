@@ -19,6 +19,7 @@
 #define FH_INGEST_STORAGE_CSR 0
 #include "fh_ingest.hpp"       // fh_rcm, fh_bandwidth
 #include "fh_mf.hpp"           // fh_mf::max_boundary_multiplier
+#include "fh_knobs.hpp"
 #include "../../include/feasthip.h"
 
 #define FH_BLOCK 256
@@ -212,7 +213,7 @@ static int band_take_band_plan(feasthip_ctx* h, const std::vector<int>& perm, co
     FH_CHECK(hipMemcpy(h->band_perm, perm.data(), N * sizeof(int), hipMemcpyHostToDevice));
     FH_CHECK(hipMemcpy(h->band_iperm, iperm.data(), N * sizeof(int), hipMemcpyHostToDevice));
     h->band_plan = 2; h->band_kl = kl1; h->band_ku = ku1;
-    if (getenv("FH_DEBUG_TIMING"))
+    if (fh_knob::debug_timing())
         fprintf(stderr, "[feasthip] band plan: stored order kl %d ku %d, band order kl %d ku %d, %.2f GB per node\n", kl0, ku0, kl1, ku1,
                 (double)fh_wband_elems((int)N, kl1, ku1) * sizeof(cplx) / 1e9);
     return 0;
@@ -225,8 +226,8 @@ static int band_make_plan(feasthip_ctx* h) {
     if ((int64_t)h->host_rowptr.size() != N + 1) { h->last_error = "banded LU: no host pattern"; return FEASTHIP_ERROR_INTERNAL; }
     int kl0 = 0, ku0 = 0;
     fh_bandwidth(N, h->host_rowptr, h->host_col, nullptr, kl0, ku0);
-    const bool force_wide = getenv("FH_WBAND") && atoi(getenv("FH_WBAND")) != 0;     // read per plan: tests switch it (and it keeps the multifrontal plan out)
-    const int mf_mode = getenv("FH_MF") ? atoi(getenv("FH_MF")) : -1;                 // 0 never, 1 always (tests), else by predicted work
+    const bool force_wide = fh_knob::wband();     // read per plan: tests switch it (and it keeps the multifrontal plan out)
+    const int mf_mode = fh_knob::mf();            // 0 never, 1 always (tests), else by predicted work
     if (!force_wide && mf_mode != 1 && kl0 + ku0 <= FH_BAND_NARROW) {
         h->band_plan = 1; h->band_kl = kl0; h->band_ku = ku0;
         return 0;
@@ -241,13 +242,12 @@ static int band_make_plan(feasthip_ctx* h) {
     {
         const int mode = mf_mode;
         if (mode != 0 && !(force_wide && mode != 1) && (N >= 2048 || mode == 1)) {
-            const int leaf = getenv("FH_MF_LEAF") ? std::max(8, atoi(getenv("FH_MF_LEAF"))) : 64;
             const auto t0 = std::chrono::steady_clock::now();
-            if (fh_mf_make_plan(h, leaf) == 0) {
+            if (fh_mf_make_plan(h, fh_knob::mf_leaf()) == 0) {
                 const double band_flops = 8.0 * (double)N * (double)kl1 * (double)(kl1 + ku1);
                 // (a front beyond 16 384 rows is outside the panel kernels' reach: such a pattern has no small separators anyway)
                 const bool take = fh_mf_max_front(h) <= 16384 && (mode == 1 || fh_mf_plan_flops(h) < 0.5 * band_flops);
-                if (getenv("FH_DEBUG_TIMING"))
+                if (fh_knob::debug_timing())
                     fprintf(stderr, "[feasthip] multifrontal plan (%.1f ms): %.3e flop and %.2f GB per node, band %.3e flop and %.2f GB -> %s\n",
                             std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(), fh_mf_plan_flops(h),
                             fh_mf_store_bytes(h, 64) / 1e9, band_flops, (double)fh_wband_elems((int)N, kl1, ku1) * sizeof(cplx) / 1e9, take ? "multifrontal" : "band");
@@ -313,7 +313,7 @@ static int band_ensure_slots(feasthip_ctx* h, int nslots) {
     struct alloc_report {
         feasthip_ctx* h; std::chrono::steady_clock::time_point t0; int had; size_t bytes;
         ~alloc_report() {
-            if ((int)h->band_factors.size() > had && getenv("FH_DEBUG_TIMING"))
+            if ((int)h->band_factors.size() > had && fh_knob::debug_timing())
                 fprintf(stderr, "[feasthip] band factors: %d x %.2f GB allocated in %.1f ms\n", (int)h->band_factors.size() - had, bytes / 1e9,
                         std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
         }
@@ -353,9 +353,7 @@ static int band_pointer_arrays(feasthip_ctx* h, const std::vector<int>& which, c
 
 // (fronts of a group) x (nodes of a call) is a grid dimension of the multifrontal kernels (FH_MF_NODES_PER_CALL: smaller batches, tests)
 static int mf_nodes_per_call(feasthip_ctx* h) {
-    int per = std::max(1, 65535 / std::max(1, fh_mf_max_group(h)));
-    if (getenv("FH_MF_NODES_PER_CALL")) per = std::max(1, std::min(per, atoi(getenv("FH_MF_NODES_PER_CALL"))));
-    return per;
+    return fh_knob::mf_nodes_per_call(std::max(1, 65535 / std::max(1, fh_mf_max_group(h))));
 }
 
 // The multifrontal plan rejected a factorisation (fh_mf.hpp: a zero pivot, or a boundary multiplier beyond
@@ -395,7 +393,7 @@ static int band_factor_batch(feasthip_ctx* h, const std::vector<int>& which, con
         FH_CHECK(hipMemcpyAsync(dz, zlist.data(), nf * sizeof(cplx), hipMemcpyHostToDevice, h->stream));
         // (fronts of a group) x (nodes of a call) is a grid dimension: node batches for long contours
         const int per_call = mf_nodes_per_call(h);
-        const double bound = getenv("FH_MF_MAX_MULTIPLIER") ? atof(getenv("FH_MF_MAX_MULTIPLIER")) : fh_mf::max_boundary_multiplier;
+        const double bound = fh_knob::mf_max_multiplier(fh_mf::max_boundary_multiplier);
         double worst = 0.0;
         bool rejected = false;
         for (int q0 = 0; q0 < nf; q0 += per_call) {
@@ -409,7 +407,7 @@ static int band_factor_batch(feasthip_ctx* h, const std::vector<int>& which, con
                 rejected = rejected || info_part[q] != 0 || !(mult_part[q] <= bound);
             }
         }
-        if (getenv("FH_DEBUG_TIMING"))
+        if (fh_knob::debug_timing())
             fprintf(stderr, "[feasthip] multifrontal LU: %d factorisations (%d-bit) in %.1f ms, largest boundary multiplier %.3g%s\n", nf, h->band_prec,
                     std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_factor).count(), worst,
                     rejected ? ": rejected, band LU from here" : "");
@@ -449,7 +447,7 @@ static int band_factor_batch(feasthip_ctx* h, const std::vector<int>& which, con
     }
     FH_CHECK(hipMemcpyAsync(info_out.data(), dinfo, nf * sizeof(int), hipMemcpyDeviceToHost, h->stream));
     FH_CHECK(hipStreamSynchronize(h->stream));
-    if (getenv("FH_DEBUG_TIMING"))
+    if (fh_knob::debug_timing())
         fprintf(stderr, "[feasthip] band LU: %d factorisations (plan %d, kl %d ku %d, %d-bit) in %.1f ms\n", nf, h->band_plan, kl, ku, h->band_prec,
                 std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_factor).count());
     return 0;

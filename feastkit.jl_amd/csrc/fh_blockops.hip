@@ -9,6 +9,7 @@
 #include "fh_common.hpp"
 #include "fh_kernels.hpp"
 #include "fh_cholqr.hpp"
+#include "fh_knobs.hpp"
 
 #define FH_BLOCK 256
 typedef double v4d __attribute__((ext_vector_type(4)));
@@ -471,8 +472,7 @@ __global__ __launch_bounds__(FH_BLOCK) void k_small_matmul_mfma(const cplx* __re
 }
 
 void fh_launch_small_matmul(const cplx* Q, const cplx* V, int N, int ld, cplx* Xout, hipStream_t st, const int* skip) {
-    static const bool valu = getenv("FH_SMALL_MATMUL_VALU") != nullptr;
-    if (!valu) {
+    if (!fh_knob::small_matmul_valu()) {
         const int rb = 16 * (4 / (ld / 16));
         const int nb = std::min((N + rb - 1) / rb, 2048);
         if (ld == 16) hipLaunchKernelGGL((k_small_matmul_mfma<16>), dim3(nb), dim3(FH_BLOCK), 0, st, Q, V, N, Xout, skip);

@@ -15,6 +15,7 @@
 // by design; it is a rehearsal transport, not the fast path.
 #include "fh_common.hpp"
 #include "fh_comm.hpp"
+#include "fh_knobs.hpp"
 #include "../../include/feasthip.h"
 
 #include <rccl/rccl.h>       // types only: the library itself is resolved with dlopen at run time
@@ -56,7 +57,7 @@ rccl_api* rccl() {
         if (api.lib) break;
     }
     if (!api.lib) {
-        const char* env = getenv("FEASTHIP_RCCL_LIB");
+        const char* env = fh_knob::rccl_lib();
         if (env) api.lib = dlopen(env, RTLD_NOW | RTLD_GLOBAL);
         for (size_t i = 0; !api.lib && i < sizeof(names) / sizeof(names[0]); ++i) api.lib = dlopen(names[i], RTLD_NOW | RTLD_GLOBAL);
     }
@@ -107,7 +108,7 @@ struct fh_comm {
     void* peer[FH_SHM_MAX_RANKS] = {nullptr};
     bool peer_ipc[FH_SHM_MAX_RANKS] = {false};       // mapped with hipIpcOpenMemHandle (to be closed), not a same-process pointer
     const double** d_peers = nullptr;                // device array of the mapped peer pointers
-    double timeout_s = 120.0;
+    double timeout_s = 0.0;                          // fh_knob::comm_timeout_s(), set by feasthip_comm_init_rank
 };
 
 // sense-reversing barrier in host shared memory; false on timeout or when a peer reported failure
@@ -151,8 +152,7 @@ static void shm_unmap_peers(fh_comm* c) {
 // fail with hipIpcGetMemHandle: invalid argument); larger reductions stream through it in chunks.
 static int shm_setup_staging(feasthip_ctx* h, fh_comm* c) {
     auto fail = [&](const std::string& msg) { c->seg->failed.store(1); h->last_error = msg; return (int)FEASTHIP_ERROR_INTERNAL; };
-    size_t cap = 32u << 20;
-    if (getenv("FEASTHIP_COMM_STAGING_MB")) cap = (size_t)std::max(1, atoi(getenv("FEASTHIP_COMM_STAGING_MB"))) << 20;
+    const size_t cap = fh_knob::comm_staging_bytes();
     hipError_t e = hipMalloc(&c->staging, cap);
     if (e != hipSuccess) return fail(std::string("comm(shm): hipMalloc(staging): ") + hipGetErrorString(e));
     c->staging_bytes = cap;
@@ -225,12 +225,12 @@ extern "C" int feasthip_comm_init_rank(feasthip_handle h, int nranks, int rank, 
     fh_comm_destroy(h);
     FH_CHECK(hipSetDevice(h->device));
     if (transport == FEASTHIP_COMM_AUTO) {
-        const char* env = getenv("FEASTHIP_COMM_TRANSPORT");
+        const char* env = fh_knob::comm_transport();
         transport = (env && !strcmp(env, "shm")) ? FEASTHIP_COMM_SHM : FEASTHIP_COMM_RCCL;
     }
     fh_comm* c = new fh_comm();
     c->nranks = nranks; c->rank = rank; c->transport = transport;
-    if (getenv("FEASTHIP_COMM_TIMEOUT_S")) c->timeout_s = std::max(1.0, atof(getenv("FEASTHIP_COMM_TIMEOUT_S")));
+    c->timeout_s = fh_knob::comm_timeout_s();
     if (transport == FEASTHIP_COMM_RCCL) {
         rccl_api* r = rccl();
         if (!r->lib) { h->last_error = "comm_init_rank: " + r->error; delete c; return FEASTHIP_ERROR_INTERNAL; }

@@ -14,6 +14,7 @@
 #include "fh_common.hpp"
 #include "fh_kernels.hpp"
 #include "fh_dense.hpp"
+#include "fh_knobs.hpp"
 #include "../../include/feasthip.h"
 
 #define FH_BLOCK 256
@@ -256,8 +257,7 @@ static void launch_dense_op_mfma(const fh_dense_op_args& a, hipStream_t st) {
 
 template <typename VT, int LD>
 static void launch_dense_op_ld(const fh_dense_op_args& a, int nblk, hipStream_t st) {
-    static const bool no_mfma = getenv("FH_DENSE_OP_VALU") != nullptr;
-    if (a.dot_mode == 0 && !no_mfma) {
+    if (a.dot_mode == 0 && !fh_knob::dense_op_valu()) {
         // 32-row tiles when 64-row tiles would leave CUs idle (single-node calls on mid-size matrices)
         if constexpr (LD >= 32) {
             if ((long)a.nodes * ((a.N + 63) / 64) < 256) { launch_dense_op_mfma<VT, LD, 2>(a, st); return; }
@@ -1469,7 +1469,6 @@ __global__ __launch_bounds__(FH_BLOCK) void k_solve_update(T* const* LUs, T* IN,
 // measured later with FH_LU_RESERVE = 2 / 4 / 8: band LU of cfg 3 (16 nodes) 583 / 502 / 500 ms, dense cfg 2 (8 nodes) 79 / 76 /
 // 77 ms against 82 at one, cfg 5 (24 nodes) unchanged -- the main stream's small kernels run on the reserved CUs too, and a
 // panel workgroup needs a completely empty one.
-static int lu_lookahead_reserve(int nf) { (void)nf; return getenv("FH_LU_RESERVE") ? atoi(getenv("FH_LU_RESERVE")) : 4; }
 static bool lu_side_stream(feasthip_ctx* h, int reserve) {
     // CUs per XCD left to the main stream: one per panel workgroup the XCD receives (workgroups go round-robin over XCDs)
     if (!h->side_stream || h->side_reserve != reserve) {
@@ -1571,7 +1570,7 @@ static int lu_factor_batch(feasthip_ctx* h, const std::vector<int>& which, const
         fh_prof_end(h);
     };
     // panels factorised by k_lu_panel_reg leave L11^-1 behind the factor (full 32-column panels only)
-    const bool trsm_subst = getenv("FH_LU_TRSM_SUBST") != nullptr;     // comparison: in-place substitution
+    const bool trsm_subst = fh_knob::lu_trsm_subst();     // comparison: in-place substitution
     auto panel_in_registers = [&](int k0) { return !h->lu_panel_legacy && N - k0 <= 16 * LU_PANEL_THREADS; };
     auto trsm = [&](int k0, int c0, int c1) {
         if (c1 <= c0) return;
@@ -1594,8 +1593,7 @@ static int lu_factor_batch(feasthip_ctx* h, const std::vector<int>& which, const
         const dim3 grid(((nsuper + 7) / 8) * 8 * 8 * sw, nf);
         if (staged || sizeof(T) != sizeof(cplx)) hipLaunchKernelGGL((k_lu_gemm<LU_NB, T>), grid, dim3(FH_BLOCK), 0, h->stream, dlus, N, k0, kd, r0, r1, c0, c1, TR, TC);
         else {
-            static const bool m3_off = getenv("FH_LU_3M") && atoi(getenv("FH_LU_3M")) == 0;
-            if (m3_off) hipLaunchKernelGGL((k_lu_gemm_direct<LU_NB, T, false>), grid, dim3(FH_BLOCK), 0, h->stream, dlus, N, k0, kd, r0, r1, c0, c1, TR, TC, 0);
+            if (!fh_knob::lu_3m()) hipLaunchKernelGGL((k_lu_gemm_direct<LU_NB, T, false>), grid, dim3(FH_BLOCK), 0, h->stream, dlus, N, k0, kd, r0, r1, c0, c1, TR, TC, 0);
             else hipLaunchKernelGGL((k_lu_gemm_direct<LU_NB, T, true>), grid, dim3(FH_BLOCK), 0, h->stream, dlus, N, k0, kd, r0, r1, c0, c1, TR, TC, 0);
         }
         fh_prof_end(h);
@@ -1604,8 +1602,7 @@ static int lu_factor_batch(feasthip_ctx* h, const std::vector<int>& which, const
     // trailing product runs at 52 instead of 46 TFLOP/s and outweighs the longer k = 32 in-block updates)
     const int KB = h->lu_outer_block > 0 ? h->lu_outer_block : (N >= 6144 ? 256 : 128);
     // (FH_LU_BLOCKINV=0: the U block row by 32-row products; needs whole 128-row slabs and the register-resident panels' inverses)
-    static const bool blockinv_off = getenv("FH_LU_BLOCKINV") && atoi(getenv("FH_LU_BLOCKINV")) == 0;
-    const bool block_inverse = !blockinv_off && !trsm_subst && KB % SOLVE_KB == 0 && !h->lu_panel_legacy && N <= 16 * LU_PANEL_THREADS;
+    const bool block_inverse = fh_knob::lu_blockinv() && !trsm_subst && KB % SOLVE_KB == 0 && !h->lu_panel_legacy && N <= 16 * LU_PANEL_THREADS;
     // Look-ahead: the panels of a block column run one 1024-thread workgroup per matrix (8 or 24 of 256 CUs), so the
     // trailing update of block column b is split by columns -- the NEXT block column [Kend, Kend2) is updated on the
     // main stream, the REST [Kend2, N) on a side stream -- and the panels / in-block products of block column b+1
@@ -1615,10 +1612,10 @@ static int lu_factor_batch(feasthip_ctx* h, const std::vector<int>& which, const
     bool lookahead = h->lu_lookahead != 0 && N > 2 * KB;
     const hipStream_t main_s = h->stream;
     // CUs per XCD left to the main stream: one per panel workgroup the XCD receives (workgroups go round-robin over XCDs)
-    const int reserve = lu_lookahead_reserve(nf);
+    const int reserve = fh_knob::lu_reserve();
     if (lookahead && !lu_side_stream(h, reserve)) lookahead = false;
     // measured (cfg 2 sweeps): no look-ahead 84 ms, plain side stream 79, plain + 4 chunks 74, CU mask 68, mask + chunks 72
-    const int lu_chunks = getenv("FH_LU_CHUNKS") ? std::max(1, atoi(getenv("FH_LU_CHUNKS"))) : (reserve > 0 ? 1 : KB / LU_NB);
+    const int lu_chunks = fh_knob::lu_chunks(reserve > 0 ? 1 : KB / LU_NB);
     bool rest_pending = false;
     for (int K0 = 0; K0 < N; K0 += KB) {
         const int Kend = std::min(N, K0 + KB);
@@ -2023,7 +2020,6 @@ static int wband_factor_t(feasthip_ctx* h, int nf, void* const* abs_host, T** db
         else
             hipLaunchKernelGGL((k_lu_trsm<LU_NB, T>), dim3((c1 - c0 + FH_BLOCK - 1) / FH_BLOCK, nf), dim3(FH_BLOCK), 0, h->stream, dbases, lda, k0, c0, c1);
     };
-    static const bool m3_off = getenv("FH_LU_3M") && atoi(getenv("FH_LU_3M")) == 0;
     auto gemm = [&](int k0, int kd, int r0, int r1, int c0, int c1) {
         if (r1 <= r0 || c1 <= c0) return;
         if (h->profiling) h->prof_work["wband_lu"] += 8.0 * (double)(r1 - r0) * (double)(c1 - c0) * (double)kd * (double)nf;
@@ -2032,7 +2028,7 @@ static int wband_factor_t(feasthip_ctx* h, int nf, void* const* abs_host, T** db
         const int nsuper = ((TR + 7) / 8) * ((TC + sw - 1) / sw);
         const dim3 grid(((nsuper + 7) / 8) * 8 * 8 * sw, nf);
         if constexpr (sizeof(T) != sizeof(cplx)) hipLaunchKernelGGL((k_lu_gemm<LU_NB, T>), grid, dim3(FH_BLOCK), 0, h->stream, dbases, lda, k0, kd, r0, r1, c0, c1, TR, TC);
-        else if (m3_off) hipLaunchKernelGGL((k_lu_gemm_direct<LU_NB, T, false>), grid, dim3(FH_BLOCK), 0, h->stream, dbases, lda, k0, kd, r0, r1, c0, c1, TR, TC, 0);
+        else if (!fh_knob::lu_3m()) hipLaunchKernelGGL((k_lu_gemm_direct<LU_NB, T, false>), grid, dim3(FH_BLOCK), 0, h->stream, dbases, lda, k0, kd, r0, r1, c0, c1, TR, TC, 0);
         else hipLaunchKernelGGL((k_lu_gemm_direct<LU_NB, T, true>), grid, dim3(FH_BLOCK), 0, h->stream, dbases, lda, k0, kd, r0, r1, c0, c1, TR, TC, 0);
     };
     // Look-ahead, as in the dense factorisation: the panels of a block column run one workgroup per node, so the update right
@@ -2041,9 +2037,9 @@ static int wband_factor_t(feasthip_ctx* h, int nf, void* const* abs_host, T** db
     // L columns and pivots of block b and writes only columns >= Kend + WB; block column b+1 writes only its own columns and
     // pivots until it waits for the rest (its interchanges to the right touch the same columns).  No interchanges go to the
     // left in the band factorisation, so nothing else is shared.  Same operations on every element: identical factors.
-    static const bool block_inverse = !(getenv("FH_WBAND_BLOCKINV") && atoi(getenv("FH_WBAND_BLOCKINV")) == 0);
+    const bool block_inverse = fh_knob::wband_blockinv();
     bool lookahead = h->lu_lookahead != 0 && kl + ku > 2 * WB && N > 4 * WB;
-    if (lookahead && !lu_side_stream(h, lu_lookahead_reserve(nf))) lookahead = false;
+    if (lookahead && !lu_side_stream(h, fh_knob::lu_reserve())) lookahead = false;
     const hipStream_t main_s = h->stream;
     bool rest_pending = false;
     for (int K0 = 0; K0 < N; K0 += WB) {
@@ -2238,8 +2234,7 @@ static int mf_for_levels(feasthip_ctx* h, fh_mf_state* S, bool ascending, Body b
     hipStream_t extra[3] = {S->extra[0], S->extra[1], S->extra[2]};
     hipEvent_t ev_fork = S->ev_fork, ev_join[3] = {S->ev_join[0], S->ev_join[1], S->ev_join[2]};
     int nextra = S->nextra;
-    static const bool side_off = getenv("FH_MF_SIDE") && atoi(getenv("FH_MF_SIDE")) == 0;
-    if (nextra == 0 && !side_off && h->lu_lookahead != 0 && lu_side_stream(h, lu_lookahead_reserve(16)) && h->side_stream && h->lu_ev_next && h->lu_ev_rest) {
+    if (nextra == 0 && fh_knob::mf_side() && h->lu_lookahead != 0 && lu_side_stream(h, fh_knob::lu_reserve()) && h->side_stream && h->lu_ev_next && h->lu_ev_rest) {
         extra[0] = h->side_stream; ev_fork = h->lu_ev_next; ev_join[0] = h->lu_ev_rest; nextra = 1;
     }
     for (const auto& lv : levels) {
@@ -2351,7 +2346,7 @@ int fh_mf_make_plan(feasthip_ctx* h, int leaf) {
         // default ONE stream.  Measured on cfg 3 with four: factorisation 110 -> 101 ms, sweep 24.7 -> 23.6 ms -- and the dense
         // LU on the same handle fell from 0.069 to 0.104 s per cfg-2 solve: with four streams of the handle in use the CU-masked
         // side stream of the LU look-ahead no longer gets a hardware queue of its own and serialises with the main stream.
-        const int want = getenv("FH_MF_STREAMS") ? std::max(1, std::min(4, atoi(getenv("FH_MF_STREAMS")))) : 1;
+        const int want = fh_knob::mf_streams();
         bool ok = hipEventCreateWithFlags(&S->ev_fork, hipEventDisableTiming) == hipSuccess;
         for (int q = 0; q + 1 < want && ok; ++q) {
             ok = hipStreamCreateWithFlags(&S->extra[q], hipStreamNonBlocking) == hipSuccess &&
@@ -2606,7 +2601,7 @@ static int mf_factor_t(feasthip_ctx* h, int nf, void* const* stores, int* const*
     const int ng = (int)P.groups.size();
     void* p;
     int rc;
-    const bool dbg = getenv("FH_DEBUG_TIMING") != nullptr;
+    const bool dbg = fh_knob::debug_timing();
     const auto t_in = std::chrono::steady_clock::now();
     auto since = [&]() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_in).count(); };
     if ((rc = fh_get_buf(h, "mf_work", (size_t)nf * P.work_elems * sizeof(T), &p))) return rc;
@@ -2625,7 +2620,6 @@ static int mf_factor_t(feasthip_ctx* h, int nf, void* const* stores, int* const*
     float* dpart = (float*)p;
     float* dmult = dpart + tot * MF_MULT_PARTS;
     FH_CHECK(hipMemsetAsync(dpart, 0, tot * MF_MULT_PARTS * sizeof(float), h->stream));
-    static const bool m3_off = getenv("FH_LU_3M") && atoi(getenv("FH_LU_3M")) == 0;
     const bool bid = h->csr.b_identity != 0, cz = h->csr.is_complex != 0;
     auto factor_group = [&](int g) -> int {
         const fh_mf::group& G = P.groups[g];
@@ -2687,7 +2681,7 @@ static int mf_factor_t(feasthip_ctx* h, int nf, void* const* stores, int* const*
             const int compact = (nmat > 64 || 2 * TR * TC <= full) ? 1 : 0;
             const dim3 grid(compact ? TR * TC : full, nmat);
             if constexpr (sizeof(T) != sizeof(cplx)) hipLaunchKernelGGL((k_lu_gemm<LU_NB, T>), grid, dim3(FH_BLOCK), 0, h->stream, W, n, k0, kd, r0, r1, c0, c1, TR, TC, compact);
-            else if (m3_off) hipLaunchKernelGGL((k_lu_gemm_direct<LU_NB, T, false>), grid, dim3(FH_BLOCK), 0, h->stream, W, n, k0, kd, r0, r1, c0, c1, TR, TC, compact);
+            else if (!fh_knob::lu_3m()) hipLaunchKernelGGL((k_lu_gemm_direct<LU_NB, T, false>), grid, dim3(FH_BLOCK), 0, h->stream, W, n, k0, kd, r0, r1, c0, c1, TR, TC, compact);
             else hipLaunchKernelGGL((k_lu_gemm_direct<LU_NB, T, true>), grid, dim3(FH_BLOCK), 0, h->stream, W, n, k0, kd, r0, r1, c0, c1, TR, TC, compact);
         };
         int* ginfo = dinfo + ptr.off[g];
@@ -2862,7 +2856,7 @@ static int mf_solve_t(feasthip_ctx* h, int nf, void* const* stores, int* const* 
     int rc;
     const auto t_in = std::chrono::steady_clock::now();
     if ((rc = mf_pointer_arrays<T>(h, *S, nf, stores, pivs, nullptr, false, ptr))) return rc;
-    struct report { std::chrono::steady_clock::time_point t0, t1; ~report() { if (getenv("FH_DEBUG_TIMING")) fprintf(stderr, "[feasthip] multifrontal solve: pointer arrays %.1f ms, buffers + launches %.1f ms (host)\n",
+    struct report { std::chrono::steady_clock::time_point t0, t1; ~report() { if (fh_knob::debug_timing()) fprintf(stderr, "[feasthip] multifrontal solve: pointer arrays %.1f ms, buffers + launches %.1f ms (host)\n",
         std::chrono::duration<double, std::milli>(t1 - t0).count(), std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count()); } } rep{t_in, std::chrono::steady_clock::now()};
     if (ld == 16) return mf_solve_ld<16, T>(h, S, nf, ptr, RHS, rhs_stride, OUT, out_stride, m);
     if (ld == 32) return mf_solve_ld<32, T>(h, S, nf, ptr, RHS, rhs_stride, OUT, out_stride, m);

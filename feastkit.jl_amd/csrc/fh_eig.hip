@@ -9,6 +9,7 @@
 #include <cstdlib>
 
 #include "fh_eig.hpp"
+#include "fh_knobs.hpp"
 
 #define EIG_THREADS 1024
 #define EIG_MAX 64
@@ -239,7 +240,7 @@ int fh_launch_herm_eig(int r, int ld, const cplx* S, const cplx* A, void* scratc
     const size_t dyn = (size_t)2 * EIG_MAX * EIG_MAX * sizeof(cplx) + 32 * 4 * sizeof(double);
     if (lds_mode < 0) {
         lds_mode = 0;
-        if (!getenv("FH_EIG_NO_LDS") &&
+        if (!fh_knob::eig_no_lds() &&
             hipFuncSetAttribute((const void*)k_herm_eig<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn) == hipSuccess)
             lds_mode = 1;
         (void)hipGetLastError();

@@ -38,6 +38,8 @@
 #include <numeric>
 #include <vector>
 
+#include "fh_knobs.hpp"
+
 namespace fh_mf {
 
 struct front {
@@ -84,7 +86,6 @@ struct plan {
 constexpr double max_boundary_multiplier = 1e3;
 
 static inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
-static inline double plan_store_slack() { const char* e = getenv("FH_MF_STORE_SLACK"); const double v = e ? atof(e) : 0.0; return v >= 1.0 ? v : 1.25; }
 static inline size_t inv32_elems(int np) { return (size_t)(np / 32) * 2 * 32 * 32; }
 static inline size_t inv128_elems(int np) { return (size_t)((np + 127) / 128) * 2 * 128 * 128; }
 
@@ -305,7 +306,7 @@ static inline int make_plan(int N, const std::vector<int>& rowptr, const std::ve
                 // The factor store keeps a group's padded geometry, so a second rule bounds the memory: a front does not join
                 // when the group's padded store would exceed store_slack x what its members need on their own.
                 const double step_flops = 2.5e8;
-                const double store_slack = plan_store_slack();
+                const double store_slack = fh_knob::mf_store_slack();
                 auto store_of = [](int np_, int nb_) { return (double)(np_ + nb_) * np_ + 64.0 * np_ + (double)np_ * nb_; };
                 double cost = 0.0, own_store = 0.0;
                 for (; j < fs.size(); ++j) {

@@ -176,7 +176,8 @@ def test_orthonormalize_one_and_two_cholesky_qr_passes(kind, monkeypatch):
     Gaussian columns (ratio ~ 1, one pass); "graded": the same columns scaled over four decades (equilibration makes it the
     first case: still one pass; ten decades would be rank deficient by the reference's |R_ii| / |R_11| rule); "ill": columns 3e-3 apart from each other in angle (ratio ~ 1e-5: two passes).  In every
     case the basis is orthonormal to 1e-12, spans the input, and equals -- up to 1e-10 in the projector -- what the
-    always-two-passes form (FH_CHOLQR_TWO_PASS=1) returns."""
+    always-two-passes form (FH_CHOLQR_TWO_PASS=1, read per call) returns.  The in-library profiler counts every launch of the Gram
+    kernel, one per pass: that the forced run really took the second pass is asserted, not assumed."""
     import feastkit_jl_amd as fk
     N, m = 3000, 40
     rng = np.random.default_rng(77)
@@ -192,9 +193,12 @@ def test_orthonormalize_one_and_two_cholesky_qr_passes(kind, monkeypatch):
             monkeypatch.setenv("FH_CHOLQR_TWO_PASS", "1")
         eng = fk.HipEngine(0)
         eng.set_problem(A, B)
+        eng.profile_enable()
         dQ = eng.upload(X)
+        grams = eng.profile_get("gram")[1]
         rank = eng.orthonormalize(dQ, m, np.sqrt(np.finfo(float).eps))
         assert rank == m
+        assert eng.profile_get("gram")[1] - grams == (2 if forced or kind == "ill" else 1), (kind, forced)
         Q = eng.download(dQ)[:, :rank]
         eng.close()
         assert np.abs(Q.conj().T @ Q - np.eye(m)).max() < 1e-12
