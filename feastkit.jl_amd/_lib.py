@@ -88,6 +88,7 @@ SYMBOLS = {
     "feasthip_last_column_iterations": (_i, [_vp, _vp, _i]),
     "feasthip_last_global_node_iterations": (_i, [_vp, _vp, _i]),
     "feasthip_last_shifted_sweep": (_i, [_vp, _vp, _vp, _vp, _vp]),
+    "feasthip_last_block_sweep": (_i, [_vp, _vp, _vp, _vp, _vp]),
     "feasthip_profile_enable": (_i, [_vp, _i]),
     "feasthip_profile_reset": (_i, [_vp]),
     "feasthip_profile_get": (_i, [_vp, C.c_char_p, _pd, _pi64]),

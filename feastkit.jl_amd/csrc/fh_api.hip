@@ -479,14 +479,16 @@ extern "C" int feasthip_set_column_mask(feasthip_handle h, int64_t m, const int*
 extern "C" int feasthip_set_solver(feasthip_handle h, int kind, double rtol, double atol, int maxit, int restart,
                                    int factor_precision, int cache_factors) {
     if (!h) return FEASTHIP_ERROR_INTERNAL;
-    if (kind < 0 || kind > FEASTHIP_SOLVER_SHIFTED_COCG || rtol < 0 || atol < 0 || maxit <= 0 || restart < 0 ||
+    if (kind < 0 || kind > FEASTHIP_SOLVER_BLOCK_COCG || rtol < 0 || atol < 0 || maxit <= 0 || restart < 0 ||
         (factor_precision != 64 && factor_precision != 32)) {
         h->last_error = "feasthip_set_solver: invalid option";
         return FEASTHIP_ERROR_FPM;
     }
     // SHIFTED_COCG is COCG with the shifted sweep where fh_contour_apply_panel finds it eligible: every other path sees COCG
     h->shifted = kind == FEASTHIP_SOLVER_SHIFTED_COCG ? 1 : 0;
-    if (h->shifted) kind = FEASTHIP_SOLVER_COCG;
+    // BLOCK_COCG likewise: COCG with the block sweep where the panel is eligible
+    h->block = kind == FEASTHIP_SOLVER_BLOCK_COCG ? 1 : 0;
+    if (h->shifted || h->block) kind = FEASTHIP_SOLVER_COCG;
     h->solver = kind; h->rtol = rtol; h->atol = atol; h->maxit = maxit; h->restart = restart;
     h->factor_precision = factor_precision; h->cache_factors = cache_factors;
     return 0;
@@ -1135,6 +1137,108 @@ static int fh_shifted_cocg(feasthip_ctx* h, int ld, int m, int nodes, const std:
 }
 
 // ---------------------------------------------------------------------------------------
+// Block COCG sweep in sum mode (fh_bcocg.hip): CSR operator with real values (B given or B = I), complex128 panels, shared
+// start r_e^0 = f_e,c * shared_src as the shifted sweep has it.  Per node the live columns share one block Krylov space; the
+// nodes advance in lock-step and each leaves on its own (converged / breakdown), decided on the device.  A node that broke
+// down is finished by the per-column sweep (fh_krylov, one node, sum mode) from the residual it stopped with: that panel is
+// its shared source, the accumulator the same.  res as fh_krylov fills it: a live column reports its node's block steps
+// (plus the per-column steps of a fallback).  *steps_max: most block steps of a node; *passes: operator node-passes that ran.
+// ---------------------------------------------------------------------------------------
+static int fh_block_cocg(feasthip_ctx* h, int ld, int m, int nodes, const std::vector<cplx>& z, fh_solve_result& res,
+                         cplx* sum_acc, const std::vector<cplx>& wnode, const cplx* shared_src, const double* lambda_host,
+                         const double* dlam, const cplx* dz, cplx* Xdummy, int* steps_max, int* breakdowns, int* passes) {
+    const int N = (int)fh_N(h);
+    const size_t panel = (size_t)N * ld, nl = (size_t)nodes * ld, mat = (size_t)ld * ld;
+    int rc;
+    void* p;
+    fh_bcocg_args a;
+    memset(&a, 0, sizeof(a));
+    a.N = N; a.nodes = nodes; a.m = m; a.node_stride = panel; a.sum_acc = sum_acc; a.src = shared_src;
+    a.rtol = h->rtol; a.atol = h->atol;
+    if ((rc = fh_get_buf(h, "bcg_vecs", 3 * (size_t)nodes * panel * sizeof(cplx), &p))) return rc;
+    a.Q = (cplx*)p; a.P = a.Q + (size_t)nodes * panel; a.W = a.P + (size_t)nodes * panel;
+    if ((rc = fh_get_buf(h, "bcg_small", (2 + 12 * (size_t)nodes) * mat * sizeof(cplx), &p))) return rc;
+    cplx* sm = (cplx*)p;
+    auto slot = [&](int i) { return sm + 2 * mat + (size_t)i * nodes * mat; };
+    a.SH = sm; a.ST = sm + mat;
+    a.GA = slot(0); a.GH = slot(1); a.GT = slot(2); a.T = slot(3); a.Tn = slot(4); a.U = slot(5); a.Ze = slot(6); a.Zi = slot(7);
+    a.Cs = slot(8); a.Al = slot(9); a.M1 = slot(10); a.Be = slot(11);
+    FH_CHECK(hipMemsetAsync(sm, 0, (2 + 12 * (size_t)nodes) * mat * sizeof(cplx), h->stream));
+    if ((rc = fh_get_buf(h, "bcg_scal_d", 3 * nl * sizeof(double), &p))) return rc;
+    a.r0norm = (double*)p; a.target = a.r0norm + nl; a.rnorm = a.target + nl;
+    const size_t nint = 4 * nl + 5 * (size_t)nodes;
+    if ((rc = fh_get_buf(h, "bcg_scal_i", nint * sizeof(int), &p))) return rc;
+    a.active = (int*)p; a.iters = a.active + nl; a.status = a.iters + nl; a.live = a.status + nl;
+    a.node_active = a.live + nl; a.stop = a.node_active + nodes; a.steps = a.stop + nodes; a.passes = a.steps + nodes;
+    a.nlive = a.passes + nodes;
+    FH_CHECK(hipMemsetAsync(a.active, 0, nint * sizeof(int), h->stream));
+    if ((rc = fh_get_buf(h, "bcg_gram", fh_bcocg_gram_work_elems(ld, nodes) * sizeof(cplx), &p))) return rc;
+    cplx* gw = (cplx*)p;
+    cplx *dfs, *dw, *dca, *dcb;
+    if ((rc = fh_upload_coefs(h, "bcg_fscale", fh_start_factors(z, nodes, m, ld, lambda_host), &dfs))) return rc;
+    if ((rc = fh_upload_coefs(h, "bcg_wnode", wnode, &dw))) return rc;
+    if ((rc = fh_upload_shift_coefs(h, "bcg_coefA", "bcg_coefB", z.data(), nodes, ld, &dca, &dcb))) return rc;
+    a.fscale = dfs; a.wnode = dw;
+    if ((rc = fh_upload_col_mask(h, ld, &a.col_mask))) return rc;
+
+    // start: the two Gram matrices of the shared source serve every node; Q_e = P_e = src Zi_e
+    fh_prof_begin(h, "bcocg_gram"); fh_launch_bcocg_gram(shared_src, 0, shared_src, 0, N, ld, 1, gw, a.SH, a.ST, nullptr, h->stream); fh_prof_end(h);
+    fh_prof_begin(h, "bcocg_small"); fh_launch_bcocg_small(a, ld, 0, h->stream); fh_prof_end(h);
+    fh_prof_begin(h, "bcocg_update"); fh_launch_bcocg_update(a, ld, 0, h->stream); fh_prof_end(h);
+    fh_op_call oc;
+    oc.m = m; oc.uniform_coef = 1; oc.coefA = dca; oc.coefB = dcb; oc.nodes = nodes; oc.prec = 64;
+    oc.X = a.P; oc.x_stride = panel; oc.Y = a.W; oc.y_stride = panel; oc.dot_mode = 0; oc.node_active = a.node_active;
+    // iterate: the published count is the number of nodes still running
+    fh_queue_chunks(h, a.node_active, nodes, N, nodes, [&](int) {
+        if (fh_apply_operator(h, ld, oc) < 0) return (int)FEASTHIP_ERROR_INTERNAL;
+        fh_prof_begin(h, "bcocg_gram"); fh_launch_bcocg_gram(a.P, panel, a.W, panel, N, ld, nodes, gw, nullptr, a.GA, a.stop, h->stream); fh_prof_end(h);
+        fh_prof_begin(h, "bcocg_small"); fh_launch_bcocg_small(a, ld, 1, h->stream); fh_prof_end(h);
+        fh_prof_begin(h, "bcocg_update"); fh_launch_bcocg_update(a, ld, 1, h->stream); fh_prof_end(h);
+        fh_prof_begin(h, "bcocg_gram"); fh_launch_bcocg_gram(a.Q, panel, a.Q, panel, N, ld, nodes, gw, a.GH, a.GT, a.stop, h->stream); fh_prof_end(h);
+        fh_prof_begin(h, "bcocg_small"); fh_launch_bcocg_small(a, ld, 2, h->stream); fh_prof_end(h);
+        fh_prof_begin(h, "bcocg_update"); fh_launch_bcocg_update(a, ld, 2, h->stream); fh_prof_end(h);
+        return 0;
+    }, &rc);
+    if (rc) return rc;
+    FH_CHECK(hipStreamSynchronize(h->stream));
+    res.status.assign(nodes, 0);
+    if ((rc = fh_collect_columns(h, a.iters, a.status, a.active, a.rnorm, a.r0norm, nullptr, nodes, m, ld, 0, FH_FAIL_STOP_TEST, res)))
+        return rc;
+    std::vector<int> word(3 * (size_t)nodes);          // stop, steps, passes (adjacent on the device)
+    FH_CHECK(hipMemcpy(word.data(), a.stop, word.size() * sizeof(int), hipMemcpyDeviceToHost));
+    const int *stop = word.data(), *steps = stop + nodes, *ran = steps + nodes;
+    *steps_max = *breakdowns = *passes = 0;
+    int launches = 0;
+    for (int e = 0; e < nodes; ++e) {
+        *steps_max = std::max(*steps_max, steps[e]); *passes += ran[e]; launches = std::max(launches, ran[e]);
+        if (stop[e] == 2) *breakdowns += 1;
+    }
+    res.op_calls = launches;
+    if (!*breakdowns) return 0;
+    // fallback: W_e = Q_e C_e is what is left of the right-hand side of a node that broke down; the per-column sweep adds its
+    // solution of S_e D = W_e to the accumulator.  A node that broke down before its first step starts from the source itself.
+    fh_prof_begin(h, "bcocg_update"); fh_launch_bcocg_update(a, ld, 3, h->stream); fh_prof_end(h);
+    for (int e = 0; e < nodes; ++e) {
+        if (stop[e] != 2) continue;
+        const bool at_start = steps[e] == 0 && ran[e] == 0;
+        fh_krylov_opts opt;
+        const std::vector<cplx> ze(1, z[e]), we(1, wnode[e]);
+        opt.sum_acc = sum_acc; opt.wnode = &we;
+        opt.shared_src = at_start ? shared_src : a.W + (size_t)e * panel;
+        if (at_start) { opt.shared_lambda = dlam; opt.shared_lambda_host = lambda_host; opt.dznode = dz + e; }
+        fh_solve_result re;
+        if ((rc = fh_krylov(h, 1, 64, ld, m, 1, ze, shared_src, Xdummy, panel, re, opt))) return rc;
+        res.status[e] = re.status[0];
+        res.iters_sum += re.node_iters[0]; res.node_iters[e] += re.node_iters[0];
+        res.max_iters = std::max(res.max_iters, res.node_iters[e]);
+        for (int c = 0; c < m; ++c) res.col_iters[(size_t)e * m + c] += re.col_iters[c];
+        res.max_rel_res = std::max(res.max_rel_res, re.max_rel_res);
+        res.op_calls += re.op_calls; *passes += (int)re.op_calls;
+    }
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------
 // restarted GMRES(m) on panels -- the reference's iterative solver
 // (solve_shifted_iterative!, src/sparse/feast_sparse.jl:164-203; Krylov.jl gmres with
 // restart=true, memory=m, zero initial guess unless X holds one, stop ||r|| <= atol + rtol ||r0||).
@@ -1475,7 +1579,15 @@ static int fh_panel_krylov(feasthip_ctx* h, fh_panel_sweep& g, bool want_moments
     const bool shifted = h->shifted && g.sum_shared && opt.shared_src && nk && !nd && h->kind == 2 && h->csr.b_identity &&
                          !h->csr.is_complex;
     h->shift_panels += 1;
-    if (shifted) {
+    // Block COCG (kind BLOCK_COCG): a CSR operator with real values (any real symmetric B), fp64 panels, sum mode from a
+    // shared start, no direct nodes.  Anything else is the per-node sweep.
+    const bool block = h->block && g.sum_shared && opt.shared_src && nk && !nd && h->kind == 2 && !h->csr.is_complex;
+    h->block_panels += 1;
+    if (block) {
+        int smax = 0, brk = 0, ran = 0;
+        if ((rc = fh_block_cocg(h, ld, m, nk, zk, sr, g.sum_acc, wk, opt.shared_src, g.ritz_lambda, dlam, dz, g.Y, &smax, &brk, &ran))) return rc;
+        h->block_used += 1; h->block_steps_max = std::max(h->block_steps_max, smax); h->block_breakdowns += brk; h->block_passes += ran;
+    } else if (shifted) {
         int seed = 0, seed_its = 0;
         if ((rc = fh_shifted_cocg(h, ld, m, nk, zk, sr, g.sum_acc, wk, opt.shared_src, g.ritz_lambda, &seed, &seed_its))) return rc;
         h->shift_used += 1; h->shift_seed = h->node_ids[g.order[seed]]; h->shift_seed_iters += seed_its;
@@ -1767,6 +1879,7 @@ static int fh_contour_apply_impl(feasthip_ctx* h, int64_t m64, const cplx* dQ, c
                                  cplx* dQproj, cplx* dzAq, cplx* dzSq, int* node_status, feasthip_stats* stats,
                                  const fh_resident_sweep* rs = nullptr) {
     h->shift_panels = h->shift_used = h->shift_seed_iters = 0; h->shift_seed = -1;      // feasthip_last_shifted_sweep
+    h->block_panels = h->block_used = h->block_steps_max = h->block_breakdowns = h->block_passes = 0;   // feasthip_last_block_sweep
     const int nr = fh_comm_nranks(h);
     int64_t c0 = 0, c1 = m64;
     if (h->col_block_hi >= 0) { c0 = std::min(h->col_block_lo, m64); c1 = std::min(std::max(h->col_block_hi, c0), m64); }
@@ -3293,6 +3406,16 @@ extern "C" int feasthip_last_shifted_sweep(feasthip_handle h, int* used, int* se
     if (seed_node) *seed_node = u ? h->shift_seed : -1;
     if (seed_iterations) *seed_iterations = u ? h->shift_seed_iters : 0;
     if (spmm_node_passes) *spmm_node_passes = u ? h->shift_seed_iters : 0;
+    return 0;
+}
+
+extern "C" int feasthip_last_block_sweep(feasthip_handle h, int* used, int* node_steps_max, int* breakdown_nodes, int* spmm_node_passes) {
+    if (!h) return FEASTHIP_ERROR_INTERNAL;
+    const bool u = h->block_panels > 0 && h->block_used == h->block_panels;
+    if (used) *used = u ? 1 : 0;
+    if (node_steps_max) *node_steps_max = u ? h->block_steps_max : 0;
+    if (breakdown_nodes) *breakdown_nodes = u ? h->block_breakdowns : 0;
+    if (spmm_node_passes) *spmm_node_passes = u ? h->block_passes : 0;
     return 0;
 }
 

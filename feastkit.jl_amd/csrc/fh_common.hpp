@@ -155,6 +155,10 @@ struct feasthip_ctx {
     int shifted = 0;               // FEASTHIP_SOLVER_SHIFTED_COCG was asked for (solver then holds COCG)
     // the last contour_apply: panels swept, panels that took the shifted sweep, its seed (contour index) and seed iterations
     int shift_panels = 0, shift_used = 0, shift_seed = -1, shift_seed_iters = 0;
+    int block = 0;                 // FEASTHIP_SOLVER_BLOCK_COCG was asked for (solver then holds COCG)
+    // the last contour_apply: panels swept, panels that took the block sweep, most block steps of a node, nodes that broke
+    // down (finished by the per-column sweep), operator node-passes that ran
+    int block_panels = 0, block_used = 0, block_steps_max = 0, block_breakdowns = 0, block_passes = 0;
     double rtol = 1e-12, atol = 0.0;
     int maxit = 500, restart = 30, factor_precision = 64, cache_factors = 1;
 

@@ -132,6 +132,35 @@ int fh_launch_shift_init(const fh_shift_args& a, int ld, hipStream_t st);
 void fh_launch_shift_fin(const fh_shift_args& a, int ld, hipStream_t st);
 // r -= alpha q; ACC += sum_e w_e alpha_e p_e; p_e = r / pi_e + beta_e p_e; partial rows of the new r; returns their number
 int fh_launch_shift_vec(const fh_shift_args& a, int ld, hipStream_t st);
+// ---- block COCG (fh_bcocg.hip): one block Krylov space per node ---------------------------------------------------------------
+// Panels are complex128.  [n][LD] arrays hold one entry per (node, ORIGINAL column); the small matrices are LD x LD, row-major,
+// zero padded, one per node ([n][LD*LD]).  stop[e]: 0 running, 1 converged, 2 breakdown; every kernel skips a node that left.
+struct fh_bcocg_args {
+    int N, nodes, m;
+    size_t node_stride;
+    cplx *Q, *P, *W;                          // [nodes] panels: orthonormal residual factor, directions, S P
+    cplx* sum_acc;                            // N x LD accumulator: ACC += w_e P_e (alpha_e C_e)
+    const cplx* src;                          // shared start residual: R_e^0 = src diag(fscale[e])
+    const cplx* fscale;                       // [n][LD]
+    const cplx* wnode;                        // [nodes]
+    cplx *SH, *ST;                            // [LD*LD] src^H src, src^T src
+    cplx *GA, *GH, *GT;                       // P^T W ; Qh^H Qh ; Qh^T Qh
+    cplx *T, *Tn, *U, *Ze, *Zi, *Cs, *Al, *M1, *Be;   // Q^T Q, its successor, scratch, zeta, zeta^-1, C, alpha, w alpha C, beta
+    double *r0norm, *target, *rnorm;          // [n][LD]
+    int *active, *iters, *status, *live;      // [n][LD]; live[e][j]: original column of block column j (-1 past nlive[e])
+    int *node_active, *stop, *steps, *passes, *nlive;   // [nodes]; steps: block steps taken, passes: operator products that ran
+    const int* col_mask;                      // [LD] or null
+    double rtol, atol;
+};
+size_t fh_bcocg_gram_work_elems(int ld, int nodes);
+// outH[e] = X_e^H Y_e and outT[e] = X_e^T Y_e (either may be null) for the nodes with stop[e] == 0 (stop null: all)
+void fh_launch_bcocg_gram(const cplx* X, size_t xs, const cplx* Y, size_t ys, int N, int ld, int nodes, cplx* work, cplx* outH,
+                          cplx* outT, const int* stop, hipStream_t st);
+// phase 0: start; 1: alpha and w alpha C from P^T W; 2: zeta, T', beta, C, norms and the stop word from the Grams of Qh
+void fh_launch_bcocg_small(const fh_bcocg_args& a, int ld, int phase, hipStream_t st);
+// phase 0: Q = P = src Zi; 1: ACC += P M1, Q -= W alpha; 2: Q = Q Zi, P = Q + P beta; 3: W = Q C for the nodes that broke down
+void fh_launch_bcocg_update(const fh_bcocg_args& a, int ld, int phase, hipStream_t st);
+
 void fh_launch_fin_init(const fh_fin_args& a, int ld, int nodes, hipStream_t st);
 void fh_launch_fin_alpha(const fh_fin_args& a, int ld, int nodes, hipStream_t st);
 void fh_launch_fin_omega(const fh_fin_args& a, int ld, int nodes, hipStream_t st);

@@ -18,10 +18,10 @@ from . import _lib
 from ._lib import FeastHipStats, FeastHipUnavailable
 from .types import FeastHipError
 
-SOLVER_LU, SOLVER_BICGSTAB, SOLVER_GMRES, SOLVER_COCG, SOLVER_BANDED, SOLVER_SHIFTED_COCG = 0, 1, 2, 3, 4, 5
+SOLVER_LU, SOLVER_BICGSTAB, SOLVER_GMRES, SOLVER_COCG, SOLVER_BANDED, SOLVER_SHIFTED_COCG, SOLVER_BLOCK_COCG = 0, 1, 2, 3, 4, 5, 6
 _SOLVER_CODES = {"direct": SOLVER_LU, "lu": SOLVER_LU, "bicgstab": SOLVER_BICGSTAB,
                  "iterative": SOLVER_BICGSTAB, "gmres": SOLVER_GMRES, "cocg": SOLVER_COCG,
-                 "banded": SOLVER_BANDED, "shifted_cocg": SOLVER_SHIFTED_COCG}
+                 "banded": SOLVER_BANDED, "shifted_cocg": SOLVER_SHIFTED_COCG, "block_cocg": SOLVER_BLOCK_COCG}
 MAX_BLOCK = 64   # FH_MAX_LD: widest panel the kernels take in one call
 
 
@@ -250,7 +250,7 @@ class HipEngine:
     def set_solver(self, solver="direct", rtol=1e-12, atol=0.0, maxit=500, restart=30,
                    factor_precision=64, cache_factors=True):
         if solver not in _SOLVER_CODES:
-            raise ValueError(f"Unsupported solver option '{solver}'. Use :direct, :banded, :bicgstab, :cocg, :shifted_cocg, :gmres, or :iterative.")
+            raise ValueError(f"Unsupported solver option '{solver}'. Use :direct, :banded, :bicgstab, :cocg, :shifted_cocg, :block_cocg, :gmres, or :iterative.")
         self._chk(self.lib.feasthip_set_solver(self.h, _SOLVER_CODES[solver], float(rtol), float(atol), int(maxit),
                                                int(restart), int(factor_precision), int(bool(cache_factors))))
 
@@ -512,6 +512,14 @@ class HipEngine:
         sweep (solver "shifted_cocg" on an eligible problem) and what that cost (feasthip_last_shifted_sweep)."""
         out = [np.zeros(1, dtype=np.int32) for _ in range(4)]
         self._chk(self.lib.feasthip_last_shifted_sweep(self.h, *[_np_ptr(v) for v in out]))
+        return bool(out[0][0]), int(out[1][0]), int(out[2][0]), int(out[3][0])
+
+    def last_block_sweep(self):
+        """(used, most block steps of a node, nodes that broke down, SpMM node-passes) of the last contour_apply: whether it
+        took the block COCG sweep (solver "block_cocg" on an eligible problem) and what that cost
+        (feasthip_last_block_sweep)."""
+        out = [np.zeros(1, dtype=np.int32) for _ in range(4)]
+        self._chk(self.lib.feasthip_last_block_sweep(self.h, *[_np_ptr(v) for v in out]))
         return bool(out[0][0]), int(out[1][0]), int(out[2][0]), int(out[3][0])
 
     def last_global_node_iterations(self):

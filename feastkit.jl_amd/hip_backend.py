@@ -709,17 +709,19 @@ def feast_hip_hermitian(engine, A, B, Emin, Emax, M0, fpm, *, freeze_guards_afte
     if inner_precision not in (32, 64):
         raise ValueError("inner_precision must be 32 or 64")
     inexact = bool(iterative and warm_start and inner_rtol is not None and float(inner_rtol) > 10.0 * tol_value)
+    # block COCG with frozen guard columns: the cocg sweep (stats["block"] then reports used = False)
+    eng_solver = "cocg" if (solver == "block_cocg" and freeze_guards_after is not None) else solver
     if iterative and warm_start:
         # inexact-solve mode: every loop reduces the (warm-started) residual by inner_rtol
         rt = tol_value if inner_rtol is None else float(inner_rtol)
         if inner_precision == 32 and rt < 1e-5:
             raise ValueError("inner_precision=32 needs inner_rtol >= 1e-5 (single-precision correction solves)")
-        engine.set_solver(solver, rtol=rt, atol=0.0, maxit=solver_maxiter, restart=solver_restart,
+        engine.set_solver(eng_solver, rtol=rt, atol=0.0, maxit=solver_maxiter, restart=solver_restart,
                           factor_precision=inner_precision)
     elif inner_precision == 32:
         if solver in DIRECT_SOLVERS:
             # dense LU / blocked band LU: complex64 factors + fp64 iterative refinement inside every solve
-            engine.set_solver(solver, rtol=tol_value, atol=0.0, maxit=solver_maxiter, restart=solver_restart,
+            engine.set_solver(eng_solver, rtol=tol_value, atol=0.0, maxit=solver_maxiter, restart=solver_restart,
                               factor_precision=32, cache_factors=True)
         else:
             raise ValueError("inner_precision=32 needs a direct solver or the warm-started inexact iterative mode")
@@ -776,7 +778,7 @@ def feast_hip_hermitian(engine, A, B, Emin, Emax, M0, fpm, *, freeze_guards_afte
                 # inexact FEAST on complex64 factors: the solves are refined only as far as the current outer residual needs
                 # (no refinement in the first loop; the last loops reach the full tolerance)
                 ref_tol = 1.0 if not math.isfinite(done.epsout) else min(1.0, max(tol_value, 1e-2 * done.epsout))
-                engine.set_solver(solver, rtol=ref_tol, atol=0.0, maxit=solver_maxiter, restart=solver_restart,
+                engine.set_solver(eng_solver, rtol=ref_tol, atol=0.0, maxit=solver_maxiter, restart=solver_restart,
                                   factor_precision=32, cache_factors=True)
             # one call = this rank's (nodes x column block) sweep + the packed all-reduce inside the C ABI: dP and status
             # come back summed over all ranks (status indexed by contour node when world > 1).  Resident panels: Q_proj
@@ -793,6 +795,10 @@ def feast_hip_hermitian(engine, A, B, Emin, Emax, M0, fpm, *, freeze_guards_afte
             if solver == "shifted_cocg" and hasattr(engine, "last_shifted_sweep"):
                 used, seed_node, seed_its, _ = engine.last_shifted_sweep()
                 stats.setdefault("shifted", []).append({"used": used, "seed_node": seed_node, "seed_iterations": seed_its})
+            if solver == "block_cocg" and hasattr(engine, "last_block_sweep"):
+                used, steps_max, brk, passes = engine.last_block_sweep()
+                stats.setdefault("block", []).append({"used": used, "node_steps_max": steps_max, "breakdown_nodes": brk,
+                                                      "spmm_node_passes": passes})
             if dn is not None:
                 dn.record(loop_idx, st, layout.local_nodes)
             layout.rebalance(engine, loop_idx, active, stats)
@@ -871,7 +877,7 @@ def feast_hip_hermitian(engine, A, B, Emin, Emax, M0, fpm, *, freeze_guards_afte
                     # policy -- fpm[18]
                     new_aspect, new_solve = pol.update(done.epsout, M, int(np.max(status)) == 5, lam_sorted, rank_q)
                     if new_solve:
-                        engine.set_solver(solver, rtol=pol.next_rtol, atol=0.0, maxit=pol.inner_cap, restart=solver_restart,
+                        engine.set_solver(eng_solver, rtol=pol.next_rtol, atol=0.0, maxit=pol.inner_cap, restart=solver_restart,
                                           factor_precision=inner_precision)
                         if pol.inner_cap != int(solver_maxiter):
                             stats["inner_cap"] = pol.inner_cap

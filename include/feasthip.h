@@ -70,6 +70,14 @@ enum {
     FEASTHIP_SOLVER_COCG = 3,      /* conjugate-orthogonal CG for the complex-SYMMETRIC shifted
                                       systems that real-symmetric A, B produce (one operator
                                       application per iteration); not in the reference      */
+    FEASTHIP_SOLVER_BLOCK_COCG = 6,  /* COCG whose contour sweep lets the columns of a node share ONE block Krylov space
+                                      (block COCG with residual orthonormalisation: the live columns of the panel are one
+                                      block right-hand side of z_e B - A; the nodes still advance side by side).  Replaces
+                                      the per-column recurrences of the solve loop, src/sparse/feast_sparse.jl:318-369 and
+                                      :164-203, for real CSR A and B (or B = I), fp64 panels, feasthip_contour_apply without
+                                      moments or direct nodes; a node whose block breaks down (rank loss, a small pivot) is
+                                      finished by the per-column sweep; every other case runs exactly as
+                                      FEASTHIP_SOLVER_COCG.  feasthip_last_block_sweep reports what ran                 */
     FEASTHIP_SOLVER_SHIFTED_COCG = 5 /* COCG whose contour sweep shares ONE Krylov space among the local nodes when
                                       B = I (shifted COCG: the matrices z_e I - A differ by multiples of the identity, so
                                       only a seed node applies the operator, the others follow by scalar recurrences).
@@ -464,6 +472,12 @@ int  feasthip_last_global_node_iterations(feasthip_handle h, int* out, int n);
  * iteration.  Sums over the 64-column panels of a wide sweep.  used = 0: seed_node = -1, the counts are 0.  Any pointer
  * may be null.                                                                                              */
 int  feasthip_last_shifted_sweep(feasthip_handle h, int* used, int* seed_node, int* seed_iterations, int* spmm_node_passes);
+/* Whether the last feasthip_contour_apply[_resident] took the block COCG sweep (FEASTHIP_SOLVER_BLOCK_COCG and an eligible
+ * problem) on this rank, and what it cost: the most block steps any node took (steps that ran on the device, not steps
+ * queued), the nodes whose block broke down and were finished by the per-column sweep (a normal outcome, never an error
+ * status), and the operator node-passes that ran (one per node and block step, plus those of the fallbacks).  Sums over the
+ * 64-column panels of a wide sweep (node_steps_max: the maximum).  used = 0: the counts are 0.  Any pointer may be null. */
+int  feasthip_last_block_sweep(feasthip_handle h, int* used, int* node_steps_max, int* breakdown_nodes, int* spmm_node_passes);
 /* [local node][m] iterations per column of the last iterative sweep (row-major, n entries). */
 int  feasthip_last_column_iterations(feasthip_handle h, int* out, int n);
 int  feasthip_profile_enable(feasthip_handle h, int enable);
