@@ -75,6 +75,9 @@ SYMBOLS = {
     "feasthip_last_ortho": (_i, [_vp, _pi, _pi, _pi, _pi, _vp, _vp, _i]),
     "feasthip_project": (_i, [_vp, _i64, _vp, _i, _i, _vp, _vp]),
     "feasthip_project_dev": (_i, [_vp, _i64, _vp, _i, _i, _vp, _vp]),
+    "feasthip_set_adjoint": (_i, [_vp, _i]),
+    "feasthip_project_pair": (_i, [_vp, _i64, _vp, _vp, _vp, _vp]),
+    "feasthip_project_pair_dev": (_i, [_vp, _i64, _vp, _vp, _vp, _vp]),
     "feasthip_ritz_residual": (_i, [_vp, _i64, _vp, _vp, _vp, _i64, _i, _i, _vp, _vp]),
     "feasthip_ritz_residual_dev": (_i, [_vp, _i64, _vp, _vp, _vp, _i64, _i, _i, _vp, _vp]),
     "feasthip_matmul": (_i, [_vp, _i, _i64, _vp, _vp]),

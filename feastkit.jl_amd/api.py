@@ -12,8 +12,8 @@ import scipy.sparse as sp
 
 from .engine import HipEngine
 from .contour import feast_contour, feast_gcontour
-from .hip_backend import (DIRECT_SOLVERS, ESTIMATE_SEED, check_direct_nodes, check_ortho, feast_hip_estimate, feast_hip_general,
-                          feast_hip_hermitian)
+from .hip_backend import (DIRECT_SOLVERS, ESTIMATE_SEED, check_direct_nodes, check_ortho, check_two_sided, feast_hip_estimate,
+                          feast_hip_general, feast_hip_general_two_sided, feast_hip_hermitian)
 from .parameters import feastdefault, feastinit
 from .types import FEAST_UNINITIALIZED, FeastHipError, FeastResult
 
@@ -438,8 +438,15 @@ def feast(A, B=None, interval=None, *, M0=10, fpm=None, backend="hip", solver="d
 
 def feast_general(A, B=None, center=0.0, radius=1.0, *, M0=10, fpm=None, backend="hip", solver="direct",
                   solver_tol=0.0, solver_maxiter=500, solver_restart=30, group=None, engine=None, device=0, Q0=None,
-                  inner_precision=64, contour=None, keep_factors=False, seed=None, direct_nodes=None, ortho="mgs"):
+                  inner_precision=64, contour=None, keep_factors=False, seed=None, direct_nodes=None, ortho="mgs",
+                  two_sided=False, QL0=None):
     """feast_general(A, [B,] center, radius; M0, fpm): src/interfaces/feast_interfaces.jl:274-379.
+    ``two_sided=True`` (dense input, ``solver="direct"``): the two-sided method -- a left subspace from conjugate-transposed
+    solves on the LU factors of the right sweep, oblique projection, both residuals with B; the result carries ``q_left``
+    (y_j^H B x_j = 1) and ``stats["two_sided"]``, and ``info`` is Feast_ERROR_NO_CONVERGENCE when the loop limit ends the run.
+    ``QL0``: left start block.  The keyword is the only switch: fpm[15], which the reference validates and never reads
+    (src/core/feast_parameters.jl:217-225), stays unread here too, so no existing call changes.  Sparse input, another
+    solver, ``inner_precision=32``, ``group=`` and ``direct_nodes=`` raise ValueError.
     ``keep_factors``, ``direct_nodes``, ``ortho``: as in feast() (this variant never orthonormalises its subspace, so ``ortho``
     changes nothing it computes).  ``fpm[14] = 2`` and ``M0="auto"``: as in feast(), on the full contour of the
     circle (the samples are complex; M = round(Re mean))."""
@@ -449,13 +456,15 @@ def feast_general(A, B=None, center=0.0, radius=1.0, *, M0=10, fpm=None, backend
         return _feast_auto(feast_general, A, B, center, radius, fpm=fpm, backend=backend, solver=solver, solver_tol=solver_tol,
                            solver_maxiter=solver_maxiter, solver_restart=solver_restart, group=group, engine=engine,
                            device=device, Q0=Q0, inner_precision=inner_precision, contour=contour, keep_factors=keep_factors,
-                           seed=seed, direct_nodes=direct_nodes, ortho=ortho)
+                           seed=seed, direct_nodes=direct_nodes, ortho=ortho, two_sided=two_sided, QL0=QL0)
     if backend not in _BACKENDS:
         raise ValueError(f"Unknown backend '{backend}' (this package provides: hip)")
     if A.shape[0] != A.shape[1]:
         raise ValueError("Matrix A must be square")
     if not radius > 0:
         raise ValueError("radius must be positive")
+    if two_sided:
+        check_two_sided(sp.issparse(A), solver, inner_precision, group, direct_nodes)
     _check_direct_nodes_early(direct_nodes, A, solver, fpm, 8, contour)
     check_ortho(ortho)
     single = _single_precision(A, B)
@@ -500,20 +509,26 @@ def feast_general(A, B=None, center=0.0, radius=1.0, *, M0=10, fpm=None, backend
         solver = "banded"
     eng = _engine(engine, device)
     dn_ignored = direct_nodes is not None and solver in DIRECT_SOLVERS
+    eps_floor = float(np.sqrt(np.finfo(np.float32).eps)) if single else 0.0
     try:
-        res = feast_hip_general(eng, A, B, complex(center), float(radius), M0, fpm, solver=solver, inner_precision=inner_precision,
-                                 solver_tol=solver_tol, solver_maxiter=solver_maxiter,
-                                 solver_restart=solver_restart, group=group, Q0=Q0, contour=contour,
-                                 eps_floor=float(np.sqrt(np.finfo(np.float32).eps)) if single else 0.0,
-                                 direct_nodes=None if dn_ignored else direct_nodes, ortho=ortho)
+        if two_sided:
+            res = feast_hip_general_two_sided(eng, A, B, complex(center), float(radius), M0, fpm, solver=solver, Q0=Q0, QL0=QL0,
+                                              contour=contour, eps_floor=eps_floor, **({} if seed is None else {"seed": int(seed)}))
+        else:
+            res = feast_hip_general(eng, A, B, complex(center), float(radius), M0, fpm, solver=solver, inner_precision=inner_precision,
+                                    solver_tol=solver_tol, solver_maxiter=solver_maxiter,
+                                    solver_restart=solver_restart, group=group, Q0=Q0, contour=contour, eps_floor=eps_floor,
+                                    direct_nodes=None if dn_ignored else direct_nodes, ortho=ortho)
         if dn_ignored and isinstance(res.stats, dict):
             res.stats["direct_nodes"] = {"ignored": "direct solver in force"}
         if substituted is not None and isinstance(res.stats, dict):
             res.stats["solver_substitution"] = substituted
     finally:
-        _release_band_factors(eng, keep_factors)
+        _release_band_factors(eng, keep_factors)          # (the dense LU factors of the two-sided sweeps among them)
     if single:
+        ql = res.q_left
         res = _demote(res, cplx_lambda=True)
+        res.q_left = None if ql is None else ql.astype(np.complex64)
     return res
 
 

@@ -441,6 +441,12 @@ extern "C" int feasthip_set_real_projection(feasthip_handle h, int real_part) {
     return 0;
 }
 
+extern "C" int feasthip_set_adjoint(feasthip_handle h, int on) {
+    if (!h) return FEASTHIP_ERROR_INTERNAL;
+    h->adjoint = on ? 1 : 0;
+    return 0;
+}
+
 extern "C" int feasthip_set_node_range(feasthip_handle h, int first, int count) {
     if (!h) return FEASTHIP_ERROR_INTERNAL;
     if (first < 0 || count < 0 || first + count > (int)h->zne.size()) {
@@ -554,6 +560,14 @@ static int fh_apply_operator(feasthip_ctx* h, int ld, const fh_op_call& c) {
     a.U = (const cplx*)c.U; a.u_node_stride = c.u_stride; a.dot_mode = c.dot_mode;
     a.partial1 = c.partial1; a.partial2 = c.partial2; a.node_active = c.node_active;
     int nblk = fh_dense_op_nblk(a.N);
+    if (h->adjoint) {
+        // the entry points that honour the switch use plain products only (fh_check_adjoint keeps the Krylov solvers out)
+        if (c.dot_mode != 0) { h->last_error = "internal: adjoint operator with fused dots"; return -1; }
+        fh_prof_begin(h, "dense_op_adjoint");
+        fh_launch_dense_op_adjoint(a, ld, h->stream);
+        fh_prof_end(h);
+        return nblk;
+    }
     fh_prof_begin(h, "dense_op");
     fh_launch_dense_op(a, ld, nblk, h->stream);
     fh_prof_end(h);
@@ -582,6 +596,21 @@ static int fh_check_problem(feasthip_ctx* h, int64_t m, int wide = 0) {
         return FEASTHIP_ERROR_M0;
     }
     return 0;
+}
+
+// Adjoint switch (feasthip_set_adjoint).  unsupported != null: the entry point has no adjoint form at all.  Otherwise the
+// handle must be what the adjoint kernels cover: a dense problem, the dense LU in fp64, no real projection, one rank.
+static int fh_check_adjoint(feasthip_ctx* h, const char* what, const char* unsupported = nullptr) {
+    if (!h || !h->adjoint) return 0;
+    const char* why = unsupported;
+    if (!why && h->kind == 2) why = "a CSR problem has no adjoint substitution (dense problems only)";
+    if (!why && h->solver != FEASTHIP_SOLVER_LU) why = "the solver must be the dense LU (FEASTHIP_SOLVER_LU)";
+    if (!why && h->factor_precision == 32) why = "factor_precision = 32 is not supported (complex128 factors only)";
+    if (!why && h->real_projection) why = "the real projection does not apply to an adjoint sweep";
+    if (!why && h->comm) why = "an attached communicator is not supported";
+    if (!why) return 0;
+    h->last_error = std::string(what) + " with the adjoint switch on (feasthip_set_adjoint): " + why;
+    return FEASTHIP_ERROR_FPM;
 }
 
 // Reserves a 64-byte aligned slot of `bytes` in the pinned ring, or *slot = null when there is no ring or the copy is too large
@@ -1712,7 +1741,7 @@ static int fh_contour_apply_panel(feasthip_ctx* h, int64_t m64, const cplx* dQ, 
         return 0;
     }
     // rhs = B Q  (hoisted out of the node loop; the reference recomputes it per node,
-    // src/dense/feast_dense.jl:184 -- it is loop invariant)
+    // src/dense/feast_dense.jl:184 -- it is loop invariant); B^H Q under the adjoint switch (fh_apply_operator)
     g.Rhs = g.Qp;
     if (!fh_b_identity(h)) {
         if ((rc = fh_get_buf(h, "ca_rhs", panel * sizeof(cplx), &p))) return rc;
@@ -1736,6 +1765,7 @@ static int fh_contour_apply_panel(feasthip_ctx* h, int64_t m64, const cplx* dQ, 
     for (int i = 0; i < nodes; ++i) {
         z[i] = h->zne[h->node_ids[g.order[i]]];
         w[i] = cscale(h->wne[h->node_ids[g.order[i]]], h->weight_scale);
+        if (h->adjoint) w[i].y = -w[i].y;         // adjoint sweep: Q_proj = sum_e conj(w_e) S_e^-H B^H Q
     }
     if ((rc = fh_get_buf(h, "ca_Y", (size_t)nodes * panel * sizeof(cplx), &p))) return rc;
     cplx* Y = g.Y = (cplx*)p;
@@ -2045,6 +2075,7 @@ extern "C" int feasthip_contour_apply_dev(feasthip_handle h, int64_t m, const vo
                                           void* dQproj, void* dzAq, void* dzSq, int* node_status, feasthip_stats* stats) {
     if (!h) return FEASTHIP_ERROR_INTERNAL;
     if (!dQ || !dQproj) { h->last_error = "contour_apply: null Q/Qproj"; return FEASTHIP_ERROR_INTERNAL; }
+    if (int arc = fh_check_adjoint(h, "contour_apply", (dzAq || dzSq) ? "the moment matrices zAq / zSq must be NULL" : nullptr)) return arc;
     // the column mask is one-shot: it applies to this sweep only and never leaks into later calls
     // (shifted_solve / RCI jobs on the same handle), whatever the outcome of the sweep
     h->mask_live = 1;
@@ -2067,6 +2098,7 @@ extern "C" int feasthip_contour_apply(feasthip_handle h, int64_t m, const void* 
     int rc = fh_check_problem(h, m, 1);
     if (rc) return rc;
     if (!Q || !Qproj) { h->last_error = "contour_apply: null Q/Qproj"; return FEASTHIP_ERROR_INTERNAL; }
+    if ((rc = fh_check_adjoint(h, "contour_apply", (zAq || zSq) ? "the moment matrices zAq / zSq must be NULL" : nullptr))) return rc;
     FH_CHECK(hipSetDevice(h->device));
     const size_t nb = (size_t)fh_N(h) * m * sizeof(cplx), mb = (size_t)m * m * sizeof(cplx);
     void *dQ, *dP, *dA = nullptr, *dS = nullptr;
@@ -2111,6 +2143,7 @@ extern "C" int feasthip_estimate_count(feasthip_handle h, int64_t m, uint64_t se
                                        feasthip_stats* stats) {
     int rc = fh_check_estimate(h, m);
     if (rc) return rc;
+    if ((rc = fh_check_adjoint(h, "estimate_count", "the estimate has no adjoint form"))) return rc;
     if (!samples) { h->last_error = "estimate_count: null samples"; return FEASTHIP_ERROR_INTERNAL; }
     const double t0 = fh_now_s();
     FH_CHECK(hipSetDevice(h->device));
@@ -2486,34 +2519,72 @@ extern "C" int feasthip_last_ortho(feasthip_handle h, int* method_used, int* sta
 // ---------------------------------------------------------------------------------------
 // Rayleigh-Ritz projection (a10)
 // ---------------------------------------------------------------------------------------
+// While it lives the handle applies the forward operator whatever feasthip_set_adjoint says (the projections are defined
+// with A and B themselves); the switch is put back on every return path.
+struct fh_forward_scope {
+    feasthip_ctx* h; int was;
+    explicit fh_forward_scope(feasthip_ctx* h_) : h(h_), was(h_->adjoint) { h->adjoint = 0; }
+    ~fh_forward_scope() { h->adjoint = was; }
+};
+
+// res = Q_L^H op Q_R (bilinear: Q_L^T) for op = A (which 0) or B (which 1), r x r column-major on the host, by ld-column
+// panels: block (i, j) is Q_L,i^H (op Q_R,j) on the operator and MFMA Gram kernels.  One download and one stream
+// synchronisation per block: a single one for r <= ld, (r / 64)^2 of them for the wide calls.
+static int fh_project_blocks(feasthip_ctx* h, int r, int ld, const cplx* dQL, const cplx* dQR, int which, int bilinear, cplx* res) {
+    const int N = (int)fh_N(h);
+    const size_t panel = (size_t)N * ld;
+    void* p;
+    int rc;
+    if ((rc = fh_get_buf(h, "pj_Q", panel * sizeof(cplx), &p))) return rc;
+    cplx* Qi = (cplx*)p;
+    if ((rc = fh_get_buf(h, "pj_Qj", panel * sizeof(cplx), &p))) return rc;
+    cplx* Qj = (cplx*)p;
+    if ((rc = fh_get_buf(h, "pj_W", panel * sizeof(cplx), &p))) return rc;
+    cplx* W = (cplx*)p;
+    if ((rc = fh_get_buf(h, "gram_work", fh_gram_work_elems(ld) * sizeof(cplx), &p))) return rc;
+    cplx* gw = (cplx*)p;
+    if ((rc = fh_get_buf(h, "gram_G", (size_t)ld * ld * sizeof(cplx), &p))) return rc;
+    cplx* G = (cplx*)p;
+    std::vector<cplx> one(ld, cmake(1, 0)), zero(ld, cmake(0, 0));
+    cplx *d1, *d0;
+    if ((rc = fh_upload_coefs(h, "pj_one", one, &d1))) return rc;
+    if ((rc = fh_upload_coefs(h, "pj_zero", zero, &d0))) return rc;
+    const int npan = (r + ld - 1) / ld;
+    std::vector<cplx> Gh((size_t)ld * ld);
+    for (int j = 0; j < npan; ++j) {
+        const int mj = std::min(ld, r - j * ld);
+        fh_launch_to_panel(dQR + (size_t)j * ld * N, N, N, mj, Qj, ld, h->stream, fh_perm(h));
+        fh_op_call oc;
+        oc.m = mj;
+        oc.X = Qj; oc.Y = W;
+        oc.coefA = which == 0 ? d1 : d0; oc.coefB = which == 0 ? d0 : d1;
+        if (fh_apply_operator(h, ld, oc) < 0) return (int)FEASTHIP_ERROR_INTERNAL;
+        for (int i = 0; i < npan; ++i) {
+            const int mi = std::min(ld, r - i * ld);
+            fh_launch_to_panel(dQL + (size_t)i * ld * N, N, N, mi, Qi, ld, h->stream, fh_perm(h));
+            fh_prof_begin(h, "gram");
+            fh_launch_gram(Qi, W, N, ld, bilinear, gw, G, h->stream);
+            fh_prof_end(h);
+            FH_CHECK(hipMemcpyAsync(Gh.data(), G, Gh.size() * sizeof(cplx), hipMemcpyDeviceToHost, h->stream));
+            FH_CHECK(hipStreamSynchronize(h->stream));
+            for (int c2 = 0; c2 < mj; ++c2)
+                for (int c1 = 0; c1 < mi; ++c1)
+                    res[(size_t)(j * ld + c2) * r + i * ld + c1] = Gh[(size_t)c2 * ld + c1];
+        }
+    }
+    return 0;
+}
+
 extern "C" int feasthip_project_dev(feasthip_handle h, int64_t r64, const void* dQ, int bilinear, int hermitize,
                                     void* Aq_host, void* Bq_host) {
     if (r64 > FH_MAX_LD) {
-        // r > 64: 64-column panels; block (i, j) of Q^H A Q is Q_i^H (A Q_j) on the MFMA Gram kernel
+        // r > 64: 64-column panels (fh_project_blocks)
         int rc0 = fh_check_problem(h, r64, 1);
         if (rc0) return rc0;
         if (!dQ || !Aq_host) { h->last_error = "project: null argument"; return FEASTHIP_ERROR_INTERNAL; }
         FH_CHECK(hipSetDevice(h->device));
-        const int r = (int)r64, ld = FH_MAX_LD, N = (int)fh_N(h);
-        const size_t panel = (size_t)N * ld;
-        void* p;
-        int rc;
-        if ((rc = fh_get_buf(h, "pj_Q", panel * sizeof(cplx), &p))) return rc;
-        cplx* Qi = (cplx*)p;
-        if ((rc = fh_get_buf(h, "pj_Qj", panel * sizeof(cplx), &p))) return rc;
-        cplx* Qj = (cplx*)p;
-        if ((rc = fh_get_buf(h, "pj_W", panel * sizeof(cplx), &p))) return rc;
-        cplx* W = (cplx*)p;
-        if ((rc = fh_get_buf(h, "gram_work", fh_gram_work_elems(ld) * sizeof(cplx), &p))) return rc;
-        cplx* gw = (cplx*)p;
-        if ((rc = fh_get_buf(h, "gram_G", (size_t)ld * ld * sizeof(cplx), &p))) return rc;
-        cplx* G = (cplx*)p;
-        std::vector<cplx> one(ld, cmake(1, 0)), zero(ld, cmake(0, 0));
-        cplx *d1, *d0;
-        if ((rc = fh_upload_coefs(h, "pj_one", one, &d1))) return rc;
-        if ((rc = fh_upload_coefs(h, "pj_zero", zero, &d0))) return rc;
-        const int npan = (r + ld - 1) / ld;
-        std::vector<cplx> Gh((size_t)ld * ld);
+        fh_forward_scope forward(h);
+        const int r = (int)r64;
         for (int which = 0; which < 2; ++which) {
             cplx* out_host = (cplx*)(which == 0 ? Aq_host : Bq_host);
             if (!out_host) continue;
@@ -2521,27 +2592,7 @@ extern "C" int feasthip_project_dev(feasthip_handle h, int64_t r64, const void* 
             if (which == 1 && fh_b_identity(h) && hermitize && !bilinear) {
                 for (int i = 0; i < r; ++i) res[(size_t)i * r + i] = cmake(1, 0);
             } else {
-                for (int j = 0; j < npan; ++j) {
-                    const int mj = std::min(ld, r - j * ld);
-                    fh_launch_to_panel((const cplx*)dQ + (size_t)j * ld * N, N, N, mj, Qj, ld, h->stream, fh_perm(h));
-                    fh_op_call oc;
-                    oc.m = mj;
-                    oc.X = Qj; oc.Y = W;
-                    oc.coefA = which == 0 ? d1 : d0; oc.coefB = which == 0 ? d0 : d1;
-                    fh_apply_operator(h, ld, oc);
-                    for (int i = 0; i < npan; ++i) {
-                        const int mi = std::min(ld, r - i * ld);
-                        fh_launch_to_panel((const cplx*)dQ + (size_t)i * ld * N, N, N, mi, Qi, ld, h->stream, fh_perm(h));
-                        fh_prof_begin(h, "gram");
-                        fh_launch_gram(Qi, W, N, ld, bilinear, gw, G, h->stream);
-                        fh_prof_end(h);
-                        FH_CHECK(hipMemcpyAsync(Gh.data(), G, Gh.size() * sizeof(cplx), hipMemcpyDeviceToHost, h->stream));
-                        FH_CHECK(hipStreamSynchronize(h->stream));
-                        for (int c2 = 0; c2 < mj; ++c2)
-                            for (int c1 = 0; c1 < mi; ++c1)
-                                res[(size_t)(j * ld + c2) * r + i * ld + c1] = Gh[(size_t)c2 * ld + c1];
-                    }
-                }
+                if ((rc0 = fh_project_blocks(h, r, FH_MAX_LD, (const cplx*)dQ, (const cplx*)dQ, which, bilinear, res.data()))) return rc0;
                 if (hermitize && !bilinear) fh_cholqr::hermitian_part(res.data(), r);
             }
             memcpy(out_host, res.data(), res.size() * sizeof(cplx));
@@ -2554,6 +2605,7 @@ extern "C" int feasthip_project_dev(feasthip_handle h, int64_t r64, const void* 
     if (rc) return rc;
     if (!dQ || !Aq_host) { h->last_error = "project: null argument"; return FEASTHIP_ERROR_INTERNAL; }
     FH_CHECK(hipSetDevice(h->device));
+    fh_forward_scope forward(h);
     const int r = (int)r64, ld = fh_pick_ld(r), N = (int)fh_N(h);
     const size_t panel = (size_t)N * ld;
     void* p;
@@ -2622,6 +2674,36 @@ extern "C" int feasthip_project(feasthip_handle h, int64_t r, const void* Q, int
     return feasthip_project_dev(h, r, dQ, bilinear, hermitize, Aq, Bq);
 }
 
+// Oblique projection of the two-sided method: Aq = Q_L^H A Q_R, Bq = Q_L^H B Q_R (Q_L^H Q_R for B = I), raw products
+// (fh_project_blocks).  Forward operator whatever the adjoint switch says.
+extern "C" int feasthip_project_pair_dev(feasthip_handle h, int64_t r64, const void* dQL, const void* dQR, void* Aq_host, void* Bq_host) {
+    int rc = fh_check_problem(h, r64, 1);
+    if (rc) return rc;
+    if (!dQL || !dQR || !Aq_host) { h->last_error = "project_pair: null argument"; return FEASTHIP_ERROR_INTERNAL; }
+    FH_CHECK(hipSetDevice(h->device));
+    fh_forward_scope forward(h);
+    const int r = (int)r64, ld = r > FH_MAX_LD ? FH_MAX_LD : fh_pick_ld(r);
+    for (int which = 0; which < 2; ++which) {
+        cplx* out_host = (cplx*)(which == 0 ? Aq_host : Bq_host);
+        if (out_host && (rc = fh_project_blocks(h, r, ld, (const cplx*)dQL, (const cplx*)dQR, which, 0, out_host))) return rc;
+    }
+    fh_prof_collect(h);
+    FH_CHECK(hipGetLastError());       // launch-configuration errors do not surface through the stream sync
+    return 0;
+}
+
+extern "C" int feasthip_project_pair(feasthip_handle h, int64_t r, const void* QL, const void* QR, void* Aq, void* Bq) {
+    int rc = fh_check_problem(h, r, 1);
+    if (rc) return rc;
+    if (!QL || !QR || !Aq) { h->last_error = "project_pair: null argument"; return FEASTHIP_ERROR_INTERNAL; }
+    FH_CHECK(hipSetDevice(h->device));
+    const size_t nb = (size_t)fh_N(h) * r * sizeof(cplx);
+    void *dL, *dR;
+    if ((rc = fh_stage_in(h, "host_Q", QL, nb, &dL))) return rc;
+    if ((rc = fh_stage_in(h, "host_X", QR, nb, &dR))) return rc;
+    return feasthip_project_pair_dev(h, r, dL, dR, Aq, Bq);
+}
+
 // ---------------------------------------------------------------------------------------
 // Ritz back-transform + residual (a12, a13)
 // ---------------------------------------------------------------------------------------
@@ -2669,6 +2751,14 @@ static void fh_residual_norms(const cplx* dots, const double* lambda, int M, dou
 extern "C" int feasthip_ritz_residual_dev(feasthip_handle h, int64_t r64, const void* dQ, const void* V_host,
                                           const double* lambda_host, int64_t M, int normalize, int use_B, void* dX,
                                           double* res_host) {
+    if (int arc = fh_check_adjoint(h, "ritz_residual")) return arc;
+    std::vector<double> lam_conj;
+    if (h && h->adjoint && lambda_host && V_host && dQ && dX && fh_check_problem(h, r64, 1) == 0) {   // (failed checks are reported below)
+        // adjoint residual A^H x - conj(lambda) B^H x: the products are adjoint through fh_apply_operator, the values here
+        lam_conj.assign(lambda_host, lambda_host + 2 * (size_t)r64);
+        for (size_t c = 0; c < (size_t)r64; ++c) lam_conj[2 * c + 1] = -lam_conj[2 * c + 1];
+        lambda_host = lam_conj.data();
+    }
     if (r64 > FH_MAX_LD) {
         // r > 64: X_j = sum_i Q_i V[i-block, j-block] per 64-column output panel, then the panel
         // goes through the same normalise / residual steps as the narrow path
@@ -2805,6 +2895,7 @@ extern "C" int feasthip_ritz_residual(feasthip_handle h, int64_t r, const void* 
     int rc = fh_check_problem(h, r, 1);
     if (rc) return rc;
     if (!Q || !X) { h->last_error = "ritz_residual: null argument"; return FEASTHIP_ERROR_INTERNAL; }
+    if ((rc = fh_check_adjoint(h, "ritz_residual"))) return rc;
     FH_CHECK(hipSetDevice(h->device));
     const size_t nb = (size_t)fh_N(h) * r * sizeof(cplx);
     void *dQ, *dX;
@@ -2855,6 +2946,7 @@ extern "C" int feasthip_contour_apply_resident(feasthip_handle h, int64_t m64, c
                                                int* node_status, feasthip_stats* stats) {
     int rc = fh_check_problem(h, m64);
     if (rc) return rc;
+    if ((rc = fh_check_adjoint(h, "contour_apply_resident", "the resident loop has no adjoint form"))) return rc;
     if (h->zne.empty()) { h->last_error = "no contour set"; return FEASTHIP_ERROR_FPM; }
     FH_CHECK(hipSetDevice(h->device));
     const int m = (int)m64, ld = fh_pick_ld(m), N = (int)fh_N(h);
@@ -2894,6 +2986,7 @@ extern "C" int feasthip_rr_reduce_resident(feasthip_handle h, int64_t m64, doubl
     int rc = fh_check_problem(h, m64);
     if (rc) return rc;
     if (!rank || !Aq_host || !Bq_host) { h->last_error = "rr_reduce_resident: null argument"; return FEASTHIP_ERROR_INTERNAL; }
+    if ((rc = fh_check_adjoint(h, "rr_reduce_resident", "the resident loop has no adjoint form"))) return rc;
     FH_CHECK(hipSetDevice(h->device));
     const int m = (int)m64, N = (int)fh_N(h);
     cplx *Pb, *Xb, *Rb;
@@ -3002,6 +3095,7 @@ extern "C" int feasthip_rr_ritz_resident(feasthip_handle h, int64_t r64, const v
     int rc = fh_check_problem(h, r64);
     if (rc) return rc;
     if (!V_host || !lambda_host) { h->last_error = "rr_ritz_resident: null argument"; return FEASTHIP_ERROR_INTERNAL; }
+    if ((rc = fh_check_adjoint(h, "rr_ritz_resident", "the resident loop has no adjoint form"))) return rc;
     if (M < 0 || M > r64) { h->last_error = "rr_ritz_resident: M out of range"; return FEASTHIP_ERROR_M0; }
     FH_CHECK(hipSetDevice(h->device));
     const int r = (int)r64, N = (int)fh_N(h);
@@ -3192,6 +3286,7 @@ extern "C" int feasthip_rayleigh_ritz_dev(feasthip_handle h, int64_t r64, const 
     int rc = fh_check_problem(h, r64);
     if (rc) return rc;
     if (!dQ || !dX || !lambda_out || !M_out) { h->last_error = "rayleigh_ritz: null argument"; return FEASTHIP_ERROR_INTERNAL; }
+    if ((rc = fh_check_adjoint(h, "rayleigh_ritz", "the Hermitian reduced eigensolver has no two-sided form"))) return rc;
     const int r = (int)r64, ld = FH_MAX_LD;
     std::vector<cplx> Sq((size_t)r * r), Aq((size_t)r * r);
     if ((rc = feasthip_project_dev(h, r64, dQ, 0, 1, Sq.data(), Aq.data()))) return rc;
@@ -3262,6 +3357,7 @@ extern "C" int feasthip_matmul_dev(feasthip_handle h, int which, int64_t m64, co
     int rc = fh_check_problem(h, m64);
     if (rc) return rc;
     if (!dX || !dY || (which != 0 && which != 1)) { h->last_error = "matmul: bad argument"; return FEASTHIP_ERROR_INTERNAL; }
+    if ((rc = fh_check_adjoint(h, "matmul"))) return rc;
     FH_CHECK(hipSetDevice(h->device));
     const int m = (int)m64, ld = fh_pick_ld(m), N = (int)fh_N(h);
     const size_t panel = (size_t)N * ld;
@@ -3290,6 +3386,7 @@ extern "C" int feasthip_matmul(feasthip_handle h, int which, int64_t m, const vo
     int rc = fh_check_problem(h, m, 1);
     if (rc) return rc;
     if (!X || !Y) { h->last_error = "matmul: null argument"; return FEASTHIP_ERROR_INTERNAL; }
+    if ((rc = fh_check_adjoint(h, "matmul"))) return rc;
     FH_CHECK(hipSetDevice(h->device));
     const size_t nb = (size_t)fh_N(h) * m * sizeof(cplx);
     void *dX, *dY;
@@ -3326,6 +3423,7 @@ extern "C" int feasthip_shifted_solve_dev(feasthip_handle h, double z_re, double
     int rc = fh_check_problem(h, m64);
     if (rc) return rc;
     if (!dX || !dY) { h->last_error = "shifted_solve: null argument"; return FEASTHIP_ERROR_INTERNAL; }
+    if ((rc = fh_check_adjoint(h, "shifted_solve"))) return rc;
     FH_CHECK(hipSetDevice(h->device));
     const int m = (int)m64, ld = fh_pick_ld(m), N = (int)fh_N(h);
     const size_t panel = (size_t)N * ld;
@@ -3373,6 +3471,7 @@ extern "C" int feasthip_shifted_solve(feasthip_handle h, double z_re, double z_i
     int rc = fh_check_problem(h, m, 1);
     if (rc) return rc;
     if (!X || !Y) { h->last_error = "shifted_solve: null argument"; return FEASTHIP_ERROR_INTERNAL; }
+    if ((rc = fh_check_adjoint(h, "shifted_solve"))) return rc;
     FH_CHECK(hipSetDevice(h->device));
     const size_t nb = (size_t)fh_N(h) * m * sizeof(cplx);
     void *dX, *dY;

@@ -146,6 +146,7 @@ struct feasthip_ctx {
     std::vector<cplx> zne, wne;
     double weight_scale = 2.0;
     int real_projection = 0;
+    int adjoint = 0;              // feasthip_set_adjoint: sweeps, solves, products and residuals act with the conjugate transposes
     int node_first = 0, node_count = 0;
     std::vector<int> node_ids;      // local node -> contour index (set by range or list)
     std::vector<int> node_kinds;    // feasthip_set_node_solver: per CONTOUR node, 0 = the handle's solver, FEASTHIP_SOLVER_BANDED = direct; empty = none

@@ -281,6 +281,151 @@ void fh_launch_dense_op(const fh_dense_op_args& a, int ld, int nblk, hipStream_t
     }
 }
 
+// Adjoint form of k_dense_op_mfma (two-sided FEAST):  Y = (cb B^H + ca A^H) X.  Same tiling, LDS staging of the panel rows
+// and block numbering; only the matrix operand differs: lane (lr, lk) feeds op^H(irow, j) = conj(M[j + irow N]), i.e. it
+// walks column irow of the stored matrix, so the 16 lanes of a k-group read 16 columns (stride N) and the four k-groups four
+// consecutive rows -- 64 B (complex) or 32 B (real) contiguous per column and load, every 128 B line shared by the loads of two
+// (four) consecutive k-steps of the same wave.  The operand is read transposed straight from global memory; staging it
+// through LDS is not built.
+template <typename VT, int LD, bool BIDENT, int TRB>
+__global__ __launch_bounds__(FH_BLOCK) void k_dense_op_mfma_adj(fh_dense_op_args a, int row_tiles) {
+    constexpr int KC = DOP_KC, CT = LD / 16, NCG = 4 / TRB, TPW = CT / NCG, XPT = KC * LD / FH_BLOCK;
+    constexpr bool CPLX = sizeof(VT) == sizeof(cplx);
+    static_assert(TPW >= 1 && XPT >= 1, "tile split");
+    __shared__ double Xre[KC][LD + DOP_PAD];
+    __shared__ double Xim[KC][LD + DOP_PAD];
+    const int b = blockIdx.x;
+    const int rt = (b & 7) + 8 * ((b >> 3) / a.nodes);
+    const int node = (b >> 3) % a.nodes;
+    if (rt >= row_tiles) return;
+    if (a.node_active && a.node_active[node] == 0) return;
+    const int N = a.N;
+    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+    const int lr = lane & 15, lk = lane >> 4;
+    const int band = w % TRB, cg = w / TRB;
+    const int i0 = rt * (16 * TRB);
+    const int irow = i0 + 16 * band + lr;          // row of op^H = column of the stored matrix
+    const cplx* X = a.X + (size_t)node * a.x_node_stride;
+    cplx* Y = a.Y + (size_t)node * a.y_node_stride;
+    const VT* A = (const VT*)a.A;
+    const VT* B = (const VT*)a.B;
+    dop_v4d aR[TPW], aI[TPW], bR[BIDENT ? 1 : TPW], bI[BIDENT ? 1 : TPW];
+#pragma unroll
+    for (int q = 0; q < TPW; ++q) {
+        aR[q] = dop_v4d{0, 0, 0, 0}; aI[q] = dop_v4d{0, 0, 0, 0};
+        if (!BIDENT) { bR[q] = dop_v4d{0, 0, 0, 0}; bI[q] = dop_v4d{0, 0, 0, 0}; }
+    }
+    cplx xn[XPT];
+    double are[KC / 4], aim[KC / 4], bre[KC / 4], bim[KC / 4];
+    auto load_chunk = [&](int j0) {
+#pragma unroll
+        for (int q = 0; q < XPT; ++q) {
+            const int e = t + q * FH_BLOCK, jj = e / LD, c = e % LD;
+            xn[q] = (j0 + jj < N) ? X[(size_t)(j0 + jj) * LD + c] : cmake(0, 0);
+        }
+#pragma unroll
+        for (int s = 0; s < KC / 4; ++s) {
+            const int j = j0 + 4 * s + lk;
+            const bool ok = irow < N && j < N;
+            if constexpr (CPLX) {
+                cplx v = ok ? A[(size_t)irow * N + j] : cmake(0, 0);
+                are[s] = v.x; aim[s] = -v.y;
+                if (!BIDENT) { cplx u = ok ? B[(size_t)irow * N + j] : cmake(0, 0); bre[s] = u.x; bim[s] = -u.y; }
+            } else {
+                are[s] = ok ? A[(size_t)irow * N + j] : 0.0;
+                if (!BIDENT) bre[s] = ok ? B[(size_t)irow * N + j] : 0.0;
+            }
+        }
+    };
+    load_chunk(0);
+    for (int j0 = 0; j0 < N; j0 += KC) {
+#pragma unroll
+        for (int q = 0; q < XPT; ++q) {
+            const int e = t + q * FH_BLOCK, jj = e / LD, c = e % LD;
+            Xre[jj][c] = xn[q].x; Xim[jj][c] = xn[q].y;
+        }
+        double cre[KC / 4], cim[KC / 4], dre[KC / 4], dim_[KC / 4];
+#pragma unroll
+        for (int s = 0; s < KC / 4; ++s) { cre[s] = are[s]; cim[s] = aim[s]; dre[s] = bre[s]; dim_[s] = bim[s]; }
+        __syncthreads();
+        if (j0 + KC < N) load_chunk(j0 + KC);
+#pragma unroll
+        for (int s = 0; s < KC / 4; ++s) {
+            double xr[TPW], xi[TPW];
+#pragma unroll
+            for (int q = 0; q < TPW; ++q) {
+                xr[q] = Xre[4 * s + lk][16 * (cg * TPW + q) + lr];
+                xi[q] = Xim[4 * s + lk][16 * (cg * TPW + q) + lr];
+            }
+#pragma unroll
+            for (int q = 0; q < TPW; ++q) aR[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(cre[s], xr[q], aR[q], 0, 0, 0);
+#pragma unroll
+            for (int q = 0; q < TPW; ++q) aI[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(cre[s], xi[q], aI[q], 0, 0, 0);
+            if constexpr (CPLX) {
+#pragma unroll
+                for (int q = 0; q < TPW; ++q) aR[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(-cim[s], xi[q], aR[q], 0, 0, 0);
+#pragma unroll
+                for (int q = 0; q < TPW; ++q) aI[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(cim[s], xr[q], aI[q], 0, 0, 0);
+            }
+            if constexpr (!BIDENT) {
+#pragma unroll
+                for (int q = 0; q < TPW; ++q) bR[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(dre[s], xr[q], bR[q], 0, 0, 0);
+#pragma unroll
+                for (int q = 0; q < TPW; ++q) bI[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(dre[s], xi[q], bI[q], 0, 0, 0);
+                if constexpr (CPLX) {
+#pragma unroll
+                    for (int q = 0; q < TPW; ++q) bR[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(-dim_[s], xi[q], bR[q], 0, 0, 0);
+#pragma unroll
+                    for (int q = 0; q < TPW; ++q) bI[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(dim_[s], xr[q], bI[q], 0, 0, 0);
+                }
+            }
+        }
+        __syncthreads();
+    }
+#pragma unroll
+    for (int q = 0; q < TPW; ++q) {
+        const int c = 16 * (cg * TPW + q) + lr;
+        const cplx ca = a.coefA[node * LD + c], cb = a.coefB[node * LD + c];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int i = i0 + 16 * band + lk + 4 * r;
+            if (i >= N) continue;
+            cplx y = cmul(ca, cmake(aR[q][r], aI[q][r]));
+            if (BIDENT) cfma(y, cb, X[(size_t)i * LD + c]); else cfma(y, cb, cmake(bR[q][r], bI[q][r]));
+            if (a.Bvec) y = csub(a.Bvec[(size_t)node * a.b_node_stride + (size_t)i * LD + c], y);
+            Y[(size_t)i * LD + c] = y;
+        }
+    }
+}
+
+template <typename VT, int LD, int TRB>
+static void launch_dense_op_mfma_adj(const fh_dense_op_args& a, hipStream_t st) {
+    const int row_tiles = (a.N + 16 * TRB - 1) / (16 * TRB);
+    const int groups = (row_tiles + 7) / 8;
+    dim3 grid(8 * a.nodes * groups), block(FH_BLOCK);
+    if (a.B == nullptr) hipLaunchKernelGGL((k_dense_op_mfma_adj<VT, LD, true, TRB>), grid, block, 0, st, a, row_tiles);
+    else hipLaunchKernelGGL((k_dense_op_mfma_adj<VT, LD, false, TRB>), grid, block, 0, st, a, row_tiles);
+}
+template <typename VT, int LD>
+static void launch_dense_op_adj_ld(const fh_dense_op_args& a, hipStream_t st) {
+    if constexpr (LD >= 32) {
+        if ((long)a.nodes * ((a.N + 63) / 64) < 256) { launch_dense_op_mfma_adj<VT, LD, 2>(a, st); return; }
+    }
+    launch_dense_op_mfma_adj<VT, LD, 4>(a, st);
+}
+// plain products only (dot_mode 0); the caller has checked that
+void fh_launch_dense_op_adjoint(const fh_dense_op_args& a, int ld, hipStream_t st) {
+    if (a.is_complex) {
+        if (ld == 16) launch_dense_op_adj_ld<cplx, 16>(a, st);
+        else if (ld == 32) launch_dense_op_adj_ld<cplx, 32>(a, st);
+        else launch_dense_op_adj_ld<cplx, 64>(a, st);
+    } else {
+        if (ld == 16) launch_dense_op_adj_ld<double, 16>(a, st);
+        else if (ld == 32) launch_dense_op_adj_ld<double, 32>(a, st);
+        else launch_dense_op_adj_ld<double, 64>(a, st);
+    }
+}
+
 __global__ __launch_bounds__(FH_BLOCK) void k_axpy_cols(cplx* __restrict__ R, const cplx* __restrict__ X,
                                                          const cplx* __restrict__ lam, size_t total, int ld,
                                                          const int* __restrict__ skip) {
@@ -1460,6 +1605,170 @@ __global__ __launch_bounds__(FH_BLOCK) void k_solve_update(T* const* LUs, T* IN,
     }
 }
 
+// Adjoint substitution on the same factors (ZGETRS 'C', two-sided FEAST):  with P S = L U,  S^H y = b  is
+//   U^H w = b   ascending over the 128-blocks   (U^H is lower triangular),
+//   L^H v = w   descending                      (L^H is unit upper triangular),
+//   y[perm[i]] = v[i].
+// k_solve_diag_inv_adj: the product with the conjugate transpose of a stored 128 x 128 inverse.  UPPER names the stored
+// inverse (true: U's), the triangle the product sees is the other one, and the operand of output tile `tile` and 16-block
+// `blk` is read as conj(inv[col][row]): lane (lr, lk) takes row 16 tile + lr of the transpose, i.e. stored column 16 tile + lr,
+// four consecutive stored rows per k-group (64 B contiguous per lane group of four k-groups).
+template <int LD, bool UPPER, typename T>
+__global__ __launch_bounds__(FH_BLOCK) void k_solve_diag_inv_adj(T* const* LUs, T* IN, T* OUT, size_t stride, lu_geom g, int K0, int kb) {
+    constexpr int NT = SOLVE_KB / 16;
+    constexpr bool UP = !UPPER;                  // triangle of the transposed inverse
+    const T* inv = LUs[blockIdx.y] + g.inv128 + ((size_t)(K0 / SOLVE_KB) * 2 + (UPPER ? 1 : 0)) * SOLVE_KB * SOLVE_KB;
+    const T* in = IN + (size_t)blockIdx.y * stride;
+    T* out = OUT + (size_t)blockIdx.y * stride;
+    const int ta = blockIdx.x;
+    __shared__ T S[SOLVE_KB][17];
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int lr = lane & 15, lk = lane >> 4;
+    const int t0 = wave, t1 = NT - 1 - wave;
+    const int n0 = UP ? NT - t0 : t0 + 1;
+    const int blo0 = UP ? t0 : 0, blo1 = UP ? t1 : 0;
+    T a[NT + 1][4];
+#pragma unroll
+    for (int q = 0; q <= NT; ++q) {
+        const int tile = q < n0 ? t0 : t1, blk = q < n0 ? blo0 + q : blo1 + q - n0;
+#pragma unroll
+        for (int s4 = 0; s4 < 4; ++s4) {
+            const T v = inv[(size_t)(16 * tile + lr) * SOLVE_KB + 16 * blk + 4 * s4 + lk];
+            a[q][s4] = LU_MK(v.x, -v.y);
+        }
+    }
+    for (int e = t; e < SOLVE_KB * 16; e += FH_BLOCK) {
+        const int i = e >> 4, c = e & 15, row = K0 + i;
+        S[i][c] = (i < LU_NB * kb && row < g.n) ? in[(size_t)row * LD + 16 * ta + c] : LU_MK(0, 0);
+    }
+    __syncthreads();
+    typename lu_el<T>::v4 re0 = {0, 0, 0, 0}, im0 = {0, 0, 0, 0}, re1 = {0, 0, 0, 0}, im1 = {0, 0, 0, 0};
+#pragma unroll
+    for (int q = 0; q <= NT; ++q) {
+        const int blk = q < n0 ? blo0 + q : blo1 + q - n0;
+#pragma unroll
+        for (int s4 = 0; s4 < 4; ++s4) {
+            const T b = S[16 * blk + 4 * s4 + lk][lr];
+            if (q < n0) {
+                re0 = lu_el<T>::mfma(a[q][s4].x, b.x, re0);
+                re0 = lu_el<T>::mfma(-a[q][s4].y, b.y, re0);
+                im0 = lu_el<T>::mfma(a[q][s4].x, b.y, im0);
+                im0 = lu_el<T>::mfma(a[q][s4].y, b.x, im0);
+            } else {
+                re1 = lu_el<T>::mfma(a[q][s4].x, b.x, re1);
+                re1 = lu_el<T>::mfma(-a[q][s4].y, b.y, re1);
+                im1 = lu_el<T>::mfma(a[q][s4].x, b.y, im1);
+                im1 = lu_el<T>::mfma(a[q][s4].y, b.x, im1);
+            }
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int i0 = 16 * t0 + lu_el<T>::mrow(lk, r), i1 = 16 * t1 + lu_el<T>::mrow(lk, r);
+        if (i0 < LU_NB * kb && K0 + i0 < g.n) out[(size_t)(K0 + i0) * LD + 16 * ta + lr] = LU_MK(re0[r], im0[r]);
+        if (i1 < LU_NB * kb && K0 + i1 < g.n) out[(size_t)(K0 + i1) * LD + 16 * ta + lr] = LU_MK(re1[r], im1[r]);
+    }
+}
+
+// k_solve_update with the factor's block ROW as operand:  IN[i,:] -= sum_{k<kd} conj(LU[K0+k, i]) Z[K0+k,:]  for the rows
+// i in [r0, r1) outside the block (below it in the U^H sweep, above it in the L^H sweep).  Lane (lr, lk) walks stored column
+// ib + lr: 16 columns (stride N) per k-group, the four k-groups four consecutive rows of each.
+template <int LD, typename T>
+__global__ __launch_bounds__(FH_BLOCK) void k_solve_update_adj(T* const* LUs, T* IN, const T* ZS, size_t stride, lu_geom g, int K0,
+                                                                int kd, int r0, int r1, int cta) {
+    typedef decltype(T().x) ET;
+    constexpr int KC = SOLVE_KC, CT = LD / 16, XPT = KC * LD / FH_BLOCK;
+    __shared__ ET Xre[KC][LD + 16];
+    __shared__ ET Xim[KC][LD + 16];
+    const T* A = LUs[blockIdx.y];
+    const int N = g.ld;
+    T* in = IN + (size_t)blockIdx.y * stride;
+    const T* zs = ZS + (size_t)blockIdx.y * stride;
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int lr = lane & 15, lk = lane >> 4;
+    const int ib = r0 + (blockIdx.x * 4 + wave) * 16;
+    const int irow = ib + lr;
+    typename lu_el<T>::v4 re[CT], im[CT];
+#pragma unroll
+    for (int q = 0; q < CT; ++q) { re[q] = typename lu_el<T>::v4{0, 0, 0, 0}; im[q] = typename lu_el<T>::v4{0, 0, 0, 0}; }
+    T xn[XPT], an[KC / 4];
+    auto load_chunk = [&](int j0) {
+#pragma unroll
+        for (int q = 0; q < XPT; ++q) {
+            const int e = t + q * FH_BLOCK, jj = e / LD, c = e % LD;
+            const bool ok = j0 + jj < kd && K0 + j0 + jj < g.n;
+            xn[q] = ok ? zs[(size_t)(K0 + j0 + jj) * LD + c] : LU_MK(0, 0);
+        }
+#pragma unroll
+        for (int s = 0; s < KC / 4; ++s) {
+            const int jk = j0 + 4 * s + lk, col = K0 + jk;
+            const bool ok = irow < r1 && jk < kd && col < g.n;
+            const T v = ok ? A[(size_t)irow * N + col] : LU_MK(0, 0);
+            an[s] = LU_MK(v.x, -v.y);
+        }
+    };
+    load_chunk(0);
+    for (int j0 = 0; j0 < kd; j0 += KC) {
+#pragma unroll
+        for (int q = 0; q < XPT; ++q) {
+            const int e = t + q * FH_BLOCK, jj = e / LD, c = e % LD;
+            Xre[jj][c] = xn[q].x; Xim[jj][c] = xn[q].y;
+        }
+        T ac[KC / 4];
+#pragma unroll
+        for (int s = 0; s < KC / 4; ++s) ac[s] = an[s];
+        __syncthreads();
+        if (j0 + KC < kd) load_chunk(j0 + KC);
+#pragma unroll
+        for (int s = 0; s < KC / 4; ++s) {
+#pragma unroll
+            for (int q = 0; q < CT; ++q) {
+                if (q >= cta) break;
+                const ET xr = Xre[4 * s + lk][16 * q + lr], xi = Xim[4 * s + lk][16 * q + lr];
+                re[q] = lu_el<T>::mfma(ac[s].x, xr, re[q]);
+                im[q] = lu_el<T>::mfma(ac[s].x, xi, im[q]);
+                re[q] = lu_el<T>::mfma(-ac[s].y, xi, re[q]);
+                im[q] = lu_el<T>::mfma(ac[s].y, xr, im[q]);
+            }
+        }
+        __syncthreads();
+    }
+#pragma unroll
+    for (int q = 0; q < CT; ++q) {
+        if (q >= cta) break;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int i = ib + lu_el<T>::mrow(lk, r);
+            if (i < r1) {
+                T* d = in + (size_t)i * LD + 16 * q + lr;
+                const T y = *d;
+                *d = LU_MK(y.x - re[q][r], y.y - im[q][r]);
+            }
+        }
+    }
+}
+
+// Z[node][i,:] = RHS[node][i,:]  (rhs_stride = 0: one shared panel), the unpermuted start of the adjoint substitution
+__global__ __launch_bounds__(FH_BLOCK) void k_copy_panels(const cplx* __restrict__ RHS, size_t rhs_stride, cplx* __restrict__ Z,
+                                                           size_t stride, size_t total) {
+    const cplx* Rn = RHS + (size_t)blockIdx.y * rhs_stride;
+    cplx* Zn = Z + (size_t)blockIdx.y * stride;
+    for (size_t e = (size_t)blockIdx.x * FH_BLOCK + threadIdx.x; e < total; e += (size_t)gridDim.x * FH_BLOCK) Zn[e] = Rn[e];
+}
+
+// Y[node][perm[i],:] = V[node][i,:]: the row permutation of the adjoint solve, applied last (perm is a bijection of [0, N))
+__global__ __launch_bounds__(FH_BLOCK) void k_scatter_perm_rows(const cplx* __restrict__ V, int* const* perms, cplx* __restrict__ Y,
+                                                                 size_t stride, int N, int ld) {
+    const int* perm = perms[blockIdx.y];
+    const cplx* Vn = V + (size_t)blockIdx.y * stride;
+    cplx* Yn = Y + (size_t)blockIdx.y * stride;
+    const size_t total = (size_t)N * ld;
+    for (size_t e = (size_t)blockIdx.x * FH_BLOCK + threadIdx.x; e < total; e += (size_t)gridDim.x * FH_BLOCK) {
+        size_t i = e / ld, c = e % ld;
+        Yn[(size_t)perm[i] * ld + c] = Vn[e];
+    }
+}
+
 // ---------------------------------------------------------------------------------------
 // host orchestration
 // ---------------------------------------------------------------------------------------
@@ -1747,6 +2056,30 @@ static void lu_solve_launch(feasthip_ctx* h, T** dlus, T* Y, T* Z, size_t stride
     }
 }
 
+// Adjoint substitution (fp64 factors, always the two-level 128-column path): Z holds the right-hand side on entry,
+// U^H sweep Z -> Y, L^H sweep Y -> Z; the caller scatters Z by the row permutation.
+template <int LD>
+static void lu_solve_adjoint_launch(feasthip_ctx* h, cplx** dlus, cplx* Y, cplx* Z, size_t stride, int N, int nf, int m) {
+    const int cta = std::max(1, std::min(LD / 16, (m + 15) / 16));
+    const lu_geom geom = lu_dense_geom<cplx>(N);
+    const int nouter = (N + SOLVE_KB - 1) / SOLVE_KB;
+    for (int b = 0; b < nouter; ++b) {        // U^H w = b   (Z -> Y)
+        const int K0 = b * SOLVE_KB, kb = std::min(SOLVE_KB / LU_NB, (N - K0 + LU_NB - 1) / LU_NB);
+        const int r0 = K0 + LU_NB * kb;
+        hipLaunchKernelGGL((k_solve_diag_inv_adj<LD, true, cplx>), dim3(cta, nf), dim3(FH_BLOCK), 0, h->stream, dlus, Z, Y, stride, geom, K0, kb);
+        if (r0 < N)
+            hipLaunchKernelGGL((k_solve_update_adj<LD, cplx>), dim3((N - r0 + 63) / 64, nf), dim3(FH_BLOCK), 0, h->stream, dlus, Z, Y,
+                               stride, geom, K0, LU_NB * kb, r0, N, cta);
+    }
+    for (int b = nouter - 1; b >= 0; --b) {   // L^H v = w   (Y -> Z)
+        const int K0 = b * SOLVE_KB, kb = std::min(SOLVE_KB / LU_NB, (N - K0 + LU_NB - 1) / LU_NB);
+        hipLaunchKernelGGL((k_solve_diag_inv_adj<LD, false, cplx>), dim3(cta, nf), dim3(FH_BLOCK), 0, h->stream, dlus, Y, Z, stride, geom, K0, kb);
+        if (K0 > 0)
+            hipLaunchKernelGGL((k_solve_update_adj<LD, cplx>), dim3((K0 + 63) / 64, nf), dim3(FH_BLOCK), 0, h->stream, dlus, Y, Z,
+                               stride, geom, K0, LU_NB * kb, 0, K0, cta);
+    }
+}
+
 // Solve with the cached factors of `slots`.  RHS: fp64 panel(s), rhs_stride = 0 when one panel is shared by
 // all nodes; Y: fp64 output panels.  T = cplxf: the right-hand side is narrowed while it is permuted, the
 // substitutions run in complex64 and the result is widened into Y (one step of the refinement loop).
@@ -1774,6 +2107,18 @@ static int lu_solve_batch(feasthip_ctx* h, int ld, int m, const std::vector<int>
     FH_CHECK(hipMemcpyAsync(dlus, lus.data(), nf * sizeof(T*), hipMemcpyHostToDevice, h->stream));
     FH_CHECK(hipMemcpyAsync(dperms, perms.data(), nf * sizeof(int*), hipMemcpyHostToDevice, h->stream));
     FH_CHECK(hipStreamSynchronize(h->stream));
+    if constexpr (sizeof(T) == sizeof(cplx)) {
+        if (h->adjoint) {                           // (z B - A)^-H on the same factors; the API layer refuses complex64 factors
+            fh_prof_begin(h, "lu_solve_adjoint");
+            hipLaunchKernelGGL(k_copy_panels, dim3(fh_vec_nblk(N, ld), nf), dim3(FH_BLOCK), 0, h->stream, RHS, rhs_stride, Z, stride, (size_t)N * ld);
+            if (ld == 16) lu_solve_adjoint_launch<16>(h, dlus, Y, Z, stride, N, nf, m);
+            else if (ld == 32) lu_solve_adjoint_launch<32>(h, dlus, Y, Z, stride, N, nf, m);
+            else lu_solve_adjoint_launch<64>(h, dlus, Y, Z, stride, N, nf, m);
+            hipLaunchKernelGGL(k_scatter_perm_rows, dim3(fh_vec_nblk(N, ld), nf), dim3(FH_BLOCK), 0, h->stream, Z, dperms, Y, stride, N, ld);
+            fh_prof_end(h);
+            return 0;
+        }
+    }
     fh_prof_begin(h, "lu_solve");
     hipLaunchKernelGGL((k_gather_rows<T>), dim3(fh_vec_nblk(N, ld), nf), dim3(FH_BLOCK), 0, h->stream, RHS, rhs_stride, dperms, W, stride, N, ld);
     if (ld == 16) lu_solve_launch<16, T>(h, dlus, W, Z, stride, N, nf, m);

@@ -17,12 +17,15 @@ struct fh_dense_op_args {
 };
 int fh_dense_op_nblk(int N);
 void fh_launch_dense_op(const fh_dense_op_args& a, int ld, int nblk, hipStream_t st);
+// Y = (cb*B^H + ca*A^H) X, plain products only (dot_mode 0, MFMA kernel)
+void fh_launch_dense_op_adjoint(const fh_dense_op_args& a, int ld, hipStream_t st);
 
 // R -= X diag(lam)
 void fh_launch_axpy_cols(cplx* R, const cplx* X, const cplx* lam, int N, int ld, hipStream_t st, const int* skip = nullptr);
 
 // Factor (cached per local node when h->cache_factors) and solve all local nodes:
 //   Y[e] = (z_e B - A)^{-1} RHS     RHS: one shared panel; Y: node-strided panels
+// (h->adjoint: (z_e B - A)^{-H} RHS by conjugate-transposed substitution on the same cached fp64 factors)
 int fh_dense_lu_solve_nodes(feasthip_ctx* h, int ld, int m, int nodes, const std::vector<cplx>& z, const cplx* RHS, size_t rhs_stride,
                             cplx* Y, size_t stride, std::vector<int>& status, int64_t* nfact);
 // one-off (uncached) solve for a single shift

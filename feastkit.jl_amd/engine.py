@@ -240,6 +240,12 @@ class HipEngine:
     def set_real_projection(self, on):
         self._chk(self.lib.feasthip_set_real_projection(self.h, int(bool(on))))
 
+    def set_adjoint(self, on):
+        """While on, contour_apply, shifted_solve, matmul and ritz_residual act with the conjugate transposes
+        (feasthip_set_adjoint): the solves reuse the LU factors the forward solves cached.  Dense problems with the
+        direct solver in fp64 only; persists on the engine."""
+        self._chk(self.lib.feasthip_set_adjoint(self.h, int(bool(on))))
+
     def set_node_range(self, first, count):
         self._chk(self.lib.feasthip_set_node_range(self.h, int(first), int(count)))
 
@@ -434,6 +440,16 @@ class HipEngine:
         Bq = np.zeros((r, r), dtype=np.complex128, order="F")
         self._chk(self.lib.feasthip_project_dev(self.h, r, C.c_void_p(dQ.data_ptr()), int(bilinear), int(hermitize),
                                                 _np_ptr(Aq), _np_ptr(Bq)))
+        return Aq, Bq
+
+    def project_pair(self, dQL, dQR, r):
+        """The oblique reduced pencil of the two-sided method: (Q_L^H A Q_R, Q_L^H B Q_R), raw products
+        (feasthip_project_pair_dev; Q_L^H Q_R for B = I)."""
+        self._sync_stream()
+        Aq = np.zeros((r, r), dtype=np.complex128, order="F")
+        Bq = np.zeros((r, r), dtype=np.complex128, order="F")
+        self._chk(self.lib.feasthip_project_pair_dev(self.h, r, C.c_void_p(dQL.data_ptr()), C.c_void_p(dQR.data_ptr()),
+                                                     _np_ptr(Aq), _np_ptr(Bq)))
         return Aq, Bq
 
     def ritz_residual(self, dQ, r, V, lam, M, normalize=True, use_B=True):

@@ -1013,6 +1013,118 @@ def feast_hip_general(engine, A, B, Emid, r, M0, fpm, *, solver="direct", solver
             dQ = dX
 
 
+TWO_SIDED_SOLVERS = ("direct", "lu")
+
+
+def check_two_sided(sparse, solver, inner_precision=64, group=None, direct_nodes=None):
+    """Host-only validation of ``feast_general(..., two_sided=True)`` (no device work): the adjoint sweep exists for dense
+    input with the direct solver in fp64 on one rank."""
+    if sparse:
+        raise ValueError("two_sided needs dense input (no adjoint substitution through the sparse direct factors yet)")
+    if solver not in TWO_SIDED_SOLVERS:
+        raise ValueError(f"two_sided needs the dense direct solver (solver='direct'), not '{solver}'")
+    if inner_precision == 32:
+        raise ValueError("two_sided does not support inner_precision=32 (the adjoint substitution runs on complex128 factors)")
+    if group is not None:
+        raise ValueError("two_sided does not support group= (single-rank sweeps only)")
+    if direct_nodes is not None:
+        raise ValueError("two_sided does not support direct_nodes= (every node is solved directly already)")
+
+
+def feast_hip_general_two_sided(engine, A, B, Emid, r, M0, fpm, *, solver="direct", Q0=None, QL0=None, seed=20260515,
+                                contour=None, eps_floor=0.0):
+    """Two-sided FEAST on a dense pencil: right and left subspaces from the same cached LU factors, oblique projection.
+
+        P_R = sum_e w_e S_e^-1 B Q_R                (forward sweep; factors cached per node)
+        P_L = sum_e conj(w_e) S_e^-H B^H Q_L        (adjoint sweep: conjugate-transposed substitution, no factorisation)
+        Aq = P_L^H A P_R,  Bq = P_L^H B P_R;   lam, V_L, V_R = eig(Aq, Bq)
+        X_R = P_R V_R,  X_L = P_L V_L  (unit columns);  epsout = max_{j < M} max(res_R, res_L), both residuals with B
+
+    The reference validates fpm[15] (one- or two-sided contour, src/core/feast_parameters.jl:217-225) and never reads it, so
+    this driver mirrors nothing: it reports Feast_ERROR_NO_CONVERGENCE when the loop limit ends the run (the last iterates
+    are still returned).  ``q`` holds unit-norm right vectors, ``q_left`` left vectors scaled to y_j^H B x_j = 1; ``res`` is
+    the larger of the two residuals of each pair."""
+    N = A.shape[0]
+    feastdefault(fpm)
+    info = _check_circle_input(N, M0, r)
+    if info:
+        return _empty_result(N, info, complex_lambda=True)
+    check_two_sided(False, solver)
+    Ac, Bc = _complex_pencil(A, B)
+    Zne, Wne = feast_gcontour(Emid, r, fpm) if contour is None else contour
+    world, count = _setup_sweep(engine, None, Ac, Bc, Zne, Wne, 1.0, False)
+    _configure_solver(engine, solver, fpm, 0.0, 500, 30, factor_precision=64)
+    dQR = engine.upload(seeded_subspace(N, M0, seed) if Q0 is None else np.asarray(Q0, dtype=np.complex128))
+    dQL = engine.upload(seeded_subspace(N, M0, seed + 1, complex_values=True) if QL0 is None
+                        else np.asarray(QL0, dtype=np.complex128))
+    eps_tol = max(feast_tolerance(fpm), float(eps_floor))
+    maxloop = int(fpm[4])
+    loop = 0
+    stats = {"krylov_iterations": 0, "factorizations": 0, "solve_seconds": 0.0}
+    ts = {"res_right": [], "res_left": [], "adjoint_factorizations": 0,
+          "seconds": {"forward_sweep": 0.0, "adjoint_sweep": 0.0, "rayleigh_ritz": 0.0}}
+    stats["two_sided"] = ts
+    tick = time.perf_counter
+    engine.set_adjoint(False)
+    try:
+        with small_lapack():
+            while True:
+                t0 = tick()
+                fail, (dPR, _, _) = _sweep(engine, dQR, M0, world, count, stats)
+                t1 = tick()
+                if not fail:
+                    engine.set_adjoint(True)
+                    fail, (dPL, _, st) = _sweep(engine, dQL, M0, world, count, stats)
+                    engine.set_adjoint(False)
+                    ts["adjoint_factorizations"] += int(st.get("factorizations", 0))
+                t2 = tick()
+                ts["seconds"]["forward_sweep"] += t1 - t0
+                ts["seconds"]["adjoint_sweep"] += t2 - t1
+                if fail:
+                    return _empty_result(N, FeastError.Feast_ERROR_LAPACK if fail == 8 else FeastError.Feast_ERROR_NO_CONVERGENCE,
+                                         loop, complex_lambda=True, stats=stats)
+                Aq, Bq = engine.project_pair(dPL, dPR, M0)
+                try:
+                    lam_red, vl_red, vr_red = sla.eig(Aq, Bq, left=True, right=True)
+                except Exception:
+                    return _empty_result(N, FeastError.Feast_ERROR_LAPACK, loop, complex_lambda=True, stats=stats)
+                perm, M = _reorder_by_contour(lam_red, Emid, r, fpm, M0)
+                if M == 0:
+                    return _empty_result(N, FeastError.Feast_ERROR_NO_CONVERGENCE, loop, complex_lambda=True, stats=stats)
+                lam = lam_red[perm]
+                # (Ritz values of the directions the filter has removed come back infinite or undefined from the singular
+                #  reduced pencil; they lie outside the contour and only their vectors are carried along)
+                lam_safe = np.where(np.isfinite(lam), lam, 0.0)
+                dXR, res_r = engine.ritz_residual(dPR, M0, np.asfortranarray(vr_red[:, perm]), lam_safe, M0, normalize=True, use_B=True)
+                engine.set_adjoint(True)
+                dXL, res_l = engine.ritz_residual(dPL, M0, np.asfortranarray(vl_red[:, perm]), lam_safe, M0, normalize=True, use_B=True)
+                engine.set_adjoint(False)
+                res_r, res_l = res_r[:M], res_l[:M]
+                ts["res_right"].append(float(res_r.max()))
+                ts["res_left"].append(float(res_l.max()))
+                epsout = float(max(res_r.max(), res_l.max()))
+                ts["seconds"]["rayleigh_ritz"] += tick() - t2
+                if epsout <= eps_tol or loop >= maxloop:
+                    break
+                loop += 1
+                dQR, dQL = dXR, dXL
+    finally:
+        engine.set_adjoint(False)
+    order = sorted(range(M), key=lambda i: abs(lam[i]) ** 2)             # feast_sort_general!
+    X = engine.download(dXR, M0)[:, :M][:, order]
+    Y = engine.download(dXL, M0)[:, :M][:, order]
+    G = Y.conj().T @ (X if Bc is None else Bc @ X)                          # Y^H B X, M x M, once per solve
+    d = np.diag(G).copy()
+    ts["overlap"] = np.abs(d)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        Y = Y / np.conj(d)[None, :]                                         # y_j^H B x_j = 1
+        Gs = G / d[:, None]
+    ts["biorthogonality"] = float(np.abs(Gs - np.diag(np.diag(Gs))).max()) if M > 1 else 0.0
+    info = 0 if epsout <= eps_tol else int(FeastError.Feast_ERROR_NO_CONVERGENCE)
+    return FeastResult(lam[:M][order].copy(), X.copy(), M, np.maximum(res_r, res_l)[order].copy(), info, epsout, loop, stats,
+                       q_left=Y.copy())
+
+
 def feast_hip_complex_symmetric(engine, A, B, Emid, r, M0, fpm, *, solver="direct", solver_tol=0.0,
                                 solver_maxiter=500, solver_restart=30, group=None, Q0=None, seed=20260515, direct_nodes=None,
                                 ortho="mgs"):

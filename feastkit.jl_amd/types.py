@@ -5,6 +5,7 @@ from __future__ import annotations
 
 import enum
 from dataclasses import dataclass, field
+from typing import Optional
 
 import numpy as np
 
@@ -38,7 +39,8 @@ class FeastRCIJob(enum.IntEnum):
 @dataclass
 class FeastResult:
     """lambda, q, M, res, info, epsout, loop -- same field names as the reference
-    (``lambda`` is a Python keyword, so the attribute is ``lambda_`` with alias ``lam``)."""
+    (``lambda`` is a Python keyword, so the attribute is ``lambda_`` with alias ``lam``).  ``q_left``: the left eigenvectors
+    of a two-sided solve (``feast_general(..., two_sided=True)``), scaled to y_j^H B x_j = 1; None everywhere else."""
     lambda_: np.ndarray
     q: np.ndarray
     M: int
@@ -47,6 +49,7 @@ class FeastResult:
     epsout: float
     loop: int
     stats: dict = field(default_factory=dict)
+    q_left: Optional[np.ndarray] = None
 
     @property
     def lam(self):

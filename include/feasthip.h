@@ -430,6 +430,30 @@ int  feasthip_ritz_residual_dev(feasthip_handle h, int64_t r, const void* dQ, co
                                 const double* lambda_host, int64_t M, int normalize, int use_B,
                                 void* dX, double* res_host);
 
+/* ---- two-sided FEAST: the adjoint switch and the oblique projection ---------------------------------------------------
+ * FEAST's fpm[15] selects a two-sided or a one-sided contour; the reference validates the slot and never reads it
+ * (src/core/feast_parameters.jl:217-225), so nothing here has a counterpart there.
+ * feasthip_set_adjoint: persistent on the handle, off by default.  While it is on
+ *   feasthip_contour_apply[_dev]   Y_e = (z_e B - A)^{-H} (B^H Q),  Qproj = sum_e weight_scale conj(w_e) Y_e  (node range, node
+ *                                  list, node_status as in the forward sweep, weights by global node); zAq / zSq must be NULL;
+ *   feasthip_shifted_solve[_dev]   Y = (z B - A)^{-H} X;
+ *   feasthip_matmul[_dev]          Y = op^H X;
+ *   feasthip_ritz_residual[_dev]   X = Q V,  res_j = ||A^H x_j - conj(lambda_j) B^H x_j|| / max(|lambda_j|, 1)  (use_B = 0 omits
+ *                                  B^H as the forward form omits B).
+ *   The solves are conjugate-transposed substitutions (ZGETRS 'C') on the LU factors the forward solves cache, matched by z_e
+ *   in the same slots: an adjoint sweep after a forward sweep on the same contour reports stats.factorizations == 0.
+ *   While it is on, FEASTHIP_ERROR_FPM (feasthip_last_error names the reason, nothing is computed) answers: a CSR problem,
+ *   a solver other than FEASTHIP_SOLVER_LU, factor_precision = 32, the real projection, a non-NULL moment matrix, an attached
+ *   communicator, the resident entry points, feasthip_estimate_count and feasthip_rayleigh_ritz_dev.
+ *   Every other entry point is unaffected: feasthip_project[_dev] and feasthip_project_pair[_dev] always apply A and B
+ *   themselves, feasthip_orthonormalize[_dev] applies no operator.
+ * feasthip_project_pair[_dev]: the raw products Aq = Q_L^H A Q_R and Bq = Q_L^H B Q_R (Q_L^H Q_R for B = I) of two N x r
+ *   blocks (c128 column-major; r > 64 in 64-column panels); Aq, Bq: r x r c128 column-major HOST buffers, Bq may be NULL.
+ *   Independent of the adjoint switch.                                                                                    */
+int  feasthip_set_adjoint(feasthip_handle h, int on);
+int  feasthip_project_pair(feasthip_handle h, int64_t r, const void* QL, const void* QR, void* Aq, void* Bq);
+int  feasthip_project_pair_dev(feasthip_handle h, int64_t r, const void* dQL, const void* dQR, void* Aq_host, void* Bq_host);
+
 /* ---- RCI / matrix-free seams -------------------------------------- */
 /* Rayleigh-Ritz step with the reduced eigenproblem on the device:
  * feasthip_project, then the Hermitian-definite r x r pencil is solved by a Jacobi eigensolver in LDS
