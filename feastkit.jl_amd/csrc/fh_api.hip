@@ -644,13 +644,8 @@ static int fh_upload_small(feasthip_ctx* h, void* dst, const void* src, size_t b
 
 // upload per-column coefficient arrays [nodes][ld]
 static int fh_upload_coefs(feasthip_ctx* h, const char* name, const std::vector<cplx>& host, cplx** dev) {
-    void* p = nullptr;
-    const size_t bytes = host.size() * sizeof(cplx);
-    int rc = fh_get_buf(h, name, bytes, &p);
-    if (rc) return rc;
-    if ((rc = fh_upload_small(h, p, host.data(), bytes))) return rc;
-    *dev = (cplx*)p;
-    return 0;
+    const int rc = fh_buf(h, name, host.size(), dev);
+    return rc ? rc : fh_upload_small(h, *dev, host.data(), host.size() * sizeof(cplx));
 }
 
 // shifted-operator coefficients S_e = z_e B - A as [nodes][ld] arrays: coefA = -1, coefB = z_e in every column of node e
@@ -669,12 +664,12 @@ static int fh_upload_col_mask(feasthip_ctx* h, int ld, const int** mask) {
     if (!h->mask_live || h->col_mask.empty()) return 0;
     std::vector<int> mk(ld, 1);
     for (int c = 0; c < ld && c < (int)h->col_mask.size(); ++c) mk[c] = h->col_mask[c];
-    void* p;
-    const int rc = fh_get_buf(h, "kry_colmask", ld * sizeof(int), &p);
+    int* dmk;
+    const int rc = fh_buf(h, "kry_colmask", ld, &dmk);
     if (rc) return rc;
-    FH_CHECK(hipMemcpyAsync(p, mk.data(), ld * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    FH_CHECK(hipMemcpyAsync(dmk, mk.data(), ld * sizeof(int), hipMemcpyHostToDevice, h->stream));
     FH_CHECK(hipStreamSynchronize(h->stream));
-    *mask = (const int*)p;
+    *mask = dmk;
     return 0;
 }
 
@@ -693,11 +688,11 @@ static int fh_upload_ritz_lambda(feasthip_ctx* h, const double* ritz_lambda, int
     if (!ritz_lambda) return 0;
     std::vector<double> lam(ld, 0.0);
     for (int c = 0; c < m; ++c) lam[c] = ritz_lambda[c];
-    void* p;
-    const int rc = fh_get_buf(h, "ca_lam", ld * sizeof(double), &p);
+    double* dl;
+    const int rc = fh_buf(h, "ca_lam", ld, &dl);
     if (rc) return rc;
-    FH_CHECK(hipMemcpy(p, lam.data(), ld * sizeof(double), hipMemcpyHostToDevice));
-    *dlam = (double*)p;
+    FH_CHECK(hipMemcpy(dl, lam.data(), ld * sizeof(double), hipMemcpyHostToDevice));
+    *dlam = dl;
     return 0;
 }
 
@@ -874,21 +869,20 @@ struct fh_krylov_work {
 int fh_krylov_work::alloc(const std::vector<cplx>& z, const std::vector<cplx>* wnode) {
     const size_t esz = prec == 32 ? sizeof(cplxf) : sizeof(cplx);
     int rc;
-    void* p;
+    char* base;                                  // complex128 or complex64 panels: sized in bytes
     const int nvec = 6 + (prec == 32 ? 2 : 0);
-    if ((rc = fh_get_buf(h, "kry_vecs", (size_t)nvec * nodes * panel * esz, &p))) return rc;
-    char* base = (char*)p;
+    if ((rc = fh_buf(h, "kry_vecs", (size_t)nvec * nodes * panel * esz, &base))) return rc;
     auto vec = [&](int i) { return (void*)(base + (size_t)i * nodes * panel * esz); };
     R = vec(0); Rh = vec(1); P = vec(2); V = vec(3); S = vec(4); T = vec(5);
     if (prec == 32) { D = vec(6); RHS32 = vec(7); }
     const size_t nl = (size_t)nodes * ld;
-    if ((rc = fh_get_buf(h, "kry_scal_c", 4 * nl * sizeof(cplx), &p))) return rc;
-    s.rho = (cplx*)p; s.alpha = s.rho + nl; s.omega = s.alpha + nl; s.beta = s.omega + nl;
-    if ((rc = fh_get_buf(h, "kry_scal_d", 5 * nl * sizeof(double), &p))) return rc;
-    s.r0norm = (double*)p; s.target = s.r0norm + nl; s.rnorm = s.target + nl;
+    if ((rc = fh_buf(h, "kry_scal_c", 4 * nl, &s.rho))) return rc;
+    s.alpha = s.rho + nl; s.omega = s.alpha + nl; s.beta = s.omega + nl;
+    if ((rc = fh_buf(h, "kry_scal_d", 5 * nl, &s.r0norm))) return rc;
+    s.target = s.r0norm + nl; s.rnorm = s.target + nl;
     r0_64 = s.rnorm + nl; inv_r0 = r0_64 + nl;
-    if ((rc = fh_get_buf(h, "kry_scal_i", (4 * nl + 2 * nodes + 4) * sizeof(int), &p))) return rc;
-    s.active = (int*)p; s.iters = s.active + nl; s.status = s.iters + nl; s.node_active = s.status + nl;
+    if ((rc = fh_buf(h, "kry_scal_i", 4 * nl + 2 * nodes + 4, &s.active))) return rc;
+    s.iters = s.active + nl; s.status = s.iters + nl; s.node_active = s.status + nl;
     // Fused COCG iteration (fh_sparse.hip): SpMM with five dots -> one finalize -> one vector kernel.  CSR operator through
     // the gather kernel only; FH_COCG_FUSED=0 selects the five-launch form for comparison.
     fused = method == 1 && h->kind == 2 && fh_knob::cocg_fused();
@@ -902,14 +896,14 @@ int fh_krylov_work::alloc(const std::vector<cplx>& z, const std::vector<cplx>* w
     nblk_vec = fh_kry_nblk(N, ld, nodes);
     if (fused) { fv_rows = fh_fused_vec_rows(N, ld, prec == 32); fv1_rows = fh_fused_vec_rows(N, ld, 1); }
     const int nblk_max = std::max(std::max(std::max(nblk_op, nblk_vec), fv_rows), fv1_rows);
-    if ((rc = fh_get_buf(h, "kry_partials", 2 * (size_t)nodes * nblk_max * ld * sizeof(cplx), &p))) return rc;
-    part1 = (cplx*)p; part2 = part1 + (size_t)nodes * nblk_max * ld;
+    if ((rc = fh_buf(h, "kry_partials", 2 * (size_t)nodes * nblk_max * ld, &part1))) return rc;
+    part2 = part1 + (size_t)nodes * nblk_max * ld;
     if (fused) {
         const size_t one = (size_t)nodes * nblk_op * ld;
-        if ((rc = fh_get_buf(h, "kry_partials_op", 2 * one * sizeof(cplx), &p))) return rc;
-        for (int q = 0; q < 2; ++q) sp[q] = (cplx*)p + q * one;
-        if ((rc = fh_get_buf(h, "kry_tickets", (size_t)nodes * sizeof(unsigned long long), &p))) return rc;
-        ff.s = s; ff.rho = part1; ff.rr = part2; ff.tickets = (unsigned long long*)p;
+        if ((rc = fh_buf(h, "kry_partials_op", 2 * one, &sp[0]))) return rc;
+        sp[1] = sp[0] + one;
+        if ((rc = fh_buf(h, "kry_tickets", (size_t)nodes, &ff.tickets))) return rc;
+        ff.s = s; ff.rho = part1; ff.rr = part2;
         FH_CHECK(hipMemsetAsync(ff.tickets, 0, (size_t)nodes * sizeof(unsigned long long), h->stream));
     }
     cplx *dca, *dcb;
@@ -937,8 +931,8 @@ int fh_krylov_work::start(const std::vector<cplx>& z, const cplx* RHS, cplx* X, 
     int rc;
     Xk = X;
     const bool shared_start = opt.shared_src && sum_acc && method == 1 && prec == 64;
-    void* R64 = R;                               // mixed precision: the fp64 residual goes to a panel set of its own
-    if (!shared_start && prec == 32 && (rc = fh_get_buf(h, "kry_r64", (size_t)nodes * panel * sizeof(cplx), &R64))) return rc;
+    cplx* R64 = (cplx*)R;                        // mixed precision: the fp64 residual goes to a panel set of its own
+    if (!shared_start && prec == 32 && (rc = fh_buf(h, "kry_r64", (size_t)nodes * panel, &R64))) return rc;
     if (!shared_start) {
         // R = RHS - S X0, ||R||^2
         oc.prec = 64; oc.X = X; oc.x_stride = panel; oc.Y = R64; oc.y_stride = panel; oc.Bvec = RHS; oc.b_stride = 0;
@@ -952,7 +946,7 @@ int fh_krylov_work::start(const std::vector<cplx>& z, const cplx* RHS, cplx* X, 
         fh_launch_fin_init(f0, ld, nodes, h->stream);
         FH_CHECK(hipMemcpyAsync(r0_64, s.r0norm, nl * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
         // narrow: RHS32 = R64 / ||r0||, D = 0, R = RHS32
-        fh_launch_narrow_scaled((const cplx*)R64, panel, (cplxf*)RHS32, panel, r0_64, N, ld, nblk_vec, nodes, h->stream);
+        fh_launch_narrow_scaled(R64, panel, (cplxf*)RHS32, panel, r0_64, N, ld, nblk_vec, nodes, h->stream);
         FH_CHECK(hipMemsetAsync(D, 0, (size_t)nodes * panel * sizeof(cplxf), h->stream));
         FH_CHECK(hipMemcpyAsync(R, RHS32, (size_t)nodes * panel * sizeof(cplxf), hipMemcpyDeviceToDevice, h->stream));
         Xk = D;
@@ -1096,24 +1090,23 @@ static int fh_shifted_cocg(feasthip_ctx* h, int ld, int m, int nodes, const std:
     const size_t nl = (size_t)nodes * ld;
     const int ntiles = ld / 16;
     int rc;
-    void* p;
     int seed = 0;
     for (int e = 1; e < nodes; ++e)
         if (fabs(z[e].y) < fabs(z[seed].y)) seed = e;
     fh_shift_args a;
     memset(&a, 0, sizeof(a));
     a.N = N; a.nodes = nodes; a.seed = seed; a.m = m; a.node_stride = panel;
-    if ((rc = fh_get_buf(h, "shc_vecs", (size_t)(2 + nodes) * panel * sizeof(cplx), &p))) return rc;
-    a.R = (cplx*)p; a.Qv = a.R + panel; a.P = a.Qv + panel;
+    if ((rc = fh_buf(h, "shc_vecs", (size_t)(2 + nodes) * panel, &a.R))) return rc;
+    a.Qv = a.R + panel; a.P = a.Qv + panel;
     a.sum_acc = sum_acc; a.src = shared_src;
-    if ((rc = fh_get_buf(h, "shc_scal_c", (5 * nl + 2 * (size_t)ld) * sizeof(cplx), &p))) return rc;
-    a.pi = (cplx*)p; a.pi_old = a.pi + nl; a.coef = a.pi_old + nl; a.ipi = a.coef + nl; a.beta_e = a.ipi + nl;
+    if ((rc = fh_buf(h, "shc_scal_c", 5 * nl + 2 * (size_t)ld, &a.pi))) return rc;
+    a.pi_old = a.pi + nl; a.coef = a.pi_old + nl; a.ipi = a.coef + nl; a.beta_e = a.ipi + nl;
     a.alpha = a.beta_e + nl; a.beta = a.alpha + ld;
-    if ((rc = fh_get_buf(h, "shc_scal_d", 3 * nl * sizeof(double), &p))) return rc;
-    a.r0norm = (double*)p; a.target = a.r0norm + nl; a.rnorm = a.target + nl;
+    if ((rc = fh_buf(h, "shc_scal_d", 3 * nl, &a.r0norm))) return rc;
+    a.target = a.r0norm + nl; a.rnorm = a.target + nl;
     const size_t nint = 4 * nl + (size_t)ld + (size_t)ntiles * nodes + ntiles + 2;
-    if ((rc = fh_get_buf(h, "shc_scal_i", nint * sizeof(int), &p))) return rc;
-    a.active = (int*)p; a.accum = a.active + nl; a.iters = a.accum + nl; a.status = a.iters + nl;
+    if ((rc = fh_buf(h, "shc_scal_i", nint, &a.active))) return rc;
+    a.accum = a.active + nl; a.iters = a.accum + nl; a.status = a.iters + nl;
     a.col_step = a.status + nl; a.node_step = a.col_step + ld;
     a.tile_alive = a.node_step + (size_t)ntiles * nodes; a.alive_total = a.tile_alive + ntiles; a.passes = a.alive_total + 1;
     FH_CHECK(hipMemsetAsync(a.active, 0, nint * sizeof(int), h->stream));
@@ -1130,8 +1123,8 @@ static int fh_shifted_cocg(feasthip_ctx* h, int ld, int m, int nodes, const std:
     if ((rc = fh_upload_col_mask(h, ld, &a.col_mask))) return rc;
     const int nblk_op = fh_op_nblk(h, ld);
     const int nrow_max = std::max(256, fh_fused_vec_rows(N, ld, 1));
-    if ((rc = fh_get_buf(h, "shc_partials", 2 * (size_t)(nrow_max + nblk_op) * ld * sizeof(cplx), &p))) return rc;
-    a.rho_part = (cplx*)p; a.rr_part = a.rho_part + (size_t)nrow_max * ld;
+    if ((rc = fh_buf(h, "shc_partials", 2 * (size_t)(nrow_max + nblk_op) * ld, &a.rho_part))) return rc;
+    a.rr_part = a.rho_part + (size_t)nrow_max * ld;
     cplx* sp0 = a.rr_part + (size_t)nrow_max * ld;
     cplx* sp1 = sp0 + (size_t)nblk_op * ld;
     a.sig = sp0; a.kap = sp1;
@@ -1179,30 +1172,29 @@ static int fh_block_cocg(feasthip_ctx* h, int ld, int m, int nodes, const std::v
     const int N = (int)fh_N(h);
     const size_t panel = (size_t)N * ld, nl = (size_t)nodes * ld, mat = (size_t)ld * ld;
     int rc;
-    void* p;
     fh_bcocg_args a;
     memset(&a, 0, sizeof(a));
     a.N = N; a.nodes = nodes; a.m = m; a.node_stride = panel; a.sum_acc = sum_acc; a.src = shared_src;
     a.rtol = h->rtol; a.atol = h->atol;
-    if ((rc = fh_get_buf(h, "bcg_vecs", 3 * (size_t)nodes * panel * sizeof(cplx), &p))) return rc;
-    a.Q = (cplx*)p; a.P = a.Q + (size_t)nodes * panel; a.W = a.P + (size_t)nodes * panel;
-    if ((rc = fh_get_buf(h, "bcg_small", (2 + 12 * (size_t)nodes) * mat * sizeof(cplx), &p))) return rc;
-    cplx* sm = (cplx*)p;
+    if ((rc = fh_buf(h, "bcg_vecs", 3 * (size_t)nodes * panel, &a.Q))) return rc;
+    a.P = a.Q + (size_t)nodes * panel; a.W = a.P + (size_t)nodes * panel;
+    cplx* sm;
+    if ((rc = fh_buf(h, "bcg_small", (2 + 12 * (size_t)nodes) * mat, &sm))) return rc;
     auto slot = [&](int i) { return sm + 2 * mat + (size_t)i * nodes * mat; };
     a.SH = sm; a.ST = sm + mat;
     a.GA = slot(0); a.GH = slot(1); a.GT = slot(2); a.T = slot(3); a.Tn = slot(4); a.U = slot(5); a.Ze = slot(6); a.Zi = slot(7);
     a.Cs = slot(8); a.Al = slot(9); a.M1 = slot(10); a.Be = slot(11);
     FH_CHECK(hipMemsetAsync(sm, 0, (2 + 12 * (size_t)nodes) * mat * sizeof(cplx), h->stream));
-    if ((rc = fh_get_buf(h, "bcg_scal_d", 3 * nl * sizeof(double), &p))) return rc;
-    a.r0norm = (double*)p; a.target = a.r0norm + nl; a.rnorm = a.target + nl;
+    if ((rc = fh_buf(h, "bcg_scal_d", 3 * nl, &a.r0norm))) return rc;
+    a.target = a.r0norm + nl; a.rnorm = a.target + nl;
     const size_t nint = 4 * nl + 5 * (size_t)nodes;
-    if ((rc = fh_get_buf(h, "bcg_scal_i", nint * sizeof(int), &p))) return rc;
-    a.active = (int*)p; a.iters = a.active + nl; a.status = a.iters + nl; a.live = a.status + nl;
+    if ((rc = fh_buf(h, "bcg_scal_i", nint, &a.active))) return rc;
+    a.iters = a.active + nl; a.status = a.iters + nl; a.live = a.status + nl;
     a.node_active = a.live + nl; a.stop = a.node_active + nodes; a.steps = a.stop + nodes; a.passes = a.steps + nodes;
     a.nlive = a.passes + nodes;
     FH_CHECK(hipMemsetAsync(a.active, 0, nint * sizeof(int), h->stream));
-    if ((rc = fh_get_buf(h, "bcg_gram", fh_bcocg_gram_work_elems(ld, nodes) * sizeof(cplx), &p))) return rc;
-    cplx* gw = (cplx*)p;
+    cplx* gw;
+    if ((rc = fh_buf(h, "bcg_gram", fh_bcocg_gram_work_elems(ld, nodes), &gw))) return rc;
     cplx *dfs, *dw, *dca, *dcb;
     if ((rc = fh_upload_coefs(h, "bcg_fscale", fh_start_factors(z, nodes, m, ld, lambda_host), &dfs))) return rc;
     if ((rc = fh_upload_coefs(h, "bcg_wnode", wnode, &dw))) return rc;
@@ -1286,7 +1278,7 @@ static int fh_gmres(feasthip_ctx* h, int ld, int m, int nodes_all, const std::ve
     const size_t panel = (size_t)N * ld;
     const int mr = std::max(h->restart, 2);
     int rc;
-    void* p;
+    cplx *V, *W, *part, *npart;
     res.status.assign(nodes_all, 0);
     // node batches: the basis costs (mr + 2) panels per node
     const size_t per_node = (size_t)(mr + 2) * panel * sizeof(cplx);
@@ -1305,8 +1297,7 @@ static int fh_gmres(feasthip_ctx* h, int ld, int m, int nodes_all, const std::ve
     int nbatch = (int)std::max<size_t>(1, std::min<size_t>((size_t)nodes_all, budget / std::max<size_t>(per_node, 1)));
     // an allocation failure halves the batch before it becomes an error
     for (;;) {
-        if (fh_get_buf(h, "gm_V", (size_t)nbatch * (mr + 1) * panel * sizeof(cplx), &p) == 0 &&
-            fh_get_buf(h, "gm_W", (size_t)nbatch * panel * sizeof(cplx), &p) == 0) break;
+        if (fh_buf(h, "gm_V", (size_t)nbatch * (mr + 1) * panel, &V) == 0 && fh_buf(h, "gm_W", (size_t)nbatch * panel, &W) == 0) break;
         if (nbatch == 1) return FEASTHIP_ERROR_MEMORY;
         hipGetLastError();                                   // clear the sticky out-of-memory status
         nbatch = (nbatch + 1) / 2;
@@ -1316,21 +1307,17 @@ static int fh_gmres(feasthip_ctx* h, int ld, int m, int nodes_all, const std::ve
     for (int e0 = 0; e0 < nodes_all; e0 += nbatch) {
         const int nodes = std::min(nbatch, nodes_all - e0);
         const size_t nl = (size_t)nodes * ld;
-        if ((rc = fh_get_buf(h, "gm_V", (size_t)nodes * (mr + 1) * panel * sizeof(cplx), &p))) return rc;
-        cplx* V = (cplx*)p;
-        if ((rc = fh_get_buf(h, "gm_W", (size_t)nodes * panel * sizeof(cplx), &p))) return rc;
-        cplx* W = (cplx*)p;
-        if ((rc = fh_get_buf(h, "gm_part", fh_gm_partial_elems(mr, nblk_vec, nodes, ld) * sizeof(cplx), &p))) return rc;
-        cplx* part = (cplx*)p;
-        if ((rc = fh_get_buf(h, "gm_npart", (size_t)nodes * std::max(nblk_vec, nblk_op) * ld * sizeof(cplx), &p))) return rc;
-        cplx* npart = (cplx*)p;
+        if ((rc = fh_buf(h, "gm_V", (size_t)nodes * (mr + 1) * panel, &V))) return rc;
+        if ((rc = fh_buf(h, "gm_W", (size_t)nodes * panel, &W))) return rc;
+        if ((rc = fh_buf(h, "gm_part", fh_gm_partial_elems(mr, nblk_vec, nodes, ld), &part))) return rc;
+        if ((rc = fh_buf(h, "gm_npart", (size_t)nodes * std::max(nblk_vec, nblk_op) * ld, &npart))) return rc;
         const size_t hsz = nl * (size_t)(mr + 1) * mr;
-        if ((rc = fh_get_buf(h, "gm_small_c", (hsz + nl * (mr + 1) * 2 + nl * mr * 3) * sizeof(cplx), &p))) return rc;
-        cplx* sc = (cplx*)p;
-        if ((rc = fh_get_buf(h, "gm_small_d", nl * 4 * sizeof(double), &p))) return rc;
-        double* sd = (double*)p;
-        if ((rc = fh_get_buf(h, "gm_small_i", (nl * 4 + nodes) * sizeof(int), &p))) return rc;
-        int* si = (int*)p;
+        cplx* sc;
+        double* sd;
+        int* si;
+        if ((rc = fh_buf(h, "gm_small_c", hsz + nl * (mr + 1) * 2 + nl * mr * 3, &sc))) return rc;
+        if ((rc = fh_buf(h, "gm_small_d", nl * 4, &sd))) return rc;
+        if ((rc = fh_buf(h, "gm_small_i", nl * 4 + nodes, &si))) return rc;
         fh_gmres_args ga;
         ga.N = N; ga.mr = mr; ga.panel = panel; ga.V = V; ga.v_node_stride = (size_t)(mr + 1) * panel; ga.W = W;
         ga.partial = part; ga.npartial = npart;
@@ -1424,7 +1411,6 @@ static int fh_dense_lu_refined(feasthip_ctx* h, int ld, int m, int nodes, const 
                                size_t panel, std::vector<int>& status, int64_t* nfact, bool single, double* worst_out, bool banded) {
     const int N = (int)fh_N(h);
     int rc;
-    void* p;
     // banded: the same loop over the complex64 band factors of the sparse direct solver (residual = fp64 SpMM)
     auto solve = [&](const cplx* rhs, size_t rhs_stride, cplx* out, int64_t* nf) -> int {
         if (banded) {
@@ -1437,14 +1423,11 @@ static int fh_dense_lu_refined(feasthip_ctx* h, int ld, int m, int nodes, const 
     if ((rc = solve(Rhs, 0, Y, nfact))) return rc;
     const double tol = std::max(h->rtol, 1e-14);
     if (tol >= 1.0) { if (worst_out) *worst_out = 0.0; return 0; }
-    if ((rc = fh_get_buf(h, "lr_R", (size_t)nodes * panel * sizeof(cplx), &p))) return rc;
-    cplx* R = (cplx*)p;
-    if ((rc = fh_get_buf(h, "lr_D", (size_t)nodes * panel * sizeof(cplx), &p))) return rc;
-    cplx* D = (cplx*)p;
-    if ((rc = fh_get_buf(h, "lr_part", (size_t)fh_vec_nblk(N, ld) * ld * sizeof(cplx), &p))) return rc;
-    cplx* part = (cplx*)p;
-    if ((rc = fh_get_buf(h, "lr_dots", (size_t)(nodes + 1) * ld * sizeof(cplx), &p))) return rc;
-    cplx* ddots = (cplx*)p;
+    cplx *R, *D, *part, *ddots;
+    if ((rc = fh_buf(h, "lr_R", (size_t)nodes * panel, &R))) return rc;
+    if ((rc = fh_buf(h, "lr_D", (size_t)nodes * panel, &D))) return rc;
+    if ((rc = fh_buf(h, "lr_part", (size_t)fh_vec_nblk(N, ld) * ld, &part))) return rc;
+    if ((rc = fh_buf(h, "lr_dots", (size_t)(nodes + 1) * ld, &ddots))) return rc;
     const std::vector<cplx> mone(ld, cmake(-1, 0));
     cplx *dca, *dcb, *dmone;
     if ((rc = fh_upload_shift_coefs(h, "lr_coefA", "lr_coefB", z.data(), nodes, ld, &dca, &dcb))) return rc;
@@ -1557,16 +1540,16 @@ static int fh_shared_start_source(feasthip_ctx* h, const fh_panel_sweep& g, cons
     if (g.io && g.io->eigres) { *src = g.io->eigres; return 0; }      // left behind by the Ritz step of the previous loop
     std::vector<cplx> ca(g.ld, cmake(1, 0)), cb(g.ld, cmake(0, 0));
     for (int c = 0; c < g.m; ++c) cb[c] = cmake(-g.ritz_lambda[c], 0);
-    cplx *dca, *dcb;
-    void* p; int rc;
+    cplx *dca, *dcb, *eigres;
+    int rc;
     if ((rc = fh_upload_coefs(h, "ca_rcoefA", ca, &dca))) return rc;
     if ((rc = fh_upload_coefs(h, "ca_rcoefB", cb, &dcb))) return rc;
-    if ((rc = fh_get_buf(h, "ca_eigres", g.panel * sizeof(cplx), &p))) return rc;
+    if ((rc = fh_buf(h, "ca_eigres", g.panel, &eigres))) return rc;
     fh_op_call oc;
     oc.m = g.m;
-    oc.X = g.Qp; oc.Y = p; oc.coefA = dca; oc.coefB = dcb;
+    oc.X = g.Qp; oc.Y = eigres; oc.coefA = dca; oc.coefB = dcb;
     fh_apply_operator(h, g.ld, oc);                    // A q - lambda B q (B = I handled by the operator kernel)
-    *src = (const cplx*)p;
+    *src = eigres;
     return 0;
 }
 
@@ -1591,7 +1574,7 @@ static int fh_panel_krylov(feasthip_ctx* h, fh_panel_sweep& g, bool want_moments
     if ((rc = fh_upload_ritz_lambda(h, g.ritz_lambda, m, ld, &dlam))) return rc;
     // sum mode: only Q_proj is wanted (no moments), so the per-node solutions are never formed
     if (h->solver == FEASTHIP_SOLVER_COCG && !want_moments && h->sum_mode) {
-        if ((rc = fh_get_buf(h, "ca_acc", panel * sizeof(cplx), (void**)&g.sum_acc))) return rc;
+        if ((rc = fh_buf(h, "ca_acc", panel, &g.sum_acc))) return rc;
         FH_CHECK(hipMemsetAsync(g.sum_acc, 0, panel * sizeof(cplx), h->stream));
     }
     g.sum_shared = g.sum_acc && h->factor_precision == 64 && !fh_knob::no_shared_start();
@@ -1663,19 +1646,16 @@ static void fh_store_sweep_result(feasthip_ctx* h, const fh_solve_result& sr, in
 static int fh_panel_moments(feasthip_ctx* h, const fh_panel_sweep& g, cplx* dzAq, cplx* dzSq, const fh_moment_ctx* mom) {
     const int m = g.m, ld = g.ld, N = g.N;
     int rc;
-    void* p;
-    if ((rc = fh_get_buf(h, "gram_work", fh_gram_work_elems(ld) * sizeof(cplx), &p))) return rc;
-    cplx* gw = (cplx*)p;
-    if ((rc = fh_get_buf(h, "gram_G", (size_t)ld * ld * sizeof(cplx), &p))) return rc;
-    cplx* G = (cplx*)p;
+    cplx *gw, *G;
+    if ((rc = fh_buf(h, "gram_work", fh_gram_work_elems(ld), &gw))) return rc;
+    if ((rc = fh_buf(h, "gram_G", (size_t)ld * ld, &G))) return rc;
     const int m_all = mom ? mom->m_all : m, col0 = mom ? mom->col0 : 0;
     std::vector<cplx> Gh((size_t)ld * ld), aq_local, sq_local;
     if (!mom) { aq_local.assign((size_t)m * m, cmake(0, 0)); sq_local.assign((size_t)m * m, cmake(0, 0)); }
     std::vector<cplx>& aq = mom ? *mom->aq : aq_local;
     std::vector<cplx>& sq = mom ? *mom->sq : sq_local;
     cplx* Qrow = g.Qp;                     // row block of Q in panel layout (the panel's own columns when not wide)
-    if (mom && (rc = fh_get_buf(h, "ca_Qrow", g.panel * sizeof(cplx), &p))) return rc;
-    if (mom) Qrow = (cplx*)p;
+    if (mom && (rc = fh_buf(h, "ca_Qrow", g.panel, &Qrow))) return rc;
     for (int r0 = 0; r0 < m_all; r0 += ld) {
         const int mr_ = std::min(ld, m_all - r0);
         if (mom) fh_launch_to_panel(mom->dQ_all + (size_t)r0 * N, N, N, mr_, Qrow, ld, h->stream, fh_perm(h));
@@ -1718,18 +1698,15 @@ static int fh_contour_apply_panel(feasthip_ctx* h, int64_t m64, const cplx* dQ, 
     const int nodes = g.nodes = h->node_count;
     const size_t panel = g.panel = (size_t)N * ld;
     g.ritz_lambda = ritz_lambda; g.io = io;
-    void* p;
     if (io && io->Qp) {
         g.Qp = const_cast<cplx*>(io->Qp);        // read only below (the right-hand side when B = I)
     } else {
-        if ((rc = fh_get_buf(h, "ca_Qp", panel * sizeof(cplx), &p))) return rc;
-        g.Qp = (cplx*)p;
+        if ((rc = fh_buf(h, "ca_Qp", panel, &g.Qp))) return rc;
         fh_launch_to_panel(dQ, N, N, m, g.Qp, ld, h->stream, fh_perm(h));
     }
     cplx* Outp = io ? io->out : nullptr;
     if (!Outp) {
-        if ((rc = fh_get_buf(h, "ca_out", panel * sizeof(cplx), &p))) return rc;
-        Outp = (cplx*)p;
+        if ((rc = fh_buf(h, "ca_out", panel, &Outp))) return rc;
     }
     if (stats) memset(stats, 0, sizeof(*stats));
     if (nodes == 0) {
@@ -1744,8 +1721,7 @@ static int fh_contour_apply_panel(feasthip_ctx* h, int64_t m64, const cplx* dQ, 
     // src/dense/feast_dense.jl:184 -- it is loop invariant); B^H Q under the adjoint switch (fh_apply_operator)
     g.Rhs = g.Qp;
     if (!fh_b_identity(h)) {
-        if ((rc = fh_get_buf(h, "ca_rhs", panel * sizeof(cplx), &p))) return rc;
-        g.Rhs = (cplx*)p;
+        if ((rc = fh_buf(h, "ca_rhs", panel, &g.Rhs))) return rc;
         std::vector<cplx> ca(ld, cmake(0, 0)), cb(ld, cmake(1, 0));
         cplx *dca, *dcb;
         if ((rc = fh_upload_coefs(h, "ca_coefA", ca, &dca))) return rc;
@@ -1767,8 +1743,8 @@ static int fh_contour_apply_panel(feasthip_ctx* h, int64_t m64, const cplx* dQ, 
         w[i] = cscale(h->wne[h->node_ids[g.order[i]]], h->weight_scale);
         if (h->adjoint) w[i].y = -w[i].y;         // adjoint sweep: Q_proj = sum_e conj(w_e) S_e^-H B^H Q
     }
-    if ((rc = fh_get_buf(h, "ca_Y", (size_t)nodes * panel * sizeof(cplx), &p))) return rc;
-    cplx* Y = g.Y = (cplx*)p;
+    if ((rc = fh_buf(h, "ca_Y", (size_t)nodes * panel, &g.Y))) return rc;
+    cplx* Y = g.Y;
 
     // destroyed on every return path (the solver branches below return early on errors)
     struct ev_guard { hipEvent_t a = nullptr, b = nullptr; ~ev_guard() { if (a) hipEventDestroy(a); if (b) hipEventDestroy(b); } } evg;
@@ -1946,14 +1922,12 @@ static int fh_contour_apply_impl(feasthip_ctx* h, int64_t m64, const cplx* dQ, c
     const size_t total = nq + (dzAq ? nm : 0) + (dzSq ? nm : 0) + 3 * (size_t)ne + 1;
     double* pack = nullptr;
     if (nr > 1) {
-        void* p = nullptr;
-        if ((rc = fh_get_buf(h, "comm_pack", total * sizeof(double), &p))) {
+        if ((rc = fh_buf(h, "comm_pack", total, &pack))) {
             // nothing to reduce into: tell the peers through the transport's own failure path where there is one
             // (shm: the failed flag releases their barriers), then give up -- the caller must treat this as fatal
             fh_comm_mark_failed(h);
             return rc;
         }
-        pack = (double*)p;
     }
     if (!local_rc && !full && !rs) soft(hipMemsetAsync(dQproj, 0, (size_t)N * m * sizeof(cplx), h->stream), "hipMemsetAsync(Q_proj)");
     cplx* rs_out = nullptr;                       // resident form: this rank's block of Q_proj, an N x rs_ldw panel
@@ -1964,19 +1938,18 @@ static int fh_contour_apply_impl(feasthip_ctx* h, int64_t m64, const cplx* dQ, c
         const int w = (int)(c1 - c0);
         rs_ldw = fh_pick_ld(w);
         fh_panel_io io;
-        void* p = nullptr;
-        int brc = fh_get_buf(h, "rs_Osub", (size_t)N * rs_ldw * sizeof(cplx), &p);
-        rs_out = (cplx*)p;
+        cplx* sub = nullptr;
+        int brc = fh_buf(h, "rs_Osub", (size_t)N * rs_ldw, &rs_out);
         if (!brc && full) { io.Qp = rs->Q; io.eigres = rs->eigres; }
         if (!brc && !full) {
             // this rank's columns of the subspace (and of its eigen-residual) as panels of their own
-            if (!(brc = fh_get_buf(h, "rs_Qsub", (size_t)N * rs_ldw * sizeof(cplx), &p))) {
-                fh_launch_panel_cols(rs->Q, rs->ld, (int)c0, w, N, (cplx*)p, rs_ldw, h->stream);
-                io.Qp = (const cplx*)p;
+            if (!(brc = fh_buf(h, "rs_Qsub", (size_t)N * rs_ldw, &sub))) {
+                fh_launch_panel_cols(rs->Q, rs->ld, (int)c0, w, N, sub, rs_ldw, h->stream);
+                io.Qp = sub;
             }
-            if (!brc && rs->eigres && !(brc = fh_get_buf(h, "rs_Esub", (size_t)N * rs_ldw * sizeof(cplx), &p))) {
-                fh_launch_panel_cols(rs->eigres, rs->ld, (int)c0, w, N, (cplx*)p, rs_ldw, h->stream);
-                io.eigres = (const cplx*)p;
+            if (!brc && rs->eigres && !(brc = fh_buf(h, "rs_Esub", (size_t)N * rs_ldw, &sub))) {
+                fh_launch_panel_cols(rs->eigres, rs->ld, (int)c0, w, N, sub, rs_ldw, h->stream);
+                io.eigres = sub;
             }
         }
         if (brc) local_rc = brc;
@@ -1996,11 +1969,10 @@ static int fh_contour_apply_impl(feasthip_ctx* h, int64_t m64, const cplx* dQ, c
         if (rs) {                                 // one rank, a column block: the other columns of Q_proj are zero
             FH_CHECK(hipMemsetAsync(rs->P, 0, (size_t)N * rs->ld * sizeof(cplx), h->stream));
             if (rs_out) {
-                void* p = nullptr;
-                if ((rc = fh_get_buf(h, "comm_pack", nq * sizeof(double), &p))) return rc;
-                fh_launch_pack_cols(rs_out, rs_ldw, (int)c0, (int)(c1 - c0), N, (double*)p, rs->ld, h->real_projection, h->stream);
-                if (h->real_projection) fh_launch_unpack_real((const double*)p, rs->P, nq, h->stream);
-                else FH_CHECK(hipMemcpyAsync(rs->P, p, nq * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+                if ((rc = fh_buf(h, "comm_pack", nq, &pack))) return rc;
+                fh_launch_pack_cols(rs_out, rs_ldw, (int)c0, (int)(c1 - c0), N, pack, rs->ld, h->real_projection, h->stream);
+                if (h->real_projection) fh_launch_unpack_real(pack, rs->P, nq, h->stream);
+                else FH_CHECK(hipMemcpyAsync(rs->P, pack, nq * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
             }
             FH_CHECK(hipStreamSynchronize(h->stream));
         }
@@ -2148,21 +2120,21 @@ extern "C" int feasthip_estimate_count(feasthip_handle h, int64_t m, uint64_t se
     const double t0 = fh_now_s();
     FH_CHECK(hipSetDevice(h->device));
     const int64_t N = fh_N(h);
-    const size_t nb = (size_t)N * m * sizeof(cplx);
-    void *dV, *dP, *dW, *dT;
-    if ((rc = fh_get_buf(h, "est_V", nb, &dV))) return rc;
-    if ((rc = fh_get_buf(h, "est_P", nb, &dP))) return rc;
-    if ((rc = fh_get_buf(h, "est_work", fh_trace_work_elems(N, m) * sizeof(cplx), &dW))) return rc;
-    if ((rc = fh_get_buf(h, "est_t", (size_t)m * 2 * sizeof(double), &dT))) return rc;
-    fh_launch_rademacher(seed, 0, N, m, (cplx*)dV, N, h->stream);
+    cplx *dV, *dP, *dW;
+    double* dT;
+    if ((rc = fh_buf(h, "est_V", (size_t)N * m, &dV))) return rc;
+    if ((rc = fh_buf(h, "est_P", (size_t)N * m, &dP))) return rc;
+    if ((rc = fh_buf(h, "est_work", fh_trace_work_elems(N, m), &dW))) return rc;
+    if ((rc = fh_buf(h, "est_t", (size_t)m * 2, &dT))) return rc;
+    fh_launch_rademacher(seed, 0, N, m, dV, N, h->stream);
     FH_CHECK(hipGetLastError());
     // the sweep of feasthip_contour_apply_dev from a zero start: Q_proj = rho V, summed over the ranks of a communicator
     h->mask_live = 1;
-    rc = fh_contour_apply_impl(h, m, (const cplx*)dV, nullptr, (cplx*)dP, nullptr, nullptr, node_status, stats);
+    rc = fh_contour_apply_impl(h, m, dV, nullptr, dP, nullptr, nullptr, node_status, stats);
     h->mask_live = 0;
     h->col_mask.clear();
     if (rc) return rc;
-    fh_launch_trace_dots((const cplx*)dP, N, m, N, seed, h->real_projection, (cplx*)dW, (double*)dT, h->stream);
+    fh_launch_trace_dots(dP, N, m, N, seed, h->real_projection, dW, dT, h->stream);
     FH_CHECK(hipGetLastError());
     FH_CHECK(hipMemcpyAsync(samples, dT, (size_t)m * 2 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     FH_CHECK(hipStreamSynchronize(h->stream));
@@ -2212,26 +2184,19 @@ static int fh_ortho_staged(feasthip_ctx* h, int m, int ld, const cplx* X, cplx* 
     const int N = (int)fh_N(h);
     const size_t panel = (size_t)N * ld;
     int rc;
-    void* p;
     *staged = false;
-    if ((rc = fh_get_buf(h, "rr_W", panel * sizeof(cplx), &p))) return rc;
-    cplx* W = (cplx*)p;
-    if ((rc = fh_get_buf(h, "rr_T", panel * sizeof(cplx), &p))) return rc;
-    cplx* T = (cplx*)p;
-    if ((rc = fh_get_buf(h, "rr_T2", panel * sizeof(cplx), &p))) return rc;
-    cplx* T2 = (cplx*)p;
-    if ((rc = fh_get_buf(h, "gram_work", fh_gram_work_elems(ld) * sizeof(cplx), &p))) return rc;
-    cplx* gw = (cplx*)p;
-    if ((rc = fh_get_buf(h, "gram_G", (size_t)ld * ld * sizeof(cplx), &p))) return rc;
-    cplx* G = (cplx*)p;
-    if ((rc = fh_get_buf(h, "or_Rinv", (size_t)ld * ld * sizeof(cplx), &p))) return rc;
-    cplx* dR = (cplx*)p;
-    if ((rc = fh_get_buf(h, "rr_C", (size_t)ld * ld * sizeof(cplx), &p))) return rc;
-    cplx* C = (cplx*)p;
-    if ((rc = fh_get_buf(h, "rr_istate", (FH_RR_PERM + FH_MAX_LD) * sizeof(int), &p))) return rc;
-    int* ist = (int*)p;
-    if ((rc = fh_get_buf(h, "rr_dstate", (2 + FH_MAX_LD) * sizeof(double), &p))) return rc;
-    double* dst = (double*)p;
+    cplx *W, *T, *T2, *gw, *G, *dR, *C;
+    if ((rc = fh_buf(h, "rr_W", panel, &W))) return rc;
+    if ((rc = fh_buf(h, "rr_T", panel, &T))) return rc;
+    if ((rc = fh_buf(h, "rr_T2", panel, &T2))) return rc;
+    if ((rc = fh_buf(h, "gram_work", fh_gram_work_elems(ld), &gw))) return rc;
+    if ((rc = fh_buf(h, "gram_G", (size_t)ld * ld, &G))) return rc;
+    if ((rc = fh_buf(h, "or_Rinv", (size_t)ld * ld, &dR))) return rc;
+    if ((rc = fh_buf(h, "rr_C", (size_t)ld * ld, &C))) return rc;
+    int* ist;
+    double* dst;
+    if ((rc = fh_buf(h, "rr_istate", FH_RR_PERM + FH_MAX_LD, &ist))) return rc;
+    if ((rc = fh_buf(h, "rr_dstate", 2 + FH_MAX_LD, &dst))) return rc;
     std::vector<cplx> ones(ld, cmake(1, 0)), mones(ld, cmake(-1, 0));
     cplx *done, *dmone;
     if ((rc = fh_upload_coefs(h, "rr_one", ones, &done))) return rc;
@@ -2292,27 +2257,23 @@ static int fh_ortho_panel(feasthip_ctx* h, int m, int ld, cplx* X, cplx* Out, do
                           int big_dim, int* rank, cplx** res) {
     const int N = (int)fh_N(h);
     int rc;
-    void* p;
-    if ((rc = fh_get_buf(h, "or_work", (size_t)256 * ld * sizeof(cplx), &p))) return rc;
-    cplx* work = (cplx*)p;
-    if ((rc = fh_get_buf(h, "or_istate", (4 + FH_MAX_LD) * sizeof(int), &p))) return rc;
-    int* istate = (int*)p;
-    if ((rc = fh_get_buf(h, "or_dstate", (2 + FH_MAX_LD) * sizeof(double), &p))) return rc;
-    double* dstate = (double*)p;
-    if ((rc = fh_get_buf(h, "or_coef", FH_MAX_LD * sizeof(cplx), &p))) return rc;
-    cplx* coef = (cplx*)p;
+    cplx *work, *coef;
+    int* istate;
+    double* dstate;
+    if ((rc = fh_buf(h, "or_work", (size_t)256 * ld, &work))) return rc;
+    if ((rc = fh_buf(h, "or_istate", 4 + FH_MAX_LD, &istate))) return rc;
+    if ((rc = fh_buf(h, "or_dstate", 2 + FH_MAX_LD, &dstate))) return rc;
+    if ((rc = fh_buf(h, "or_coef", FH_MAX_LD, &coef))) return rc;
     int fell_back = 0;
     // Fast path (Cholesky-QR, one or two passes) when the panel is far from rank deficient (fh_cholqr::accept: the pivoted
     // Cholesky pivots of the Gram matrix are the squared R_kk of the pivoted QR).  Otherwise fall through to the
     // rank-revealing pivoted Gram-Schmidt.  The Rayleigh-Ritz step that follows uses Q^H B Q anyway, so one pass suffices
     // when it is orthonormal to 1e-14.
     if (!fh_knob::no_cholqr()) {
-        if ((rc = fh_get_buf(h, "gram_work", fh_gram_work_elems(ld) * sizeof(cplx), &p))) return rc;
-        cplx* gw = (cplx*)p;
-        if ((rc = fh_get_buf(h, "gram_G", (size_t)ld * ld * sizeof(cplx), &p))) return rc;
-        cplx* G = (cplx*)p;
-        if ((rc = fh_get_buf(h, "or_Rinv", (size_t)ld * ld * sizeof(cplx), &p))) return rc;
-        cplx* dR = (cplx*)p;
+        cplx *gw, *G, *dR;
+        if ((rc = fh_buf(h, "gram_work", fh_gram_work_elems(ld), &gw))) return rc;
+        if ((rc = fh_buf(h, "gram_G", (size_t)ld * ld, &G))) return rc;
+        if ((rc = fh_buf(h, "or_Rinv", (size_t)ld * ld, &dR))) return rc;
         std::vector<cplx> Gh((size_t)ld * ld), Rinv;
         std::vector<double> dcol;
         bool ok = true;
@@ -2389,23 +2350,15 @@ static int fh_ortho_wide(feasthip_ctx* h, int m, cplx* dQ, double rank_tol, int*
     const int N = (int)fh_N(h), ld = FH_MAX_LD;
     const size_t panel = (size_t)N * ld;
     int rc;
-    void* p;
-    if ((rc = fh_get_buf(h, "or_X", panel * sizeof(cplx), &p))) return rc;
-    cplx* X = (cplx*)p;
-    if ((rc = fh_get_buf(h, "or_out", panel * sizeof(cplx), &p))) return rc;
-    cplx* Out = (cplx*)p;
-    if ((rc = fh_get_buf(h, "ow_K", panel * sizeof(cplx), &p))) return rc;
-    cplx* K = (cplx*)p;
-    if ((rc = fh_get_buf(h, "ow_T", panel * sizeof(cplx), &p))) return rc;
-    cplx* T = (cplx*)p;
-    if ((rc = fh_get_buf(h, "gram_work", fh_gram_work_elems(ld) * sizeof(cplx), &p))) return rc;
-    cplx* gw = (cplx*)p;
-    if ((rc = fh_get_buf(h, "ow_C", (size_t)ld * ld * sizeof(cplx), &p))) return rc;
-    cplx* C = (cplx*)p;
-    if ((rc = fh_get_buf(h, "ow_part", (size_t)fh_vec_nblk(N, ld) * ld * sizeof(cplx), &p))) return rc;
-    cplx* part = (cplx*)p;
-    if ((rc = fh_get_buf(h, "ow_dots", (size_t)ld * sizeof(cplx), &p))) return rc;
-    cplx* ddots = (cplx*)p;
+    cplx *X, *Out, *K, *T, *gw, *C, *part, *ddots;
+    if ((rc = fh_buf(h, "or_X", panel, &X))) return rc;
+    if ((rc = fh_buf(h, "or_out", panel, &Out))) return rc;
+    if ((rc = fh_buf(h, "ow_K", panel, &K))) return rc;
+    if ((rc = fh_buf(h, "ow_T", panel, &T))) return rc;
+    if ((rc = fh_buf(h, "gram_work", fh_gram_work_elems(ld), &gw))) return rc;
+    if ((rc = fh_buf(h, "ow_C", (size_t)ld * ld, &C))) return rc;
+    if ((rc = fh_buf(h, "ow_part", (size_t)fh_vec_nblk(N, ld) * ld, &part))) return rc;
+    if ((rc = fh_buf(h, "ow_dots", (size_t)ld, &ddots))) return rc;
     std::vector<cplx> ones(ld, cmake(1, 0));
     cplx* done;
     if ((rc = fh_upload_coefs(h, "ow_one", ones, &done))) return rc;
@@ -2462,11 +2415,9 @@ extern "C" int feasthip_orthonormalize_dev(feasthip_handle h, int64_t m64, void*
     }
     const int m = (int)m64, ld = fh_pick_ld(m), N = (int)fh_N(h);
     const size_t panel = (size_t)N * ld;
-    void* p;
-    if ((rc = fh_get_buf(h, "or_X", panel * sizeof(cplx), &p))) return rc;
-    cplx* X = (cplx*)p;
-    if ((rc = fh_get_buf(h, "or_out", panel * sizeof(cplx), &p))) return rc;
-    cplx* Out = (cplx*)p;
+    cplx *X, *Out;
+    if ((rc = fh_buf(h, "or_X", panel, &X))) return rc;
+    if ((rc = fh_buf(h, "or_out", panel, &Out))) return rc;
     fh_launch_to_panel((const cplx*)dQ, N, N, m, X, ld, h->stream, fh_perm(h));
     cplx* res = nullptr;
     if ((rc = fh_ortho_panel(h, m, ld, X, Out, rank_tol, 0.0, m, rank, &res))) return rc;
@@ -2527,44 +2478,83 @@ struct fh_forward_scope {
     ~fh_forward_scope() { h->adjoint = was; }
 };
 
+// What one operator-Gram step works with: the product panel W, the Gram kernel's workspace and the unit / zero coefficient
+// vectors that select A or B in the operator kernel.  The projections and the resident reduce share them by name.
+struct fh_op_gram {
+    feasthip_ctx* h; int ld;
+    cplx *W, *gw, *d1, *d0;
+    int acquire(feasthip_ctx* h_, int ld_) {
+        h = h_; ld = ld_;
+        int rc;
+        if ((rc = fh_buf(h, "pj_W", (size_t)fh_N(h) * ld, &W))) return rc;
+        if ((rc = fh_buf(h, "gram_work", fh_gram_work_elems(ld), &gw))) return rc;
+        const std::vector<cplx> one(ld, cmake(1, 0)), zero(ld, cmake(0, 0));
+        if ((rc = fh_upload_coefs(h, "pj_one", one, &d1))) return rc;
+        return fh_upload_coefs(h, "pj_zero", zero, &d0);
+    }
+    // queues W = op X on the first m columns, op = A (which 0) or B (which 1)
+    int product(int m, const cplx* X, int which) const {
+        fh_op_call oc;
+        oc.m = m;
+        oc.X = X; oc.Y = W;
+        oc.coefA = which == 0 ? d1 : d0; oc.coefB = which == 0 ? d0 : d1;
+        return fh_apply_operator(h, ld, oc) < 0 ? (int)FEASTHIP_ERROR_INTERNAL : 0;
+    }
+    // queues G = QL^H W (bilinear: QL^T W) as one launch of the "gram" profile class
+    void gram(const cplx* QL, int bilinear, cplx* G) const {
+        fh_prof_begin(h, "gram");
+        fh_launch_gram(QL, W, (int)fh_N(h), ld, bilinear, gw, G, h->stream);
+        fh_prof_end(h);
+    }
+    // the whole step, G = QL^H (op X): nothing is synchronised or downloaded; the operator's error code comes back
+    int step(int m, const cplx* QL, const cplx* X, int which, int bilinear, cplx* G) const {
+        const int rc = product(m, X, which);
+        if (!rc) gram(QL, bilinear, G);
+        return rc;
+    }
+};
+
+// out (r x r column-major, host) = the leading r x r block of Gsrc (host, leading dimension ld), scaled by 1 / (d_i d_j) when
+// d != null, its Hermitian part when asked
+static void fh_gram_to_host(const cplx* Gsrc, int ld, int r, const double* d, bool hermitian, cplx* out) {
+    for (int j = 0; j < r; ++j)
+        for (int i = 0; i < r; ++i) {
+            cplx g = Gsrc[(size_t)j * ld + i];
+            if (d) g = cscale(g, 1.0 / (d[i] * d[j]));
+            out[(size_t)j * r + i] = g;
+        }
+    if (hermitian) fh_cholqr::hermitian_part(out, r);
+}
+// out = I exactly: the B-part of an orthonormal basis when B = I (src/dense/feast_dense.jl:255-259)
+static void fh_identity_to_host(int r, cplx* out) {
+    for (int j = 0; j < r; ++j)
+        for (int i = 0; i < r; ++i) out[(size_t)j * r + i] = cmake(i == j ? 1.0 : 0.0, 0.0);
+}
+
 // res = Q_L^H op Q_R (bilinear: Q_L^T) for op = A (which 0) or B (which 1), r x r column-major on the host, by ld-column
-// panels: block (i, j) is Q_L,i^H (op Q_R,j) on the operator and MFMA Gram kernels.  One download and one stream
-// synchronisation per block: a single one for r <= ld, (r / 64)^2 of them for the wide calls.
+// panels: block (i, j) is Q_L,i^H (op Q_R,j), one operator product (fh_op_gram::product) per block column and one Gram
+// launch per block.  One download and one stream synchronisation per block: a single one for r <= ld, (r / 64)^2 of them
+// for the wide calls.
 static int fh_project_blocks(feasthip_ctx* h, int r, int ld, const cplx* dQL, const cplx* dQR, int which, int bilinear, cplx* res) {
     const int N = (int)fh_N(h);
     const size_t panel = (size_t)N * ld;
-    void* p;
     int rc;
-    if ((rc = fh_get_buf(h, "pj_Q", panel * sizeof(cplx), &p))) return rc;
-    cplx* Qi = (cplx*)p;
-    if ((rc = fh_get_buf(h, "pj_Qj", panel * sizeof(cplx), &p))) return rc;
-    cplx* Qj = (cplx*)p;
-    if ((rc = fh_get_buf(h, "pj_W", panel * sizeof(cplx), &p))) return rc;
-    cplx* W = (cplx*)p;
-    if ((rc = fh_get_buf(h, "gram_work", fh_gram_work_elems(ld) * sizeof(cplx), &p))) return rc;
-    cplx* gw = (cplx*)p;
-    if ((rc = fh_get_buf(h, "gram_G", (size_t)ld * ld * sizeof(cplx), &p))) return rc;
-    cplx* G = (cplx*)p;
-    std::vector<cplx> one(ld, cmake(1, 0)), zero(ld, cmake(0, 0));
-    cplx *d1, *d0;
-    if ((rc = fh_upload_coefs(h, "pj_one", one, &d1))) return rc;
-    if ((rc = fh_upload_coefs(h, "pj_zero", zero, &d0))) return rc;
+    cplx *Qi, *Qj, *G;
+    fh_op_gram og;
+    if ((rc = fh_buf(h, "pj_Q", panel, &Qi))) return rc;
+    if ((rc = fh_buf(h, "pj_Qj", panel, &Qj))) return rc;
+    if ((rc = fh_buf(h, "gram_G", (size_t)ld * ld, &G))) return rc;
+    if ((rc = og.acquire(h, ld))) return rc;
     const int npan = (r + ld - 1) / ld;
     std::vector<cplx> Gh((size_t)ld * ld);
     for (int j = 0; j < npan; ++j) {
         const int mj = std::min(ld, r - j * ld);
         fh_launch_to_panel(dQR + (size_t)j * ld * N, N, N, mj, Qj, ld, h->stream, fh_perm(h));
-        fh_op_call oc;
-        oc.m = mj;
-        oc.X = Qj; oc.Y = W;
-        oc.coefA = which == 0 ? d1 : d0; oc.coefB = which == 0 ? d0 : d1;
-        if (fh_apply_operator(h, ld, oc) < 0) return (int)FEASTHIP_ERROR_INTERNAL;
+        if ((rc = og.product(mj, Qj, which))) return rc;
         for (int i = 0; i < npan; ++i) {
             const int mi = std::min(ld, r - i * ld);
             fh_launch_to_panel(dQL + (size_t)i * ld * N, N, N, mi, Qi, ld, h->stream, fh_perm(h));
-            fh_prof_begin(h, "gram");
-            fh_launch_gram(Qi, W, N, ld, bilinear, gw, G, h->stream);
-            fh_prof_end(h);
+            og.gram(Qi, bilinear, G);
             FH_CHECK(hipMemcpyAsync(Gh.data(), G, Gh.size() * sizeof(cplx), hipMemcpyDeviceToHost, h->stream));
             FH_CHECK(hipStreamSynchronize(h->stream));
             for (int c2 = 0; c2 < mj; ++c2)
@@ -2577,87 +2567,44 @@ static int fh_project_blocks(feasthip_ctx* h, int r, int ld, const cplx* dQL, co
 
 extern "C" int feasthip_project_dev(feasthip_handle h, int64_t r64, const void* dQ, int bilinear, int hermitize,
                                     void* Aq_host, void* Bq_host) {
-    if (r64 > FH_MAX_LD) {
-        // r > 64: 64-column panels (fh_project_blocks)
-        int rc0 = fh_check_problem(h, r64, 1);
-        if (rc0) return rc0;
-        if (!dQ || !Aq_host) { h->last_error = "project: null argument"; return FEASTHIP_ERROR_INTERNAL; }
-        FH_CHECK(hipSetDevice(h->device));
-        fh_forward_scope forward(h);
-        const int r = (int)r64;
-        for (int which = 0; which < 2; ++which) {
-            cplx* out_host = (cplx*)(which == 0 ? Aq_host : Bq_host);
-            if (!out_host) continue;
-            std::vector<cplx> res((size_t)r * r, cmake(0, 0));
-            if (which == 1 && fh_b_identity(h) && hermitize && !bilinear) {
-                for (int i = 0; i < r; ++i) res[(size_t)i * r + i] = cmake(1, 0);
-            } else {
-                if ((rc0 = fh_project_blocks(h, r, FH_MAX_LD, (const cplx*)dQ, (const cplx*)dQ, which, bilinear, res.data()))) return rc0;
-                if (hermitize && !bilinear) fh_cholqr::hermitian_part(res.data(), r);
-            }
-            memcpy(out_host, res.data(), res.size() * sizeof(cplx));
-        }
-        fh_prof_collect(h);
-        return 0;
-    }
-
-    int rc = fh_check_problem(h, r64);
+    const bool wide = r64 > FH_MAX_LD;                  // r > 64: 64-column panels (fh_project_blocks)
+    int rc = fh_check_problem(h, r64, wide);
     if (rc) return rc;
     if (!dQ || !Aq_host) { h->last_error = "project: null argument"; return FEASTHIP_ERROR_INTERNAL; }
     FH_CHECK(hipSetDevice(h->device));
     fh_forward_scope forward(h);
-    const int r = (int)r64, ld = fh_pick_ld(r), N = (int)fh_N(h);
-    const size_t panel = (size_t)N * ld;
-    void* p;
-    if ((rc = fh_get_buf(h, "pj_Q", panel * sizeof(cplx), &p))) return rc;
-    cplx* Qp = (cplx*)p;
-    if ((rc = fh_get_buf(h, "pj_W", panel * sizeof(cplx), &p))) return rc;
-    cplx* W = (cplx*)p;
-    if ((rc = fh_get_buf(h, "gram_work", fh_gram_work_elems(ld) * sizeof(cplx), &p))) return rc;
-    cplx* gw = (cplx*)p;
-    if ((rc = fh_get_buf(h, "gram_G", (size_t)ld * ld * sizeof(cplx), &p))) return rc;
-    cplx* G = (cplx*)p;
-    fh_launch_to_panel((const cplx*)dQ, N, N, r, Qp, ld, h->stream, fh_perm(h));
-    std::vector<cplx> one(ld, cmake(1, 0)), zero(ld, cmake(0, 0));
-    cplx *d1, *d0;
-    if ((rc = fh_upload_coefs(h, "pj_one", one, &d1))) return rc;
-    if ((rc = fh_upload_coefs(h, "pj_zero", zero, &d0))) return rc;
-    // both Gram matrices are queued before the ONE synchronisation that brings them to the host
-    if ((rc = fh_get_buf(h, "gram_G2", 2 * (size_t)ld * ld * sizeof(cplx), &p))) return rc;
-    G = (cplx*)p;
-    std::vector<cplx> Gh(2 * (size_t)ld * ld);
-    bool queued[2] = {false, false};
-    for (int which = 0; which < 2; ++which) {
-        cplx* out_host = (cplx*)(which == 0 ? Aq_host : Bq_host);
-        if (!out_host) continue;
-        if (which == 1 && fh_b_identity(h) && hermitize && !bilinear) continue;       // Aq_rank = I exactly, below
-        // (B = I without orthonormal Q, variant C: the operator kernel yields W = Q, so G = Q^H Q)
-        fh_op_call oc;
-        oc.m = r;
-        oc.X = Qp; oc.Y = W;
-        oc.coefA = which == 0 ? d1 : d0; oc.coefB = which == 0 ? d0 : d1;
-        fh_apply_operator(h, ld, oc);
-        fh_prof_begin(h, "gram");
-        fh_launch_gram(Qp, W, N, ld, bilinear, gw, G + (size_t)which * ld * ld, h->stream);
-        fh_prof_end(h);
-        FH_CHECK(hipMemcpyAsync(Gh.data() + (size_t)which * ld * ld, G + (size_t)which * ld * ld, (size_t)ld * ld * sizeof(cplx),
-                                hipMemcpyDeviceToHost, h->stream));
-        queued[which] = true;
-    }
-    FH_CHECK(hipStreamSynchronize(h->stream));
-    for (int which = 0; which < 2; ++which) {
-        cplx* out_host = (cplx*)(which == 0 ? Aq_host : Bq_host);
-        if (!out_host) continue;
-        std::vector<cplx> res((size_t)r * r);
-        if (!queued[which]) {
-            // variant A: Q is orthonormal, Aq_rank = I exactly (src/dense/feast_dense.jl:255-259)
-            for (int j = 0; j < r; ++j) for (int i = 0; i < r; ++i) res[(size_t)j * r + i] = cmake(i == j ? 1.0 : 0.0, 0.0);
-        } else {
-            const cplx* Gw = Gh.data() + (size_t)which * ld * ld;
-            for (int j = 0; j < r; ++j) for (int i = 0; i < r; ++i) res[(size_t)j * r + i] = Gw[(size_t)j * ld + i];
-            if (hermitize && !bilinear) fh_cholqr::hermitian_part(res.data(), r);
+    const int r = (int)r64, N = (int)fh_N(h);
+    const int ld = wide ? r : fh_pick_ld(r);            // leading dimension of the Gram data on the host
+    const size_t g2 = (size_t)ld * ld;
+    cplx* const out_host[2] = {(cplx*)Aq_host, (cplx*)Bq_host};
+    // variant A: Q is orthonormal and B = I, so Bq = I exactly and no product is formed for it
+    // (B = I without orthonormal Q, variant C: the operator kernel yields W = Q, so G = Q^H Q)
+    const bool b_exact = fh_b_identity(h) && hermitize && !bilinear;
+    auto produced = [&](int which) { return out_host[which] && !(which == 1 && b_exact); };
+    std::vector<cplx> Gh(2 * g2);
+    if (wide) {
+        for (int which = 0; which < 2; ++which)
+            if (produced(which) && (rc = fh_project_blocks(h, r, FH_MAX_LD, (const cplx*)dQ, (const cplx*)dQ, which, bilinear,
+                                                           Gh.data() + which * g2))) return rc;
+    } else {
+        cplx *Qp, *G;
+        fh_op_gram og;
+        if ((rc = fh_buf(h, "pj_Q", (size_t)N * ld, &Qp))) return rc;
+        fh_launch_to_panel((const cplx*)dQ, N, N, r, Qp, ld, h->stream, fh_perm(h));
+        if ((rc = og.acquire(h, ld))) return rc;
+        // both Gram matrices are queued before the ONE synchronisation that brings them to the host
+        if ((rc = fh_buf(h, "gram_G2", 2 * g2, &G))) return rc;
+        for (int which = 0; which < 2; ++which) {
+            if (!produced(which)) continue;
+            if ((rc = og.step(r, Qp, Qp, which, bilinear, G + which * g2))) return rc;
+            FH_CHECK(hipMemcpyAsync(Gh.data() + which * g2, G + which * g2, g2 * sizeof(cplx), hipMemcpyDeviceToHost, h->stream));
         }
-        memcpy(out_host, res.data(), res.size() * sizeof(cplx));
+        FH_CHECK(hipStreamSynchronize(h->stream));
+    }
+    for (int which = 0; which < 2; ++which) {
+        if (!out_host[which]) continue;
+        if (produced(which)) fh_gram_to_host(Gh.data() + which * g2, ld, r, nullptr, hermitize && !bilinear, out_host[which]);
+        else fh_identity_to_host(r, out_host[which]);
     }
     fh_prof_collect(h);
     FH_CHECK(hipGetLastError());       // launch-configuration errors do not surface through the stream sync
@@ -2748,72 +2695,92 @@ static void fh_residual_norms(const cplx* dots, const double* lambda, int M, dou
     }
 }
 
+// The rz_* workspace of the Ritz back-transform X = Q V and its residual.  staged: the caller's column-major Q and X go
+// through panels of their own (rz_Q, rz_X, rz_R; the resident loop has its panels already); wide: the r > 64 path sums its
+// block products through rz_T.
+struct fh_ritz_ws {
+    cplx *Qp = nullptr, *Xp = nullptr, *Rp = nullptr, *Tp = nullptr, *dV = nullptr, *part = nullptr, *ddots = nullptr;
+    int acquire(feasthip_ctx* h, int ld, bool staged, bool wide) {
+        const int N = (int)fh_N(h);
+        const size_t panel = (size_t)N * ld;
+        int rc;
+        if (staged) {
+            if ((rc = fh_buf(h, "rz_Q", panel, &Qp))) return rc;
+            if ((rc = fh_buf(h, "rz_X", panel, &Xp))) return rc;
+            if ((rc = fh_buf(h, "rz_R", panel, &Rp))) return rc;
+        }
+        if (wide && (rc = fh_buf(h, "rz_T", panel, &Tp))) return rc;
+        if ((rc = fh_buf(h, "rz_V", (size_t)ld * ld, &dV))) return rc;
+        if ((rc = fh_buf(h, "rz_part", (size_t)std::max(fh_op_nblk(h, ld), fh_vec_nblk(N, ld)) * ld, &part))) return rc;
+        return fh_buf(h, "rz_dots", (size_t)ld, &ddots);
+    }
+};
+
+// Vp (ld x ld, zero padded) = block (i, j) of the r x r column-major host matrix V cut into ld-column blocks -- all of V for
+// r <= ld -- with row k of V scaled by rowscale[k].x when rowscale != null
+static void fh_pad_block(const cplx* V, int r, int ld, int i, int j, const cplx* rowscale, std::vector<cplx>& Vp) {
+    const int mi = std::min(ld, r - i * ld), mj = std::min(ld, r - j * ld);
+    Vp.assign((size_t)ld * ld, cmake(0, 0));
+    for (int c2 = 0; c2 < mj; ++c2)
+        for (int c1 = 0; c1 < mi; ++c1) {
+            const cplx v = V[(size_t)(j * ld + c2) * r + i * ld + c1];
+            Vp[(size_t)c2 * ld + c1] = rowscale ? cscale(v, rowscale[i * ld + c1].x) : v;
+        }
+}
+
 extern "C" int feasthip_ritz_residual_dev(feasthip_handle h, int64_t r64, const void* dQ, const void* V_host,
                                           const double* lambda_host, int64_t M, int normalize, int use_B, void* dX,
                                           double* res_host) {
-    if (int arc = fh_check_adjoint(h, "ritz_residual")) return arc;
+    const bool wide = r64 > FH_MAX_LD;
+    int rc = fh_check_adjoint(h, "ritz_residual");
+    if (rc) return rc;
+    if ((rc = fh_check_problem(h, r64, wide))) return rc;
+    if (!dQ || !V_host || !lambda_host || !dX) { h->last_error = "ritz_residual: null argument"; return FEASTHIP_ERROR_INTERNAL; }
+    if (M < 0 || M > r64) { h->last_error = "ritz_residual: M out of range"; return FEASTHIP_ERROR_M0; }
     std::vector<double> lam_conj;
-    if (h && h->adjoint && lambda_host && V_host && dQ && dX && fh_check_problem(h, r64, 1) == 0) {   // (failed checks are reported below)
+    if (h->adjoint) {
         // adjoint residual A^H x - conj(lambda) B^H x: the products are adjoint through fh_apply_operator, the values here
         lam_conj.assign(lambda_host, lambda_host + 2 * (size_t)r64);
         for (size_t c = 0; c < (size_t)r64; ++c) lam_conj[2 * c + 1] = -lam_conj[2 * c + 1];
         lambda_host = lam_conj.data();
     }
-    if (r64 > FH_MAX_LD) {
+    FH_CHECK(hipSetDevice(h->device));
+    const int r = (int)r64, ld = wide ? FH_MAX_LD : fh_pick_ld(r), N = (int)fh_N(h);
+    fh_ritz_ws ws;
+    if ((rc = ws.acquire(h, ld, true, wide))) return rc;
+    cplx *Qp = ws.Qp, *Xp = ws.Xp, *Rp = ws.Rp, *dV = ws.dV, *part = ws.part, *ddots = ws.ddots;
+    const cplx* Vh = (const cplx*)V_host;
+    std::vector<cplx> Vp;
+    std::vector<char> dots_fb;
+    if (wide) {
         // r > 64: X_j = sum_i Q_i V[i-block, j-block] per 64-column output panel, then the panel
         // goes through the same normalise / residual steps as the narrow path
-        int rc0 = fh_check_problem(h, r64, 1);
-        if (rc0) return rc0;
-        if (!dQ || !V_host || !lambda_host || !dX) { h->last_error = "ritz_residual: null argument"; return FEASTHIP_ERROR_INTERNAL; }
-        if (M < 0 || M > r64) { h->last_error = "ritz_residual: M out of range"; return FEASTHIP_ERROR_M0; }
         if (dQ == dX) { h->last_error = "ritz_residual: X must not alias Q for r > 64"; return FEASTHIP_ERROR_INTERNAL; }
-        FH_CHECK(hipSetDevice(h->device));
-        const int r = (int)r64, ld = FH_MAX_LD, N = (int)fh_N(h);
-        const size_t panel = (size_t)N * ld;
-        void* p;
-        int rc;
-        if ((rc = fh_get_buf(h, "rz_Q", panel * sizeof(cplx), &p))) return rc;
-        cplx* Qp = (cplx*)p;
-        if ((rc = fh_get_buf(h, "rz_X", panel * sizeof(cplx), &p))) return rc;
-        cplx* Xp = (cplx*)p;
-        if ((rc = fh_get_buf(h, "rz_R", panel * sizeof(cplx), &p))) return rc;
-        cplx* Rp = (cplx*)p;
-        if ((rc = fh_get_buf(h, "rz_T", panel * sizeof(cplx), &p))) return rc;
-        cplx* Tp = (cplx*)p;
-        if ((rc = fh_get_buf(h, "rz_V", (size_t)ld * ld * sizeof(cplx), &p))) return rc;
-        cplx* dV = (cplx*)p;
-        const int nblk_op = fh_op_nblk(h, ld), nblk_vec = fh_vec_nblk(N, ld);
-        if ((rc = fh_get_buf(h, "rz_part", (size_t)std::max(nblk_op, nblk_vec) * ld * sizeof(cplx), &p))) return rc;
-        cplx* part = (cplx*)p;
-        if ((rc = fh_get_buf(h, "rz_dots", (size_t)ld * sizeof(cplx), &p))) return rc;
-        cplx* ddots = (cplx*)p;
         std::vector<cplx> mones(ld, cmake(-1, 0));
         cplx* dmone;
         if ((rc = fh_upload_coefs(h, "rz_mone", mones, &dmone))) return rc;
-        const cplx* Vh = (const cplx*)V_host;
         const int npan = (r + ld - 1) / ld;
-        std::vector<cplx> Vp((size_t)ld * ld), dots(ld);
-        std::vector<char> dots_fb;
+        std::vector<cplx> dots(ld);
         for (int j = 0; j < npan; ++j) {
             const int mj = std::min(ld, r - j * ld);
             for (int i = 0; i < npan; ++i) {
                 const int mi = std::min(ld, r - i * ld);
-                std::fill(Vp.begin(), Vp.end(), cmake(0, 0));
-                for (int c2 = 0; c2 < mj; ++c2)
-                    for (int c1 = 0; c1 < mi; ++c1) Vp[(size_t)c2 * ld + c1] = Vh[(size_t)(j * ld + c2) * r + i * ld + c1];
+                fh_pad_block(Vh, r, ld, i, j, nullptr, Vp);
                 FH_CHECK(hipMemcpyAsync(dV, Vp.data(), Vp.size() * sizeof(cplx), hipMemcpyHostToDevice, h->stream));
                 fh_launch_to_panel((const cplx*)dQ + (size_t)i * ld * N, N, N, mi, Qp, ld, h->stream, fh_perm(h));
                 fh_prof_begin(h, "ritz");
                 if (i == 0) {
                     fh_launch_small_matmul(Qp, dV, N, ld, Xp, h->stream);
                 } else {
-                    fh_launch_small_matmul(Qp, dV, N, ld, Tp, h->stream);
-                    fh_launch_axpy_cols(Xp, Tp, dmone, N, ld, h->stream);      // X += T
+                    fh_launch_small_matmul(Qp, dV, N, ld, ws.Tp, h->stream);
+                    fh_launch_axpy_cols(Xp, ws.Tp, dmone, N, ld, h->stream);    // X += T
                 }
                 fh_prof_end(h);
                 FH_CHECK(hipStreamSynchronize(h->stream));                      // Vp (host) is reused
             }
             const int Mj = std::max(0, std::min(mj, (int)M - j * ld));          // columns of this panel below M
+            // (unlike the narrow and resident paths, which normalise on the device with fh_launch_normalize_cols, the norms
+            //  make a host round trip here; not folded in: it would change the launches and the synchronisations)
             if (normalize && Mj > 0) {
                 fh_launch_dot_cols(Xp, Xp, N, ld, part, ddots, h->stream);
                 FH_CHECK(hipMemcpyAsync(dots.data(), ddots, ld * sizeof(cplx), hipMemcpyDeviceToHost, h->stream));
@@ -2840,32 +2807,7 @@ extern "C" int feasthip_ritz_residual_dev(feasthip_handle h, int64_t r64, const 
         fh_prof_collect(h);
         return 0;
     }
-
-    int rc = fh_check_problem(h, r64);
-    if (rc) return rc;
-    if (!dQ || !V_host || !lambda_host || !dX) { h->last_error = "ritz_residual: null argument"; return FEASTHIP_ERROR_INTERNAL; }
-    if (M < 0 || M > r64) { h->last_error = "ritz_residual: M out of range"; return FEASTHIP_ERROR_M0; }
-    FH_CHECK(hipSetDevice(h->device));
-    const int r = (int)r64, ld = fh_pick_ld(r), N = (int)fh_N(h);
-    const size_t panel = (size_t)N * ld;
-    void* p;
-    if ((rc = fh_get_buf(h, "rz_Q", panel * sizeof(cplx), &p))) return rc;
-    cplx* Qp = (cplx*)p;
-    if ((rc = fh_get_buf(h, "rz_X", panel * sizeof(cplx), &p))) return rc;
-    cplx* Xp = (cplx*)p;
-    if ((rc = fh_get_buf(h, "rz_R", panel * sizeof(cplx), &p))) return rc;
-    cplx* Rp = (cplx*)p;
-    if ((rc = fh_get_buf(h, "rz_V", (size_t)ld * ld * sizeof(cplx), &p))) return rc;
-    cplx* dV = (cplx*)p;
-    const int nblk_op = fh_op_nblk(h, ld), nblk_vec = fh_vec_nblk(N, ld);
-    if ((rc = fh_get_buf(h, "rz_part", (size_t)std::max(nblk_op, nblk_vec) * ld * sizeof(cplx), &p))) return rc;
-    cplx* part = (cplx*)p;
-    if ((rc = fh_get_buf(h, "rz_dots", (size_t)ld * sizeof(cplx), &p))) return rc;
-    cplx* ddots = (cplx*)p;
-    // V padded to ld x ld
-    std::vector<cplx> Vp((size_t)ld * ld, cmake(0, 0));
-    const cplx* Vh = (const cplx*)V_host;
-    for (int j = 0; j < r; ++j) for (int i = 0; i < r; ++i) Vp[(size_t)j * ld + i] = Vh[(size_t)j * r + i];
+    fh_pad_block(Vh, r, ld, 0, 0, nullptr, Vp);
     FH_CHECK(hipMemcpyAsync(dV, Vp.data(), Vp.size() * sizeof(cplx), hipMemcpyHostToDevice, h->stream));
     fh_launch_to_panel((const cplx*)dQ, N, N, r, Qp, ld, h->stream, fh_perm(h));
     fh_prof_begin(h, "ritz");
@@ -2879,7 +2821,6 @@ extern "C" int feasthip_ritz_residual_dev(feasthip_handle h, int64_t r64, const 
     fh_launch_from_panel(Xp, ld, N, r, (cplx*)dX, N, h->stream, fh_perm(h));
     if (M > 0 && res_host) {
         const cplx* rdots = nullptr;
-        std::vector<char> dots_fb;
         if ((rc = fh_panel_residual(h, ld, r, Xp, Rp, lambda_host, use_B, part, ddots, &rdots, dots_fb))) return rc;
         FH_CHECK(hipStreamSynchronize(h->stream));
         fh_residual_norms(rdots, lambda_host, (int)M, res_host);
@@ -2920,7 +2861,8 @@ extern "C" int feasthip_ritz_residual(feasthip_handle h, int64_t r, const void* 
 //   feasthip_resident_export          column-major copy of X (the converged Ritz vectors, once per solve)
 // The orthonormal basis is never formed when Q_proj is well conditioned (the steady state of FEAST): the Rayleigh-Ritz
 // pairs of a subspace do not depend on the basis, so the reduced pencil is taken on Q_proj with unit columns -- three Gram
-// products (Q^H Q for the test, Q^H A Q, Q^H B Q) queued behind ONE synchronisation, an O(m^2) scaling on the host -- and
+// products (Q^H Q for the test, Q^H A Q, Q^H B Q: fh_op_gram, the step the per-primitive projections use) queued behind ONE
+// synchronisation, an O(m^2) scaling on the host (fh_gram_to_host) -- and
 // handed to the host's generalized eigensolver, whose Cholesky factorisation of the B-part does what the Cholesky-QR did;
 // the Ritz vectors are Q_proj (D^-1 V): one tall product instead of two.  The acceptance test is fh_ortho_panel's own
 // (fh_cholqr::accept) and the implicit basis is taken when it decides "one pass"; anything else -- rank deficiency, a ratio
@@ -2930,16 +2872,11 @@ extern "C" int feasthip_ritz_residual(feasthip_handle h, int64_t r, const void* 
 // residual (fh_contour_apply_panel: shared_src), which saves that sweep's first operator product.
 // ---------------------------------------------------------------------------------------
 static int fh_rs_panels(feasthip_ctx* h, cplx** P, cplx** X, cplx** R) {
-    const size_t bytes = (size_t)fh_N(h) * FH_MAX_LD * sizeof(cplx);
-    void* p;
+    const size_t panel = (size_t)fh_N(h) * FH_MAX_LD;
     int rc;
-    if ((rc = fh_get_buf(h, "rs_P", bytes, &p))) return rc;
-    *P = (cplx*)p;
-    if ((rc = fh_get_buf(h, "rs_X", bytes, &p))) return rc;
-    *X = (cplx*)p;
-    if ((rc = fh_get_buf(h, "rs_R", bytes, &p))) return rc;
-    *R = (cplx*)p;
-    return 0;
+    if ((rc = fh_buf(h, "rs_P", panel, P))) return rc;
+    if ((rc = fh_buf(h, "rs_X", panel, X))) return rc;
+    return fh_buf(h, "rs_R", panel, R);
 }
 
 extern "C" int feasthip_contour_apply_resident(feasthip_handle h, int64_t m64, const void* dQ, const double* ritz_lambda_host,
@@ -2955,10 +2892,10 @@ extern "C" int feasthip_contour_apply_resident(feasthip_handle h, int64_t m64, c
     fh_resident_sweep rs;
     rs.P = P; rs.ld = ld; rs.eigres = nullptr;
     if (dQ) {
-        void* p;
-        if ((rc = fh_get_buf(h, "rs_Q0", (size_t)N * FH_MAX_LD * sizeof(cplx), &p))) return rc;
-        fh_launch_to_panel((const cplx*)dQ, N, N, m, (cplx*)p, ld, h->stream, fh_perm(h));
-        rs.Q = (const cplx*)p;
+        cplx* Q0;
+        if ((rc = fh_buf(h, "rs_Q0", (size_t)N * FH_MAX_LD, &Q0))) return rc;
+        fh_launch_to_panel((const cplx*)dQ, N, N, m, Q0, ld, h->stream, fh_perm(h));
+        rs.Q = Q0;
     } else {
         if (h->rs_X != X || h->rs_X_m != m || h->rs_X_ld != ld) {
             h->last_error = "contour_apply_resident: no resident Ritz vectors of this width (pass Q, or run rr_ritz_resident first)";
@@ -2994,56 +2931,25 @@ extern "C" int feasthip_rr_reduce_resident(feasthip_handle h, int64_t m64, doubl
     if (h->rs_P != Pb || h->rs_m != m) { h->last_error = "rr_reduce_resident: no resident Q_proj of this width"; return FEASTHIP_ERROR_M0; }
     const int ld = h->rs_ld;
     cplx* P = h->rs_P;
-    const size_t panel = (size_t)N * ld, g2 = (size_t)ld * ld;
-    void* p;
-    if ((rc = fh_get_buf(h, "pj_W", panel * sizeof(cplx), &p))) return rc;
-    cplx* W = (cplx*)p;
-    if ((rc = fh_get_buf(h, "gram_work", fh_gram_work_elems(ld) * sizeof(cplx), &p))) return rc;
-    cplx* gw = (cplx*)p;
-    if ((rc = fh_get_buf(h, "gram_G3", 3 * g2 * sizeof(cplx), &p))) return rc;
-    cplx* G = (cplx*)p;
-    std::vector<cplx> one(ld, cmake(1, 0)), zero(ld, cmake(0, 0));
-    cplx *d1, *d0;
-    if ((rc = fh_upload_coefs(h, "pj_one", one, &d1))) return rc;
-    if ((rc = fh_upload_coefs(h, "pj_zero", zero, &d0))) return rc;
+    const size_t g2 = (size_t)ld * ld;
+    cplx* G;
+    fh_op_gram og;
+    if ((rc = og.acquire(h, ld))) return rc;
+    if ((rc = fh_buf(h, "gram_G3", 3 * g2, &G))) return rc;
     const bool b_id = fh_b_identity(h);
     // Gram products of `basis`: [0] basis^H basis (want_g0), [1] basis^H A basis, [2] basis^H B basis (B != I); one sync
     const cplx* Gh = nullptr;
     std::vector<char> gh_fallback;
     auto grams = [&](const cplx* basis, bool want_g0) -> int {
-        if (want_g0) { fh_prof_begin(h, "gram"); fh_launch_gram(basis, basis, N, ld, 0, gw, G, h->stream); fh_prof_end(h); }
-        for (int which = 0; which < 2; ++which) {
-            if (which == 1 && b_id) break;
-            fh_op_call oc;
-            oc.m = m;
-            oc.X = basis; oc.Y = W;
-            oc.coefA = which == 0 ? d1 : d0; oc.coefB = which == 0 ? d0 : d1;
-            fh_apply_operator(h, ld, oc);
-            fh_prof_begin(h, "gram");
-            fh_launch_gram(basis, W, N, ld, 0, gw, G + (size_t)(1 + which) * g2, h->stream);
-            fh_prof_end(h);
-        }
+        if (want_g0) { fh_prof_begin(h, "gram"); fh_launch_gram(basis, basis, N, ld, 0, og.gw, G, h->stream); fh_prof_end(h); }
+        int drc;
+        for (int which = 0; which < (b_id ? 1 : 2); ++which)
+            if ((drc = og.step(m, basis, basis, which, 0, G + (1 + which) * g2))) return drc;
         const void* slot = nullptr;
-        int drc = fh_download_small(h, G, 3 * g2 * sizeof(cplx), &slot, gh_fallback);
-        if (drc) return drc;
+        if ((drc = fh_download_small(h, G, 3 * g2 * sizeof(cplx), &slot, gh_fallback))) return drc;
         FH_CHECK(hipStreamSynchronize(h->stream));
         Gh = (const cplx*)slot;
         return 0;
-    };
-    // out (r x r, column-major) = Gsrc scaled by 1/(d_i d_j) (d == null: as is), Hermitian part when asked
-    auto emit = [&](const cplx* Gsrc, const double* d, int r, void* out_host) {
-        cplx* out = (cplx*)out_host;
-        for (int j = 0; j < r; ++j)
-            for (int i = 0; i < r; ++i) {
-                cplx g = Gsrc[(size_t)j * ld + i];
-                if (d) g = cscale(g, 1.0 / (d[i] * d[j]));
-                out[(size_t)j * r + i] = g;
-            }
-        if (hermitize) fh_cholqr::hermitian_part(out, r);
-    };
-    auto identity = [&](int r, void* out_host) {
-        cplx* out = (cplx*)out_host;
-        for (int j = 0; j < r; ++j) for (int i = 0; i < r; ++i) out[(size_t)j * r + i] = cmake(i == j ? 1.0 : 0.0, 0.0);
     };
     if ((rc = grams(P, true))) return rc;
     // ---- implicit basis: fh_ortho_panel's acceptance test on the Gram matrix we already have; its one-pass decision (the basis
@@ -3060,8 +2966,8 @@ extern "C" int feasthip_rr_reduce_resident(feasthip_handle h, int64_t m64, doubl
         for (int j = 0; j < m; ++j) ident[j] = j;
         fh_ortho_note(h, FEASTHIP_ORTHO_USED_CHOLQR, 0, 0, m, ident.data(), nullptr);
         // basis = Q_proj D^-1 (unit columns): its pencil is the equilibrated Gram pair; the orthonormal basis is never formed
-        emit(Gh + g2, dcol.data(), m, Aq_host);
-        emit(b_id ? Gh : Gh + 2 * g2, dcol.data(), m, Bq_host);
+        fh_gram_to_host(Gh + g2, ld, m, dcol.data(), hermitize, (cplx*)Aq_host);
+        fh_gram_to_host(b_id ? Gh : Gh + 2 * g2, ld, m, dcol.data(), hermitize, (cplx*)Bq_host);
         h->rs_basis = P; h->rs_rank = m;
         h->rs_T.assign(m, cmake(1, 0));
         for (int j = 0; j < m; ++j) h->rs_T[j] = cmake(1.0 / dcol[j], 0.0);
@@ -3071,8 +2977,8 @@ extern "C" int feasthip_rr_reduce_resident(feasthip_handle h, int64_t m64, doubl
         return 0;
     }
     // ---- general path: the rank-revealing orthonormalisation on the resident panel, then the projections of its result ----
-    if ((rc = fh_get_buf(h, "or_out", (size_t)N * FH_MAX_LD * sizeof(cplx), &p))) return rc;
-    cplx* Out = (cplx*)p;
+    cplx* Out;
+    if ((rc = fh_buf(h, "or_out", (size_t)N * FH_MAX_LD, &Out))) return rc;
     cplx* res = nullptr;
     int r = 0;
     fh_ortho_note_reset(h);
@@ -3082,9 +2988,9 @@ extern "C" int feasthip_rr_reduce_resident(feasthip_handle h, int64_t m64, doubl
     h->rs_rank = r; h->rs_T.clear(); h->rs_basis = res;
     if (r == 0) { fh_prof_collect(h); return 0; }
     if ((rc = grams(res, false))) return rc;
-    emit(Gh + g2, nullptr, r, Aq_host);
-    if (b_id) identity(r, Bq_host);               // orthonormal basis, B = I: exactly I (src/dense/feast_dense.jl:255-259)
-    else emit(Gh + 2 * g2, nullptr, r, Bq_host);
+    fh_gram_to_host(Gh + g2, ld, r, nullptr, hermitize, (cplx*)Aq_host);
+    if (b_id) fh_identity_to_host(r, (cplx*)Bq_host);       // orthonormal basis, B = I
+    else fh_gram_to_host(Gh + 2 * g2, ld, r, nullptr, hermitize, (cplx*)Bq_host);
     fh_prof_collect(h);
     FH_CHECK(hipGetLastError());
     return 0;
@@ -3103,23 +3009,12 @@ extern "C" int feasthip_rr_ritz_resident(feasthip_handle h, int64_t r64, const v
     if ((rc = fh_rs_panels(h, &Pb, &Xp, &Rp))) return rc;
     if (!h->rs_basis || h->rs_rank != r) { h->last_error = "rr_ritz_resident: run rr_reduce_resident first (rank mismatch)"; return FEASTHIP_ERROR_M0; }
     const int ld = h->rs_ld;
-    void* p;
-    if ((rc = fh_get_buf(h, "rz_V", (size_t)ld * ld * sizeof(cplx), &p))) return rc;
-    cplx* dV = (cplx*)p;
-    const int nblk_op = fh_op_nblk(h, ld), nblk_vec = fh_vec_nblk(N, ld);
-    if ((rc = fh_get_buf(h, "rz_part", (size_t)std::max(nblk_op, nblk_vec) * ld * sizeof(cplx), &p))) return rc;
-    cplx* part = (cplx*)p;
-    if ((rc = fh_get_buf(h, "rz_dots", (size_t)ld * sizeof(cplx), &p))) return rc;
-    cplx* ddots = (cplx*)p;
+    fh_ritz_ws ws;
+    if ((rc = ws.acquire(h, ld, false, false))) return rc;
+    cplx *dV = ws.dV, *part = ws.part, *ddots = ws.ddots;
     // V padded to ld x ld; the implicit basis is Q_proj D^-1, so X = Q_proj (D^-1 V)
-    std::vector<cplx> Vp((size_t)ld * ld, cmake(0, 0));
-    const cplx* Vh = (const cplx*)V_host;
-    const bool scaled = !h->rs_T.empty();
-    for (int j = 0; j < r; ++j)
-        for (int i = 0; i < r; ++i) {
-            const cplx v = Vh[(size_t)j * r + i];
-            Vp[(size_t)j * ld + i] = scaled ? cscale(v, h->rs_T[i].x) : v;
-        }
+    std::vector<cplx> Vp;
+    fh_pad_block((const cplx*)V_host, r, ld, 0, 0, h->rs_T.empty() ? nullptr : h->rs_T.data(), Vp);
     if ((rc = fh_upload_small(h, dV, Vp.data(), Vp.size() * sizeof(cplx)))) return rc;
     h->rs_X = nullptr; h->rs_R = nullptr;
     fh_prof_begin(h, "ritz");
@@ -3138,8 +3033,8 @@ extern "C" int feasthip_rr_ritz_resident(feasthip_handle h, int64_t r64, const v
     int ldx = ld;
     if (fh_pick_ld(r) < ld) {
         ldx = fh_pick_ld(r);
-        if ((rc = fh_get_buf(h, "rs_tmp", (size_t)N * FH_MAX_LD * sizeof(cplx), &p))) return rc;
-        cplx* tmp = (cplx*)p;
+        cplx* tmp;
+        if ((rc = fh_buf(h, "rs_tmp", (size_t)N * FH_MAX_LD, &tmp))) return rc;
         for (cplx* pan : {Xp, Rp}) {
             fh_launch_panel_cols(pan, ld, 0, r, N, tmp, ldx, h->stream);
             FH_CHECK(hipMemcpyAsync(pan, tmp, (size_t)N * ldx * sizeof(cplx), hipMemcpyDeviceToDevice, h->stream));
@@ -3291,19 +3186,16 @@ extern "C" int feasthip_rayleigh_ritz_dev(feasthip_handle h, int64_t r64, const 
     std::vector<cplx> Sq((size_t)r * r), Aq((size_t)r * r);
     if ((rc = feasthip_project_dev(h, r64, dQ, 0, 1, Sq.data(), Aq.data()))) return rc;
     bool a_identity = fh_b_identity(h) != 0;                 // project returned exactly I
-    void* p;
-    if ((rc = fh_get_buf(h, "rr_S", (size_t)ld * ld * sizeof(cplx), &p))) return rc;
-    cplx* dS = (cplx*)p;
-    if ((rc = fh_get_buf(h, "rr_A", (size_t)ld * ld * sizeof(cplx), &p))) return rc;
-    cplx* dA = (cplx*)p;
-    if ((rc = fh_get_buf(h, "rr_V", (size_t)ld * ld * sizeof(cplx), &p))) return rc;
-    cplx* dV = (cplx*)p;
-    if ((rc = fh_get_buf(h, "rr_lam", ld * sizeof(double), &p))) return rc;
-    double* dlam = (double*)p;
-    if ((rc = fh_get_buf(h, "rr_flags", 4 * sizeof(int), &p))) return rc;
-    int* dflags = (int*)p;
-    if ((rc = fh_get_buf(h, "rr_scratch", fh_herm_eig_scratch_bytes(), &p))) return rc;
-    void* scratch = p;
+    cplx *dS, *dA, *dV;
+    double* dlam;
+    int* dflags;
+    void* scratch;                               // (laid out by the kernel: sized in bytes)
+    if ((rc = fh_buf(h, "rr_S", (size_t)ld * ld, &dS))) return rc;
+    if ((rc = fh_buf(h, "rr_A", (size_t)ld * ld, &dA))) return rc;
+    if ((rc = fh_buf(h, "rr_V", (size_t)ld * ld, &dV))) return rc;
+    if ((rc = fh_buf(h, "rr_lam", ld, &dlam))) return rc;
+    if ((rc = fh_buf(h, "rr_flags", 4, &dflags))) return rc;
+    if ((rc = fh_get_buf(h, "rr_scratch", fh_herm_eig_scratch_bytes(), &scratch))) return rc;
     std::vector<cplx> pad((size_t)ld * ld, cmake(0, 0));
     for (int j = 0; j < r; ++j) for (int i = 0; i < r; ++i) pad[(size_t)j * ld + i] = Sq[(size_t)j * r + i];
     FH_CHECK(hipMemcpyAsync(dS, pad.data(), pad.size() * sizeof(cplx), hipMemcpyHostToDevice, h->stream));
@@ -3361,11 +3253,9 @@ extern "C" int feasthip_matmul_dev(feasthip_handle h, int which, int64_t m64, co
     FH_CHECK(hipSetDevice(h->device));
     const int m = (int)m64, ld = fh_pick_ld(m), N = (int)fh_N(h);
     const size_t panel = (size_t)N * ld;
-    void* p;
-    if ((rc = fh_get_buf(h, "mm_X", panel * sizeof(cplx), &p))) return rc;
-    cplx* Xp = (cplx*)p;
-    if ((rc = fh_get_buf(h, "mm_Y", panel * sizeof(cplx), &p))) return rc;
-    cplx* Yp = (cplx*)p;
+    cplx *Xp, *Yp;
+    if ((rc = fh_buf(h, "mm_X", panel, &Xp))) return rc;
+    if ((rc = fh_buf(h, "mm_Y", panel, &Yp))) return rc;
     fh_launch_to_panel((const cplx*)dX, N, N, m, Xp, ld, h->stream, fh_perm(h));
     std::vector<cplx> ca(ld, cmake(which == 0 ? 1 : 0, 0)), cb(ld, cmake(which == 1 ? 1 : 0, 0));
     cplx *dca, *dcb;
@@ -3427,11 +3317,9 @@ extern "C" int feasthip_shifted_solve_dev(feasthip_handle h, double z_re, double
     FH_CHECK(hipSetDevice(h->device));
     const int m = (int)m64, ld = fh_pick_ld(m), N = (int)fh_N(h);
     const size_t panel = (size_t)N * ld;
-    void* p;
-    if ((rc = fh_get_buf(h, "ss_rhs", panel * sizeof(cplx), &p))) return rc;
-    cplx* Rhs = (cplx*)p;
-    if ((rc = fh_get_buf(h, "ss_Y", panel * sizeof(cplx), &p))) return rc;
-    cplx* Y = (cplx*)p;
+    cplx *Rhs, *Y;
+    if ((rc = fh_buf(h, "ss_rhs", panel, &Rhs))) return rc;
+    if ((rc = fh_buf(h, "ss_Y", panel, &Y))) return rc;
     if (stats) memset(stats, 0, sizeof(*stats));
     fh_launch_to_panel((const cplx*)dX, N, N, m, Rhs, ld, h->stream, fh_perm(h));
     std::vector<cplx> z(1, cmake(z_re, z_im));

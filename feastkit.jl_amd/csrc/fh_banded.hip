@@ -331,18 +331,16 @@ static int band_ensure_slots(feasthip_ctx* h, int nslots) {
 static int band_pointer_arrays(feasthip_ctx* h, const std::vector<int>& which, cplx*** dabs_out, int*** dpvs_out, int*** dperms_out) {
     const int nf = (int)which.size();
     const size_t off = h->band_plan == 2 ? fh_wband_base_offset((int)h->csr.N, h->band_kl, h->band_ku) : 0;
-    void* p;
     int rc;
     std::vector<cplx*> abs(nf);
     std::vector<int*> pvs(nf), perms(nf, h->band_perm);
     const size_t esz = (h->band_plan == 2 && h->band_prec == 32) ? sizeof(cplxf) : sizeof(cplx);
     for (int q = 0; q < nf; ++q) { abs[q] = (cplx*)((char*)h->band_factors[which[q]] + off * esz); pvs[q] = h->band_pivots[which[q]]; }
-    if ((rc = fh_get_buf(h, "bd_ptrs", nf * sizeof(cplx*), &p))) return rc;
-    cplx** dabs = (cplx**)p;
-    if ((rc = fh_get_buf(h, "bd_pptrs", nf * sizeof(int*), &p))) return rc;
-    int** dpvs = (int**)p;
-    if ((rc = fh_get_buf(h, "bd_permptrs", nf * sizeof(int*), &p))) return rc;
-    int** dperms = (int**)p;
+    cplx** dabs;
+    int **dpvs, **dperms;
+    if ((rc = fh_buf(h, "bd_ptrs", nf, &dabs))) return rc;
+    if ((rc = fh_buf(h, "bd_pptrs", nf, &dpvs))) return rc;
+    if ((rc = fh_buf(h, "bd_permptrs", nf, &dperms))) return rc;
     FH_CHECK(hipMemcpyAsync(dabs, abs.data(), nf * sizeof(cplx*), hipMemcpyHostToDevice, h->stream));
     FH_CHECK(hipMemcpyAsync(dpvs, pvs.data(), nf * sizeof(int*), hipMemcpyHostToDevice, h->stream));
     FH_CHECK(hipMemcpyAsync(dperms, perms.data(), nf * sizeof(int*), hipMemcpyHostToDevice, h->stream));
@@ -382,14 +380,13 @@ static int band_factor_batch(feasthip_ctx* h, const std::vector<int>& which, con
     if (nf == 0) return 0;
     const int N = (int)h->csr.N, kl = h->band_kl, ku = h->band_ku;
     const auto t_factor = std::chrono::steady_clock::now();
-    void* p;
     int rc;
+    cplx* dz;
     if (h->band_plan == 3) {
         std::vector<void*> stores(nf);
         std::vector<int*> pvs(nf);
         for (int q = 0; q < nf; ++q) { stores[q] = h->band_factors[which[q]]; pvs[q] = h->band_pivots[which[q]]; }
-        if ((rc = fh_get_buf(h, "bd_z", nf * sizeof(cplx), &p))) return rc;
-        cplx* dz = (cplx*)p;
+        if ((rc = fh_buf(h, "bd_z", nf, &dz))) return rc;
         FH_CHECK(hipMemcpyAsync(dz, zlist.data(), nf * sizeof(cplx), hipMemcpyHostToDevice, h->stream));
         // (fronts of a group) x (nodes of a call) is a grid dimension: node batches for long contours
         const int per_call = mf_nodes_per_call(h);
@@ -417,10 +414,9 @@ static int band_factor_batch(feasthip_ctx* h, const std::vector<int>& which, con
     }
     cplx** dabs; int** dpvs; int** dperms;
     if ((rc = band_pointer_arrays(h, which, &dabs, &dpvs, &dperms))) return rc;
-    if ((rc = fh_get_buf(h, "bd_z", nf * sizeof(cplx), &p))) return rc;
-    cplx* dz = (cplx*)p;
-    if ((rc = fh_get_buf(h, "bd_info", nf * sizeof(int), &p))) return rc;
-    int* dinfo = (int*)p;
+    int* dinfo;
+    if ((rc = fh_buf(h, "bd_z", nf, &dz))) return rc;
+    if ((rc = fh_buf(h, "bd_info", nf, &dinfo))) return rc;
     FH_CHECK(hipMemcpyAsync(dz, zlist.data(), nf * sizeof(cplx), hipMemcpyHostToDevice, h->stream));
     FH_CHECK(hipMemsetAsync(dinfo, 0, nf * sizeof(int), h->stream));
     if (h->band_plan == 2) {
@@ -471,13 +467,11 @@ static int band_solve_batch(feasthip_ctx* h, int ld, int m, const std::vector<in
     cplx** dabs; int** dpvs; int** dperms;
     if ((rc = band_pointer_arrays(h, slots, &dabs, &dpvs, &dperms))) return rc;
     if (h->band_plan == 2) {
-        void* p;
+        void *Yb, *Zb;                               // complex128 or complex64 panels: sized in bytes
         const size_t bstride = (size_t)N * ld;
         const size_t esz = h->band_prec == 32 ? sizeof(cplxf) : sizeof(cplx);
-        if ((rc = fh_get_buf(h, "bd_ypanel", (size_t)nf * bstride * esz, &p))) return rc;
-        void* Yb = p;
-        if ((rc = fh_get_buf(h, "bd_zpanel", (size_t)nf * bstride * esz, &p))) return rc;
-        void* Zb = p;
+        if ((rc = fh_get_buf(h, "bd_ypanel", (size_t)nf * bstride * esz, &Yb))) return rc;
+        if ((rc = fh_get_buf(h, "bd_zpanel", (size_t)nf * bstride * esz, &Zb))) return rc;
         return fh_wband_solve(h, h->band_prec, nf, (void**)dabs, dpvs, dperms, h->band_perm, RHS, rhs_stride, Y, stride, Yb, Zb, ld, m, h->band_kl, h->band_ku);
     }
     fh_prof_begin(h, "band_solve");

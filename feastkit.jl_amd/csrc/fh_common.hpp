@@ -242,6 +242,13 @@ struct feasthip_ctx {
 
 // workspace helper: returns a device buffer of at least `bytes`, reallocating if needed
 int fh_get_buf(feasthip_ctx* h, const char* name, size_t bytes, void** out);
+// the same for `count` elements of T (*out is left alone when the request fails)
+template <typename T> inline int fh_buf(feasthip_ctx* h, const char* name, size_t count, T** out) {
+    void* p = nullptr;
+    const int rc = fh_get_buf(h, name, count * sizeof(T), &p);
+    if (!rc) *out = (T*)p;
+    return rc;
+}
 void fh_free_bufs(feasthip_ctx* h);
 
 // profiling helpers

@@ -1835,19 +1835,18 @@ static int lu_factor_batch(feasthip_ctx* h, const std::vector<int>& which, const
     if (nf == 0) return 0;
     const int N = (int)h->dense.N;
     const lu_geom geom = lu_dense_geom<T>(N);
-    void* p;
     int rc;
     std::vector<T*> lus(nf);
     std::vector<int*> pvs(nf);
     for (int q = 0; q < nf; ++q) { lus[q] = (T*)h->lu_factors[which[q]]; pvs[q] = h->lu_pivots[which[q]]; }
-    if ((rc = fh_get_buf(h, "lu_ptrs", nf * sizeof(T*), &p))) return rc;
-    T** dlus = (T**)p;
-    if ((rc = fh_get_buf(h, "lu_pptrs", nf * sizeof(int*), &p))) return rc;
-    int** dpvs = (int**)p;
-    if ((rc = fh_get_buf(h, "lu_z", nf * sizeof(cplx), &p))) return rc;
-    cplx* dz = (cplx*)p;
-    if ((rc = fh_get_buf(h, "lu_info", nf * sizeof(int), &p))) return rc;
-    int* dinfo = (int*)p;
+    T** dlus;
+    int** dpvs;
+    cplx* dz;
+    int* dinfo;
+    if ((rc = fh_buf(h, "lu_ptrs", nf, &dlus))) return rc;
+    if ((rc = fh_buf(h, "lu_pptrs", nf, &dpvs))) return rc;
+    if ((rc = fh_buf(h, "lu_z", nf, &dz))) return rc;
+    if ((rc = fh_buf(h, "lu_info", nf, &dinfo))) return rc;
     FH_CHECK(hipMemcpyAsync(dlus, lus.data(), nf * sizeof(T*), hipMemcpyHostToDevice, h->stream));
     FH_CHECK(hipMemcpyAsync(dpvs, pvs.data(), nf * sizeof(int*), hipMemcpyHostToDevice, h->stream));
     FH_CHECK(hipMemcpyAsync(dz, zlist.data(), nf * sizeof(cplx), hipMemcpyHostToDevice, h->stream));
@@ -2088,22 +2087,18 @@ static int lu_solve_batch(feasthip_ctx* h, int ld, int m, const std::vector<int>
                           cplx* Y, size_t stride) {
     const int nf = (int)slots.size();
     const int N = (int)h->dense.N;
-    void* p;
     int rc;
     std::vector<T*> lus(nf);
     std::vector<int*> perms(nf);
     for (int q = 0; q < nf; ++q) { lus[q] = (T*)h->lu_factors[slots[q]]; perms[q] = h->lu_pivots[slots[q]] + N; }
-    if ((rc = fh_get_buf(h, "lu_ptrs", nf * sizeof(T*), &p))) return rc;
-    T** dlus = (T**)p;
-    if ((rc = fh_get_buf(h, "lu_permptrs", nf * sizeof(int*), &p))) return rc;
-    int** dperms = (int**)p;
-    if ((rc = fh_get_buf(h, "lu_zpanel", (size_t)nf * stride * sizeof(T), &p))) return rc;
-    T* Z = (T*)p;
+    T** dlus;
+    int** dperms;
+    T* Z;
+    if ((rc = fh_buf(h, "lu_ptrs", nf, &dlus))) return rc;
+    if ((rc = fh_buf(h, "lu_permptrs", nf, &dperms))) return rc;
+    if ((rc = fh_buf(h, "lu_zpanel", (size_t)nf * stride, &Z))) return rc;
     T* W = (T*)Y;                                   // working panel: Y itself in fp64, a complex64 buffer otherwise
-    if (sizeof(T) != sizeof(cplx)) {
-        if ((rc = fh_get_buf(h, "lu_wpanel", (size_t)nf * stride * sizeof(T), &p))) return rc;
-        W = (T*)p;
-    }
+    if (sizeof(T) != sizeof(cplx) && (rc = fh_buf(h, "lu_wpanel", (size_t)nf * stride, &W))) return rc;
     FH_CHECK(hipMemcpyAsync(dlus, lus.data(), nf * sizeof(T*), hipMemcpyHostToDevice, h->stream));
     FH_CHECK(hipMemcpyAsync(dperms, perms.data(), nf * sizeof(int*), hipMemcpyHostToDevice, h->stream));
     FH_CHECK(hipStreamSynchronize(h->stream));
@@ -2919,10 +2914,9 @@ static int mf_pointer_arrays(feasthip_ctx* h, const fh_mf_state& S, int nf, void
                 hp[m] = pivs[q] + G.piv_off + s * 2 * (size_t)G.np;
             }
     }
-    void* p;
     int rc;
-    if ((rc = fh_get_buf(h, "mf_ptrs", 4 * tot * sizeof(void*), &p))) return rc;
-    out.work = (T**)p; out.store = out.work + tot; out.u12 = out.store + tot; out.piv = (int**)(out.u12 + tot);
+    if ((rc = fh_buf(h, "mf_ptrs", 4 * tot, &out.work))) return rc;      // (four arrays of pointers: T* and int* have one size)
+    out.store = out.work + tot; out.u12 = out.store + tot; out.piv = (int**)(out.u12 + tot);
     FH_CHECK(hipMemcpyAsync(out.work, hw.data(), tot * sizeof(void*), hipMemcpyHostToDevice, h->stream));
     FH_CHECK(hipMemcpyAsync(out.store, hs.data(), tot * sizeof(void*), hipMemcpyHostToDevice, h->stream));
     FH_CHECK(hipMemcpyAsync(out.u12, hu.data(), tot * sizeof(void*), hipMemcpyHostToDevice, h->stream));
@@ -2944,13 +2938,12 @@ static int mf_factor_t(feasthip_ctx* h, int nf, void* const* stores, int* const*
     if (!S) { h->last_error = "multifrontal LU: no plan"; return FEASTHIP_ERROR_INTERNAL; }
     const fh_mf::plan& P = S->P;
     const int ng = (int)P.groups.size();
-    void* p;
     int rc;
     const bool dbg = fh_knob::debug_timing();
     const auto t_in = std::chrono::steady_clock::now();
     auto since = [&]() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_in).count(); };
-    if ((rc = fh_get_buf(h, "mf_work", (size_t)nf * P.work_elems * sizeof(T), &p))) return rc;
-    T* work = (T*)p;
+    T* work;
+    if ((rc = fh_buf(h, "mf_work", (size_t)nf * P.work_elems, &work))) return rc;
     const double t_work = since();
     mf_ptrs<T> ptr;
     if ((rc = mf_pointer_arrays<T>(h, *S, nf, stores, pivs, work, true, ptr))) return rc;
@@ -2958,11 +2951,11 @@ static int mf_factor_t(feasthip_ctx* h, int nf, void* const* stores, int* const*
     const size_t tot = ptr.off[ng];
     for (int g = 0; g < ng; ++g)
         if (P.groups[g].fronts.size() * (size_t)nf > 65535) { h->last_error = "multifrontal LU: more than 65535 fronts x nodes in one group"; return FEASTHIP_ERROR_FPM; }
-    if ((rc = fh_get_buf(h, "mf_info", tot * sizeof(int), &p))) return rc;
-    int* dinfo = (int*)p;
+    int* dinfo;
+    if ((rc = fh_buf(h, "mf_info", tot, &dinfo))) return rc;
     FH_CHECK(hipMemsetAsync(dinfo, 0, tot * sizeof(int), h->stream));
-    if ((rc = fh_get_buf(h, "mf_mult", tot * (MF_MULT_PARTS + 1) * sizeof(float), &p))) return rc;
-    float* dpart = (float*)p;
+    float* dpart;
+    if ((rc = fh_buf(h, "mf_mult", tot * (MF_MULT_PARTS + 1), &dpart))) return rc;
     float* dmult = dpart + tot * MF_MULT_PARTS;
     FH_CHECK(hipMemsetAsync(dpart, 0, tot * MF_MULT_PARTS * sizeof(float), h->stream));
     const bool bid = h->csr.b_identity != 0, cz = h->csr.is_complex != 0;
@@ -3108,13 +3101,11 @@ template <int LD, typename T>
 static int mf_solve_ld(feasthip_ctx* h, fh_mf_state* S, int nf, const mf_ptrs<T>& ptr, const cplx* RHS, size_t rhs_stride, cplx* OUT, size_t out_stride, int m) {
     const fh_mf::plan& P = S->P;
     const int cta = std::max(1, std::min(LD / 16, (m + 15) / 16));
-    void* p;
     int rc;
     const size_t rows = P.rhs_rows * (size_t)nf;
-    if ((rc = fh_get_buf(h, "mf_y", rows * LD * sizeof(T), &p))) return rc;
-    T* Y = (T*)p;
-    if ((rc = fh_get_buf(h, "mf_z", rows * LD * sizeof(T), &p))) return rc;
-    T* Z = (T*)p;
+    T *Y, *Z;
+    if ((rc = fh_buf(h, "mf_y", rows * LD, &Y))) return rc;
+    if ((rc = fh_buf(h, "mf_z", rows * LD, &Z))) return rc;
     fh_prof_begin(h, "mf_solve");
     auto diag = [&](bool upper, T** ST, T* IN, T* OUTp, size_t stride, const lu_geom& gd, int K0, int kb, int nmat, bool inv128) {
         const dim3 grid(cta, nmat), block(FH_BLOCK);

@@ -104,6 +104,84 @@ def test_project_matches_numpy(engine, N, m):
     assert np.abs(At - Q.T @ (A @ Q)).max() <= 1e-11 * np.abs(refA).max()
 
 
+@pytest.mark.parametrize("m", [16, 40, 65, 130])      # one panel at ld 16, one at ld 64, two (the second a single column), three
+@pytest.mark.parametrize("bid", [False, True])
+def test_rayleigh_ritz_calls_issue_the_pinned_work(m, bid):
+    """The Gram and Ritz launches every Rayleigh-Ritz entry point issues per call, counted by the in-library profiler, next to
+    the numerical results against numpy (tolerances of test_project_matches_numpy and test_ritz_residual).  npan = ceil(m / 64).
+    project: 2 Gram launches per npan^2 blocks, 1 when B = I and the Hermitian form returns I exactly without a product;
+    project_pair: always 2 npan^2; ritz_residual: npan^2 Ritz brackets; the resident reduce of a well-conditioned panel
+    (fast path, m <= 64): Q^H Q, Q^H A Q and, for general B, Q^H B Q; the resident Ritz step: 1."""
+    import feastkit_jl_amd as fk
+    N = 300
+    npan = (m + 63) // 64
+    A, B = sparse_pair(N, 3, cplx=True, b_identity=bid)
+    Bm = sp.identity(N, format="csr") if bid else B
+    Q, QL = rand_block(N, m, 9), rand_block(N, m, 10)
+    V = rand_block(m, m, 3)
+    lam = np.linspace(0.5, 3.0, m) + 0j
+    M = m - 3
+    eng = fk.HipEngine(0)
+    try:
+        eng.set_problem(A, B)
+        eng.profile_enable()
+        dQ, dQL = eng.upload(Q), eng.upload(QL)
+
+        def launches(cls, call):
+            before = eng.profile_get(cls)[1]
+            out = call()
+            return eng.profile_get(cls)[1] - before, out
+
+        rawA, rawB = Q.conj().T @ (A @ Q), Q.conj().T @ (Bm @ Q)
+        refA, refB = fo.hermitian_part(rawA), fo.hermitian_part(rawB)
+        n, (Aq, Bq) = launches("gram", lambda: eng.project(dQ, m, bilinear=False, hermitize=True))
+        assert n == (1 if bid else 2) * npan * npan
+        assert np.abs(Aq - refA).max() <= 1e-11 * np.abs(refA).max()
+        if bid:
+            assert np.array_equal(Bq, np.eye(m))
+        else:
+            assert np.abs(Bq - refB).max() <= 1e-11 * np.abs(refB).max()
+        n, (Ar, Br) = launches("gram", lambda: eng.project(dQ, m, bilinear=False, hermitize=False))
+        assert n == 2 * npan * npan
+        assert np.abs(Ar - rawA).max() <= 1e-11 * np.abs(refA).max()
+        assert np.abs(Br - rawB).max() <= 1e-11 * np.abs(refB).max()
+
+        pairA, pairB = QL.conj().T @ (A @ Q), QL.conj().T @ (Bm @ Q)
+        n, (Ap, Bp) = launches("gram", lambda: eng.project_pair(dQL, dQ, m))
+        assert n == 2 * npan * npan
+        assert np.abs(Ap - pairA).max() <= 1e-11 * np.abs(pairA).max()
+        assert np.abs(Bp - pairB).max() <= 1e-11 * np.abs(pairB).max()
+
+        n, (dX, res) = launches("ritz", lambda: eng.ritz_residual(dQ, m, V, lam, M, normalize=True, use_B=True))
+        assert n == npan * npan
+        X = Q @ V
+        X[:, :M] /= np.linalg.norm(X[:, :M], axis=0)
+        assert np.abs(eng.download(dX) - X).max() <= 1e-11 * np.abs(X).max()
+        ref = fo.feast_residual(A, B, lam.real, X, M)
+        assert np.abs(res - ref).max() <= 1e-10 * ref.max()
+
+        if m <= 64:
+            # resident stages on an imported panel with orthogonal columns of norms 1 .. 2: the implicit basis is taken
+            P = np.linalg.qr(Q)[0] * np.linspace(1.0, 2.0, m)[None, :]
+            Pn = P / np.linalg.norm(P, axis=0)
+            eng.import_resident(eng.upload(P), m, which=1)
+            n, (rank, Aq, Bq) = launches("gram", lambda: eng.rr_reduce_resident(m, np.sqrt(np.finfo(float).eps)))
+            assert rank == m and eng.last_ortho()["method"] == "cholqr"
+            assert n == (2 if bid else 3)
+            refA, refB = fo.hermitian_part(Pn.conj().T @ (A @ Pn)), fo.hermitian_part(Pn.conj().T @ (Bm @ Pn))
+            assert np.abs(Aq - refA).max() <= 1e-11 * np.abs(refA).max()
+            assert np.abs(Bq - refB).max() <= 1e-11 * np.abs(refB).max()
+            n, res = launches("ritz", lambda: eng.rr_ritz_resident(m, V, lam, M, normalize=True, use_B=True))
+            assert n == 1
+            X = Pn @ V
+            X[:, :M] /= np.linalg.norm(X[:, :M], axis=0)
+            assert np.abs(eng.download(eng.export_resident(m)) - X).max() <= 1e-11 * np.abs(X).max()
+            ref = fo.feast_residual(A, B, lam.real, X, M)
+            assert np.abs(res - ref).max() <= 1e-10 * ref.max()
+    finally:
+        eng.close()
+
+
 @pytest.mark.parametrize("N,m", [(257, 16), (1000, 33), (2049, 64)])
 def test_real_panels_take_the_one_product_path(engine, N, m):
     """Panels without imaginary parts (what a real projection of a real pencil produces) make the MFMA Gram and Q V kernels
