@@ -76,6 +76,7 @@ SYMBOLS = {
     "feasthip_project": (_i, [_vp, _i64, _vp, _i, _i, _vp, _vp]),
     "feasthip_project_dev": (_i, [_vp, _i64, _vp, _i, _i, _vp, _vp]),
     "feasthip_set_adjoint": (_i, [_vp, _i]),
+    "feasthip_require_adjoint": (_i, [_vp, _i]),
     "feasthip_project_pair": (_i, [_vp, _i64, _vp, _vp, _vp, _vp]),
     "feasthip_project_pair_dev": (_i, [_vp, _i64, _vp, _vp, _vp, _vp]),
     "feasthip_ritz_residual": (_i, [_vp, _i64, _vp, _vp, _vp, _i64, _i, _i, _vp, _vp]),

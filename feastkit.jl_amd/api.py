@@ -27,14 +27,8 @@ def _is_hermitian(A, tol=0.0):
     return np.array_equal(A, A.conj().T)
 
 
-def _sparse_direct_solver(A, B, nodes, budget_bytes=32 << 30, dense_limit=12288):
-    """``solver=:direct`` for sparse input (UMFPACK in the reference, src/sparse/feast_sparse.jl:334-342, :943):
-      "banded" -- the union pattern of A and B is a narrow band whose LU factors (2 kl + ku + 1 rows per column and
-                  node, complex128) fit the budget: batched banded LU on the CSR arrays;
-      "dense"  -- any other pattern up to N = dense_limit whose N x N complex128 factors (one per node, plus A and B)
-                  fit the budget: the matrix is expanded on ingest and factored by the batched dense LU -- an exact
-                  direct solve like the reference's, at O(N^3) per node, which the MFMA LU affords at these sizes;
-      "krylov" -- everything larger: the batched Krylov solvers (north_star's iterative path)."""
+def _band_widths(A, B):
+    """(kl, ku) of the union pattern of A and B in the caller's order."""
     kl = ku = 0
     for M in (A, B):
         if M is None:
@@ -43,9 +37,26 @@ def _sparse_direct_solver(A, B, nodes, budget_bytes=32 << 30, dense_limit=12288)
         if c.nnz:
             kl = max(kl, int((c.row - c.col).max()))
             ku = max(ku, int((c.col - c.row).max()))
+    return kl, ku
+
+
+# kl + ku up to which the library's direct plan is the one-workgroup narrow band LU (FH_BAND_NARROW, csrc/fh_banded.hip)
+_NARROW_BAND = 64
+
+
+def _sparse_direct_solver(A, B, nodes, budget_bytes=32 << 30, dense_limit=12288, allow_band=True):
+    """``solver=:direct`` for sparse input (UMFPACK in the reference, src/sparse/feast_sparse.jl:334-342, :943):
+      "banded" -- the union pattern of A and B is a narrow band whose LU factors (2 kl + ku + 1 rows per column and
+                  node, complex128) fit the budget: batched banded LU on the CSR arrays;
+      "dense"  -- any other pattern up to N = dense_limit whose N x N complex128 factors (one per node, plus A and B)
+                  fit the budget: the matrix is expanded on ingest and factored by the batched dense LU -- an exact
+                  direct solve like the reference's, at O(N^3) per node, which the MFMA LU affords at these sizes;
+      "krylov" -- everything larger: the batched Krylov solvers (north_star's iterative path).
+    ``allow_band=False`` leaves the narrow-band answer out (the two-sided call: that LU has no adjoint substitution)."""
+    kl, ku = _band_widths(A, B)
     ldab = 2 * kl + ku + 1
     N = A.shape[0]
-    if 2 * kl + ku + 1 <= 3500 and ldab * N * 16 * max(nodes, 1) <= budget_bytes and kl + ku <= 512:
+    if allow_band and 2 * kl + ku + 1 <= 3500 and ldab * N * 16 * max(nodes, 1) <= budget_bytes and kl + ku <= 512:
         return "banded"
     if N <= dense_limit and (max(nodes, 1) + 2) * N * N * 16 <= budget_bytes:
         return "dense"
@@ -436,16 +447,53 @@ def feast(A, B=None, interval=None, *, M0=10, fpm=None, backend="hip", solver="d
     return res
 
 
+def _two_sided_sparse_route(A, B, solver, nodes, engine, device):
+    """Where ``feast_general(A_sparse, ..., two_sided=True)`` runs -> (A, B, solver, substitution record, engine).
+    ``direct`` / ``lu``: ValueError for a pattern inside the library's narrow band (kl + ku <= 64: that solver means the
+    one-workgroup band LU there, which has no adjoint substitution, and a band that thin is not expanded silently: the caller
+    chooses ``sparse_direct`` or dense input); else the expanded matrix under the dense LU inside _sparse_direct_solver's dense
+    window (the wider band answer is left out: that LU has no adjoint substitution either), else -- as for an explicit ``sparse_direct`` / ``banded`` -- the
+    sparse direct solver with the multifrontal plan
+    (require_adjoint is set BEFORE the plan is queried, so the plan query already answers for the plan that has an adjoint
+    substitution; the driver clears it), provided its factors fit the device.  Otherwise ValueError: there is no Krylov solver
+    on the conjugate transpose."""
+    if solver in ("direct", "lu"):
+        kl, ku = _band_widths(A, B)
+        if kl + ku <= _NARROW_BAND:
+            # (host-only, before any engine exists: the refusal the dense-only version of this keyword gave such input stays)
+            raise ValueError("two_sided with solver='direct' on a sparse matrix inside the narrow band (kl + ku <= 64): the band LU "
+                             "that solver means for it has no adjoint substitution, and expanding a band this thin is not done "
+                             "silently; pass solver='sparse_direct' (multifrontal LU) or dense input")
+    if solver in ("direct", "lu") and _sparse_direct_solver(A, B, nodes, allow_band=False) == "dense":
+        return _densify(A), _densify(B), "direct", {"requested": "direct", "used": "dense LU of the expanded matrix"}, engine
+    explicit = solver in ("sparse_direct", "banded")
+    engine = _engine(engine, device)
+    engine.require_adjoint(True)
+    try:
+        fits = _band_direct_fits(engine, A, B, nodes, None, complexify=True)
+        label = _direct_label(engine) if fits else None
+    finally:
+        engine.require_adjoint(False)
+    if not fits and not explicit:
+        raise ValueError("two_sided on this sparse input: the factors of the sparse direct solver do not fit the device, and "
+                         "there is no Krylov solver on the conjugate transpose")
+    return A, B, "banded", (None if explicit else {"requested": "direct", "used": label}), engine
+
+
 def feast_general(A, B=None, center=0.0, radius=1.0, *, M0=10, fpm=None, backend="hip", solver="direct",
                   solver_tol=0.0, solver_maxiter=500, solver_restart=30, group=None, engine=None, device=0, Q0=None,
                   inner_precision=64, contour=None, keep_factors=False, seed=None, direct_nodes=None, ortho="mgs",
                   two_sided=False, QL0=None):
     """feast_general(A, [B,] center, radius; M0, fpm): src/interfaces/feast_interfaces.jl:274-379.
-    ``two_sided=True`` (dense input, ``solver="direct"``): the two-sided method -- a left subspace from conjugate-transposed
-    solves on the LU factors of the right sweep, oblique projection, both residuals with B; the result carries ``q_left``
-    (y_j^H B x_j = 1) and ``stats["two_sided"]``, and ``info`` is Feast_ERROR_NO_CONVERGENCE when the loop limit ends the run.
+    ``two_sided=True`` (``solver="direct"``; sparse input also ``"sparse_direct"`` / ``"banded"``): the two-sided method -- a
+    left subspace from conjugate-transposed solves on the LU factors of the right sweep, oblique projection, both residuals
+    with B; the result carries ``q_left`` (y_j^H B x_j = 1) and ``stats["two_sided"]`` (``direct_plan`` names the factors that
+    ran), and ``info`` is Feast_ERROR_NO_CONVERGENCE when the loop limit ends the run.  Sparse input runs on the multifrontal
+    LU of the sparse direct solver, or -- ``solver="direct"`` up to N = 12 288 -- on the dense LU of the expanded matrix
+    (``stats["solver_substitution"]``); ``solver="direct"`` on a narrow band (kl + ku <= 64) raises ValueError and names
+    ``solver="sparse_direct"``; there is no Krylov solver on the conjugate transpose.
     ``QL0``: left start block.  The keyword is the only switch: fpm[15], which the reference validates and never reads
-    (src/core/feast_parameters.jl:217-225), stays unread here too, so no existing call changes.  Sparse input, another
+    (src/core/feast_parameters.jl:217-225), stays unread here too, so no existing call changes.  A Krylov
     solver, ``inner_precision=32``, ``group=`` and ``direct_nodes=`` raise ValueError.
     ``keep_factors``, ``direct_nodes``, ``ortho``: as in feast() (this variant never orthonormalises its subspace, so ``ortho``
     changes nothing it computes).  ``fpm[14] = 2`` and ``M0="auto"``: as in feast(), on the full contour of the
@@ -482,7 +530,9 @@ def feast_general(A, B=None, center=0.0, radius=1.0, *, M0=10, fpm=None, backend
                                   solver_maxiter, solver_restart, group)
         return _estimate_result(N, info, est, False)
     substituted = None
-    if sp.issparse(A) and solver in ("direct", "lu"):
+    if two_sided and sp.issparse(A):
+        A, B, solver, substituted, engine = _two_sided_sparse_route(A, B, solver, int(fpm[8]), engine, device)
+    elif sp.issparse(A) and solver in ("direct", "lu"):
         # the reference factors z B - A with UMFPACK (src/sparse/feast_sparse.jl:943); here: banded LU for narrow
         # bands, else batched BiCGStab on the (non-symmetric) shifted systems with the reference's iterative
         # settings (zero guess, rtol = atol = 10^-fpm[3], src/sparse/feast_sparse.jl:164-203)

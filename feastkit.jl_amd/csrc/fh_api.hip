@@ -176,6 +176,11 @@ extern "C" int feasthip_create(feasthip_handle* out, int device_id) {
     return 0;
 }
 
+static void fh_free_adjoint_csr(feasthip_ctx* h) {
+    for (void* p : {(void*)h->csr_adj.rowptr, (void*)h->csr_adj.col, h->csr_adj.aval, h->csr_adj.bval}) if (p) hipFree(p);
+    h->csr_adj = fh_csr();
+}
+
 static void fh_free_problem(feasthip_ctx* h) {
     if (h->csr.rowptr) hipFree(h->csr.rowptr);
     if (h->csr.col) hipFree(h->csr.col);
@@ -191,6 +196,7 @@ static void fh_free_problem(feasthip_ctx* h) {
     if (h->csr.ext_idx) hipFree(h->csr.ext_idx);
     if (h->csr.lcol) hipFree(h->csr.lcol);
     h->csr = fh_csr();
+    fh_free_adjoint_csr(h);
     if (h->dense.A) hipFree(h->dense.A);
     if (h->dense.B) hipFree(h->dense.B);
     h->dense = fh_dense();
@@ -257,6 +263,7 @@ extern "C" int feasthip_synchronize(feasthip_handle h) {
 // ---------------------------------------------------------------------------------------
 static inline cplx fh_ing_zero(cplx) { return cmake(0, 0); }
 static inline cplx fh_ing_add(cplx a, cplx b) { return cadd(a, b); }
+static inline cplx fh_ing_conj(cplx a) { return cmake(a.x, -a.y); }
 #define FH_INGEST_STORAGE_CSR FEASTHIP_STORAGE_CSR
 #include "fh_ingest.hpp"       // host side of the ingest (pure C++; also compiled under ASan/UBSan by tests/host_ingest_harness.cpp)
 #include "fh_policy.hpp"       // host policy of the inexact mode (pure C++), exported as feasthip_policy_*
@@ -324,6 +331,44 @@ static int set_csr_typed(feasthip_ctx* h, int64_t N, int index_base, int storage
     }
     h->kind = 2;
     return 0;
+}
+
+// The adjoint CSR set of the problem (h->csr_adj), built on first use: the host keeps only the pattern, so the values come back
+// from the device once; the transpose is fh_adjoint_csr (fh_ingest.hpp).  Only what k_spmm reads is made: no chunk-of-8 rows,
+// no LDS-window data.
+template <typename VT>
+static int fh_adjoint_csr_build(feasthip_ctx* h) {
+    const fh_csr& d = h->csr;
+    const int64_t N = d.N;
+    const size_t nnz = (size_t)d.nnz;
+    if ((int64_t)h->host_rowptr.size() != N + 1 || h->host_col.size() != nnz) { h->last_error = "adjoint CSR set: no host pattern"; return FEASTHIP_ERROR_INTERNAL; }
+    std::vector<VT> av(nnz), bv(d.b_identity ? 0 : nnz);
+    FH_CHECK(hipStreamSynchronize(h->stream));
+    if (nnz) FH_CHECK(hipMemcpy(av.data(), d.aval, nnz * sizeof(VT), hipMemcpyDeviceToHost));
+    if (nnz && !d.b_identity) FH_CHECK(hipMemcpy(bv.data(), d.bval, nnz * sizeof(VT), hipMemcpyDeviceToHost));
+    std::vector<int> rp, cl;
+    std::vector<VT> avt, bvt;
+    fh_adjoint_csr<VT>(N, h->host_rowptr, h->host_col, av.data(), d.b_identity ? nullptr : bv.data(), rp, cl, avt, bvt);
+    fh_free_adjoint_csr(h);
+    fh_csr& t = h->csr_adj;
+    FH_CHECK(hipMalloc((void**)&t.rowptr, (N + 1) * sizeof(int)));
+    FH_CHECK(hipMalloc((void**)&t.col, std::max<size_t>(1, nnz) * sizeof(int)));
+    FH_CHECK(hipMalloc(&t.aval, std::max<size_t>(1, nnz) * sizeof(VT)));
+    FH_CHECK(hipMemcpy(t.rowptr, rp.data(), (N + 1) * sizeof(int), hipMemcpyHostToDevice));
+    if (nnz) FH_CHECK(hipMemcpy(t.col, cl.data(), nnz * sizeof(int), hipMemcpyHostToDevice));
+    if (nnz) FH_CHECK(hipMemcpy(t.aval, avt.data(), nnz * sizeof(VT), hipMemcpyHostToDevice));
+    if (!d.b_identity) {
+        FH_CHECK(hipMalloc(&t.bval, std::max<size_t>(1, nnz) * sizeof(VT)));
+        if (nnz) FH_CHECK(hipMemcpy(t.bval, bvt.data(), nnz * sizeof(VT), hipMemcpyHostToDevice));
+    }
+    t.N = N; t.nnz = d.nnz; t.is_complex = d.is_complex; t.b_identity = d.b_identity;
+    return 0;
+}
+static int fh_adjoint_csr_ensure(feasthip_ctx* h) {
+    if (h->csr_adj.rowptr && h->csr_adj.N == h->csr.N) return 0;
+    const int rc = h->csr.is_complex ? fh_adjoint_csr_build<cplx>(h) : fh_adjoint_csr_build<double>(h);
+    if (rc) fh_free_adjoint_csr(h);
+    return rc;
 }
 
 extern "C" int feasthip_set_csr(feasthip_handle h, int64_t N, int is_complex, int index_base, int storage,
@@ -447,6 +492,12 @@ extern "C" int feasthip_set_adjoint(feasthip_handle h, int on) {
     return 0;
 }
 
+extern "C" int feasthip_require_adjoint(feasthip_handle h, int on) {
+    if (!h) return FEASTHIP_ERROR_INTERNAL;
+    h->require_adjoint = on ? 1 : 0;
+    return 0;
+}
+
 extern "C" int feasthip_set_node_range(feasthip_handle h, int first, int count) {
     if (!h) return FEASTHIP_ERROR_INTERNAL;
     if (first < 0 || count < 0 || first + count > (int)h->zne.size()) {
@@ -526,6 +577,24 @@ static bool fh_row_kernel_ok(feasthip_ctx* h, int ld) {
 
 // returns number of blocks used in x (needed to size / read partials)
 static int fh_apply_operator(feasthip_ctx* h, int ld, const fh_op_call& c) {
+    if (h->kind == 2 && h->adjoint) {
+        // the conjugate-transposed set through the gather kernel (plain products only, as for the dense adjoint operator)
+        if (c.dot_mode != 0 || c.colscale) { h->last_error = "internal: adjoint operator with fused dots"; return -1; }
+        if (fh_adjoint_csr_ensure(h)) return -1;
+        fh_spmm_args a;
+        a.rowptr = h->csr_adj.rowptr; a.col = h->csr_adj.col; a.aval = h->csr_adj.aval; a.bval = h->csr_adj.bval;
+        a.N = (int)h->csr.N; a.nodes = c.nodes;
+        a.X = c.X; a.x_node_stride = c.x_stride; a.Y = c.Y; a.y_node_stride = c.y_stride;
+        a.coefA = c.coefA; a.coefB = c.coefB; a.Bvec = c.Bvec; a.b_node_stride = c.b_stride;
+        a.U = c.U; a.u_node_stride = c.u_stride; a.dot_mode = 0;
+        a.partial1 = nullptr; a.partial2 = nullptr; a.node_active = c.node_active;
+        a.nblk_rows = 0; a.blk_start = nullptr; a.ext_ptr = nullptr; a.ext_idx = nullptr; a.lcol = nullptr;
+        a.counters = h->profiling ? h->d_counters : nullptr; a.m = c.m; a.uniform_coef = c.uniform_coef; a.prec = c.prec;
+        fh_prof_begin(h, "spmm_adjoint");
+        fh_launch_spmm(a, ld, h->csr.is_complex != 0, h->csr.b_identity != 0, fh_spmm_grid(a.N, ld), h->stream);
+        fh_prof_end(h);
+        return fh_spmm_partials(a.N, ld);
+    }
     if (h->kind == 2) {
         fh_spmm_args a;
         a.rowptr = h->csr.rowptr; a.col = h->csr.col; a.aval = h->csr.aval; a.bval = h->csr.bval;
@@ -599,15 +668,26 @@ static int fh_check_problem(feasthip_ctx* h, int64_t m, int wide = 0) {
 }
 
 // Adjoint switch (feasthip_set_adjoint).  unsupported != null: the entry point has no adjoint form at all.  Otherwise the
-// handle must be what the adjoint kernels cover: a dense problem, the dense LU in fp64, no real projection, one rank.
+// handle must be what the adjoint kernels cover: fp64 factors, no real projection, one rank, and either a dense problem under
+// the dense LU or a CSR problem under the sparse direct solver with the multifrontal plan (made here if need be).
 static int fh_check_adjoint(feasthip_ctx* h, const char* what, const char* unsupported = nullptr) {
     if (!h || !h->adjoint) return 0;
     const char* why = unsupported;
-    if (!why && h->kind == 2) why = "a CSR problem has no adjoint substitution (dense problems only)";
-    if (!why && h->solver != FEASTHIP_SOLVER_LU) why = "the solver must be the dense LU (FEASTHIP_SOLVER_LU)";
+    if (!why && h->kind == 2 && h->solver == FEASTHIP_SOLVER_LU) why = "a CSR problem has no dense LU; its adjoint substitution needs FEASTHIP_SOLVER_BANDED with the multifrontal plan";
+    if (!why && h->kind == 2 && h->solver != FEASTHIP_SOLVER_BANDED) why = "the solver of a CSR problem must be the sparse direct one (FEASTHIP_SOLVER_BANDED): there is no Krylov solver on the conjugate transpose";
+    if (!why && h->kind != 2 && h->solver != FEASTHIP_SOLVER_LU) why = "the solver must be the dense LU (FEASTHIP_SOLVER_LU)";
     if (!why && h->factor_precision == 32) why = "factor_precision = 32 is not supported (complex128 factors only)";
     if (!why && h->real_projection) why = "the real projection does not apply to an adjoint sweep";
     if (!why && h->comm) why = "an attached communicator is not supported";
+    if (!why && h->kind == 2)
+        for (int k : h->node_kinds) if (k != 0) { why = "per-node solver kinds (feasthip_set_node_solver) are not supported"; break; }
+    std::string plan_why;
+    if (!why && h->kind == 2 && !h->poisoned) {
+        if (hipSetDevice(h->device) != hipSuccess) { h->last_error = "hipSetDevice"; return FEASTHIP_ERROR_INTERNAL; }
+        if (fh_banded_adjoint_ready(h)) { plan_why = h->last_error; why = plan_why.c_str(); }
+        // the conjugate-transposed CSR set, built here at the first adjoint call so that a failed build is an error of the call
+        else if (int rc = fh_adjoint_csr_ensure(h)) return rc;
+    }
     if (!why) return 0;
     h->last_error = std::string(what) + " with the adjoint switch on (feasthip_set_adjoint): " + why;
     return FEASTHIP_ERROR_FPM;

@@ -188,7 +188,7 @@ void fh_banded_free(feasthip_ctx* h) {
     if (h->band_perm) hipFree(h->band_perm);
     if (h->band_iperm) hipFree(h->band_iperm);
     h->band_perm = nullptr; h->band_iperm = nullptr;
-    h->band_plan = 0; h->band_kl = 0; h->band_ku = 0;
+    h->band_plan = 0; h->band_kl = 0; h->band_ku = 0; h->band_plan_required = 0;
     fh_mf_free(h);
 }
 
@@ -220,14 +220,23 @@ static int band_take_band_plan(feasthip_ctx* h, const std::vector<int>& perm, co
 }
 
 static int band_make_plan(feasthip_ctx* h) {
+    // feasthip_require_adjoint: only the multifrontal plan has an adjoint substitution, so a cached plan of another kind goes,
+    // together with its factors, and the plan is made again below as FH_MF=1 would make it
+    // A plan made under the requirement goes likewise once the requirement is off: the calls that never asked for an adjoint
+    // get the plan (and the bits) they would have got without it.
+    if (h->band_plan && ((h->require_adjoint && h->band_plan != 3) || (!h->require_adjoint && h->band_plan_required))) {
+        fh_banded_free(h);
+        fh_mf_free_buffers(h);
+    }
     if (h->band_plan) return 0;
+    h->band_plan_required = h->require_adjoint;
     if (h->kind != 2) { h->last_error = "banded LU needs a CSR matrix (feasthip_set_csr)"; return FEASTHIP_ERROR_FPM; }
     const int64_t N = h->csr.N;
     if ((int64_t)h->host_rowptr.size() != N + 1) { h->last_error = "banded LU: no host pattern"; return FEASTHIP_ERROR_INTERNAL; }
     int kl0 = 0, ku0 = 0;
     fh_bandwidth(N, h->host_rowptr, h->host_col, nullptr, kl0, ku0);
-    const bool force_wide = fh_knob::wband();     // read per plan: tests switch it (and it keeps the multifrontal plan out)
-    const int mf_mode = fh_knob::mf();            // 0 never, 1 always (tests), else by predicted work
+    const bool force_wide = fh_knob::wband() && !h->require_adjoint;     // read per plan: tests switch it (and it keeps the multifrontal plan out)
+    const int mf_mode = h->require_adjoint ? 1 : fh_knob::mf();          // 0 never, 1 always (tests, feasthip_require_adjoint), else by predicted work
     if (!force_wide && mf_mode != 1 && kl0 + ku0 <= FH_BAND_NARROW) {
         h->band_plan = 1; h->band_kl = kl0; h->band_ku = ku0;
         return 0;
@@ -257,6 +266,10 @@ static int band_make_plan(feasthip_ctx* h) {
                 h->last_error.clear();
             }
         }
+    }
+    if (h->require_adjoint) {
+        h->last_error = "sparse direct solver: no multifrontal plan for this pattern (a front beyond 16 384 rows), and the band LU has no adjoint substitution (feasthip_require_adjoint)";
+        return FEASTHIP_ERROR_FPM;
     }
     return band_take_band_plan(h, perm, iperm, kl0, ku0, kl1, ku1);
 }
@@ -393,6 +406,7 @@ static int band_factor_batch(feasthip_ctx* h, const std::vector<int>& which, con
         const double bound = fh_knob::mf_max_multiplier(fh_mf::max_boundary_multiplier);
         double worst = 0.0;
         bool rejected = false;
+        std::vector<double> mult_all(nf, 0.0);
         for (int q0 = 0; q0 < nf; q0 += per_call) {
             const int cnt = std::min(per_call, nf - q0);
             std::vector<int> info_part;
@@ -400,6 +414,7 @@ static int band_factor_batch(feasthip_ctx* h, const std::vector<int>& which, con
             if ((rc = fh_mf_factor(h, h->band_prec, cnt, stores.data() + q0, pvs.data() + q0, dz + q0, info_part, mult_part))) return rc;
             for (int q = 0; q < cnt; ++q) {
                 info_out[q0 + q] = info_part[q];
+                mult_all[q0 + q] = mult_part[q];
                 worst = std::max(worst, mult_part[q]);
                 rejected = rejected || info_part[q] != 0 || !(mult_part[q] <= bound);
             }
@@ -409,6 +424,14 @@ static int band_factor_batch(feasthip_ctx* h, const std::vector<int>& which, con
                     std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_factor).count(), worst,
                     rejected ? ": rejected, band LU from here" : "");
         if (!rejected) return 0;
+        if (h->require_adjoint) {
+            // no band LU fallback: it has no adjoint form.  The rejected nodes are reported (status 8 / FEASTHIP_ERROR_LAPACK).
+            for (int q = 0; q < nf; ++q)
+                if (info_out[q] == 0 && !(mult_all[q] <= bound)) info_out[q] = 1;
+            h->last_error = "multifrontal LU rejected a pivot (largest boundary multiplier " + std::to_string(worst) +
+                            "); no band LU fallback while feasthip_require_adjoint is on (the band LU has no adjoint substitution)";
+            return 0;
+        }
         if ((rc = band_fall_back(h))) return rc;
         return band_factor_batch(h, which, zlist, info_out);
     }
@@ -460,10 +483,14 @@ static int band_solve_batch(feasthip_ctx* h, int ld, int m, const std::vector<in
         const int per_call = mf_nodes_per_call(h);
         for (int q0 = 0; q0 < nf; q0 += per_call) {
             const int cnt = std::min(per_call, nf - q0);
-            if ((rc = fh_mf_solve(h, h->band_prec, cnt, stores.data() + q0, pvs.data() + q0, RHS + (size_t)q0 * rhs_stride, rhs_stride, Y + (size_t)q0 * stride, stride, ld, m))) return rc;
+            rc = h->adjoint ? fh_mf_solve_adjoint(h, h->band_prec, cnt, stores.data() + q0, pvs.data() + q0, RHS + (size_t)q0 * rhs_stride, rhs_stride, Y + (size_t)q0 * stride, stride, ld, m)
+                            : fh_mf_solve(h, h->band_prec, cnt, stores.data() + q0, pvs.data() + q0, RHS + (size_t)q0 * rhs_stride, rhs_stride, Y + (size_t)q0 * stride, stride, ld, m);
+            if (rc) return rc;
         }
         return 0;
     }
+    // (the API layer lets the adjoint switch through for the multifrontal plan only: fh_banded_adjoint_ready)
+    if (h->adjoint) { h->last_error = "internal: adjoint substitution on a band plan"; return FEASTHIP_ERROR_INTERNAL; }
     cplx** dabs; int** dpvs; int** dperms;
     if ((rc = band_pointer_arrays(h, slots, &dabs, &dpvs, &dperms))) return rc;
     if (h->band_plan == 2) {
@@ -587,6 +614,17 @@ int fh_banded_solve_single(feasthip_ctx* h, int ld, int m, cplx z, const cplx* R
     if ((rc = band_solve_batch(h, ld, m, need, RHS, 0, Y, (size_t)h->csr.N * ld))) return rc;
     *status = h->band_valid[slot] == 1 ? 0 : FEASTHIP_ERROR_LAPACK;
     return 0;
+}
+
+// The adjoint switch on a CSR handle (fh_api.hip: fh_check_adjoint): the plan is made if need be and must be the multifrontal
+// one -- the band plans have no conjugate-transposed substitution.
+int fh_banded_adjoint_ready(feasthip_ctx* h) {
+    const int rc = band_check(h);
+    if (rc) return rc;
+    if (h->band_plan == 3) return 0;
+    h->last_error = std::string("the direct plan of this matrix is the ") + (h->band_plan == 1 ? "narrow band LU (plan 1)" : "blocked band LU (plan 2)") +
+                    ", which has no adjoint substitution: declare the need with feasthip_require_adjoint before the plan is made";
+    return FEASTHIP_ERROR_FPM;
 }
 
 // real flops of ONE node's factorisation under the plan in force (band: 8 N kl (kl + ku); multifrontal: the padded fronts)

@@ -14,3 +14,5 @@ int fh_banded_solve_single(feasthip_ctx* h, int ld, int m, cplx z, const cplx* R
 void fh_banded_free(feasthip_ctx* h);
 int fh_banded_plan(feasthip_ctx* h, int* kl, int* ku, int64_t* bytes_per_node, int* blocked);
 int fh_banded_plan_flops(feasthip_ctx* h, double* flops);
+// adjoint switch on a CSR handle: 0 when the direct plan (made here if need be) is the multifrontal one, else FEASTHIP_ERROR_FPM
+int fh_banded_adjoint_ready(feasthip_ctx* h);

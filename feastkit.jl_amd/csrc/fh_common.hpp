@@ -140,6 +140,9 @@ struct feasthip_ctx {
     // problem
     int kind = 0;  // 0 none, 1 dense, 2 sparse
     fh_csr csr;
+    // conjugate transpose of `csr` (A^H, B^H on the transposed union pattern, internal numbering; rowptr / col / aval / bval only):
+    // built at the first adjoint product of a CSR problem (fh_api.hip: fh_adjoint_csr_ensure), freed with the problem
+    fh_csr csr_adj;
     fh_dense dense;
 
     // contour
@@ -147,6 +150,7 @@ struct feasthip_ctx {
     double weight_scale = 2.0;
     int real_projection = 0;
     int adjoint = 0;              // feasthip_set_adjoint: sweeps, solves, products and residuals act with the conjugate transposes
+    int require_adjoint = 0;      // feasthip_require_adjoint: the direct plan of a CSR problem must have an adjoint substitution (the multifrontal one)
     int node_first = 0, node_count = 0;
     std::vector<int> node_ids;      // local node -> contour index (set by range or list)
     std::vector<int> node_kinds;    // feasthip_set_node_solver: per CONTOUR node, 0 = the handle's solver, FEASTHIP_SOLVER_BANDED = direct; empty = none
@@ -199,6 +203,7 @@ struct feasthip_ctx {
     // band plan (fh_banded.hip): 0 not made, 1 narrow band in stored order (one-workgroup elimination), 2 blocked band LU
     // on the dense kernels in band order (band_perm[band row] = stored row, band_iperm its inverse; both on the device)
     int band_plan = 0, band_kl = 0, band_ku = 0;
+    int band_plan_required = 0;   // the plan was made while feasthip_require_adjoint was on (dropped when it is next needed with the requirement off)
     int band_prec = 64;           // element type of the cached band factors (blocked plan): 64 = complex128, 32 = complex64
     int* band_perm = nullptr;
     int* band_iperm = nullptr;

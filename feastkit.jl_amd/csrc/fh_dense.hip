@@ -1748,6 +1748,83 @@ __global__ __launch_bounds__(FH_BLOCK) void k_solve_update_adj(T* const* LUs, T*
     }
 }
 
+// Adjoint twin of k_solve_diag (no IDENT form) for the factors that keep only 32-block inverses -- most fronts of the
+// multifrontal tree: one workgroup per (column tile, matrix) keeps the SOLVE_KB x 16 slab in LDS and walks its 32-blocks in
+// the opposite order of the twin.  UPPER names the stored factor: true is U, whose conjugate transpose is LOWER triangular
+// (blocks ascending, z_i = Uinv_ii^H s_i, then s_j -= U_ij^H z_i for j > i); false is L, L^H is unit UPPER triangular
+// (descending, j < i).  Operands are read as conj(inv[col][row]) and conj(A[row * ld + col]): lane (lr, lk) takes row lr of the
+// transposed operand, i.e. stored column lr, four consecutive stored rows per k-group.  Rows and columns are bounded by the
+// pivot block (g.n), as in the twin; the same v_mfma_f64_16x16x4_f64 products.
+template <int LD, bool UPPER, typename T>
+__global__ __launch_bounds__(FH_BLOCK) void k_solve_diag_adj(T* const* LUs, T* IN, T* OUT, size_t stride, lu_geom g, int K0, int kb) {
+    const int node = blockIdx.y;
+    const T* A = LUs[node];
+    const int N = g.ld, NBND = g.n;
+    const T* invbase = A + g.inv32;
+    const T* in = IN + (size_t)node * stride;
+    T* out = OUT + (size_t)node * stride;
+    const int ta = blockIdx.x;
+    __shared__ T S[SOLVE_KB][17];
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int lr = lane & 15, lk = lane >> 4;
+    for (int e = t; e < SOLVE_KB * 16; e += FH_BLOCK) {
+        const int i = e >> 4, c = e & 15, row = K0 + i;
+        S[i][c] = (i < LU_NB * kb && row < NBND) ? in[(size_t)row * LD + 16 * ta + c] : LU_MK(0, 0);
+    }
+    __syncthreads();
+    for (int step = 0; step < kb; ++step) {
+        const int i = UPPER ? step : kb - 1 - step;
+        const int k0 = K0 + LU_NB * i;
+        const T* inv = invbase + ((size_t)(k0 / LU_NB) * 2 + (UPPER ? 1 : 0)) * LU_NB * LU_NB;
+        typename lu_el<T>::v4 re = {0, 0, 0, 0}, im = {0, 0, 0, 0};
+        if (wave < 2) {
+#pragma unroll
+            for (int kk = 0; kk < LU_NB; kk += 4) {
+                const T v = inv[(size_t)(16 * wave + lr) * LU_NB + kk + lk];
+                const T a = LU_MK(v.x, -v.y);
+                const T b = S[LU_NB * i + kk + lk][lr];
+                re = lu_el<T>::mfma(a.x, b.x, re);
+                re = lu_el<T>::mfma(-a.y, b.y, re);
+                im = lu_el<T>::mfma(a.x, b.y, im);
+                im = lu_el<T>::mfma(a.y, b.x, im);
+            }
+        }
+        __syncthreads();
+        if (wave < 2) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) S[LU_NB * i + 16 * wave + lu_el<T>::mrow(lk, r)][lr] = LU_MK(re[r], im[r]);
+        }
+        __syncthreads();
+        const int nj = UPPER ? kb - 1 - i : i;
+        for (int q = wave; q < 2 * nj; q += 4) {
+            const int j = UPPER ? i + 1 + q / 2 : q / 2;
+            const int rbase = LU_NB * j + 16 * (q & 1);
+            typename lu_el<T>::v4 ur = {0, 0, 0, 0}, ui = {0, 0, 0, 0};
+#pragma unroll
+            for (int kk = 0; kk < LU_NB; kk += 4) {
+                const int grow = K0 + rbase + lr, gcol = k0 + kk + lk;      // row / column of the TRANSPOSED operand
+                const T v = (grow < NBND && gcol < NBND) ? A[(size_t)grow * N + gcol] : LU_MK(0, 0);
+                const T a = LU_MK(v.x, -v.y);
+                const T b = S[LU_NB * i + kk + lk][lr];
+                ur = lu_el<T>::mfma(a.x, b.x, ur);
+                ur = lu_el<T>::mfma(-a.y, b.y, ur);
+                ui = lu_el<T>::mfma(a.x, b.y, ui);
+                ui = lu_el<T>::mfma(a.y, b.x, ui);
+            }
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                T& d = S[rbase + lu_el<T>::mrow(lk, r)][lr];
+                d = LU_MK(d.x - ur[r], d.y - ui[r]);
+            }
+        }
+        __syncthreads();
+    }
+    for (int e = t; e < SOLVE_KB * 16; e += FH_BLOCK) {
+        const int i = e >> 4, c = e & 15, row = K0 + i;
+        if (i < LU_NB * kb && row < NBND) out[(size_t)row * LD + 16 * ta + c] = S[i][c];
+    }
+}
+
 // Z[node][i,:] = RHS[node][i,:]  (rhs_stride = 0: one shared panel), the unpermuted start of the adjoint substitution
 __global__ __launch_bounds__(FH_BLOCK) void k_copy_panels(const cplx* __restrict__ RHS, size_t rhs_stride, cplx* __restrict__ Z,
                                                            size_t stride, size_t total) {
@@ -2889,6 +2966,29 @@ __global__ __launch_bounds__(FH_BLOCK) void k_mf_scatter(const mf_slot* slots, i
     }
 }
 
+// adjoint, last step of a front: the row permutation of its pivot block undone, X[m][p[r],:] = V[m][r,:] (p the permutation
+// k_mf_fwd_perm applies first in the forward sweep; a bijection of [0, np), so every pivot row of X is written once), and the
+// rows of the real pivots on to the caller's panel.  X keeps the un-permuted rows for the children's gather (k_mf_bwd_load).
+template <int LD, typename T>
+__global__ __launch_bounds__(FH_BLOCK) void k_mf_adj_unperm_scatter(int* const* pivs, const mf_slot* slots, int F, const T* __restrict__ V, T* __restrict__ X,
+                                                                     const int* __restrict__ perm, cplx* OUT, size_t out_stride, int n, int np) {
+    const int m = blockIdx.y, s = m % F, node = m / F;
+    const mf_slot sl = slots[s];
+    const int* pr = pivs[m] + np;
+    const T* v = V + (size_t)m * n * LD;
+    T* x = X + (size_t)m * n * LD;
+    cplx* o = OUT + (size_t)node * out_stride;
+    const size_t total = (size_t)np * LD;
+    for (size_t e = (size_t)blockIdx.x * FH_BLOCK + threadIdx.x; e < total; e += (size_t)gridDim.x * FH_BLOCK) {
+        const int r = (int)(e / LD), c = (int)(e % LD);
+        const int d = pr[r];
+        if ((unsigned)d >= (unsigned)np) continue;           // (never for a permutation: no write outside the front's panel whatever the pivots hold)
+        const T val = v[e];
+        x[(size_t)d * LD + c] = val;
+        if (d < sl.npiv) o[(size_t)perm[sl.piv0 + d] * LD + c] = cmake((double)val.x, (double)val.y);
+    }
+}
+
 // pointer arrays of one call: per group and matrix (node-major, m = q * F + slot) the work matrix, the factor store, the
 // shifted U12 view and the pivots
 template <typename T> struct mf_ptrs { T** work; T** store; T** u12; int** piv; std::vector<size_t> off; };
@@ -3180,6 +3280,118 @@ static int mf_solve_ld(feasthip_ctx* h, fh_mf_state* S, int nf, const mf_ptrs<T>
     if ((rc = mf_for_levels(h, S, false, backward_group))) return rc;
     fh_prof_end(h);
     return 0;
+}
+
+// Adjoint substitution on the same factors (two-sided FEAST on sparse input; complex128 factors).  In plan order the
+// factorisation reads  S = P_1^T L_1 ... P_k^T L_k U  (fronts leaves first; P_f the row permutation of front f's pivot block,
+// L_f the identity but for f's block column [L11; L21], U the fronts' block rows [U11 U12]), so  S^H x = b  is
+//   ascending, leaves first    U^H w = b:   z = [b1; 0] + the children's boundary rows (k_mf_fwd_load WITHOUT a pivot
+//                              permutation, k_mf_fwd_add),  w1 = U11^-H z1  ascending over the pivot blocks,  z2 -= U12^H w1
+//                              goes up to the parent
+//   descending, root first     v2 = the parent's rows (k_mf_bwd_load),  v1 = L11^-H (w1 - L21^H v2)  descending,
+//                              x1[p[i]] = v1[i]  LAST (k_mf_adj_unperm_scatter): the children gather un-permuted rows
+// Buffers: Z holds z (its boundary rows are what the parents read), Y holds w1, then [x1; v2]; v1 passes through Z's pivot rows.
+// The forward sweep's maps and batches; k_solve_diag_adj / k_solve_diag_inv_adj / k_solve_update_adj; no atomics.
+template <int LD>
+static int mf_solve_adjoint_ld(feasthip_ctx* h, fh_mf_state* S, int nf, const mf_ptrs<cplx>& ptr, const cplx* RHS, size_t rhs_stride, cplx* OUT, size_t out_stride, int m) {
+    typedef cplx T;
+    const fh_mf::plan& P = S->P;
+    const int cta = std::max(1, std::min(LD / 16, (m + 15) / 16));
+    int rc;
+    const size_t rows = P.rhs_rows * (size_t)nf;
+    T *Y, *Z;
+    if ((rc = fh_buf(h, "mf_y", rows * LD, &Y))) return rc;
+    if ((rc = fh_buf(h, "mf_z", rows * LD, &Z))) return rc;
+    fh_prof_begin(h, "mf_solve_adjoint");
+    auto diag = [&](bool upper, T** ST, T* IN, T* OUTp, size_t stride, const lu_geom& gd, int K0, int kb, int nmat, bool inv128) {
+        const dim3 grid(cta, nmat), block(FH_BLOCK);
+        if (inv128) {
+            if (upper) hipLaunchKernelGGL((k_solve_diag_inv_adj<LD, true, T>), grid, block, 0, h->stream, ST, IN, OUTp, stride, gd, K0, kb);
+            else hipLaunchKernelGGL((k_solve_diag_inv_adj<LD, false, T>), grid, block, 0, h->stream, ST, IN, OUTp, stride, gd, K0, kb);
+        } else {
+            if (upper) hipLaunchKernelGGL((k_solve_diag_adj<LD, true, T>), grid, block, 0, h->stream, ST, IN, OUTp, stride, gd, K0, kb);
+            else hipLaunchKernelGGL((k_solve_diag_adj<LD, false, T>), grid, block, 0, h->stream, ST, IN, OUTp, stride, gd, K0, kb);
+        }
+    };
+    auto ascending_group = [&](int g) -> int {                   // U^H: leaves first
+        const fh_mf::group& G = P.groups[g];
+        const int F = (int)G.fronts.size(), nmat = F * nf, n = G.n, np = G.np, nb = G.nb;
+        T* Yg = Y + G.rhs_off * (size_t)nf * LD;
+        T* Zg = Z + G.rhs_off * (size_t)nf * LD;
+        const size_t stride = (size_t)n * LD;
+        T** ST = ptr.store + ptr.off[g];
+        const unsigned gb = mf_blocks((size_t)n * LD, 4 * FH_BLOCK, 64);
+        hipLaunchKernelGGL((k_mf_fwd_load<LD, T>), dim3(gb, nmat), dim3(FH_BLOCK), 0, h->stream, RHS, rhs_stride, S->d_perm, S->d_slots + S->slot_off[g], F, Zg, n);
+        for (int side = 0; side < 2; ++side) {
+            const size_t k0 = S->kid_off[side][g], k1 = side == 0 ? S->kid_off[1][g] : S->kid_off[0][g + 1];
+            if (k1 > k0) {
+                int nbmax = 0;
+                for (int c : G.kids[side]) nbmax = std::max(nbmax, P.fronts[c].nbnd);
+                if (nbmax > 0)
+                    hipLaunchKernelGGL((k_mf_fwd_add<LD, T>), dim3(mf_blocks((size_t)nbmax * LD, 4 * FH_BLOCK, 64), (unsigned)(k1 - k0), nf), dim3(FH_BLOCK), 0, h->stream,
+                                       S->d_kids + k0, Z, Zg, S->d_rel, nf, F, n);
+            }
+        }
+        const size_t i32 = fh_mf::inv32_elems(np);
+        const lu_geom gd{n, np, (size_t)n * np, (size_t)n * np + i32};      // rows and columns of the pivot block only
+        for (int K0 = 0; K0 < np; K0 += SOLVE_KB) {
+            const int kb = std::min(SOLVE_KB / LU_NB, (np - K0) / LU_NB);
+            const int r0 = K0 + LU_NB * kb;
+            diag(true, ST, Zg, Yg, stride, gd, K0, kb, nmat, G.inv128 != 0);
+            if (r0 < np)
+                hipLaunchKernelGGL((k_solve_update_adj<LD, T>), dim3((np - r0 + 63) / 64, nmat), dim3(FH_BLOCK), 0, h->stream, ST, Zg, Yg, stride, gd, K0, LU_NB * kb, r0, np, cta);
+        }
+        if (nb > 0) {
+            // z2 -= U12^H w1: U12 through its leading-dimension-np view (stored columns np .. n are the rows of U12^H), k = np
+            const lu_geom g12{np, n, 0, 0};
+            hipLaunchKernelGGL((k_solve_update_adj<LD, T>), dim3((nb + 63) / 64, nmat), dim3(FH_BLOCK), 0, h->stream, ptr.u12 + ptr.off[g], Zg, Yg, stride, g12, 0, np, np, n, cta);
+        }
+        return 0;
+    };
+    auto descending_group = [&](int g) -> int {                  // L^H and the row permutations: root first
+        const fh_mf::group& G = P.groups[g];
+        const int F = (int)G.fronts.size(), nmat = F * nf, n = G.n, np = G.np, nb = G.nb;
+        T* Yg = Y + G.rhs_off * (size_t)nf * LD;
+        T* Zg = Z + G.rhs_off * (size_t)nf * LD;
+        const size_t stride = (size_t)n * LD;
+        T** ST = ptr.store + ptr.off[g];
+        const size_t i32 = fh_mf::inv32_elems(np);
+        const lu_geom gd{n, np, (size_t)n * np, (size_t)n * np + i32};
+        const lu_geom gu{n, n, (size_t)n * np, (size_t)n * np + i32};
+        if (nb > 0) {
+            hipLaunchKernelGGL((k_mf_bwd_load<LD, T>), dim3(mf_blocks((size_t)nb * LD, 4 * FH_BLOCK, 64), nmat), dim3(FH_BLOCK), 0, h->stream, S->d_slots + S->slot_off[g], F,
+                               Y, Yg, S->d_rel, nf, n, np);
+            // w1 -= L21^H v2: stored rows np .. n of the L block column, columns = pivot rows
+            hipLaunchKernelGGL((k_solve_update_adj<LD, T>), dim3((np + 63) / 64, nmat), dim3(FH_BLOCK), 0, h->stream, ST, Yg, Yg, stride, gu, np, nb, 0, np, cta);
+        }
+        for (int K0 = ((np - 1) / SOLVE_KB) * SOLVE_KB; K0 >= 0; K0 -= SOLVE_KB) {
+            const int kb = std::min(SOLVE_KB / LU_NB, (np - K0) / LU_NB);
+            diag(false, ST, Yg, Zg, stride, gd, K0, kb, nmat, G.inv128 != 0);
+            if (K0 > 0)
+                hipLaunchKernelGGL((k_solve_update_adj<LD, T>), dim3((K0 + 63) / 64, nmat), dim3(FH_BLOCK), 0, h->stream, ST, Yg, Zg, stride, gd, K0, LU_NB * kb, 0, K0, cta);
+        }
+        hipLaunchKernelGGL((k_mf_adj_unperm_scatter<LD, T>), dim3(mf_blocks((size_t)np * LD, 4 * FH_BLOCK, 64), nmat), dim3(FH_BLOCK), 0, h->stream, ptr.piv + ptr.off[g],
+                           S->d_slots + S->slot_off[g], F, Zg, Yg, S->d_perm, OUT, out_stride, n, np);
+        return 0;
+    };
+    if ((rc = mf_for_levels(h, S, true, ascending_group))) return rc;
+    if ((rc = mf_for_levels(h, S, false, descending_group))) return rc;
+    fh_prof_end(h);
+    return 0;
+}
+
+// OUT[q] = (z_q B - A)^-H RHS[q] with the factors of fh_mf_factor: the forward factors, complex128 only (the API layer refuses
+// complex64 factors under the adjoint switch).  Panels as for fh_mf_solve.
+int fh_mf_solve_adjoint(feasthip_ctx* h, int prec, int nf, void* const* stores, int* const* pivs, const cplx* RHS, size_t rhs_stride, cplx* OUT, size_t out_stride, int ld, int m) {
+    fh_mf_state* S = (fh_mf_state*)h->mf;
+    if (!S) { h->last_error = "multifrontal LU: no plan"; return FEASTHIP_ERROR_INTERNAL; }
+    if (prec != 64) { h->last_error = "multifrontal LU: the adjoint substitution needs complex128 factors"; return FEASTHIP_ERROR_FPM; }
+    mf_ptrs<cplx> ptr;
+    int rc;
+    if ((rc = mf_pointer_arrays<cplx>(h, *S, nf, stores, pivs, nullptr, false, ptr))) return rc;
+    if (ld == 16) return mf_solve_adjoint_ld<16>(h, S, nf, ptr, RHS, rhs_stride, OUT, out_stride, m);
+    if (ld == 32) return mf_solve_adjoint_ld<32>(h, S, nf, ptr, RHS, rhs_stride, OUT, out_stride, m);
+    return mf_solve_adjoint_ld<64>(h, S, nf, ptr, RHS, rhs_stride, OUT, out_stride, m);
 }
 
 // OUT[q] = (z_q B - A)^-1 RHS[q] with the factors of fh_mf_factor.  Panels row-major N x ld (fp64 in and out: complex64 factors narrow

@@ -56,3 +56,5 @@ size_t fh_mf_work_bytes(feasthip_ctx* h, int prec);
 int fh_mf_factor(feasthip_ctx* h, int prec, int nf, void* const* stores, int* const* pivs, const cplx* dz, std::vector<int>& info_out,
                  std::vector<double>& multiplier_out);
 int fh_mf_solve(feasthip_ctx* h, int prec, int nf, void* const* stores, int* const* pivs, const cplx* RHS, size_t rhs_stride, cplx* OUT, size_t out_stride, int ld, int m);
+// (z_q B - A)^-H RHS[q] on the same factors (h->adjoint; complex128 factors only): the conjugate-transposed walk through the tree
+int fh_mf_solve_adjoint(feasthip_ctx* h, int prec, int nf, void* const* stores, int* const* pivs, const cplx* RHS, size_t rhs_stride, cplx* OUT, size_t out_stride, int ld, int m);

@@ -361,3 +361,32 @@ static int fh_prepare_csr(int64_t N, int index_base, int storage, int64_t nnzA, 
     }
     return 0;
 }
+
+// Conjugate transpose of the union-pattern set (the adjoint products of the two-sided solver: B^H Q, A^H X).  Input: the
+// set as it is stored (rowptr / col in the internal numbering, A and B values on the one pattern; bv null: B = I).  Output: the
+// same for A^H and B^H on the transposed pattern.  A stable counting sort over the stored rows in ascending order: entry k of
+// stored row i lands in transposed row col[k], behind every entry of a smaller stored row -- so a transposed row lists its
+// columns in ascending order (equal columns, which the ingest has already summed away, would keep their stored order), whatever
+// the order inside the stored rows.  That fixed order makes the products on the set bitwise reproducible.  Empty rows and
+// empty columns are fine; the complex overload of fh_ing_conj comes from the includer, like fh_ing_zero / fh_ing_add.
+static inline double fh_ing_conj(double a) { return a; }
+
+template <typename VT>
+static inline void fh_adjoint_csr(int64_t N, const std::vector<int>& rowptr, const std::vector<int>& col, const VT* av, const VT* bv,
+                                  std::vector<int>& rowptr_t, std::vector<int>& col_t, std::vector<VT>& av_t, std::vector<VT>& bv_t) {
+    const size_t nnz = N > 0 ? (size_t)rowptr[N] : 0;
+    rowptr_t.assign(N + 1, 0);
+    col_t.assign(nnz, 0);
+    av_t.assign(nnz, fh_ing_zero(VT()));
+    bv_t.assign(bv ? nnz : 0, fh_ing_zero(VT()));
+    for (size_t k = 0; k < nnz; ++k) rowptr_t[col[k] + 1]++;
+    for (int64_t i = 0; i < N; ++i) rowptr_t[i + 1] += rowptr_t[i];
+    std::vector<int> fill(rowptr_t.begin(), rowptr_t.begin() + N);
+    for (int64_t i = 0; i < N; ++i)
+        for (int k = rowptr[i]; k < rowptr[i + 1]; ++k) {
+            const int o = fill[col[k]]++;
+            col_t[o] = (int)i;
+            av_t[o] = fh_ing_conj(av[k]);
+            if (bv) bv_t[o] = fh_ing_conj(bv[k]);
+        }
+}

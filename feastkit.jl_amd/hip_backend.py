@@ -1014,14 +1014,16 @@ def feast_hip_general(engine, A, B, Emid, r, M0, fpm, *, solver="direct", solver
 
 
 TWO_SIDED_SOLVERS = ("direct", "lu")
+TWO_SIDED_SPARSE_SOLVERS = ("direct", "lu", "sparse_direct", "banded")
 
 
 def check_two_sided(sparse, solver, inner_precision=64, group=None, direct_nodes=None):
-    """Host-only validation of ``feast_general(..., two_sided=True)`` (no device work): the adjoint sweep exists for dense
-    input with the direct solver in fp64 on one rank."""
-    if sparse:
-        raise ValueError("two_sided needs dense input (no adjoint substitution through the sparse direct factors yet)")
-    if solver not in TWO_SIDED_SOLVERS:
+    """Host-only validation of ``feast_general(..., two_sided=True)`` (no device work): the adjoint sweep exists for the
+    direct solvers in fp64 on one rank -- the dense LU, and for sparse input the sparse direct solver (its multifrontal
+    plan; there is no Krylov solver on the conjugate transpose)."""
+    if sparse and solver not in TWO_SIDED_SPARSE_SOLVERS:
+        raise ValueError(f"two_sided on sparse input needs a direct solver (solver='direct' or 'sparse_direct'), not '{solver}'")
+    if not sparse and solver not in TWO_SIDED_SOLVERS:
         raise ValueError(f"two_sided needs the dense direct solver (solver='direct'), not '{solver}'")
     if inner_precision == 32:
         raise ValueError("two_sided does not support inner_precision=32 (the adjoint substitution runs on complex128 factors)")
@@ -1033,7 +1035,9 @@ def check_two_sided(sparse, solver, inner_precision=64, group=None, direct_nodes
 
 def feast_hip_general_two_sided(engine, A, B, Emid, r, M0, fpm, *, solver="direct", Q0=None, QL0=None, seed=20260515,
                                 contour=None, eps_floor=0.0):
-    """Two-sided FEAST on a dense pencil: right and left subspaces from the same cached LU factors, oblique projection.
+    """Two-sided FEAST on a dense pencil, or on a sparse one under the sparse direct solver (``solver="banded"``: the
+    multifrontal plan, declared with engine.require_adjoint): right and left subspaces from the same cached LU factors,
+    oblique projection.
 
         P_R = sum_e w_e S_e^-1 B Q_R                (forward sweep; factors cached per node)
         P_L = sum_e conj(w_e) S_e^-H B^H Q_L        (adjoint sweep: conjugate-transposed substitution, no factorisation)
@@ -1049,11 +1053,21 @@ def feast_hip_general_two_sided(engine, A, B, Emid, r, M0, fpm, *, solver="direc
     info = _check_circle_input(N, M0, r)
     if info:
         return _empty_result(N, info, complex_lambda=True)
-    check_two_sided(False, solver)
+    import scipy.sparse as _sp
+    sparse = _sp.issparse(A)
+    check_two_sided(sparse, solver)
+    if sparse and solver != "banded":
+        raise ValueError("two_sided on sparse input runs on the sparse direct solver (solver='banded')")
     Ac, Bc = _complex_pencil(A, B)
     Zne, Wne = feast_gcontour(Emid, r, fpm) if contour is None else contour
-    world, count = _setup_sweep(engine, None, Ac, Bc, Zne, Wne, 1.0, False)
-    _configure_solver(engine, solver, fpm, 0.0, 500, 30, factor_precision=64)
+    engine.set_adjoint(False)
+    engine.require_adjoint(sparse)              # before the problem's direct plan is made or queried
+    try:
+        world, count = _setup_sweep(engine, None, Ac, Bc, Zne, Wne, 1.0, False)
+        _configure_solver(engine, solver, fpm, 0.0, 500, 30, factor_precision=64)
+    except BaseException:
+        engine.require_adjoint(False)
+        raise
     dQR = engine.upload(seeded_subspace(N, M0, seed) if Q0 is None else np.asarray(Q0, dtype=np.complex128))
     dQL = engine.upload(seeded_subspace(N, M0, seed + 1, complex_values=True) if QL0 is None
                         else np.asarray(QL0, dtype=np.complex128))
@@ -1065,8 +1079,12 @@ def feast_hip_general_two_sided(engine, A, B, Emid, r, M0, fpm, *, solver="direc
           "seconds": {"forward_sweep": 0.0, "adjoint_sweep": 0.0, "rayleigh_ritz": 0.0}}
     stats["two_sided"] = ts
     tick = time.perf_counter
-    engine.set_adjoint(False)
     try:
+        if sparse:
+            ts["direct_plan"] = ("multifrontal LU on a nested-dissection tree" if engine.band_plan()[3] == 2
+                                 else "band LU after reverse Cuthill-McKee")
+        else:
+            ts["direct_plan"] = "dense LU"
         with small_lapack():
             while True:
                 t0 = tick()
@@ -1110,6 +1128,7 @@ def feast_hip_general_two_sided(engine, A, B, Emid, r, M0, fpm, *, solver="direc
                 dQR, dQL = dXR, dXL
     finally:
         engine.set_adjoint(False)
+        engine.require_adjoint(False)
     order = sorted(range(M), key=lambda i: abs(lam[i]) ** 2)             # feast_sort_general!
     X = engine.download(dXR, M0)[:, :M][:, order]
     Y = engine.download(dXL, M0)[:, :M][:, order]
