@@ -130,11 +130,26 @@ __global__ __launch_bounds__(FH_BLOCK) void k_dense_op(fh_dense_op_args a) {
 // segment per 16 lanes).  Blocks are numbered so that the 8 consecutive ids that land on the 8 XCDs
 // carry 8 different row tiles and the blocks of one XCD walk the nodes of the same row tile, which
 // keeps the tile of A in that XCD's L2 while every node consumes it.
+//
+// ADJ (two-sided FEAST):  Y = (cb B^H + ca A^H) X.  Same tiling, LDS staging of the panel rows and block numbering; only
+// the matrix operand differs (op_at): lane (lr, lk) feeds op^H(irow, j) = conj(M[j + irow N]), i.e. it walks column irow
+// of the stored matrix, so the 16 lanes of a k-group read 16 columns (stride N) and the four k-groups four consecutive rows
+// -- 64 B (complex) or 32 B (real) contiguous per column and load, every 128 B line shared by the loads of two (four)
+// consecutive k-steps of the same wave.  The operand is read transposed straight from global memory; staging it through
+// LDS is not built.
 typedef double dop_v4d __attribute__((ext_vector_type(4)));
 #define DOP_KC 16
 #define DOP_PAD 16
 
-template <typename VT, int LD, bool BIDENT, int TRB>
+// Matrix operand of the MFMA kernels of this file: the stored element that (row, col) of op(M) reads, M column-major with
+// leading dimension ld and op(M) = M or, under ADJ, its (conjugate) transpose.  A complex ADJ kernel conjugates what it has
+// loaded, after its bounds select.  Bounds are the caller's.
+template <bool ADJ, typename T>
+__device__ inline const T& op_at(const T* M, int ld, int row, int col) {
+    return ADJ ? M[(size_t)row * ld + col] : M[(size_t)col * ld + row];
+}
+
+template <typename VT, int LD, bool BIDENT, int TRB, bool ADJ>
 __global__ __launch_bounds__(FH_BLOCK) void k_dense_op_mfma(fh_dense_op_args a, int row_tiles) {
     constexpr int KC = DOP_KC, CT = LD / 16, NCG = 4 / TRB, TPW = CT / NCG, XPT = KC * LD / FH_BLOCK;
     constexpr bool CPLX = sizeof(VT) == sizeof(cplx);
@@ -151,7 +166,7 @@ __global__ __launch_bounds__(FH_BLOCK) void k_dense_op_mfma(fh_dense_op_args a, 
     const int lr = lane & 15, lk = lane >> 4;
     const int band = w % TRB, cg = w / TRB;
     const int i0 = rt * (16 * TRB);
-    const int irow = i0 + 16 * band + lr;          // matrix row this lane feeds as MFMA A operand
+    const int irow = i0 + 16 * band + lr;          // row of op(M) this lane feeds as MFMA A operand
     const cplx* X = a.X + (size_t)node * a.x_node_stride;
     cplx* Y = a.Y + (size_t)node * a.y_node_stride;
     const VT* A = (const VT*)a.A;
@@ -175,12 +190,12 @@ __global__ __launch_bounds__(FH_BLOCK) void k_dense_op_mfma(fh_dense_op_args a, 
             const int j = j0 + 4 * s + lk;
             const bool ok = irow < N && j < N;
             if constexpr (CPLX) {
-                cplx v = ok ? A[(size_t)j * N + irow] : cmake(0, 0);
-                are[s] = v.x; aim[s] = v.y;
-                if (!BIDENT) { cplx u = ok ? B[(size_t)j * N + irow] : cmake(0, 0); bre[s] = u.x; bim[s] = u.y; }
+                cplx v = ok ? op_at<ADJ>(A, N, irow, j) : cmake(0, 0);
+                are[s] = v.x; aim[s] = ADJ ? -v.y : v.y;
+                if (!BIDENT) { cplx u = ok ? op_at<ADJ>(B, N, irow, j) : cmake(0, 0); bre[s] = u.x; bim[s] = ADJ ? -u.y : u.y; }
             } else {
-                are[s] = ok ? A[(size_t)j * N + irow] : 0.0;
-                if (!BIDENT) bre[s] = ok ? B[(size_t)j * N + irow] : 0.0;
+                are[s] = ok ? op_at<ADJ>(A, N, irow, j) : 0.0;
+                if (!BIDENT) bre[s] = ok ? op_at<ADJ>(B, N, irow, j) : 0.0;
             }
         }
     };
@@ -246,185 +261,44 @@ __global__ __launch_bounds__(FH_BLOCK) void k_dense_op_mfma(fh_dense_op_args a, 
     }
 }
 
-template <typename VT, int LD, int TRB>
+template <typename VT, int LD, int TRB, bool ADJ>
 static void launch_dense_op_mfma(const fh_dense_op_args& a, hipStream_t st) {
     const int row_tiles = (a.N + 16 * TRB - 1) / (16 * TRB);
     const int groups = (row_tiles + 7) / 8;
     dim3 grid(8 * a.nodes * groups), block(FH_BLOCK);
-    if (a.B == nullptr) hipLaunchKernelGGL((k_dense_op_mfma<VT, LD, true, TRB>), grid, block, 0, st, a, row_tiles);
-    else hipLaunchKernelGGL((k_dense_op_mfma<VT, LD, false, TRB>), grid, block, 0, st, a, row_tiles);
+    if (a.B == nullptr) hipLaunchKernelGGL((k_dense_op_mfma<VT, LD, true, TRB, ADJ>), grid, block, 0, st, a, row_tiles);
+    else hipLaunchKernelGGL((k_dense_op_mfma<VT, LD, false, TRB, ADJ>), grid, block, 0, st, a, row_tiles);
 }
 
-template <typename VT, int LD>
+// The adjoint form exists as the MFMA kernel only: plain products (dot_mode 0), the caller has checked that.
+template <typename VT, int LD, bool ADJ>
 static void launch_dense_op_ld(const fh_dense_op_args& a, int nblk, hipStream_t st) {
-    if (a.dot_mode == 0 && !fh_knob::dense_op_valu()) {
+    if (ADJ || (a.dot_mode == 0 && !fh_knob::dense_op_valu())) {
         // 32-row tiles when 64-row tiles would leave CUs idle (single-node calls on mid-size matrices)
         if constexpr (LD >= 32) {
-            if ((long)a.nodes * ((a.N + 63) / 64) < 256) { launch_dense_op_mfma<VT, LD, 2>(a, st); return; }
+            if ((long)a.nodes * ((a.N + 63) / 64) < 256) { launch_dense_op_mfma<VT, LD, 2, ADJ>(a, st); return; }
         }
-        launch_dense_op_mfma<VT, LD, 4>(a, st);
+        launch_dense_op_mfma<VT, LD, 4, ADJ>(a, st);
         return;
     }
     dim3 grid(nblk, a.nodes), block(FH_BLOCK);
     if (a.B == nullptr) hipLaunchKernelGGL((k_dense_op<VT, LD, true>), grid, block, 0, st, a);
     else hipLaunchKernelGGL((k_dense_op<VT, LD, false>), grid, block, 0, st, a);
 }
-void fh_launch_dense_op(const fh_dense_op_args& a, int ld, int nblk, hipStream_t st) {
+template <bool ADJ>
+static void launch_dense_op(const fh_dense_op_args& a, int ld, int nblk, hipStream_t st) {
     if (a.is_complex) {
-        if (ld == 16) launch_dense_op_ld<cplx, 16>(a, nblk, st);
-        else if (ld == 32) launch_dense_op_ld<cplx, 32>(a, nblk, st);
-        else launch_dense_op_ld<cplx, 64>(a, nblk, st);
+        if (ld == 16) launch_dense_op_ld<cplx, 16, ADJ>(a, nblk, st);
+        else if (ld == 32) launch_dense_op_ld<cplx, 32, ADJ>(a, nblk, st);
+        else launch_dense_op_ld<cplx, 64, ADJ>(a, nblk, st);
     } else {
-        if (ld == 16) launch_dense_op_ld<double, 16>(a, nblk, st);
-        else if (ld == 32) launch_dense_op_ld<double, 32>(a, nblk, st);
-        else launch_dense_op_ld<double, 64>(a, nblk, st);
+        if (ld == 16) launch_dense_op_ld<double, 16, ADJ>(a, nblk, st);
+        else if (ld == 32) launch_dense_op_ld<double, 32, ADJ>(a, nblk, st);
+        else launch_dense_op_ld<double, 64, ADJ>(a, nblk, st);
     }
 }
-
-// Adjoint form of k_dense_op_mfma (two-sided FEAST):  Y = (cb B^H + ca A^H) X.  Same tiling, LDS staging of the panel rows
-// and block numbering; only the matrix operand differs: lane (lr, lk) feeds op^H(irow, j) = conj(M[j + irow N]), i.e. it
-// walks column irow of the stored matrix, so the 16 lanes of a k-group read 16 columns (stride N) and the four k-groups four
-// consecutive rows -- 64 B (complex) or 32 B (real) contiguous per column and load, every 128 B line shared by the loads of two
-// (four) consecutive k-steps of the same wave.  The operand is read transposed straight from global memory; staging it
-// through LDS is not built.
-template <typename VT, int LD, bool BIDENT, int TRB>
-__global__ __launch_bounds__(FH_BLOCK) void k_dense_op_mfma_adj(fh_dense_op_args a, int row_tiles) {
-    constexpr int KC = DOP_KC, CT = LD / 16, NCG = 4 / TRB, TPW = CT / NCG, XPT = KC * LD / FH_BLOCK;
-    constexpr bool CPLX = sizeof(VT) == sizeof(cplx);
-    static_assert(TPW >= 1 && XPT >= 1, "tile split");
-    __shared__ double Xre[KC][LD + DOP_PAD];
-    __shared__ double Xim[KC][LD + DOP_PAD];
-    const int b = blockIdx.x;
-    const int rt = (b & 7) + 8 * ((b >> 3) / a.nodes);
-    const int node = (b >> 3) % a.nodes;
-    if (rt >= row_tiles) return;
-    if (a.node_active && a.node_active[node] == 0) return;
-    const int N = a.N;
-    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
-    const int lr = lane & 15, lk = lane >> 4;
-    const int band = w % TRB, cg = w / TRB;
-    const int i0 = rt * (16 * TRB);
-    const int irow = i0 + 16 * band + lr;          // row of op^H = column of the stored matrix
-    const cplx* X = a.X + (size_t)node * a.x_node_stride;
-    cplx* Y = a.Y + (size_t)node * a.y_node_stride;
-    const VT* A = (const VT*)a.A;
-    const VT* B = (const VT*)a.B;
-    dop_v4d aR[TPW], aI[TPW], bR[BIDENT ? 1 : TPW], bI[BIDENT ? 1 : TPW];
-#pragma unroll
-    for (int q = 0; q < TPW; ++q) {
-        aR[q] = dop_v4d{0, 0, 0, 0}; aI[q] = dop_v4d{0, 0, 0, 0};
-        if (!BIDENT) { bR[q] = dop_v4d{0, 0, 0, 0}; bI[q] = dop_v4d{0, 0, 0, 0}; }
-    }
-    cplx xn[XPT];
-    double are[KC / 4], aim[KC / 4], bre[KC / 4], bim[KC / 4];
-    auto load_chunk = [&](int j0) {
-#pragma unroll
-        for (int q = 0; q < XPT; ++q) {
-            const int e = t + q * FH_BLOCK, jj = e / LD, c = e % LD;
-            xn[q] = (j0 + jj < N) ? X[(size_t)(j0 + jj) * LD + c] : cmake(0, 0);
-        }
-#pragma unroll
-        for (int s = 0; s < KC / 4; ++s) {
-            const int j = j0 + 4 * s + lk;
-            const bool ok = irow < N && j < N;
-            if constexpr (CPLX) {
-                cplx v = ok ? A[(size_t)irow * N + j] : cmake(0, 0);
-                are[s] = v.x; aim[s] = -v.y;
-                if (!BIDENT) { cplx u = ok ? B[(size_t)irow * N + j] : cmake(0, 0); bre[s] = u.x; bim[s] = -u.y; }
-            } else {
-                are[s] = ok ? A[(size_t)irow * N + j] : 0.0;
-                if (!BIDENT) bre[s] = ok ? B[(size_t)irow * N + j] : 0.0;
-            }
-        }
-    };
-    load_chunk(0);
-    for (int j0 = 0; j0 < N; j0 += KC) {
-#pragma unroll
-        for (int q = 0; q < XPT; ++q) {
-            const int e = t + q * FH_BLOCK, jj = e / LD, c = e % LD;
-            Xre[jj][c] = xn[q].x; Xim[jj][c] = xn[q].y;
-        }
-        double cre[KC / 4], cim[KC / 4], dre[KC / 4], dim_[KC / 4];
-#pragma unroll
-        for (int s = 0; s < KC / 4; ++s) { cre[s] = are[s]; cim[s] = aim[s]; dre[s] = bre[s]; dim_[s] = bim[s]; }
-        __syncthreads();
-        if (j0 + KC < N) load_chunk(j0 + KC);
-#pragma unroll
-        for (int s = 0; s < KC / 4; ++s) {
-            double xr[TPW], xi[TPW];
-#pragma unroll
-            for (int q = 0; q < TPW; ++q) {
-                xr[q] = Xre[4 * s + lk][16 * (cg * TPW + q) + lr];
-                xi[q] = Xim[4 * s + lk][16 * (cg * TPW + q) + lr];
-            }
-#pragma unroll
-            for (int q = 0; q < TPW; ++q) aR[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(cre[s], xr[q], aR[q], 0, 0, 0);
-#pragma unroll
-            for (int q = 0; q < TPW; ++q) aI[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(cre[s], xi[q], aI[q], 0, 0, 0);
-            if constexpr (CPLX) {
-#pragma unroll
-                for (int q = 0; q < TPW; ++q) aR[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(-cim[s], xi[q], aR[q], 0, 0, 0);
-#pragma unroll
-                for (int q = 0; q < TPW; ++q) aI[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(cim[s], xr[q], aI[q], 0, 0, 0);
-            }
-            if constexpr (!BIDENT) {
-#pragma unroll
-                for (int q = 0; q < TPW; ++q) bR[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(dre[s], xr[q], bR[q], 0, 0, 0);
-#pragma unroll
-                for (int q = 0; q < TPW; ++q) bI[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(dre[s], xi[q], bI[q], 0, 0, 0);
-                if constexpr (CPLX) {
-#pragma unroll
-                    for (int q = 0; q < TPW; ++q) bR[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(-dim_[s], xi[q], bR[q], 0, 0, 0);
-#pragma unroll
-                    for (int q = 0; q < TPW; ++q) bI[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(dim_[s], xr[q], bI[q], 0, 0, 0);
-                }
-            }
-        }
-        __syncthreads();
-    }
-#pragma unroll
-    for (int q = 0; q < TPW; ++q) {
-        const int c = 16 * (cg * TPW + q) + lr;
-        const cplx ca = a.coefA[node * LD + c], cb = a.coefB[node * LD + c];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int i = i0 + 16 * band + lk + 4 * r;
-            if (i >= N) continue;
-            cplx y = cmul(ca, cmake(aR[q][r], aI[q][r]));
-            if (BIDENT) cfma(y, cb, X[(size_t)i * LD + c]); else cfma(y, cb, cmake(bR[q][r], bI[q][r]));
-            if (a.Bvec) y = csub(a.Bvec[(size_t)node * a.b_node_stride + (size_t)i * LD + c], y);
-            Y[(size_t)i * LD + c] = y;
-        }
-    }
-}
-
-template <typename VT, int LD, int TRB>
-static void launch_dense_op_mfma_adj(const fh_dense_op_args& a, hipStream_t st) {
-    const int row_tiles = (a.N + 16 * TRB - 1) / (16 * TRB);
-    const int groups = (row_tiles + 7) / 8;
-    dim3 grid(8 * a.nodes * groups), block(FH_BLOCK);
-    if (a.B == nullptr) hipLaunchKernelGGL((k_dense_op_mfma_adj<VT, LD, true, TRB>), grid, block, 0, st, a, row_tiles);
-    else hipLaunchKernelGGL((k_dense_op_mfma_adj<VT, LD, false, TRB>), grid, block, 0, st, a, row_tiles);
-}
-template <typename VT, int LD>
-static void launch_dense_op_adj_ld(const fh_dense_op_args& a, hipStream_t st) {
-    if constexpr (LD >= 32) {
-        if ((long)a.nodes * ((a.N + 63) / 64) < 256) { launch_dense_op_mfma_adj<VT, LD, 2>(a, st); return; }
-    }
-    launch_dense_op_mfma_adj<VT, LD, 4>(a, st);
-}
-// plain products only (dot_mode 0); the caller has checked that
-void fh_launch_dense_op_adjoint(const fh_dense_op_args& a, int ld, hipStream_t st) {
-    if (a.is_complex) {
-        if (ld == 16) launch_dense_op_adj_ld<cplx, 16>(a, st);
-        else if (ld == 32) launch_dense_op_adj_ld<cplx, 32>(a, st);
-        else launch_dense_op_adj_ld<cplx, 64>(a, st);
-    } else {
-        if (ld == 16) launch_dense_op_adj_ld<double, 16>(a, st);
-        else if (ld == 32) launch_dense_op_adj_ld<double, 32>(a, st);
-        else launch_dense_op_adj_ld<double, 64>(a, st);
-    }
-}
+void fh_launch_dense_op(const fh_dense_op_args& a, int ld, int nblk, hipStream_t st) { launch_dense_op<false>(a, ld, nblk, st); }
+void fh_launch_dense_op_adjoint(const fh_dense_op_args& a, int ld, hipStream_t st) { launch_dense_op<true>(a, ld, 0, st); }
 
 __global__ __launch_bounds__(FH_BLOCK) void k_axpy_cols(cplx* __restrict__ R, const cplx* __restrict__ X,
                                                          const cplx* __restrict__ lam, size_t total, int ld,
@@ -463,6 +337,9 @@ template <> struct lu_el<cplxf> {
     __device__ static v4 mfma(float a, float b, v4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
 };
 #define LU_MK(a, b) lu_el<T>::mk((a), (b))
+// the conjugation that follows op_at<true> in the adjoint substitution (below)
+template <typename T>
+__device__ inline T lu_conj(T v) { return LU_MK(v.x, -v.y); }
 // Geometry of a factor the LU / substitution kernels work on.  Dense factor: ld = n = N, the inverted diagonal blocks sit
 // behind the N x N matrix.  Band factor (fh_wband_*, below): the SAME kernels run on general band storage viewed as a
 // column-major matrix with leading dimension ldab - 1 (element (i, j) of the band at base + i + j (ldab - 1)), n = matrix
@@ -1324,13 +1201,20 @@ __global__ __launch_bounds__(FH_BLOCK) void k_solve_step(T* const* LUs, T* IN, T
 //                   16-deep chunks (split re/im, padded, register prefetch), factor operands from global.
 // Against the 32-wide steps this rewrites the right-hand-side rows 4x less often and needs 2 launches per
 // 128 columns instead of 4.
+//
+// ADJ: the adjoint substitution on the same factors (ZGETRS 'C', two-sided FEAST):  with P S = L U,  S^H y = b  is
+//   U^H w = b   ascending over the 128-blocks   (U^H is lower triangular),
+//   L^H v = w   descending                      (L^H is unit upper triangular),
+//   y[perm[i]] = v[i].
+// UPPER keeps naming the STORED factor / inverse that is addressed; the triangle the kernels see is UPPER != ADJ, and every
+// factor operand (op_at<ADJ>, lu_conj) is read as conj(M[col][row]): lane (lr, lk) takes row lr of the transposed operand,
+// i.e. stored column lr, four consecutive stored rows per k-group (64 B contiguous per lane group of four k-groups).  The
+// same MFMA products, bounds and launch shapes in both directions.  The reads of the block inverses spell their index out
+// (`inv[ADJ ? ... : ...]`) instead of going through op_at: their minor index is a sum that is widened term by term, and the
+// compiler schedules the widened sum differently.
 #define SOLVE_KB 128
 #define SOLVE_KC 16
 
-// IDENT: the right-hand side is the identity (grid = 8 column tiles x 128-blocks x nodes) and the result, the
-// inverse of the 128 x 128 diagonal block, goes behind the 32-block inverses (column-major, identity-padded):
-//   inv128 = LU + N*N + nblk32*2*32*32 + (2*block128 + upper)*128*128.
-// With it the per-step diagonal solve of the substitution is one product (k_solve_diag_inv).
 template <typename T>
 __host__ __device__ inline size_t lu_inv128_offset(int N) {
     return (size_t)N * N + (size_t)((N + LU_NB - 1) / LU_NB) * 2 * LU_NB * LU_NB;
@@ -1339,8 +1223,19 @@ __host__ __device__ inline size_t lu_inv128_offset(int N) {
 template <typename T>
 static inline lu_geom lu_dense_geom(int N) { return lu_geom{N, N, (size_t)N * N, lu_inv128_offset<T>(N)}; }
 
-template <int LD, bool UPPER, bool IDENT, typename T>
+// IDENT: the right-hand side is the identity (grid = 8 column tiles x 128-blocks x nodes) and the result, the
+// inverse of the 128 x 128 diagonal block, goes behind the 32-block inverses (column-major, identity-padded):
+//   inv128 = LU + N*N + nblk32*2*32*32 + (2*block128 + upper)*128*128.
+// With it the per-step diagonal solve of the substitution is one product (k_solve_diag_inv).
+//
+// ADJ serves the factors that keep only 32-block inverses -- most fronts of the multifrontal tree -- and walks the slab's
+// 32-blocks in the opposite order: stored U, whose conjugate transpose is LOWER triangular, ascending (z_i = Uinv_ii^H s_i,
+// then s_j -= U_ij^H z_i for j > i); stored L, L^H unit UPPER triangular, descending (j < i).  Rows and columns are bounded by
+// the pivot block (g.n) either way.
+template <int LD, bool UPPER, bool IDENT, bool ADJ, typename T>
 __global__ __launch_bounds__(FH_BLOCK) void k_solve_diag(T* const* LUs, T* IN, T* OUT, size_t stride, lu_geom g, int K0, int kb) {
+    static_assert(!(IDENT && ADJ), "the identity form (block inverses) has no adjoint use");
+    constexpr bool UP = UPPER != ADJ;            // triangle of op(factor): blocks are walked descending exactly when it is upper
     const int node = IDENT ? blockIdx.z : blockIdx.y;
     const T* A = LUs[node];
     const int N = g.ld, NBND = g.n;
@@ -1359,14 +1254,15 @@ __global__ __launch_bounds__(FH_BLOCK) void k_solve_diag(T* const* LUs, T* IN, T
     }
     __syncthreads();
     for (int step = 0; step < kb; ++step) {
-        const int i = UPPER ? kb - 1 - step : step;
+        const int i = UP ? kb - 1 - step : step;
         const int k0 = K0 + LU_NB * i;
         const T* inv = invbase + ((size_t)(k0 / LU_NB) * 2 + (UPPER ? 1 : 0)) * LU_NB * LU_NB;
         typename lu_el<T>::v4 re = {0, 0, 0, 0}, im = {0, 0, 0, 0};
         if (wave < 2) {
 #pragma unroll
             for (int kk = 0; kk < LU_NB; kk += 4) {
-                const T a = inv[(size_t)(kk + lk) * LU_NB + 16 * wave + lr];
+                T a = inv[ADJ ? (size_t)(16 * wave + lr) * LU_NB + kk + lk : (size_t)(kk + lk) * LU_NB + 16 * wave + lr];
+                if constexpr (ADJ) a = lu_conj(a);
                 const T b = S[LU_NB * i + kk + lk][lr];
                 re = lu_el<T>::mfma(a.x, b.x, re);
                 re = lu_el<T>::mfma(-a.y, b.y, re);
@@ -1380,15 +1276,16 @@ __global__ __launch_bounds__(FH_BLOCK) void k_solve_diag(T* const* LUs, T* IN, T
             for (int r = 0; r < 4; ++r) S[LU_NB * i + 16 * wave + lu_el<T>::mrow(lk, r)][lr] = LU_MK(re[r], im[r]);
         }
         __syncthreads();
-        const int nj = UPPER ? i : kb - 1 - i;
+        const int nj = UP ? i : kb - 1 - i;
         for (int q = wave; q < 2 * nj; q += 4) {
-            const int j = UPPER ? q / 2 : i + 1 + q / 2;
+            const int j = UP ? q / 2 : i + 1 + q / 2;
             const int rbase = LU_NB * j + 16 * (q & 1);
             typename lu_el<T>::v4 ur = {0, 0, 0, 0}, ui = {0, 0, 0, 0};
 #pragma unroll
             for (int kk = 0; kk < LU_NB; kk += 4) {
-                const int grow = K0 + rbase + lr, gcol = k0 + kk + lk;
-                const T a = (grow < NBND && gcol < NBND) ? A[(size_t)gcol * N + grow] : LU_MK(0, 0);
+                const int grow = K0 + rbase + lr, gcol = k0 + kk + lk;      // row / column of op(factor)
+                T a = (grow < NBND && gcol < NBND) ? op_at<ADJ>(A, N, grow, gcol) : LU_MK(0, 0);
+                if constexpr (ADJ) a = lu_conj(a);
                 const T b = S[LU_NB * i + kk + lk][lr];
                 ur = lu_el<T>::mfma(a.x, b.x, ur);
                 ur = lu_el<T>::mfma(-a.y, b.y, ur);
@@ -1421,9 +1318,11 @@ __global__ __launch_bounds__(FH_BLOCK) void k_solve_diag(T* const* LUs, T* IN, T
 // contraction of output tile ti (lower: 16-blocks 0..ti; upper: ti..7); wave w takes the tiles w and 7 - w, nine
 // 16-blocks together for every wave, and issues all nine operand loads before the slab is even in LDS: the
 // kernel sits on the critical path of the substitution and is pure latency.
-template <int LD, bool UPPER, typename T>
+// ADJ: the product with the conjugate transpose of the stored inverse, whose triangle is the other one.
+template <int LD, bool UPPER, bool ADJ, typename T>
 __global__ __launch_bounds__(FH_BLOCK) void k_solve_diag_inv(T* const* LUs, T* IN, T* OUT, size_t stride, lu_geom g, int K0, int kb) {
     constexpr int NT = SOLVE_KB / 16;
+    constexpr bool UP = UPPER != ADJ;            // triangle of op(inverse); UPPER names the stored inverse that is addressed
     const T* inv = LUs[blockIdx.y] + g.inv128 + ((size_t)(K0 / SOLVE_KB) * 2 + (UPPER ? 1 : 0)) * SOLVE_KB * SOLVE_KB;
     const T* in = IN + (size_t)blockIdx.y * stride;
     T* out = OUT + (size_t)blockIdx.y * stride;
@@ -1432,14 +1331,17 @@ __global__ __launch_bounds__(FH_BLOCK) void k_solve_diag_inv(T* const* LUs, T* I
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const int lr = lane & 15, lk = lane >> 4;
     const int t0 = wave, t1 = NT - 1 - wave;
-    const int n0 = UPPER ? NT - t0 : t0 + 1;
-    const int blo0 = UPPER ? t0 : 0, blo1 = UPPER ? t1 : 0;
+    const int n0 = UP ? NT - t0 : t0 + 1;
+    const int blo0 = UP ? t0 : 0, blo1 = UP ? t1 : 0;
     T a[NT + 1][4];
 #pragma unroll
     for (int q = 0; q <= NT; ++q) {
         const int tile = q < n0 ? t0 : t1, blk = q < n0 ? blo0 + q : blo1 + q - n0;
 #pragma unroll
-        for (int s4 = 0; s4 < 4; ++s4) a[q][s4] = inv[(size_t)(16 * blk + 4 * s4 + lk) * SOLVE_KB + 16 * tile + lr];
+        for (int s4 = 0; s4 < 4; ++s4) {
+            a[q][s4] = inv[ADJ ? (size_t)(16 * tile + lr) * SOLVE_KB + 16 * blk + 4 * s4 + lk : (size_t)(16 * blk + 4 * s4 + lk) * SOLVE_KB + 16 * tile + lr];
+            if constexpr (ADJ) a[q][s4] = lu_conj(a[q][s4]);
+        }
     }
     for (int e = t; e < SOLVE_KB * 16; e += FH_BLOCK) {
         const int i = e >> 4, c = e & 15, row = K0 + i;
@@ -1478,7 +1380,9 @@ __global__ __launch_bounds__(FH_BLOCK) void k_solve_diag_inv(T* const* LUs, T* I
 // c in [c0, c1) of the column-major factor, L11^-1 the 128 x 128 inverse k_solve_diag<IDENT> leaves behind the factor.  The
 // product is k_solve_diag_inv's (one workgroup per 16 columns, wave w the output tiles w and 7 - w); only the slab is read
 // and written along columns instead of panel rows.  Replaces four L11^-1 products of 32 rows and three k = 32 row-block
-// products per block column and side of the look-ahead.
+// products per block column and side of the look-ahead.  The product is kept as a copy on purpose: moved into a function
+// shared with k_solve_diag_inv (slab fill as a callback, or a load / multiply pair) it compiled to other register counts in
+// one kernel or the other.
 template <typename T>
 __global__ __launch_bounds__(FH_BLOCK) void k_lu_trsm128(T* const* LUs, lu_geom g, int K0, int c0, int c1) {
     constexpr int NT = SOLVE_KB / 16;
@@ -1532,7 +1436,10 @@ __global__ __launch_bounds__(FH_BLOCK) void k_lu_trsm128(T* const* LUs, lu_geom 
     }
 }
 
-template <int LD, typename T>
+// ADJ: the factor's block ROW is the operand,  IN[i,:] -= sum_{k<kd} conj(LU[K0+k, i]) Z[K0+k,:]  for the rows i in [r0, r1)
+// outside the block (below it in the U^H sweep, above it in the L^H sweep).  Lane (lr, lk) walks stored column ib + lr: 16
+// columns (stride N) per k-group, the four k-groups four consecutive rows of each.
+template <int LD, bool ADJ, typename T>
 __global__ __launch_bounds__(FH_BLOCK) void k_solve_update(T* const* LUs, T* IN, const T* ZS, size_t stride, lu_geom g, int K0,
                                                             int kd, int r0, int r1, int cta) {
     typedef decltype(T().x) ET;
@@ -1561,7 +1468,8 @@ __global__ __launch_bounds__(FH_BLOCK) void k_solve_update(T* const* LUs, T* IN,
 #pragma unroll
         for (int s = 0; s < KC / 4; ++s) {
             const int jk = j0 + 4 * s + lk, col = K0 + jk;
-            an[s] = (irow < r1 && jk < kd && col < g.n) ? A[(size_t)col * N + irow] : LU_MK(0, 0);
+            an[s] = (irow < r1 && jk < kd && col < g.n) ? op_at<ADJ>(A, N, irow, col) : LU_MK(0, 0);
+            if constexpr (ADJ) an[s] = lu_conj(an[s]);
         }
     };
     load_chunk(0);
@@ -1602,226 +1510,6 @@ __global__ __launch_bounds__(FH_BLOCK) void k_solve_update(T* const* LUs, T* IN,
                 *d = LU_MK(y.x - re[q][r], y.y - im[q][r]);
             }
         }
-    }
-}
-
-// Adjoint substitution on the same factors (ZGETRS 'C', two-sided FEAST):  with P S = L U,  S^H y = b  is
-//   U^H w = b   ascending over the 128-blocks   (U^H is lower triangular),
-//   L^H v = w   descending                      (L^H is unit upper triangular),
-//   y[perm[i]] = v[i].
-// k_solve_diag_inv_adj: the product with the conjugate transpose of a stored 128 x 128 inverse.  UPPER names the stored
-// inverse (true: U's), the triangle the product sees is the other one, and the operand of output tile `tile` and 16-block
-// `blk` is read as conj(inv[col][row]): lane (lr, lk) takes row 16 tile + lr of the transpose, i.e. stored column 16 tile + lr,
-// four consecutive stored rows per k-group (64 B contiguous per lane group of four k-groups).
-template <int LD, bool UPPER, typename T>
-__global__ __launch_bounds__(FH_BLOCK) void k_solve_diag_inv_adj(T* const* LUs, T* IN, T* OUT, size_t stride, lu_geom g, int K0, int kb) {
-    constexpr int NT = SOLVE_KB / 16;
-    constexpr bool UP = !UPPER;                  // triangle of the transposed inverse
-    const T* inv = LUs[blockIdx.y] + g.inv128 + ((size_t)(K0 / SOLVE_KB) * 2 + (UPPER ? 1 : 0)) * SOLVE_KB * SOLVE_KB;
-    const T* in = IN + (size_t)blockIdx.y * stride;
-    T* out = OUT + (size_t)blockIdx.y * stride;
-    const int ta = blockIdx.x;
-    __shared__ T S[SOLVE_KB][17];
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int lr = lane & 15, lk = lane >> 4;
-    const int t0 = wave, t1 = NT - 1 - wave;
-    const int n0 = UP ? NT - t0 : t0 + 1;
-    const int blo0 = UP ? t0 : 0, blo1 = UP ? t1 : 0;
-    T a[NT + 1][4];
-#pragma unroll
-    for (int q = 0; q <= NT; ++q) {
-        const int tile = q < n0 ? t0 : t1, blk = q < n0 ? blo0 + q : blo1 + q - n0;
-#pragma unroll
-        for (int s4 = 0; s4 < 4; ++s4) {
-            const T v = inv[(size_t)(16 * tile + lr) * SOLVE_KB + 16 * blk + 4 * s4 + lk];
-            a[q][s4] = LU_MK(v.x, -v.y);
-        }
-    }
-    for (int e = t; e < SOLVE_KB * 16; e += FH_BLOCK) {
-        const int i = e >> 4, c = e & 15, row = K0 + i;
-        S[i][c] = (i < LU_NB * kb && row < g.n) ? in[(size_t)row * LD + 16 * ta + c] : LU_MK(0, 0);
-    }
-    __syncthreads();
-    typename lu_el<T>::v4 re0 = {0, 0, 0, 0}, im0 = {0, 0, 0, 0}, re1 = {0, 0, 0, 0}, im1 = {0, 0, 0, 0};
-#pragma unroll
-    for (int q = 0; q <= NT; ++q) {
-        const int blk = q < n0 ? blo0 + q : blo1 + q - n0;
-#pragma unroll
-        for (int s4 = 0; s4 < 4; ++s4) {
-            const T b = S[16 * blk + 4 * s4 + lk][lr];
-            if (q < n0) {
-                re0 = lu_el<T>::mfma(a[q][s4].x, b.x, re0);
-                re0 = lu_el<T>::mfma(-a[q][s4].y, b.y, re0);
-                im0 = lu_el<T>::mfma(a[q][s4].x, b.y, im0);
-                im0 = lu_el<T>::mfma(a[q][s4].y, b.x, im0);
-            } else {
-                re1 = lu_el<T>::mfma(a[q][s4].x, b.x, re1);
-                re1 = lu_el<T>::mfma(-a[q][s4].y, b.y, re1);
-                im1 = lu_el<T>::mfma(a[q][s4].x, b.y, im1);
-                im1 = lu_el<T>::mfma(a[q][s4].y, b.x, im1);
-            }
-        }
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const int i0 = 16 * t0 + lu_el<T>::mrow(lk, r), i1 = 16 * t1 + lu_el<T>::mrow(lk, r);
-        if (i0 < LU_NB * kb && K0 + i0 < g.n) out[(size_t)(K0 + i0) * LD + 16 * ta + lr] = LU_MK(re0[r], im0[r]);
-        if (i1 < LU_NB * kb && K0 + i1 < g.n) out[(size_t)(K0 + i1) * LD + 16 * ta + lr] = LU_MK(re1[r], im1[r]);
-    }
-}
-
-// k_solve_update with the factor's block ROW as operand:  IN[i,:] -= sum_{k<kd} conj(LU[K0+k, i]) Z[K0+k,:]  for the rows
-// i in [r0, r1) outside the block (below it in the U^H sweep, above it in the L^H sweep).  Lane (lr, lk) walks stored column
-// ib + lr: 16 columns (stride N) per k-group, the four k-groups four consecutive rows of each.
-template <int LD, typename T>
-__global__ __launch_bounds__(FH_BLOCK) void k_solve_update_adj(T* const* LUs, T* IN, const T* ZS, size_t stride, lu_geom g, int K0,
-                                                                int kd, int r0, int r1, int cta) {
-    typedef decltype(T().x) ET;
-    constexpr int KC = SOLVE_KC, CT = LD / 16, XPT = KC * LD / FH_BLOCK;
-    __shared__ ET Xre[KC][LD + 16];
-    __shared__ ET Xim[KC][LD + 16];
-    const T* A = LUs[blockIdx.y];
-    const int N = g.ld;
-    T* in = IN + (size_t)blockIdx.y * stride;
-    const T* zs = ZS + (size_t)blockIdx.y * stride;
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int lr = lane & 15, lk = lane >> 4;
-    const int ib = r0 + (blockIdx.x * 4 + wave) * 16;
-    const int irow = ib + lr;
-    typename lu_el<T>::v4 re[CT], im[CT];
-#pragma unroll
-    for (int q = 0; q < CT; ++q) { re[q] = typename lu_el<T>::v4{0, 0, 0, 0}; im[q] = typename lu_el<T>::v4{0, 0, 0, 0}; }
-    T xn[XPT], an[KC / 4];
-    auto load_chunk = [&](int j0) {
-#pragma unroll
-        for (int q = 0; q < XPT; ++q) {
-            const int e = t + q * FH_BLOCK, jj = e / LD, c = e % LD;
-            const bool ok = j0 + jj < kd && K0 + j0 + jj < g.n;
-            xn[q] = ok ? zs[(size_t)(K0 + j0 + jj) * LD + c] : LU_MK(0, 0);
-        }
-#pragma unroll
-        for (int s = 0; s < KC / 4; ++s) {
-            const int jk = j0 + 4 * s + lk, col = K0 + jk;
-            const bool ok = irow < r1 && jk < kd && col < g.n;
-            const T v = ok ? A[(size_t)irow * N + col] : LU_MK(0, 0);
-            an[s] = LU_MK(v.x, -v.y);
-        }
-    };
-    load_chunk(0);
-    for (int j0 = 0; j0 < kd; j0 += KC) {
-#pragma unroll
-        for (int q = 0; q < XPT; ++q) {
-            const int e = t + q * FH_BLOCK, jj = e / LD, c = e % LD;
-            Xre[jj][c] = xn[q].x; Xim[jj][c] = xn[q].y;
-        }
-        T ac[KC / 4];
-#pragma unroll
-        for (int s = 0; s < KC / 4; ++s) ac[s] = an[s];
-        __syncthreads();
-        if (j0 + KC < kd) load_chunk(j0 + KC);
-#pragma unroll
-        for (int s = 0; s < KC / 4; ++s) {
-#pragma unroll
-            for (int q = 0; q < CT; ++q) {
-                if (q >= cta) break;
-                const ET xr = Xre[4 * s + lk][16 * q + lr], xi = Xim[4 * s + lk][16 * q + lr];
-                re[q] = lu_el<T>::mfma(ac[s].x, xr, re[q]);
-                im[q] = lu_el<T>::mfma(ac[s].x, xi, im[q]);
-                re[q] = lu_el<T>::mfma(-ac[s].y, xi, re[q]);
-                im[q] = lu_el<T>::mfma(ac[s].y, xr, im[q]);
-            }
-        }
-        __syncthreads();
-    }
-#pragma unroll
-    for (int q = 0; q < CT; ++q) {
-        if (q >= cta) break;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int i = ib + lu_el<T>::mrow(lk, r);
-            if (i < r1) {
-                T* d = in + (size_t)i * LD + 16 * q + lr;
-                const T y = *d;
-                *d = LU_MK(y.x - re[q][r], y.y - im[q][r]);
-            }
-        }
-    }
-}
-
-// Adjoint twin of k_solve_diag (no IDENT form) for the factors that keep only 32-block inverses -- most fronts of the
-// multifrontal tree: one workgroup per (column tile, matrix) keeps the SOLVE_KB x 16 slab in LDS and walks its 32-blocks in
-// the opposite order of the twin.  UPPER names the stored factor: true is U, whose conjugate transpose is LOWER triangular
-// (blocks ascending, z_i = Uinv_ii^H s_i, then s_j -= U_ij^H z_i for j > i); false is L, L^H is unit UPPER triangular
-// (descending, j < i).  Operands are read as conj(inv[col][row]) and conj(A[row * ld + col]): lane (lr, lk) takes row lr of the
-// transposed operand, i.e. stored column lr, four consecutive stored rows per k-group.  Rows and columns are bounded by the
-// pivot block (g.n), as in the twin; the same v_mfma_f64_16x16x4_f64 products.
-template <int LD, bool UPPER, typename T>
-__global__ __launch_bounds__(FH_BLOCK) void k_solve_diag_adj(T* const* LUs, T* IN, T* OUT, size_t stride, lu_geom g, int K0, int kb) {
-    const int node = blockIdx.y;
-    const T* A = LUs[node];
-    const int N = g.ld, NBND = g.n;
-    const T* invbase = A + g.inv32;
-    const T* in = IN + (size_t)node * stride;
-    T* out = OUT + (size_t)node * stride;
-    const int ta = blockIdx.x;
-    __shared__ T S[SOLVE_KB][17];
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int lr = lane & 15, lk = lane >> 4;
-    for (int e = t; e < SOLVE_KB * 16; e += FH_BLOCK) {
-        const int i = e >> 4, c = e & 15, row = K0 + i;
-        S[i][c] = (i < LU_NB * kb && row < NBND) ? in[(size_t)row * LD + 16 * ta + c] : LU_MK(0, 0);
-    }
-    __syncthreads();
-    for (int step = 0; step < kb; ++step) {
-        const int i = UPPER ? step : kb - 1 - step;
-        const int k0 = K0 + LU_NB * i;
-        const T* inv = invbase + ((size_t)(k0 / LU_NB) * 2 + (UPPER ? 1 : 0)) * LU_NB * LU_NB;
-        typename lu_el<T>::v4 re = {0, 0, 0, 0}, im = {0, 0, 0, 0};
-        if (wave < 2) {
-#pragma unroll
-            for (int kk = 0; kk < LU_NB; kk += 4) {
-                const T v = inv[(size_t)(16 * wave + lr) * LU_NB + kk + lk];
-                const T a = LU_MK(v.x, -v.y);
-                const T b = S[LU_NB * i + kk + lk][lr];
-                re = lu_el<T>::mfma(a.x, b.x, re);
-                re = lu_el<T>::mfma(-a.y, b.y, re);
-                im = lu_el<T>::mfma(a.x, b.y, im);
-                im = lu_el<T>::mfma(a.y, b.x, im);
-            }
-        }
-        __syncthreads();
-        if (wave < 2) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) S[LU_NB * i + 16 * wave + lu_el<T>::mrow(lk, r)][lr] = LU_MK(re[r], im[r]);
-        }
-        __syncthreads();
-        const int nj = UPPER ? kb - 1 - i : i;
-        for (int q = wave; q < 2 * nj; q += 4) {
-            const int j = UPPER ? i + 1 + q / 2 : q / 2;
-            const int rbase = LU_NB * j + 16 * (q & 1);
-            typename lu_el<T>::v4 ur = {0, 0, 0, 0}, ui = {0, 0, 0, 0};
-#pragma unroll
-            for (int kk = 0; kk < LU_NB; kk += 4) {
-                const int grow = K0 + rbase + lr, gcol = k0 + kk + lk;      // row / column of the TRANSPOSED operand
-                const T v = (grow < NBND && gcol < NBND) ? A[(size_t)grow * N + gcol] : LU_MK(0, 0);
-                const T a = LU_MK(v.x, -v.y);
-                const T b = S[LU_NB * i + kk + lk][lr];
-                ur = lu_el<T>::mfma(a.x, b.x, ur);
-                ur = lu_el<T>::mfma(-a.y, b.y, ur);
-                ui = lu_el<T>::mfma(a.x, b.y, ui);
-                ui = lu_el<T>::mfma(a.y, b.x, ui);
-            }
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                T& d = S[rbase + lu_el<T>::mrow(lk, r)][lr];
-                d = LU_MK(d.x - ur[r], d.y - ui[r]);
-            }
-        }
-        __syncthreads();
-    }
-    for (int e = t; e < SOLVE_KB * 16; e += FH_BLOCK) {
-        const int i = e >> 4, c = e & 15, row = K0 + i;
-        if (i < LU_NB * kb && row < NBND) out[(size_t)row * LD + 16 * ta + c] = S[i][c];
     }
 }
 
@@ -2053,7 +1741,7 @@ static int lu_factor_batch(feasthip_ctx* h, const std::vector<int>& which, const
         };
         const int Kend2 = lookahead ? std::min(N, Kend + KB) : N;
         if (block_inverse && Kend < N)      // 128 x 128 inverses of the block column's unit-lower diagonal slabs (from the panels' 32-block inverses)
-            hipLaunchKernelGGL((k_solve_diag<16, false, true, T>), dim3(SOLVE_KB / 16, (Kend - K0) / SOLVE_KB, nf), dim3(FH_BLOCK), 0, h->stream, dlus,
+            hipLaunchKernelGGL((k_solve_diag<16, false, true, false, T>), dim3(SOLVE_KB / 16, (Kend - K0) / SOLVE_KB, nf), dim3(FH_BLOCK), 0, h->stream, dlus,
                                (T*)nullptr, (T*)nullptr, (size_t)0, geom, K0, 0);
         laswp(K0, Kend - K0, 0, K0, Kend, Kend2);
         right_of_block(Kend, Kend2, 1);
@@ -2074,8 +1762,8 @@ static int lu_factor_batch(feasthip_ctx* h, const std::vector<int>& which, const
     hipLaunchKernelGGL((k_lu_invert_diag<LU_NB, T>), dim3((N + LU_NB - 1) / LU_NB, nf), dim3(64), 0, h->stream, dlus, geom);
     {   // 128 x 128 inverses from the 32-block inverses: the in-block substitution applied to the identity
         dim3 g(SOLVE_KB / 16, (N + SOLVE_KB - 1) / SOLVE_KB, nf);
-        hipLaunchKernelGGL((k_solve_diag<16, false, true, T>), g, dim3(FH_BLOCK), 0, h->stream, dlus, (T*)nullptr, (T*)nullptr, (size_t)0, geom, 0, 0);
-        hipLaunchKernelGGL((k_solve_diag<16, true, true, T>), g, dim3(FH_BLOCK), 0, h->stream, dlus, (T*)nullptr, (T*)nullptr, (size_t)0, geom, 0, 0);
+        hipLaunchKernelGGL((k_solve_diag<16, false, true, false, T>), g, dim3(FH_BLOCK), 0, h->stream, dlus, (T*)nullptr, (T*)nullptr, (size_t)0, geom, 0, 0);
+        hipLaunchKernelGGL((k_solve_diag<16, true, true, false, T>), g, dim3(FH_BLOCK), 0, h->stream, dlus, (T*)nullptr, (T*)nullptr, (size_t)0, geom, 0, 0);
     }
     if (N <= 16000) hipLaunchKernelGGL(k_build_perm, dim3(nf), dim3(FH_BLOCK), (size_t)N * sizeof(int), h->stream, dpvs, N);
     else hipLaunchKernelGGL(k_build_perm_global, dim3(nf), dim3(64), 0, h->stream, dpvs, N);
@@ -2093,27 +1781,35 @@ static int lu_solve_rb(int rows, int nf) {
     return std::max(1, std::min(8, rb));
 }
 
-template <int LD, typename T>
+// The two sweeps of a solve with the dense factors.  Both directions walk the 128-blocks up, then down, updating the rows
+// still to come after each diagonal step; what differs is the stored triangle each sweep addresses and the buffer roles:
+//   forward            up: L z = P b   (stored L, Y -> Z)     down: U x = z     (stored U, Z -> Y)    Y: permuted rhs in, x out
+//   ADJ (ZGETRS 'C')   up: U^H w = b   (stored U, Z -> Y)     down: L^H v = w   (stored L, Y -> Z)    Z: rhs in, v out; the
+//                                                                               caller scatters Z by the row permutation
+// The adjoint is always two-level (fp64 factors only); the one-level legacy sweeps (k_solve_step) are forward-only.
+template <int LD, bool ADJ, typename T>
 static void lu_solve_launch(feasthip_ctx* h, T** dlus, T* Y, T* Z, size_t stride, int N, int nf, int m) {
     const int cta = std::max(1, std::min(LD / 16, (m + 15) / 16));
     const lu_geom geom = lu_dense_geom<T>(N);
     const int nblocks = (N + LU_NB - 1) / LU_NB;
     const bool one_level = h->lu_solve_legacy != 0;
-    if (!one_level) {
+    if (ADJ || !one_level) {
         const int nouter = (N + SOLVE_KB - 1) / SOLVE_KB;
-        for (int b = 0; b < nouter; ++b) {        // forward: L z = P b   (Y -> Z)
+        T* const P = ADJ ? Z : Y;                 // read by the upward sweep, written by the downward one
+        T* const Q = ADJ ? Y : Z;
+        for (int b = 0; b < nouter; ++b) {        // up (P -> Q)
             const int K0 = b * SOLVE_KB, kb = std::min(SOLVE_KB / LU_NB, (N - K0 + LU_NB - 1) / LU_NB);
             const int r0 = K0 + LU_NB * kb;
-            hipLaunchKernelGGL((k_solve_diag_inv<LD, false, T>), dim3(cta, nf), dim3(FH_BLOCK), 0, h->stream, dlus, Y, Z, stride, geom, K0, kb);
+            hipLaunchKernelGGL((k_solve_diag_inv<LD, ADJ, ADJ, T>), dim3(cta, nf), dim3(FH_BLOCK), 0, h->stream, dlus, P, Q, stride, geom, K0, kb);
             if (r0 < N)
-                hipLaunchKernelGGL((k_solve_update<LD, T>), dim3((N - r0 + 63) / 64, nf), dim3(FH_BLOCK), 0, h->stream, dlus, Y, Z,
+                hipLaunchKernelGGL((k_solve_update<LD, ADJ, T>), dim3((N - r0 + 63) / 64, nf), dim3(FH_BLOCK), 0, h->stream, dlus, P, Q,
                                    stride, geom, K0, LU_NB * kb, r0, N, cta);
         }
-        for (int b = nouter - 1; b >= 0; --b) {   // backward: U x = z   (Z -> Y)
+        for (int b = nouter - 1; b >= 0; --b) {   // down (Q -> P)
             const int K0 = b * SOLVE_KB, kb = std::min(SOLVE_KB / LU_NB, (N - K0 + LU_NB - 1) / LU_NB);
-            hipLaunchKernelGGL((k_solve_diag_inv<LD, true, T>), dim3(cta, nf), dim3(FH_BLOCK), 0, h->stream, dlus, Z, Y, stride, geom, K0, kb);
+            hipLaunchKernelGGL((k_solve_diag_inv<LD, !ADJ, ADJ, T>), dim3(cta, nf), dim3(FH_BLOCK), 0, h->stream, dlus, Q, P, stride, geom, K0, kb);
             if (K0 > 0)
-                hipLaunchKernelGGL((k_solve_update<LD, T>), dim3((K0 + 63) / 64, nf), dim3(FH_BLOCK), 0, h->stream, dlus, Z, Y,
+                hipLaunchKernelGGL((k_solve_update<LD, ADJ, T>), dim3((K0 + 63) / 64, nf), dim3(FH_BLOCK), 0, h->stream, dlus, Q, P,
                                    stride, geom, K0, LU_NB * kb, 0, K0, cta);
         }
         return;
@@ -2129,30 +1825,6 @@ static void lu_solve_launch(feasthip_ctx* h, T** dlus, T* Y, T* Z, size_t stride
         const int rb = lu_solve_rb(k0, nf);
         const int gx = std::max(1, (k0 + 64 * rb - 1) / (64 * rb));
         hipLaunchKernelGGL((k_solve_step<LU_NB, LD, true, T>), dim3(gx, nf), dim3(FH_BLOCK), 0, h->stream, dlus, Z, Y, stride, N, k0, 0, k0, rb, cta);
-    }
-}
-
-// Adjoint substitution (fp64 factors, always the two-level 128-column path): Z holds the right-hand side on entry,
-// U^H sweep Z -> Y, L^H sweep Y -> Z; the caller scatters Z by the row permutation.
-template <int LD>
-static void lu_solve_adjoint_launch(feasthip_ctx* h, cplx** dlus, cplx* Y, cplx* Z, size_t stride, int N, int nf, int m) {
-    const int cta = std::max(1, std::min(LD / 16, (m + 15) / 16));
-    const lu_geom geom = lu_dense_geom<cplx>(N);
-    const int nouter = (N + SOLVE_KB - 1) / SOLVE_KB;
-    for (int b = 0; b < nouter; ++b) {        // U^H w = b   (Z -> Y)
-        const int K0 = b * SOLVE_KB, kb = std::min(SOLVE_KB / LU_NB, (N - K0 + LU_NB - 1) / LU_NB);
-        const int r0 = K0 + LU_NB * kb;
-        hipLaunchKernelGGL((k_solve_diag_inv_adj<LD, true, cplx>), dim3(cta, nf), dim3(FH_BLOCK), 0, h->stream, dlus, Z, Y, stride, geom, K0, kb);
-        if (r0 < N)
-            hipLaunchKernelGGL((k_solve_update_adj<LD, cplx>), dim3((N - r0 + 63) / 64, nf), dim3(FH_BLOCK), 0, h->stream, dlus, Z, Y,
-                               stride, geom, K0, LU_NB * kb, r0, N, cta);
-    }
-    for (int b = nouter - 1; b >= 0; --b) {   // L^H v = w   (Y -> Z)
-        const int K0 = b * SOLVE_KB, kb = std::min(SOLVE_KB / LU_NB, (N - K0 + LU_NB - 1) / LU_NB);
-        hipLaunchKernelGGL((k_solve_diag_inv_adj<LD, false, cplx>), dim3(cta, nf), dim3(FH_BLOCK), 0, h->stream, dlus, Y, Z, stride, geom, K0, kb);
-        if (K0 > 0)
-            hipLaunchKernelGGL((k_solve_update_adj<LD, cplx>), dim3((K0 + 63) / 64, nf), dim3(FH_BLOCK), 0, h->stream, dlus, Y, Z,
-                               stride, geom, K0, LU_NB * kb, 0, K0, cta);
     }
 }
 
@@ -2183,9 +1855,9 @@ static int lu_solve_batch(feasthip_ctx* h, int ld, int m, const std::vector<int>
         if (h->adjoint) {                           // (z B - A)^-H on the same factors; the API layer refuses complex64 factors
             fh_prof_begin(h, "lu_solve_adjoint");
             hipLaunchKernelGGL(k_copy_panels, dim3(fh_vec_nblk(N, ld), nf), dim3(FH_BLOCK), 0, h->stream, RHS, rhs_stride, Z, stride, (size_t)N * ld);
-            if (ld == 16) lu_solve_adjoint_launch<16>(h, dlus, Y, Z, stride, N, nf, m);
-            else if (ld == 32) lu_solve_adjoint_launch<32>(h, dlus, Y, Z, stride, N, nf, m);
-            else lu_solve_adjoint_launch<64>(h, dlus, Y, Z, stride, N, nf, m);
+            if (ld == 16) lu_solve_launch<16, true, T>(h, dlus, W, Z, stride, N, nf, m);
+            else if (ld == 32) lu_solve_launch<32, true, T>(h, dlus, W, Z, stride, N, nf, m);
+            else lu_solve_launch<64, true, T>(h, dlus, W, Z, stride, N, nf, m);
             hipLaunchKernelGGL(k_scatter_perm_rows, dim3(fh_vec_nblk(N, ld), nf), dim3(FH_BLOCK), 0, h->stream, Z, dperms, Y, stride, N, ld);
             fh_prof_end(h);
             return 0;
@@ -2193,9 +1865,9 @@ static int lu_solve_batch(feasthip_ctx* h, int ld, int m, const std::vector<int>
     }
     fh_prof_begin(h, "lu_solve");
     hipLaunchKernelGGL((k_gather_rows<T>), dim3(fh_vec_nblk(N, ld), nf), dim3(FH_BLOCK), 0, h->stream, RHS, rhs_stride, dperms, W, stride, N, ld);
-    if (ld == 16) lu_solve_launch<16, T>(h, dlus, W, Z, stride, N, nf, m);
-    else if (ld == 32) lu_solve_launch<32, T>(h, dlus, W, Z, stride, N, nf, m);
-    else lu_solve_launch<64, T>(h, dlus, W, Z, stride, N, nf, m);
+    if (ld == 16) lu_solve_launch<16, false, T>(h, dlus, W, Z, stride, N, nf, m);
+    else if (ld == 32) lu_solve_launch<32, false, T>(h, dlus, W, Z, stride, N, nf, m);
+    else lu_solve_launch<64, false, T>(h, dlus, W, Z, stride, N, nf, m);
     if constexpr (sizeof(T) != sizeof(cplx))
         hipLaunchKernelGGL(k_widen_panels, dim3(fh_vec_nblk(N, ld), nf), dim3(FH_BLOCK), 0, h->stream, (const cplxf*)W, Y, stride, (size_t)N * ld);
     fh_prof_end(h);
@@ -2501,7 +2173,7 @@ static int wband_factor_t(feasthip_ctx* h, int nf, void* const* abs_host, T** db
         // row right of it is then ONE product per side of the look-ahead instead of four 32-row products and three k = 32
         // row-block products (FH_WBAND_BLOCKINV=0: the 32-row sequence)
         if (block_inverse)
-            hipLaunchKernelGGL((k_solve_diag<16, false, true, T>), dim3(SOLVE_KB / 16, 1, nf), dim3(FH_BLOCK), 0, h->stream, dbases, (T*)nullptr, (T*)nullptr, (size_t)0, geom, K0, 0);
+            hipLaunchKernelGGL((k_solve_diag<16, false, true, false, T>), dim3(SOLVE_KB / 16, 1, nf), dim3(FH_BLOCK), 0, h->stream, dbases, (T*)nullptr, (T*)nullptr, (size_t)0, geom, K0, 0);
         const int Kend2 = lookahead ? std::min(nc, Kend + WB) : nc;
         // the rest needs the block column's panels only, not the next block column's update: it starts beside that update
         if (Kend2 < nc) {
@@ -2521,8 +2193,8 @@ static int wband_factor_t(feasthip_ctx* h, int nf, void* const* abs_host, T** db
     hipLaunchKernelGGL((k_lu_invert_diag<LU_NB, T>), dim3((N + LU_NB - 1) / LU_NB, nf), dim3(64), 0, h->stream, dbases, geom);
     {
         dim3 g(SOLVE_KB / 16, (N + SOLVE_KB - 1) / SOLVE_KB, nf);
-        hipLaunchKernelGGL((k_solve_diag<16, false, true, T>), g, dim3(FH_BLOCK), 0, h->stream, dbases, (T*)nullptr, (T*)nullptr, (size_t)0, geom, 0, 0);
-        hipLaunchKernelGGL((k_solve_diag<16, true, true, T>), g, dim3(FH_BLOCK), 0, h->stream, dbases, (T*)nullptr, (T*)nullptr, (size_t)0, geom, 0, 0);
+        hipLaunchKernelGGL((k_solve_diag<16, false, true, false, T>), g, dim3(FH_BLOCK), 0, h->stream, dbases, (T*)nullptr, (T*)nullptr, (size_t)0, geom, 0, 0);
+        hipLaunchKernelGGL((k_solve_diag<16, true, true, false, T>), g, dim3(FH_BLOCK), 0, h->stream, dbases, (T*)nullptr, (T*)nullptr, (size_t)0, geom, 0, 0);
     }
     fh_prof_end(h);
     (void)dinfo;
@@ -2540,17 +2212,17 @@ static void wband_solve_launch(feasthip_ctx* h, T** dbases, int** dpvs, T* Y, T*
         const int kb = (Kend - K0 + LU_NB - 1) / LU_NB;
         const int nr = std::min(N, Kend + kl);
         hipLaunchKernelGGL((k_wband_swap<T>), dim3(LD / 16, nf), dim3(FH_BLOCK), (size_t)(nr - K0) * sizeof(int), h->stream, dpvs, Y, stride, LD, K0, Kend - K0, nr - K0);
-        hipLaunchKernelGGL((k_solve_diag_inv<LD, false, T>), dim3(cta, nf), dim3(FH_BLOCK), 0, h->stream, dbases, Y, Z, stride, geom, K0, kb);
+        hipLaunchKernelGGL((k_solve_diag_inv<LD, false, false, T>), dim3(cta, nf), dim3(FH_BLOCK), 0, h->stream, dbases, Y, Z, stride, geom, K0, kb);
         if (Kend < nr)
-            hipLaunchKernelGGL((k_solve_update<LD, T>), dim3((nr - Kend + 63) / 64, nf), dim3(FH_BLOCK), 0, h->stream, dbases, Y, Z, stride, geom, K0, Kend - K0, Kend, nr, cta);
+            hipLaunchKernelGGL((k_solve_update<LD, false, T>), dim3((nr - Kend + 63) / 64, nf), dim3(FH_BLOCK), 0, h->stream, dbases, Y, Z, stride, geom, K0, Kend - K0, Kend, nr, cta);
     }
     for (int b = nouter - 1; b >= 0; --b) {        // backward: U11 x = z, rows above (within kl + ku) -= U12 x   (Z -> Y)
         const int K0 = b * SOLVE_KB, Kend = std::min(N, K0 + SOLVE_KB);
         const int kb = (Kend - K0 + LU_NB - 1) / LU_NB;
-        hipLaunchKernelGGL((k_solve_diag_inv<LD, true, T>), dim3(cta, nf), dim3(FH_BLOCK), 0, h->stream, dbases, Z, Y, stride, geom, K0, kb);
+        hipLaunchKernelGGL((k_solve_diag_inv<LD, true, false, T>), dim3(cta, nf), dim3(FH_BLOCK), 0, h->stream, dbases, Z, Y, stride, geom, K0, kb);
         const int r0 = std::max(0, K0 - kv);
         if (r0 < K0)
-            hipLaunchKernelGGL((k_solve_update<LD, T>), dim3((K0 - r0 + 63) / 64, nf), dim3(FH_BLOCK), 0, h->stream, dbases, Z, Y, stride, geom, K0, Kend - K0, r0, K0, cta);
+            hipLaunchKernelGGL((k_solve_update<LD, false, T>), dim3((K0 - r0 + 63) / 64, nf), dim3(FH_BLOCK), 0, h->stream, dbases, Z, Y, stride, geom, K0, Kend - K0, r0, K0, cta);
     }
 }
 
@@ -3160,8 +2832,8 @@ static int mf_factor_t(feasthip_ctx* h, int nf, void* const* stores, int* const*
         hipLaunchKernelGGL((k_lu_invert_diag<LU_NB, T>), dim3(np / LU_NB, nmat), dim3(64), 0, h->stream, ST, gs);
         if (G.inv128) {
             const dim3 gi(SOLVE_KB / 16, (np + SOLVE_KB - 1) / SOLVE_KB, nmat);
-            hipLaunchKernelGGL((k_solve_diag<16, false, true, T>), gi, dim3(FH_BLOCK), 0, h->stream, ST, (T*)nullptr, (T*)nullptr, (size_t)0, gs, 0, 0);
-            hipLaunchKernelGGL((k_solve_diag<16, true, true, T>), gi, dim3(FH_BLOCK), 0, h->stream, ST, (T*)nullptr, (T*)nullptr, (size_t)0, gs, 0, 0);
+            hipLaunchKernelGGL((k_solve_diag<16, false, true, false, T>), gi, dim3(FH_BLOCK), 0, h->stream, ST, (T*)nullptr, (T*)nullptr, (size_t)0, gs, 0, 0);
+            hipLaunchKernelGGL((k_solve_diag<16, true, true, false, T>), gi, dim3(FH_BLOCK), 0, h->stream, ST, (T*)nullptr, (T*)nullptr, (size_t)0, gs, 0, 0);
         }
         hipLaunchKernelGGL(k_build_perm, dim3(nmat), dim3(FH_BLOCK), (size_t)np * sizeof(int), h->stream, PV, np);
         fh_prof_end(h);
@@ -3197,6 +2869,58 @@ int fh_mf_factor(feasthip_ctx* h, int prec, int nf, void* const* stores, int* co
     return mf_factor_t<cplx>(h, nf, stores, pivs, dz, info_out, mult_out);
 }
 
+// What every group step of the two multifrontal solves works on: the group's batch (F fronts x nf nodes of one shape), its
+// rows of the two panel buffers, its stored factors and the two views of them the substitution kernels take.
+template <typename T>
+struct mf_group_view {
+    const fh_mf::group& G;
+    int F, nmat, n, np, nb;
+    T *Yg, *Zg;
+    size_t stride;
+    T** ST;
+    lu_geom gd;         // diagonal solves: rows and columns bounded by the pivot block
+    lu_geom gu;         // updates: all rows of the front
+};
+template <int LD, typename T>
+static mf_group_view<T> mf_group(const fh_mf::plan& P, const mf_ptrs<T>& ptr, int g, int nf, T* Y, T* Z) {
+    const fh_mf::group& G = P.groups[g];
+    const int F = (int)G.fronts.size(), n = G.n, np = G.np;
+    const size_t i32 = fh_mf::inv32_elems(np);
+    return mf_group_view<T>{G, F, F * nf, n, np, G.nb, Y + G.rhs_off * (size_t)nf * LD, Z + G.rhs_off * (size_t)nf * LD, (size_t)n * LD,
+                            ptr.store + ptr.off[g], lu_geom{n, np, (size_t)n * np, (size_t)n * np + i32}, lu_geom{n, n, (size_t)n * np, (size_t)n * np + i32}};
+}
+
+// One diagonal step on the stored L (upper = false) or U of a group: a product with the 128-block inverse where the group
+// keeps one, the walk over the 32-blocks otherwise.
+template <int LD, bool ADJ, typename T>
+static void mf_diag(feasthip_ctx* h, int cta, bool upper, const mf_group_view<T>& v, T* IN, T* OUTp, int K0, int kb) {
+    const dim3 grid(cta, v.nmat), block(FH_BLOCK);
+    if (v.G.inv128 != 0) {
+        if (upper) hipLaunchKernelGGL((k_solve_diag_inv<LD, true, ADJ, T>), grid, block, 0, h->stream, v.ST, IN, OUTp, v.stride, v.gd, K0, kb);
+        else hipLaunchKernelGGL((k_solve_diag_inv<LD, false, ADJ, T>), grid, block, 0, h->stream, v.ST, IN, OUTp, v.stride, v.gd, K0, kb);
+    } else {
+        if (upper) hipLaunchKernelGGL((k_solve_diag<LD, true, false, ADJ, T>), grid, block, 0, h->stream, v.ST, IN, OUTp, v.stride, v.gd, K0, kb);
+        else hipLaunchKernelGGL((k_solve_diag<LD, false, false, ADJ, T>), grid, block, 0, h->stream, v.ST, IN, OUTp, v.stride, v.gd, K0, kb);
+    }
+}
+
+// Zg = [b1; 0] + the children's boundary rows, the children's panels read from `kids` (the buffer the sweep leaves them in)
+template <int LD, typename T>
+static void mf_gather_rhs(feasthip_ctx* h, fh_mf_state* S, int g, int nf, const mf_group_view<T>& v, const cplx* RHS, size_t rhs_stride, const T* kids) {
+    const unsigned gb = mf_blocks((size_t)v.n * LD, 4 * FH_BLOCK, 64);
+    hipLaunchKernelGGL((k_mf_fwd_load<LD, T>), dim3(gb, v.nmat), dim3(FH_BLOCK), 0, h->stream, RHS, rhs_stride, S->d_perm, S->d_slots + S->slot_off[g], v.F, v.Zg, v.n);
+    for (int side = 0; side < 2; ++side) {
+        const size_t k0 = S->kid_off[side][g], k1 = side == 0 ? S->kid_off[1][g] : S->kid_off[0][g + 1];
+        if (k1 > k0) {
+            int nbmax = 0;
+            for (int c : v.G.kids[side]) nbmax = std::max(nbmax, S->P.fronts[c].nbnd);
+            if (nbmax > 0)
+                hipLaunchKernelGGL((k_mf_fwd_add<LD, T>), dim3(mf_blocks((size_t)nbmax * LD, 4 * FH_BLOCK, 64), (unsigned)(k1 - k0), nf), dim3(FH_BLOCK), 0, h->stream,
+                                   S->d_kids + k0, kids, v.Zg, S->d_rel, nf, v.F, v.n);
+        }
+    }
+}
+
 template <int LD, typename T>
 static int mf_solve_ld(feasthip_ctx* h, fh_mf_state* S, int nf, const mf_ptrs<T>& ptr, const cplx* RHS, size_t rhs_stride, cplx* OUT, size_t out_stride, int m) {
     const fh_mf::plan& P = S->P;
@@ -3207,73 +2931,36 @@ static int mf_solve_ld(feasthip_ctx* h, fh_mf_state* S, int nf, const mf_ptrs<T>
     if ((rc = fh_buf(h, "mf_y", rows * LD, &Y))) return rc;
     if ((rc = fh_buf(h, "mf_z", rows * LD, &Z))) return rc;
     fh_prof_begin(h, "mf_solve");
-    auto diag = [&](bool upper, T** ST, T* IN, T* OUTp, size_t stride, const lu_geom& gd, int K0, int kb, int nmat, bool inv128) {
-        const dim3 grid(cta, nmat), block(FH_BLOCK);
-        if (inv128) {
-            if (upper) hipLaunchKernelGGL((k_solve_diag_inv<LD, true, T>), grid, block, 0, h->stream, ST, IN, OUTp, stride, gd, K0, kb);
-            else hipLaunchKernelGGL((k_solve_diag_inv<LD, false, T>), grid, block, 0, h->stream, ST, IN, OUTp, stride, gd, K0, kb);
-        } else {
-            if (upper) hipLaunchKernelGGL((k_solve_diag<LD, true, false, T>), grid, block, 0, h->stream, ST, IN, OUTp, stride, gd, K0, kb);
-            else hipLaunchKernelGGL((k_solve_diag<LD, false, false, T>), grid, block, 0, h->stream, ST, IN, OUTp, stride, gd, K0, kb);
-        }
-    };
     auto forward_group = [&](int g) -> int {                     // forward: leaves first
-        const fh_mf::group& G = P.groups[g];
-        const int F = (int)G.fronts.size(), nmat = F * nf, n = G.n, np = G.np;
-        T* Yg = Y + G.rhs_off * (size_t)nf * LD;
-        T* Zg = Z + G.rhs_off * (size_t)nf * LD;
-        const size_t stride = (size_t)n * LD;
-        T** ST = ptr.store + ptr.off[g];
-        const unsigned gb = mf_blocks((size_t)n * LD, 4 * FH_BLOCK, 64);
-        hipLaunchKernelGGL((k_mf_fwd_load<LD, T>), dim3(gb, nmat), dim3(FH_BLOCK), 0, h->stream, RHS, rhs_stride, S->d_perm, S->d_slots + S->slot_off[g], F, Zg, n);
-        for (int side = 0; side < 2; ++side) {
-            const size_t k0 = S->kid_off[side][g], k1 = side == 0 ? S->kid_off[1][g] : S->kid_off[0][g + 1];
-            if (k1 > k0) {
-                int nbmax = 0;
-                for (int c : G.kids[side]) nbmax = std::max(nbmax, P.fronts[c].nbnd);
-                if (nbmax > 0)
-                    hipLaunchKernelGGL((k_mf_fwd_add<LD, T>), dim3(mf_blocks((size_t)nbmax * LD, 4 * FH_BLOCK, 64), (unsigned)(k1 - k0), nf), dim3(FH_BLOCK), 0, h->stream,
-                                       S->d_kids + k0, Y, Zg, S->d_rel, nf, F, n);
-            }
-        }
-        hipLaunchKernelGGL((k_mf_fwd_perm<LD, T>), dim3(gb, nmat), dim3(FH_BLOCK), 0, h->stream, ptr.piv + ptr.off[g], Zg, Yg, n, np);
-        const size_t i32 = fh_mf::inv32_elems(np);
-        const lu_geom gd{n, np, (size_t)n * np, (size_t)n * np + i32};      // diagonal solves: bounded by the pivot block
-        const lu_geom gu{n, n, (size_t)n * np, (size_t)n * np + i32};       // updates: all rows of the front
-        for (int K0 = 0; K0 < np; K0 += SOLVE_KB) {
-            const int kb = std::min(SOLVE_KB / LU_NB, (np - K0) / LU_NB);
+        const mf_group_view<T> v = mf_group<LD>(P, ptr, g, nf, Y, Z);
+        mf_gather_rhs<LD>(h, S, g, nf, v, RHS, rhs_stride, Y);
+        hipLaunchKernelGGL((k_mf_fwd_perm<LD, T>), dim3(mf_blocks((size_t)v.n * LD, 4 * FH_BLOCK, 64), v.nmat), dim3(FH_BLOCK), 0, h->stream, ptr.piv + ptr.off[g], v.Zg, v.Yg, v.n, v.np);
+        for (int K0 = 0; K0 < v.np; K0 += SOLVE_KB) {
+            const int kb = std::min(SOLVE_KB / LU_NB, (v.np - K0) / LU_NB);
             const int r0 = K0 + LU_NB * kb;
-            diag(false, ST, Yg, Zg, stride, gd, K0, kb, nmat, G.inv128 != 0);
-            if (r0 < n)
-                hipLaunchKernelGGL((k_solve_update<LD, T>), dim3((n - r0 + 63) / 64, nmat), dim3(FH_BLOCK), 0, h->stream, ST, Yg, Zg, stride, gu, K0, LU_NB * kb, r0, n, cta);
+            mf_diag<LD, false>(h, cta, false, v, v.Yg, v.Zg, K0, kb);
+            if (r0 < v.n)
+                hipLaunchKernelGGL((k_solve_update<LD, false, T>), dim3((v.n - r0 + 63) / 64, v.nmat), dim3(FH_BLOCK), 0, h->stream, v.ST, v.Yg, v.Zg, v.stride, v.gu, K0, LU_NB * kb, r0, v.n, cta);
         }
         return 0;
     };
     auto backward_group = [&](int g) -> int {                    // backward: root first
-        const fh_mf::group& G = P.groups[g];
-        const int F = (int)G.fronts.size(), nmat = F * nf, n = G.n, np = G.np, nb = G.nb;
-        T* Yg = Y + G.rhs_off * (size_t)nf * LD;
-        T* Zg = Z + G.rhs_off * (size_t)nf * LD;
-        const size_t stride = (size_t)n * LD;
-        T** ST = ptr.store + ptr.off[g];
-        const size_t i32 = fh_mf::inv32_elems(np);
-        const lu_geom gd{n, np, (size_t)n * np, (size_t)n * np + i32};
-        const lu_geom gu{n, n, (size_t)n * np, (size_t)n * np + i32};
-        if (nb > 0) {
-            hipLaunchKernelGGL((k_mf_bwd_load<LD, T>), dim3(mf_blocks((size_t)nb * LD, 4 * FH_BLOCK, 64), nmat), dim3(FH_BLOCK), 0, h->stream, S->d_slots + S->slot_off[g], F,
-                               Y, Yg, S->d_rel, nf, n, np);
+        const mf_group_view<T> v = mf_group<LD>(P, ptr, g, nf, Y, Z);
+        if (v.nb > 0) {
+            hipLaunchKernelGGL((k_mf_bwd_load<LD, T>), dim3(mf_blocks((size_t)v.nb * LD, 4 * FH_BLOCK, 64), v.nmat), dim3(FH_BLOCK), 0, h->stream, S->d_slots + S->slot_off[g], v.F,
+                               Y, v.Yg, S->d_rel, nf, v.n, v.np);
             // z1 -= U12 x2: U12 through its leading-dimension-np view (columns np .. n)
-            const lu_geom g12{np, n, 0, 0};
-            hipLaunchKernelGGL((k_solve_update<LD, T>), dim3((np + 63) / 64, nmat), dim3(FH_BLOCK), 0, h->stream, ptr.u12 + ptr.off[g], Zg, Yg, stride, g12, np, nb, 0, np, cta);
+            const lu_geom g12{v.np, v.n, 0, 0};
+            hipLaunchKernelGGL((k_solve_update<LD, false, T>), dim3((v.np + 63) / 64, v.nmat), dim3(FH_BLOCK), 0, h->stream, ptr.u12 + ptr.off[g], v.Zg, v.Yg, v.stride, g12, v.np, v.nb, 0, v.np, cta);
         }
-        for (int K0 = ((np - 1) / SOLVE_KB) * SOLVE_KB; K0 >= 0; K0 -= SOLVE_KB) {
-            const int kb = std::min(SOLVE_KB / LU_NB, (np - K0) / LU_NB);
-            diag(true, ST, Zg, Yg, stride, gd, K0, kb, nmat, G.inv128 != 0);
+        for (int K0 = ((v.np - 1) / SOLVE_KB) * SOLVE_KB; K0 >= 0; K0 -= SOLVE_KB) {
+            const int kb = std::min(SOLVE_KB / LU_NB, (v.np - K0) / LU_NB);
+            mf_diag<LD, false>(h, cta, true, v, v.Zg, v.Yg, K0, kb);
             if (K0 > 0)
-                hipLaunchKernelGGL((k_solve_update<LD, T>), dim3((K0 + 63) / 64, nmat), dim3(FH_BLOCK), 0, h->stream, ST, Zg, Yg, stride, gu, K0, LU_NB * kb, 0, K0, cta);
+                hipLaunchKernelGGL((k_solve_update<LD, false, T>), dim3((K0 + 63) / 64, v.nmat), dim3(FH_BLOCK), 0, h->stream, v.ST, v.Zg, v.Yg, v.stride, v.gu, K0, LU_NB * kb, 0, K0, cta);
         }
-        hipLaunchKernelGGL((k_mf_scatter<LD, T>), dim3(mf_blocks((size_t)np * LD, 4 * FH_BLOCK, 64), nmat), dim3(FH_BLOCK), 0, h->stream, S->d_slots + S->slot_off[g], F, Yg,
-                           S->d_perm, OUT, out_stride, n);
+        hipLaunchKernelGGL((k_mf_scatter<LD, T>), dim3(mf_blocks((size_t)v.np * LD, 4 * FH_BLOCK, 64), v.nmat), dim3(FH_BLOCK), 0, h->stream, S->d_slots + S->slot_off[g], v.F, v.Yg,
+                           S->d_perm, OUT, out_stride, v.n);
         return 0;
     };
     if ((rc = mf_for_levels(h, S, true, forward_group))) return rc;
@@ -3285,13 +2972,13 @@ static int mf_solve_ld(feasthip_ctx* h, fh_mf_state* S, int nf, const mf_ptrs<T>
 // Adjoint substitution on the same factors (two-sided FEAST on sparse input; complex128 factors).  In plan order the
 // factorisation reads  S = P_1^T L_1 ... P_k^T L_k U  (fronts leaves first; P_f the row permutation of front f's pivot block,
 // L_f the identity but for f's block column [L11; L21], U the fronts' block rows [U11 U12]), so  S^H x = b  is
-//   ascending, leaves first    U^H w = b:   z = [b1; 0] + the children's boundary rows (k_mf_fwd_load WITHOUT a pivot
-//                              permutation, k_mf_fwd_add),  w1 = U11^-H z1  ascending over the pivot blocks,  z2 -= U12^H w1
+//   ascending, leaves first    U^H w = b:   z = [b1; 0] + the children's boundary rows (mf_gather_rhs WITHOUT a pivot
+//                              permutation after it),  w1 = U11^-H z1  ascending over the pivot blocks,  z2 -= U12^H w1
 //                              goes up to the parent
 //   descending, root first     v2 = the parent's rows (k_mf_bwd_load),  v1 = L11^-H (w1 - L21^H v2)  descending,
 //                              x1[p[i]] = v1[i]  LAST (k_mf_adj_unperm_scatter): the children gather un-permuted rows
 // Buffers: Z holds z (its boundary rows are what the parents read), Y holds w1, then [x1; v2]; v1 passes through Z's pivot rows.
-// The forward sweep's maps and batches; k_solve_diag_adj / k_solve_diag_inv_adj / k_solve_update_adj; no atomics.
+// The forward sweep's maps and batches; the ADJ instantiations of k_solve_diag / k_solve_diag_inv / k_solve_update; no atomics.
 template <int LD>
 static int mf_solve_adjoint_ld(feasthip_ctx* h, fh_mf_state* S, int nf, const mf_ptrs<cplx>& ptr, const cplx* RHS, size_t rhs_stride, cplx* OUT, size_t out_stride, int m) {
     typedef cplx T;
@@ -3303,75 +2990,39 @@ static int mf_solve_adjoint_ld(feasthip_ctx* h, fh_mf_state* S, int nf, const mf
     if ((rc = fh_buf(h, "mf_y", rows * LD, &Y))) return rc;
     if ((rc = fh_buf(h, "mf_z", rows * LD, &Z))) return rc;
     fh_prof_begin(h, "mf_solve_adjoint");
-    auto diag = [&](bool upper, T** ST, T* IN, T* OUTp, size_t stride, const lu_geom& gd, int K0, int kb, int nmat, bool inv128) {
-        const dim3 grid(cta, nmat), block(FH_BLOCK);
-        if (inv128) {
-            if (upper) hipLaunchKernelGGL((k_solve_diag_inv_adj<LD, true, T>), grid, block, 0, h->stream, ST, IN, OUTp, stride, gd, K0, kb);
-            else hipLaunchKernelGGL((k_solve_diag_inv_adj<LD, false, T>), grid, block, 0, h->stream, ST, IN, OUTp, stride, gd, K0, kb);
-        } else {
-            if (upper) hipLaunchKernelGGL((k_solve_diag_adj<LD, true, T>), grid, block, 0, h->stream, ST, IN, OUTp, stride, gd, K0, kb);
-            else hipLaunchKernelGGL((k_solve_diag_adj<LD, false, T>), grid, block, 0, h->stream, ST, IN, OUTp, stride, gd, K0, kb);
-        }
-    };
     auto ascending_group = [&](int g) -> int {                   // U^H: leaves first
-        const fh_mf::group& G = P.groups[g];
-        const int F = (int)G.fronts.size(), nmat = F * nf, n = G.n, np = G.np, nb = G.nb;
-        T* Yg = Y + G.rhs_off * (size_t)nf * LD;
-        T* Zg = Z + G.rhs_off * (size_t)nf * LD;
-        const size_t stride = (size_t)n * LD;
-        T** ST = ptr.store + ptr.off[g];
-        const unsigned gb = mf_blocks((size_t)n * LD, 4 * FH_BLOCK, 64);
-        hipLaunchKernelGGL((k_mf_fwd_load<LD, T>), dim3(gb, nmat), dim3(FH_BLOCK), 0, h->stream, RHS, rhs_stride, S->d_perm, S->d_slots + S->slot_off[g], F, Zg, n);
-        for (int side = 0; side < 2; ++side) {
-            const size_t k0 = S->kid_off[side][g], k1 = side == 0 ? S->kid_off[1][g] : S->kid_off[0][g + 1];
-            if (k1 > k0) {
-                int nbmax = 0;
-                for (int c : G.kids[side]) nbmax = std::max(nbmax, P.fronts[c].nbnd);
-                if (nbmax > 0)
-                    hipLaunchKernelGGL((k_mf_fwd_add<LD, T>), dim3(mf_blocks((size_t)nbmax * LD, 4 * FH_BLOCK, 64), (unsigned)(k1 - k0), nf), dim3(FH_BLOCK), 0, h->stream,
-                                       S->d_kids + k0, Z, Zg, S->d_rel, nf, F, n);
-            }
-        }
-        const size_t i32 = fh_mf::inv32_elems(np);
-        const lu_geom gd{n, np, (size_t)n * np, (size_t)n * np + i32};      // rows and columns of the pivot block only
-        for (int K0 = 0; K0 < np; K0 += SOLVE_KB) {
-            const int kb = std::min(SOLVE_KB / LU_NB, (np - K0) / LU_NB);
+        const mf_group_view<T> v = mf_group<LD>(P, ptr, g, nf, Y, Z);
+        mf_gather_rhs<LD>(h, S, g, nf, v, RHS, rhs_stride, Z);
+        for (int K0 = 0; K0 < v.np; K0 += SOLVE_KB) {           // rows and columns of the pivot block only (gd)
+            const int kb = std::min(SOLVE_KB / LU_NB, (v.np - K0) / LU_NB);
             const int r0 = K0 + LU_NB * kb;
-            diag(true, ST, Zg, Yg, stride, gd, K0, kb, nmat, G.inv128 != 0);
-            if (r0 < np)
-                hipLaunchKernelGGL((k_solve_update_adj<LD, T>), dim3((np - r0 + 63) / 64, nmat), dim3(FH_BLOCK), 0, h->stream, ST, Zg, Yg, stride, gd, K0, LU_NB * kb, r0, np, cta);
+            mf_diag<LD, true>(h, cta, true, v, v.Zg, v.Yg, K0, kb);
+            if (r0 < v.np)
+                hipLaunchKernelGGL((k_solve_update<LD, true, T>), dim3((v.np - r0 + 63) / 64, v.nmat), dim3(FH_BLOCK), 0, h->stream, v.ST, v.Zg, v.Yg, v.stride, v.gd, K0, LU_NB * kb, r0, v.np, cta);
         }
-        if (nb > 0) {
+        if (v.nb > 0) {
             // z2 -= U12^H w1: U12 through its leading-dimension-np view (stored columns np .. n are the rows of U12^H), k = np
-            const lu_geom g12{np, n, 0, 0};
-            hipLaunchKernelGGL((k_solve_update_adj<LD, T>), dim3((nb + 63) / 64, nmat), dim3(FH_BLOCK), 0, h->stream, ptr.u12 + ptr.off[g], Zg, Yg, stride, g12, 0, np, np, n, cta);
+            const lu_geom g12{v.np, v.n, 0, 0};
+            hipLaunchKernelGGL((k_solve_update<LD, true, T>), dim3((v.nb + 63) / 64, v.nmat), dim3(FH_BLOCK), 0, h->stream, ptr.u12 + ptr.off[g], v.Zg, v.Yg, v.stride, g12, 0, v.np, v.np, v.n, cta);
         }
         return 0;
     };
     auto descending_group = [&](int g) -> int {                  // L^H and the row permutations: root first
-        const fh_mf::group& G = P.groups[g];
-        const int F = (int)G.fronts.size(), nmat = F * nf, n = G.n, np = G.np, nb = G.nb;
-        T* Yg = Y + G.rhs_off * (size_t)nf * LD;
-        T* Zg = Z + G.rhs_off * (size_t)nf * LD;
-        const size_t stride = (size_t)n * LD;
-        T** ST = ptr.store + ptr.off[g];
-        const size_t i32 = fh_mf::inv32_elems(np);
-        const lu_geom gd{n, np, (size_t)n * np, (size_t)n * np + i32};
-        const lu_geom gu{n, n, (size_t)n * np, (size_t)n * np + i32};
-        if (nb > 0) {
-            hipLaunchKernelGGL((k_mf_bwd_load<LD, T>), dim3(mf_blocks((size_t)nb * LD, 4 * FH_BLOCK, 64), nmat), dim3(FH_BLOCK), 0, h->stream, S->d_slots + S->slot_off[g], F,
-                               Y, Yg, S->d_rel, nf, n, np);
+        const mf_group_view<T> v = mf_group<LD>(P, ptr, g, nf, Y, Z);
+        if (v.nb > 0) {
+            hipLaunchKernelGGL((k_mf_bwd_load<LD, T>), dim3(mf_blocks((size_t)v.nb * LD, 4 * FH_BLOCK, 64), v.nmat), dim3(FH_BLOCK), 0, h->stream, S->d_slots + S->slot_off[g], v.F,
+                               Y, v.Yg, S->d_rel, nf, v.n, v.np);
             // w1 -= L21^H v2: stored rows np .. n of the L block column, columns = pivot rows
-            hipLaunchKernelGGL((k_solve_update_adj<LD, T>), dim3((np + 63) / 64, nmat), dim3(FH_BLOCK), 0, h->stream, ST, Yg, Yg, stride, gu, np, nb, 0, np, cta);
+            hipLaunchKernelGGL((k_solve_update<LD, true, T>), dim3((v.np + 63) / 64, v.nmat), dim3(FH_BLOCK), 0, h->stream, v.ST, v.Yg, v.Yg, v.stride, v.gu, v.np, v.nb, 0, v.np, cta);
         }
-        for (int K0 = ((np - 1) / SOLVE_KB) * SOLVE_KB; K0 >= 0; K0 -= SOLVE_KB) {
-            const int kb = std::min(SOLVE_KB / LU_NB, (np - K0) / LU_NB);
-            diag(false, ST, Yg, Zg, stride, gd, K0, kb, nmat, G.inv128 != 0);
+        for (int K0 = ((v.np - 1) / SOLVE_KB) * SOLVE_KB; K0 >= 0; K0 -= SOLVE_KB) {
+            const int kb = std::min(SOLVE_KB / LU_NB, (v.np - K0) / LU_NB);
+            mf_diag<LD, true>(h, cta, false, v, v.Yg, v.Zg, K0, kb);
             if (K0 > 0)
-                hipLaunchKernelGGL((k_solve_update_adj<LD, T>), dim3((K0 + 63) / 64, nmat), dim3(FH_BLOCK), 0, h->stream, ST, Yg, Zg, stride, gd, K0, LU_NB * kb, 0, K0, cta);
+                hipLaunchKernelGGL((k_solve_update<LD, true, T>), dim3((K0 + 63) / 64, v.nmat), dim3(FH_BLOCK), 0, h->stream, v.ST, v.Yg, v.Zg, v.stride, v.gd, K0, LU_NB * kb, 0, K0, cta);
         }
-        hipLaunchKernelGGL((k_mf_adj_unperm_scatter<LD, T>), dim3(mf_blocks((size_t)np * LD, 4 * FH_BLOCK, 64), nmat), dim3(FH_BLOCK), 0, h->stream, ptr.piv + ptr.off[g],
-                           S->d_slots + S->slot_off[g], F, Zg, Yg, S->d_perm, OUT, out_stride, n, np);
+        hipLaunchKernelGGL((k_mf_adj_unperm_scatter<LD, T>), dim3(mf_blocks((size_t)v.np * LD, 4 * FH_BLOCK, 64), v.nmat), dim3(FH_BLOCK), 0, h->stream, ptr.piv + ptr.off[g],
+                           S->d_slots + S->slot_off[g], v.F, v.Zg, v.Yg, S->d_perm, OUT, out_stride, v.n, v.np);
         return 0;
     };
     if ((rc = mf_for_levels(h, S, true, ascending_group))) return rc;
