@@ -14,6 +14,7 @@
 // padded, one set per node.  No atomics on data: the Gram partials are summed in slot order.
 #include "fh_common.hpp"
 #include "fh_kernels.hpp"
+#include "fh_device.hpp"
 #include <algorithm>
 
 typedef double bc_v4d __attribute__((ext_vector_type(4)));
@@ -117,20 +118,13 @@ static void bcocg_gram_launch(const cplx* X, size_t xs, const cplx* Y, size_t ys
 }
 void fh_launch_bcocg_gram(const cplx* X, size_t xs, const cplx* Y, size_t ys, int N, int ld, int nodes, cplx* work, cplx* outH,
                           cplx* outT, const int* stop, hipStream_t st) {
-    if (ld == 16) bcocg_gram_launch<16>(X, xs, Y, ys, N, nodes, work, outH, outT, stop, st);
-    else if (ld == 32) bcocg_gram_launch<32>(X, xs, Y, ys, N, nodes, work, outH, outT, stop, st);
-    else bcocg_gram_launch<64>(X, xs, Y, ys, N, nodes, work, outH, outT, stop, st);
+    fh_with_ld(ld, [&](auto L) { bcocg_gram_launch<decltype(L)::value>(X, xs, Y, ys, N, nodes, work, outH, outT, stop, st); });
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
 // k_bcocg_small: the n x n algebra of one node on one workgroup; the two working matrices (LD x LD complex128 each: 128 KiB
 // at LD = 64) live in LDS, everything else in the node's global slots.
 // ---------------------------------------------------------------------------------------------------------------------
-__device__ inline double bc_shfl_xor(double v, int o) {
-    return __hiloint2double(__shfl_xor(__double2hiint(v), o), __shfl_xor(__double2loint(v), o));
-}
-__device__ inline bool bc_finite(cplx a) { return isfinite(a.x) && isfinite(a.y); }
-
 // out (global, LD x LD row-major, zero outside ni x nj) = op(A) B with A, B in LDS (stride LD); op = transpose when ta
 template <int LD>
 __device__ inline void bc_mm(cplx* __restrict__ out, const cplx* A, bool ta, const cplx* B, int ni, int nk, int nj, cplx scale) {
@@ -225,7 +219,7 @@ __device__ __forceinline__ void bc_chol_zeta(cplx* A, cplx* B, int n, double* ds
     for (int e = t; e < n * n; e += blockDim.x) {
         const int i = e / n, j = e % n;
         const cplx v = A[i * LD + j];
-        if (!bc_finite(v)) *bad = 1;
+        if (!fh_finite(v)) *bad = 1;
         const double s = 1.0 / (dsc[i] * dsc[j]);
         A[i * LD + j] = cmake(v.x * s, v.y * s);
     }
@@ -360,7 +354,7 @@ __global__ __launch_bounds__(FH_BC_SMALL_THREADS) void k_bcocg_small(fh_bcocg_ar
         bc_load<LD>(Am, a.GA + mo);
         bc_load<LD>(Bm, a.T + mo);
         __syncthreads();
-        for (int e = t; e < n * n; e += blockDim.x) if (!bc_finite(Am[(e / n) * LD + e % n]) || !bc_finite(Bm[(e / n) * LD + e % n])) bad = 1;
+        for (int e = t; e < n * n; e += blockDim.x) if (!fh_finite(Am[(e / n) * LD + e % n]) || !fh_finite(Bm[(e / n) * LD + e % n])) bad = 1;
         __syncthreads();
         if (!bad) bc_lu_solve<LD>(Am, Bm, n, n, &bad, &piv_row, &amax_s, dsc);
         __syncthreads();
@@ -391,7 +385,7 @@ __global__ __launch_bounds__(FH_BC_SMALL_THREADS) void k_bcocg_small(fh_bcocg_ar
     bc_load<LD>(Bm, a.U + mo);                                             // beta = T^-1 U
     bc_load<LD>(Am, a.T + mo);
     __syncthreads();
-    for (int e = t; e < n * n; e += blockDim.x) if (!bc_finite(Am[(e / n) * LD + e % n]) || !bc_finite(Bm[(e / n) * LD + e % n])) bad = 1;
+    for (int e = t; e < n * n; e += blockDim.x) if (!fh_finite(Am[(e / n) * LD + e % n]) || !fh_finite(Bm[(e / n) * LD + e % n])) bad = 1;
     __syncthreads();
     if (!bad) bc_lu_solve<LD>(Am, Bm, n, n, &bad, &piv_row, &amax_s, dsc);
     __syncthreads();
@@ -447,9 +441,7 @@ static void bcocg_small_ld(const fh_bcocg_args& a, int phase, hipStream_t st) {
     else bcocg_small_launch<LD, 2>(a, st);
 }
 void fh_launch_bcocg_small(const fh_bcocg_args& a, int ld, int phase, hipStream_t st) {
-    if (ld == 16) bcocg_small_ld<16>(a, phase, st);
-    else if (ld == 32) bcocg_small_ld<32>(a, phase, st);
-    else bcocg_small_ld<64>(a, phase, st);
+    fh_with_ld(ld, [&](auto L) { bcocg_small_ld<decltype(L)::value>(a, phase, st); });
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -559,7 +551,5 @@ static void bcocg_update_ld(const fh_bcocg_args& a, int phase, hipStream_t st) {
     else hipLaunchKernelGGL((k_bcocg_update<LD, 3>), dim3(nb), dim3(256), 0, st, a);
 }
 void fh_launch_bcocg_update(const fh_bcocg_args& a, int ld, int phase, hipStream_t st) {
-    if (ld == 16) bcocg_update_ld<16>(a, phase, st);
-    else if (ld == 32) bcocg_update_ld<32>(a, phase, st);
-    else bcocg_update_ld<64>(a, phase, st);
+    fh_with_ld(ld, [&](auto L) { bcocg_update_ld<decltype(L)::value>(a, phase, st); });
 }

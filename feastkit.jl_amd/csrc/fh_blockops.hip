@@ -8,6 +8,7 @@
 #include <stdlib.h>
 #include "fh_common.hpp"
 #include "fh_kernels.hpp"
+#include "fh_device.hpp"
 #include "fh_cholqr.hpp"
 #include "fh_knobs.hpp"
 
@@ -178,16 +179,8 @@ __global__ __launch_bounds__(FH_BLOCK) void k_sum_partials(const cplx* __restric
 void fh_launch_dot_cols(const cplx* U, const cplx* V, int N, int ld, cplx* work, cplx* out, hipStream_t st) {
     int nblk = fh_vec_nblk(N, ld);
     size_t total = (size_t)N * ld;
-    if (ld == 16) {
-        hipLaunchKernelGGL((k_dot_cols<16>), dim3(nblk), dim3(FH_BLOCK), 0, st, U, V, total, work);
-        hipLaunchKernelGGL((k_sum_partials<16>), dim3(1), dim3(FH_BLOCK), 0, st, work, nblk, out);
-    } else if (ld == 32) {
-        hipLaunchKernelGGL((k_dot_cols<32>), dim3(nblk), dim3(FH_BLOCK), 0, st, U, V, total, work);
-        hipLaunchKernelGGL((k_sum_partials<32>), dim3(1), dim3(FH_BLOCK), 0, st, work, nblk, out);
-    } else {
-        hipLaunchKernelGGL((k_dot_cols<64>), dim3(nblk), dim3(FH_BLOCK), 0, st, U, V, total, work);
-        hipLaunchKernelGGL((k_sum_partials<64>), dim3(1), dim3(FH_BLOCK), 0, st, work, nblk, out);
-    }
+    FH_LAUNCH_LD(ld, k_dot_cols, dim3(nblk), dim3(FH_BLOCK), st, U, V, total, work);
+    FH_LAUNCH_LD(ld, k_sum_partials, dim3(1), dim3(FH_BLOCK), st, work, nblk, out);
 }
 
 __global__ __launch_bounds__(FH_BLOCK) void k_scale_cols(cplx* __restrict__ X, const cplx* __restrict__ s,
@@ -384,9 +377,7 @@ static void gram_launch(const cplx* X, const cplx* Y, int N, int bilinear, cplx*
 }
 void fh_launch_gram(const cplx* X, const cplx* Y, int N, int ld, int bilinear, cplx* work, cplx* G,
                     hipStream_t st, const int* skip) {
-    if (ld == 16) gram_launch<16>(X, Y, N, bilinear, work, G, st, skip);
-    else if (ld == 32) gram_launch<32>(X, Y, N, bilinear, work, G, st, skip);
-    else gram_launch<64>(X, Y, N, bilinear, work, G, st, skip);
+    fh_with_ld(ld, [&](auto L) { gram_launch<decltype(L)::value>(X, Y, N, bilinear, work, G, st, skip); });
 }
 
 // ---------------------------------------------------------------------------------------
@@ -475,17 +466,15 @@ void fh_launch_small_matmul(const cplx* Q, const cplx* V, int N, int ld, cplx* X
     if (!fh_knob::small_matmul_valu()) {
         const int rb = 16 * (4 / (ld / 16));
         const int nb = std::min((N + rb - 1) / rb, 2048);
-        if (ld == 16) hipLaunchKernelGGL((k_small_matmul_mfma<16>), dim3(nb), dim3(FH_BLOCK), 0, st, Q, V, N, Xout, skip);
-        else if (ld == 32) hipLaunchKernelGGL((k_small_matmul_mfma<32>), dim3(nb), dim3(FH_BLOCK), 0, st, Q, V, N, Xout, skip);
-        else hipLaunchKernelGGL((k_small_matmul_mfma<64>), dim3(nb), dim3(FH_BLOCK), 0, st, Q, V, N, Xout, skip);
+        FH_LAUNCH_LD(ld, k_small_matmul_mfma, dim3(nb), dim3(FH_BLOCK), st, Q, V, N, Xout, skip);
         return;
     }
     int rpb = FH_BLOCK / ld;
     int nblk = std::min((N + rpb - 1) / rpb, 2048);
     size_t shm = ((size_t)ld * ld + FH_BLOCK) * sizeof(cplx);
-    if (ld == 16) hipLaunchKernelGGL((k_small_matmul<16>), dim3(nblk), dim3(FH_BLOCK), shm, st, Q, V, N, Xout, skip);
-    else if (ld == 32) hipLaunchKernelGGL((k_small_matmul<32>), dim3(nblk), dim3(FH_BLOCK), shm, st, Q, V, N, Xout, skip);
-    else hipLaunchKernelGGL((k_small_matmul<64>), dim3(nblk), dim3(FH_BLOCK), shm, st, Q, V, N, Xout, skip);
+    fh_with_ld(ld, [&](auto L) {
+        hipLaunchKernelGGL((k_small_matmul<decltype(L)::value>), dim3(nblk), dim3(FH_BLOCK), shm, st, Q, V, N, Xout, skip);
+    });
 }
 
 // ---------------------------------------------------------------------------------------
@@ -695,9 +684,7 @@ static void mgs_run_ld(const fh_mgs_args& a, hipStream_t st) {
 }
 
 void fh_mgs_run(const fh_mgs_args& a, hipStream_t st) {
-    if (a.ld == 16) mgs_run_ld<16>(a, st);
-    else if (a.ld == 32) mgs_run_ld<32>(a, st);
-    else mgs_run_ld<64>(a, st);
+    fh_with_ld(a.ld, [&](auto L) { mgs_run_ld<decltype(L)::value>(a, st); });
 }
 
 // ---------------------------------------------------------------------------------------
@@ -872,7 +859,7 @@ __global__ __launch_bounds__(FH_BLOCK) void k_pchol_stage(const cplx* __restrict
     for (int e = t; e < LD * LD; e += FH_BLOCK) {
         if (!sm.alive[e % LD] || !sm.alive[e / LD]) continue;
         const cplx v = G[e];
-        bad |= !(isfinite(v.x) && isfinite(v.y));
+        bad |= !fh_finite(v);
         imag |= v.y != 0.0;
     }
     bad = __syncthreads_or(bad);
@@ -907,7 +894,5 @@ static void pchol_launch(const cplx* G, int m, int refine, double window, double
 }
 void fh_launch_pchol_stage(const cplx* G, int m, int ld, int refine, double window, double thr, double ref_scale, int* istate,
                            double* dstate, cplx* Rinv, hipStream_t st) {
-    if (ld == 16) pchol_launch<16>(G, m, refine, window, thr, ref_scale, istate, dstate, Rinv, st);
-    else if (ld == 32) pchol_launch<32>(G, m, refine, window, thr, ref_scale, istate, dstate, Rinv, st);
-    else pchol_launch<64>(G, m, refine, window, thr, ref_scale, istate, dstate, Rinv, st);
+    fh_with_ld(ld, [&](auto L) { pchol_launch<decltype(L)::value>(G, m, refine, window, thr, ref_scale, istate, dstate, Rinv, st); });
 }

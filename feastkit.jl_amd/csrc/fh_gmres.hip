@@ -285,37 +285,30 @@ __global__ __launch_bounds__(GM_BLOCK) void k_gm_cycle_steps(const int* kdim, in
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
-#define GM_DISPATCH(ld, KERNEL, grid, st, ...)                                                        \
-    do {                                                                                               \
-        if ((ld) == 16) hipLaunchKernelGGL((KERNEL<16>), grid, dim3(GM_BLOCK), 0, st, __VA_ARGS__);     \
-        else if ((ld) == 32) hipLaunchKernelGGL((KERNEL<32>), grid, dim3(GM_BLOCK), 0, st, __VA_ARGS__); \
-        else hipLaunchKernelGGL((KERNEL<64>), grid, dim3(GM_BLOCK), 0, st, __VA_ARGS__);                \
-    } while (0)
-
 int fh_gm_nchunk(int k) { return (k + 1 + GM_CHUNK - 1) / GM_CHUNK; }
 size_t fh_gm_partial_elems(int mr, int nblk, int nodes, int ld) { return (size_t)nodes * fh_gm_nchunk(mr) * nblk * GM_CHUNK * ld; }
 
 void fh_launch_gm_orthogonalize(const fh_gmres_args& a, int ld, int k, int nblk, int nodes, hipStream_t st) {
     const int nchunk = fh_gm_nchunk(k);
     for (int pass = 0; pass < 2; ++pass) {
-        GM_DISPATCH(ld, k_gm_dots, dim3(nblk, nodes, nchunk), st, a, k);
-        GM_DISPATCH(ld, k_gm_fin_h, dim3(nodes), st, a, k, nblk, nchunk, pass);
-        GM_DISPATCH(ld, k_gm_update, dim3(nblk, nodes), st, a, k, pass);
+        FH_LAUNCH_LD(ld, k_gm_dots, dim3(nblk, nodes, nchunk), dim3(GM_BLOCK), st, a, k);
+        FH_LAUNCH_LD(ld, k_gm_fin_h, dim3(nodes), dim3(GM_BLOCK), st, a, k, nblk, nchunk, pass);
+        FH_LAUNCH_LD(ld, k_gm_update, dim3(nblk, nodes), dim3(GM_BLOCK), st, a, k, pass);
     }
 }
 void fh_launch_gm_start(const fh_gmres_args& a, int ld, int nblk_norm, int nodes, int first, double rtol, double atol, int m, hipStream_t st) {
-    GM_DISPATCH(ld, k_gm_start, dim3(nodes), st, a, nblk_norm, first, rtol, atol, m);
+    FH_LAUNCH_LD(ld, k_gm_start, dim3(nodes), dim3(GM_BLOCK), st, a, nblk_norm, first, rtol, atol, m);
 }
 void fh_launch_gm_givens(const fh_gmres_args& a, int ld, int k, int nblk, int nodes, hipStream_t st) {
-    GM_DISPATCH(ld, k_gm_givens, dim3(nodes), st, a, k, nblk);
+    FH_LAUNCH_LD(ld, k_gm_givens, dim3(nodes), dim3(GM_BLOCK), st, a, k, nblk);
 }
 void fh_launch_gm_scale_store(const fh_gmres_args& a, int ld, const cplx* src, size_t src_node_stride, int dst_index, int nblk, int nodes,
                               hipStream_t st) {
-    GM_DISPATCH(ld, k_gm_scale_store, dim3(nblk, nodes), st, a, src, src_node_stride, dst_index);
+    FH_LAUNCH_LD(ld, k_gm_scale_store, dim3(nblk, nodes), dim3(GM_BLOCK), st, a, src, src_node_stride, dst_index);
 }
 void fh_launch_gm_finish_cycle(const fh_gmres_args& a, int ld, cplx* X, size_t x_node_stride, int kmax, int nblk, int nodes,
                                unsigned long long* steps_ran, hipStream_t st) {
-    GM_DISPATCH(ld, k_gm_solve_y, dim3((nodes * ld + GM_BLOCK - 1) / GM_BLOCK), st, a, nodes);
-    GM_DISPATCH(ld, k_gm_xupdate, dim3(nblk, nodes), st, a, X, x_node_stride, kmax);
+    FH_LAUNCH_LD(ld, k_gm_solve_y, dim3((nodes * ld + GM_BLOCK - 1) / GM_BLOCK), dim3(GM_BLOCK), st, a, nodes);
+    FH_LAUNCH_LD(ld, k_gm_xupdate, dim3(nblk, nodes), dim3(GM_BLOCK), st, a, X, x_node_stride, kmax);
     hipLaunchKernelGGL(k_gm_cycle_steps, dim3(1), dim3(GM_BLOCK), 0, st, a.kdim, nodes * ld, steps_ran);
 }

@@ -1,6 +1,27 @@
 // fh_kernels.hpp -- argument structs and launcher prototypes shared by the .hip units.
 #pragma once
 #include "fh_common.hpp"
+#include <type_traits>
+
+// ---- launch dispatch: the panel width (16 | 32 | 64) and the panel precision (64 | 32) as compile-time values -------------
+//   fh_with_ld(ld, [&](auto L) { constexpr int LD = decltype(L)::value; hipLaunchKernelGGL((k_x<LD>), ...); });
+//   fh_with_prec(prec, [&](auto ct) { using CT = decltype(ct); ... });
+template <typename F> inline void fh_with_ld(int ld, F&& f) {
+    if (ld == 16) f(std::integral_constant<int, 16>{});
+    else if (ld == 32) f(std::integral_constant<int, 32>{});
+    else f(std::integral_constant<int, 64>{});
+}
+template <typename F> inline void fh_with_prec(int prec, F&& f) {
+    if (prec == 32) f(cplxf{});
+    else f(cplx{});
+}
+// the two common launches: KERNEL<LD> and KERNEL<CT, LD> with the given grid, block and arguments, no dynamic LDS
+#define FH_LAUNCH_LD(ld, KERNEL, grid, block, st, ...) \
+    fh_with_ld(ld, [&](auto L) { hipLaunchKernelGGL((KERNEL<decltype(L)::value>), grid, block, 0, st, __VA_ARGS__); })
+#define FH_LAUNCH_PREC_LD(prec, ld, KERNEL, grid, block, st, ...)                                                      \
+    fh_with_prec(prec, [&](auto ct) {                                                                                   \
+        fh_with_ld(ld, [&](auto L) { hipLaunchKernelGGL((KERNEL<decltype(ct), decltype(L)::value>), grid, block, 0, st, __VA_ARGS__); }); \
+    })
 
 // ---- sparse operator -------------------------------------------------------------------
 // Panel pointers are void*: complex128 panels when prec == 64, complex64 when prec == 32.

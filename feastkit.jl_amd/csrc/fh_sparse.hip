@@ -14,6 +14,7 @@
 // Every reduction (dots, norms) accumulates in fp64 whatever the panel precision.
 #include "fh_common.hpp"
 #include "fh_kernels.hpp"
+#include "fh_device.hpp"
 
 #define FH_BLOCK 256
 #define FH_FIN_BLOCK 1024
@@ -118,6 +119,29 @@ template <typename CT> __device__ __forceinline__ CT fh_czero();
 template <> __device__ __forceinline__ cplx fh_czero<cplx>() { return cmake(0, 0); }
 template <> __device__ __forceinline__ cplxf fh_czero<cplxf>() { return cmakef(0.f, 0.f); }
 
+// Node prologue of k_spmm and k_spmm_row.  An inactive node is skipped (true): the first W threads clear this workgroup's partial
+// row of the node.  Otherwise the first thread of the grid adds to the profiling counters: one matrix sweep per active node
+// plus (vector passes) x (active columns) column sweeps.  (The arguments come by value: behind a reference both kernels
+// compile to other registers.  k_spmm_lds clears and counts for all nodes at once, before its row blocks.)
+template <int W>
+__device__ __forceinline__ bool fh_spmm_skip_node(const fh_spmm_args a, int node, size_t pbase) {
+    const int t = threadIdx.x;
+    if (a.node_active && a.node_active[node] == 0) {
+        if (a.dot_mode != 0 && t < W) {
+            if (a.partial1) a.partial1[pbase + t] = cmake(0, 0);
+            if (a.partial2) a.partial2[pbase + t] = cmake(0, 0);
+        }
+        return true;
+    }
+    if (a.counters && blockIdx.x == 0 && t == 0) {
+        const int cols = a.node_active ? a.node_active[node] : a.m;
+        const int passes = (a.dot_mode == 1 || a.Bvec) ? 3 : 2;
+        atomicAdd(a.counters + 0, 1ull);
+        atomicAdd(a.counters + 1, (unsigned long long)(cols * passes));
+    }
+    return false;
+}
+
 // SCALED: the lazy start's first product (fh_spmm_args::colscale); its own instantiation -- the two extra registers of the
 // column factor spill 6-14 VGPRs at this kernel's 128-VGPR budget
 template <typename CT, typename VT, int LD, bool BIDENT, bool SCALED = false>
@@ -145,21 +169,7 @@ __global__ __launch_bounds__(FH_BLOCK, 4) void k_spmm(fh_spmm_args a) {
 
     for (int node = 0; node < a.nodes; ++node) {
         const size_t pbase = ((size_t)node * nprow + prow) * LD + ct * 16;
-        if (a.node_active && a.node_active[node] == 0) {
-            if (a.dot_mode != 0 && t < 16) {
-                if (a.partial1) a.partial1[pbase + t] = cmake(0, 0);
-                if (a.partial2) a.partial2[pbase + t] = cmake(0, 0);
-            }
-            continue;
-        }
-        if (a.counters && blockIdx.x == 0 && t == 0) {
-            // measurement support: one matrix sweep per active node plus
-            // (vector passes) x (active columns) column sweeps
-            const int cols = a.node_active ? a.node_active[node] : a.m;
-            const int passes = (a.dot_mode == 1 || a.Bvec) ? 3 : 2;
-            atomicAdd(a.counters + 0, 1ull);
-            atomicAdd(a.counters + 1, (unsigned long long)(cols * passes));
-        }
+        if (fh_spmm_skip_node<16>(a, node, pbase)) continue;
         const CT* __restrict__ X = (const CT*)a.X + (size_t)node * a.x_node_stride;
         CT* __restrict__ Y = (CT*)a.Y + (size_t)node * a.y_node_stride;
         const CT* __restrict__ Bv = a.Bvec ? (const CT*)a.Bvec + (size_t)node * a.b_node_stride : nullptr;
@@ -371,19 +381,7 @@ __global__ __launch_bounds__(FH_ROW_THREADS, FH_ROW_WAVES) void k_spmm_row(fh_sp
 
     for (int node = 0; node < a.nodes; ++node) {
         const size_t pbase = ((size_t)node * nprow + prow) * LD;
-        if (a.node_active && a.node_active[node] == 0) {
-            if (a.dot_mode != 0 && threadIdx.x < LD) {
-                if (a.partial1) a.partial1[pbase + threadIdx.x] = cmake(0, 0);
-                if (a.partial2) a.partial2[pbase + threadIdx.x] = cmake(0, 0);
-            }
-            continue;
-        }
-        if (a.counters && blockIdx.x == 0 && threadIdx.x == 0) {
-            const int cols = a.node_active ? a.node_active[node] : a.m;
-            const int passes = (a.dot_mode == 1 || a.Bvec) ? 3 : 2;
-            atomicAdd(a.counters + 0, 1ull);
-            atomicAdd(a.counters + 1, (unsigned long long)(cols * passes));
-        }
+        if (fh_spmm_skip_node<LD>(a, node, pbase)) continue;
         const CT* __restrict__ X = (const CT*)a.X + (size_t)node * a.x_node_stride;
         CT* __restrict__ Y = (CT*)a.Y + (size_t)node * a.y_node_stride;
         const CT* __restrict__ Bv = a.Bvec ? (const CT*)a.Bvec + (size_t)node * a.b_node_stride : nullptr;
@@ -740,18 +738,6 @@ static void launch_spmm_ld(const fh_spmm_args& a, bool bident, int nblk, hipStre
     else
         hipLaunchKernelGGL((k_spmm<CT, VT, LD, false>), grid, block, 0, st, a);
 }
-template <typename CT>
-static void launch_spmm_ct(const fh_spmm_args& a, int ld, bool is_complex, bool bident, int nblk, hipStream_t st) {
-    if (is_complex) {
-        if (ld == 16) launch_spmm_ld<CT, cplx, 16>(a, bident, nblk, st);
-        else if (ld == 32) launch_spmm_ld<CT, cplx, 32>(a, bident, nblk, st);
-        else launch_spmm_ld<CT, cplx, 64>(a, bident, nblk, st);
-    } else {
-        if (ld == 16) launch_spmm_ld<CT, double, 16>(a, bident, nblk, st);
-        else if (ld == 32) launch_spmm_ld<CT, double, 32>(a, bident, nblk, st);
-        else launch_spmm_ld<CT, double, 64>(a, bident, nblk, st);
-    }
-}
 // workgroups of the row-per-wave kernel: 8 XCD groups x (32 CUs x resident workgroups per CU), capped so that a band
 // step never exceeds the rows of a slice
 int fh_spmm_row_grid(int N) {
@@ -774,32 +760,33 @@ void fh_launch_spmm(const fh_spmm_args& a, int ld, bool is_complex, bool bident,
 #define FH_ROW_LAUNCH(CT_, BI_) \
         do { if (a.uniform_coef) hipLaunchKernelGGL((k_spmm_row<CT_, BI_, true>), grid, block, 0, st, a); \
              else hipLaunchKernelGGL((k_spmm_row<CT_, BI_, false>), grid, block, 0, st, a); } while (0)
-        if (a.prec == 32) { if (bident) FH_ROW_LAUNCH(cplxf, true); else FH_ROW_LAUNCH(cplxf, false); }
-        else { if (bident) FH_ROW_LAUNCH(cplx, true); else FH_ROW_LAUNCH(cplx, false); }
+        fh_with_prec(a.prec, [&](auto ct) {
+            using CT = decltype(ct);
+            if (bident) FH_ROW_LAUNCH(CT, true); else FH_ROW_LAUNCH(CT, false);
+        });
 #undef FH_ROW_LAUNCH
         return;
     }
     if (a.prec == 64 && a.lcol) {          // renumbered matrix, complex128 panels: the LDS-window kernel
-        if (is_complex) {
-            if (ld == 16) launch_spmm_lds<cplx, 16>(a, bident, st);
-            else if (ld == 32) launch_spmm_lds<cplx, 32>(a, bident, st);
-            else launch_spmm_lds<cplx, 64>(a, bident, st);
-        } else {
-            if (ld == 16) launch_spmm_lds<double, 16>(a, bident, st);
-            else if (ld == 32) launch_spmm_lds<double, 32>(a, bident, st);
-            else launch_spmm_lds<double, 64>(a, bident, st);
-        }
+        fh_with_ld(ld, [&](auto L) {
+            if (is_complex) launch_spmm_lds<cplx, decltype(L)::value>(a, bident, st);
+            else launch_spmm_lds<double, decltype(L)::value>(a, bident, st);
+        });
         return;
     }
-    if (a.prec == 32) launch_spmm_ct<cplxf>(a, ld, is_complex, bident, nblk, st);
-    else launch_spmm_ct<cplx>(a, ld, is_complex, bident, nblk, st);
+    fh_with_prec(a.prec, [&](auto ct) {
+        fh_with_ld(ld, [&](auto L) {
+            if (is_complex) launch_spmm_ld<decltype(ct), cplx, decltype(L)::value>(a, bident, nblk, st);
+            else launch_spmm_ld<decltype(ct), double, decltype(L)::value>(a, bident, nblk, st);
+        });
+    });
 }
 
 // ------------------------------------------------------------------------------------
 // Krylov vector kernels.  Flat element index over the N*LD panel, grid-stride with a stride
 // that is a multiple of LD so a thread always sees the same column.
 // ------------------------------------------------------------------------------------
-template <typename CT, int LD>
+template <int LD>
 __global__ __launch_bounds__(FH_BLOCK) void k_init_guess(fh_vec_args a) {
     // X0[i,c] = Q[i,c] / (z_node - lambda_c)   (lambda == nullptr -> zero guess); always fp64
     const int node = blockIdx.y;
@@ -992,8 +979,6 @@ __device__ __forceinline__ void fh_sum_partials2(const cplx* partial1, const cpl
     }
     __syncthreads();
 }
-
-__device__ __forceinline__ bool fh_finite(cplx a) { return isfinite(a.x) && isfinite(a.y); }
 
 // mode 0: BiCGStab (rho = ||r||^2 from partial2); mode 1: COCG (rho = r^T r from partial1)
 template <int LD>
@@ -1410,47 +1395,34 @@ void fh_fused_vec_geometry(int N, int ld, int half, int* nblk, int* nseg, int* p
     *nblk = (int)g; *nseg = (int)segs; *per_thread = (int)e;
 }
 
+// ---- the two steps k_fused_fin and k_shift_fin share ----------------------------------------------------------------------
+// Sums the partial rows of one 16-column tile on FH_FIN_BLOCK threads: 64 row groups x 16 columns; every thread has all its
+// loads in flight at once (the rows were written by other XCDs: each load is a trip to the Infinity Cache), summed in a
+// fixed order -- the thread's own rows, the four row groups of a wave (lanes c16, c16 + 16, + 32, + 48), then the 16 waves
+// through LDS.  base_vec / base_op: the offset of this thread's column in row 0 of the vector kernel's partials (rho, rr) and
+// of the SpMM's (sig, kap; read when with_op).  Ends with the barrier after which red holds the 16 waves' sums; thread t < 16
+// then takes the totals of column t of the tile with fh_fin_totals: w = { rho.x, rho.y, rr, sig.x, sig.y, kap.x, kap.y }.
 template <int LD>
-__global__ __launch_bounds__(FH_FIN_BLOCK) void k_fused_fin(fh_fused_fin_args a) {
-    // grid (LD / 16, nodes): one workgroup sums the partial rows of one 16-column tile of one node.  64 row groups x 16
-    // columns; every thread has all its loads in flight at once (the rows were written by other XCDs: each load is a
-    // trip to the Infinity Cache), summed in a fixed order.
-    __shared__ double red[FH_FIN_BLOCK / 64][16][8];
-    __shared__ int cnt_active, cnt_accum;
-    const int node = blockIdx.y, tile = blockIdx.x, t = threadIdx.x;
-    const int lane = t & 63, wave = t >> 6;
-    const int c16 = lane & 15, g = wave * 4 + (lane >> 4);   // 64 row groups x 16 columns
-    const int c = tile * 16 + c16;
-    const int i = node * LD + c;
-    if (a.s.node_active[node] == 0) {                   // (node_active is only rewritten by the node's LAST tile workgroup, at its end)
-        if (!a.final_check) {
-            if (t < 16) a.s.accum[i] = 0;
-            if (tile == 0 && t == 0) a.s.node_accum[node] = 0;
-        }
-        return;
-    }
-    if (t == 0) { cnt_active = 0; cnt_accum = 0; }
+__device__ __forceinline__ void fh_fin_sum_rows(const cplx* rho, const cplx* rr, size_t base_vec, int nblk_vec, const cplx* sig,
+                                                const cplx* kap, size_t base_op, int nblk_op, bool with_op,
+                                                double (&red)[FH_FIN_BLOCK / 64][16][8]) {
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int g = wave * 4 + (lane >> 4);
     double v[8];
 #pragma unroll
     for (int q = 0; q < 8; ++q) v[q] = 0.0;
-    {
-        const size_t base = (size_t)node * a.nblk_vec * LD + c;
 #pragma unroll 4
-        for (int b = g; b < a.nblk_vec; b += 64) {
-            const cplx r1 = a.rho[base + (size_t)b * LD], r2 = a.rr[base + (size_t)b * LD];
-            v[0] += r1.x; v[1] += r1.y; v[2] += r2.x;
-        }
+    for (int b = g; b < nblk_vec; b += 64) {
+        const cplx r1 = rho[base_vec + (size_t)b * LD], r2 = rr[base_vec + (size_t)b * LD];
+        v[0] += r1.x; v[1] += r1.y; v[2] += r2.x;
     }
-    if (!a.final_check) {
-        const size_t base = (size_t)node * a.nblk_op * LD + c;
+    if (with_op) {
 #pragma unroll 4
-        for (int b = g; b < a.nblk_op; b += 64) {
-            const size_t o = base + (size_t)b * LD;
-            const cplx s1 = a.sig[o], s3 = a.kap[o];
+        for (int b = g; b < nblk_op; b += 64) {
+            const cplx s1 = sig[base_op + (size_t)b * LD], s3 = kap[base_op + (size_t)b * LD];
             v[3] += s1.x; v[4] += s1.y; v[5] += s3.x; v[6] += s3.y;
         }
     }
-    // the four row groups of a wave (lanes c16, c16 + 16, + 32, + 48), then the 16 waves through LDS in a fixed order
 #pragma unroll
     for (int q = 0; q < 7; ++q) {
         v[q] += __shfl_xor(v[q], 16);
@@ -1461,15 +1433,39 @@ __global__ __launch_bounds__(FH_FIN_BLOCK) void k_fused_fin(fh_fused_fin_args a)
         for (int q = 0; q < 7; ++q) red[wave][lane][q] = v[q];
     }
     __syncthreads();
+}
+__device__ __forceinline__ void fh_fin_totals(const double (&red)[FH_FIN_BLOCK / 64][16][8], double (&w)[7]) {
+    const int t = threadIdx.x;
+#pragma unroll
+    for (int q = 0; q < 7; ++q) {
+        double sacc = red[0][t][q];
+#pragma unroll
+        for (int k = 1; k < FH_FIN_BLOCK / 64; ++k) sacc += red[k][t][q];
+        w[q] = sacc;
+    }
+}
+
+template <int LD>
+__global__ __launch_bounds__(FH_FIN_BLOCK) void k_fused_fin(fh_fused_fin_args a) {
+    // grid (LD / 16, nodes): one workgroup sums the partial rows of one 16-column tile of one node (fh_fin_sum_rows)
+    __shared__ double red[FH_FIN_BLOCK / 64][16][8];
+    __shared__ int cnt_active, cnt_accum;
+    const int node = blockIdx.y, tile = blockIdx.x, t = threadIdx.x;
+    const int c = tile * 16 + (t & 15);
+    const int i = node * LD + c;
+    if (a.s.node_active[node] == 0) {                   // (node_active is only rewritten by the node's LAST tile workgroup, at its end)
+        if (!a.final_check) {
+            if (t < 16) a.s.accum[i] = 0;
+            if (tile == 0 && t == 0) a.s.node_accum[node] = 0;
+        }
+        return;
+    }
+    if (t == 0) { cnt_active = 0; cnt_accum = 0; }
+    fh_fin_sum_rows<LD>(a.rho, a.rr, (size_t)node * a.nblk_vec * LD + c, a.nblk_vec, a.sig, a.kap, (size_t)node * a.nblk_op * LD + c,
+                        a.nblk_op, !a.final_check, red);
     if (t < 16) {
         double w[7];
-#pragma unroll
-        for (int q = 0; q < 7; ++q) {
-            double sacc = red[0][t][q];
-#pragma unroll
-            for (int k = 1; k < FH_FIN_BLOCK / 64; ++k) sacc += red[k][t][q];
-            w[q] = sacc;
-        }
+        fh_fin_totals(red, w);
         int stepped = 0;
         if (a.s.active[i]) {
             const cplx rho = cmake(w[0], w[1]);
@@ -1482,6 +1478,8 @@ __global__ __launch_bounds__(FH_FIN_BLOCK) void k_fused_fin(fh_fused_fin_args a)
             if (!isfinite(rn)) { act = 0; a.s.status[i] = 8; }
             else if (!(rn > a.s.target[i])) { act = 0; a.s.status[i] = 0; }       // the true norm says: converged
             else if (!a.final_check) {
+                // the COCG scalar step; k_shift_fin holds the same one.  Every shared form tried moves the registers of one
+                // of the two kernels (profiles/krylov_fold_check.txt): a change of the breakdown rule goes into both
                 const cplx sigma = cmake(w[3], w[4]), kappa = cmake(w[5], w[6]);
                 const cplx al = cdiv(rho, sigma);
                 if (cabs2(sigma) == 0.0 || cabs2(rho) == 0.0 || !fh_finite(al)) {
@@ -1533,6 +1531,20 @@ __global__ __launch_bounds__(FH_FIN_BLOCK) void k_fused_fin(fh_fused_fin_args a)
     }
 }
 
+// The panel elements a thread of k_fused_vec / k_shift_vec OWNS in a grid (nblk, nseg) of FH_FV_THREADS threads: per_thread of
+// them, `stride` = nblk * FH_FV_THREADS apart (a multiple of LD: one column per thread); segment blockIdx.y takes the
+// elements from blockIdx.y * stride * per_thread on.
+struct fh_owned {
+    size_t e0, stride, total;
+    int per_thread;
+    __device__ __forceinline__ fh_owned(size_t total_, int per_thread_) : total(total_), per_thread(per_thread_) {
+        stride = (size_t)gridDim.x * FH_FV_THREADS;
+        e0 = (size_t)blockIdx.y * stride * per_thread + (size_t)blockIdx.x * FH_FV_THREADS + threadIdx.x;
+    }
+    __device__ __forceinline__ size_t e(int j) const { return e0 + (size_t)j * stride; }                  // the thread's element j
+    __device__ __forceinline__ bool ok(int j) const { return (j < per_thread) && e(j) < total; }          // ... exists
+};
+
 // FIRST: the lazy start's first iteration -- residual and direction of node n are first_scale[n][c] * first_src (shared by
 // the nodes: the reads of the 51 MB source panel are served by the caches after the first node), R and P are written here
 template <typename CT, int LD, bool SUM, bool FIRST>
@@ -1545,9 +1557,7 @@ __global__ __launch_bounds__(FH_FV_THREADS, 2) void k_fused_vec(fh_vec_args a, i
     __shared__ double red[FH_FV_THREADS / 64][LD][3];
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const int c = t % LD;
-    const size_t total = (size_t)a.N * LD;
-    const size_t stride = (size_t)gridDim.x * FH_FV_THREADS;
-    const size_t e0 = (size_t)blockIdx.y * stride * per_thread + (size_t)blockIdx.x * FH_FV_THREADS + t;
+    const fh_owned own((size_t)a.N * LD, per_thread);
     const int prow = blockIdx.y * gridDim.x + blockIdx.x, nprow = gridDim.x * gridDim.y;
     constexpr int GRP = sizeof(CT) == 8 ? 2 : 4;               // elements per thread in flight at once, 3 loads each (complex64 panels with 4: the compiler spills 90 VGPRs)
     // complex64 panels: half as many elements per thread (and twice the segments) -- with 28 the compiler hoists 3 x 28 64-bit
@@ -1592,8 +1602,8 @@ __global__ __launch_bounds__(FH_FV_THREADS, 2) void k_fused_vec(fh_vec_args a, i
                 bool ok[GRP];
 #pragma unroll
                 for (int u = 0; u < GRP; ++u) {
-                    const size_t e = e0 + (size_t)(j0 + u) * stride;
-                    ok[u] = (j0 + u < per_thread) && e < total;
+                    const size_t e = own.e(j0 + u);
+                    ok[u] = own.ok(j0 + u);
                     pv[u] = fh_czero<CT>(); qv[u] = fh_czero<CT>(); rv[u] = fh_czero<CT>(); xv[u] = fh_czero<CT>();
                     if (ok[u]) {
                         if (FIRST) { pv[u] = cvt<CT>(cmul(fsc, fsrc[e])); rv[u] = pv[u]; }
@@ -1604,7 +1614,7 @@ __global__ __launch_bounds__(FH_FV_THREADS, 2) void k_fused_vec(fh_vec_args a, i
                 }
 #pragma unroll
                 for (int u = 0; u < GRP; ++u) {
-                    const size_t e = e0 + (size_t)(j0 + u) * stride;
+                    const size_t e = own.e(j0 + u);
                     if (SUM) cfma(acc[j0 + u], coef, to_d(pv[u]));
                     else if (ok[u]) { cfma(xv[u], alpha, pv[u]); X[e] = xv[u]; }
                     if (act && ok[u]) {
@@ -1618,7 +1628,8 @@ __global__ __launch_bounds__(FH_FV_THREADS, 2) void k_fused_vec(fh_vec_args a, i
             }
         }
         // per-column sums of the workgroup: lanes that share a column inside a wave first (LD < 64), then the 8 waves in
-        // a fixed order through LDS
+        // a fixed order through LDS.  (k_shift_vec holds the same text: moved into a function, every instantiation of both
+        // kernels compiles to other code -- profiles/krylov_fold_check.txt)
         if (LD < 64) {
 #pragma unroll
             for (int off = LD; off < 64; off <<= 1) {
@@ -1641,8 +1652,8 @@ __global__ __launch_bounds__(FH_FV_THREADS, 2) void k_fused_vec(fh_vec_args a, i
     if (SUM && any) {
 #pragma unroll
         for (int j = 0; j < EMAX; ++j) {
-            const size_t e = e0 + (size_t)j * stride;
-            if (j < per_thread && e < total) a.sum_acc[e] = cadd(a.sum_acc[e], acc[j]);
+            const size_t e = own.e(j);
+            if (own.ok(j)) a.sum_acc[e] = cadd(a.sum_acc[e], acc[j]);
         }
     }
 }
@@ -1689,55 +1700,21 @@ __global__ __launch_bounds__(FH_BLOCK) void k_shift_init(fh_shift_args a) {
 
 template <int LD>
 __global__ __launch_bounds__(FH_FIN_BLOCK) void k_shift_fin(fh_shift_args a) {
-    // grid (LD / 16): one workgroup per 16-column tile; the partial rows are summed as in k_fused_fin (64 row groups x 16
-    // columns, fixed order), then the threads spread over (node, column of the tile)
+    // grid (LD / 16): one workgroup per 16-column tile; the partial rows are summed as in k_fused_fin (fh_fin_sum_rows), then
+    // the threads spread over (node, column of the tile)
     __shared__ double red[FH_FIN_BLOCK / 64][16][8];
     __shared__ cplx s_alpha[16], s_beta[16], s_fac[16];
     __shared__ double s_rn[16];
     __shared__ int s_flag[16], s_alive[16], s_step[16];
-    const int tile = blockIdx.x, t = threadIdx.x;
-    const int lane = t & 63, wave = t >> 6;
-    const int c16 = lane & 15, g = wave * 4 + (lane >> 4);
+    const int tile = blockIdx.x, t = threadIdx.x, lane = t & 63;
     const bool final_check = a.phase == 2, first = a.phase == 0;
-    double v[8];
-#pragma unroll
-    for (int q = 0; q < 8; ++q) v[q] = 0.0;
-    {
-        const size_t base = (size_t)tile * 16 + c16;
-#pragma unroll 4
-        for (int b = g; b < a.nblk_vec; b += 64) {
-            const cplx r1 = a.rho_part[base + (size_t)b * LD], r2 = a.rr_part[base + (size_t)b * LD];
-            v[0] += r1.x; v[1] += r1.y; v[2] += r2.x;
-        }
-        if (!final_check) {
-#pragma unroll 4
-            for (int b = g; b < a.nblk_op; b += 64) {
-                const cplx s1 = a.sig[base + (size_t)b * LD], s3 = a.kap[base + (size_t)b * LD];
-                v[3] += s1.x; v[4] += s1.y; v[5] += s3.x; v[6] += s3.y;
-            }
-        }
-    }
-#pragma unroll
-    for (int q = 0; q < 7; ++q) {
-        v[q] += __shfl_xor(v[q], 16);
-        v[q] += __shfl_xor(v[q], 32);
-    }
-    if (lane < 16) {
-#pragma unroll
-        for (int q = 0; q < 7; ++q) red[wave][lane][q] = v[q];
-    }
-    __syncthreads();
+    const size_t base = (size_t)tile * 16 + (t & 15);
+    fh_fin_sum_rows<LD>(a.rho_part, a.rr_part, base, a.nblk_vec, a.sig, a.kap, base, a.nblk_op, !final_check, red);
     // the seed's scalars of the column.  flag 0: no step (final check), 1: step, 2: breakdown before the step, 3: |r| not
     // finite, 4: step, then breakdown (beta not finite)
     if (t < 16) {
         double w[7];
-#pragma unroll
-        for (int q = 0; q < 7; ++q) {
-            double sacc = red[0][t][q];
-#pragma unroll
-            for (int k = 1; k < FH_FIN_BLOCK / 64; ++k) sacc += red[k][t][q];
-            w[q] = sacc;
-        }
+        fh_fin_totals(red, w);
         const int c = tile * 16 + t;
         const cplx rho = cmake(w[0], w[1]);
         const double rn = sqrt(w[2]);
@@ -1745,7 +1722,7 @@ __global__ __launch_bounds__(FH_FIN_BLOCK) void k_shift_fin(fh_shift_args a) {
         cplx al = cmake(0, 0), beta = cmake(0, 0), fac = cmake(0, 0);
         if (!isfinite(rn)) flag = 3;
         else if (final_check) flag = 0;
-        else {
+        else {                                                 // the scalar step of k_fused_fin (see there)
             const cplx sigma = cmake(w[3], w[4]), kappa = cmake(w[5], w[6]);
             al = cdiv(rho, sigma);
             if (cabs2(sigma) == 0.0 || cabs2(rho) == 0.0 || !fh_finite(al)) flag = 2;
@@ -1842,9 +1819,7 @@ __global__ __launch_bounds__(FH_FV_THREADS, 2) void k_shift_vec(fh_shift_args a,
     __shared__ double red[FH_FV_THREADS / 64][LD][3];
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const int c = t % LD;
-    const size_t total = (size_t)a.N * LD;
-    const size_t stride = (size_t)gridDim.x * FH_FV_THREADS;
-    const size_t e0 = (size_t)blockIdx.y * stride * per_thread + (size_t)blockIdx.x * FH_FV_THREADS + t;
+    const fh_owned own((size_t)a.N * LD, per_thread);
     const int prow = blockIdx.y * gridDim.x + blockIdx.x;
     constexpr int GRP = 2;
     if (prow == 0 && t == 0) {
@@ -1866,8 +1841,8 @@ __global__ __launch_bounds__(FH_FV_THREADS, 2) void k_shift_vec(fh_shift_args a,
             bool ok[GRP];
 #pragma unroll
             for (int u = 0; u < GRP; ++u) {
-                const size_t e = e0 + (size_t)(j0 + u) * stride;
-                ok[u] = (j0 + u < per_thread) && e < total;
+                const size_t e = own.e(j0 + u);
+                ok[u] = own.ok(j0 + u);
                 qv[u] = cmake(0, 0); rv[u] = cmake(0, 0);
                 if (ok[u]) { qv[u] = fh_ld_nt(a.Qv + e); rv[u] = a.R[e]; }
             }
@@ -1875,7 +1850,7 @@ __global__ __launch_bounds__(FH_FV_THREADS, 2) void k_shift_vec(fh_shift_args a,
             for (int u = 0; u < GRP; ++u) {
                 if (!ok[u]) continue;
                 const cplx r = csub(rv[u], cmul(alpha, qv[u]));
-                a.R[e0 + (size_t)(j0 + u) * stride] = r;
+                a.R[own.e(j0 + u)] = r;
                 rn[j0 + u] = r;
                 d1x += r.x * r.x - r.y * r.y; d1y += 2.0 * r.x * r.y; d2 += cabs2(r);
             }
@@ -1919,8 +1894,8 @@ __global__ __launch_bounds__(FH_FV_THREADS, 2) void k_shift_vec(fh_shift_args a,
             bool ok[GRP];
 #pragma unroll
             for (int u = 0; u < GRP; ++u) {
-                const size_t e = e0 + (size_t)(j0 + u) * stride;
-                ok[u] = (j0 + u < per_thread) && e < total;
+                const size_t e = own.e(j0 + u);
+                ok[u] = own.ok(j0 + u);
                 pv[u] = cmake(0, 0);
                 if (ok[u]) pv[u] = P[e];
             }
@@ -1928,15 +1903,15 @@ __global__ __launch_bounds__(FH_FV_THREADS, 2) void k_shift_vec(fh_shift_args a,
             for (int u = 0; u < GRP; ++u) {
                 if (!ok[u]) continue;
                 cfma(acc[j0 + u], coef, pv[u]);
-                P[e0 + (size_t)(j0 + u) * stride] = cadd(cmul(rn[j0 + u], ip), cmul(be, pv[u]));
+                P[own.e(j0 + u)] = cadd(cmul(rn[j0 + u], ip), cmul(be, pv[u]));
             }
         }
     }
     if (any) {
 #pragma unroll
         for (int j = 0; j < FH_SV_EMAX; ++j) {
-            const size_t e = e0 + (size_t)j * stride;
-            if (j < per_thread && e < total) a.sum_acc[e] = cadd(a.sum_acc[e], acc[j]);
+            const size_t e = own.e(j);
+            if (own.ok(j)) a.sum_acc[e] = cadd(a.sum_acc[e], acc[j]);
         }
     }
 }
@@ -1947,111 +1922,78 @@ __global__ __launch_bounds__(FH_FV_THREADS, 2) void k_shift_vec(fh_shift_args a,
 int fh_launch_shift_init(const fh_shift_args& a, int ld, hipStream_t st) {
     const size_t total = (size_t)a.N * ld;
     const int nblk = (int)std::min<size_t>((total + FH_BLOCK - 1) / FH_BLOCK, 256);
-    if (ld == 16) hipLaunchKernelGGL((k_shift_init<16>), dim3(nblk), dim3(FH_BLOCK), 0, st, a);
-    else if (ld == 32) hipLaunchKernelGGL((k_shift_init<32>), dim3(nblk), dim3(FH_BLOCK), 0, st, a);
-    else hipLaunchKernelGGL((k_shift_init<64>), dim3(nblk), dim3(FH_BLOCK), 0, st, a);
+    FH_LAUNCH_LD(ld, k_shift_init, dim3(nblk), dim3(FH_BLOCK), st, a);
     return nblk;
 }
 void fh_launch_shift_fin(const fh_shift_args& a, int ld, hipStream_t st) {
-    if (ld == 16) hipLaunchKernelGGL((k_shift_fin<16>), dim3(1), dim3(FH_FIN_BLOCK), 0, st, a);
-    else if (ld == 32) hipLaunchKernelGGL((k_shift_fin<32>), dim3(2), dim3(FH_FIN_BLOCK), 0, st, a);
-    else hipLaunchKernelGGL((k_shift_fin<64>), dim3(4), dim3(FH_FIN_BLOCK), 0, st, a);
+    FH_LAUNCH_LD(ld, k_shift_fin, dim3(ld / 16), dim3(FH_FIN_BLOCK), st, a);
 }
 int fh_launch_shift_vec(const fh_shift_args& a, int ld, hipStream_t st) {
     int nblk, nseg, per;
     fh_fused_vec_geometry(a.N, ld, 1, &nblk, &nseg, &per);
-    const dim3 grid(nblk, nseg);
-    if (ld == 16) hipLaunchKernelGGL((k_shift_vec<16>), grid, dim3(FH_FV_THREADS), 0, st, a, per);
-    else if (ld == 32) hipLaunchKernelGGL((k_shift_vec<32>), grid, dim3(FH_FV_THREADS), 0, st, a, per);
-    else hipLaunchKernelGGL((k_shift_vec<64>), grid, dim3(FH_FV_THREADS), 0, st, a, per);
+    FH_LAUNCH_LD(ld, k_shift_vec, dim3(nblk, nseg), dim3(FH_FV_THREADS), st, a, per);
     return nblk * nseg;
 }
 
-#define FH_DISPATCH_VEC(prec, ld, KERNEL, grid, st, args)                                          \
-    do {                                                                                            \
-        if ((prec) == 32) {                                                                         \
-            if ((ld) == 16) hipLaunchKernelGGL((KERNEL<cplxf, 16>), grid, dim3(FH_BLOCK), 0, st, args); \
-            else if ((ld) == 32) hipLaunchKernelGGL((KERNEL<cplxf, 32>), grid, dim3(FH_BLOCK), 0, st, args); \
-            else hipLaunchKernelGGL((KERNEL<cplxf, 64>), grid, dim3(FH_BLOCK), 0, st, args);        \
-        } else {                                                                                    \
-            if ((ld) == 16) hipLaunchKernelGGL((KERNEL<cplx, 16>), grid, dim3(FH_BLOCK), 0, st, args); \
-            else if ((ld) == 32) hipLaunchKernelGGL((KERNEL<cplx, 32>), grid, dim3(FH_BLOCK), 0, st, args); \
-            else hipLaunchKernelGGL((KERNEL<cplx, 64>), grid, dim3(FH_BLOCK), 0, st, args);         \
-        }                                                                                           \
-    } while (0)
-
-#define FH_DISPATCH_FIN(ld, KERNEL, grid, st, args)                                           \
-    do {                                                                                        \
-        if ((ld) == 16) hipLaunchKernelGGL((KERNEL<16>), grid, dim3(FH_FIN_BLOCK), 0, st, args); \
-        else if ((ld) == 32) hipLaunchKernelGGL((KERNEL<32>), grid, dim3(FH_FIN_BLOCK), 0, st, args); \
-        else hipLaunchKernelGGL((KERNEL<64>), grid, dim3(FH_FIN_BLOCK), 0, st, args);           \
-    } while (0)
-
 void fh_launch_init_guess(const fh_vec_args& a, int ld, int nblk, int nodes, hipStream_t st) {
-    FH_DISPATCH_VEC(64, ld, k_init_guess, dim3(nblk, nodes), st, a);
+    FH_LAUNCH_LD(ld, k_init_guess, dim3(nblk, nodes), dim3(FH_BLOCK), st, a);
 }
 void fh_launch_copy_r(const fh_vec_args& a, int ld, int nblk, int nodes, hipStream_t st) {
-    FH_DISPATCH_VEC(a.prec, ld, k_copy_r, dim3(nblk, nodes), st, a);
+    FH_LAUNCH_PREC_LD(a.prec, ld, k_copy_r, dim3(nblk, nodes), dim3(FH_BLOCK), st, a);
 }
 void fh_launch_p_update(const fh_vec_args& a, int ld, int nblk, int nodes, hipStream_t st) {
-    FH_DISPATCH_VEC(a.prec, ld, k_p_update, dim3(nblk, nodes), st, a);
+    FH_LAUNCH_PREC_LD(a.prec, ld, k_p_update, dim3(nblk, nodes), dim3(FH_BLOCK), st, a);
 }
 void fh_launch_s_update(const fh_vec_args& a, int ld, int nblk, int nodes, hipStream_t st) {
-    FH_DISPATCH_VEC(a.prec, ld, k_s_update, dim3(nblk, nodes), st, a);
+    FH_LAUNCH_PREC_LD(a.prec, ld, k_s_update, dim3(nblk, nodes), dim3(FH_BLOCK), st, a);
 }
 void fh_launch_xr_update(const fh_vec_args& a, int ld, int nblk, int nodes, hipStream_t st) {
-    FH_DISPATCH_VEC(a.prec, ld, k_xr_update, dim3(nblk, nodes), st, a);
+    FH_LAUNCH_PREC_LD(a.prec, ld, k_xr_update, dim3(nblk, nodes), dim3(FH_BLOCK), st, a);
 }
 void fh_launch_cocg_init(const fh_vec_args& a, int ld, int nblk, int nodes, hipStream_t st) {
-    FH_DISPATCH_VEC(a.prec, ld, k_cocg_init, dim3(nblk, nodes), st, a);
+    FH_LAUNCH_PREC_LD(a.prec, ld, k_cocg_init, dim3(nblk, nodes), dim3(FH_BLOCK), st, a);
 }
 void fh_launch_cocg_init_shared(const fh_vec_args& a, int ld, int nblk, int nodes, hipStream_t st) {
-    FH_DISPATCH_VEC(a.prec, ld, k_cocg_init_shared, dim3(nblk, nodes), st, a);
+    FH_LAUNCH_PREC_LD(a.prec, ld, k_cocg_init_shared, dim3(nblk, nodes), dim3(FH_BLOCK), st, a);
 }
 void fh_launch_cocg_init_lazy(const fh_vec_args& a, int ld, int nblk, int nodes, hipStream_t st) {
     (void)nodes;
-    if (ld == 16) hipLaunchKernelGGL((k_cocg_init_lazy<16>), dim3(nblk), dim3(FH_BLOCK), 0, st, a);
-    else if (ld == 32) hipLaunchKernelGGL((k_cocg_init_lazy<32>), dim3(nblk), dim3(FH_BLOCK), 0, st, a);
-    else hipLaunchKernelGGL((k_cocg_init_lazy<64>), dim3(nblk), dim3(FH_BLOCK), 0, st, a);
+    FH_LAUNCH_LD(ld, k_cocg_init_lazy, dim3(nblk), dim3(FH_BLOCK), st, a);
 }
 void fh_launch_sum_finish(const cplx* src, const cplx* rho, const cplx* acc, cplx* out, int N, int ld, int real_part, hipStream_t st) {
     const size_t total = (size_t)N * ld;
     const int nblk = (int)std::min<size_t>((total + FH_BLOCK - 1) / FH_BLOCK, 2048);
-    if (ld == 16) hipLaunchKernelGGL((k_sum_finish<16>), dim3(nblk), dim3(FH_BLOCK), 0, st, src, rho, acc, out, total, real_part);
-    else if (ld == 32) hipLaunchKernelGGL((k_sum_finish<32>), dim3(nblk), dim3(FH_BLOCK), 0, st, src, rho, acc, out, total, real_part);
-    else hipLaunchKernelGGL((k_sum_finish<64>), dim3(nblk), dim3(FH_BLOCK), 0, st, src, rho, acc, out, total, real_part);
+    FH_LAUNCH_LD(ld, k_sum_finish, dim3(nblk), dim3(FH_BLOCK), st, src, rho, acc, out, total, real_part);
 }
 void fh_launch_node_finish(const cplx* src, const cplx* rho, const cplx* acc, const cplx* Yd, size_t stride, const cplx* wd, int nd,
                            cplx* out, int N, int ld, int real_part, hipStream_t st) {
     const size_t total = (size_t)N * ld;
     const int nblk = (int)std::min<size_t>((total + FH_BLOCK - 1) / FH_BLOCK, 2048);
-    if (ld == 16) hipLaunchKernelGGL((k_node_finish<16>), dim3(nblk), dim3(FH_BLOCK), 0, st, src, rho, acc, Yd, stride, wd, nd, out, total, real_part);
-    else if (ld == 32) hipLaunchKernelGGL((k_node_finish<32>), dim3(nblk), dim3(FH_BLOCK), 0, st, src, rho, acc, Yd, stride, wd, nd, out, total, real_part);
-    else hipLaunchKernelGGL((k_node_finish<64>), dim3(nblk), dim3(FH_BLOCK), 0, st, src, rho, acc, Yd, stride, wd, nd, out, total, real_part);
+    FH_LAUNCH_LD(ld, k_node_finish, dim3(nblk), dim3(FH_BLOCK), st, src, rho, acc, Yd, stride, wd, nd, out, total, real_part);
 }
 void fh_launch_cocg_update(const fh_vec_args& a, int ld, int nblk, int nodes, hipStream_t st) {
-    FH_DISPATCH_VEC(a.prec, ld, k_cocg_update, dim3(nblk, nodes), st, a);
+    FH_LAUNCH_PREC_LD(a.prec, ld, k_cocg_update, dim3(nblk, nodes), dim3(FH_BLOCK), st, a);
 }
 void fh_launch_cocg_p(const fh_vec_args& a, int ld, int nblk, int nodes, hipStream_t st) {
-    FH_DISPATCH_VEC(a.prec, ld, k_cocg_p, dim3(nblk, nodes), st, a);
+    FH_LAUNCH_PREC_LD(a.prec, ld, k_cocg_p, dim3(nblk, nodes), dim3(FH_BLOCK), st, a);
 }
 void fh_launch_cocg_p_sum(const fh_vec_args& a, int ld, int nodes, hipStream_t st) {
     (void)nodes;
     const size_t total = (size_t)a.N * ld;
     const int nblk = (int)((total + (size_t)FH_PSUM_K * FH_BLOCK - 1) / ((size_t)FH_PSUM_K * FH_BLOCK));
-    FH_DISPATCH_VEC(a.prec, ld, k_cocg_p_sum, dim3(nblk), st, a);
+    FH_LAUNCH_PREC_LD(a.prec, ld, k_cocg_p_sum, dim3(nblk), dim3(FH_BLOCK), st, a);
 }
 void fh_launch_fin_init(const fh_fin_args& a, int ld, int nodes, hipStream_t st) {
-    FH_DISPATCH_FIN(ld, k_fin_init, dim3(nodes), st, a);
+    FH_LAUNCH_LD(ld, k_fin_init, dim3(nodes), dim3(FH_FIN_BLOCK), st, a);
 }
 void fh_launch_fin_alpha(const fh_fin_args& a, int ld, int nodes, hipStream_t st) {
-    FH_DISPATCH_FIN(ld, k_fin_alpha, dim3(nodes), st, a);
+    FH_LAUNCH_LD(ld, k_fin_alpha, dim3(nodes), dim3(FH_FIN_BLOCK), st, a);
 }
 void fh_launch_fin_omega(const fh_fin_args& a, int ld, int nodes, hipStream_t st) {
-    FH_DISPATCH_FIN(ld, k_fin_omega, dim3(nodes), st, a);
+    FH_LAUNCH_LD(ld, k_fin_omega, dim3(nodes), dim3(FH_FIN_BLOCK), st, a);
 }
 void fh_launch_fin_rho(const fh_fin_args& a, int ld, int nodes, hipStream_t st) {
-    FH_DISPATCH_FIN(ld, k_fin_rho, dim3(nodes), st, a);
+    FH_LAUNCH_LD(ld, k_fin_rho, dim3(nodes), dim3(FH_FIN_BLOCK), st, a);
 }
 void fh_launch_count_active(const int* node_active, int nodes, int* out, hipStream_t st) {
     hipLaunchKernelGGL(k_count_active, dim3(1), dim3(64), 0, st, node_active, nodes, out);
@@ -2062,44 +2004,30 @@ void fh_launch_publish_progress(const int* node_active, int nodes, unsigned long
 void fh_launch_narrow_scaled(const cplx* src, size_t src_stride, cplxf* dst, size_t dst_stride, const double* r0norm,
                              int N, int ld, int nblk, int nodes, hipStream_t st) {
     size_t total = (size_t)N * ld;
-    if (ld == 16) hipLaunchKernelGGL((k_narrow_scaled<16>), dim3(nblk, nodes), dim3(FH_BLOCK), 0, st, src, src_stride, dst, dst_stride, r0norm, total);
-    else if (ld == 32) hipLaunchKernelGGL((k_narrow_scaled<32>), dim3(nblk, nodes), dim3(FH_BLOCK), 0, st, src, src_stride, dst, dst_stride, r0norm, total);
-    else hipLaunchKernelGGL((k_narrow_scaled<64>), dim3(nblk, nodes), dim3(FH_BLOCK), 0, st, src, src_stride, dst, dst_stride, r0norm, total);
+    FH_LAUNCH_LD(ld, k_narrow_scaled, dim3(nblk, nodes), dim3(FH_BLOCK), st, src, src_stride, dst, dst_stride, r0norm, total);
 }
 void fh_launch_widen_axpy(cplx* X, size_t x_stride, const cplxf* D, size_t d_stride, const double* r0norm,
                           int N, int ld, int nblk, int nodes, hipStream_t st) {
     size_t total = (size_t)N * ld;
-    if (ld == 16) hipLaunchKernelGGL((k_widen_axpy<16>), dim3(nblk, nodes), dim3(FH_BLOCK), 0, st, X, x_stride, D, d_stride, r0norm, total);
-    else if (ld == 32) hipLaunchKernelGGL((k_widen_axpy<32>), dim3(nblk, nodes), dim3(FH_BLOCK), 0, st, X, x_stride, D, d_stride, r0norm, total);
-    else hipLaunchKernelGGL((k_widen_axpy<64>), dim3(nblk, nodes), dim3(FH_BLOCK), 0, st, X, x_stride, D, d_stride, r0norm, total);
+    FH_LAUNCH_LD(ld, k_widen_axpy, dim3(nblk, nodes), dim3(FH_BLOCK), st, X, x_stride, D, d_stride, r0norm, total);
 }
 
 void fh_launch_fused_fin(const fh_fused_fin_args& a, int ld, int nodes, hipStream_t st) {
-    if (ld == 16) hipLaunchKernelGGL((k_fused_fin<16>), dim3(1, nodes), dim3(FH_FIN_BLOCK), 0, st, a);
-    else if (ld == 32) hipLaunchKernelGGL((k_fused_fin<32>), dim3(2, nodes), dim3(FH_FIN_BLOCK), 0, st, a);
-    else hipLaunchKernelGGL((k_fused_fin<64>), dim3(4, nodes), dim3(FH_FIN_BLOCK), 0, st, a);
-}
-template <typename CT, int LD>
-static void launch_fused_vec_t(const fh_vec_args& a, dim3 grid, int per_thread, hipStream_t st) {
-    if (a.first_src) {       // lazy start: sum mode, fp64 panels only (fh_krylov)
-        if (a.sum_acc) hipLaunchKernelGGL((k_fused_vec<CT, LD, true, true>), grid, dim3(FH_FV_THREADS), 0, st, a, per_thread);
-        else hipLaunchKernelGGL((k_fused_vec<CT, LD, false, true>), grid, dim3(FH_FV_THREADS), 0, st, a, per_thread);
-        return;
-    }
-    if (a.sum_acc) hipLaunchKernelGGL((k_fused_vec<CT, LD, true, false>), grid, dim3(FH_FV_THREADS), 0, st, a, per_thread);
-    else hipLaunchKernelGGL((k_fused_vec<CT, LD, false, false>), grid, dim3(FH_FV_THREADS), 0, st, a, per_thread);
+    FH_LAUNCH_LD(ld, k_fused_fin, dim3(ld / 16, nodes), dim3(FH_FIN_BLOCK), st, a);
 }
 void fh_launch_fused_vec(const fh_vec_args& a, int ld, hipStream_t st) {
     int nblk, nseg, per;
     fh_fused_vec_geometry(a.N, ld, a.prec == 32 || a.first_src != nullptr, &nblk, &nseg, &per);
-    const dim3 grid(nblk, nseg);
-    if (a.prec == 32) {
-        if (ld == 16) launch_fused_vec_t<cplxf, 16>(a, grid, per, st);
-        else if (ld == 32) launch_fused_vec_t<cplxf, 32>(a, grid, per, st);
-        else launch_fused_vec_t<cplxf, 64>(a, grid, per, st);
-    } else {
-        if (ld == 16) launch_fused_vec_t<cplx, 16>(a, grid, per, st);
-        else if (ld == 32) launch_fused_vec_t<cplx, 32>(a, grid, per, st);
-        else launch_fused_vec_t<cplx, 64>(a, grid, per, st);
-    }
+    const dim3 grid(nblk, nseg), block(FH_FV_THREADS);
+    fh_with_prec(a.prec, [&](auto ct) {
+        fh_with_ld(ld, [&](auto L) {
+            using CT = decltype(ct);
+            constexpr int LD = decltype(L)::value;
+            if (a.first_src) {       // lazy start: sum mode, fp64 panels only (fh_krylov)
+                if (a.sum_acc) hipLaunchKernelGGL((k_fused_vec<CT, LD, true, true>), grid, block, 0, st, a, per);
+                else hipLaunchKernelGGL((k_fused_vec<CT, LD, false, true>), grid, block, 0, st, a, per);
+            } else if (a.sum_acc) hipLaunchKernelGGL((k_fused_vec<CT, LD, true, false>), grid, block, 0, st, a, per);
+            else hipLaunchKernelGGL((k_fused_vec<CT, LD, false, false>), grid, block, 0, st, a, per);
+        });
+    });
 }

@@ -7,7 +7,7 @@ that two builds (a refactor and its parent) can be compared bit for bit on the C
       cases in which that build differs from itself are named, and compared within the solver's TOLERANCES entry instead.
 
 The list covers every solver kind (LU with 64- and 32-bit factors, banded, BiCGStab, COCG fused and five-launch, shifted COCG,
-GMRES), the COCG starts (zero guess, Ritz warm start, lazy start on and off, sum mode on and off) and the call variants (a
+block COCG with B given and B = I, GMRES), the COCG starts (zero guess, Ritz warm start, lazy start on and off, sum mode on and off) and the call variants (a
 column mask, a node list with direct nodes, moments, a width above 64).  Switches that the library reads once per process
 or per handle (FH_COCG_FUSED, FH_NO_SUM_MODE) get a group, that is a fresh child process, of their own; the parent process
 never opens the GPU.  Per case: Q_proj, the node statuses, last_node_iterations, last_column_iterations, the stats counters
@@ -54,6 +54,10 @@ def run_group(lib_path, group, out):
     fpm[2], fpm[16], fpm[18] = 8, 0, 100
     Z, W = fk.contour.feast_contour(0.0, 0.62, fpm)
     Zd, Wd = fk.contour.feast_contour(0.5, 1.5, fpm)
+    # block COCG: the N = 3200 pencil and interval of tests/block_cocg_cases.py, its B = I counterpart, the test's narrow block
+    Ab, Bb, lamb = fk.workloads.laplacian_3d_pencil(20, 16, 10)[:3]
+    Abi, lambi = fk.workloads.laplacian_3d_standard(20, 16, 10)[:2]
+    Zb, Wb = fk.contour.feast_contour(0.0, 0.42, fpm)
 
     def ritz(values, m):                               # Ritz values of a warm start: the spectrum's low end, perturbed
         return np.sort(values)[:m] * (1.0 + 1e-3 * np.cos(np.arange(m)))
@@ -87,6 +91,8 @@ def run_group(lib_path, group, out):
             data[pre + "node_iterations"] = eng.last_node_iterations(nodes)
             data[pre + "column_iterations"] = eng.last_column_iterations(nodes, m)
             used, seed, seed_its, _ = eng.last_shifted_sweep()
+            if solver == "block_cocg":
+                data[pre + "block_sweep"] = np.array(eng.last_block_sweep(), dtype=np.int64)      # used, steps, breakdowns, passes
             counters = {k: st[k] for k in ("krylov_iterations", "factorizations", "max_rel_residual")}
             counters["spmm_calls" if used or solver in ("gmres", "direct", "banded") else "spmm_calls_queued"] = st["spmm_calls"]
             counters["shifted_used"], counters["shifted_seed"], counters["shifted_seed_iterations"] = int(used), seed, seed_its
@@ -94,7 +100,8 @@ def run_group(lib_path, group, out):
                 data[pre + "stats." + k] = np.array(v)
             if moments:
                 data[pre + "zAq"], data[pre + "zSq"] = res[3], res[4]
-            print("%s status=%s iterations=%d" % (pre[:-1], list(status[:nodes]), st["krylov_iterations"]), flush=True)
+            print("%s status=%s iterations=%d%s" % (pre[:-1], list(status[:nodes]), st["krylov_iterations"],
+                                                    " block_sweep=%s" % (eng.last_block_sweep(),) if solver == "block_cocg" else ""), flush=True)
         finally:
             for k in (env or {}):
                 del os.environ[k]
@@ -142,6 +149,8 @@ def run_group(lib_path, group, out):
     case("shifted_ritz_mask", std, 24, "shifted_cocg", warm=True, mask=mask24, **tight)
     case("shifted_wide_mask", std, 80, "shifted_cocg", warm=True, mask=mask80, **tight)
     case("shifted_falls_back_gen", gen, 24, "shifted_cocg", warm=True, **tight)
+    case("block_cocg_gen", (Ab, Bb, lamb), 5, "block_cocg", real=False, contour=(Zb, Wb), **loose)
+    case("block_cocg_std", (Abi, None, lambi), 5, "block_cocg", real=False, contour=(Zb, Wb), **loose)
     eng.close()
     np.savez(out, **data)
 
