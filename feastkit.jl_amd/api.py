@@ -452,11 +452,13 @@ def _two_sided_sparse_route(A, B, solver, nodes, engine, device):
     ``direct`` / ``lu``: ValueError for a pattern inside the library's narrow band (kl + ku <= 64: that solver means the
     one-workgroup band LU there, which has no adjoint substitution, and a band that thin is not expanded silently: the caller
     chooses ``sparse_direct`` or dense input); else the expanded matrix under the dense LU inside _sparse_direct_solver's dense
-    window (the wider band answer is left out: that LU has no adjoint substitution either), else -- as for an explicit ``sparse_direct`` / ``banded`` -- the
-    sparse direct solver with the multifrontal plan
+    window, else -- as for an explicit ``sparse_direct`` / ``banded`` -- the sparse direct solver with the plan the requirement
+    gives: the multifrontal LU, or the blocked band LU for a pattern that has no multifrontal plan
     (require_adjoint is set BEFORE the plan is queried, so the plan query already answers for the plan that has an adjoint
     substitution; the driver clears it), provided its factors fit the device.  Otherwise ValueError: there is no Krylov solver
-    on the conjugate transpose."""
+    on the conjugate transpose.  The fit is that of the plan in force: a multifrontal LU that rejects a pivot during the solve
+    falls back to the blocked band LU, whose factors are larger; if those do not fit, the solve raises the library's
+    FeastHipError (``banded LU: ... do not fit the free device memory``), it is not turned into a result code."""
     if solver in ("direct", "lu"):
         kl, ku = _band_widths(A, B)
         if kl + ku <= _NARROW_BAND:
@@ -488,8 +490,10 @@ def feast_general(A, B=None, center=0.0, radius=1.0, *, M0=10, fpm=None, backend
     ``two_sided=True`` (``solver="direct"``; sparse input also ``"sparse_direct"`` / ``"banded"``): the two-sided method -- a
     left subspace from conjugate-transposed solves on the LU factors of the right sweep, oblique projection, both residuals
     with B; the result carries ``q_left`` (y_j^H B x_j = 1) and ``stats["two_sided"]`` (``direct_plan`` names the factors that
-    ran), and ``info`` is Feast_ERROR_NO_CONVERGENCE when the loop limit ends the run.  Sparse input runs on the multifrontal
-    LU of the sparse direct solver, or -- ``solver="direct"`` up to N = 12 288 -- on the dense LU of the expanded matrix
+    ran, ``fell_back`` whether the multifrontal LU handed the matrix to the band LU), and ``info`` is
+    Feast_ERROR_NO_CONVERGENCE when the loop limit ends the run.  Sparse input runs on the multifrontal
+    LU of the sparse direct solver -- on its blocked band LU where a pivot is rejected (saddle-point, zero-diagonal pencils)
+    or the pattern has no multifrontal plan --, or -- ``solver="direct"`` up to N = 12 288 -- on the dense LU of the expanded matrix
     (``stats["solver_substitution"]``); ``solver="direct"`` on a narrow band (kl + ku <= 64) raises ValueError and names
     ``solver="sparse_direct"``; there is no Krylov solver on the conjugate transpose.
     ``QL0``: left start block.  The keyword is the only switch: fpm[15], which the reference validates and never reads

@@ -669,11 +669,12 @@ static int fh_check_problem(feasthip_ctx* h, int64_t m, int wide = 0) {
 
 // Adjoint switch (feasthip_set_adjoint).  unsupported != null: the entry point has no adjoint form at all.  Otherwise the
 // handle must be what the adjoint kernels cover: fp64 factors, no real projection, one rank, and either a dense problem under
-// the dense LU or a CSR problem under the sparse direct solver with the multifrontal plan (made here if need be).
+// the dense LU or a CSR problem under the sparse direct solver with the multifrontal plan or the blocked band LU (the plan is
+// made here if need be; fh_banded_adjoint_ready).
 static int fh_check_adjoint(feasthip_ctx* h, const char* what, const char* unsupported = nullptr) {
     if (!h || !h->adjoint) return 0;
     const char* why = unsupported;
-    if (!why && h->kind == 2 && h->solver == FEASTHIP_SOLVER_LU) why = "a CSR problem has no dense LU; its adjoint substitution needs FEASTHIP_SOLVER_BANDED with the multifrontal plan";
+    if (!why && h->kind == 2 && h->solver == FEASTHIP_SOLVER_LU) why = "a CSR problem has no dense LU; its adjoint substitution needs FEASTHIP_SOLVER_BANDED (multifrontal plan or blocked band LU)";
     if (!why && h->kind == 2 && h->solver != FEASTHIP_SOLVER_BANDED) why = "the solver of a CSR problem must be the sparse direct one (FEASTHIP_SOLVER_BANDED): there is no Krylov solver on the conjugate transpose";
     if (!why && h->kind != 2 && h->solver != FEASTHIP_SOLVER_LU) why = "the solver must be the dense LU (FEASTHIP_SOLVER_LU)";
     if (!why && h->factor_precision == 32) why = "factor_precision = 32 is not supported (complex128 factors only)";

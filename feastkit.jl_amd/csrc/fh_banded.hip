@@ -220,11 +220,15 @@ static int band_take_band_plan(feasthip_ctx* h, const std::vector<int>& perm, co
 }
 
 static int band_make_plan(feasthip_ctx* h) {
-    // feasthip_require_adjoint: only the multifrontal plan has an adjoint substitution, so a cached plan of another kind goes,
-    // together with its factors, and the plan is made again below as FH_MF=1 would make it
+    // feasthip_require_adjoint: the multifrontal plan and the blocked band plan have an adjoint substitution, the narrow plan
+    // has none, and the multifrontal one is preferred.  So a cached plan that was NOT made under the requirement goes unless it
+    // is the multifrontal one, together with its factors, and the plan is made again below as FH_MF=1 would make it.  A blocked
+    // band plan that WAS made under the requirement -- no multifrontal plan for the pattern, or the multifrontal LU rejected a
+    // pivot (band_fall_back) -- stays while the requirement does: dropping it would plan and factor again on every call.
     // A plan made under the requirement goes likewise once the requirement is off: the calls that never asked for an adjoint
     // get the plan (and the bits) they would have got without it.
-    if (h->band_plan && ((h->require_adjoint && h->band_plan != 3) || (!h->require_adjoint && h->band_plan_required))) {
+    if (h->band_plan && ((h->require_adjoint && h->band_plan != 3 && !(h->band_plan == 2 && h->band_plan_required)) ||
+                         (!h->require_adjoint && h->band_plan_required))) {
         fh_banded_free(h);
         fh_mf_free_buffers(h);
     }
@@ -267,10 +271,8 @@ static int band_make_plan(feasthip_ctx* h) {
             }
         }
     }
-    if (h->require_adjoint) {
-        h->last_error = "sparse direct solver: no multifrontal plan for this pattern (a front beyond 16 384 rows), and the band LU has no adjoint substitution (feasthip_require_adjoint)";
-        return FEASTHIP_ERROR_FPM;
-    }
+    // (under feasthip_require_adjoint too: no multifrontal plan for this pattern -- a front beyond 16 384 rows -- and the blocked
+    // band LU has the adjoint substitution, fh_wband_solve_adjoint)
     return band_take_band_plan(h, perm, iperm, kl0, ku0, kl1, ku1);
 }
 
@@ -373,7 +375,9 @@ static int mf_nodes_per_call(feasthip_ctx* h) {
 // again when it is next used), as many as there were.  A band whose factors do not fit fails here with the reason in last_error.
 static int band_fall_back(feasthip_ctx* h) {
     const int nslots = (int)h->band_factors.size();
+    const int required = h->band_plan_required;
     fh_banded_free(h);
+    h->band_plan_required = required;       // the band plan inherits it: band_make_plan keeps such a plan while the requirement is on
     fh_mf_free_buffers(h);         // the dead plan's work arena would otherwise count against the band factors' memory check
     const int64_t N = h->csr.N;
     int kl0 = 0, ku0 = 0, kl1 = 0, ku1 = 0;
@@ -406,7 +410,6 @@ static int band_factor_batch(feasthip_ctx* h, const std::vector<int>& which, con
         const double bound = fh_knob::mf_max_multiplier(fh_mf::max_boundary_multiplier);
         double worst = 0.0;
         bool rejected = false;
-        std::vector<double> mult_all(nf, 0.0);
         for (int q0 = 0; q0 < nf; q0 += per_call) {
             const int cnt = std::min(per_call, nf - q0);
             std::vector<int> info_part;
@@ -414,7 +417,6 @@ static int band_factor_batch(feasthip_ctx* h, const std::vector<int>& which, con
             if ((rc = fh_mf_factor(h, h->band_prec, cnt, stores.data() + q0, pvs.data() + q0, dz + q0, info_part, mult_part))) return rc;
             for (int q = 0; q < cnt; ++q) {
                 info_out[q0 + q] = info_part[q];
-                mult_all[q0 + q] = mult_part[q];
                 worst = std::max(worst, mult_part[q]);
                 rejected = rejected || info_part[q] != 0 || !(mult_part[q] <= bound);
             }
@@ -424,14 +426,7 @@ static int band_factor_batch(feasthip_ctx* h, const std::vector<int>& which, con
                     std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_factor).count(), worst,
                     rejected ? ": rejected, band LU from here" : "");
         if (!rejected) return 0;
-        if (h->require_adjoint) {
-            // no band LU fallback: it has no adjoint form.  The rejected nodes are reported (status 8 / FEASTHIP_ERROR_LAPACK).
-            for (int q = 0; q < nf; ++q)
-                if (info_out[q] == 0 && !(mult_all[q] <= bound)) info_out[q] = 1;
-            h->last_error = "multifrontal LU rejected a pivot (largest boundary multiplier " + std::to_string(worst) +
-                            "); no band LU fallback while feasthip_require_adjoint is on (the band LU has no adjoint substitution)";
-            return 0;
-        }
+        // (under feasthip_require_adjoint as well: the blocked band LU has the adjoint substitution, fh_wband_solve_adjoint)
         if ((rc = band_fall_back(h))) return rc;
         return band_factor_batch(h, which, zlist, info_out);
     }
@@ -489,8 +484,9 @@ static int band_solve_batch(feasthip_ctx* h, int ld, int m, const std::vector<in
         }
         return 0;
     }
-    // (the API layer lets the adjoint switch through for the multifrontal plan only: fh_banded_adjoint_ready)
-    if (h->adjoint) { h->last_error = "internal: adjoint substitution on a band plan"; return FEASTHIP_ERROR_INTERNAL; }
+    // (the API layer lets the adjoint switch through for the multifrontal and the blocked band plan with complex128 factors:
+    // fh_banded_adjoint_ready, fh_check_adjoint)
+    if (h->adjoint && (h->band_plan != 2 || h->band_prec == 32)) { h->last_error = "internal: adjoint substitution on the narrow band plan or on complex64 factors"; return FEASTHIP_ERROR_INTERNAL; }
     cplx** dabs; int** dpvs; int** dperms;
     if ((rc = band_pointer_arrays(h, slots, &dabs, &dpvs, &dperms))) return rc;
     if (h->band_plan == 2) {
@@ -499,6 +495,7 @@ static int band_solve_batch(feasthip_ctx* h, int ld, int m, const std::vector<in
         const size_t esz = h->band_prec == 32 ? sizeof(cplxf) : sizeof(cplx);
         if ((rc = fh_get_buf(h, "bd_ypanel", (size_t)nf * bstride * esz, &Yb))) return rc;
         if ((rc = fh_get_buf(h, "bd_zpanel", (size_t)nf * bstride * esz, &Zb))) return rc;
+        if (h->adjoint) return fh_wband_solve_adjoint(h, nf, (void**)dabs, dpvs, dperms, h->band_perm, RHS, rhs_stride, Y, stride, Yb, Zb, ld, m, h->band_kl, h->band_ku);
         return fh_wband_solve(h, h->band_prec, nf, (void**)dabs, dpvs, dperms, h->band_perm, RHS, rhs_stride, Y, stride, Yb, Zb, ld, m, h->band_kl, h->band_ku);
     }
     fh_prof_begin(h, "band_solve");
@@ -617,13 +614,19 @@ int fh_banded_solve_single(feasthip_ctx* h, int ld, int m, cplx z, const cplx* R
 }
 
 // The adjoint switch on a CSR handle (fh_api.hip: fh_check_adjoint): the plan is made if need be and must be the multifrontal
-// one -- the band plans have no conjugate-transposed substitution.
+// one or the blocked band LU with complex128 factors (fh_wband_solve_adjoint) -- the narrow one-workgroup plan has no
+// conjugate-transposed substitution.
 int fh_banded_adjoint_ready(feasthip_ctx* h) {
     const int rc = band_check(h);
     if (rc) return rc;
     if (h->band_plan == 3) return 0;
-    h->last_error = std::string("the direct plan of this matrix is the ") + (h->band_plan == 1 ? "narrow band LU (plan 1)" : "blocked band LU (plan 2)") +
-                    ", which has no adjoint substitution: declare the need with feasthip_require_adjoint before the plan is made";
+    if (h->band_plan == 2) {
+        if (h->factor_precision != 32) return 0;
+        h->last_error = "the direct plan of this matrix is the blocked band LU (plan 2) with complex64 factors; its adjoint substitution needs complex128 factors";
+        return FEASTHIP_ERROR_FPM;
+    }
+    h->last_error = "the direct plan of this matrix is the narrow band LU (plan 1), which has no adjoint substitution: declare the need with "
+                    "feasthip_require_adjoint before the plan is made";
     return FEASTHIP_ERROR_FPM;
 }
 

@@ -2020,7 +2020,8 @@ __global__ __launch_bounds__(FH_BLOCK) void k_wband_form(const int* __restrict__
 // The row interchanges piv[K0 .. K0 + nbk) of one block column applied to the rows [K0, K0 + W) of row-major panels:
 // the swaps are composed on row INDICES in LDS (one thread, nbk short steps), the (at most 2 nbk) rows that end up
 // somewhere else are read by all threads into registers and written to their places.  grid (ld / 16, nodes).
-template <typename T>
+// REVERSE: the inverse permutation -- the same interchanges composed last to first (adjoint sweep, wband_solve_adjoint_launch).
+template <typename T, bool REVERSE = false>
 __global__ __launch_bounds__(FH_BLOCK) void k_wband_swap(int* const* pivs, T* Y, size_t stride, int ld, int K0, int nbk, int W) {
     extern __shared__ int wb_cur[];          // [W] original row (relative to K0) now at position i
     __shared__ int s_dst[2 * WB], s_src[2 * WB];
@@ -2032,9 +2033,16 @@ __global__ __launch_bounds__(FH_BLOCK) void k_wband_swap(int* const* pivs, T* Y,
     if (t == 0) s_cnt = 0;
     __syncthreads();
     if (t == 0) {
-        for (int j = 0; j < nbk; ++j) {
-            const int p = piv[j] - K0;
-            if (p != j && p >= 0 && p < W) { const int u = wb_cur[j]; wb_cur[j] = wb_cur[p]; wb_cur[p] = u; }
+        if constexpr (!REVERSE) {
+            for (int j = 0; j < nbk; ++j) {
+                const int p = piv[j] - K0;
+                if (p != j && p >= 0 && p < W) { const int u = wb_cur[j]; wb_cur[j] = wb_cur[p]; wb_cur[p] = u; }
+            }
+        } else {
+            for (int j = nbk - 1; j >= 0; --j) {
+                const int p = piv[j] - K0;
+                if (p != j && p >= 0 && p < W) { const int u = wb_cur[j]; wb_cur[j] = wb_cur[p]; wb_cur[p] = u; }
+            }
         }
     }
     __syncthreads();
@@ -2224,6 +2232,128 @@ static void wband_solve_launch(feasthip_ctx* h, T** dbases, int** dpvs, T* Y, T*
         if (r0 < K0)
             hipLaunchKernelGGL((k_solve_update<LD, false, T>), dim3((K0 - r0 + 63) / 64, nf), dim3(FH_BLOCK), 0, h->stream, dbases, Z, Y, stride, geom, K0, Kend - K0, r0, K0, cta);
     }
+}
+
+// Left-looking step of the adjoint band sweep (below): the rows of block column [K0, Kend) take what the rows under them
+// already hold,
+//     V[K0+r, :] -= sum_{i in [Kend, nr)} conj(L[i, K0+r]) V[i, :],
+// 128 output rows against a contraction of up to kl.  k_solve_update<LD, true> computes the same from (2, nodes) workgroups
+// that each walk the whole of k; on a serial chain of block steps that leaves most of the chip idle, so here one workgroup
+// owns ONE 16 x 16 output tile -- grid (row tiles of the block, column tiles, nodes) -- and its four waves split k in
+// 16-row chunks (wave w: chunks w, w + 4, ...).  Both operands come straight from global memory: lane (lr, lk) reads stored
+// column K0 + 16 tile + lr of L at four consecutive rows per k-group (op_at<true>, lu_conj) and row i of the panel at
+// column lr, the next chunk in flight while the current one is multiplied.  The partial tiles of waves 1..3 go through LDS
+// (lane-contiguous doubles: conflict-free) and wave 0 adds them in wave order: no atomics, the same bits every call.
+template <int LD, typename T>
+__global__ __launch_bounds__(FH_BLOCK) void k_wband_update_adj(T* const* LUs, T* V, size_t stride, lu_geom g, int K0, int Kend, int nr) {
+    typedef decltype(T().x) ET;
+    constexpr int KC = SOLVE_KC, NW = FH_BLOCK / 64;
+    __shared__ ET red[NW - 1][2][4][64];
+    const T* A = LUs[blockIdx.z];
+    T* v = V + (size_t)blockIdx.z * stride;
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int lr = lane & 15, lk = lane >> 4;
+    const int ib = K0 + 16 * blockIdx.x, c0 = 16 * blockIdx.y;
+    const int icol = ib + lr;                    // stored column of L: the output row this lane's factor operand belongs to
+    typename lu_el<T>::v4 re = {0, 0, 0, 0}, im = {0, 0, 0, 0};
+    T an[KC / 4], xn[KC / 4];
+#pragma unroll
+    for (int s = 0; s < KC / 4; ++s) { an[s] = LU_MK(0, 0); xn[s] = LU_MK(0, 0); }
+    auto load_chunk = [&](int j0) {
+#pragma unroll
+        for (int s = 0; s < KC / 4; ++s) {
+            const int i = j0 + 4 * s + lk;
+            an[s] = (i < nr && icol < Kend) ? op_at<true>(A, g.ld, icol, i) : LU_MK(0, 0);
+            an[s] = lu_conj(an[s]);
+            xn[s] = i < nr ? v[(size_t)i * LD + c0 + lr] : LU_MK(0, 0);
+        }
+    };
+    int j0 = Kend + KC * wave;
+    if (j0 < nr) load_chunk(j0);
+    for (; j0 < nr; j0 += KC * NW) {
+        T ac[KC / 4], xc[KC / 4];
+#pragma unroll
+        for (int s = 0; s < KC / 4; ++s) { ac[s] = an[s]; xc[s] = xn[s]; }
+        if (j0 + KC * NW < nr) load_chunk(j0 + KC * NW);
+#pragma unroll
+        for (int s = 0; s < KC / 4; ++s) {
+            re = lu_el<T>::mfma(ac[s].x, xc[s].x, re);
+            im = lu_el<T>::mfma(ac[s].x, xc[s].y, im);
+            re = lu_el<T>::mfma(-ac[s].y, xc[s].y, re);
+            im = lu_el<T>::mfma(ac[s].y, xc[s].x, im);
+        }
+    }
+    if (wave > 0) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) { red[wave - 1][0][r][lane] = re[r]; red[wave - 1][1][r][lane] = im[r]; }
+    }
+    __syncthreads();
+    if (wave > 0) return;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        ET sr = re[r], si = im[r];
+#pragma unroll
+        for (int w = 0; w < NW - 1; ++w) { sr += red[w][0][r][lane]; si += red[w][1][r][lane]; }
+        const int i = ib + lu_el<T>::mrow(lk, r);
+        if (i < Kend) {
+            T* d = v + (size_t)i * LD + c0 + lr;
+            const T y = *d;
+            *d = LU_MK(y.x - sr, y.y - si);
+        }
+    }
+}
+
+// The adjoint of wband_solve_launch (ZGBTRS 'C').  The interchanges of block column b were not applied to the block columns
+// left of it, so S = P_0 L_0 P_1 L_1 ... U and  S^-H = P_0 L_0^-H P_1 L_1^-H ... U^-H,  read right to left:
+//   up    U^H w = b, blocks ascending (U^H is lower triangular): w_b = U11^-H y_b, then the rows below, as far as the block
+//         row of U reaches (kl + ku), take  y[i] -= sum_k conj(U[K0+k, i]) w[K0+k]  -- right-looking, as the dense adjoint (Y -> Z)
+//   down  blocks descending, in place in Z:  v_b -= L21^H v[Kend:nr)  (k_wband_update_adj),  v_b = L11^-H v_b,  then the
+//         INVERSE of the block's interchanges on the rows [K0, nr).  Left-looking of necessity: those interchanges move rows
+//         the later (earlier-numbered) blocks have yet to read, so an update pushed into them ahead of time would not commute.
+// k_solve_diag_inv may run in place: a workgroup reads its column tile of the slab into LDS before it writes any of it.
+// The result is left in Z.
+template <int LD, typename T>
+static void wband_solve_adjoint_launch(feasthip_ctx* h, T** dbases, int** dpvs, T* Y, T* Z, size_t stride, const wband_geom& w, int nf, int m) {
+    const int N = w.N, kl = w.kl, kv = w.kl + w.ku;
+    const lu_geom geom = w.g;
+    const int cta = std::max(1, std::min(LD / 16, (m + 15) / 16));
+    const int nouter = (N + SOLVE_KB - 1) / SOLVE_KB;
+    for (int b = 0; b < nouter; ++b) {
+        const int K0 = b * SOLVE_KB, Kend = std::min(N, K0 + SOLVE_KB);
+        const int kb = (Kend - K0 + LU_NB - 1) / LU_NB;
+        hipLaunchKernelGGL((k_solve_diag_inv<LD, true, true, T>), dim3(cta, nf), dim3(FH_BLOCK), 0, h->stream, dbases, Y, Z, stride, geom, K0, kb);
+        const int r1 = std::min(N, Kend + kv);
+        if (Kend < r1)
+            hipLaunchKernelGGL((k_solve_update<LD, true, T>), dim3((r1 - Kend + 63) / 64, nf), dim3(FH_BLOCK), 0, h->stream, dbases, Y, Z, stride, geom, K0, Kend - K0, Kend, r1, cta);
+    }
+    for (int b = nouter - 1; b >= 0; --b) {
+        const int K0 = b * SOLVE_KB, Kend = std::min(N, K0 + SOLVE_KB);
+        const int kb = (Kend - K0 + LU_NB - 1) / LU_NB;
+        const int nr = std::min(N, Kend + kl);
+        if (Kend < nr)
+            hipLaunchKernelGGL((k_wband_update_adj<LD, T>), dim3((Kend - K0 + 15) / 16, cta, nf), dim3(FH_BLOCK), 0, h->stream, dbases, Z, stride, geom, K0, Kend, nr);
+        hipLaunchKernelGGL((k_solve_diag_inv<LD, false, true, T>), dim3(cta, nf), dim3(FH_BLOCK), 0, h->stream, dbases, Z, Z, stride, geom, K0, kb);
+        hipLaunchKernelGGL((k_wband_swap<T, true>), dim3(LD / 16, nf), dim3(FH_BLOCK), (size_t)(nr - K0) * sizeof(int), h->stream, dpvs, Z, stride, LD, K0, Kend - K0, nr - K0);
+    }
+}
+
+// Y[node] = (z_node B - A)^-H RHS on the factors of fh_wband_factor (complex128).  The band order is a symmetric permutation
+// of the matrix, so the right-hand side is gathered and the result scattered with the same perm arrays as in fh_wband_solve.
+int fh_wband_solve_adjoint(feasthip_ctx* h, int nf, void** dbases, int** dpvs, int** dperms, const int* d_perm, const cplx* RHS, size_t rhs_stride,
+                           cplx* Y, size_t stride, void* Yb, void* Zb, int ld, int m, int kl, int ku) {
+    const int N = (int)h->csr.N;
+    const wband_geom w = wband_geometry(N, kl, ku);
+    const size_t bstride = (size_t)N * ld;
+    cplx* const P = (cplx*)Yb;
+    cplx* const Q = (cplx*)Zb;
+    fh_prof_begin(h, "wband_solve_adjoint");
+    hipLaunchKernelGGL((k_gather_rows<cplx>), dim3(fh_vec_nblk(N, ld), nf), dim3(FH_BLOCK), 0, h->stream, RHS, rhs_stride, dperms, P, bstride, N, ld);
+    if (ld == 16) wband_solve_adjoint_launch<16, cplx>(h, (cplx**)dbases, dpvs, P, Q, bstride, w, nf, m);
+    else if (ld == 32) wband_solve_adjoint_launch<32, cplx>(h, (cplx**)dbases, dpvs, P, Q, bstride, w, nf, m);
+    else wband_solve_adjoint_launch<64, cplx>(h, (cplx**)dbases, dpvs, P, Q, bstride, w, nf, m);
+    hipLaunchKernelGGL((k_scatter_rows<cplx>), dim3(fh_vec_nblk(N, ld), nf), dim3(FH_BLOCK), 0, h->stream, Q, bstride, d_perm, Y, stride, N, ld);
+    fh_prof_end(h);
+    return 0;
 }
 
 // Y[node] = (z_node B - A)^-1 RHS with the factors of fh_wband_factor.  RHS: one shared panel (row-major N x ld, the

@@ -41,6 +41,9 @@ int fh_wband_factor(feasthip_ctx* h, int prec, int nf, void* const* abs_host, vo
                     const int* d_iperm, int kl, int ku);
 int fh_wband_solve(feasthip_ctx* h, int prec, int nf, void** dbases, int** dpvs, int** dperms, const int* d_perm, const cplx* RHS, size_t rhs_stride,
                    cplx* Y, size_t stride, void* Yb, void* Zb, int ld, int m, int kl, int ku);
+// Y[node] = (z_node B - A)^-H RHS on the same factors (ZGBTRS 'C'; complex128 factors only), same arguments
+int fh_wband_solve_adjoint(feasthip_ctx* h, int nf, void** dbases, int** dpvs, int** dperms, const int* d_perm, const cplx* RHS, size_t rhs_stride,
+                           cplx* Y, size_t stride, void* Yb, void* Zb, int ld, int m, int kl, int ku);
 
 // Multifrontal sparse LU (fh_dense.hip, symbolic phase fh_mf.hpp): plan from the host pattern, batched numeric factorisation
 // of nf shifted matrices into per-node stores, substitution through the elimination tree.  prec 64: complex128 factors; 32: complex64 factors (refinement is the caller's).

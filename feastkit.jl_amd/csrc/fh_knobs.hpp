@@ -65,8 +65,8 @@ inline bool eig_no_lds() { static const bool v = present("FH_EIG_NO_LDS"); retur
 // ---- blocked LU (dense, band, fronts) ----
 // outer block column of the two-level LU, rounded down to a multiple of 32, at least 32; dflt 0 = by size.  Per handle (lu_outer_block).
 inline int lu_kb(int dflt) { return present("FH_LU_KB") ? std::max(32, int_or("FH_LU_KB", 0) / 32 * 32) : dflt; }
-// 32-column one-launch substitution steps (forward solves only: the adjoint substitution of feasthip_set_adjoint always takes
-// the two-level 128-column path).  Per handle (lu_solve_legacy).
+// 32-column one-launch substitution steps of the dense LU (forward solves only: the adjoint substitutions of
+// feasthip_set_adjoint -- dense, multifrontal and blocked band alike -- always take the 128-column path).  Per handle (lu_solve_legacy).
 inline bool lu_solve_32() { return present("FH_LU_SOLVE_32"); }
 // trailing update with both panels staged through LDS.  Per handle (lu_gemm_staged).
 inline bool lu_gemm_staged() { return present("FH_LU_GEMM_STAGED"); }

@@ -243,13 +243,14 @@ class HipEngine:
     def set_adjoint(self, on):
         """While on, contour_apply, shifted_solve, matmul and ritz_residual act with the conjugate transposes
         (feasthip_set_adjoint): the solves reuse the LU factors the forward solves cached.  Dense problems with the
-        direct solver, sparse problems with the sparse direct solver under its multifrontal plan (require_adjoint), in
-        fp64 only; persists on the engine."""
+        direct solver, sparse problems with the sparse direct solver under its multifrontal plan or its blocked band LU
+        (require_adjoint; the narrow one-workgroup band plan has no adjoint form), in fp64 only; persists on the engine."""
         self._chk(self.lib.feasthip_set_adjoint(self.h, int(bool(on))))
 
     def require_adjoint(self, on):
-        """While on, the sparse direct solver plans for a CSR problem what has an adjoint substitution, i.e. the
-        multifrontal LU (feasthip_require_adjoint): set before the first plan query or solve; persists on the engine."""
+        """While on, the sparse direct solver plans for a CSR problem what has an adjoint substitution: the multifrontal
+        LU, or -- where that plan does not exist for the pattern, or rejects a pivot -- the blocked band LU, never the
+        narrow band plan (feasthip_require_adjoint): set before the first plan query or solve; persists on the engine."""
         self._chk(self.lib.feasthip_require_adjoint(self.h, int(bool(on))))
 
     def set_node_range(self, first, count):

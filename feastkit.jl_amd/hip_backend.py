@@ -1036,8 +1036,9 @@ def check_two_sided(sparse, solver, inner_precision=64, group=None, direct_nodes
 def feast_hip_general_two_sided(engine, A, B, Emid, r, M0, fpm, *, solver="direct", Q0=None, QL0=None, seed=20260515,
                                 contour=None, eps_floor=0.0):
     """Two-sided FEAST on a dense pencil, or on a sparse one under the sparse direct solver (``solver="banded"``: the
-    multifrontal plan, declared with engine.require_adjoint): right and left subspaces from the same cached LU factors,
-    oblique projection.
+    multifrontal plan, or the blocked band LU where that plan is missing or rejects a pivot, declared with
+    engine.require_adjoint): right and left subspaces from the same cached LU factors, oblique projection.
+    ``stats["two_sided"]["direct_plan"]`` names the factors that ran, ``fell_back`` whether they are not the ones planned.
 
         P_R = sum_e w_e S_e^-1 B Q_R                (forward sweep; factors cached per node)
         P_L = sum_e conj(w_e) S_e^-H B^H Q_L        (adjoint sweep: conjugate-transposed substitution, no factorisation)
@@ -1079,12 +1080,17 @@ def feast_hip_general_two_sided(engine, A, B, Emid, r, M0, fpm, *, solver="direc
           "seconds": {"forward_sweep": 0.0, "adjoint_sweep": 0.0, "rayleigh_ritz": 0.0}}
     stats["two_sided"] = ts
     tick = time.perf_counter
+    def plan_name():
+        if not sparse:
+            return "dense LU"
+        return ("multifrontal LU on a nested-dissection tree" if engine.band_plan()[3] == 2
+                else "band LU after reverse Cuthill-McKee")
+
     try:
-        if sparse:
-            ts["direct_plan"] = ("multifrontal LU on a nested-dissection tree" if engine.band_plan()[3] == 2
-                                 else "band LU after reverse Cuthill-McKee")
-        else:
-            ts["direct_plan"] = "dense LU"
+        # the plan as made; a multifrontal LU that rejects a pivot hands the matrix to the band LU inside the first sweep, so
+        # the name is read again after every pair of sweeps: it names the factors that ran
+        planned = ts["direct_plan"] = plan_name()
+        ts["fell_back"] = False
         with small_lapack():
             while True:
                 t0 = tick()
@@ -1098,6 +1104,9 @@ def feast_hip_general_two_sided(engine, A, B, Emid, r, M0, fpm, *, solver="direc
                 t2 = tick()
                 ts["seconds"]["forward_sweep"] += t1 - t0
                 ts["seconds"]["adjoint_sweep"] += t2 - t1
+                if sparse:
+                    ts["direct_plan"] = plan_name()
+                    ts["fell_back"] = ts["fell_back"] or ts["direct_plan"] != planned
                 if fail:
                     return _empty_result(N, FeastError.Feast_ERROR_LAPACK if fail == 8 else FeastError.Feast_ERROR_NO_CONVERGENCE,
                                          loop, complex_lambda=True, stats=stats)

@@ -443,11 +443,14 @@ int  feasthip_ritz_residual_dev(feasthip_handle h, int64_t r, const void* dQ, co
  *   The solves are conjugate-transposed substitutions (ZGETRS 'C') on the LU factors the forward solves cache, matched by z_e
  *   in the same slots: an adjoint sweep after a forward sweep on the same contour reports stats.factorizations == 0.
  *   A dense problem needs FEASTHIP_SOLVER_LU.  A CSR problem needs FEASTHIP_SOLVER_BANDED with the MULTIFRONTAL direct plan
- *   (feasthip_band_plan: blocked == 2): the substitution walks the front tree conjugate-transposed (U^H leaves first, L^H and
- *   the fronts' row permutations root first) and the products run on a conjugate-transposed copy of the CSR set, built at the
- *   first adjoint product (one device-to-host copy of the values) and kept until the problem changes.
+ *   (feasthip_band_plan: blocked == 2) or the BLOCKED BAND LU (blocked == 1).  Multifrontal: the substitution walks the front
+ *   tree conjugate-transposed (U^H leaves first, L^H and the fronts' row permutations root first).  Blocked band LU: ZGBTRS 'C'
+ *   on the band factors -- U^H block by block ascending, then per block descending L^H (left-looking) and the block's row
+ *   interchanges undone in reverse order; gather and scatter by the band order as in the forward solve.  The products run on a
+ *   conjugate-transposed copy of the CSR set, built at the first adjoint product (one device-to-host copy of the values) and
+ *   kept until the problem changes.
  *   While it is on, FEASTHIP_ERROR_FPM (feasthip_last_error names the reason, nothing is computed) answers: FEASTHIP_SOLVER_LU on
- *   a CSR problem, the Krylov solvers, a band plan (1 or 2; the message names it), feasthip_set_node_solver kinds,
+ *   a CSR problem, the Krylov solvers, the narrow band plan (plan 1; the message names it), feasthip_set_node_solver kinds,
  *   factor_precision = 32, the real projection, a non-NULL moment matrix, an attached communicator, the resident entry points,
  *   feasthip_estimate_count and feasthip_rayleigh_ritz_dev.
  *   Every other entry point is unaffected: feasthip_project[_dev] and feasthip_project_pair[_dev] always apply A and B
@@ -457,12 +460,13 @@ int  feasthip_ritz_residual_dev(feasthip_handle h, int64_t r, const void* dQ, co
  *   Independent of the adjoint switch.
  * feasthip_require_adjoint: persistent on the handle, off by default; a capability the driver declares, not a tuning switch.
  *   While it is on, the direct plan of a CSR problem is the multifrontal one whenever one can be made (as FH_MF=1 does), because
- *   the band plans have no adjoint substitution: a cached plan of another kind for the same matrix is dropped with its factors
- *   when the plan is next needed; a pivot rejection does not fall back to the band LU but reports node status 8
- *   (FEASTHIP_ERROR_LAPACK; feasthip_last_error says so); a pattern with no multifrontal plan (a front beyond 16 384 rows)
- *   answers FEASTHIP_ERROR_FPM.  Set it before the first plan query or solve.  A plan made while it was on is dropped in turn,
- *   with its factors, when the plan is next needed with the requirement off: calls that never asked for an adjoint keep the plan
- *   and the results they had.  No effect on dense problems.                                                                */
+ *   the narrow band plan has no adjoint substitution: a cached plan of another kind for the same matrix that was not made under
+ *   the requirement is dropped with its factors when the plan is next needed.  A pivot rejection falls back to the blocked band
+ *   LU as it does without the requirement, and a pattern with no multifrontal plan (a front beyond 16 384 rows) takes the
+ *   blocked band LU from the start; such a band plan is kept while the requirement stays on (no re-planning, the cached
+ *   factors serve both directions).  Set it before the first plan query or solve.  A plan made while it was on is dropped in
+ *   turn, with its factors, when the plan is next needed with the requirement off: calls that never asked for an adjoint keep
+ *   the plan and the results they had.  No effect on dense problems.                                                        */
 int  feasthip_set_adjoint(feasthip_handle h, int on);
 int  feasthip_require_adjoint(feasthip_handle h, int on);
 int  feasthip_project_pair(feasthip_handle h, int64_t r, const void* QL, const void* QR, void* Aq, void* Bq);

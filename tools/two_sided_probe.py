@@ -9,6 +9,9 @@ and the two-sided solve's split into forward sweep, adjoint sweep and Rayleigh-R
                                its multifrontal plan.  Also printed: forward and adjoint contour_apply on the SAME cached
                                factors (median of five alternating sweeps), and the first adjoint product of the handle (the
                                lazy build of the conjugate-transposed CSR set) against the second.
+  --workload sparse --plan band  the same in a child process with FH_MF_MAX_MULTIPLIER=0: the multifrontal LU rejects every
+                               matrix, so every solve and both sweeps run on the blocked band LU (kl = ku = 951 after reverse
+                               Cuthill-McKee); each solve then includes the rejected multifrontal factorisation.
 
     python tools/two_sided_probe.py [--workload sparse]                        # timing
     rocprofv3 --kernel-trace --stats -- python tools/two_sided_probe.py --once two_sided    # device time per kernel: the
@@ -17,6 +20,7 @@ and the two-sided solve's split into forward sweep, adjoint sweep and Rayleigh-R
 import argparse
 import json
 import os
+import subprocess
 import sys
 import time
 
@@ -72,7 +76,6 @@ def sparse_sweeps(A, B, center, radius, M0, nodes, runs):
         eng.set_real_projection(False)
         eng.set_node_range(0, len(Zne))
         eng.set_solver("banded")
-        plan = eng.band_plan()[3]
         dQ = eng.upload(fk.seeded_subspace(A.shape[0], M0))
         eng.matmul(1, dQ, M0)                               # forward product: kernels loaded, buffers made
         eng.synchronize()
@@ -97,6 +100,7 @@ def sparse_sweeps(A, B, center, radius, M0, nodes, runs):
                 if k:
                     (adj if on else fwd).append(ms)
         eng.set_adjoint(False)
+        plan = eng.band_plan()[3]                           # after the sweeps: the factors that ran (1 band, 2 multifrontal)
         print(json.dumps({"method": "sweeps_on_cached_factors", "direct_plan_blocked": plan, "nodes": len(Zne), "M0": M0,
                           "first_adjoint_product_ms": first[0], "second_adjoint_product_ms": first[1],
                           "forward_sweep_ms_median": float(np.median(fwd)), "adjoint_sweep_ms_median": float(np.median(adj)),
@@ -114,7 +118,15 @@ def main():
     ap.add_argument("--M0", type=int, default=None)
     ap.add_argument("--nodes", type=int, default=None)
     ap.add_argument("--runs", type=int, default=5)
+    ap.add_argument("--plan", default="library", choices=("library", "band"),
+                    help="band (sparse workload): run in a child with FH_MF_MAX_MULTIPLIER=0, i.e. on the band LU's factors")
     a = ap.parse_args()
+    if a.plan == "band":
+        if a.workload != "sparse":
+            ap.error("--plan band needs --workload sparse")
+        if os.environ.get("FH_MF_MAX_MULTIPLIER") != "0":
+            args = [sys.executable, os.path.abspath(__file__)] + sys.argv[1:]
+            sys.exit(subprocess.run(args, env=dict(os.environ, FH_MF_MAX_MULTIPLIER="0")).returncode)
     if a.workload == "sparse":
         A, B, lam = convection_pencil()
         center, radius = 0.08875, 0.08875
@@ -157,6 +169,7 @@ def main():
             row["biorthogonality"] = ts["biorthogonality"]
             row["min_overlap"] = float(np.min(ts["overlap"])) if len(ts["overlap"]) else None
             row["direct_plan"] = ts.get("direct_plan")
+            row["fell_back"] = ts.get("fell_back")
         print(json.dumps(row), flush=True)
     eng.close()
     if a.workload == "sparse":
