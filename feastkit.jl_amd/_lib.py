@@ -88,6 +88,12 @@ SYMBOLS = {
     "feasthip_release_factors": (_i, [_vp]),
     "feasthip_shifted_solve": (_i, [_vp, _d, _d, _i64, _vp, _vp, _ps]),
     "feasthip_shifted_solve_dev": (_i, [_vp, _d, _d, _i64, _vp, _vp, _ps]),
+    "feasthip_set_polynomial": (_i, [_vp, _i64, _i, _i, _vp, _vp]),
+    "feasthip_poly_solve_dev": (_i, [_vp, _d, _d, _i64, _vp, _vp, _ps]),
+    "feasthip_poly_contour_apply_dev": (_i, [_vp, _i64, _vp, _vp, _vp, _ps]),
+    "feasthip_poly_matmul_dev": (_i, [_vp, _i, _i64, _vp, _vp]),
+    "feasthip_poly_project_dev": (_i, [_vp, _i64, _vp, _vp, _vp]),
+    "feasthip_poly_ritz_residual_dev": (_i, [_vp, _i64, _vp, _vp, _vp, _i64, _i, _i, _vp, _vp, _vp]),
     "feasthip_last_node_iterations": (_i, [_vp, _vp, _i]),
     "feasthip_last_column_iterations": (_i, [_vp, _vp, _i]),
     "feasthip_last_global_node_iterations": (_i, [_vp, _vp, _i]),

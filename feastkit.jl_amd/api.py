@@ -13,7 +13,7 @@ import scipy.sparse as sp
 from .engine import HipEngine
 from .contour import feast_contour, feast_gcontour
 from .hip_backend import (DIRECT_SOLVERS, ESTIMATE_SEED, check_direct_nodes, check_ortho, check_two_sided, feast_hip_estimate,
-                          feast_hip_general, feast_hip_general_two_sided, feast_hip_hermitian)
+                          feast_hip_general, feast_hip_general_two_sided, feast_hip_hermitian, feast_hip_polynomial, POLY_RESIDUALS)
 from .parameters import feastdefault, feastinit
 from .types import FEAST_UNINITIALIZED, FeastHipError, FeastResult
 
@@ -584,6 +584,77 @@ def feast_general(A, B=None, center=0.0, radius=1.0, *, M0=10, fpm=None, backend
         res = _demote(res, cplx_lambda=True)
         res.q_left = None if ql is None else ql.astype(np.complex64)
     return res
+
+
+POLY_MAX_DEGREE = 8          # FEASTHIP_POLY_MAX_DEGREE
+POLY_DENSE_LIMIT = 12288     # sparse coefficients are expanded up to this size
+
+
+def feast_polynomial(coeffs, center, radius, *, M0=10, fpm=None, engine=None, device=0, Q0=None, contour=None, seed=None,
+                     keep_factors=False, residual="pencil"):
+    """feast_polynomial(coeffs, center, radius; M0, fpm): src/interfaces/feast_interfaces.jl:448-462, feast_pep! /
+    feast_gepev! / feast_hepev! / feast_sypev! (src/dense/feast_dense.jl:715-772, 946-979).  Eigenpairs of
+    P(lambda) x = 0, P(lambda) = coeffs[0] + lambda coeffs[1] + ... + lambda^d coeffs[d], with lambda inside the circle.
+    The reference builds the dN x dN companion pencil and factors it per node; here a node costs one LU of P(z_e), order N.
+
+    ``coeffs``: d + 1 square matrices of one size, 1 <= d <= 8, real or complex (float32 / complex64 input is promoted and
+    the result demoted as in feast_general).  Sparse coefficients are expanded up to N = 12 288
+    (``stats["solver_substitution"]``); beyond that ValueError.  ``M0`` (clipped to N) sizes the subspace: the loop runs
+    M0 d columns, as feast_pep! does.  ``Q0``: linearised start block, (d N) x (M0 d).
+    ``residual``: what ``res`` / ``epsout`` and the stop test measure on the unit linearised Ritz vector x of the companion
+    pencil (A_lin, B_lin):
+      "pencil" (default)  ||A_lin x - lambda B_lin x|| / max(|lambda|, 1)
+      "reference"         ||A_lin x - lambda x|| / max(|lambda|, 1), the reference's measure, which omits B_lin
+                          (src/kernel/feast_kernel.jl:899-906).  For coeffs[d] != I that measure never falls: the reference
+                          on a non-monic quadratic runs every loop and returns info = 0 with epsout = 0.34 while its
+                          eigenvalues are right to 6e-14.  That is why the default differs.
+    Result: FeastResult with complex ``lambda_`` (feast_sort_general order), ``q`` = the first N rows of the M linearised Ritz
+    vectors as the reference returns them (src/dense/feast_dense.jl:768), ``res`` in the chosen measure;
+    ``stats["polynomial"]`` = {degree, columns, residual, backward_error, eps_history} with backward_error[j] =
+    ||P(lambda_j) q_j|| / (sum_k |lambda_j|^k ||A_k||_F ||q_j||); ``stats["factorizations"]`` counts N x N factorisations.
+    ``keep_factors``, ``contour``, ``seed``: as in feast_general."""
+    mats = list(coeffs)
+    if len(mats) < 2:
+        raise ValueError("feast_polynomial needs at least two coefficient matrices (degree >= 1)")
+    if len(mats) - 1 > POLY_MAX_DEGREE:
+        raise ValueError(f"degree {len(mats) - 1} exceeds the supported maximum {POLY_MAX_DEGREE}")
+    shape = mats[0].shape
+    for c in mats:
+        if len(c.shape) != 2 or c.shape[0] != c.shape[1]:
+            raise ValueError("coefficient matrices must be square")
+        if c.shape != shape:
+            raise ValueError("coefficient matrices must have equal shapes")
+    if not radius > 0:
+        raise ValueError("radius must be positive")
+    if residual not in POLY_RESIDUALS:
+        raise ValueError(f"residual must be one of {POLY_RESIDUALS}, not {residual!r}")
+    N = shape[0]
+    substituted = None
+    if any(sp.issparse(c) for c in mats):
+        if N > POLY_DENSE_LIMIT:
+            raise ValueError(f"sparse coefficients are expanded to dense matrices up to N = {POLY_DENSE_LIMIT}; N = {N}")
+        mats = [_densify(c) if sp.issparse(c) else c for c in mats]
+        substituted = {"requested": "direct", "used": "dense LU of the expanded coefficients"}
+    mats = [np.asarray(c) for c in mats]
+    single = _single_precision(*mats)
+    if single:
+        mats = [_promote(c) for c in mats]
+    fpm = feastinit() if fpm is None else fpm
+    feastdefault(fpm)
+    M0 = min(int(M0), N)
+    eng = _engine(engine, device)
+    eps_floor = float(np.sqrt(np.finfo(np.float32).eps)) if single else 0.0
+    try:
+        res = feast_hip_polynomial(eng, mats, complex(center), float(radius), M0, fpm, Q0=Q0, contour=contour, residual=residual,
+                                   eps_floor=eps_floor, **({} if seed is None else {"seed": int(seed)}))
+        if substituted is not None and isinstance(res.stats, dict):
+            res.stats["solver_substitution"] = substituted
+    finally:
+        _release_band_factors(eng, keep_factors)          # (the N x N LU factors of the nodes)
+    return _demote(res, cplx_lambda=True) if single else res
+
+
+feast_pep = feast_polynomial
 
 
 def _feast_auto(driver, A, B, *where, fpm=None, engine=None, device=0, solver="direct", solver_tol=0.0,

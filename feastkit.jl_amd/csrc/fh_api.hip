@@ -181,7 +181,7 @@ static void fh_free_adjoint_csr(feasthip_ctx* h) {
     h->csr_adj = fh_csr();
 }
 
-static void fh_free_problem(feasthip_ctx* h) {
+void fh_free_problem(feasthip_ctx* h) {
     if (h->csr.rowptr) hipFree(h->csr.rowptr);
     if (h->csr.col) hipFree(h->csr.col);
     if (h->csr.aval) hipFree(h->csr.aval);
@@ -200,6 +200,8 @@ static void fh_free_problem(feasthip_ctx* h) {
     if (h->dense.A) hipFree(h->dense.A);
     if (h->dense.B) hipFree(h->dense.B);
     h->dense = fh_dense();
+    for (void* p : h->poly.coef) if (p) hipFree(p);
+    h->poly = fh_poly();
     for (void* p : h->lu_factors) if (p) hipFree(p);
     for (int* p : h->lu_pivots) if (p) hipFree(p);
     h->lu_factors.clear(); h->lu_pivots.clear(); h->lu_valid.clear(); h->lu_z.clear();
@@ -488,6 +490,7 @@ extern "C" int feasthip_set_real_projection(feasthip_handle h, int real_part) {
 
 extern "C" int feasthip_set_adjoint(feasthip_handle h, int on) {
     if (!h) return FEASTHIP_ERROR_INTERNAL;
+    if (on && h->kind == 3) { h->last_error = "feasthip_set_adjoint: a polynomial handle has no adjoint form (the feasthip_poly_* calls are forward only)"; return FEASTHIP_ERROR_FPM; }
     h->adjoint = on ? 1 : 0;
     return 0;
 }
@@ -504,6 +507,10 @@ extern "C" int feasthip_set_node_range(feasthip_handle h, int first, int count) 
         h->last_error = "feasthip_set_node_range: range outside the contour";
         return FEASTHIP_ERROR_FPM;
     }
+    if (h->kind == 3 && (first != 0 || count != (int)h->zne.size())) {
+        h->last_error = "feasthip_set_node_range: a polynomial handle sweeps the whole contour (feasthip_poly_contour_apply_dev runs on one rank)";
+        return FEASTHIP_ERROR_FPM;
+    }
     h->node_first = first;
     h->node_count = count;
     h->node_ids.resize(count);
@@ -514,6 +521,10 @@ extern "C" int feasthip_set_node_range(feasthip_handle h, int first, int count) 
 extern "C" int feasthip_set_node_list(feasthip_handle h, int count, const int* indices) {
     if (!h) return FEASTHIP_ERROR_INTERNAL;
     if (count < 0 || (count > 0 && !indices)) { h->last_error = "feasthip_set_node_list: bad arguments"; return FEASTHIP_ERROR_FPM; }
+    if (h->kind == 3) {
+        h->last_error = "feasthip_set_node_list: a polynomial handle sweeps the whole contour (feasthip_poly_contour_apply_dev runs on one rank)";
+        return FEASTHIP_ERROR_FPM;
+    }
     for (int e = 0; e < count; ++e)
         if (indices[e] < 0 || indices[e] >= (int)h->zne.size()) {
             h->last_error = "feasthip_set_node_list: index outside the contour";
@@ -539,6 +550,10 @@ extern "C" int feasthip_set_solver(feasthip_handle h, int kind, double rtol, dou
     if (kind < 0 || kind > FEASTHIP_SOLVER_BLOCK_COCG || rtol < 0 || atol < 0 || maxit <= 0 || restart < 0 ||
         (factor_precision != 64 && factor_precision != 32)) {
         h->last_error = "feasthip_set_solver: invalid option";
+        return FEASTHIP_ERROR_FPM;
+    }
+    if (h->kind == 3 && (kind != FEASTHIP_SOLVER_LU || factor_precision != 64)) {
+        h->last_error = "feasthip_set_solver: a polynomial handle needs FEASTHIP_SOLVER_LU with factor_precision = 64";
         return FEASTHIP_ERROR_FPM;
     }
     // SHIFTED_COCG is COCG with the shifted sweep where fh_contour_apply_panel finds it eligible: every other path sees COCG
@@ -660,6 +675,11 @@ static int fh_check_problem(feasthip_ctx* h, int64_t m, int wide = 0) {
     if (!h) return FEASTHIP_ERROR_INTERNAL;
     if (h->poisoned) { h->last_error = "handle poisoned by an earlier device failure: destroy it"; return FEASTHIP_ERROR_INTERNAL; }
     if (h->kind == 0) { h->last_error = "no matrix set (feasthip_set_dense / feasthip_set_csr)"; return FEASTHIP_ERROR_N; }
+    if (h->kind == 3) {     // every entry point that comes through here works on a pencil; the polynomial has its own (fh_poly.hip)
+        h->last_error = "this entry point does not take a polynomial handle (feasthip_set_polynomial): use feasthip_poly_solve_dev, "
+                        "feasthip_poly_contour_apply_dev, feasthip_poly_matmul_dev, feasthip_poly_project_dev or feasthip_poly_ritz_residual_dev";
+        return FEASTHIP_ERROR_FPM;
+    }
     if (m <= 0 || (!wide && m > FH_MAX_LD) || m > fh_N(h)) {
         h->last_error = wide ? "block width m must satisfy 1 <= m <= N" : "block width m must satisfy 1 <= m <= min(N, 64)";
         return FEASTHIP_ERROR_M0;
@@ -3138,6 +3158,7 @@ extern "C" int feasthip_resident_export(feasthip_handle h, int which, int64_t nc
     if (!h) return FEASTHIP_ERROR_INTERNAL;
     if (h->poisoned) { h->last_error = "handle poisoned by an earlier device failure: destroy it"; return FEASTHIP_ERROR_INTERNAL; }
     if (!dX) { h->last_error = "resident_export: null destination"; return FEASTHIP_ERROR_INTERNAL; }
+    if (h->kind == 3) { h->last_error = "resident_export: a polynomial handle has no resident panels (use the feasthip_poly_* calls)"; return FEASTHIP_ERROR_FPM; }
     const cplx* src = which == 0 ? h->rs_X : h->rs_P;
     const int have = which == 0 ? h->rs_X_m : h->rs_m, ld = which == 0 ? h->rs_X_ld : h->rs_ld;
     if (!src || ncols < 0 || ncols > have) { h->last_error = "resident_export: no such resident panel / too many columns"; return FEASTHIP_ERROR_M0; }

@@ -110,6 +110,15 @@ struct fh_dense {
     void* B = nullptr;
 };
 
+// Matrix polynomial P(lambda) = A_0 + lambda A_1 + ... + lambda^d A_d (feasthip_set_polynomial, fh_poly.hip): the d + 1
+// coefficients, N x N column-major, all double or all cplx; fro[k] = ||A_k||_F.  N and is_complex live in fh_dense.
+#define FH_POLY_MAX_DEGREE 8
+struct fh_poly {
+    int degree = 0;
+    void* coef[FH_POLY_MAX_DEGREE + 1] = {};
+    double fro[FH_POLY_MAX_DEGREE + 1] = {};
+};
+
 // Per-(node,column) Krylov scalars, struct of arrays; each array is [nodes][ld].
 struct fh_krylov_scalars {
     cplx* rho = nullptr;
@@ -138,7 +147,8 @@ struct feasthip_ctx {
     std::string last_error;
 
     // problem
-    int kind = 0;  // 0 none, 1 dense, 2 sparse
+    int kind = 0;  // 0 none, 1 dense, 2 sparse, 3 dense matrix polynomial (the feasthip_poly_* entry points only)
+    fh_poly poly;
     fh_csr csr;
     // conjugate transpose of `csr` (A^H, B^H on the transposed union pattern, internal numbering; rowptr / col / aval / bval only):
     // built at the first adjoint product of a CSR problem (fh_api.hip: fh_adjoint_csr_ensure), freed with the problem
@@ -255,6 +265,8 @@ template <typename T> inline int fh_buf(feasthip_ctx* h, const char* name, size_
     return rc;
 }
 void fh_free_bufs(feasthip_ctx* h);
+// frees the matrices, factors and plans of the current problem (any kind) and leaves h->kind = 0
+void fh_free_problem(feasthip_ctx* h);
 
 // profiling helpers
 void fh_prof_begin(feasthip_ctx* h, const char* cls);

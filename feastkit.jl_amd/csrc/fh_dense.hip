@@ -1618,8 +1618,9 @@ static int lu_factor_batch(feasthip_ctx* h, const std::vector<int>& which, const
     FH_CHECK(hipMemsetAsync(dinfo, 0, nf * sizeof(int), h->stream));
     FH_CHECK(hipStreamSynchronize(h->stream));
 
-    // form z B - A
-    {
+    // form z B - A (a polynomial handle: P(z), all nodes in one pass over the coefficients)
+    if (h->kind == 3) fh_poly_form(h, (void* const*)dlus, dz, nf, sizeof(T) == sizeof(cplx) ? 64 : 32);
+    else {
         dim3 grid(2048, nf), block(FH_BLOCK);
         fh_prof_begin(h, "lu_form");
         const bool bid = h->dense.b_identity != 0;

@@ -23,6 +23,10 @@ void fh_launch_dense_op_adjoint(const fh_dense_op_args& a, int ld, hipStream_t s
 // R -= X diag(lam)
 void fh_launch_axpy_cols(cplx* R, const cplx* X, const cplx* lam, int N, int ld, hipStream_t st, const int* skip = nullptr);
 
+// Polynomial handle (h->kind == 3, fh_poly.hip): LUs[e] = P(z_e) for the nf matrices lu_factor_batch is about to factor, in one
+// pass over the coefficients; prec 64: complex128 factors, 32: complex64.
+void fh_poly_form(feasthip_ctx* h, void* const* dlus, const cplx* dz, int nf, int prec);
+
 // Factor (cached per local node when h->cache_factors) and solve all local nodes:
 //   Y[e] = (z_e B - A)^{-1} RHS     RHS: one shared panel; Y: node-strided panels
 // (h->adjoint: (z_e B - A)^{-H} RHS by conjugate-transposed substitution on the same cached fp64 factors)

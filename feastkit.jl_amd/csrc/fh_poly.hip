@@ -1,0 +1,549 @@
+// fh_poly.hip -- polynomial eigenproblems P(lambda) x = 0, P(lambda) = A_0 + lambda A_1 + ... + lambda^d A_d (dense
+// coefficients), on ONE N x N LU per quadrature node (gfx950).
+//
+// Replaces  feast_pep!                 src/dense/feast_dense.jl:715-772  (companion pencil :745-760, feast_gegv! on it :763)
+//           feast_gepev!/hepev!/sypev! src/dense/feast_dense.jl:946-979
+// The reference builds the dN x dN first companion form
+//     A_lin = [ 0 I . . ; . . I . ; ... ; -A_0 ... -A_{d-1} ],   B_lin = diag(I, ..., I, A_d)
+// and factors z B_lin - A_lin per node.  The companion matrix is never formed here: for R = [R_0; ...; R_{d-1}] the system
+// (z B_lin - A_lin) Y = R is
+//     D_p      = sum_{k=0}^{min(d-2, d-1-p)} A_{k+1+p} R_k          p = 0 .. d-1      (node independent)
+//     P(z) Y_0 = R_{d-1} + sum_p z^p D_p                                                (one N x N solve)
+//     Y_{i+1}  = z Y_i - R_i                                          i = 0 .. d-2
+// so a node costs one LU of order N (the batched MFMA LU of fh_dense.hip, its factor cache included) instead of one of
+// order dN: d^3 times fewer flops, d^2 times less factor memory.
+//
+// Panels: a dN x m block is kept as ONE row-major (dN) x ld panel (fh_common.hpp), i.e. the d row-major N x ld panels of
+// its blocks one behind the other -- block i of a panel P is P + i N ld -- so the column-major <-> panel kernels, the Gram
+// kernel, the small product and the column dots of fh_blockops.hip take it as a tall panel, and the dense product kernel
+// takes one block of it.
+#include "fh_common.hpp"
+#include "fh_kernels.hpp"
+#include "fh_dense.hpp"
+#include "../../include/feasthip.h"
+
+#include <algorithm>
+#include <chrono>
+#include <cmath>
+#include <cstring>
+
+#define FH_BLOCK 256
+#define PD FH_POLY_MAX_DEGREE
+static_assert(FH_POLY_MAX_DEGREE == FEASTHIP_POLY_MAX_DEGREE, "degree bound of the ABI");
+
+struct fh_poly_ptrs { const void* c[PD + 1]; };
+
+__device__ inline cplx poly_val(cplx v) { return v; }
+__device__ inline cplx poly_val(double v) { return cmake(v, 0.0); }
+
+// ---------------------------------------------------------------------------------------
+// S_e = P(z_e) for the nf matrices about to be factored, in one pass over the coefficients: a thread owns matrix elements,
+// loads their d + 1 coefficient values once (16 B per lane for complex input) and runs Horner per node.  Traffic:
+// (d + 1) N^2 sizeof(VT) read, nf N^2 sizeof(T) written (k_form_shifted reads A and B once per node).
+// ---------------------------------------------------------------------------------------
+template <typename VT, typename T>
+__global__ __launch_bounds__(FH_BLOCK) void k_form_poly(fh_poly_ptrs P, int d, T* const* LUs, const cplx* __restrict__ z, int nf,
+                                                         size_t total) {
+    for (size_t e = (size_t)blockIdx.x * FH_BLOCK + threadIdx.x; e < total; e += (size_t)gridDim.x * FH_BLOCK) {
+        cplx a[PD + 1];
+#pragma unroll
+        for (int k = 0; k <= PD; ++k) a[k] = k <= d ? poly_val(((const VT*)P.c[k])[e]) : cmake(0, 0);
+        for (int q = 0; q < nf; ++q) {
+            const cplx zz = z[q];
+            cplx v = cmake(0, 0);
+#pragma unroll
+            for (int k = PD; k >= 0; --k)
+                if (k <= d) v = cadd(cmul(v, zz), a[k]);
+            LUs[q][e] = cvt<T>(v);
+        }
+    }
+}
+
+void fh_poly_form(feasthip_ctx* h, void* const* dlus, const cplx* dz, int nf, int prec) {
+    fh_poly_ptrs P;
+    for (int k = 0; k <= PD; ++k) P.c[k] = h->poly.coef[k];
+    const int d = h->poly.degree;
+    const size_t total = (size_t)h->dense.N * (size_t)h->dense.N;
+    const dim3 grid((unsigned)std::min<size_t>(2048, (total + FH_BLOCK - 1) / FH_BLOCK)), block(FH_BLOCK);
+    fh_prof_begin(h, "poly_form");
+    if (h->dense.is_complex) {
+        if (prec == 32) hipLaunchKernelGGL((k_form_poly<cplx, cplxf>), grid, block, 0, h->stream, P, d, (cplxf* const*)dlus, dz, nf, total);
+        else hipLaunchKernelGGL((k_form_poly<cplx, cplx>), grid, block, 0, h->stream, P, d, (cplx* const*)dlus, dz, nf, total);
+    } else {
+        if (prec == 32) hipLaunchKernelGGL((k_form_poly<double, cplxf>), grid, block, 0, h->stream, P, d, (cplxf* const*)dlus, dz, nf, total);
+        else hipLaunchKernelGGL((k_form_poly<double, cplx>), grid, block, 0, h->stream, P, d, (cplx* const*)dlus, dz, nf, total);
+    }
+    fh_prof_end(h);
+}
+
+// ---------------------------------------------------------------------------------------
+// RHS_e = R_last + sum_{p < nd} z_e^p D_p for every node in one pass: the nd + 1 panels are read once, ne panels written
+// (stride: what fh_dense_lu_solve_nodes takes as rhs_stride).  D: nd panels of `total` elements one behind the other.
+// ---------------------------------------------------------------------------------------
+__global__ __launch_bounds__(FH_BLOCK) void k_poly_rhs(const cplx* __restrict__ Rlast, const cplx* __restrict__ D, int nd,
+                                                        const cplx* __restrict__ z, int ne, cplx* __restrict__ RHS, size_t stride,
+                                                        size_t total) {
+    for (size_t e = (size_t)blockIdx.x * FH_BLOCK + threadIdx.x; e < total; e += (size_t)gridDim.x * FH_BLOCK) {
+        const cplx r = Rlast[e];
+        cplx dv[PD];
+#pragma unroll
+        for (int p = 0; p < PD; ++p) dv[p] = p < nd ? D[(size_t)p * total + e] : cmake(0, 0);
+        for (int q = 0; q < ne; ++q) {
+            const cplx zz = z[q];
+            cplx v = cmake(0, 0);
+#pragma unroll
+            for (int p = PD - 1; p >= 0; --p)
+                if (p < nd) v = cadd(cmul(v, zz), dv[p]);
+            RHS[(size_t)q * stride + e] = cadd(r, v);
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------
+// The sweep's epilogue in one pass over the nodes' Y_0 panels: per panel element d accumulators,
+//     y = Y_0e;  acc_0 += w_e y;  y = z_e y - R_i;  acc_{i+1} += w_e y   (i = 0 .. d-2),
+// and the d blocks of Q_proj = sum_e w_e Y_e written once.  No dN-row per-node panel exists.  R, OUT: tall panels (block i
+// at i * total).
+// ---------------------------------------------------------------------------------------
+__global__ __launch_bounds__(FH_BLOCK) void k_poly_expand_sum(const cplx* __restrict__ Y, size_t stride, const cplx* __restrict__ R,
+                                                               int d, const cplx* __restrict__ z, const cplx* __restrict__ w, int ne,
+                                                               cplx* __restrict__ OUT, size_t total) {
+    for (size_t e = (size_t)blockIdx.x * FH_BLOCK + threadIdx.x; e < total; e += (size_t)gridDim.x * FH_BLOCK) {
+        cplx acc[PD], r[PD - 1];
+#pragma unroll
+        for (int i = 0; i < PD; ++i) acc[i] = cmake(0, 0);
+#pragma unroll
+        for (int i = 0; i < PD - 1; ++i) r[i] = i < d - 1 ? R[(size_t)i * total + e] : cmake(0, 0);
+        for (int q = 0; q < ne; ++q) {
+            const cplx zz = z[q], ww = w[q];
+            cplx y = Y[(size_t)q * stride + e];
+            cfma(acc[0], ww, y);
+#pragma unroll
+            for (int i = 0; i < PD - 1; ++i)
+                if (i < d - 1) {
+                    y = csub(cmul(zz, y), r[i]);
+                    cfma(acc[i + 1], ww, y);
+                }
+        }
+#pragma unroll
+        for (int i = 0; i < PD; ++i)
+            if (i < d) OUT[(size_t)i * total + e] = acc[i];
+    }
+}
+
+// ---------------------------------------------------------------------------------------
+// Residuals of the Ritz pairs, fused with their column norms.  Per column c (lambda = lam[c]) three sums of squares over the
+// rows, as partial[block][3][ld]:
+//   [0]  || A_lin x - lambda B_lin x ||^2  (use_B = 0: || A_lin x - lambda x ||^2, the reference's measure,
+//        src/kernel/feast_kernel.jl:899-906): blocks i < d-1 are x_{i+1} - lambda x_i, the last one -T - lambda (U | x_{d-1})
+//        with T = sum_j A_j x_j and U = A_d x_{d-1}
+//   [1]  || sum_k lambda^k (A_k x_0) ||^2 = || P(lambda) x_0 ||^2 from the d + 1 product panels PK (Horner)
+//   [2]  || x_0 ||^2
+// X: tall panel; T, U: N x ld panels; PK: d + 1 panels one behind the other.
+// ---------------------------------------------------------------------------------------
+__global__ __launch_bounds__(FH_BLOCK) void k_poly_residual(const cplx* __restrict__ X, const cplx* __restrict__ T, const cplx* __restrict__ U,
+                                                             const cplx* __restrict__ PK, const cplx* __restrict__ lam, int d, int use_B,
+                                                             int ld, size_t total, double* __restrict__ partial) {
+    __shared__ double red[3][FH_BLOCK];
+    const int t = threadIdx.x;
+    const cplx l = lam[t % ld];
+    double s0 = 0.0, s1 = 0.0, s2 = 0.0;
+    for (size_t e = (size_t)blockIdx.x * FH_BLOCK + t; e < total; e += (size_t)gridDim.x * FH_BLOCK) {   // (the stride keeps the column)
+        cplx xp = X[e];
+        s2 += cabs2(xp);
+#pragma unroll
+        for (int b = 0; b < PD - 1; ++b)
+            if (b < d - 1) {
+                const cplx xn = X[(size_t)(b + 1) * total + e];
+                s0 += cabs2(csub(xn, cmul(l, xp)));
+                xp = xn;
+            }
+        const cplx bx = use_B ? U[e] : xp;
+        const cplx tt = T[e];
+        s0 += cabs2(cadd(tt, cmul(l, bx)));
+        cplx v = cmake(0, 0);
+#pragma unroll
+        for (int k = PD; k >= 0; --k)
+            if (k <= d) v = cadd(cmul(v, l), PK[(size_t)k * total + e]);
+        s1 += cabs2(v);
+    }
+    red[0][t] = s0; red[1][t] = s1; red[2][t] = s2;
+    __syncthreads();
+    if (t < ld) {
+        double a0 = 0.0, a1 = 0.0, a2 = 0.0;
+        for (int j = t; j < FH_BLOCK; j += ld) { a0 += red[0][j]; a1 += red[1][j]; a2 += red[2][j]; }
+        double* o = partial + (size_t)blockIdx.x * 3 * ld;
+        o[t] = a0; o[ld + t] = a1; o[2 * ld + t] = a2;
+    }
+}
+// out[3][ld] = sum over the blocks' partials, in block order
+__global__ __launch_bounds__(FH_BLOCK) void k_poly_residual_fin(const double* __restrict__ partial, int nblk, int n, double* __restrict__ out) {
+    for (int i = threadIdx.x; i < n; i += FH_BLOCK) {
+        double s = 0.0;
+        for (int b = 0; b < nblk; ++b) s += partial[(size_t)b * n + i];
+        out[i] = s;
+    }
+}
+
+// ---------------------------------------------------------------------------------------
+// host side
+// ---------------------------------------------------------------------------------------
+static inline double poly_now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+
+// What every feasthip_poly_* call needs: a polynomial handle in the one configuration the structured solve covers, and
+// 1 <= m <= maxm.  what: the entry point's name for the message.
+static int poly_check(feasthip_ctx* h, const char* what, int64_t m, int64_t maxm) {
+    if (!h) return FEASTHIP_ERROR_INTERNAL;
+    if (h->poisoned) { h->last_error = "handle poisoned by an earlier device failure: destroy it"; return FEASTHIP_ERROR_INTERNAL; }
+    const char* why = nullptr;
+    if (h->kind != 3) why = "needs a polynomial handle (feasthip_set_polynomial); a dense or CSR handle takes the entry points without poly_";
+    else if (h->solver != FEASTHIP_SOLVER_LU) why = "the solver must be FEASTHIP_SOLVER_LU";
+    else if (h->factor_precision != 64) why = "factor_precision = 32 is not supported (complex128 factors only)";
+    else if (h->adjoint) why = "the adjoint switch is not supported";
+    else if (h->comm) why = "an attached communicator is not supported (one rank)";
+    else if (h->node_count != (int)h->zne.size() || h->node_first != 0) why = "a node range or list is not supported (the whole contour on one rank)";
+    else
+        for (int e = 0; e < (int)h->node_ids.size(); ++e)
+            if (h->node_ids[e] != e) { why = "a node range or list is not supported (the whole contour on one rank)"; break; }
+    if (why) { h->last_error = std::string(what) + ": " + why; return FEASTHIP_ERROR_FPM; }
+    if (m <= 0 || m > maxm) { h->last_error = std::string(what) + ": block width out of range"; return FEASTHIP_ERROR_M0; }
+    return 0;
+}
+
+// small synchronous host -> device copy into a named workspace
+template <typename T> static int poly_upload(feasthip_ctx* h, const char* name, const std::vector<T>& host, T** dev) {
+    int rc = fh_buf(h, name, host.size(), dev);
+    if (rc) return rc;
+    FH_CHECK(hipMemcpyAsync(*dev, host.data(), host.size() * sizeof(T), hipMemcpyHostToDevice, h->stream));
+    FH_CHECK(hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+// the unit, minus-unit and zero coefficient vectors the dense product kernel selects with
+struct poly_coefs {
+    cplx *plus = nullptr, *minus = nullptr, *zero = nullptr;
+    int acquire(feasthip_ctx* h) {
+        std::vector<cplx> c(3 * FH_MAX_LD, cmake(0, 0));
+        for (int i = 0; i < FH_MAX_LD; ++i) { c[i] = cmake(1, 0); c[FH_MAX_LD + i] = cmake(-1, 0); }
+        cplx* d;
+        const int rc = poly_upload(h, "poly_coefs", c, &d);
+        if (rc) return rc;
+        plus = d; minus = d + FH_MAX_LD; zero = d + 2 * FH_MAX_LD;
+        return 0;
+    }
+};
+
+// Y = s A_k X (accumulate: Y += s A_k X), s = -1 when negate, on N x ld panels, through the dense product kernel with the
+// coefficient pointer in place of dense.A and no B.  (accumulate: the kernel's Y = Bvec - ca A X with Bvec = Y, every element
+// read and written by the one lane that owns it.)
+static void poly_product(feasthip_ctx* h, const poly_coefs& pc, int ld, int k, const cplx* X, cplx* Y, bool accumulate, bool negate) {
+    fh_dense_op_args a;
+    memset(&a, 0, sizeof(a));
+    a.A = h->poly.coef[k]; a.B = nullptr; a.N = (int)h->dense.N; a.is_complex = h->dense.is_complex; a.nodes = 1;
+    a.X = X; a.Y = Y;
+    a.coefB = pc.zero;
+    if (!accumulate) a.coefA = negate ? pc.minus : pc.plus;
+    else { a.coefA = negate ? pc.plus : pc.minus; a.Bvec = Y; }
+    fh_prof_begin(h, "dense_op");
+    fh_launch_dense_op(a, ld, fh_dense_op_nblk(a.N), h->stream);
+    fh_prof_end(h);
+}
+
+// W = A_lin X (which 0) or B_lin X (which 1) on tall panels: block shifts, -sum_j A_j X_j and A_d X_{d-1}
+static int poly_lin_product(feasthip_ctx* h, const poly_coefs& pc, int which, int ld, const cplx* X, cplx* W) {
+    const int d = h->poly.degree;
+    const size_t panel = (size_t)h->dense.N * ld;
+    cplx* last = W + (size_t)(d - 1) * panel;
+    if (d > 1) FH_CHECK(hipMemcpyAsync(W, which == 0 ? X + panel : X, (size_t)(d - 1) * panel * sizeof(cplx), hipMemcpyDeviceToDevice, h->stream));
+    if (which == 0) for (int j = 0; j < d; ++j) poly_product(h, pc, ld, j, X + (size_t)j * panel, last, j > 0, true);
+    else poly_product(h, pc, ld, d, X + (size_t)(d - 1) * panel, last, false, false);
+    return 0;
+}
+
+extern "C" int feasthip_set_polynomial(feasthip_handle h, int64_t N, int degree, int is_complex, const void* const* coeffs,
+                                       const int64_t* ld) {
+    if (!h) return FEASTHIP_ERROR_INTERNAL;
+    if (h->poisoned) { h->last_error = "handle poisoned by an earlier device failure: destroy it"; return FEASTHIP_ERROR_INTERNAL; }
+    if (N <= 0 || N > 65536) { h->last_error = "feasthip_set_polynomial: N out of range"; return FEASTHIP_ERROR_N; }
+    if (degree < 1 || degree > FEASTHIP_POLY_MAX_DEGREE) { h->last_error = "feasthip_set_polynomial: degree must be 1 .. FEASTHIP_POLY_MAX_DEGREE"; return FEASTHIP_ERROR_FPM; }
+    if (!coeffs || !ld) { h->last_error = "feasthip_set_polynomial: null argument"; return FEASTHIP_ERROR_N; }
+    for (int k = 0; k <= degree; ++k)
+        if (!coeffs[k] || ld[k] < N) { h->last_error = "feasthip_set_polynomial: bad coefficient pointer or leading dimension"; return FEASTHIP_ERROR_N; }
+    FH_CHECK(hipSetDevice(h->device));
+    FH_CHECK(hipStreamSynchronize(h->stream));
+    fh_free_problem(h);
+    const size_t es = is_complex ? sizeof(cplx) : sizeof(double);
+    h->dense.N = N; h->dense.is_complex = is_complex ? 1 : 0; h->dense.b_identity = 0;
+    h->poly.degree = degree;
+    for (int k = 0; k <= degree; ++k) {
+        FH_CHECK(hipMalloc(&h->poly.coef[k], (size_t)N * N * es));
+        FH_CHECK(hipMemcpy2D(h->poly.coef[k], (size_t)N * es, coeffs[k], (size_t)ld[k] * es, (size_t)N * es, (size_t)N, hipMemcpyHostToDevice));
+        // ||A_k||_F for the backward error (ingest arithmetic, once per problem)
+        const double* v = (const double*)coeffs[k];
+        const size_t per = is_complex ? 2 : 1;
+        double s = 0.0;
+        for (int64_t j = 0; j < N; ++j) {
+            const double* col = v + (size_t)j * ld[k] * per;
+            double sj = 0.0;
+            for (size_t i = 0; i < (size_t)N * per; ++i) sj += col[i] * col[i];
+            s += sj;
+        }
+        h->poly.fro[k] = std::sqrt(s);
+    }
+    h->adjoint = 0;
+    h->kind = 3;
+    return 0;
+}
+
+// Y = P(z)^-1 R, N x m column-major; the factor is cached in the slot of the contour node z equals, else in one extra slot
+extern "C" int feasthip_poly_solve_dev(feasthip_handle h, double z_re, double z_im, int64_t m64, const void* dR, void* dY,
+                                       feasthip_stats* stats) {
+    int rc = poly_check(h, "feasthip_poly_solve_dev", m64, 1 << 20);       // right-hand sides, not a subspace: any count
+    if (rc) return rc;
+    if (!dR || !dY) { h->last_error = "feasthip_poly_solve_dev: null argument"; return FEASTHIP_ERROR_INTERNAL; }
+    FH_CHECK(hipSetDevice(h->device));
+    const double t0 = poly_now();
+    const int N = (int)h->dense.N;
+    if (stats) memset(stats, 0, sizeof(*stats));
+    int worst = 0;
+    for (int64_t c0 = 0; c0 < m64; c0 += FH_MAX_LD) {
+        const int m = (int)std::min<int64_t>(FH_MAX_LD, m64 - c0), ld = fh_pick_ld(m);
+        const size_t panel = (size_t)N * ld;
+        cplx *Rhs, *Y;
+        if ((rc = fh_buf(h, "ps_rhs", panel, &Rhs))) return rc;
+        if ((rc = fh_buf(h, "ps_Y", panel, &Y))) return rc;
+        fh_launch_to_panel((const cplx*)dR + (size_t)c0 * N, N, N, m, Rhs, ld, h->stream);
+        int status = 0;
+        int64_t nfact = 0;
+        if ((rc = fh_dense_lu_solve_single(h, ld, m, cmake(z_re, z_im), Rhs, Y, &status, &nfact))) return rc;
+        fh_launch_from_panel(Y, ld, N, m, (cplx*)dY + (size_t)c0 * N, N, h->stream);
+        if (stats) stats->factorizations += nfact;
+        worst = std::max(worst, status);
+    }
+    FH_CHECK(hipStreamSynchronize(h->stream));
+    fh_prof_collect(h);
+    FH_CHECK(hipGetLastError());
+    if (stats) stats->seconds_total = poly_now() - t0;
+    return worst;
+}
+
+// Qproj = sum_e weight_scale w_e (z_e B_lin - A_lin)^-1 (B_lin Q) on dN x m column-major blocks
+extern "C" int feasthip_poly_contour_apply_dev(feasthip_handle h, int64_t m64, const void* dQ, void* dQproj, int* node_status,
+                                               feasthip_stats* stats) {
+    int rc = poly_check(h, "feasthip_poly_contour_apply_dev", m64, h && h->kind == 3 ? h->dense.N * h->poly.degree : 1);
+    if (rc) return rc;
+    if (!dQ || !dQproj) { h->last_error = "feasthip_poly_contour_apply_dev: null argument"; return FEASTHIP_ERROR_INTERNAL; }
+    if (h->zne.empty()) { h->last_error = "feasthip_poly_contour_apply_dev: no contour set (feasthip_set_contour)"; return FEASTHIP_ERROR_FPM; }
+    if (h->real_projection) { h->last_error = "feasthip_poly_contour_apply_dev: the real projection does not apply to a polynomial sweep"; return FEASTHIP_ERROR_FPM; }
+    FH_CHECK(hipSetDevice(h->device));
+    const double t0 = poly_now();
+    const int N = (int)h->dense.N, d = h->poly.degree, ne = (int)h->zne.size();
+    const int64_t dN = (int64_t)d * N;
+    if (stats) memset(stats, 0, sizeof(*stats));
+    if (node_status) for (int e = 0; e < ne; ++e) node_status[e] = 0;
+    poly_coefs pc;
+    if ((rc = pc.acquire(h))) return rc;
+    std::vector<cplx> zw(2 * (size_t)ne);
+    for (int e = 0; e < ne; ++e) { zw[e] = h->zne[e]; zw[ne + e] = cscale(h->wne[e], h->weight_scale); }
+    cplx* dzw;
+    if ((rc = poly_upload(h, "pc_zw", zw, &dzw))) return rc;
+    const int nd = d == 1 ? 0 : d;          // D panels the right-hand side reads (degree 1: none, the pencil's own sweep)
+    for (int64_t c0 = 0; c0 < m64; c0 += FH_MAX_LD) {
+        const int m = (int)std::min<int64_t>(FH_MAX_LD, m64 - c0), ld = fh_pick_ld(m);
+        const size_t panel = (size_t)N * ld;
+        cplx *Qs, *Rs, *D, *RHS, *Y, *OUT;
+        if ((rc = fh_buf(h, "pc_Q", (size_t)d * panel, &Qs))) return rc;
+        if ((rc = fh_buf(h, "pc_R", (size_t)d * panel, &Rs))) return rc;
+        if ((rc = fh_buf(h, "pc_D", (size_t)std::max(1, nd) * panel, &D))) return rc;
+        if ((rc = fh_buf(h, "pc_rhs", (size_t)ne * panel, &RHS))) return rc;
+        if ((rc = fh_buf(h, "pc_Y", (size_t)ne * panel, &Y))) return rc;
+        if ((rc = fh_buf(h, "pc_out", (size_t)d * panel, &OUT))) return rc;
+        fh_launch_to_panel((const cplx*)dQ + (size_t)c0 * dN, dN, (int)dN, m, Qs, ld, h->stream);
+        if ((rc = poly_lin_product(h, pc, 1, ld, Qs, Rs))) return rc;              // R = B_lin Q
+        // D_p = sum_k A_{k+1+p} R_k: d (d + 1) / 2 - 1 products per sweep, whatever the node count
+        for (int p = 0; p < nd; ++p)
+            for (int k = 0; k <= std::min(d - 2, d - 1 - p); ++k)
+                poly_product(h, pc, ld, k + 1 + p, Rs + (size_t)k * panel, D + (size_t)p * panel, k > 0, false);
+        const dim3 grid(fh_vec_nblk(N, ld)), block(FH_BLOCK);
+        fh_prof_begin(h, "poly_rhs");
+        hipLaunchKernelGGL(k_poly_rhs, grid, block, 0, h->stream, Rs + (size_t)(d - 1) * panel, D, nd, dzw, ne, RHS, panel, panel);
+        fh_prof_end(h);
+        std::vector<int> status;
+        int64_t nfact = 0;
+        if ((rc = fh_dense_lu_solve_nodes(h, ld, m, ne, h->zne, RHS, panel, Y, panel, status, &nfact))) return rc;
+        fh_prof_begin(h, "poly_expand");
+        hipLaunchKernelGGL(k_poly_expand_sum, grid, block, 0, h->stream, Y, panel, Rs, d, dzw, dzw + ne, ne, OUT, panel);
+        fh_prof_end(h);
+        fh_launch_from_panel(OUT, ld, (int)dN, m, (cplx*)dQproj + (size_t)c0 * dN, dN, h->stream);
+        if (stats) stats->factorizations += nfact;
+        if (node_status) for (int e = 0; e < ne; ++e) node_status[e] = std::max(node_status[e], status[e]);
+    }
+    FH_CHECK(hipStreamSynchronize(h->stream));
+    fh_prof_collect(h);
+    FH_CHECK(hipGetLastError());
+    if (stats) stats->seconds_total = poly_now() - t0;
+    return 0;
+}
+
+// Y = A_lin X (which 0) or B_lin X (which 1), dN x m column-major
+extern "C" int feasthip_poly_matmul_dev(feasthip_handle h, int which, int64_t m64, const void* dX, void* dY) {
+    int rc = poly_check(h, "feasthip_poly_matmul_dev", m64, h && h->kind == 3 ? h->dense.N * h->poly.degree : 1);
+    if (rc) return rc;
+    if (!dX || !dY || (which != 0 && which != 1)) { h->last_error = "feasthip_poly_matmul_dev: bad argument"; return FEASTHIP_ERROR_INTERNAL; }
+    FH_CHECK(hipSetDevice(h->device));
+    const int N = (int)h->dense.N, d = h->poly.degree;
+    const int64_t dN = (int64_t)d * N;
+    poly_coefs pc;
+    if ((rc = pc.acquire(h))) return rc;
+    for (int64_t c0 = 0; c0 < m64; c0 += FH_MAX_LD) {
+        const int m = (int)std::min<int64_t>(FH_MAX_LD, m64 - c0), ld = fh_pick_ld(m);
+        const size_t tall = (size_t)dN * ld;
+        cplx *Xs, *Ws;
+        if ((rc = fh_buf(h, "pm_X", tall, &Xs))) return rc;
+        if ((rc = fh_buf(h, "pm_W", tall, &Ws))) return rc;
+        fh_launch_to_panel((const cplx*)dX + (size_t)c0 * dN, dN, (int)dN, m, Xs, ld, h->stream);
+        if ((rc = poly_lin_product(h, pc, which, ld, Xs, Ws))) return rc;
+        fh_launch_from_panel(Ws, ld, (int)dN, m, (cplx*)dY + (size_t)c0 * dN, dN, h->stream);
+    }
+    FH_CHECK(hipStreamSynchronize(h->stream));
+    fh_prof_collect(h);
+    FH_CHECK(hipGetLastError());
+    return 0;
+}
+
+// Aq = Q^H A_lin Q, Sq = Q^H B_lin Q (raw products, r x r column-major on the host) by 64-column panels: block (i, j) is
+// Q_i^H (op Q_j), one linearised product per block column and operator, one Gram launch over the dN rows per block
+extern "C" int feasthip_poly_project_dev(feasthip_handle h, int64_t r64, const void* dQ, void* Aq_host, void* Sq_host) {
+    int rc = poly_check(h, "feasthip_poly_project_dev", r64, h && h->kind == 3 ? h->dense.N * h->poly.degree : 1);
+    if (rc) return rc;
+    if (!dQ || !Aq_host || !Sq_host) { h->last_error = "feasthip_poly_project_dev: null argument"; return FEASTHIP_ERROR_INTERNAL; }
+    FH_CHECK(hipSetDevice(h->device));
+    const int N = (int)h->dense.N, d = h->poly.degree, r = (int)r64;
+    const int64_t dN = (int64_t)d * N;
+    const int ld = r > FH_MAX_LD ? FH_MAX_LD : fh_pick_ld(r), npan = (r + ld - 1) / ld;
+    const size_t tall = (size_t)dN * ld, g2 = (size_t)ld * ld;
+    poly_coefs pc;
+    if ((rc = pc.acquire(h))) return rc;
+    cplx *Qi, *Qj, *W, *G, *gw;
+    if ((rc = fh_buf(h, "pp_Qi", tall, &Qi))) return rc;
+    if ((rc = fh_buf(h, "pp_Qj", tall, &Qj))) return rc;
+    if ((rc = fh_buf(h, "pp_W", 2 * tall, &W))) return rc;
+    if ((rc = fh_buf(h, "pp_G", 2 * g2, &G))) return rc;
+    if ((rc = fh_buf(h, "gram_work", fh_gram_work_elems(ld), &gw))) return rc;
+    cplx* const out[2] = {(cplx*)Aq_host, (cplx*)Sq_host};
+    std::vector<cplx> Gh(2 * g2);
+    for (int j = 0; j < npan; ++j) {
+        const int mj = std::min(ld, r - j * ld);
+        fh_launch_to_panel((const cplx*)dQ + (size_t)j * ld * dN, dN, (int)dN, mj, Qj, ld, h->stream);
+        for (int which = 0; which < 2; ++which)
+            if ((rc = poly_lin_product(h, pc, which, ld, Qj, W + which * tall))) return rc;
+        for (int i = 0; i < npan; ++i) {
+            const int mi = std::min(ld, r - i * ld);
+            const cplx* Ql = Qj;
+            if (i != j) { fh_launch_to_panel((const cplx*)dQ + (size_t)i * ld * dN, dN, (int)dN, mi, Qi, ld, h->stream); Ql = Qi; }
+            for (int which = 0; which < 2; ++which) {
+                fh_prof_begin(h, "gram");
+                fh_launch_gram(Ql, W + which * tall, (int)dN, ld, 0, gw, G + which * g2, h->stream);
+                fh_prof_end(h);
+            }
+            FH_CHECK(hipMemcpyAsync(Gh.data(), G, Gh.size() * sizeof(cplx), hipMemcpyDeviceToHost, h->stream));
+            FH_CHECK(hipStreamSynchronize(h->stream));
+            for (int which = 0; which < 2; ++which)
+                for (int c2 = 0; c2 < mj; ++c2)
+                    for (int c1 = 0; c1 < mi; ++c1)
+                        out[which][(size_t)(j * ld + c2) * r + i * ld + c1] = Gh[which * g2 + (size_t)c2 * ld + c1];
+        }
+    }
+    fh_prof_collect(h);
+    FH_CHECK(hipGetLastError());
+    return 0;
+}
+
+// X = Q V (dN x r), the first M columns scaled to unit length (normalize), and for j < M
+//   res[j]            = || A_lin x_j - lambda_j B_lin x_j || / max(|lambda_j|, 1)   (use_B = 0: without B_lin)
+//   backward_error[j] = || P(lambda_j) x_j^(0) || / (sum_k |lambda_j|^k ||A_k||_F  ||x_j^(0)||),  x^(0) = the first block
+extern "C" int feasthip_poly_ritz_residual_dev(feasthip_handle h, int64_t r64, const void* dQ, const void* V_host, const void* lambda,
+                                               int64_t M, int normalize, int use_B, void* dX, double* res, double* backward_error) {
+    int rc = poly_check(h, "feasthip_poly_ritz_residual_dev", r64, h && h->kind == 3 ? h->dense.N * h->poly.degree : 1);
+    if (rc) return rc;
+    if (!dQ || !V_host || !lambda || !dX || dQ == dX) { h->last_error = "feasthip_poly_ritz_residual_dev: null argument, or X aliases Q"; return FEASTHIP_ERROR_INTERNAL; }
+    if (M < 0 || M > r64) { h->last_error = "feasthip_poly_ritz_residual_dev: M out of range"; return FEASTHIP_ERROR_M0; }
+    FH_CHECK(hipSetDevice(h->device));
+    const int N = (int)h->dense.N, d = h->poly.degree, r = (int)r64;
+    const int64_t dN = (int64_t)d * N;
+    const int ld = r > FH_MAX_LD ? FH_MAX_LD : fh_pick_ld(r), npan = (r + ld - 1) / ld;
+    const size_t panel = (size_t)N * ld, tall = (size_t)dN * ld;
+    const int nblk = fh_vec_nblk(N, ld);
+    poly_coefs pc;
+    if ((rc = pc.acquire(h))) return rc;
+    cplx *Qp, *Xp, *Tp, *Tl, *U, *PK, *part, *ddots;
+    double *rpart, *rsum;
+    if ((rc = fh_buf(h, "pr_Q", tall, &Qp))) return rc;
+    if ((rc = fh_buf(h, "pr_X", tall, &Xp))) return rc;
+    if ((rc = fh_buf(h, "pr_T", tall, &Tp))) return rc;
+    if ((rc = fh_buf(h, "pr_Tl", panel, &Tl))) return rc;
+    if ((rc = fh_buf(h, "pr_U", panel, &U))) return rc;
+    if ((rc = fh_buf(h, "pr_PK", (size_t)(d + 1) * panel, &PK))) return rc;
+    if ((rc = fh_buf(h, "pr_part", (size_t)fh_vec_nblk((int)dN, ld) * ld, &part))) return rc;
+    if ((rc = fh_buf(h, "pr_dots", (size_t)ld, &ddots))) return rc;
+    if ((rc = fh_buf(h, "pr_rpart", (size_t)nblk * 3 * ld, &rpart))) return rc;
+    if ((rc = fh_buf(h, "pr_rsum", (size_t)3 * ld, &rsum))) return rc;
+    const cplx* Vh = (const cplx*)V_host;
+    const cplx* lamh = (const cplx*)lambda;
+    std::vector<cplx> Vp((size_t)ld * ld), lamp(ld);
+    std::vector<double> sums(3 * (size_t)ld);
+    for (int j = 0; j < npan; ++j) {
+        const int mj = std::min(ld, r - j * ld);
+        for (int i = 0; i < npan; ++i) {
+            const int mi = std::min(ld, r - i * ld);
+            std::fill(Vp.begin(), Vp.end(), cmake(0, 0));
+            for (int c2 = 0; c2 < mj; ++c2)
+                for (int c1 = 0; c1 < mi; ++c1) Vp[(size_t)c2 * ld + c1] = Vh[(size_t)(j * ld + c2) * r + i * ld + c1];
+            cplx* dV;
+            if ((rc = poly_upload(h, "pr_V", Vp, &dV))) return rc;
+            fh_launch_to_panel((const cplx*)dQ + (size_t)i * ld * dN, dN, (int)dN, mi, Qp, ld, h->stream);
+            fh_prof_begin(h, "ritz");
+            if (i == 0) fh_launch_small_matmul(Qp, dV, (int)dN, ld, Xp, h->stream);
+            else {
+                fh_launch_small_matmul(Qp, dV, (int)dN, ld, Tp, h->stream);
+                fh_launch_axpy_cols(Xp, Tp, pc.minus, (int)dN, ld, h->stream);          // X += T
+            }
+            fh_prof_end(h);
+        }
+        const int Mj = std::max(0, std::min(mj, (int)M - j * ld));
+        if (normalize && Mj > 0) {
+            fh_launch_dot_cols(Xp, Xp, (int)dN, ld, part, ddots, h->stream);
+            fh_launch_normalize_cols(Xp, ddots, (int)dN, ld, Mj, h->stream);
+        }
+        fh_launch_from_panel(Xp, ld, (int)dN, mj, (cplx*)dX + (size_t)j * ld * dN, dN, h->stream);
+        if (Mj > 0 && (res || backward_error)) {
+            for (int k = 0; k < d; ++k) poly_product(h, pc, ld, k, Xp + (size_t)k * panel, Tl, k > 0, false);     // T = sum_k A_k x_k
+            if (use_B) poly_product(h, pc, ld, d, Xp + (size_t)(d - 1) * panel, U, false, false);               // U = A_d x_{d-1}
+            for (int k = 0; k <= d; ++k) poly_product(h, pc, ld, k, Xp, PK + (size_t)k * panel, false, false);  // A_k x_0
+            std::fill(lamp.begin(), lamp.end(), cmake(0, 0));
+            for (int c = 0; c < mj; ++c) lamp[c] = lamh[j * ld + c];
+            cplx* dlam;
+            if ((rc = poly_upload(h, "pr_lam", lamp, &dlam))) return rc;
+            fh_prof_begin(h, "poly_residual");
+            hipLaunchKernelGGL(k_poly_residual, dim3(nblk), dim3(FH_BLOCK), 0, h->stream, Xp, Tl, U, PK, dlam, d, use_B ? 1 : 0, ld, panel, rpart);
+            hipLaunchKernelGGL(k_poly_residual_fin, dim3(1), dim3(FH_BLOCK), 0, h->stream, rpart, nblk, 3 * ld, rsum);
+            fh_prof_end(h);
+            FH_CHECK(hipMemcpyAsync(sums.data(), rsum, sums.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+            FH_CHECK(hipStreamSynchronize(h->stream));
+            for (int c = 0; c < Mj; ++c) {
+                const double la = std::hypot(lamp[c].x, lamp[c].y);
+                if (res) res[j * ld + c] = std::sqrt(sums[c]) / std::max(la, 1.0);
+                if (backward_error) {
+                    double scale = 0.0, pw = 1.0;
+                    for (int k = 0; k <= d; ++k) { scale += pw * h->poly.fro[k]; pw *= la; }
+                    const double den = scale * std::sqrt(sums[2 * ld + c]);
+                    backward_error[j * ld + c] = den > 0.0 ? std::sqrt(sums[ld + c]) / den : 0.0;
+                }
+            }
+        }
+    }
+    FH_CHECK(hipStreamSynchronize(h->stream));
+    fh_prof_collect(h);
+    FH_CHECK(hipGetLastError());
+    return 0;
+}

@@ -502,6 +502,81 @@ class HipEngine:
         self.last_stats = stats.asdict()
         return dY, rc
 
+    # -- polynomial eigenproblems (feasthip_poly_*): linearised blocks are column-major dN x m, i.e. (m, d N) tensors ------------
+    def set_polynomial(self, coeffs):
+        """P(lambda) = sum_k lambda^k coeffs[k] becomes the engine's problem (feasthip_set_polynomial): dense square matrices
+        of one size, real or complex; afterwards only the poly_* methods, set_contour, set_solver("direct") and free_factors
+        apply until set_problem installs a pencil again."""
+        mats = [np.asarray(c) for c in coeffs]
+        if len(mats) < 2:
+            raise ValueError("a polynomial needs at least two coefficient matrices")
+        N = mats[0].shape[0]
+        for c in mats:
+            if c.ndim != 2 or c.shape != (N, N):
+                raise ValueError("coefficient matrices must be square and of one size")
+        cplx = any(np.iscomplexobj(c) for c in mats)
+        dt = np.complex128 if cplx else np.float64
+        fs = [np.asfortranarray(c, dtype=dt) for c in mats]
+        ptrs = (C.c_void_p * len(fs))(*[f.ctypes.data for f in fs])
+        lds = np.full(len(fs), N, dtype=np.int64)
+        self._chk(self.lib.feasthip_set_polynomial(self.h, N, len(fs) - 1, int(cplx), ptrs, _np_ptr(lds)))
+        self.N, self.b_identity, self.poly_degree = N, False, len(fs) - 1
+        self._problem_fp = None
+
+    def _poly_empty(self, m):
+        return self.torch.empty((m, self.poly_degree * self.N), dtype=self.torch.complex128, device=self.device)
+
+    def poly_solve(self, z, dR, m):
+        """Y = P(z)^-1 R on an N x m device block -> (dY, code 0 | 8); feasthip_poly_solve_dev."""
+        self._sync_stream()
+        dY = self.empty(dR.shape[0])
+        stats = FeastHipStats()
+        rc = self.lib.feasthip_poly_solve_dev(self.h, float(np.real(z)), float(np.imag(z)), int(m), C.c_void_p(dR.data_ptr()),
+                                              C.c_void_p(dY.data_ptr()), C.byref(stats))
+        self._chk(rc, ok=(0, 8))
+        self.last_stats = stats.asdict()
+        return dY, rc
+
+    def poly_contour_apply(self, dQ, m):
+        """Q_proj = sum_e w_e (z_e B_lin - A_lin)^-1 B_lin Q on a dN x m device block -> (dP, status per node, stats)."""
+        self._sync_stream()
+        dP = self._poly_empty(dQ.shape[0])
+        status = np.zeros(max(1, self.ne), dtype=np.int32)
+        stats = FeastHipStats()
+        self._chk(self.lib.feasthip_poly_contour_apply_dev(self.h, int(m), C.c_void_p(dQ.data_ptr()), C.c_void_p(dP.data_ptr()),
+                                                           _np_ptr(status), C.byref(stats)))
+        self.last_stats = stats.asdict()
+        return dP, status, self.last_stats
+
+    def poly_matmul(self, which, dX, m):
+        """A_lin X (which 0) or B_lin X (which 1) on a dN x m device block."""
+        self._sync_stream()
+        dY = self._poly_empty(dX.shape[0])
+        self._chk(self.lib.feasthip_poly_matmul_dev(self.h, int(which), int(m), C.c_void_p(dX.data_ptr()), C.c_void_p(dY.data_ptr())))
+        return dY
+
+    def poly_project(self, dQ, r):
+        """(Q^H A_lin Q, Q^H B_lin Q), raw products, r x r on the host."""
+        self._sync_stream()
+        Aq = np.zeros((r, r), dtype=np.complex128, order="F")
+        Sq = np.zeros((r, r), dtype=np.complex128, order="F")
+        self._chk(self.lib.feasthip_poly_project_dev(self.h, int(r), C.c_void_p(dQ.data_ptr()), _np_ptr(Aq), _np_ptr(Sq)))
+        return Aq, Sq
+
+    def poly_ritz_residual(self, dQ, r, V, lam, M, normalize=True, use_B=True):
+        """X = Q V on the linearisation, the first M columns normalised -> (dX, res[M], backward_error[M]): the linearised
+        residual with (use_B) or without B_lin, and the backward error of (lambda_j, first block of x_j) in P."""
+        self._sync_stream()
+        Vf = np.asfortranarray(V, dtype=np.complex128)
+        lamc = np.ascontiguousarray(lam, dtype=np.complex128)
+        dX = self._poly_empty(dQ.shape[0])
+        res = np.zeros(max(1, r), dtype=np.float64)
+        bwd = np.zeros(max(1, r), dtype=np.float64)
+        self._chk(self.lib.feasthip_poly_ritz_residual_dev(self.h, int(r), C.c_void_p(dQ.data_ptr()), _np_ptr(Vf), _np_ptr(lamc),
+                                                           int(M), int(normalize), int(use_B), C.c_void_p(dX.data_ptr()),
+                                                           _np_ptr(res), _np_ptr(bwd)))
+        return dX, res[:M].copy(), bwd[:M].copy()
+
     def free_factors(self):
         """Drop the cached LU / band factors of the direct solvers (feasthip_release_factors)."""
         self._chk(self.lib.feasthip_release_factors(self.h))

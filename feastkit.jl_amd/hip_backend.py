@@ -1013,6 +1013,71 @@ def feast_hip_general(engine, A, B, Emid, r, M0, fpm, *, solver="direct", solver
             dQ = dX
 
 
+POLY_RESIDUALS = ("pencil", "reference")
+
+
+def feast_hip_polynomial(engine, coeffs, Emid, r, M0, fpm, *, Q0=None, seed=20260515, contour=None, residual="pencil",
+                         eps_floor=0.0):
+    """P(lambda) x = 0 inside a circle: feast_hip_general's loop on the first companion linearisation with M0 d columns
+    (feast_pep!, src/dense/feast_dense.jl:715-772, driving feast_gegv! :763) -- full contour, no factor 2, no
+    orthonormalisation -- with the companion pencil replaced by the engine's poly_* calls: one N x N LU per node.
+    ``residual``: "pencil" measures ||A_lin x - lambda B_lin x|| / max(|lambda|, 1), "reference" omits B_lin as the
+    reference's kernel does (src/kernel/feast_kernel.jl:899-906).  q: the first N rows of the M linearised Ritz vectors
+    (src/dense/feast_dense.jl:768)."""
+    d = len(coeffs) - 1
+    N = coeffs[0].shape[0]
+    cols = M0 * d
+    feastdefault(fpm)
+    info = _check_circle_input(N, M0, r)
+    if info:
+        return _empty_result(N, info, complex_lambda=True)
+    Zne, Wne = feast_gcontour(Emid, r, fpm) if contour is None else contour
+    engine.set_polynomial(coeffs)
+    engine.set_solver("direct", cache_factors=True, factor_precision=64)
+    engine.set_real_projection(False)
+    engine.set_contour(Zne, Wne, 1.0)
+    Q_host = seeded_subspace(d * N, cols, seed) if Q0 is None else np.asarray(Q0, dtype=np.complex128)
+    if Q_host.shape != (d * N, cols):
+        raise ValueError(f"Q0 must be the linearised start block of shape ({d * N}, {cols})")
+    dQ = engine.upload(Q_host)
+    eps_tol = max(feast_tolerance(fpm), float(eps_floor))
+    maxloop = int(fpm[4])
+    use_B = residual == "pencil"
+    loop = 0
+    eps_hist = []
+    stats = {"krylov_iterations": 0, "factorizations": 0, "solve_seconds": 0.0,
+             "polynomial": {"degree": d, "columns": cols, "residual": residual, "backward_error": np.zeros(0), "eps_history": eps_hist}}
+    while True:
+        dq, status, st = engine.poly_contour_apply(dQ, cols)
+        stats["factorizations"] += st.get("factorizations", 0)
+        stats["solve_seconds"] += st.get("seconds_total", 0.0)
+        if int(np.max(status)):
+            return _empty_result(N, FeastError.Feast_ERROR_LAPACK, loop, complex_lambda=True, stats=stats)
+        Aq, Sq = engine.poly_project(dq, cols)
+        try:
+            with small_lapack():
+                lam_red, v_red = sla.eig(Aq, Sq)                                # feast_kernel.jl:812
+        except Exception:
+            return _empty_result(N, FeastError.Feast_ERROR_LAPACK, loop, complex_lambda=True, stats=stats)
+        perm, M = _reorder_by_contour(lam_red, Emid, r, fpm, cols)
+        if M == 0:
+            return _empty_result(N, FeastError.Feast_ERROR_NO_CONVERGENCE, loop, complex_lambda=True, stats=stats)
+        lam = lam_red[perm]
+        V = np.asfortranarray(v_red[:, perm])
+        # all columns normalised (feast_kernel.jl:864-876)
+        dX, res, bwd = engine.poly_ritz_residual(dq, cols, V, lam, cols, normalize=True, use_B=use_B)
+        res, bwd = res[:M], bwd[:M]
+        epsout = float(res.max())
+        eps_hist.append(epsout)
+        if epsout <= eps_tol or loop >= maxloop:
+            order = sorted(range(M), key=lambda i: abs(lam[i]) ** 2)             # feast_sort_general!
+            X = engine.download(dX, cols)
+            stats["polynomial"]["backward_error"] = bwd[order].copy()
+            return FeastResult(lam[:M][order].copy(), X[:N, :M][:, order].copy(), M, res[order].copy(), 0, epsout, loop, stats)
+        loop += 1
+        dQ = dX
+
+
 TWO_SIDED_SOLVERS = ("direct", "lu")
 TWO_SIDED_SPARSE_SOLVERS = ("direct", "lu", "sparse_direct", "banded")
 

@@ -496,6 +496,47 @@ int  feasthip_shifted_solve(feasthip_handle h, double z_re, double z_im, int64_t
 int  feasthip_shifted_solve_dev(feasthip_handle h, double z_re, double z_im, int64_t m,
                                 const void* dX, void* dY, feasthip_stats* stats);
 
+/* ---- polynomial eigenproblems: P(lambda) x = 0, P(lambda) = A_0 + lambda A_1 + ... + lambda^d A_d ------------------------
+ * The reference's feast_pep! builds the dN x dN first companion form (src/dense/feast_dense.jl:745-760)
+ *     A_lin = [0 I . ; . . I ; -A_0 ... -A_{d-1}],   B_lin = diag(I, ..., I, A_d)
+ * and hands it to feast_gegv! (:763), one LU of order dN per node.  Here the companion matrix is never formed: a node costs one
+ * LU of P(z_e), order N (d^3 times fewer flops, d^2 times less factor memory), and the linearised vectors exist only as the
+ * dN x m blocks the caller sees.  Device blocks are column-major complex128 like the other _dev entry points; block i of a
+ * column is its rows i N .. (i + 1) N - 1.  m > 64 runs in 64-column panels.
+ * feasthip_set_polynomial: dense coefficients A_0 .. A_degree (host, column-major, ld[k] >= N; all double or all interleaved
+ *   complex128), 1 <= degree <= FEASTHIP_POLY_MAX_DEGREE.  Replaces the coeffs argument of feast_pep!
+ *   (src/dense/feast_dense.jl:715-744) and of feast_gepev! / feast_hepev! / feast_sypev! (:946-979).  The handle becomes a
+ *   POLYNOMIAL handle: feasthip_set_contour, feasthip_set_solver (FEASTHIP_SOLVER_LU with factor_precision 64 only),
+ *   feasthip_release_factors, the stream and the profile calls work on it; every other entry point above returns
+ *   FEASTHIP_ERROR_FPM and names the feasthip_poly_* calls (feasthip_set_adjoint(1), a node range or list, a communicator and
+ *   factor_precision 32 included: a polynomial sweep is one rank, forward, fp64).  feasthip_set_dense / feasthip_set_csr
+ *   restore an ordinary handle.  A feasthip_poly_* call on any other handle returns FEASTHIP_ERROR_FPM.
+ * feasthip_poly_solve_dev: Y = P(z)^-1 R, N x m (the shifted solve inside the companion elimination; no reference
+ *   counterpart).  Factors are cached per contour node and matched by z, as in feasthip_shifted_solve.  Returns 0 or 8.
+ * feasthip_poly_contour_apply_dev: Qproj = sum_e weight_scale w_e (z_e B_lin - A_lin)^-1 (B_lin Q), dN x m: the loop body
+ *   of feast_grci! as feast_gegv! drives it on the companion pencil (src/dense/feast_dense.jl:468-584).  node_status[e]: 0 or 8,
+ *   ne entries.  stats.factorizations counts the N x N factorisations of the call (0 on a repeated contour).
+ * feasthip_poly_matmul_dev: Y = A_lin X (which 0) or B_lin X (which 1), dN x m (RCI jobs 30 / 40 on the companion pencil).
+ * feasthip_poly_project_dev: the raw products Aq = Q^H A_lin Q and Sq = Q^H B_lin Q (src/kernel/feast_kernel.jl:790, 805),
+ *   r x r column-major host buffers.
+ * feasthip_poly_ritz_residual_dev: X = Q V (dN x r; V r x r column-major, host), the first M columns scaled to unit length
+ *   when normalize != 0 (src/kernel/feast_kernel.jl:864-876); for j < M
+ *     res[j]            = ||A_lin x_j - lambda_j B_lin x_j||_2 / max(|lambda_j|, 1)  (use_B = 0 omits B_lin, as the reference
+ *                         does, src/kernel/feast_kernel.jl:899-906: for A_d != I that measure does not fall),
+ *     backward_error[j] = ||P(lambda_j) x_j||_2 / (sum_k |lambda_j|^k ||A_k||_F ||x_j||_2),  x_j the first block of column j
+ *   (no reference counterpart).  lambda: r complex values; res, backward_error: M doubles each, either may be NULL; X must
+ *   not alias Q.                                                                                                        */
+#define FEASTHIP_POLY_MAX_DEGREE 8
+int  feasthip_set_polynomial(feasthip_handle h, int64_t N, int degree, int is_complex,
+                             const void* const* coeffs /* degree + 1, column-major */, const int64_t* ld);
+int  feasthip_poly_solve_dev(feasthip_handle h, double z_re, double z_im, int64_t m, const void* dR, void* dY, feasthip_stats* stats);
+int  feasthip_poly_contour_apply_dev(feasthip_handle h, int64_t m, const void* dQ, void* dQproj, int* node_status,
+                                     feasthip_stats* stats);
+int  feasthip_poly_matmul_dev(feasthip_handle h, int which /* 0 A_lin, 1 B_lin */, int64_t m, const void* dX, void* dY);
+int  feasthip_poly_project_dev(feasthip_handle h, int64_t r, const void* dQ, void* Aq_host, void* Sq_host);
+int  feasthip_poly_ritz_residual_dev(feasthip_handle h, int64_t r, const void* dQ, const void* V_host, const void* lambda, int64_t M,
+                                     int normalize, int use_B, void* dX, double* res, double* backward_error);
+
 /* ---- measurement support ---------------------------------------------------------- */
 /* Average device time (ms, HIP events on the handle's stream) and launch count of the
  * named kernel class since the last reset; classes: "spmm", "bicg_update", "dot_finalize",
