@@ -89,6 +89,7 @@ SYMBOLS = {
     "feasthip_shifted_solve": (_i, [_vp, _d, _d, _i64, _vp, _vp, _ps]),
     "feasthip_shifted_solve_dev": (_i, [_vp, _d, _d, _i64, _vp, _vp, _ps]),
     "feasthip_set_polynomial": (_i, [_vp, _i64, _i, _i, _vp, _vp]),
+    "feasthip_set_polynomial_csr": (_i, [_vp, _i64, _i, _i, _vp, _vp, _vp]),
     "feasthip_poly_solve_dev": (_i, [_vp, _d, _d, _i64, _vp, _vp, _ps]),
     "feasthip_poly_contour_apply_dev": (_i, [_vp, _i64, _vp, _vp, _vp, _ps]),
     "feasthip_poly_matmul_dev": (_i, [_vp, _i, _i64, _vp, _vp]),

@@ -14,6 +14,7 @@ from .engine import HipEngine
 from .contour import feast_contour, feast_gcontour
 from .hip_backend import (DIRECT_SOLVERS, ESTIMATE_SEED, check_direct_nodes, check_ortho, check_two_sided, feast_hip_estimate,
                           feast_hip_general, feast_hip_general_two_sided, feast_hip_hermitian, feast_hip_polynomial, POLY_RESIDUALS)
+from .ingest import polynomial_union_csr
 from .parameters import feastdefault, feastinit
 from .types import FEAST_UNINITIALIZED, FeastHipError, FeastResult
 
@@ -590,17 +591,31 @@ POLY_MAX_DEGREE = 8          # FEASTHIP_POLY_MAX_DEGREE
 POLY_DENSE_LIMIT = 12288     # sparse coefficients are expanded up to this size
 
 
+POLY_SOLVERS = ("direct", "sparse_direct")
+
+
 def feast_polynomial(coeffs, center, radius, *, M0=10, fpm=None, engine=None, device=0, Q0=None, contour=None, seed=None,
-                     keep_factors=False, residual="pencil"):
+                     keep_factors=False, residual="pencil", solver="direct"):
     """feast_polynomial(coeffs, center, radius; M0, fpm): src/interfaces/feast_interfaces.jl:448-462, feast_pep! /
     feast_gepev! / feast_hepev! / feast_sypev! (src/dense/feast_dense.jl:715-772, 946-979).  Eigenpairs of
     P(lambda) x = 0, P(lambda) = coeffs[0] + lambda coeffs[1] + ... + lambda^d coeffs[d], with lambda inside the circle.
     The reference builds the dN x dN companion pencil and factors it per node; here a node costs one LU of P(z_e), order N.
 
     ``coeffs``: d + 1 square matrices of one size, 1 <= d <= 8, real or complex (float32 / complex64 input is promoted and
-    the result demoted as in feast_general).  Sparse coefficients are expanded up to N = 12 288
-    (``stats["solver_substitution"]``); beyond that ValueError.  ``M0`` (clipped to N) sizes the subspace: the loop runs
-    M0 d columns, as feast_pep! does.  ``Q0``: linearised start block, (d N) x (M0 d).
+    the result demoted as in feast_general).  ``M0`` (clipped to N) sizes the subspace: the loop runs M0 d columns, as
+    feast_pep! does.  ``Q0``: linearised start block, (d N) x (M0 d).
+    ``solver``:
+      "direct" (default)  the dense LU of P(z_e).  Sparse coefficients are expanded up to N = 12 288
+                          (``stats["solver_substitution"]``); beyond that ValueError.
+      "sparse_direct"     every coefficient a scipy.sparse matrix, any N: the counterpart of the reference's feast_scsrpev! /
+                          feast_hcsrpev! / feast_gcsrpev! (src/sparse/feast_sparse.jl), which run on the explicit sparse
+                          companion.  The coefficients go on one union pattern (ingest.polynomial_union_csr) and P(z_e) is
+                          factored by the multifrontal LU of the sparse direct solver.  That LU pivots only inside a front's
+                          fully-summed block: when it rejects a pivot at any node, or the pattern has no multifrontal plan
+                          (a front beyond 16 384 rows), the call reruns on the dense expansion if N <= 12 288
+                          (``stats["polynomial"]["fell_back"]`` = True, plan = "dense", ``stats["solver_substitution"]``),
+                          else raises FeastHipError naming the cause and the sizes -- as it does when the factors do not fit
+                          the device.  There is no band LU for polynomials.
     ``residual``: what ``res`` / ``epsout`` and the stop test measure on the unit linearised Ritz vector x of the companion
     pencil (A_lin, B_lin):
       "pencil" (default)  ||A_lin x - lambda B_lin x|| / max(|lambda|, 1)
@@ -612,6 +627,8 @@ def feast_polynomial(coeffs, center, radius, *, M0=10, fpm=None, engine=None, de
     vectors as the reference returns them (src/dense/feast_dense.jl:768), ``res`` in the chosen measure;
     ``stats["polynomial"]`` = {degree, columns, residual, backward_error, eps_history} with backward_error[j] =
     ||P(lambda_j) q_j|| / (sum_k |lambda_j|^k ||A_k||_F ||q_j||); ``stats["factorizations"]`` counts N x N factorisations.
+    Under "sparse_direct" also plan ("multifrontal" | "dense"), plan_factor_bytes / plan_transient_bytes / plan_flops per node
+    (feasthip_direct_plan_bytes / _flops; absent for "dense"), plan_nnz of the union pattern, and fell_back.
     ``keep_factors``, ``contour``, ``seed``: as in feast_general."""
     mats = list(coeffs)
     if len(mats) < 2:
@@ -628,14 +645,21 @@ def feast_polynomial(coeffs, center, radius, *, M0=10, fpm=None, engine=None, de
         raise ValueError("radius must be positive")
     if residual not in POLY_RESIDUALS:
         raise ValueError(f"residual must be one of {POLY_RESIDUALS}, not {residual!r}")
+    if solver not in POLY_SOLVERS:
+        raise ValueError(f"solver must be one of {POLY_SOLVERS}, not {solver!r}")
     N = shape[0]
+    sparse_direct = solver == "sparse_direct"
+    if sparse_direct and not all(sp.issparse(c) for c in mats):
+        raise ValueError('solver="sparse_direct" needs every coefficient as a scipy.sparse matrix; dense coefficients take '
+                         'solver="direct"')
     substituted = None
-    if any(sp.issparse(c) for c in mats):
+    if not sparse_direct and any(sp.issparse(c) for c in mats):
         if N > POLY_DENSE_LIMIT:
             raise ValueError(f"sparse coefficients are expanded to dense matrices up to N = {POLY_DENSE_LIMIT}; N = {N}")
         mats = [_densify(c) if sp.issparse(c) else c for c in mats]
         substituted = {"requested": "direct", "used": "dense LU of the expanded coefficients"}
-    mats = [np.asarray(c) for c in mats]
+    if not sparse_direct:
+        mats = [np.asarray(c) for c in mats]
     single = _single_precision(*mats)
     if single:
         mats = [_promote(c) for c in mats]
@@ -644,9 +668,27 @@ def feast_polynomial(coeffs, center, radius, *, M0=10, fpm=None, engine=None, de
     M0 = min(int(M0), N)
     eng = _engine(engine, device)
     eps_floor = float(np.sqrt(np.finfo(np.float32).eps)) if single else 0.0
+    common = dict(Q0=Q0, contour=contour, residual=residual, eps_floor=eps_floor, **({} if seed is None else {"seed": int(seed)}))
     try:
-        res = feast_hip_polynomial(eng, mats, complex(center), float(radius), M0, fpm, Q0=Q0, contour=contour, residual=residual,
-                                   eps_floor=eps_floor, **({} if seed is None else {"seed": int(seed)}))
+        res = None
+        if sparse_direct:
+            union = polynomial_union_csr(mats)
+            try:
+                res = feast_hip_polynomial(eng, mats, complex(center), float(radius), M0, fpm, union_csr=union, **common)
+                if isinstance(res.stats, dict) and "polynomial" in res.stats:
+                    res.stats["polynomial"]["fell_back"] = False
+            except FeastHipError as err:
+                # 9: no multifrontal plan for the pattern, 8: a rejected pivot.  (6, factors that do not fit, is not a
+                # reason to try N^2 dense ones.)
+                if err.code not in (8, 9) or N > POLY_DENSE_LIMIT:
+                    raise
+                eng.free_factors()
+                substituted = {"requested": "sparse_direct", "used": "dense LU of the expanded coefficients", "reason": str(err)}
+                mats = [_densify(c) for c in mats]
+        if res is None:
+            res = feast_hip_polynomial(eng, mats, complex(center), float(radius), M0, fpm, **common)
+            if sparse_direct and isinstance(res.stats, dict) and "polynomial" in res.stats:
+                res.stats["polynomial"].update(plan="dense", plan_nnz=int(len(union[1])), fell_back=True)
         if substituted is not None and isinstance(res.stats, dict):
             res.stats["solver_substitution"] = substituted
     finally:

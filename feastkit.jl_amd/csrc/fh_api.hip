@@ -477,7 +477,10 @@ extern "C" int feasthip_set_node_solver(feasthip_handle h, int count, const int*
 extern "C" int feasthip_direct_plan_bytes(feasthip_handle h, int nodes, int64_t* factor_bytes, int64_t* transient_bytes) {
     if (!h) return FEASTHIP_ERROR_INTERNAL;
     if (h->poisoned) { h->last_error = "handle poisoned by an earlier device failure: destroy it"; return FEASTHIP_ERROR_INTERNAL; }
-    if (h->kind != 2 || nodes < 0) { h->last_error = "feasthip_direct_plan_bytes: needs a CSR problem and nodes >= 0"; return FEASTHIP_ERROR_FPM; }
+    if (!(h->kind == 2 || (h->kind == 3 && h->poly.sparse)) || nodes < 0) {
+        h->last_error = "feasthip_direct_plan_bytes: needs a CSR problem (or a sparse polynomial) and nodes >= 0";
+        return FEASTHIP_ERROR_FPM;
+    }
     FH_CHECK(hipSetDevice(h->device));
     return fh_banded_plan_bytes(h, nodes, factor_bytes, transient_bytes);
 }

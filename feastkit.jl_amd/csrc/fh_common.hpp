@@ -112,12 +112,18 @@ struct fh_dense {
 
 // Matrix polynomial P(lambda) = A_0 + lambda A_1 + ... + lambda^d A_d (feasthip_set_polynomial, fh_poly.hip): the d + 1
 // coefficients, N x N column-major, all double or all cplx; fro[k] = ||A_k||_F.  N and is_complex live in fh_dense.
+// sparse (feasthip_set_polynomial_csr): the coefficients share ONE CSR pattern that holds the whole diagonal -- device rowptr /
+// col in feasthip_ctx::csr (N, nnz, is_complex; aval and bval stay null, b_identity 0), the host copy in host_rowptr / host_col
+// in the caller's order -- and coef[k] is the array of nnz values of A_k on that pattern, explicit zeros included.
 #define FH_POLY_MAX_DEGREE 8
 struct fh_poly {
     int degree = 0;
+    int sparse = 0;
     void* coef[FH_POLY_MAX_DEGREE + 1] = {};
     double fro[FH_POLY_MAX_DEGREE + 1] = {};
 };
+// the coefficient pointers as a kernel argument
+struct fh_poly_ptrs { const void* c[FH_POLY_MAX_DEGREE + 1]; };
 
 // Per-(node,column) Krylov scalars, struct of arrays; each array is [nodes][ld].
 struct fh_krylov_scalars {
@@ -147,7 +153,7 @@ struct feasthip_ctx {
     std::string last_error;
 
     // problem
-    int kind = 0;  // 0 none, 1 dense, 2 sparse, 3 dense matrix polynomial (the feasthip_poly_* entry points only)
+    int kind = 0;  // 0 none, 1 dense, 2 sparse, 3 matrix polynomial, dense or (poly.sparse) CSR (the feasthip_poly_* entry points only)
     fh_poly poly;
     fh_csr csr;
     // conjugate transpose of `csr` (A^H, B^H on the transposed union pattern, internal numbering; rowptr / col / aval / bval only):

@@ -2635,6 +2635,33 @@ __global__ __launch_bounds__(FH_BLOCK) void k_mf_assemble(const int* __restrict_
     }
 }
 
+// The same for a sparse polynomial handle (feasthip_set_polynomial_csr): the entry is P(z) at CSR position src[q], Horner over
+// the d + 1 value arrays of the shared pattern.  A polynomial has no implicit identity, so the flagged-diagonal bit of dst adds
+// nothing (the plan of such a handle is made without it; the bit is only decoded).  Traffic per node: 8 B of lists per entry,
+// (d + 1) sizeof(VT) of values, sizeof(T) written.
+template <typename VT, typename T>
+__global__ __launch_bounds__(FH_BLOCK) void k_mf_assemble_poly(const int* __restrict__ dst, const int* __restrict__ src, size_t count, T* base, size_t node_stride,
+                                                                fh_poly_ptrs P, int deg, const cplx* z) {
+    T* A = base + (size_t)blockIdx.y * node_stride;
+    const cplx zz = z[blockIdx.y];
+    for (size_t q = (size_t)blockIdx.x * FH_BLOCK + threadIdx.x; q < count; q += (size_t)gridDim.x * FH_BLOCK) {
+        int d = dst[q];
+        if (d < 0) d = ~d;
+        const int k = src[q];
+        cplx v = cmake(0, 0);
+        if (k >= 0) {
+#pragma unroll
+            for (int j = FH_POLY_MAX_DEGREE; j >= 0; --j)
+                if (j <= deg) {
+                    cplx a;
+                    if constexpr (sizeof(VT) == sizeof(cplx)) a = ((const cplx*)P.c[j])[k]; else a = cmake(((const double*)P.c[j])[k], 0.0);
+                    v = cadd(cmul(v, zz), a);
+                }
+        }
+        A[d] = cvt<T>(v);
+    }
+}
+
 // parent front += Schur complement of a child (grid.y = child, grid.z = node)
 template <typename T>
 __global__ __launch_bounds__(FH_BLOCK) void k_mf_extend_add(const mf_kid* kids, T* base, size_t node_stride, const int* __restrict__ rel, int n_p) {
@@ -2879,7 +2906,16 @@ static int mf_factor_t(feasthip_ctx* h, int nf, void* const* stores, int* const*
                 T* base = work + G.work_off;
                 const int* dd = S->d_asm_dst + G.asm_begin;
                 const int* ss = S->d_asm_src + G.asm_begin;
-                if (cz) {
+                if (h->kind == 3) {          // sparse polynomial handle: P(z_e) in place of z_e B - A, a profile class of its own
+                    fh_poly_ptrs pp;
+                    for (int k = 0; k <= FH_POLY_MAX_DEGREE; ++k) pp.c[k] = h->poly.coef[k];
+                    fh_prof_end(h);
+                    fh_prof_begin(h, "poly_mf_assemble");
+                    if (cz) hipLaunchKernelGGL((k_mf_assemble_poly<cplx, T>), grid, block, 0, h->stream, dd, ss, cnt, base, P.work_elems, pp, h->poly.degree, dz);
+                    else hipLaunchKernelGGL((k_mf_assemble_poly<double, T>), grid, block, 0, h->stream, dd, ss, cnt, base, P.work_elems, pp, h->poly.degree, dz);
+                    fh_prof_end(h);
+                    fh_prof_begin(h, "mf_assemble");
+                } else if (cz) {
                     if (bid) hipLaunchKernelGGL((k_mf_assemble<cplx, true, T>), grid, block, 0, h->stream, dd, ss, cnt, base, P.work_elems, (const cplx*)h->csr.aval, (const cplx*)nullptr, dz);
                     else hipLaunchKernelGGL((k_mf_assemble<cplx, false, T>), grid, block, 0, h->stream, dd, ss, cnt, base, P.work_elems, (const cplx*)h->csr.aval, (const cplx*)h->csr.bval, dz);
                 } else {

@@ -17,9 +17,16 @@
 // its blocks one behind the other -- block i of a panel P is P + i N ld -- so the column-major <-> panel kernels, the Gram
 // kernel, the small product and the column dots of fh_blockops.hip take it as a tall panel, and the dense product kernel
 // takes one block of it.
+//
+// Sparse coefficients (feasthip_set_polynomial_csr) replace  feast_scsrpev! / feast_hcsrpev! / feast_gcsrpev!
+// (src/sparse/feast_sparse.jl), which run on the explicit sparse companion.  The structured solve above touches the matrices in
+// two places only, and both have a sparse counterpart: "form P(z_e)" is k_mf_assemble_poly inside the multifrontal LU of the
+// sparse direct solver (fh_dense.hip, planned by fh_banded.hip, its per-node factor cache as it stands), and Y +-= A_k X is
+// k_spmm_fan below.  Everything else in this file is shared by the two flavours.
 #include "fh_common.hpp"
 #include "fh_kernels.hpp"
 #include "fh_dense.hpp"
+#include "fh_banded.hpp"
 #include "../../include/feasthip.h"
 
 #include <algorithm>
@@ -30,8 +37,6 @@
 #define FH_BLOCK 256
 #define PD FH_POLY_MAX_DEGREE
 static_assert(FH_POLY_MAX_DEGREE == FEASTHIP_POLY_MAX_DEGREE, "degree bound of the ABI");
-
-struct fh_poly_ptrs { const void* c[PD + 1]; };
 
 __device__ inline cplx poly_val(cplx v) { return v; }
 __device__ inline cplx poly_val(double v) { return cmake(v, 0.0); }
@@ -74,6 +79,64 @@ void fh_poly_form(feasthip_ctx* h, void* const* dlus, const cplx* dz, int nf, in
         else hipLaunchKernelGGL((k_form_poly<double, cplx>), grid, block, 0, h->stream, P, d, (cplx* const*)dlus, dz, nf, total);
     }
     fh_prof_end(h);
+}
+
+// ---------------------------------------------------------------------------------------
+// Sparse coefficients (feasthip_set_polynomial_csr): fan-out product on the shared pattern.  One input panel X (N x LD,
+// row-major) and nout <= FH_FAN_MAX outputs, Y_t = s_t A_{k_t} X (+ the old Y_t when accumulate_t), s_t = +-1.  The structured
+// solve and the residual step apply many coefficients to the SAME panel, and the gather of the X rows, not the matrix bytes,
+// bounds the SpMM here: so per nonzero the column index and the gathered X row are loaded ONCE and the
+// nout coefficient values at that nonzero feed nout accumulators that stay in registers.  A row is owned by one slice of LD
+// lanes (lane <-> column: LD = 64 one wave per row, 32 two rows per wave, 16 four), which also reads and writes its Y_t
+// elements: no atomics, the summation order is the row's CSR order, the result is reproducible.
+// Algorithmic traffic: nnz (4 + nout sizeof(VT)) of matrix, one X row of 16 LD B gathered per nonzero (cache hits for a
+// stencil), N LD 16 B per output written and as much read per accumulating output.
+// ---------------------------------------------------------------------------------------
+#define FH_FAN_MAX (PD + 1)
+struct fh_fan_args {
+    const int* rowptr; const int* col;
+    const cplx* X;
+    int N, nout;
+    const void* val[FH_FAN_MAX];      // values of A_{k_t} on the pattern
+    cplx* Y[FH_FAN_MAX];
+    int flags[FH_FAN_MAX];            // bit 0: accumulate, bit 1: negate
+};
+struct fh_fan_out { int k; cplx* Y; bool accumulate, negate; };
+
+template <typename VT, int LD>
+__global__ __launch_bounds__(FH_BLOCK) void k_spmm_fan(fh_fan_args a) {
+    constexpr int ROWS = FH_BLOCK / LD;          // rows of a workgroup
+    const int c = threadIdx.x % LD;
+    const int i = blockIdx.x * ROWS + threadIdx.x / LD;
+    if (i >= a.N) return;
+    const int* __restrict__ colidx = a.col;
+    const cplx* __restrict__ X = a.X;
+    const int k0 = a.rowptr[i], k1 = a.rowptr[i + 1];
+    cplx acc[FH_FAN_MAX];
+#pragma unroll
+    for (int t = 0; t < FH_FAN_MAX; ++t) acc[t] = cmake(0, 0);
+    // batches of 4 nonzeros: the gathers are issued together, then the values are read and multiplied (a slot past the row end
+    // gathers the row's last column again and adds nothing)
+    for (int kb = k0; kb < k1; kb += 4) {
+        cplx xs[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) xs[q] = X[(size_t)colidx[min(kb + q, k1 - 1)] * LD + c];
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+            if (kb + q < k1) {
+#pragma unroll
+                for (int t = 0; t < FH_FAN_MAX; ++t)
+                    if (t < a.nout) acc[t] = cadd(acc[t], vmul(((const VT*)a.val[t])[kb + q], xs[q]));
+            }
+    }
+    const size_t e = (size_t)i * LD + c;
+#pragma unroll
+    for (int t = 0; t < FH_FAN_MAX; ++t)
+        if (t < a.nout) {
+            cplx r = (a.flags[t] & 2) ? cmake(-acc[t].x, -acc[t].y) : acc[t];
+            if (a.flags[t] & 1) r = cadd(a.Y[t][e], r);
+            a.Y[t][e] = r;
+        }
 }
 
 // ---------------------------------------------------------------------------------------
@@ -249,14 +312,61 @@ static void poly_product(feasthip_ctx* h, const poly_coefs& pc, int ld, int k, c
     fh_prof_end(h);
 }
 
+// Sparse handle: outs[t].Y = +-A_{outs[t].k} X (+ its old value) for nout <= FH_FAN_MAX outputs in one launch of k_spmm_fan
+static void poly_fan(feasthip_ctx* h, int ld, const cplx* X, const fh_fan_out* outs, int nout) {
+    fh_fan_args a;
+    memset(&a, 0, sizeof(a));
+    a.rowptr = h->csr.rowptr; a.col = h->csr.col; a.X = X; a.N = (int)h->csr.N; a.nout = nout;
+    for (int t = 0; t < nout; ++t) {
+        a.val[t] = h->poly.coef[outs[t].k]; a.Y[t] = outs[t].Y;
+        a.flags[t] = (outs[t].accumulate ? 1 : 0) | (outs[t].negate ? 2 : 0);
+    }
+    const dim3 grid((unsigned)((a.N + FH_BLOCK / ld - 1) / (FH_BLOCK / ld))), block(FH_BLOCK);
+    fh_prof_begin(h, "poly_spmm");
+#define FH_FAN_LAUNCH(VT_) \
+    do { if (ld == 64) hipLaunchKernelGGL((k_spmm_fan<VT_, 64>), grid, block, 0, h->stream, a); \
+         else if (ld == 32) hipLaunchKernelGGL((k_spmm_fan<VT_, 32>), grid, block, 0, h->stream, a); \
+         else hipLaunchKernelGGL((k_spmm_fan<VT_, 16>), grid, block, 0, h->stream, a); } while (0)
+    if (h->csr.is_complex) FH_FAN_LAUNCH(cplx); else FH_FAN_LAUNCH(double);
+#undef FH_FAN_LAUNCH
+    fh_prof_end(h);
+}
+
+// Y = s A_k X (accumulate: Y += s A_k X) on either flavour of handle
+static void poly_apply(feasthip_ctx* h, const poly_coefs& pc, int ld, int k, const cplx* X, cplx* Y, bool accumulate, bool negate) {
+    if (h->poly.sparse) { const fh_fan_out o{k, Y, accumulate, negate}; poly_fan(h, ld, X, &o, 1); }
+    else poly_product(h, pc, ld, k, X, Y, accumulate, negate);
+}
+
+// The products of the residual step on a sparse handle, T = sum_{k<d} A_k x_k, U = A_d x_{d-1} (use_B) and PK_k = A_k x_0, in d
+// launches instead of 2 d + 2: x_0 fans to A_0 .. A_d (the PK panels; T starts as a copy of PK_0 = A_0 x_0), one launch adds
+// A_j x_j to T for each x_j in between, x_{d-1} fans to A_{d-1} (into T) and A_d (U).  X: tall panel.
+static int poly_residual_fan(feasthip_ctx* h, int ld, bool use_B, const cplx* X, cplx* T, cplx* U, cplx* PK) {
+    const int d = h->poly.degree;
+    const size_t panel = (size_t)h->dense.N * ld;
+    fh_fan_out outs[FH_FAN_MAX];
+    for (int k = 0; k <= d; ++k) outs[k] = fh_fan_out{k, PK + (size_t)k * panel, false, false};
+    poly_fan(h, ld, X, outs, d + 1);
+    FH_CHECK(hipMemcpyAsync(T, PK, panel * sizeof(cplx), hipMemcpyDeviceToDevice, h->stream));
+    if (d == 1) {
+        if (use_B) FH_CHECK(hipMemcpyAsync(U, PK + panel, panel * sizeof(cplx), hipMemcpyDeviceToDevice, h->stream));
+        return 0;
+    }
+    for (int k = 1; k <= d - 2; ++k) { outs[0] = fh_fan_out{k, T, true, false}; poly_fan(h, ld, X + (size_t)k * panel, outs, 1); }
+    outs[0] = fh_fan_out{d - 1, T, true, false};
+    outs[1] = fh_fan_out{d, U, false, false};
+    poly_fan(h, ld, X + (size_t)(d - 1) * panel, outs, use_B ? 2 : 1);
+    return 0;
+}
+
 // W = A_lin X (which 0) or B_lin X (which 1) on tall panels: block shifts, -sum_j A_j X_j and A_d X_{d-1}
 static int poly_lin_product(feasthip_ctx* h, const poly_coefs& pc, int which, int ld, const cplx* X, cplx* W) {
     const int d = h->poly.degree;
     const size_t panel = (size_t)h->dense.N * ld;
     cplx* last = W + (size_t)(d - 1) * panel;
     if (d > 1) FH_CHECK(hipMemcpyAsync(W, which == 0 ? X + panel : X, (size_t)(d - 1) * panel * sizeof(cplx), hipMemcpyDeviceToDevice, h->stream));
-    if (which == 0) for (int j = 0; j < d; ++j) poly_product(h, pc, ld, j, X + (size_t)j * panel, last, j > 0, true);
-    else poly_product(h, pc, ld, d, X + (size_t)(d - 1) * panel, last, false, false);
+    if (which == 0) for (int j = 0; j < d; ++j) poly_apply(h, pc, ld, j, X + (size_t)j * panel, last, j > 0, true);
+    else poly_apply(h, pc, ld, d, X + (size_t)(d - 1) * panel, last, false, false);
     return 0;
 }
 
@@ -295,6 +405,71 @@ extern "C" int feasthip_set_polynomial(feasthip_handle h, int64_t N, int degree,
     return 0;
 }
 
+// Sparse coefficients on one CSR pattern (0-based, columns strictly increasing inside a row, so no duplicates): the multifrontal
+// LU of P(z_e) (fh_banded.hip plans it, k_mf_assemble_poly forms the fronts) in place of the dense one, k_spmm_fan in place of
+// the dense product.  The pattern is kept in the caller's order (no renumbering: the multifrontal plan brings its own).
+extern "C" int feasthip_set_polynomial_csr(feasthip_handle h, int64_t N, int degree, int is_complex, const int64_t* rowptr,
+                                           const int64_t* col, const void* const* vals) {
+    if (!h) return FEASTHIP_ERROR_INTERNAL;
+    if (h->poisoned) { h->last_error = "handle poisoned by an earlier device failure: destroy it"; return FEASTHIP_ERROR_INTERNAL; }
+    if (N <= 0 || N > INT32_MAX / FH_MAX_LD / FEASTHIP_POLY_MAX_DEGREE) { h->last_error = "feasthip_set_polynomial_csr: N out of range"; return FEASTHIP_ERROR_N; }
+    if (degree < 1 || degree > FEASTHIP_POLY_MAX_DEGREE) { h->last_error = "feasthip_set_polynomial_csr: degree must be 1 .. FEASTHIP_POLY_MAX_DEGREE"; return FEASTHIP_ERROR_FPM; }
+    if (!rowptr || !vals) { h->last_error = "feasthip_set_polynomial_csr: null argument"; return FEASTHIP_ERROR_N; }
+    if (rowptr[0] != 0) { h->last_error = "feasthip_set_polynomial_csr: rowptr[0] must be 0"; return FEASTHIP_ERROR_N; }
+    for (int64_t i = 0; i < N; ++i)
+        if (rowptr[i + 1] < rowptr[i]) { h->last_error = "feasthip_set_polynomial_csr: row pointers not monotone at row " + std::to_string(i); return FEASTHIP_ERROR_N; }
+    const int64_t nnz = rowptr[N];
+    if (nnz > INT32_MAX) { h->last_error = "feasthip_set_polynomial_csr: more than 2^31 - 1 nonzeros"; return FEASTHIP_ERROR_N; }
+    if (nnz > 0 && !col) { h->last_error = "feasthip_set_polynomial_csr: null column array"; return FEASTHIP_ERROR_N; }
+    for (int k = 0; k <= degree; ++k)
+        if (nnz > 0 && !vals[k]) { h->last_error = "feasthip_set_polynomial_csr: null value array of coefficient " + std::to_string(k); return FEASTHIP_ERROR_N; }
+    std::vector<int> rp((size_t)N + 1), cl((size_t)nnz);
+    for (int64_t i = 0; i < N; ++i) {
+        rp[i] = (int)rowptr[i];
+        for (int64_t k = rowptr[i]; k < rowptr[i + 1]; ++k) {
+            if (col[k] < 0 || col[k] >= N) { h->last_error = "feasthip_set_polynomial_csr: column index out of range in row " + std::to_string(i); return FEASTHIP_ERROR_N; }
+            if (k > rowptr[i] && col[k] <= col[k - 1]) { h->last_error = "feasthip_set_polynomial_csr: columns of row " + std::to_string(i) + " are not strictly increasing"; return FEASTHIP_ERROR_N; }
+            cl[k] = (int)col[k];
+        }
+    }
+    rp[N] = (int)nnz;
+    FH_CHECK(hipSetDevice(h->device));
+    FH_CHECK(hipStreamSynchronize(h->stream));
+    fh_free_problem(h);
+    const size_t es = is_complex ? sizeof(cplx) : sizeof(double);
+    h->dense.N = N; h->dense.is_complex = is_complex ? 1 : 0; h->dense.b_identity = 0;
+    h->poly.degree = degree; h->poly.sparse = 1;
+    fh_csr& c = h->csr;
+    c.N = N; c.nnz = nnz; c.is_complex = is_complex ? 1 : 0; c.b_identity = 0;
+    FH_CHECK(hipMalloc((void**)&c.rowptr, ((size_t)N + 1) * sizeof(int)));
+    FH_CHECK(hipMalloc((void**)&c.col, std::max<size_t>(1, (size_t)nnz) * sizeof(int)));
+    FH_CHECK(hipMemcpy(c.rowptr, rp.data(), ((size_t)N + 1) * sizeof(int), hipMemcpyHostToDevice));
+    if (nnz) FH_CHECK(hipMemcpy(c.col, cl.data(), (size_t)nnz * sizeof(int), hipMemcpyHostToDevice));
+    for (int k = 0; k <= degree; ++k) {
+        FH_CHECK(hipMalloc(&h->poly.coef[k], std::max<size_t>(1, (size_t)nnz) * es));
+        if (nnz) FH_CHECK(hipMemcpy(h->poly.coef[k], vals[k], (size_t)nnz * es, hipMemcpyHostToDevice));
+        // ||A_k||_F for the backward error (ingest arithmetic, once per problem; the explicit zeros add nothing)
+        const double* v = (const double*)vals[k];
+        double s = 0.0;
+        for (size_t i = 0; i < (size_t)nnz * (is_complex ? 2 : 1); ++i) s += v[i] * v[i];
+        h->poly.fro[k] = std::sqrt(s);
+    }
+    h->host_rowptr.swap(rp); h->host_col.swap(cl);
+    h->adjoint = 0;
+    h->kind = 3;
+    return 0;
+}
+
+// The N x N solves of either flavour: the dense LU of P(z_e), or for sparse coefficients the multifrontal one through the
+// factor cache of the sparse direct solver (same slots, same matching by z)
+static int poly_lu_single(feasthip_ctx* h, int ld, int m, cplx z, const cplx* Rhs, cplx* Y, int* status, int64_t* nfact) {
+    return h->poly.sparse ? fh_banded_solve_single(h, ld, m, z, Rhs, Y, status, nfact) : fh_dense_lu_solve_single(h, ld, m, z, Rhs, Y, status, nfact);
+}
+static int poly_lu_nodes(feasthip_ctx* h, int ld, int m, int ne, const cplx* RHS, size_t panel, cplx* Y, std::vector<int>& status, int64_t* nfact) {
+    return h->poly.sparse ? fh_banded_solve_nodes(h, ld, m, ne, h->zne, RHS, panel, Y, panel, status, nfact)
+                          : fh_dense_lu_solve_nodes(h, ld, m, ne, h->zne, RHS, panel, Y, panel, status, nfact);
+}
+
 // Y = P(z)^-1 R, N x m column-major; the factor is cached in the slot of the contour node z equals, else in one extra slot
 extern "C" int feasthip_poly_solve_dev(feasthip_handle h, double z_re, double z_im, int64_t m64, const void* dR, void* dY,
                                        feasthip_stats* stats) {
@@ -315,7 +490,7 @@ extern "C" int feasthip_poly_solve_dev(feasthip_handle h, double z_re, double z_
         fh_launch_to_panel((const cplx*)dR + (size_t)c0 * N, N, N, m, Rhs, ld, h->stream);
         int status = 0;
         int64_t nfact = 0;
-        if ((rc = fh_dense_lu_solve_single(h, ld, m, cmake(z_re, z_im), Rhs, Y, &status, &nfact))) return rc;
+        if ((rc = poly_lu_single(h, ld, m, cmake(z_re, z_im), Rhs, Y, &status, &nfact))) return rc;
         fh_launch_from_panel(Y, ld, N, m, (cplx*)dY + (size_t)c0 * N, N, h->stream);
         if (stats) stats->factorizations += nfact;
         worst = std::max(worst, status);
@@ -360,17 +535,27 @@ extern "C" int feasthip_poly_contour_apply_dev(feasthip_handle h, int64_t m64, c
         if ((rc = fh_buf(h, "pc_out", (size_t)d * panel, &OUT))) return rc;
         fh_launch_to_panel((const cplx*)dQ + (size_t)c0 * dN, dN, (int)dN, m, Qs, ld, h->stream);
         if ((rc = poly_lin_product(h, pc, 1, ld, Qs, Rs))) return rc;              // R = B_lin Q
-        // D_p = sum_k A_{k+1+p} R_k: d (d + 1) / 2 - 1 products per sweep, whatever the node count
-        for (int p = 0; p < nd; ++p)
-            for (int k = 0; k <= std::min(d - 2, d - 1 - p); ++k)
-                poly_product(h, pc, ld, k + 1 + p, Rs + (size_t)k * panel, D + (size_t)p * panel, k > 0, false);
+        // D_p = sum_k A_{k+1+p} R_k: d (d + 1) / 2 - 1 products per sweep, whatever the node count.  Sparse: one launch per R_k
+        // fanning over p (d - 1 launches; with R_{d-1} above, d per sweep), each D_p still summed in ascending k.
+        if (h->poly.sparse) {
+            for (int k = 0; k <= d - 2; ++k) {
+                fh_fan_out outs[FH_FAN_MAX];
+                int nout = 0;
+                for (int p = 0; p <= d - 1 - k; ++p) outs[nout++] = fh_fan_out{k + 1 + p, D + (size_t)p * panel, k > 0, false};
+                poly_fan(h, ld, Rs + (size_t)k * panel, outs, nout);
+            }
+        } else {
+            for (int p = 0; p < nd; ++p)
+                for (int k = 0; k <= std::min(d - 2, d - 1 - p); ++k)
+                    poly_product(h, pc, ld, k + 1 + p, Rs + (size_t)k * panel, D + (size_t)p * panel, k > 0, false);
+        }
         const dim3 grid(fh_vec_nblk(N, ld)), block(FH_BLOCK);
         fh_prof_begin(h, "poly_rhs");
         hipLaunchKernelGGL(k_poly_rhs, grid, block, 0, h->stream, Rs + (size_t)(d - 1) * panel, D, nd, dzw, ne, RHS, panel, panel);
         fh_prof_end(h);
         std::vector<int> status;
         int64_t nfact = 0;
-        if ((rc = fh_dense_lu_solve_nodes(h, ld, m, ne, h->zne, RHS, panel, Y, panel, status, &nfact))) return rc;
+        if ((rc = poly_lu_nodes(h, ld, m, ne, RHS, panel, Y, status, &nfact))) return rc;
         fh_prof_begin(h, "poly_expand");
         hipLaunchKernelGGL(k_poly_expand_sum, grid, block, 0, h->stream, Y, panel, Rs, d, dzw, dzw + ne, ne, OUT, panel);
         fh_prof_end(h);
@@ -517,9 +702,13 @@ extern "C" int feasthip_poly_ritz_residual_dev(feasthip_handle h, int64_t r64, c
         }
         fh_launch_from_panel(Xp, ld, (int)dN, mj, (cplx*)dX + (size_t)j * ld * dN, dN, h->stream);
         if (Mj > 0 && (res || backward_error)) {
-            for (int k = 0; k < d; ++k) poly_product(h, pc, ld, k, Xp + (size_t)k * panel, Tl, k > 0, false);     // T = sum_k A_k x_k
-            if (use_B) poly_product(h, pc, ld, d, Xp + (size_t)(d - 1) * panel, U, false, false);               // U = A_d x_{d-1}
-            for (int k = 0; k <= d; ++k) poly_product(h, pc, ld, k, Xp, PK + (size_t)k * panel, false, false);  // A_k x_0
+            if (h->poly.sparse) {
+                if ((rc = poly_residual_fan(h, ld, use_B != 0, Xp, Tl, U, PK))) return rc;
+            } else {
+                for (int k = 0; k < d; ++k) poly_product(h, pc, ld, k, Xp + (size_t)k * panel, Tl, k > 0, false);     // T = sum_k A_k x_k
+                if (use_B) poly_product(h, pc, ld, d, Xp + (size_t)(d - 1) * panel, U, false, false);               // U = A_d x_{d-1}
+                for (int k = 0; k <= d; ++k) poly_product(h, pc, ld, k, Xp, PK + (size_t)k * panel, false, false);  // A_k x_0
+            }
             std::fill(lamp.begin(), lamp.end(), cmake(0, 0));
             for (int c = 0; c < mj; ++c) lamp[c] = lamh[j * ld + c];
             cplx* dlam;

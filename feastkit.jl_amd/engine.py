@@ -523,6 +523,25 @@ class HipEngine:
         self.N, self.b_identity, self.poly_degree = N, False, len(fs) - 1
         self._problem_fp = None
 
+    def set_polynomial_csr(self, rowptr, col, vals):
+        """The same for sparse coefficients on one CSR pattern (feasthip_set_polynomial_csr; ingest.polynomial_union_csr makes
+        the arrays): rowptr / col 0-based, vals[k] the values of coeffs[k] on the pattern.  The poly_* methods work as on a
+        dense polynomial; P(z_e) is factored by the multifrontal LU of the sparse direct solver (band_plan, direct_plan_flops
+        and direct_plan_bytes describe it)."""
+        if len(vals) < 2:
+            raise ValueError("a polynomial needs at least two coefficient matrices")
+        rp = np.ascontiguousarray(rowptr, dtype=np.int64)
+        cl = np.ascontiguousarray(col, dtype=np.int64)
+        N = len(rp) - 1
+        cplx = any(np.iscomplexobj(v) for v in vals)
+        vs = [np.ascontiguousarray(v, dtype=np.complex128 if cplx else np.float64) for v in vals]
+        if N < 1 or rp[-1] != len(cl) or any(v.shape != (len(cl),) for v in vs):
+            raise ValueError("rowptr, col and the value arrays do not describe one pattern")
+        ptrs = (C.c_void_p * len(vs))(*[v.ctypes.data for v in vs])
+        self._chk(self.lib.feasthip_set_polynomial_csr(self.h, N, len(vs) - 1, int(cplx), _np_ptr(rp), _np_ptr(cl), ptrs))
+        self.N, self.b_identity, self.poly_degree = N, False, len(vs) - 1
+        self._problem_fp = None
+
     def _poly_empty(self, m):
         return self.torch.empty((m, self.poly_degree * self.N), dtype=self.torch.complex128, device=self.device)
 

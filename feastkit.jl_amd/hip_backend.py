@@ -1017,13 +1017,18 @@ POLY_RESIDUALS = ("pencil", "reference")
 
 
 def feast_hip_polynomial(engine, coeffs, Emid, r, M0, fpm, *, Q0=None, seed=20260515, contour=None, residual="pencil",
-                         eps_floor=0.0):
+                         eps_floor=0.0, union_csr=None):
     """P(lambda) x = 0 inside a circle: feast_hip_general's loop on the first companion linearisation with M0 d columns
     (feast_pep!, src/dense/feast_dense.jl:715-772, driving feast_gegv! :763) -- full contour, no factor 2, no
     orthonormalisation -- with the companion pencil replaced by the engine's poly_* calls: one N x N LU per node.
     ``residual``: "pencil" measures ||A_lin x - lambda B_lin x|| / max(|lambda|, 1), "reference" omits B_lin as the
     reference's kernel does (src/kernel/feast_kernel.jl:899-906).  q: the first N rows of the M linearised Ritz vectors
-    (src/dense/feast_dense.jl:768)."""
+    (src/dense/feast_dense.jl:768).
+    ``union_csr`` = (rowptr, col, vals) of ingest.polynomial_union_csr(coeffs): the coefficients stay sparse
+    (engine.set_polynomial_csr), P(z_e) is factored by the multifrontal LU and ``stats["polynomial"]`` gains plan =
+    "multifrontal", plan_factor_bytes / plan_transient_bytes / plan_flops per node and plan_nnz of the union pattern.  A
+    pattern without a plan, factors that do not fit and a rejected pivot raise FeastHipError (codes 9, 6, 8): there is no
+    band LU for polynomials, the caller decides what to do instead."""
     d = len(coeffs) - 1
     N = coeffs[0].shape[0]
     cols = M0 * d
@@ -1032,10 +1037,18 @@ def feast_hip_polynomial(engine, coeffs, Emid, r, M0, fpm, *, Q0=None, seed=2026
     if info:
         return _empty_result(N, info, complex_lambda=True)
     Zne, Wne = feast_gcontour(Emid, r, fpm) if contour is None else contour
-    engine.set_polynomial(coeffs)
+    plan = None
+    if union_csr is None:
+        engine.set_polynomial(coeffs)
+    else:
+        engine.set_polynomial_csr(*union_csr)
     engine.set_solver("direct", cache_factors=True, factor_precision=64)
     engine.set_real_projection(False)
     engine.set_contour(Zne, Wne, 1.0)
+    if union_csr is not None:
+        factor_bytes, transient_bytes = engine.direct_plan_bytes(1)
+        plan = {"plan": "multifrontal", "plan_factor_bytes": factor_bytes, "plan_transient_bytes": transient_bytes,
+                "plan_flops": engine.direct_plan_flops(), "plan_nnz": int(len(union_csr[1]))}
     Q_host = seeded_subspace(d * N, cols, seed) if Q0 is None else np.asarray(Q0, dtype=np.complex128)
     if Q_host.shape != (d * N, cols):
         raise ValueError(f"Q0 must be the linearised start block of shape ({d * N}, {cols})")
@@ -1047,6 +1060,8 @@ def feast_hip_polynomial(engine, coeffs, Emid, r, M0, fpm, *, Q0=None, seed=2026
     eps_hist = []
     stats = {"krylov_iterations": 0, "factorizations": 0, "solve_seconds": 0.0,
              "polynomial": {"degree": d, "columns": cols, "residual": residual, "backward_error": np.zeros(0), "eps_history": eps_hist}}
+    if plan is not None:
+        stats["polynomial"].update(plan)
     while True:
         dq, status, st = engine.poly_contour_apply(dQ, cols)
         stats["factorizations"] += st.get("factorizations", 0)

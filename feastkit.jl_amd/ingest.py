@@ -106,6 +106,44 @@ def julia_csc(A):
     return M.indptr.astype(np.int64) + 1, M.indices.astype(np.int64) + 1, np.ascontiguousarray(M.data)
 
 
+def polynomial_union_csr(coeffs):
+    """Sparse coefficients A_0 .. A_d of a matrix polynomial on ONE CSR pattern (feasthip_set_polynomial_csr): the union of
+    their patterns plus the whole diagonal (the multifrontal LU pivots there), columns sorted inside a row.
+    -> (rowptr int64[N + 1], col int64[nnz], vals): vals[k] = the nnz values of A_k on that pattern, explicit zeros where A_k
+    has no entry (duplicates of a coefficient are summed); all float64, or all complex128 if any coefficient is complex."""
+    mats = [sp.csr_matrix(c) for c in coeffs]
+    if not mats:
+        raise ValueError("no coefficient matrices")
+    N = mats[0].shape[0]
+    for m in mats:
+        if m.shape != (N, N):
+            raise ValueError("coefficient matrices must be square and of one size")
+    dt = np.complex128 if any(np.iscomplexobj(m.data) for m in mats) else np.float64
+    mats = [sp.csr_matrix(m, dtype=dt, copy=True) for m in mats]
+    for m in mats:
+        m.sum_duplicates()
+    # the pattern: a sum of 0/1 indicator matrices can never cancel, unlike a sum of the values
+    pat = sp.identity(N, dtype=np.int64, format="csr")
+    for m in mats:
+        pat = pat + sp.csr_matrix((np.ones(m.nnz, dtype=np.int64), m.indices, m.indptr), shape=(N, N))
+    pat = sp.csr_matrix(pat)
+    pat.sort_indices()
+    rowptr = pat.indptr.astype(np.int64)
+    col = pat.indices.astype(np.int64)
+    nnz = len(col)
+    rows = np.repeat(np.arange(N, dtype=np.int64), np.diff(rowptr))
+    key = rows * N + col                                   # sorted: row-major order with sorted columns
+    vals = []
+    for m in mats:
+        m.sort_indices()
+        mrows = np.repeat(np.arange(N, dtype=np.int64), np.diff(m.indptr))
+        pos = np.searchsorted(key, mrows * N + m.indices.astype(np.int64))
+        v = np.zeros(nnz, dtype=dt)
+        v[pos] = m.data
+        vals.append(v)
+    return rowptr, col, vals
+
+
 # ---- band storage of the reference's banded drivers (src/banded/feast_banded.jl:1-7, 205-271, 488-509)
 def band_upper_to_csr(Ab, k, kind="symmetric"):
     """Upper band storage, (k+1) x N with A(i, j) = Ab[k + i - j, j] for i <= j (0-based), to a full

@@ -511,6 +511,20 @@ int  feasthip_shifted_solve_dev(feasthip_handle h, double z_re, double z_im, int
  *   FEASTHIP_ERROR_FPM and names the feasthip_poly_* calls (feasthip_set_adjoint(1), a node range or list, a communicator and
  *   factor_precision 32 included: a polynomial sweep is one rank, forward, fp64).  feasthip_set_dense / feasthip_set_csr
  *   restore an ordinary handle.  A feasthip_poly_* call on any other handle returns FEASTHIP_ERROR_FPM.
+ * feasthip_set_polynomial_csr: the same handle for SPARSE coefficients, the counterpart of the reference's sparse polynomial
+ *   family feast_scsrpev! / feast_hcsrpev! / feast_gcsrpev! (src/sparse/feast_sparse.jl), which runs feast on the explicit
+ *   sparse dN x dN companion.  The degree + 1 coefficients share ONE CSR pattern (host arrays, 0-based: rowptr N + 1 entries
+ *   starting at 0 and monotone, col in 0 .. N - 1 and strictly increasing inside a row -- anything else is FEASTHIP_ERROR_N);
+ *   vals[k] holds the nnz = rowptr[N] values of A_k on that pattern, explicit zeros where A_k has no entry (all double or all
+ *   interleaved complex128).  The pattern should hold the whole diagonal (the multifrontal LU pivots there).  Every
+ *   feasthip_poly_* call below works on such a handle with the same meaning, and everything a polynomial handle refuses stays
+ *   refused.  P(z_e) is factored by the multifrontal LU of the sparse direct solver -- always: FH_MF / FH_WBAND do not apply,
+ *   FH_MF_LEAF does -- with its per-node factor cache; feasthip_direct_plan_flops / feasthip_direct_plan_bytes /
+ *   feasthip_band_plan describe the plan.  There is NO band LU behind it: a pattern without a multifrontal plan (a front beyond
+ *   16 384 rows) makes those calls and every solve return FEASTHIP_ERROR_FPM, and a factorisation whose pivots the multifrontal
+ *   LU rejects (zero pivot, or a boundary multiplier beyond the bound: it pivots only inside a front's fully-summed block)
+ *   makes the solve or sweep return FEASTHIP_ERROR_LAPACK with nothing computed; feasthip_last_error names the cause and the
+ *   sizes.  Factors that do not fit the device: FEASTHIP_ERROR_MEMORY.
  * feasthip_poly_solve_dev: Y = P(z)^-1 R, N x m (the shifted solve inside the companion elimination; no reference
  *   counterpart).  Factors are cached per contour node and matched by z, as in feasthip_shifted_solve.  Returns 0 or 8.
  * feasthip_poly_contour_apply_dev: Qproj = sum_e weight_scale w_e (z_e B_lin - A_lin)^-1 (B_lin Q), dN x m: the loop body
@@ -529,6 +543,8 @@ int  feasthip_shifted_solve_dev(feasthip_handle h, double z_re, double z_im, int
 #define FEASTHIP_POLY_MAX_DEGREE 8
 int  feasthip_set_polynomial(feasthip_handle h, int64_t N, int degree, int is_complex,
                              const void* const* coeffs /* degree + 1, column-major */, const int64_t* ld);
+int  feasthip_set_polynomial_csr(feasthip_handle h, int64_t N, int degree, int is_complex, const int64_t* rowptr,
+                                 const int64_t* col, const void* const* vals /* degree + 1 arrays of rowptr[N] values */);
 int  feasthip_poly_solve_dev(feasthip_handle h, double z_re, double z_im, int64_t m, const void* dR, void* dY, feasthip_stats* stats);
 int  feasthip_poly_contour_apply_dev(feasthip_handle h, int64_t m, const void* dQ, void* dQproj, int* node_status,
                                      feasthip_stats* stats);

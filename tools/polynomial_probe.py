@@ -11,6 +11,14 @@ calls run the same loop from the same start block.  Both calls factor in every s
     python tools/polynomial_probe.py                                     # both methods
     python tools/polynomial_probe.py --companion-only --package-root P   # the companion call on another checkout (the parent
                                                                          # commit: it has no feast_polynomial)
+
+--workload sparse: the sparse path (solver="sparse_direct") on the cfg 3 grid.  (A, B, mu) = workloads.laplacian_3d_pencil(50,
+40, 25), A_0 = A, A_1 = alpha B + beta A, A_2 = B (non-monic, N = 50 000): every pencil eigenvalue mu gives the two roots of
+lambda^2 + (alpha + beta mu) lambda + mu = 0, so the spectrum is known.  The circle holds the roots of smallest positive
+imaginary part up to the widest gap among the 8th .. 16th.  Comparator: feast_general on the explicit sparse 2N x 2N companion
+through the sparse direct solver from the same start block (how the reference's feast_gcsrpev! does it); --companion-only
+--package-root P runs that call alone on another checkout.  Also: k_spmm_fan's achieved GB/s on its algorithmic bytes in the
+residual step, and that step's products as single-coefficient feasthip_matmul_dev calls on CSR handles holding A_k.
 """
 import argparse
 import json
@@ -68,8 +76,14 @@ def main():
     ap.add_argument("--maxloop", type=int, default=4)
     ap.add_argument("--companion-only", action="store_true")
     ap.add_argument("--package-root", default=ROOT, help="checkout to import feastkit_jl_amd from")
+    ap.add_argument("--workload", choices=("dense", "sparse"), default="dense")
+    ap.add_argument("--grid", type=int, nargs=3, default=(50, 40, 25), help="sparse workload: nx ny nz")
+    ap.add_argument("--alpha", type=float, default=0.1)
+    ap.add_argument("--beta", type=float, default=0.05)
     a = ap.parse_args()
     sys.path[:0] = [a.package_root]
+    if a.workload == "sparse":
+        return main_sparse(a)
     import numpy as np
     import feastkit_jl_amd as fk
 
@@ -143,6 +157,164 @@ def main():
             row["lu_form"] = {"bytes_per_launch": traffic, "GB_per_s": round(gbs, 1), "fraction_of_copy_ceiling_4800": round(gbs / 4800.0, 4)}
         print(json.dumps(row), flush=True)
     eng.close()
+
+
+SPARSE_CLASSES = ("poly_spmm", "poly_mf_assemble", "poly_rhs", "poly_expand", "poly_residual", "mf_assemble", "mf_lu", "mf_solve", "spmm",
+                  "gram", "ritz")
+
+
+def sparse_quadratic(grid, alpha, beta):
+    """-> (coeffs CSR, centre, radius, roots inside) of A + lambda (alpha B + beta A) + lambda^2 B on the Laplacian pencil"""
+    import numpy as np
+    import scipy.sparse as sp
+    from feastkit_jl_amd import workloads
+    A, B, mu = workloads.laplacian_3d_pencil(*grid)
+    b = alpha + beta * mu
+    root = np.sqrt((b * b - 4.0 * mu).astype(complex))
+    lam = np.concatenate([(-b + root) / 2.0, (-b - root) / 2.0])
+    up = lam[lam.imag > 1e-8]
+    up = up[np.argsort(up.imag)]
+    center = complex(np.mean(up[:8]))
+    dist = np.sort(np.abs(lam - center))
+    j = 7 + int(np.argmax(dist[8:17] - dist[7:16]))                  # the circle holds dist[0 .. j]
+    radius = 0.5 * (dist[j] + dist[j + 1])
+    inside = lam[np.abs(lam - center) <= radius]
+    return [sp.csr_matrix(A), sp.csr_matrix(alpha * B + beta * A), sp.csr_matrix(B)], center, float(radius), inside
+
+
+def sparse_companion(coeffs):
+    import scipy.sparse as sp
+    N = coeffs[0].shape[0]
+    I = sp.identity(N, format="csr")
+    A = sp.bmat([[None, I], [-coeffs[0], -coeffs[1]]], format="csr")
+    B = sp.bmat([[I, None], [None, coeffs[2]]], format="csr")
+    return A, B
+
+
+def match_error(found, expected):
+    import numpy as np
+    if len(found) != len(expected):
+        return None
+    left, worst = list(expected), 0.0
+    for l in found:
+        j = int(np.argmin([abs(l - e) for e in left]))
+        worst = max(worst, abs(l - left.pop(j)))
+    return worst
+
+
+def main_sparse(a):
+    import numpy as np
+    import feastkit_jl_amd as fk
+    coeffs, center, radius, inside = sparse_quadratic(tuple(a.grid), a.alpha, a.beta)
+    d, N = 2, coeffs[0].shape[0]
+    M0 = len(inside)
+    Alin, Blin = sparse_companion(coeffs)
+    Q0 = fk.seeded_subspace(d * N, M0 * d)
+    eng = fk.HipEngine(0)
+    nodes = 16
+
+    def fpm():
+        f = fk.feastinit()
+        f[8], f[4], f[3] = nodes, 20, 10
+        return f
+
+    def run(name):
+        eng.synchronize()
+        t0 = time.perf_counter()
+        try:
+            if name == "polynomial":
+                r = fk.feast_polynomial(coeffs, center, radius, M0=M0, fpm=fpm(), engine=eng, Q0=Q0, solver="sparse_direct")
+            else:
+                r = fk.feast_general(Alin, Blin, center, radius, M0=M0 * d, fpm=fpm(), engine=eng, Q0=Q0, solver="sparse_direct")
+        except Exception as err:                    # does not fit, no plan: recorded, not tuned away
+            return err, 1e3 * (time.perf_counter() - t0)
+        eng.synchronize()
+        return r, 1e3 * (time.perf_counter() - t0)
+
+    names = ("companion",) if a.companion_only else ("polynomial", "companion")
+    for name in names:
+        run(name)
+    ms = {n: [] for n in names}
+    last = {}
+    for _ in range(a.runs):
+        for name in names:
+            last[name], t = run(name)
+            ms[name].append(t)
+    for name in names:
+        r = last[name]
+        row = {"workload": "sparse", "method": name, "grid": list(a.grid), "N": N, "order": N if name == "polynomial" else d * N, "M0": M0,
+               "columns": M0 * d, "nodes": nodes, "ms_median": float(np.median(ms[name])), "ms_all": ms[name]}
+        if isinstance(r, Exception):
+            row["error"] = str(r)
+        else:
+            row.update(loops=r.loop, M=r.M, expected_M=len(inside), info=r.info, epsout=r.epsout, factorizations=r.stats.get("factorizations"),
+                       eigenvalue_error=match_error(r.lambda_, inside), solver_substitution=r.stats.get("solver_substitution"))
+            if name == "polynomial":
+                poly = r.stats["polynomial"]
+                row.update(backward_error_max=float(np.max(poly["backward_error"])), plan=poly.get("plan"), fell_back=poly.get("fell_back"),
+                           factor_bytes_per_node=poly.get("plan_factor_bytes"), flops_per_node=poly.get("plan_flops"), nnz=poly.get("plan_nnz"))
+        print(json.dumps(row), flush=True)
+    for name in names:
+        eng.profile_enable(True)
+        eng.profile_set_period(1)
+        eng.profile_reset()
+        _, t = run(name)
+        prof = {}
+        for cls in SPARSE_CLASSES:
+            total, n = eng.profile_get(cls)
+            if n:
+                prof[cls] = {"ms": round(total, 3), "launches": n}
+        eng.profile_enable(False)
+        print(json.dumps({"workload": "sparse", "method": name, "profiled_solve_ms": t, "classes": prof}), flush=True)
+    if not a.companion_only:
+        fan_against_single_products(eng, fk, coeffs, M0 * d)
+    eng.close()
+
+
+def fan_against_single_products(eng, fk, coeffs, m):
+    """The residual step's products on one 64-column panel: d launches of k_spmm_fan (x_0 -> A_0 .. A_d, x_1 -> A_1, A_2) against
+    the same 2 d + 2 products as single-coefficient feasthip_matmul_dev calls on CSR handles holding A_k."""
+    import numpy as np
+    from feastkit_jl_amd.ingest import polynomial_union_csr
+    d, N = len(coeffs) - 1, coeffs[0].shape[0]
+    m = min(m, 64)
+    union = polynomial_union_csr(coeffs)
+    nnz = len(union[1])
+    eng.set_polynomial_csr(*union)
+    eng.set_solver("direct")
+    rng = np.random.default_rng(7)
+    dX = eng.upload(np.asfortranarray(rng.standard_normal((d * N, m)) + 1j * rng.standard_normal((d * N, m))))
+    V, lam = np.eye(m, dtype=complex), np.full(m, 0.1 + 0.5j)
+    eng.poly_ritz_residual(dX, m, V, lam, m)                       # warm-up
+    eng.profile_enable(True)
+    eng.profile_set_period(1)
+    reps = 10
+    eng.profile_reset()
+    for _ in range(reps):
+        eng.poly_ritz_residual(dX, m, V, lam, m)
+    fan_ms, fan_n = eng.profile_get("poly_spmm")
+    ld = 16 if m <= 16 else (32 if m <= 32 else 64)
+    panel = 16.0 * N * ld
+    # per residual step: launch 1 (d + 1 outputs), launch 2 (2 outputs, one accumulating): matrix bytes + X read + Y written (+ read)
+    bytes_step = (nnz * (4 + 8 * (d + 1)) + panel * (1 + d + 1)) + (nnz * (4 + 8 * 2) + panel * (1 + 2 + 1))
+    row = {"workload": "sparse", "what": "residual-step products", "m": m, "ld": ld, "fan_ms_per_step": fan_ms / reps, "fan_launches_per_step": fan_n / reps,
+           "fan_bytes_per_step": bytes_step, "fan_GB_per_s": bytes_step / (fan_ms / reps * 1e-3) / 1e9}
+    row["fan_fraction_of_copy_ceiling_4800"] = row["fan_GB_per_s"] / 4800.0
+    # the parent's way: one product per coefficient on CSR handles
+    dx0 = eng.upload(np.ascontiguousarray(eng.download(dX, m)[:N]))
+    single_ms, single_n = 0.0, 0
+    for k, count in ((0, 2), (1, 2), (2, 2)):                       # A_0 x_0 twice (T, PK_0), A_1 x_1 and A_1 x_0, A_2 x_1 and A_2 x_0
+        eng.set_problem(coeffs[k])
+        eng.matmul(0, dx0, m)
+        eng.profile_reset()
+        for _ in range(reps * count):
+            eng.matmul(0, dx0, m)
+        t, n = eng.profile_get("spmm")
+        single_ms += t / reps
+        single_n += n / reps
+    eng.profile_enable(False)
+    row.update(single_ms_per_step=single_ms, single_launches_per_step=single_n, single_over_fan=single_ms / (fan_ms / reps))
+    print(json.dumps(row), flush=True)
 
 
 def N2(name, N, d):
