@@ -95,6 +95,11 @@ SYMBOLS = {
     "feasthip_poly_matmul_dev": (_i, [_vp, _i, _i64, _vp, _vp]),
     "feasthip_poly_project_dev": (_i, [_vp, _i64, _vp, _vp, _vp]),
     "feasthip_poly_ritz_residual_dev": (_i, [_vp, _i64, _vp, _vp, _vp, _i64, _i, _i, _vp, _vp, _vp]),
+    "feasthip_poly_eval_cols_dev": (_i, [_vp, _i64, _vp, _vp, _vp]),
+    "feasthip_poly_resinv_apply_dev": (_i, [_vp, _i64, _vp, _vp, _vp, _vp, _ps]),
+    "feasthip_poly_project_reduced_dev": (_i, [_vp, _i64, _vp, _vp]),
+    "feasthip_poly_ritz_eval_dev": (_i, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "feasthip_poly_orthonormalize_dev": (_i, [_vp, _i64, _vp, _i, _d, _pi]),
     "feasthip_last_node_iterations": (_i, [_vp, _vp, _i]),
     "feasthip_last_column_iterations": (_i, [_vp, _vp, _i]),
     "feasthip_last_global_node_iterations": (_i, [_vp, _vp, _i]),

@@ -13,7 +13,8 @@ import scipy.sparse as sp
 from .engine import HipEngine
 from .contour import feast_contour, feast_gcontour
 from .hip_backend import (DIRECT_SOLVERS, ESTIMATE_SEED, check_direct_nodes, check_ortho, check_two_sided, feast_hip_estimate,
-                          feast_hip_general, feast_hip_general_two_sided, feast_hip_hermitian, feast_hip_polynomial, POLY_RESIDUALS)
+                          feast_hip_general, feast_hip_general_two_sided, feast_hip_hermitian, feast_hip_polynomial, feast_hip_polynomial_projected,
+                          POLY_METHODS, POLY_RESIDUALS, POLY_SET_ASIDE)
 from .ingest import polynomial_union_csr
 from .parameters import feastdefault, feastinit
 from .types import FEAST_UNINITIALIZED, FeastHipError, FeastResult
@@ -589,13 +590,14 @@ def feast_general(A, B=None, center=0.0, radius=1.0, *, M0=10, fpm=None, backend
 
 POLY_MAX_DEGREE = 8          # FEASTHIP_POLY_MAX_DEGREE
 POLY_DENSE_LIMIT = 12288     # sparse coefficients are expanded up to this size
+# POLY_SET_ASIDE (hip_backend): the two thresholds of the projected method's set-aside rule, (absolute, factor)
 
 
 POLY_SOLVERS = ("direct", "sparse_direct")
 
 
 def feast_polynomial(coeffs, center, radius, *, M0=10, fpm=None, engine=None, device=0, Q0=None, contour=None, seed=None,
-                     keep_factors=False, residual="pencil", solver="direct"):
+                     keep_factors=False, residual="pencil", solver="direct", method="linearised", ortho="mgs"):
     """feast_polynomial(coeffs, center, radius; M0, fpm): src/interfaces/feast_interfaces.jl:448-462, feast_pep! /
     feast_gepev! / feast_hepev! / feast_sypev! (src/dense/feast_dense.jl:715-772, 946-979).  Eigenpairs of
     P(lambda) x = 0, P(lambda) = coeffs[0] + lambda coeffs[1] + ... + lambda^d coeffs[d], with lambda inside the circle.
@@ -629,8 +631,34 @@ def feast_polynomial(coeffs, center, radius, *, M0=10, fpm=None, engine=None, de
     ||P(lambda_j) q_j|| / (sum_k |lambda_j|^k ||A_k||_F ||q_j||); ``stats["factorizations"]`` counts N x N factorisations.
     Under "sparse_direct" also plan ("multifrontal" | "dense"), plan_factor_bytes / plan_transient_bytes / plan_flops per node
     (feasthip_direct_plan_bytes / _flops; absent for "dense"), plan_nnz of the union pattern, and fell_back.
-    ``keep_factors``, ``contour``, ``seed``: as in feast_general."""
+    ``keep_factors``, ``contour``, ``seed``: as in feast_general.
+
+    ``method``:
+      "linearised" (default)  the loop described above, on M0 d linearised columns that are never orthonormalised.  It carries
+                          junk directions whose Ritz values can fall inside the circle, and may wander or stop at the loop
+                          limit on a start block it does not like.
+      "projected"         polynomial FEAST on an N-row subspace (Gavin, Miedlar, Polizzi): ``M0`` is the number of N-row
+                          columns -- choose M0 >= 1.3 x the expected count, as for feast -- and ``Q0`` is (N, M0).  Per loop the
+                          subspace is orthonormalised in the N-dimensional space (``ortho``: "mgs" | "cholqr_rr", as in feast),
+                          the polynomial itself is projected (Q^H A_k Q) and only the small r x r polynomial is linearised, on
+                          the host; the contour step is a residual-inverse sweep with the Ritz values as per-column shifts.
+                          A node is still factored once per solve (``stats["factorizations"]`` = the node count) and solves
+                          M0 right-hand sides per loop instead of M0 d.  The stop test, ``res`` and ``epsout`` are the backward
+                          error ||P(lambda) q|| / sum_k |lambda|^k ||A_k||_F of the unit vectors ``q``, so ``residual`` must stay
+                          "pencil" (the default; "reference" raises ValueError).  Of the d r candidates of a loop, those inside the
+                          circle are kept in ascending backward error, then those outside by distance; a kept pair inside whose
+                          backward error exceeds both POLY_SET_ASIDE[0] and POLY_SET_ASIDE[1] times the best one is set aside:
+                          it stays in the subspace and is left out of M and epsout.  At the loop limit the last iterates are
+                          returned with info = Feast_ERROR_NO_CONVERGENCE.  ``stats["polynomial"]`` = {degree, method, columns (M0),
+                          rank, candidates, set_aside, eps_history (one entry per loop each), backward_error}, plus the plan
+                          fields under "sparse_direct"; ``stats["ortho"]`` as in feast.
+    ``ortho`` is checked for both methods and used by "projected" only (the linearised loop never orthonormalises)."""
     mats = list(coeffs)
+    if method not in POLY_METHODS:
+        raise ValueError(f"method must be one of {POLY_METHODS}, not {method!r}")
+    check_ortho(ortho)
+    if method == "projected" and residual == "reference":
+        raise ValueError('method="projected" stops on the backward error of (lambda, q): residual="reference" does not apply')
     if len(mats) < 2:
         raise ValueError("feast_polynomial needs at least two coefficient matrices (degree >= 1)")
     if len(mats) - 1 > POLY_MAX_DEGREE:
@@ -666,15 +694,21 @@ def feast_polynomial(coeffs, center, radius, *, M0=10, fpm=None, engine=None, de
     fpm = feastinit() if fpm is None else fpm
     feastdefault(fpm)
     M0 = min(int(M0), N)
+    if method == "projected" and Q0 is not None and np.shape(Q0) != (N, M0):
+        raise ValueError(f'method="projected": Q0 must be the N-row start block of shape ({N}, {M0}), not {np.shape(Q0)}')
     eng = _engine(engine, device)
     eps_floor = float(np.sqrt(np.finfo(np.float32).eps)) if single else 0.0
-    common = dict(Q0=Q0, contour=contour, residual=residual, eps_floor=eps_floor, **({} if seed is None else {"seed": int(seed)}))
+    common = dict(Q0=Q0, contour=contour, eps_floor=eps_floor, **({} if seed is None else {"seed": int(seed)}))
+    if method == "projected":
+        driver, common["ortho"] = feast_hip_polynomial_projected, ortho
+    else:
+        driver, common["residual"] = feast_hip_polynomial, residual
     try:
         res = None
         if sparse_direct:
             union = polynomial_union_csr(mats)
             try:
-                res = feast_hip_polynomial(eng, mats, complex(center), float(radius), M0, fpm, union_csr=union, **common)
+                res = driver(eng, mats, complex(center), float(radius), M0, fpm, union_csr=union, **common)
                 if isinstance(res.stats, dict) and "polynomial" in res.stats:
                     res.stats["polynomial"]["fell_back"] = False
             except FeastHipError as err:
@@ -686,7 +720,7 @@ def feast_polynomial(coeffs, center, radius, *, M0=10, fpm=None, engine=None, de
                 substituted = {"requested": "sparse_direct", "used": "dense LU of the expanded coefficients", "reason": str(err)}
                 mats = [_densify(c) for c in mats]
         if res is None:
-            res = feast_hip_polynomial(eng, mats, complex(center), float(radius), M0, fpm, **common)
+            res = driver(eng, mats, complex(center), float(radius), M0, fpm, **common)
             if sparse_direct and isinstance(res.stats, dict) and "polynomial" in res.stats:
                 res.stats["polynomial"].update(plan="dense", plan_nnz=int(len(union[1])), fell_back=True)
         if substituted is not None and isinstance(res.stats, dict):

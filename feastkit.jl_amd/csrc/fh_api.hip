@@ -2506,10 +2506,9 @@ static int fh_ortho_wide(feasthip_ctx* h, int m, cplx* dQ, double rank_tol, int*
     return 0;
 }
 
-extern "C" int feasthip_orthonormalize_dev(feasthip_handle h, int64_t m64, void* dQ, double rank_tol, int* rank) {
-    int rc = fh_check_problem(h, m64, 1);
-    if (rc) return rc;
-    if (!dQ || !rank) { h->last_error = "orthonormalize: null argument"; return FEASTHIP_ERROR_INTERNAL; }
+// the body of feasthip_orthonormalize_dev / feasthip_poly_orthonormalize_dev once the handle and m are checked
+static int fh_orthonormalize_checked(feasthip_ctx* h, int64_t m64, void* dQ, double rank_tol, int* rank) {
+    int rc;
     FH_CHECK(hipSetDevice(h->device));
     fh_ortho_note_reset(h);
     if (m64 > FH_MAX_LD) {
@@ -2530,6 +2529,42 @@ extern "C" int feasthip_orthonormalize_dev(feasthip_handle h, int64_t m64, void*
     fh_prof_collect(h);
     FH_CHECK(hipGetLastError());       // launch-configuration errors do not surface through the stream sync
     return 0;
+}
+
+extern "C" int feasthip_orthonormalize_dev(feasthip_handle h, int64_t m64, void* dQ, double rank_tol, int* rank) {
+    int rc = fh_check_problem(h, m64, 1);
+    if (rc) return rc;
+    if (!dQ || !rank) { h->last_error = "orthonormalize: null argument"; return FEASTHIP_ERROR_INTERNAL; }
+    return fh_orthonormalize_checked(h, m64, dQ, rank_tol, rank);
+}
+
+// The same orthonormalisation for the N x m panels of a polynomial handle (the projected method's subspace lives in the
+// N-dimensional space; feasthip_orthonormalize_dev keeps refusing such a handle, like every pencil entry point).
+// unit_columns: every column is scaled to unit length first (a column of zero length is left alone), so that the rank rule
+// measures directions, not the lengths the contour sum happened to give them.
+extern "C" int feasthip_poly_orthonormalize_dev(feasthip_handle h, int64_t m64, void* dQ, int unit_columns, double rank_tol, int* rank) {
+    if (!h) return FEASTHIP_ERROR_INTERNAL;
+    if (h->poisoned) { h->last_error = "handle poisoned by an earlier device failure: destroy it"; return FEASTHIP_ERROR_INTERNAL; }
+    if (h->kind != 3) { h->last_error = "feasthip_poly_orthonormalize_dev: needs a polynomial handle (feasthip_set_polynomial); a dense or CSR handle takes feasthip_orthonormalize_dev"; return FEASTHIP_ERROR_FPM; }
+    if (m64 <= 0 || m64 > fh_N(h)) { h->last_error = "feasthip_poly_orthonormalize_dev: block width m must satisfy 1 <= m <= N"; return FEASTHIP_ERROR_M0; }
+    if (!dQ || !rank) { h->last_error = "feasthip_poly_orthonormalize_dev: null argument"; return FEASTHIP_ERROR_INTERNAL; }
+    if (unit_columns) {
+        FH_CHECK(hipSetDevice(h->device));
+        const int N = (int)fh_N(h);
+        int rc;
+        for (int64_t c0 = 0; c0 < m64; c0 += FH_MAX_LD) {
+            const int m = (int)std::min<int64_t>(FH_MAX_LD, m64 - c0), ld = fh_pick_ld(m);
+            cplx *X, *part, *ddots;
+            if ((rc = fh_buf(h, "po_X", (size_t)N * ld, &X))) return rc;
+            if ((rc = fh_buf(h, "po_part", (size_t)fh_vec_nblk(N, ld) * ld, &part))) return rc;
+            if ((rc = fh_buf(h, "po_dots", (size_t)ld, &ddots))) return rc;
+            fh_launch_to_panel((cplx*)dQ + (size_t)c0 * N, N, N, m, X, ld, h->stream);
+            fh_launch_dot_cols(X, X, N, ld, part, ddots, h->stream);
+            fh_launch_normalize_cols(X, ddots, N, ld, m, h->stream);
+            fh_launch_from_panel(X, ld, N, m, (cplx*)dQ + (size_t)c0 * N, N, h->stream);
+        }
+    }
+    return fh_orthonormalize_checked(h, m64, dQ, rank_tol, rank);
 }
 
 extern "C" int feasthip_orthonormalize(feasthip_handle h, int64_t m, void* Q, double rank_tol, int* rank) {

@@ -249,6 +249,72 @@ __global__ __launch_bounds__(FH_BLOCK) void k_poly_residual_fin(const double* __
 }
 
 // ---------------------------------------------------------------------------------------
+// Projected method (feasthip_poly_eval_cols_dev and the calls built on it): R[:, c] = P(lambda_c) X[:, c] on sparse
+// coefficients in one pass.  The row-slice layout of k_spmm_fan (lane <-> column, LD lanes own a row, gathers batched four
+// deep); per nonzero the column index, the d + 1 coefficient values and the gathered X row are loaded once, the lane forms
+// sum_k a_k lambda_c^k by Horner in registers (lambda_c loaded once per row slice) and adds its product with the X element to ONE
+// accumulator.  A nout = d + 1 fan-out holds d + 1 accumulators, writes d + 1 panels and needs a pass that combines them.
+// No atomics, the row sum runs in CSR order: reproducible.
+// Algorithmic traffic: nnz (4 + (d + 1) sizeof(VT)) of matrix, one X row of 16 LD B gathered per nonzero, N LD 16 B written.
+// ---------------------------------------------------------------------------------------
+struct fh_horner_args {
+    const int* rowptr; const int* col;
+    const cplx* X; const cplx* lam;   // N x LD panel, LD per-column values
+    cplx* Y;
+    int N, d;
+    const void* val[PD + 1];
+};
+
+template <typename VT, int LD>
+__global__ __launch_bounds__(FH_BLOCK) void k_spmm_horner(fh_horner_args a) {
+    constexpr int ROWS = FH_BLOCK / LD;
+    const int c = threadIdx.x % LD;
+    const int i = blockIdx.x * ROWS + threadIdx.x / LD;
+    if (i >= a.N) return;
+    const int* __restrict__ colidx = a.col;
+    const cplx* __restrict__ X = a.X;
+    const cplx l = a.lam[c];
+    const int k0 = a.rowptr[i], k1 = a.rowptr[i + 1];
+    cplx acc = cmake(0, 0);
+    for (int kb = k0; kb < k1; kb += 4) {
+        cplx xs[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) xs[q] = X[(size_t)colidx[min(kb + q, k1 - 1)] * LD + c];
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+            if (kb + q < k1) {
+                cplx v = cmake(0, 0);
+#pragma unroll
+                for (int k = PD; k >= 0; --k)
+                    if (k <= a.d) v = cadd(cmul(v, l), poly_val(((const VT*)a.val[k])[kb + q]));
+                cfma(acc, v, xs[q]);
+            }
+    }
+    a.Y[(size_t)i * LD + c] = acc;
+}
+
+// ---------------------------------------------------------------------------------------
+// The residual-inverse sweep's sum in one pass over the ne node-solution panels, nodes in ascending e, one write per element:
+//     Q[i, c] = sum_e T[e][c] (X[i, c] - Y_e[i, c]),   T[e][c] = w_e / (z_e - sigma_c)   (host table, ne x ld)
+// X == null: the plain sweep Q = sum_e T[e][c] Y_e with T[e][c] = w_e.  (The grid stride is a multiple of ld: a thread keeps its
+// column.)  Traffic: ne + 1 panels read, one written.
+// ---------------------------------------------------------------------------------------
+__global__ __launch_bounds__(FH_BLOCK) void k_poly_resinv_acc(const cplx* __restrict__ X, const cplx* __restrict__ Y, size_t stride,
+                                                               const cplx* __restrict__ T, int ne, int ld, cplx* __restrict__ Q, size_t total) {
+    const int c = threadIdx.x % ld;
+    for (size_t e = (size_t)blockIdx.x * FH_BLOCK + threadIdx.x; e < total; e += (size_t)gridDim.x * FH_BLOCK) {
+        const cplx x = X ? X[e] : cmake(0, 0);
+        cplx acc = cmake(0, 0);
+#pragma unroll 4
+        for (int q = 0; q < ne; ++q) {
+            const cplx y = Y[(size_t)q * stride + e];
+            cfma(acc, T[(size_t)q * ld + c], X ? csub(x, y) : y);
+        }
+        Q[e] = acc;
+    }
+}
+
+// ---------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------
 static inline double poly_now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
@@ -465,9 +531,10 @@ extern "C" int feasthip_set_polynomial_csr(feasthip_handle h, int64_t N, int deg
 static int poly_lu_single(feasthip_ctx* h, int ld, int m, cplx z, const cplx* Rhs, cplx* Y, int* status, int64_t* nfact) {
     return h->poly.sparse ? fh_banded_solve_single(h, ld, m, z, Rhs, Y, status, nfact) : fh_dense_lu_solve_single(h, ld, m, z, Rhs, Y, status, nfact);
 }
-static int poly_lu_nodes(feasthip_ctx* h, int ld, int m, int ne, const cplx* RHS, size_t panel, cplx* Y, std::vector<int>& status, int64_t* nfact) {
-    return h->poly.sparse ? fh_banded_solve_nodes(h, ld, m, ne, h->zne, RHS, panel, Y, panel, status, nfact)
-                          : fh_dense_lu_solve_nodes(h, ld, m, ne, h->zne, RHS, panel, Y, panel, status, nfact);
+// (rhs_stride: `panel` for one right-hand side panel per node, 0 for one panel shared by all nodes)
+static int poly_lu_nodes(feasthip_ctx* h, int ld, int m, int ne, const cplx* RHS, size_t rhs_stride, size_t panel, cplx* Y, std::vector<int>& status, int64_t* nfact) {
+    return h->poly.sparse ? fh_banded_solve_nodes(h, ld, m, ne, h->zne, RHS, rhs_stride, Y, panel, status, nfact)
+                          : fh_dense_lu_solve_nodes(h, ld, m, ne, h->zne, RHS, rhs_stride, Y, panel, status, nfact);
 }
 
 // Y = P(z)^-1 R, N x m column-major; the factor is cached in the slot of the contour node z equals, else in one extra slot
@@ -555,7 +622,7 @@ extern "C" int feasthip_poly_contour_apply_dev(feasthip_handle h, int64_t m64, c
         fh_prof_end(h);
         std::vector<int> status;
         int64_t nfact = 0;
-        if ((rc = poly_lu_nodes(h, ld, m, ne, RHS, panel, Y, status, &nfact))) return rc;
+        if ((rc = poly_lu_nodes(h, ld, m, ne, RHS, panel, panel, Y, status, &nfact))) return rc;
         fh_prof_begin(h, "poly_expand");
         hipLaunchKernelGGL(k_poly_expand_sum, grid, block, 0, h->stream, Y, panel, Rs, d, dzw, dzw + ne, ne, OUT, panel);
         fh_prof_end(h);
@@ -729,6 +796,276 @@ extern "C" int feasthip_poly_ritz_residual_dev(feasthip_handle h, int64_t r64, c
                     backward_error[j * ld + c] = den > 0.0 ? std::sqrt(sums[ld + c]) / den : 0.0;
                 }
             }
+        }
+    }
+    FH_CHECK(hipStreamSynchronize(h->stream));
+    fh_prof_collect(h);
+    FH_CHECK(hipGetLastError());
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------
+// Projected method (method = "projected" of feast_polynomial): the subspace lives in the N-dimensional space, so every call
+// below works on N x m panels and a node's solve has m right-hand sides, not m d.
+// ---------------------------------------------------------------------------------------
+
+// R[:, c] = P(lam_c) X[:, c] on one N x ld panel; dlam: ld device values.  Sparse: k_spmm_horner.  Dense: R = sum_k A_k (X diag
+// lam^k) through the dense product on the column-scaled copy W of X (scaled once more per degree).  X is left as it is.
+static int poly_eval_panel(feasthip_ctx* h, const poly_coefs& pc, int ld, const cplx* dlam, const cplx* X, cplx* W, cplx* R) {
+    const int N = (int)h->dense.N, d = h->poly.degree;
+    if (h->poly.sparse) {
+        fh_horner_args a;
+        memset(&a, 0, sizeof(a));
+        a.rowptr = h->csr.rowptr; a.col = h->csr.col; a.X = X; a.lam = dlam; a.Y = R; a.N = N; a.d = d;
+        for (int k = 0; k <= d; ++k) a.val[k] = h->poly.coef[k];
+        const dim3 grid((unsigned)((N + FH_BLOCK / ld - 1) / (FH_BLOCK / ld))), block(FH_BLOCK);
+        fh_prof_begin(h, "poly_horner");
+        fh_with_ld(ld, [&](auto L) {
+            constexpr int LD = decltype(L)::value;
+            if (h->csr.is_complex) hipLaunchKernelGGL((k_spmm_horner<cplx, LD>), grid, block, 0, h->stream, a);
+            else hipLaunchKernelGGL((k_spmm_horner<double, LD>), grid, block, 0, h->stream, a);
+        });
+        fh_prof_end(h);
+        return 0;
+    }
+    FH_CHECK(hipMemcpyAsync(W, X, (size_t)N * ld * sizeof(cplx), hipMemcpyDeviceToDevice, h->stream));
+    for (int k = 0; k <= d; ++k) {
+        poly_product(h, pc, ld, k, W, R, k > 0, false);
+        if (k < d) {
+            fh_prof_begin(h, "poly_horner");
+            fh_launch_scale_cols(W, dlam, N, ld, h->stream);
+            fh_prof_end(h);
+        }
+    }
+    return 0;
+}
+
+// ld device values: v[c0 .. c0 + m) of the host array, zero padded; a non-finite entry is replaced by `instead`
+static int poly_upload_cols(feasthip_ctx* h, const char* name, const cplx* v, int64_t c0, int m, int ld, cplx instead, cplx** dev) {
+    std::vector<cplx> p(ld, cmake(0, 0));
+    for (int c = 0; c < m; ++c) {
+        const cplx x = v[c0 + c];
+        p[c] = std::isfinite(x.x) && std::isfinite(x.y) ? x : instead;
+    }
+    return poly_upload(h, name, p, dev);
+}
+
+// R[:, j] = P(lambda_j) X[:, j], N x m column-major, lambda: m complex values on the host
+extern "C" int feasthip_poly_eval_cols_dev(feasthip_handle h, int64_t m64, const void* lambda, const void* dX, void* dR) {
+    int rc = poly_check(h, "feasthip_poly_eval_cols_dev", m64, 1 << 20);
+    if (rc) return rc;
+    if (!lambda || !dX || !dR) { h->last_error = "feasthip_poly_eval_cols_dev: null argument"; return FEASTHIP_ERROR_INTERNAL; }
+    FH_CHECK(hipSetDevice(h->device));
+    const int N = (int)h->dense.N;
+    poly_coefs pc;
+    if ((rc = pc.acquire(h))) return rc;
+    for (int64_t c0 = 0; c0 < m64; c0 += FH_MAX_LD) {
+        const int m = (int)std::min<int64_t>(FH_MAX_LD, m64 - c0), ld = fh_pick_ld(m);
+        const size_t panel = (size_t)N * ld;
+        cplx *Xs, *W, *R, *dlam;
+        if ((rc = fh_buf(h, "pe_X", panel, &Xs))) return rc;
+        if ((rc = fh_buf(h, "pe_W", panel, &W))) return rc;
+        if ((rc = fh_buf(h, "pe_R", panel, &R))) return rc;
+        if ((rc = poly_upload_cols(h, "pe_lam", (const cplx*)lambda, c0, m, ld, cmake(0, 0), &dlam))) return rc;
+        fh_launch_to_panel((const cplx*)dX + (size_t)c0 * N, N, N, m, Xs, ld, h->stream);
+        if ((rc = poly_eval_panel(h, pc, ld, dlam, Xs, W, R))) return rc;
+        fh_launch_from_panel(R, ld, N, m, (cplx*)dR + (size_t)c0 * N, N, h->stream);
+    }
+    FH_CHECK(hipStreamSynchronize(h->stream));
+    fh_prof_collect(h);
+    FH_CHECK(hipGetLastError());
+    return 0;
+}
+
+// The contour step of the projected method on an N x m block.
+//   sigma == null:  Q = sum_e w_e P(z_e)^-1 X                                                  (plain sweep)
+//   else         :  R[:, j] = P(sigma_j) x_j,  Y_e = P(z_e)^-1 R,  Q[:, j] = sum_e w_e (x_j - Y_e[:, j]) / (z_e - sigma_j)
+// One right-hand side panel is shared by all nodes; the factors come from the per-node cache as in the linearised sweep.
+extern "C" int feasthip_poly_resinv_apply_dev(feasthip_handle h, int64_t m64, const void* sigma, const void* dX, void* dQ,
+                                              int* node_status, feasthip_stats* stats) {
+    int rc = poly_check(h, "feasthip_poly_resinv_apply_dev", m64, 1 << 20);
+    if (rc) return rc;
+    if (!dX || !dQ) { h->last_error = "feasthip_poly_resinv_apply_dev: null argument"; return FEASTHIP_ERROR_INTERNAL; }
+    if (h->zne.empty()) { h->last_error = "feasthip_poly_resinv_apply_dev: no contour set (feasthip_set_contour)"; return FEASTHIP_ERROR_FPM; }
+    if (h->real_projection) { h->last_error = "feasthip_poly_resinv_apply_dev: the real projection does not apply to a polynomial sweep"; return FEASTHIP_ERROR_FPM; }
+    const int N = (int)h->dense.N, ne = (int)h->zne.size();
+    const cplx* sg = (const cplx*)sigma;
+    if (sg)
+        for (int64_t j = 0; j < m64; ++j) {
+            if (!std::isfinite(sg[j].x) || !std::isfinite(sg[j].y)) { h->last_error = "feasthip_poly_resinv_apply_dev: shift " + std::to_string(j) + " is not finite"; return FEASTHIP_ERROR_FPM; }
+            for (int e = 0; e < ne; ++e) {
+                const cplx z = h->zne[e];
+                const double dist = std::hypot(z.x - sg[j].x, z.y - sg[j].y), scale = std::max(std::hypot(z.x, z.y), std::hypot(sg[j].x, sg[j].y));
+                if (dist <= 4.0 * 2.220446049250313e-16 * scale || dist == 0.0) {
+                    h->last_error = "feasthip_poly_resinv_apply_dev: shift " + std::to_string(j) + " coincides with contour node " + std::to_string(e);
+                    return FEASTHIP_ERROR_FPM;
+                }
+            }
+        }
+    FH_CHECK(hipSetDevice(h->device));
+    const double t0 = poly_now();
+    if (stats) memset(stats, 0, sizeof(*stats));
+    if (node_status) for (int e = 0; e < ne; ++e) node_status[e] = 0;
+    poly_coefs pc;
+    if ((rc = pc.acquire(h))) return rc;
+    for (int64_t c0 = 0; c0 < m64; c0 += FH_MAX_LD) {
+        const int m = (int)std::min<int64_t>(FH_MAX_LD, m64 - c0), ld = fh_pick_ld(m);
+        const size_t panel = (size_t)N * ld;
+        cplx *Xs, *W, *R, *Y, *Q, *dlam = nullptr, *dT;
+        if ((rc = fh_buf(h, "ri_X", panel, &Xs))) return rc;
+        if ((rc = fh_buf(h, "ri_W", panel, &W))) return rc;
+        if ((rc = fh_buf(h, "ri_R", panel, &R))) return rc;
+        if ((rc = fh_buf(h, "ri_Y", (size_t)ne * panel, &Y))) return rc;
+        if ((rc = fh_buf(h, "ri_Q", panel, &Q))) return rc;
+        // T[e][c] = w_e / (z_e - sigma_c), or w_e for the plain sweep; the padding columns are zero
+        std::vector<cplx> T((size_t)ne * ld, cmake(0, 0));
+        for (int e = 0; e < ne; ++e) {
+            const cplx w = cscale(h->wne[e], h->weight_scale);
+            for (int c = 0; c < m; ++c) T[(size_t)e * ld + c] = sg ? cdiv(w, csub(h->zne[e], sg[c0 + c])) : w;
+        }
+        if ((rc = poly_upload(h, "ri_T", T, &dT))) return rc;
+        fh_launch_to_panel((const cplx*)dX + (size_t)c0 * N, N, N, m, Xs, ld, h->stream);
+        const cplx* rhs = Xs;
+        if (sg) {
+            if ((rc = poly_upload_cols(h, "ri_lam", sg, c0, m, ld, cmake(0, 0), &dlam))) return rc;
+            if ((rc = poly_eval_panel(h, pc, ld, dlam, Xs, W, R))) return rc;
+            rhs = R;
+        }
+        std::vector<int> status;
+        int64_t nfact = 0;
+        if ((rc = poly_lu_nodes(h, ld, m, ne, rhs, 0, panel, Y, status, &nfact))) return rc;
+        fh_prof_begin(h, "poly_resinv");
+        hipLaunchKernelGGL(k_poly_resinv_acc, dim3(fh_vec_nblk(N, ld)), dim3(FH_BLOCK), 0, h->stream, sg ? Xs : (const cplx*)nullptr, Y, panel, dT, ne, ld, Q, panel);
+        fh_prof_end(h);
+        fh_launch_from_panel(Q, ld, N, m, (cplx*)dQ + (size_t)c0 * N, N, h->stream);
+        if (stats) stats->factorizations += nfact;
+        if (node_status) for (int e = 0; e < ne; ++e) node_status[e] = std::max(node_status[e], status[e]);
+    }
+    FH_CHECK(hipStreamSynchronize(h->stream));
+    fh_prof_collect(h);
+    FH_CHECK(hipGetLastError());
+    if (stats) stats->seconds_total = poly_now() - t0;
+    return 0;
+}
+
+// Ahat_k = Q^H A_k Q, k = 0 .. d: d + 1 r x r column-major matrices one behind the other on the host.  Per 64-column panel Q_j
+// the products W_k = A_k Q_j (sparse: one fan-out launch), then one Gram launch per block (i, j) and coefficient.
+extern "C" int feasthip_poly_project_reduced_dev(feasthip_handle h, int64_t r64, const void* dQ, void* Ahat_host) {
+    int rc = poly_check(h, "feasthip_poly_project_reduced_dev", r64, h && h->kind == 3 ? h->dense.N : 1);
+    if (rc) return rc;
+    if (!dQ || !Ahat_host) { h->last_error = "feasthip_poly_project_reduced_dev: null argument"; return FEASTHIP_ERROR_INTERNAL; }
+    FH_CHECK(hipSetDevice(h->device));
+    const int N = (int)h->dense.N, d = h->poly.degree, r = (int)r64;
+    const int ld = r > FH_MAX_LD ? FH_MAX_LD : fh_pick_ld(r), npan = (r + ld - 1) / ld;
+    const size_t panel = (size_t)N * ld, g2 = (size_t)ld * ld;
+    poly_coefs pc;
+    if ((rc = pc.acquire(h))) return rc;
+    cplx *Qi, *Qj, *W, *G, *gw;
+    if ((rc = fh_buf(h, "pq_Qi", panel, &Qi))) return rc;
+    if ((rc = fh_buf(h, "pq_Qj", panel, &Qj))) return rc;
+    if ((rc = fh_buf(h, "pq_W", (size_t)(d + 1) * panel, &W))) return rc;
+    if ((rc = fh_buf(h, "pq_G", (size_t)(d + 1) * g2, &G))) return rc;
+    if ((rc = fh_buf(h, "gram_work", fh_gram_work_elems(ld), &gw))) return rc;
+    cplx* out = (cplx*)Ahat_host;
+    std::vector<cplx> Gh((size_t)(d + 1) * g2);
+    for (int j = 0; j < npan; ++j) {
+        const int mj = std::min(ld, r - j * ld);
+        fh_launch_to_panel((const cplx*)dQ + (size_t)j * ld * N, N, N, mj, Qj, ld, h->stream);
+        if (h->poly.sparse) {
+            fh_fan_out outs[FH_FAN_MAX];
+            for (int k = 0; k <= d; ++k) outs[k] = fh_fan_out{k, W + (size_t)k * panel, false, false};
+            poly_fan(h, ld, Qj, outs, d + 1);
+        } else {
+            for (int k = 0; k <= d; ++k) poly_product(h, pc, ld, k, Qj, W + (size_t)k * panel, false, false);
+        }
+        for (int i = 0; i < npan; ++i) {
+            const int mi = std::min(ld, r - i * ld);
+            const cplx* Ql = Qj;
+            if (i != j) { fh_launch_to_panel((const cplx*)dQ + (size_t)i * ld * N, N, N, mi, Qi, ld, h->stream); Ql = Qi; }
+            for (int k = 0; k <= d; ++k) {
+                fh_prof_begin(h, "gram");
+                fh_launch_gram(Ql, W + (size_t)k * panel, N, ld, 0, gw, G + (size_t)k * g2, h->stream);
+                fh_prof_end(h);
+            }
+            FH_CHECK(hipMemcpyAsync(Gh.data(), G, Gh.size() * sizeof(cplx), hipMemcpyDeviceToHost, h->stream));
+            FH_CHECK(hipStreamSynchronize(h->stream));
+            for (int k = 0; k <= d; ++k)
+                for (int c2 = 0; c2 < mj; ++c2)
+                    for (int c1 = 0; c1 < mi; ++c1)
+                        out[(size_t)k * r * r + (size_t)(j * ld + c2) * r + i * ld + c1] = Gh[(size_t)k * g2 + (size_t)c2 * ld + c1];
+        }
+    }
+    fh_prof_collect(h);
+    FH_CHECK(hipGetLastError());
+    return 0;
+}
+
+// X = Q Y (N x ncand; Q: N x r, Y: r x ncand column-major on the host), every column scaled to unit length, and
+//   backward_error[i] = || P(theta_i) x_i || / sum_k |theta_i|^k ||A_k||_F
+// (+inf for a non-finite theta_i and for a column of zero length).  backward_error may be null.
+extern "C" int feasthip_poly_ritz_eval_dev(feasthip_handle h, int64_t r64, const void* dQ, int64_t ncand, const void* Y_host,
+                                           const void* theta, void* dX, double* backward_error) {
+    int rc = poly_check(h, "feasthip_poly_ritz_eval_dev", r64, h && h->kind == 3 ? h->dense.N : 1);
+    if (rc) return rc;
+    if (!dQ || !Y_host || !dX || dQ == dX || (backward_error && !theta)) { h->last_error = "feasthip_poly_ritz_eval_dev: null argument, or X aliases Q"; return FEASTHIP_ERROR_INTERNAL; }
+    if (ncand < 1 || ncand > (1 << 20)) { h->last_error = "feasthip_poly_ritz_eval_dev: candidate count out of range"; return FEASTHIP_ERROR_M0; }
+    FH_CHECK(hipSetDevice(h->device));
+    const int N = (int)h->dense.N, d = h->poly.degree, r = (int)r64;
+    const int ld = (r > FH_MAX_LD || ncand > FH_MAX_LD) ? FH_MAX_LD : fh_pick_ld(std::max<int64_t>(r, ncand));
+    const int npr = (r + ld - 1) / ld, npc = (int)((ncand + ld - 1) / ld);
+    const size_t panel = (size_t)N * ld;
+    poly_coefs pc;
+    if ((rc = pc.acquire(h))) return rc;
+    cplx *Qp, *Xp, *Tp, *W, *R, *part, *ddots;
+    if ((rc = fh_buf(h, "pv_Q", panel, &Qp))) return rc;
+    if ((rc = fh_buf(h, "pv_X", panel, &Xp))) return rc;
+    if ((rc = fh_buf(h, "pv_T", panel, &Tp))) return rc;
+    if ((rc = fh_buf(h, "pv_W", panel, &W))) return rc;
+    if ((rc = fh_buf(h, "pv_R", panel, &R))) return rc;
+    if ((rc = fh_buf(h, "pv_part", (size_t)fh_vec_nblk(N, ld) * ld, &part))) return rc;
+    if ((rc = fh_buf(h, "pv_dots", (size_t)2 * ld, &ddots))) return rc;
+    const cplx* Yh = (const cplx*)Y_host;
+    const cplx* th = (const cplx*)theta;
+    std::vector<cplx> Vp((size_t)ld * ld), dots(2 * (size_t)ld);
+    for (int j = 0; j < npc; ++j) {
+        const int mj = (int)std::min<int64_t>(ld, ncand - (int64_t)j * ld);
+        for (int i = 0; i < npr; ++i) {
+            const int mi = std::min(ld, r - i * ld);
+            std::fill(Vp.begin(), Vp.end(), cmake(0, 0));
+            for (int c2 = 0; c2 < mj; ++c2)
+                for (int c1 = 0; c1 < mi; ++c1) Vp[(size_t)c2 * ld + c1] = Yh[(size_t)((int64_t)j * ld + c2) * r + i * ld + c1];
+            cplx* dV;
+            if ((rc = poly_upload(h, "pv_V", Vp, &dV))) return rc;
+            fh_launch_to_panel((const cplx*)dQ + (size_t)i * ld * N, N, N, mi, Qp, ld, h->stream);
+            fh_prof_begin(h, "ritz");
+            if (i == 0) fh_launch_small_matmul(Qp, dV, N, ld, Xp, h->stream);
+            else {
+                fh_launch_small_matmul(Qp, dV, N, ld, Tp, h->stream);
+                fh_launch_axpy_cols(Xp, Tp, pc.minus, N, ld, h->stream);          // X += T
+            }
+            fh_prof_end(h);
+        }
+        fh_launch_dot_cols(Xp, Xp, N, ld, part, ddots, h->stream);
+        fh_launch_normalize_cols(Xp, ddots, N, ld, mj, h->stream);
+        fh_launch_from_panel(Xp, ld, N, mj, (cplx*)dX + (size_t)j * ld * N, N, h->stream);
+        if (!backward_error) continue;
+        cplx* dlam;
+        if ((rc = poly_upload_cols(h, "pv_lam", th, (int64_t)j * ld, mj, ld, cmake(0, 0), &dlam))) return rc;
+        if ((rc = poly_eval_panel(h, pc, ld, dlam, Xp, W, R))) return rc;
+        fh_launch_dot_cols(R, R, N, ld, part, ddots + ld, h->stream);
+        FH_CHECK(hipMemcpyAsync(dots.data(), ddots, dots.size() * sizeof(cplx), hipMemcpyDeviceToHost, h->stream));
+        FH_CHECK(hipStreamSynchronize(h->stream));
+        for (int c = 0; c < mj; ++c) {
+            const cplx t = th[(int64_t)j * ld + c];
+            double be = INFINITY;
+            if (std::isfinite(t.x) && std::isfinite(t.y) && dots[c].x > 0.0) {
+                const double la = std::hypot(t.x, t.y);
+                double scale = 0.0, pw = 1.0;
+                for (int k = 0; k <= d; ++k) { scale += pw * h->poly.fro[k]; pw *= la; }
+                be = scale > 0.0 ? std::sqrt(dots[ld + c].x) / scale : 0.0;
+                if (!std::isfinite(be)) be = INFINITY;
+            }
+            backward_error[(int64_t)j * ld + c] = be;
         }
     }
     FH_CHECK(hipStreamSynchronize(h->stream));

@@ -596,6 +596,72 @@ class HipEngine:
                                                            _np_ptr(res), _np_ptr(bwd)))
         return dX, res[:M].copy(), bwd[:M].copy()
 
+    # -- projected method: N x m blocks, i.e. (m, N) tensors as for a pencil -------------------------------------------------------
+    def poly_eval_cols(self, dX, lam, m):
+        """R[:, j] = P(lam_j) X[:, j] on an N x m device block (feasthip_poly_eval_cols_dev)."""
+        self._sync_stream()
+        lamc = np.ascontiguousarray(lam, dtype=np.complex128)
+        if lamc.shape != (int(m),):
+            raise ValueError("poly_eval_cols needs one value per column")
+        dR = self.empty(dX.shape[0])
+        self._chk(self.lib.feasthip_poly_eval_cols_dev(self.h, int(m), _np_ptr(lamc), C.c_void_p(dX.data_ptr()), C.c_void_p(dR.data_ptr())))
+        return dR
+
+    def poly_resinv_apply(self, dX, m, sigma=None):
+        """The projected method's contour step on an N x m device block -> (dQ, status per node, stats): the plain sweep
+        sum_e w_e P(z_e)^-1 X (sigma None), else the residual-inverse sweep with one shift per column
+        (feasthip_poly_resinv_apply_dev)."""
+        self._sync_stream()
+        sg = None
+        if sigma is not None:
+            sg = np.ascontiguousarray(sigma, dtype=np.complex128)
+            if sg.shape != (int(m),):
+                raise ValueError("poly_resinv_apply needs one shift per column")
+        dQ = self.empty(dX.shape[0])
+        status = np.zeros(max(1, self.ne), dtype=np.int32)
+        stats = FeastHipStats()
+        self._chk(self.lib.feasthip_poly_resinv_apply_dev(self.h, int(m), None if sg is None else _np_ptr(sg), C.c_void_p(dX.data_ptr()),
+                                                          C.c_void_p(dQ.data_ptr()), _np_ptr(status), C.byref(stats)))
+        self.last_stats = stats.asdict()
+        return dQ, status, self.last_stats
+
+    def poly_project_reduced(self, dQ, r):
+        """[Q^H A_k Q for k = 0 .. d], r x r on the host (feasthip_poly_project_reduced_dev)."""
+        self._sync_stream()
+        d = getattr(self, "poly_degree", 1)
+        Ahat = np.zeros((d + 1, r, r), dtype=np.complex128)       # [k] column-major r x r == [k].T in C order
+        self._chk(self.lib.feasthip_poly_project_reduced_dev(self.h, int(r), C.c_void_p(dQ.data_ptr()), _np_ptr(Ahat)))
+        return [np.asfortranarray(Ahat[k].T) for k in range(d + 1)]
+
+    def poly_ritz_eval(self, dQ, r, Y, theta=None):
+        """X = Q Y with unit columns (Y: r x ncand) -> (dX, backward_error[ncand] of the pairs (theta_i, x_i), or None without
+        theta); feasthip_poly_ritz_eval_dev."""
+        self._sync_stream()
+        Yf = np.asfortranarray(Y, dtype=np.complex128)
+        ncand = Yf.shape[1]
+        if Yf.shape[0] != int(r):
+            raise ValueError("poly_ritz_eval: Y must have r rows")
+        dX = self.empty(ncand)
+        th = bwd = None
+        if theta is not None:
+            th = np.ascontiguousarray(theta, dtype=np.complex128)
+            if th.shape != (ncand,):
+                raise ValueError("poly_ritz_eval needs one value per candidate")
+            bwd = np.zeros(ncand, dtype=np.float64)
+        self._chk(self.lib.feasthip_poly_ritz_eval_dev(self.h, int(r), C.c_void_p(dQ.data_ptr()), int(ncand), _np_ptr(Yf),
+                                                       None if th is None else _np_ptr(th), C.c_void_p(dX.data_ptr()),
+                                                       None if bwd is None else _np_ptr(bwd)))
+        return dX, bwd
+
+    def poly_orthonormalize(self, dQ, m, rank_tol, unit_columns=True):
+        """Rank-revealing orthonormalisation of the N x m block of a polynomial handle, in place -> rank
+        (feasthip_poly_orthonormalize_dev; set_ortho_method and last_ortho apply as for a pencil)."""
+        self._sync_stream()
+        rank = C.c_int(0)
+        self._chk(self.lib.feasthip_poly_orthonormalize_dev(self.h, int(m), C.c_void_p(dQ.data_ptr()), int(bool(unit_columns)),
+                                                            float(rank_tol), C.byref(rank)))
+        return rank.value
+
     def free_factors(self):
         """Drop the cached LU / band factors of the direct solvers (feasthip_release_factors)."""
         self._chk(self.lib.feasthip_release_factors(self.h))

@@ -1016,6 +1016,25 @@ def feast_hip_general(engine, A, B, Emid, r, M0, fpm, *, solver="direct", solver
 POLY_RESIDUALS = ("pencil", "reference")
 
 
+def _poly_setup(engine, coeffs, Emid, r, fpm, contour, union_csr):
+    """What both polynomial drivers do before their loop: the polynomial (dense, or sparse from ``union_csr``) becomes the engine's
+    problem with the direct solver, cached fp64 factors, no real projection and the full contour -> the plan fields of
+    ``stats["polynomial"]`` for sparse coefficients, else None."""
+    Zne, Wne = feast_gcontour(Emid, r, fpm) if contour is None else contour
+    if union_csr is None:
+        engine.set_polynomial(coeffs)
+    else:
+        engine.set_polynomial_csr(*union_csr)
+    engine.set_solver("direct", cache_factors=True, factor_precision=64)
+    engine.set_real_projection(False)
+    engine.set_contour(Zne, Wne, 1.0)
+    if union_csr is None:
+        return None
+    factor_bytes, transient_bytes = engine.direct_plan_bytes(1)
+    return {"plan": "multifrontal", "plan_factor_bytes": factor_bytes, "plan_transient_bytes": transient_bytes,
+            "plan_flops": engine.direct_plan_flops(), "plan_nnz": int(len(union_csr[1]))}
+
+
 def feast_hip_polynomial(engine, coeffs, Emid, r, M0, fpm, *, Q0=None, seed=20260515, contour=None, residual="pencil",
                          eps_floor=0.0, union_csr=None):
     """P(lambda) x = 0 inside a circle: feast_hip_general's loop on the first companion linearisation with M0 d columns
@@ -1036,19 +1055,7 @@ def feast_hip_polynomial(engine, coeffs, Emid, r, M0, fpm, *, Q0=None, seed=2026
     info = _check_circle_input(N, M0, r)
     if info:
         return _empty_result(N, info, complex_lambda=True)
-    Zne, Wne = feast_gcontour(Emid, r, fpm) if contour is None else contour
-    plan = None
-    if union_csr is None:
-        engine.set_polynomial(coeffs)
-    else:
-        engine.set_polynomial_csr(*union_csr)
-    engine.set_solver("direct", cache_factors=True, factor_precision=64)
-    engine.set_real_projection(False)
-    engine.set_contour(Zne, Wne, 1.0)
-    if union_csr is not None:
-        factor_bytes, transient_bytes = engine.direct_plan_bytes(1)
-        plan = {"plan": "multifrontal", "plan_factor_bytes": factor_bytes, "plan_transient_bytes": transient_bytes,
-                "plan_flops": engine.direct_plan_flops(), "plan_nnz": int(len(union_csr[1]))}
+    plan = _poly_setup(engine, coeffs, Emid, r, fpm, contour, union_csr)
     Q_host = seeded_subspace(d * N, cols, seed) if Q0 is None else np.asarray(Q0, dtype=np.complex128)
     if Q_host.shape != (d * N, cols):
         raise ValueError(f"Q0 must be the linearised start block of shape ({d * N}, {cols})")
@@ -1059,7 +1066,7 @@ def feast_hip_polynomial(engine, coeffs, Emid, r, M0, fpm, *, Q0=None, seed=2026
     loop = 0
     eps_hist = []
     stats = {"krylov_iterations": 0, "factorizations": 0, "solve_seconds": 0.0,
-             "polynomial": {"degree": d, "columns": cols, "residual": residual, "backward_error": np.zeros(0), "eps_history": eps_hist}}
+             "polynomial": {"degree": d, "method": "linearised", "columns": cols, "residual": residual, "backward_error": np.zeros(0), "eps_history": eps_hist}}
     if plan is not None:
         stats["polynomial"].update(plan)
     while True:
@@ -1091,6 +1098,122 @@ def feast_hip_polynomial(engine, coeffs, Emid, r, M0, fpm, *, Q0=None, seed=2026
             return FeastResult(lam[:M][order].copy(), X[:N, :M][:, order].copy(), M, res[order].copy(), 0, epsout, loop, stats)
         loop += 1
         dQ = dX
+
+
+POLY_METHODS = ("linearised", "projected")
+# Set-aside rule of the projected method: a selected pair inside the circle whose backward error exceeds BOTH the absolute
+# threshold and `factor` times the smallest backward error inside is kept in the subspace but left out of M and epsout (the
+# shape of feasthip_policy_set_aside's rule).  (absolute, factor)
+POLY_SET_ASIDE = (1e-3, 100.0)
+
+
+def _poly_companion(Ahat):
+    """First companion pencil (A_lin, B_lin) of the small polynomial sum_k lambda^k Ahat[k], r x r coefficients."""
+    d, r = len(Ahat) - 1, Ahat[0].shape[0]
+    Al = np.zeros((d * r, d * r), dtype=np.complex128)
+    Bl = np.eye(d * r, dtype=np.complex128)
+    for i in range(d - 1):
+        Al[i * r:(i + 1) * r, (i + 1) * r:(i + 2) * r] = np.eye(r)
+    for j in range(d):
+        Al[(d - 1) * r:, j * r:(j + 1) * r] = -Ahat[j]
+    Bl[(d - 1) * r:, (d - 1) * r:] = Ahat[d]
+    return Al, Bl
+
+
+def poly_select(theta, be, center, radius, keep):
+    """Selection and set-aside of the projected method.  The reduced polynomial has d r Ritz values for r columns, and the
+    surplus ones fall inside a circle that the spectrum surrounds; "nearest to the centre" picks them and stagnates.  So:
+    the candidates inside the circle in ascending backward error, then those outside in ascending distance, `keep` in all;
+    among the selected inside ones a pair is set aside under POLY_SET_ASIDE.
+    -> (selected indices, mask over them: inside and not set aside, number set aside)"""
+    dist = np.abs(np.where(np.isfinite(theta), theta, np.inf) - center)
+    inside = dist <= radius
+    ins = np.flatnonzero(inside)
+    ins = ins[np.argsort(be[ins], kind="stable")]
+    out = np.flatnonzero(~inside)
+    out = out[np.argsort(dist[out], kind="stable")]
+    sel = np.concatenate([ins, out])[:keep]
+    good = inside[sel].copy()
+    aside = 0
+    if good.any():
+        best = be[sel][good].min()
+        bad = good & (be[sel] > POLY_SET_ASIDE[0]) & (be[sel] > POLY_SET_ASIDE[1] * best)
+        aside = int(bad.sum())
+        good &= ~bad
+    return sel, good, aside
+
+
+def feast_hip_polynomial_projected(engine, coeffs, Emid, r, M0, fpm, *, Q0=None, seed=20260515, contour=None, eps_floor=0.0,
+                                   union_csr=None, ortho="mgs"):
+    """P(lambda) x = 0 inside a circle on an N-row subspace of M0 columns: polynomial FEAST with a residual-inverse contour
+    step (Gavin, Miedlar, Polizzi).  Per loop: the contour step on the N x m block (loop 0 the plain sweep, which factors
+    P(z_e) once per node and fills the cache; afterwards R_j = P(sigma_j) x_j, Y_e = P(z_e)^-1 R, Q_j = sum_e w_e (x_j - Y_e,j)
+    / (z_e - sigma_j) on the cached factors), unit columns and the rank-revealing orthonormalisation of ``ortho``, the
+    projected polynomial Q^H A_k Q, its dr x dr companion pencil solved on the host, the backward error of ALL dr candidates,
+    poly_select.  Stop test: the largest backward error among the kept pairs inside the circle.  At the loop limit the last
+    iterates are returned with info = Feast_ERROR_NO_CONVERGENCE.  ``union_csr`` and the exceptions: as feast_hip_polynomial."""
+    d = len(coeffs) - 1
+    N = coeffs[0].shape[0]
+    feastdefault(fpm)
+    info = _check_circle_input(N, M0, r)
+    if info:
+        return _empty_result(N, info, complex_lambda=True)
+    plan = _poly_setup(engine, coeffs, Emid, r, fpm, contour, union_csr)
+    X_host = seeded_subspace(N, M0, seed) if Q0 is None else np.asarray(Q0, dtype=np.complex128)
+    if X_host.shape != (N, M0):
+        raise ValueError(f"Q0 must be the start block of shape ({N}, {M0})")
+    dX = engine.upload(X_host)
+    eps_tol = max(feast_tolerance(fpm), float(eps_floor))
+    maxloop = int(fpm[4])
+    center = complex(Emid)
+    loop, m, sigma = 0, M0, None
+    poly = {"degree": d, "method": "projected", "columns": M0, "backward_error": np.zeros(0), "eps_history": [], "rank": [],
+            "candidates": [], "set_aside": []}
+    stats = {"krylov_iterations": 0, "factorizations": 0, "solve_seconds": 0.0, "polynomial": poly}
+    if plan is not None:
+        poly.update(plan)
+    no_conv = FeastError.Feast_ERROR_NO_CONVERGENCE
+    with _ortho_scope(engine, ortho, stats):
+        while True:
+            dQ, status, st = engine.poly_resinv_apply(dX, m, sigma)
+            stats["factorizations"] += st.get("factorizations", 0)
+            stats["solve_seconds"] += st.get("seconds_total", 0.0)
+            if int(np.max(status)):
+                return _empty_result(N, FeastError.Feast_ERROR_LAPACK, loop, complex_lambda=True, stats=stats)
+            rank_q = engine.poly_orthonormalize(dQ, m, SQRT_EPS, unit_columns=True)
+            _note_ortho(engine, stats)
+            if rank_q == 0:
+                return _empty_result(N, no_conv, loop, complex_lambda=True, stats=stats)
+            Ahat = engine.poly_project_reduced(dQ, rank_q)
+            try:
+                with small_lapack():
+                    theta, V = sla.eig(*_poly_companion(Ahat))
+            except Exception:
+                return _empty_result(N, FeastError.Feast_ERROR_LAPACK, loop, complex_lambda=True, stats=stats)
+            ncand = d * rank_q
+            dXc, be = engine.poly_ritz_eval(dQ, rank_q, np.asfortranarray(V[:rank_q, :]), theta)
+            keep = min(M0, ncand)
+            sel, good, aside = poly_select(theta, be, center, r, keep)
+            M = int(good.sum())
+            epsout = float(be[sel][good].max()) if M else math.inf
+            poly["eps_history"].append(epsout)
+            poly["rank"].append(int(rank_q))
+            poly["candidates"].append(int(ncand))
+            poly["set_aside"].append(aside)
+            done = M > 0 and epsout <= eps_tol
+            if done or loop >= maxloop:
+                if M == 0:
+                    return _empty_result(N, no_conv, loop, complex_lambda=True, stats=stats)
+                idx = sel[good]
+                idx = idx[np.argsort(np.abs(theta[idx]) ** 2, kind="stable")]                 # feast_sort_general!
+                Xall = engine.download(dXc, ncand)
+                poly["backward_error"] = be[idx].copy()
+                return FeastResult(theta[idx].copy(), Xall[:, idx].copy(), M, be[idx].copy(), 0 if done else int(no_conv), epsout,
+                                   loop, stats)
+            dX = dXc[engine.torch.as_tensor(sel, device=dXc.device)].contiguous()
+            sigma = np.where(np.isfinite(theta[sel]), theta[sel], center)
+            m = keep
+            loop += 1
 
 
 TWO_SIDED_SOLVERS = ("direct", "lu")

@@ -553,6 +553,32 @@ int  feasthip_poly_project_dev(feasthip_handle h, int64_t r, const void* dQ, voi
 int  feasthip_poly_ritz_residual_dev(feasthip_handle h, int64_t r, const void* dQ, const void* V_host, const void* lambda, int64_t M,
                                      int normalize, int use_B, void* dX, double* res, double* backward_error);
 
+/* ---- polynomial eigenproblems, projected method: the subspace is N x m, the small r x r polynomial is linearised on the host --
+ * (polynomial FEAST with a residual-inverse contour step, Gavin, Miedlar, Polizzi; no reference counterpart).  Every call works
+ * on dense and sparse polynomial handles, refuses what the calls above refuse, and takes any m >= 1 in 64-column panels.
+ * feasthip_poly_eval_cols_dev: R[:, j] = P(lambda_j) X[:, j], N x m; lambda: m complex values on the host.
+ * feasthip_poly_resinv_apply_dev: the contour step.  sigma == NULL: Q = sum_e weight_scale w_e P(z_e)^-1 X (plain sweep).
+ *   Otherwise, with sigma: m complex shifts on the host,
+ *     R[:, j] = P(sigma_j) x_j,  Y_e = P(z_e)^-1 R,  Q[:, j] = sum_e weight_scale w_e (x_j - Y_e[:, j]) / (z_e - sigma_j).
+ *   Factors come from the per-node cache (stats.factorizations as in feasthip_poly_contour_apply_dev); node_status[e]: 0 or 8.
+ *   A shift that is not finite or that coincides with a contour node to working precision: FEASTHIP_ERROR_FPM.
+ * feasthip_poly_project_reduced_dev: Ahat_k = Q^H A_k Q, k = 0 .. degree, for an N x r block Q; Ahat_host: degree + 1 r x r
+ *   column-major matrices one behind the other.
+ * feasthip_poly_ritz_eval_dev: X = Q Y (Y: r x ncand column-major, host) with every column scaled to unit length, and
+ *     backward_error[i] = ||P(theta_i) x_i||_2 / sum_k |theta_i|^k ||A_k||_F      (||A_k||_F from ingest)
+ *   for i < ncand; +inf for a theta_i that is not finite and for a column of zero length.  backward_error may be NULL (then
+ *   theta may be too).  X must not alias Q.
+ * feasthip_poly_orthonormalize_dev: feasthip_orthonormalize_dev (method of feasthip_set_ortho_method, report through
+ *   feasthip_last_ortho) for the N x m block of a polynomial handle, which feasthip_orthonormalize_dev itself refuses like every
+ *   pencil entry point; unit_columns != 0 scales every column to unit length first.                                    */
+int  feasthip_poly_eval_cols_dev(feasthip_handle h, int64_t m, const void* lambda, const void* dX, void* dR);
+int  feasthip_poly_resinv_apply_dev(feasthip_handle h, int64_t m, const void* sigma /* host, or NULL */, const void* dX, void* dQ,
+                                    int* node_status, feasthip_stats* stats);
+int  feasthip_poly_project_reduced_dev(feasthip_handle h, int64_t r, const void* dQ, void* Ahat_host);
+int  feasthip_poly_ritz_eval_dev(feasthip_handle h, int64_t r, const void* dQ, int64_t ncand, const void* Y_host, const void* theta,
+                                 void* dX, double* backward_error);
+int  feasthip_poly_orthonormalize_dev(feasthip_handle h, int64_t m, void* dQ, int unit_columns, double rank_tol, int* rank);
+
 /* ---- measurement support ---------------------------------------------------------- */
 /* Average device time (ms, HIP events on the handle's stream) and launch count of the
  * named kernel class since the last reset; classes: "spmm", "bicg_update", "dot_finalize",

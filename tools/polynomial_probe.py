@@ -19,6 +19,12 @@ imaginary part up to the widest gap among the 8th .. 16th.  Comparator: feast_ge
 through the sparse direct solver from the same start block (how the reference's feast_gcsrpev! does it); --companion-only
 --package-root P runs that call alone on another checkout.  Also: k_spmm_fan's achieved GB/s on its algorithmic bytes in the
 residual step, and that step's products as single-coefficient feasthip_matmul_dev calls on CSR handles holding A_k.
+
+--method projected (either workload): feast_polynomial(..., method="projected") with --columns N-row columns (default 32 dense,
+24 sparse) and a loop limit of 20, alternating with the linearised call as above (the comparator then is the linearised call,
+not the companion pencil): ms per solve, loops, M, the per-loop history, rank and set-aside counts; then the achieved GB/s of
+k_poly_resinv_acc (ne + 1 panels read, one written) and, sparse workload, of k_spmm_horner (nnz (4 + (d + 1) sizeof(VT)) plus
+one panel written) on one 64-column panel, against the measured copy ceiling bench.py quotes.
 """
 import argparse
 import json
@@ -62,7 +68,7 @@ def companion(coeffs):
     return A, np.asfortranarray(B)
 
 
-CLASSES = ("poly_form", "poly_rhs", "poly_expand", "poly_residual", "lu_form", "lu_panel", "lu_laswp", "lu_trsm", "lu_gemm_in", "lu_gemm",
+CLASSES = ("poly_form", "poly_rhs", "poly_expand", "poly_residual", "poly_horner", "poly_resinv", "ortho", "lu_form", "lu_panel", "lu_laswp", "lu_trsm", "lu_gemm_in", "lu_gemm",
            "lu_invert", "lu_solve", "dense_op", "gram", "ritz")
 
 
@@ -80,8 +86,15 @@ def main():
     ap.add_argument("--grid", type=int, nargs=3, default=(50, 40, 25), help="sparse workload: nx ny nz")
     ap.add_argument("--alpha", type=float, default=0.1)
     ap.add_argument("--beta", type=float, default=0.05)
+    ap.add_argument("--method", choices=("linearised", "projected"), default="linearised")
+    ap.add_argument("--columns", type=int, default=None, help="--method projected: N-row columns (default 32 dense, 24 sparse)")
+    ap.add_argument("--set-aside", type=float, nargs=2, default=None, metavar=("ABS", "FACTOR"),
+                    help="experiment: run the projected method with these set-aside thresholds instead of POLY_SET_ASIDE")
     a = ap.parse_args()
     sys.path[:0] = [a.package_root]
+    if a.set_aside is not None:
+        import feastkit_jl_amd.hip_backend as hb
+        hb.POLY_SET_ASIDE = (float(a.set_aside[0]), float(a.set_aside[1]))
     if a.workload == "sparse":
         return main_sparse(a)
     import numpy as np
@@ -101,14 +114,19 @@ def main():
     def run(name):
         eng.synchronize()
         t0 = time.perf_counter()
-        if name == "polynomial":
+        if name == "projected":
+            f = fpm()
+            f[4] = 20
+            r = fk.feast_polynomial(coeffs, center, radius, M0=columns, fpm=f, engine=eng, method="projected")
+        elif name == "polynomial":
             r = fk.feast_polynomial(coeffs, center, radius, M0=a.M0, fpm=fpm(), engine=eng, Q0=Q0, residual="reference")
         else:
             r = fk.feast_general(Alin, Blin, center, radius, M0=a.M0 * d, fpm=fpm(), engine=eng, Q0=Q0)
         eng.synchronize()
         return r, 1e3 * (time.perf_counter() - t0)
 
-    names = ("companion",) if a.companion_only else ("polynomial", "companion")
+    columns = a.columns or 32
+    names = ("companion",) if a.companion_only else (("projected", "polynomial") if a.method == "projected" else ("polynomial", "companion"))
     for name in names:
         run(name)                                   # warm-up: kernels loaded, workspaces and factor slots made
     ms = {n: [] for n in names}
@@ -130,8 +148,11 @@ def main():
                "ms_all": ms[name], "loops": r.loop, "M": r.M, "expected_M": len(inside), "info": r.info, "epsout": r.epsout,
                "factorizations": r.stats.get("factorizations"), "eigenvalue_error": lam_err,
                "factor_bytes": a.nodes * 16 * (N if name == "polynomial" else d * N) ** 2}
-        if name == "polynomial":
+        if name in ("polynomial", "projected") and len(r.stats["polynomial"]["backward_error"]):
             row["backward_error_max"] = float(np.max(r.stats["polynomial"]["backward_error"]))
+        if name == "projected":
+            row.update(projected_fields(r, columns))
+            row["factor_bytes"] = a.nodes * 16 * N ** 2
         print(json.dumps(row), flush=True)
     # device time per profile class: one further solve of each with every launch timed
     for name in names:
@@ -156,10 +177,71 @@ def main():
             gbs = traffic / (prof["lu_form"]["ms"] / prof["lu_form"]["launches"] * 1e-3) / 1e9
             row["lu_form"] = {"bytes_per_launch": traffic, "GB_per_s": round(gbs, 1), "fraction_of_copy_ceiling_4800": round(gbs / 4800.0, 4)}
         print(json.dumps(row), flush=True)
+    if a.method == "projected" and not a.companion_only:
+        projected_kernels(eng, fk, coeffs, center, radius, a.nodes, sparse=False)
     eng.close()
 
 
-SPARSE_CLASSES = ("poly_spmm", "poly_mf_assemble", "poly_rhs", "poly_expand", "poly_residual", "mf_assemble", "mf_lu", "mf_solve", "spmm",
+def projected_fields(r, columns):
+    poly = r.stats["polynomial"]
+    import feastkit_jl_amd.hip_backend as hb
+    return {"set_aside_thresholds": list(hb.POLY_SET_ASIDE), "columns": columns, "eps_history": [float(e) for e in poly["eps_history"]], "rank": poly["rank"], "candidates": poly["candidates"],
+            "set_aside": poly["set_aside"]}
+
+
+def projected_kernels(eng, fk, coeffs, center, radius, nodes, sparse):
+    """k_poly_resinv_acc and (sparse) k_spmm_horner on one 64-column panel: device ms per launch and GB/s on the algorithmic bytes"""
+    import numpy as np
+    d, N, m = len(coeffs) - 1, coeffs[0].shape[0], 64
+    nnz = None
+    if sparse:
+        from feastkit_jl_amd.ingest import polynomial_union_csr
+        union = polynomial_union_csr(coeffs)
+        nnz = len(union[1])
+        cplx = np.iscomplexobj(union[2][0])
+        eng.set_polynomial_csr(*union)
+    else:
+        eng.set_polynomial(coeffs)
+    eng.set_solver("direct", cache_factors=True, factor_precision=64)
+    eng.set_real_projection(False)
+    f = fk.feastinit()
+    fk.feastdefault(f)
+    f[8] = nodes
+    Zne, Wne = fk.feast_gcontour(center, radius, f)
+    eng.set_contour(Zne, Wne, 1.0)
+    rng = np.random.default_rng(7)
+    dX = eng.upload(np.asfortranarray(rng.standard_normal((N, m)) + 1j * rng.standard_normal((N, m))))
+    sigma = center + 0.5 * radius * np.exp(2j * np.pi * (np.arange(m) + 0.25) / m)
+    eng.poly_resinv_apply(dX, m, sigma)                          # warm-up: factors, workspaces
+    eng.poly_eval_cols(dX, sigma, m)
+    eng.profile_enable(True)
+    eng.profile_set_period(1)
+    reps = 10
+    eng.profile_reset()
+    for _ in range(reps):
+        eng.poly_resinv_apply(dX, m, sigma)
+    ms, n = eng.profile_get("poly_resinv")
+    panel = 16.0 * N * m
+    traffic = panel * (nodes + 2)
+    row = {"what": "k_poly_resinv_acc", "N": N, "m": m, "nodes": nodes, "ms_per_launch": ms / n, "bytes_per_launch": traffic,
+           "GB_per_s": traffic / (ms / n * 1e-3) / 1e9}
+    row["fraction_of_copy_ceiling_4800"] = row["GB_per_s"] / 4800.0
+    print(json.dumps(row), flush=True)
+    if sparse:
+        eng.profile_reset()
+        for _ in range(reps):
+            eng.poly_eval_cols(dX, sigma, m)
+        ms, n = eng.profile_get("poly_horner")
+        traffic = nnz * (4.0 + (d + 1) * (16 if cplx else 8)) + panel
+        row = {"what": "k_spmm_horner", "N": N, "m": m, "nnz": nnz, "degree": d, "complex_values": bool(cplx), "ms_per_launch": ms / n,
+               "bytes_per_launch": traffic, "GB_per_s": traffic / (ms / n * 1e-3) / 1e9, "gathered_bytes_per_launch": nnz * 16.0 * m}
+        row["fraction_of_copy_ceiling_4800"] = row["GB_per_s"] / 4800.0
+        print(json.dumps(row), flush=True)
+    eng.profile_enable(False)
+    eng.free_factors()
+
+
+SPARSE_CLASSES = ("poly_spmm", "poly_mf_assemble", "poly_rhs", "poly_expand", "poly_residual", "poly_horner", "poly_resinv", "ortho", "mf_assemble", "mf_lu", "mf_solve", "spmm",
                   "gram", "ritz")
 
 
@@ -222,7 +304,9 @@ def main_sparse(a):
         eng.synchronize()
         t0 = time.perf_counter()
         try:
-            if name == "polynomial":
+            if name == "projected":
+                r = fk.feast_polynomial(coeffs, center, radius, M0=columns, fpm=fpm(), engine=eng, solver="sparse_direct", method="projected")
+            elif name == "polynomial":
                 r = fk.feast_polynomial(coeffs, center, radius, M0=M0, fpm=fpm(), engine=eng, Q0=Q0, solver="sparse_direct")
             else:
                 r = fk.feast_general(Alin, Blin, center, radius, M0=M0 * d, fpm=fpm(), engine=eng, Q0=Q0, solver="sparse_direct")
@@ -231,7 +315,8 @@ def main_sparse(a):
         eng.synchronize()
         return r, 1e3 * (time.perf_counter() - t0)
 
-    names = ("companion",) if a.companion_only else ("polynomial", "companion")
+    columns = a.columns or 24
+    names = ("companion",) if a.companion_only else (("projected", "polynomial") if a.method == "projected" else ("polynomial", "companion"))
     for name in names:
         run(name)
     ms = {n: [] for n in names}
@@ -249,7 +334,9 @@ def main_sparse(a):
         else:
             row.update(loops=r.loop, M=r.M, expected_M=len(inside), info=r.info, epsout=r.epsout, factorizations=r.stats.get("factorizations"),
                        eigenvalue_error=match_error(r.lambda_, inside), solver_substitution=r.stats.get("solver_substitution"))
-            if name == "polynomial":
+            if name == "projected":
+                row.update(projected_fields(r, columns))
+            if name in ("polynomial", "projected") and len(r.stats["polynomial"]["backward_error"]):
                 poly = r.stats["polynomial"]
                 row.update(backward_error_max=float(np.max(poly["backward_error"])), plan=poly.get("plan"), fell_back=poly.get("fell_back"),
                            factor_bytes_per_node=poly.get("plan_factor_bytes"), flops_per_node=poly.get("plan_flops"), nnz=poly.get("plan_nnz"))
@@ -266,7 +353,9 @@ def main_sparse(a):
                 prof[cls] = {"ms": round(total, 3), "launches": n}
         eng.profile_enable(False)
         print(json.dumps({"workload": "sparse", "method": name, "profiled_solve_ms": t, "classes": prof}), flush=True)
-    if not a.companion_only:
+    if a.method == "projected" and not a.companion_only:
+        projected_kernels(eng, fk, coeffs, center, radius, nodes, sparse=True)
+    elif not a.companion_only:
         fan_against_single_products(eng, fk, coeffs, M0 * d)
     eng.close()
 
