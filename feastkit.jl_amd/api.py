@@ -593,11 +593,13 @@ POLY_DENSE_LIMIT = 12288     # sparse coefficients are expanded up to this size
 # POLY_SET_ASIDE (hip_backend): the two thresholds of the projected method's set-aside rule, (absolute, factor)
 
 
-POLY_SOLVERS = ("direct", "sparse_direct")
+POLY_SOLVERS = ("direct", "sparse_direct")               # the direct solvers
+POLY_KRYLOV_SOLVERS = ("bicgstab", "cocg", "gmres")      # sparse coefficients under method="projected" only
 
 
 def feast_polynomial(coeffs, center, radius, *, M0=10, fpm=None, engine=None, device=0, Q0=None, contour=None, seed=None,
-                     keep_factors=False, residual="pencil", solver="direct", method="linearised", ortho="mgs"):
+                     keep_factors=False, residual="pencil", solver="direct", method="linearised", ortho="mgs", solver_tol=0.0,
+                     solver_maxiter=500, solver_restart=30):
     """feast_polynomial(coeffs, center, radius; M0, fpm): src/interfaces/feast_interfaces.jl:448-462, feast_pep! /
     feast_gepev! / feast_hepev! / feast_sypev! (src/dense/feast_dense.jl:715-772, 946-979).  Eigenpairs of
     P(lambda) x = 0, P(lambda) = coeffs[0] + lambda coeffs[1] + ... + lambda^d coeffs[d], with lambda inside the circle.
@@ -618,6 +620,23 @@ def feast_polynomial(coeffs, center, radius, *, M0=10, fpm=None, engine=None, de
                           (``stats["polynomial"]["fell_back"]`` = True, plan = "dense", ``stats["solver_substitution"]``),
                           else raises FeastHipError naming the cause and the sizes -- as it does when the factors do not fit
                           the device.  There is no band LU for polynomials.
+      "bicgstab" | "cocg" | "gmres"   no factors at all: every coefficient a scipy.sparse matrix, ``method="projected"``.  The
+                          solves P(z_e) Y_e = R of the contour step run on the batched Krylov drivers of feast / feast_general
+                          (the counterpart of the reference's difeast_scsrpev! / zifeast_hcsrpev! / zifeast_gcsrpev! family),
+                          with the operator P(z_e) applied per nonzero on the union pattern, from a zero start, without a
+                          preconditioner.  ``solver_tol`` (0 = 10^-fpm[3], the package's convention), ``solver_maxiter`` and
+                          ``solver_restart`` (GMRES) as in feast.  The stop test is relative only, ||r|| <= solver_tol ||rhs||
+                          (atol = 0): the right-hand side of a residual-inverse solve is P(sigma_j) x_j, which shrinks with
+                          the outer residual, so an absolute floor would stop the inner solves of the late loops at once.
+                          Inexact solves are enough: at solver_tol = 1e-4 the loop history stays within a few percent of the
+                          exact-solve one.  A node whose column stops at ``solver_maxiter`` is a normal outcome (its iterate
+                          is used; ``stats["polynomial"]["krylov"][loop]["capped_nodes"]`` counts them).  "cocg" needs every
+                          coefficient exactly symmetric (A_k == A_k^T; complex symmetric qualifies, Hermitian does not), else
+                          ValueError naming "bicgstab".  ``method="linearised"`` (one right-hand side per node) and dense
+                          coefficients raise ValueError; a Krylov call never falls back to the dense expansion.
+                          ``stats["krylov_iterations"]`` sums the slowest column of every node and loop,
+                          ``stats["polynomial"]["krylov"]`` holds per loop {iterations (worst column), node_iterations,
+                          capped_nodes}, ``stats["factorizations"]`` stays 0, plan = "krylov", fell_back = False.
     ``residual``: what ``res`` / ``epsout`` and the stop test measure on the unit linearised Ritz vector x of the companion
     pencil (A_lin, B_lin):
       "pencil" (default)  ||A_lin x - lambda B_lin x|| / max(|lambda|, 1)
@@ -673,10 +692,23 @@ def feast_polynomial(coeffs, center, radius, *, M0=10, fpm=None, engine=None, de
         raise ValueError("radius must be positive")
     if residual not in POLY_RESIDUALS:
         raise ValueError(f"residual must be one of {POLY_RESIDUALS}, not {residual!r}")
-    if solver not in POLY_SOLVERS:
-        raise ValueError(f"solver must be one of {POLY_SOLVERS}, not {solver!r}")
+    if solver not in POLY_SOLVERS + POLY_KRYLOV_SOLVERS:
+        raise ValueError(f"solver must be one of {POLY_SOLVERS + POLY_KRYLOV_SOLVERS}, not {solver!r}")
     N = shape[0]
-    sparse_direct = solver == "sparse_direct"
+    krylov = solver in POLY_KRYLOV_SOLVERS
+    if krylov:
+        if not all(sp.issparse(c) for c in mats):
+            raise ValueError(f'solver="{solver}" needs every coefficient as a scipy.sparse matrix; dense coefficients take '
+                             'solver="direct"')
+        if method != "projected":
+            raise ValueError(f'solver="{solver}" solves one right-hand-side block shared by the contour nodes: it needs '
+                             'method="projected" (the linearised sweep has one right-hand side per node)')
+        if solver == "cocg" and any(abs(c - c.T).max() != 0 for c in mats):
+            raise ValueError('solver="cocg" needs every coefficient exactly symmetric (A_k == A_k^T; Hermitian does not '
+                             'qualify); use solver="bicgstab"')
+        if solver_tol < 0 or int(solver_maxiter) < 1 or int(solver_restart) < 0:
+            raise ValueError("solver_tol must be >= 0, solver_maxiter >= 1, solver_restart >= 0")
+    sparse_direct = solver == "sparse_direct" or krylov
     if sparse_direct and not all(sp.issparse(c) for c in mats):
         raise ValueError('solver="sparse_direct" needs every coefficient as a scipy.sparse matrix; dense coefficients take '
                          'solver="direct"')
@@ -705,6 +737,8 @@ def feast_polynomial(coeffs, center, radius, *, M0=10, fpm=None, engine=None, de
         driver, common["residual"] = feast_hip_polynomial, residual
     try:
         res = None
+        if krylov:
+            common["krylov"] = (solver, float(solver_tol), int(solver_maxiter), int(solver_restart))
         if sparse_direct:
             union = polynomial_union_csr(mats)
             try:
@@ -714,7 +748,7 @@ def feast_polynomial(coeffs, center, radius, *, M0=10, fpm=None, engine=None, de
             except FeastHipError as err:
                 # 9: no multifrontal plan for the pattern, 8: a rejected pivot.  (6, factors that do not fit, is not a
                 # reason to try N^2 dense ones.)
-                if err.code not in (8, 9) or N > POLY_DENSE_LIMIT:
+                if krylov or err.code not in (8, 9) or N > POLY_DENSE_LIMIT:
                     raise
                 eng.free_factors()
                 substituted = {"requested": "sparse_direct", "used": "dense LU of the expanded coefficients", "reason": str(err)}

@@ -2,6 +2,7 @@
 // of the gfx950 kernels; no arithmetic on the host except M0 x M0 bookkeeping.
 #include "fh_common.hpp"
 #include "fh_kernels.hpp"
+#include "fh_krylov.hpp"
 #include "fh_dense.hpp"
 #include "fh_banded.hpp"
 #include "fh_eig.hpp"
@@ -555,9 +556,15 @@ extern "C" int feasthip_set_solver(feasthip_handle h, int kind, double rtol, dou
         h->last_error = "feasthip_set_solver: invalid option";
         return FEASTHIP_ERROR_FPM;
     }
-    if (h->kind == 3 && (kind != FEASTHIP_SOLVER_LU || factor_precision != 64)) {
-        h->last_error = "feasthip_set_solver: a polynomial handle needs FEASTHIP_SOLVER_LU with factor_precision = 64";
-        return FEASTHIP_ERROR_FPM;
+    if (h->kind == 3) {
+        // dense coefficients: the LU of P(z_e) only.  CSR coefficients: that (the multifrontal LU), or a Krylov solver on the
+        // operator P(z_e) (fh_poly.hip: k_spmm_poly); complex128 throughout
+        const bool krylov = kind == FEASTHIP_SOLVER_BICGSTAB || kind == FEASTHIP_SOLVER_COCG || kind == FEASTHIP_SOLVER_GMRES;
+        if (factor_precision != 64 || !(kind == FEASTHIP_SOLVER_LU || (krylov && h->poly.sparse))) {
+            h->last_error = h->poly.sparse ? "feasthip_set_solver: a CSR polynomial handle needs FEASTHIP_SOLVER_LU, _BICGSTAB, _COCG or _GMRES with factor_precision = 64"
+                                           : "feasthip_set_solver: a dense polynomial handle needs FEASTHIP_SOLVER_LU with factor_precision = 64";
+            return FEASTHIP_ERROR_FPM;
+        }
     }
     // SHIFTED_COCG is COCG with the shifted sweep where fh_contour_apply_panel finds it eligible: every other path sees COCG
     h->shifted = kind == FEASTHIP_SOLVER_SHIFTED_COCG ? 1 : 0;
@@ -639,6 +646,21 @@ static int fh_apply_operator(feasthip_ctx* h, int ld, const fh_op_call& c) {
         if (lds_kernel) return (8 / (ld / 16)) * fh_spmm_lds_slots(a.nblk_rows, ld);
         return fh_spmm_partials(a.N, ld);     // partial-sum rows per node
     }
+    if (h->kind == 3) {
+        // sparse polynomial handle: S_e = P(z_e), z_e = coefB[node][0] of the shifted-operator coefficients (coefA is not read);
+        // complex128 panels, the plain product and dot modes 1 .. 4
+        if (!h->poly.sparse || h->adjoint || c.prec != 64 || c.colscale || c.dot_mode == 6 || !c.coefB) {
+            h->last_error = "internal: the polynomial operator takes a CSR polynomial handle, complex128 panels and dot modes 0 .. 4";
+            return -1;
+        }
+        fh_polyop_call a;
+        a.X = (const cplx*)c.X; a.x_node_stride = c.x_stride; a.Y = (cplx*)c.Y; a.y_node_stride = c.y_stride;
+        a.znode = c.coefB; a.z_stride = ld;
+        a.Bvec = (const cplx*)c.Bvec; a.b_node_stride = c.b_stride; a.U = (const cplx*)c.U; a.u_node_stride = c.u_stride;
+        a.dot_mode = c.dot_mode; a.partial1 = c.partial1; a.partial2 = c.partial2; a.node_active = c.node_active;
+        a.nodes = c.nodes; a.m = c.m;
+        return fh_launch_spmm_poly(h, ld, a);
+    }
     fh_dense_op_args a;
     a.A = h->dense.A; a.B = h->dense.B; a.N = (int)h->dense.N; a.is_complex = h->dense.is_complex;
     // dense operator: complex128 panels only (fh_krylov forces prec 64 for dense matrices)
@@ -666,6 +688,7 @@ static int fh_op_nblk(feasthip_ctx* h, int ld) {
     //  fh_apply_operator returns for the kernel it actually launched)
     if (h->kind == 2) return std::max(std::max(fh_spmm_partials((int)h->csr.N, ld), ld == 64 ? fh_spmm_row_grid((int)h->csr.N) : 0),
                                       h->csr.lcol ? (8 / (ld / 16)) * fh_spmm_lds_slots(h->csr.nblk, ld) : 0);
+    if (h->kind == 3 && h->poly.sparse) return fh_poly_op_nblk((int)h->dense.N, ld);
     return fh_dense_op_nblk((int)h->dense.N);
 }
 // row permutation of the panels (block order of a renumbered sparse matrix), or null
@@ -826,14 +849,7 @@ static int fh_download_small(feasthip_ctx* h, const void* src, size_t bytes, con
 //             relative reduction of r0 (inexact solves), so single precision is ample; the
 //             warm start, the residual and the Rayleigh-Ritz step stay fp64.
 // ---------------------------------------------------------------------------------------
-struct fh_solve_result {
-    std::vector<int> node_iters, col_iters;
-    int64_t iters_sum = 0;      // sum over nodes of max column iterations
-    int64_t op_calls = 0;
-    int max_iters = 0;
-    std::vector<int> status;    // per node
-    double max_rel_res = 0.0;
-};
+// (fh_solve_result: fh_krylov.hpp)
 
 // Throttle of the Krylov drivers' queueing loops: after chunk `tag` has been queued (with its publish kernel), wait -- by
 // polling the host-mapped progress word -- until the device is at most three chunks behind; *all_done when a published
@@ -930,18 +946,7 @@ static int fh_collect_columns(feasthip_ctx* h, const int* d_iters, const int* d_
     return 0;
 }
 
-// The optional parts of a fh_krylov call; default-constructed: a plain solve from the guess in X.
-// sum_acc and wnode (COCG only): "sum mode" -- X keeps the initial guess, every step alpha p of every node is added, weighted
-// with wnode[e], to the N x ld accumulator sum_acc (zeroed by the caller): sum_e w_e X_e(final) = sum_e w_e X_e(initial) + sum_acc.
-// shared_src (sum mode, prec 64): the initial residual of every node is  f_node,c * shared_src  with f = 1/(z_node -
-// shared_lambda[c]) (Ritz warm start: the values on the device and on the host, dznode: the nodes on the device) or 1 (no
-// shared_lambda: zero guess, the source is RHS).  X and RHS are then never read: no warm-start panels, no residual product.
-struct fh_krylov_opts {
-    cplx* sum_acc = nullptr;
-    const std::vector<cplx>* wnode = nullptr;
-    const cplx *shared_src = nullptr, *dznode = nullptr;
-    const double *shared_lambda = nullptr, *shared_lambda_host = nullptr;
-};
+// (fh_krylov_opts, the optional parts of a fh_krylov call: fh_krylov.hpp)
 
 namespace {      // (internal linkage for the member functions, as the static helpers have)
 // What the phases of fh_krylov share: the shape of the call, the work panels and the argument blocks of the kernels
@@ -1142,8 +1147,8 @@ void fh_krylov_work::cocg_fused_step(int it) {
 }  // namespace
 
 // Batched BiCGStab (method 0) or COCG (method 1) on `nodes` panels, in five phases: allocate, start, iterate, finish, collect.
-static int fh_krylov(feasthip_ctx* h, int method, int prec, int ld, int m, int nodes, const std::vector<cplx>& z,
-                     const cplx* RHS, cplx* X, size_t stride, fh_solve_result& res, const fh_krylov_opts& opt) {
+int fh_krylov(feasthip_ctx* h, int method, int prec, int ld, int m, int nodes, const std::vector<cplx>& z,
+              const cplx* RHS, cplx* X, size_t stride, fh_solve_result& res, const fh_krylov_opts& opt) {
     if (h->kind != 2) prec = 64;          // the dense operator kernel takes complex128 panels only
     fh_krylov_work k{h, res};
     k.method = method; k.prec = prec; k.ld = ld; k.m = m; k.nodes = nodes; k.N = (int)fh_N(h); k.panel = (size_t)k.N * ld;
@@ -1376,8 +1381,8 @@ static int fh_block_cocg(feasthip_ctx* h, int ld, int m, int nodes, const std::v
 // and the host adds it after the synchronisation of the next cycle start.  (Counting queued steps made the budget left for a
 // column that the restart's true residual reactivates, and spmm_calls, depend on host/device timing.)
 // ---------------------------------------------------------------------------------------
-static int fh_gmres(feasthip_ctx* h, int ld, int m, int nodes_all, const std::vector<cplx>& z, const cplx* RHS, cplx* X,
-                    size_t stride, fh_solve_result& res) {
+int fh_gmres(feasthip_ctx* h, int ld, int m, int nodes_all, const std::vector<cplx>& z, const cplx* RHS, cplx* X,
+             size_t stride, fh_solve_result& res) {
     const int N = (int)fh_N(h);
     const size_t panel = (size_t)N * ld;
     const int mr = std::max(h->restart, 2);

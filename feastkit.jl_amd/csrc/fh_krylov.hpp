@@ -1,0 +1,51 @@
+// fh_krylov.hpp -- the batched Krylov drivers of fh_api.hip for the other .hip units, and the polynomial operator
+// (fh_poly.hip) that fh_apply_operator launches for a sparse polynomial handle.
+#pragma once
+#include "fh_common.hpp"
+#include <vector>
+
+// What a batched solve reports (filled by fh_collect_columns)
+struct fh_solve_result {
+    std::vector<int> node_iters, col_iters;
+    int64_t iters_sum = 0;      // sum over nodes of max column iterations
+    int64_t op_calls = 0;
+    int max_iters = 0;
+    std::vector<int> status;    // per node
+    double max_rel_res = 0.0;
+};
+
+// The optional parts of a fh_krylov call; default-constructed: a plain solve from the guess in X.
+// sum_acc and wnode (COCG only): "sum mode" -- X keeps the initial guess, every step alpha p of every node is added, weighted
+// with wnode[e], to the N x ld accumulator sum_acc (zeroed by the caller): sum_e w_e X_e(final) = sum_e w_e X_e(initial) + sum_acc.
+// shared_src (sum mode, prec 64): the initial residual of every node is  f_node,c * shared_src  with f = 1/(z_node -
+// shared_lambda[c]) (Ritz warm start: the values on the device and on the host, dznode: the nodes on the device) or 1 (no
+// shared_lambda: zero guess, the source is RHS).  X and RHS are then never read: no warm-start panels, no residual product.
+struct fh_krylov_opts {
+    cplx* sum_acc = nullptr;
+    const std::vector<cplx>* wnode = nullptr;
+    const cplx *shared_src = nullptr, *dznode = nullptr;
+    const double *shared_lambda = nullptr, *shared_lambda_host = nullptr;
+};
+
+// S_e X_e = RHS for e in [0, nodes), S_e = z_e B - A of a pencil handle or P(z_e) of a sparse polynomial handle; one
+// right-hand-side panel shared by the nodes, X (`stride` = N ld elements apart) holds the guess on entry.  The handle's rtol,
+// atol, maxit (and restart) apply.  fh_krylov: BiCGStab (method 0) or COCG (method 1); fh_gmres: restarted GMRES.
+int fh_krylov(feasthip_ctx* h, int method, int prec, int ld, int m, int nodes, const std::vector<cplx>& z, const cplx* RHS,
+              cplx* X, size_t stride, fh_solve_result& res, const fh_krylov_opts& opt);
+int fh_gmres(feasthip_ctx* h, int ld, int m, int nodes_all, const std::vector<cplx>& z, const cplx* RHS, cplx* X, size_t stride,
+             fh_solve_result& res);
+
+// Y_e = [Bvec -] P(z_e) X_e on a sparse polynomial handle (fh_poly.hip: k_spmm_poly), complex128 panels; the fields are those
+// of fh_spmm_args.  z_e = znode[e * z_stride].  Returns the partial-sum rows per node it wrote (fh_poly_op_nblk).
+struct fh_polyop_call {
+    const cplx* X; size_t x_node_stride;
+    cplx* Y; size_t y_node_stride;
+    const cplx* znode; int z_stride;
+    const cplx* Bvec; size_t b_node_stride;
+    const cplx* U; size_t u_node_stride;
+    int dot_mode; cplx* partial1; cplx* partial2;     // modes 0 .. 4 of fh_sparse.hip
+    const int* node_active;
+    int nodes, m;
+};
+int fh_poly_op_nblk(int N, int ld);
+int fh_launch_spmm_poly(feasthip_ctx* h, int ld, const fh_polyop_call& c);

@@ -25,6 +25,7 @@
 // k_spmm_fan below.  Everything else in this file is shared by the two flavours.
 #include "fh_common.hpp"
 #include "fh_kernels.hpp"
+#include "fh_krylov.hpp"
 #include "fh_dense.hpp"
 #include "fh_banded.hpp"
 #include "../../include/feasthip.h"
@@ -315,18 +316,167 @@ __global__ __launch_bounds__(FH_BLOCK) void k_poly_resinv_acc(const cplx* __rest
 }
 
 // ---------------------------------------------------------------------------------------
+// Krylov solvers on P(z) (sparse handle; fh_api.hip: fh_apply_operator): the node-batched operator product
+//     Y_e = P(z_e) X_e     or     Y_e = Bvec - P(z_e) X_e      e = 0 .. nodes-1
+// with the fused dots the batched BiCGStab / COCG / GMRES drivers read (dot modes 0 .. 4 of fh_sparse.hip, same conjugation):
+//     1: partial1 = <U, Y>      2: partial1 = <Y, X>, partial2 = <Y, Y>      3: partial2 = <Y, Y>      4: partial1 = X^T Y
+// The row-slice layout of k_spmm_fan / k_spmm_horner (LD lanes own a row, lane <-> column, gathers batched four deep); per
+// nonzero s = sum_k a_k z_e^k is formed by Horner in registers from the d + 1 value arrays -- P(z_e) is never materialised.
+// The node loop is outermost (as in k_spmm), z_e comes from a device table, an inactive node is skipped and its partial rows
+// cleared.  Persistent grid of 8 S <= FH_POLYOP_GRID_MAX workgroups, ONE partial row per workgroup and node,
+// partial[(node nprow + blockIdx.x) LD + c] with nprow = gridDim.x: a thread adds its rows in ascending order, the FH_BLOCK / LD
+// threads of a column are added through LDS in thread order.  No atomics: reproducible.
+// Rows to workgroups as in k_spmm: XCD group g = blockIdx.x & 7 owns row slice g of ceil(N / 8) rows and its S workgroups sweep
+// it as a moving band of S ROWS consecutive rows, so a gathered X line is wanted by one private L2 only and lives there for the
+// stencil's reuse distance.  Y is written and Bvec / U are read with non-temporal accesses: they stream past the X window.
+// (Placement affects speed only.)
+// Algorithmic traffic per active node: nnz (4 + (d + 1) sizeof(VT)) of matrix, one X row of 16 LD B gathered per nonzero,
+// N LD 16 B written, as much read for each of Bvec, U and (modes 2, 4) the row's own X element.
+// ---------------------------------------------------------------------------------------
+#define FH_POLYOP_GRID_MAX 1024
+struct fh_polyop_args {
+    const int* rowptr; const int* col;
+    const void* val[PD + 1];
+    int N, d, nodes;
+    fh_polyop_call c;
+    unsigned long long* counters;     // profiling: [0] active node-launches, [1] active column x vector passes (may be null)
+};
+
+__device__ __forceinline__ cplx poly_ld_nt(const cplx* p) { return cmake(__builtin_nontemporal_load(&p->x), __builtin_nontemporal_load(&p->y)); }
+__device__ __forceinline__ void poly_st_nt(cplx* p, cplx v) { __builtin_nontemporal_store(v.x, &p->x); __builtin_nontemporal_store(v.y, &p->y); }
+
+template <typename VT, int LD>
+__global__ __launch_bounds__(FH_BLOCK) void k_spmm_poly(fh_polyop_args a) {
+    constexpr int ROWS = FH_BLOCK / LD;
+    __shared__ cplx red[FH_BLOCK];
+    const int t = threadIdx.x;
+    const int c = t % LD, r = t / LD;
+    const int* __restrict__ rowptr = a.rowptr;
+    const int* __restrict__ colidx = a.col;
+    const int nprow = gridDim.x;
+    const int mode = a.c.dot_mode;
+    const int S = nprow >> 3, grp = blockIdx.x & 7, slot = blockIdx.x >> 3;
+    const int slice_rows = (a.N + 7) / 8;
+    const int row_lo = min(a.N, grp * slice_rows), row_hi = min(a.N, row_lo + slice_rows);
+    for (int node = 0; node < a.nodes; ++node) {
+        const size_t pbase = ((size_t)node * nprow + blockIdx.x) * LD;
+        if (a.c.node_active && a.c.node_active[node] == 0) {          // (uniform over the workgroup)
+            if (mode != 0 && t < LD) {
+                if (a.c.partial1) a.c.partial1[pbase + t] = cmake(0, 0);
+                if (a.c.partial2) a.c.partial2[pbase + t] = cmake(0, 0);
+            }
+            continue;
+        }
+        if (a.counters && blockIdx.x == 0 && t == 0) {
+            const int cols = a.c.node_active ? a.c.node_active[node] : a.c.m;
+            atomicAdd(a.counters + 0, 1ull);
+            atomicAdd(a.counters + 1, (unsigned long long)(cols * ((mode == 1 || a.c.Bvec) ? 3 : 2)));
+        }
+        const cplx* __restrict__ X = a.c.X + (size_t)node * a.c.x_node_stride;
+        cplx* __restrict__ Y = a.c.Y + (size_t)node * a.c.y_node_stride;
+        const cplx* __restrict__ Bv = a.c.Bvec ? a.c.Bvec + (size_t)node * a.c.b_node_stride : nullptr;
+        const cplx* __restrict__ U = a.c.U ? a.c.U + (size_t)node * a.c.u_node_stride : nullptr;
+        const cplx z = a.c.znode[(size_t)node * a.c.z_stride];
+        cplx d1 = cmake(0, 0), d2 = cmake(0, 0);
+        for (int i = row_lo + slot * ROWS + r; i < row_hi; i += S * ROWS) {
+            const int k0 = rowptr[i], k1 = rowptr[i + 1];
+            cplx acc = cmake(0, 0);
+            // batches of 4 nonzeros: the gathers are issued together (a slot past the row end gathers the row's last column
+            // again and adds nothing), then per nonzero the d + 1 values are read and s = P(z_e)[i, j] formed by Horner
+            for (int kb = k0; kb < k1; kb += 4) {
+                cplx xs[4];
+#pragma unroll
+                for (int q = 0; q < 4; ++q) xs[q] = X[(size_t)colidx[min(kb + q, k1 - 1)] * LD + c];
+#pragma unroll
+                for (int q = 0; q < 4; ++q)
+                    if (kb + q < k1) {
+                        cplx v = cmake(0, 0);
+#pragma unroll
+                        for (int k = PD; k >= 0; --k)
+                            if (k <= a.d) v = cadd(cmul(v, z), poly_val(((const VT*)a.val[k])[kb + q]));
+                        cfma(acc, v, xs[q]);
+                    }
+            }
+            const size_t e = (size_t)i * LD + c;
+            if (Bv) acc = csub(poly_ld_nt(Bv + e), acc);
+            poly_st_nt(Y + e, acc);
+            if (mode == 1) d1 = cadd(d1, cmulc(poly_ld_nt(U + e), acc));
+            else if (mode == 2) { d1 = cadd(d1, cmulc(acc, X[e])); d2.x += cabs2(acc); }
+            else if (mode == 3) d2.x += cabs2(acc);
+            else if (mode == 4) d1 = cadd(d1, cmul(X[e], acc));          // unconjugated p^T (S p), COCG
+        }
+        if (mode != 0) {
+            // column c: the ROWS threads t = c + k LD, added in ascending k
+            if (mode != 3) {
+                red[t] = d1;
+                __syncthreads();
+                if (t < LD) {
+                    cplx s = red[t];
+#pragma unroll
+                    for (int k = 1; k < ROWS; ++k) s = cadd(s, red[t + k * LD]);
+                    a.c.partial1[pbase + t] = s;
+                }
+                __syncthreads();
+            }
+            if (mode == 2 || mode == 3) {
+                red[t] = d2;
+                __syncthreads();
+                if (t < LD) {
+                    cplx s = red[t];
+#pragma unroll
+                    for (int k = 1; k < ROWS; ++k) s = cadd(s, red[t + k * LD]);
+                    a.c.partial2[pbase + t] = s;
+                }
+                __syncthreads();
+            }
+        }
+    }
+}
+
+// 8 S workgroups: S per row slice, enough for one pass over the slice up to the grid limit
+int fh_poly_op_nblk(int N, int ld) {
+    const int rows = FH_BLOCK / ld, slice_rows = (N + 7) / 8;
+    return 8 * std::max(1, std::min(FH_POLYOP_GRID_MAX / 8, (slice_rows + rows - 1) / rows));
+}
+
+int fh_launch_spmm_poly(feasthip_ctx* h, int ld, const fh_polyop_call& c) {
+    fh_polyop_args a;
+    memset(&a, 0, sizeof(a));
+    a.rowptr = h->csr.rowptr; a.col = h->csr.col; a.N = (int)h->csr.N; a.d = h->poly.degree; a.nodes = c.nodes;
+    for (int k = 0; k <= a.d; ++k) a.val[k] = h->poly.coef[k];
+    a.c = c;
+    a.counters = h->profiling ? h->d_counters : nullptr;
+    const int nprow = fh_poly_op_nblk(a.N, ld);
+    const dim3 grid((unsigned)nprow), block(FH_BLOCK);
+    fh_prof_begin(h, "spmm_poly");
+    fh_with_ld(ld, [&](auto L) {
+        constexpr int LD = decltype(L)::value;
+        if (h->csr.is_complex) hipLaunchKernelGGL((k_spmm_poly<cplx, LD>), grid, block, 0, h->stream, a);
+        else hipLaunchKernelGGL((k_spmm_poly<double, LD>), grid, block, 0, h->stream, a);
+    });
+    fh_prof_end(h);
+    return nprow;
+}
+
+// ---------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------
 static inline double poly_now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
-// What every feasthip_poly_* call needs: a polynomial handle in the one configuration the structured solve covers, and
-// 1 <= m <= maxm.  what: the entry point's name for the message.
+// true: the handle's solver is a Krylov method on the operator P(z_e) (CSR coefficients only)
+static bool poly_krylov(const feasthip_ctx* h) {
+    return h->solver == FEASTHIP_SOLVER_BICGSTAB || h->solver == FEASTHIP_SOLVER_COCG || h->solver == FEASTHIP_SOLVER_GMRES;
+}
+
+// What every feasthip_poly_* call needs: a polynomial handle in a configuration the structured solve covers -- the LU of
+// P(z_e), or for CSR coefficients a Krylov solver on it -- and 1 <= m <= maxm.  what: the entry point's name for the message.
 static int poly_check(feasthip_ctx* h, const char* what, int64_t m, int64_t maxm) {
     if (!h) return FEASTHIP_ERROR_INTERNAL;
     if (h->poisoned) { h->last_error = "handle poisoned by an earlier device failure: destroy it"; return FEASTHIP_ERROR_INTERNAL; }
     const char* why = nullptr;
     if (h->kind != 3) why = "needs a polynomial handle (feasthip_set_polynomial); a dense or CSR handle takes the entry points without poly_";
-    else if (h->solver != FEASTHIP_SOLVER_LU) why = "the solver must be FEASTHIP_SOLVER_LU";
+    else if (h->solver != FEASTHIP_SOLVER_LU && !(poly_krylov(h) && h->poly.sparse && !h->shifted && !h->block))
+        why = h->poly.sparse ? "the solver must be FEASTHIP_SOLVER_LU, _BICGSTAB, _COCG or _GMRES" : "the solver of a dense polynomial handle must be FEASTHIP_SOLVER_LU";
     else if (h->factor_precision != 64) why = "factor_precision = 32 is not supported (complex128 factors only)";
     else if (h->adjoint) why = "the adjoint switch is not supported";
     else if (h->comm) why = "an attached communicator is not supported (one rank)";
@@ -526,16 +676,68 @@ extern "C" int feasthip_set_polynomial_csr(feasthip_handle h, int64_t N, int deg
     return 0;
 }
 
-// The N x N solves of either flavour: the dense LU of P(z_e), or for sparse coefficients the multifrontal one through the
-// factor cache of the sparse direct solver (same slots, same matching by z)
-static int poly_lu_single(feasthip_ctx* h, int ld, int m, cplx z, const cplx* Rhs, cplx* Y, int* status, int64_t* nfact) {
+// Krylov solves P(z_e) Y_e = RHS for the nodes z (one right-hand-side panel shared by all of them), from a zero start, under the
+// handle's rtol / atol / maxit / restart, through the batched drivers of fh_api.hip on the operator k_spmm_poly.  status[e] = 5
+// for a node with a column that did not pass the stop test.  The counts go into `it`.
+struct poly_iters {
+    int64_t sum = 0, op_calls = 0;
+    double max_rel_res = 0.0;
+    std::vector<int> node, col;       // per node: most steps of a column; [node][m]
+};
+static int poly_krylov_nodes(feasthip_ctx* h, int ld, int m, const std::vector<cplx>& z, const cplx* RHS, size_t panel, cplx* Y,
+                             std::vector<int>& status, poly_iters& it) {
+    const int ne = (int)z.size();
+    FH_CHECK(hipMemsetAsync(Y, 0, (size_t)ne * panel * sizeof(cplx), h->stream));
+    fh_solve_result sr;
+    const int rc = h->solver == FEASTHIP_SOLVER_GMRES ? fh_gmres(h, ld, m, ne, z, RHS, Y, panel, sr)
+                                                      : fh_krylov(h, h->solver == FEASTHIP_SOLVER_COCG ? 1 : 0, 64, ld, m, ne, z, RHS, Y, panel, sr, fh_krylov_opts());
+    if (rc) return rc;
+    status = sr.status;
+    it.sum += sr.iters_sum; it.op_calls += sr.op_calls; it.max_rel_res = std::max(it.max_rel_res, sr.max_rel_res);
+    it.node = sr.node_iters; it.col = sr.col_iters;
+    return 0;
+}
+
+// The N x N solves, a dispatch on the handle's solver: the dense LU of P(z_e), for sparse coefficients the multifrontal one
+// through the factor cache of the sparse direct solver (same slots, same matching by z), or the Krylov solves above
+static int poly_lu_single(feasthip_ctx* h, int ld, int m, cplx z, const cplx* Rhs, cplx* Y, int* status, int64_t* nfact, poly_iters& it) {
+    if (poly_krylov(h)) {
+        std::vector<int> st;
+        const int rc = poly_krylov_nodes(h, ld, m, std::vector<cplx>(1, z), Rhs, (size_t)h->dense.N * ld, Y, st, it);
+        if (!rc) *status = st[0];
+        return rc;
+    }
     return h->poly.sparse ? fh_banded_solve_single(h, ld, m, z, Rhs, Y, status, nfact) : fh_dense_lu_solve_single(h, ld, m, z, Rhs, Y, status, nfact);
 }
-// (rhs_stride: `panel` for one right-hand side panel per node, 0 for one panel shared by all nodes)
-static int poly_lu_nodes(feasthip_ctx* h, int ld, int m, int ne, const cplx* RHS, size_t rhs_stride, size_t panel, cplx* Y, std::vector<int>& status, int64_t* nfact) {
+// (rhs_stride: `panel` for one right-hand side panel per node, 0 for one panel shared by all nodes -- the only form the Krylov
+//  drivers take)
+static int poly_lu_nodes(feasthip_ctx* h, int ld, int m, int ne, const cplx* RHS, size_t rhs_stride, size_t panel, cplx* Y, std::vector<int>& status, int64_t* nfact, poly_iters& it) {
+    if (poly_krylov(h)) {
+        if (rhs_stride != 0) { h->last_error = "internal: a Krylov solver takes one right-hand-side panel shared by the nodes"; return FEASTHIP_ERROR_INTERNAL; }
+        return poly_krylov_nodes(h, ld, m, h->zne, RHS, panel, Y, status, it);
+    }
     return h->poly.sparse ? fh_banded_solve_nodes(h, ld, m, ne, h->zne, RHS, rhs_stride, Y, panel, status, nfact)
                           : fh_dense_lu_solve_nodes(h, ld, m, ne, h->zne, RHS, rhs_stride, Y, panel, status, nfact);
 }
+
+// The Krylov counts of a call that ran `ne` nodes on m64 columns in 64-column panels: the statistics, and what
+// feasthip_last_node_iterations / feasthip_last_column_iterations report ([node][m64]; a node's count is its slowest column's)
+struct poly_iter_record {
+    int ne; int64_t m64;
+    poly_iters tot;
+    std::vector<int> node, col;
+    poly_iter_record(int ne_, int64_t m64_) : ne(ne_), m64(m64_), node(ne_, 0), col((size_t)ne_ * m64_, 0) {}
+    void panel(const poly_iters& it, int64_t c0, int m) {
+        for (int e = 0; e < ne && e < (int)it.node.size(); ++e) {
+            node[e] = std::max(node[e], it.node[e]);
+            for (int c = 0; c < m; ++c) col[(size_t)e * m64 + c0 + c] = it.col[(size_t)e * m + c];
+        }
+    }
+    void publish(feasthip_ctx* h, const poly_iters& it, feasthip_stats* stats) {
+        h->last_node_iters = node; h->last_col_iters = col; h->last_col_m = (int)m64;
+        if (stats) { stats->krylov_iterations = it.sum; stats->spmm_calls = it.op_calls; stats->max_rel_residual = it.max_rel_res; }
+    }
+};
 
 // Y = P(z)^-1 R, N x m column-major; the factor is cached in the slot of the contour node z equals, else in one extra slot
 extern "C" int feasthip_poly_solve_dev(feasthip_handle h, double z_re, double z_im, int64_t m64, const void* dR, void* dY,
@@ -548,6 +750,8 @@ extern "C" int feasthip_poly_solve_dev(feasthip_handle h, double z_re, double z_
     const int N = (int)h->dense.N;
     if (stats) memset(stats, 0, sizeof(*stats));
     int worst = 0;
+    poly_iters it;
+    poly_iter_record rec(1, m64);
     for (int64_t c0 = 0; c0 < m64; c0 += FH_MAX_LD) {
         const int m = (int)std::min<int64_t>(FH_MAX_LD, m64 - c0), ld = fh_pick_ld(m);
         const size_t panel = (size_t)N * ld;
@@ -557,7 +761,8 @@ extern "C" int feasthip_poly_solve_dev(feasthip_handle h, double z_re, double z_
         fh_launch_to_panel((const cplx*)dR + (size_t)c0 * N, N, N, m, Rhs, ld, h->stream);
         int status = 0;
         int64_t nfact = 0;
-        if ((rc = poly_lu_single(h, ld, m, cmake(z_re, z_im), Rhs, Y, &status, &nfact))) return rc;
+        if ((rc = poly_lu_single(h, ld, m, cmake(z_re, z_im), Rhs, Y, &status, &nfact, it))) return rc;
+        if (poly_krylov(h)) rec.panel(it, c0, m);
         fh_launch_from_panel(Y, ld, N, m, (cplx*)dY + (size_t)c0 * N, N, h->stream);
         if (stats) stats->factorizations += nfact;
         worst = std::max(worst, status);
@@ -565,6 +770,7 @@ extern "C" int feasthip_poly_solve_dev(feasthip_handle h, double z_re, double z_
     FH_CHECK(hipStreamSynchronize(h->stream));
     fh_prof_collect(h);
     FH_CHECK(hipGetLastError());
+    if (poly_krylov(h)) rec.publish(h, it, stats);
     if (stats) stats->seconds_total = poly_now() - t0;
     return worst;
 }
@@ -577,6 +783,11 @@ extern "C" int feasthip_poly_contour_apply_dev(feasthip_handle h, int64_t m64, c
     if (!dQ || !dQproj) { h->last_error = "feasthip_poly_contour_apply_dev: null argument"; return FEASTHIP_ERROR_INTERNAL; }
     if (h->zne.empty()) { h->last_error = "feasthip_poly_contour_apply_dev: no contour set (feasthip_set_contour)"; return FEASTHIP_ERROR_FPM; }
     if (h->real_projection) { h->last_error = "feasthip_poly_contour_apply_dev: the real projection does not apply to a polynomial sweep"; return FEASTHIP_ERROR_FPM; }
+    if (poly_krylov(h)) {
+        h->last_error = "feasthip_poly_contour_apply_dev: the linearised sweep has one right-hand side per node, which the Krylov solvers do not take; "
+                        "under a Krylov solver use the projected method (feasthip_poly_resinv_apply_dev), or FEASTHIP_SOLVER_LU";
+        return FEASTHIP_ERROR_FPM;
+    }
     FH_CHECK(hipSetDevice(h->device));
     const double t0 = poly_now();
     const int N = (int)h->dense.N, d = h->poly.degree, ne = (int)h->zne.size();
@@ -622,7 +833,8 @@ extern "C" int feasthip_poly_contour_apply_dev(feasthip_handle h, int64_t m64, c
         fh_prof_end(h);
         std::vector<int> status;
         int64_t nfact = 0;
-        if ((rc = poly_lu_nodes(h, ld, m, ne, RHS, panel, panel, Y, status, &nfact))) return rc;
+        poly_iters none;
+        if ((rc = poly_lu_nodes(h, ld, m, ne, RHS, panel, panel, Y, status, &nfact, none))) return rc;
         fh_prof_begin(h, "poly_expand");
         hipLaunchKernelGGL(k_poly_expand_sum, grid, block, 0, h->stream, Y, panel, Rs, d, dzw, dzw + ne, ne, OUT, panel);
         fh_prof_end(h);
@@ -637,11 +849,46 @@ extern "C" int feasthip_poly_contour_apply_dev(feasthip_handle h, int64_t m64, c
     return 0;
 }
 
-// Y = A_lin X (which 0) or B_lin X (which 1), dN x m column-major
+// The operator of the Krylov solvers as a product of its own (which 2, 3, 4 of feasthip_poly_matmul_dev): CSR coefficients, a
+// contour of ne nodes, m <= 64; X and Y hold ne blocks of N x m (column-major) one behind the other.
+//   2: Y_e = P(z_e) X_e      3: Y_e = B - P(z_e) X_e, B = block 0 of Y on entry      4: Y_e = B_e - P(z_e) X_e, B_e = block e of Y on entry
+static int poly_node_products(feasthip_ctx* h, int which, int64_t m64, const cplx* dX, cplx* dY) {
+    const char* why = nullptr;
+    if (!h->poly.sparse) why = "the node products (which 2, 3, 4) need CSR coefficients (feasthip_set_polynomial_csr)";
+    else if (h->zne.empty()) why = "the node products (which 2, 3, 4) need a contour (feasthip_set_contour)";
+    if (why) { h->last_error = std::string("feasthip_poly_matmul_dev: ") + why; return FEASTHIP_ERROR_FPM; }
+    if (m64 > FH_MAX_LD) { h->last_error = "feasthip_poly_matmul_dev: the node products take at most 64 columns"; return FEASTHIP_ERROR_M0; }
+    FH_CHECK(hipSetDevice(h->device));
+    const int N = (int)h->dense.N, ne = (int)h->zne.size(), m = (int)m64, ld = fh_pick_ld(m);
+    const size_t panel = (size_t)N * ld, blockN = (size_t)N * m;
+    const int nb = which == 4 ? ne : which == 3 ? 1 : 0;
+    int rc;
+    cplx *Xs, *Ys, *Bs, *dz;
+    if ((rc = fh_buf(h, "pn_X", (size_t)ne * panel, &Xs))) return rc;
+    if ((rc = fh_buf(h, "pn_Y", (size_t)ne * panel, &Ys))) return rc;
+    if ((rc = fh_buf(h, "pn_B", (size_t)std::max(1, nb) * panel, &Bs))) return rc;
+    if ((rc = poly_upload(h, "pn_z", h->zne, &dz))) return rc;
+    for (int e = 0; e < ne; ++e) fh_launch_to_panel(dX + (size_t)e * blockN, N, N, m, Xs + (size_t)e * panel, ld, h->stream);
+    for (int e = 0; e < nb; ++e) fh_launch_to_panel(dY + (size_t)e * blockN, N, N, m, Bs + (size_t)e * panel, ld, h->stream);
+    fh_polyop_call c;
+    memset(&c, 0, sizeof(c));
+    c.X = Xs; c.x_node_stride = panel; c.Y = Ys; c.y_node_stride = panel; c.znode = dz; c.z_stride = 1;
+    c.Bvec = nb ? Bs : nullptr; c.b_node_stride = which == 4 ? panel : 0;
+    c.nodes = ne; c.m = m;
+    fh_launch_spmm_poly(h, ld, c);
+    for (int e = 0; e < ne; ++e) fh_launch_from_panel(Ys + (size_t)e * panel, ld, N, m, dY + (size_t)e * blockN, N, h->stream);
+    FH_CHECK(hipStreamSynchronize(h->stream));
+    fh_prof_collect(h);
+    FH_CHECK(hipGetLastError());
+    return 0;
+}
+
+// Y = A_lin X (which 0) or B_lin X (which 1), dN x m column-major; which 2, 3, 4: poly_node_products
 extern "C" int feasthip_poly_matmul_dev(feasthip_handle h, int which, int64_t m64, const void* dX, void* dY) {
     int rc = poly_check(h, "feasthip_poly_matmul_dev", m64, h && h->kind == 3 ? h->dense.N * h->poly.degree : 1);
     if (rc) return rc;
-    if (!dX || !dY || (which != 0 && which != 1)) { h->last_error = "feasthip_poly_matmul_dev: bad argument"; return FEASTHIP_ERROR_INTERNAL; }
+    if (!dX || !dY || which < 0 || which > 4) { h->last_error = "feasthip_poly_matmul_dev: bad argument"; return FEASTHIP_ERROR_INTERNAL; }
+    if (which >= 2) return poly_node_products(h, which, m64, (const cplx*)dX, (cplx*)dY);
     FH_CHECK(hipSetDevice(h->device));
     const int N = (int)h->dense.N, d = h->poly.degree;
     const int64_t dN = (int64_t)d * N;
@@ -908,6 +1155,8 @@ extern "C" int feasthip_poly_resinv_apply_dev(feasthip_handle h, int64_t m64, co
     if (node_status) for (int e = 0; e < ne; ++e) node_status[e] = 0;
     poly_coefs pc;
     if ((rc = pc.acquire(h))) return rc;
+    poly_iters it;
+    poly_iter_record rec(ne, m64);
     for (int64_t c0 = 0; c0 < m64; c0 += FH_MAX_LD) {
         const int m = (int)std::min<int64_t>(FH_MAX_LD, m64 - c0), ld = fh_pick_ld(m);
         const size_t panel = (size_t)N * ld;
@@ -933,7 +1182,8 @@ extern "C" int feasthip_poly_resinv_apply_dev(feasthip_handle h, int64_t m64, co
         }
         std::vector<int> status;
         int64_t nfact = 0;
-        if ((rc = poly_lu_nodes(h, ld, m, ne, rhs, 0, panel, Y, status, &nfact))) return rc;
+        if ((rc = poly_lu_nodes(h, ld, m, ne, rhs, 0, panel, Y, status, &nfact, it))) return rc;
+        if (poly_krylov(h)) rec.panel(it, c0, m);
         fh_prof_begin(h, "poly_resinv");
         hipLaunchKernelGGL(k_poly_resinv_acc, dim3(fh_vec_nblk(N, ld)), dim3(FH_BLOCK), 0, h->stream, sg ? Xs : (const cplx*)nullptr, Y, panel, dT, ne, ld, Q, panel);
         fh_prof_end(h);
@@ -944,6 +1194,7 @@ extern "C" int feasthip_poly_resinv_apply_dev(feasthip_handle h, int64_t m64, co
     FH_CHECK(hipStreamSynchronize(h->stream));
     fh_prof_collect(h);
     FH_CHECK(hipGetLastError());
+    if (poly_krylov(h)) rec.publish(h, it, stats);
     if (stats) stats->seconds_total = poly_now() - t0;
     return 0;
 }

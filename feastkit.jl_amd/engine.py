@@ -527,7 +527,8 @@ class HipEngine:
         """The same for sparse coefficients on one CSR pattern (feasthip_set_polynomial_csr; ingest.polynomial_union_csr makes
         the arrays): rowptr / col 0-based, vals[k] the values of coeffs[k] on the pattern.  The poly_* methods work as on a
         dense polynomial; P(z_e) is factored by the multifrontal LU of the sparse direct solver (band_plan, direct_plan_flops
-        and direct_plan_bytes describe it)."""
+        and direct_plan_bytes describe it), or, after set_solver("bicgstab" | "cocg" | "gmres"), poly_solve and poly_resinv_apply
+        solve with that Krylov method on the operator P(z_e) and nothing is factored."""
         if len(vals) < 2:
             raise ValueError("a polynomial needs at least two coefficient matrices")
         rp = np.ascontiguousarray(rowptr, dtype=np.int64)
@@ -546,13 +547,14 @@ class HipEngine:
         return self.torch.empty((m, self.poly_degree * self.N), dtype=self.torch.complex128, device=self.device)
 
     def poly_solve(self, z, dR, m):
-        """Y = P(z)^-1 R on an N x m device block -> (dY, code 0 | 8); feasthip_poly_solve_dev."""
+        """Y = P(z)^-1 R on an N x m device block -> (dY, code 0 | 8); feasthip_poly_solve_dev.  Under a Krylov solver (sparse
+        coefficients) the code is 0 or 5 (a column stopped at maxit) and last_stats holds the iteration counts."""
         self._sync_stream()
         dY = self.empty(dR.shape[0])
         stats = FeastHipStats()
         rc = self.lib.feasthip_poly_solve_dev(self.h, float(np.real(z)), float(np.imag(z)), int(m), C.c_void_p(dR.data_ptr()),
                                               C.c_void_p(dY.data_ptr()), C.byref(stats))
-        self._chk(rc, ok=(0, 8))
+        self._chk(rc, ok=(0, 5, 8))
         self.last_stats = stats.asdict()
         return dY, rc
 
@@ -572,6 +574,24 @@ class HipEngine:
         self._sync_stream()
         dY = self._poly_empty(dX.shape[0])
         self._chk(self.lib.feasthip_poly_matmul_dev(self.h, int(which), int(m), C.c_void_p(dX.data_ptr()), C.c_void_p(dY.data_ptr())))
+        return dY
+
+    def poly_node_products(self, dX, m, dB=None):
+        """The operator of the Krylov solvers as a product (sparse coefficients, m <= 64): dX holds one N x m block per contour
+        node, an (ne m, N) tensor -> the same shape with Y_e = P(z_e) X_e, or Y_e = B - P(z_e) X_e for dB an (m, N) tensor
+        shared by the nodes, or Y_e = B_e - P(z_e) X_e for dB of dX's shape (feasthip_poly_matmul_dev, which 2 | 3 | 4)."""
+        m = int(m)
+        if dX.shape[0] != self.ne * m:
+            raise ValueError("poly_node_products needs one N x m block per contour node")
+        which = 2
+        dY = self.empty(dX.shape[0])
+        if dB is not None:
+            if dB.shape[0] not in (m, self.ne * m):
+                raise ValueError("poly_node_products: B is one N x m block, or one per node")
+            which = 3 if dB.shape[0] == m else 4
+            dY[:dB.shape[0]].copy_(dB)
+        self._sync_stream()
+        self._chk(self.lib.feasthip_poly_matmul_dev(self.h, which, m, C.c_void_p(dX.data_ptr()), C.c_void_p(dY.data_ptr())))
         return dY
 
     def poly_project(self, dQ, r):
@@ -610,7 +630,7 @@ class HipEngine:
     def poly_resinv_apply(self, dX, m, sigma=None):
         """The projected method's contour step on an N x m device block -> (dQ, status per node, stats): the plain sweep
         sum_e w_e P(z_e)^-1 X (sigma None), else the residual-inverse sweep with one shift per column
-        (feasthip_poly_resinv_apply_dev)."""
+        (feasthip_poly_resinv_apply_dev).  Under a Krylov solver a node's status is 0 or 5 (a column stopped at maxit)."""
         self._sync_stream()
         sg = None
         if sigma is not None:

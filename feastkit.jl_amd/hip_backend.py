@@ -1016,18 +1016,26 @@ def feast_hip_general(engine, A, B, Emid, r, M0, fpm, *, solver="direct", solver
 POLY_RESIDUALS = ("pencil", "reference")
 
 
-def _poly_setup(engine, coeffs, Emid, r, fpm, contour, union_csr):
+def _poly_setup(engine, coeffs, Emid, r, fpm, contour, union_csr, krylov=None):
     """What both polynomial drivers do before their loop: the polynomial (dense, or sparse from ``union_csr``) becomes the engine's
     problem with the direct solver, cached fp64 factors, no real projection and the full contour -> the plan fields of
-    ``stats["polynomial"]`` for sparse coefficients, else None."""
+    ``stats["polynomial"]`` for sparse coefficients, else None.  ``krylov`` = (solver, tol, maxiter, restart), sparse
+    coefficients only: that Krylov solver on P(z_e) instead, relative stop test (tol 0 = 10^-fpm[3]) -> {"plan": "krylov"}."""
     Zne, Wne = feast_gcontour(Emid, r, fpm) if contour is None else contour
     if union_csr is None:
         engine.set_polynomial(coeffs)
     else:
         engine.set_polynomial_csr(*union_csr)
-    engine.set_solver("direct", cache_factors=True, factor_precision=64)
+    if krylov is not None:
+        solver, tol, maxiter, restart = krylov
+        engine.set_solver(solver, rtol=feast_tolerance(fpm) if tol == 0.0 else float(tol), atol=0.0, maxit=maxiter, restart=restart,
+                          factor_precision=64)
+    else:
+        engine.set_solver("direct", cache_factors=True, factor_precision=64)
     engine.set_real_projection(False)
     engine.set_contour(Zne, Wne, 1.0)
+    if krylov is not None:
+        return {"plan": "krylov"}
     if union_csr is None:
         return None
     factor_bytes, transient_bytes = engine.direct_plan_bytes(1)
@@ -1144,21 +1152,27 @@ def poly_select(theta, be, center, radius, keep):
 
 
 def feast_hip_polynomial_projected(engine, coeffs, Emid, r, M0, fpm, *, Q0=None, seed=20260515, contour=None, eps_floor=0.0,
-                                   union_csr=None, ortho="mgs"):
+                                   union_csr=None, ortho="mgs", krylov=None):
     """P(lambda) x = 0 inside a circle on an N-row subspace of M0 columns: polynomial FEAST with a residual-inverse contour
     step (Gavin, Miedlar, Polizzi).  Per loop: the contour step on the N x m block (loop 0 the plain sweep, which factors
     P(z_e) once per node and fills the cache; afterwards R_j = P(sigma_j) x_j, Y_e = P(z_e)^-1 R, Q_j = sum_e w_e (x_j - Y_e,j)
     / (z_e - sigma_j) on the cached factors), unit columns and the rank-revealing orthonormalisation of ``ortho``, the
     projected polynomial Q^H A_k Q, its dr x dr companion pencil solved on the host, the backward error of ALL dr candidates,
     poly_select.  Stop test: the largest backward error among the kept pairs inside the circle.  At the loop limit the last
-    iterates are returned with info = Feast_ERROR_NO_CONVERGENCE.  ``union_csr`` and the exceptions: as feast_hip_polynomial."""
+    iterates are returned with info = Feast_ERROR_NO_CONVERGENCE.  ``union_csr`` and the exceptions: as feast_hip_polynomial.
+    ``krylov`` = (solver, tol, maxiter, restart) with ``union_csr``: the solves of the contour step run on that Krylov solver
+    (_poly_setup) and are inexact.  A node whose column stopped at maxiter (status 5) is the normal outcome of such a sweep and
+    the loop goes on with its iterate; ``stats["polynomial"]["krylov"]`` gets one entry per loop, {iterations (worst column),
+    node_iterations, capped_nodes}, ``stats["krylov_iterations"]`` the engine's count, and nothing is factored."""
     d = len(coeffs) - 1
     N = coeffs[0].shape[0]
     feastdefault(fpm)
     info = _check_circle_input(N, M0, r)
     if info:
         return _empty_result(N, info, complex_lambda=True)
-    plan = _poly_setup(engine, coeffs, Emid, r, fpm, contour, union_csr)
+    if krylov is not None and union_csr is None:
+        raise ValueError("a Krylov solver on P(z) needs sparse coefficients (union_csr)")
+    plan = _poly_setup(engine, coeffs, Emid, r, fpm, contour, union_csr, krylov)
     X_host = seeded_subspace(N, M0, seed) if Q0 is None else np.asarray(Q0, dtype=np.complex128)
     if X_host.shape != (N, M0):
         raise ValueError(f"Q0 must be the start block of shape ({N}, {M0})")
@@ -1172,12 +1186,20 @@ def feast_hip_polynomial_projected(engine, coeffs, Emid, r, M0, fpm, *, Q0=None,
     stats = {"krylov_iterations": 0, "factorizations": 0, "solve_seconds": 0.0, "polynomial": poly}
     if plan is not None:
         poly.update(plan)
+    if krylov is not None:
+        poly["krylov"] = []
     no_conv = FeastError.Feast_ERROR_NO_CONVERGENCE
     with _ortho_scope(engine, ortho, stats):
         while True:
             dQ, status, st = engine.poly_resinv_apply(dX, m, sigma)
             stats["factorizations"] += st.get("factorizations", 0)
             stats["solve_seconds"] += st.get("seconds_total", 0.0)
+            if krylov is not None:
+                stats["krylov_iterations"] += int(st.get("krylov_iterations", 0))
+                node_it = engine.last_node_iterations(len(status))
+                poly["krylov"].append({"iterations": int(node_it.max()) if len(node_it) else 0,
+                                       "node_iterations": [int(v) for v in node_it], "capped_nodes": int(np.sum(status == 5))})
+                status = np.where(status == 5, 0, status)
             if int(np.max(status)):
                 return _empty_result(N, FeastError.Feast_ERROR_LAPACK, loop, complex_lambda=True, stats=stats)
             rank_q = engine.poly_orthonormalize(dQ, m, SQRT_EPS, unit_columns=True)

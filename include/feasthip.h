@@ -506,7 +506,8 @@ int  feasthip_shifted_solve_dev(feasthip_handle h, double z_re, double z_im, int
  * feasthip_set_polynomial: dense coefficients A_0 .. A_degree (host, column-major, ld[k] >= N; all double or all interleaved
  *   complex128), 1 <= degree <= FEASTHIP_POLY_MAX_DEGREE.  Replaces the coeffs argument of feast_pep!
  *   (src/dense/feast_dense.jl:715-744) and of feast_gepev! / feast_hepev! / feast_sypev! (:946-979).  The handle becomes a
- *   POLYNOMIAL handle: feasthip_set_contour, feasthip_set_solver (FEASTHIP_SOLVER_LU with factor_precision 64 only),
+ *   POLYNOMIAL handle: feasthip_set_contour, feasthip_set_solver (FEASTHIP_SOLVER_LU with factor_precision 64 only; a CSR
+ *   polynomial handle also takes the Krylov solvers, see "Krylov solvers on P(z)" below),
  *   feasthip_release_factors, the stream and the profile calls work on it; every other entry point above returns
  *   FEASTHIP_ERROR_FPM and names the feasthip_poly_* calls (feasthip_set_adjoint(1), a node range or list, a communicator and
  *   factor_precision 32 included: a polynomial sweep is one rank, forward, fp64).  feasthip_set_dense / feasthip_set_csr
@@ -525,12 +526,24 @@ int  feasthip_shifted_solve_dev(feasthip_handle h, double z_re, double z_im, int
  *   LU rejects (zero pivot, or a boundary multiplier beyond the bound: it pivots only inside a front's fully-summed block)
  *   makes the solve or sweep return FEASTHIP_ERROR_LAPACK with nothing computed; feasthip_last_error names the cause and the
  *   sizes.  Factors that do not fit the device: FEASTHIP_ERROR_MEMORY.
+ *   Krylov solvers on P(z): feasthip_set_solver also accepts FEASTHIP_SOLVER_BICGSTAB, _COCG (every coefficient symmetric,
+ *   A_k == A_k^T, real or complex: the caller's promise) and _GMRES on a CSR polynomial handle, factor_precision 64.  Then
+ *   feasthip_poly_solve_dev and feasthip_poly_resinv_apply_dev solve with the batched Krylov drivers on the operator P(z_e)
+ *   (formed per nonzero by Horner, never stored): zero start, no preconditioner, the handle's rtol / atol / maxit / restart, no
+ *   factors (stats.factorizations = 0).  stats.krylov_iterations, stats.spmm_calls, feasthip_last_node_iterations and
+ *   feasthip_last_column_iterations report as for a pencil; a node with a column that stopped at maxit has status
+ *   FEASTHIP_ERROR_NO_CONVERGENCE (5), its iterate is still used.  feasthip_poly_contour_apply_dev returns FEASTHIP_ERROR_FPM
+ *   under a Krylov solver (one right-hand side per node: use the projected method).  A dense polynomial handle refuses them.
  * feasthip_poly_solve_dev: Y = P(z)^-1 R, N x m (the shifted solve inside the companion elimination; no reference
- *   counterpart).  Factors are cached per contour node and matched by z, as in feasthip_shifted_solve.  Returns 0 or 8.
+ *   counterpart).  Factors are cached per contour node and matched by z, as in feasthip_shifted_solve.  Returns 0 or 8
+ *   (Krylov solver: 0 or 5).
  * feasthip_poly_contour_apply_dev: Qproj = sum_e weight_scale w_e (z_e B_lin - A_lin)^-1 (B_lin Q), dN x m: the loop body
  *   of feast_grci! as feast_gegv! drives it on the companion pencil (src/dense/feast_dense.jl:468-584).  node_status[e]: 0 or 8,
  *   ne entries.  stats.factorizations counts the N x N factorisations of the call (0 on a repeated contour).
  * feasthip_poly_matmul_dev: Y = A_lin X (which 0) or B_lin X (which 1), dN x m (RCI jobs 30 / 40 on the companion pencil).
+ *   which 2, 3, 4 (CSR coefficients, a contour of ne nodes, m <= 64): the operator of the Krylov solvers as a product of its
+ *   own.  X and Y hold ne blocks of N x m one behind the other;  2: Y_e = P(z_e) X_e;  3: Y_e = B - P(z_e) X_e with B = block 0
+ *   of Y on entry;  4: Y_e = B_e - P(z_e) X_e with B_e = block e of Y on entry.
  * feasthip_poly_project_dev: the raw products Aq = Q^H A_lin Q and Sq = Q^H B_lin Q (src/kernel/feast_kernel.jl:790, 805),
  *   r x r column-major host buffers.
  * feasthip_poly_ritz_residual_dev: X = Q V (dN x r; V r x r column-major, host), the first M columns scaled to unit length
@@ -548,7 +561,7 @@ int  feasthip_set_polynomial_csr(feasthip_handle h, int64_t N, int degree, int i
 int  feasthip_poly_solve_dev(feasthip_handle h, double z_re, double z_im, int64_t m, const void* dR, void* dY, feasthip_stats* stats);
 int  feasthip_poly_contour_apply_dev(feasthip_handle h, int64_t m, const void* dQ, void* dQproj, int* node_status,
                                      feasthip_stats* stats);
-int  feasthip_poly_matmul_dev(feasthip_handle h, int which /* 0 A_lin, 1 B_lin */, int64_t m, const void* dX, void* dY);
+int  feasthip_poly_matmul_dev(feasthip_handle h, int which /* 0 A_lin, 1 B_lin, 2 .. 4 node products */, int64_t m, const void* dX, void* dY);
 int  feasthip_poly_project_dev(feasthip_handle h, int64_t r, const void* dQ, void* Aq_host, void* Sq_host);
 int  feasthip_poly_ritz_residual_dev(feasthip_handle h, int64_t r, const void* dQ, const void* V_host, const void* lambda, int64_t M,
                                      int normalize, int use_B, void* dX, double* res, double* backward_error);
@@ -560,7 +573,8 @@ int  feasthip_poly_ritz_residual_dev(feasthip_handle h, int64_t r, const void* d
  * feasthip_poly_resinv_apply_dev: the contour step.  sigma == NULL: Q = sum_e weight_scale w_e P(z_e)^-1 X (plain sweep).
  *   Otherwise, with sigma: m complex shifts on the host,
  *     R[:, j] = P(sigma_j) x_j,  Y_e = P(z_e)^-1 R,  Q[:, j] = sum_e weight_scale w_e (x_j - Y_e[:, j]) / (z_e - sigma_j).
- *   Factors come from the per-node cache (stats.factorizations as in feasthip_poly_contour_apply_dev); node_status[e]: 0 or 8.
+ *   Factors come from the per-node cache (stats.factorizations as in feasthip_poly_contour_apply_dev); node_status[e]: 0 or 8
+ *   (Krylov solver: 0 or 5, and the sums use the iterates the capped nodes stopped with).
  *   A shift that is not finite or that coincides with a contour node to working precision: FEASTHIP_ERROR_FPM.
  * feasthip_poly_project_reduced_dev: Ahat_k = Q^H A_k Q, k = 0 .. degree, for an N x r block Q; Ahat_host: degree + 1 r x r
  *   column-major matrices one behind the other.

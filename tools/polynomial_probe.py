@@ -25,6 +25,13 @@ residual step, and that step's products as single-coefficient feasthip_matmul_de
 not the companion pencil): ms per solve, loops, M, the per-loop history, rank and set-aside counts; then the achieved GB/s of
 k_poly_resinv_acc (ne + 1 panels read, one written) and, sparse workload, of k_spmm_horner (nnz (4 + (d + 1) sizeof(VT)) plus
 one panel written) on one 64-column panel, against the measured copy ceiling bench.py quotes.
+
+--solver NAME [NAME ...] (--workload sparse --method projected; names of bicgstab, cocg, gmres): the projected method on Krylov
+solves of P(z_e) x = r (no factors) at every --solver-tol, alternating with solver="sparse_direct" from the same start block in
+one process: ms per solve, loops, Krylov iterations (total and the worst column per loop), capped nodes, and the device memory
+each variant holds at the end of a solve on a handle of its own (hipMemGetInfo; the direct variant with its factors kept).
+Then k_spmm_poly: device ms per launch on one node and on all nodes, 64 columns, against its algorithmic bytes nodes x (nnz (4 +
+(d + 1) sizeof(VT)) + two panels), next to k_spmm on the pencil (A_0, A_d) of the same pattern (one node, 64 columns).
 """
 import argparse
 import json
@@ -88,6 +95,10 @@ def main():
     ap.add_argument("--beta", type=float, default=0.05)
     ap.add_argument("--method", choices=("linearised", "projected"), default="linearised")
     ap.add_argument("--columns", type=int, default=None, help="--method projected: N-row columns (default 32 dense, 24 sparse)")
+    ap.add_argument("--solver", nargs="+", default=None, choices=("bicgstab", "cocg", "gmres"),
+                    help="sparse workload, projected method: Krylov solvers on P(z) to set beside solver=sparse_direct")
+    ap.add_argument("--solver-tol", type=float, nargs="+", default=(1e-4, 1e-2))
+    ap.add_argument("--solver-maxiter", type=int, default=2000)
     ap.add_argument("--set-aside", type=float, nargs=2, default=None, metavar=("ABS", "FACTOR"),
                     help="experiment: run the projected method with these set-aside thresholds instead of POLY_SET_ASIDE")
     a = ap.parse_args()
@@ -95,6 +106,10 @@ def main():
     if a.set_aside is not None:
         import feastkit_jl_amd.hip_backend as hb
         hb.POLY_SET_ASIDE = (float(a.set_aside[0]), float(a.set_aside[1]))
+    if a.solver:
+        if a.workload != "sparse" or a.method != "projected":
+            ap.error("--solver needs --workload sparse --method projected")
+        return main_krylov(a)
     if a.workload == "sparse":
         return main_sparse(a)
     import numpy as np
@@ -357,6 +372,123 @@ def main_sparse(a):
         projected_kernels(eng, fk, coeffs, center, radius, nodes, sparse=True)
     elif not a.companion_only:
         fan_against_single_products(eng, fk, coeffs, M0 * d)
+    eng.close()
+
+
+def main_krylov(a):
+    import numpy as np
+    import torch
+    import feastkit_jl_amd as fk
+    from feastkit_jl_amd.ingest import polynomial_union_csr
+    coeffs, center, radius, inside = sparse_quadratic(tuple(a.grid), a.alpha, a.beta)
+    d, N = 2, coeffs[0].shape[0]
+    columns = a.columns or 24
+    nodes = 16
+    Q0 = fk.seeded_subspace(N, columns)
+    symmetric = all(abs(c - c.T).max() == 0 for c in coeffs)
+    variants = [("sparse_direct", None)] + [(s, t) for s in a.solver for t in a.solver_tol if s != "cocg" or symmetric]
+    if "cocg" in a.solver and not symmetric:
+        print(json.dumps({"note": "cocg left out: a coefficient is not symmetric"}), flush=True)
+
+    def fpm():
+        f = fk.feastinit()
+        f[8], f[4], f[3] = nodes, 20, 10
+        return f
+
+    def run(eng, v, **kw):
+        eng.synchronize()
+        t0 = time.perf_counter()
+        extra = {} if v[1] is None else {"solver_tol": v[1], "solver_maxiter": a.solver_maxiter}
+        try:
+            r = fk.feast_polynomial(coeffs, center, radius, M0=columns, fpm=fpm(), engine=eng, Q0=Q0, solver=v[0], method="projected", **extra, **kw)
+        except Exception as err:
+            return err, 1e3 * (time.perf_counter() - t0)
+        eng.synchronize()
+        return r, 1e3 * (time.perf_counter() - t0)
+
+    # device memory per variant: a handle of its own, read at the end of one solve (which also warms the kernels up)
+    mem = {}
+    for v in variants:
+        torch.cuda.synchronize()
+        free0, _ = torch.cuda.mem_get_info()
+        e1 = fk.HipEngine(0)
+        run(e1, v, keep_factors=True)
+        free1, _ = torch.cuda.mem_get_info()
+        mem[v] = int(free0 - free1)
+        e1.free_factors()
+        e1.close()
+    eng = fk.HipEngine(0)
+    for v in variants:
+        run(eng, v)
+    ms = {v: [] for v in variants}
+    last = {}
+    for _ in range(a.runs):
+        for v in variants:
+            last[v], t = run(eng, v)
+            ms[v].append(t)
+    for v in variants:
+        r = last[v]
+        row = {"workload": "sparse", "method": "projected", "solver": v[0], "solver_tol": v[1], "grid": list(a.grid), "N": N, "columns": columns,
+               "nodes": nodes, "ms_median": float(np.median(ms[v])), "ms_all": ms[v], "device_bytes_held": mem[v]}
+        if isinstance(r, Exception):
+            row["error"] = str(r)
+        else:
+            poly = r.stats["polynomial"]
+            row.update(loops=r.loop, M=r.M, expected_M=len(inside), info=r.info, epsout=r.epsout, factorizations=r.stats.get("factorizations"),
+                       eigenvalue_error=match_error(r.lambda_, inside), eps_history=[float(e) for e in poly["eps_history"]], plan=poly.get("plan"),
+                       krylov_iterations=r.stats.get("krylov_iterations"))
+            if "krylov" in poly:
+                row.update(worst_column_steps=[k["iterations"] for k in poly["krylov"]], capped_nodes=[k["capped_nodes"] for k in poly["krylov"]])
+        print(json.dumps(row), flush=True)
+    # device time per class of one further solve of each Krylov variant
+    for v in variants[1:]:
+        eng.profile_enable(True)
+        eng.profile_set_period(1)
+        eng.profile_reset()
+        _, t = run(eng, v)
+        prof = {}
+        for cls in SPARSE_CLASSES + ("spmm_poly", "dot_finalize", "bicg_s", "bicg_xr", "bicg_p", "cocg_xr", "cocg_p", "gmres_ortho"):
+            total, n = eng.profile_get(cls)
+            if n:
+                prof[cls] = {"ms": round(total, 3), "launches": n}
+        eng.profile_enable(False)
+        print(json.dumps({"workload": "sparse", "solver": v[0], "solver_tol": v[1], "profiled_solve_ms": t, "classes": prof}), flush=True)
+    # k_spmm_poly on 64 columns, one node and all nodes, and k_spmm on the pencil of the same pattern
+    union = polynomial_union_csr(coeffs)
+    nnz, cplx, m, reps = len(union[1]), np.iscomplexobj(union[2][0]), 64, 20
+    f = fpm()
+    fk.feastdefault(f)
+    Zne, Wne = fk.feast_gcontour(center, radius, f)
+    rng = np.random.default_rng(7)
+    panel = 16.0 * N * m
+    eng.profile_enable(True)
+    eng.profile_set_period(1)
+    for ne in (1, nodes):
+        eng.set_polynomial_csr(*union)
+        eng.set_solver("direct")
+        eng.set_contour(Zne[:ne], Wne[:ne], 1.0)
+        dX = eng.upload(np.asfortranarray(rng.standard_normal((N, ne * m)) + 1j * rng.standard_normal((N, ne * m))))
+        eng.poly_node_products(dX, m)
+        eng.profile_reset()
+        for _ in range(reps):
+            eng.poly_node_products(dX, m)
+        t, n = eng.profile_get("spmm_poly")
+        traffic = ne * (nnz * (4.0 + (d + 1) * (16 if cplx else 8)) + 2 * panel)
+        row = {"what": "k_spmm_poly", "N": N, "m": m, "nodes": ne, "nnz": nnz, "degree": d, "complex_values": bool(cplx), "ms_per_launch": t / n,
+               "bytes_per_launch": traffic, "GB_per_s": traffic / (t / n * 1e-3) / 1e9, "gathered_bytes_per_launch": ne * nnz * 16.0 * m}
+        row["fraction_of_copy_ceiling_4800"] = row["GB_per_s"] / 4800.0
+        print(json.dumps(row), flush=True)
+    eng.set_problem(coeffs[0], coeffs[d])
+    dX = eng.upload(np.asfortranarray(rng.standard_normal((N, m)) + 1j * rng.standard_normal((N, m))))
+    eng.matmul(0, dX, m)
+    eng.profile_reset()
+    for _ in range(reps):
+        eng.matmul(0, dX, m)
+    t, n = eng.profile_get("spmm")
+    traffic = nnz * (4.0 + 2 * 8) + 2 * panel
+    print(json.dumps({"what": "k_spmm (pencil of the same pattern, one node)", "N": N, "m": m, "ms_per_launch": t / n, "bytes_per_launch": traffic,
+                      "GB_per_s": traffic / (t / n * 1e-3) / 1e9}), flush=True)
+    eng.profile_enable(False)
     eng.close()
 
 
