@@ -2860,18 +2860,6 @@ struct fh_ritz_ws {
     }
 };
 
-// Vp (ld x ld, zero padded) = block (i, j) of the r x r column-major host matrix V cut into ld-column blocks -- all of V for
-// r <= ld -- with row k of V scaled by rowscale[k].x when rowscale != null
-static void fh_pad_block(const cplx* V, int r, int ld, int i, int j, const cplx* rowscale, std::vector<cplx>& Vp) {
-    const int mi = std::min(ld, r - i * ld), mj = std::min(ld, r - j * ld);
-    Vp.assign((size_t)ld * ld, cmake(0, 0));
-    for (int c2 = 0; c2 < mj; ++c2)
-        for (int c1 = 0; c1 < mi; ++c1) {
-            const cplx v = V[(size_t)(j * ld + c2) * r + i * ld + c1];
-            Vp[(size_t)c2 * ld + c1] = rowscale ? cscale(v, rowscale[i * ld + c1].x) : v;
-        }
-}
-
 extern "C" int feasthip_ritz_residual_dev(feasthip_handle h, int64_t r64, const void* dQ, const void* V_host,
                                           const double* lambda_host, int64_t M, int normalize, int use_B, void* dX,
                                           double* res_host) {
@@ -2909,7 +2897,7 @@ extern "C" int feasthip_ritz_residual_dev(feasthip_handle h, int64_t r64, const 
             const int mj = std::min(ld, r - j * ld);
             for (int i = 0; i < npan; ++i) {
                 const int mi = std::min(ld, r - i * ld);
-                fh_pad_block(Vh, r, ld, i, j, nullptr, Vp);
+                fh_pad_block(Vh, r, r, ld, i, j, nullptr, Vp);
                 FH_CHECK(hipMemcpyAsync(dV, Vp.data(), Vp.size() * sizeof(cplx), hipMemcpyHostToDevice, h->stream));
                 fh_launch_to_panel((const cplx*)dQ + (size_t)i * ld * N, N, N, mi, Qp, ld, h->stream, fh_perm(h));
                 fh_prof_begin(h, "ritz");
@@ -2951,7 +2939,7 @@ extern "C" int feasthip_ritz_residual_dev(feasthip_handle h, int64_t r64, const 
         fh_prof_collect(h);
         return 0;
     }
-    fh_pad_block(Vh, r, ld, 0, 0, nullptr, Vp);
+    fh_pad_block(Vh, r, r, ld, 0, 0, nullptr, Vp);
     FH_CHECK(hipMemcpyAsync(dV, Vp.data(), Vp.size() * sizeof(cplx), hipMemcpyHostToDevice, h->stream));
     fh_launch_to_panel((const cplx*)dQ, N, N, r, Qp, ld, h->stream, fh_perm(h));
     fh_prof_begin(h, "ritz");
@@ -3158,7 +3146,7 @@ extern "C" int feasthip_rr_ritz_resident(feasthip_handle h, int64_t r64, const v
     cplx *dV = ws.dV, *part = ws.part, *ddots = ws.ddots;
     // V padded to ld x ld; the implicit basis is Q_proj D^-1, so X = Q_proj (D^-1 V)
     std::vector<cplx> Vp;
-    fh_pad_block((const cplx*)V_host, r, ld, 0, 0, h->rs_T.empty() ? nullptr : h->rs_T.data(), Vp);
+    fh_pad_block((const cplx*)V_host, r, r, ld, 0, 0, h->rs_T.empty() ? nullptr : h->rs_T.data(), Vp);
     if ((rc = fh_upload_small(h, dV, Vp.data(), Vp.size() * sizeof(cplx)))) return rc;
     h->rs_X = nullptr; h->rs_R = nullptr;
     fh_prof_begin(h, "ritz");

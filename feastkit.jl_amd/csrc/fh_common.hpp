@@ -122,8 +122,21 @@ struct fh_poly {
     void* coef[FH_POLY_MAX_DEGREE + 1] = {};
     double fro[FH_POLY_MAX_DEGREE + 1] = {};
 };
-// the coefficient pointers as a kernel argument
+// the coefficient pointers as a kernel argument (fh_poly_coef_ptrs below fills it; null past the degree)
 struct fh_poly_ptrs { const void* c[FH_POLY_MAX_DEGREE + 1]; };
+
+// A coefficient value (real or complex storage) as a complex number, and sum_{k <= d} coef(k) z^k by Horner: fully unrolled
+// from the compile-time top index TOP down, so a register array of TOP + 1 entries behind coef stays in registers and no
+// guarded-out step indexes past it (d <= TOP).
+__device__ inline cplx poly_val(cplx v) { return v; }
+__device__ inline cplx poly_val(double v) { return cmake(v, 0.0); }
+template <int TOP, typename F> __device__ __forceinline__ cplx fh_horner(int d, cplx z, F&& coef) {
+    cplx v = cmake(0, 0);
+#pragma unroll
+    for (int k = TOP; k >= 0; --k)
+        if (k <= d) v = cadd(cmul(v, z), coef(k));
+    return v;
+}
 
 // Per-(node,column) Krylov scalars, struct of arrays; each array is [nodes][ld].
 struct fh_krylov_scalars {
@@ -283,4 +296,23 @@ static inline int fh_pick_ld(int64_t m) {
     if (m <= 16) return 16;
     if (m <= 32) return 32;
     return 64;
+}
+
+// the coefficient table of a polynomial handle for a kernel launch
+static inline fh_poly_ptrs fh_poly_coef_ptrs(const feasthip_ctx* h) {
+    fh_poly_ptrs P;
+    for (int k = 0; k <= FH_POLY_MAX_DEGREE; ++k) P.c[k] = h->poly.coef[k];
+    return P;
+}
+
+// Vp (ld x ld, zero padded) = block (i, j) of the r x nc column-major host matrix V cut into ld x ld blocks -- all of V for
+// r, nc <= ld -- with row k of V scaled by rowscale[k].x when rowscale != null
+static inline void fh_pad_block(const cplx* V, int r, int64_t nc, int ld, int i, int64_t j, const cplx* rowscale, std::vector<cplx>& Vp) {
+    const int mi = r - i * ld < ld ? r - i * ld : ld, mj = (int)(nc - j * ld < ld ? nc - j * ld : ld);
+    Vp.assign((size_t)ld * ld, cmake(0, 0));
+    for (int c2 = 0; c2 < mj; ++c2)
+        for (int c1 = 0; c1 < mi; ++c1) {
+            const cplx v = V[(size_t)(j * ld + c2) * r + i * ld + c1];
+            Vp[(size_t)c2 * ld + c1] = rowscale ? cscale(v, rowscale[i * ld + c1].x) : v;
+        }
 }

@@ -2649,15 +2649,7 @@ __global__ __launch_bounds__(FH_BLOCK) void k_mf_assemble_poly(const int* __rest
         if (d < 0) d = ~d;
         const int k = src[q];
         cplx v = cmake(0, 0);
-        if (k >= 0) {
-#pragma unroll
-            for (int j = FH_POLY_MAX_DEGREE; j >= 0; --j)
-                if (j <= deg) {
-                    cplx a;
-                    if constexpr (sizeof(VT) == sizeof(cplx)) a = ((const cplx*)P.c[j])[k]; else a = cmake(((const double*)P.c[j])[k], 0.0);
-                    v = cadd(cmul(v, zz), a);
-                }
-        }
+        if (k >= 0) v = fh_horner<FH_POLY_MAX_DEGREE>(deg, zz, [&](int j) { return poly_val(((const VT*)P.c[j])[k]); });
         A[d] = cvt<T>(v);
     }
 }
@@ -2907,8 +2899,7 @@ static int mf_factor_t(feasthip_ctx* h, int nf, void* const* stores, int* const*
                 const int* dd = S->d_asm_dst + G.asm_begin;
                 const int* ss = S->d_asm_src + G.asm_begin;
                 if (h->kind == 3) {          // sparse polynomial handle: P(z_e) in place of z_e B - A, a profile class of its own
-                    fh_poly_ptrs pp;
-                    for (int k = 0; k <= FH_POLY_MAX_DEGREE; ++k) pp.c[k] = h->poly.coef[k];
+                    const fh_poly_ptrs pp = fh_poly_coef_ptrs(h);
                     fh_prof_end(h);
                     fh_prof_begin(h, "poly_mf_assemble");
                     if (cz) hipLaunchKernelGGL((k_mf_assemble_poly<cplx, T>), grid, block, 0, h->stream, dd, ss, cnt, base, P.work_elems, pp, h->poly.degree, dz);

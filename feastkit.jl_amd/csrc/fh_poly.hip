@@ -1,5 +1,11 @@
-// fh_poly.hip -- polynomial eigenproblems P(lambda) x = 0, P(lambda) = A_0 + lambda A_1 + ... + lambda^d A_d (dense
-// coefficients), on ONE N x N LU per quadrature node (gfx950).
+// fh_poly.hip -- polynomial eigenproblems P(lambda) x = 0, P(lambda) = A_0 + lambda A_1 + ... + lambda^d A_d, on ONE N x N
+// solve per quadrature node (gfx950).  Four flavours share this file:
+//   dense coefficients      the batched dense LU of P(z_e)                                  (feasthip_set_polynomial)
+//   sparse coefficients     the multifrontal LU of P(z_e), k_spmm_fan for the products      (feasthip_set_polynomial_csr)
+//   the projected method    N-row subspaces: k_spmm_horner, the residual-inverse sweep      (either kind of coefficients)
+//   Krylov solves on P(z)   BiCGStab / COCG / GMRES on the operator k_spmm_poly             (sparse coefficients)
+// The steps they share exist once: Horner over the coefficients is fh_horner (fh_common.hpp), the batched row gather of the
+// three SpMM kernels is POLY_ROW_GATHER, the kernels' coefficient table is fh_poly_coef_ptrs (fh_common.hpp).
 //
 // Replaces  feast_pep!                 src/dense/feast_dense.jl:715-772  (companion pencil :745-760, feast_gegv! on it :763)
 //           feast_gepev!/hepev!/sypev! src/dense/feast_dense.jl:946-979
@@ -39,8 +45,13 @@
 #define PD FH_POLY_MAX_DEGREE
 static_assert(FH_POLY_MAX_DEGREE == FEASTHIP_POLY_MAX_DEGREE, "degree bound of the ABI");
 
-__device__ inline cplx poly_val(cplx v) { return v; }
-__device__ inline cplx poly_val(double v) { return cmake(v, 0.0); }
+// KERNEL<VT, LD>(a) on the value type of the handle's CSR coefficients and the panel width
+#define POLY_LAUNCH_CSR(KERNEL, ld, grid, a)                                                                            \
+    fh_with_ld(ld, [&](auto L) {                                                                                         \
+        constexpr int LD = decltype(L)::value;                                                                           \
+        if (h->csr.is_complex) hipLaunchKernelGGL((KERNEL<cplx, LD>), grid, dim3(FH_BLOCK), 0, h->stream, a);            \
+        else hipLaunchKernelGGL((KERNEL<double, LD>), grid, dim3(FH_BLOCK), 0, h->stream, a);                            \
+    })
 
 // ---------------------------------------------------------------------------------------
 // S_e = P(z_e) for the nf matrices about to be factored, in one pass over the coefficients: a thread owns matrix elements,
@@ -54,20 +65,12 @@ __global__ __launch_bounds__(FH_BLOCK) void k_form_poly(fh_poly_ptrs P, int d, T
         cplx a[PD + 1];
 #pragma unroll
         for (int k = 0; k <= PD; ++k) a[k] = k <= d ? poly_val(((const VT*)P.c[k])[e]) : cmake(0, 0);
-        for (int q = 0; q < nf; ++q) {
-            const cplx zz = z[q];
-            cplx v = cmake(0, 0);
-#pragma unroll
-            for (int k = PD; k >= 0; --k)
-                if (k <= d) v = cadd(cmul(v, zz), a[k]);
-            LUs[q][e] = cvt<T>(v);
-        }
+        for (int q = 0; q < nf; ++q) LUs[q][e] = cvt<T>(fh_horner<PD>(d, z[q], [&](int k) { return a[k]; }));
     }
 }
 
 void fh_poly_form(feasthip_ctx* h, void* const* dlus, const cplx* dz, int nf, int prec) {
-    fh_poly_ptrs P;
-    for (int k = 0; k <= PD; ++k) P.c[k] = h->poly.coef[k];
+    const fh_poly_ptrs P = fh_poly_coef_ptrs(h);
     const int d = h->poly.degree;
     const size_t total = (size_t)h->dense.N * (size_t)h->dense.N;
     const dim3 grid((unsigned)std::min<size_t>(2048, (total + FH_BLOCK - 1) / FH_BLOCK)), block(FH_BLOCK);
@@ -93,6 +96,20 @@ void fh_poly_form(feasthip_ctx* h, void* const* dlus, const cplx* dz, int nf, in
 // Algorithmic traffic: nnz (4 + nout sizeof(VT)) of matrix, one X row of 16 LD B gathered per nonzero (cache hits for a
 // stencil), N LD 16 B per output written and as much read per accumulating output.
 // ---------------------------------------------------------------------------------------
+// One row of the row-slice SpMM kernels below (k_spmm_fan, k_spmm_horner, k_spmm_poly): LD lanes own the row, lane <-> column
+// c.  The nonzeros [k0, k1) go in batches of 4: the gathers of a batch are issued together (a slot past the row end gathers
+// the row's last column again and adds nothing), then the statements given last run for each nonzero, K its index and XV its
+// gathered X element, in CSR order.  A macro, not a function template taking the term as a callable: through a closure the
+// compiler orders the operands of the complex products the other way round and contracts a different half of each into the
+// FMA, so the sums would differ in the last bit from what these kernels have always returned.
+#define POLY_ROW_GATHER(LD_, colidx_, X_, k0_, k1_, c_, K, XV, ...)                                                     \
+    for (int kb_ = (k0_); kb_ < (k1_); kb_ += 4) {                                                                       \
+        cplx xs_[4];                                                                                                     \
+        _Pragma("unroll") for (int q_ = 0; q_ < 4; ++q_) xs_[q_] = (X_)[(size_t)(colidx_)[min(kb_ + q_, (k1_) - 1)] * (LD_) + (c_)]; \
+        _Pragma("unroll") for (int q_ = 0; q_ < 4; ++q_)                                                                 \
+            if (kb_ + q_ < (k1_)) { const int K = kb_ + q_; const cplx& XV = xs_[q_]; __VA_ARGS__ }                      \
+    }
+
 #define FH_FAN_MAX (PD + 1)
 struct fh_fan_args {
     const int* rowptr; const int* col;
@@ -116,20 +133,10 @@ __global__ __launch_bounds__(FH_BLOCK) void k_spmm_fan(fh_fan_args a) {
     cplx acc[FH_FAN_MAX];
 #pragma unroll
     for (int t = 0; t < FH_FAN_MAX; ++t) acc[t] = cmake(0, 0);
-    // batches of 4 nonzeros: the gathers are issued together, then the values are read and multiplied (a slot past the row end
-    // gathers the row's last column again and adds nothing)
-    for (int kb = k0; kb < k1; kb += 4) {
-        cplx xs[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) xs[q] = X[(size_t)colidx[min(kb + q, k1 - 1)] * LD + c];
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-            if (kb + q < k1) {
-#pragma unroll
-                for (int t = 0; t < FH_FAN_MAX; ++t)
-                    if (t < a.nout) acc[t] = cadd(acc[t], vmul(((const VT*)a.val[t])[kb + q], xs[q]));
-            }
-    }
+    POLY_ROW_GATHER(LD, colidx, X, k0, k1, c, k, x,
+        _Pragma("unroll") for (int t = 0; t < FH_FAN_MAX; ++t)
+            if (t < a.nout) acc[t] = cadd(acc[t], vmul(((const VT*)a.val[t])[k], x));
+    )
     const size_t e = (size_t)i * LD + c;
 #pragma unroll
     for (int t = 0; t < FH_FAN_MAX; ++t)
@@ -152,6 +159,8 @@ __global__ __launch_bounds__(FH_BLOCK) void k_poly_rhs(const cplx* __restrict__ 
         cplx dv[PD];
 #pragma unroll
         for (int p = 0; p < PD; ++p) dv[p] = p < nd ? D[(size_t)p * total + e] : cmake(0, 0);
+        // (Horner written out, not fh_horner<PD - 1>(nd - 1, ...): guarded by p <= nd - 1 the compiler keeps eight scalar
+        //  compares in the node loop that p < nd lets it hoist, and the kernel ran 5 % longer)
         for (int q = 0; q < ne; ++q) {
             const cplx zz = z[q];
             cplx v = cmake(0, 0);
@@ -225,11 +234,7 @@ __global__ __launch_bounds__(FH_BLOCK) void k_poly_residual(const cplx* __restri
         const cplx bx = use_B ? U[e] : xp;
         const cplx tt = T[e];
         s0 += cabs2(cadd(tt, cmul(l, bx)));
-        cplx v = cmake(0, 0);
-#pragma unroll
-        for (int k = PD; k >= 0; --k)
-            if (k <= d) v = cadd(cmul(v, l), PK[(size_t)k * total + e]);
-        s1 += cabs2(v);
+        s1 += cabs2(fh_horner<PD>(d, l, [&](int k) { return PK[(size_t)k * total + e]; }));
     }
     red[0][t] = s0; red[1][t] = s1; red[2][t] = s2;
     __syncthreads();
@@ -263,7 +268,7 @@ struct fh_horner_args {
     const cplx* X; const cplx* lam;   // N x LD panel, LD per-column values
     cplx* Y;
     int N, d;
-    const void* val[PD + 1];
+    fh_poly_ptrs val;
 };
 
 template <typename VT, int LD>
@@ -277,20 +282,9 @@ __global__ __launch_bounds__(FH_BLOCK) void k_spmm_horner(fh_horner_args a) {
     const cplx l = a.lam[c];
     const int k0 = a.rowptr[i], k1 = a.rowptr[i + 1];
     cplx acc = cmake(0, 0);
-    for (int kb = k0; kb < k1; kb += 4) {
-        cplx xs[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) xs[q] = X[(size_t)colidx[min(kb + q, k1 - 1)] * LD + c];
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-            if (kb + q < k1) {
-                cplx v = cmake(0, 0);
-#pragma unroll
-                for (int k = PD; k >= 0; --k)
-                    if (k <= a.d) v = cadd(cmul(v, l), poly_val(((const VT*)a.val[k])[kb + q]));
-                cfma(acc, v, xs[q]);
-            }
-    }
+    POLY_ROW_GATHER(LD, colidx, X, k0, k1, c, k, x,
+        cfma(acc, fh_horner<PD>(a.d, l, [&](int j) { return poly_val(((const VT*)a.val.c[j])[k]); }), x);
+    )
     a.Y[(size_t)i * LD + c] = acc;
 }
 
@@ -336,7 +330,7 @@ __global__ __launch_bounds__(FH_BLOCK) void k_poly_resinv_acc(const cplx* __rest
 #define FH_POLYOP_GRID_MAX 1024
 struct fh_polyop_args {
     const int* rowptr; const int* col;
-    const void* val[PD + 1];
+    fh_poly_ptrs val;
     int N, d, nodes;
     fh_polyop_call c;
     unsigned long long* counters;     // profiling: [0] active node-launches, [1] active column x vector passes (may be null)
@@ -344,6 +338,20 @@ struct fh_polyop_args {
 
 __device__ __forceinline__ cplx poly_ld_nt(const cplx* p) { return cmake(__builtin_nontemporal_load(&p->x), __builtin_nontemporal_load(&p->y)); }
 __device__ __forceinline__ void poly_st_nt(cplx* p, cplx v) { __builtin_nontemporal_store(v.x, &p->x); __builtin_nontemporal_store(v.y, &p->y); }
+
+// out[c] = the sum over the FH_BLOCK / LD threads t = c + k LD of a workgroup of their dsum, added through LDS in ascending k
+// (every thread of the workgroup calls it; red: FH_BLOCK elements)
+template <int LD> __device__ __forceinline__ void poly_column_sum(cplx* red, int t, cplx dsum, cplx* out) {
+    red[t] = dsum;
+    __syncthreads();
+    if (t < LD) {
+        cplx s = red[t];
+#pragma unroll
+        for (int k = 1; k < FH_BLOCK / LD; ++k) s = cadd(s, red[t + k * LD]);
+        out[t] = s;
+    }
+    __syncthreads();
+}
 
 template <typename VT, int LD>
 __global__ __launch_bounds__(FH_BLOCK) void k_spmm_poly(fh_polyop_args a) {
@@ -381,22 +389,15 @@ __global__ __launch_bounds__(FH_BLOCK) void k_spmm_poly(fh_polyop_args a) {
         for (int i = row_lo + slot * ROWS + r; i < row_hi; i += S * ROWS) {
             const int k0 = rowptr[i], k1 = rowptr[i + 1];
             cplx acc = cmake(0, 0);
-            // batches of 4 nonzeros: the gathers are issued together (a slot past the row end gathers the row's last column
-            // again and adds nothing), then per nonzero the d + 1 values are read and s = P(z_e)[i, j] formed by Horner
-            for (int kb = k0; kb < k1; kb += 4) {
-                cplx xs[4];
-#pragma unroll
-                for (int q = 0; q < 4; ++q) xs[q] = X[(size_t)colidx[min(kb + q, k1 - 1)] * LD + c];
-#pragma unroll
-                for (int q = 0; q < 4; ++q)
-                    if (kb + q < k1) {
-                        cplx v = cmake(0, 0);
-#pragma unroll
-                        for (int k = PD; k >= 0; --k)
-                            if (k <= a.d) v = cadd(cmul(v, z), poly_val(((const VT*)a.val[k])[kb + q]));
-                        cfma(acc, v, xs[q]);
-                    }
-            }
+            // per nonzero the d + 1 values are read and P(z_e)[i, j] formed by Horner.  (Written out, not fh_horner: with the
+            // helper inlined here the compiler contracts the <Y, Y> dot below the other way round, x x + (y y) for y y + (x x),
+            // and the Krylov solves would leave the bits they have had.)
+            POLY_ROW_GATHER(LD, colidx, X, k0, k1, c, k, x,
+                cplx v = cmake(0, 0);
+                _Pragma("unroll") for (int j = PD; j >= 0; --j)
+                    if (j <= a.d) v = cadd(cmul(v, z), poly_val(((const VT*)a.val.c[j])[k]));
+                cfma(acc, v, x);
+            )
             const size_t e = (size_t)i * LD + c;
             if (Bv) acc = csub(poly_ld_nt(Bv + e), acc);
             poly_st_nt(Y + e, acc);
@@ -405,31 +406,8 @@ __global__ __launch_bounds__(FH_BLOCK) void k_spmm_poly(fh_polyop_args a) {
             else if (mode == 3) d2.x += cabs2(acc);
             else if (mode == 4) d1 = cadd(d1, cmul(X[e], acc));          // unconjugated p^T (S p), COCG
         }
-        if (mode != 0) {
-            // column c: the ROWS threads t = c + k LD, added in ascending k
-            if (mode != 3) {
-                red[t] = d1;
-                __syncthreads();
-                if (t < LD) {
-                    cplx s = red[t];
-#pragma unroll
-                    for (int k = 1; k < ROWS; ++k) s = cadd(s, red[t + k * LD]);
-                    a.c.partial1[pbase + t] = s;
-                }
-                __syncthreads();
-            }
-            if (mode == 2 || mode == 3) {
-                red[t] = d2;
-                __syncthreads();
-                if (t < LD) {
-                    cplx s = red[t];
-#pragma unroll
-                    for (int k = 1; k < ROWS; ++k) s = cadd(s, red[t + k * LD]);
-                    a.c.partial2[pbase + t] = s;
-                }
-                __syncthreads();
-            }
-        }
+        if (mode != 0 && mode != 3) poly_column_sum<LD>(red, t, d1, a.c.partial1 + pbase);
+        if (mode == 2 || mode == 3) poly_column_sum<LD>(red, t, d2, a.c.partial2 + pbase);
     }
 }
 
@@ -443,17 +421,12 @@ int fh_launch_spmm_poly(feasthip_ctx* h, int ld, const fh_polyop_call& c) {
     fh_polyop_args a;
     memset(&a, 0, sizeof(a));
     a.rowptr = h->csr.rowptr; a.col = h->csr.col; a.N = (int)h->csr.N; a.d = h->poly.degree; a.nodes = c.nodes;
-    for (int k = 0; k <= a.d; ++k) a.val[k] = h->poly.coef[k];
+    a.val = fh_poly_coef_ptrs(h);
     a.c = c;
     a.counters = h->profiling ? h->d_counters : nullptr;
     const int nprow = fh_poly_op_nblk(a.N, ld);
-    const dim3 grid((unsigned)nprow), block(FH_BLOCK);
     fh_prof_begin(h, "spmm_poly");
-    fh_with_ld(ld, [&](auto L) {
-        constexpr int LD = decltype(L)::value;
-        if (h->csr.is_complex) hipLaunchKernelGGL((k_spmm_poly<cplx, LD>), grid, block, 0, h->stream, a);
-        else hipLaunchKernelGGL((k_spmm_poly<double, LD>), grid, block, 0, h->stream, a);
-    });
+    POLY_LAUNCH_CSR(k_spmm_poly, ld, dim3((unsigned)nprow), a);
     fh_prof_end(h);
     return nprow;
 }
@@ -468,8 +441,10 @@ static bool poly_krylov(const feasthip_ctx* h) {
     return h->solver == FEASTHIP_SOLVER_BICGSTAB || h->solver == FEASTHIP_SOLVER_COCG || h->solver == FEASTHIP_SOLVER_GMRES;
 }
 
-// What every feasthip_poly_* call needs: a polynomial handle in a configuration the structured solve covers -- the LU of
-// P(z_e), or for CSR coefficients a Krylov solver on it -- and 1 <= m <= maxm.  what: the entry point's name for the message.
+// What every feasthip_poly_* call needs, linearised or projected: a polynomial handle whose solver the solves with P(z_e)
+// cover -- FEASTHIP_SOLVER_LU (the dense LU, or the multifrontal one for CSR coefficients), or for CSR coefficients the plain
+// BiCGStab / COCG / GMRES on the operator -- complex128 factors, no adjoint, one rank, the whole contour, and 1 <= m <= maxm.
+// what: the entry point's name for the message.
 static int poly_check(feasthip_ctx* h, const char* what, int64_t m, int64_t maxm) {
     if (!h) return FEASTHIP_ERROR_INTERNAL;
     if (h->poisoned) { h->last_error = "handle poisoned by an earlier device failure: destroy it"; return FEASTHIP_ERROR_INTERNAL; }
@@ -487,6 +462,21 @@ static int poly_check(feasthip_ctx* h, const char* what, int64_t m, int64_t maxm
     if (why) { h->last_error = std::string(what) + ": " + why; return FEASTHIP_ERROR_FPM; }
     if (m <= 0 || m > maxm) { h->last_error = std::string(what) + ": block width out of range"; return FEASTHIP_ERROR_M0; }
     return 0;
+}
+
+// the end of an entry point: everything queued has run, the profile is read, a launch failure is reported
+static int poly_finish(feasthip_ctx* h) {
+    FH_CHECK(hipStreamSynchronize(h->stream));
+    fh_prof_collect(h);
+    FH_CHECK(hipGetLastError());
+    return 0;
+}
+
+// sum_k |lambda|^k ||A_k||_F, the scale of the backward errors
+static double poly_bwd_scale(const feasthip_ctx* h, double la) {
+    double scale = 0.0, pw = 1.0;
+    for (int k = 0; k <= h->poly.degree; ++k) { scale += pw * h->poly.fro[k]; pw *= la; }
+    return scale;
 }
 
 // small synchronous host -> device copy into a named workspace
@@ -533,18 +523,13 @@ static void poly_fan(feasthip_ctx* h, int ld, const cplx* X, const fh_fan_out* o
     fh_fan_args a;
     memset(&a, 0, sizeof(a));
     a.rowptr = h->csr.rowptr; a.col = h->csr.col; a.X = X; a.N = (int)h->csr.N; a.nout = nout;
+    const fh_poly_ptrs P = fh_poly_coef_ptrs(h);
     for (int t = 0; t < nout; ++t) {
-        a.val[t] = h->poly.coef[outs[t].k]; a.Y[t] = outs[t].Y;
+        a.val[t] = P.c[outs[t].k]; a.Y[t] = outs[t].Y;
         a.flags[t] = (outs[t].accumulate ? 1 : 0) | (outs[t].negate ? 2 : 0);
     }
-    const dim3 grid((unsigned)((a.N + FH_BLOCK / ld - 1) / (FH_BLOCK / ld))), block(FH_BLOCK);
     fh_prof_begin(h, "poly_spmm");
-#define FH_FAN_LAUNCH(VT_) \
-    do { if (ld == 64) hipLaunchKernelGGL((k_spmm_fan<VT_, 64>), grid, block, 0, h->stream, a); \
-         else if (ld == 32) hipLaunchKernelGGL((k_spmm_fan<VT_, 32>), grid, block, 0, h->stream, a); \
-         else hipLaunchKernelGGL((k_spmm_fan<VT_, 16>), grid, block, 0, h->stream, a); } while (0)
-    if (h->csr.is_complex) FH_FAN_LAUNCH(cplx); else FH_FAN_LAUNCH(double);
-#undef FH_FAN_LAUNCH
+    POLY_LAUNCH_CSR(k_spmm_fan, ld, dim3((unsigned)((a.N + FH_BLOCK / ld - 1) / (FH_BLOCK / ld))), a);
     fh_prof_end(h);
 }
 
@@ -586,39 +571,53 @@ static int poly_lin_product(feasthip_ctx* h, const poly_coefs& pc, int which, in
     return 0;
 }
 
-extern "C" int feasthip_set_polynomial(feasthip_handle h, int64_t N, int degree, int is_complex, const void* const* coeffs,
-                                       const int64_t* ld) {
+// The two setters' shared steps.  poly_set_check: the handle, N <= Nmax and the degree (what: the setter's name for the
+// message).  poly_set_begin: the handle's problem replaced by an empty polynomial of this size.  poly_sumsq: the sum of squares
+// of n doubles, for ||A_k||_F of the backward error (ingest arithmetic, once per problem).  poly_set_commit: the handle is a
+// polynomial one.
+static int poly_set_check(feasthip_ctx* h, const char* what, int64_t N, int64_t Nmax, int degree) {
     if (!h) return FEASTHIP_ERROR_INTERNAL;
     if (h->poisoned) { h->last_error = "handle poisoned by an earlier device failure: destroy it"; return FEASTHIP_ERROR_INTERNAL; }
-    if (N <= 0 || N > 65536) { h->last_error = "feasthip_set_polynomial: N out of range"; return FEASTHIP_ERROR_N; }
-    if (degree < 1 || degree > FEASTHIP_POLY_MAX_DEGREE) { h->last_error = "feasthip_set_polynomial: degree must be 1 .. FEASTHIP_POLY_MAX_DEGREE"; return FEASTHIP_ERROR_FPM; }
-    if (!coeffs || !ld) { h->last_error = "feasthip_set_polynomial: null argument"; return FEASTHIP_ERROR_N; }
-    for (int k = 0; k <= degree; ++k)
-        if (!coeffs[k] || ld[k] < N) { h->last_error = "feasthip_set_polynomial: bad coefficient pointer or leading dimension"; return FEASTHIP_ERROR_N; }
+    if (N <= 0 || N > Nmax) { h->last_error = std::string(what) + ": N out of range"; return FEASTHIP_ERROR_N; }
+    if (degree < 1 || degree > FEASTHIP_POLY_MAX_DEGREE) { h->last_error = std::string(what) + ": degree must be 1 .. FEASTHIP_POLY_MAX_DEGREE"; return FEASTHIP_ERROR_FPM; }
+    return 0;
+}
+static int poly_set_begin(feasthip_ctx* h, int64_t N, int degree, int is_complex) {
     FH_CHECK(hipSetDevice(h->device));
     FH_CHECK(hipStreamSynchronize(h->stream));
     fh_free_problem(h);
-    const size_t es = is_complex ? sizeof(cplx) : sizeof(double);
     h->dense.N = N; h->dense.is_complex = is_complex ? 1 : 0; h->dense.b_identity = 0;
     h->poly.degree = degree;
-    for (int k = 0; k <= degree; ++k) {
-        FH_CHECK(hipMalloc(&h->poly.coef[k], (size_t)N * N * es));
-        FH_CHECK(hipMemcpy2D(h->poly.coef[k], (size_t)N * es, coeffs[k], (size_t)ld[k] * es, (size_t)N * es, (size_t)N, hipMemcpyHostToDevice));
-        // ||A_k||_F for the backward error (ingest arithmetic, once per problem)
-        const double* v = (const double*)coeffs[k];
-        const size_t per = is_complex ? 2 : 1;
-        double s = 0.0;
-        for (int64_t j = 0; j < N; ++j) {
-            const double* col = v + (size_t)j * ld[k] * per;
-            double sj = 0.0;
-            for (size_t i = 0; i < (size_t)N * per; ++i) sj += col[i] * col[i];
-            s += sj;
-        }
-        h->poly.fro[k] = std::sqrt(s);
-    }
+    return 0;
+}
+static double poly_sumsq(const double* v, size_t n) {
+    double s = 0.0;
+    for (size_t i = 0; i < n; ++i) s += v[i] * v[i];
+    return s;
+}
+static int poly_set_commit(feasthip_ctx* h) {
     h->adjoint = 0;
     h->kind = 3;
     return 0;
+}
+
+extern "C" int feasthip_set_polynomial(feasthip_handle h, int64_t N, int degree, int is_complex, const void* const* coeffs,
+                                       const int64_t* ld) {
+    int rc = poly_set_check(h, "feasthip_set_polynomial", N, 65536, degree);
+    if (rc) return rc;
+    if (!coeffs || !ld) { h->last_error = "feasthip_set_polynomial: null argument"; return FEASTHIP_ERROR_N; }
+    for (int k = 0; k <= degree; ++k)
+        if (!coeffs[k] || ld[k] < N) { h->last_error = "feasthip_set_polynomial: bad coefficient pointer or leading dimension"; return FEASTHIP_ERROR_N; }
+    if ((rc = poly_set_begin(h, N, degree, is_complex))) return rc;
+    const size_t es = is_complex ? sizeof(cplx) : sizeof(double), per = is_complex ? 2 : 1;
+    for (int k = 0; k <= degree; ++k) {
+        FH_CHECK(hipMalloc(&h->poly.coef[k], (size_t)N * N * es));
+        FH_CHECK(hipMemcpy2D(h->poly.coef[k], (size_t)N * es, coeffs[k], (size_t)ld[k] * es, (size_t)N * es, (size_t)N, hipMemcpyHostToDevice));
+        double s = 0.0;          // column by column
+        for (int64_t j = 0; j < N; ++j) s += poly_sumsq((const double*)coeffs[k] + (size_t)j * ld[k] * per, (size_t)N * per);
+        h->poly.fro[k] = std::sqrt(s);
+    }
+    return poly_set_commit(h);
 }
 
 // Sparse coefficients on one CSR pattern (0-based, columns strictly increasing inside a row, so no duplicates): the multifrontal
@@ -626,10 +625,8 @@ extern "C" int feasthip_set_polynomial(feasthip_handle h, int64_t N, int degree,
 // the dense product.  The pattern is kept in the caller's order (no renumbering: the multifrontal plan brings its own).
 extern "C" int feasthip_set_polynomial_csr(feasthip_handle h, int64_t N, int degree, int is_complex, const int64_t* rowptr,
                                            const int64_t* col, const void* const* vals) {
-    if (!h) return FEASTHIP_ERROR_INTERNAL;
-    if (h->poisoned) { h->last_error = "handle poisoned by an earlier device failure: destroy it"; return FEASTHIP_ERROR_INTERNAL; }
-    if (N <= 0 || N > INT32_MAX / FH_MAX_LD / FEASTHIP_POLY_MAX_DEGREE) { h->last_error = "feasthip_set_polynomial_csr: N out of range"; return FEASTHIP_ERROR_N; }
-    if (degree < 1 || degree > FEASTHIP_POLY_MAX_DEGREE) { h->last_error = "feasthip_set_polynomial_csr: degree must be 1 .. FEASTHIP_POLY_MAX_DEGREE"; return FEASTHIP_ERROR_FPM; }
+    int rc = poly_set_check(h, "feasthip_set_polynomial_csr", N, INT32_MAX / FH_MAX_LD / FEASTHIP_POLY_MAX_DEGREE, degree);
+    if (rc) return rc;
     if (!rowptr || !vals) { h->last_error = "feasthip_set_polynomial_csr: null argument"; return FEASTHIP_ERROR_N; }
     if (rowptr[0] != 0) { h->last_error = "feasthip_set_polynomial_csr: rowptr[0] must be 0"; return FEASTHIP_ERROR_N; }
     for (int64_t i = 0; i < N; ++i)
@@ -649,12 +646,9 @@ extern "C" int feasthip_set_polynomial_csr(feasthip_handle h, int64_t N, int deg
         }
     }
     rp[N] = (int)nnz;
-    FH_CHECK(hipSetDevice(h->device));
-    FH_CHECK(hipStreamSynchronize(h->stream));
-    fh_free_problem(h);
+    if ((rc = poly_set_begin(h, N, degree, is_complex))) return rc;
     const size_t es = is_complex ? sizeof(cplx) : sizeof(double);
-    h->dense.N = N; h->dense.is_complex = is_complex ? 1 : 0; h->dense.b_identity = 0;
-    h->poly.degree = degree; h->poly.sparse = 1;
+    h->poly.sparse = 1;
     fh_csr& c = h->csr;
     c.N = N; c.nnz = nnz; c.is_complex = is_complex ? 1 : 0; c.b_identity = 0;
     FH_CHECK(hipMalloc((void**)&c.rowptr, ((size_t)N + 1) * sizeof(int)));
@@ -664,16 +658,10 @@ extern "C" int feasthip_set_polynomial_csr(feasthip_handle h, int64_t N, int deg
     for (int k = 0; k <= degree; ++k) {
         FH_CHECK(hipMalloc(&h->poly.coef[k], std::max<size_t>(1, (size_t)nnz) * es));
         if (nnz) FH_CHECK(hipMemcpy(h->poly.coef[k], vals[k], (size_t)nnz * es, hipMemcpyHostToDevice));
-        // ||A_k||_F for the backward error (ingest arithmetic, once per problem; the explicit zeros add nothing)
-        const double* v = (const double*)vals[k];
-        double s = 0.0;
-        for (size_t i = 0; i < (size_t)nnz * (is_complex ? 2 : 1); ++i) s += v[i] * v[i];
-        h->poly.fro[k] = std::sqrt(s);
+        h->poly.fro[k] = std::sqrt(poly_sumsq((const double*)vals[k], (size_t)nnz * (is_complex ? 2 : 1)));      // (the explicit zeros add nothing)
     }
     h->host_rowptr.swap(rp); h->host_col.swap(cl);
-    h->adjoint = 0;
-    h->kind = 3;
-    return 0;
+    return poly_set_commit(h);
 }
 
 // Krylov solves P(z_e) Y_e = RHS for the nodes z (one right-hand-side panel shared by all of them), from a zero start, under the
@@ -698,9 +686,9 @@ static int poly_krylov_nodes(feasthip_ctx* h, int ld, int m, const std::vector<c
     return 0;
 }
 
-// The N x N solves, a dispatch on the handle's solver: the dense LU of P(z_e), for sparse coefficients the multifrontal one
-// through the factor cache of the sparse direct solver (same slots, same matching by z), or the Krylov solves above
-static int poly_lu_single(feasthip_ctx* h, int ld, int m, cplx z, const cplx* Rhs, cplx* Y, int* status, int64_t* nfact, poly_iters& it) {
+// Y = P(z)^-1 Rhs under the handle's solver: the Krylov solves above, else the dense LU of P(z), for sparse coefficients the
+// multifrontal one through the factor cache of the sparse direct solver (same slots, same matching by z)
+static int poly_solve_single(feasthip_ctx* h, int ld, int m, cplx z, const cplx* Rhs, cplx* Y, int* status, int64_t* nfact, poly_iters& it) {
     if (poly_krylov(h)) {
         std::vector<int> st;
         const int rc = poly_krylov_nodes(h, ld, m, std::vector<cplx>(1, z), Rhs, (size_t)h->dense.N * ld, Y, st, it);
@@ -709,9 +697,9 @@ static int poly_lu_single(feasthip_ctx* h, int ld, int m, cplx z, const cplx* Rh
     }
     return h->poly.sparse ? fh_banded_solve_single(h, ld, m, z, Rhs, Y, status, nfact) : fh_dense_lu_solve_single(h, ld, m, z, Rhs, Y, status, nfact);
 }
-// (rhs_stride: `panel` for one right-hand side panel per node, 0 for one panel shared by all nodes -- the only form the Krylov
-//  drivers take)
-static int poly_lu_nodes(feasthip_ctx* h, int ld, int m, int ne, const cplx* RHS, size_t rhs_stride, size_t panel, cplx* Y, std::vector<int>& status, int64_t* nfact, poly_iters& it) {
+// The same for every contour node, Y_e = P(z_e)^-1 RHS_e (rhs_stride: `panel` for one right-hand side panel per node, 0 for
+// one panel shared by all nodes -- the only form the Krylov drivers take)
+static int poly_solve_nodes(feasthip_ctx* h, int ld, int m, int ne, const cplx* RHS, size_t rhs_stride, size_t panel, cplx* Y, std::vector<int>& status, int64_t* nfact, poly_iters& it) {
     if (poly_krylov(h)) {
         if (rhs_stride != 0) { h->last_error = "internal: a Krylov solver takes one right-hand-side panel shared by the nodes"; return FEASTHIP_ERROR_INTERNAL; }
         return poly_krylov_nodes(h, ld, m, h->zne, RHS, panel, Y, status, it);
@@ -761,15 +749,13 @@ extern "C" int feasthip_poly_solve_dev(feasthip_handle h, double z_re, double z_
         fh_launch_to_panel((const cplx*)dR + (size_t)c0 * N, N, N, m, Rhs, ld, h->stream);
         int status = 0;
         int64_t nfact = 0;
-        if ((rc = poly_lu_single(h, ld, m, cmake(z_re, z_im), Rhs, Y, &status, &nfact, it))) return rc;
+        if ((rc = poly_solve_single(h, ld, m, cmake(z_re, z_im), Rhs, Y, &status, &nfact, it))) return rc;
         if (poly_krylov(h)) rec.panel(it, c0, m);
         fh_launch_from_panel(Y, ld, N, m, (cplx*)dY + (size_t)c0 * N, N, h->stream);
         if (stats) stats->factorizations += nfact;
         worst = std::max(worst, status);
     }
-    FH_CHECK(hipStreamSynchronize(h->stream));
-    fh_prof_collect(h);
-    FH_CHECK(hipGetLastError());
+    if ((rc = poly_finish(h))) return rc;
     if (poly_krylov(h)) rec.publish(h, it, stats);
     if (stats) stats->seconds_total = poly_now() - t0;
     return worst;
@@ -834,7 +820,7 @@ extern "C" int feasthip_poly_contour_apply_dev(feasthip_handle h, int64_t m64, c
         std::vector<int> status;
         int64_t nfact = 0;
         poly_iters none;
-        if ((rc = poly_lu_nodes(h, ld, m, ne, RHS, panel, panel, Y, status, &nfact, none))) return rc;
+        if ((rc = poly_solve_nodes(h, ld, m, ne, RHS, panel, panel, Y, status, &nfact, none))) return rc;
         fh_prof_begin(h, "poly_expand");
         hipLaunchKernelGGL(k_poly_expand_sum, grid, block, 0, h->stream, Y, panel, Rs, d, dzw, dzw + ne, ne, OUT, panel);
         fh_prof_end(h);
@@ -842,9 +828,7 @@ extern "C" int feasthip_poly_contour_apply_dev(feasthip_handle h, int64_t m64, c
         if (stats) stats->factorizations += nfact;
         if (node_status) for (int e = 0; e < ne; ++e) node_status[e] = std::max(node_status[e], status[e]);
     }
-    FH_CHECK(hipStreamSynchronize(h->stream));
-    fh_prof_collect(h);
-    FH_CHECK(hipGetLastError());
+    if ((rc = poly_finish(h))) return rc;
     if (stats) stats->seconds_total = poly_now() - t0;
     return 0;
 }
@@ -877,10 +861,7 @@ static int poly_node_products(feasthip_ctx* h, int which, int64_t m64, const cpl
     c.nodes = ne; c.m = m;
     fh_launch_spmm_poly(h, ld, c);
     for (int e = 0; e < ne; ++e) fh_launch_from_panel(Ys + (size_t)e * panel, ld, N, m, dY + (size_t)e * blockN, N, h->stream);
-    FH_CHECK(hipStreamSynchronize(h->stream));
-    fh_prof_collect(h);
-    FH_CHECK(hipGetLastError());
-    return 0;
+    return poly_finish(h);
 }
 
 // Y = A_lin X (which 0) or B_lin X (which 1), dN x m column-major; which 2, 3, 4: poly_node_products
@@ -904,8 +885,48 @@ extern "C" int feasthip_poly_matmul_dev(feasthip_handle h, int which, int64_t m6
         if ((rc = poly_lin_product(h, pc, which, ld, Xs, Ws))) return rc;
         fh_launch_from_panel(Ws, ld, (int)dN, m, (cplx*)dY + (size_t)c0 * dN, dN, h->stream);
     }
-    FH_CHECK(hipStreamSynchronize(h->stream));
-    fh_prof_collect(h);
+    return poly_finish(h);
+}
+
+// The blocked Gram projection of both methods: out[w] = Q^H W_w, w < nops (raw products, r x r column-major on the host), Q:
+// rows x r column-major on the device, by 64-column panels.  Per block column j, form(ld, Qj, W) writes the nops product panels
+// W + w rows ld of the staged panel Q_j; then per block (i, j) one Gram launch over the rows per product, ONE download and the
+// scatter into the host blocks.  buf: the entry point's workspace names for Q_i, Q_j, the products and the Gram blocks.
+template <typename F>
+static int poly_project_blocks(feasthip_ctx* h, const char* const (&buf)[4], int64_t rows, int r, int nops, const cplx* dQ,
+                               cplx* const* out, F&& form) {
+    const int ld = r > FH_MAX_LD ? FH_MAX_LD : fh_pick_ld(r), npan = (r + ld - 1) / ld;
+    const size_t tall = (size_t)rows * ld, g2 = (size_t)ld * ld;
+    int rc;
+    cplx *Qi, *Qj, *W, *G, *gw;
+    if ((rc = fh_buf(h, buf[0], tall, &Qi))) return rc;
+    if ((rc = fh_buf(h, buf[1], tall, &Qj))) return rc;
+    if ((rc = fh_buf(h, buf[2], nops * tall, &W))) return rc;
+    if ((rc = fh_buf(h, buf[3], nops * g2, &G))) return rc;
+    if ((rc = fh_buf(h, "gram_work", fh_gram_work_elems(ld), &gw))) return rc;
+    std::vector<cplx> Gh(nops * g2);
+    for (int j = 0; j < npan; ++j) {
+        const int mj = std::min(ld, r - j * ld);
+        fh_launch_to_panel(dQ + (size_t)j * ld * rows, rows, (int)rows, mj, Qj, ld, h->stream);
+        if ((rc = form(ld, Qj, W))) return rc;
+        for (int i = 0; i < npan; ++i) {
+            const int mi = std::min(ld, r - i * ld);
+            const cplx* Ql = Qj;
+            if (i != j) { fh_launch_to_panel(dQ + (size_t)i * ld * rows, rows, (int)rows, mi, Qi, ld, h->stream); Ql = Qi; }
+            for (int w = 0; w < nops; ++w) {
+                fh_prof_begin(h, "gram");
+                fh_launch_gram(Ql, W + w * tall, (int)rows, ld, 0, gw, G + w * g2, h->stream);
+                fh_prof_end(h);
+            }
+            FH_CHECK(hipMemcpyAsync(Gh.data(), G, Gh.size() * sizeof(cplx), hipMemcpyDeviceToHost, h->stream));
+            FH_CHECK(hipStreamSynchronize(h->stream));
+            for (int w = 0; w < nops; ++w)
+                for (int c2 = 0; c2 < mj; ++c2)
+                    for (int c1 = 0; c1 < mi; ++c1)
+                        out[w][(size_t)(j * ld + c2) * r + i * ld + c1] = Gh[w * g2 + (size_t)c2 * ld + c1];
+        }
+    }
+    fh_prof_collect(h);          // (every block ended on a synchronisation)
     FH_CHECK(hipGetLastError());
     return 0;
 }
@@ -917,44 +938,43 @@ extern "C" int feasthip_poly_project_dev(feasthip_handle h, int64_t r64, const v
     if (rc) return rc;
     if (!dQ || !Aq_host || !Sq_host) { h->last_error = "feasthip_poly_project_dev: null argument"; return FEASTHIP_ERROR_INTERNAL; }
     FH_CHECK(hipSetDevice(h->device));
-    const int N = (int)h->dense.N, d = h->poly.degree, r = (int)r64;
-    const int64_t dN = (int64_t)d * N;
-    const int ld = r > FH_MAX_LD ? FH_MAX_LD : fh_pick_ld(r), npan = (r + ld - 1) / ld;
-    const size_t tall = (size_t)dN * ld, g2 = (size_t)ld * ld;
+    const int64_t dN = h->dense.N * h->poly.degree;
     poly_coefs pc;
     if ((rc = pc.acquire(h))) return rc;
-    cplx *Qi, *Qj, *W, *G, *gw;
-    if ((rc = fh_buf(h, "pp_Qi", tall, &Qi))) return rc;
-    if ((rc = fh_buf(h, "pp_Qj", tall, &Qj))) return rc;
-    if ((rc = fh_buf(h, "pp_W", 2 * tall, &W))) return rc;
-    if ((rc = fh_buf(h, "pp_G", 2 * g2, &G))) return rc;
-    if ((rc = fh_buf(h, "gram_work", fh_gram_work_elems(ld), &gw))) return rc;
     cplx* const out[2] = {(cplx*)Aq_host, (cplx*)Sq_host};
-    std::vector<cplx> Gh(2 * g2);
-    for (int j = 0; j < npan; ++j) {
-        const int mj = std::min(ld, r - j * ld);
-        fh_launch_to_panel((const cplx*)dQ + (size_t)j * ld * dN, dN, (int)dN, mj, Qj, ld, h->stream);
+    return poly_project_blocks(h, {"pp_Qi", "pp_Qj", "pp_W", "pp_G"}, dN, (int)r64, 2, (const cplx*)dQ, out, [&](int ld, const cplx* Qj, cplx* W) {
         for (int which = 0; which < 2; ++which)
-            if ((rc = poly_lin_product(h, pc, which, ld, Qj, W + which * tall))) return rc;
-        for (int i = 0; i < npan; ++i) {
-            const int mi = std::min(ld, r - i * ld);
-            const cplx* Ql = Qj;
-            if (i != j) { fh_launch_to_panel((const cplx*)dQ + (size_t)i * ld * dN, dN, (int)dN, mi, Qi, ld, h->stream); Ql = Qi; }
-            for (int which = 0; which < 2; ++which) {
-                fh_prof_begin(h, "gram");
-                fh_launch_gram(Ql, W + which * tall, (int)dN, ld, 0, gw, G + which * g2, h->stream);
-                fh_prof_end(h);
-            }
-            FH_CHECK(hipMemcpyAsync(Gh.data(), G, Gh.size() * sizeof(cplx), hipMemcpyDeviceToHost, h->stream));
-            FH_CHECK(hipStreamSynchronize(h->stream));
-            for (int which = 0; which < 2; ++which)
-                for (int c2 = 0; c2 < mj; ++c2)
-                    for (int c1 = 0; c1 < mi; ++c1)
-                        out[which][(size_t)(j * ld + c2) * r + i * ld + c1] = Gh[which * g2 + (size_t)c2 * ld + c1];
+            if (const int e = poly_lin_product(h, pc, which, ld, Qj, W + (size_t)which * dN * ld)) return e;
+        return 0;
+    });
+}
+
+// The Ritz back-transform of both methods, block column j of X = Q V on `rows`-row panels: ws.X = sum_i Q_i V_ij (Q: rows x r
+// column-major on the device, V: r x nc column-major on the host, V_ij uploaded as a zero-padded ld x ld block into the
+// workspace ws.vname), its first nnorm columns scaled to unit length, its mj columns written to block column j of dX.
+struct poly_ritz_ws { const char* vname; cplx *Q, *X, *T, *part, *dots; };
+static int poly_ritz_vectors(feasthip_ctx* h, const poly_coefs& pc, const poly_ritz_ws& ws, int64_t rows, int r, int64_t nc, int ld,
+                             int64_t j, const cplx* dQ, const cplx* Vh, int mj, int nnorm, cplx* dX) {
+    std::vector<cplx> Vp;
+    for (int i = 0; i < (r + ld - 1) / ld; ++i) {
+        fh_pad_block(Vh, r, nc, ld, i, j, nullptr, Vp);
+        cplx* dV;
+        const int rc = poly_upload(h, ws.vname, Vp, &dV);
+        if (rc) return rc;
+        fh_launch_to_panel(dQ + (size_t)i * ld * rows, rows, (int)rows, std::min(ld, r - i * ld), ws.Q, ld, h->stream);
+        fh_prof_begin(h, "ritz");
+        if (i == 0) fh_launch_small_matmul(ws.Q, dV, (int)rows, ld, ws.X, h->stream);
+        else {
+            fh_launch_small_matmul(ws.Q, dV, (int)rows, ld, ws.T, h->stream);
+            fh_launch_axpy_cols(ws.X, ws.T, pc.minus, (int)rows, ld, h->stream);          // X += T
         }
+        fh_prof_end(h);
     }
-    fh_prof_collect(h);
-    FH_CHECK(hipGetLastError());
+    if (nnorm > 0) {
+        fh_launch_dot_cols(ws.X, ws.X, (int)rows, ld, ws.part, ws.dots, h->stream);
+        fh_launch_normalize_cols(ws.X, ws.dots, (int)rows, ld, nnorm, h->stream);
+    }
+    fh_launch_from_panel(ws.X, ld, (int)rows, mj, dX + (size_t)j * ld * rows, rows, h->stream);
     return 0;
 }
 
@@ -987,34 +1007,13 @@ extern "C" int feasthip_poly_ritz_residual_dev(feasthip_handle h, int64_t r64, c
     if ((rc = fh_buf(h, "pr_dots", (size_t)ld, &ddots))) return rc;
     if ((rc = fh_buf(h, "pr_rpart", (size_t)nblk * 3 * ld, &rpart))) return rc;
     if ((rc = fh_buf(h, "pr_rsum", (size_t)3 * ld, &rsum))) return rc;
-    const cplx* Vh = (const cplx*)V_host;
+    const poly_ritz_ws ws{"pr_V", Qp, Xp, Tp, part, ddots};
     const cplx* lamh = (const cplx*)lambda;
-    std::vector<cplx> Vp((size_t)ld * ld), lamp(ld);
+    std::vector<cplx> lamp(ld);
     std::vector<double> sums(3 * (size_t)ld);
     for (int j = 0; j < npan; ++j) {
-        const int mj = std::min(ld, r - j * ld);
-        for (int i = 0; i < npan; ++i) {
-            const int mi = std::min(ld, r - i * ld);
-            std::fill(Vp.begin(), Vp.end(), cmake(0, 0));
-            for (int c2 = 0; c2 < mj; ++c2)
-                for (int c1 = 0; c1 < mi; ++c1) Vp[(size_t)c2 * ld + c1] = Vh[(size_t)(j * ld + c2) * r + i * ld + c1];
-            cplx* dV;
-            if ((rc = poly_upload(h, "pr_V", Vp, &dV))) return rc;
-            fh_launch_to_panel((const cplx*)dQ + (size_t)i * ld * dN, dN, (int)dN, mi, Qp, ld, h->stream);
-            fh_prof_begin(h, "ritz");
-            if (i == 0) fh_launch_small_matmul(Qp, dV, (int)dN, ld, Xp, h->stream);
-            else {
-                fh_launch_small_matmul(Qp, dV, (int)dN, ld, Tp, h->stream);
-                fh_launch_axpy_cols(Xp, Tp, pc.minus, (int)dN, ld, h->stream);          // X += T
-            }
-            fh_prof_end(h);
-        }
-        const int Mj = std::max(0, std::min(mj, (int)M - j * ld));
-        if (normalize && Mj > 0) {
-            fh_launch_dot_cols(Xp, Xp, (int)dN, ld, part, ddots, h->stream);
-            fh_launch_normalize_cols(Xp, ddots, (int)dN, ld, Mj, h->stream);
-        }
-        fh_launch_from_panel(Xp, ld, (int)dN, mj, (cplx*)dX + (size_t)j * ld * dN, dN, h->stream);
+        const int mj = std::min(ld, r - j * ld), Mj = std::max(0, std::min(mj, (int)M - j * ld));
+        if ((rc = poly_ritz_vectors(h, pc, ws, dN, r, r, ld, j, (const cplx*)dQ, (const cplx*)V_host, mj, normalize ? Mj : 0, (cplx*)dX))) return rc;
         if (Mj > 0 && (res || backward_error)) {
             if (h->poly.sparse) {
                 if ((rc = poly_residual_fan(h, ld, use_B != 0, Xp, Tl, U, PK))) return rc;
@@ -1037,18 +1036,13 @@ extern "C" int feasthip_poly_ritz_residual_dev(feasthip_handle h, int64_t r64, c
                 const double la = std::hypot(lamp[c].x, lamp[c].y);
                 if (res) res[j * ld + c] = std::sqrt(sums[c]) / std::max(la, 1.0);
                 if (backward_error) {
-                    double scale = 0.0, pw = 1.0;
-                    for (int k = 0; k <= d; ++k) { scale += pw * h->poly.fro[k]; pw *= la; }
-                    const double den = scale * std::sqrt(sums[2 * ld + c]);
+                    const double den = poly_bwd_scale(h, la) * std::sqrt(sums[2 * ld + c]);
                     backward_error[j * ld + c] = den > 0.0 ? std::sqrt(sums[ld + c]) / den : 0.0;
                 }
             }
         }
     }
-    FH_CHECK(hipStreamSynchronize(h->stream));
-    fh_prof_collect(h);
-    FH_CHECK(hipGetLastError());
-    return 0;
+    return poly_finish(h);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1064,14 +1058,9 @@ static int poly_eval_panel(feasthip_ctx* h, const poly_coefs& pc, int ld, const 
         fh_horner_args a;
         memset(&a, 0, sizeof(a));
         a.rowptr = h->csr.rowptr; a.col = h->csr.col; a.X = X; a.lam = dlam; a.Y = R; a.N = N; a.d = d;
-        for (int k = 0; k <= d; ++k) a.val[k] = h->poly.coef[k];
-        const dim3 grid((unsigned)((N + FH_BLOCK / ld - 1) / (FH_BLOCK / ld))), block(FH_BLOCK);
+        a.val = fh_poly_coef_ptrs(h);
         fh_prof_begin(h, "poly_horner");
-        fh_with_ld(ld, [&](auto L) {
-            constexpr int LD = decltype(L)::value;
-            if (h->csr.is_complex) hipLaunchKernelGGL((k_spmm_horner<cplx, LD>), grid, block, 0, h->stream, a);
-            else hipLaunchKernelGGL((k_spmm_horner<double, LD>), grid, block, 0, h->stream, a);
-        });
+        POLY_LAUNCH_CSR(k_spmm_horner, ld, dim3((unsigned)((N + FH_BLOCK / ld - 1) / (FH_BLOCK / ld))), a);
         fh_prof_end(h);
         return 0;
     }
@@ -1118,10 +1107,7 @@ extern "C" int feasthip_poly_eval_cols_dev(feasthip_handle h, int64_t m64, const
         if ((rc = poly_eval_panel(h, pc, ld, dlam, Xs, W, R))) return rc;
         fh_launch_from_panel(R, ld, N, m, (cplx*)dR + (size_t)c0 * N, N, h->stream);
     }
-    FH_CHECK(hipStreamSynchronize(h->stream));
-    fh_prof_collect(h);
-    FH_CHECK(hipGetLastError());
-    return 0;
+    return poly_finish(h);
 }
 
 // The contour step of the projected method on an N x m block.
@@ -1182,7 +1168,7 @@ extern "C" int feasthip_poly_resinv_apply_dev(feasthip_handle h, int64_t m64, co
         }
         std::vector<int> status;
         int64_t nfact = 0;
-        if ((rc = poly_lu_nodes(h, ld, m, ne, rhs, 0, panel, Y, status, &nfact, it))) return rc;
+        if ((rc = poly_solve_nodes(h, ld, m, ne, rhs, 0, panel, Y, status, &nfact, it))) return rc;
         if (poly_krylov(h)) rec.panel(it, c0, m);
         fh_prof_begin(h, "poly_resinv");
         hipLaunchKernelGGL(k_poly_resinv_acc, dim3(fh_vec_nblk(N, ld)), dim3(FH_BLOCK), 0, h->stream, sg ? Xs : (const cplx*)nullptr, Y, panel, dT, ne, ld, Q, panel);
@@ -1191,9 +1177,7 @@ extern "C" int feasthip_poly_resinv_apply_dev(feasthip_handle h, int64_t m64, co
         if (stats) stats->factorizations += nfact;
         if (node_status) for (int e = 0; e < ne; ++e) node_status[e] = std::max(node_status[e], status[e]);
     }
-    FH_CHECK(hipStreamSynchronize(h->stream));
-    fh_prof_collect(h);
-    FH_CHECK(hipGetLastError());
+    if ((rc = poly_finish(h))) return rc;
     if (poly_krylov(h)) rec.publish(h, it, stats);
     if (stats) stats->seconds_total = poly_now() - t0;
     return 0;
@@ -1206,49 +1190,19 @@ extern "C" int feasthip_poly_project_reduced_dev(feasthip_handle h, int64_t r64,
     if (rc) return rc;
     if (!dQ || !Ahat_host) { h->last_error = "feasthip_poly_project_reduced_dev: null argument"; return FEASTHIP_ERROR_INTERNAL; }
     FH_CHECK(hipSetDevice(h->device));
-    const int N = (int)h->dense.N, d = h->poly.degree, r = (int)r64;
-    const int ld = r > FH_MAX_LD ? FH_MAX_LD : fh_pick_ld(r), npan = (r + ld - 1) / ld;
-    const size_t panel = (size_t)N * ld, g2 = (size_t)ld * ld;
+    const int N = (int)h->dense.N, d = h->poly.degree;
     poly_coefs pc;
     if ((rc = pc.acquire(h))) return rc;
-    cplx *Qi, *Qj, *W, *G, *gw;
-    if ((rc = fh_buf(h, "pq_Qi", panel, &Qi))) return rc;
-    if ((rc = fh_buf(h, "pq_Qj", panel, &Qj))) return rc;
-    if ((rc = fh_buf(h, "pq_W", (size_t)(d + 1) * panel, &W))) return rc;
-    if ((rc = fh_buf(h, "pq_G", (size_t)(d + 1) * g2, &G))) return rc;
-    if ((rc = fh_buf(h, "gram_work", fh_gram_work_elems(ld), &gw))) return rc;
-    cplx* out = (cplx*)Ahat_host;
-    std::vector<cplx> Gh((size_t)(d + 1) * g2);
-    for (int j = 0; j < npan; ++j) {
-        const int mj = std::min(ld, r - j * ld);
-        fh_launch_to_panel((const cplx*)dQ + (size_t)j * ld * N, N, N, mj, Qj, ld, h->stream);
-        if (h->poly.sparse) {
-            fh_fan_out outs[FH_FAN_MAX];
-            for (int k = 0; k <= d; ++k) outs[k] = fh_fan_out{k, W + (size_t)k * panel, false, false};
-            poly_fan(h, ld, Qj, outs, d + 1);
-        } else {
-            for (int k = 0; k <= d; ++k) poly_product(h, pc, ld, k, Qj, W + (size_t)k * panel, false, false);
-        }
-        for (int i = 0; i < npan; ++i) {
-            const int mi = std::min(ld, r - i * ld);
-            const cplx* Ql = Qj;
-            if (i != j) { fh_launch_to_panel((const cplx*)dQ + (size_t)i * ld * N, N, N, mi, Qi, ld, h->stream); Ql = Qi; }
-            for (int k = 0; k <= d; ++k) {
-                fh_prof_begin(h, "gram");
-                fh_launch_gram(Ql, W + (size_t)k * panel, N, ld, 0, gw, G + (size_t)k * g2, h->stream);
-                fh_prof_end(h);
-            }
-            FH_CHECK(hipMemcpyAsync(Gh.data(), G, Gh.size() * sizeof(cplx), hipMemcpyDeviceToHost, h->stream));
-            FH_CHECK(hipStreamSynchronize(h->stream));
-            for (int k = 0; k <= d; ++k)
-                for (int c2 = 0; c2 < mj; ++c2)
-                    for (int c1 = 0; c1 < mi; ++c1)
-                        out[(size_t)k * r * r + (size_t)(j * ld + c2) * r + i * ld + c1] = Gh[(size_t)k * g2 + (size_t)c2 * ld + c1];
-        }
-    }
-    fh_prof_collect(h);
-    FH_CHECK(hipGetLastError());
-    return 0;
+    cplx* out[PD + 1];
+    for (int k = 0; k <= d; ++k) out[k] = (cplx*)Ahat_host + (size_t)k * r64 * r64;
+    return poly_project_blocks(h, {"pq_Qi", "pq_Qj", "pq_W", "pq_G"}, N, (int)r64, d + 1, (const cplx*)dQ, out, [&](int ld, const cplx* Qj, cplx* W) {
+        const size_t panel = (size_t)N * ld;
+        fh_fan_out outs[FH_FAN_MAX];
+        for (int k = 0; k <= d; ++k) outs[k] = fh_fan_out{k, W + (size_t)k * panel, false, false};
+        if (h->poly.sparse) poly_fan(h, ld, Qj, outs, d + 1);
+        else for (int k = 0; k <= d; ++k) poly_product(h, pc, ld, k, Qj, outs[k].Y, false, false);
+        return 0;
+    });
 }
 
 // X = Q Y (N x ncand; Q: N x r, Y: r x ncand column-major on the host), every column scaled to unit length, and
@@ -1261,9 +1215,9 @@ extern "C" int feasthip_poly_ritz_eval_dev(feasthip_handle h, int64_t r64, const
     if (!dQ || !Y_host || !dX || dQ == dX || (backward_error && !theta)) { h->last_error = "feasthip_poly_ritz_eval_dev: null argument, or X aliases Q"; return FEASTHIP_ERROR_INTERNAL; }
     if (ncand < 1 || ncand > (1 << 20)) { h->last_error = "feasthip_poly_ritz_eval_dev: candidate count out of range"; return FEASTHIP_ERROR_M0; }
     FH_CHECK(hipSetDevice(h->device));
-    const int N = (int)h->dense.N, d = h->poly.degree, r = (int)r64;
+    const int N = (int)h->dense.N, r = (int)r64;
     const int ld = (r > FH_MAX_LD || ncand > FH_MAX_LD) ? FH_MAX_LD : fh_pick_ld(std::max<int64_t>(r, ncand));
-    const int npr = (r + ld - 1) / ld, npc = (int)((ncand + ld - 1) / ld);
+    const int npc = (int)((ncand + ld - 1) / ld);
     const size_t panel = (size_t)N * ld;
     poly_coefs pc;
     if ((rc = pc.acquire(h))) return rc;
@@ -1275,30 +1229,12 @@ extern "C" int feasthip_poly_ritz_eval_dev(feasthip_handle h, int64_t r64, const
     if ((rc = fh_buf(h, "pv_R", panel, &R))) return rc;
     if ((rc = fh_buf(h, "pv_part", (size_t)fh_vec_nblk(N, ld) * ld, &part))) return rc;
     if ((rc = fh_buf(h, "pv_dots", (size_t)2 * ld, &ddots))) return rc;
-    const cplx* Yh = (const cplx*)Y_host;
+    const poly_ritz_ws ws{"pv_V", Qp, Xp, Tp, part, ddots};
     const cplx* th = (const cplx*)theta;
-    std::vector<cplx> Vp((size_t)ld * ld), dots(2 * (size_t)ld);
+    std::vector<cplx> dots(2 * (size_t)ld);
     for (int j = 0; j < npc; ++j) {
         const int mj = (int)std::min<int64_t>(ld, ncand - (int64_t)j * ld);
-        for (int i = 0; i < npr; ++i) {
-            const int mi = std::min(ld, r - i * ld);
-            std::fill(Vp.begin(), Vp.end(), cmake(0, 0));
-            for (int c2 = 0; c2 < mj; ++c2)
-                for (int c1 = 0; c1 < mi; ++c1) Vp[(size_t)c2 * ld + c1] = Yh[(size_t)((int64_t)j * ld + c2) * r + i * ld + c1];
-            cplx* dV;
-            if ((rc = poly_upload(h, "pv_V", Vp, &dV))) return rc;
-            fh_launch_to_panel((const cplx*)dQ + (size_t)i * ld * N, N, N, mi, Qp, ld, h->stream);
-            fh_prof_begin(h, "ritz");
-            if (i == 0) fh_launch_small_matmul(Qp, dV, N, ld, Xp, h->stream);
-            else {
-                fh_launch_small_matmul(Qp, dV, N, ld, Tp, h->stream);
-                fh_launch_axpy_cols(Xp, Tp, pc.minus, N, ld, h->stream);          // X += T
-            }
-            fh_prof_end(h);
-        }
-        fh_launch_dot_cols(Xp, Xp, N, ld, part, ddots, h->stream);
-        fh_launch_normalize_cols(Xp, ddots, N, ld, mj, h->stream);
-        fh_launch_from_panel(Xp, ld, N, mj, (cplx*)dX + (size_t)j * ld * N, N, h->stream);
+        if ((rc = poly_ritz_vectors(h, pc, ws, N, r, ncand, ld, j, (const cplx*)dQ, (const cplx*)Y_host, mj, mj, (cplx*)dX))) return rc;
         if (!backward_error) continue;
         cplx* dlam;
         if ((rc = poly_upload_cols(h, "pv_lam", th, (int64_t)j * ld, mj, ld, cmake(0, 0), &dlam))) return rc;
@@ -1310,17 +1246,12 @@ extern "C" int feasthip_poly_ritz_eval_dev(feasthip_handle h, int64_t r64, const
             const cplx t = th[(int64_t)j * ld + c];
             double be = INFINITY;
             if (std::isfinite(t.x) && std::isfinite(t.y) && dots[c].x > 0.0) {
-                const double la = std::hypot(t.x, t.y);
-                double scale = 0.0, pw = 1.0;
-                for (int k = 0; k <= d; ++k) { scale += pw * h->poly.fro[k]; pw *= la; }
+                const double scale = poly_bwd_scale(h, std::hypot(t.x, t.y));
                 be = scale > 0.0 ? std::sqrt(dots[ld + c].x) / scale : 0.0;
                 if (!std::isfinite(be)) be = INFINITY;
             }
             backward_error[(int64_t)j * ld + c] = be;
         }
     }
-    FH_CHECK(hipStreamSynchronize(h->stream));
-    fh_prof_collect(h);
-    FH_CHECK(hipGetLastError());
-    return 0;
+    return poly_finish(h);
 }

@@ -17,9 +17,9 @@ FPM3 = 10          # stop at 1e-10: at the default 1e-12 the loop count of these
 DRIVER_CASES = [(70, 2, 6, 6, True), (70, 2, 6, 6, False), (45, 3, 7, 5, True), (45, 3, 7, 5, False), (70, 1, 5, 8, False)]
 DRIVER_IDS = ["N%d-d%d-k%d-M0%d-%s" % (N, d, k, M0, "monic" if monic else "nonmonic") for N, d, k, M0, monic in DRIVER_CASES]
 # primitive shapes of the sweep / product / residual tests: (N, d, m)
-SWEEP_SHAPES = [(70, 2, 12), (45, 3, 15), (193, 2, 72)]
+SWEEP_SHAPES = [(70, 2, 12), (45, 3, 15), (193, 2, 72), (45, 8, 15)]
 # poly_solve: (N, d, complex coefficients)
-SOLVE_SHAPES = [(70, 1, True), (70, 2, True), (45, 3, False), (193, 2, True), (130, 4, True)]
+SOLVE_SHAPES = [(70, 1, True), (70, 2, True), (45, 3, False), (193, 2, True), (130, 4, True), (45, 8, True)]
 
 
 def _unitary(rng, N):

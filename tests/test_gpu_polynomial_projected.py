@@ -59,9 +59,9 @@ def test_symbols_are_declared_and_exported():
 
 # ---- P(lambda_j) x_j -----------------------------------------------------------------------------------------------------------
 # dense: (N, d, complex); sparse: (grid, d, complex) -- every grid, d = 1 .. 4, real and complex values
-EVAL_DENSE = [(70, 1, True), (70, 2, True), (45, 3, False), (130, 4, True)]
+EVAL_DENSE = [(70, 1, True), (70, 2, True), (45, 3, False), (130, 4, True), (45, 8, True)]
 EVAL_SPARSE = [((9, 7, 1), 1, False), ((9, 7, 1), 4, True), ((13, 11, 2), 2, True), ((13, 11, 2), 3, False), ((20, 16, 1), 3, True),
-               ((20, 16, 1), 2, False)]
+               ((20, 16, 1), 2, False), ((9, 7, 1), 8, True)]
 EVAL_M = [5, 24, 64, 72]          # panel widths 16, 32, 64, and 64 + 16 across the 64-column panel
 
 
@@ -128,7 +128,9 @@ def _sweep_reference(kind, key, d, m, ne):
     return (Zne, Wne), X, sigma, plain, shifted, float(conds.max())
 
 
-RESINV_SHAPES = [("dense", N, d, m) for N, d, m in pc.SWEEP_SHAPES] + [("sparse", (13, 11, 2), 2, 72)]
+# (the sparse row stays fourth: pytest numbers its grid by position, and its id stays as it was)
+_RESINV_DENSE = [("dense", N, d, m) for N, d, m in pc.SWEEP_SHAPES]
+RESINV_SHAPES = _RESINV_DENSE[:3] + [("sparse", (13, 11, 2), 2, 72)] + _RESINV_DENSE[3:]
 
 
 @pytest.mark.parametrize("ne", [8, 16])
@@ -167,7 +169,7 @@ def test_poly_resinv_apply(engine, restore, kind, key, d, m, ne):
 
 # ---- the reduced polynomial and the candidates --------------------------------------------------------------------------------
 REDUCED_SHAPES = [("dense", 70, 2, 7), ("dense", 45, 3, 7), ("dense", 70, 2, 64), ("dense", 193, 2, 72), ("sparse", (9, 7, 1), 3, 7),
-                  ("sparse", (13, 11, 2), 2, 72)]
+                  ("sparse", (13, 11, 2), 2, 72), ("sparse", (9, 7, 1), 8, 7)]
 
 
 @pytest.mark.parametrize("kind,key,d,r", REDUCED_SHAPES)

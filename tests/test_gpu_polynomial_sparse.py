@@ -56,10 +56,13 @@ def leaf(request, monkeypatch):
 
 
 # (grid, d, complex coefficients)
-SOLVE_SHAPES = [((9, 7, 1), 1, True), ((9, 7, 1), 4, False), ((13, 11, 2), 2, True), ((13, 11, 2), 3, False), ((20, 16, 1), 1, False), ((20, 16, 1), 3, True)]
-# (grid, d, m, complex coefficients): d = 1 .. 4, m = 5, 64, 72 (two panels), every N
-SWEEP_SHAPES = [((9, 7, 1), 1, 5, False), ((9, 7, 1), 4, 5, True), ((9, 7, 1), 3, 72, False), ((13, 11, 2), 2, 72, False), ((20, 16, 1), 2, 64, True)]
-PRODUCT_SHAPES = SWEEP_SHAPES + [((13, 11, 2), 4, 64, True), ((20, 16, 1), 3, 72, False)]
+SOLVE_SHAPES = [((9, 7, 1), 1, True), ((9, 7, 1), 4, False), ((13, 11, 2), 2, True), ((13, 11, 2), 3, False), ((20, 16, 1), 1, False), ((20, 16, 1), 3, True),
+                ((9, 7, 1), 8, True)]
+# (grid, d, m, complex coefficients): d = 1 .. 4 and 8 (the degree bound: full fan width), m = 5, 64, 72 (two panels), every N
+SWEEP_SHAPES = [((9, 7, 1), 1, 5, False), ((9, 7, 1), 4, 5, True), ((9, 7, 1), 3, 72, False), ((13, 11, 2), 2, 72, False), ((20, 16, 1), 2, 64, True),
+                ((9, 7, 1), 8, 5, True)]
+# (the d = 8 row goes last here too: pytest numbers the grids by position, and the ids of the other rows stay as they were)
+PRODUCT_SHAPES = SWEEP_SHAPES[:5] + [((13, 11, 2), 4, 64, True), ((20, 16, 1), 3, 72, False)] + SWEEP_SHAPES[5:]
 
 
 @pytest.mark.parametrize("m", [5, 64])
