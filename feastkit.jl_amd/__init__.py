@@ -12,11 +12,11 @@ from .parameters import feastinit, feastdefault, feast_tolerance, check_feast_sr
 from .contour import (feast_contour, feast_gcontour, feast_inside_gcontour, zolotarev_point,   # noqa: F401
                       distribute_contour_points, balanced_contour_points, cost_balanced_contour_points)
 from . import workloads   # noqa: F401
-from .hip_backend import (feast_hip_hermitian, feast_hip_general, feast_hip_complex_symmetric, feast_hip_polynomial, feast_hip_polynomial_projected,   # noqa: F401
+from .hip_backend import (feast_hip_hermitian, feast_hip_general, feast_hip_complex_symmetric, feast_hip_polynomial, feast_hip_polynomial_projected, feast_hip_nonlinear,   # noqa: F401
                           pfeast_hip_moments, pfeast_hip_hermitian_moments, feast_hip_symmetric_kernel,
                           seeded_subspace)   # noqa: F401
 from .engine import HipEngine   # noqa: F401
-from .api import feast, feast_general, feast_polynomial, feast_pep   # noqa: F401
+from .api import feast, feast_general, feast_polynomial, feast_pep, feast_nonlinear, feast_nep   # noqa: F401
 from . import rci   # noqa: F401
 from . import ingest   # noqa: F401
 from . import banded   # noqa: F401

@@ -100,6 +100,13 @@ SYMBOLS = {
     "feasthip_poly_project_reduced_dev": (_i, [_vp, _i64, _vp, _vp]),
     "feasthip_poly_ritz_eval_dev": (_i, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp]),
     "feasthip_poly_orthonormalize_dev": (_i, [_vp, _i64, _vp, _i, _d, _pi]),
+    "feasthip_set_terms": (_i, [_vp, _i64, _i, _i, _vp, _vp]),
+    "feasthip_set_terms_csr": (_i, [_vp, _i64, _i, _i, _vp, _vp, _vp]),
+    "feasthip_nep_set_node_values": (_i, [_vp, _i, _vp]),
+    "feasthip_nep_solve_dev": (_i, [_vp, _i, _i64, _vp, _vp, _ps]),
+    "feasthip_nep_eval_cols_dev": (_i, [_vp, _i64, _vp, _vp, _vp]),
+    "feasthip_nep_resinv_apply_dev": (_i, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _ps]),
+    "feasthip_nep_ritz_eval_dev": (_i, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp]),
     "feasthip_last_node_iterations": (_i, [_vp, _vp, _i]),
     "feasthip_last_column_iterations": (_i, [_vp, _vp, _i]),
     "feasthip_last_global_node_iterations": (_i, [_vp, _vp, _i]),

@@ -14,7 +14,7 @@ from .engine import HipEngine
 from .contour import feast_contour, feast_gcontour
 from .hip_backend import (DIRECT_SOLVERS, ESTIMATE_SEED, check_direct_nodes, check_ortho, check_two_sided, feast_hip_estimate,
                           feast_hip_general, feast_hip_general_two_sided, feast_hip_hermitian, feast_hip_polynomial, feast_hip_polynomial_projected,
-                          POLY_METHODS, POLY_RESIDUALS, POLY_SET_ASIDE)
+                          POLY_METHODS, POLY_RESIDUALS, POLY_SET_ASIDE, feast_hip_nonlinear, nep_functions, nep_table)
 from .ingest import polynomial_union_csr
 from .parameters import feastdefault, feastinit
 from .types import FEAST_UNINITIALIZED, FeastHipError, FeastResult
@@ -765,6 +765,125 @@ def feast_polynomial(coeffs, center, radius, *, M0=10, fpm=None, engine=None, de
 
 
 feast_pep = feast_polynomial
+
+
+def feast_nonlinear(terms, center, radius, *, M0=10, fpm=None, solver="direct", ortho="mgs", Q0=None, contour=None, seed=None,
+                    keep_factors=False, moments=2, reduced_nodes=128, engine=None, device=0):
+    """Eigenpairs of the nonlinear eigenproblem T(lambda) x = 0 in split form,
+        T(lambda) = sum_k f_k(lambda) A_k,
+    with lambda inside the circle: the projected method of feast_polynomial (FEAST with a residual-inverse contour step on an
+    N-row subspace; Gavin, Miedlar, Polizzi) with arbitrary analytic scalar functions in place of the powers of lambda.  No
+    reference counterpart.
+
+    ``terms``: 2 to 9 pairs (A_k, f_k).  The A_k are square and of one size, all numpy arrays or all scipy.sparse matrices
+    (a mix is expanded under "direct"), real or complex; float32 / complex64 input is promoted and the result demoted as in
+    feast_polynomial.  f_k is a callable mapping a complex numpy array to a complex array of the same shape, or a non-negative
+    int p for lambda^p.  The f_k are only ever evaluated -- at the contour nodes, the reduced contour and the Ritz values -- and
+    never differentiated analytically; the device sees tables of their values, not the functions.
+    ``M0`` (clipped to N): the number of N-row columns; choose M0 >= 1.3 x the expected count.  ``Q0``: (N, M0).
+    ``solver``: "direct" (the dense LU of T(z_e); sparse terms are expanded up to N = 12 288, ``stats["solver_substitution"]``)
+    or "sparse_direct" (every A_k sparse: the multifrontal LU on the union pattern, with feast_polynomial's fallback to the
+    dense expansion on a rejected pivot or a pattern without a plan, and FeastHipError where it raises one).  "bicgstab",
+    "cocg" and "gmres" raise ValueError: Krylov solves on T(z) are not provided.
+    Per loop the subspace is orthonormalised (``ortho`` as in feast), the terms are projected (Q^H A_k Q) and the small r x r
+    problem is solved on the host: Beyn's integral method on ``reduced_nodes`` trapezoid points of the same circle with
+    ``moments`` block moments (>= 2 are needed where eigenvalues inside share an eigenvector, as the branches of a delay term
+    do), then a guarded Newton polish of each candidate whose derivative is a central difference of the f_k.  Candidates are
+    ranked by their backward error on the device as in feast_polynomial (POLY_SET_ASIDE).  Loop 0 factors every node once;
+    later loops reuse the factors.
+    Result: FeastResult with complex ``lambda_`` (feast_sort_general order), unit vectors ``q``, ``res[j]`` the backward error
+    ||T(lambda_j) q_j|| / sum_k |f_k(lambda_j)| ||A_k||_F, ``epsout`` the largest, ``info`` 0 or Feast_ERROR_NO_CONVERGENCE (loop
+    limit, with the last iterates; or nothing found inside, M = 0).  ``stats["nonlinear"]`` = {terms, columns, rank, candidates,
+    set_aside, eps_history (one entry per loop each), backward_error, moments, reduced_nodes, reduced_seconds}, plus the plan fields
+    and fell_back under "sparse_direct"; ``stats["factorizations"]``, ``stats["solve_seconds"]``, ``stats["ortho"]`` as in
+    feast_polynomial.  ``keep_factors``, ``contour``, ``seed``: as in feast_general.
+
+    Known limits of the method: an eigenvalue just outside the circle slows the filter of a 16-node
+    contour to a contraction of about one half per loop, so the loop limit may be reached with info = Feast_ERROR_NO_CONVERGENCE
+    (more nodes cure it); a spurious candidate of the small problem inside the circle whose backward error is below
+    POLY_SET_ASIDE[0] is not set aside: it is counted in M and epsout stalls at its backward error.
+
+    Not covered: Krylov solves on T(z); multi-rank sweeps; complex64 factors; the two-sided form; functions with a branch cut
+    that crosses the circle (keeping the cut away is the caller's responsibility); eigenvalues where some f_k has a pole inside
+    the circle."""
+    terms = list(terms)
+    check_ortho(ortho)
+    if len(terms) < 2 or len(terms) > POLY_MAX_DEGREE + 1:
+        raise ValueError(f"feast_nonlinear needs 2 to {POLY_MAX_DEGREE + 1} terms (A_k, f_k), not {len(terms)}")
+    if any(not isinstance(t, (tuple, list)) or len(t) != 2 for t in terms):
+        raise ValueError("each term must be a pair (A_k, f_k)")
+    mats = [t[0] for t in terms]
+    funcs = nep_functions([t[1] for t in terms])
+    shape = mats[0].shape
+    for c in mats:
+        if len(c.shape) != 2 or c.shape[0] != c.shape[1]:
+            raise ValueError("the matrices A_k must be square")
+        if c.shape != shape:
+            raise ValueError("the matrices A_k must have equal shapes")
+    if not radius > 0:
+        raise ValueError("radius must be positive")
+    if solver in POLY_KRYLOV_SOLVERS:
+        raise ValueError(f'solver="{solver}": Krylov solves on T(z) are out of scope for feast_nonlinear; use "direct" or "sparse_direct"')
+    if solver not in POLY_SOLVERS:
+        raise ValueError(f"solver must be one of {POLY_SOLVERS}, not {solver!r}")
+    if int(moments) < 1 or int(reduced_nodes) < 8:
+        raise ValueError("moments must be >= 1 and reduced_nodes >= 8")
+    N = shape[0]
+    sparse_direct = solver == "sparse_direct"
+    if sparse_direct and not all(sp.issparse(c) for c in mats):
+        raise ValueError('solver="sparse_direct" needs every A_k as a scipy.sparse matrix (no mix of dense and sparse terms); dense terms take '
+                         'solver="direct"')
+    substituted = None
+    if not sparse_direct and any(sp.issparse(c) for c in mats):
+        if N > POLY_DENSE_LIMIT:
+            raise ValueError(f"sparse terms are expanded to dense matrices up to N = {POLY_DENSE_LIMIT}; N = {N}")
+        mats = [_densify(c) if sp.issparse(c) else c for c in mats]
+        substituted = {"requested": "direct", "used": "dense LU of the expanded terms"}
+    if not sparse_direct:
+        mats = [np.asarray(c) for c in mats]
+    single = _single_precision(*mats)
+    if single:
+        mats = [_promote(c) for c in mats]
+    fpm = feastinit() if fpm is None else fpm
+    feastdefault(fpm)
+    M0 = min(int(M0), N)
+    if Q0 is not None and np.shape(Q0) != (N, M0):
+        raise ValueError(f"Q0 must be the N-row start block of shape ({N}, {M0}), not {np.shape(Q0)}")
+    Zne, Wne = feast_gcontour(complex(center), float(radius), fpm) if contour is None else contour
+    F_node = nep_table(funcs, Zne)
+    if not np.isfinite(F_node).all():
+        bad = int(np.flatnonzero(~np.isfinite(F_node).all(axis=0))[0])
+        raise ValueError(f"f_{bad} is not finite at a contour node (a pole or an overflow on the circle)")
+    eng = _engine(engine, device)
+    eps_floor = float(np.sqrt(np.finfo(np.float32).eps)) if single else 0.0
+    common = dict(Q0=Q0, contour=(Zne, Wne), eps_floor=eps_floor, ortho=ortho, moments=int(moments), reduced_nodes=int(reduced_nodes),
+                  **({} if seed is None else {"seed": int(seed)}))
+    try:
+        res = None
+        if sparse_direct:
+            union = polynomial_union_csr(mats)
+            try:
+                res = feast_hip_nonlinear(eng, mats, funcs, complex(center), float(radius), M0, fpm, union_csr=union, **common)
+                if isinstance(res.stats, dict) and "nonlinear" in res.stats:
+                    res.stats["nonlinear"]["fell_back"] = False
+            except FeastHipError as err:
+                if err.code not in (8, 9) or N > POLY_DENSE_LIMIT:          # (as feast_polynomial: 6 is no reason to try dense factors)
+                    raise
+                eng.free_factors()
+                substituted = {"requested": "sparse_direct", "used": "dense LU of the expanded terms", "reason": str(err)}
+                mats = [_densify(c) for c in mats]
+        if res is None:
+            res = feast_hip_nonlinear(eng, mats, funcs, complex(center), float(radius), M0, fpm, **common)
+            if sparse_direct and isinstance(res.stats, dict) and "nonlinear" in res.stats:
+                res.stats["nonlinear"].update(plan="dense", plan_nnz=int(len(union[1])), fell_back=True)
+        if substituted is not None and isinstance(res.stats, dict):
+            res.stats["solver_substitution"] = substituted
+    finally:
+        _release_band_factors(eng, keep_factors)
+    return _demote(res, cplx_lambda=True) if single else res
+
+
+feast_nep = feast_nonlinear
 
 
 def _feast_auto(driver, A, B, *where, fpm=None, engine=None, device=0, solver="direct", solver_tol=0.0,

@@ -560,6 +560,10 @@ extern "C" int feasthip_set_solver(feasthip_handle h, int kind, double rtol, dou
         // dense coefficients: the LU of P(z_e) only.  CSR coefficients: that (the multifrontal LU), or a Krylov solver on the
         // operator P(z_e) (fh_poly.hip: k_spmm_poly); complex128 throughout
         const bool krylov = kind == FEASTHIP_SOLVER_BICGSTAB || kind == FEASTHIP_SOLVER_COCG || kind == FEASTHIP_SOLVER_GMRES;
+        if (h->poly.terms && kind != FEASTHIP_SOLVER_LU) {      // the Krylov operator k_spmm_poly forms powers of z_e
+            h->last_error = "feasthip_set_solver: a term handle (feasthip_set_terms) takes FEASTHIP_SOLVER_LU only; Krylov solves on T(z) are not provided";
+            return FEASTHIP_ERROR_FPM;
+        }
         if (factor_precision != 64 || !(kind == FEASTHIP_SOLVER_LU || (krylov && h->poly.sparse))) {
             h->last_error = h->poly.sparse ? "feasthip_set_solver: a CSR polynomial handle needs FEASTHIP_SOLVER_LU, _BICGSTAB, _COCG or _GMRES with factor_precision = 64"
                                            : "feasthip_set_solver: a dense polynomial handle needs FEASTHIP_SOLVER_LU with factor_precision = 64";

@@ -115,12 +115,17 @@ struct fh_dense {
 // sparse (feasthip_set_polynomial_csr): the coefficients share ONE CSR pattern that holds the whole diagonal -- device rowptr /
 // col in feasthip_ctx::csr (N, nnz, is_complex; aval and bval stay null, b_identity 0), the host copy in host_rowptr / host_col
 // in the caller's order -- and coef[k] is the array of nnz values of A_k on that pattern, explicit zeros included.
+// terms (feasthip_set_terms / feasthip_set_terms_csr): the same storage read as the split form T(lambda) = sum_k f_k(lambda) A_k
+// of degree + 1 terms, f_k arbitrary scalar functions that only the caller evaluates -- fnode[e * (degree + 1) + k] = f_k(z_e) on
+// the contour fnode_z (feasthip_nep_set_node_values); the feasthip_nep_* entry points take the other scalars as tables.
 #define FH_POLY_MAX_DEGREE 8
 struct fh_poly {
     int degree = 0;
     int sparse = 0;
+    int terms = 0;
     void* coef[FH_POLY_MAX_DEGREE + 1] = {};
     double fro[FH_POLY_MAX_DEGREE + 1] = {};
+    std::vector<cplx> fnode, fnode_z;
 };
 // the coefficient pointers as a kernel argument (fh_poly_coef_ptrs below fills it; null past the degree)
 struct fh_poly_ptrs { const void* c[FH_POLY_MAX_DEGREE + 1]; };
@@ -135,6 +140,15 @@ template <int TOP, typename F> __device__ __forceinline__ cplx fh_horner(int d, 
 #pragma unroll
     for (int k = TOP; k >= 0; --k)
         if (k <= d) v = cadd(cmul(v, z), coef(k));
+    return v;
+}
+// The table form of the same combination: sum_{k < nt} f[k] coef(k) in ascending k, for the split form of a term handle
+// (fh_poly::terms), whose scalars come from a table instead of the powers of z.  f: nt values, uniform or per lane.
+template <int TOP, typename FS, typename F> __device__ __forceinline__ cplx fh_term_sum(int nt, FS&& f, F&& coef) {
+    cplx v = cmake(0, 0);
+#pragma unroll
+    for (int k = 0; k <= TOP; ++k)
+        if (k < nt) cfma(v, f(k), coef(k));
     return v;
 }
 

@@ -1619,8 +1619,9 @@ static int lu_factor_batch(feasthip_ctx* h, const std::vector<int>& which, const
     FH_CHECK(hipStreamSynchronize(h->stream));
 
     // form z B - A (a polynomial handle: P(z), all nodes in one pass over the coefficients)
-    if (h->kind == 3) fh_poly_form(h, (void* const*)dlus, dz, nf, sizeof(T) == sizeof(cplx) ? 64 : 32);
-    else {
+    if (h->kind == 3) {
+        if ((rc = fh_poly_form(h, (void* const*)dlus, dz, nf, sizeof(T) == sizeof(cplx) ? 64 : 32))) return rc;
+    } else {
         dim3 grid(2048, nf), block(FH_BLOCK);
         fh_prof_begin(h, "lu_form");
         const bool bid = h->dense.b_identity != 0;
@@ -2654,6 +2655,23 @@ __global__ __launch_bounds__(FH_BLOCK) void k_mf_assemble_poly(const int* __rest
     }
 }
 
+// The table form for a term handle (feasthip_set_terms_csr): the entry is sum_k F[node][k] a_k at CSR position src[q], F the
+// nf x nt table of fh_poly_term_table -- a node's row is uniform over its workgroups.  Same lists, same traffic.
+template <typename VT, typename T>
+__global__ __launch_bounds__(FH_BLOCK) void k_mf_assemble_terms(const int* __restrict__ dst, const int* __restrict__ src, size_t count, T* base, size_t node_stride,
+                                                                 fh_poly_ptrs P, int nt, const cplx* __restrict__ F) {
+    T* A = base + (size_t)blockIdx.y * node_stride;
+    const cplx* __restrict__ f = F + (size_t)blockIdx.y * nt;
+    for (size_t q = (size_t)blockIdx.x * FH_BLOCK + threadIdx.x; q < count; q += (size_t)gridDim.x * FH_BLOCK) {
+        int d = dst[q];
+        if (d < 0) d = ~d;
+        const int k = src[q];
+        cplx v = cmake(0, 0);
+        if (k >= 0) v = fh_term_sum<FH_POLY_MAX_DEGREE>(nt, [&](int j) { return f[j]; }, [&](int j) { return poly_val(((const VT*)P.c[j])[k]); });
+        A[d] = cvt<T>(v);
+    }
+}
+
 // parent front += Schur complement of a child (grid.y = child, grid.z = node)
 template <typename T>
 __global__ __launch_bounds__(FH_BLOCK) void k_mf_extend_add(const mf_kid* kids, T* base, size_t node_stride, const int* __restrict__ rel, int n_p) {
@@ -2881,6 +2899,8 @@ static int mf_factor_t(feasthip_ctx* h, int nf, void* const* stores, int* const*
     float* dmult = dpart + tot * MF_MULT_PARTS;
     FH_CHECK(hipMemsetAsync(dpart, 0, tot * MF_MULT_PARTS * sizeof(float), h->stream));
     const bool bid = h->csr.b_identity != 0, cz = h->csr.is_complex != 0;
+    const cplx* dterms = nullptr;          // term handle: the rows of its node table for these shifts
+    if (h->kind == 3 && h->poly.terms && (rc = fh_poly_term_table(h, dz, nf, &dterms))) return rc;
     auto factor_group = [&](int g) -> int {
         const fh_mf::group& G = P.groups[g];
         const int F = (int)G.fronts.size(), nmat = F * nf, n = G.n, np = G.np, nb = G.nb;
@@ -2898,7 +2918,15 @@ static int mf_factor_t(feasthip_ctx* h, int nf, void* const* stores, int* const*
                 T* base = work + G.work_off;
                 const int* dd = S->d_asm_dst + G.asm_begin;
                 const int* ss = S->d_asm_src + G.asm_begin;
-                if (h->kind == 3) {          // sparse polynomial handle: P(z_e) in place of z_e B - A, a profile class of its own
+                if (h->kind == 3 && h->poly.terms) {          // sparse term handle: T(z_e) from the node table, a profile class of its own
+                    const fh_poly_ptrs pp = fh_poly_coef_ptrs(h);
+                    fh_prof_end(h);
+                    fh_prof_begin(h, "terms_mf_assemble");
+                    if (cz) hipLaunchKernelGGL((k_mf_assemble_terms<cplx, T>), grid, block, 0, h->stream, dd, ss, cnt, base, P.work_elems, pp, h->poly.degree + 1, dterms);
+                    else hipLaunchKernelGGL((k_mf_assemble_terms<double, T>), grid, block, 0, h->stream, dd, ss, cnt, base, P.work_elems, pp, h->poly.degree + 1, dterms);
+                    fh_prof_end(h);
+                    fh_prof_begin(h, "mf_assemble");
+                } else if (h->kind == 3) {          // sparse polynomial handle: P(z_e) in place of z_e B - A, a profile class of its own
                     const fh_poly_ptrs pp = fh_poly_coef_ptrs(h);
                     fh_prof_end(h);
                     fh_prof_begin(h, "poly_mf_assemble");

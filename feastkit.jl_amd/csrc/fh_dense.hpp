@@ -25,7 +25,12 @@ void fh_launch_axpy_cols(cplx* R, const cplx* X, const cplx* lam, int N, int ld,
 
 // Polynomial handle (h->kind == 3, fh_poly.hip): LUs[e] = P(z_e) for the nf matrices lu_factor_batch is about to factor, in one
 // pass over the coefficients; prec 64: complex128 factors, 32: complex64.
-void fh_poly_form(feasthip_ctx* h, void* const* dlus, const cplx* dz, int nf, int prec);
+// A term handle (fh_poly::terms) forms T(z_e) = sum_k f_k(z_e) A_k from its node table instead; a shift that is no contour
+// node of that table is an error.
+int fh_poly_form(feasthip_ctx* h, void* const* dlus, const cplx* dz, int nf, int prec);
+// Term handle: *dF = the nf x (degree + 1) device table of the rows f_k(z) of the node table that belong to the shifts dz (device,
+// each one a node of the table's contour, matched exactly) -- what the forming kernels of both direct solvers read.
+int fh_poly_term_table(feasthip_ctx* h, const cplx* dz, int nf, const cplx** dF);
 
 // Factor (cached per local node when h->cache_factors) and solve all local nodes:
 //   Y[e] = (z_e B - A)^{-1} RHS     RHS: one shared panel; Y: node-strided panels

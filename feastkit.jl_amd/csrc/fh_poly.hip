@@ -4,6 +4,11 @@
 //   sparse coefficients     the multifrontal LU of P(z_e), k_spmm_fan for the products      (feasthip_set_polynomial_csr)
 //   the projected method    N-row subspaces: k_spmm_horner, the residual-inverse sweep      (either kind of coefficients)
 //   Krylov solves on P(z)   BiCGStab / COCG / GMRES on the operator k_spmm_poly             (sparse coefficients)
+// A fifth user reads the same storage as a split form: a TERM handle (feasthip_set_terms[_csr], fh_poly::terms) holds the A_k of
+// T(lambda) = sum_k f_k(lambda) A_k, the f_k arbitrary scalar functions that only the caller evaluates.  It runs the projected
+// method's calls with host tables of the f_k where a polynomial handle forms powers (the feasthip_nep_* entry points; one body
+// per call, shared with its feasthip_poly_* sibling), through the table-form kernels k_form_terms, k_mf_assemble_terms
+// (fh_dense.hip) and k_spmm_terms; the sum over the terms is fh_term_sum (fh_common.hpp), the sibling of fh_horner.
 // The steps they share exist once: Horner over the coefficients is fh_horner (fh_common.hpp), the batched row gather of the
 // three SpMM kernels is POLY_ROW_GATHER, the kernels' coefficient table is fh_poly_coef_ptrs (fh_common.hpp).
 //
@@ -69,11 +74,66 @@ __global__ __launch_bounds__(FH_BLOCK) void k_form_poly(fh_poly_ptrs P, int d, T
     }
 }
 
-void fh_poly_form(feasthip_ctx* h, void* const* dlus, const cplx* dz, int nf, int prec) {
+// The table form for a term handle: S_q = sum_{k < nt} F[q][k] a_k, F the nf x nt table of fh_poly_term_table.  The same
+// streaming pass -- a thread's nt coefficient values loaded once, nf elements written -- with the node's scalars read through
+// uniform addresses (the row and term indices are the same in every lane, so they come by scalar loads, not per-lane gathers).
+template <typename VT, typename T>
+__global__ __launch_bounds__(FH_BLOCK) void k_form_terms(fh_poly_ptrs P, int nt, T* const* LUs, const cplx* __restrict__ F, int nf, size_t total) {
+    for (size_t e = (size_t)blockIdx.x * FH_BLOCK + threadIdx.x; e < total; e += (size_t)gridDim.x * FH_BLOCK) {
+        cplx a[PD + 1];
+#pragma unroll
+        for (int k = 0; k <= PD; ++k) a[k] = k < nt ? poly_val(((const VT*)P.c[k])[e]) : cmake(0, 0);
+        for (int q = 0; q < nf; ++q) {
+            const cplx* __restrict__ f = F + (size_t)q * nt;
+            LUs[q][e] = cvt<T>(fh_term_sum<PD>(nt, [&](int k) { return f[k]; }, [&](int k) { return a[k]; }));
+        }
+    }
+}
+
+int fh_poly_term_table(feasthip_ctx* h, const cplx* dz, int nf, const cplx** dF) {
+    const int nt = h->poly.degree + 1, ne = (int)h->poly.fnode_z.size();
+    if (!h->poly.terms || ne == 0 || h->poly.fnode.size() != (size_t)ne * nt) {
+        h->last_error = "term handle: no node values set (feasthip_nep_set_node_values)";
+        return FEASTHIP_ERROR_FPM;
+    }
+    std::vector<cplx> z(nf), rows((size_t)nf * nt);
+    FH_CHECK(hipMemcpyAsync(z.data(), dz, nf * sizeof(cplx), hipMemcpyDeviceToHost, h->stream));
+    FH_CHECK(hipStreamSynchronize(h->stream));
+    for (int q = 0; q < nf; ++q) {
+        int e = 0;
+        while (e < ne && !(h->poly.fnode_z[e].x == z[q].x && h->poly.fnode_z[e].y == z[q].y)) ++e;
+        if (e == ne) { h->last_error = "term handle: a solve at a shift that is no node of the contour the node values were set for"; return FEASTHIP_ERROR_FPM; }
+        for (int k = 0; k < nt; ++k) rows[(size_t)q * nt + k] = h->poly.fnode[(size_t)e * nt + k];
+    }
+    cplx* d;
+    int rc = fh_buf(h, "terms_rows", rows.size(), &d);
+    if (rc) return rc;
+    FH_CHECK(hipMemcpyAsync(d, rows.data(), rows.size() * sizeof(cplx), hipMemcpyHostToDevice, h->stream));
+    FH_CHECK(hipStreamSynchronize(h->stream));          // (rows is a local)
+    *dF = d;
+    return 0;
+}
+
+int fh_poly_form(feasthip_ctx* h, void* const* dlus, const cplx* dz, int nf, int prec) {
     const fh_poly_ptrs P = fh_poly_coef_ptrs(h);
     const int d = h->poly.degree;
     const size_t total = (size_t)h->dense.N * (size_t)h->dense.N;
     const dim3 grid((unsigned)std::min<size_t>(2048, (total + FH_BLOCK - 1) / FH_BLOCK)), block(FH_BLOCK);
+    if (h->poly.terms) {
+        const cplx* dF;
+        const int rc = fh_poly_term_table(h, dz, nf, &dF);
+        if (rc) return rc;
+        fh_prof_begin(h, "terms_form");
+        if (h->dense.is_complex) {
+            if (prec == 32) hipLaunchKernelGGL((k_form_terms<cplx, cplxf>), grid, block, 0, h->stream, P, d + 1, (cplxf* const*)dlus, dF, nf, total);
+            else hipLaunchKernelGGL((k_form_terms<cplx, cplx>), grid, block, 0, h->stream, P, d + 1, (cplx* const*)dlus, dF, nf, total);
+        } else {
+            if (prec == 32) hipLaunchKernelGGL((k_form_terms<double, cplxf>), grid, block, 0, h->stream, P, d + 1, (cplxf* const*)dlus, dF, nf, total);
+            else hipLaunchKernelGGL((k_form_terms<double, cplx>), grid, block, 0, h->stream, P, d + 1, (cplx* const*)dlus, dF, nf, total);
+        }
+        fh_prof_end(h);
+        return 0;
+    }
     fh_prof_begin(h, "poly_form");
     if (h->dense.is_complex) {
         if (prec == 32) hipLaunchKernelGGL((k_form_poly<cplx, cplxf>), grid, block, 0, h->stream, P, d, (cplxf* const*)dlus, dz, nf, total);
@@ -83,6 +143,7 @@ void fh_poly_form(feasthip_ctx* h, void* const* dlus, const cplx* dz, int nf, in
         else hipLaunchKernelGGL((k_form_poly<double, cplx>), grid, block, 0, h->stream, P, d, (cplx* const*)dlus, dz, nf, total);
     }
     fh_prof_end(h);
+    return 0;
 }
 
 // ---------------------------------------------------------------------------------------
@@ -288,6 +349,29 @@ __global__ __launch_bounds__(FH_BLOCK) void k_spmm_horner(fh_horner_args a) {
     a.Y[(size_t)i * LD + c] = acc;
 }
 
+// The table form for a term handle (feasthip_nep_eval_cols_dev and the calls built on it): R[:, c] = sum_k F[k][c] A_k X[:, c].
+// a.lam is the nt x LD table, term-major, so the lanes of a row slice read consecutive values; a lane loads its nt scalars once
+// into registers before the row's nonzeros (at most 9 complex values).  Same layout, same traffic, same order as above.
+template <typename VT, int LD>
+__global__ __launch_bounds__(FH_BLOCK) void k_spmm_terms(fh_horner_args a) {
+    constexpr int ROWS = FH_BLOCK / LD;
+    const int c = threadIdx.x % LD;
+    const int i = blockIdx.x * ROWS + threadIdx.x / LD;
+    if (i >= a.N) return;
+    const int* __restrict__ colidx = a.col;
+    const cplx* __restrict__ X = a.X;
+    const int nt = a.d + 1;
+    cplx f[PD + 1];
+#pragma unroll
+    for (int j = 0; j <= PD; ++j) f[j] = j < nt ? a.lam[(size_t)j * LD + c] : cmake(0, 0);
+    const int k0 = a.rowptr[i], k1 = a.rowptr[i + 1];
+    cplx acc = cmake(0, 0);
+    POLY_ROW_GATHER(LD, colidx, X, k0, k1, c, k, x,
+        cfma(acc, fh_term_sum<PD>(nt, [&](int j) { return f[j]; }, [&](int j) { return poly_val(((const VT*)a.val.c[j])[k]); }), x);
+    )
+    a.Y[(size_t)i * LD + c] = acc;
+}
+
 // ---------------------------------------------------------------------------------------
 // The residual-inverse sweep's sum in one pass over the ne node-solution panels, nodes in ascending e, one write per element:
 //     Q[i, c] = sum_e T[e][c] (X[i, c] - Y_e[i, c]),   T[e][c] = w_e / (z_e - sigma_c)   (host table, ne x ld)
@@ -444,12 +528,20 @@ static bool poly_krylov(const feasthip_ctx* h) {
 // What every feasthip_poly_* call needs, linearised or projected: a polynomial handle whose solver the solves with P(z_e)
 // cover -- FEASTHIP_SOLVER_LU (the dense LU, or the multifrontal one for CSR coefficients), or for CSR coefficients the plain
 // BiCGStab / COCG / GMRES on the operator -- complex128 factors, no adjoint, one rank, the whole contour, and 1 <= m <= maxm.
-// what: the entry point's name for the message.
-static int poly_check(feasthip_ctx* h, const char* what, int64_t m, int64_t maxm) {
+// what: the entry point's name for the message.  form: which scalar form of the handle the call serves -- POLY_POWERS (the
+// default: a polynomial handle only, the call forms powers of lambda), POLY_ANY_FORM (coefficients only) or POLY_TERMS (a term
+// handle with its node table set for the current contour).
+enum { POLY_POWERS = 0, POLY_ANY_FORM = 1, POLY_TERMS = 2 };
+static int poly_check(feasthip_ctx* h, const char* what, int64_t m, int64_t maxm, int form = POLY_POWERS) {
     if (!h) return FEASTHIP_ERROR_INTERNAL;
     if (h->poisoned) { h->last_error = "handle poisoned by an earlier device failure: destroy it"; return FEASTHIP_ERROR_INTERNAL; }
     const char* why = nullptr;
     if (h->kind != 3) why = "needs a polynomial handle (feasthip_set_polynomial); a dense or CSR handle takes the entry points without poly_";
+    else if (h->poly.terms && form == POLY_POWERS)
+        why = "forms powers of lambda, which a term handle (feasthip_set_terms) does not have: use feasthip_nep_solve_dev, feasthip_nep_eval_cols_dev, "
+              "feasthip_nep_resinv_apply_dev or feasthip_nep_ritz_eval_dev with tables of the f_k";
+    else if (!h->poly.terms && form == POLY_TERMS) why = "needs a term handle (feasthip_set_terms / feasthip_set_terms_csr); a polynomial handle takes the feasthip_poly_* calls";
+    else if (h->poly.terms && h->solver != FEASTHIP_SOLVER_LU) why = "the solver of a term handle must be FEASTHIP_SOLVER_LU (Krylov solves on T(z) are not provided)";
     else if (h->solver != FEASTHIP_SOLVER_LU && !(poly_krylov(h) && h->poly.sparse && !h->shifted && !h->block))
         why = h->poly.sparse ? "the solver must be FEASTHIP_SOLVER_LU, _BICGSTAB, _COCG or _GMRES" : "the solver of a dense polynomial handle must be FEASTHIP_SOLVER_LU";
     else if (h->factor_precision != 64) why = "factor_precision = 32 is not supported (complex128 factors only)";
@@ -461,6 +553,14 @@ static int poly_check(feasthip_ctx* h, const char* what, int64_t m, int64_t maxm
             if (h->node_ids[e] != e) { why = "a node range or list is not supported (the whole contour on one rank)"; break; }
     if (why) { h->last_error = std::string(what) + ": " + why; return FEASTHIP_ERROR_FPM; }
     if (m <= 0 || m > maxm) { h->last_error = std::string(what) + ": block width out of range"; return FEASTHIP_ERROR_M0; }
+    return 0;
+}
+// a feasthip_nep_* call that solves with T(z_e): the node table belongs to the handle's contour
+static int nep_check_nodes(feasthip_ctx* h, const char* what) {
+    const size_t ne = h->zne.size();
+    bool ok = ne > 0 && h->poly.fnode_z.size() == ne && h->poly.fnode.size() == ne * (size_t)(h->poly.degree + 1);
+    for (size_t e = 0; ok && e < ne; ++e) ok = h->poly.fnode_z[e].x == h->zne[e].x && h->poly.fnode_z[e].y == h->zne[e].y;
+    if (!ok) { h->last_error = std::string(what) + ": no node values for the current contour (feasthip_set_contour, then feasthip_nep_set_node_values)"; return FEASTHIP_ERROR_FPM; }
     return 0;
 }
 
@@ -477,6 +577,18 @@ static double poly_bwd_scale(const feasthip_ctx* h, double la) {
     double scale = 0.0, pw = 1.0;
     for (int k = 0; k <= h->poly.degree; ++k) { scale += pw * h->poly.fro[k]; pw *= la; }
     return scale;
+}
+
+// its sibling for a term handle: sum_k |f[k]| ||A_k||_F from one row of a table
+static double nep_bwd_scale(const feasthip_ctx* h, const cplx* f) {
+    double scale = 0.0;
+    for (int k = 0; k <= h->poly.degree; ++k) scale += std::hypot(f[k].x, f[k].y) * h->poly.fro[k];
+    return scale;
+}
+static bool nep_row_finite(const feasthip_ctx* h, const cplx* f) {
+    for (int k = 0; k <= h->poly.degree; ++k)
+        if (!std::isfinite(f[k].x) || !std::isfinite(f[k].y)) return false;
+    return true;
 }
 
 // small synchronous host -> device copy into a named workspace
@@ -575,11 +687,14 @@ static int poly_lin_product(feasthip_ctx* h, const poly_coefs& pc, int which, in
 // message).  poly_set_begin: the handle's problem replaced by an empty polynomial of this size.  poly_sumsq: the sum of squares
 // of n doubles, for ||A_k||_F of the backward error (ingest arithmetic, once per problem).  poly_set_commit: the handle is a
 // polynomial one.
-static int poly_set_check(feasthip_ctx* h, const char* what, int64_t N, int64_t Nmax, int degree) {
+static int poly_set_check(feasthip_ctx* h, const char* what, int64_t N, int64_t Nmax, int degree, bool terms = false) {
     if (!h) return FEASTHIP_ERROR_INTERNAL;
     if (h->poisoned) { h->last_error = "handle poisoned by an earlier device failure: destroy it"; return FEASTHIP_ERROR_INTERNAL; }
     if (N <= 0 || N > Nmax) { h->last_error = std::string(what) + ": N out of range"; return FEASTHIP_ERROR_N; }
-    if (degree < 1 || degree > FEASTHIP_POLY_MAX_DEGREE) { h->last_error = std::string(what) + ": degree must be 1 .. FEASTHIP_POLY_MAX_DEGREE"; return FEASTHIP_ERROR_FPM; }
+    if (degree < 1 || degree > FEASTHIP_POLY_MAX_DEGREE) {
+        h->last_error = std::string(what) + (terms ? ": nterms must be 2 .. FEASTHIP_POLY_MAX_DEGREE + 1" : ": degree must be 1 .. FEASTHIP_POLY_MAX_DEGREE");
+        return FEASTHIP_ERROR_FPM;
+    }
     return 0;
 }
 static int poly_set_begin(feasthip_ctx* h, int64_t N, int degree, int is_complex) {
@@ -595,19 +710,22 @@ static double poly_sumsq(const double* v, size_t n) {
     for (size_t i = 0; i < n; ++i) s += v[i] * v[i];
     return s;
 }
-static int poly_set_commit(feasthip_ctx* h) {
+static int poly_set_commit(feasthip_ctx* h, bool terms = false) {
     h->adjoint = 0;
     h->kind = 3;
+    h->poly.terms = terms ? 1 : 0;
+    if (terms) { h->solver = FEASTHIP_SOLVER_LU; h->shifted = h->block = 0; h->factor_precision = 64; }
     return 0;
 }
 
-extern "C" int feasthip_set_polynomial(feasthip_handle h, int64_t N, int degree, int is_complex, const void* const* coeffs,
-                                       const int64_t* ld) {
-    int rc = poly_set_check(h, "feasthip_set_polynomial", N, 65536, degree);
+// (both setters: `what` the entry point's name; terms: the matrices are the A_k of a split form, feasthip_set_terms[_csr])
+static int poly_set_dense(feasthip_ctx* h, const std::string& what, bool terms, int64_t N, int degree, int is_complex, const void* const* coeffs,
+                          const int64_t* ld) {
+    int rc = poly_set_check(h, what.c_str(), N, 65536, degree, terms);
     if (rc) return rc;
-    if (!coeffs || !ld) { h->last_error = "feasthip_set_polynomial: null argument"; return FEASTHIP_ERROR_N; }
+    if (!coeffs || !ld) { h->last_error = what + ": null argument"; return FEASTHIP_ERROR_N; }
     for (int k = 0; k <= degree; ++k)
-        if (!coeffs[k] || ld[k] < N) { h->last_error = "feasthip_set_polynomial: bad coefficient pointer or leading dimension"; return FEASTHIP_ERROR_N; }
+        if (!coeffs[k] || ld[k] < N) { h->last_error = what + ": bad coefficient pointer or leading dimension"; return FEASTHIP_ERROR_N; }
     if ((rc = poly_set_begin(h, N, degree, is_complex))) return rc;
     const size_t es = is_complex ? sizeof(cplx) : sizeof(double), per = is_complex ? 2 : 1;
     for (int k = 0; k <= degree; ++k) {
@@ -617,31 +735,38 @@ extern "C" int feasthip_set_polynomial(feasthip_handle h, int64_t N, int degree,
         for (int64_t j = 0; j < N; ++j) s += poly_sumsq((const double*)coeffs[k] + (size_t)j * ld[k] * per, (size_t)N * per);
         h->poly.fro[k] = std::sqrt(s);
     }
-    return poly_set_commit(h);
+    return poly_set_commit(h, terms);
+}
+extern "C" int feasthip_set_polynomial(feasthip_handle h, int64_t N, int degree, int is_complex, const void* const* coeffs,
+                                       const int64_t* ld) {
+    return poly_set_dense(h, "feasthip_set_polynomial", false, N, degree, is_complex, coeffs, ld);
+}
+extern "C" int feasthip_set_terms(feasthip_handle h, int64_t N, int nterms, int is_complex, const void* const* mats, const int64_t* ld) {
+    return poly_set_dense(h, "feasthip_set_terms", true, N, nterms - 1, is_complex, mats, ld);
 }
 
 // Sparse coefficients on one CSR pattern (0-based, columns strictly increasing inside a row, so no duplicates): the multifrontal
 // LU of P(z_e) (fh_banded.hip plans it, k_mf_assemble_poly forms the fronts) in place of the dense one, k_spmm_fan in place of
 // the dense product.  The pattern is kept in the caller's order (no renumbering: the multifrontal plan brings its own).
-extern "C" int feasthip_set_polynomial_csr(feasthip_handle h, int64_t N, int degree, int is_complex, const int64_t* rowptr,
-                                           const int64_t* col, const void* const* vals) {
-    int rc = poly_set_check(h, "feasthip_set_polynomial_csr", N, INT32_MAX / FH_MAX_LD / FEASTHIP_POLY_MAX_DEGREE, degree);
+static int poly_set_csr(feasthip_ctx* h, const std::string& what, bool terms, int64_t N, int degree, int is_complex, const int64_t* rowptr,
+                        const int64_t* col, const void* const* vals) {
+    int rc = poly_set_check(h, what.c_str(), N, INT32_MAX / FH_MAX_LD / FEASTHIP_POLY_MAX_DEGREE, degree, terms);
     if (rc) return rc;
-    if (!rowptr || !vals) { h->last_error = "feasthip_set_polynomial_csr: null argument"; return FEASTHIP_ERROR_N; }
-    if (rowptr[0] != 0) { h->last_error = "feasthip_set_polynomial_csr: rowptr[0] must be 0"; return FEASTHIP_ERROR_N; }
+    if (!rowptr || !vals) { h->last_error = what + ": null argument"; return FEASTHIP_ERROR_N; }
+    if (rowptr[0] != 0) { h->last_error = what + ": rowptr[0] must be 0"; return FEASTHIP_ERROR_N; }
     for (int64_t i = 0; i < N; ++i)
-        if (rowptr[i + 1] < rowptr[i]) { h->last_error = "feasthip_set_polynomial_csr: row pointers not monotone at row " + std::to_string(i); return FEASTHIP_ERROR_N; }
+        if (rowptr[i + 1] < rowptr[i]) { h->last_error = what + ": row pointers not monotone at row " + std::to_string(i); return FEASTHIP_ERROR_N; }
     const int64_t nnz = rowptr[N];
-    if (nnz > INT32_MAX) { h->last_error = "feasthip_set_polynomial_csr: more than 2^31 - 1 nonzeros"; return FEASTHIP_ERROR_N; }
-    if (nnz > 0 && !col) { h->last_error = "feasthip_set_polynomial_csr: null column array"; return FEASTHIP_ERROR_N; }
+    if (nnz > INT32_MAX) { h->last_error = what + ": more than 2^31 - 1 nonzeros"; return FEASTHIP_ERROR_N; }
+    if (nnz > 0 && !col) { h->last_error = what + ": null column array"; return FEASTHIP_ERROR_N; }
     for (int k = 0; k <= degree; ++k)
-        if (nnz > 0 && !vals[k]) { h->last_error = "feasthip_set_polynomial_csr: null value array of coefficient " + std::to_string(k); return FEASTHIP_ERROR_N; }
+        if (nnz > 0 && !vals[k]) { h->last_error = what + ": null value array of coefficient " + std::to_string(k); return FEASTHIP_ERROR_N; }
     std::vector<int> rp((size_t)N + 1), cl((size_t)nnz);
     for (int64_t i = 0; i < N; ++i) {
         rp[i] = (int)rowptr[i];
         for (int64_t k = rowptr[i]; k < rowptr[i + 1]; ++k) {
-            if (col[k] < 0 || col[k] >= N) { h->last_error = "feasthip_set_polynomial_csr: column index out of range in row " + std::to_string(i); return FEASTHIP_ERROR_N; }
-            if (k > rowptr[i] && col[k] <= col[k - 1]) { h->last_error = "feasthip_set_polynomial_csr: columns of row " + std::to_string(i) + " are not strictly increasing"; return FEASTHIP_ERROR_N; }
+            if (col[k] < 0 || col[k] >= N) { h->last_error = what + ": column index out of range in row " + std::to_string(i); return FEASTHIP_ERROR_N; }
+            if (k > rowptr[i] && col[k] <= col[k - 1]) { h->last_error = what + ": columns of row " + std::to_string(i) + " are not strictly increasing"; return FEASTHIP_ERROR_N; }
             cl[k] = (int)col[k];
         }
     }
@@ -661,7 +786,40 @@ extern "C" int feasthip_set_polynomial_csr(feasthip_handle h, int64_t N, int deg
         h->poly.fro[k] = std::sqrt(poly_sumsq((const double*)vals[k], (size_t)nnz * (is_complex ? 2 : 1)));      // (the explicit zeros add nothing)
     }
     h->host_rowptr.swap(rp); h->host_col.swap(cl);
-    return poly_set_commit(h);
+    return poly_set_commit(h, terms);
+}
+extern "C" int feasthip_set_polynomial_csr(feasthip_handle h, int64_t N, int degree, int is_complex, const int64_t* rowptr,
+                                           const int64_t* col, const void* const* vals) {
+    return poly_set_csr(h, "feasthip_set_polynomial_csr", false, N, degree, is_complex, rowptr, col, vals);
+}
+extern "C" int feasthip_set_terms_csr(feasthip_handle h, int64_t N, int nterms, int is_complex, const int64_t* rowptr, const int64_t* col,
+                                      const void* const* vals) {
+    return poly_set_csr(h, "feasthip_set_terms_csr", true, N, nterms - 1, is_complex, rowptr, col, vals);
+}
+
+// The node table of a term handle: F[e * nterms + k] = f_k(z_e) for the contour set last.  Factors cached for other values are dropped.
+extern "C" int feasthip_nep_set_node_values(feasthip_handle h, int ne, const void* F_host) {
+    int rc = poly_check(h, "feasthip_nep_set_node_values", 1, 1, POLY_TERMS);
+    if (rc) return rc;
+    const int nt = h->poly.degree + 1;
+    if (!F_host || ne != (int)h->zne.size() || ne <= 0) {
+        h->last_error = "feasthip_nep_set_node_values: ne must be the node count of the contour set before (feasthip_set_contour), F not null";
+        return FEASTHIP_ERROR_FPM;
+    }
+    const cplx* F = (const cplx*)F_host;
+    for (int i = 0; i < ne * nt; ++i)
+        if (!std::isfinite(F[i].x) || !std::isfinite(F[i].y)) {
+            h->last_error = "feasthip_nep_set_node_values: f_" + std::to_string(i % nt) + " is not finite at contour node " + std::to_string(i / nt);
+            return FEASTHIP_ERROR_FPM;
+        }
+    bool same = h->poly.fnode.size() == (size_t)ne * nt && h->poly.fnode_z.size() == (size_t)ne;
+    for (int i = 0; same && i < ne * nt; ++i) same = h->poly.fnode[i].x == F[i].x && h->poly.fnode[i].y == F[i].y;
+    for (int e = 0; same && e < ne; ++e) same = h->poly.fnode_z[e].x == h->zne[e].x && h->poly.fnode_z[e].y == h->zne[e].y;
+    if (same) return 0;
+    if ((rc = feasthip_release_factors(h))) return rc;          // the cache matches by z_e alone
+    h->poly.fnode.assign(F, F + (size_t)ne * nt);
+    h->poly.fnode_z = h->zne;
+    return 0;
 }
 
 // Krylov solves P(z_e) Y_e = RHS for the nodes z (one right-hand-side panel shared by all of them), from a zero start, under the
@@ -728,11 +886,10 @@ struct poly_iter_record {
 };
 
 // Y = P(z)^-1 R, N x m column-major; the factor is cached in the slot of the contour node z equals, else in one extra slot
-extern "C" int feasthip_poly_solve_dev(feasthip_handle h, double z_re, double z_im, int64_t m64, const void* dR, void* dY,
-                                       feasthip_stats* stats) {
-    int rc = poly_check(h, "feasthip_poly_solve_dev", m64, 1 << 20);       // right-hand sides, not a subspace: any count
-    if (rc) return rc;
-    if (!dR || !dY) { h->last_error = "feasthip_poly_solve_dev: null argument"; return FEASTHIP_ERROR_INTERNAL; }
+static int poly_solve_body(feasthip_ctx* h, const std::string& what, double z_re, double z_im, int64_t m64, const void* dR, void* dY,
+                           feasthip_stats* stats) {
+    int rc;
+    if (!dR || !dY) { h->last_error = what + ": null argument"; return FEASTHIP_ERROR_INTERNAL; }
     FH_CHECK(hipSetDevice(h->device));
     const double t0 = poly_now();
     const int N = (int)h->dense.N;
@@ -759,6 +916,18 @@ extern "C" int feasthip_poly_solve_dev(feasthip_handle h, double z_re, double z_
     if (poly_krylov(h)) rec.publish(h, it, stats);
     if (stats) stats->seconds_total = poly_now() - t0;
     return worst;
+}
+extern "C" int feasthip_poly_solve_dev(feasthip_handle h, double z_re, double z_im, int64_t m64, const void* dR, void* dY,
+                                       feasthip_stats* stats) {
+    const int rc = poly_check(h, "feasthip_poly_solve_dev", m64, 1 << 20);       // right-hand sides, not a subspace: any count
+    return rc ? rc : poly_solve_body(h, "feasthip_poly_solve_dev", z_re, z_im, m64, dR, dY, stats);
+}
+// Term handle: Y = T(z_e)^-1 R for the contour node `node`, N x m column-major, on the cached factor of that node
+extern "C" int feasthip_nep_solve_dev(feasthip_handle h, int node, int64_t m64, const void* dR, void* dY, feasthip_stats* stats) {
+    int rc = poly_check(h, "feasthip_nep_solve_dev", m64, 1 << 20, POLY_TERMS);
+    if (rc || (rc = nep_check_nodes(h, "feasthip_nep_solve_dev"))) return rc;
+    if (node < 0 || node >= (int)h->zne.size()) { h->last_error = "feasthip_nep_solve_dev: node index outside the contour"; return FEASTHIP_ERROR_FPM; }
+    return poly_solve_body(h, "feasthip_nep_solve_dev", h->zne[node].x, h->zne[node].y, m64, dR, dY, stats);
 }
 
 // Qproj = sum_e weight_scale w_e (z_e B_lin - A_lin)^-1 (B_lin Q) on dN x m column-major blocks
@@ -1059,9 +1228,21 @@ static int poly_eval_panel(feasthip_ctx* h, const poly_coefs& pc, int ld, const 
         memset(&a, 0, sizeof(a));
         a.rowptr = h->csr.rowptr; a.col = h->csr.col; a.X = X; a.lam = dlam; a.Y = R; a.N = N; a.d = d;
         a.val = fh_poly_coef_ptrs(h);
-        fh_prof_begin(h, "poly_horner");
-        POLY_LAUNCH_CSR(k_spmm_horner, ld, dim3((unsigned)((N + FH_BLOCK / ld - 1) / (FH_BLOCK / ld))), a);
+        const dim3 grid((unsigned)((N + FH_BLOCK / ld - 1) / (FH_BLOCK / ld)));
+        fh_prof_begin(h, h->poly.terms ? "terms_spmm" : "poly_horner");
+        if (h->poly.terms) POLY_LAUNCH_CSR(k_spmm_terms, ld, grid, a);
+        else POLY_LAUNCH_CSR(k_spmm_horner, ld, grid, a);
         fh_prof_end(h);
+        return 0;
+    }
+    if (h->poly.terms) {          // R = sum_k A_k (X diag F[k]): the copy of X scaled by row k of the table, per term
+        for (int k = 0; k <= d; ++k) {
+            FH_CHECK(hipMemcpyAsync(W, X, (size_t)N * ld * sizeof(cplx), hipMemcpyDeviceToDevice, h->stream));
+            fh_prof_begin(h, "terms_scale");
+            fh_launch_scale_cols(W, dlam + (size_t)k * ld, N, ld, h->stream);
+            fh_prof_end(h);
+            poly_product(h, pc, ld, k, W, R, k > 0, false);
+        }
         return 0;
     }
     FH_CHECK(hipMemcpyAsync(W, X, (size_t)N * ld * sizeof(cplx), hipMemcpyDeviceToDevice, h->stream));
@@ -1076,9 +1257,18 @@ static int poly_eval_panel(feasthip_ctx* h, const poly_coefs& pc, int ld, const 
     return 0;
 }
 
-// ld device values: v[c0 .. c0 + m) of the host array, zero padded; a non-finite entry is replaced by `instead`
+// ld device values: v[c0 .. c0 + m) of the host array, zero padded; a non-finite entry is replaced by `instead`.  (Term handle:
+// v is the caller's m x (degree + 1) table of the f_k per column, uploaded term-major for poly_eval_panel.)
 static int poly_upload_cols(feasthip_ctx* h, const char* name, const cplx* v, int64_t c0, int m, int ld, cplx instead, cplx** dev) {
     std::vector<cplx> p(ld, cmake(0, 0));
+    if (h->poly.terms) {          // v: rows of degree + 1 values per column -> the term-major table; a non-finite row becomes zero
+        const int nt = h->poly.degree + 1;
+        p.assign((size_t)nt * ld, cmake(0, 0));
+        for (int c = 0; c < m; ++c)
+            if (nep_row_finite(h, v + (size_t)(c0 + c) * nt))
+                for (int k = 0; k < nt; ++k) p[(size_t)k * ld + c] = v[(size_t)(c0 + c) * nt + k];
+        return poly_upload(h, name, p, dev);
+    }
     for (int c = 0; c < m; ++c) {
         const cplx x = v[c0 + c];
         p[c] = std::isfinite(x.x) && std::isfinite(x.y) ? x : instead;
@@ -1087,10 +1277,9 @@ static int poly_upload_cols(feasthip_ctx* h, const char* name, const cplx* v, in
 }
 
 // R[:, j] = P(lambda_j) X[:, j], N x m column-major, lambda: m complex values on the host
-extern "C" int feasthip_poly_eval_cols_dev(feasthip_handle h, int64_t m64, const void* lambda, const void* dX, void* dR) {
-    int rc = poly_check(h, "feasthip_poly_eval_cols_dev", m64, 1 << 20);
-    if (rc) return rc;
-    if (!lambda || !dX || !dR) { h->last_error = "feasthip_poly_eval_cols_dev: null argument"; return FEASTHIP_ERROR_INTERNAL; }
+static int poly_eval_cols_body(feasthip_ctx* h, const std::string& what, int64_t m64, const void* lambda, const void* dX, void* dR) {
+    int rc;
+    if (!lambda || !dX || !dR) { h->last_error = what + ": null argument"; return FEASTHIP_ERROR_INTERNAL; }
     FH_CHECK(hipSetDevice(h->device));
     const int N = (int)h->dense.N;
     poly_coefs pc;
@@ -1109,28 +1298,37 @@ extern "C" int feasthip_poly_eval_cols_dev(feasthip_handle h, int64_t m64, const
     }
     return poly_finish(h);
 }
+extern "C" int feasthip_poly_eval_cols_dev(feasthip_handle h, int64_t m64, const void* lambda, const void* dX, void* dR) {
+    const int rc = poly_check(h, "feasthip_poly_eval_cols_dev", m64, 1 << 20);
+    return rc ? rc : poly_eval_cols_body(h, "feasthip_poly_eval_cols_dev", m64, lambda, dX, dR);
+}
+// Term handle: R[:, j] = sum_k F[j][k] A_k X[:, j], N x m column-major, F: m x nterms on the host
+extern "C" int feasthip_nep_eval_cols_dev(feasthip_handle h, int64_t m64, const void* F_host, const void* dX, void* dR) {
+    const int rc = poly_check(h, "feasthip_nep_eval_cols_dev", m64, 1 << 20, POLY_TERMS);
+    return rc ? rc : poly_eval_cols_body(h, "feasthip_nep_eval_cols_dev", m64, F_host, dX, dR);
+}
 
 // The contour step of the projected method on an N x m block.
 //   sigma == null:  Q = sum_e w_e P(z_e)^-1 X                                                  (plain sweep)
 //   else         :  R[:, j] = P(sigma_j) x_j,  Y_e = P(z_e)^-1 R,  Q[:, j] = sum_e w_e (x_j - Y_e[:, j]) / (z_e - sigma_j)
 // One right-hand side panel is shared by all nodes; the factors come from the per-node cache as in the linearised sweep.
-extern "C" int feasthip_poly_resinv_apply_dev(feasthip_handle h, int64_t m64, const void* sigma, const void* dX, void* dQ,
-                                              int* node_status, feasthip_stats* stats) {
-    int rc = poly_check(h, "feasthip_poly_resinv_apply_dev", m64, 1 << 20);
-    if (rc) return rc;
-    if (!dX || !dQ) { h->last_error = "feasthip_poly_resinv_apply_dev: null argument"; return FEASTHIP_ERROR_INTERNAL; }
-    if (h->zne.empty()) { h->last_error = "feasthip_poly_resinv_apply_dev: no contour set (feasthip_set_contour)"; return FEASTHIP_ERROR_FPM; }
-    if (h->real_projection) { h->last_error = "feasthip_poly_resinv_apply_dev: the real projection does not apply to a polynomial sweep"; return FEASTHIP_ERROR_FPM; }
+// (ftab: a term handle's m x nterms table f_k(sigma_j), which takes the place of the powers of sigma_j)
+static int poly_resinv_body(feasthip_ctx* h, const std::string& what, int64_t m64, const void* sigma, const void* ftab, const void* dX, void* dQ,
+                            int* node_status, feasthip_stats* stats) {
+    int rc;
+    if (!dX || !dQ) { h->last_error = what + ": null argument"; return FEASTHIP_ERROR_INTERNAL; }
+    if (h->zne.empty()) { h->last_error = what + ": no contour set (feasthip_set_contour)"; return FEASTHIP_ERROR_FPM; }
+    if (h->real_projection) { h->last_error = what + ": the real projection does not apply to a polynomial sweep"; return FEASTHIP_ERROR_FPM; }
     const int N = (int)h->dense.N, ne = (int)h->zne.size();
     const cplx* sg = (const cplx*)sigma;
     if (sg)
         for (int64_t j = 0; j < m64; ++j) {
-            if (!std::isfinite(sg[j].x) || !std::isfinite(sg[j].y)) { h->last_error = "feasthip_poly_resinv_apply_dev: shift " + std::to_string(j) + " is not finite"; return FEASTHIP_ERROR_FPM; }
+            if (!std::isfinite(sg[j].x) || !std::isfinite(sg[j].y)) { h->last_error = what + ": shift " + std::to_string(j) + " is not finite"; return FEASTHIP_ERROR_FPM; }
             for (int e = 0; e < ne; ++e) {
                 const cplx z = h->zne[e];
                 const double dist = std::hypot(z.x - sg[j].x, z.y - sg[j].y), scale = std::max(std::hypot(z.x, z.y), std::hypot(sg[j].x, sg[j].y));
                 if (dist <= 4.0 * 2.220446049250313e-16 * scale || dist == 0.0) {
-                    h->last_error = "feasthip_poly_resinv_apply_dev: shift " + std::to_string(j) + " coincides with contour node " + std::to_string(e);
+                    h->last_error = what + ": shift " + std::to_string(j) + " coincides with contour node " + std::to_string(e);
                     return FEASTHIP_ERROR_FPM;
                 }
             }
@@ -1162,7 +1360,7 @@ extern "C" int feasthip_poly_resinv_apply_dev(feasthip_handle h, int64_t m64, co
         fh_launch_to_panel((const cplx*)dX + (size_t)c0 * N, N, N, m, Xs, ld, h->stream);
         const cplx* rhs = Xs;
         if (sg) {
-            if ((rc = poly_upload_cols(h, "ri_lam", sg, c0, m, ld, cmake(0, 0), &dlam))) return rc;
+            if ((rc = poly_upload_cols(h, "ri_lam", ftab ? (const cplx*)ftab : sg, c0, m, ld, cmake(0, 0), &dlam))) return rc;
             if ((rc = poly_eval_panel(h, pc, ld, dlam, Xs, W, R))) return rc;
             rhs = R;
         }
@@ -1182,11 +1380,31 @@ extern "C" int feasthip_poly_resinv_apply_dev(feasthip_handle h, int64_t m64, co
     if (stats) stats->seconds_total = poly_now() - t0;
     return 0;
 }
+extern "C" int feasthip_poly_resinv_apply_dev(feasthip_handle h, int64_t m64, const void* sigma, const void* dX, void* dQ,
+                                              int* node_status, feasthip_stats* stats) {
+    const int rc = poly_check(h, "feasthip_poly_resinv_apply_dev", m64, 1 << 20);
+    return rc ? rc : poly_resinv_body(h, "feasthip_poly_resinv_apply_dev", m64, sigma, nullptr, dX, dQ, node_status, stats);
+}
+// Term handle: the same contour step with T in place of P.  sigma and F_sigma (m x nterms on the host, F_sigma[j][k] =
+// f_k(sigma_j)) both null: the plain sweep; both given: the residual-inverse sweep.
+extern "C" int feasthip_nep_resinv_apply_dev(feasthip_handle h, int64_t m64, const void* sigma, const void* F_sigma, const void* dX, void* dQ,
+                                             int* node_status, feasthip_stats* stats) {
+    int rc = poly_check(h, "feasthip_nep_resinv_apply_dev", m64, 1 << 20, POLY_TERMS);
+    if (rc || (rc = nep_check_nodes(h, "feasthip_nep_resinv_apply_dev"))) return rc;
+    if ((sigma == nullptr) != (F_sigma == nullptr)) { h->last_error = "feasthip_nep_resinv_apply_dev: sigma and F_sigma go together (both null: the plain sweep)"; return FEASTHIP_ERROR_FPM; }
+    if (F_sigma)
+        for (int64_t j = 0; j < m64; ++j)
+            if (!nep_row_finite(h, (const cplx*)F_sigma + j * (h->poly.degree + 1))) {
+                h->last_error = "feasthip_nep_resinv_apply_dev: the table row of shift " + std::to_string(j) + " is not finite";
+                return FEASTHIP_ERROR_FPM;
+            }
+    return poly_resinv_body(h, "feasthip_nep_resinv_apply_dev", m64, sigma, F_sigma, dX, dQ, node_status, stats);
+}
 
 // Ahat_k = Q^H A_k Q, k = 0 .. d: d + 1 r x r column-major matrices one behind the other on the host.  Per 64-column panel Q_j
 // the products W_k = A_k Q_j (sparse: one fan-out launch), then one Gram launch per block (i, j) and coefficient.
 extern "C" int feasthip_poly_project_reduced_dev(feasthip_handle h, int64_t r64, const void* dQ, void* Ahat_host) {
-    int rc = poly_check(h, "feasthip_poly_project_reduced_dev", r64, h && h->kind == 3 ? h->dense.N : 1);
+    int rc = poly_check(h, "feasthip_poly_project_reduced_dev", r64, h && h->kind == 3 ? h->dense.N : 1, POLY_ANY_FORM);
     if (rc) return rc;
     if (!dQ || !Ahat_host) { h->last_error = "feasthip_poly_project_reduced_dev: null argument"; return FEASTHIP_ERROR_INTERNAL; }
     FH_CHECK(hipSetDevice(h->device));
@@ -1208,12 +1426,12 @@ extern "C" int feasthip_poly_project_reduced_dev(feasthip_handle h, int64_t r64,
 // X = Q Y (N x ncand; Q: N x r, Y: r x ncand column-major on the host), every column scaled to unit length, and
 //   backward_error[i] = || P(theta_i) x_i || / sum_k |theta_i|^k ||A_k||_F
 // (+inf for a non-finite theta_i and for a column of zero length).  backward_error may be null.
-extern "C" int feasthip_poly_ritz_eval_dev(feasthip_handle h, int64_t r64, const void* dQ, int64_t ncand, const void* Y_host,
-                                           const void* theta, void* dX, double* backward_error) {
-    int rc = poly_check(h, "feasthip_poly_ritz_eval_dev", r64, h && h->kind == 3 ? h->dense.N : 1);
-    if (rc) return rc;
-    if (!dQ || !Y_host || !dX || dQ == dX || (backward_error && !theta)) { h->last_error = "feasthip_poly_ritz_eval_dev: null argument, or X aliases Q"; return FEASTHIP_ERROR_INTERNAL; }
-    if (ncand < 1 || ncand > (1 << 20)) { h->last_error = "feasthip_poly_ritz_eval_dev: candidate count out of range"; return FEASTHIP_ERROR_M0; }
+// (term handle: theta is the ncand x nterms table f_k(theta_i) instead)
+static int poly_ritz_eval_body(feasthip_ctx* h, const std::string& what, int64_t r64, const void* dQ, int64_t ncand, const void* Y_host,
+                               const void* theta, void* dX, double* backward_error) {
+    int rc;
+    if (!dQ || !Y_host || !dX || dQ == dX || (backward_error && !theta)) { h->last_error = what + ": null argument, or X aliases Q"; return FEASTHIP_ERROR_INTERNAL; }
+    if (ncand < 1 || ncand > (1 << 20)) { h->last_error = what + ": candidate count out of range"; return FEASTHIP_ERROR_M0; }
     FH_CHECK(hipSetDevice(h->device));
     const int N = (int)h->dense.N, r = (int)r64;
     const int ld = (r > FH_MAX_LD || ncand > FH_MAX_LD) ? FH_MAX_LD : fh_pick_ld(std::max<int64_t>(r, ncand));
@@ -1243,10 +1461,10 @@ extern "C" int feasthip_poly_ritz_eval_dev(feasthip_handle h, int64_t r64, const
         FH_CHECK(hipMemcpyAsync(dots.data(), ddots, dots.size() * sizeof(cplx), hipMemcpyDeviceToHost, h->stream));
         FH_CHECK(hipStreamSynchronize(h->stream));
         for (int c = 0; c < mj; ++c) {
-            const cplx t = th[(int64_t)j * ld + c];
+            const cplx* t = th + ((int64_t)j * ld + c) * (h->poly.terms ? h->poly.degree + 1 : 1);
             double be = INFINITY;
-            if (std::isfinite(t.x) && std::isfinite(t.y) && dots[c].x > 0.0) {
-                const double scale = poly_bwd_scale(h, std::hypot(t.x, t.y));
+            if ((h->poly.terms ? nep_row_finite(h, t) : std::isfinite(t->x) && std::isfinite(t->y)) && dots[c].x > 0.0) {
+                const double scale = h->poly.terms ? nep_bwd_scale(h, t) : poly_bwd_scale(h, std::hypot(t->x, t->y));
                 be = scale > 0.0 ? std::sqrt(dots[ld + c].x) / scale : 0.0;
                 if (!std::isfinite(be)) be = INFINITY;
             }
@@ -1254,4 +1472,16 @@ extern "C" int feasthip_poly_ritz_eval_dev(feasthip_handle h, int64_t r64, const
         }
     }
     return poly_finish(h);
+}
+extern "C" int feasthip_poly_ritz_eval_dev(feasthip_handle h, int64_t r64, const void* dQ, int64_t ncand, const void* Y_host,
+                                           const void* theta, void* dX, double* backward_error) {
+    const int rc = poly_check(h, "feasthip_poly_ritz_eval_dev", r64, h && h->kind == 3 ? h->dense.N : 1);
+    return rc ? rc : poly_ritz_eval_body(h, "feasthip_poly_ritz_eval_dev", r64, dQ, ncand, Y_host, theta, dX, backward_error);
+}
+// Term handle: X = Q Y with unit columns and backward_error[i] = || sum_k F_theta[i][k] A_k x_i || / sum_k |F_theta[i][k]| ||A_k||_F
+// (F_theta: ncand x nterms on the host; +inf for a non-finite row and for a column of zero length)
+extern "C" int feasthip_nep_ritz_eval_dev(feasthip_handle h, int64_t r64, const void* dQ, int64_t ncand, const void* Y_host,
+                                          const void* F_theta, void* dX, double* backward_error) {
+    const int rc = poly_check(h, "feasthip_nep_ritz_eval_dev", r64, h && h->kind == 3 ? h->dense.N : 1, POLY_TERMS);
+    return rc ? rc : poly_ritz_eval_body(h, "feasthip_nep_ritz_eval_dev", r64, dQ, ncand, Y_host, F_theta, dX, backward_error);
 }

@@ -503,13 +503,14 @@ class HipEngine:
         return dY, rc
 
     # -- polynomial eigenproblems (feasthip_poly_*): linearised blocks are column-major dN x m, i.e. (m, d N) tensors ------------
-    def set_polynomial(self, coeffs):
+    def set_polynomial(self, coeffs, terms=False):
         """P(lambda) = sum_k lambda^k coeffs[k] becomes the engine's problem (feasthip_set_polynomial): dense square matrices
         of one size, real or complex; afterwards only the poly_* methods, set_contour, set_solver("direct") and free_factors
-        apply until set_problem installs a pencil again."""
+        apply until set_problem installs a pencil again.  ``terms``: the matrices are the A_k of a split form instead
+        (set_terms)."""
         mats = [np.asarray(c) for c in coeffs]
         if len(mats) < 2:
-            raise ValueError("a polynomial needs at least two coefficient matrices")
+            raise ValueError("a split form needs at least two terms" if terms else "a polynomial needs at least two coefficient matrices")
         N = mats[0].shape[0]
         for c in mats:
             if c.ndim != 2 or c.shape != (N, N):
@@ -519,18 +520,21 @@ class HipEngine:
         fs = [np.asfortranarray(c, dtype=dt) for c in mats]
         ptrs = (C.c_void_p * len(fs))(*[f.ctypes.data for f in fs])
         lds = np.full(len(fs), N, dtype=np.int64)
-        self._chk(self.lib.feasthip_set_polynomial(self.h, N, len(fs) - 1, int(cplx), ptrs, _np_ptr(lds)))
+        if terms:
+            self._chk(self.lib.feasthip_set_terms(self.h, N, len(fs), int(cplx), ptrs, _np_ptr(lds)))
+        else:
+            self._chk(self.lib.feasthip_set_polynomial(self.h, N, len(fs) - 1, int(cplx), ptrs, _np_ptr(lds)))
         self.N, self.b_identity, self.poly_degree = N, False, len(fs) - 1
         self._problem_fp = None
 
-    def set_polynomial_csr(self, rowptr, col, vals):
+    def set_polynomial_csr(self, rowptr, col, vals, terms=False):
         """The same for sparse coefficients on one CSR pattern (feasthip_set_polynomial_csr; ingest.polynomial_union_csr makes
         the arrays): rowptr / col 0-based, vals[k] the values of coeffs[k] on the pattern.  The poly_* methods work as on a
         dense polynomial; P(z_e) is factored by the multifrontal LU of the sparse direct solver (band_plan, direct_plan_flops
         and direct_plan_bytes describe it), or, after set_solver("bicgstab" | "cocg" | "gmres"), poly_solve and poly_resinv_apply
-        solve with that Krylov method on the operator P(z_e) and nothing is factored."""
+        solve with that Krylov method on the operator P(z_e) and nothing is factored.  ``terms``: set_terms_csr."""
         if len(vals) < 2:
-            raise ValueError("a polynomial needs at least two coefficient matrices")
+            raise ValueError("a split form needs at least two terms" if terms else "a polynomial needs at least two coefficient matrices")
         rp = np.ascontiguousarray(rowptr, dtype=np.int64)
         cl = np.ascontiguousarray(col, dtype=np.int64)
         N = len(rp) - 1
@@ -539,7 +543,10 @@ class HipEngine:
         if N < 1 or rp[-1] != len(cl) or any(v.shape != (len(cl),) for v in vs):
             raise ValueError("rowptr, col and the value arrays do not describe one pattern")
         ptrs = (C.c_void_p * len(vs))(*[v.ctypes.data for v in vs])
-        self._chk(self.lib.feasthip_set_polynomial_csr(self.h, N, len(vs) - 1, int(cplx), _np_ptr(rp), _np_ptr(cl), ptrs))
+        if terms:
+            self._chk(self.lib.feasthip_set_terms_csr(self.h, N, len(vs), int(cplx), _np_ptr(rp), _np_ptr(cl), ptrs))
+        else:
+            self._chk(self.lib.feasthip_set_polynomial_csr(self.h, N, len(vs) - 1, int(cplx), _np_ptr(rp), _np_ptr(cl), ptrs))
         self.N, self.b_identity, self.poly_degree = N, False, len(vs) - 1
         self._problem_fp = None
 
@@ -681,6 +688,85 @@ class HipEngine:
         self._chk(self.lib.feasthip_poly_orthonormalize_dev(self.h, int(m), C.c_void_p(dQ.data_ptr()), int(bool(unit_columns)),
                                                             float(rank_tol), C.byref(rank)))
         return rank.value
+
+    # -- nonlinear eigenproblems in split form (feasthip_nep_*): a term handle, the scalars f_k(.) as host tables --------------------
+    def set_terms(self, mats):
+        """T(lambda) = sum_k f_k(lambda) mats[k] becomes the engine's problem (feasthip_set_terms): a term handle.  The f_k stay
+        with the caller; the nep_* methods take tables of their values, poly_project_reduced and poly_orthonormalize work as on
+        a polynomial, every other poly_* method is refused."""
+        self.set_polynomial(mats, terms=True)
+
+    def set_terms_csr(self, rowptr, col, vals):
+        """The same for sparse terms on one CSR pattern (feasthip_set_terms_csr; ingest.polynomial_union_csr makes the arrays)."""
+        self.set_polynomial_csr(rowptr, col, vals, terms=True)
+
+    def _nep_table(self, F, rows, what):
+        Fc = np.ascontiguousarray(F, dtype=np.complex128)
+        if Fc.shape != (int(rows), self.poly_degree + 1):
+            raise ValueError(f"{what} needs a table of shape ({int(rows)}, {self.poly_degree + 1})")
+        return Fc
+
+    def nep_set_node_values(self, F):
+        """F[e, k] = f_k(z_e) on the contour of the last set_contour (feasthip_nep_set_node_values)."""
+        Fc = np.ascontiguousarray(F, dtype=np.complex128)
+        if Fc.ndim != 2 or Fc.shape[1] != self.poly_degree + 1:
+            raise ValueError("nep_set_node_values needs one row of nterms values per contour node")
+        self._chk(self.lib.feasthip_nep_set_node_values(self.h, Fc.shape[0], _np_ptr(Fc)))
+
+    def nep_solve(self, node, dR, m):
+        """Y = T(z_node)^-1 R on an N x m device block -> (dY, code 0 | 8); feasthip_nep_solve_dev."""
+        self._sync_stream()
+        dY = self.empty(dR.shape[0])
+        stats = FeastHipStats()
+        rc = self.lib.feasthip_nep_solve_dev(self.h, int(node), int(m), C.c_void_p(dR.data_ptr()), C.c_void_p(dY.data_ptr()), C.byref(stats))
+        self._chk(rc, ok=(0, 8))
+        self.last_stats = stats.asdict()
+        return dY, rc
+
+    def nep_eval_cols(self, dX, F, m):
+        """R[:, j] = sum_k F[j, k] A_k X[:, j] on an N x m device block (feasthip_nep_eval_cols_dev)."""
+        self._sync_stream()
+        Fc = self._nep_table(F, m, "nep_eval_cols")
+        dR = self.empty(dX.shape[0])
+        self._chk(self.lib.feasthip_nep_eval_cols_dev(self.h, int(m), _np_ptr(Fc), C.c_void_p(dX.data_ptr()), C.c_void_p(dR.data_ptr())))
+        return dR
+
+    def nep_resinv_apply(self, dX, m, sigma=None, F_sigma=None):
+        """The contour step on an N x m device block of a term handle -> (dQ, status per node, stats): the plain sweep (sigma
+        and F_sigma None), else the residual-inverse sweep with F_sigma[j, k] = f_k(sigma_j) (feasthip_nep_resinv_apply_dev)."""
+        self._sync_stream()
+        sg = Fc = None
+        if sigma is not None:
+            sg = np.ascontiguousarray(sigma, dtype=np.complex128)
+            if sg.shape != (int(m),):
+                raise ValueError("nep_resinv_apply needs one shift per column")
+        if F_sigma is not None:
+            Fc = self._nep_table(F_sigma, m, "nep_resinv_apply")
+        dQ = self.empty(dX.shape[0])
+        status = np.zeros(max(1, self.ne), dtype=np.int32)
+        stats = FeastHipStats()
+        self._chk(self.lib.feasthip_nep_resinv_apply_dev(self.h, int(m), None if sg is None else _np_ptr(sg), None if Fc is None else _np_ptr(Fc),
+                                                         C.c_void_p(dX.data_ptr()), C.c_void_p(dQ.data_ptr()), _np_ptr(status), C.byref(stats)))
+        self.last_stats = stats.asdict()
+        return dQ, status, self.last_stats
+
+    def nep_ritz_eval(self, dQ, r, Y, F_theta=None):
+        """X = Q Y with unit columns (Y: r x ncand) -> (dX, backward_error[ncand] of the pairs (theta_i, x_i) from F_theta[i, k]
+        = f_k(theta_i), or None without the table); feasthip_nep_ritz_eval_dev."""
+        self._sync_stream()
+        Yf = np.asfortranarray(Y, dtype=np.complex128)
+        ncand = Yf.shape[1]
+        if Yf.shape[0] != int(r):
+            raise ValueError("nep_ritz_eval: Y must have r rows")
+        dX = self.empty(ncand)
+        Fc = bwd = None
+        if F_theta is not None:
+            Fc = self._nep_table(F_theta, ncand, "nep_ritz_eval")
+            bwd = np.zeros(ncand, dtype=np.float64)
+        self._chk(self.lib.feasthip_nep_ritz_eval_dev(self.h, int(r), C.c_void_p(dQ.data_ptr()), int(ncand), _np_ptr(Yf),
+                                                      None if Fc is None else _np_ptr(Fc), C.c_void_p(dX.data_ptr()),
+                                                      None if bwd is None else _np_ptr(bwd)))
+        return dX, bwd
 
     def free_factors(self):
         """Drop the cached LU / band factors of the direct solvers (feasthip_release_factors)."""

@@ -28,6 +28,7 @@ import ctypes
 import math
 import threading
 import time
+import warnings
 
 import numpy as np
 import scipy.linalg as sla
@@ -1016,16 +1017,17 @@ def feast_hip_general(engine, A, B, Emid, r, M0, fpm, *, solver="direct", solver
 POLY_RESIDUALS = ("pencil", "reference")
 
 
-def _poly_setup(engine, coeffs, Emid, r, fpm, contour, union_csr, krylov=None):
+def _poly_setup(engine, coeffs, Emid, r, fpm, contour, union_csr, krylov=None, terms=False):
     """What both polynomial drivers do before their loop: the polynomial (dense, or sparse from ``union_csr``) becomes the engine's
     problem with the direct solver, cached fp64 factors, no real projection and the full contour -> the plan fields of
     ``stats["polynomial"]`` for sparse coefficients, else None.  ``krylov`` = (solver, tol, maxiter, restart), sparse
-    coefficients only: that Krylov solver on P(z_e) instead, relative stop test (tol 0 = 10^-fpm[3]) -> {"plan": "krylov"}."""
+    coefficients only: that Krylov solver on P(z_e) instead, relative stop test (tol 0 = 10^-fpm[3]) -> {"plan": "krylov"}.
+    ``terms``: the matrices are the A_k of a split form and the handle becomes a term handle (feast_hip_nonlinear)."""
     Zne, Wne = feast_gcontour(Emid, r, fpm) if contour is None else contour
     if union_csr is None:
-        engine.set_polynomial(coeffs)
+        engine.set_polynomial(coeffs, terms=terms)
     else:
-        engine.set_polynomial_csr(*union_csr)
+        engine.set_polynomial_csr(*union_csr, terms=terms)
     if krylov is not None:
         solver, tol, maxiter, restart = krylov
         engine.set_solver(solver, rtol=feast_tolerance(fpm) if tol == 0.0 else float(tol), atol=0.0, maxit=maxiter, restart=restart,
@@ -1151,13 +1153,92 @@ def poly_select(theta, be, center, radius, keep):
     return sel, good, aside
 
 
+class ReducedSolveError(Exception):
+    """Host LAPACK failed on the small projected problem of a projected-method loop (-> Feast_ERROR_LAPACK)."""
+
+
+def _projected_loop(engine, N, M0, Emid, r, fpm, Q0, seed, eps_floor, ortho, stats, rec, sweep, reduced, evaluate, krylov=False):
+    """The loop of the projected method, shared by feast_hip_polynomial_projected and feast_hip_nonlinear; the problem is the
+    engine's already.  Per loop: ``sweep(dX, m, sigma)`` -> (dQ, status, stats) is the contour step (sigma None: the plain sweep
+    of loop 0), then unit columns and the rank-revealing orthonormalisation of ``ortho``, the projected matrices Q^H A_k Q,
+    ``reduced(Ahat, rank)`` -> (theta, Y) the candidates of the small problem (it raises ReducedSolveError when host LAPACK
+    fails; whatever else it raises is the caller's), ``evaluate(dQ, rank, Y, theta)`` -> (dXc, backward errors) on the device,
+    poly_select.  Stop test: the largest backward error among the kept pairs inside the circle.  At the loop limit the last
+    iterates are returned with info = Feast_ERROR_NO_CONVERGENCE; no candidate at all ends the loop with M = 0.  ``rec``: the
+    method's entry of ``stats``, which gets eps_history, rank, candidates, set_aside (one entry per loop) and backward_error;
+    ``krylov``: the sweeps are inexact Krylov solves, recorded per loop in rec["krylov"], and a node status 5 is no failure."""
+    X_host = seeded_subspace(N, M0, seed) if Q0 is None else np.asarray(Q0, dtype=np.complex128)
+    if X_host.shape != (N, M0):
+        raise ValueError(f"Q0 must be the start block of shape ({N}, {M0})")
+    dX = engine.upload(X_host)
+    eps_tol = max(feast_tolerance(fpm), float(eps_floor))
+    maxloop = int(fpm[4])
+    center = complex(Emid)
+    loop, m, sigma = 0, M0, None
+    rec.update({"backward_error": np.zeros(0), "eps_history": [], "rank": [], "candidates": [], "set_aside": []})
+    if krylov:
+        rec["krylov"] = []
+    no_conv = FeastError.Feast_ERROR_NO_CONVERGENCE
+    with _ortho_scope(engine, ortho, stats):
+        while True:
+            dQ, status, st = sweep(dX, m, sigma)
+            stats["factorizations"] += st.get("factorizations", 0)
+            stats["solve_seconds"] += st.get("seconds_total", 0.0)
+            if krylov:
+                stats["krylov_iterations"] += int(st.get("krylov_iterations", 0))
+                node_it = engine.last_node_iterations(len(status))
+                rec["krylov"].append({"iterations": int(node_it.max()) if len(node_it) else 0,
+                                      "node_iterations": [int(v) for v in node_it], "capped_nodes": int(np.sum(status == 5))})
+                status = np.where(status == 5, 0, status)
+            if int(np.max(status)):
+                return _empty_result(N, FeastError.Feast_ERROR_LAPACK, loop, complex_lambda=True, stats=stats)
+            rank_q = engine.poly_orthonormalize(dQ, m, SQRT_EPS, unit_columns=True)
+            _note_ortho(engine, stats)
+            if rank_q == 0:
+                return _empty_result(N, no_conv, loop, complex_lambda=True, stats=stats)
+            Ahat = engine.poly_project_reduced(dQ, rank_q)
+            try:
+                with small_lapack():
+                    theta, Y = reduced(Ahat, rank_q)
+            except ReducedSolveError:
+                return _empty_result(N, FeastError.Feast_ERROR_LAPACK, loop, complex_lambda=True, stats=stats)
+            ncand = len(theta)
+            rec["rank"].append(int(rank_q))
+            rec["candidates"].append(int(ncand))
+            if ncand == 0:
+                rec["eps_history"].append(math.inf)
+                rec["set_aside"].append(0)
+                return _empty_result(N, no_conv, loop, complex_lambda=True, stats=stats)
+            dXc, be = evaluate(dQ, rank_q, np.asfortranarray(Y), theta)
+            keep = min(M0, ncand)
+            sel, good, aside = poly_select(theta, be, center, r, keep)
+            M = int(good.sum())
+            epsout = float(be[sel][good].max()) if M else math.inf
+            rec["eps_history"].append(epsout)
+            rec["set_aside"].append(aside)
+            done = M > 0 and epsout <= eps_tol
+            if done or loop >= maxloop:
+                if M == 0:
+                    return _empty_result(N, no_conv, loop, complex_lambda=True, stats=stats)
+                idx = sel[good]
+                idx = idx[np.argsort(np.abs(theta[idx]) ** 2, kind="stable")]                 # feast_sort_general!
+                Xall = engine.download(dXc, ncand)
+                rec["backward_error"] = be[idx].copy()
+                return FeastResult(theta[idx].copy(), Xall[:, idx].copy(), M, be[idx].copy(), 0 if done else int(no_conv), epsout,
+                                   loop, stats)
+            dX = dXc[engine.torch.as_tensor(sel, device=dXc.device)].contiguous()
+            sigma = np.where(np.isfinite(theta[sel]), theta[sel], center)
+            m = keep
+            loop += 1
+
+
 def feast_hip_polynomial_projected(engine, coeffs, Emid, r, M0, fpm, *, Q0=None, seed=20260515, contour=None, eps_floor=0.0,
                                    union_csr=None, ortho="mgs", krylov=None):
     """P(lambda) x = 0 inside a circle on an N-row subspace of M0 columns: polynomial FEAST with a residual-inverse contour
-    step (Gavin, Miedlar, Polizzi).  Per loop: the contour step on the N x m block (loop 0 the plain sweep, which factors
-    P(z_e) once per node and fills the cache; afterwards R_j = P(sigma_j) x_j, Y_e = P(z_e)^-1 R, Q_j = sum_e w_e (x_j - Y_e,j)
-    / (z_e - sigma_j) on the cached factors), unit columns and the rank-revealing orthonormalisation of ``ortho``, the
-    projected polynomial Q^H A_k Q, its dr x dr companion pencil solved on the host, the backward error of ALL dr candidates,
+    step (Gavin, Miedlar, Polizzi).  Per loop (_projected_loop): the contour step on the N x m block (loop 0 the plain sweep,
+    which factors P(z_e) once per node and fills the cache; afterwards R_j = P(sigma_j) x_j, Y_e = P(z_e)^-1 R, Q_j = sum_e w_e
+    (x_j - Y_e,j) / (z_e - sigma_j) on the cached factors), unit columns and the rank-revealing orthonormalisation of ``ortho``,
+    the projected polynomial Q^H A_k Q, its dr x dr companion pencil solved on the host, the backward error of ALL dr candidates,
     poly_select.  Stop test: the largest backward error among the kept pairs inside the circle.  At the loop limit the last
     iterates are returned with info = Feast_ERROR_NO_CONVERGENCE.  ``union_csr`` and the exceptions: as feast_hip_polynomial.
     ``krylov`` = (solver, tol, maxiter, restart) with ``union_csr``: the solves of the contour step run on that Krylov solver
@@ -1173,69 +1254,192 @@ def feast_hip_polynomial_projected(engine, coeffs, Emid, r, M0, fpm, *, Q0=None,
     if krylov is not None and union_csr is None:
         raise ValueError("a Krylov solver on P(z) needs sparse coefficients (union_csr)")
     plan = _poly_setup(engine, coeffs, Emid, r, fpm, contour, union_csr, krylov)
-    X_host = seeded_subspace(N, M0, seed) if Q0 is None else np.asarray(Q0, dtype=np.complex128)
-    if X_host.shape != (N, M0):
-        raise ValueError(f"Q0 must be the start block of shape ({N}, {M0})")
-    dX = engine.upload(X_host)
-    eps_tol = max(feast_tolerance(fpm), float(eps_floor))
-    maxloop = int(fpm[4])
-    center = complex(Emid)
-    loop, m, sigma = 0, M0, None
-    poly = {"degree": d, "method": "projected", "columns": M0, "backward_error": np.zeros(0), "eps_history": [], "rank": [],
-            "candidates": [], "set_aside": []}
+    poly = {"degree": d, "method": "projected", "columns": M0}
     stats = {"krylov_iterations": 0, "factorizations": 0, "solve_seconds": 0.0, "polynomial": poly}
     if plan is not None:
         poly.update(plan)
-    if krylov is not None:
-        poly["krylov"] = []
-    no_conv = FeastError.Feast_ERROR_NO_CONVERGENCE
-    with _ortho_scope(engine, ortho, stats):
-        while True:
-            dQ, status, st = engine.poly_resinv_apply(dX, m, sigma)
-            stats["factorizations"] += st.get("factorizations", 0)
-            stats["solve_seconds"] += st.get("seconds_total", 0.0)
-            if krylov is not None:
-                stats["krylov_iterations"] += int(st.get("krylov_iterations", 0))
-                node_it = engine.last_node_iterations(len(status))
-                poly["krylov"].append({"iterations": int(node_it.max()) if len(node_it) else 0,
-                                       "node_iterations": [int(v) for v in node_it], "capped_nodes": int(np.sum(status == 5))})
-                status = np.where(status == 5, 0, status)
-            if int(np.max(status)):
-                return _empty_result(N, FeastError.Feast_ERROR_LAPACK, loop, complex_lambda=True, stats=stats)
-            rank_q = engine.poly_orthonormalize(dQ, m, SQRT_EPS, unit_columns=True)
-            _note_ortho(engine, stats)
-            if rank_q == 0:
-                return _empty_result(N, no_conv, loop, complex_lambda=True, stats=stats)
-            Ahat = engine.poly_project_reduced(dQ, rank_q)
-            try:
-                with small_lapack():
-                    theta, V = sla.eig(*_poly_companion(Ahat))
-            except Exception:
-                return _empty_result(N, FeastError.Feast_ERROR_LAPACK, loop, complex_lambda=True, stats=stats)
-            ncand = d * rank_q
-            dXc, be = engine.poly_ritz_eval(dQ, rank_q, np.asfortranarray(V[:rank_q, :]), theta)
-            keep = min(M0, ncand)
-            sel, good, aside = poly_select(theta, be, center, r, keep)
-            M = int(good.sum())
-            epsout = float(be[sel][good].max()) if M else math.inf
-            poly["eps_history"].append(epsout)
-            poly["rank"].append(int(rank_q))
-            poly["candidates"].append(int(ncand))
-            poly["set_aside"].append(aside)
-            done = M > 0 and epsout <= eps_tol
-            if done or loop >= maxloop:
-                if M == 0:
-                    return _empty_result(N, no_conv, loop, complex_lambda=True, stats=stats)
-                idx = sel[good]
-                idx = idx[np.argsort(np.abs(theta[idx]) ** 2, kind="stable")]                 # feast_sort_general!
-                Xall = engine.download(dXc, ncand)
-                poly["backward_error"] = be[idx].copy()
-                return FeastResult(theta[idx].copy(), Xall[:, idx].copy(), M, be[idx].copy(), 0 if done else int(no_conv), epsout,
-                                   loop, stats)
-            dX = dXc[engine.torch.as_tensor(sel, device=dXc.device)].contiguous()
-            sigma = np.where(np.isfinite(theta[sel]), theta[sel], center)
-            m = keep
-            loop += 1
+
+    def reduced(Ahat, rank_q):
+        try:
+            theta, V = sla.eig(*_poly_companion(Ahat))
+        except Exception as err:
+            raise ReducedSolveError(str(err)) from err
+        return theta, V[:rank_q, :]
+
+    return _projected_loop(engine, N, M0, Emid, r, fpm, Q0, seed, eps_floor, ortho, stats, poly, engine.poly_resinv_apply, reduced,
+                           engine.poly_ritz_eval, krylov=krylov is not None)
+
+
+# Host rules of feast_hip_nonlinear's reduced solve.  Beyn: singular values of the block Hankel matrix H0 below BEYN_RANK_TOL
+# times the largest are cut; a largest one below BEYN_NOISE max_j ||That(z_j)^-1||_F means an empty circle (the moments are then
+# the rounding left over by a sum that cancels) and nothing is returned.  Newton polish of a candidate: at most NEWTON_STEPS steps, derivative by a central difference of
+# the f_k with step NEWTON_FD max(1, |theta|), stop at a reduced backward error NEWTON_DONE; a polished pair that moved further
+# than NEWTON_REACH radius is rejected.
+BEYN_RANK_TOL = 1e-10
+BEYN_NOISE = 1e-10
+NEWTON_STEPS = 6
+NEWTON_FD = 1e-6
+NEWTON_DONE = 1e-14
+NEWTON_REACH = 0.1
+
+
+def nep_functions(funcs):
+    """The scalar functions of a split form as callables: a non-negative int p stands for lambda^p."""
+    out = []
+    for f in funcs:
+        if callable(f):
+            out.append(f)
+        elif isinstance(f, (int, np.integer)) and not isinstance(f, bool) and f >= 0:
+            out.append(lambda z, p=int(f): np.asarray(z, dtype=np.complex128) ** p)
+        else:
+            raise ValueError("each f_k must be a callable or a non-negative int p (for lambda^p)")
+    return out
+
+
+def nep_table(funcs, z):
+    """F[i, k] = f_k(z_i), complex128, for a 1-D array z: the only place the f_k are evaluated (never differentiated)."""
+    z = np.atleast_1d(np.asarray(z, dtype=np.complex128))
+    F = np.empty((len(z), len(funcs)), dtype=np.complex128)
+    with np.errstate(all="ignore"):
+        for k, f in enumerate(funcs):
+            v = np.asarray(f(z), dtype=np.complex128)
+            if v.shape not in ((), z.shape):
+                raise ValueError(f"f_{k} must map an array to an array of the same shape")
+            F[:, k] = v
+    return F
+
+
+def _nep_at(Ahat, frow):
+    return sum(f * A for f, A in zip(frow, Ahat))
+
+
+def nep_beyn(Ahat, funcs, center, radius, moments, reduced_nodes):
+    """Beyn's integral method for the small problem sum_k f_k(lambda) Ahat[k] on the circle, in the scaled variable
+    u = (z - center) / radius: the block moments M_p = (1 / n) sum_j u_j^{p+1} That(z_j)^-1, p < 2 moments, by the trapezoid rule
+    on reduced_nodes points with the full identity as probe, the block Hankel pair (H0, H1), the SVD of H0 cut at BEYN_RANK_TOL,
+    the eigenvalues of U0^H H1 V0 S0^-1 mapped back -> (theta[ncand], Y[r, ncand]), Y the first r rows of U0 S.  Two or more
+    moments let it return eigenvalues that share an eigenvector (one moment cannot: its rank is that of the vectors).  An
+    empty circle (BEYN_NOISE) returns no candidates."""
+    r = Ahat[0].shape[0]
+    K, n = int(moments), int(reduced_nodes)
+    u = np.exp(2j * np.pi * (np.arange(n) + 0.5) / n)
+    F = nep_table(funcs, center + radius * u)
+    Mp = np.zeros((2 * K, r, r), dtype=np.complex128)
+    scale = 0.0
+    try:          # (no f_k is called from here on: what LAPACK refuses is a ReducedSolveError)
+        for j in range(n):
+            Tinv = sla.inv(_nep_at(Ahat, F[j]), check_finite=False)
+            scale = max(scale, float(np.linalg.norm(Tinv)))
+            for p in range(2 * K):
+                Mp[p] += (u[j] ** (p + 1) / n) * Tinv
+        H0 = np.block([[Mp[i + j] for j in range(K)] for i in range(K)])
+        H1 = np.block([[Mp[i + j + 1] for j in range(K)] for i in range(K)])
+        U, s, Vh = sla.svd(H0)
+        k = int(np.sum(s > BEYN_RANK_TOL * s[0])) if s[0] > BEYN_NOISE * scale else 0
+        if k == 0:
+            return np.zeros(0, dtype=np.complex128), np.zeros((r, 0), dtype=np.complex128)
+        U0, V0 = U[:, :k], Vh[:k].conj().T
+        mu, S = sla.eig((U0.conj().T @ H1 @ V0) / s[None, :k])
+    except (np.linalg.LinAlgError, ValueError) as err:
+        raise ReducedSolveError(str(err)) from err
+    return center + radius * mu, (U0 @ S)[:r]
+
+
+def _nep_reduced_error(Ahat, fro, funcs, theta, v):
+    f = nep_table(funcs, theta)[0]
+    if not np.isfinite(f).all():
+        return math.inf, math.inf
+    res = float(np.linalg.norm(_nep_at(Ahat, f) @ v))
+    den = float(np.abs(f) @ fro)
+    return res, (res / den if den > 0 else math.inf)
+
+
+def nep_newton_polish(Ahat, funcs, theta0, v0, radius):
+    """Guarded Newton polish of one pair of the small problem: steps on the bordered system [That(theta), That'(theta) v; v^H, 0]
+    with That' from central differences of the f_k (the residual is exact, so the root is).  The polished pair is returned only
+    if it stayed finite and within NEWTON_REACH radius of its start AND (reached a reduced backward error NEWTON_DONE or ended
+    with a smaller reduced residual than it began with); otherwise the start pair, with unit v.  (An unguarded fixed number of
+    steps carries junk candidates to points of small but not converged residual inside the circle, where the loop stagnates.)"""
+    fro = np.array([np.linalg.norm(A) for A in Ahat])
+    r = len(v0)
+    nv = np.linalg.norm(v0)
+    if not (np.isfinite(theta0) and nv > 0 and np.isfinite(nv)):
+        return theta0, v0
+    v0 = v0 / nv
+    res0, be0 = _nep_reduced_error(Ahat, fro, funcs, theta0, v0)
+    theta, v, res, be = theta0, v0, res0, be0
+    for _ in range(NEWTON_STEPS):
+        if not be > NEWTON_DONE:
+            break
+        h = NEWTON_FD * max(1.0, abs(theta))
+        F = nep_table(funcs, [theta, theta + h, theta - h])
+        if not np.isfinite(F).all():
+            return theta0, v0
+        Jb = np.zeros((r + 1, r + 1), dtype=np.complex128)
+        Jb[:r, :r] = _nep_at(Ahat, F[0])
+        Jb[:r, r] = _nep_at(Ahat, (F[1] - F[2]) / (2.0 * h)) @ v
+        Jb[r, :r] = v.conj()
+        rhs = np.zeros(r + 1, dtype=np.complex128)
+        rhs[r] = 1.0
+        try:
+            with warnings.catch_warnings():
+                warnings.simplefilter("ignore")
+                sol = sla.solve(Jb, rhs, check_finite=False)
+        except (np.linalg.LinAlgError, ValueError):          # a singular or non-finite bordered matrix: keep what there is
+            break
+        nrm = np.linalg.norm(sol[:r])
+        if not (np.isfinite(sol).all() and nrm > 0):
+            return theta0, v0
+        theta, v = theta + sol[r], sol[:r] / nrm
+        res, be = _nep_reduced_error(Ahat, fro, funcs, theta, v)
+    ok = np.isfinite(theta) and np.isfinite(res) and abs(theta - theta0) <= NEWTON_REACH * radius and (be <= NEWTON_DONE or res < res0)
+    return (theta, v) if ok else (theta0, v0)
+
+
+def feast_hip_nonlinear(engine, mats, funcs, Emid, r, M0, fpm, *, Q0=None, seed=20260515, contour=None, eps_floor=0.0,
+                        union_csr=None, ortho="mgs", moments=2, reduced_nodes=128):
+    """T(lambda) x = 0, T(lambda) = sum_k f_k(lambda) mats[k], inside a circle: feast_hip_polynomial_projected's loop
+    (_projected_loop) on a term handle (engine.set_terms), with two changes.  The scalars are host tables of the f_k -- at the
+    contour nodes once, at the shifts and the candidates once per loop -- so the device never sees the functions.  The reduced
+    r x r problem sum_k f_k(lambda) Q^H A_k Q is solved on the host by nep_beyn and each candidate polished by
+    nep_newton_polish; the candidates then go through the polynomial method's ranking by device backward error (poly_select,
+    POLY_SET_ASIDE).  Loop 0 is the plain sweep, which factors T(z_e) once per node; later loops are residual-inverse sweeps on
+    the cached factors.  Stop test, loop limit and ``union_csr``: as feast_hip_polynomial_projected.  A circle in which the
+    reduced problem finds nothing returns Feast_ERROR_NO_CONVERGENCE with M = 0.  What an f_k raises is the caller's to see."""
+    N = mats[0].shape[0]
+    feastdefault(fpm)
+    info = _check_circle_input(N, M0, r)
+    if info:
+        return _empty_result(N, info, complex_lambda=True)
+    center = complex(Emid)
+    Zne, Wne = feast_gcontour(Emid, r, fpm) if contour is None else contour
+    F_node = nep_table(funcs, Zne)
+    if not np.isfinite(F_node).all():
+        k = int(np.flatnonzero(~np.isfinite(F_node).all(axis=0))[0])
+        raise ValueError(f"f_{k} is not finite at a contour node")
+    plan = _poly_setup(engine, mats, Emid, r, fpm, (Zne, Wne), union_csr, terms=True)
+    engine.nep_set_node_values(F_node)
+    nep = {"terms": len(mats), "columns": M0, "moments": int(moments), "reduced_nodes": int(reduced_nodes), "reduced_seconds": 0.0}
+    stats = {"krylov_iterations": 0, "factorizations": 0, "solve_seconds": 0.0, "nonlinear": nep}
+    if plan is not None:
+        nep.update(plan)
+
+    def sweep(dX, m, sigma):
+        return engine.nep_resinv_apply(dX, m, sigma, None if sigma is None else nep_table(funcs, sigma))
+
+    def reduced(Ahat, rank_q):
+        t0 = time.perf_counter()
+        theta, Y = nep_beyn(Ahat, funcs, center, r, moments, reduced_nodes)
+        theta, Y = theta.copy(), np.array(Y, dtype=np.complex128)
+        for i in range(len(theta)):
+            theta[i], Y[:, i] = nep_newton_polish(Ahat, funcs, theta[i], Y[:, i], r)
+        nep["reduced_seconds"] += time.perf_counter() - t0
+        return theta, Y
+
+    def evaluate(dQ, rank_q, Y, theta):
+        return engine.nep_ritz_eval(dQ, rank_q, Y, nep_table(funcs, theta))
+
+    return _projected_loop(engine, N, M0, Emid, r, fpm, Q0, seed, eps_floor, ortho, stats, nep, sweep, reduced, evaluate)
 
 
 TWO_SIDED_SOLVERS = ("direct", "lu")

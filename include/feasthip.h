@@ -593,6 +593,47 @@ int  feasthip_poly_ritz_eval_dev(feasthip_handle h, int64_t r, const void* dQ, i
                                  void* dX, double* backward_error);
 int  feasthip_poly_orthonormalize_dev(feasthip_handle h, int64_t m, void* dQ, int unit_columns, double rank_tol, int* rank);
 
+/* ---- nonlinear eigenproblems in split form: T(lambda) x = 0, T(lambda) = sum_{k < nterms} f_k(lambda) A_k ----------------------
+ * The f_k are scalar functions that only the caller evaluates: the library never sees them, it takes tables of their values.
+ * A TERM HANDLE is a polynomial handle whose scalars come from such tables instead of the powers of lambda; it keeps the
+ * storage, the per-node factor cache, the dense / multifrontal LU of the solver FEASTHIP_SOLVER_LU and the restrictions of a
+ * polynomial handle (complex128 factors, one rank, the whole contour, no adjoint).  (No reference counterpart.)
+ * feasthip_set_terms / feasthip_set_terms_csr: the arguments and checks of feasthip_set_polynomial / _csr with nterms = 2 ..
+ *   FEASTHIP_POLY_MAX_DEGREE + 1 matrices A_k in place of the degree + 1 coefficients; ||A_k||_F is kept for the backward error.
+ * feasthip_nep_set_node_values: F_host[e * nterms + k] = f_k(z_e) for the contour set before (feasthip_set_contour; set the
+ *   values again after every new contour).  ne other than the contour's node count, or a value that is not finite:
+ *   FEASTHIP_ERROR_FPM.  Values that differ from the ones set before drop the cached factors.
+ * feasthip_nep_solve_dev: Y = T(z_e)^-1 R for the contour node index `node`, N x m column-major; the factor is cached in the
+ *   node's slot; returns 0 or 8 (T(z_e) singular to working precision).
+ * feasthip_nep_eval_cols_dev: R[:, j] = sum_k F[j * nterms + k] A_k X[:, j], N x m; F: m x nterms on the host.
+ * feasthip_nep_resinv_apply_dev: the contour step of feasthip_poly_resinv_apply_dev with T in place of P.  sigma and F_sigma
+ *   both NULL: the plain sweep Q = sum_e weight_scale w_e T(z_e)^-1 X.  Both given (sigma: m shifts, F_sigma[j * nterms + k] =
+ *   f_k(sigma_j), host):  R[:, j] = sum_k F_sigma[j][k] A_k x_j,  Y_e = T(z_e)^-1 R,
+ *   Q[:, j] = sum_e weight_scale w_e (x_j - Y_e[:, j]) / (z_e - sigma_j).  One of the two NULL, a shift or a table row that is
+ *   not finite, a shift that coincides with a contour node to working precision: FEASTHIP_ERROR_FPM.  node_status and stats as
+ *   in feasthip_poly_resinv_apply_dev.
+ * feasthip_nep_ritz_eval_dev: X = Q Y (Y: r x ncand column-major, host) with unit columns, and
+ *     backward_error[i] = ||sum_k F_theta[i][k] A_k x_i||_2 / sum_k |F_theta[i][k]| ||A_k||_F,   F_theta: ncand x nterms, host;
+ *   +inf for a row of the table that is not finite and for a column of zero length.  backward_error may be NULL (then F_theta
+ *   may be too).  X must not alias Q.
+ * feasthip_poly_project_reduced_dev (Ahat_k = Q^H A_k Q, k < nterms) and feasthip_poly_orthonormalize_dev take a term handle
+ * as they are.  Every other feasthip_poly_* call forms powers of lambda and returns FEASTHIP_ERROR_FPM on a term handle
+ * (feasthip_last_error names the call to use instead), as does feasthip_set_solver with any solver but FEASTHIP_SOLVER_LU;
+ * the pencil entry points refuse a term handle as they refuse a polynomial handle.  All calls take any m >= 1 in 64-column
+ * panels.                                                                                                              */
+int  feasthip_set_terms(feasthip_handle h, int64_t N, int nterms, int is_complex, const void* const* mats /* nterms pointers */,
+                        const int64_t* ld /* nterms leading dimensions */);
+int  feasthip_set_terms_csr(feasthip_handle h, int64_t N, int nterms, int is_complex, const int64_t* rowptr, const int64_t* col,
+                            const void* const* vals /* nterms arrays of rowptr[N] values */);
+int  feasthip_nep_set_node_values(feasthip_handle h, int ne, const void* F_host /* ne x nterms complex */);
+int  feasthip_nep_solve_dev(feasthip_handle h, int node, int64_t m, const void* dR, void* dY, feasthip_stats* stats);
+int  feasthip_nep_eval_cols_dev(feasthip_handle h, int64_t m, const void* F_host /* m x nterms */, const void* dX, void* dR);
+int  feasthip_nep_resinv_apply_dev(feasthip_handle h, int64_t m, const void* sigma /* host, or NULL */,
+                                   const void* F_sigma /* host m x nterms, or NULL */, const void* dX, void* dQ, int* node_status,
+                                   feasthip_stats* stats);
+int  feasthip_nep_ritz_eval_dev(feasthip_handle h, int64_t r, const void* dQ, int64_t ncand, const void* Y_host, const void* F_theta,
+                                void* dX, double* backward_error);
+
 /* ---- measurement support ---------------------------------------------------------- */
 /* Average device time (ms, HIP events on the handle's stream) and launch count of the
  * named kernel class since the last reset; classes: "spmm", "bicg_update", "dot_finalize",
