@@ -14,7 +14,7 @@ from .contour import (feast_contour, feast_gcontour, feast_inside_gcontour, zolo
 from . import workloads   # noqa: F401
 from .hip_backend import (feast_hip_hermitian, feast_hip_general, feast_hip_complex_symmetric, feast_hip_polynomial, feast_hip_polynomial_projected, feast_hip_nonlinear,   # noqa: F401
                           pfeast_hip_moments, pfeast_hip_hermitian_moments, feast_hip_symmetric_kernel,
-                          seeded_subspace)   # noqa: F401
+                          feast_hip_poly_estimate, poly_derivative_table, nep_derivative_table, seeded_subspace)   # noqa: F401
 from .engine import HipEngine   # noqa: F401
 from .api import feast, feast_general, feast_polynomial, feast_pep, feast_nonlinear, feast_nep   # noqa: F401
 from . import rci   # noqa: F401

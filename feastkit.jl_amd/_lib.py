@@ -107,6 +107,7 @@ SYMBOLS = {
     "feasthip_nep_eval_cols_dev": (_i, [_vp, _i64, _vp, _vp, _vp]),
     "feasthip_nep_resinv_apply_dev": (_i, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _ps]),
     "feasthip_nep_ritz_eval_dev": (_i, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "feasthip_poly_estimate_count": (_i, [_vp, _i64, C.c_uint64, _vp, _pd, _vp, _vp, _ps]),
     "feasthip_last_node_iterations": (_i, [_vp, _vp, _i]),
     "feasthip_last_column_iterations": (_i, [_vp, _vp, _i]),
     "feasthip_last_global_node_iterations": (_i, [_vp, _vp, _i]),

@@ -14,7 +14,8 @@ from .engine import HipEngine
 from .contour import feast_contour, feast_gcontour
 from .hip_backend import (DIRECT_SOLVERS, ESTIMATE_SEED, check_direct_nodes, check_ortho, check_two_sided, feast_hip_estimate,
                           feast_hip_general, feast_hip_general_two_sided, feast_hip_hermitian, feast_hip_polynomial, feast_hip_polynomial_projected,
-                          POLY_METHODS, POLY_RESIDUALS, POLY_SET_ASIDE, feast_hip_nonlinear, nep_functions, nep_table)
+                          POLY_METHODS, POLY_RESIDUALS, POLY_SET_ASIDE, feast_hip_nonlinear, feast_hip_poly_estimate, nep_functions,
+                          nep_table)
 from .ingest import polynomial_union_csr
 from .parameters import feastdefault, feastinit
 from .types import FEAST_UNINITIALIZED, FeastHipError, FeastResult
@@ -597,6 +598,50 @@ POLY_SOLVERS = ("direct", "sparse_direct")               # the direct solvers
 POLY_KRYLOV_SOLVERS = ("bicgstab", "cocg", "gmres")      # sparse coefficients under method="projected" only
 
 
+def _check_poly_M0(M0, Q0):
+    """M0 of feast_polynomial / feast_nonlinear: an integer, or "auto" without a start block (whose width is then not known)"""
+    if isinstance(M0, str):
+        if M0 != "auto":
+            raise ValueError("M0 must be an integer or 'auto'")
+        if Q0 is not None:
+            raise ValueError('M0="auto" chooses the width of the subspace: a start block Q0 cannot be given with it')
+
+
+def _poly_estimate_mode(M0, fpm):
+    """(M0 is "auto", fpm[14] = 2) of a feast_polynomial / feast_nonlinear call; the two together make no sense"""
+    auto, estimate_only = isinstance(M0, str), int(fpm[14]) == 2
+    if auto and estimate_only:
+        raise ValueError('M0="auto" sizes a solve; under fpm[14] = 2 M0 is the sample count of the estimate')
+    return auto, estimate_only
+
+
+def _poly_estimate_or_solve(eng, driver, mats, funcs, center, radius, M0, fpm, union, common, auto, estimate_only, seed, krylov, width):
+    """One attempt of feast_polynomial / feast_nonlinear on the engine (the callers' fallback to the dense expansion wraps it):
+    the solve ``driver(eng, mats, [funcs,] center, radius, M0, fpm, union_csr=union, **common)``; under fpm[14] = 2 the count
+    estimate alone, M0 its sample count; under M0 = "auto" the estimate with AUTO_SAMPLES samples on the contour of the solve,
+    then the solve on the same handle set-up (``prepared``: the factors the estimate cached serve it) with M0 = auto_M0, or
+    ``width(auto_M0)`` where the method runs several columns per unit of M0.  The estimate's Krylov solves (``krylov`` = (solver,
+    tol, maxiter, restart)) stop at solver_tol, ESTIMATE_TOL when that is 0."""
+    args = (eng, mats) + (() if funcs is None else (funcs,)) + (center, radius)
+    if not (auto or estimate_only):
+        return driver(*args, M0, fpm, union_csr=union, **common)
+    N = mats[0].shape[0]
+    ekry = None if krylov is None else (krylov[0], krylov[1] if krylov[1] > 0.0 else ESTIMATE_TOL) + tuple(krylov[2:])
+    info, est, _plan, nfact = feast_hip_poly_estimate(eng, mats, funcs, center, radius, M0, fpm, seed=ESTIMATE_SEED if seed is None else int(seed),
+                                                      contour=common.get("contour"), union_csr=union, krylov=ekry)
+    if estimate_only or est is None:
+        return _estimate_result(N, info, est, False)
+    M0a = auto_M0(est, N)
+    if width is not None:
+        M0a = width(M0a)
+    res = driver(*args, M0a, fpm, union_csr=union, prepared=True, **common)
+    if isinstance(res.stats, dict):
+        res.stats["factorizations"] = res.stats.get("factorizations", 0) + nfact
+        res.stats["estimate"] = est
+        res.stats["M0_auto"] = M0a
+    return res
+
+
 def feast_polynomial(coeffs, center, radius, *, M0=10, fpm=None, engine=None, device=0, Q0=None, contour=None, seed=None,
                      keep_factors=False, residual="pencil", solver="direct", method="linearised", ortho="mgs", solver_tol=0.0,
                      solver_maxiter=500, solver_restart=30):
@@ -671,8 +716,27 @@ def feast_polynomial(coeffs, center, radius, *, M0=10, fpm=None, engine=None, de
                           returned with info = Feast_ERROR_NO_CONVERGENCE.  ``stats["polynomial"]`` = {degree, method, columns (M0),
                           rank, candidates, set_aside, eps_history (one entry per loop each), backward_error}, plus the plan
                           fields under "sparse_direct"; ``stats["ortho"]`` as in feast.
-    ``ortho`` is checked for both methods and used by "projected" only (the linearised loop never orthonormalises)."""
+    ``ortho`` is checked for both methods and used by "projected" only (the linearised loop never orthonormalises).
+
+    ``fpm[14] = 2``: no eigensolve -- a stochastic estimate of the number of eigenvalues inside the circle
+    (hip_backend.feast_hip_poly_estimate): Hutchinson samples of sum_e w_e tr(P'(z_e) P(z_e)^-1) over ``M0`` Rademacher columns
+    from one set of solves on the call's contour, under any ``solver`` of the call (Krylov solves stop at ``solver_tol``, 1e-8
+    when that is 0; the Krylov names are accepted with either ``method`` here, since the estimate's solves share one
+    right-hand-side block).  ``Q0`` is ignored; ``method``, ``residual`` and ``ortho`` are validated and unused.  The result has no
+    eigenpairs, complex dtype, M = max(0, round(Re mean)) and ``stats["estimate"]`` = {mean, stderr, samples, nodes, solver, seed,
+    seconds, dropped_terms}; a node that fails (status 5 / 8) gives that info and ``stats["estimate"] = None``.  feastdefault
+    lowers an unset fpm[8] to 6 under fpm[14] = 2: six nodes are a blunt filter for this use, set
+    fpm[8] >= 16.
+    ``M0="auto"``: such an estimate with 64 samples on the contour of the solve (the caller's fpm[8], default 16 -- not the
+    six-node estimate contour), then the solve on the same handle, so that under "direct" / "sparse_direct" it reuses the factors
+    the estimate cached and ``stats["factorizations"]`` of the whole call is the node count.  "projected": M0 = min(N, max(8,
+    ceil(1.5 (mean + 2 stderr)))); "linearised": that number divided by d, rounded up.  ``stats["estimate"]`` and
+    ``stats["M0_auto"]`` as in feast; ``seed`` picks both the estimate's block and the start block.  The estimate takes
+    min(64, N) samples.  When a node of the estimate fails (status 5 / 8) no solve follows: the call returns the estimate's
+    result -- that info, no eigenpairs, ``stats["estimate"] = None``, no ``stats["M0_auto"]`` or ``stats["factorizations"]``.  ``Q0`` with "auto" raises
+    ValueError (the width is not known), as does any other string."""
     mats = list(coeffs)
+    _check_poly_M0(M0, Q0)
     if method not in POLY_METHODS:
         raise ValueError(f"method must be one of {POLY_METHODS}, not {method!r}")
     check_ortho(ortho)
@@ -700,7 +764,8 @@ def feast_polynomial(coeffs, center, radius, *, M0=10, fpm=None, engine=None, de
         if not all(sp.issparse(c) for c in mats):
             raise ValueError(f'solver="{solver}" needs every coefficient as a scipy.sparse matrix; dense coefficients take '
                              'solver="direct"')
-        if method != "projected":
+        # (the estimate of fpm[14] = 2 solves with one shared right-hand-side block whatever the method)
+        if method != "projected" and not (fpm is not None and int(fpm[14]) == 2):
             raise ValueError(f'solver="{solver}" solves one right-hand-side block shared by the contour nodes: it needs '
                              'method="projected" (the linearised sweep has one right-hand side per node)')
         if solver == "cocg" and any(abs(c - c.T).max() != 0 for c in mats):
@@ -725,7 +790,10 @@ def feast_polynomial(coeffs, center, radius, *, M0=10, fpm=None, engine=None, de
         mats = [_promote(c) for c in mats]
     fpm = feastinit() if fpm is None else fpm
     feastdefault(fpm)
-    M0 = min(int(M0), N)
+    auto, estimate_only = _poly_estimate_mode(M0, fpm)
+    M0 = min(AUTO_SAMPLES if auto else int(M0), N)
+    if estimate_only and M0 <= 0:
+        return _estimate_result(N, 2, None, False)
     if method == "projected" and Q0 is not None and np.shape(Q0) != (N, M0):
         raise ValueError(f'method="projected": Q0 must be the N-row start block of shape ({N}, {M0}), not {np.shape(Q0)}')
     eng = _engine(engine, device)
@@ -735,14 +803,19 @@ def feast_polynomial(coeffs, center, radius, *, M0=10, fpm=None, engine=None, de
         driver, common["ortho"] = feast_hip_polynomial_projected, ortho
     else:
         driver, common["residual"] = feast_hip_polynomial, residual
+    kry = (solver, float(solver_tol), int(solver_maxiter), int(solver_restart)) if krylov else None
+    if krylov:
+        common["krylov"] = kry
+
+    def run(mats, union):
+        return _poly_estimate_or_solve(eng, driver, mats, None, complex(center), float(radius), M0, fpm, union, common, auto, estimate_only,
+                                       seed, kry, (lambda M: max(1, math.ceil(M / (len(mats) - 1)))) if method == "linearised" else None)
     try:
         res = None
-        if krylov:
-            common["krylov"] = (solver, float(solver_tol), int(solver_maxiter), int(solver_restart))
         if sparse_direct:
             union = polynomial_union_csr(mats)
             try:
-                res = driver(eng, mats, complex(center), float(radius), M0, fpm, union_csr=union, **common)
+                res = run(mats, union)
                 if isinstance(res.stats, dict) and "polynomial" in res.stats:
                     res.stats["polynomial"]["fell_back"] = False
             except FeastHipError as err:
@@ -754,7 +827,7 @@ def feast_polynomial(coeffs, center, radius, *, M0=10, fpm=None, engine=None, de
                 substituted = {"requested": "sparse_direct", "used": "dense LU of the expanded coefficients", "reason": str(err)}
                 mats = [_densify(c) for c in mats]
         if res is None:
-            res = driver(eng, mats, complex(center), float(radius), M0, fpm, **common)
+            res = run(mats, None)
             if sparse_direct and isinstance(res.stats, dict) and "polynomial" in res.stats:
                 res.stats["polynomial"].update(plan="dense", plan_nnz=int(len(union[1])), fell_back=True)
         if substituted is not None and isinstance(res.stats, dict):
@@ -803,10 +876,17 @@ def feast_nonlinear(terms, center, radius, *, M0=10, fpm=None, solver="direct", 
     (more nodes cure it); a spurious candidate of the small problem inside the circle whose backward error is below
     POLY_SET_ASIDE[0] is not set aside: it is counted in M and epsout stalls at its backward error.
 
+    ``fpm[14] = 2`` and ``M0="auto"``: as in feast_polynomial (a failed estimate node under "auto" included), with T'(z_e) = sum_k f_k'(z_e) A_k from central differences of the
+    f_k (hip_backend.nep_derivative_table; the f_k are still only evaluated, at z_e +- 1e-6 max(1, |z_e|) too, and a value that is
+    not finite there raises ValueError).  Under fpm[14] = 2 ``moments`` and ``reduced_nodes`` are validated and unused.  The
+    estimate integrates the analytic remainder of tr(T^-1 T') by the quadrature as well, which falls with the node count; a pole
+    of an f_k inside the circle would be counted negatively.
+
     Not covered: Krylov solves on T(z); multi-rank sweeps; complex64 factors; the two-sided form; functions with a branch cut
     that crosses the circle (keeping the cut away is the caller's responsibility); eigenvalues where some f_k has a pole inside
     the circle."""
     terms = list(terms)
+    _check_poly_M0(M0, Q0)
     check_ortho(ortho)
     if len(terms) < 2 or len(terms) > POLY_MAX_DEGREE + 1:
         raise ValueError(f"feast_nonlinear needs 2 to {POLY_MAX_DEGREE + 1} terms (A_k, f_k), not {len(terms)}")
@@ -846,7 +926,10 @@ def feast_nonlinear(terms, center, radius, *, M0=10, fpm=None, solver="direct", 
         mats = [_promote(c) for c in mats]
     fpm = feastinit() if fpm is None else fpm
     feastdefault(fpm)
-    M0 = min(int(M0), N)
+    auto, estimate_only = _poly_estimate_mode(M0, fpm)
+    M0 = min(AUTO_SAMPLES if auto else int(M0), N)
+    if estimate_only and M0 <= 0:
+        return _estimate_result(N, 2, None, False)
     if Q0 is not None and np.shape(Q0) != (N, M0):
         raise ValueError(f"Q0 must be the N-row start block of shape ({N}, {M0}), not {np.shape(Q0)}")
     Zne, Wne = feast_gcontour(complex(center), float(radius), fpm) if contour is None else contour
@@ -858,12 +941,16 @@ def feast_nonlinear(terms, center, radius, *, M0=10, fpm=None, solver="direct", 
     eps_floor = float(np.sqrt(np.finfo(np.float32).eps)) if single else 0.0
     common = dict(Q0=Q0, contour=(Zne, Wne), eps_floor=eps_floor, ortho=ortho, moments=int(moments), reduced_nodes=int(reduced_nodes),
                   **({} if seed is None else {"seed": int(seed)}))
+
+    def run(mats, union):
+        return _poly_estimate_or_solve(eng, feast_hip_nonlinear, mats, funcs, complex(center), float(radius), M0, fpm, union, common, auto,
+                                       estimate_only, seed, None, None)
     try:
         res = None
         if sparse_direct:
             union = polynomial_union_csr(mats)
             try:
-                res = feast_hip_nonlinear(eng, mats, funcs, complex(center), float(radius), M0, fpm, union_csr=union, **common)
+                res = run(mats, union)
                 if isinstance(res.stats, dict) and "nonlinear" in res.stats:
                     res.stats["nonlinear"]["fell_back"] = False
             except FeastHipError as err:
@@ -873,7 +960,7 @@ def feast_nonlinear(terms, center, radius, *, M0=10, fpm=None, solver="direct", 
                 substituted = {"requested": "sparse_direct", "used": "dense LU of the expanded terms", "reason": str(err)}
                 mats = [_densify(c) for c in mats]
         if res is None:
-            res = feast_hip_nonlinear(eng, mats, funcs, complex(center), float(radius), M0, fpm, **common)
+            res = run(mats, None)
             if sparse_direct and isinstance(res.stats, dict) and "nonlinear" in res.stats:
                 res.stats["nonlinear"].update(plan="dense", plan_nnz=int(len(union[1])), fell_back=True)
         if substituted is not None and isinstance(res.stats, dict):

@@ -11,7 +11,8 @@
 //     k   = mix64(seed + 0x9E3779B97F4A7C15 * (i + 1))
 //     b   = mix64(k ^ (0xD1B54A32D192ED03 * (j + 1)))          (all arithmetic mod 2^64)
 //     v_ij = +1 when the top bit of b is clear, else -1
-// with mix64 the splitmix64 finaliser.
+// with mix64 the splitmix64 finaliser (fh_mix64 / fh_row_key / fh_rademacher, fh_kernels.hpp).
+// col0: the block's first column is column col0 of the caller's block (a 64-column panel of a wider block).
 #include "fh_common.hpp"
 #include "fh_kernels.hpp"
 
@@ -19,18 +20,6 @@
 
 #define FH_EST_BLOCK 256
 #define FH_EST_GRID 2048          // memory-bound stream kernels: 256 CUs x 8 blocks, grid-stride beyond
-
-__host__ __device__ inline uint64_t fh_mix64(uint64_t z) {
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-__device__ inline uint64_t fh_row_key(uint64_t seed, int64_t row) {
-    return fh_mix64(seed + 0x9E3779B97F4A7C15ull * (uint64_t)(row + 1));
-}
-__device__ inline double fh_rademacher(uint64_t row_key, int64_t col) {
-    return (fh_mix64(row_key ^ (0xD1B54A32D192ED03ull * (uint64_t)(col + 1))) >> 63) ? -1.0 : 1.0;
-}
 
 // blocks along the rows of one column: enough to keep FH_EST_GRID blocks over all columns, at least 4 rows per thread
 static int fh_est_row_blocks(int64_t nrows, int64_t m) {
@@ -41,23 +30,23 @@ static int fh_est_row_blocks(int64_t nrows, int64_t m) {
 
 // X[r, j] (column-major, leading dimension ldx) = v(row0 + r, j) for r < nrows, j < m.  grid = (row blocks, m)
 __global__ __launch_bounds__(FH_EST_BLOCK) void k_rademacher_fill(uint64_t seed, int64_t row0, int64_t nrows, cplx* __restrict__ X,
-                                                                  int64_t ldx) {
+                                                                  int64_t ldx, int64_t col0) {
     const int64_t j = blockIdx.y;
     cplx* col = X + j * ldx;
     for (int64_t r = (int64_t)blockIdx.x * FH_EST_BLOCK + threadIdx.x; r < nrows; r += (int64_t)gridDim.x * FH_EST_BLOCK)
-        col[r] = cmake(fh_rademacher(fh_row_key(seed, row0 + r), j), 0.0);
+        col[r] = cmake(fh_rademacher(fh_row_key(seed, row0 + r), col0 + j), 0.0);
 }
 
-void fh_launch_rademacher(uint64_t seed, int64_t row0, int64_t nrows, int64_t m, cplx* X, int64_t ldx, hipStream_t st) {
+void fh_launch_rademacher(uint64_t seed, int64_t row0, int64_t nrows, int64_t m, cplx* X, int64_t ldx, hipStream_t st, int64_t col0) {
     if (nrows <= 0 || m <= 0) return;
     hipLaunchKernelGGL(k_rademacher_fill, dim3(fh_est_row_blocks(nrows, m), (unsigned)m), dim3(FH_EST_BLOCK), 0, st,
-                       seed, row0, nrows, X, ldx);
+                       seed, row0, nrows, X, ldx, col0);
 }
 
 // stage 1: partial[j * gridDim.x + b] = sum over block b's rows of v(i, j) * P[i, j].  Every block owns a contiguous row
 // range of one column; one 16-byte load per lane, wave sums by shuffles, the four waves summed in wave order.
 __global__ __launch_bounds__(FH_EST_BLOCK) void k_trace_partials(const cplx* __restrict__ P, int64_t N, int64_t ldp, uint64_t seed,
-                                                                 cplx* __restrict__ partial) {
+                                                                 cplx* __restrict__ partial, int64_t col0) {
     const int64_t j = blockIdx.y;
     const int64_t per = (N + gridDim.x - 1) / gridDim.x;
     const int64_t r0 = (int64_t)blockIdx.x * per, r1 = std::min(N, r0 + per);
@@ -65,7 +54,7 @@ __global__ __launch_bounds__(FH_EST_BLOCK) void k_trace_partials(const cplx* __r
     double sx = 0.0, sy = 0.0;
     for (int64_t r = r0 + threadIdx.x; r < r1; r += FH_EST_BLOCK) {
         const cplx p = col[r];
-        const double v = fh_rademacher(fh_row_key(seed, r), j);
+        const double v = fh_rademacher(fh_row_key(seed, r), col0 + j);
         sx += v * p.x;
         sy += v * p.y;
     }
@@ -102,10 +91,15 @@ __global__ __launch_bounds__(FH_EST_BLOCK) void k_trace_finish(const cplx* __res
 
 size_t fh_trace_work_elems(int64_t N, int64_t m) { return (size_t)fh_est_row_blocks(N, m) * (size_t)m; }
 
+void fh_launch_trace_finish(const cplx* partial, int nb, int64_t m, int real_only, double* t, hipStream_t st) {
+    if (nb <= 0 || m <= 0) return;
+    hipLaunchKernelGGL(k_trace_finish, dim3(1), dim3(FH_EST_BLOCK), 0, st, partial, nb, m, real_only, t);
+}
+
 void fh_launch_trace_dots(const cplx* P, int64_t N, int64_t m, int64_t ldp, uint64_t seed, int real_only, cplx* work, double* t,
-                          hipStream_t st) {
+                          hipStream_t st, int64_t col0) {
     if (N <= 0 || m <= 0) return;
     const int nb = fh_est_row_blocks(N, m);
-    hipLaunchKernelGGL(k_trace_partials, dim3(nb, (unsigned)m), dim3(FH_EST_BLOCK), 0, st, P, N, ldp, seed, work);
-    hipLaunchKernelGGL(k_trace_finish, dim3(1), dim3(FH_EST_BLOCK), 0, st, work, nb, m, real_only, t);
+    hipLaunchKernelGGL(k_trace_partials, dim3(nb, (unsigned)m), dim3(FH_EST_BLOCK), 0, st, P, N, ldp, seed, work, col0);
+    fh_launch_trace_finish(work, nb, m, real_only, t, st);
 }

@@ -256,12 +256,26 @@ void fh_launch_small_matmul(const cplx* Q, const cplx* V, int N, int ld, cplx* X
 // dst[:,k] = src[:,perm[k]] for k < count else 0
 void fh_launch_gather_cols(const cplx* src, const int* perm, int count, int N, int ld, cplx* dst, hipStream_t st);
 
-// stochastic eigenvalue-count estimate (fh_estimate.hip): Rademacher block X[r, j] = v(row0 + r, j) (column-major, N x m,
-// m <= 65535), and t[2j], t[2j+1] = re, im of sum_i v(i, j) P[i, j] over the column-major N x m block P; work: fh_trace_work_elems
-void fh_launch_rademacher(uint64_t seed, int64_t row0, int64_t nrows, int64_t m, cplx* X, int64_t ldx, hipStream_t st);
+// stochastic eigenvalue-count estimate (fh_estimate.hip): Rademacher block X[r, j] = v(row0 + r, col0 + j) (column-major, N x m,
+// m <= 65535), and t[2j], t[2j+1] = re, im of sum_i v(i, col0 + j) P[i, j] over the column-major N x m block P; work:
+// fh_trace_work_elems.  fh_launch_trace_finish is the second stage on its own: t[j] = sum_{b < nb} partial[j nb + b], in order.
+// The entry v(i, j) itself, for a kernel that regenerates it (k_trace_partials, k_spmm_fanin_trace of fh_poly.hip):
+__host__ __device__ inline uint64_t fh_mix64(uint64_t z) {
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+__device__ inline uint64_t fh_row_key(uint64_t seed, int64_t row) {
+    return fh_mix64(seed + 0x9E3779B97F4A7C15ull * (uint64_t)(row + 1));
+}
+__device__ inline double fh_rademacher(uint64_t row_key, int64_t col) {
+    return (fh_mix64(row_key ^ (0xD1B54A32D192ED03ull * (uint64_t)(col + 1))) >> 63) ? -1.0 : 1.0;
+}
+void fh_launch_rademacher(uint64_t seed, int64_t row0, int64_t nrows, int64_t m, cplx* X, int64_t ldx, hipStream_t st, int64_t col0 = 0);
 size_t fh_trace_work_elems(int64_t N, int64_t m);
 void fh_launch_trace_dots(const cplx* P, int64_t N, int64_t m, int64_t ldp, uint64_t seed, int real_only, cplx* work, double* t,
-                          hipStream_t st);
+                          hipStream_t st, int64_t col0 = 0);
+void fh_launch_trace_finish(const cplx* partial, int nb, int64_t m, int real_only, double* t, hipStream_t st);
 
 // column-pivoted modified Gram-Schmidt with re-orthogonalisation, fully on device.
 // state: int[4 + ld] = {k (steps done), rank, done, pivot, perm[ld]}; dstate: double[2+ld] = {R11, thr, norm2[ld]}

@@ -163,13 +163,22 @@ int fh_poly_form(feasthip_ctx* h, void* const* dlus, const cplx* dz, int nf, int
 // gathered X element, in CSR order.  A macro, not a function template taking the term as a callable: through a closure the
 // compiler orders the operands of the complex products the other way round and contracts a different half of each into the
 // FMA, so the sums would differ in the last bit from what these kernels have always returned.
-#define POLY_ROW_GATHER(LD_, colidx_, X_, k0_, k1_, c_, K, XV, ...)                                                     \
-    for (int kb_ = (k0_); kb_ < (k1_); kb_ += 4) {                                                                       \
-        cplx xs_[4];                                                                                                     \
-        _Pragma("unroll") for (int q_ = 0; q_ < 4; ++q_) xs_[q_] = (X_)[(size_t)(colidx_)[min(kb_ + q_, (k1_) - 1)] * (LD_) + (c_)]; \
-        _Pragma("unroll") for (int q_ = 0; q_ < 4; ++q_)                                                                 \
-            if (kb_ + q_ < (k1_)) { const int K = kb_ + q_; const cplx& XV = xs_[q_]; __VA_ARGS__ }                      \
+// POLY_ROW_GATHER_N is the step itself, for np_ <= NP_ panels one behind the other (panel p at X_ + p pstride_) and batches of
+// DEPTH_ nonzeros: the column index is loaded once per nonzero and the row of every panel gathered at it, XS[p] the element of
+// panel p.  POLY_ROW_GATHER is its one-panel, four-deep form.
+#define POLY_ROW_GATHER_N(NP_, DEPTH_, LD_, colidx_, X_, pstride_, np_, k0_, k1_, c_, K, XS, ...)                        \
+    for (int kb_ = (k0_); kb_ < (k1_); kb_ += (DEPTH_)) {                                                                \
+        cplx xs_[DEPTH_][NP_];                                                                                           \
+        _Pragma("unroll") for (int q_ = 0; q_ < (DEPTH_); ++q_) {                                                        \
+            const cplx* xp_ = (X_) + ((size_t)(colidx_)[min(kb_ + q_, (k1_) - 1)] * (LD_) + (c_));                       \
+            _Pragma("unroll") for (int p_ = 0; p_ < (NP_); ++p_)                                                         \
+                if (p_ < (np_)) xs_[q_][p_] = xp_[(size_t)p_ * (pstride_)];                                              \
+        }                                                                                                                \
+        _Pragma("unroll") for (int q_ = 0; q_ < (DEPTH_); ++q_)                                                          \
+            if (kb_ + q_ < (k1_)) { const int K = kb_ + q_; const cplx* XS = xs_[q_]; __VA_ARGS__ }                      \
     }
+#define POLY_ROW_GATHER(LD_, colidx_, X_, k0_, k1_, c_, K, XV, ...)                                                     \
+    POLY_ROW_GATHER_N(1, 4, LD_, colidx_, X_, 0, 1, k0_, k1_, c_, K, xv_, const cplx& XV = xv_[0]; __VA_ARGS__)
 
 #define FH_FAN_MAX (PD + 1)
 struct fh_fan_args {
@@ -424,15 +433,15 @@ __device__ __forceinline__ cplx poly_ld_nt(const cplx* p) { return cmake(__built
 __device__ __forceinline__ void poly_st_nt(cplx* p, cplx v) { __builtin_nontemporal_store(v.x, &p->x); __builtin_nontemporal_store(v.y, &p->y); }
 
 // out[c] = the sum over the FH_BLOCK / LD threads t = c + k LD of a workgroup of their dsum, added through LDS in ascending k
-// (every thread of the workgroup calls it; red: FH_BLOCK elements)
-template <int LD> __device__ __forceinline__ void poly_column_sum(cplx* red, int t, cplx dsum, cplx* out) {
+// (every thread of the workgroup calls it; red: FH_BLOCK elements; ostride: elements between the columns of out)
+template <int LD> __device__ __forceinline__ void poly_column_sum(cplx* red, int t, cplx dsum, cplx* out, size_t ostride = 1) {
     red[t] = dsum;
     __syncthreads();
     if (t < LD) {
         cplx s = red[t];
 #pragma unroll
         for (int k = 1; k < FH_BLOCK / LD; ++k) s = cadd(s, red[t + k * LD]);
-        out[t] = s;
+        out[t * ostride] = s;
     }
     __syncthreads();
 }
@@ -513,6 +522,78 @@ int fh_launch_spmm_poly(feasthip_ctx* h, int ld, const fh_polyop_call& c) {
     POLY_LAUNCH_CSR(k_spmm_poly, ld, dim3((unsigned)nprow), a);
     fh_prof_end(h);
     return nprow;
+}
+
+// ---------------------------------------------------------------------------------------
+// Count estimate (feasthip_poly_estimate_count): t_c = v_c^T sum_e w_e T'(z_e) T(z_e)^-1 v_c with T'(z_e) = sum_k g_k(z_e) A_k.
+// The node sum commutes with the matrices, sum_e w_e T'(z_e) Y_e = sum_k A_k Z_k, so two kernels follow the solves Y_e =
+// T(z_e)^-1 V: the fan-out k_node_combine forms the Z_k, the fan-in k_spmm_fanin_trace (CSR coefficients) takes the trace of
+// sum_k A_k Z_k against V without writing the product.
+//
+// k_node_combine: Z_t[i, c] = sum_e G[e][t] Y_e[i, c] for t < nt kept terms, G the ne x nt host table w_e g_k(z_e) of the kept
+// terms.  The sibling of k_poly_resinv_acc with a fan-out: a thread owns panel elements, reads every Y_e element once, nodes in
+// ascending e, and holds the nt <= 9 sums in registers.  G[e][t] has the same address in every lane, so its loads are scalar
+// ones whatever ne is.  No atomics.  Traffic: ne panels read, nt written.
+// ---------------------------------------------------------------------------------------
+__global__ __launch_bounds__(FH_BLOCK) void k_node_combine(const cplx* __restrict__ Y, size_t stride, const cplx* __restrict__ G, int ne,
+                                                            int nt, cplx* __restrict__ Z, size_t total) {
+    for (size_t e = (size_t)blockIdx.x * FH_BLOCK + threadIdx.x; e < total; e += (size_t)gridDim.x * FH_BLOCK) {
+        cplx acc[PD + 1];
+#pragma unroll
+        for (int t = 0; t <= PD; ++t) acc[t] = cmake(0, 0);
+#pragma unroll 4          // (four node loads in flight per thread, as in k_poly_resinv_acc)
+        for (int q = 0; q < ne; ++q) {
+            const cplx y = Y[(size_t)q * stride + e];
+            const cplx* __restrict__ g = G + (size_t)q * nt;
+#pragma unroll
+            for (int t = 0; t <= PD; ++t)
+                if (t < nt) cfma(acc[t], g[t], y);
+        }
+#pragma unroll
+        for (int t = 0; t <= PD; ++t)
+            if (t < nt) Z[(size_t)t * total + e] = acc[t];
+    }
+}
+
+// k_spmm_fanin_trace: partial sums of t_c = sum_i v(i, col0 + c) sum_t sum_j A_{k_t}[i, j] Z_t[j, c] over nt panels Z_t (one
+// behind the other, zstride apart).  The row-slice layout of k_spmm_fan / k_spmm_horner; per nonzero the column index is loaded
+// once, then the nt values and the nt gathered rows, into ONE accumulator per lane (gathers batched two deep: 2 nt rows in
+// flight).  v is regenerated from (seed, row, column) as in k_trace_partials (fh_estimate.hip); the block V is never read.  A
+// workgroup walks its rows in ascending order, its FH_BLOCK / LD threads of a column are added through LDS in thread order, and
+// it writes ONE partial row, partial[c nprow + blockIdx.x] with nprow = gridDim.x -- the layout k_trace_finish sums in block
+// order.  No atomics: reproducible.
+// Algorithmic traffic: nnz (4 + nt sizeof(VT)) of matrix, nt rows of 16 LD B gathered per nonzero, nothing written but the partials.
+#define FH_FANIN_GRID_MAX 1024
+struct fh_fanin_args {
+    const int* rowptr; const int* col;
+    const cplx* Z; size_t zstride;
+    int N, nt;
+    const void* val[FH_FAN_MAX];      // values of the kept A_k on the pattern
+    uint64_t seed; int64_t col0;
+    cplx* partial;
+};
+
+template <typename VT, int LD>
+__global__ __launch_bounds__(FH_BLOCK) void k_spmm_fanin_trace(fh_fanin_args a) {
+    constexpr int ROWS = FH_BLOCK / LD;
+    __shared__ cplx red[FH_BLOCK];
+    const int t = threadIdx.x;
+    const int c = t % LD;
+    const int* __restrict__ colidx = a.col;
+    const cplx* __restrict__ Z = a.Z;
+    cplx dsum = cmake(0, 0);
+    for (int i = blockIdx.x * ROWS + t / LD; i < a.N; i += gridDim.x * ROWS) {
+        const int k0 = a.rowptr[i], k1 = a.rowptr[i + 1];
+        cplx acc = cmake(0, 0);
+        POLY_ROW_GATHER_N(FH_FAN_MAX, 2, LD, colidx, Z, a.zstride, a.nt, k0, k1, c, k, zs,
+            _Pragma("unroll") for (int p = 0; p < FH_FAN_MAX; ++p)
+                if (p < a.nt) acc = cadd(acc, vmul(((const VT*)a.val[p])[k], zs[p]));
+        )
+        const double v = fh_rademacher(fh_row_key(a.seed, i), a.col0 + c);
+        dsum.x += v * acc.x;
+        dsum.y += v * acc.y;
+    }
+    poly_column_sum<LD>(red, t, dsum, a.partial + blockIdx.x, gridDim.x);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1399,6 +1480,102 @@ extern "C" int feasthip_nep_resinv_apply_dev(feasthip_handle h, int64_t m64, con
                 return FEASTHIP_ERROR_FPM;
             }
     return poly_resinv_body(h, "feasthip_nep_resinv_apply_dev", m64, sigma, F_sigma, dX, dQ, node_status, stats);
+}
+
+// Count estimate of a polynomial or term handle: samples t_c = v_c^T [sum_e w_e T'(z_e) T(z_e)^-1 v_c], c < m, for the Rademacher
+// block V of `seed` (the (seed, i, j) rule of fh_estimate.hip).  G_host: ne x (degree + 1), G[e][k] = w_e g_k(z_e) with T'(z) =
+// sum_k g_k(z) A_k; a term whose column of G is zero at every node is dropped (A_0 of a polynomial, a constant f_k).  Per
+// 64-column panel: Y_e = T(z_e)^-1 V on one shared right-hand-side panel (poly_solve_nodes: any solver of the handle, the factor
+// cache as in the sweeps), Z_t = sum_e G[e][k_t] Y_e (k_node_combine), then the trace of sum_t A_{k_t} Z_t against V --
+// k_spmm_fanin_trace and k_trace_finish on CSR coefficients, the dense product accumulated into one panel and the pencil
+// estimate's k_trace_partials / k_trace_finish on dense ones.  dV (may be null): receives V, N x m column-major.
+extern "C" int feasthip_poly_estimate_count(feasthip_handle h, int64_t m64, uint64_t seed, const void* G_host, double* samples, void* dV,
+                                            int* node_status, feasthip_stats* stats) {
+    const char* what = "feasthip_poly_estimate_count";
+    int rc = poly_check(h, what, m64, h && h->kind == 3 ? std::min<int64_t>(h->dense.N, 65535) : 1, POLY_ANY_FORM);
+    if (rc) return rc;
+    if (h->poly.terms && (rc = nep_check_nodes(h, what))) return rc;
+    if (!G_host || !samples) { h->last_error = std::string(what) + ": null argument"; return FEASTHIP_ERROR_INTERNAL; }
+    if (h->zne.empty()) { h->last_error = std::string(what) + ": no contour set (feasthip_set_contour)"; return FEASTHIP_ERROR_FPM; }
+    if (h->real_projection) { h->last_error = std::string(what) + ": the real projection does not apply to a polynomial sweep"; return FEASTHIP_ERROR_FPM; }
+    const int N = (int)h->dense.N, ne = (int)h->zne.size(), nt = h->poly.degree + 1;
+    const cplx* Gh = (const cplx*)G_host;
+    for (int i = 0; i < ne * nt; ++i)
+        if (!std::isfinite(Gh[i].x) || !std::isfinite(Gh[i].y)) {
+            h->last_error = std::string(what) + ": G is not finite at contour node " + std::to_string(i / nt) + ", term " + std::to_string(i % nt);
+            return FEASTHIP_ERROR_FPM;
+        }
+    int kept[PD + 1], ntk = 0;
+    for (int k = 0; k < nt; ++k) {
+        bool zero = true;
+        for (int e = 0; zero && e < ne; ++e) zero = Gh[(size_t)e * nt + k].x == 0.0 && Gh[(size_t)e * nt + k].y == 0.0;
+        if (!zero) kept[ntk++] = k;
+    }
+    std::vector<cplx> Gk((size_t)ne * std::max(1, ntk));
+    for (int e = 0; e < ne; ++e)
+        for (int t = 0; t < ntk; ++t) Gk[(size_t)e * ntk + t] = Gh[(size_t)e * nt + kept[t]];
+    FH_CHECK(hipSetDevice(h->device));
+    const double t0 = poly_now();
+    if (stats) memset(stats, 0, sizeof(*stats));
+    if (node_status) for (int e = 0; e < ne; ++e) node_status[e] = 0;
+    poly_coefs pc;
+    if ((rc = pc.acquire(h))) return rc;
+    cplx* dG;
+    double* dT;
+    if ((rc = poly_upload(h, "ec_G", Gk, &dG))) return rc;
+    if ((rc = fh_buf(h, "ec_t", (size_t)m64 * 2, &dT))) return rc;
+    FH_CHECK(hipMemsetAsync(dT, 0, (size_t)m64 * 2 * sizeof(double), h->stream));
+    const fh_poly_ptrs P = fh_poly_coef_ptrs(h);
+    poly_iters it;
+    poly_iter_record rec(ne, m64);
+    for (int64_t c0 = 0; c0 < m64; c0 += FH_MAX_LD) {
+        const int m = (int)std::min<int64_t>(FH_MAX_LD, m64 - c0), ld = fh_pick_ld(m);
+        const size_t panel = (size_t)N * ld;
+        cplx *Vc, *Vs, *Y, *Z;
+        if (dV) Vc = (cplx*)dV + (size_t)c0 * N;
+        else if ((rc = fh_buf(h, "ec_Vc", (size_t)N * m, &Vc))) return rc;
+        if ((rc = fh_buf(h, "ec_V", panel, &Vs))) return rc;
+        fh_launch_rademacher(seed, 0, N, m, Vc, N, h->stream, c0);
+        fh_launch_to_panel(Vc, N, N, m, Vs, ld, h->stream);
+        if (ntk == 0) continue;          // T' = 0 on the whole contour: every sample is zero
+        if ((rc = fh_buf(h, "ec_Y", (size_t)ne * panel, &Y))) return rc;
+        if ((rc = fh_buf(h, "ec_Z", (size_t)ntk * panel, &Z))) return rc;
+        std::vector<int> status;
+        int64_t nfact = 0;
+        if ((rc = poly_solve_nodes(h, ld, m, ne, Vs, 0, panel, Y, status, &nfact, it))) return rc;
+        if (poly_krylov(h)) rec.panel(it, c0, m);
+        fh_prof_begin(h, "node_combine");
+        hipLaunchKernelGGL(k_node_combine, dim3(fh_vec_nblk(N, ld)), dim3(FH_BLOCK), 0, h->stream, Y, panel, dG, ne, ntk, Z, panel);
+        fh_prof_end(h);
+        if (h->poly.sparse) {
+            fh_fanin_args a;
+            memset(&a, 0, sizeof(a));
+            a.rowptr = h->csr.rowptr; a.col = h->csr.col; a.Z = Z; a.zstride = panel; a.N = N; a.nt = ntk;
+            for (int t = 0; t < ntk; ++t) a.val[t] = P.c[kept[t]];
+            a.seed = seed; a.col0 = c0;
+            const int rows = FH_BLOCK / ld, nprow = std::max(1, std::min(FH_FANIN_GRID_MAX, (N + rows - 1) / rows));
+            if ((rc = fh_buf(h, "ec_part", (size_t)nprow * ld, &a.partial))) return rc;
+            fh_prof_begin(h, "fanin_trace");
+            POLY_LAUNCH_CSR(k_spmm_fanin_trace, ld, dim3((unsigned)nprow), a);
+            fh_prof_end(h);
+            fh_launch_trace_finish(a.partial, nprow, m, 0, dT + 2 * c0, h->stream);
+        } else {
+            cplx *W, *Pc, *work;
+            if ((rc = fh_buf(h, "ec_W", panel, &W))) return rc;
+            if ((rc = fh_buf(h, "ec_P", (size_t)N * m, &Pc))) return rc;
+            if ((rc = fh_buf(h, "ec_work", fh_trace_work_elems(N, m), &work))) return rc;
+            for (int t = 0; t < ntk; ++t) poly_product(h, pc, ld, kept[t], Z + (size_t)t * panel, W, t > 0, false);
+            fh_launch_from_panel(W, ld, N, m, Pc, N, h->stream);
+            fh_launch_trace_dots(Pc, N, m, N, seed, 0, work, dT + 2 * c0, h->stream, c0);
+        }
+        if (stats) stats->factorizations += nfact;
+        if (node_status) for (int e = 0; e < ne; ++e) node_status[e] = std::max(node_status[e], status[e]);
+    }
+    FH_CHECK(hipMemcpyAsync(samples, dT, (size_t)m64 * 2 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if ((rc = poly_finish(h))) return rc;
+    if (poly_krylov(h)) rec.publish(h, it, stats);
+    if (stats) stats->seconds_total = poly_now() - t0;
+    return 0;
 }
 
 // Ahat_k = Q^H A_k Q, k = 0 .. d: d + 1 r x r column-major matrices one behind the other on the host.  Per 64-column panel Q_j

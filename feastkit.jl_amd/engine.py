@@ -768,6 +768,29 @@ class HipEngine:
                                                       None if bwd is None else _np_ptr(bwd)))
         return dX, bwd
 
+    def poly_estimate_count(self, m, seed, G, want_block=False):
+        """Hutchinson samples of the eigenvalue count of a polynomial or term handle (feasthip_poly_estimate_count):
+        t_c = v_c^T [sum_e w_e T'(z_e) T(z_e)^-1 v_c] for the m Rademacher columns of ``seed``, with G[e, k] = w_e g_k(z_e) the
+        ne x (degree + 1) table of T'(z_e) = sum_k g_k(z_e) A_k (hip_backend.poly_derivative_table / nep_derivative_table times
+        the weights).  Returns (samples: m complex values, status per node, stats), and with ``want_block`` also the block V the
+        samples were taken with (an (m, N) tensor)."""
+        self._sync_stream()
+        m = int(m)
+        Gc = np.ascontiguousarray(G, dtype=np.complex128)
+        if Gc.shape != (max(1, self.ne), self.poly_degree + 1):
+            raise ValueError(f"poly_estimate_count needs a table of shape ({self.ne}, {self.poly_degree + 1})")
+        samples = np.zeros(2 * max(m, 0), dtype=np.float64)
+        status = np.zeros(max(1, self.ne), dtype=np.int32)
+        stats = FeastHipStats()
+        dV = self.empty(m) if want_block and m > 0 else None
+        self._chk(self.lib.feasthip_poly_estimate_count(self.h, m, C.c_uint64(int(seed) & (2 ** 64 - 1)), _np_ptr(Gc),
+                                                        samples.ctypes.data_as(C.POINTER(C.c_double)),
+                                                        None if dV is None else C.c_void_p(dV.data_ptr()), _np_ptr(status),
+                                                        C.byref(stats)))
+        self.last_stats = stats.asdict()
+        t = samples[0::2] + 1j * samples[1::2]
+        return (t, status, self.last_stats, dV) if want_block else (t, status, self.last_stats)
+
     def free_factors(self):
         """Drop the cached LU / band factors of the direct solvers (feasthip_release_factors)."""
         self._chk(self.lib.feasthip_release_factors(self.h))

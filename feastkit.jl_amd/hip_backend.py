@@ -1017,16 +1017,18 @@ def feast_hip_general(engine, A, B, Emid, r, M0, fpm, *, solver="direct", solver
 POLY_RESIDUALS = ("pencil", "reference")
 
 
-def _poly_setup(engine, coeffs, Emid, r, fpm, contour, union_csr, krylov=None, terms=False):
+def _poly_setup(engine, coeffs, Emid, r, fpm, contour, union_csr, krylov=None, terms=False, prepared=False):
     """What both polynomial drivers do before their loop: the polynomial (dense, or sparse from ``union_csr``) becomes the engine's
     problem with the direct solver, cached fp64 factors, no real projection and the full contour -> the plan fields of
     ``stats["polynomial"]`` for sparse coefficients, else None.  ``krylov`` = (solver, tol, maxiter, restart), sparse
     coefficients only: that Krylov solver on P(z_e) instead, relative stop test (tol 0 = 10^-fpm[3]) -> {"plan": "krylov"}.
-    ``terms``: the matrices are the A_k of a split form and the handle becomes a term handle (feast_hip_nonlinear)."""
+    ``terms``: the matrices are the A_k of a split form and the handle becomes a term handle (feast_hip_nonlinear).
+    ``prepared``: the engine holds this problem and this contour already (the estimate behind M0 = "auto" set them and cached
+    the factors): only the solver is set again."""
     Zne, Wne = feast_gcontour(Emid, r, fpm) if contour is None else contour
-    if union_csr is None:
+    if not prepared and union_csr is None:
         engine.set_polynomial(coeffs, terms=terms)
-    else:
+    elif not prepared:
         engine.set_polynomial_csr(*union_csr, terms=terms)
     if krylov is not None:
         solver, tol, maxiter, restart = krylov
@@ -1034,8 +1036,9 @@ def _poly_setup(engine, coeffs, Emid, r, fpm, contour, union_csr, krylov=None, t
                           factor_precision=64)
     else:
         engine.set_solver("direct", cache_factors=True, factor_precision=64)
-    engine.set_real_projection(False)
-    engine.set_contour(Zne, Wne, 1.0)
+    if not prepared:
+        engine.set_real_projection(False)
+        engine.set_contour(Zne, Wne, 1.0)
     if krylov is not None:
         return {"plan": "krylov"}
     if union_csr is None:
@@ -1046,7 +1049,7 @@ def _poly_setup(engine, coeffs, Emid, r, fpm, contour, union_csr, krylov=None, t
 
 
 def feast_hip_polynomial(engine, coeffs, Emid, r, M0, fpm, *, Q0=None, seed=20260515, contour=None, residual="pencil",
-                         eps_floor=0.0, union_csr=None):
+                         eps_floor=0.0, union_csr=None, prepared=False):
     """P(lambda) x = 0 inside a circle: feast_hip_general's loop on the first companion linearisation with M0 d columns
     (feast_pep!, src/dense/feast_dense.jl:715-772, driving feast_gegv! :763) -- full contour, no factor 2, no
     orthonormalisation -- with the companion pencil replaced by the engine's poly_* calls: one N x N LU per node.
@@ -1057,7 +1060,7 @@ def feast_hip_polynomial(engine, coeffs, Emid, r, M0, fpm, *, Q0=None, seed=2026
     (engine.set_polynomial_csr), P(z_e) is factored by the multifrontal LU and ``stats["polynomial"]`` gains plan =
     "multifrontal", plan_factor_bytes / plan_transient_bytes / plan_flops per node and plan_nnz of the union pattern.  A
     pattern without a plan, factors that do not fit and a rejected pivot raise FeastHipError (codes 9, 6, 8): there is no
-    band LU for polynomials, the caller decides what to do instead."""
+    band LU for polynomials, the caller decides what to do instead.  ``prepared``: as in _poly_setup."""
     d = len(coeffs) - 1
     N = coeffs[0].shape[0]
     cols = M0 * d
@@ -1065,7 +1068,7 @@ def feast_hip_polynomial(engine, coeffs, Emid, r, M0, fpm, *, Q0=None, seed=2026
     info = _check_circle_input(N, M0, r)
     if info:
         return _empty_result(N, info, complex_lambda=True)
-    plan = _poly_setup(engine, coeffs, Emid, r, fpm, contour, union_csr)
+    plan = _poly_setup(engine, coeffs, Emid, r, fpm, contour, union_csr, prepared=prepared)
     Q_host = seeded_subspace(d * N, cols, seed) if Q0 is None else np.asarray(Q0, dtype=np.complex128)
     if Q_host.shape != (d * N, cols):
         raise ValueError(f"Q0 must be the linearised start block of shape ({d * N}, {cols})")
@@ -1233,7 +1236,7 @@ def _projected_loop(engine, N, M0, Emid, r, fpm, Q0, seed, eps_floor, ortho, sta
 
 
 def feast_hip_polynomial_projected(engine, coeffs, Emid, r, M0, fpm, *, Q0=None, seed=20260515, contour=None, eps_floor=0.0,
-                                   union_csr=None, ortho="mgs", krylov=None):
+                                   union_csr=None, ortho="mgs", krylov=None, prepared=False):
     """P(lambda) x = 0 inside a circle on an N-row subspace of M0 columns: polynomial FEAST with a residual-inverse contour
     step (Gavin, Miedlar, Polizzi).  Per loop (_projected_loop): the contour step on the N x m block (loop 0 the plain sweep,
     which factors P(z_e) once per node and fills the cache; afterwards R_j = P(sigma_j) x_j, Y_e = P(z_e)^-1 R, Q_j = sum_e w_e
@@ -1244,7 +1247,8 @@ def feast_hip_polynomial_projected(engine, coeffs, Emid, r, M0, fpm, *, Q0=None,
     ``krylov`` = (solver, tol, maxiter, restart) with ``union_csr``: the solves of the contour step run on that Krylov solver
     (_poly_setup) and are inexact.  A node whose column stopped at maxiter (status 5) is the normal outcome of such a sweep and
     the loop goes on with its iterate; ``stats["polynomial"]["krylov"]`` gets one entry per loop, {iterations (worst column),
-    node_iterations, capped_nodes}, ``stats["krylov_iterations"]`` the engine's count, and nothing is factored."""
+    node_iterations, capped_nodes}, ``stats["krylov_iterations"]`` the engine's count, and nothing is factored.
+    ``prepared``: as in _poly_setup."""
     d = len(coeffs) - 1
     N = coeffs[0].shape[0]
     feastdefault(fpm)
@@ -1253,7 +1257,7 @@ def feast_hip_polynomial_projected(engine, coeffs, Emid, r, M0, fpm, *, Q0=None,
         return _empty_result(N, info, complex_lambda=True)
     if krylov is not None and union_csr is None:
         raise ValueError("a Krylov solver on P(z) needs sparse coefficients (union_csr)")
-    plan = _poly_setup(engine, coeffs, Emid, r, fpm, contour, union_csr, krylov)
+    plan = _poly_setup(engine, coeffs, Emid, r, fpm, contour, union_csr, krylov, prepared=prepared)
     poly = {"degree": d, "method": "projected", "columns": M0}
     stats = {"krylov_iterations": 0, "factorizations": 0, "solve_seconds": 0.0, "polynomial": poly}
     if plan is not None:
@@ -1307,6 +1311,32 @@ def nep_table(funcs, z):
                 raise ValueError(f"f_{k} must map an array to an array of the same shape")
             F[:, k] = v
     return F
+
+
+def poly_derivative_table(degree, z):
+    """D[i, k] = k z_i^(k-1), k = 0 .. degree: P'(z_i) = sum_k D[i, k] A_k for a polynomial, exact.  Column 0 is zero."""
+    z = np.atleast_1d(np.asarray(z, dtype=np.complex128))
+    D = np.zeros((len(z), int(degree) + 1), dtype=np.complex128)
+    for k in range(1, int(degree) + 1):
+        D[:, k] = k * z ** (k - 1)
+    return D
+
+
+def nep_derivative_table(funcs, z):
+    """D[i, k] ~ f_k'(z_i) for a 1-D array z, as the central difference (f_k(z + h) - f_k(z - h)) / 2h with h = NEWTON_FD
+    max(1, |z|) -- the quantity nep_newton_polish forms for the small problem, here for T'(z_i) = sum_k D[i, k] A_k of the count
+    estimate.  The f_k are still only evaluated.  Error: h^2 |f'''| / 6 of truncation plus eps |f| / h of rounding, 1e-10-class
+    for functions of unit scale (on the delay cases the trace built on it agrees with one built on a Cauchy-integral derivative
+    to the four digits printed).  A constant f_k gives an exactly zero column.  A value f_k(z_i +- h) that is not finite raises
+    ValueError, as a node value that is not finite does."""
+    z = np.atleast_1d(np.asarray(z, dtype=np.complex128))
+    h = NEWTON_FD * np.maximum(1.0, np.abs(z))
+    Fp, Fm = nep_table(funcs, z + h), nep_table(funcs, z - h)
+    bad = ~(np.isfinite(Fp) & np.isfinite(Fm))
+    if bad.any():
+        k = int(np.flatnonzero(bad.any(axis=0))[0])
+        raise ValueError(f"f_{k} is not finite next to a contour node (the central difference of the count estimate needs it there)")
+    return (Fp - Fm) / (2.0 * h[:, None])
 
 
 def _nep_at(Ahat, frow):
@@ -1397,7 +1427,7 @@ def nep_newton_polish(Ahat, funcs, theta0, v0, radius):
 
 
 def feast_hip_nonlinear(engine, mats, funcs, Emid, r, M0, fpm, *, Q0=None, seed=20260515, contour=None, eps_floor=0.0,
-                        union_csr=None, ortho="mgs", moments=2, reduced_nodes=128):
+                        union_csr=None, ortho="mgs", moments=2, reduced_nodes=128, prepared=False):
     """T(lambda) x = 0, T(lambda) = sum_k f_k(lambda) mats[k], inside a circle: feast_hip_polynomial_projected's loop
     (_projected_loop) on a term handle (engine.set_terms), with two changes.  The scalars are host tables of the f_k -- at the
     contour nodes once, at the shifts and the candidates once per loop -- so the device never sees the functions.  The reduced
@@ -1405,7 +1435,8 @@ def feast_hip_nonlinear(engine, mats, funcs, Emid, r, M0, fpm, *, Q0=None, seed=
     nep_newton_polish; the candidates then go through the polynomial method's ranking by device backward error (poly_select,
     POLY_SET_ASIDE).  Loop 0 is the plain sweep, which factors T(z_e) once per node; later loops are residual-inverse sweeps on
     the cached factors.  Stop test, loop limit and ``union_csr``: as feast_hip_polynomial_projected.  A circle in which the
-    reduced problem finds nothing returns Feast_ERROR_NO_CONVERGENCE with M = 0.  What an f_k raises is the caller's to see."""
+    reduced problem finds nothing returns Feast_ERROR_NO_CONVERGENCE with M = 0.  What an f_k raises is the caller's to see.
+    ``prepared``: as in _poly_setup (the node values are set again, which changes nothing when they are the same)."""
     N = mats[0].shape[0]
     feastdefault(fpm)
     info = _check_circle_input(N, M0, r)
@@ -1417,7 +1448,7 @@ def feast_hip_nonlinear(engine, mats, funcs, Emid, r, M0, fpm, *, Q0=None, seed=
     if not np.isfinite(F_node).all():
         k = int(np.flatnonzero(~np.isfinite(F_node).all(axis=0))[0])
         raise ValueError(f"f_{k} is not finite at a contour node")
-    plan = _poly_setup(engine, mats, Emid, r, fpm, (Zne, Wne), union_csr, terms=True)
+    plan = _poly_setup(engine, mats, Emid, r, fpm, (Zne, Wne), union_csr, terms=True, prepared=prepared)
     engine.nep_set_node_values(F_node)
     nep = {"terms": len(mats), "columns": M0, "moments": int(moments), "reduced_nodes": int(reduced_nodes), "reduced_seconds": 0.0}
     stats = {"krylov_iterations": 0, "factorizations": 0, "solve_seconds": 0.0, "nonlinear": nep}
@@ -1440,6 +1471,52 @@ def feast_hip_nonlinear(engine, mats, funcs, Emid, r, M0, fpm, *, Q0=None, seed=
         return engine.nep_ritz_eval(dQ, rank_q, Y, nep_table(funcs, theta))
 
     return _projected_loop(engine, N, M0, Emid, r, fpm, Q0, seed, eps_floor, ortho, stats, nep, sweep, reduced, evaluate)
+
+
+def feast_hip_poly_estimate(engine, mats, funcs, Emid, r, m, fpm, *, seed=ESTIMATE_SEED, contour=None, union_csr=None, krylov=None):
+    """Stochastic estimate of the number of eigenvalues of P(lambda) = sum_k lambda^k mats[k] (``funcs`` None) or T(lambda) =
+    sum_k f_k(lambda) mats[k] inside the contour: fpm[14] = 2 of feast_polynomial / feast_nonlinear.  For a regular T the count
+    is (1 / 2 pi i) oint tr(T(z)^-1 T'(z)) dz; with the contour's nodes and weights it is sum_e w_e tr(T'(z_e) T(z_e)^-1), and
+    Hutchinson's samples of that trace over m Rademacher columns come from one set of solves T(z_e)^-1 V
+    (engine.poly_estimate_count).  T'(z_e) = sum_k g_k(z_e) A_k goes to the device as the table G[e, k] = w_e g_k(z_e):
+    poly_derivative_table (exact) or nep_derivative_table (central differences of the f_k).
+    The estimate is a sum of filter values counted with algebraic multiplicity, not an integer; for a non-normal problem its
+    variance grows with the departure of the eigenvector basis from orthogonality.  ``union_csr`` / ``krylov``: as _poly_setup.
+    The engine keeps the problem, the contour and (direct solvers) the cached factors, so a solve that follows with
+    ``prepared=True`` factors nothing.
+
+    Returns (info, estimate, plan, factorizations): info 0 with the dict {mean, stderr, samples, nodes, solver, seed, seconds,
+    dropped_terms} -- stderr = std(t) / sqrt(m) of the complex samples, as feast_hip_estimate(general=True) reports it: it counts
+    the spread of the imaginary parts too, so it overstates the standard error of Re mean, which is what M is rounded from -- or the status 5 / 8 of a failed node as info and None; plan: what _poly_setup returned."""
+    t0 = time.perf_counter()
+    feastdefault(fpm)
+    Zne, Wne = feast_gcontour(Emid, r, fpm) if contour is None else contour
+    Zne, Wne = np.asarray(Zne, dtype=np.complex128), np.asarray(Wne, dtype=np.complex128)
+    F_node = None
+    if funcs is None:
+        D = poly_derivative_table(len(mats) - 1, Zne)
+    else:
+        F_node = nep_table(funcs, Zne)
+        if not np.isfinite(F_node).all():
+            k = int(np.flatnonzero(~np.isfinite(F_node).all(axis=0))[0])
+            raise ValueError(f"f_{k} is not finite at a contour node")
+        D = nep_derivative_table(funcs, Zne)
+    G = Wne[:, None] * D
+    plan = _poly_setup(engine, mats, Emid, r, fpm, (Zne, Wne), union_csr, krylov, terms=funcs is not None)
+    if F_node is not None:
+        engine.nep_set_node_values(F_node)
+    samples, status, st = engine.poly_estimate_count(int(m), seed, G)
+    nfact = int(st.get("factorizations", 0))
+    fail = int(np.max(status))
+    if fail:
+        return (int(FeastError.Feast_ERROR_LAPACK) if fail == 8 else int(FeastError.Feast_ERROR_NO_CONVERGENCE)), None, plan, nfact
+    solver = krylov[0] if krylov is not None else ("direct" if union_csr is None else "sparse_direct")
+    est = {"mean": complex(np.mean(samples)), "stderr": float(np.std(samples, ddof=1) / math.sqrt(m)) if m > 1 else math.inf,
+           "samples": samples.copy(), "nodes": len(Zne), "solver": solver, "seed": int(seed), "seconds": time.perf_counter() - t0,
+           "dropped_terms": [int(k) for k in np.flatnonzero(~G.any(axis=0))]}
+    if krylov is not None:
+        est["solver_tol"] = float(krylov[1])
+    return 0, est, plan, nfact
 
 
 TWO_SIDED_SOLVERS = ("direct", "lu")

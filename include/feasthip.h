@@ -634,6 +634,28 @@ int  feasthip_nep_resinv_apply_dev(feasthip_handle h, int64_t m, const void* sig
 int  feasthip_nep_ritz_eval_dev(feasthip_handle h, int64_t r, const void* dQ, int64_t ncand, const void* Y_host, const void* F_theta,
                                 void* dX, double* backward_error);
 
+/* ---- stochastic estimate of the eigenvalue count of a polynomial or term handle (fpm[14] = 2 of feast_polynomial / feast_nonlinear) --
+ * For a regular T the number of eigenvalues inside the contour is (1 / 2 pi i) oint tr(T(z)^-1 T'(z)) dz, with the handle's
+ * quadrature sum_e w_e tr(T'(z_e) T(z_e)^-1); for T = z B - A that is the trace feasthip_estimate_count samples.
+ * feasthip_poly_estimate_count: t_c = v_c^T [sum_e weight_scale w_e T'(z_e) T(z_e)^-1 v_c] for the m Rademacher columns of `seed`
+ *   (the (seed, i, j) rule of feasthip_random_block_dev), so mean(t) estimates the count (a sum of filter values counted with
+ *   algebraic multiplicity, not an integer) and std(t) / sqrt(m) its standard error.  T'(z) = sum_k g_k(z) A_k is given by the
+ *   host table G_host[e * (degree + 1) + k] = weight_scale w_e g_k(z_e) -- g_k(z) = k z^(k-1) for a polynomial handle, f_k' for a term
+ *   handle (nterms = degree + 1 columns) -- and a term whose column is zero at every node is left out of the work.  A value of G
+ *   that is not finite: FEASTHIP_ERROR_FPM, feasthip_last_error names the node and the term.  Serves a polynomial handle and a
+ *   term handle (which needs the node values of the current contour, feasthip_nep_set_node_values) under every solver the handle
+ *   takes; FEASTHIP_SOLVER_LU factors through the per-node cache, so a following sweep on the same contour factors nothing
+ *   (stats.factorizations counts what this call factored; the Krylov counts as in feasthip_poly_resinv_apply_dev).
+ *   samples: 2 * m doubles (re, im of t_c), written whatever the statuses; node_status[e]: 0, 5 or 8 as in
+ *   feasthip_poly_resinv_apply_dev.  dV (may be NULL): receives the block V the samples were taken with, N x m c128
+ *   column-major on the device (feasthip_random_block_dev itself refuses a polynomial handle).  m > 64 runs in 64-column
+ *   panels; 1 <= m <= min(N, 65535), else FEASTHIP_ERROR_M0.  The result is reproducible bit for bit.
+ *   feasthip_estimate_count keeps refusing a polynomial handle.                                                          */
+int  feasthip_poly_estimate_count(feasthip_handle h, int64_t m, uint64_t seed,
+                                  const void* G_host /* ne x (degree+1) c128, row e = w_e g_k(z_e) */,
+                                  double* samples /* 2*m: t_c re, im */, void* dV /* N x m c128 col-major, may be NULL */,
+                                  int* node_status, feasthip_stats* stats);
+
 /* ---- measurement support ---------------------------------------------------------- */
 /* Average device time (ms, HIP events on the handle's stream) and launch count of the
  * named kernel class since the last reset; classes: "spmm", "bicg_update", "dot_finalize",

@@ -129,7 +129,8 @@ def sparse_runs(eng, fk, np, pp, grid, runs):
         print(json.dumps({"measurement": "b", "method": name, "classes": profiled(eng, lambda: run(name))}), flush=True)
 
 
-def delay_run(eng, fk, np, pp, grid, runs):
+def delay_problem(np, grid):
+    """the delay problem of measurement (c) -> (terms, center, radius, eigenvalues inside, N)"""
     import scipy.sparse as sp
     from scipy.special import lambertw
     from feastkit_jl_amd import workloads
@@ -144,6 +145,11 @@ def delay_run(eng, fk, np, pp, grid, runs):
     radius = float(0.5 * (dist[j] + dist[j + 1]))
     inside = roots[np.abs(roots - center) <= radius]
     terms = [(sp.csr_matrix(A), 0), (sp.csr_matrix(B), lambda z: -z), (sp.csr_matrix(c * B), lambda z: np.exp(-tau * z))]
+    return terms, center, radius, inside, A.shape[0]
+
+
+def delay_run(eng, fk, np, pp, grid, runs):
+    terms, center, radius, inside, N = delay_problem(np, grid)
     fpm = fk.feastinit()
     fpm[8], fpm[3] = 16, 10
     ms = []
@@ -154,7 +160,7 @@ def delay_run(eng, fk, np, pp, grid, runs):
         eng.synchronize()
         ms.append(1e3 * (time.perf_counter() - t0))
     st = r.stats["nonlinear"]
-    print(json.dumps({"measurement": "c", "grid": list(grid), "N": A.shape[0], "center": [center.real, center.imag], "radius": radius,
+    print(json.dumps({"measurement": "c", "grid": list(grid), "N": N, "center": [center.real, center.imag], "radius": radius,
                       "expected_M": len(inside), "M": r.M, "info": r.info, "loops": r.loop, "epsout": r.epsout, "ms_median": float(np.median(ms[1:])),
                       "ms_all": [round(t, 1) for t in ms[1:]], "host_reduced_ms": 1e3 * st["reduced_seconds"], "plan": st.get("plan"),
                       "eigenvalue_error": pp.match_error(r.lambda_, inside), "eps_history": [float(e) for e in st["eps_history"]],
