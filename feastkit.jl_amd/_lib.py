@@ -36,6 +36,9 @@ class FeastHipPolicy(C.Structure):
 _vp, _i, _i64, _d = C.c_void_p, C.c_int, C.c_int64, C.c_double
 _pi, _pd, _pi64 = C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_int64)
 _ps = C.POINTER(FeastHipStats)
+# feasthip_apply_fn: (user, which, nodes, ld, N, dX, x_node_stride, dY, y_node_stride, stream) -> 0 or the caller's code
+APPLY_FN = C.CFUNCTYPE(_i, _vp, _i, _i, _i, _i64, _vp, _i64, _vp, _i64, _vp)
+OP_B_IDENTITY, OP_COMPLEX, OP_SYMMETRIC = 1, 2, 4      # FEASTHIP_OP_*
 SYMBOLS = {
     "feasthip_version": (_i, [_pi, _pi]),
     "feasthip_create": (_i, [C.POINTER(_vp), _i]),
@@ -51,6 +54,7 @@ SYMBOLS = {
     "feasthip_set_column_block": (_i, [_vp, _i64, _i64]),
     "feasthip_set_dense": (_i, [_vp, _i64, _i, _vp, _i64, _vp, _i64]),
     "feasthip_set_csr": (_i, [_vp, _i64, _i, _i, _i, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
+    "feasthip_set_operator": (_i, [_vp, _i64, APPLY_FN, _vp, _i]),
     "feasthip_set_contour": (_i, [_vp, _i, _vp, _vp, _d]),
     "feasthip_set_real_projection": (_i, [_vp, _i]),
     "feasthip_set_node_range": (_i, [_vp, _i, _i]),

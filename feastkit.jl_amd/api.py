@@ -992,3 +992,112 @@ def _feast_auto(driver, A, B, *where, fpm=None, engine=None, device=0, solver="d
         res.stats["estimate"] = est
         res.stats["M0_auto"] = M0
     return res
+
+
+# ---- matrix-free FEAST: the caller's operators on the device (engine.set_operator, feasthip_set_operator) ---------------------
+_MATVEC_KRYLOV = ("gmres", "bicgstab", "iterative", "cocg", "shifted_cocg", "block_cocg")
+HERMITIAN_PROBE_TOL = 1e-10       # |<x, A y> - <A x, y>| against the product norms, feast_matvec(check=True)
+
+
+class _ShapeOnly:
+    """stands where a matrix goes in a driver call on a preloaded engine: only its shape is read"""
+    def __init__(self, N):
+        self.shape = (N, N)
+
+
+def _check_matvec(who, A_mul, B_mul, N, M0, solver, symmetric, inner_precision):
+    """The argument checks of feast_matvec / feast_general_matvec; all of them run before an engine is made or used."""
+    if not callable(A_mul):
+        raise ValueError(f"{who}: A_mul must be callable, A_mul(Y, X) writes A X into Y")
+    if B_mul is not None and not callable(B_mul):
+        raise ValueError(f"{who}: B_mul must be callable or None (B = I)")
+    if int(N) < 1:
+        raise ValueError(f"{who}: N must be at least 1")
+    if isinstance(M0, str):
+        raise ValueError(f"{who}: M0 must be an integer (the count estimate of M0='auto' is not provided for operators)")
+    if solver in ("direct", "lu", "sparse_direct", "banded"):
+        raise ValueError(f"{who}: solver '{solver}' needs a matrix to factor; a matrix-free operator takes the Krylov solvers "
+                         "'gmres', 'bicgstab' or (symmetric=True) 'cocg'")
+    if solver not in _MATVEC_KRYLOV:
+        raise ValueError(f"{who}: unknown solver '{solver}'; a matrix-free operator takes the Krylov solvers 'gmres', 'bicgstab' "
+                         "or (symmetric=True) 'cocg'")
+    if solver in ("cocg", "shifted_cocg", "block_cocg") and not symmetric:
+        raise ValueError(f"{who}: solver '{solver}' needs symmetric=True (A = A^T and B = B^T); use 'bicgstab' or 'gmres' otherwise")
+    if inner_precision != 64:
+        raise ValueError(f"{who}: inner_precision={inner_precision} is not provided for operators (complex128 panels only)")
+
+
+def _hermitian_probe(eng, N, real, names, seed):
+    """|<x, M y> - <M x, y>| on one random two-column block for M = A (and B): ValueError naming the operator when they differ
+    by more than HERMITIAN_PROBE_TOL of the product norms."""
+    rng = np.random.default_rng(20260515 if seed is None else seed)
+    XY = rng.standard_normal((N, 2)) + (0 if real else 1j * rng.standard_normal((N, 2)))
+    dXY = eng.upload(XY)
+    for which, name in names:
+        M = eng.download(eng.matmul(which, dXY, 2), 2)
+        x, y, Mx, My = XY[:, 0], XY[:, 1], M[:, 0], M[:, 1]
+        gap = abs(np.vdot(x, My) - np.vdot(Mx, y))
+        scale = max(np.linalg.norm(x) * np.linalg.norm(My), np.linalg.norm(Mx) * np.linalg.norm(y))
+        if not gap <= HERMITIAN_PROBE_TOL * scale:
+            raise ValueError(f"feast_matvec: {name} is not Hermitian: |<x, {name} y> - <{name} x, y>| = {gap:.3e} on a random pair "
+                             f"(product norms {scale:.3e}); feast_general_matvec takes non-Hermitian operators")
+
+
+def _operator_delta(eng, before):
+    now = eng.operator_stats()
+    return {k: now[k] - before[k] for k in now}
+
+
+def feast_matvec(A_mul, B_mul, N, interval, *, M0=10, fpm=None, solver="gmres", solver_tol=1e-6, solver_maxiter=200,
+                 solver_restart=20, real=True, symmetric=False, batched=False, check=True, Q0=None, seed=None, contour=None,
+                 warm_start=True, inner_rtol=None, inner_precision=64, engine=None, device=0):
+    """Matrix-free feast: feast_matvec(A_mul!, B_mul!, N, interval; M0, fpm) of src/interfaces/feast_interfaces.jl:465-481 for
+    Hermitian operators that live on the device.  ``A_mul(Y, X)`` / ``B_mul(Y, X)`` write A X / B X into Y; X and Y are torch
+    views of the solver's panels (engine.set_operator describes them: ``real``, ``batched``); ``B_mul=None`` means B = I.  The
+    solver defaults are the reference's (GMRES(20), 1e-6, 200 steps: src/sparse/feast_sparse.jl:1287-1290); ``solver`` is
+    "gmres", "bicgstab" or -- ``symmetric=True``: A = A^T, B = B^T, i.e. real symmetric operators -- "cocg".  ``real=True``
+    (a real operator on the real view of the panels) also selects the real projection, as real matrices do in feast().
+    ``check``: a Hermitian probe of A (and B) on one random pair before the solve; ValueError names the operator that fails.
+    ``stats["operator"]`` = {A_calls, B_calls, callback_seconds} of this call, the probe included."""
+    _check_matvec("feast_matvec", A_mul, B_mul, N, M0, solver, symmetric, inner_precision)
+    N = int(N)
+    Emin, Emax = float(interval[0]), float(interval[1])
+    fpm = feastinit() if fpm is None else fpm
+    feastdefault(fpm)
+    eng = _engine(engine, device)
+    eng.set_operator(N, A_mul, B_mul, real=real, symmetric=symmetric, batched=batched)
+    before = eng.operator_stats()
+    if check:
+        _hermitian_probe(eng, N, real, [(0, "A")] + ([] if B_mul is None else [(1, "B")]), seed)
+    kw = {} if seed is None else {"seed": seed}
+    res = feast_hip_hermitian(eng, _ShapeOnly(N), None if B_mul is None else _ShapeOnly(N), Emin, Emax, min(int(M0), N), fpm,
+                              solver=solver, solver_tol=solver_tol, solver_maxiter=int(solver_maxiter),
+                              solver_restart=int(solver_restart), warm_start=bool(warm_start), inner_rtol=inner_rtol,
+                              real_projection=None if real else False, Q0=Q0, contour=contour, preloaded=True, **kw)
+    if isinstance(res.stats, dict):
+        res.stats["operator"] = _operator_delta(eng, before)
+    if real:
+        res = FeastResult(res.lambda_, np.real(res.q), res.M, res.res, res.info, res.epsout, res.loop, res.stats)
+    return res
+
+
+def feast_general_matvec(A_mul, B_mul, N, center, radius, *, M0=10, fpm=None, solver="gmres", solver_tol=1e-6,
+                         solver_maxiter=200, solver_restart=20, real=True, symmetric=False, batched=False, Q0=None, seed=None,
+                         contour=None, inner_precision=64, engine=None, device=0):
+    """Matrix-free feast_general: the eigenvalues of the caller's operators inside the circle (center, radius); the arguments
+    are feast_matvec's, ``real=False`` takes complex operators (complex128 panels of shape (N, ld)), and no Hermitian probe
+    runs.  ``stats["operator"]`` as in feast_matvec."""
+    _check_matvec("feast_general_matvec", A_mul, B_mul, N, M0, solver, symmetric, inner_precision)
+    N = int(N)
+    fpm = feastinit() if fpm is None else fpm
+    feastdefault(fpm)
+    eng = _engine(engine, device)
+    eng.set_operator(N, A_mul, B_mul, real=real, symmetric=symmetric, batched=batched)
+    before = eng.operator_stats()
+    kw = {} if seed is None else {"seed": seed}
+    res = feast_hip_general(eng, _ShapeOnly(N), None if B_mul is None else _ShapeOnly(N), complex(center), float(radius),
+                            min(int(M0), N), fpm, solver=solver, solver_tol=solver_tol, solver_maxiter=int(solver_maxiter),
+                            solver_restart=int(solver_restart), Q0=Q0, contour=contour, preloaded=True, **kw)
+    if isinstance(res.stats, dict):
+        res.stats["operator"] = _operator_delta(eng, before)
+    return res

@@ -203,6 +203,7 @@ void fh_free_problem(feasthip_ctx* h) {
     h->dense = fh_dense();
     for (void* p : h->poly.coef) if (p) hipFree(p);
     h->poly = fh_poly();
+    h->op = fh_operator();
     for (void* p : h->lu_factors) if (p) hipFree(p);
     for (int* p : h->lu_pivots) if (p) hipFree(p);
     h->lu_factors.clear(); h->lu_pivots.clear(); h->lu_valid.clear(); h->lu_z.clear();
@@ -439,6 +440,20 @@ extern "C" int feasthip_set_dense(feasthip_handle h, int64_t N, int is_complex, 
     return 0;
 }
 
+// What an operator handle (h->kind == 4, feasthip_set_operator) cannot take; every message names the solvers it does take
+static const char* const fh_operator_why_adjoint =
+    "an operator handle (feasthip_set_operator) has no adjoint form: the callback applies A and B only, under the Krylov solvers FEASTHIP_SOLVER_BICGSTAB, _COCG or _GMRES";
+static const char* fh_operator_solver_why(const feasthip_ctx* h, int kind, int factor_precision) {
+    if (kind == FEASTHIP_SOLVER_LU || kind == FEASTHIP_SOLVER_BANDED)
+        return "an operator handle (feasthip_set_operator) has no matrix to factor: use the Krylov solvers FEASTHIP_SOLVER_BICGSTAB, _COCG or _GMRES";
+    const bool cocg = kind == FEASTHIP_SOLVER_COCG || kind == FEASTHIP_SOLVER_SHIFTED_COCG || kind == FEASTHIP_SOLVER_BLOCK_COCG;
+    if (cocg && (!h->op.symmetric || h->dense.is_complex))
+        return "FEASTHIP_SOLVER_COCG on an operator handle needs FEASTHIP_OP_SYMMETRIC and a real operator (A = A^T, B = B^T): of the Krylov solvers FEASTHIP_SOLVER_BICGSTAB, _COCG or _GMRES take _BICGSTAB or _GMRES";
+    if (factor_precision == 32)
+        return "factor_precision = 32 is not supported on an operator handle: the Krylov solvers FEASTHIP_SOLVER_BICGSTAB, _COCG or _GMRES run on complex128 panels";
+    return nullptr;
+}
+
 extern "C" int feasthip_set_contour(feasthip_handle h, int ne, const double* zne, const double* wne, double weight_scale) {
     if (!h) return FEASTHIP_ERROR_INTERNAL;
     if (ne <= 0 || !zne || !wne) { h->last_error = "feasthip_set_contour: ne <= 0 or null arrays"; return FEASTHIP_ERROR_FPM; }
@@ -471,6 +486,12 @@ extern "C" int feasthip_set_node_solver(feasthip_handle h, int count, const int*
             h->last_error = "feasthip_set_node_solver: kind " + std::to_string(kinds[e]) + " of node " + std::to_string(e) + " (0 or FEASTHIP_SOLVER_BANDED)";
             return FEASTHIP_ERROR_FPM;
         }
+    if (h->kind == 4)
+        for (int e = 0; e < count; ++e)
+            if (kinds[e] != 0) {
+                h->last_error = "feasthip_set_node_solver: an operator handle (feasthip_set_operator) has no matrix for a direct node; every node takes the Krylov solvers FEASTHIP_SOLVER_BICGSTAB, _COCG or _GMRES";
+                return FEASTHIP_ERROR_FPM;
+            }
     h->node_kinds.assign(kinds, kinds + count);
     return 0;
 }
@@ -495,6 +516,7 @@ extern "C" int feasthip_set_real_projection(feasthip_handle h, int real_part) {
 extern "C" int feasthip_set_adjoint(feasthip_handle h, int on) {
     if (!h) return FEASTHIP_ERROR_INTERNAL;
     if (on && h->kind == 3) { h->last_error = "feasthip_set_adjoint: a polynomial handle has no adjoint form (the feasthip_poly_* calls are forward only)"; return FEASTHIP_ERROR_FPM; }
+    if (on && h->kind == 4) { h->last_error = std::string("feasthip_set_adjoint: ") + fh_operator_why_adjoint; return FEASTHIP_ERROR_FPM; }
     h->adjoint = on ? 1 : 0;
     return 0;
 }
@@ -570,6 +592,8 @@ extern "C" int feasthip_set_solver(feasthip_handle h, int kind, double rtol, dou
             return FEASTHIP_ERROR_FPM;
         }
     }
+    if (h->kind == 4)
+        if (const char* why = fh_operator_solver_why(h, kind, factor_precision)) { h->last_error = std::string("feasthip_set_solver: ") + why; return FEASTHIP_ERROR_FPM; }
     // SHIFTED_COCG is COCG with the shifted sweep where fh_contour_apply_panel finds it eligible: every other path sees COCG
     h->shifted = kind == FEASTHIP_SOLVER_SHIFTED_COCG ? 1 : 0;
     // BLOCK_COCG likewise: COCG with the block sweep where the panel is eligible
@@ -597,6 +621,7 @@ struct fh_op_call {
     int uniform_coef = 0;  // coefA/coefB identical across columns
     int prec = 64;         // panel precision of X/Y/Bvec/U
     const cplx* colscale = nullptr;   // row kernel only (fh_spmm_args::colscale): X is a shared panel times per-node column factors
+    int skip = 0;          // host hint (operator handle): bit 0 -- coefA is zero everywhere, bit 1 -- coefB is: that callback is not made
 };
 
 // full-width panels over a real matrix go through the row-per-wave kernel (FH_SPMM_ROW=0: the 4-rows-per-wave gather kernel)
@@ -665,6 +690,21 @@ static int fh_apply_operator(feasthip_ctx* h, int ld, const fh_op_call& c) {
         a.nodes = c.nodes; a.m = c.m;
         return fh_launch_spmm_poly(h, ld, a);
     }
+    if (h->kind == 4) {
+        // operator handle: the caller's products, then one launch of k_op_combine (fh_operator.hip); complex128 panels, the
+        // plain product and dot modes 1 .. 4.  -1 also when a callback failed (h->op.failed): the caller returns at once
+        if (h->adjoint || c.prec != 64 || c.colscale || c.dot_mode == 6 || !c.coefA || !c.coefB) {
+            h->last_error = "internal: the operator handle takes forward products on complex128 panels and dot modes 0 .. 4";
+            return -1;
+        }
+        fh_userop_call a;
+        a.X = (const cplx*)c.X; a.x_node_stride = c.x_stride; a.Y = (cplx*)c.Y; a.y_node_stride = c.y_stride;
+        a.coefA = c.coefA; a.coefB = c.coefB; a.Bvec = (const cplx*)c.Bvec; a.b_node_stride = c.b_stride;
+        a.U = (const cplx*)c.U; a.u_node_stride = c.u_stride;
+        a.dot_mode = c.dot_mode; a.partial1 = c.partial1; a.partial2 = c.partial2; a.node_active = c.node_active;
+        a.nodes = c.nodes; a.skip = c.skip;
+        return fh_apply_user_operator(h, ld, a);
+    }
     fh_dense_op_args a;
     a.A = h->dense.A; a.B = h->dense.B; a.N = (int)h->dense.N; a.is_complex = h->dense.is_complex;
     // dense operator: complex128 panels only (fh_krylov forces prec 64 for dense matrices)
@@ -693,6 +733,7 @@ static int fh_op_nblk(feasthip_ctx* h, int ld) {
     if (h->kind == 2) return std::max(std::max(fh_spmm_partials((int)h->csr.N, ld), ld == 64 ? fh_spmm_row_grid((int)h->csr.N) : 0),
                                       h->csr.lcol ? (8 / (ld / 16)) * fh_spmm_lds_slots(h->csr.nblk, ld) : 0);
     if (h->kind == 3 && h->poly.sparse) return fh_poly_op_nblk((int)h->dense.N, ld);
+    if (h->kind == 4) return fh_op_combine_nblk((int)h->dense.N, ld);
     return fh_dense_op_nblk((int)h->dense.N);
 }
 // row permutation of the panels (block order of a renumbered sparse matrix), or null
@@ -710,6 +751,10 @@ static int fh_check_problem(feasthip_ctx* h, int64_t m, int wide = 0) {
                         "feasthip_poly_contour_apply_dev, feasthip_poly_matmul_dev, feasthip_poly_project_dev or feasthip_poly_ritz_residual_dev";
         return FEASTHIP_ERROR_FPM;
     }
+    if (h->kind == 4) {
+        h->op.failed = 0;          // a new entry point: the callback is tried again
+        if (h->comm) { h->last_error = "an operator handle (feasthip_set_operator) does not take an attached communicator: it sweeps on one rank, under the Krylov solvers FEASTHIP_SOLVER_BICGSTAB, _COCG or _GMRES"; return FEASTHIP_ERROR_FPM; }
+    }
     if (m <= 0 || (!wide && m > FH_MAX_LD) || m > fh_N(h)) {
         h->last_error = wide ? "block width m must satisfy 1 <= m <= N" : "block width m must satisfy 1 <= m <= min(N, 64)";
         return FEASTHIP_ERROR_M0;
@@ -724,6 +769,7 @@ static int fh_check_problem(feasthip_ctx* h, int64_t m, int wide = 0) {
 static int fh_check_adjoint(feasthip_ctx* h, const char* what, const char* unsupported = nullptr) {
     if (!h || !h->adjoint) return 0;
     const char* why = unsupported;
+    if (!why && h->kind == 4) why = fh_operator_why_adjoint;
     if (!why && h->kind == 2 && h->solver == FEASTHIP_SOLVER_LU) why = "a CSR problem has no dense LU; its adjoint substitution needs FEASTHIP_SOLVER_BANDED (multifrontal plan or blocked band LU)";
     if (!why && h->kind == 2 && h->solver != FEASTHIP_SOLVER_BANDED) why = "the solver of a CSR problem must be the sparse direct one (FEASTHIP_SOLVER_BANDED): there is no Krylov solver on the conjugate transpose";
     if (!why && h->kind != 2 && h->solver != FEASTHIP_SOLVER_LU) why = "the solver must be the dense LU (FEASTHIP_SOLVER_LU)";
@@ -741,6 +787,18 @@ static int fh_check_adjoint(feasthip_ctx* h, const char* what, const char* unsup
     }
     if (!why) return 0;
     h->last_error = std::string(what) + " with the adjoint switch on (feasthip_set_adjoint): " + why;
+    return FEASTHIP_ERROR_FPM;
+}
+
+// Operator handle: the solver settings may date from another problem (feasthip_set_solver refuses them only while the operator
+// is set), so the entry points that solve look again
+static int fh_check_operator_solve(feasthip_ctx* h, const char* what) {
+    if (h->kind != 4) return 0;
+    const char* why = fh_operator_solver_why(h, h->solver, h->factor_precision);
+    if (!why)
+        for (int k : h->node_kinds) if (k != 0) { why = "an operator handle (feasthip_set_operator) has no matrix for a direct node (feasthip_set_node_solver); every node takes the Krylov solvers FEASTHIP_SOLVER_BICGSTAB, _COCG or _GMRES"; break; }
+    if (!why) return 0;
+    h->last_error = std::string(what) + ": " + why;
     return FEASTHIP_ERROR_FPM;
 }
 
@@ -973,7 +1031,8 @@ struct fh_krylov_work {
     fh_fused_fin_args ff;                    // (fused iteration; s, rho, rr and tickets are filled once)
     int alloc(const std::vector<cplx>& z, const std::vector<cplx>* wnode);
     int start(const std::vector<cplx>& z, const cplx* RHS, cplx* X, const fh_krylov_opts& opt);
-    void bicgstab_step(), cocg_step(), cocg_fused_step(int it);
+    int bicgstab_step(), cocg_step();          // non-zero: the operator failed (an operator handle's callback), nothing more was queued
+    void cocg_fused_step(int it);
 };
 
 // allocate: the work panels R, Rhat, P, V, S, T (+ D and RHS32 for the mixed-precision correction), the per-column scalars
@@ -988,6 +1047,8 @@ int fh_krylov_work::alloc(const std::vector<cplx>& z, const std::vector<cplx>* w
     auto vec = [&](int i) { return (void*)(base + (size_t)i * nodes * panel * esz); };
     R = vec(0); Rh = vec(1); P = vec(2); V = vec(3); S = vec(4); T = vec(5);
     if (prec == 32) { D = vec(6); RHS32 = vec(7); }
+    // operator handle: the callback sees whole panels, and the vector kernels never write the padding columns of S and T
+    if (h->kind == 4) FH_CHECK(hipMemsetAsync(base, 0, (size_t)nvec * nodes * panel * esz, h->stream));
     const size_t nl = (size_t)nodes * ld;
     if ((rc = fh_buf(h, "kry_scal_c", 4 * nl, &s.rho))) return rc;
     s.alpha = s.rho + nl; s.omega = s.alpha + nl; s.beta = s.omega + nl;
@@ -1051,6 +1112,7 @@ int fh_krylov_work::start(const std::vector<cplx>& z, const cplx* RHS, cplx* X, 
         oc.prec = 64; oc.X = X; oc.x_stride = panel; oc.Y = R64; oc.y_stride = panel; oc.Bvec = RHS; oc.b_stride = 0;
         oc.dot_mode = 3; oc.node_active = nullptr;
         fa.nblk = fh_apply_operator(h, ld, oc);
+        if (fa.nblk < 0) return FEASTHIP_ERROR_INTERNAL;
         res.op_calls += 1;
     }
     if (!shared_start && prec == 32) {
@@ -1098,27 +1160,31 @@ int fh_krylov_work::start(const std::vector<cplx>& z, const cplx* RHS, cplx* X, 
 }
 
 // One BiCGStab step: two operator products, each with its finalize and vector update, then rho and the new direction
-void fh_krylov_work::bicgstab_step() {
+int fh_krylov_work::bicgstab_step() {
     // V = S P, sigma = <Rhat, V>
     oc.X = P; oc.Y = V; oc.U = Rh; oc.u_stride = panel; oc.dot_mode = 1; oc.node_active = s.node_active;
     fa.nblk = fh_apply_operator(h, ld, oc);
+    if (fa.nblk < 0) return FEASTHIP_ERROR_INTERNAL;
     fh_prof_begin(h, "dot_finalize"); fh_launch_fin_alpha(fa, ld, nodes, h->stream); fh_prof_end(h);
     fh_prof_begin(h, "bicg_s"); fh_launch_s_update(va, ld, nblk_vec, nodes, h->stream); fh_prof_end(h);
     // T = S S, <T,S>, <T,T>
     oc.X = S; oc.Y = T; oc.U = nullptr; oc.dot_mode = 2;
     fa.nblk = fh_apply_operator(h, ld, oc);
+    if (fa.nblk < 0) return FEASTHIP_ERROR_INTERNAL;
     fh_prof_begin(h, "dot_finalize"); fh_launch_fin_omega(fa, ld, nodes, h->stream); fh_prof_end(h);
     fh_prof_begin(h, "bicg_xr"); fh_launch_xr_update(va, ld, nblk_vec, nodes, h->stream); fh_prof_end(h);
     fa.nblk = nblk_vec;
     fh_prof_begin(h, "dot_finalize"); fh_launch_fin_rho(fa, ld, nodes, h->stream); fh_prof_end(h);
     fh_prof_begin(h, "bicg_p"); fh_launch_p_update(va, ld, nblk_vec, nodes, h->stream); fh_prof_end(h);
     res.op_calls += 2;
+    return 0;
 }
 
 // One COCG step in five launches: Q = S P with sigma = p^T S p, finalize, x / r update, finalize of rho, new direction
-void fh_krylov_work::cocg_step() {
+int fh_krylov_work::cocg_step() {
     oc.X = P; oc.Y = V; oc.U = nullptr; oc.dot_mode = 4; oc.node_active = s.node_active;     // Q is stored in V
     fa.nblk = fh_apply_operator(h, ld, oc);
+    if (fa.nblk < 0) return FEASTHIP_ERROR_INTERNAL;
     fh_prof_begin(h, "dot_finalize"); fh_launch_fin_alpha(fa, ld, nodes, h->stream); fh_prof_end(h);
     fh_prof_begin(h, "cocg_xr"); fh_launch_cocg_update(va, ld, nblk_vec, nodes, h->stream); fh_prof_end(h);
     fa.nblk = nblk_vec;
@@ -1128,6 +1194,7 @@ void fh_krylov_work::cocg_step() {
     else fh_launch_cocg_p(va, ld, nblk_vec, nodes, h->stream);
     fh_prof_end(h);
     res.op_calls += 1;
+    return 0;
 }
 
 // Step `it` of the fused COCG iteration (fh_sparse.hip): Q = S P (stored in V) with sigma = p^T q and kappa = q^T q, one
@@ -1164,8 +1231,8 @@ int fh_krylov(feasthip_ctx* h, int method, int prec, int ld, int m, int nodes, c
     // iterate: the steps go to the stream in chunks; the published count is the number of nodes with a live column
     const auto t_loop0 = std::chrono::steady_clock::now();
     const int it = fh_queue_chunks(h, k.s.node_active, nodes, k.N, nodes, [&](int i) {
-        method == 0 ? k.bicgstab_step() : k.fused ? k.cocg_fused_step(i) : k.cocg_step();
-        return 0;
+        if (k.fused) { k.cocg_fused_step(i); return 0; }
+        return method == 0 ? k.bicgstab_step() : k.cocg_step();
     }, &rc);
     if (rc) return rc;
     // finish: the fused iteration's last stop test (true norms from the last vector kernel's partials: no SpMM follows it),
@@ -1439,6 +1506,10 @@ int fh_gmres(feasthip_ctx* h, int ld, int m, int nodes_all, const std::vector<cp
         ga.inv = sd; ga.r0norm = sd + nl; ga.target = sd + 2 * nl; ga.rnorm = sd + 3 * nl;
         ga.active = si; ga.iters = si + nl; ga.status = si + 2 * nl; ga.kdim = si + 3 * nl; ga.node_active = si + 4 * nl;
         FH_CHECK(hipMemsetAsync(sc, 0, hsz * sizeof(cplx), h->stream));
+        if (h->kind == 4) {     // operator handle: the callback sees whole basis panels, padding columns included
+            FH_CHECK(hipMemsetAsync(V, 0, (size_t)nodes * (mr + 1) * panel * sizeof(cplx), h->stream));
+            FH_CHECK(hipMemsetAsync(W, 0, (size_t)nodes * panel * sizeof(cplx), h->stream));
+        }
 
         cplx *dca, *dcb;
         if ((rc = fh_upload_shift_coefs(h, "gm_coefA", "gm_coefB", z.data() + e0, nodes, ld, &dca, &dcb))) return rc;
@@ -1455,6 +1526,7 @@ int fh_gmres(feasthip_ctx* h, int ld, int m, int nodes_all, const std::vector<cp
             // true residual r = b - S x (into W), ||r|| per column, activity from the stop test
             oc.X = Xb; oc.x_stride = stride; oc.Y = W; oc.y_stride = panel; oc.Bvec = RHS; oc.b_stride = 0; oc.dot_mode = 3; oc.node_active = nullptr;
             const int nb_norm = fh_apply_operator(h, ld, oc);
+            if (nb_norm < 0) return FEASTHIP_ERROR_INTERNAL;
             res.op_calls += 1;
             fh_launch_gm_start(ga, ld, nb_norm, nodes, first, h->rtol, h->atol, m, h->stream);
             first = 0;
@@ -1472,8 +1544,9 @@ int fh_gmres(feasthip_ctx* h, int ld, int m, int nodes_all, const std::vector<cp
             for (int k = 0; k < mr && total_it + k < h->maxit; ++k) {
                 oc.X = V + (size_t)k * panel; oc.x_stride = ga.v_node_stride; oc.Y = W; oc.y_stride = panel; oc.Bvec = nullptr;
                 oc.dot_mode = 0; oc.node_active = ga.node_active; oc.partial2 = nullptr;
-                fh_apply_operator(h, ld, oc);                                                  // w = S v_k
+                const int nb_w = fh_apply_operator(h, ld, oc);                                 // w = S v_k
                 oc.partial2 = npart;
+                if (nb_w < 0) return FEASTHIP_ERROR_INTERNAL;
                 fh_prof_begin(h, "gmres_ortho");
                 fh_launch_gm_orthogonalize(ga, ld, k, nblk_vec, nodes, h->stream);             // CGS2 against v_0..v_k
                 fh_launch_gm_givens(ga, ld, k, nblk_vec, nodes, h->stream);
@@ -1661,7 +1734,7 @@ static int fh_shared_start_source(feasthip_ctx* h, const fh_panel_sweep& g, cons
     fh_op_call oc;
     oc.m = g.m;
     oc.X = g.Qp; oc.Y = eigres; oc.coefA = dca; oc.coefB = dcb;
-    fh_apply_operator(h, g.ld, oc);                    // A q - lambda B q (B = I handled by the operator kernel)
+    if (fh_apply_operator(h, g.ld, oc) < 0) return FEASTHIP_ERROR_INTERNAL;      // A q - lambda B q (B = I handled by the operator kernel)
     *src = eigres;
     return 0;
 }
@@ -1803,6 +1876,7 @@ static int fh_contour_apply_panel(feasthip_ctx* h, int64_t m64, const cplx* dQ, 
                                   const fh_moment_ctx* mom = nullptr, const fh_panel_io* io = nullptr) {
     int rc = fh_check_problem(h, m64);
     if (rc) return rc;
+    if ((rc = fh_check_operator_solve(h, "contour_apply"))) return rc;
     if (h->zne.empty()) { h->last_error = "no contour set"; return FEASTHIP_ERROR_FPM; }
     auto t0 = std::chrono::steady_clock::now();
     FH_CHECK(hipSetDevice(h->device));
@@ -1841,8 +1915,8 @@ static int fh_contour_apply_panel(feasthip_ctx* h, int64_t m64, const cplx* dQ, 
         if ((rc = fh_upload_coefs(h, "ca_coefB", cb, &dcb))) return rc;
         fh_op_call oc;
         oc.m = m;
-        oc.X = g.Qp; oc.Y = g.Rhs; oc.coefA = dca; oc.coefB = dcb;
-        fh_apply_operator(h, ld, oc);
+        oc.X = g.Qp; oc.Y = g.Rhs; oc.coefA = dca; oc.coefB = dcb; oc.skip = 1;
+        if (fh_apply_operator(h, ld, oc) < 0) return FEASTHIP_ERROR_INTERNAL;
     }
     // Per-node solver (feasthip_set_node_solver): the local nodes split into a Krylov set and a direct set; with no direct
     // node the order is the identity and nothing below differs from the one-solver sweep.
@@ -2554,6 +2628,7 @@ extern "C" int feasthip_orthonormalize_dev(feasthip_handle h, int64_t m64, void*
 extern "C" int feasthip_poly_orthonormalize_dev(feasthip_handle h, int64_t m64, void* dQ, int unit_columns, double rank_tol, int* rank) {
     if (!h) return FEASTHIP_ERROR_INTERNAL;
     if (h->poisoned) { h->last_error = "handle poisoned by an earlier device failure: destroy it"; return FEASTHIP_ERROR_INTERNAL; }
+    if (h->kind == 4) { h->last_error = "feasthip_poly_orthonormalize_dev: an operator handle (feasthip_set_operator) has no polynomial form: it takes feasthip_orthonormalize_dev and the other pencil entry points, under the Krylov solvers FEASTHIP_SOLVER_BICGSTAB, _COCG or _GMRES"; return FEASTHIP_ERROR_FPM; }
     if (h->kind != 3) { h->last_error = "feasthip_poly_orthonormalize_dev: needs a polynomial handle (feasthip_set_polynomial); a dense or CSR handle takes feasthip_orthonormalize_dev"; return FEASTHIP_ERROR_FPM; }
     if (m64 <= 0 || m64 > fh_N(h)) { h->last_error = "feasthip_poly_orthonormalize_dev: block width m must satisfy 1 <= m <= N"; return FEASTHIP_ERROR_M0; }
     if (!dQ || !rank) { h->last_error = "feasthip_poly_orthonormalize_dev: null argument"; return FEASTHIP_ERROR_INTERNAL; }
@@ -2645,7 +2720,7 @@ struct fh_op_gram {
         fh_op_call oc;
         oc.m = m;
         oc.X = X; oc.Y = W;
-        oc.coefA = which == 0 ? d1 : d0; oc.coefB = which == 0 ? d0 : d1;
+        oc.coefA = which == 0 ? d1 : d0; oc.coefB = which == 0 ? d0 : d1; oc.skip = which == 0 ? 2 : 1;
         return fh_apply_operator(h, ld, oc) < 0 ? (int)FEASTHIP_ERROR_INTERNAL : 0;
     }
     // queues G = QL^H W (bilinear: QL^T W) as one launch of the "gram" profile class
@@ -2818,8 +2893,8 @@ static int fh_panel_residual(feasthip_ctx* h, int ld, int ncols, const cplx* X, 
     if ((rc = fh_upload_coefs(h, "rz_coefB", cb, &dcb))) return rc;
     fh_op_call oc;
     oc.m = ncols;
-    oc.X = X; oc.Y = R; oc.coefA = dca; oc.coefB = dcb;
-    fh_apply_operator(h, ld, oc);
+    oc.X = X; oc.Y = R; oc.coefA = dca; oc.coefB = dcb; oc.skip = lam_in_op ? 0 : 2;
+    if (fh_apply_operator(h, ld, oc) < 0) return FEASTHIP_ERROR_INTERNAL;
     if (!lam_in_op) {
         std::vector<cplx> lam(ld, cmake(0, 0));
         for (int c = 0; c < ncols; ++c) lam[c] = cmake(lambda[2 * c], lambda[2 * c + 1]);
@@ -3400,8 +3475,8 @@ extern "C" int feasthip_matmul_dev(feasthip_handle h, int which, int64_t m64, co
     if ((rc = fh_upload_coefs(h, "mm_coefB", cb, &dcb))) return rc;
     fh_op_call oc;
     oc.m = m;
-    oc.X = Xp; oc.Y = Yp; oc.coefA = dca; oc.coefB = dcb;
-    fh_apply_operator(h, ld, oc);
+    oc.X = Xp; oc.Y = Yp; oc.coefA = dca; oc.coefB = dcb; oc.skip = which == 0 ? 2 : 1;
+    if (fh_apply_operator(h, ld, oc) < 0) return FEASTHIP_ERROR_INTERNAL;
     fh_launch_from_panel(Yp, ld, N, m, (cplx*)dY, N, h->stream, fh_perm(h));
     FH_CHECK(hipStreamSynchronize(h->stream));
     fh_prof_collect(h);
@@ -3450,6 +3525,7 @@ extern "C" int feasthip_shifted_solve_dev(feasthip_handle h, double z_re, double
     int rc = fh_check_problem(h, m64);
     if (rc) return rc;
     if (!dX || !dY) { h->last_error = "shifted_solve: null argument"; return FEASTHIP_ERROR_INTERNAL; }
+    if ((rc = fh_check_operator_solve(h, "shifted_solve"))) return rc;
     if ((rc = fh_check_adjoint(h, "shifted_solve"))) return rc;
     FH_CHECK(hipSetDevice(h->device));
     const int m = (int)m64, ld = fh_pick_ld(m), N = (int)fh_N(h);

@@ -152,6 +152,19 @@ template <int TOP, typename FS, typename F> __device__ __forceinline__ cplx fh_t
     return v;
 }
 
+// Operator handle (h->kind == 4, feasthip_set_operator): the products A X and B X are the caller's callback
+// (feasthip_apply_fn of include/feasthip.h) on whole node batches of panels; fh_operator.hip turns them into what the
+// drivers read.  N, b_identity and is_complex live in fh_dense.  failed: a callback of the running entry point returned
+// non-zero -- no further product is made or launched in that call (cleared by fh_check_problem at the next one).
+typedef int (*fh_apply_fn)(void* user, int which, int nodes, int ld, int64_t N, const void* dX, int64_t x_node_stride, void* dY,
+                           int64_t y_node_stride, void* stream);
+struct fh_operator {
+    fh_apply_fn apply = nullptr;
+    void* user = nullptr;
+    int symmetric = 0;
+    int failed = 0;
+};
+
 // Per-(node,column) Krylov scalars, struct of arrays; each array is [nodes][ld].
 struct fh_krylov_scalars {
     cplx* rho = nullptr;
@@ -180,8 +193,9 @@ struct feasthip_ctx {
     std::string last_error;
 
     // problem
-    int kind = 0;  // 0 none, 1 dense, 2 sparse, 3 matrix polynomial, dense or (poly.sparse) CSR (the feasthip_poly_* entry points only)
+    int kind = 0;  // 0 none, 1 dense, 2 sparse, 3 matrix polynomial, dense or (poly.sparse) CSR (the feasthip_poly_* entry points only), 4 operator (Krylov solvers only)
     fh_poly poly;
+    fh_operator op;
     fh_csr csr;
     // conjugate transpose of `csr` (A^H, B^H on the transposed union pattern, internal numbering; rowptr / col / aval / bval only):
     // built at the first adjoint product of a CSR problem (fh_api.hip: fh_adjoint_csr_ensure), freed with the problem

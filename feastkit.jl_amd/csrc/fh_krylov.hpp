@@ -1,5 +1,5 @@
-// fh_krylov.hpp -- the batched Krylov drivers of fh_api.hip for the other .hip units, and the polynomial operator
-// (fh_poly.hip) that fh_apply_operator launches for a sparse polynomial handle.
+// fh_krylov.hpp -- the batched Krylov drivers of fh_api.hip for the other .hip units, and the operators that fh_apply_operator
+// launches for a sparse polynomial handle (fh_poly.hip) and for an operator handle (fh_operator.hip).
 #pragma once
 #include "fh_common.hpp"
 #include <vector>
@@ -49,3 +49,21 @@ struct fh_polyop_call {
 };
 int fh_poly_op_nblk(int N, int ld);
 int fh_launch_spmm_poly(feasthip_ctx* h, int ld, const fh_polyop_call& c);
+
+// Y_e = [Bvec -] (coefB[e] B X_e + coefA[e] A X_e) on an operator handle (fh_operator.hip): the caller's callback forms A X
+// and B X for all nodes, k_op_combine does the rest; complex128 panels, the fields are those of fh_spmm_args.  skip: what the
+// host knows about the coefficients -- bit 0: coefA is zero everywhere, bit 1: coefB is -- so that the unused callback is not
+// made.  Returns the partial-sum rows per node it wrote (fh_op_combine_nblk), or -1 with last_error set: a failed callback
+// (h->op.failed is then set and every later call returns -1 at once) or a workspace that could not be had.
+struct fh_userop_call {
+    const cplx* X; size_t x_node_stride;
+    cplx* Y; size_t y_node_stride;
+    const cplx* coefA; const cplx* coefB;             // [nodes][ld]
+    const cplx* Bvec; size_t b_node_stride;
+    const cplx* U; size_t u_node_stride;
+    int dot_mode; cplx* partial1; cplx* partial2;     // modes 0 .. 4 of fh_sparse.hip
+    const int* node_active;
+    int nodes, skip;
+};
+int fh_op_combine_nblk(int N, int ld);
+int fh_apply_user_operator(feasthip_ctx* h, int ld, const fh_userop_call& c);

@@ -35,6 +35,7 @@
 // sparse direct solver (fh_dense.hip, planned by fh_banded.hip, its per-node factor cache as it stands), and Y +-= A_k X is
 // k_spmm_fan below.  Everything else in this file is shared by the two flavours.
 #include "fh_common.hpp"
+#include "fh_device.hpp"
 #include "fh_kernels.hpp"
 #include "fh_krylov.hpp"
 #include "fh_dense.hpp"
@@ -429,23 +430,6 @@ struct fh_polyop_args {
     unsigned long long* counters;     // profiling: [0] active node-launches, [1] active column x vector passes (may be null)
 };
 
-__device__ __forceinline__ cplx poly_ld_nt(const cplx* p) { return cmake(__builtin_nontemporal_load(&p->x), __builtin_nontemporal_load(&p->y)); }
-__device__ __forceinline__ void poly_st_nt(cplx* p, cplx v) { __builtin_nontemporal_store(v.x, &p->x); __builtin_nontemporal_store(v.y, &p->y); }
-
-// out[c] = the sum over the FH_BLOCK / LD threads t = c + k LD of a workgroup of their dsum, added through LDS in ascending k
-// (every thread of the workgroup calls it; red: FH_BLOCK elements; ostride: elements between the columns of out)
-template <int LD> __device__ __forceinline__ void poly_column_sum(cplx* red, int t, cplx dsum, cplx* out, size_t ostride = 1) {
-    red[t] = dsum;
-    __syncthreads();
-    if (t < LD) {
-        cplx s = red[t];
-#pragma unroll
-        for (int k = 1; k < FH_BLOCK / LD; ++k) s = cadd(s, red[t + k * LD]);
-        out[t * ostride] = s;
-    }
-    __syncthreads();
-}
-
 template <typename VT, int LD>
 __global__ __launch_bounds__(FH_BLOCK) void k_spmm_poly(fh_polyop_args a) {
     constexpr int ROWS = FH_BLOCK / LD;
@@ -492,15 +476,15 @@ __global__ __launch_bounds__(FH_BLOCK) void k_spmm_poly(fh_polyop_args a) {
                 cfma(acc, v, x);
             )
             const size_t e = (size_t)i * LD + c;
-            if (Bv) acc = csub(poly_ld_nt(Bv + e), acc);
-            poly_st_nt(Y + e, acc);
-            if (mode == 1) d1 = cadd(d1, cmulc(poly_ld_nt(U + e), acc));
+            if (Bv) acc = csub(fh_ld_nt(Bv + e), acc);
+            fh_st_nt(Y + e, acc);
+            if (mode == 1) d1 = cadd(d1, cmulc(fh_ld_nt(U + e), acc));
             else if (mode == 2) { d1 = cadd(d1, cmulc(acc, X[e])); d2.x += cabs2(acc); }
             else if (mode == 3) d2.x += cabs2(acc);
             else if (mode == 4) d1 = cadd(d1, cmul(X[e], acc));          // unconjugated p^T (S p), COCG
         }
-        if (mode != 0 && mode != 3) poly_column_sum<LD>(red, t, d1, a.c.partial1 + pbase);
-        if (mode == 2 || mode == 3) poly_column_sum<LD>(red, t, d2, a.c.partial2 + pbase);
+        if (mode != 0 && mode != 3) fh_column_sum<LD, FH_BLOCK>(red, t, d1, a.c.partial1 + pbase);
+        if (mode == 2 || mode == 3) fh_column_sum<LD, FH_BLOCK>(red, t, d2, a.c.partial2 + pbase);
     }
 }
 
@@ -593,7 +577,7 @@ __global__ __launch_bounds__(FH_BLOCK) void k_spmm_fanin_trace(fh_fanin_args a) 
         dsum.x += v * acc.x;
         dsum.y += v * acc.y;
     }
-    poly_column_sum<LD>(red, t, dsum, a.partial + blockIdx.x, gridDim.x);
+    fh_column_sum<LD, FH_BLOCK>(red, t, dsum, a.partial + blockIdx.x, gridDim.x);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -617,7 +601,8 @@ static int poly_check(feasthip_ctx* h, const char* what, int64_t m, int64_t maxm
     if (!h) return FEASTHIP_ERROR_INTERNAL;
     if (h->poisoned) { h->last_error = "handle poisoned by an earlier device failure: destroy it"; return FEASTHIP_ERROR_INTERNAL; }
     const char* why = nullptr;
-    if (h->kind != 3) why = "needs a polynomial handle (feasthip_set_polynomial); a dense or CSR handle takes the entry points without poly_";
+    if (h->kind == 4) why = "an operator handle (feasthip_set_operator) has no polynomial or term form: it takes the pencil entry points under the Krylov solvers FEASTHIP_SOLVER_BICGSTAB, _COCG or _GMRES";
+    else if (h->kind != 3) why = "needs a polynomial handle (feasthip_set_polynomial); a dense or CSR handle takes the entry points without poly_";
     else if (h->poly.terms && form == POLY_POWERS)
         why = "forms powers of lambda, which a term handle (feasthip_set_terms) does not have: use feasthip_nep_solve_dev, feasthip_nep_eval_cols_dev, "
               "feasthip_nep_resinv_apply_dev or feasthip_nep_ritz_eval_dev with tables of the f_k";

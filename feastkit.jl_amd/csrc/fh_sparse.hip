@@ -95,21 +95,12 @@ __device__ __forceinline__ cplx fh_bc16(cplx v, int q) { return cmake(fh_bc16(v.
 __device__ __forceinline__ cplxf fh_bc16(cplxf v, int q) { return cmakef(fh_bc16(v.x, q), fh_bc16(v.y, q)); }
 __device__ __forceinline__ double fh_vzero(double) { return 0.0; }
 __device__ __forceinline__ cplx fh_vzero(cplx) { return cmake(0, 0); }
-__device__ __forceinline__ cplx fh_ld_nt(const cplx* p) {
-    cplx r;
-    r.x = __builtin_nontemporal_load(&p->x);
-    r.y = __builtin_nontemporal_load(&p->y);
-    return r;
-}
+// (the complex128 forms of fh_ld_nt / fh_st_nt: fh_device.hpp)
 __device__ __forceinline__ cplxf fh_ld_nt(const cplxf* p) {
     cplxf r;
     r.x = __builtin_nontemporal_load(&p->x);
     r.y = __builtin_nontemporal_load(&p->y);
     return r;
-}
-__device__ __forceinline__ void fh_st_nt(cplx* p, cplx v) {
-    __builtin_nontemporal_store(v.x, &p->x);
-    __builtin_nontemporal_store(v.y, &p->y);
 }
 __device__ __forceinline__ void fh_st_nt(cplxf* p, cplxf v) {
     __builtin_nontemporal_store(v.x, &p->x);

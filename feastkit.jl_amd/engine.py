@@ -64,9 +64,16 @@ class HipEngine:
             pass
 
     def _chk(self, rc, ok=(0,)):
+        op = getattr(self, "_op", None)
+        cause = None
+        if op is not None:                           # what the operator callback caught during this call, if anything
+            cause, op["error"] = op["error"], None
         if rc not in ok:
             msg = self.lib.feasthip_last_error(self.h)
-            raise FeastHipError(rc, msg.decode() if msg else "")
+            err = FeastHipError(rc, msg.decode() if msg else "")
+            if cause is not None:
+                raise err from cause
+            raise err
         return rc
 
     # -- communicator (the collective lives in the C ABI; the host only ships the unique id) -----
@@ -167,6 +174,7 @@ class HipEngine:
 
     def set_problem(self, A, B=None):
         import scipy.sparse as sp
+        self._op = None                                  # (a set_operator problem ends here)
         if sp.issparse(A):
             fp = (self._fingerprint(A), self._fingerprint(B))
             if fp[0] and fp[1] is not False and fp == getattr(self, "_problem_fp", None) and self.N == A.shape[0]:
@@ -212,6 +220,88 @@ class HipEngine:
                                             nb, _np_ptr(pb), _np_ptr(ib), _np_ptr(vb)))
         self.N, self.b_identity = N, B is None
 
+    def set_operator(self, N, A_mul, B_mul=None, *, real=True, symmetric=False, batched=False):
+        """Matrix-free problem (feasthip_set_operator): the engine holds no matrix and calls ``A_mul(Y, X)`` / ``B_mul(Y, X)``
+        (``B_mul=None``: B = I) wherever it needs a product; each writes its product into ``Y``, like the reference's
+        ``A_mul!(y, x)``.  X and Y are torch views of the library's own panels (no copy), on this engine's device:
+
+        real=True     float64 tensors of shape (N, 2 ld): the real view of the N x ld complex panel (re, im interleaved per
+                      column), so a real linear operator is applied once to the real and the imaginary columns alike;
+        real=False    complex128 tensors of shape (N, ld);
+        batched=True  one call with a leading node dimension, (nodes, N, ...); otherwise one call per node.
+
+        ld is 16, 32 or 64; the columns beyond the block width are padding, which a linear operator may multiply along.
+        ``symmetric``: A = A^T and B = B^T (what solver "cocg" needs).  The functions run under the library's stream
+        (``torch.cuda.stream(ExternalStream(...))``): torch work they queue is ordered with the library's kernels, and they
+        must not synchronise on other streams' results.  A function may return a non-zero int to report failure; an
+        exception is caught, the call that needed the product raises FeastHipError and chains it.  Only Krylov solvers
+        apply (set_solver "bicgstab" | "cocg" | "gmres"); ``operator_stats()`` counts the calls."""
+        torch = self.torch
+        N = int(N)
+        if N < 1:
+            raise ValueError("set_operator: N must be at least 1")
+        if not callable(A_mul) or (B_mul is not None and not callable(B_mul)):
+            raise ValueError("set_operator: A_mul and B_mul must be callable (B_mul=None: B = I)")
+        import time
+        state = {"error": None, "A_calls": 0, "B_calls": 0, "callback_seconds": 0.0, "views": {}}
+        muls = (A_mul, B_mul)
+        dtype_str, width = ("<f8", 2) if real else ("<c16", 1)
+
+        class _Panel:       # a device pointer as the CUDA array interface: torch.as_tensor wraps it without a copy
+            def __init__(self, ptr, nodes, ld, stride):
+                self.__cuda_array_interface__ = {"shape": (nodes, N, ld * width), "typestr": dtype_str, "data": (ptr, False),
+                                                 "version": 2, "strides": (stride * 16, ld * 16, 16 // width)}
+
+        def view(ptr, nodes, ld, stride):
+            key = (ptr, nodes, ld, stride)
+            t = state["views"].get(key)
+            if t is None:
+                if len(state["views"]) > 256:
+                    state["views"].clear()
+                t = torch.as_tensor(_Panel(ptr, nodes, ld, stride), device=self.device)
+                state["views"][key] = t
+            return t
+
+        def callback(_user, which, nodes, ld, _n, dX, xs, dY, ys, stream):
+            t0 = time.perf_counter()
+            try:
+                X, Y = view(dX, nodes, ld, xs), view(dY, nodes, ld, ys)
+                mul = muls[which]
+                state["A_calls" if which == 0 else "B_calls"] += 1
+                with torch.cuda.stream(torch.cuda.ExternalStream(stream or 0, device=self.device)):
+                    if batched:
+                        code = mul(Y, X)
+                        code = int(code) if isinstance(code, int) else 0
+                    else:
+                        code = 0
+                        for e in range(nodes):
+                            ce = mul(Y[e], X[e])
+                            if isinstance(ce, int) and ce != 0:
+                                code = int(ce)
+                                break
+                return code
+            except BaseException as exc:          # never let an exception cross the C frames
+                state["error"] = exc
+                return -1
+            finally:
+                state["callback_seconds"] += time.perf_counter() - t0
+
+        cb = _lib.APPLY_FN(callback)
+        flags = (_lib.OP_B_IDENTITY if B_mul is None else 0) | (0 if real else _lib.OP_COMPLEX) | (_lib.OP_SYMMETRIC if symmetric else 0)
+        self._sync_stream()
+        self._chk(self.lib.feasthip_set_operator(self.h, N, cb, None, flags))
+        self._op_thunk = cb                        # the ctypes thunk lives until the next operator replaces it
+        self._op = state
+        self.N, self.b_identity = N, B_mul is None
+        self._problem_fp = None
+
+    def operator_stats(self):
+        """{A_calls, B_calls, callback_seconds} of the operator set by set_operator since it was set."""
+        op = getattr(self, "_op", None)
+        if op is None:
+            return {"A_calls": 0, "B_calls": 0, "callback_seconds": 0.0}
+        return {k: op[k] for k in ("A_calls", "B_calls", "callback_seconds")}
+
     def set_problem_csc(self, N, A_csc, B_csc=None, index_base=1):
         """Raw ``SparseMatrixCSC`` arrays (colptr, rowval, nzval) as the Julia shim passes them
         (set_matrices!): storage = CSC, 1-based by default; transposed on ingest."""
@@ -229,6 +319,7 @@ class HipEngine:
         self._chk(self.lib.feasthip_set_csr(self.h, int(N), int(cplx), int(index_base), 1, len(va), _np_ptr(pa), _np_ptr(ia), _np_ptr(va),
                                             nb, _np_ptr(pb), _np_ptr(ib), _np_ptr(vb)))
         self.N, self.b_identity = int(N), B_csc is None
+        self._op = None
         self._problem_fp = None
 
     def set_contour(self, Zne, Wne, weight_scale):
@@ -525,6 +616,7 @@ class HipEngine:
         else:
             self._chk(self.lib.feasthip_set_polynomial(self.h, N, len(fs) - 1, int(cplx), ptrs, _np_ptr(lds)))
         self.N, self.b_identity, self.poly_degree = N, False, len(fs) - 1
+        self._op = None
         self._problem_fp = None
 
     def set_polynomial_csr(self, rowptr, col, vals, terms=False):
@@ -548,6 +640,7 @@ class HipEngine:
         else:
             self._chk(self.lib.feasthip_set_polynomial_csr(self.h, N, len(vs) - 1, int(cplx), _np_ptr(rp), _np_ptr(cl), ptrs))
         self.N, self.b_identity, self.poly_degree = N, False, len(vs) - 1
+        self._op = None
         self._problem_fp = None
 
     def _poly_empty(self, m):

@@ -162,10 +162,12 @@ def _empty_result(N, info, loop=0, *, complex_lambda=False, real_q=False, epsout
                        np.zeros(0), int(info), epsout, loop, {} if stats is None else stats)
 
 
-def _setup_sweep(engine, group, A, B, Zne, Wne, weight, real_projection):
-    """Communicator, pencil, contour (weights weight * Wne[e]), projection and this rank's block of nodes -> (world, count)."""
+def _setup_sweep(engine, group, A, B, Zne, Wne, weight, real_projection, preloaded=False):
+    """Communicator, pencil (unless the engine holds the problem already: preloaded), contour (weights weight * Wne[e]),
+    projection and this rank's block of nodes -> (world, count)."""
     rank, world = _world(engine, group)
-    engine.set_problem(A, B)
+    if not preloaded:
+        engine.set_problem(A, B)
     engine.set_contour(Zne, Wne, weight)
     engine.set_real_projection(real_projection)
     first, count = distribute_contour_points(len(Zne), world)[rank]
@@ -948,9 +950,10 @@ def feast_hip_estimate(engine, A, B, Zne, Wne, weight_scale, m, *, general=False
 
 def feast_hip_general(engine, A, B, Emid, r, M0, fpm, *, solver="direct", solver_tol=0.0, solver_maxiter=500,
                       solver_restart=30, group=None, Q0=None, seed=20260515, inner_precision=64, contour=None, eps_floor=0.0,
-                      direct_nodes=None, ortho="mgs"):
+                      direct_nodes=None, ortho="mgs", preloaded=False):
     """Variant C (general, full contour, no factor 2, no orthonormalisation, residual
     without B): src/kernel/feast_kernel.jl:752-950 driven as in src/dense/feast_dense.jl:468-584.
+    ``preloaded``: the engine holds the problem already (engine.set_operator); A and B are then read for their shape only.
     ``ortho`` is checked and set on the engine for the solve like in the other drivers; this variant never orthonormalises
     its subspace, so ``stats["ortho"]`` stays empty."""
     N = A.shape[0]
@@ -958,10 +961,10 @@ def feast_hip_general(engine, A, B, Emid, r, M0, fpm, *, solver="direct", solver
     info = _check_circle_input(N, M0, r)
     if info:
         return _empty_result(N, info, complex_lambda=True)
-    Ac, Bc = _complex_pencil(A, B)
+    Ac, Bc = (A, B) if preloaded else _complex_pencil(A, B)
     # caller-supplied nodes/weights: the reference's "x" drivers (feast_gcsrgvx!/feast_gegvx!, src/sparse/feast_sparse.jl:1008-)
     Zne, Wne = feast_gcontour(Emid, r, fpm) if contour is None else contour
-    world, count = _setup_sweep(engine, group, Ac, Bc, Zne, Wne, 1.0, False)
+    world, count = _setup_sweep(engine, group, Ac, Bc, Zne, Wne, 1.0, False, preloaded)
     if inner_precision == 32 and solver not in DIRECT_SOLVERS:
         raise ValueError("inner_precision=32 (complex64 LU factors + fp64 refinement) needs a direct solver")
     _configure_solver(engine, solver, fpm, solver_tol, solver_maxiter, solver_restart,

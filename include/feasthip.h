@@ -155,6 +155,48 @@ int  feasthip_set_csr(feasthip_handle h, int64_t N, int is_complex, int index_ba
                       int64_t nnzA, const int64_t* ptrA, const int64_t* idxA, const void* valA,
                       int64_t nnzB, const int64_t* ptrB, const int64_t* idxB, const void* valB);
 
+/* Matrix-free problem: an OPERATOR handle.  The library holds no matrix; wherever it needs A X or B X it calls `apply`.
+ * Replaces the A_mul! / B_mul! arguments of feast_matvec (src/interfaces/feast_interfaces.jl:465-481) and the
+ * MatrixFreeOperator of src/interfaces/feast_matfree.jl.
+ *
+ * The callback:  apply(user, which, nodes, ld, N, dX, x_node_stride, dY, y_node_stride, stream)  forms Y_e = A X_e (which 0)
+ * or Y_e = B X_e (which 1) for e = 0 .. nodes-1 and returns 0.
+ *   - dX and dY are DEVICE pointers to `nodes` panels of N x ld complex128 values in the library's panel layout: element
+ *     (i, c) of a panel is at i * ld + c, node e starts at e * stride elements (x_node_stride for dX, y_node_stride for dY;
+ *     both at least N * ld).  ld is 16, 32 or 64.
+ *   - The padding columns (beyond the block width of the call) are part of the panel: the operator is linear, so applying it
+ *     to them is harmless, and the library keeps uninitialised memory out of every panel it hands out (padding is zero or
+ *     the image of zero).  The callback writes all ld columns of dY, or leaves the padding of dY alone -- either is fine.
+ *   - The work is enqueued on `stream` (a hipStream_t: the stream the handle runs on), or finished before the callback
+ *     returns.  dX is read only; dY is scratch of the handle and holds nothing on entry.
+ *   - All `nodes` panels are multiplied whatever the solver's state: which nodes have finished is known on the device only.
+ *   - The callback must not call back into the same handle.
+ *   - A non-zero return ends the entry point that made the call: it returns FEASTHIP_ERROR_INTERNAL with feasthip_last_error =
+ *     "operator callback failed (which=..., code=...)", launches nothing more, and leaves the handle usable (not poisoned).
+ *     The outputs of that entry point are undefined.
+ * flags: FEASTHIP_OP_B_IDENTITY -- B = I, `which` = 1 is never called; FEASTHIP_OP_COMPLEX -- the operator is not real (a real
+ * operator maps the real and the imaginary parts of a panel separately; the flag feeds the COCG admission below and the
+ * callers' choice of the real projection, nothing else); FEASTHIP_OP_SYMMETRIC -- A = A^T and B = B^T (not conjugated),
+ * which is what COCG needs.
+ * An operator handle takes every path a dense handle takes under the Krylov solvers FEASTHIP_SOLVER_BICGSTAB, _COCG (also
+ * asked for as _SHIFTED_COCG or _BLOCK_COCG: the cocg sweep) and _GMRES: feasthip_contour_apply[_dev] and the resident
+ * calls, feasthip_shifted_solve[_dev], feasthip_matmul[_dev], feasthip_project[_dev] / _project_pair[_dev],
+ * feasthip_ritz_residual[_dev], feasthip_rayleigh_ritz_dev, feasthip_orthonormalize[_dev], feasthip_estimate_count.
+ * FEASTHIP_ERROR_FPM, with a message that names the Krylov solvers, answers: FEASTHIP_SOLVER_LU and _BANDED; a COCG kind
+ * without FEASTHIP_OP_SYMMETRIC or with FEASTHIP_OP_COMPLEX; factor_precision 32; feasthip_set_adjoint(1);
+ * feasthip_set_node_solver with a direct node; an attached communicator (feasthip_comm_init_rank on the handle, or
+ * feasthip_set_operator on a handle that has one); every feasthip_poly_* / feasthip_nep_* call.
+ * N: 1 .. INT32_MAX / 64, else FEASTHIP_ERROR_N (also for a null callback).  feasthip_set_dense / feasthip_set_csr restore an
+ * ordinary handle.  A Julia `@cfunction` or any C function pointer serves this ABI.                     */
+typedef int (*feasthip_apply_fn)(void* user, int which /* 0: A, 1: B */, int nodes, int ld, int64_t N,
+                                 const void* dX, int64_t x_node_stride, void* dY, int64_t y_node_stride, void* stream);
+enum {
+    FEASTHIP_OP_B_IDENTITY = 1,
+    FEASTHIP_OP_COMPLEX = 2,
+    FEASTHIP_OP_SYMMETRIC = 4
+};
+int  feasthip_set_operator(feasthip_handle h, int64_t N, feasthip_apply_fn apply, void* user, int flags);
+
 /* Contour nodes/weights as produced by feast_contour / feast_gcontour
  * (src/core/feast_tools.jl:212-371): zne/wne are 2*ne doubles (re,im interleaved).
  * weight_scale = 2.0 for the Hermitian half contour (src/dense/feast_dense.jl:174),
