@@ -17,7 +17,7 @@ from .hip_backend import (feast_hip_hermitian, feast_hip_general, feast_hip_comp
                           feast_hip_poly_estimate, poly_derivative_table, nep_derivative_table, seeded_subspace)   # noqa: F401
 from .engine import HipEngine   # noqa: F401
 from .api import (feast, feast_general, feast_polynomial, feast_pep, feast_nonlinear, feast_nep, feast_matvec,   # noqa: F401
-                  feast_general_matvec)
+                  feast_general_matvec, feast_nonlinear_matvec, feast_polynomial_matvec)
 from . import rci   # noqa: F401
 from . import ingest   # noqa: F401
 from . import banded   # noqa: F401

@@ -55,6 +55,8 @@ SYMBOLS = {
     "feasthip_set_dense": (_i, [_vp, _i64, _i, _vp, _i64, _vp, _i64]),
     "feasthip_set_csr": (_i, [_vp, _i64, _i, _i, _i, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
     "feasthip_set_operator": (_i, [_vp, _i64, APPLY_FN, _vp, _i]),
+    "feasthip_set_term_operator": (_i, [_vp, _i64, _i, APPLY_FN, _vp, _i, C.c_uint, _i64]),
+    "feasthip_set_term_norms": (_i, [_vp, _pd]),
     "feasthip_set_contour": (_i, [_vp, _i, _vp, _vp, _d]),
     "feasthip_set_real_projection": (_i, [_vp, _i]),
     "feasthip_set_node_range": (_i, [_vp, _i, _i]),

@@ -1101,3 +1101,148 @@ def feast_general_matvec(A_mul, B_mul, N, center, radius, *, M0=10, fpm=None, so
     if isinstance(res.stats, dict):
         res.stats["operator"] = _operator_delta(eng, before)
     return res
+
+
+# ---- matrix-free split forms and polynomials: the caller's term operators on the device (engine.set_term_operator) -------------
+_TERM_KRYLOV = ("gmres", "bicgstab", "cocg")
+NORM_SAMPLES = 32                 # +-1 columns of the norm estimate of feast_nonlinear_matvec(norms=None)
+NORM_SEED = 20260515
+
+
+def _check_term_matvec(who, muls, N, M0, Q0, solver, symmetric, norms, ortho):
+    """The argument checks of feast_nonlinear_matvec / feast_polynomial_matvec that need no function value; all of them run
+    before an engine is made or used."""
+    if len(muls) < 2 or len(muls) > POLY_MAX_DEGREE + 1:
+        raise ValueError(f"{who} needs 2 to {POLY_MAX_DEGREE + 1} terms, not {len(muls)}")
+    for k, mul in enumerate(muls):
+        if mul is not None and not callable(mul):
+            raise ValueError(f"{who}: term {k} must be callable, mul(Y, X) writes A_k X into Y, or None for the identity")
+    if int(N) < 1:
+        raise ValueError(f"{who}: N must be at least 1")
+    if isinstance(M0, str):
+        raise ValueError(f"{who}: M0 must be an integer (the count estimate of M0='auto' is not provided for operators)")
+    _check_poly_M0(M0, Q0)
+    check_ortho(ortho)
+    if solver in ("direct", "lu", "sparse_direct", "banded"):
+        raise ValueError(f"{who}: solver '{solver}' needs a matrix to factor; term operators take the Krylov solvers "
+                         "'gmres', 'bicgstab' or (symmetric=True) 'cocg'")
+    if solver not in _TERM_KRYLOV:
+        raise ValueError(f"{who}: unknown solver '{solver}'; term operators take the Krylov solvers 'gmres', 'bicgstab' or "
+                         "(symmetric=True) 'cocg'")
+    if solver == "cocg" and not symmetric:
+        raise ValueError(f"{who}: solver 'cocg' needs symmetric=True (every A_k = A_k^T); use 'bicgstab' or 'gmres' otherwise")
+    if norms is not None:
+        nv = np.asarray(norms, dtype=np.float64)
+        if nv.shape != (len(muls),) or not np.all(np.isfinite(nv)) or not np.all(nv > 0):
+            raise ValueError(f"{who}: norms must be {len(muls)} positive numbers, one per term")
+
+
+def _estimate_term_norms(eng, N, muls):
+    """||A_k||_F^2 ~ (1 / NORM_SAMPLES) sum_c ||A_k v_c||^2 over NORM_SAMPLES seeded +-1 columns (E ||A v||^2 = ||A||_F^2 for
+    independent +-1 entries): one callback per non-identity term, through nep_eval_cols with a unit-row table.  sqrt(N),
+    exact, for an identity term."""
+    m = min(NORM_SAMPLES, N)
+    rng = np.random.default_rng(NORM_SEED)
+    V = rng.integers(0, 2, size=(N, m)).astype(np.float64) * 2.0 - 1.0
+    dV = eng.upload(V.astype(np.complex128))
+    norms = np.empty(len(muls))
+    for k, mul in enumerate(muls):
+        if mul is None:
+            norms[k] = math.sqrt(N)
+            continue
+        F = np.zeros((m, len(muls)), dtype=np.complex128)
+        F[:, k] = 1.0
+        W = eng.download(eng.nep_eval_cols(dV, F, m), m)
+        norms[k] = math.sqrt(float(np.sum(np.abs(W) ** 2)) / m)
+    return norms
+
+
+def _term_matvec(who, key, muls, funcs, N, center, radius, M0, fpm, solver, solver_tol, solver_maxiter, solver_restart, real, symmetric,
+                 batched, norms, ortho, Q0, contour, seed, engine, device, companion, extra):
+    _check_term_matvec(who, muls, N, M0, Q0, solver, symmetric, norms, ortho)
+    N = int(N)
+    if not radius > 0:
+        raise ValueError("radius must be positive")
+    fpm = feastinit() if fpm is None else fpm
+    feastdefault(fpm)
+    M0 = min(int(M0), N)
+    if Q0 is not None and np.shape(Q0) != (N, M0):
+        raise ValueError(f"Q0 must be the N-row start block of shape ({N}, {M0}), not {np.shape(Q0)}")
+    Zne, Wne = feast_gcontour(complex(center), float(radius), fpm) if contour is None else contour
+    F_node = nep_table(funcs, Zne)
+    if not np.isfinite(F_node).all():
+        bad = int(np.flatnonzero(~np.isfinite(F_node).all(axis=0))[0])
+        raise ValueError(f"f_{bad} is not finite at a contour node (a pole or an overflow on the circle)")
+    eng = _engine(engine, device)
+    eng.set_term_operator(N, muls, real=real, symmetric=symmetric, batched=batched)
+    before = eng.operator_stats()
+    estimated = norms is None
+    nv = _estimate_term_norms(eng, N, muls) if estimated else np.asarray(norms, dtype=np.float64)
+    if not np.all(nv > 0):          # (a zero operator: any positive number serves a term that adds nothing)
+        nv = np.where(nv > 0, nv, 1.0)
+    eng.set_term_norms(nv)
+    eng.set_real_projection(False)
+    eng.set_contour(Zne, Wne, 1.0)
+    kw = {} if seed is None else {"seed": int(seed)}
+    res = feast_hip_nonlinear(eng, [_ShapeOnly(N) for _ in muls], funcs, complex(center), float(radius), M0, fpm, Q0=Q0,
+                              contour=(Zne, Wne), ortho=ortho, prepared=True, companion=companion,
+                              krylov=(solver, float(solver_tol), int(solver_maxiter), int(solver_restart)), **extra, **kw)
+    if isinstance(res.stats, dict):
+        now = eng.operator_stats()
+        res.stats["operator"] = {"term_calls": [a - b for a, b in zip(now["term_calls"], before["term_calls"])],
+                                 "callback_seconds": now["callback_seconds"] - before["callback_seconds"],
+                                 "norms": [float(v) for v in nv], "norms_estimated": bool(estimated)}
+        rec = res.stats.get("nonlinear")
+        if key == "polynomial" and rec is not None:
+            del res.stats["nonlinear"]
+            poly = {"degree": len(muls) - 1, "method": "projected", "columns": rec.pop("columns")}
+            for drop in ("terms", "moments", "reduced_nodes", "reduced_seconds"):
+                rec.pop(drop, None)
+            poly.update(rec)
+            res.stats["polynomial"] = poly
+    return res
+
+
+def feast_nonlinear_matvec(terms, N, center, radius, *, M0=10, fpm=None, solver="gmres", solver_tol=1e-6, solver_maxiter=200,
+                           solver_restart=20, real=True, symmetric=False, batched=False, norms=None, ortho="mgs", Q0=None,
+                           contour=None, seed=None, moments=2, reduced_nodes=128, engine=None, device=0):
+    """Matrix-free feast_nonlinear: the eigenvalues of T(lambda) = sum_k f_k(lambda) A_k inside the circle, the A_k given as
+    products on the device.  ``terms``: 2 to 9 pairs (A_mul_k, f_k); ``A_mul_k(Y, X)`` writes A_k X into Y on torch views of the
+    solver's panels (engine.set_term_operator describes them: ``real``, ``batched``), or is None for A_k = I; f_k is a callable
+    or a non-negative int p for lambda^p, as in feast_nonlinear.  The method is feast_nonlinear's with every solve T(z_e) Y = R
+    done by ``solver``: "gmres" (the default, with feast_matvec's defaults GMRES(20), 1e-6, 200 steps), "bicgstab", or
+    -- ``symmetric=True``: every A_k = A_k^T -- "cocg".  ``solver_tol`` = 0 means 10^-fpm[3]; the stop test is relative only,
+    solves start from zero, and a node stopped at the cap is counted (``stats["nonlinear"]["krylov"][loop]["capped_nodes"]``),
+    not an error.  On non-normal dense problems restarted GMRES(20) can stall: raise ``solver_restart``.
+    ``norms``: one positive number per term that stands where ||A_k||_F stands in the backward errors ``res`` / ``epsout``;
+    None: estimated from 32 seeded +-1 columns (one call per non-identity term; sqrt(N), exact, for an identity), recorded in
+    ``stats["operator"]["norms"]`` with ``"norms_estimated": True``.
+    ``stats["operator"]`` = {term_calls, callback_seconds, norms, norms_estimated}; ``stats["nonlinear"]`` as feast_nonlinear
+    fills it, plus ``"plan": "krylov"`` and the per-loop ``"krylov"`` records.  All argument checks run before an engine is made
+    or used.  Not covered: M0 = "auto" and the count estimate, preconditioners, complex64 panels, multi-rank sweeps."""
+    terms = list(terms)
+    if any(not isinstance(t, (tuple, list)) or len(t) != 2 for t in terms):
+        raise ValueError("each term must be a pair (A_mul_k, f_k)")
+    if int(moments) < 1 or int(reduced_nodes) < 8:
+        raise ValueError("moments must be >= 1 and reduced_nodes >= 8")
+    muls = [t[0] for t in terms]
+    _check_term_matvec("feast_nonlinear_matvec", muls, N, M0, Q0, solver, symmetric, norms, ortho)
+    funcs = nep_functions([t[1] for t in terms])
+    return _term_matvec("feast_nonlinear_matvec", "nonlinear", muls, funcs, N, center, radius, M0, fpm, solver, solver_tol,
+                        solver_maxiter, solver_restart, real, symmetric, batched, norms, ortho, Q0, contour, seed, engine, device, False,
+                        dict(moments=int(moments), reduced_nodes=int(reduced_nodes)))
+
+
+def feast_polynomial_matvec(coeff_muls, N, center, radius, *, M0=10, fpm=None, solver="gmres", solver_tol=1e-6, solver_maxiter=200,
+                            solver_restart=20, real=True, symmetric=False, batched=False, norms=None, ortho="mgs", Q0=None,
+                            contour=None, seed=None, engine=None, device=0):
+    """Matrix-free feast_polynomial: the eigenvalues of P(lambda) = sum_k lambda^k A_k inside the circle for coefficients given
+    as products on the device -- feast_polynomial(coeffs_ops::Vector{<:MatrixFreeOperator}, center, radius; solver=:gmres) of
+    src/interfaces/feast_matfree.jl:607-647, by the projected method on N-row subspaces instead of the dN x dN companion
+    operator.  ``coeff_muls[k](Y, X)`` writes A_k X into Y (None: A_k = I); every other argument and the statistics are
+    feast_nonlinear_matvec's, with ``stats["polynomial"]`` as feast_polynomial(method="projected") fills it."""
+    muls = list(coeff_muls)
+    _check_term_matvec("feast_polynomial_matvec", muls, N, M0, Q0, solver, symmetric, norms, ortho)
+    funcs = nep_functions(list(range(len(muls))))
+    return _term_matvec("feast_polynomial_matvec", "polynomial", muls, funcs, N, center, radius, M0, fpm, solver, solver_tol,
+                        solver_maxiter, solver_restart, real, symmetric, batched, norms, ortho, Q0, contour, seed, engine, device, True, {})

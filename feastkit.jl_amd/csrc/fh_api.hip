@@ -204,6 +204,7 @@ void fh_free_problem(feasthip_ctx* h) {
     for (void* p : h->poly.coef) if (p) hipFree(p);
     h->poly = fh_poly();
     h->op = fh_operator();
+    h->top = fh_termop();
     for (void* p : h->lu_factors) if (p) hipFree(p);
     for (int* p : h->lu_pivots) if (p) hipFree(p);
     h->lu_factors.clear(); h->lu_pivots.clear(); h->lu_valid.clear(); h->lu_z.clear();
@@ -454,6 +455,15 @@ static const char* fh_operator_solver_why(const feasthip_ctx* h, int kind, int f
     return nullptr;
 }
 
+// What a term-operator handle (h->kind == 5, feasthip_set_term_operator) cannot take; every message names the solvers it does take
+const char* fh_termop_solver_why(const feasthip_ctx* h, int kind, int factor_precision) {
+    if (kind == FEASTHIP_SOLVER_LU || kind == FEASTHIP_SOLVER_BANDED) return "there is no matrix to factor: " FH_TERMOP_TAKES;
+    if (kind == FEASTHIP_SOLVER_SHIFTED_COCG || kind == FEASTHIP_SOLVER_BLOCK_COCG) return "the shifted and block COCG sweeps are pencil sweeps: " FH_TERMOP_TAKES;
+    if (kind == FEASTHIP_SOLVER_COCG && !h->op.symmetric) return "FEASTHIP_SOLVER_COCG needs FEASTHIP_OP_SYMMETRIC (every A_k = A_k^T): " FH_TERMOP_TAKES;
+    if (factor_precision == 32) return "factor_precision = 32 is not supported (complex128 panels): " FH_TERMOP_TAKES;
+    return nullptr;
+}
+
 extern "C" int feasthip_set_contour(feasthip_handle h, int ne, const double* zne, const double* wne, double weight_scale) {
     if (!h) return FEASTHIP_ERROR_INTERNAL;
     if (ne <= 0 || !zne || !wne) { h->last_error = "feasthip_set_contour: ne <= 0 or null arrays"; return FEASTHIP_ERROR_FPM; }
@@ -492,6 +502,9 @@ extern "C" int feasthip_set_node_solver(feasthip_handle h, int count, const int*
                 h->last_error = "feasthip_set_node_solver: an operator handle (feasthip_set_operator) has no matrix for a direct node; every node takes the Krylov solvers FEASTHIP_SOLVER_BICGSTAB, _COCG or _GMRES";
                 return FEASTHIP_ERROR_FPM;
             }
+    if (h->kind == 5)
+        for (int e = 0; e < count; ++e)
+            if (kinds[e] != 0) { h->last_error = "feasthip_set_node_solver: there is no matrix for a direct node: " FH_TERMOP_TAKES; return FEASTHIP_ERROR_FPM; }
     h->node_kinds.assign(kinds, kinds + count);
     return 0;
 }
@@ -517,6 +530,7 @@ extern "C" int feasthip_set_adjoint(feasthip_handle h, int on) {
     if (!h) return FEASTHIP_ERROR_INTERNAL;
     if (on && h->kind == 3) { h->last_error = "feasthip_set_adjoint: a polynomial handle has no adjoint form (the feasthip_poly_* calls are forward only)"; return FEASTHIP_ERROR_FPM; }
     if (on && h->kind == 4) { h->last_error = std::string("feasthip_set_adjoint: ") + fh_operator_why_adjoint; return FEASTHIP_ERROR_FPM; }
+    if (on && h->kind == 5) { h->last_error = "feasthip_set_adjoint: the callback applies the A_k only, there is no adjoint form: " FH_TERMOP_TAKES; return FEASTHIP_ERROR_FPM; }
     h->adjoint = on ? 1 : 0;
     return 0;
 }
@@ -533,6 +547,10 @@ extern "C" int feasthip_set_node_range(feasthip_handle h, int first, int count) 
         h->last_error = "feasthip_set_node_range: range outside the contour";
         return FEASTHIP_ERROR_FPM;
     }
+    if (h->kind == 5 && (first != 0 || count != (int)h->zne.size())) {
+        h->last_error = "feasthip_set_node_range: the whole contour is swept on one rank: " FH_TERMOP_TAKES;
+        return FEASTHIP_ERROR_FPM;
+    }
     if (h->kind == 3 && (first != 0 || count != (int)h->zne.size())) {
         h->last_error = "feasthip_set_node_range: a polynomial handle sweeps the whole contour (feasthip_poly_contour_apply_dev runs on one rank)";
         return FEASTHIP_ERROR_FPM;
@@ -547,6 +565,7 @@ extern "C" int feasthip_set_node_range(feasthip_handle h, int first, int count) 
 extern "C" int feasthip_set_node_list(feasthip_handle h, int count, const int* indices) {
     if (!h) return FEASTHIP_ERROR_INTERNAL;
     if (count < 0 || (count > 0 && !indices)) { h->last_error = "feasthip_set_node_list: bad arguments"; return FEASTHIP_ERROR_FPM; }
+    if (h->kind == 5) { h->last_error = "feasthip_set_node_list: the whole contour is swept on one rank: " FH_TERMOP_TAKES; return FEASTHIP_ERROR_FPM; }
     if (h->kind == 3) {
         h->last_error = "feasthip_set_node_list: a polynomial handle sweeps the whole contour (feasthip_poly_contour_apply_dev runs on one rank)";
         return FEASTHIP_ERROR_FPM;
@@ -594,6 +613,8 @@ extern "C" int feasthip_set_solver(feasthip_handle h, int kind, double rtol, dou
     }
     if (h->kind == 4)
         if (const char* why = fh_operator_solver_why(h, kind, factor_precision)) { h->last_error = std::string("feasthip_set_solver: ") + why; return FEASTHIP_ERROR_FPM; }
+    if (h->kind == 5)
+        if (const char* why = fh_termop_solver_why(h, kind, factor_precision)) { h->last_error = std::string("feasthip_set_solver: ") + why; return FEASTHIP_ERROR_FPM; }
     // SHIFTED_COCG is COCG with the shifted sweep where fh_contour_apply_panel finds it eligible: every other path sees COCG
     h->shifted = kind == FEASTHIP_SOLVER_SHIFTED_COCG ? 1 : 0;
     // BLOCK_COCG likewise: COCG with the block sweep where the panel is eligible
@@ -623,6 +644,8 @@ struct fh_op_call {
     const cplx* colscale = nullptr;   // row kernel only (fh_spmm_args::colscale): X is a shared panel times per-node column factors
     int skip = 0;          // host hint (operator handle): bit 0 -- coefA is zero everywhere, bit 1 -- coefB is: that callback is not made
 };
+
+static int fh_upload_coefs(feasthip_ctx* h, const char* name, const std::vector<cplx>& host, cplx** dev);      // (below: the pinned ring)
 
 // full-width panels over a real matrix go through the row-per-wave kernel (FH_SPMM_ROW=0: the 4-rows-per-wave gather kernel)
 static bool fh_row_kernel_ok(feasthip_ctx* h, int ld) {
@@ -705,6 +728,38 @@ static int fh_apply_operator(feasthip_ctx* h, int ld, const fh_op_call& c) {
         a.nodes = c.nodes; a.skip = c.skip;
         return fh_apply_user_operator(h, ld, a);
     }
+    if (h->kind == 5) {
+        // term-operator handle: S_e = T(z_e) = sum_k f_k(z_e) A_k on the caller's products (fh_termop.hip); z_e = coefB[node][0] is
+        // the key into the node table, as on the polynomial branch, and comes from the host record of the upload; complex128
+        // panels, the plain product and dot modes 1 .. 4.  -1 also when a callback failed (h->op.failed)
+        if (h->adjoint || c.prec != 64 || c.colscale || c.dot_mode == 6 || !c.coefB || c.coefB != h->top.shift_dev || c.nodes > (int)h->top.shift_z.size()) {
+            h->last_error = "internal: the term operator takes forward products at uploaded node shifts, complex128 panels and dot modes 0 .. 4";
+            return -1;
+        }
+        const int nt = h->poly.degree + 1, ne = (int)h->poly.fnode_z.size();
+        std::vector<cplx> rows((size_t)c.nodes * nt);
+        unsigned terms = 0;
+        for (int q = 0; q < c.nodes; ++q) {
+            const cplx z = h->top.shift_z[q];
+            int e = 0;
+            while (e < ne && !(h->poly.fnode_z[e].x == z.x && h->poly.fnode_z[e].y == z.y)) ++e;
+            if (e == ne || h->poly.fnode.size() != (size_t)ne * nt) { h->last_error = "term operator: a solve at a shift that is no node of the contour the node values were set for (feasthip_nep_set_node_values)"; return -1; }
+            for (int k = 0; k < nt; ++k) {
+                const cplx f = h->poly.fnode[(size_t)e * nt + k];
+                rows[(size_t)q * nt + k] = f;
+                if (f.x != 0.0 || f.y != 0.0) terms |= 1u << k;
+            }
+        }
+        cplx* dF;
+        if (fh_upload_coefs(h, "top_F", rows, &dF)) return -1;
+        fh_termop_call a;
+        a.X = (const cplx*)c.X; a.x_node_stride = c.x_stride; a.Y = (cplx*)c.Y; a.y_node_stride = c.y_stride;
+        a.F = dF; a.cols = 0; a.terms = terms;
+        a.Bvec = (const cplx*)c.Bvec; a.b_node_stride = c.b_stride; a.U = (const cplx*)c.U; a.u_node_stride = c.u_stride;
+        a.dot_mode = c.dot_mode; a.partial1 = c.partial1; a.partial2 = c.partial2; a.node_active = c.node_active;
+        a.nodes = c.nodes;
+        return fh_apply_term_operator(h, ld, a);
+    }
     fh_dense_op_args a;
     a.A = h->dense.A; a.B = h->dense.B; a.N = (int)h->dense.N; a.is_complex = h->dense.is_complex;
     // dense operator: complex128 panels only (fh_krylov forces prec 64 for dense matrices)
@@ -733,7 +788,7 @@ static int fh_op_nblk(feasthip_ctx* h, int ld) {
     if (h->kind == 2) return std::max(std::max(fh_spmm_partials((int)h->csr.N, ld), ld == 64 ? fh_spmm_row_grid((int)h->csr.N) : 0),
                                       h->csr.lcol ? (8 / (ld / 16)) * fh_spmm_lds_slots(h->csr.nblk, ld) : 0);
     if (h->kind == 3 && h->poly.sparse) return fh_poly_op_nblk((int)h->dense.N, ld);
-    if (h->kind == 4) return fh_op_combine_nblk((int)h->dense.N, ld);
+    if (h->kind == 4 || h->kind == 5) return fh_op_combine_nblk((int)h->dense.N, ld);
     return fh_dense_op_nblk((int)h->dense.N);
 }
 // row permutation of the panels (block order of a renumbered sparse matrix), or null
@@ -749,6 +804,11 @@ static int fh_check_problem(feasthip_ctx* h, int64_t m, int wide = 0) {
     if (h->kind == 3) {     // every entry point that comes through here works on a pencil; the polynomial has its own (fh_poly.hip)
         h->last_error = "this entry point does not take a polynomial handle (feasthip_set_polynomial): use feasthip_poly_solve_dev, "
                         "feasthip_poly_contour_apply_dev, feasthip_poly_matmul_dev, feasthip_poly_project_dev or feasthip_poly_ritz_residual_dev";
+        return FEASTHIP_ERROR_FPM;
+    }
+    if (h->kind == 5) {
+        h->last_error = "this entry point works on a pencil: " FH_TERMOP_TAKES ", through feasthip_nep_set_node_values, feasthip_nep_solve_dev, "
+                        "feasthip_nep_eval_cols_dev, feasthip_nep_resinv_apply_dev, feasthip_nep_ritz_eval_dev, feasthip_poly_project_reduced_dev and feasthip_poly_orthonormalize_dev";
         return FEASTHIP_ERROR_FPM;
     }
     if (h->kind == 4) {
@@ -843,8 +903,10 @@ static int fh_upload_shift_coefs(feasthip_ctx* h, const char* nameA, const char*
     std::vector<cplx> ca((size_t)nodes * ld, cmake(-1, 0)), cb((size_t)nodes * ld);
     for (int e = 0; e < nodes; ++e)
         for (int c = 0; c < ld; ++c) cb[(size_t)e * ld + c] = z[e];
-    const int rc = fh_upload_coefs(h, nameA, ca, dca);
-    return rc ? rc : fh_upload_coefs(h, nameB, cb, dcb);
+    int rc = fh_upload_coefs(h, nameA, ca, dca);
+    if (!rc) rc = fh_upload_coefs(h, nameB, cb, dcb);
+    if (!rc && h->kind == 5) { h->top.shift_dev = *dcb; h->top.shift_z.assign(z, z + nodes); }      // the key into the node table
+    return rc;
 }
 
 // the column mask of the running sweep, padded with ones to ld, in "kry_colmask"; *mask = null when no mask is live
@@ -1048,7 +1110,7 @@ int fh_krylov_work::alloc(const std::vector<cplx>& z, const std::vector<cplx>* w
     R = vec(0); Rh = vec(1); P = vec(2); V = vec(3); S = vec(4); T = vec(5);
     if (prec == 32) { D = vec(6); RHS32 = vec(7); }
     // operator handle: the callback sees whole panels, and the vector kernels never write the padding columns of S and T
-    if (h->kind == 4) FH_CHECK(hipMemsetAsync(base, 0, (size_t)nvec * nodes * panel * esz, h->stream));
+    if (h->kind == 4 || h->kind == 5) FH_CHECK(hipMemsetAsync(base, 0, (size_t)nvec * nodes * panel * esz, h->stream));
     const size_t nl = (size_t)nodes * ld;
     if ((rc = fh_buf(h, "kry_scal_c", 4 * nl, &s.rho))) return rc;
     s.alpha = s.rho + nl; s.omega = s.alpha + nl; s.beta = s.omega + nl;
@@ -1506,7 +1568,7 @@ int fh_gmres(feasthip_ctx* h, int ld, int m, int nodes_all, const std::vector<cp
         ga.inv = sd; ga.r0norm = sd + nl; ga.target = sd + 2 * nl; ga.rnorm = sd + 3 * nl;
         ga.active = si; ga.iters = si + nl; ga.status = si + 2 * nl; ga.kdim = si + 3 * nl; ga.node_active = si + 4 * nl;
         FH_CHECK(hipMemsetAsync(sc, 0, hsz * sizeof(cplx), h->stream));
-        if (h->kind == 4) {     // operator handle: the callback sees whole basis panels, padding columns included
+        if (h->kind == 4 || h->kind == 5) {     // operator handle: the callback sees whole basis panels, padding columns included
             FH_CHECK(hipMemsetAsync(V, 0, (size_t)nodes * (mr + 1) * panel * sizeof(cplx), h->stream));
             FH_CHECK(hipMemsetAsync(W, 0, (size_t)nodes * panel * sizeof(cplx), h->stream));
         }
@@ -2629,7 +2691,7 @@ extern "C" int feasthip_poly_orthonormalize_dev(feasthip_handle h, int64_t m64, 
     if (!h) return FEASTHIP_ERROR_INTERNAL;
     if (h->poisoned) { h->last_error = "handle poisoned by an earlier device failure: destroy it"; return FEASTHIP_ERROR_INTERNAL; }
     if (h->kind == 4) { h->last_error = "feasthip_poly_orthonormalize_dev: an operator handle (feasthip_set_operator) has no polynomial form: it takes feasthip_orthonormalize_dev and the other pencil entry points, under the Krylov solvers FEASTHIP_SOLVER_BICGSTAB, _COCG or _GMRES"; return FEASTHIP_ERROR_FPM; }
-    if (h->kind != 3) { h->last_error = "feasthip_poly_orthonormalize_dev: needs a polynomial handle (feasthip_set_polynomial); a dense or CSR handle takes feasthip_orthonormalize_dev"; return FEASTHIP_ERROR_FPM; }
+    if (h->kind != 3 && h->kind != 5) { h->last_error = "feasthip_poly_orthonormalize_dev: needs a polynomial handle (feasthip_set_polynomial); a dense or CSR handle takes feasthip_orthonormalize_dev"; return FEASTHIP_ERROR_FPM; }
     if (m64 <= 0 || m64 > fh_N(h)) { h->last_error = "feasthip_poly_orthonormalize_dev: block width m must satisfy 1 <= m <= N"; return FEASTHIP_ERROR_M0; }
     if (!dQ || !rank) { h->last_error = "feasthip_poly_orthonormalize_dev: null argument"; return FEASTHIP_ERROR_INTERNAL; }
     if (unit_columns) {

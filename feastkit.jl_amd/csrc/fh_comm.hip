@@ -226,6 +226,7 @@ extern "C" int feasthip_comm_init_rank(feasthip_handle h, int nranks, int rank, 
         h->last_error = "comm_init_rank: an operator handle (feasthip_set_operator) does not take a communicator: it sweeps on one rank, under the Krylov solvers FEASTHIP_SOLVER_BICGSTAB, _COCG or _GMRES";
         return FEASTHIP_ERROR_FPM;
     }
+    if (h->kind == 5) { h->last_error = "comm_init_rank: the contour is swept on one rank: " FH_TERMOP_TAKES; return FEASTHIP_ERROR_FPM; }
     fh_comm_destroy(h);
     FH_CHECK(hipSetDevice(h->device));
     if (transport == FEASTHIP_COMM_AUTO) {

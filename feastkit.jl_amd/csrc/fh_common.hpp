@@ -165,6 +165,27 @@ struct fh_operator {
     int failed = 0;
 };
 
+// Term-operator handle (h->kind == 5, feasthip_set_term_operator, fh_termop.hip): the split form of a term handle whose
+// products A_k X are the caller's callback (fh_operator::apply with which = k).  N and is_complex live in fh_dense, the term
+// count (degree + 1), the node table and the norms (fro) in fh_poly with terms = 1, the callback in fh_operator.
+// shift_dev / shift_z: the node shifts fh_upload_shift_coefs sent last and where -- the Krylov drivers hand the operator their
+// coefB array, and the host finds the rows of the node table by these z without reading them back.  col_terms: bit k set when
+// row k of the column table poly_upload_cols sent last has a non-zero entry.
+struct fh_termop {
+    unsigned identity_mask = 0;
+    size_t scratch_bytes = 0;
+    int norms_set = 0;
+    const cplx* shift_dev = nullptr;
+    std::vector<cplx> shift_z;
+    unsigned col_terms = 0;
+};
+
+// what every refusal of a term-operator handle ends with, and the reason feasthip_set_solver and the solving entry points
+// refuse a solver kind on it (null: the kind is taken; fh_api.hip)
+#define FH_TERMOP_TAKES "a term-operator handle (feasthip_set_term_operator) takes the Krylov solvers FEASTHIP_SOLVER_BICGSTAB, _GMRES or (FEASTHIP_OP_SYMMETRIC) _COCG"
+struct feasthip_ctx;
+const char* fh_termop_solver_why(const feasthip_ctx* h, int kind, int factor_precision);
+
 // Per-(node,column) Krylov scalars, struct of arrays; each array is [nodes][ld].
 struct fh_krylov_scalars {
     cplx* rho = nullptr;
@@ -193,9 +214,10 @@ struct feasthip_ctx {
     std::string last_error;
 
     // problem
-    int kind = 0;  // 0 none, 1 dense, 2 sparse, 3 matrix polynomial, dense or (poly.sparse) CSR (the feasthip_poly_* entry points only), 4 operator (Krylov solvers only)
+    int kind = 0;  // 0 none, 1 dense, 2 sparse, 3 matrix polynomial, dense or (poly.sparse) CSR (the feasthip_poly_* entry points only), 4 operator (Krylov solvers only), 5 term operator (the feasthip_nep_* entry points, Krylov solvers only)
     fh_poly poly;
     fh_operator op;
+    fh_termop top;
     fh_csr csr;
     // conjugate transpose of `csr` (A^H, B^H on the transposed union pattern, internal numbering; rowptr / col / aval / bval only):
     // built at the first adjoint product of a CSR problem (fh_api.hip: fh_adjoint_csr_ensure), freed with the problem

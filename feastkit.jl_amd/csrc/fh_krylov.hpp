@@ -67,3 +67,22 @@ struct fh_userop_call {
 };
 int fh_op_combine_nblk(int N, int ld);
 int fh_apply_user_operator(feasthip_ctx* h, int ld, const fh_userop_call& c);
+
+// Y_e = [Bvec -] sum_k F(e, c, k) A_k X_e on a term-operator handle (fh_termop.hip): the caller's callback forms A_k X for the
+// kept terms, k_terms_combine does the rest; complex128 panels, the fields are those of fh_userop_call.  F: the DEVICE table --
+// cols = 0: the node table F[e * nt + k] (nt = the handle's term count), uniform over the columns; cols = 1 (nodes = 1): the
+// column table F[k * ld + c].  terms: bit k set when term k has a non-zero entry in the table; the others are neither produced
+// nor read.  Returns the partial-sum rows per node it wrote (fh_op_combine_nblk), or -1 as fh_apply_user_operator does.
+struct fh_termop_call {
+    const cplx* X; size_t x_node_stride;
+    cplx* Y; size_t y_node_stride;
+    const cplx* F; int cols; unsigned terms;
+    const cplx* Bvec; size_t b_node_stride;
+    const cplx* U; size_t u_node_stride;
+    int dot_mode; cplx* partial1; cplx* partial2;     // modes 0 .. 4 of fh_sparse.hip
+    const int* node_active;
+    int nodes;
+};
+int fh_apply_term_operator(feasthip_ctx* h, int ld, const fh_termop_call& c);
+// W + k N ld = A_k X for every term k of the handle on one N x ld panel (an identity term: a copy of X); 0, or -1 as above
+int fh_term_products(feasthip_ctx* h, int ld, const cplx* X, cplx* W);

@@ -9,6 +9,8 @@
 // method's calls with host tables of the f_k where a polynomial handle forms powers (the feasthip_nep_* entry points; one body
 // per call, shared with its feasthip_poly_* sibling), through the table-form kernels k_form_terms, k_mf_assemble_terms
 // (fh_dense.hip) and k_spmm_terms; the sum over the terms is fh_term_sum (fh_common.hpp), the sibling of fh_horner.
+// A term-OPERATOR handle (feasthip_set_term_operator, h->kind == 5, fh_termop.hip) is a term handle without matrices: the same
+// calls under a Krylov solver, with the caller's callback and k_terms_combine where the others launch a product kernel.
 // The steps they share exist once: Horner over the coefficients is fh_horner (fh_common.hpp), the batched row gather of the
 // three SpMM kernels is POLY_ROW_GATHER, the kernels' coefficient table is fh_poly_coef_ptrs (fh_common.hpp).
 //
@@ -601,15 +603,20 @@ static int poly_check(feasthip_ctx* h, const char* what, int64_t m, int64_t maxm
     if (!h) return FEASTHIP_ERROR_INTERNAL;
     if (h->poisoned) { h->last_error = "handle poisoned by an earlier device failure: destroy it"; return FEASTHIP_ERROR_INTERNAL; }
     const char* why = nullptr;
-    if (h->kind == 4) why = "an operator handle (feasthip_set_operator) has no polynomial or term form: it takes the pencil entry points under the Krylov solvers FEASTHIP_SOLVER_BICGSTAB, _COCG or _GMRES";
-    else if (h->kind != 3) why = "needs a polynomial handle (feasthip_set_polynomial); a dense or CSR handle takes the entry points without poly_";
+    const bool top = h->kind == 5;
+    if (top && (why = fh_termop_solver_why(h, h->shifted ? FEASTHIP_SOLVER_SHIFTED_COCG : h->block ? FEASTHIP_SOLVER_BLOCK_COCG : h->solver, h->factor_precision))) {}
+    else if (h->kind == 4) why = "an operator handle (feasthip_set_operator) has no polynomial or term form: it takes the pencil entry points under the Krylov solvers FEASTHIP_SOLVER_BICGSTAB, _COCG or _GMRES";
+    else if (h->kind != 3 && !top) why = "needs a polynomial handle (feasthip_set_polynomial); a dense or CSR handle takes the entry points without poly_";
+    else if (top && form == POLY_POWERS) why = "forms powers of lambda or linearised columns, which a split form does not have: " FH_TERMOP_TAKES ", through the feasthip_nep_* calls with tables of the f_k";
     else if (h->poly.terms && form == POLY_POWERS)
         why = "forms powers of lambda, which a term handle (feasthip_set_terms) does not have: use feasthip_nep_solve_dev, feasthip_nep_eval_cols_dev, "
               "feasthip_nep_resinv_apply_dev or feasthip_nep_ritz_eval_dev with tables of the f_k";
     else if (!h->poly.terms && form == POLY_TERMS) why = "needs a term handle (feasthip_set_terms / feasthip_set_terms_csr); a polynomial handle takes the feasthip_poly_* calls";
+    else if (top) {}          // (its solver was looked at above)
     else if (h->poly.terms && h->solver != FEASTHIP_SOLVER_LU) why = "the solver of a term handle must be FEASTHIP_SOLVER_LU (Krylov solves on T(z) are not provided)";
     else if (h->solver != FEASTHIP_SOLVER_LU && !(poly_krylov(h) && h->poly.sparse && !h->shifted && !h->block))
         why = h->poly.sparse ? "the solver must be FEASTHIP_SOLVER_LU, _BICGSTAB, _COCG or _GMRES" : "the solver of a dense polynomial handle must be FEASTHIP_SOLVER_LU";
+    if (why) {}
     else if (h->factor_precision != 64) why = "factor_precision = 32 is not supported (complex128 factors only)";
     else if (h->adjoint) why = "the adjoint switch is not supported";
     else if (h->comm) why = "an attached communicator is not supported (one rank)";
@@ -619,8 +626,11 @@ static int poly_check(feasthip_ctx* h, const char* what, int64_t m, int64_t maxm
             if (h->node_ids[e] != e) { why = "a node range or list is not supported (the whole contour on one rank)"; break; }
     if (why) { h->last_error = std::string(what) + ": " + why; return FEASTHIP_ERROR_FPM; }
     if (m <= 0 || m > maxm) { h->last_error = std::string(what) + ": block width out of range"; return FEASTHIP_ERROR_M0; }
+    if (top) h->op.failed = 0;          // a new entry point: the callback is tried again
     return 0;
 }
+// the widest subspace of a projected-method call: N on a polynomial, term or term-operator handle
+static int64_t poly_rows(const feasthip_ctx* h) { return h && (h->kind == 3 || h->kind == 5) ? h->dense.N : 1; }
 // a feasthip_nep_* call that solves with T(z_e): the node table belongs to the handle's contour
 static int nep_check_nodes(feasthip_ctx* h, const char* what) {
     const size_t ne = h->zne.size();
@@ -1289,6 +1299,12 @@ extern "C" int feasthip_poly_ritz_residual_dev(feasthip_handle h, int64_t r64, c
 // lam^k) through the dense product on the column-scaled copy W of X (scaled once more per degree).  X is left as it is.
 static int poly_eval_panel(feasthip_ctx* h, const poly_coefs& pc, int ld, const cplx* dlam, const cplx* X, cplx* W, cplx* R) {
     const int N = (int)h->dense.N, d = h->poly.degree;
+    if (h->kind == 5) {          // the callback flavour: one callback per kept term on the panel, then k_terms_combine on the column table
+        fh_termop_call a;
+        memset(&a, 0, sizeof(a));
+        a.X = X; a.Y = R; a.F = dlam; a.cols = 1; a.terms = h->top.col_terms; a.nodes = 1;
+        return fh_apply_term_operator(h, ld, a) < 0 ? (int)FEASTHIP_ERROR_INTERNAL : 0;
+    }
     if (h->poly.sparse) {
         fh_horner_args a;
         memset(&a, 0, sizeof(a));
@@ -1333,6 +1349,10 @@ static int poly_upload_cols(feasthip_ctx* h, const char* name, const cplx* v, in
         for (int c = 0; c < m; ++c)
             if (nep_row_finite(h, v + (size_t)(c0 + c) * nt))
                 for (int k = 0; k < nt; ++k) p[(size_t)k * ld + c] = v[(size_t)(c0 + c) * nt + k];
+        h->top.col_terms = 0;          // (term operator: the terms with a non-zero entry are the ones its callbacks produce)
+        for (int k = 0; k < nt; ++k)
+            for (int c = 0; c < m; ++c)
+                if (p[(size_t)k * ld + c].x != 0.0 || p[(size_t)k * ld + c].y != 0.0) { h->top.col_terms |= 1u << k; break; }
         return poly_upload(h, name, p, dev);
     }
     for (int c = 0; c < m; ++c) {
@@ -1477,6 +1497,7 @@ extern "C" int feasthip_nep_resinv_apply_dev(feasthip_handle h, int64_t m64, con
 extern "C" int feasthip_poly_estimate_count(feasthip_handle h, int64_t m64, uint64_t seed, const void* G_host, double* samples, void* dV,
                                             int* node_status, feasthip_stats* stats) {
     const char* what = "feasthip_poly_estimate_count";
+    if (h && h->kind == 5 && !h->poisoned) { h->last_error = std::string(what) + ": the count estimate is not provided for operators: " FH_TERMOP_TAKES ", with an integer subspace size"; return FEASTHIP_ERROR_FPM; }
     int rc = poly_check(h, what, m64, h && h->kind == 3 ? std::min<int64_t>(h->dense.N, 65535) : 1, POLY_ANY_FORM);
     if (rc) return rc;
     if (h->poly.terms && (rc = nep_check_nodes(h, what))) return rc;
@@ -1566,7 +1587,7 @@ extern "C" int feasthip_poly_estimate_count(feasthip_handle h, int64_t m64, uint
 // Ahat_k = Q^H A_k Q, k = 0 .. d: d + 1 r x r column-major matrices one behind the other on the host.  Per 64-column panel Q_j
 // the products W_k = A_k Q_j (sparse: one fan-out launch), then one Gram launch per block (i, j) and coefficient.
 extern "C" int feasthip_poly_project_reduced_dev(feasthip_handle h, int64_t r64, const void* dQ, void* Ahat_host) {
-    int rc = poly_check(h, "feasthip_poly_project_reduced_dev", r64, h && h->kind == 3 ? h->dense.N : 1, POLY_ANY_FORM);
+    int rc = poly_check(h, "feasthip_poly_project_reduced_dev", r64, poly_rows(h), POLY_ANY_FORM);
     if (rc) return rc;
     if (!dQ || !Ahat_host) { h->last_error = "feasthip_poly_project_reduced_dev: null argument"; return FEASTHIP_ERROR_INTERNAL; }
     FH_CHECK(hipSetDevice(h->device));
@@ -1577,6 +1598,7 @@ extern "C" int feasthip_poly_project_reduced_dev(feasthip_handle h, int64_t r64,
     for (int k = 0; k <= d; ++k) out[k] = (cplx*)Ahat_host + (size_t)k * r64 * r64;
     return poly_project_blocks(h, {"pq_Qi", "pq_Qj", "pq_W", "pq_G"}, N, (int)r64, d + 1, (const cplx*)dQ, out, [&](int ld, const cplx* Qj, cplx* W) {
         const size_t panel = (size_t)N * ld;
+        if (h->kind == 5) return fh_term_products(h, ld, Qj, W) < 0 ? (int)FEASTHIP_ERROR_INTERNAL : 0;          // the callback flavour
         fh_fan_out outs[FH_FAN_MAX];
         for (int k = 0; k <= d; ++k) outs[k] = fh_fan_out{k, W + (size_t)k * panel, false, false};
         if (h->poly.sparse) poly_fan(h, ld, Qj, outs, d + 1);
@@ -1644,6 +1666,10 @@ extern "C" int feasthip_poly_ritz_eval_dev(feasthip_handle h, int64_t r64, const
 // (F_theta: ncand x nterms on the host; +inf for a non-finite row and for a column of zero length)
 extern "C" int feasthip_nep_ritz_eval_dev(feasthip_handle h, int64_t r64, const void* dQ, int64_t ncand, const void* Y_host,
                                           const void* F_theta, void* dX, double* backward_error) {
-    const int rc = poly_check(h, "feasthip_nep_ritz_eval_dev", r64, h && h->kind == 3 ? h->dense.N : 1, POLY_TERMS);
+    const int rc = poly_check(h, "feasthip_nep_ritz_eval_dev", r64, poly_rows(h), POLY_TERMS);
+    if (!rc && h->kind == 5 && !h->top.norms_set) {
+        h->last_error = "feasthip_nep_ritz_eval_dev: a term-operator handle has no matrices to take ||A_k||_F from: set the norms of the backward error with feasthip_set_term_norms";
+        return FEASTHIP_ERROR_FPM;
+    }
     return rc ? rc : poly_ritz_eval_body(h, "feasthip_nep_ritz_eval_dev", r64, dQ, ncand, Y_host, F_theta, dX, backward_error);
 }

@@ -236,15 +236,30 @@ class HipEngine:
         must not synchronise on other streams' results.  A function may return a non-zero int to report failure; an
         exception is caught, the call that needed the product raises FeastHipError and chains it.  Only Krylov solvers
         apply (set_solver "bicgstab" | "cocg" | "gmres"); ``operator_stats()`` counts the calls."""
-        torch = self.torch
         N = int(N)
         if N < 1:
             raise ValueError("set_operator: N must be at least 1")
         if not callable(A_mul) or (B_mul is not None and not callable(B_mul)):
             raise ValueError("set_operator: A_mul and B_mul must be callable (B_mul=None: B = I)")
+
+        def count(st, which):
+            st["A_calls" if which == 0 else "B_calls"] += 1
+
+        cb, state = self._operator_thunk(N, (A_mul, B_mul), real, batched, {"A_calls": 0, "B_calls": 0}, count)
+        flags = (_lib.OP_B_IDENTITY if B_mul is None else 0) | (0 if real else _lib.OP_COMPLEX) | (_lib.OP_SYMMETRIC if symmetric else 0)
+        self._sync_stream()
+        self._chk(self.lib.feasthip_set_operator(self.h, N, cb, None, flags))
+        self._op_thunk = cb                        # the ctypes thunk lives until the next operator replaces it
+        self._op = state
+        self.N, self.b_identity = N, B_mul is None
+        self._problem_fp = None
+
+    def _operator_thunk(self, N, muls, real, batched, counters, count):
+        """The ctypes callback of set_operator / set_term_operator and its state: ``muls[which](Y, X)`` on torch views of the
+        library's panels under the library's stream; ``count(state, which)`` books the call in ``counters``."""
         import time
-        state = {"error": None, "A_calls": 0, "B_calls": 0, "callback_seconds": 0.0, "views": {}}
-        muls = (A_mul, B_mul)
+        torch = self.torch
+        state = {"error": None, "callback_seconds": 0.0, "views": {}, **counters}
         dtype_str, width = ("<f8", 2) if real else ("<c16", 1)
 
         class _Panel:       # a device pointer as the CUDA array interface: torch.as_tensor wraps it without a copy
@@ -267,7 +282,7 @@ class HipEngine:
             try:
                 X, Y = view(dX, nodes, ld, xs), view(dY, nodes, ld, ys)
                 mul = muls[which]
-                state["A_calls" if which == 0 else "B_calls"] += 1
+                count(state, which)
                 with torch.cuda.stream(torch.cuda.ExternalStream(stream or 0, device=self.device)):
                     if batched:
                         code = mul(Y, X)
@@ -286,20 +301,58 @@ class HipEngine:
             finally:
                 state["callback_seconds"] += time.perf_counter() - t0
 
-        cb = _lib.APPLY_FN(callback)
-        flags = (_lib.OP_B_IDENTITY if B_mul is None else 0) | (0 if real else _lib.OP_COMPLEX) | (_lib.OP_SYMMETRIC if symmetric else 0)
+        return _lib.APPLY_FN(callback), state
+
+    def set_term_operator(self, N, muls, *, real=True, symmetric=False, batched=False, norms=None, scratch_bytes=0):
+        """Matrix-free split form (feasthip_set_term_operator): T(z) X = sum_k f_k(z) A_k X with ``muls[k](Y, X)`` writing A_k X
+        into Y, or ``muls[k] = None`` for A_k = I (no call: the kernel reads X).  2 to 9 terms.  The views, ``real``, ``batched``,
+        the stream rule and the failure rule are set_operator's; ``symmetric``: every A_k = A_k^T (what "cocg" needs, complex
+        operators included).  The engine is then a term handle for the nep_* methods, poly_project_reduced and
+        poly_orthonormalize, under set_solver("bicgstab" | "gmres" | "cocg") only.  ``norms``: set_term_norms.
+        ``scratch_bytes``: bound of the product scratch (0: the library's default); when the nodes of a call do not fit, the
+        callbacks see node chunks.  ``operator_stats()`` = {"term_calls": [per term], "callback_seconds"}."""
+        N = int(N)
+        muls = list(muls)
+        if N < 1:
+            raise ValueError("set_term_operator: N must be at least 1")
+        if len(muls) < 2 or len(muls) > 9:
+            raise ValueError(f"set_term_operator needs 2 to 9 terms, not {len(muls)}")
+        if any(m is not None and not callable(m) for m in muls):
+            raise ValueError("set_term_operator: each term must be callable, mul(Y, X) writes A_k X into Y, or None for the identity")
+        if int(scratch_bytes) < 0:
+            raise ValueError("set_term_operator: scratch_bytes must not be negative")
+
+        def count(st, which):
+            st["term_calls"][which] += 1
+
+        cb, state = self._operator_thunk(N, muls, real, batched, {"term_calls": [0] * len(muls)}, count)
+        flags = (0 if real else _lib.OP_COMPLEX) | (_lib.OP_SYMMETRIC if symmetric else 0)
+        mask = sum(1 << k for k, m in enumerate(muls) if m is None)
         self._sync_stream()
-        self._chk(self.lib.feasthip_set_operator(self.h, N, cb, None, flags))
-        self._op_thunk = cb                        # the ctypes thunk lives until the next operator replaces it
+        self._chk(self.lib.feasthip_set_term_operator(self.h, N, len(muls), cb, None, flags, mask, int(scratch_bytes)))
+        self._op_thunk = cb
         self._op = state
-        self.N, self.b_identity = N, B_mul is None
+        self.N, self.b_identity, self.poly_degree = N, False, len(muls) - 1
         self._problem_fp = None
+        if norms is not None:
+            self.set_term_norms(norms)
+
+    def set_term_norms(self, norms):
+        """nterms positive numbers that stand where ||A_k||_F stands in the backward errors of nep_ritz_eval on a term-operator
+        handle (feasthip_set_term_norms)."""
+        nv = np.ascontiguousarray(norms, dtype=np.float64)
+        if nv.shape != (getattr(self, "poly_degree", 0) + 1,):
+            raise ValueError("set_term_norms needs one norm per term")
+        self._chk(self.lib.feasthip_set_term_norms(self.h, nv.ctypes.data_as(C.POINTER(C.c_double))))
 
     def operator_stats(self):
-        """{A_calls, B_calls, callback_seconds} of the operator set by set_operator since it was set."""
+        """{A_calls, B_calls, callback_seconds} of the operator set by set_operator since it was set; for set_term_operator
+        {"term_calls": [per term], "callback_seconds"}."""
         op = getattr(self, "_op", None)
         if op is None:
             return {"A_calls": 0, "B_calls": 0, "callback_seconds": 0.0}
+        if "term_calls" in op:
+            return {"term_calls": list(op["term_calls"]), "callback_seconds": op["callback_seconds"]}
         return {k: op[k] for k in ("A_calls", "B_calls", "callback_seconds")}
 
     def set_problem_csc(self, N, A_csc, B_csc=None, index_base=1):
@@ -807,12 +860,13 @@ class HipEngine:
         self._chk(self.lib.feasthip_nep_set_node_values(self.h, Fc.shape[0], _np_ptr(Fc)))
 
     def nep_solve(self, node, dR, m):
-        """Y = T(z_node)^-1 R on an N x m device block -> (dY, code 0 | 8); feasthip_nep_solve_dev."""
+        """Y = T(z_node)^-1 R on an N x m device block -> (dY, code 0 | 8); feasthip_nep_solve_dev.  On a term-operator handle
+        (a Krylov solve) the code is 0 or 5 (a column stopped at maxit) and last_stats holds the iteration counts."""
         self._sync_stream()
         dY = self.empty(dR.shape[0])
         stats = FeastHipStats()
         rc = self.lib.feasthip_nep_solve_dev(self.h, int(node), int(m), C.c_void_p(dR.data_ptr()), C.c_void_p(dY.data_ptr()), C.byref(stats))
-        self._chk(rc, ok=(0, 8))
+        self._chk(rc, ok=(0, 5, 8))
         self.last_stats = stats.asdict()
         return dY, rc
 

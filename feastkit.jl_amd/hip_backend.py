@@ -1430,7 +1430,7 @@ def nep_newton_polish(Ahat, funcs, theta0, v0, radius):
 
 
 def feast_hip_nonlinear(engine, mats, funcs, Emid, r, M0, fpm, *, Q0=None, seed=20260515, contour=None, eps_floor=0.0,
-                        union_csr=None, ortho="mgs", moments=2, reduced_nodes=128, prepared=False):
+                        union_csr=None, ortho="mgs", moments=2, reduced_nodes=128, prepared=False, krylov=None, companion=False):
     """T(lambda) x = 0, T(lambda) = sum_k f_k(lambda) mats[k], inside a circle: feast_hip_polynomial_projected's loop
     (_projected_loop) on a term handle (engine.set_terms), with two changes.  The scalars are host tables of the f_k -- at the
     contour nodes once, at the shifts and the candidates once per loop -- so the device never sees the functions.  The reduced
@@ -1439,7 +1439,12 @@ def feast_hip_nonlinear(engine, mats, funcs, Emid, r, M0, fpm, *, Q0=None, seed=
     POLY_SET_ASIDE).  Loop 0 is the plain sweep, which factors T(z_e) once per node; later loops are residual-inverse sweeps on
     the cached factors.  Stop test, loop limit and ``union_csr``: as feast_hip_polynomial_projected.  A circle in which the
     reduced problem finds nothing returns Feast_ERROR_NO_CONVERGENCE with M = 0.  What an f_k raises is the caller's to see.
-    ``prepared``: as in _poly_setup (the node values are set again, which changes nothing when they are the same)."""
+    ``prepared``: as in _poly_setup (the node values are set again, which changes nothing when they are the same).
+    ``krylov`` = (solver, tol, maxiter, restart): the solves of the contour step run on that Krylov solver and are inexact, as in
+    feast_hip_polynomial_projected (``stats["nonlinear"]["krylov"]`` per loop, a capped node is no failure, nothing is factored).
+    That is the path of a term-operator handle (engine.set_term_operator) on a ``prepared`` engine, where ``mats`` are shape-only
+    stand-ins.  ``companion``: the f_k are the powers lambda^k, and the reduced problem is the polynomial method's companion
+    pencil (_poly_companion) instead of Beyn's method and the polish."""
     N = mats[0].shape[0]
     feastdefault(fpm)
     info = _check_circle_input(N, M0, r)
@@ -1451,7 +1456,7 @@ def feast_hip_nonlinear(engine, mats, funcs, Emid, r, M0, fpm, *, Q0=None, seed=
     if not np.isfinite(F_node).all():
         k = int(np.flatnonzero(~np.isfinite(F_node).all(axis=0))[0])
         raise ValueError(f"f_{k} is not finite at a contour node")
-    plan = _poly_setup(engine, mats, Emid, r, fpm, (Zne, Wne), union_csr, terms=True, prepared=prepared)
+    plan = _poly_setup(engine, mats, Emid, r, fpm, (Zne, Wne), union_csr, krylov, terms=True, prepared=prepared)
     engine.nep_set_node_values(F_node)
     nep = {"terms": len(mats), "columns": M0, "moments": int(moments), "reduced_nodes": int(reduced_nodes), "reduced_seconds": 0.0}
     stats = {"krylov_iterations": 0, "factorizations": 0, "solve_seconds": 0.0, "nonlinear": nep}
@@ -1463,6 +1468,13 @@ def feast_hip_nonlinear(engine, mats, funcs, Emid, r, M0, fpm, *, Q0=None, seed=
 
     def reduced(Ahat, rank_q):
         t0 = time.perf_counter()
+        if companion:
+            try:
+                theta, V = sla.eig(*_poly_companion(Ahat))
+            except Exception as err:
+                raise ReducedSolveError(str(err)) from err
+            nep["reduced_seconds"] += time.perf_counter() - t0
+            return theta, V[:rank_q, :]
         theta, Y = nep_beyn(Ahat, funcs, center, r, moments, reduced_nodes)
         theta, Y = theta.copy(), np.array(Y, dtype=np.complex128)
         for i in range(len(theta)):
@@ -1473,7 +1485,8 @@ def feast_hip_nonlinear(engine, mats, funcs, Emid, r, M0, fpm, *, Q0=None, seed=
     def evaluate(dQ, rank_q, Y, theta):
         return engine.nep_ritz_eval(dQ, rank_q, Y, nep_table(funcs, theta))
 
-    return _projected_loop(engine, N, M0, Emid, r, fpm, Q0, seed, eps_floor, ortho, stats, nep, sweep, reduced, evaluate)
+    return _projected_loop(engine, N, M0, Emid, r, fpm, Q0, seed, eps_floor, ortho, stats, nep, sweep, reduced, evaluate,
+                           krylov=krylov is not None)
 
 
 def feast_hip_poly_estimate(engine, mats, funcs, Emid, r, m, fpm, *, seed=ESTIMATE_SEED, contour=None, union_csr=None, krylov=None):

@@ -197,6 +197,30 @@ enum {
 };
 int  feasthip_set_operator(feasthip_handle h, int64_t N, feasthip_apply_fn apply, void* user, int flags);
 
+/* Term-operator handle: a split form whose matrices are the caller's products,
+ *     T(z) X = sum_k f_k(z) (A_k X),   k = 0 .. nterms-1,   2 <= nterms <= FEASTHIP_POLY_MAX_DEGREE + 1.
+ * `apply` is the callback of feasthip_set_operator with which = k, the term index: all nodes of a call in one invocation, the
+ * same panel layout and stream rules.  The scalars f_k(.) stay host tables as on a term handle (feasthip_set_terms); a
+ * polynomial is the case f_k(z) = z^k.
+ * flags: FEASTHIP_OP_COMPLEX and FEASTHIP_OP_SYMMETRIC (every A_k = A_k^T).  Bit k of identity_mask: A_k = I -- no callback and
+ * no scratch for that term, the combine kernel reads X.  scratch_bytes bounds the product scratch (nt' * nodes * 16 N ld bytes,
+ * nt' the non-identity terms a call keeps; 0: the library's default): when the nodes of a call do not fit, the operator is
+ * applied in node chunks -- the callback sees the chunk's node count, one kernel launch per chunk.
+ * The handle is a TERM handle for the feasthip_nep_* family under the Krylov solvers FEASTHIP_SOLVER_BICGSTAB, _GMRES and (with
+ * FEASTHIP_OP_SYMMETRIC) _COCG: feasthip_nep_set_node_values, feasthip_nep_solve_dev, feasthip_nep_eval_cols_dev,
+ * feasthip_nep_resinv_apply_dev, feasthip_poly_project_reduced_dev, feasthip_nep_ritz_eval_dev and
+ * feasthip_poly_orthonormalize_dev.  A solve's shift must be a node of the contour the node values were set for.  A term
+ * whose table entries are zero for every node (or column) of a call is neither produced (no callback) nor read.
+ * FEASTHIP_ERROR_FPM, with a message that names the three Krylov solvers, answers: the LU, banded and sparse-direct solvers;
+ * factor_precision 32; shifted and block COCG; _COCG without FEASTHIP_OP_SYMMETRIC; the adjoint switch; per-node solvers; a
+ * communicator; node ranges and lists; every other feasthip_poly_* call (they form powers of lambda or linearised columns);
+ * feasthip_poly_estimate_count; the pencil entry points.  A failed callback behaves as on an operator handle.
+ * feasthip_set_term_norms: nterms positive doubles that stand where ||A_k||_F stands in the backward error of
+ * feasthip_nep_ritz_eval_dev, which returns FEASTHIP_ERROR_FPM until they are set.                                        */
+int  feasthip_set_term_operator(feasthip_handle h, int64_t N, int nterms, feasthip_apply_fn apply, void* user, int flags,
+                                unsigned identity_mask, int64_t scratch_bytes);
+int  feasthip_set_term_norms(feasthip_handle h, const double* norms /* nterms */);
+
 /* Contour nodes/weights as produced by feast_contour / feast_gcontour
  * (src/core/feast_tools.jl:212-371): zne/wne are 2*ne doubles (re,im interleaved).
  * weight_scale = 2.0 for the Hermitian half contour (src/dense/feast_dense.jl:174),
