@@ -14,6 +14,7 @@ import gmres_reference as gr
 import krylov_cases as kc
 import krylov_reference as kr
 from krylov_cases import FAR_SHIFT, LEFT_OUT_MAX, MARGIN_MIN, POWER, contour8, near_shift, project, tile_columns  # noqa: F401
+from ragged_cases import ragged_pair
 from test_gpu_primitives import rand_block, sparse_pair
 
 RTOL_TRUNC = 1e-14
@@ -51,6 +52,8 @@ TRUNC = {
     "cfg3-N1080-m1-r30": (_cfg3_mid, 1, 30, (1, 15, 29, 30, 31), (0.0, 0.5)),      # (far from the spectrum it converges at 33)
     "cfg3-N1080-m24-r0": (_cfg3_mid, 24, 0, (1, 2, 3, 4), (0.0, 0.5)),
     "csr-B-N333-m17-r16": (lambda: sparse_pair(333, 7), 17, 16, (8, 15, 16, 17, 32, 33), (20.0, 30.0)),
+    # ragged rows with an unsymmetric pattern (ragged_cases.py): k_spmm at ld 32 under dot mode 1 and the Arnoldi dots
+    "ragged-nonsym-N323-m17-r8": (lambda: ragged_pair(323, 21, unsymmetric=True), 17, 8, (1, 5, 8, 9, 16, 17, 30), (0.0, 1.0)),
 }
 TRUNC_HOST = ("csr-I-N45-m7-r7", "dense-N203-m16-r30", "cfg3-N1080-m1-r30", "cfg3-N1080-m24-r0")
 

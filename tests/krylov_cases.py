@@ -9,6 +9,7 @@ import scipy.linalg as sla
 import feast_oracle as fo
 import feastkit_jl_amd as fk
 import krylov_reference as kr
+from ragged_cases import ragged_pair
 from test_gpu_primitives import rand_block, sparse_pair
 
 TRUNC_KS = (1, 2, 3, 5, 15, 16, 17, 31, 33, 48)
@@ -62,6 +63,7 @@ def _dense(builder):
 # GPU test assert the condition for every k listed here.
 KS_SHORT = (1, 2, 3, 5, 15, 16, 17)
 KS_NEAR = (1, 2, 3)
+RAGGED_SEED = 21
 # name -> (device solver, restatement, builder of (A, B), m, ks far from the spectrum, ks next to it, interval whose
 #          8-node contour gives the near shift)
 TRUNC = {
@@ -74,7 +76,18 @@ TRUNC = {
     "cocg-csr-N1080-m1": ("cocg", "cocg_fused", _cfg3_mid, 1, TRUNC_KS, TRUNC_KS, (0.0, 0.5)),
     "cocg-dense-N336-m7": ("cocg", "cocg5", _dense(_cfg3_small), 7, TRUNC_KS, TRUNC_KS, (0.0, 0.5)),
     "cocg-csr-N60000-m64": ("cocg", "cocg_fused", _cfg3_big, 64, (1, 2, 5), (1, 2, 5), (0.0, 0.5)),
+    # ragged rows (ragged_cases.py).  m = 64 over real values: k_spmm_row and k_fused_vec; m = 17 and m = 7: k_spmm at ld 32
+    # and 16, with B = I over rows without entries.  Next to the spectrum the ks are the longest prefix of the far ones that
+    # keeps 32 D <= 1e-7: all of them but on N = 47, where the drift passes it at k = 31 (7e-6).  N = 47 also ends its far ks
+    # at 33: COCG exhausts the Krylov space of 47 unknowns at step 47 in long double and stops there, complex128 does not
+    # (fp64_steps_agree fails at k = 48): which of the two the device follows is a matter of rounding.
+    "cocg-ragged-B-N323-m64": ("cocg", "cocg_fused", lambda: ragged_pair(323, RAGGED_SEED), 64, TRUNC_KS, TRUNC_KS, (0.0, 1.0)),
+    "cocg-ragged-I-N331-m17": ("cocg", "cocg_fused", lambda: ragged_pair(331, RAGGED_SEED, b_identity=True), 17, TRUNC_KS, TRUNC_KS, (0.0, 12.0)),
+    "cocg-ragged-I-N47-m7": ("cocg", "cocg_fused", lambda: ragged_pair(47, RAGGED_SEED, b_identity=True), 7, TRUNC_KS[:-1], KS_SHORT, (0.0, 12.0)),
+    "bicgstab-ragged-B-N323-m17": ("bicgstab", "bicgstab", lambda: ragged_pair(323, RAGGED_SEED), 17, KS_SHORT, KS_NEAR, (0.0, 1.0)),
+    "bicgstab-ragged-hermitian-N331-m48": ("bicgstab", "bicgstab", lambda: ragged_pair(331, RAGGED_SEED, cplx=True), 48, KS_SHORT, KS_NEAR, (0.0, 1.0)),
 }
+RAGGED = tuple(n for n in TRUNC if "ragged" in n)
 TRUNC_HOST = ("bicgstab-csr-I-N45-m7", "bicgstab-dense-N203-m16", "cocg-csr-N1080-m1", "cocg-dense-N336-m7")
 FAR_SHIFT = -3.0 + 2.0j
 
@@ -105,6 +118,7 @@ def trunc_case(name, near):
     PD = kr.Pencil(A, B, np.complex128)
     c.ref = [kr.solve_column(PL, c.z, c.X[:, j], method, 1e-14, 0.0, kmax, keep_history=True) for j in c.columns]
     c.drift = {k: 0.0 for k in ks}
+    c.fp64_steps_agree = {k: True for k in ks}        # the complex128 restatement takes the long-double one's steps up to k
     for chunks, seed in kr.DRIFT_ORDERS:
         dots = kr.Dots(N, chunks, seed)
         for j, ref in zip(c.columns, c.ref):
@@ -112,6 +126,7 @@ def trunc_case(name, near):
             for k in ks:
                 xr, sr = kr.truncated(ref, k)[:2]
                 xd, sd = kr.truncated(d, k)[:2]
+                c.fp64_steps_agree[k] &= sr == sd
                 if sr == sd:
                     c.drift[k] = max(c.drift[k], kr.rel_dist(xd, xr))
     return c
@@ -181,21 +196,33 @@ SWEEP_M = (4, 24, 40, 64)
 BICGSTAB_SWEEPS = (("cfg3", True, 50), ("cfg3", False, 50), ("hermitian", False, 5))
 
 
+SWEEP_KINDS = ("cfg3", "ragged", "ragged-I")
+RAGGED_SWEEP_M = (24, 64)
+_SWEEP_INTERVAL = {"cfg3": (0.0, 0.5), "hermitian": (0.0, 8.0), "ragged": (0.0, 1.0), "ragged-I": (0.0, 12.0)}
+_SWEEP_RITZ = {"cfg3": (0.05, 0.9), "hermitian": (-1.0, 10.0), "ragged": (-0.2, 1.5), "ragged-I": (-2.0, 15.0)}
+
+
 @functools.lru_cache(maxsize=None)
 def sweep_problem(kind="cfg3"):
     """(A, B, Z, W, weight scale).  cfg3: the 12 x 10 x 9 pencil and the 8-node half contour over (0, 0.5);
-    hermitian: a complex Hermitian CSR pencil, N = 500, half contour over (0, 8) at the lower end of its spectrum."""
+    hermitian: a complex Hermitian CSR pencil, N = 500, half contour over (0, 8) at the lower end of its spectrum;
+    ragged: ragged_pair(323) with B, half contour over (0, 1); ragged-I: ragged_pair(331, b_identity=True), over (0, 12):
+    both at the lower end, where the rows without a diagonal put their eigenvalues."""
     if kind == "cfg3":
         A, B, _ = fo.cfg3_problem(12, 10, 9)
-        Z, W = contour8(0.0, 0.5)
-    else:
+    elif kind == "hermitian":
         A, B = sparse_pair(500, 9, cplx=True)
-        Z, W = contour8(0.0, 8.0)
+    elif kind == "ragged":
+        A, B = ragged_pair(323, RAGGED_SEED)
+    else:
+        assert kind == "ragged-I", kind
+        A, B = ragged_pair(331, RAGGED_SEED, b_identity=True)
+    Z, W = contour8(*_SWEEP_INTERVAL[kind])
     return A, B, Z, W, 2.0
 
 
 def sweep_ritz(m, kind="cfg3"):
-    lo, hi = (0.05, 0.9) if kind == "cfg3" else (-1.0, 10.0)       # straddles the interval: some 1/(z_e - lambda_c) are large
+    lo, hi = _SWEEP_RITZ[kind]                  # straddles the interval: some 1/(z_e - lambda_c) are large
     return np.linspace(lo, hi, m)
 
 

@@ -32,7 +32,8 @@ METHODS = ("bicgstab", "cocg5", "cocg_fused")
 
 class Pencil:
     """S(z) x = z B x - A x in the arithmetic of ``dtype``.  A, B: dense arrays or scipy sparse matrices (B None: identity).
-    Sparse products are row sums over the CSR arrays (every type numpy has, long double included)."""
+    Sparse products are row sums over the CSR arrays (every type numpy has, long double included); a row without entries
+    gives zero."""
 
     def __init__(self, A, B=None, dtype=np.clongdouble):
         self.dtype = np.dtype(dtype)
@@ -49,8 +50,10 @@ class Pencil:
             data = M.data.astype(self.dtype if cplx else self.real)
             if self.dtype == np.complex128:
                 return ("scipy", M.astype(np.complex128 if cplx else np.float64))
-            assert (np.diff(M.indptr) > 0).all(), "a row without entries: the row-sum product needs one per row"
-            return ("csr", data, M.indices.copy(), M.indptr[:-1].copy())
+            filled = np.diff(M.indptr) > 0
+            # a row without entries gives zero: reduceat sums from each listed start to the next, so it gets the starts of the
+            # rows that have entries and the others keep the zero (rows = None: every row has one, the sums are the result)
+            return ("csr", data, M.indices.copy(), M.indptr[:-1][filled].copy(), None if filled.all() else np.flatnonzero(filled))
         M = np.asarray(M)
         return ("dense", M.astype(self.dtype if np.iscomplexobj(M) else self.real))
 
@@ -59,8 +62,13 @@ class Pencil:
             return M[1] @ x
         if M[0] == "dense":
             return M[1] @ x
-        _, data, idx, ptr = M
-        return np.add.reduceat(data * x[idx], ptr)
+        _, data, idx, ptr, rows = M
+        if rows is None:
+            return np.add.reduceat(data * x[idx], ptr)
+        y = np.zeros(self.N, dtype=np.result_type(data, x))
+        if len(ptr):
+            y[rows] = np.add.reduceat(data * x[idx], ptr)
+        return y
 
     def mulA(self, x):
         return self._mul(self.A, x)

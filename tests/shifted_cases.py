@@ -10,6 +10,7 @@ import feastkit_jl_amd as fk
 import krylov_reference as kr
 import shifted_krylov_reference as skr
 import scipy.sparse as sp
+from ragged_cases import ragged_pair
 
 MARGIN_MIN = 1e-6
 POWER = 1e-7
@@ -29,7 +30,11 @@ PROBLEMS = {
     "lap-N336": (lambda: fo.cfg3_problem(8, 7, 6)[0], (0.4, 1.5)),
     "lap-N1080": (lambda: fo.cfg3_problem(12, 10, 9)[0], (0.2, 0.9)),
     "rand-N45": (lambda: _rand_csr(45, 8), (10.0, 20.0)),
+    # ragged rows, some without entries (ragged_cases.py); the interval at the low end of the spectrum, where the rows
+    # without a diagonal put their eigenvalues
+    "ragged-I-N331": (lambda: ragged_pair(331, 21, b_identity=True)[0], (0.0, 12.0)),
 }
+RAGGED = "ragged-I-N331"
 HOST_M = 3          # columns the host test compares
 LD_M = {16: 9, 32: 24, 64: 40}
 

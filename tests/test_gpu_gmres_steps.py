@@ -20,6 +20,8 @@ largest D, the largest distance of the device from the long-double reference and
     sweeps, batches 8 / 3 / 1   48   D <= 1.4e-14   device <= 7.5e-15   0.03
     mask                         1   D <= 5.4e-15   device <= 4.8e-15   0.03
 """
+import os
+
 import numpy as np
 import pytest
 
@@ -27,10 +29,14 @@ import gmres_cases as gc
 import krylov_reference as kr
 
 pytestmark = pytest.mark.gpu
+REPORT = os.environ.get("FH_KRYLOV_STEPS_REPORT")        # measurement runs: the file of test_gpu_krylov_steps.py
 
 
 def close_enough(group, dist, D):
     print("gmres-steps %s D=%.3e device=%.3e tol=%.3e" % (group, D, dist, kr.tolerance(D)))
+    if REPORT:
+        with open(REPORT, "a") as f:
+            f.write("gmres/%s %.3e %.3e\n" % (group, D, dist))
     assert 32.0 * D <= gc.POWER, (group, D)              # a condition on the reference alone
     assert dist <= kr.tolerance(D), (group, dist, D)
 

@@ -22,6 +22,15 @@ of the device from the long-double reference, and the largest share of its toler
     bicgstab sweeps                    D <= 2.0e-11   device <= 2.0e-12   0.03
     mask / node list / column block    D <= 5.4e-15   device <= 7.2e-15   0.05
 
+On the ragged pencils of ragged_cases.py (70 more cases: rows of 0 to 65 entries and one of N - 1, missing diagonals,
+N = 47 / 323 / 331; the whole report is profiles/ragged_krylov_steps.txt):
+
+    truncated cocg, far shift          D <= 3.9e-12   device <= 1.8e-12   0.04
+    truncated cocg, node next to Emax  D <= 7.0e-10   device <= 7.7e-10   0.07
+    truncated bicgstab, far / near     D <= 1.1e-12   device <= 1.0e-12   0.03
+    inexact cocg sweeps (96)           D <= 3.3e-10   device <= 5.0e-11   0.03
+    start paths (12)                   D <= 3.3e-10   device <= 9.2e-11   0.03
+
 The device never needed more than a tenth of 32 D.  BiCGStab's own drift limits how far its cases can be cut (see
 krylov_cases.py: k <= 17 far from the spectrum for the two larger pencils, k <= 3 next to it, 5 steps for the Hermitian
 sweep): beyond that 32 D passes 1e-7 and the comparison would no longer tell a defect from rounding.
@@ -157,16 +166,21 @@ def check_sweep(group, c, out, status, real, counts=None, node_its=None, stats=N
             assert stats["krylov_iterations"] == rowmax.sum(), (group, stats, rowmax)
 
 
+# the full grid of widths on cfg 3; the ragged pencils (krylov_cases.sweep_problem) at one k_spmm width and the full one
+SWEEP_GRID = [("cfg3", m) for m in kc.SWEEP_M] + [(kind, m) for kind in kc.SWEEP_KINDS[1:] for m in kc.RAGGED_SWEEP_M]
+
+
 @pytest.mark.parametrize("real", [True, False], ids=["real", "complex"])
 @pytest.mark.parametrize("warm", [True, False], ids=["ritz", "zero"])
-@pytest.mark.parametrize("m", kc.SWEEP_M)
+@pytest.mark.parametrize("kind,m", SWEEP_GRID, ids=[str(m) if kind == "cfg3" else "%s-%d" % (kind, m) for kind, m in SWEEP_GRID])
 @pytest.mark.parametrize("rtol,maxit", kc.SWEEP_SETTINGS)
-def test_inexact_cocg_sweep(engine, rtol, maxit, m, warm, real):
-    c = kc.sweep_case("cocg_fused", rtol, maxit, m, warm)
+def test_inexact_cocg_sweep(engine, rtol, maxit, kind, m, warm, real):
+    c = kc.sweep_case("cocg_fused", rtol, maxit, m, warm, kind=kind)
     setup_sweep(engine, c, real)
     use_solver(engine, "cocg", rtol, 0.0, maxit)
     dQ = engine.upload(c.Q)
-    tag = "sweep/cocg/rtol=%g/maxit=%d/m=%d/%s/%s" % (rtol, maxit, m, "ritz" if warm else "zero", "real" if real else "complex")
+    tag = "sweep/cocg/%srtol=%g/maxit=%d/m=%d/%s/%s" % ("" if kind == "cfg3" else kind + "/", rtol, maxit, m, "ritz" if warm else "zero",
+                                                        "real" if real else "complex")
     n = len(c.Z)
     dP, status, st = engine.contour_apply(dQ, m, c.ritz)
     check_sweep(tag, c, engine.download(dP, m), status, real, engine.last_column_iterations(n, m),
@@ -182,16 +196,18 @@ def test_inexact_cocg_sweep(engine, rtol, maxit, m, warm, real):
 
 
 PATHS = {"lazy": {}, "no-lazy": {"FH_NO_LAZY_START": "1"}, "no-shared": {"FH_NO_SHARED_START": "1"}}
+PATH_GRID = [(p, "cfg3") for p in list(PATHS) + ["moments", "no-sum-mode"]] + [(p, "ragged") for p in PATHS]
 
 
 @pytest.mark.parametrize("warm", [True, False], ids=["ritz", "zero"])
-@pytest.mark.parametrize("path", list(PATHS) + ["moments", "no-sum-mode"])
+@pytest.mark.parametrize("path,kind", PATH_GRID, ids=[p if kind == "cfg3" else "%s-%s" % (kind, p) for p, kind in PATH_GRID])
 @pytest.mark.parametrize("rtol,maxit", kc.SWEEP_SETTINGS[:2])
-def test_start_paths_meet_the_same_reference(engine, monkeypatch, rtol, maxit, path, warm):
+def test_start_paths_meet_the_same_reference(engine, monkeypatch, rtol, maxit, path, kind, warm):
     """Lazy start (default), materialised shared start, per-node start residuals, and the two forms without the shared
-    accumulator (moments requested; FH_NO_SUM_MODE=1, read when a handle is created)."""
+    accumulator (moments requested; FH_NO_SUM_MODE=1, read when a handle is created).  The first three also on the ragged
+    pencil with B: the column-scaled first product (colscale) over rows of every length."""
     import feastkit_jl_amd as fk
-    c = kc.sweep_case("cocg_fused", rtol, maxit, 24, warm)
+    c = kc.sweep_case("cocg_fused", rtol, maxit, 24, warm, kind=kind)
     for k, v in PATHS.get(path, {}).items():
         monkeypatch.setenv(k, v)
     eng = engine
@@ -203,7 +219,7 @@ def test_start_paths_meet_the_same_reference(engine, monkeypatch, rtol, maxit, p
         use_solver(eng, "cocg", rtol, 0.0, maxit)
         r = eng.contour_apply(eng.upload(c.Q), 24, c.ritz, want_moments=(path == "moments"))
         n = len(c.Z)
-        check_sweep("paths/%s/rtol=%g/%s" % (path, rtol, "ritz" if warm else "zero"), c, eng.download(r[0], 24), r[1], True,
+        check_sweep("paths/%s%s/rtol=%g/%s" % ("" if kind == "cfg3" else kind + "/", path, rtol, "ritz" if warm else "zero"), c, eng.download(r[0], 24), r[1], True,
                     eng.last_column_iterations(n, 24), eng.last_node_iterations(n), r[2])
         if c.decided.all():
             first = 0 if path in ("lazy", "no-lazy") else 1        # the start residual is a product of its own

@@ -31,6 +31,7 @@ import shifted_cases as sc
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+REPORT = os.environ.get("FH_KRYLOV_STEPS_REPORT")        # measurement runs: the file of test_gpu_krylov_steps.py
 
 
 @pytest.fixture(autouse=True)
@@ -53,6 +54,9 @@ def setup(engine, c, real, solver="shifted_cocg", rtol=3e-2, maxit=60, **kw):
 
 def close_enough(group, dist, D):
     print("shifted-steps %s D=%.3e device=%.3e tol=%.3e" % (group, D, dist, kr.tolerance(D)))
+    if REPORT:
+        with open(REPORT, "a") as f:
+            f.write("shifted/%s %.3e %.3e\n" % (group, D, dist))
     assert dist <= kr.tolerance(D), (group, dist, D)
 
 
@@ -105,6 +109,32 @@ def test_sweep_is_the_restatement_step_for_step(engine, rtol, maxit, ld, family,
         dQ = engine.upload(c.Q)
         dP, status, st = engine.contour_apply(dQ, m, c.ritz)
         tag = "ld=%d/family=%s/rtol=%g/maxit=%d/%s" % (ld, family, rtol, maxit, "ritz" if warm else "zero")
+        check(tag, engine, c, real, engine.download(dP, m), status)
+        status2, st2 = engine.contour_apply_resident(dQ, m, c.ritz)
+        check(tag + "/resident", engine, c, real, engine.download(engine.export_resident(m, which=1), m), status2)
+    finally:
+        engine.set_node_list(np.arange(16))
+
+
+@pytest.mark.parametrize("warm", [True, False], ids=["ritz", "zero"])
+@pytest.mark.parametrize("family", ["3", "16"])
+@pytest.mark.parametrize("ld", [32, 64])
+@pytest.mark.parametrize("rtol,maxit", sc.INEXACT)
+def test_sweep_on_ragged_rows_is_the_restatement(engine, rtol, maxit, ld, family, warm):
+    """The inexact sweeps on ragged_pair(331, b_identity=True): rows of 1 to 65 entries and one of N - 10, rows without a
+    diagonal, rows without entries (k_spmm at ld 32, k_spmm_row at ld 64, k_shift_vec).  On this matrix the zero-guess sum
+    does not cancel (the interval starts inside a cluster of eigenvalues): every case has the discriminating power of
+    test_gpu_krylov_steps.py, asserted on the reference here and in test_ragged_cases_host.py."""
+    m = sc.LD_M[ld]
+    c = sc.sweep_case(sc.RAGGED, family, rtol, maxit, m, warm)
+    assert c.decided.all() and c.fp64_steps_agree
+    assert 32.0 * max(c.drift.values()) <= sc.POWER, c.drift
+    real = ld != 32
+    try:
+        setup(engine, c, real, rtol=rtol, maxit=maxit)
+        dQ = engine.upload(c.Q)
+        dP, status, st = engine.contour_apply(dQ, m, c.ritz)
+        tag = "ragged/ld=%d/family=%s/rtol=%g/maxit=%d/%s" % (ld, family, rtol, maxit, "ritz" if warm else "zero")
         check(tag, engine, c, real, engine.download(dP, m), status)
         status2, st2 = engine.contour_apply_resident(dQ, m, c.ritz)
         check(tag + "/resident", engine, c, real, engine.download(engine.export_resident(m, which=1), m), status2)
