@@ -1,670 +1,46 @@
-// fh_api.hip -- the C ABI of libfeasthip.so (include/feasthip.h).  Host-side orchestration
-// of the gfx950 kernels; no arithmetic on the host except M0 x M0 bookkeeping.
-#include "fh_common.hpp"
+// fh_api.hip -- the sweep side of the C ABI of libfeasthip.so (include/feasthip.h): the operator application, the batched
+// Krylov drivers and their launch geometry, the contour sweep, the count estimate, and the products and shifted solves of the
+// RCI seams.  Host-side orchestration of the gfx950 kernels; no arithmetic on the host except M0 x M0 bookkeeping.  The handle
+// itself: fh_handle.hip; the problem: fh_problem.hip; orthonormalisation: fh_ortho.hip; Rayleigh-Ritz: fh_ritz.hip.
+#include "fh_host.hpp"
 #include "fh_kernels.hpp"
 #include "fh_krylov.hpp"
 #include "fh_dense.hpp"
 #include "fh_banded.hpp"
-#include "fh_eig.hpp"
 #include "fh_comm.hpp"
-#include "fh_cholqr.hpp"
+#include "fh_policy.hpp"       // fh_column_failed
 #include "fh_knobs.hpp"
-#include "../../include/feasthip.h"
 
-#include <algorithm>
-#include <chrono>
 #include <thread>
-#include <cmath>
-#include <cstring>
-
-// ---------------------------------------------------------------------------------------
-// workspace + profiling helpers
-// ---------------------------------------------------------------------------------------
-int fh_get_buf(feasthip_ctx* h, const char* name, size_t bytes, void** out) {
-    auto it = h->bufs.find(name);
-    if (it != h->bufs.end() && it->second.second >= bytes) {
-        *out = it->second.first;
-        return 0;
-    }
-    if (it != h->bufs.end()) {
-        hipStreamSynchronize(h->stream);
-        hipFree(it->second.first);
-        h->bufs.erase(it);
-    }
-    void* p = nullptr;
-    size_t alloc = bytes < 256 ? 256 : bytes;
-    hipError_t e = hipMalloc(&p, alloc);
-    if (e != hipSuccess) {
-        h->last_error = std::string("hipMalloc(") + name + ", " + std::to_string(alloc) + "): " + hipGetErrorString(e);
-        return FEASTHIP_ERROR_MEMORY;
-    }
-    h->bufs[name] = {p, alloc};
-    *out = p;
-    return 0;
-}
-
-// A call is about to return an error while its kernels may still be queued or running on h->stream (progress
-// deadline, faulted queue).  Give the stream a bounded chance to drain; if it does not, the handle is POISONED: the
-// workspaces those kernels use must not be reused or freed, so every later call fails fast until destroy (which then
-// skips the stream synchronisation and leaks the buffers to the process -- the host must exit non-zero or continue in
-// a fresh process; see include/feasthip.h).
-static void fh_poison_unless_drained(feasthip_ctx* h, double grace_s) {
-    const auto t0 = std::chrono::steady_clock::now();
-    for (;;) {
-        const hipError_t q = hipStreamQuery(h->stream);
-        if (q == hipSuccess) return;                        // drained: the handle stays usable
-        if (q != hipErrorNotReady) break;                   // the queue itself reports a fault
-        if (std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > grace_s) break;
-        std::this_thread::sleep_for(std::chrono::milliseconds(5));
-    }
-    h->poisoned = 1;
-    h->last_error += " [handle poisoned: device work may still be in flight; destroy the handle and exit the process]";
-}
-
-void fh_free_bufs(feasthip_ctx* h) {
-    for (auto& kv : h->bufs) hipFree(kv.second.first);
-    h->bufs.clear();
-}
-
-// Sampled event timing (1 launch in 13: a period coprime to the iteration caps, so the samples do not alias with
-// the position inside a solve, where kernel durations shrink as nodes converge): every FH_PROF_PERIOD-th launch of a class is bracketed by two events
-// on the launch stream; the class average is (sum of sampled durations)/(samples).
-#define FH_PROF_PERIOD 13
-static thread_local int fh_prof_open = 0;
-static inline double fh_now_s() {
-    return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
-void fh_prof_begin(feasthip_ctx* h, const char* cls) {
-    fh_prof_open = 0;
-    if (!h->profiling) return;
-    fh_prof_class& pc = h->prof[cls];
-    pc.launches += 1;
-    const int period = h->prof_period > 0 ? h->prof_period : fh_knob::prof_period(FH_PROF_PERIOD);
-    const long eff = (long)period * h->prof_mult;
-    if (eff > 1 && (pc.launches % eff) != 1) return;
-    if (h->pending_events.size() > 60000) return;
-    const double t_in = fh_now_s();
-    fh_event_pair ep;
-    ep.cls = cls;
-    // events are recycled through a pool: creating and destroying a pair per sample cost more than recording it
-    if (!fh_knob::prof_nopool() && h->event_pool.size() >= 2) {
-        ep.a = h->event_pool.back(); h->event_pool.pop_back();
-        ep.b = h->event_pool.back(); h->event_pool.pop_back();
-    } else {
-        if (hipEventCreate(&ep.a) != hipSuccess) return;
-        if (hipEventCreate(&ep.b) != hipSuccess) { hipEventDestroy(ep.a); return; }
-    }
-    hipEventRecord(ep.a, h->stream);
-    h->pending_events.push_back(ep);
-    fh_prof_open = 1;
-    h->prof_host_s += fh_now_s() - t_in;
-}
-void fh_prof_end(feasthip_ctx* h) {
-    if (!fh_prof_open) return;
-    const double t_in = fh_now_s();
-    hipEventRecord(h->pending_events.back().b, h->stream);
-    fh_prof_open = 0;
-    h->prof_host_s += fh_now_s() - t_in;
-}
-void fh_prof_collect(feasthip_ctx* h) {
-    if (h->pending_events.empty()) return;
-    hipStreamSynchronize(h->stream);
-    const double t_in = fh_now_s();
-    for (auto& ep : h->pending_events) {
-        float ms = 0.f;
-        if (hipEventElapsedTime(&ms, ep.a, ep.b) == hipSuccess) {
-            fh_prof_class& pc = h->prof[ep.cls + std::string("#sampled")];
-            pc.total_ms += ms;
-            pc.launches += 1;
-        }
-        if (h->event_pool.size() < 8192) { h->event_pool.push_back(ep.a); h->event_pool.push_back(ep.b); }
-        else { hipEventDestroy(ep.a); hipEventDestroy(ep.b); }
-    }
-    h->pending_events.clear();
-    // Event calls are cheap on most hosts (0.7 % of a bench step at 1 launch in 13) but were seen to cost ~90 us each
-    // on a loaded box: when sampling has taken more than 1 % of the wall time since it was switched on, sample 7x
-    // less often (91 stays coprime to the iteration caps), up to 1 launch in 637.
-    h->prof_host_s += fh_now_s() - t_in;
-    const double wall = fh_now_s() - h->prof_t0;
-    if ((h->prof_period > 0 ? h->prof_period : fh_knob::prof_period(FH_PROF_PERIOD)) > 1 && wall > 0.05 && h->prof_host_s > 0.01 * wall && h->prof_mult < 49) {   // period 1 = exact timing requested
-        h->prof_mult *= 7;
-        h->prof_host_s = 0.0;
-        h->prof_t0 = fh_now_s();
-    }
-}
-
-// ---------------------------------------------------------------------------------------
-// lifecycle
-// ---------------------------------------------------------------------------------------
-extern "C" int feasthip_version(int* major, int* minor) {
-    if (major) *major = FEASTHIP_VERSION_MAJOR;
-    if (minor) *minor = FEASTHIP_VERSION_MINOR;
-    return 0;
-}
-
-extern "C" int feasthip_create(feasthip_handle* out, int device_id) {
-    if (!out) return FEASTHIP_ERROR_INTERNAL;
-    *out = nullptr;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return FEASTHIP_ERROR_INTERNAL;
-    if (device_id < 0 || device_id >= ndev) return FEASTHIP_ERROR_INTERNAL;
-    feasthip_ctx* h = new (std::nothrow) feasthip_ctx();
-    if (!h) return FEASTHIP_ERROR_MEMORY;
-    h->device = device_id;
-    h->lu_outer_block = fh_knob::lu_kb(h->lu_outer_block);
-    h->lu_solve_legacy = fh_knob::lu_solve_32();
-    h->lu_gemm_staged = fh_knob::lu_gemm_staged();
-    h->lu_lookahead = fh_knob::lu_lookahead();
-    h->sum_mode = fh_knob::no_sum_mode() ? 0 : 1;
-    h->lu_panel_legacy = fh_knob::lu_panel_legacy();
-    if (hipSetDevice(device_id) != hipSuccess) { delete h; return FEASTHIP_ERROR_INTERNAL; }
-    if (hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking) != hipSuccess) { delete h; return FEASTHIP_ERROR_INTERNAL; }
-    h->stream = h->own_stream;
-    if (hipHostMalloc((void**)&h->pin, (size_t)1 << 20, hipHostMallocDefault) == hipSuccess) h->pin_cap = (size_t)1 << 20;
-    else { h->pin = nullptr; h->pin_cap = 0; hipGetLastError(); }
-    if (hipMalloc((void**)&h->d_counters, 8 * sizeof(unsigned long long)) != hipSuccess) { hipStreamDestroy(h->own_stream); delete h; return FEASTHIP_ERROR_MEMORY; }
-    hipMemset(h->d_counters, 0, 8 * sizeof(unsigned long long));
-    {
-        void* hp = nullptr;
-        if (hipHostMalloc(&hp, 64, hipHostMallocMapped) != hipSuccess) { hipFree(h->d_counters); hipStreamDestroy(h->own_stream); delete h; return FEASTHIP_ERROR_MEMORY; }
-        h->h_progress = (volatile unsigned long long*)hp;
-        *h->h_progress = 0ull;
-        void* dp = nullptr;
-        if (hipHostGetDevicePointer(&dp, hp, 0) != hipSuccess) { hipHostFree(hp); hipFree(h->d_counters); hipStreamDestroy(h->own_stream); delete h; return FEASTHIP_ERROR_INTERNAL; }
-        h->d_progress = (unsigned long long*)dp;
-    }
-    *out = h;
-    return 0;
-}
-
-static void fh_free_adjoint_csr(feasthip_ctx* h) {
-    for (void* p : {(void*)h->csr_adj.rowptr, (void*)h->csr_adj.col, h->csr_adj.aval, h->csr_adj.bval}) if (p) hipFree(p);
-    h->csr_adj = fh_csr();
-}
-
-void fh_free_problem(feasthip_ctx* h) {
-    if (h->csr.rowptr) hipFree(h->csr.rowptr);
-    if (h->csr.col) hipFree(h->csr.col);
-    if (h->csr.aval) hipFree(h->csr.aval);
-    if (h->csr.bval) hipFree(h->csr.bval);
-    if (h->csr.perm) hipFree(h->csr.perm);
-    if (h->csr.rp8) hipFree(h->csr.rp8);
-    if (h->csr.col8) hipFree(h->csr.col8);
-    if (h->csr.a8) hipFree(h->csr.a8);
-    if (h->csr.b8) hipFree(h->csr.b8);
-    if (h->csr.blk_start) hipFree(h->csr.blk_start);
-    if (h->csr.ext_ptr) hipFree(h->csr.ext_ptr);
-    if (h->csr.ext_idx) hipFree(h->csr.ext_idx);
-    if (h->csr.lcol) hipFree(h->csr.lcol);
-    h->csr = fh_csr();
-    fh_free_adjoint_csr(h);
-    if (h->dense.A) hipFree(h->dense.A);
-    if (h->dense.B) hipFree(h->dense.B);
-    h->dense = fh_dense();
-    for (void* p : h->poly.coef) if (p) hipFree(p);
-    h->poly = fh_poly();
-    h->op = fh_operator();
-    h->top = fh_termop();
-    for (void* p : h->lu_factors) if (p) hipFree(p);
-    for (int* p : h->lu_pivots) if (p) hipFree(p);
-    h->lu_factors.clear(); h->lu_pivots.clear(); h->lu_valid.clear(); h->lu_z.clear();
-    fh_banded_free(h);
-    h->kind = 0;
-    h->rs_P = h->rs_basis = h->rs_X = h->rs_R = nullptr;
-    h->rs_m = h->rs_ld = h->rs_rank = h->rs_X_m = h->rs_X_ld = 0;
-    h->rs_T.clear(); h->rs_R_lambda.clear();
-}
-
-extern "C" int feasthip_destroy(feasthip_handle h) {
-    if (!h) return 0;
-    hipSetDevice(h->device);
-    if (h->poisoned) {
-        // kernels of a failed call may still be running on the workspaces: neither wait for them (a wedged kernel
-        // never ends) nor free what they touch.  The memory goes back to the driver when the process exits.
-        fh_comm_mark_failed(h);
-        delete h;
-        return 0;
-    }
-    hipStreamSynchronize(h->stream);
-    fh_comm_destroy(h);
-    fh_prof_collect(h);
-    fh_free_problem(h);
-    fh_free_bufs(h);
-    if (h->d_counters) hipFree(h->d_counters);
-    for (auto& ep : h->pending_events) { hipEventDestroy(ep.a); hipEventDestroy(ep.b); }
-    for (hipEvent_t e : h->event_pool) hipEventDestroy(e);
-    if (h->h_progress) hipHostFree((void*)h->h_progress);
-    if (h->pin) hipHostFree(h->pin);
-    if (h->lu_ev_next) hipEventDestroy(h->lu_ev_next);
-    if (h->lu_ev_rest) hipEventDestroy(h->lu_ev_rest);
-    if (h->side_stream) hipStreamDestroy(h->side_stream);
-    if (h->own_stream) hipStreamDestroy(h->own_stream);
-    delete h;
-    return 0;
-}
-
-extern "C" const char* feasthip_last_error(feasthip_handle h) { return h ? h->last_error.c_str() : "null handle"; }
-
-extern "C" int feasthip_set_stream(feasthip_handle h, void* hip_stream) {
-    if (!h) return FEASTHIP_ERROR_INTERNAL;
-    if (h->poisoned) { h->last_error = "handle poisoned by an earlier device failure: destroy it"; return FEASTHIP_ERROR_INTERNAL; }
-    hipStreamSynchronize(h->stream);
-    h->stream = hip_stream ? (hipStream_t)hip_stream : h->own_stream;
-    return 0;
-}
-
-extern "C" int feasthip_synchronize(feasthip_handle h) {
-    if (!h) return FEASTHIP_ERROR_INTERNAL;
-    if (h->poisoned) { h->last_error = "handle poisoned by an earlier device failure: destroy it"; return FEASTHIP_ERROR_INTERNAL; }
-    FH_CHECK(hipSetDevice(h->device));
-    FH_CHECK(hipStreamSynchronize(h->stream));
-    fh_prof_collect(h);
-    FH_CHECK(hipGetLastError());       // launch-configuration errors do not surface through the stream sync
-    return 0;
-}
-
-// ---------------------------------------------------------------------------------------
-// problem definition
-// ---------------------------------------------------------------------------------------
-static inline cplx fh_ing_zero(cplx) { return cmake(0, 0); }
-static inline cplx fh_ing_add(cplx a, cplx b) { return cadd(a, b); }
-static inline cplx fh_ing_conj(cplx a) { return cmake(a.x, -a.y); }
-#define FH_INGEST_STORAGE_CSR FEASTHIP_STORAGE_CSR
-#include "fh_ingest.hpp"       // host side of the ingest (pure C++; also compiled under ASan/UBSan by tests/host_ingest_harness.cpp)
-#include "fh_policy.hpp"       // host policy of the inexact mode (pure C++), exported as feasthip_policy_*
-
-template <typename VT>
-static int set_csr_typed(feasthip_ctx* h, int64_t N, int index_base, int storage, int64_t nnzA, const int64_t* ptrA,
-                         const int64_t* idxA, const VT* valA, int64_t nnzB, const int64_t* ptrB, const int64_t* idxB,
-                         const VT* valB) {
-    // Row-block renumbering (fh_ingest.hpp: recursive bisection into 128-row blocks).  ON by default for wide patterns since
-    // round 3: the row-per-wave SpMM is bound by the traffic that misses L2 (1-KB rows: the two far stencil planes of the
-    // caller's order do not fit 4 MiB), and compact blocks keep a slice's gathers local -- cfg 3: 37 -> 30 us per node and
-    // launch, 163 -> 159 ms per solve.  (k_spmm, with its 256-B tiles, never cared: round 2.)  FH_REORDER=0 keeps the caller's
-    // order, FH_REORDER=2 renumbers whenever there are at least two blocks (test rigs push small problems through it).  The
-    // LDS-window kernel the renumbering was built for stays opt-in (FH_LDS_SPMM=1): 57 vs 33 us per node on cfg 3.
-    fh_prepared<VT> P;
-    std::string err;
-    const int prc = fh_prepare_csr<VT>(N, index_base, storage, nnzA, ptrA, idxA, valA, nnzB, ptrB, idxB, valB, fh_knob::reorder(),
-                                       FH_SPMM_R, FH_SPMM_EXT, sizeof(VT) == sizeof(double), P, err);
-    if (prc) { h->last_error = "feasthip_set_csr: " + err; return prc == 3 ? FEASTHIP_ERROR_MEMORY : FEASTHIP_ERROR_N; }
-    const bool hasB = ptrB != nullptr;
-    fh_free_problem(h);
-    h->csr_kl = P.kl; h->csr_ku = P.ku;
-    h->host_rowptr = P.rowptr; h->host_col = P.col;
-    const std::vector<int>& rowptr = P.rowptr;
-    const std::vector<int>& col = P.col;
-    fh_csr& d = h->csr;
-    d.N = N; d.nnz = (int64_t)col.size(); d.is_complex = sizeof(VT) == sizeof(cplx); d.b_identity = hasB ? 0 : 1;
-    FH_CHECK(hipMalloc((void**)&d.rowptr, (N + 1) * sizeof(int)));
-    FH_CHECK(hipMalloc((void**)&d.col, std::max<size_t>(1, col.size()) * sizeof(int)));
-    FH_CHECK(hipMalloc(&d.aval, std::max<size_t>(1, col.size()) * sizeof(VT)));
-    FH_CHECK(hipMemcpy(d.rowptr, rowptr.data(), (N + 1) * sizeof(int), hipMemcpyHostToDevice));
-    FH_CHECK(hipMemcpy(d.col, col.data(), col.size() * sizeof(int), hipMemcpyHostToDevice));
-    FH_CHECK(hipMemcpy(d.aval, P.av.data(), col.size() * sizeof(VT), hipMemcpyHostToDevice));
-    if (hasB) {
-        FH_CHECK(hipMalloc(&d.bval, std::max<size_t>(1, col.size()) * sizeof(VT)));
-        FH_CHECK(hipMemcpy(d.bval, P.bv.data(), col.size() * sizeof(VT), hipMemcpyHostToDevice));
-    }
-    if (!P.rp8.empty()) {
-        FH_CHECK(hipMalloc((void**)&d.rp8, (N + 1) * sizeof(int)));
-        FH_CHECK(hipMalloc((void**)&d.col8, P.col8.size() * sizeof(int)));
-        FH_CHECK(hipMalloc((void**)&d.a8, P.a8.size() * sizeof(double)));
-        FH_CHECK(hipMemcpy(d.rp8, P.rp8.data(), (N + 1) * sizeof(int), hipMemcpyHostToDevice));
-        FH_CHECK(hipMemcpy(d.col8, P.col8.data(), P.col8.size() * sizeof(int), hipMemcpyHostToDevice));
-        FH_CHECK(hipMemcpy(d.a8, P.a8.data(), P.a8.size() * sizeof(double), hipMemcpyHostToDevice));
-        if (hasB) {
-            FH_CHECK(hipMalloc((void**)&d.b8, P.b8.size() * sizeof(double)));
-            FH_CHECK(hipMemcpy(d.b8, P.b8.data(), P.b8.size() * sizeof(double), hipMemcpyHostToDevice));
-        }
-    }
-    if (!P.perm.empty()) {
-        const int nb = (int)P.blk_start.size() - 1;
-        FH_CHECK(hipMalloc((void**)&d.perm, N * sizeof(int)));
-        FH_CHECK(hipMemcpy(d.perm, P.perm.data(), N * sizeof(int), hipMemcpyHostToDevice));
-        d.nblk = nb;
-        FH_CHECK(hipMalloc((void**)&d.blk_start, (nb + 1) * sizeof(int)));
-        FH_CHECK(hipMalloc((void**)&d.ext_ptr, (nb + 1) * sizeof(int)));
-        FH_CHECK(hipMalloc((void**)&d.ext_idx, std::max<size_t>(1, P.ext_idx.size()) * sizeof(int)));
-        FH_CHECK(hipMalloc((void**)&d.lcol, std::max<size_t>(1, P.lcol.size()) * sizeof(unsigned short)));
-        FH_CHECK(hipMemcpy(d.blk_start, P.blk_start.data(), (nb + 1) * sizeof(int), hipMemcpyHostToDevice));
-        FH_CHECK(hipMemcpy(d.ext_ptr, P.ext_ptr.data(), (nb + 1) * sizeof(int), hipMemcpyHostToDevice));
-        FH_CHECK(hipMemcpy(d.ext_idx, P.ext_idx.data(), P.ext_idx.size() * sizeof(int), hipMemcpyHostToDevice));
-        FH_CHECK(hipMemcpy(d.lcol, P.lcol.data(), P.lcol.size() * sizeof(unsigned short), hipMemcpyHostToDevice));
-        if (fh_knob::debug_timing())
-            fprintf(stderr, "[feasthip] renumbered into %d row blocks, %.1f outside rows per block on average\n", nb, nb ? (double)P.ext_idx.size() / nb : 0.0);
-    }
-    h->kind = 2;
-    return 0;
-}
-
-// The adjoint CSR set of the problem (h->csr_adj), built on first use: the host keeps only the pattern, so the values come back
-// from the device once; the transpose is fh_adjoint_csr (fh_ingest.hpp).  Only what k_spmm reads is made: no chunk-of-8 rows,
-// no LDS-window data.
-template <typename VT>
-static int fh_adjoint_csr_build(feasthip_ctx* h) {
-    const fh_csr& d = h->csr;
-    const int64_t N = d.N;
-    const size_t nnz = (size_t)d.nnz;
-    if ((int64_t)h->host_rowptr.size() != N + 1 || h->host_col.size() != nnz) { h->last_error = "adjoint CSR set: no host pattern"; return FEASTHIP_ERROR_INTERNAL; }
-    std::vector<VT> av(nnz), bv(d.b_identity ? 0 : nnz);
-    FH_CHECK(hipStreamSynchronize(h->stream));
-    if (nnz) FH_CHECK(hipMemcpy(av.data(), d.aval, nnz * sizeof(VT), hipMemcpyDeviceToHost));
-    if (nnz && !d.b_identity) FH_CHECK(hipMemcpy(bv.data(), d.bval, nnz * sizeof(VT), hipMemcpyDeviceToHost));
-    std::vector<int> rp, cl;
-    std::vector<VT> avt, bvt;
-    fh_adjoint_csr<VT>(N, h->host_rowptr, h->host_col, av.data(), d.b_identity ? nullptr : bv.data(), rp, cl, avt, bvt);
-    fh_free_adjoint_csr(h);
-    fh_csr& t = h->csr_adj;
-    FH_CHECK(hipMalloc((void**)&t.rowptr, (N + 1) * sizeof(int)));
-    FH_CHECK(hipMalloc((void**)&t.col, std::max<size_t>(1, nnz) * sizeof(int)));
-    FH_CHECK(hipMalloc(&t.aval, std::max<size_t>(1, nnz) * sizeof(VT)));
-    FH_CHECK(hipMemcpy(t.rowptr, rp.data(), (N + 1) * sizeof(int), hipMemcpyHostToDevice));
-    if (nnz) FH_CHECK(hipMemcpy(t.col, cl.data(), nnz * sizeof(int), hipMemcpyHostToDevice));
-    if (nnz) FH_CHECK(hipMemcpy(t.aval, avt.data(), nnz * sizeof(VT), hipMemcpyHostToDevice));
-    if (!d.b_identity) {
-        FH_CHECK(hipMalloc(&t.bval, std::max<size_t>(1, nnz) * sizeof(VT)));
-        if (nnz) FH_CHECK(hipMemcpy(t.bval, bvt.data(), nnz * sizeof(VT), hipMemcpyHostToDevice));
-    }
-    t.N = N; t.nnz = d.nnz; t.is_complex = d.is_complex; t.b_identity = d.b_identity;
-    return 0;
-}
-static int fh_adjoint_csr_ensure(feasthip_ctx* h) {
-    if (h->csr_adj.rowptr && h->csr_adj.N == h->csr.N) return 0;
-    const int rc = h->csr.is_complex ? fh_adjoint_csr_build<cplx>(h) : fh_adjoint_csr_build<double>(h);
-    if (rc) fh_free_adjoint_csr(h);
-    return rc;
-}
-
-extern "C" int feasthip_set_csr(feasthip_handle h, int64_t N, int is_complex, int index_base, int storage,
-                                int64_t nnzA, const int64_t* ptrA, const int64_t* idxA, const void* valA,
-                                int64_t nnzB, const int64_t* ptrB, const int64_t* idxB, const void* valB) {
-    if (!h) return FEASTHIP_ERROR_INTERNAL;
-    if (N <= 0 || N > INT32_MAX / FH_MAX_LD) { h->last_error = "feasthip_set_csr: N out of range"; return FEASTHIP_ERROR_N; }
-    if (!ptrA || (nnzA > 0 && (!idxA || !valA))) { h->last_error = "feasthip_set_csr: null A"; return FEASTHIP_ERROR_N; }
-    if (index_base != 0 && index_base != 1) { h->last_error = "feasthip_set_csr: index_base must be 0 or 1"; return FEASTHIP_ERROR_FPM; }
-    if (storage != FEASTHIP_STORAGE_CSR && storage != FEASTHIP_STORAGE_CSC) { h->last_error = "feasthip_set_csr: bad storage"; return FEASTHIP_ERROR_FPM; }
-    FH_CHECK(hipSetDevice(h->device));
-    FH_CHECK(hipStreamSynchronize(h->stream));
-    if (is_complex)
-        return set_csr_typed<cplx>(h, N, index_base, storage, nnzA, ptrA, idxA, (const cplx*)valA, nnzB, ptrB, idxB, (const cplx*)valB);
-    return set_csr_typed<double>(h, N, index_base, storage, nnzA, ptrA, idxA, (const double*)valA, nnzB, ptrB, idxB, (const double*)valB);
-}
-
-extern "C" int feasthip_release_factors(feasthip_handle h) {
-    if (!h) return FEASTHIP_ERROR_INTERNAL;
-    if (h->poisoned) { h->last_error = "handle poisoned by an earlier device failure: destroy it"; return FEASTHIP_ERROR_INTERNAL; }
-    FH_CHECK(hipSetDevice(h->device));
-    FH_CHECK(hipStreamSynchronize(h->stream));
-    if (h->side_stream) FH_CHECK(hipStreamSynchronize(h->side_stream));
-    for (void* p : h->lu_factors) if (p) hipFree(p);
-    for (int* p : h->lu_pivots) if (p) hipFree(p);
-    h->lu_factors.clear(); h->lu_pivots.clear(); h->lu_valid.clear(); h->lu_z.clear();
-    for (void* p : h->band_factors) if (p) hipFree(p);
-    for (int* p : h->band_pivots) if (p) hipFree(p);
-    h->band_factors.clear(); h->band_pivots.clear(); h->band_valid.clear(); h->band_z.clear();
-    fh_mf_free_buffers(h);
-    return 0;
-}
-
-extern "C" int feasthip_band_plan(feasthip_handle h, int* kl, int* ku, int64_t* bytes_per_node, int* blocked) {
-    if (!h) return FEASTHIP_ERROR_INTERNAL;
-    if (h->poisoned) { h->last_error = "handle poisoned by an earlier device failure: destroy it"; return FEASTHIP_ERROR_INTERNAL; }
-    FH_CHECK(hipSetDevice(h->device));
-    return fh_banded_plan(h, kl, ku, bytes_per_node, blocked);
-}
-extern "C" int feasthip_direct_plan_flops(feasthip_handle h, double* flops_per_node) {
-    if (!h) return FEASTHIP_ERROR_INTERNAL;
-    if (h->poisoned) { h->last_error = "handle poisoned by an earlier device failure: destroy it"; return FEASTHIP_ERROR_INTERNAL; }
-    FH_CHECK(hipSetDevice(h->device));
-    return fh_banded_plan_flops(h, flops_per_node);
-}
-
-extern "C" int feasthip_set_dense(feasthip_handle h, int64_t N, int is_complex, const void* A, int64_t lda,
-                                  const void* B, int64_t ldb) {
-    if (!h) return FEASTHIP_ERROR_INTERNAL;
-    if (N <= 0 || N > 65536) { h->last_error = "feasthip_set_dense: N out of range"; return FEASTHIP_ERROR_N; }
-    if (!A || lda < N || (B && ldb < N)) { h->last_error = "feasthip_set_dense: bad A/lda/ldb"; return FEASTHIP_ERROR_N; }
-    FH_CHECK(hipSetDevice(h->device));
-    FH_CHECK(hipStreamSynchronize(h->stream));
-    fh_free_problem(h);
-    size_t es = is_complex ? sizeof(cplx) : sizeof(double);
-    fh_dense& d = h->dense;
-    d.N = N; d.is_complex = is_complex; d.b_identity = B ? 0 : 1;
-    FH_CHECK(hipMalloc(&d.A, (size_t)N * N * es));
-    FH_CHECK(hipMemcpy2D(d.A, (size_t)N * es, A, (size_t)lda * es, (size_t)N * es, (size_t)N, hipMemcpyHostToDevice));
-    if (B) {
-        FH_CHECK(hipMalloc(&d.B, (size_t)N * N * es));
-        FH_CHECK(hipMemcpy2D(d.B, (size_t)N * es, B, (size_t)ldb * es, (size_t)N * es, (size_t)N, hipMemcpyHostToDevice));
-    }
-    h->kind = 1;
-    return 0;
-}
-
-// What an operator handle (h->kind == 4, feasthip_set_operator) cannot take; every message names the solvers it does take
-static const char* const fh_operator_why_adjoint =
-    "an operator handle (feasthip_set_operator) has no adjoint form: the callback applies A and B only, under the Krylov solvers FEASTHIP_SOLVER_BICGSTAB, _COCG or _GMRES";
-static const char* fh_operator_solver_why(const feasthip_ctx* h, int kind, int factor_precision) {
-    if (kind == FEASTHIP_SOLVER_LU || kind == FEASTHIP_SOLVER_BANDED)
-        return "an operator handle (feasthip_set_operator) has no matrix to factor: use the Krylov solvers FEASTHIP_SOLVER_BICGSTAB, _COCG or _GMRES";
-    const bool cocg = kind == FEASTHIP_SOLVER_COCG || kind == FEASTHIP_SOLVER_SHIFTED_COCG || kind == FEASTHIP_SOLVER_BLOCK_COCG;
-    if (cocg && (!h->op.symmetric || h->dense.is_complex))
-        return "FEASTHIP_SOLVER_COCG on an operator handle needs FEASTHIP_OP_SYMMETRIC and a real operator (A = A^T, B = B^T): of the Krylov solvers FEASTHIP_SOLVER_BICGSTAB, _COCG or _GMRES take _BICGSTAB or _GMRES";
-    if (factor_precision == 32)
-        return "factor_precision = 32 is not supported on an operator handle: the Krylov solvers FEASTHIP_SOLVER_BICGSTAB, _COCG or _GMRES run on complex128 panels";
-    return nullptr;
-}
-
-// What a term-operator handle (h->kind == 5, feasthip_set_term_operator) cannot take; every message names the solvers it does take
-const char* fh_termop_solver_why(const feasthip_ctx* h, int kind, int factor_precision) {
-    if (kind == FEASTHIP_SOLVER_LU || kind == FEASTHIP_SOLVER_BANDED) return "there is no matrix to factor: " FH_TERMOP_TAKES;
-    if (kind == FEASTHIP_SOLVER_SHIFTED_COCG || kind == FEASTHIP_SOLVER_BLOCK_COCG) return "the shifted and block COCG sweeps are pencil sweeps: " FH_TERMOP_TAKES;
-    if (kind == FEASTHIP_SOLVER_COCG && !h->op.symmetric) return "FEASTHIP_SOLVER_COCG needs FEASTHIP_OP_SYMMETRIC (every A_k = A_k^T): " FH_TERMOP_TAKES;
-    if (factor_precision == 32) return "factor_precision = 32 is not supported (complex128 panels): " FH_TERMOP_TAKES;
-    return nullptr;
-}
-
-extern "C" int feasthip_set_contour(feasthip_handle h, int ne, const double* zne, const double* wne, double weight_scale) {
-    if (!h) return FEASTHIP_ERROR_INTERNAL;
-    if (ne <= 0 || !zne || !wne) { h->last_error = "feasthip_set_contour: ne <= 0 or null arrays"; return FEASTHIP_ERROR_FPM; }
-    h->zne.resize(ne); h->wne.resize(ne);
-    for (int e = 0; e < ne; ++e) {
-        h->zne[e] = cmake(zne[2 * e], zne[2 * e + 1]);
-        h->wne[e] = cmake(wne[2 * e], wne[2 * e + 1]);
-    }
-    h->weight_scale = weight_scale;
-    if ((int)h->node_kinds.size() != ne) h->node_kinds.clear();      // feasthip_set_node_solver: kinds of another contour
-    h->node_first = 0;
-    h->node_count = ne;
-    h->node_ids.resize(ne);
-    for (int e = 0; e < ne; ++e) h->node_ids[e] = e;
-    // cached factors stay: slot e is reused only when its shift equals the new z_e exactly (fh_dense_lu_solve_nodes,
-    // fh_banded_solve_nodes), so a repeated solve on the same contour keeps its factorisations and any other contour
-    // refactors slot by slot
-    return 0;
-}
-
-extern "C" int feasthip_set_node_solver(feasthip_handle h, int count, const int* kinds) {
-    if (!h) return FEASTHIP_ERROR_INTERNAL;
-    if (count == 0 || !kinds) { h->node_kinds.clear(); return 0; }
-    if (count != (int)h->zne.size()) {
-        h->last_error = "feasthip_set_node_solver: count " + std::to_string(count) + " is not the contour's node count " + std::to_string(h->zne.size());
-        return FEASTHIP_ERROR_FPM;
-    }
-    for (int e = 0; e < count; ++e)
-        if (kinds[e] != 0 && kinds[e] != FEASTHIP_SOLVER_BANDED) {
-            h->last_error = "feasthip_set_node_solver: kind " + std::to_string(kinds[e]) + " of node " + std::to_string(e) + " (0 or FEASTHIP_SOLVER_BANDED)";
-            return FEASTHIP_ERROR_FPM;
-        }
-    if (h->kind == 4)
-        for (int e = 0; e < count; ++e)
-            if (kinds[e] != 0) {
-                h->last_error = "feasthip_set_node_solver: an operator handle (feasthip_set_operator) has no matrix for a direct node; every node takes the Krylov solvers FEASTHIP_SOLVER_BICGSTAB, _COCG or _GMRES";
-                return FEASTHIP_ERROR_FPM;
-            }
-    if (h->kind == 5)
-        for (int e = 0; e < count; ++e)
-            if (kinds[e] != 0) { h->last_error = "feasthip_set_node_solver: there is no matrix for a direct node: " FH_TERMOP_TAKES; return FEASTHIP_ERROR_FPM; }
-    h->node_kinds.assign(kinds, kinds + count);
-    return 0;
-}
-
-extern "C" int feasthip_direct_plan_bytes(feasthip_handle h, int nodes, int64_t* factor_bytes, int64_t* transient_bytes) {
-    if (!h) return FEASTHIP_ERROR_INTERNAL;
-    if (h->poisoned) { h->last_error = "handle poisoned by an earlier device failure: destroy it"; return FEASTHIP_ERROR_INTERNAL; }
-    if (!(h->kind == 2 || (h->kind == 3 && h->poly.sparse)) || nodes < 0) {
-        h->last_error = "feasthip_direct_plan_bytes: needs a CSR problem (or a sparse polynomial) and nodes >= 0";
-        return FEASTHIP_ERROR_FPM;
-    }
-    FH_CHECK(hipSetDevice(h->device));
-    return fh_banded_plan_bytes(h, nodes, factor_bytes, transient_bytes);
-}
-
-extern "C" int feasthip_set_real_projection(feasthip_handle h, int real_part) {
-    if (!h) return FEASTHIP_ERROR_INTERNAL;
-    h->real_projection = real_part ? 1 : 0;
-    return 0;
-}
-
-extern "C" int feasthip_set_adjoint(feasthip_handle h, int on) {
-    if (!h) return FEASTHIP_ERROR_INTERNAL;
-    if (on && h->kind == 3) { h->last_error = "feasthip_set_adjoint: a polynomial handle has no adjoint form (the feasthip_poly_* calls are forward only)"; return FEASTHIP_ERROR_FPM; }
-    if (on && h->kind == 4) { h->last_error = std::string("feasthip_set_adjoint: ") + fh_operator_why_adjoint; return FEASTHIP_ERROR_FPM; }
-    if (on && h->kind == 5) { h->last_error = "feasthip_set_adjoint: the callback applies the A_k only, there is no adjoint form: " FH_TERMOP_TAKES; return FEASTHIP_ERROR_FPM; }
-    h->adjoint = on ? 1 : 0;
-    return 0;
-}
-
-extern "C" int feasthip_require_adjoint(feasthip_handle h, int on) {
-    if (!h) return FEASTHIP_ERROR_INTERNAL;
-    h->require_adjoint = on ? 1 : 0;
-    return 0;
-}
-
-extern "C" int feasthip_set_node_range(feasthip_handle h, int first, int count) {
-    if (!h) return FEASTHIP_ERROR_INTERNAL;
-    if (first < 0 || count < 0 || first + count > (int)h->zne.size()) {
-        h->last_error = "feasthip_set_node_range: range outside the contour";
-        return FEASTHIP_ERROR_FPM;
-    }
-    if (h->kind == 5 && (first != 0 || count != (int)h->zne.size())) {
-        h->last_error = "feasthip_set_node_range: the whole contour is swept on one rank: " FH_TERMOP_TAKES;
-        return FEASTHIP_ERROR_FPM;
-    }
-    if (h->kind == 3 && (first != 0 || count != (int)h->zne.size())) {
-        h->last_error = "feasthip_set_node_range: a polynomial handle sweeps the whole contour (feasthip_poly_contour_apply_dev runs on one rank)";
-        return FEASTHIP_ERROR_FPM;
-    }
-    h->node_first = first;
-    h->node_count = count;
-    h->node_ids.resize(count);
-    for (int e = 0; e < count; ++e) h->node_ids[e] = first + e;
-    return 0;
-}
-
-extern "C" int feasthip_set_node_list(feasthip_handle h, int count, const int* indices) {
-    if (!h) return FEASTHIP_ERROR_INTERNAL;
-    if (count < 0 || (count > 0 && !indices)) { h->last_error = "feasthip_set_node_list: bad arguments"; return FEASTHIP_ERROR_FPM; }
-    if (h->kind == 5) { h->last_error = "feasthip_set_node_list: the whole contour is swept on one rank: " FH_TERMOP_TAKES; return FEASTHIP_ERROR_FPM; }
-    if (h->kind == 3) {
-        h->last_error = "feasthip_set_node_list: a polynomial handle sweeps the whole contour (feasthip_poly_contour_apply_dev runs on one rank)";
-        return FEASTHIP_ERROR_FPM;
-    }
-    for (int e = 0; e < count; ++e)
-        if (indices[e] < 0 || indices[e] >= (int)h->zne.size()) {
-            h->last_error = "feasthip_set_node_list: index outside the contour";
-            return FEASTHIP_ERROR_FPM;
-        }
-    h->node_ids.assign(indices, indices + count);
-    h->node_first = count > 0 ? indices[0] : 0;
-    h->node_count = count;
-    return 0;
-}
-
-extern "C" int feasthip_set_column_mask(feasthip_handle h, int64_t m, const int* mask) {
-    if (!h) return FEASTHIP_ERROR_INTERNAL;
-    if (m < 0 || m > (1 << 20)) { h->last_error = "set_column_mask: m out of range"; return FEASTHIP_ERROR_M0; }
-    h->col_mask.clear();
-    if (mask && m > 0) h->col_mask.assign(mask, mask + m);
-    return 0;
-}
-
-extern "C" int feasthip_set_solver(feasthip_handle h, int kind, double rtol, double atol, int maxit, int restart,
-                                   int factor_precision, int cache_factors) {
-    if (!h) return FEASTHIP_ERROR_INTERNAL;
-    if (kind < 0 || kind > FEASTHIP_SOLVER_BLOCK_COCG || rtol < 0 || atol < 0 || maxit <= 0 || restart < 0 ||
-        (factor_precision != 64 && factor_precision != 32)) {
-        h->last_error = "feasthip_set_solver: invalid option";
-        return FEASTHIP_ERROR_FPM;
-    }
-    if (h->kind == 3) {
-        // dense coefficients: the LU of P(z_e) only.  CSR coefficients: that (the multifrontal LU), or a Krylov solver on the
-        // operator P(z_e) (fh_poly.hip: k_spmm_poly); complex128 throughout
-        const bool krylov = kind == FEASTHIP_SOLVER_BICGSTAB || kind == FEASTHIP_SOLVER_COCG || kind == FEASTHIP_SOLVER_GMRES;
-        if (h->poly.terms && kind != FEASTHIP_SOLVER_LU) {      // the Krylov operator k_spmm_poly forms powers of z_e
-            h->last_error = "feasthip_set_solver: a term handle (feasthip_set_terms) takes FEASTHIP_SOLVER_LU only; Krylov solves on T(z) are not provided";
-            return FEASTHIP_ERROR_FPM;
-        }
-        if (factor_precision != 64 || !(kind == FEASTHIP_SOLVER_LU || (krylov && h->poly.sparse))) {
-            h->last_error = h->poly.sparse ? "feasthip_set_solver: a CSR polynomial handle needs FEASTHIP_SOLVER_LU, _BICGSTAB, _COCG or _GMRES with factor_precision = 64"
-                                           : "feasthip_set_solver: a dense polynomial handle needs FEASTHIP_SOLVER_LU with factor_precision = 64";
-            return FEASTHIP_ERROR_FPM;
-        }
-    }
-    if (h->kind == 4)
-        if (const char* why = fh_operator_solver_why(h, kind, factor_precision)) { h->last_error = std::string("feasthip_set_solver: ") + why; return FEASTHIP_ERROR_FPM; }
-    if (h->kind == 5)
-        if (const char* why = fh_termop_solver_why(h, kind, factor_precision)) { h->last_error = std::string("feasthip_set_solver: ") + why; return FEASTHIP_ERROR_FPM; }
-    // SHIFTED_COCG is COCG with the shifted sweep where fh_contour_apply_panel finds it eligible: every other path sees COCG
-    h->shifted = kind == FEASTHIP_SOLVER_SHIFTED_COCG ? 1 : 0;
-    // BLOCK_COCG likewise: COCG with the block sweep where the panel is eligible
-    h->block = kind == FEASTHIP_SOLVER_BLOCK_COCG ? 1 : 0;
-    if (h->shifted || h->block) kind = FEASTHIP_SOLVER_COCG;
-    h->solver = kind; h->rtol = rtol; h->atol = atol; h->maxit = maxit; h->restart = restart;
-    h->factor_precision = factor_precision; h->cache_factors = cache_factors;
-    return 0;
-}
 
 // ---------------------------------------------------------------------------------------
 // operator application on panels (sparse or dense):  Y = (cb*B + ca*A) X  per column
 // ---------------------------------------------------------------------------------------
 
-struct fh_op_call {
-    const void* X = nullptr; size_t x_stride = 0;
-    void* Y = nullptr; size_t y_stride = 0;
-    const cplx* coefA = nullptr; const cplx* coefB = nullptr;   // device [nodes][ld]
-    const void* Bvec = nullptr; size_t b_stride = 0;
-    const void* U = nullptr; size_t u_stride = 0;
-    int dot_mode = 0; cplx* partial1 = nullptr; cplx* partial2 = nullptr;
-    const int* node_active = nullptr;
-    int nodes = 1;
-    int m = FH_MAX_LD;     // active columns (measurement only)
-    int uniform_coef = 0;  // coefA/coefB identical across columns
-    int prec = 64;         // panel precision of X/Y/Bvec/U
-    const cplx* colscale = nullptr;   // row kernel only (fh_spmm_args::colscale): X is a shared panel times per-node column factors
-    int skip = 0;          // host hint (operator handle): bit 0 -- coefA is zero everywhere, bit 1 -- coefB is: that callback is not made
-};
-
-static int fh_upload_coefs(feasthip_ctx* h, const char* name, const std::vector<cplx>& host, cplx** dev);      // (below: the pinned ring)
-
 // full-width panels over a real matrix go through the row-per-wave kernel (FH_SPMM_ROW=0: the 4-rows-per-wave gather kernel)
 static bool fh_row_kernel_ok(feasthip_ctx* h, int ld) {
-    return h->kind == 2 && ld == 64 && !h->csr.is_complex && h->csr.rp8 && fh_knob::spmm_row();
+    return h->kind == FH_KIND_CSR && ld == 64 && !h->csr.is_complex && h->csr.rp8 && fh_knob::spmm_row();
+}
+
+// The operands that every argument block of an operator has under the same names (fh_spmm_args, fh_polyop_call, fh_userop_call,
+// fh_termop_call, fh_dense_op_args), from the call; the panels take the block's own pointer types.
+template <class Args> static void fh_op_operands(Args& a, const fh_op_call& c) {
+    a.X = (decltype(a.X))c.X; a.x_node_stride = c.x_stride; a.Y = (decltype(a.Y))c.Y; a.y_node_stride = c.y_stride;
+    a.Bvec = (decltype(a.Bvec))c.Bvec; a.b_node_stride = c.b_stride; a.U = (decltype(a.U))c.U; a.u_node_stride = c.u_stride;
+    a.dot_mode = c.dot_mode; a.partial1 = c.partial1; a.partial2 = c.partial2; a.node_active = c.node_active;
 }
 
 // returns number of blocks used in x (needed to size / read partials)
-static int fh_apply_operator(feasthip_ctx* h, int ld, const fh_op_call& c) {
-    if (h->kind == 2 && h->adjoint) {
+int fh_apply_operator(feasthip_ctx* h, int ld, const fh_op_call& c) {
+    if (h->kind == FH_KIND_CSR && h->adjoint) {
         // the conjugate-transposed set through the gather kernel (plain products only, as for the dense adjoint operator)
         if (c.dot_mode != 0 || c.colscale) { h->last_error = "internal: adjoint operator with fused dots"; return -1; }
         if (fh_adjoint_csr_ensure(h)) return -1;
         fh_spmm_args a;
         a.rowptr = h->csr_adj.rowptr; a.col = h->csr_adj.col; a.aval = h->csr_adj.aval; a.bval = h->csr_adj.bval;
         a.N = (int)h->csr.N; a.nodes = c.nodes;
-        a.X = c.X; a.x_node_stride = c.x_stride; a.Y = c.Y; a.y_node_stride = c.y_stride;
-        a.coefA = c.coefA; a.coefB = c.coefB; a.Bvec = c.Bvec; a.b_node_stride = c.b_stride;
-        a.U = c.U; a.u_node_stride = c.u_stride; a.dot_mode = 0;
-        a.partial1 = nullptr; a.partial2 = nullptr; a.node_active = c.node_active;
+        fh_op_operands(a, c);
+        a.coefA = c.coefA; a.coefB = c.coefB; a.partial1 = nullptr; a.partial2 = nullptr;      // (dot_mode is 0: no partial sums)
         a.nblk_rows = 0; a.blk_start = nullptr; a.ext_ptr = nullptr; a.ext_idx = nullptr; a.lcol = nullptr;
         a.counters = h->profiling ? h->d_counters : nullptr; a.m = c.m; a.uniform_coef = c.uniform_coef; a.prec = c.prec;
         fh_prof_begin(h, "spmm_adjoint");
@@ -672,14 +48,12 @@ static int fh_apply_operator(feasthip_ctx* h, int ld, const fh_op_call& c) {
         fh_prof_end(h);
         return fh_spmm_partials(a.N, ld);
     }
-    if (h->kind == 2) {
+    if (h->kind == FH_KIND_CSR) {
         fh_spmm_args a;
         a.rowptr = h->csr.rowptr; a.col = h->csr.col; a.aval = h->csr.aval; a.bval = h->csr.bval;
         a.N = (int)h->csr.N; a.nodes = c.nodes;
-        a.X = c.X; a.x_node_stride = c.x_stride; a.Y = c.Y; a.y_node_stride = c.y_stride;
-        a.coefA = c.coefA; a.coefB = c.coefB; a.Bvec = c.Bvec; a.b_node_stride = c.b_stride;
-        a.U = c.U; a.u_node_stride = c.u_stride; a.dot_mode = c.dot_mode;
-        a.partial1 = c.partial1; a.partial2 = c.partial2; a.node_active = c.node_active;
+        fh_op_operands(a, c);
+        a.coefA = c.coefA; a.coefB = c.coefB;
         a.counters = h->profiling ? h->d_counters : nullptr; a.m = c.m; a.uniform_coef = c.uniform_coef; a.prec = c.prec;
         // (the LDS-window kernel keeps its active-node list in a 64-entry LDS array: wider node batches -- trapezoid
         //  contours put no bound on fpm[2] -- take the gather kernel, which has no such limit)
@@ -698,7 +72,7 @@ static int fh_apply_operator(feasthip_ctx* h, int ld, const fh_op_call& c) {
         if (lds_kernel) return (8 / (ld / 16)) * fh_spmm_lds_slots(a.nblk_rows, ld);
         return fh_spmm_partials(a.N, ld);     // partial-sum rows per node
     }
-    if (h->kind == 3) {
+    if (h->kind == FH_KIND_POLYNOMIAL) {
         // sparse polynomial handle: S_e = P(z_e), z_e = coefB[node][0] of the shifted-operator coefficients (coefA is not read);
         // complex128 panels, the plain product and dot modes 1 .. 4
         if (!h->poly.sparse || h->adjoint || c.prec != 64 || c.colscale || c.dot_mode == 6 || !c.coefB) {
@@ -706,14 +80,12 @@ static int fh_apply_operator(feasthip_ctx* h, int ld, const fh_op_call& c) {
             return -1;
         }
         fh_polyop_call a;
-        a.X = (const cplx*)c.X; a.x_node_stride = c.x_stride; a.Y = (cplx*)c.Y; a.y_node_stride = c.y_stride;
+        fh_op_operands(a, c);
         a.znode = c.coefB; a.z_stride = ld;
-        a.Bvec = (const cplx*)c.Bvec; a.b_node_stride = c.b_stride; a.U = (const cplx*)c.U; a.u_node_stride = c.u_stride;
-        a.dot_mode = c.dot_mode; a.partial1 = c.partial1; a.partial2 = c.partial2; a.node_active = c.node_active;
         a.nodes = c.nodes; a.m = c.m;
         return fh_launch_spmm_poly(h, ld, a);
     }
-    if (h->kind == 4) {
+    if (h->kind == FH_KIND_OPERATOR) {
         // operator handle: the caller's products, then one launch of k_op_combine (fh_operator.hip); complex128 panels, the
         // plain product and dot modes 1 .. 4.  -1 also when a callback failed (h->op.failed): the caller returns at once
         if (h->adjoint || c.prec != 64 || c.colscale || c.dot_mode == 6 || !c.coefA || !c.coefB) {
@@ -721,14 +93,12 @@ static int fh_apply_operator(feasthip_ctx* h, int ld, const fh_op_call& c) {
             return -1;
         }
         fh_userop_call a;
-        a.X = (const cplx*)c.X; a.x_node_stride = c.x_stride; a.Y = (cplx*)c.Y; a.y_node_stride = c.y_stride;
-        a.coefA = c.coefA; a.coefB = c.coefB; a.Bvec = (const cplx*)c.Bvec; a.b_node_stride = c.b_stride;
-        a.U = (const cplx*)c.U; a.u_node_stride = c.u_stride;
-        a.dot_mode = c.dot_mode; a.partial1 = c.partial1; a.partial2 = c.partial2; a.node_active = c.node_active;
+        fh_op_operands(a, c);
+        a.coefA = c.coefA; a.coefB = c.coefB;
         a.nodes = c.nodes; a.skip = c.skip;
         return fh_apply_user_operator(h, ld, a);
     }
-    if (h->kind == 5) {
+    if (h->kind == FH_KIND_TERM_OPERATOR) {
         // term-operator handle: S_e = T(z_e) = sum_k f_k(z_e) A_k on the caller's products (fh_termop.hip); z_e = coefB[node][0] is
         // the key into the node table, as on the polynomial branch, and comes from the host record of the upload; complex128
         // panels, the plain product and dot modes 1 .. 4.  -1 also when a callback failed (h->op.failed)
@@ -753,20 +123,16 @@ static int fh_apply_operator(feasthip_ctx* h, int ld, const fh_op_call& c) {
         cplx* dF;
         if (fh_upload_coefs(h, "top_F", rows, &dF)) return -1;
         fh_termop_call a;
-        a.X = (const cplx*)c.X; a.x_node_stride = c.x_stride; a.Y = (cplx*)c.Y; a.y_node_stride = c.y_stride;
+        fh_op_operands(a, c);
         a.F = dF; a.cols = 0; a.terms = terms;
-        a.Bvec = (const cplx*)c.Bvec; a.b_node_stride = c.b_stride; a.U = (const cplx*)c.U; a.u_node_stride = c.u_stride;
-        a.dot_mode = c.dot_mode; a.partial1 = c.partial1; a.partial2 = c.partial2; a.node_active = c.node_active;
         a.nodes = c.nodes;
         return fh_apply_term_operator(h, ld, a);
     }
     fh_dense_op_args a;
     a.A = h->dense.A; a.B = h->dense.B; a.N = (int)h->dense.N; a.is_complex = h->dense.is_complex;
     // dense operator: complex128 panels only (fh_krylov forces prec 64 for dense matrices)
-    a.nodes = c.nodes; a.X = (const cplx*)c.X; a.x_node_stride = c.x_stride; a.Y = (cplx*)c.Y; a.y_node_stride = c.y_stride;
-    a.coefA = c.coefA; a.coefB = c.coefB; a.Bvec = (const cplx*)c.Bvec; a.b_node_stride = c.b_stride;
-    a.U = (const cplx*)c.U; a.u_node_stride = c.u_stride; a.dot_mode = c.dot_mode;
-    a.partial1 = c.partial1; a.partial2 = c.partial2; a.node_active = c.node_active;
+    a.nodes = c.nodes; a.coefA = c.coefA; a.coefB = c.coefB;
+    fh_op_operands(a, c);
     int nblk = fh_dense_op_nblk(a.N);
     if (h->adjoint) {
         // the entry points that honour the switch use plain products only (fh_check_adjoint keeps the Krylov solvers out)
@@ -782,36 +148,31 @@ static int fh_apply_operator(feasthip_ctx* h, int ld, const fh_op_call& c) {
     return nblk;
 }
 
-static int fh_op_nblk(feasthip_ctx* h, int ld) {
+int fh_op_nblk(feasthip_ctx* h, int ld) {
     // (an upper bound is enough here: it sizes the partial-sum buffers; the row count used by the finalize kernels is what
     //  fh_apply_operator returns for the kernel it actually launched)
-    if (h->kind == 2) return std::max(std::max(fh_spmm_partials((int)h->csr.N, ld), ld == 64 ? fh_spmm_row_grid((int)h->csr.N) : 0),
+    if (h->kind == FH_KIND_CSR) return std::max(std::max(fh_spmm_partials((int)h->csr.N, ld), ld == 64 ? fh_spmm_row_grid((int)h->csr.N) : 0),
                                       h->csr.lcol ? (8 / (ld / 16)) * fh_spmm_lds_slots(h->csr.nblk, ld) : 0);
-    if (h->kind == 3 && h->poly.sparse) return fh_poly_op_nblk((int)h->dense.N, ld);
-    if (h->kind == 4 || h->kind == 5) return fh_op_combine_nblk((int)h->dense.N, ld);
+    if (h->kind == FH_KIND_POLYNOMIAL && h->poly.sparse) return fh_poly_op_nblk((int)h->dense.N, ld);
+    if (fh_callback_products(h)) return fh_op_combine_nblk((int)h->dense.N, ld);
     return fh_dense_op_nblk((int)h->dense.N);
 }
-// row permutation of the panels (block order of a renumbered sparse matrix), or null
-static const int* fh_perm(feasthip_ctx* h) { return h->kind == 2 ? h->csr.perm : nullptr; }
-static int64_t fh_N(feasthip_ctx* h) { return h->kind == 2 ? h->csr.N : h->dense.N; }
-static bool fh_b_identity(feasthip_ctx* h) { return h->kind == 2 ? h->csr.b_identity != 0 : h->dense.b_identity != 0; }
 
 // wide = 1: the entry point also takes m > FH_MAX_LD (processed in 64-column panels)
-static int fh_check_problem(feasthip_ctx* h, int64_t m, int wide = 0) {
-    if (!h) return FEASTHIP_ERROR_INTERNAL;
-    if (h->poisoned) { h->last_error = "handle poisoned by an earlier device failure: destroy it"; return FEASTHIP_ERROR_INTERNAL; }
-    if (h->kind == 0) { h->last_error = "no matrix set (feasthip_set_dense / feasthip_set_csr)"; return FEASTHIP_ERROR_N; }
-    if (h->kind == 3) {     // every entry point that comes through here works on a pencil; the polynomial has its own (fh_poly.hip)
+int fh_check_problem(feasthip_ctx* h, int64_t m, int wide) {
+    if (int gate = fh_gate(h)) return gate;
+    if (h->kind == FH_KIND_NONE) { h->last_error = "no matrix set (feasthip_set_dense / feasthip_set_csr)"; return FEASTHIP_ERROR_N; }
+    if (h->kind == FH_KIND_POLYNOMIAL) {     // every entry point that comes through here works on a pencil; the polynomial has its own (fh_poly.hip)
         h->last_error = "this entry point does not take a polynomial handle (feasthip_set_polynomial): use feasthip_poly_solve_dev, "
                         "feasthip_poly_contour_apply_dev, feasthip_poly_matmul_dev, feasthip_poly_project_dev or feasthip_poly_ritz_residual_dev";
         return FEASTHIP_ERROR_FPM;
     }
-    if (h->kind == 5) {
+    if (h->kind == FH_KIND_TERM_OPERATOR) {
         h->last_error = "this entry point works on a pencil: " FH_TERMOP_TAKES ", through feasthip_nep_set_node_values, feasthip_nep_solve_dev, "
                         "feasthip_nep_eval_cols_dev, feasthip_nep_resinv_apply_dev, feasthip_nep_ritz_eval_dev, feasthip_poly_project_reduced_dev and feasthip_poly_orthonormalize_dev";
         return FEASTHIP_ERROR_FPM;
     }
-    if (h->kind == 4) {
+    if (h->kind == FH_KIND_OPERATOR) {
         h->op.failed = 0;          // a new entry point: the callback is tried again
         if (h->comm) { h->last_error = "an operator handle (feasthip_set_operator) does not take an attached communicator: it sweeps on one rank, under the Krylov solvers FEASTHIP_SOLVER_BICGSTAB, _COCG or _GMRES"; return FEASTHIP_ERROR_FPM; }
     }
@@ -826,20 +187,20 @@ static int fh_check_problem(feasthip_ctx* h, int64_t m, int wide = 0) {
 // handle must be what the adjoint kernels cover: fp64 factors, no real projection, one rank, and either a dense problem under
 // the dense LU or a CSR problem under the sparse direct solver with the multifrontal plan or the blocked band LU (the plan is
 // made here if need be; fh_banded_adjoint_ready).
-static int fh_check_adjoint(feasthip_ctx* h, const char* what, const char* unsupported = nullptr) {
+int fh_check_adjoint(feasthip_ctx* h, const char* what, const char* unsupported) {
     if (!h || !h->adjoint) return 0;
     const char* why = unsupported;
-    if (!why && h->kind == 4) why = fh_operator_why_adjoint;
-    if (!why && h->kind == 2 && h->solver == FEASTHIP_SOLVER_LU) why = "a CSR problem has no dense LU; its adjoint substitution needs FEASTHIP_SOLVER_BANDED (multifrontal plan or blocked band LU)";
-    if (!why && h->kind == 2 && h->solver != FEASTHIP_SOLVER_BANDED) why = "the solver of a CSR problem must be the sparse direct one (FEASTHIP_SOLVER_BANDED): there is no Krylov solver on the conjugate transpose";
-    if (!why && h->kind != 2 && h->solver != FEASTHIP_SOLVER_LU) why = "the solver must be the dense LU (FEASTHIP_SOLVER_LU)";
+    if (!why && h->kind == FH_KIND_OPERATOR) why = fh_operator_why_adjoint;
+    if (!why && h->kind == FH_KIND_CSR && h->solver == FEASTHIP_SOLVER_LU) why = "a CSR problem has no dense LU; its adjoint substitution needs FEASTHIP_SOLVER_BANDED (multifrontal plan or blocked band LU)";
+    if (!why && h->kind == FH_KIND_CSR && h->solver != FEASTHIP_SOLVER_BANDED) why = "the solver of a CSR problem must be the sparse direct one (FEASTHIP_SOLVER_BANDED): there is no Krylov solver on the conjugate transpose";
+    if (!why && h->kind != FH_KIND_CSR && h->solver != FEASTHIP_SOLVER_LU) why = "the solver must be the dense LU (FEASTHIP_SOLVER_LU)";
     if (!why && h->factor_precision == 32) why = "factor_precision = 32 is not supported (complex128 factors only)";
     if (!why && h->real_projection) why = "the real projection does not apply to an adjoint sweep";
     if (!why && h->comm) why = "an attached communicator is not supported";
-    if (!why && h->kind == 2)
+    if (!why && h->kind == FH_KIND_CSR)
         for (int k : h->node_kinds) if (k != 0) { why = "per-node solver kinds (feasthip_set_node_solver) are not supported"; break; }
     std::string plan_why;
-    if (!why && h->kind == 2 && !h->poisoned) {
+    if (!why && h->kind == FH_KIND_CSR && !h->poisoned) {
         if (hipSetDevice(h->device) != hipSuccess) { h->last_error = "hipSetDevice"; return FEASTHIP_ERROR_INTERNAL; }
         if (fh_banded_adjoint_ready(h)) { plan_why = h->last_error; why = plan_why.c_str(); }
         // the conjugate-transposed CSR set, built here at the first adjoint call so that a failed build is an error of the call
@@ -853,7 +214,7 @@ static int fh_check_adjoint(feasthip_ctx* h, const char* what, const char* unsup
 // Operator handle: the solver settings may date from another problem (feasthip_set_solver refuses them only while the operator
 // is set), so the entry points that solve look again
 static int fh_check_operator_solve(feasthip_ctx* h, const char* what) {
-    if (h->kind != 4) return 0;
+    if (h->kind != FH_KIND_OPERATOR) return 0;
     const char* why = fh_operator_solver_why(h, h->solver, h->factor_precision);
     if (!why)
         for (int k : h->node_kinds) if (k != 0) { why = "an operator handle (feasthip_set_operator) has no matrix for a direct node (feasthip_set_node_solver); every node takes the Krylov solvers FEASTHIP_SOLVER_BICGSTAB, _COCG or _GMRES"; break; }
@@ -877,7 +238,7 @@ static int fh_pin_reserve(feasthip_ctx* h, size_t bytes, char** slot) {
 
 // Small host -> device copy through the pinned ring (queued: the source may go out of scope at once; falls back to a
 // synchronous copy)
-static int fh_upload_small(feasthip_ctx* h, void* dst, const void* src, size_t bytes) {
+int fh_upload_small(feasthip_ctx* h, void* dst, const void* src, size_t bytes) {
     char* pin;
     int rc = fh_pin_reserve(h, bytes, &pin);
     if (rc) return rc;
@@ -892,7 +253,7 @@ static int fh_upload_small(feasthip_ctx* h, void* dst, const void* src, size_t b
 }
 
 // upload per-column coefficient arrays [nodes][ld]
-static int fh_upload_coefs(feasthip_ctx* h, const char* name, const std::vector<cplx>& host, cplx** dev) {
+int fh_upload_coefs(feasthip_ctx* h, const char* name, const std::vector<cplx>& host, cplx** dev) {
     const int rc = fh_buf(h, name, host.size(), dev);
     return rc ? rc : fh_upload_small(h, *dev, host.data(), host.size() * sizeof(cplx));
 }
@@ -905,7 +266,7 @@ static int fh_upload_shift_coefs(feasthip_ctx* h, const char* nameA, const char*
         for (int c = 0; c < ld; ++c) cb[(size_t)e * ld + c] = z[e];
     int rc = fh_upload_coefs(h, nameA, ca, dca);
     if (!rc) rc = fh_upload_coefs(h, nameB, cb, dcb);
-    if (!rc && h->kind == 5) { h->top.shift_dev = *dcb; h->top.shift_z.assign(z, z + nodes); }      // the key into the node table
+    if (!rc && h->kind == FH_KIND_TERM_OPERATOR) { h->top.shift_dev = *dcb; h->top.shift_z.assign(z, z + nodes); }      // the key into the node table
     return rc;
 }
 
@@ -949,7 +310,7 @@ static int fh_upload_ritz_lambda(feasthip_ctx* h, const double* ritz_lambda, int
 
 // Small device -> host copy: lands in the pinned ring (one DMA, no pageable staging), *slot points at it; valid after the
 // caller's next stream synchronisation and until the ring wraps
-static int fh_download_small(feasthip_ctx* h, const void* src, size_t bytes, const void** slot, std::vector<char>& fallback) {
+int fh_download_small(feasthip_ctx* h, const void* src, size_t bytes, const void** slot, std::vector<char>& fallback) {
     char* pin;
     int rc = fh_pin_reserve(h, bytes, &pin);
     if (rc) return rc;
@@ -974,6 +335,24 @@ static int fh_download_small(feasthip_ctx* h, const void* src, size_t bytes, con
 //             warm start, the residual and the Rayleigh-Ritz step stay fp64.
 // ---------------------------------------------------------------------------------------
 // (fh_solve_result: fh_krylov.hpp)
+
+// A call is about to return an error while its kernels may still be queued or running on h->stream (progress
+// deadline, faulted queue).  Give the stream a bounded chance to drain; if it does not, the handle is POISONED: the
+// workspaces those kernels use must not be reused or freed, so every later call fails fast until destroy (which then
+// skips the stream synchronisation and leaks the buffers to the process -- the host must exit non-zero or continue in
+// a fresh process; see include/feasthip.h).
+static void fh_poison_unless_drained(feasthip_ctx* h, double grace_s) {
+    const auto t0 = std::chrono::steady_clock::now();
+    for (;;) {
+        const hipError_t q = hipStreamQuery(h->stream);
+        if (q == hipSuccess) return;                        // drained: the handle stays usable
+        if (q != hipErrorNotReady) break;                   // the queue itself reports a fault
+        if (std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > grace_s) break;
+        std::this_thread::sleep_for(std::chrono::milliseconds(5));
+    }
+    h->poisoned = 1;
+    h->last_error += " [handle poisoned: device work may still be in flight; destroy the handle and exit the process]";
+}
 
 // Throttle of the Krylov drivers' queueing loops: after chunk `tag` has been queued (with its publish kernel), wait -- by
 // polling the host-mapped progress word -- until the device is at most three chunks behind; *all_done when a published
@@ -1110,7 +489,7 @@ int fh_krylov_work::alloc(const std::vector<cplx>& z, const std::vector<cplx>* w
     R = vec(0); Rh = vec(1); P = vec(2); V = vec(3); S = vec(4); T = vec(5);
     if (prec == 32) { D = vec(6); RHS32 = vec(7); }
     // operator handle: the callback sees whole panels, and the vector kernels never write the padding columns of S and T
-    if (h->kind == 4 || h->kind == 5) FH_CHECK(hipMemsetAsync(base, 0, (size_t)nvec * nodes * panel * esz, h->stream));
+    if (fh_callback_products(h)) FH_CHECK(hipMemsetAsync(base, 0, (size_t)nvec * nodes * panel * esz, h->stream));
     const size_t nl = (size_t)nodes * ld;
     if ((rc = fh_buf(h, "kry_scal_c", 4 * nl, &s.rho))) return rc;
     s.alpha = s.rho + nl; s.omega = s.alpha + nl; s.beta = s.omega + nl;
@@ -1121,7 +500,7 @@ int fh_krylov_work::alloc(const std::vector<cplx>& z, const std::vector<cplx>* w
     s.iters = s.active + nl; s.status = s.iters + nl; s.node_active = s.status + nl;
     // Fused COCG iteration (fh_sparse.hip): SpMM with five dots -> one finalize -> one vector kernel.  CSR operator through
     // the gather kernel only; FH_COCG_FUSED=0 selects the five-launch form for comparison.
-    fused = method == 1 && h->kind == 2 && fh_knob::cocg_fused();
+    fused = method == 1 && h->kind == FH_KIND_CSR && fh_knob::cocg_fused();
     if (sum_acc || fused) {
         s.accum = s.node_active + nodes + 4; s.node_accum = s.accum + nl;
         FH_CHECK(hipMemsetAsync(s.accum, 0, (nl + nodes) * sizeof(int), h->stream));
@@ -1198,7 +577,7 @@ int fh_krylov_work::start(const std::vector<cplx>& z, const cplx* RHS, cplx* X, 
     }
     va.X = Xk;
     // FH_NO_LAZY_START=1: materialise R and P of a shared start as before.  Read per call (the tests flip it).
-    lazy = shared_start && fused && h->kind == 2 && !h->csr.is_complex && !fh_knob::no_lazy_start() &&
+    lazy = shared_start && fused && h->kind == FH_KIND_CSR && !h->csr.is_complex && !fh_knob::no_lazy_start() &&
            (!opt.shared_lambda || opt.shared_lambda_host) && !fh_knob::lds_spmm();
     if (lazy) {
         if ((rc = fh_upload_coefs(h, "kry_fscale", fh_start_factors(z, nodes, m, ld, opt.shared_lambda_host), &dfs))) return rc;
@@ -1282,7 +661,7 @@ void fh_krylov_work::cocg_fused_step(int it) {
 // Batched BiCGStab (method 0) or COCG (method 1) on `nodes` panels, in five phases: allocate, start, iterate, finish, collect.
 int fh_krylov(feasthip_ctx* h, int method, int prec, int ld, int m, int nodes, const std::vector<cplx>& z,
               const cplx* RHS, cplx* X, size_t stride, fh_solve_result& res, const fh_krylov_opts& opt) {
-    if (h->kind != 2) prec = 64;          // the dense operator kernel takes complex128 panels only
+    if (h->kind != FH_KIND_CSR) prec = 64;          // the dense operator kernel takes complex128 panels only
     fh_krylov_work k{h, res};
     k.method = method; k.prec = prec; k.ld = ld; k.m = m; k.nodes = nodes; k.N = (int)fh_N(h); k.panel = (size_t)k.N * ld;
     k.sum_acc = (method == 1 && opt.wnode) ? opt.sum_acc : nullptr;
@@ -1568,7 +947,7 @@ int fh_gmres(feasthip_ctx* h, int ld, int m, int nodes_all, const std::vector<cp
         ga.inv = sd; ga.r0norm = sd + nl; ga.target = sd + 2 * nl; ga.rnorm = sd + 3 * nl;
         ga.active = si; ga.iters = si + nl; ga.status = si + 2 * nl; ga.kdim = si + 3 * nl; ga.node_active = si + 4 * nl;
         FH_CHECK(hipMemsetAsync(sc, 0, hsz * sizeof(cplx), h->stream));
-        if (h->kind == 4 || h->kind == 5) {     // operator handle: the callback sees whole basis panels, padding columns included
+        if (fh_callback_products(h)) {     // operator handle: the callback sees whole basis panels, padding columns included
             FH_CHECK(hipMemsetAsync(V, 0, (size_t)nodes * (mr + 1) * panel * sizeof(cplx), h->stream));
             FH_CHECK(hipMemsetAsync(W, 0, (size_t)nodes * panel * sizeof(cplx), h->stream));
         }
@@ -1643,7 +1022,7 @@ int fh_gmres(feasthip_ctx* h, int ld, int m, int nodes_all, const std::vector<cp
     return 0;
 }
 
-static bool fh_is_complex_input(feasthip_ctx* h) { return h->kind == 2 ? h->csr.is_complex != 0 : h->dense.is_complex != 0; }
+static bool fh_is_complex_input(feasthip_ctx* h) { return h->kind == FH_KIND_CSR ? h->csr.is_complex != 0 : h->dense.is_complex != 0; }
 
 // ---------------------------------------------------------------------------------------
 // contour sweep
@@ -1746,7 +1125,7 @@ static int fh_split_nodes(feasthip_ctx* h, std::vector<int>& order, int* nd) {
     order.insert(order.end(), direct.begin(), direct.end());
     if (!*nd) return 0;
     const char* why = nullptr;
-    if (h->kind != 2) why = "a dense problem has no sparse direct solver";
+    if (h->kind != FH_KIND_CSR) why = "a dense problem has no sparse direct solver";
     else if (h->solver != FEASTHIP_SOLVER_COCG && h->solver != FEASTHIP_SOLVER_BICGSTAB) why = "the handle's solver must be COCG or BICGSTAB (GMRES sweeps do not mix)";
     else if (h->factor_precision != 64) why = "factor_precision = 32 is not supported";
     else if (*nd > FH_NODE_FINISH_MAX) why = "more than 64 direct nodes on one rank";
@@ -1771,7 +1150,7 @@ struct fh_panel_sweep {
 // complex64 factors.  Y_e = S_e^-1 Rhs, sr.status per node, sr.max_rel_res the worst refined residual.
 static int fh_panel_direct(feasthip_ctx* h, const fh_panel_sweep& g, int64_t* nfact, fh_solve_result& sr) {
     const bool banded = h->solver == FEASTHIP_SOLVER_BANDED;
-    if (!banded && h->kind != 1) { h->last_error = "solver LU requires a dense matrix (sparse direct factorisation is not provided; use BICGSTAB)"; return FEASTHIP_ERROR_FPM; }
+    if (!banded && h->kind != FH_KIND_DENSE) { h->last_error = "solver LU requires a dense matrix (sparse direct factorisation is not provided; use BICGSTAB)"; return FEASTHIP_ERROR_FPM; }
     sr.status.assign(g.nodes, 0);
     if (h->factor_precision == 32)
         return fh_dense_lu_refined(h, g.ld, g.m, g.nodes, g.z, g.Rhs, g.Y, g.panel, sr.status, nfact, false, &sr.max_rel_res, banded);
@@ -1836,12 +1215,12 @@ static int fh_panel_krylov(feasthip_ctx* h, fh_panel_sweep& g, bool want_moments
     }
     // Shifted COCG (feasthip_set_solver kind SHIFTED_COCG): a CSR operator with real values and B = I, fp64 panels, sum mode
     // from a shared start, no direct nodes.  Anything else is the per-node sweep.
-    const bool shifted = h->shifted && g.sum_shared && opt.shared_src && nk && !nd && h->kind == 2 && h->csr.b_identity &&
+    const bool shifted = h->shifted && g.sum_shared && opt.shared_src && nk && !nd && h->kind == FH_KIND_CSR && h->csr.b_identity &&
                          !h->csr.is_complex;
     h->shift_panels += 1;
     // Block COCG (kind BLOCK_COCG): a CSR operator with real values (any real symmetric B), fp64 panels, sum mode from a
     // shared start, no direct nodes.  Anything else is the per-node sweep.
-    const bool block = h->block && g.sum_shared && opt.shared_src && nk && !nd && h->kind == 2 && !h->csr.is_complex;
+    const bool block = h->block && g.sum_shared && opt.shared_src && nk && !nd && h->kind == FH_KIND_CSR && !h->csr.is_complex;
     h->block_panels += 1;
     if (block) {
         int smax = 0, brk = 0, ran = 0;
@@ -2130,9 +1509,18 @@ struct fh_resident_sweep {
     const cplx* Q; const cplx* eigres; cplx* P; int ld;
 };
 
+// While a sweep runs, the handle's column mask (feasthip_set_column_mask) is live.  The mask is one-shot: it applies to this
+// sweep only and never leaks into later calls (shifted_solve / RCI jobs on the same handle), whatever the outcome of the sweep.
+struct fh_mask_live {
+    feasthip_ctx* h;
+    explicit fh_mask_live(feasthip_ctx* h_) : h(h_) { h->mask_live = 1; }
+    ~fh_mask_live() { h->mask_live = 0; h->col_mask.clear(); }
+};
+
 static int fh_contour_apply_impl(feasthip_ctx* h, int64_t m64, const cplx* dQ, const double* ritz_lambda,
                                  cplx* dQproj, cplx* dzAq, cplx* dzSq, int* node_status, feasthip_stats* stats,
                                  const fh_resident_sweep* rs = nullptr) {
+    fh_mask_live live(h);
     h->shift_panels = h->shift_used = h->shift_seed_iters = 0; h->shift_seed = -1;      // feasthip_last_shifted_sweep
     h->block_panels = h->block_used = h->block_steps_max = h->block_breakdowns = h->block_passes = 0;   // feasthip_last_block_sweep
     const int nr = fh_comm_nranks(h);
@@ -2297,17 +1685,11 @@ extern "C" int feasthip_contour_apply_dev(feasthip_handle h, int64_t m, const vo
     if (!h) return FEASTHIP_ERROR_INTERNAL;
     if (!dQ || !dQproj) { h->last_error = "contour_apply: null Q/Qproj"; return FEASTHIP_ERROR_INTERNAL; }
     if (int arc = fh_check_adjoint(h, "contour_apply", (dzAq || dzSq) ? "the moment matrices zAq / zSq must be NULL" : nullptr)) return arc;
-    // the column mask is one-shot: it applies to this sweep only and never leaks into later calls
-    // (shifted_solve / RCI jobs on the same handle), whatever the outcome of the sweep
-    h->mask_live = 1;
-    const int rc = fh_contour_apply_impl(h, m, (const cplx*)dQ, ritz_lambda_host, (cplx*)dQproj, (cplx*)dzAq, (cplx*)dzSq, node_status, stats);
-    h->mask_live = 0;
-    h->col_mask.clear();
-    return rc;
+    return fh_contour_apply_impl(h, m, (const cplx*)dQ, ritz_lambda_host, (cplx*)dQproj, (cplx*)dzAq, (cplx*)dzSq, node_status, stats);
 }
 
 // host-pointer wrapper helpers
-static int fh_stage_in(feasthip_ctx* h, const char* name, const void* host, size_t bytes, void** dev) {
+int fh_stage_in(feasthip_ctx* h, const char* name, const void* host, size_t bytes, void** dev) {
     int rc = fh_get_buf(h, name, bytes, dev);
     if (rc) return rc;
     FH_CHECK(hipMemcpyAsync(*dev, host, bytes, hipMemcpyHostToDevice, h->stream));
@@ -2327,11 +1709,7 @@ extern "C" int feasthip_contour_apply(feasthip_handle h, int64_t m, const void* 
     if ((rc = fh_get_buf(h, "host_Qproj", nb, &dP))) return rc;
     if (zAq && (rc = fh_get_buf(h, "host_zAq", mb, &dA))) return rc;
     if (zSq && (rc = fh_get_buf(h, "host_zSq", mb, &dS))) return rc;
-    h->mask_live = 1;
-    rc = fh_contour_apply_impl(h, m, (const cplx*)dQ, ritz_lambda, (cplx*)dP, (cplx*)dA, (cplx*)dS, node_status, stats);
-    h->mask_live = 0;
-    h->col_mask.clear();
-    if (rc) return rc;
+    if ((rc = fh_contour_apply_impl(h, m, (const cplx*)dQ, ritz_lambda, (cplx*)dP, (cplx*)dA, (cplx*)dS, node_status, stats))) return rc;
     FH_CHECK(hipMemcpy(Qproj, dP, nb, hipMemcpyDeviceToHost));
     if (zAq) FH_CHECK(hipMemcpy(zAq, dA, mb, hipMemcpyDeviceToHost));
     if (zSq) FH_CHECK(hipMemcpy(zSq, dS, mb, hipMemcpyDeviceToHost));
@@ -2378,11 +1756,7 @@ extern "C" int feasthip_estimate_count(feasthip_handle h, int64_t m, uint64_t se
     fh_launch_rademacher(seed, 0, N, m, dV, N, h->stream);
     FH_CHECK(hipGetLastError());
     // the sweep of feasthip_contour_apply_dev from a zero start: Q_proj = rho V, summed over the ranks of a communicator
-    h->mask_live = 1;
-    rc = fh_contour_apply_impl(h, m, dV, nullptr, dP, nullptr, nullptr, node_status, stats);
-    h->mask_live = 0;
-    h->col_mask.clear();
-    if (rc) return rc;
+    if ((rc = fh_contour_apply_impl(h, m, dV, nullptr, dP, nullptr, nullptr, node_status, stats))) return rc;
     fh_launch_trace_dots(dP, N, m, N, seed, h->real_projection, dW, dT, h->stream);
     FH_CHECK(hipGetLastError());
     FH_CHECK(hipMemcpyAsync(samples, dT, (size_t)m * 2 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
@@ -2391,767 +1765,7 @@ extern "C" int feasthip_estimate_count(feasthip_handle h, int64_t m, uint64_t se
     return 0;
 }
 
-// ---------------------------------------------------------------------------------------
-// orthonormalisation (a9)
-// ---------------------------------------------------------------------------------------
-// what the last orthonormalisation did (feasthip_last_ortho).  A call over several panels (fh_ortho_wide) adds up stages,
-// fall-backs and rank; perm / rdiag are the last panel's.  The method reported for such a call is the staged path if any
-// panel took it, else the Gram-Schmidt if any did, else the Cholesky-QR fast path.
-static void fh_ortho_note(feasthip_ctx* h, int used, int stages, int fell_back, int rank, const int* perm, const double* rdiag) {
-    auto& o = h->ortho_last;
-    auto weight = [](int u) { return u == FEASTHIP_ORTHO_CHOLQR_RR ? 2 : u == FEASTHIP_ORTHO_MGS ? 1 : 0; };
-    if (o.panels == 0 || weight(used) > weight(o.used)) o.used = used;
-    o.panels += 1;
-    o.stages += stages; o.fell_back += fell_back; o.rank += rank;
-    o.perm.assign(perm, perm + rank);
-    if (rdiag) o.rdiag.assign(rdiag, rdiag + rank);
-    else o.rdiag.assign(rank, 0.0);
-}
-static void fh_ortho_note_reset(feasthip_ctx* h) {
-    h->ortho_last.panels = h->ortho_last.used = h->ortho_last.stages = h->ortho_last.fell_back = h->ortho_last.rank = 0;
-    h->ortho_last.perm.clear(); h->ortho_last.rdiag.clear();
-}
-
-// The staged rank-revealing Cholesky-QR (FEASTHIP_ORTHO_CHOLQR_RR) on a panel that fh_cholqr::accept rejected.  Per stage:
-//   G = W^H W of the working copy W -> k_pchol_stage: the pivots this stage may judge, R^-1 with the permutation folded in
-//   T = W R^-1 (the accepted columns, first pass); from the second stage on T -= K (K^H T) against the columns K kept so far
-//   G = T^H T -> k_pchol_stage (refine): second pass, T2 = T R2^-1 lands in the columns [rank, rank + accepted) of a zero panel
-//   Out += T2;  twice:  W -= T2 (T2^H W)
-// All of it is queued for a fixed number of stages; the device decides how many run (the launches of a stage past the
-// decision return at once) and the host reads the state once.  The Gram product, the panel product and the column update
-// are the existing kernels (k_gram_mfma, k_small_matmul_mfma, k_axpy_cols) with a skip word: fusing gather, product and
-// subtraction would save two passes over W per stage, which is not where the time of a 2-3 stage call goes (the latency
-// chain of k_pchol_stage and the launch count are).  *staged = false: a non-finite Gram matrix, a stage that accepted
-// nothing, a second pass that broke down, or no decision within FH_RR_MAX_STAGES; X is untouched in every case.
-// colmax: the largest column norm of X (accept() has it).  The working copy is scaled by the power of two that brings it
-// into [1, 2): exact, and the Gram matrices of the later stages -- squares of what is left after the projections -- stay
-// clear of the denormal range for panels of any magnitude.
-#define FH_RR_MAX_STAGES 6
-#define FH_RR_WINDOW 1e-10
-static int fh_ortho_staged(feasthip_ctx* h, int m, int ld, const cplx* X, cplx* Out, double rank_tol, double ref_scale, int big_dim,
-                           double colmax, int* rank, bool* staged) {
-    const int N = (int)fh_N(h);
-    const size_t panel = (size_t)N * ld;
-    int rc;
-    *staged = false;
-    cplx *W, *T, *T2, *gw, *G, *dR, *C;
-    if ((rc = fh_buf(h, "rr_W", panel, &W))) return rc;
-    if ((rc = fh_buf(h, "rr_T", panel, &T))) return rc;
-    if ((rc = fh_buf(h, "rr_T2", panel, &T2))) return rc;
-    if ((rc = fh_buf(h, "gram_work", fh_gram_work_elems(ld), &gw))) return rc;
-    if ((rc = fh_buf(h, "gram_G", (size_t)ld * ld, &G))) return rc;
-    if ((rc = fh_buf(h, "or_Rinv", (size_t)ld * ld, &dR))) return rc;
-    if ((rc = fh_buf(h, "rr_C", (size_t)ld * ld, &C))) return rc;
-    int* ist;
-    double* dst;
-    if ((rc = fh_buf(h, "rr_istate", FH_RR_PERM + FH_MAX_LD, &ist))) return rc;
-    if ((rc = fh_buf(h, "rr_dstate", 2 + FH_MAX_LD, &dst))) return rc;
-    std::vector<cplx> ones(ld, cmake(1, 0)), mones(ld, cmake(-1, 0));
-    cplx *done, *dmone;
-    if ((rc = fh_upload_coefs(h, "rr_one", ones, &done))) return rc;
-    if ((rc = fh_upload_coefs(h, "rr_mone", mones, &dmone))) return rc;
-    const double eps = 2.220446049250313e-16;
-    const double big = (double)std::max(N, std::max(big_dim, m));
-    const double thr = std::max(rank_tol, eps * big);                     // the threshold of k_mgs_pick
-    const double scale = colmax > 0.0 && std::isfinite(colmax) ? std::ldexp(1.0, -std::ilogb(colmax)) : 1.0;
-    std::vector<cplx> scl(ld, cmake(scale, 0));
-    cplx* dscale;
-    if ((rc = fh_upload_coefs(h, "rr_scale", scl, &dscale))) return rc;
-    const int* skip = ist + FH_RR_SKIP;
-    const int* decided = ist + FH_RR_DONE;
-    hipStream_t st = h->stream;
-    fh_prof_begin(h, "ortho");
-    FH_CHECK(hipMemcpyAsync(W, X, panel * sizeof(cplx), hipMemcpyDeviceToDevice, st));
-    if (scale != 1.0) fh_launch_scale_cols(W, dscale, N, ld, st);
-    FH_CHECK(hipMemsetAsync(Out, 0, panel * sizeof(cplx), st));
-    fh_launch_rr_init(ist, dst, ld, st);
-    for (int s = 0; s < FH_RR_MAX_STAGES; ++s) {
-        fh_launch_gram(W, W, N, ld, 0, gw, G, st, decided);
-        fh_launch_pchol_stage(G, m, ld, 0, FH_RR_WINDOW, thr, ref_scale * scale, ist, dst, dR, st);
-        fh_launch_small_matmul(W, dR, N, ld, T, st, skip);
-        if (s > 0) {
-            fh_launch_gram(Out, T, N, ld, 0, gw, C, st, skip);
-            fh_launch_small_matmul(Out, C, N, ld, T2, st, skip);
-            fh_launch_axpy_cols(T, T2, done, N, ld, st, skip);              // T -= K (K^H T)
-        }
-        fh_launch_gram(T, T, N, ld, 0, gw, G, st, skip);
-        fh_launch_pchol_stage(G, m, ld, 1, 0.0, thr, ref_scale * scale, ist, dst, dR, st);
-        fh_launch_small_matmul(T, dR, N, ld, T2, st, skip);
-        fh_launch_axpy_cols(Out, T2, dmone, N, ld, st, skip);               // Out += T2
-        for (int pass = 0; pass < 2; ++pass) {
-            fh_launch_gram(T2, W, N, ld, 0, gw, C, st, decided);
-            fh_launch_small_matmul(T2, C, N, ld, T, st, decided);
-            fh_launch_axpy_cols(W, T, done, N, ld, st, decided);            // W -= T2 (T2^H W)
-        }
-    }
-    fh_prof_end(h);
-    int hst[FH_RR_PERM + FH_MAX_LD];
-    double hds[2 + FH_MAX_LD];
-    FH_CHECK(hipMemcpyAsync(hst, ist, (FH_RR_PERM + ld) * sizeof(int), hipMemcpyDeviceToHost, st));
-    FH_CHECK(hipMemcpyAsync(hds, dst, (2 + ld) * sizeof(double), hipMemcpyDeviceToHost, st));
-    FH_CHECK(hipStreamSynchronize(st));
-    const int r = hst[FH_RR_RANK];
-    if (hst[FH_RR_FAIL] || !hst[FH_RR_DONE] || r < 0 || r > m) return 0;
-    *rank = r;
-    *staged = true;
-    for (int k = 0; k < r; ++k) hds[2 + k] /= scale;
-    fh_ortho_note(h, FEASTHIP_ORTHO_CHOLQR_RR, hst[FH_RR_STAGES], 0, r, hst + FH_RR_PERM, hds + 2);
-    return 0;
-}
-
-// Rank-revealing orthonormalisation of the m (<= ld) columns of panel X.  On success *res is the
-// panel (X or Out) whose first *rank columns hold the basis.  ref_scale > 0 / big_dim: X is a
-// block of a wider matrix (see k_mgs_pick).
-static int fh_ortho_panel(feasthip_ctx* h, int m, int ld, cplx* X, cplx* Out, double rank_tol, double ref_scale,
-                          int big_dim, int* rank, cplx** res) {
-    const int N = (int)fh_N(h);
-    int rc;
-    cplx *work, *coef;
-    int* istate;
-    double* dstate;
-    if ((rc = fh_buf(h, "or_work", (size_t)256 * ld, &work))) return rc;
-    if ((rc = fh_buf(h, "or_istate", 4 + FH_MAX_LD, &istate))) return rc;
-    if ((rc = fh_buf(h, "or_dstate", 2 + FH_MAX_LD, &dstate))) return rc;
-    if ((rc = fh_buf(h, "or_coef", FH_MAX_LD, &coef))) return rc;
-    int fell_back = 0;
-    // Fast path (Cholesky-QR, one or two passes) when the panel is far from rank deficient (fh_cholqr::accept: the pivoted
-    // Cholesky pivots of the Gram matrix are the squared R_kk of the pivoted QR).  Otherwise fall through to the
-    // rank-revealing pivoted Gram-Schmidt.  The Rayleigh-Ritz step that follows uses Q^H B Q anyway, so one pass suffices
-    // when it is orthonormal to 1e-14.
-    if (!fh_knob::no_cholqr()) {
-        cplx *gw, *G, *dR;
-        if ((rc = fh_buf(h, "gram_work", fh_gram_work_elems(ld), &gw))) return rc;
-        if ((rc = fh_buf(h, "gram_G", (size_t)ld * ld, &G))) return rc;
-        if ((rc = fh_buf(h, "or_Rinv", (size_t)ld * ld, &dR))) return rc;
-        std::vector<cplx> Gh((size_t)ld * ld), Rinv;
-        std::vector<double> dcol;
-        bool ok = true;
-        cplx* src = X;
-        cplx* dst = Out;
-        int npass = 2;
-        const bool always_two = fh_knob::cholqr_two_pass();
-        for (int pass = 0; pass < npass && ok; ++pass) {
-            fh_prof_begin(h, "gram");
-            fh_launch_gram(src, src, N, ld, 0, gw, G, h->stream);
-            fh_prof_end(h);
-            FH_CHECK(hipMemcpyAsync(Gh.data(), G, Gh.size() * sizeof(cplx), hipMemcpyDeviceToHost, h->stream));
-            FH_CHECK(hipStreamSynchronize(h->stream));
-            if (pass == 0) {         // equilibrates Gh: G = D G' D, D = diag(dcol)
-                const fh_cholqr::Plan plan = fh_cholqr::accept(Gh, m, ld, ref_scale, rank_tol, always_two, dcol);
-                if (plan == fh_cholqr::Plan::reject) { ok = false; break; }
-                if (plan == fh_cholqr::Plan::one_pass) npass = 1;
-            }
-            if (!fh_cholqr::gram_upper_inverse(Gh, m, ld, Rinv)) { ok = false; break; }
-            if (pass == 0)       // R = R' D  =>  R^-1 = D^-1 R'^-1: scale row i by 1/d_i
-                for (int j = 0; j < m; ++j)
-                    for (int i = 0; i < m; ++i) Rinv[(size_t)j * ld + i] = cscale(Rinv[(size_t)j * ld + i], 1.0 / dcol[i]);
-            FH_CHECK(hipMemcpyAsync(dR, Rinv.data(), Rinv.size() * sizeof(cplx), hipMemcpyHostToDevice, h->stream));
-            fh_prof_begin(h, "ortho");
-            fh_launch_small_matmul(src, dR, N, ld, dst, h->stream);
-            fh_prof_end(h);
-            FH_CHECK(hipStreamSynchronize(h->stream));     // Rinv (host vector) is reused
-            std::swap(src, dst);
-        }
-        if (ok) {       // src after the swaps: X after two passes, Out after one
-            *rank = m;
-            *res = src;
-            std::vector<int> ident(m);
-            for (int j = 0; j < m; ++j) ident[j] = j;
-            fh_ortho_note(h, FEASTHIP_ORTHO_USED_CHOLQR, 0, 0, m, ident.data(), nullptr);
-            return 0;
-        }
-        // a failure happens before the pass writes its destination: X still holds the input
-        // (pass 0 writes Out, pass 1 would have written X)
-        if (h->ortho_method == FEASTHIP_ORTHO_CHOLQR_RR) {
-            bool staged = false;
-            double colmax = 0.0;
-            for (double dj : dcol) colmax = std::max(colmax, dj);
-            if ((rc = fh_ortho_staged(h, m, ld, X, Out, rank_tol, ref_scale, big_dim, colmax, rank, &staged))) return rc;
-            if (staged) { *res = Out; return 0; }
-            fell_back = 1;                     // X is untouched: the Gram-Schmidt decides as it would have
-        }
-    }
-    fh_mgs_args a;
-    a.X = X; a.N = N; a.ld = ld; a.m = m; a.istate = istate; a.dstate = dstate; a.coef = coef; a.work = work;
-    a.rank_tol = rank_tol; a.ref_scale = ref_scale; a.big_dim = big_dim;
-    fh_prof_begin(h, "ortho");
-    fh_mgs_run(a, h->stream);
-    fh_prof_end(h);
-    int hst[4 + FH_MAX_LD];
-    FH_CHECK(hipMemcpyAsync(hst, istate, (4 + ld) * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    FH_CHECK(hipStreamSynchronize(h->stream));
-    int r = hst[2] ? hst[1] : hst[0];
-    if (r < 0) r = 0;
-    if (r > m) r = m;
-    *rank = r;
-    fh_launch_gather_cols(X, istate + 4, r, N, ld, Out, h->stream);
-    *res = Out;
-    fh_ortho_note(h, FEASTHIP_ORTHO_MGS, 0, fell_back, r, hst + 4, nullptr);
-    return 0;
-}
-
-// m > 64: block Gram-Schmidt over 64-column panels.  Panel j is projected twice against the kept
-// columns (C = K^H X_j on the MFMA Gram kernel, X_j -= K C), then orthonormalised by fh_ortho_panel
-// with the rank threshold tied to the largest column norm of the WHOLE matrix -- the R_11 of the
-// reference's pivoted QR (src/core/feast_aux.jl:113-124).  Kept columns are packed to the front of
-// Q.  Pivoting is per panel, not global: for a full-rank input the basis spans the same space.
-static int fh_ortho_wide(feasthip_ctx* h, int m, cplx* dQ, double rank_tol, int* rank) {
-    const int N = (int)fh_N(h), ld = FH_MAX_LD;
-    const size_t panel = (size_t)N * ld;
-    int rc;
-    cplx *X, *Out, *K, *T, *gw, *C, *part, *ddots;
-    if ((rc = fh_buf(h, "or_X", panel, &X))) return rc;
-    if ((rc = fh_buf(h, "or_out", panel, &Out))) return rc;
-    if ((rc = fh_buf(h, "ow_K", panel, &K))) return rc;
-    if ((rc = fh_buf(h, "ow_T", panel, &T))) return rc;
-    if ((rc = fh_buf(h, "gram_work", fh_gram_work_elems(ld), &gw))) return rc;
-    if ((rc = fh_buf(h, "ow_C", (size_t)ld * ld, &C))) return rc;
-    if ((rc = fh_buf(h, "ow_part", (size_t)fh_vec_nblk(N, ld) * ld, &part))) return rc;
-    if ((rc = fh_buf(h, "ow_dots", (size_t)ld, &ddots))) return rc;
-    std::vector<cplx> ones(ld, cmake(1, 0));
-    cplx* done;
-    if ((rc = fh_upload_coefs(h, "ow_one", ones, &done))) return rc;
-    const int npan = (m + ld - 1) / ld;
-    // largest column norm of the whole matrix
-    double ref = 0.0;
-    std::vector<cplx> dots(ld);
-    for (int j = 0; j < npan; ++j) {
-        const int mj = std::min(ld, m - j * ld);
-        fh_launch_to_panel(dQ + (size_t)j * ld * N, N, N, mj, X, ld, h->stream, fh_perm(h));
-        fh_launch_dot_cols(X, X, N, ld, part, ddots, h->stream);
-        FH_CHECK(hipMemcpyAsync(dots.data(), ddots, ld * sizeof(cplx), hipMemcpyDeviceToHost, h->stream));
-        FH_CHECK(hipStreamSynchronize(h->stream));
-        for (int c = 0; c < mj; ++c) if (dots[c].x > ref * ref) ref = std::sqrt(dots[c].x);
-    }
-    int kept = 0;
-    for (int j = 0; j < npan; ++j) {
-        const int mj = std::min(ld, m - j * ld);
-        fh_launch_to_panel(dQ + (size_t)j * ld * N, N, N, mj, X, ld, h->stream, fh_perm(h));
-        for (int pass = 0; pass < 2; ++pass) {
-            for (int k0 = 0; k0 < kept; k0 += ld) {
-                const int kw = std::min(ld, kept - k0);
-                fh_launch_to_panel(dQ + (size_t)k0 * N, N, N, kw, K, ld, h->stream, fh_perm(h));
-                fh_prof_begin(h, "gram");
-                fh_launch_gram(K, X, N, ld, 0, gw, C, h->stream);        // C = K^H X
-                fh_prof_end(h);
-                fh_prof_begin(h, "ortho");
-                fh_launch_small_matmul(K, C, N, ld, T, h->stream);       // T = K C
-                fh_launch_axpy_cols(X, T, done, N, ld, h->stream);       // X -= T
-                fh_prof_end(h);
-            }
-        }
-        int rj = 0;
-        cplx* res = nullptr;
-        if ((rc = fh_ortho_panel(h, mj, ld, X, Out, rank_tol, ref, m, &rj, &res))) return rc;
-        if (rj > 0) fh_launch_from_panel(res, ld, N, rj, dQ + (size_t)kept * N, N, h->stream, fh_perm(h));
-        kept += rj;
-    }
-    *rank = kept;
-    FH_CHECK(hipStreamSynchronize(h->stream));
-    return 0;
-}
-
-// the body of feasthip_orthonormalize_dev / feasthip_poly_orthonormalize_dev once the handle and m are checked
-static int fh_orthonormalize_checked(feasthip_ctx* h, int64_t m64, void* dQ, double rank_tol, int* rank) {
-    int rc;
-    FH_CHECK(hipSetDevice(h->device));
-    fh_ortho_note_reset(h);
-    if (m64 > FH_MAX_LD) {
-        rc = fh_ortho_wide(h, (int)m64, (cplx*)dQ, rank_tol, rank);
-        fh_prof_collect(h);
-        return rc;
-    }
-    const int m = (int)m64, ld = fh_pick_ld(m), N = (int)fh_N(h);
-    const size_t panel = (size_t)N * ld;
-    cplx *X, *Out;
-    if ((rc = fh_buf(h, "or_X", panel, &X))) return rc;
-    if ((rc = fh_buf(h, "or_out", panel, &Out))) return rc;
-    fh_launch_to_panel((const cplx*)dQ, N, N, m, X, ld, h->stream, fh_perm(h));
-    cplx* res = nullptr;
-    if ((rc = fh_ortho_panel(h, m, ld, X, Out, rank_tol, 0.0, m, rank, &res))) return rc;
-    fh_launch_from_panel(res, ld, N, m, (cplx*)dQ, N, h->stream, fh_perm(h));
-    FH_CHECK(hipStreamSynchronize(h->stream));
-    fh_prof_collect(h);
-    FH_CHECK(hipGetLastError());       // launch-configuration errors do not surface through the stream sync
-    return 0;
-}
-
-extern "C" int feasthip_orthonormalize_dev(feasthip_handle h, int64_t m64, void* dQ, double rank_tol, int* rank) {
-    int rc = fh_check_problem(h, m64, 1);
-    if (rc) return rc;
-    if (!dQ || !rank) { h->last_error = "orthonormalize: null argument"; return FEASTHIP_ERROR_INTERNAL; }
-    return fh_orthonormalize_checked(h, m64, dQ, rank_tol, rank);
-}
-
-// The same orthonormalisation for the N x m panels of a polynomial handle (the projected method's subspace lives in the
-// N-dimensional space; feasthip_orthonormalize_dev keeps refusing such a handle, like every pencil entry point).
-// unit_columns: every column is scaled to unit length first (a column of zero length is left alone), so that the rank rule
-// measures directions, not the lengths the contour sum happened to give them.
-extern "C" int feasthip_poly_orthonormalize_dev(feasthip_handle h, int64_t m64, void* dQ, int unit_columns, double rank_tol, int* rank) {
-    if (!h) return FEASTHIP_ERROR_INTERNAL;
-    if (h->poisoned) { h->last_error = "handle poisoned by an earlier device failure: destroy it"; return FEASTHIP_ERROR_INTERNAL; }
-    if (h->kind == 4) { h->last_error = "feasthip_poly_orthonormalize_dev: an operator handle (feasthip_set_operator) has no polynomial form: it takes feasthip_orthonormalize_dev and the other pencil entry points, under the Krylov solvers FEASTHIP_SOLVER_BICGSTAB, _COCG or _GMRES"; return FEASTHIP_ERROR_FPM; }
-    if (h->kind != 3 && h->kind != 5) { h->last_error = "feasthip_poly_orthonormalize_dev: needs a polynomial handle (feasthip_set_polynomial); a dense or CSR handle takes feasthip_orthonormalize_dev"; return FEASTHIP_ERROR_FPM; }
-    if (m64 <= 0 || m64 > fh_N(h)) { h->last_error = "feasthip_poly_orthonormalize_dev: block width m must satisfy 1 <= m <= N"; return FEASTHIP_ERROR_M0; }
-    if (!dQ || !rank) { h->last_error = "feasthip_poly_orthonormalize_dev: null argument"; return FEASTHIP_ERROR_INTERNAL; }
-    if (unit_columns) {
-        FH_CHECK(hipSetDevice(h->device));
-        const int N = (int)fh_N(h);
-        int rc;
-        for (int64_t c0 = 0; c0 < m64; c0 += FH_MAX_LD) {
-            const int m = (int)std::min<int64_t>(FH_MAX_LD, m64 - c0), ld = fh_pick_ld(m);
-            cplx *X, *part, *ddots;
-            if ((rc = fh_buf(h, "po_X", (size_t)N * ld, &X))) return rc;
-            if ((rc = fh_buf(h, "po_part", (size_t)fh_vec_nblk(N, ld) * ld, &part))) return rc;
-            if ((rc = fh_buf(h, "po_dots", (size_t)ld, &ddots))) return rc;
-            fh_launch_to_panel((cplx*)dQ + (size_t)c0 * N, N, N, m, X, ld, h->stream);
-            fh_launch_dot_cols(X, X, N, ld, part, ddots, h->stream);
-            fh_launch_normalize_cols(X, ddots, N, ld, m, h->stream);
-            fh_launch_from_panel(X, ld, N, m, (cplx*)dQ + (size_t)c0 * N, N, h->stream);
-        }
-    }
-    return fh_orthonormalize_checked(h, m64, dQ, rank_tol, rank);
-}
-
-extern "C" int feasthip_orthonormalize(feasthip_handle h, int64_t m, void* Q, double rank_tol, int* rank) {
-    int rc = fh_check_problem(h, m, 1);
-    if (rc) return rc;
-    if (!Q || !rank) { h->last_error = "orthonormalize: null argument"; return FEASTHIP_ERROR_INTERNAL; }
-    FH_CHECK(hipSetDevice(h->device));
-    const size_t nb = (size_t)fh_N(h) * m * sizeof(cplx);
-    void* dQ;
-    if ((rc = fh_stage_in(h, "host_Q", Q, nb, &dQ))) return rc;
-    rc = feasthip_orthonormalize_dev(h, m, dQ, rank_tol, rank);
-    if (rc) return rc;
-    FH_CHECK(hipMemcpy(Q, dQ, nb, hipMemcpyDeviceToHost));
-    return 0;
-}
-
-extern "C" int feasthip_set_ortho_method(feasthip_handle h, int method) {
-    if (!h) return FEASTHIP_ERROR_INTERNAL;
-    if (method != FEASTHIP_ORTHO_MGS && method != FEASTHIP_ORTHO_CHOLQR_RR) {
-        h->last_error = "set_ortho_method: unknown method";
-        return FEASTHIP_ERROR_FPM;
-    }
-    h->ortho_method = method;
-    return 0;
-}
-
-extern "C" int feasthip_last_ortho(feasthip_handle h, int* method_used, int* stages, int* fell_back, int* rank, int* perm,
-                                   double* rdiag, int n) {
-    if (!h) return FEASTHIP_ERROR_INTERNAL;
-    const auto& o = h->ortho_last;
-    if (method_used) *method_used = o.used;
-    if (stages) *stages = o.stages;
-    if (fell_back) *fell_back = o.fell_back;
-    if (rank) *rank = o.rank;
-    for (int k = 0; k < n; ++k) {
-        if (perm) perm[k] = k < (int)o.perm.size() ? o.perm[k] : -1;
-        if (rdiag) rdiag[k] = k < (int)o.rdiag.size() ? o.rdiag[k] : 0.0;
-    }
-    return 0;
-}
-
-// ---------------------------------------------------------------------------------------
-// Rayleigh-Ritz projection (a10)
-// ---------------------------------------------------------------------------------------
-// While it lives the handle applies the forward operator whatever feasthip_set_adjoint says (the projections are defined
-// with A and B themselves); the switch is put back on every return path.
-struct fh_forward_scope {
-    feasthip_ctx* h; int was;
-    explicit fh_forward_scope(feasthip_ctx* h_) : h(h_), was(h_->adjoint) { h->adjoint = 0; }
-    ~fh_forward_scope() { h->adjoint = was; }
-};
-
-// What one operator-Gram step works with: the product panel W, the Gram kernel's workspace and the unit / zero coefficient
-// vectors that select A or B in the operator kernel.  The projections and the resident reduce share them by name.
-struct fh_op_gram {
-    feasthip_ctx* h; int ld;
-    cplx *W, *gw, *d1, *d0;
-    int acquire(feasthip_ctx* h_, int ld_) {
-        h = h_; ld = ld_;
-        int rc;
-        if ((rc = fh_buf(h, "pj_W", (size_t)fh_N(h) * ld, &W))) return rc;
-        if ((rc = fh_buf(h, "gram_work", fh_gram_work_elems(ld), &gw))) return rc;
-        const std::vector<cplx> one(ld, cmake(1, 0)), zero(ld, cmake(0, 0));
-        if ((rc = fh_upload_coefs(h, "pj_one", one, &d1))) return rc;
-        return fh_upload_coefs(h, "pj_zero", zero, &d0);
-    }
-    // queues W = op X on the first m columns, op = A (which 0) or B (which 1)
-    int product(int m, const cplx* X, int which) const {
-        fh_op_call oc;
-        oc.m = m;
-        oc.X = X; oc.Y = W;
-        oc.coefA = which == 0 ? d1 : d0; oc.coefB = which == 0 ? d0 : d1; oc.skip = which == 0 ? 2 : 1;
-        return fh_apply_operator(h, ld, oc) < 0 ? (int)FEASTHIP_ERROR_INTERNAL : 0;
-    }
-    // queues G = QL^H W (bilinear: QL^T W) as one launch of the "gram" profile class
-    void gram(const cplx* QL, int bilinear, cplx* G) const {
-        fh_prof_begin(h, "gram");
-        fh_launch_gram(QL, W, (int)fh_N(h), ld, bilinear, gw, G, h->stream);
-        fh_prof_end(h);
-    }
-    // the whole step, G = QL^H (op X): nothing is synchronised or downloaded; the operator's error code comes back
-    int step(int m, const cplx* QL, const cplx* X, int which, int bilinear, cplx* G) const {
-        const int rc = product(m, X, which);
-        if (!rc) gram(QL, bilinear, G);
-        return rc;
-    }
-};
-
-// out (r x r column-major, host) = the leading r x r block of Gsrc (host, leading dimension ld), scaled by 1 / (d_i d_j) when
-// d != null, its Hermitian part when asked
-static void fh_gram_to_host(const cplx* Gsrc, int ld, int r, const double* d, bool hermitian, cplx* out) {
-    for (int j = 0; j < r; ++j)
-        for (int i = 0; i < r; ++i) {
-            cplx g = Gsrc[(size_t)j * ld + i];
-            if (d) g = cscale(g, 1.0 / (d[i] * d[j]));
-            out[(size_t)j * r + i] = g;
-        }
-    if (hermitian) fh_cholqr::hermitian_part(out, r);
-}
-// out = I exactly: the B-part of an orthonormal basis when B = I (src/dense/feast_dense.jl:255-259)
-static void fh_identity_to_host(int r, cplx* out) {
-    for (int j = 0; j < r; ++j)
-        for (int i = 0; i < r; ++i) out[(size_t)j * r + i] = cmake(i == j ? 1.0 : 0.0, 0.0);
-}
-
-// res = Q_L^H op Q_R (bilinear: Q_L^T) for op = A (which 0) or B (which 1), r x r column-major on the host, by ld-column
-// panels: block (i, j) is Q_L,i^H (op Q_R,j), one operator product (fh_op_gram::product) per block column and one Gram
-// launch per block.  One download and one stream synchronisation per block: a single one for r <= ld, (r / 64)^2 of them
-// for the wide calls.
-static int fh_project_blocks(feasthip_ctx* h, int r, int ld, const cplx* dQL, const cplx* dQR, int which, int bilinear, cplx* res) {
-    const int N = (int)fh_N(h);
-    const size_t panel = (size_t)N * ld;
-    int rc;
-    cplx *Qi, *Qj, *G;
-    fh_op_gram og;
-    if ((rc = fh_buf(h, "pj_Q", panel, &Qi))) return rc;
-    if ((rc = fh_buf(h, "pj_Qj", panel, &Qj))) return rc;
-    if ((rc = fh_buf(h, "gram_G", (size_t)ld * ld, &G))) return rc;
-    if ((rc = og.acquire(h, ld))) return rc;
-    const int npan = (r + ld - 1) / ld;
-    std::vector<cplx> Gh((size_t)ld * ld);
-    for (int j = 0; j < npan; ++j) {
-        const int mj = std::min(ld, r - j * ld);
-        fh_launch_to_panel(dQR + (size_t)j * ld * N, N, N, mj, Qj, ld, h->stream, fh_perm(h));
-        if ((rc = og.product(mj, Qj, which))) return rc;
-        for (int i = 0; i < npan; ++i) {
-            const int mi = std::min(ld, r - i * ld);
-            fh_launch_to_panel(dQL + (size_t)i * ld * N, N, N, mi, Qi, ld, h->stream, fh_perm(h));
-            og.gram(Qi, bilinear, G);
-            FH_CHECK(hipMemcpyAsync(Gh.data(), G, Gh.size() * sizeof(cplx), hipMemcpyDeviceToHost, h->stream));
-            FH_CHECK(hipStreamSynchronize(h->stream));
-            for (int c2 = 0; c2 < mj; ++c2)
-                for (int c1 = 0; c1 < mi; ++c1)
-                    res[(size_t)(j * ld + c2) * r + i * ld + c1] = Gh[(size_t)c2 * ld + c1];
-        }
-    }
-    return 0;
-}
-
-extern "C" int feasthip_project_dev(feasthip_handle h, int64_t r64, const void* dQ, int bilinear, int hermitize,
-                                    void* Aq_host, void* Bq_host) {
-    const bool wide = r64 > FH_MAX_LD;                  // r > 64: 64-column panels (fh_project_blocks)
-    int rc = fh_check_problem(h, r64, wide);
-    if (rc) return rc;
-    if (!dQ || !Aq_host) { h->last_error = "project: null argument"; return FEASTHIP_ERROR_INTERNAL; }
-    FH_CHECK(hipSetDevice(h->device));
-    fh_forward_scope forward(h);
-    const int r = (int)r64, N = (int)fh_N(h);
-    const int ld = wide ? r : fh_pick_ld(r);            // leading dimension of the Gram data on the host
-    const size_t g2 = (size_t)ld * ld;
-    cplx* const out_host[2] = {(cplx*)Aq_host, (cplx*)Bq_host};
-    // variant A: Q is orthonormal and B = I, so Bq = I exactly and no product is formed for it
-    // (B = I without orthonormal Q, variant C: the operator kernel yields W = Q, so G = Q^H Q)
-    const bool b_exact = fh_b_identity(h) && hermitize && !bilinear;
-    auto produced = [&](int which) { return out_host[which] && !(which == 1 && b_exact); };
-    std::vector<cplx> Gh(2 * g2);
-    if (wide) {
-        for (int which = 0; which < 2; ++which)
-            if (produced(which) && (rc = fh_project_blocks(h, r, FH_MAX_LD, (const cplx*)dQ, (const cplx*)dQ, which, bilinear,
-                                                           Gh.data() + which * g2))) return rc;
-    } else {
-        cplx *Qp, *G;
-        fh_op_gram og;
-        if ((rc = fh_buf(h, "pj_Q", (size_t)N * ld, &Qp))) return rc;
-        fh_launch_to_panel((const cplx*)dQ, N, N, r, Qp, ld, h->stream, fh_perm(h));
-        if ((rc = og.acquire(h, ld))) return rc;
-        // both Gram matrices are queued before the ONE synchronisation that brings them to the host
-        if ((rc = fh_buf(h, "gram_G2", 2 * g2, &G))) return rc;
-        for (int which = 0; which < 2; ++which) {
-            if (!produced(which)) continue;
-            if ((rc = og.step(r, Qp, Qp, which, bilinear, G + which * g2))) return rc;
-            FH_CHECK(hipMemcpyAsync(Gh.data() + which * g2, G + which * g2, g2 * sizeof(cplx), hipMemcpyDeviceToHost, h->stream));
-        }
-        FH_CHECK(hipStreamSynchronize(h->stream));
-    }
-    for (int which = 0; which < 2; ++which) {
-        if (!out_host[which]) continue;
-        if (produced(which)) fh_gram_to_host(Gh.data() + which * g2, ld, r, nullptr, hermitize && !bilinear, out_host[which]);
-        else fh_identity_to_host(r, out_host[which]);
-    }
-    fh_prof_collect(h);
-    FH_CHECK(hipGetLastError());       // launch-configuration errors do not surface through the stream sync
-    return 0;
-}
-
-extern "C" int feasthip_project(feasthip_handle h, int64_t r, const void* Q, int bilinear, int hermitize, void* Aq, void* Bq) {
-    int rc = fh_check_problem(h, r, 1);
-    if (rc) return rc;
-    if (!Q) { h->last_error = "project: null Q"; return FEASTHIP_ERROR_INTERNAL; }
-    FH_CHECK(hipSetDevice(h->device));
-    void* dQ;
-    if ((rc = fh_stage_in(h, "host_Q", Q, (size_t)fh_N(h) * r * sizeof(cplx), &dQ))) return rc;
-    return feasthip_project_dev(h, r, dQ, bilinear, hermitize, Aq, Bq);
-}
-
-// Oblique projection of the two-sided method: Aq = Q_L^H A Q_R, Bq = Q_L^H B Q_R (Q_L^H Q_R for B = I), raw products
-// (fh_project_blocks).  Forward operator whatever the adjoint switch says.
-extern "C" int feasthip_project_pair_dev(feasthip_handle h, int64_t r64, const void* dQL, const void* dQR, void* Aq_host, void* Bq_host) {
-    int rc = fh_check_problem(h, r64, 1);
-    if (rc) return rc;
-    if (!dQL || !dQR || !Aq_host) { h->last_error = "project_pair: null argument"; return FEASTHIP_ERROR_INTERNAL; }
-    FH_CHECK(hipSetDevice(h->device));
-    fh_forward_scope forward(h);
-    const int r = (int)r64, ld = r > FH_MAX_LD ? FH_MAX_LD : fh_pick_ld(r);
-    for (int which = 0; which < 2; ++which) {
-        cplx* out_host = (cplx*)(which == 0 ? Aq_host : Bq_host);
-        if (out_host && (rc = fh_project_blocks(h, r, ld, (const cplx*)dQL, (const cplx*)dQR, which, 0, out_host))) return rc;
-    }
-    fh_prof_collect(h);
-    FH_CHECK(hipGetLastError());       // launch-configuration errors do not surface through the stream sync
-    return 0;
-}
-
-extern "C" int feasthip_project_pair(feasthip_handle h, int64_t r, const void* QL, const void* QR, void* Aq, void* Bq) {
-    int rc = fh_check_problem(h, r, 1);
-    if (rc) return rc;
-    if (!QL || !QR || !Aq) { h->last_error = "project_pair: null argument"; return FEASTHIP_ERROR_INTERNAL; }
-    FH_CHECK(hipSetDevice(h->device));
-    const size_t nb = (size_t)fh_N(h) * r * sizeof(cplx);
-    void *dL, *dR;
-    if ((rc = fh_stage_in(h, "host_Q", QL, nb, &dL))) return rc;
-    if ((rc = fh_stage_in(h, "host_X", QR, nb, &dR))) return rc;
-    return feasthip_project_pair_dev(h, r, dL, dR, Aq, Bq);
-}
-
-// ---------------------------------------------------------------------------------------
-// Ritz back-transform + residual (a12, a13)
-// ---------------------------------------------------------------------------------------
-// R = A X - B X diag(lambda) on the first ncols columns of an ld-wide panel -- A X - X diag(lambda) when use_B = 0 and B != I
-// (RCI-style residual, src/kernel/feast_kernel.jl:899-906); lambda holds (re, im) pairs.  With dots != null the squared
-// column norms are queued into the pinned ring as well: *dots is valid after the caller's next stream synchronisation
-// (fh_residual_norms).  No synchronisation of its own.
-static int fh_panel_residual(feasthip_ctx* h, int ld, int ncols, const cplx* X, cplx* R, const double* lambda, int use_B,
-                             cplx* part, cplx* ddots, const cplx** dots, std::vector<char>& fallback) {
-    const int N = (int)fh_N(h);
-    const bool lam_in_op = use_B || fh_b_identity(h);
-    std::vector<cplx> ca(ld, cmake(1, 0)), cb(ld, cmake(0, 0));
-    for (int c = 0; c < ncols; ++c) cb[c] = lam_in_op ? cmake(-lambda[2 * c], -lambda[2 * c + 1]) : cmake(0, 0);
-    int rc;
-    cplx *dca, *dcb;
-    if ((rc = fh_upload_coefs(h, "rz_coefA", ca, &dca))) return rc;
-    if ((rc = fh_upload_coefs(h, "rz_coefB", cb, &dcb))) return rc;
-    fh_op_call oc;
-    oc.m = ncols;
-    oc.X = X; oc.Y = R; oc.coefA = dca; oc.coefB = dcb; oc.skip = lam_in_op ? 0 : 2;
-    if (fh_apply_operator(h, ld, oc) < 0) return FEASTHIP_ERROR_INTERNAL;
-    if (!lam_in_op) {
-        std::vector<cplx> lam(ld, cmake(0, 0));
-        for (int c = 0; c < ncols; ++c) lam[c] = cmake(lambda[2 * c], lambda[2 * c + 1]);
-        cplx* dl;
-        if ((rc = fh_upload_coefs(h, "rz_lam", lam, &dl))) return rc;
-        fh_launch_axpy_cols(R, X, dl, N, ld, h->stream);   // R -= X diag(lam)
-    }
-    if (!dots) return 0;
-    fh_launch_dot_cols(R, R, N, ld, part, ddots, h->stream);
-    const void* slot = nullptr;
-    if ((rc = fh_download_small(h, ddots, ld * sizeof(cplx), &slot, fallback))) return rc;
-    *dots = (const cplx*)slot;
-    return 0;
-}
-
-// res_j = ||R_j|| / max(|lambda_j|, 1), j < M, from the squared norms of fh_panel_residual
-static void fh_residual_norms(const cplx* dots, const double* lambda, int M, double* res) {
-    for (int c = 0; c < M; ++c) {
-        const double la = std::hypot(lambda[2 * c], lambda[2 * c + 1]);
-        res[c] = std::sqrt(dots[c].x) / std::max(la, 1.0);
-    }
-}
-
-// The rz_* workspace of the Ritz back-transform X = Q V and its residual.  staged: the caller's column-major Q and X go
-// through panels of their own (rz_Q, rz_X, rz_R; the resident loop has its panels already); wide: the r > 64 path sums its
-// block products through rz_T.
-struct fh_ritz_ws {
-    cplx *Qp = nullptr, *Xp = nullptr, *Rp = nullptr, *Tp = nullptr, *dV = nullptr, *part = nullptr, *ddots = nullptr;
-    int acquire(feasthip_ctx* h, int ld, bool staged, bool wide) {
-        const int N = (int)fh_N(h);
-        const size_t panel = (size_t)N * ld;
-        int rc;
-        if (staged) {
-            if ((rc = fh_buf(h, "rz_Q", panel, &Qp))) return rc;
-            if ((rc = fh_buf(h, "rz_X", panel, &Xp))) return rc;
-            if ((rc = fh_buf(h, "rz_R", panel, &Rp))) return rc;
-        }
-        if (wide && (rc = fh_buf(h, "rz_T", panel, &Tp))) return rc;
-        if ((rc = fh_buf(h, "rz_V", (size_t)ld * ld, &dV))) return rc;
-        if ((rc = fh_buf(h, "rz_part", (size_t)std::max(fh_op_nblk(h, ld), fh_vec_nblk(N, ld)) * ld, &part))) return rc;
-        return fh_buf(h, "rz_dots", (size_t)ld, &ddots);
-    }
-};
-
-extern "C" int feasthip_ritz_residual_dev(feasthip_handle h, int64_t r64, const void* dQ, const void* V_host,
-                                          const double* lambda_host, int64_t M, int normalize, int use_B, void* dX,
-                                          double* res_host) {
-    const bool wide = r64 > FH_MAX_LD;
-    int rc = fh_check_adjoint(h, "ritz_residual");
-    if (rc) return rc;
-    if ((rc = fh_check_problem(h, r64, wide))) return rc;
-    if (!dQ || !V_host || !lambda_host || !dX) { h->last_error = "ritz_residual: null argument"; return FEASTHIP_ERROR_INTERNAL; }
-    if (M < 0 || M > r64) { h->last_error = "ritz_residual: M out of range"; return FEASTHIP_ERROR_M0; }
-    std::vector<double> lam_conj;
-    if (h->adjoint) {
-        // adjoint residual A^H x - conj(lambda) B^H x: the products are adjoint through fh_apply_operator, the values here
-        lam_conj.assign(lambda_host, lambda_host + 2 * (size_t)r64);
-        for (size_t c = 0; c < (size_t)r64; ++c) lam_conj[2 * c + 1] = -lam_conj[2 * c + 1];
-        lambda_host = lam_conj.data();
-    }
-    FH_CHECK(hipSetDevice(h->device));
-    const int r = (int)r64, ld = wide ? FH_MAX_LD : fh_pick_ld(r), N = (int)fh_N(h);
-    fh_ritz_ws ws;
-    if ((rc = ws.acquire(h, ld, true, wide))) return rc;
-    cplx *Qp = ws.Qp, *Xp = ws.Xp, *Rp = ws.Rp, *dV = ws.dV, *part = ws.part, *ddots = ws.ddots;
-    const cplx* Vh = (const cplx*)V_host;
-    std::vector<cplx> Vp;
-    std::vector<char> dots_fb;
-    if (wide) {
-        // r > 64: X_j = sum_i Q_i V[i-block, j-block] per 64-column output panel, then the panel
-        // goes through the same normalise / residual steps as the narrow path
-        if (dQ == dX) { h->last_error = "ritz_residual: X must not alias Q for r > 64"; return FEASTHIP_ERROR_INTERNAL; }
-        std::vector<cplx> mones(ld, cmake(-1, 0));
-        cplx* dmone;
-        if ((rc = fh_upload_coefs(h, "rz_mone", mones, &dmone))) return rc;
-        const int npan = (r + ld - 1) / ld;
-        std::vector<cplx> dots(ld);
-        for (int j = 0; j < npan; ++j) {
-            const int mj = std::min(ld, r - j * ld);
-            for (int i = 0; i < npan; ++i) {
-                const int mi = std::min(ld, r - i * ld);
-                fh_pad_block(Vh, r, r, ld, i, j, nullptr, Vp);
-                FH_CHECK(hipMemcpyAsync(dV, Vp.data(), Vp.size() * sizeof(cplx), hipMemcpyHostToDevice, h->stream));
-                fh_launch_to_panel((const cplx*)dQ + (size_t)i * ld * N, N, N, mi, Qp, ld, h->stream, fh_perm(h));
-                fh_prof_begin(h, "ritz");
-                if (i == 0) {
-                    fh_launch_small_matmul(Qp, dV, N, ld, Xp, h->stream);
-                } else {
-                    fh_launch_small_matmul(Qp, dV, N, ld, ws.Tp, h->stream);
-                    fh_launch_axpy_cols(Xp, ws.Tp, dmone, N, ld, h->stream);    // X += T
-                }
-                fh_prof_end(h);
-                FH_CHECK(hipStreamSynchronize(h->stream));                      // Vp (host) is reused
-            }
-            const int Mj = std::max(0, std::min(mj, (int)M - j * ld));          // columns of this panel below M
-            // (unlike the narrow and resident paths, which normalise on the device with fh_launch_normalize_cols, the norms
-            //  make a host round trip here; not folded in: it would change the launches and the synchronisations)
-            if (normalize && Mj > 0) {
-                fh_launch_dot_cols(Xp, Xp, N, ld, part, ddots, h->stream);
-                FH_CHECK(hipMemcpyAsync(dots.data(), ddots, ld * sizeof(cplx), hipMemcpyDeviceToHost, h->stream));
-                FH_CHECK(hipStreamSynchronize(h->stream));
-                std::vector<cplx> sc(ld, cmake(1, 0));
-                for (int c = 0; c < Mj; ++c) {
-                    double n = std::sqrt(dots[c].x);
-                    if (n > 0) sc[c] = cmake(1.0 / n, 0);
-                }
-                cplx* dsc;
-                if ((rc = fh_upload_coefs(h, "rz_scale", sc, &dsc))) return rc;
-                fh_launch_scale_cols(Xp, dsc, N, ld, h->stream);
-            }
-            fh_launch_from_panel(Xp, ld, N, mj, (cplx*)dX + (size_t)j * ld * N, N, h->stream, fh_perm(h));
-            if (Mj > 0 && res_host) {
-                const double* lam = lambda_host + 2 * (size_t)j * ld;
-                const cplx* rdots = nullptr;
-                if ((rc = fh_panel_residual(h, ld, mj, Xp, Rp, lam, use_B, part, ddots, &rdots, dots_fb))) return rc;
-                FH_CHECK(hipStreamSynchronize(h->stream));
-                fh_residual_norms(rdots, lam, Mj, res_host + (size_t)j * ld);
-            }
-        }
-        FH_CHECK(hipStreamSynchronize(h->stream));
-        fh_prof_collect(h);
-        return 0;
-    }
-    fh_pad_block(Vh, r, r, ld, 0, 0, nullptr, Vp);
-    FH_CHECK(hipMemcpyAsync(dV, Vp.data(), Vp.size() * sizeof(cplx), hipMemcpyHostToDevice, h->stream));
-    fh_launch_to_panel((const cplx*)dQ, N, N, r, Qp, ld, h->stream, fh_perm(h));
-    fh_prof_begin(h, "ritz");
-    fh_launch_small_matmul(Qp, dV, N, ld, Xp, h->stream);
-    fh_prof_end(h);
-    if (normalize && M > 0) {
-        // normalise the first M columns (src/dense/feast_dense.jl:301-305): norms and scaling stay on the device
-        fh_launch_dot_cols(Xp, Xp, N, ld, part, ddots, h->stream);
-        fh_launch_normalize_cols(Xp, ddots, N, ld, (int)M, h->stream);
-    }
-    fh_launch_from_panel(Xp, ld, N, r, (cplx*)dX, N, h->stream, fh_perm(h));
-    if (M > 0 && res_host) {
-        const cplx* rdots = nullptr;
-        if ((rc = fh_panel_residual(h, ld, r, Xp, Rp, lambda_host, use_B, part, ddots, &rdots, dots_fb))) return rc;
-        FH_CHECK(hipStreamSynchronize(h->stream));
-        fh_residual_norms(rdots, lambda_host, (int)M, res_host);
-    }
-    FH_CHECK(hipStreamSynchronize(h->stream));
-    fh_prof_collect(h);
-    FH_CHECK(hipGetLastError());       // launch-configuration errors do not surface through the stream sync
-    return 0;
-}
-
-extern "C" int feasthip_ritz_residual(feasthip_handle h, int64_t r, const void* Q, const void* V, const double* lambda,
-                                      int64_t M, int normalize, int use_B, void* X, double* res) {
-    int rc = fh_check_problem(h, r, 1);
-    if (rc) return rc;
-    if (!Q || !X) { h->last_error = "ritz_residual: null argument"; return FEASTHIP_ERROR_INTERNAL; }
-    if ((rc = fh_check_adjoint(h, "ritz_residual"))) return rc;
-    FH_CHECK(hipSetDevice(h->device));
-    const size_t nb = (size_t)fh_N(h) * r * sizeof(cplx);
-    void *dQ, *dX;
-    if ((rc = fh_stage_in(h, "host_Q", Q, nb, &dQ))) return rc;
-    if ((rc = fh_get_buf(h, "host_X", nb, &dX))) return rc;
-    rc = feasthip_ritz_residual_dev(h, r, dQ, V, lambda, M, normalize, use_B, dX, res);
-    if (rc) return rc;
-    FH_CHECK(hipMemcpy(X, dX, nb, hipMemcpyDeviceToHost));
-    return 0;
-}
-
-// ---------------------------------------------------------------------------------------
-// Resident refinement loop (rows a7, a9-a13 of one FEAST loop without leaving the kernels' panel layout)
-//
-// The per-primitive entry points above speak column-major at the C ABI, so one loop of variant A crossed the boundary seven
-// times (contour_apply in/out, orthonormalize in/out, project in, ritz_residual in/out: k_to_panel / k_from_panel each) and
-// synchronised the stream about twenty times (every small host -> device upload).  Here the panels stay where the kernels
-// left them:
-//   feasthip_contour_apply_resident   Q (imported once, or the Ritz vectors of the previous loop)  ->  Q_proj   [rs_P]
-//   feasthip_rr_reduce_resident       rank + the reduced pencil  (Q_o^H A Q_o, Q_o^H B Q_o)  of the orthonormal basis Q_o of Q_proj
-//   feasthip_rr_ritz_resident         X = Q_o V, normalise, residuals; X becomes the next loop's Q   [rs_X, rs_R]
-//   feasthip_resident_export          column-major copy of X (the converged Ritz vectors, once per solve)
-// The orthonormal basis is never formed when Q_proj is well conditioned (the steady state of FEAST): the Rayleigh-Ritz
-// pairs of a subspace do not depend on the basis, so the reduced pencil is taken on Q_proj with unit columns -- three Gram
-// products (Q^H Q for the test, Q^H A Q, Q^H B Q: fh_op_gram, the step the per-primitive projections use) queued behind ONE
-// synchronisation, an O(m^2) scaling on the host (fh_gram_to_host) -- and
-// handed to the host's generalized eigensolver, whose Cholesky factorisation of the B-part does what the Cholesky-QR did;
-// the Ritz vectors are Q_proj (D^-1 V): one tall product instead of two.  The acceptance test is fh_ortho_panel's own
-// (fh_cholqr::accept) and the implicit basis is taken when it decides "one pass"; anything else -- rank deficiency, a ratio
-// that needs the second Cholesky-QR pass -- takes fh_ortho_panel itself on the resident panel, so the rank decisions are the
-// same as the per-primitive path's.
-// The eigen-residual panel A X - B X diag(lambda) the Ritz step forms for its norms is the next sweep's shared start
-// residual (fh_contour_apply_panel: shared_src), which saves that sweep's first operator product.
-// ---------------------------------------------------------------------------------------
-static int fh_rs_panels(feasthip_ctx* h, cplx** P, cplx** X, cplx** R) {
-    const size_t panel = (size_t)fh_N(h) * FH_MAX_LD;
-    int rc;
-    if ((rc = fh_buf(h, "rs_P", panel, P))) return rc;
-    if ((rc = fh_buf(h, "rs_X", panel, X))) return rc;
-    return fh_buf(h, "rs_R", panel, R);
-}
-
+// The sweep of the resident refinement loop (fh_ritz.hip, "Resident refinement loop"): Q and Q_proj stay panels
 extern "C" int feasthip_contour_apply_resident(feasthip_handle h, int64_t m64, const void* dQ, const double* ritz_lambda_host,
                                                int* node_status, feasthip_stats* stats) {
     int rc = fh_check_problem(h, m64);
@@ -3182,331 +1796,14 @@ extern "C" int feasthip_contour_apply_resident(feasthip_handle h, int64_t m64, c
         }
     }
     h->rs_P = nullptr; h->rs_basis = nullptr; h->rs_T.clear(); h->rs_rank = 0;
-    h->mask_live = 1;
-    rc = fh_contour_apply_impl(h, m64, nullptr, ritz_lambda_host, nullptr, nullptr, nullptr, node_status, stats, &rs);
-    h->mask_live = 0;
-    h->col_mask.clear();
-    if (rc) return rc;
+    if ((rc = fh_contour_apply_impl(h, m64, nullptr, ritz_lambda_host, nullptr, nullptr, nullptr, node_status, stats, &rs))) return rc;
     h->rs_P = P; h->rs_m = m; h->rs_ld = ld;
     return 0;
-}
-
-extern "C" int feasthip_rr_reduce_resident(feasthip_handle h, int64_t m64, double rank_tol, int hermitize, int* rank,
-                                           void* Aq_host, void* Bq_host) {
-    int rc = fh_check_problem(h, m64);
-    if (rc) return rc;
-    if (!rank || !Aq_host || !Bq_host) { h->last_error = "rr_reduce_resident: null argument"; return FEASTHIP_ERROR_INTERNAL; }
-    if ((rc = fh_check_adjoint(h, "rr_reduce_resident", "the resident loop has no adjoint form"))) return rc;
-    FH_CHECK(hipSetDevice(h->device));
-    const int m = (int)m64, N = (int)fh_N(h);
-    cplx *Pb, *Xb, *Rb;
-    if ((rc = fh_rs_panels(h, &Pb, &Xb, &Rb))) return rc;
-    if (h->rs_P != Pb || h->rs_m != m) { h->last_error = "rr_reduce_resident: no resident Q_proj of this width"; return FEASTHIP_ERROR_M0; }
-    const int ld = h->rs_ld;
-    cplx* P = h->rs_P;
-    const size_t g2 = (size_t)ld * ld;
-    cplx* G;
-    fh_op_gram og;
-    if ((rc = og.acquire(h, ld))) return rc;
-    if ((rc = fh_buf(h, "gram_G3", 3 * g2, &G))) return rc;
-    const bool b_id = fh_b_identity(h);
-    // Gram products of `basis`: [0] basis^H basis (want_g0), [1] basis^H A basis, [2] basis^H B basis (B != I); one sync
-    const cplx* Gh = nullptr;
-    std::vector<char> gh_fallback;
-    auto grams = [&](const cplx* basis, bool want_g0) -> int {
-        if (want_g0) { fh_prof_begin(h, "gram"); fh_launch_gram(basis, basis, N, ld, 0, og.gw, G, h->stream); fh_prof_end(h); }
-        int drc;
-        for (int which = 0; which < (b_id ? 1 : 2); ++which)
-            if ((drc = og.step(m, basis, basis, which, 0, G + (1 + which) * g2))) return drc;
-        const void* slot = nullptr;
-        if ((drc = fh_download_small(h, G, 3 * g2 * sizeof(cplx), &slot, gh_fallback))) return drc;
-        FH_CHECK(hipStreamSynchronize(h->stream));
-        Gh = (const cplx*)slot;
-        return 0;
-    };
-    if ((rc = grams(P, true))) return rc;
-    // ---- implicit basis: fh_ortho_panel's acceptance test on the Gram matrix we already have; its one-pass decision (the basis
-    //      below is then as good as an orthonormalised one to 1e-14) takes the fast path ----
-    std::vector<double> dcol;
-    bool fast = false;
-    if (!fh_knob::no_cholqr()) {
-        std::vector<cplx> G0(Gh, Gh + g2);
-        fast = fh_cholqr::accept(G0, m, ld, 0.0, rank_tol, fh_knob::cholqr_two_pass(), dcol) == fh_cholqr::Plan::one_pass;
-    }
-    if (fast) {
-        fh_ortho_note_reset(h);
-        std::vector<int> ident(m);
-        for (int j = 0; j < m; ++j) ident[j] = j;
-        fh_ortho_note(h, FEASTHIP_ORTHO_USED_CHOLQR, 0, 0, m, ident.data(), nullptr);
-        // basis = Q_proj D^-1 (unit columns): its pencil is the equilibrated Gram pair; the orthonormal basis is never formed
-        fh_gram_to_host(Gh + g2, ld, m, dcol.data(), hermitize, (cplx*)Aq_host);
-        fh_gram_to_host(b_id ? Gh : Gh + 2 * g2, ld, m, dcol.data(), hermitize, (cplx*)Bq_host);
-        h->rs_basis = P; h->rs_rank = m;
-        h->rs_T.assign(m, cmake(1, 0));
-        for (int j = 0; j < m; ++j) h->rs_T[j] = cmake(1.0 / dcol[j], 0.0);
-        *rank = m;
-        fh_prof_collect(h);
-        FH_CHECK(hipGetLastError());
-        return 0;
-    }
-    // ---- general path: the rank-revealing orthonormalisation on the resident panel, then the projections of its result ----
-    cplx* Out;
-    if ((rc = fh_buf(h, "or_out", (size_t)N * FH_MAX_LD, &Out))) return rc;
-    cplx* res = nullptr;
-    int r = 0;
-    fh_ortho_note_reset(h);
-    if ((rc = fh_ortho_panel(h, m, ld, P, Out, rank_tol, 0.0, m, &r, &res))) return rc;
-    h->rs_P = nullptr;                            // (the orthonormalisation may have overwritten the projection panel)
-    *rank = r;
-    h->rs_rank = r; h->rs_T.clear(); h->rs_basis = res;
-    if (r == 0) { fh_prof_collect(h); return 0; }
-    if ((rc = grams(res, false))) return rc;
-    fh_gram_to_host(Gh + g2, ld, r, nullptr, hermitize, (cplx*)Aq_host);
-    if (b_id) fh_identity_to_host(r, (cplx*)Bq_host);       // orthonormal basis, B = I
-    else fh_gram_to_host(Gh + 2 * g2, ld, r, nullptr, hermitize, (cplx*)Bq_host);
-    fh_prof_collect(h);
-    FH_CHECK(hipGetLastError());
-    return 0;
-}
-
-extern "C" int feasthip_rr_ritz_resident(feasthip_handle h, int64_t r64, const void* V_host, const double* lambda_host, int64_t M,
-                                         int normalize, int use_B, double* res_host) {
-    int rc = fh_check_problem(h, r64);
-    if (rc) return rc;
-    if (!V_host || !lambda_host) { h->last_error = "rr_ritz_resident: null argument"; return FEASTHIP_ERROR_INTERNAL; }
-    if ((rc = fh_check_adjoint(h, "rr_ritz_resident", "the resident loop has no adjoint form"))) return rc;
-    if (M < 0 || M > r64) { h->last_error = "rr_ritz_resident: M out of range"; return FEASTHIP_ERROR_M0; }
-    FH_CHECK(hipSetDevice(h->device));
-    const int r = (int)r64, N = (int)fh_N(h);
-    cplx *Pb, *Xp, *Rp;
-    if ((rc = fh_rs_panels(h, &Pb, &Xp, &Rp))) return rc;
-    if (!h->rs_basis || h->rs_rank != r) { h->last_error = "rr_ritz_resident: run rr_reduce_resident first (rank mismatch)"; return FEASTHIP_ERROR_M0; }
-    const int ld = h->rs_ld;
-    fh_ritz_ws ws;
-    if ((rc = ws.acquire(h, ld, false, false))) return rc;
-    cplx *dV = ws.dV, *part = ws.part, *ddots = ws.ddots;
-    // V padded to ld x ld; the implicit basis is Q_proj D^-1, so X = Q_proj (D^-1 V)
-    std::vector<cplx> Vp;
-    fh_pad_block((const cplx*)V_host, r, r, ld, 0, 0, h->rs_T.empty() ? nullptr : h->rs_T.data(), Vp);
-    if ((rc = fh_upload_small(h, dV, Vp.data(), Vp.size() * sizeof(cplx)))) return rc;
-    h->rs_X = nullptr; h->rs_R = nullptr;
-    fh_prof_begin(h, "ritz");
-    fh_launch_small_matmul(h->rs_basis, dV, N, ld, Xp, h->stream);
-    fh_prof_end(h);
-    if (normalize && M > 0) {
-        fh_launch_dot_cols(Xp, Xp, N, ld, part, ddots, h->stream);
-        fh_launch_normalize_cols(Xp, ddots, N, ld, (int)M, h->stream);
-    }
-    // R for all r columns (the next sweep's start residual); its column norms only when asked for
-    const cplx* dots_h = nullptr;
-    std::vector<char> dots_fb;
-    const bool want_res = M > 0 && res_host;
-    if ((rc = fh_panel_residual(h, ld, r, Xp, Rp, lambda_host, use_B, part, ddots, want_res ? &dots_h : nullptr, dots_fb))) return rc;
-    // the rank dropped below the panel's padded width (64 -> 32 / 16 columns): the next sweep works on the narrower panel
-    int ldx = ld;
-    if (fh_pick_ld(r) < ld) {
-        ldx = fh_pick_ld(r);
-        cplx* tmp;
-        if ((rc = fh_buf(h, "rs_tmp", (size_t)N * FH_MAX_LD, &tmp))) return rc;
-        for (cplx* pan : {Xp, Rp}) {
-            fh_launch_panel_cols(pan, ld, 0, r, N, tmp, ldx, h->stream);
-            FH_CHECK(hipMemcpyAsync(pan, tmp, (size_t)N * ldx * sizeof(cplx), hipMemcpyDeviceToDevice, h->stream));
-        }
-    }
-    FH_CHECK(hipStreamSynchronize(h->stream));
-    if (want_res) fh_residual_norms(dots_h, lambda_host, (int)M, res_host);
-    h->rs_X = Xp; h->rs_X_m = r; h->rs_X_ld = ldx;
-    h->rs_R_lambda.assign(ld, cmake(0, 0));
-    if (use_B || fh_b_identity(h)) {                  // the start residual of the sweeps is the one WITH B
-        for (int c = 0; c < r; ++c) h->rs_R_lambda[c] = cmake(lambda_host[2 * c], lambda_host[2 * c + 1]);
-        h->rs_R = Rp;
-    }
-    fh_prof_collect(h);
-    FH_CHECK(hipGetLastError());
-    return 0;
-}
-
-extern "C" int feasthip_resident_export(feasthip_handle h, int which, int64_t ncols, void* dX) {
-    if (!h) return FEASTHIP_ERROR_INTERNAL;
-    if (h->poisoned) { h->last_error = "handle poisoned by an earlier device failure: destroy it"; return FEASTHIP_ERROR_INTERNAL; }
-    if (!dX) { h->last_error = "resident_export: null destination"; return FEASTHIP_ERROR_INTERNAL; }
-    if (h->kind == 3) { h->last_error = "resident_export: a polynomial handle has no resident panels (use the feasthip_poly_* calls)"; return FEASTHIP_ERROR_FPM; }
-    const cplx* src = which == 0 ? h->rs_X : h->rs_P;
-    const int have = which == 0 ? h->rs_X_m : h->rs_m, ld = which == 0 ? h->rs_X_ld : h->rs_ld;
-    if (!src || ncols < 0 || ncols > have) { h->last_error = "resident_export: no such resident panel / too many columns"; return FEASTHIP_ERROR_M0; }
-    FH_CHECK(hipSetDevice(h->device));
-    const int N = (int)fh_N(h);
-    if (ncols > 0) fh_launch_from_panel(src, ld, N, (int)ncols, (cplx*)dX, N, h->stream, fh_perm(h));
-    FH_CHECK(hipStreamSynchronize(h->stream));
-    return 0;
-}
-
-extern "C" int feasthip_resident_import(feasthip_handle h, int which, int64_t ncols, const void* dX) {
-    int rc = fh_check_problem(h, ncols);
-    if (rc) return rc;
-    if (!dX) { h->last_error = "resident_import: null source"; return FEASTHIP_ERROR_INTERNAL; }
-    FH_CHECK(hipSetDevice(h->device));
-    const int m = (int)ncols, ld = fh_pick_ld(m), N = (int)fh_N(h);
-    cplx *P, *X, *R;
-    if ((rc = fh_rs_panels(h, &P, &X, &R))) return rc;
-    fh_launch_to_panel((const cplx*)dX, N, N, m, which == 0 ? X : P, ld, h->stream, fh_perm(h));
-    FH_CHECK(hipStreamSynchronize(h->stream));
-    if (which == 0) { h->rs_X = X; h->rs_X_m = m; h->rs_X_ld = ld; h->rs_R = nullptr; h->rs_R_lambda.clear(); }
-    else { h->rs_P = P; h->rs_m = m; h->rs_ld = ld; h->rs_basis = nullptr; h->rs_T.clear(); h->rs_rank = 0; }
-    return 0;
-}
-
-// ---------------------------------------------------------------------------------------
-// Host policy of the inexact FEAST mode (fh_policy.hpp): exported so that host shims call it instead of re-porting it
-// ---------------------------------------------------------------------------------------
-extern "C" int feasthip_policy_init(feasthip_policy* p, double Emin, double Emax, int ne, int quadrature, double inner_rtol,
-                                    double outer_tol, int solver_maxiter, int steer, int fpm18) {
-    if (!p || !(Emax > Emin) || ne < 1 || !(inner_rtol > 0.0) || solver_maxiter < 1) return FEASTHIP_ERROR_FPM;
-    memset(p, 0, sizeof(*p));
-    p->Emin = Emin; p->Emax = Emax; p->inner_rtol = inner_rtol; p->outer_tol = outer_tol;
-    p->ne = ne; p->quadrature = quadrature;
-    p->steer = (steer && (quadrature == 0 || quadrature == 1)) ? 1 : 0;
-    p->cap = 8000; p->inner_cap = p->base_cap = solver_maxiter;
-    p->eps_prev = INFINITY; p->next_rtol = inner_rtol; p->last_reach = -1.0;
-    // a priori the subspace (1.5 x the eigenvalue count is the usual M0) reaches about 1.4 half widths
-    p->aspect = p->steer ? fh_policy::pick(Emin, Emax, ne, quadrature, inner_rtol, p->cap, 1.4, nullptr, 0, 0) : fpm18;
-    return 0;
-}
-
-extern "C" int feasthip_policy_update(feasthip_policy* p, double epsout, int M, int any_node_capped, const double* ritz, int nritz) {
-    if (!p || (nritz > 0 && !ritz) || M < 0 || M > nritz) return FEASTHIP_ERROR_FPM;
-    // stagnation guard: the outer residual should contract by about inner_rtol per loop.  When it has not even halved over
-    // two loops the inner solves are not delivering (iteration cap too low for this matrix): double the cap
-    if (p->n_hist < 3) p->eps_hist[p->n_hist++] = epsout;
-    else { p->eps_hist[0] = p->eps_hist[1]; p->eps_hist[1] = p->eps_hist[2]; p->eps_hist[2] = epsout; }
-    if (p->n_hist >= 3 && p->eps_hist[2] > 0.5 * p->eps_hist[0] && p->inner_cap < 16 * p->base_cap) {
-        p->inner_cap *= 2;
-        p->n_hist = 0;
-    }
-    if (p->steer) {
-        // Safeguard first.  The policy promised a contraction of max(filter ratio, inner_rtol) < 0.5 per loop.  When a loop
-        // delivers less than 0.3 there are two possible culprits: inner solves that stopped at the iteration cap before
-        // reaching inner_rtol (a taller ellipse would only HELP them -- raise the cap instead), or a filter that is too soft
-        // for this spectrum (lower the ellipse, down to the circle).
-        if (std::isfinite(p->eps_prev) && std::isfinite(epsout) && epsout > 0.3 * p->eps_prev) {
-            if (any_node_capped && p->inner_cap < 16 * p->base_cap) { p->inner_cap *= 2; p->n_hist = 0; }
-            else if (p->aspect > 100) p->cap = std::max(100, p->aspect / 2);
-        }
-        // Steering: the filter model at the reach of the subspace.  The guard Ritz values overshoot outward while they are far
-        // from converged, hence a cautious quantile of their distances early, nearly the outermost one later, and never more
-        // than double the ratio in one loop.
-        const double reach = M > 0 ? fh_policy::subspace_reach(ritz, nritz, p->Emin, p->Emax, !(epsout < 1e-2) ? 0.8 : 0.95) : -1.0;
-        p->last_reach = reach;
-        p->aspect = reach >= 0.0 ? fh_policy::pick(p->Emin, p->Emax, p->ne, p->quadrature, p->inner_rtol, p->cap, reach, ritz, M, 2 * p->aspect)
-                                 : std::min(p->aspect, p->cap);
-    }
-    // The last loop: a sweep reduces the outer residual by about 2 x its inner tolerance; when less than that is still
-    // needed to reach outer_tol, the next sweep's inner tolerance is relaxed to what is needed (with a margin of 3), never
-    // beyond 0.3 -- on cfg 3 a loop that starts at 1.3e-12 for a target of 1e-12 costs a third of a full one
-    p->next_rtol = p->inner_rtol;
-    if (p->outer_tol > 0.0 && std::isfinite(epsout) && epsout > p->outer_tol)
-        p->next_rtol = std::min(0.3, std::max(p->inner_rtol, 0.32 * p->outer_tol / epsout));
-    p->eps_prev = epsout;
-    return 0;
-}
-
-extern "C" int feasthip_policy_pick_direct_nodes(const int* node_iters, int ne, int max_direct, double t_iter, double t_solve,
-                                                 double t_factor, int loops_left, int* kinds) {
-    return fh_policy::pick_direct_nodes(node_iters, ne, max_direct, t_iter, t_solve, t_factor, loops_left, kinds);
-}
-
-extern "C" int feasthip_policy_set_aside(const double* res, int M, int* flags) {
-    // Inexact inner solves leave solver noise in the guard columns.  Its Ritz values are arbitrary; one that lands inside
-    // the interval has an O(1) residual that never contracts and would hold epsout up forever (variant A has no
-    // spurious-pair removal; with exact solves the guard columns are true eigen-directions and stay outside).  A pair is set
-    // aside when its relative residual is > 0.1 AND > 100x the smallest residual of the pairs inside: a true pair inside the
-    // interval sees a filter value >= 1/2 and contracts with the others.
-    if (!res || !flags || M <= 1) { if (flags) for (int j = 0; j < M; ++j) flags[j] = 0; return 0; }
-    double rmin = res[0];
-    for (int j = 1; j < M; ++j) rmin = std::min(rmin, res[j]);
-    int n = 0;
-    for (int j = 0; j < M; ++j) { flags[j] = (res[j] > 0.1 && res[j] > 100.0 * rmin) ? 1 : 0; n += flags[j]; }
-    if (n == 0 || n >= M) { for (int j = 0; j < M; ++j) flags[j] = 0; return 0; }
-    return n;
-}
-
-extern "C" double feasthip_policy_filter_ratio(double Emin, double Emax, int ne, int quadrature, int fpm18, double reach,
-                                               const double* inside, int n_inside) {
-    if (!(Emax > Emin) || ne < 1 || fpm18 < 0 || (quadrature != 0 && quadrature != 1)) return NAN;
-    return fh_policy::filter_ratio(Emin, Emax, ne, quadrature, fpm18, reach, inside, n_inside);
-}
-
-extern "C" double feasthip_policy_reach(const double* ritz, int n, double Emin, double Emax, double quantile) {
-    if (n > 0 && !ritz) return -1.0;
-    return fh_policy::subspace_reach(ritz, n, Emin, Emax, quantile);
 }
 
 // ---------------------------------------------------------------------------------------
 // RCI seams: Y = A X / B X (jobs 30/40), Y = (zB - A)^{-1} X (jobs 10+11, linear_solver)
 // ---------------------------------------------------------------------------------------
-// Rayleigh-Ritz step with the reduced eigenproblem on the device: project,
-// Jacobi eigensolver (fh_eig.hip) instead of host ZHEGV, stable inside-first reorder for [Emin, Emax]
-// (src/core/feast_aux.jl:144-197), X = Q V, normalise the inside columns, residuals.  The host sees
-// lambda[r] (reordered), M and res[M] only.  FEASTHIP_ERROR_LAPACK: the reduced B matrix is not
-// positive definite -- the caller falls back to project + host eigen + ritz_residual
-// (the general fallback of src/dense/feast_dense.jl:276-284).
-extern "C" int feasthip_rayleigh_ritz_dev(feasthip_handle h, int64_t r64, const void* dQ, double Emin, double Emax,
-                                          int use_B, void* dX, double* lambda_out, int* M_out, double* res_out) {
-    int rc = fh_check_problem(h, r64);
-    if (rc) return rc;
-    if (!dQ || !dX || !lambda_out || !M_out) { h->last_error = "rayleigh_ritz: null argument"; return FEASTHIP_ERROR_INTERNAL; }
-    if ((rc = fh_check_adjoint(h, "rayleigh_ritz", "the Hermitian reduced eigensolver has no two-sided form"))) return rc;
-    const int r = (int)r64, ld = FH_MAX_LD;
-    std::vector<cplx> Sq((size_t)r * r), Aq((size_t)r * r);
-    if ((rc = feasthip_project_dev(h, r64, dQ, 0, 1, Sq.data(), Aq.data()))) return rc;
-    bool a_identity = fh_b_identity(h) != 0;                 // project returned exactly I
-    cplx *dS, *dA, *dV;
-    double* dlam;
-    int* dflags;
-    void* scratch;                               // (laid out by the kernel: sized in bytes)
-    if ((rc = fh_buf(h, "rr_S", (size_t)ld * ld, &dS))) return rc;
-    if ((rc = fh_buf(h, "rr_A", (size_t)ld * ld, &dA))) return rc;
-    if ((rc = fh_buf(h, "rr_V", (size_t)ld * ld, &dV))) return rc;
-    if ((rc = fh_buf(h, "rr_lam", ld, &dlam))) return rc;
-    if ((rc = fh_buf(h, "rr_flags", 4, &dflags))) return rc;
-    if ((rc = fh_get_buf(h, "rr_scratch", fh_herm_eig_scratch_bytes(), &scratch))) return rc;
-    std::vector<cplx> pad((size_t)ld * ld, cmake(0, 0));
-    for (int j = 0; j < r; ++j) for (int i = 0; i < r; ++i) pad[(size_t)j * ld + i] = Sq[(size_t)j * r + i];
-    FH_CHECK(hipMemcpyAsync(dS, pad.data(), pad.size() * sizeof(cplx), hipMemcpyHostToDevice, h->stream));
-    FH_CHECK(hipStreamSynchronize(h->stream));
-    if (!a_identity) {
-        for (int j = 0; j < r; ++j) for (int i = 0; i < r; ++i) pad[(size_t)j * ld + i] = Aq[(size_t)j * r + i];
-        FH_CHECK(hipMemcpyAsync(dA, pad.data(), pad.size() * sizeof(cplx), hipMemcpyHostToDevice, h->stream));
-        FH_CHECK(hipStreamSynchronize(h->stream));
-    }
-    fh_prof_begin(h, "reduced_eig");
-    fh_launch_herm_eig(r, ld, dS, a_identity ? nullptr : dA, scratch, dlam, dV, dflags, h->stream);
-    fh_prof_end(h);
-    std::vector<double> lam(r);
-    std::vector<cplx> V((size_t)ld * ld);
-    int flags[4];
-    FH_CHECK(hipMemcpyAsync(flags, dflags, sizeof(flags), hipMemcpyDeviceToHost, h->stream));
-    FH_CHECK(hipMemcpyAsync(lam.data(), dlam, r * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    FH_CHECK(hipMemcpyAsync(V.data(), dV, V.size() * sizeof(cplx), hipMemcpyDeviceToHost, h->stream));
-    FH_CHECK(hipStreamSynchronize(h->stream));
-    if (fh_knob::debug_timing()) fprintf(stderr, "[rayleigh_ritz] r=%d jacobi sweeps=%d\n", r, flags[3]);
-    if (flags[0] || flags[2]) { h->last_error = "rayleigh_ritz: reduced B matrix not positive definite"; return FEASTHIP_ERROR_LAPACK; }
-    // stable inside-first permutation
-    std::vector<int> perm;
-    for (int i = 0; i < r; ++i) if (lam[i] >= Emin && lam[i] <= Emax) perm.push_back(i);
-    const int M = (int)perm.size();
-    for (int i = 0; i < r; ++i) if (!(lam[i] >= Emin && lam[i] <= Emax)) perm.push_back(i);
-    std::vector<cplx> Vs((size_t)r * r);
-    std::vector<double> lamc(2 * (size_t)r);
-    for (int k = 0; k < r; ++k) {
-        lambda_out[k] = lam[perm[k]];
-        lamc[2 * k] = lam[perm[k]]; lamc[2 * k + 1] = 0.0;
-        for (int i = 0; i < r; ++i) Vs[(size_t)k * r + i] = V[(size_t)perm[k] * ld + i];
-    }
-    *M_out = M;
-    return feasthip_ritz_residual_dev(h, r64, dQ, Vs.data(), lamc.data(), M, 1, use_B, dX, res_out);
-}
-
 extern "C" int feasthip_matmul_dev(feasthip_handle h, int which, int64_t m64, const void* dX, void* dY) {
     if (m64 > FH_MAX_LD) {          // independent columns: 64 at a time
         int rc0 = fh_check_problem(h, m64, 1);
@@ -3540,10 +1837,7 @@ extern "C" int feasthip_matmul_dev(feasthip_handle h, int which, int64_t m64, co
     oc.X = Xp; oc.Y = Yp; oc.coefA = dca; oc.coefB = dcb; oc.skip = which == 0 ? 2 : 1;
     if (fh_apply_operator(h, ld, oc) < 0) return FEASTHIP_ERROR_INTERNAL;
     fh_launch_from_panel(Yp, ld, N, m, (cplx*)dY, N, h->stream, fh_perm(h));
-    FH_CHECK(hipStreamSynchronize(h->stream));
-    fh_prof_collect(h);
-    FH_CHECK(hipGetLastError());       // launch-configuration errors do not surface through the stream sync
-    return 0;
+    return fh_finish(h);
 }
 
 extern "C" int feasthip_matmul(feasthip_handle h, int which, int64_t m, const void* X, void* Y) {
@@ -3601,7 +1895,7 @@ extern "C" int feasthip_shifted_solve_dev(feasthip_handle h, double z_re, double
     std::vector<int> status(1, 0);
     if (h->solver == FEASTHIP_SOLVER_LU || h->solver == FEASTHIP_SOLVER_BANDED) {
         const bool banded = h->solver == FEASTHIP_SOLVER_BANDED;
-        if (!banded && h->kind != 1) { h->last_error = "solver LU requires a dense matrix"; return FEASTHIP_ERROR_FPM; }
+        if (!banded && h->kind != FH_KIND_DENSE) { h->last_error = "solver LU requires a dense matrix"; return FEASTHIP_ERROR_FPM; }
         int64_t nfact = 0;          // (the factors are cached per quadrature node when z is one, else in one extra slot)
         double worst = 0.0;
         if (h->factor_precision == 32) rc = fh_dense_lu_refined(h, ld, m, 1, z, Rhs, Y, panel, status, &nfact, true, &worst, banded);
@@ -3644,99 +1938,4 @@ extern "C" int feasthip_shifted_solve(feasthip_handle h, double z_re, double z_i
     if (rc != 0 && rc != FEASTHIP_ERROR_NO_CONVERGENCE) return rc;
     FH_CHECK(hipMemcpy(Y, dY, nb, hipMemcpyDeviceToHost));
     return rc;
-}
-
-// ---------------------------------------------------------------------------------------
-// measurement support
-// ---------------------------------------------------------------------------------------
-extern "C" int feasthip_last_node_iterations(feasthip_handle h, int* out, int n) {
-    if (!h || !out) return FEASTHIP_ERROR_INTERNAL;
-    for (int e = 0; e < n; ++e) out[e] = e < (int)h->last_node_iters.size() ? h->last_node_iters[e] : 0;
-    return 0;
-}
-
-extern "C" int feasthip_last_global_node_iterations(feasthip_handle h, int* out, int n) {
-    if (!h || !out) return FEASTHIP_ERROR_INTERNAL;
-    for (int e = 0; e < n; ++e) out[e] = e < (int)h->global_node_iters.size() ? h->global_node_iters[e] : 0;
-    return 0;
-}
-
-extern "C" int feasthip_last_shifted_sweep(feasthip_handle h, int* used, int* seed_node, int* seed_iterations, int* spmm_node_passes) {
-    if (!h) return FEASTHIP_ERROR_INTERNAL;
-    const bool u = h->shift_panels > 0 && h->shift_used == h->shift_panels;
-    if (used) *used = u ? 1 : 0;
-    if (seed_node) *seed_node = u ? h->shift_seed : -1;
-    if (seed_iterations) *seed_iterations = u ? h->shift_seed_iters : 0;
-    if (spmm_node_passes) *spmm_node_passes = u ? h->shift_seed_iters : 0;
-    return 0;
-}
-
-extern "C" int feasthip_last_block_sweep(feasthip_handle h, int* used, int* node_steps_max, int* breakdown_nodes, int* spmm_node_passes) {
-    if (!h) return FEASTHIP_ERROR_INTERNAL;
-    const bool u = h->block_panels > 0 && h->block_used == h->block_panels;
-    if (used) *used = u ? 1 : 0;
-    if (node_steps_max) *node_steps_max = u ? h->block_steps_max : 0;
-    if (breakdown_nodes) *breakdown_nodes = u ? h->block_breakdowns : 0;
-    if (spmm_node_passes) *spmm_node_passes = u ? h->block_passes : 0;
-    return 0;
-}
-
-extern "C" int feasthip_last_column_iterations(feasthip_handle h, int* out, int n) {
-    if (!h || !out) return FEASTHIP_ERROR_INTERNAL;
-    for (int e = 0; e < n; ++e) out[e] = e < (int)h->last_col_iters.size() ? h->last_col_iters[e] : 0;
-    return 0;
-}
-
-extern "C" int feasthip_profile_enable(feasthip_handle h, int enable) {
-    if (!h) return FEASTHIP_ERROR_INTERNAL;
-    h->profiling = enable ? 1 : 0;
-    if (enable) { h->prof_host_s = 0.0; h->prof_t0 = fh_now_s(); }
-    return 0;
-}
-extern "C" int feasthip_profile_reset(feasthip_handle h) {
-    if (!h) return FEASTHIP_ERROR_INTERNAL;
-    fh_prof_collect(h);
-    h->prof.clear();
-    h->prof_work.clear();
-    h->prof_mult = 1;
-    hipMemset(h->d_counters, 0, 8 * sizeof(unsigned long long));
-    return 0;
-}
-extern "C" int feasthip_profile_set_period(feasthip_handle h, int period) {
-    if (!h || period < 0) return FEASTHIP_ERROR_INTERNAL;
-    h->prof_period = period;
-    return 0;
-}
-extern "C" int feasthip_profile_get_work(feasthip_handle h, const char* kernel_class, double* work) {
-    if (!h || !kernel_class || !work) return FEASTHIP_ERROR_INTERNAL;
-    auto it = h->prof_work.find(kernel_class);
-    *work = it == h->prof_work.end() ? 0.0 : it->second;
-    return 0;
-}
-extern "C" int feasthip_profile_get(feasthip_handle h, const char* kernel_class, double* total_ms, int64_t* launches) {
-    if (!h || !kernel_class) return FEASTHIP_ERROR_INTERNAL;
-    fh_prof_collect(h);
-    // device-side work counters: [0] active node-sweeps of the SpMM, [1] its active column x vector passes, [2] columns that
-    // took a step in an update kernel, [3] of those the columns that go on iterating (the fused vector kernel reads and
-    // writes five panels for them, one for a column on its last step), [4] distinct columns whose accumulator entries a
-    // sum-mode launch read and wrote, [5] the part of [3] counted in the first vector launch of a lazy start (four passes)
-    static const char* const names[] = {"spmm.node_launches", "spmm.column_passes", "update.active_columns", "update.continuing_columns",
-                                        "update.accumulator_columns", "update.first_launch_columns"};
-    for (int k = 0; k < 6; ++k)
-        if (!strcmp(kernel_class, names[k])) {
-            unsigned long long c[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-            hipStreamSynchronize(h->stream);
-            hipMemcpy(c, h->d_counters, sizeof(c), hipMemcpyDeviceToHost);
-            if (launches) *launches = (int64_t)c[k];
-            if (total_ms) *total_ms = 0.0;
-            return 0;
-        }
-    auto it = h->prof.find(kernel_class);
-    auto is = h->prof.find(std::string(kernel_class) + "#sampled");
-    int64_t n = it == h->prof.end() ? 0 : it->second.launches;
-    double avg = 0.0;
-    if (is != h->prof.end() && is->second.launches > 0) avg = is->second.total_ms / (double)is->second.launches;
-    if (total_ms) *total_ms = avg * (double)n;   // estimated total = sampled average x launches
-    if (launches) *launches = n;
-    return 0;
 }

@@ -237,7 +237,7 @@ static int band_make_plan(feasthip_ctx* h) {
     // A sparse polynomial handle (feasthip_set_polynomial_csr) always plans multifrontal -- the mode 1 branch below without the
     // environment switch -- and has no band plan to fall back on: a pattern without a plan is refused here, a rejected pivot in
     // band_factor_batch, and the caller decides (feast_polynomial reruns on the dense expansion where that fits).
-    if (h->kind == 3 && h->poly.sparse) {
+    if (h->kind == FH_KIND_POLYNOMIAL && h->poly.sparse) {
         const int64_t N = h->csr.N;
         if ((int64_t)h->host_rowptr.size() != N + 1) { h->last_error = "sparse polynomial: no host pattern"; return FEASTHIP_ERROR_INTERNAL; }
         const int rc = fh_mf_make_plan(h, fh_knob::mf_leaf());
@@ -252,7 +252,7 @@ static int band_make_plan(feasthip_ctx* h) {
         h->band_plan = 3; h->band_kl = 0; h->band_ku = 0;
         return 0;
     }
-    if (h->kind != 2) { h->last_error = "banded LU needs a CSR matrix (feasthip_set_csr)"; return FEASTHIP_ERROR_FPM; }
+    if (h->kind != FH_KIND_CSR) { h->last_error = "banded LU needs a CSR matrix (feasthip_set_csr)"; return FEASTHIP_ERROR_FPM; }
     const int64_t N = h->csr.N;
     if ((int64_t)h->host_rowptr.size() != N + 1) { h->last_error = "banded LU: no host pattern"; return FEASTHIP_ERROR_INTERNAL; }
     int kl0 = 0, ku0 = 0;
@@ -444,7 +444,7 @@ static int band_factor_batch(feasthip_ctx* h, const std::vector<int>& which, con
                     std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_factor).count(), worst,
                     rejected ? ": rejected, band LU from here" : "");
         if (!rejected) return 0;
-        if (h->kind == 3) {          // no band LU for polynomials: the call fails, the factors of the batch are not used
+        if (h->kind == FH_KIND_POLYNOMIAL) {          // no band LU for polynomials: the call fails, the factors of the batch are not used
             char mult[32];
             snprintf(mult, sizeof(mult), "%.3g", worst);
             h->last_error = "sparse polynomial: the multifrontal LU rejected a pivot (N = " + std::to_string(N) + ", largest boundary multiplier " + mult +

@@ -1,5 +1,5 @@
 // fh_cholqr.hpp -- host half of the Cholesky-QR orthonormalisation (pure C++17, no HIP): the small dense maths that decides
-// the rank of every FEAST refinement loop's subspace.  fh_ortho_panel and feasthip_rr_reduce_resident (fh_api.hip) both take
+// the rank of every FEAST refinement loop's subspace.  fh_ortho_panel and feasthip_rr_reduce_resident (fh_ortho.hip, fh_ritz.hip) both take
 // their decision from accept() below; tests/host_cholqr_harness.cpp and tests/host_cholqr_rr_harness.cpp check this file on
 // the CPU under sanitizers.
 //

@@ -222,11 +222,11 @@ extern "C" int feasthip_comm_destroy(feasthip_handle h) {
 extern "C" int feasthip_comm_init_rank(feasthip_handle h, int nranks, int rank, const char* uid, int transport) {
     if (!h) return FEASTHIP_ERROR_INTERNAL;
     if (nranks < 1 || rank < 0 || rank >= nranks || !uid) { h->last_error = "comm_init_rank: need 0 <= rank < nranks and a unique id"; return FEASTHIP_ERROR_INTERNAL; }
-    if (h->kind == 4) {
+    if (h->kind == FH_KIND_OPERATOR) {
         h->last_error = "comm_init_rank: an operator handle (feasthip_set_operator) does not take a communicator: it sweeps on one rank, under the Krylov solvers FEASTHIP_SOLVER_BICGSTAB, _COCG or _GMRES";
         return FEASTHIP_ERROR_FPM;
     }
-    if (h->kind == 5) { h->last_error = "comm_init_rank: the contour is swept on one rank: " FH_TERMOP_TAKES; return FEASTHIP_ERROR_FPM; }
+    if (h->kind == FH_KIND_TERM_OPERATOR) { h->last_error = "comm_init_rank: the contour is swept on one rank: " FH_TERMOP_TAKES; return FEASTHIP_ERROR_FPM; }
     fh_comm_destroy(h);
     FH_CHECK(hipSetDevice(h->device));
     if (transport == FEASTHIP_COMM_AUTO) {

@@ -152,7 +152,7 @@ template <int TOP, typename FS, typename F> __device__ __forceinline__ cplx fh_t
     return v;
 }
 
-// Operator handle (h->kind == 4, feasthip_set_operator): the products A X and B X are the caller's callback
+// Operator handle (FH_KIND_OPERATOR, feasthip_set_operator): the products A X and B X are the caller's callback
 // (feasthip_apply_fn of include/feasthip.h) on whole node batches of panels; fh_operator.hip turns them into what the
 // drivers read.  N, b_identity and is_complex live in fh_dense.  failed: a callback of the running entry point returned
 // non-zero -- no further product is made or launched in that call (cleared by fh_check_problem at the next one).
@@ -165,7 +165,7 @@ struct fh_operator {
     int failed = 0;
 };
 
-// Term-operator handle (h->kind == 5, feasthip_set_term_operator, fh_termop.hip): the split form of a term handle whose
+// Term-operator handle (FH_KIND_TERM_OPERATOR, feasthip_set_term_operator, fh_termop.hip): the split form of a term handle whose
 // products A_k X are the caller's callback (fh_operator::apply with which = k).  N and is_complex live in fh_dense, the term
 // count (degree + 1), the node table and the norms (fro) in fh_poly with terms = 1, the callback in fh_operator.
 // shift_dev / shift_z: the node shifts fh_upload_shift_coefs sent last and where -- the Krylov drivers hand the operator their
@@ -181,7 +181,7 @@ struct fh_termop {
 };
 
 // what every refusal of a term-operator handle ends with, and the reason feasthip_set_solver and the solving entry points
-// refuse a solver kind on it (null: the kind is taken; fh_api.hip)
+// refuse a solver kind on it (null: the kind is taken; fh_problem.hip)
 #define FH_TERMOP_TAKES "a term-operator handle (feasthip_set_term_operator) takes the Krylov solvers FEASTHIP_SOLVER_BICGSTAB, _GMRES or (FEASTHIP_OP_SYMMETRIC) _COCG"
 struct feasthip_ctx;
 const char* fh_termop_solver_why(const feasthip_ctx* h, int kind, int factor_precision);
@@ -205,6 +205,11 @@ struct fh_krylov_scalars {
 
 struct fh_comm;   // fh_comm.hip: RCCL (or shared-device) communicator attached by feasthip_comm_init_rank
 
+// What problem a handle holds (feasthip_ctx::kind).  POLYNOMIAL: a matrix polynomial, dense or (poly.sparse) CSR, for the
+// feasthip_poly_* entry points only; OPERATOR: Krylov solvers only; TERM_OPERATOR: the feasthip_nep_* entry points, Krylov
+// solvers only.
+enum fh_kind { FH_KIND_NONE = 0, FH_KIND_DENSE = 1, FH_KIND_CSR = 2, FH_KIND_POLYNOMIAL = 3, FH_KIND_OPERATOR = 4, FH_KIND_TERM_OPERATOR = 5 };
+
 struct feasthip_ctx {
     int device = 0;
     fh_comm* comm = nullptr;
@@ -214,13 +219,13 @@ struct feasthip_ctx {
     std::string last_error;
 
     // problem
-    int kind = 0;  // 0 none, 1 dense, 2 sparse, 3 matrix polynomial, dense or (poly.sparse) CSR (the feasthip_poly_* entry points only), 4 operator (Krylov solvers only), 5 term operator (the feasthip_nep_* entry points, Krylov solvers only)
+    fh_kind kind = FH_KIND_NONE;
     fh_poly poly;
     fh_operator op;
     fh_termop top;
     fh_csr csr;
     // conjugate transpose of `csr` (A^H, B^H on the transposed union pattern, internal numbering; rowptr / col / aval / bval only):
-    // built at the first adjoint product of a CSR problem (fh_api.hip: fh_adjoint_csr_ensure), freed with the problem
+    // built at the first adjoint product of a CSR problem (fh_problem.hip: fh_adjoint_csr_ensure), freed with the problem
     fh_csr csr_adj;
     fh_dense dense;
 
@@ -324,6 +329,9 @@ struct feasthip_ctx {
     double prof_t0 = 0.0;                       // steady-clock seconds at profile_enable
 };
 
+// the handle's products are the caller's callback (an operator or a term-operator handle)
+inline bool fh_callback_products(const feasthip_ctx* h) { return h->kind == FH_KIND_OPERATOR || h->kind == FH_KIND_TERM_OPERATOR; }
+
 // workspace helper: returns a device buffer of at least `bytes`, reallocating if needed
 int fh_get_buf(feasthip_ctx* h, const char* name, size_t bytes, void** out);
 // the same for `count` elements of T (*out is left alone when the request fails)
@@ -334,7 +342,7 @@ template <typename T> inline int fh_buf(feasthip_ctx* h, const char* name, size_
     return rc;
 }
 void fh_free_bufs(feasthip_ctx* h);
-// frees the matrices, factors and plans of the current problem (any kind) and leaves h->kind = 0
+// frees the matrices, factors and plans of the current problem (any kind) and leaves h->kind = FH_KIND_NONE
 void fh_free_problem(feasthip_ctx* h);
 
 // profiling helpers

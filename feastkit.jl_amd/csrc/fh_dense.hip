@@ -1619,7 +1619,7 @@ static int lu_factor_batch(feasthip_ctx* h, const std::vector<int>& which, const
     FH_CHECK(hipStreamSynchronize(h->stream));
 
     // form z B - A (a polynomial handle: P(z), all nodes in one pass over the coefficients)
-    if (h->kind == 3) {
+    if (h->kind == FH_KIND_POLYNOMIAL) {
         if ((rc = fh_poly_form(h, (void* const*)dlus, dz, nf, sizeof(T) == sizeof(cplx) ? 64 : 32))) return rc;
     } else {
         dim3 grid(2048, nf), block(FH_BLOCK);
@@ -2900,7 +2900,7 @@ static int mf_factor_t(feasthip_ctx* h, int nf, void* const* stores, int* const*
     FH_CHECK(hipMemsetAsync(dpart, 0, tot * MF_MULT_PARTS * sizeof(float), h->stream));
     const bool bid = h->csr.b_identity != 0, cz = h->csr.is_complex != 0;
     const cplx* dterms = nullptr;          // term handle: the rows of its node table for these shifts
-    if (h->kind == 3 && h->poly.terms && (rc = fh_poly_term_table(h, dz, nf, &dterms))) return rc;
+    if (h->kind == FH_KIND_POLYNOMIAL && h->poly.terms && (rc = fh_poly_term_table(h, dz, nf, &dterms))) return rc;
     auto factor_group = [&](int g) -> int {
         const fh_mf::group& G = P.groups[g];
         const int F = (int)G.fronts.size(), nmat = F * nf, n = G.n, np = G.np, nb = G.nb;
@@ -2918,7 +2918,7 @@ static int mf_factor_t(feasthip_ctx* h, int nf, void* const* stores, int* const*
                 T* base = work + G.work_off;
                 const int* dd = S->d_asm_dst + G.asm_begin;
                 const int* ss = S->d_asm_src + G.asm_begin;
-                if (h->kind == 3 && h->poly.terms) {          // sparse term handle: T(z_e) from the node table, a profile class of its own
+                if (h->kind == FH_KIND_POLYNOMIAL && h->poly.terms) {          // sparse term handle: T(z_e) from the node table, a profile class of its own
                     const fh_poly_ptrs pp = fh_poly_coef_ptrs(h);
                     fh_prof_end(h);
                     fh_prof_begin(h, "terms_mf_assemble");
@@ -2926,7 +2926,7 @@ static int mf_factor_t(feasthip_ctx* h, int nf, void* const* stores, int* const*
                     else hipLaunchKernelGGL((k_mf_assemble_terms<double, T>), grid, block, 0, h->stream, dd, ss, cnt, base, P.work_elems, pp, h->poly.degree + 1, dterms);
                     fh_prof_end(h);
                     fh_prof_begin(h, "mf_assemble");
-                } else if (h->kind == 3) {          // sparse polynomial handle: P(z_e) in place of z_e B - A, a profile class of its own
+                } else if (h->kind == FH_KIND_POLYNOMIAL) {          // sparse polynomial handle: P(z_e) in place of z_e B - A, a profile class of its own
                     const fh_poly_ptrs pp = fh_poly_coef_ptrs(h);
                     fh_prof_end(h);
                     fh_prof_begin(h, "poly_mf_assemble");

@@ -23,7 +23,7 @@ void fh_launch_dense_op_adjoint(const fh_dense_op_args& a, int ld, hipStream_t s
 // R -= X diag(lam)
 void fh_launch_axpy_cols(cplx* R, const cplx* X, const cplx* lam, int N, int ld, hipStream_t st, const int* skip = nullptr);
 
-// Polynomial handle (h->kind == 3, fh_poly.hip): LUs[e] = P(z_e) for the nf matrices lu_factor_batch is about to factor, in one
+// Polynomial handle (h->kind == FH_KIND_POLYNOMIAL, fh_poly.hip): LUs[e] = P(z_e) for the nf matrices lu_factor_batch is about to factor, in one
 // pass over the coefficients; prec 64: complex128 factors, 32: complex64.
 // A term handle (fh_poly::terms) forms T(z_e) = sum_k f_k(z_e) A_k from its node table instead; a shift that is no contour
 // node of that table is an error.

@@ -1,6 +1,6 @@
 // fh_ingest.hpp -- host-side ingest of a sparse pencil (pure C++17, no HIP): everything feasthip_set_csr does before the
 // upload.  Kept free of device headers so that tests/host_ingest_harness.cpp can compile it with gcc under
-// AddressSanitizer / UBSan and fuzz it on the CPU (tests/test_ingest_sanitizer.py); fh_api.hip includes the same file.
+// AddressSanitizer / UBSan and fuzz it on the CPU (tests/test_ingest_sanitizer.py); fh_problem.hip includes the same file.
 //
 //   (CSR | CSC, 0- | 1-based, unsorted rows, duplicates)  ->  0-based CSR rows sorted by column          to_csr0
 //   A, B -> union pattern, duplicates summed, band widths kl / ku                                         fh_prepare_csr
@@ -24,7 +24,7 @@ struct host_csr {
     std::vector<VT> val;
 };
 
-// value arithmetic the ingest needs: zero and sum (double here; fh_api.hip adds the complex overloads before including)
+// value arithmetic the ingest needs: zero and sum (double here; fh_problem.hip adds the complex overloads before including)
 static inline double fh_ing_zero(double) { return 0.0; }
 static inline double fh_ing_add(double a, double b) { return a + b; }
 

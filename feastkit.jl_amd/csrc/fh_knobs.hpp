@@ -23,7 +23,7 @@ inline double double_or(const char* name, double dflt) { const char* e = str_or_
 // ---- diagnostics and the in-library profiler ----
 // host-side phase timings and plan decisions on stderr.  Per call.
 inline bool debug_timing() { return present("FH_DEBUG_TIMING"); }
-// HIP-event sampling period of the profiler (1 = every launch; dflt is the macro of the same name in fh_api.hip).  Per process.
+// HIP-event sampling period of the profiler (1 = every launch; dflt is the macro of the same name in fh_handle.hip).  Per process.
 inline int prof_period(int dflt) { static const int v = std::max(1, int_or("FH_PROF_PERIOD", dflt)); return v; }
 // profiler creates and destroys an event pair per sample instead of recycling them through a pool.  Per process.
 inline bool prof_nopool() { static const bool v = present("FH_PROF_NOPOOL"); return v; }

@@ -1,4 +1,4 @@
-// fh_operator.hip -- operator handles (feasthip_set_operator, h->kind == 4): matrix-free FEAST on the caller's products.
+// fh_operator.hip -- operator handles (feasthip_set_operator, h->kind == FH_KIND_OPERATOR): matrix-free FEAST on the caller's products.
 //
 // The handle holds no matrix.  Where a dense or CSR handle launches its operator kernel, fh_apply_operator (fh_api.hip) comes
 // here: the caller's callback forms A X_e and B X_e for ALL nodes of the call in one go each, into scratch panels of the
@@ -24,7 +24,7 @@
 #include "fh_device.hpp"
 #include "fh_kernels.hpp"
 #include "fh_krylov.hpp"
-#include "../../include/feasthip.h"
+#include "fh_host.hpp"
 
 #include <algorithm>
 #include <string>
@@ -125,8 +125,7 @@ int fh_apply_user_operator(feasthip_ctx* h, int ld, const fh_userop_call& c) {
 }
 
 extern "C" int feasthip_set_operator(feasthip_handle h, int64_t N, feasthip_apply_fn apply, void* user, int flags) {
-    if (!h) return FEASTHIP_ERROR_INTERNAL;
-    if (h->poisoned) { h->last_error = "handle poisoned by an earlier device failure: destroy it"; return FEASTHIP_ERROR_INTERNAL; }
+    if (int gate = fh_gate(h)) return gate;
     if (N <= 0 || N > INT32_MAX / FH_MAX_LD) { h->last_error = "feasthip_set_operator: N out of range"; return FEASTHIP_ERROR_N; }
     if (!apply) { h->last_error = "feasthip_set_operator: null callback"; return FEASTHIP_ERROR_N; }
     const int known = FEASTHIP_OP_B_IDENTITY | FEASTHIP_OP_COMPLEX | FEASTHIP_OP_SYMMETRIC;
@@ -143,6 +142,6 @@ extern "C" int feasthip_set_operator(feasthip_handle h, int64_t N, feasthip_appl
     h->dense.b_identity = (flags & FEASTHIP_OP_B_IDENTITY) ? 1 : 0;
     h->op.apply = (fh_apply_fn)apply; h->op.user = user;
     h->op.symmetric = (flags & FEASTHIP_OP_SYMMETRIC) ? 1 : 0;
-    h->kind = 4;
+    h->kind = FH_KIND_OPERATOR;
     return 0;
 }

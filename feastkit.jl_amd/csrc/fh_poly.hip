@@ -9,7 +9,7 @@
 // method's calls with host tables of the f_k where a polynomial handle forms powers (the feasthip_nep_* entry points; one body
 // per call, shared with its feasthip_poly_* sibling), through the table-form kernels k_form_terms, k_mf_assemble_terms
 // (fh_dense.hip) and k_spmm_terms; the sum over the terms is fh_term_sum (fh_common.hpp), the sibling of fh_horner.
-// A term-OPERATOR handle (feasthip_set_term_operator, h->kind == 5, fh_termop.hip) is a term handle without matrices: the same
+// A term-OPERATOR handle (feasthip_set_term_operator, h->kind == FH_KIND_TERM_OPERATOR, fh_termop.hip) is a term handle without matrices: the same
 // calls under a Krylov solver, with the caller's callback and k_terms_combine where the others launch a product kernel.
 // The steps they share exist once: Horner over the coefficients is fh_horner (fh_common.hpp), the batched row gather of the
 // three SpMM kernels is POLY_ROW_GATHER, the kernels' coefficient table is fh_poly_coef_ptrs (fh_common.hpp).
@@ -40,12 +40,11 @@
 #include "fh_device.hpp"
 #include "fh_kernels.hpp"
 #include "fh_krylov.hpp"
+#include "fh_host.hpp"
 #include "fh_dense.hpp"
 #include "fh_banded.hpp"
-#include "../../include/feasthip.h"
 
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <cstring>
 
@@ -585,8 +584,6 @@ __global__ __launch_bounds__(FH_BLOCK) void k_spmm_fanin_trace(fh_fanin_args a) 
 // ---------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------
-static inline double poly_now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-
 // true: the handle's solver is a Krylov method on the operator P(z_e) (CSR coefficients only)
 static bool poly_krylov(const feasthip_ctx* h) {
     return h->solver == FEASTHIP_SOLVER_BICGSTAB || h->solver == FEASTHIP_SOLVER_COCG || h->solver == FEASTHIP_SOLVER_GMRES;
@@ -600,13 +597,12 @@ static bool poly_krylov(const feasthip_ctx* h) {
 // handle with its node table set for the current contour).
 enum { POLY_POWERS = 0, POLY_ANY_FORM = 1, POLY_TERMS = 2 };
 static int poly_check(feasthip_ctx* h, const char* what, int64_t m, int64_t maxm, int form = POLY_POWERS) {
-    if (!h) return FEASTHIP_ERROR_INTERNAL;
-    if (h->poisoned) { h->last_error = "handle poisoned by an earlier device failure: destroy it"; return FEASTHIP_ERROR_INTERNAL; }
+    if (int gate = fh_gate(h)) return gate;
     const char* why = nullptr;
-    const bool top = h->kind == 5;
+    const bool top = h->kind == FH_KIND_TERM_OPERATOR;
     if (top && (why = fh_termop_solver_why(h, h->shifted ? FEASTHIP_SOLVER_SHIFTED_COCG : h->block ? FEASTHIP_SOLVER_BLOCK_COCG : h->solver, h->factor_precision))) {}
-    else if (h->kind == 4) why = "an operator handle (feasthip_set_operator) has no polynomial or term form: it takes the pencil entry points under the Krylov solvers FEASTHIP_SOLVER_BICGSTAB, _COCG or _GMRES";
-    else if (h->kind != 3 && !top) why = "needs a polynomial handle (feasthip_set_polynomial); a dense or CSR handle takes the entry points without poly_";
+    else if (h->kind == FH_KIND_OPERATOR) why = "an operator handle (feasthip_set_operator) has no polynomial or term form: it takes the pencil entry points under the Krylov solvers FEASTHIP_SOLVER_BICGSTAB, _COCG or _GMRES";
+    else if (h->kind != FH_KIND_POLYNOMIAL && !top) why = "needs a polynomial handle (feasthip_set_polynomial); a dense or CSR handle takes the entry points without poly_";
     else if (top && form == POLY_POWERS) why = "forms powers of lambda or linearised columns, which a split form does not have: " FH_TERMOP_TAKES ", through the feasthip_nep_* calls with tables of the f_k";
     else if (h->poly.terms && form == POLY_POWERS)
         why = "forms powers of lambda, which a term handle (feasthip_set_terms) does not have: use feasthip_nep_solve_dev, feasthip_nep_eval_cols_dev, "
@@ -630,21 +626,13 @@ static int poly_check(feasthip_ctx* h, const char* what, int64_t m, int64_t maxm
     return 0;
 }
 // the widest subspace of a projected-method call: N on a polynomial, term or term-operator handle
-static int64_t poly_rows(const feasthip_ctx* h) { return h && (h->kind == 3 || h->kind == 5) ? h->dense.N : 1; }
+static int64_t poly_rows(const feasthip_ctx* h) { return h && (h->kind == FH_KIND_POLYNOMIAL || h->kind == FH_KIND_TERM_OPERATOR) ? h->dense.N : 1; }
 // a feasthip_nep_* call that solves with T(z_e): the node table belongs to the handle's contour
 static int nep_check_nodes(feasthip_ctx* h, const char* what) {
     const size_t ne = h->zne.size();
     bool ok = ne > 0 && h->poly.fnode_z.size() == ne && h->poly.fnode.size() == ne * (size_t)(h->poly.degree + 1);
     for (size_t e = 0; ok && e < ne; ++e) ok = h->poly.fnode_z[e].x == h->zne[e].x && h->poly.fnode_z[e].y == h->zne[e].y;
     if (!ok) { h->last_error = std::string(what) + ": no node values for the current contour (feasthip_set_contour, then feasthip_nep_set_node_values)"; return FEASTHIP_ERROR_FPM; }
-    return 0;
-}
-
-// the end of an entry point: everything queued has run, the profile is read, a launch failure is reported
-static int poly_finish(feasthip_ctx* h) {
-    FH_CHECK(hipStreamSynchronize(h->stream));
-    fh_prof_collect(h);
-    FH_CHECK(hipGetLastError());
     return 0;
 }
 
@@ -764,8 +752,7 @@ static int poly_lin_product(feasthip_ctx* h, const poly_coefs& pc, int which, in
 // of n doubles, for ||A_k||_F of the backward error (ingest arithmetic, once per problem).  poly_set_commit: the handle is a
 // polynomial one.
 static int poly_set_check(feasthip_ctx* h, const char* what, int64_t N, int64_t Nmax, int degree, bool terms = false) {
-    if (!h) return FEASTHIP_ERROR_INTERNAL;
-    if (h->poisoned) { h->last_error = "handle poisoned by an earlier device failure: destroy it"; return FEASTHIP_ERROR_INTERNAL; }
+    if (int gate = fh_gate(h)) return gate;
     if (N <= 0 || N > Nmax) { h->last_error = std::string(what) + ": N out of range"; return FEASTHIP_ERROR_N; }
     if (degree < 1 || degree > FEASTHIP_POLY_MAX_DEGREE) {
         h->last_error = std::string(what) + (terms ? ": nterms must be 2 .. FEASTHIP_POLY_MAX_DEGREE + 1" : ": degree must be 1 .. FEASTHIP_POLY_MAX_DEGREE");
@@ -788,7 +775,7 @@ static double poly_sumsq(const double* v, size_t n) {
 }
 static int poly_set_commit(feasthip_ctx* h, bool terms = false) {
     h->adjoint = 0;
-    h->kind = 3;
+    h->kind = FH_KIND_POLYNOMIAL;
     h->poly.terms = terms ? 1 : 0;
     if (terms) { h->solver = FEASTHIP_SOLVER_LU; h->shifted = h->block = 0; h->factor_precision = 64; }
     return 0;
@@ -967,7 +954,7 @@ static int poly_solve_body(feasthip_ctx* h, const std::string& what, double z_re
     int rc;
     if (!dR || !dY) { h->last_error = what + ": null argument"; return FEASTHIP_ERROR_INTERNAL; }
     FH_CHECK(hipSetDevice(h->device));
-    const double t0 = poly_now();
+    const double t0 = fh_now_s();
     const int N = (int)h->dense.N;
     if (stats) memset(stats, 0, sizeof(*stats));
     int worst = 0;
@@ -988,9 +975,9 @@ static int poly_solve_body(feasthip_ctx* h, const std::string& what, double z_re
         if (stats) stats->factorizations += nfact;
         worst = std::max(worst, status);
     }
-    if ((rc = poly_finish(h))) return rc;
+    if ((rc = fh_finish(h))) return rc;
     if (poly_krylov(h)) rec.publish(h, it, stats);
-    if (stats) stats->seconds_total = poly_now() - t0;
+    if (stats) stats->seconds_total = fh_now_s() - t0;
     return worst;
 }
 extern "C" int feasthip_poly_solve_dev(feasthip_handle h, double z_re, double z_im, int64_t m64, const void* dR, void* dY,
@@ -1009,7 +996,7 @@ extern "C" int feasthip_nep_solve_dev(feasthip_handle h, int node, int64_t m64, 
 // Qproj = sum_e weight_scale w_e (z_e B_lin - A_lin)^-1 (B_lin Q) on dN x m column-major blocks
 extern "C" int feasthip_poly_contour_apply_dev(feasthip_handle h, int64_t m64, const void* dQ, void* dQproj, int* node_status,
                                                feasthip_stats* stats) {
-    int rc = poly_check(h, "feasthip_poly_contour_apply_dev", m64, h && h->kind == 3 ? h->dense.N * h->poly.degree : 1);
+    int rc = poly_check(h, "feasthip_poly_contour_apply_dev", m64, h && h->kind == FH_KIND_POLYNOMIAL ? h->dense.N * h->poly.degree : 1);
     if (rc) return rc;
     if (!dQ || !dQproj) { h->last_error = "feasthip_poly_contour_apply_dev: null argument"; return FEASTHIP_ERROR_INTERNAL; }
     if (h->zne.empty()) { h->last_error = "feasthip_poly_contour_apply_dev: no contour set (feasthip_set_contour)"; return FEASTHIP_ERROR_FPM; }
@@ -1020,7 +1007,7 @@ extern "C" int feasthip_poly_contour_apply_dev(feasthip_handle h, int64_t m64, c
         return FEASTHIP_ERROR_FPM;
     }
     FH_CHECK(hipSetDevice(h->device));
-    const double t0 = poly_now();
+    const double t0 = fh_now_s();
     const int N = (int)h->dense.N, d = h->poly.degree, ne = (int)h->zne.size();
     const int64_t dN = (int64_t)d * N;
     if (stats) memset(stats, 0, sizeof(*stats));
@@ -1073,8 +1060,8 @@ extern "C" int feasthip_poly_contour_apply_dev(feasthip_handle h, int64_t m64, c
         if (stats) stats->factorizations += nfact;
         if (node_status) for (int e = 0; e < ne; ++e) node_status[e] = std::max(node_status[e], status[e]);
     }
-    if ((rc = poly_finish(h))) return rc;
-    if (stats) stats->seconds_total = poly_now() - t0;
+    if ((rc = fh_finish(h))) return rc;
+    if (stats) stats->seconds_total = fh_now_s() - t0;
     return 0;
 }
 
@@ -1106,12 +1093,12 @@ static int poly_node_products(feasthip_ctx* h, int which, int64_t m64, const cpl
     c.nodes = ne; c.m = m;
     fh_launch_spmm_poly(h, ld, c);
     for (int e = 0; e < ne; ++e) fh_launch_from_panel(Ys + (size_t)e * panel, ld, N, m, dY + (size_t)e * blockN, N, h->stream);
-    return poly_finish(h);
+    return fh_finish(h);
 }
 
 // Y = A_lin X (which 0) or B_lin X (which 1), dN x m column-major; which 2, 3, 4: poly_node_products
 extern "C" int feasthip_poly_matmul_dev(feasthip_handle h, int which, int64_t m64, const void* dX, void* dY) {
-    int rc = poly_check(h, "feasthip_poly_matmul_dev", m64, h && h->kind == 3 ? h->dense.N * h->poly.degree : 1);
+    int rc = poly_check(h, "feasthip_poly_matmul_dev", m64, h && h->kind == FH_KIND_POLYNOMIAL ? h->dense.N * h->poly.degree : 1);
     if (rc) return rc;
     if (!dX || !dY || which < 0 || which > 4) { h->last_error = "feasthip_poly_matmul_dev: bad argument"; return FEASTHIP_ERROR_INTERNAL; }
     if (which >= 2) return poly_node_products(h, which, m64, (const cplx*)dX, (cplx*)dY);
@@ -1130,7 +1117,7 @@ extern "C" int feasthip_poly_matmul_dev(feasthip_handle h, int which, int64_t m6
         if ((rc = poly_lin_product(h, pc, which, ld, Xs, Ws))) return rc;
         fh_launch_from_panel(Ws, ld, (int)dN, m, (cplx*)dY + (size_t)c0 * dN, dN, h->stream);
     }
-    return poly_finish(h);
+    return fh_finish(h);
 }
 
 // The blocked Gram projection of both methods: out[w] = Q^H W_w, w < nops (raw products, r x r column-major on the host), Q:
@@ -1179,7 +1166,7 @@ static int poly_project_blocks(feasthip_ctx* h, const char* const (&buf)[4], int
 // Aq = Q^H A_lin Q, Sq = Q^H B_lin Q (raw products, r x r column-major on the host) by 64-column panels: block (i, j) is
 // Q_i^H (op Q_j), one linearised product per block column and operator, one Gram launch over the dN rows per block
 extern "C" int feasthip_poly_project_dev(feasthip_handle h, int64_t r64, const void* dQ, void* Aq_host, void* Sq_host) {
-    int rc = poly_check(h, "feasthip_poly_project_dev", r64, h && h->kind == 3 ? h->dense.N * h->poly.degree : 1);
+    int rc = poly_check(h, "feasthip_poly_project_dev", r64, h && h->kind == FH_KIND_POLYNOMIAL ? h->dense.N * h->poly.degree : 1);
     if (rc) return rc;
     if (!dQ || !Aq_host || !Sq_host) { h->last_error = "feasthip_poly_project_dev: null argument"; return FEASTHIP_ERROR_INTERNAL; }
     FH_CHECK(hipSetDevice(h->device));
@@ -1228,7 +1215,7 @@ static int poly_ritz_vectors(feasthip_ctx* h, const poly_coefs& pc, const poly_r
 //   backward_error[j] = || P(lambda_j) x_j^(0) || / (sum_k |lambda_j|^k ||A_k||_F  ||x_j^(0)||),  x^(0) = the first block
 extern "C" int feasthip_poly_ritz_residual_dev(feasthip_handle h, int64_t r64, const void* dQ, const void* V_host, const void* lambda,
                                                int64_t M, int normalize, int use_B, void* dX, double* res, double* backward_error) {
-    int rc = poly_check(h, "feasthip_poly_ritz_residual_dev", r64, h && h->kind == 3 ? h->dense.N * h->poly.degree : 1);
+    int rc = poly_check(h, "feasthip_poly_ritz_residual_dev", r64, h && h->kind == FH_KIND_POLYNOMIAL ? h->dense.N * h->poly.degree : 1);
     if (rc) return rc;
     if (!dQ || !V_host || !lambda || !dX || dQ == dX) { h->last_error = "feasthip_poly_ritz_residual_dev: null argument, or X aliases Q"; return FEASTHIP_ERROR_INTERNAL; }
     if (M < 0 || M > r64) { h->last_error = "feasthip_poly_ritz_residual_dev: M out of range"; return FEASTHIP_ERROR_M0; }
@@ -1287,7 +1274,7 @@ extern "C" int feasthip_poly_ritz_residual_dev(feasthip_handle h, int64_t r64, c
             }
         }
     }
-    return poly_finish(h);
+    return fh_finish(h);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1299,7 +1286,7 @@ extern "C" int feasthip_poly_ritz_residual_dev(feasthip_handle h, int64_t r64, c
 // lam^k) through the dense product on the column-scaled copy W of X (scaled once more per degree).  X is left as it is.
 static int poly_eval_panel(feasthip_ctx* h, const poly_coefs& pc, int ld, const cplx* dlam, const cplx* X, cplx* W, cplx* R) {
     const int N = (int)h->dense.N, d = h->poly.degree;
-    if (h->kind == 5) {          // the callback flavour: one callback per kept term on the panel, then k_terms_combine on the column table
+    if (h->kind == FH_KIND_TERM_OPERATOR) {          // the callback flavour: one callback per kept term on the panel, then k_terms_combine on the column table
         fh_termop_call a;
         memset(&a, 0, sizeof(a));
         a.X = X; a.Y = R; a.F = dlam; a.cols = 1; a.terms = h->top.col_terms; a.nodes = 1;
@@ -1382,7 +1369,7 @@ static int poly_eval_cols_body(feasthip_ctx* h, const std::string& what, int64_t
         if ((rc = poly_eval_panel(h, pc, ld, dlam, Xs, W, R))) return rc;
         fh_launch_from_panel(R, ld, N, m, (cplx*)dR + (size_t)c0 * N, N, h->stream);
     }
-    return poly_finish(h);
+    return fh_finish(h);
 }
 extern "C" int feasthip_poly_eval_cols_dev(feasthip_handle h, int64_t m64, const void* lambda, const void* dX, void* dR) {
     const int rc = poly_check(h, "feasthip_poly_eval_cols_dev", m64, 1 << 20);
@@ -1420,7 +1407,7 @@ static int poly_resinv_body(feasthip_ctx* h, const std::string& what, int64_t m6
             }
         }
     FH_CHECK(hipSetDevice(h->device));
-    const double t0 = poly_now();
+    const double t0 = fh_now_s();
     if (stats) memset(stats, 0, sizeof(*stats));
     if (node_status) for (int e = 0; e < ne; ++e) node_status[e] = 0;
     poly_coefs pc;
@@ -1461,9 +1448,9 @@ static int poly_resinv_body(feasthip_ctx* h, const std::string& what, int64_t m6
         if (stats) stats->factorizations += nfact;
         if (node_status) for (int e = 0; e < ne; ++e) node_status[e] = std::max(node_status[e], status[e]);
     }
-    if ((rc = poly_finish(h))) return rc;
+    if ((rc = fh_finish(h))) return rc;
     if (poly_krylov(h)) rec.publish(h, it, stats);
-    if (stats) stats->seconds_total = poly_now() - t0;
+    if (stats) stats->seconds_total = fh_now_s() - t0;
     return 0;
 }
 extern "C" int feasthip_poly_resinv_apply_dev(feasthip_handle h, int64_t m64, const void* sigma, const void* dX, void* dQ,
@@ -1497,8 +1484,8 @@ extern "C" int feasthip_nep_resinv_apply_dev(feasthip_handle h, int64_t m64, con
 extern "C" int feasthip_poly_estimate_count(feasthip_handle h, int64_t m64, uint64_t seed, const void* G_host, double* samples, void* dV,
                                             int* node_status, feasthip_stats* stats) {
     const char* what = "feasthip_poly_estimate_count";
-    if (h && h->kind == 5 && !h->poisoned) { h->last_error = std::string(what) + ": the count estimate is not provided for operators: " FH_TERMOP_TAKES ", with an integer subspace size"; return FEASTHIP_ERROR_FPM; }
-    int rc = poly_check(h, what, m64, h && h->kind == 3 ? std::min<int64_t>(h->dense.N, 65535) : 1, POLY_ANY_FORM);
+    if (h && h->kind == FH_KIND_TERM_OPERATOR && !h->poisoned) { h->last_error = std::string(what) + ": the count estimate is not provided for operators: " FH_TERMOP_TAKES ", with an integer subspace size"; return FEASTHIP_ERROR_FPM; }
+    int rc = poly_check(h, what, m64, h && h->kind == FH_KIND_POLYNOMIAL ? std::min<int64_t>(h->dense.N, 65535) : 1, POLY_ANY_FORM);
     if (rc) return rc;
     if (h->poly.terms && (rc = nep_check_nodes(h, what))) return rc;
     if (!G_host || !samples) { h->last_error = std::string(what) + ": null argument"; return FEASTHIP_ERROR_INTERNAL; }
@@ -1521,7 +1508,7 @@ extern "C" int feasthip_poly_estimate_count(feasthip_handle h, int64_t m64, uint
     for (int e = 0; e < ne; ++e)
         for (int t = 0; t < ntk; ++t) Gk[(size_t)e * ntk + t] = Gh[(size_t)e * nt + kept[t]];
     FH_CHECK(hipSetDevice(h->device));
-    const double t0 = poly_now();
+    const double t0 = fh_now_s();
     if (stats) memset(stats, 0, sizeof(*stats));
     if (node_status) for (int e = 0; e < ne; ++e) node_status[e] = 0;
     poly_coefs pc;
@@ -1578,9 +1565,9 @@ extern "C" int feasthip_poly_estimate_count(feasthip_handle h, int64_t m64, uint
         if (node_status) for (int e = 0; e < ne; ++e) node_status[e] = std::max(node_status[e], status[e]);
     }
     FH_CHECK(hipMemcpyAsync(samples, dT, (size_t)m64 * 2 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    if ((rc = poly_finish(h))) return rc;
+    if ((rc = fh_finish(h))) return rc;
     if (poly_krylov(h)) rec.publish(h, it, stats);
-    if (stats) stats->seconds_total = poly_now() - t0;
+    if (stats) stats->seconds_total = fh_now_s() - t0;
     return 0;
 }
 
@@ -1598,7 +1585,7 @@ extern "C" int feasthip_poly_project_reduced_dev(feasthip_handle h, int64_t r64,
     for (int k = 0; k <= d; ++k) out[k] = (cplx*)Ahat_host + (size_t)k * r64 * r64;
     return poly_project_blocks(h, {"pq_Qi", "pq_Qj", "pq_W", "pq_G"}, N, (int)r64, d + 1, (const cplx*)dQ, out, [&](int ld, const cplx* Qj, cplx* W) {
         const size_t panel = (size_t)N * ld;
-        if (h->kind == 5) return fh_term_products(h, ld, Qj, W) < 0 ? (int)FEASTHIP_ERROR_INTERNAL : 0;          // the callback flavour
+        if (h->kind == FH_KIND_TERM_OPERATOR) return fh_term_products(h, ld, Qj, W) < 0 ? (int)FEASTHIP_ERROR_INTERNAL : 0;          // the callback flavour
         fh_fan_out outs[FH_FAN_MAX];
         for (int k = 0; k <= d; ++k) outs[k] = fh_fan_out{k, W + (size_t)k * panel, false, false};
         if (h->poly.sparse) poly_fan(h, ld, Qj, outs, d + 1);
@@ -1655,11 +1642,11 @@ static int poly_ritz_eval_body(feasthip_ctx* h, const std::string& what, int64_t
             backward_error[(int64_t)j * ld + c] = be;
         }
     }
-    return poly_finish(h);
+    return fh_finish(h);
 }
 extern "C" int feasthip_poly_ritz_eval_dev(feasthip_handle h, int64_t r64, const void* dQ, int64_t ncand, const void* Y_host,
                                            const void* theta, void* dX, double* backward_error) {
-    const int rc = poly_check(h, "feasthip_poly_ritz_eval_dev", r64, h && h->kind == 3 ? h->dense.N : 1);
+    const int rc = poly_check(h, "feasthip_poly_ritz_eval_dev", r64, h && h->kind == FH_KIND_POLYNOMIAL ? h->dense.N : 1);
     return rc ? rc : poly_ritz_eval_body(h, "feasthip_poly_ritz_eval_dev", r64, dQ, ncand, Y_host, theta, dX, backward_error);
 }
 // Term handle: X = Q Y with unit columns and backward_error[i] = || sum_k F_theta[i][k] A_k x_i || / sum_k |F_theta[i][k]| ||A_k||_F
@@ -1667,7 +1654,7 @@ extern "C" int feasthip_poly_ritz_eval_dev(feasthip_handle h, int64_t r64, const
 extern "C" int feasthip_nep_ritz_eval_dev(feasthip_handle h, int64_t r64, const void* dQ, int64_t ncand, const void* Y_host,
                                           const void* F_theta, void* dX, double* backward_error) {
     const int rc = poly_check(h, "feasthip_nep_ritz_eval_dev", r64, poly_rows(h), POLY_TERMS);
-    if (!rc && h->kind == 5 && !h->top.norms_set) {
+    if (!rc && h->kind == FH_KIND_TERM_OPERATOR && !h->top.norms_set) {
         h->last_error = "feasthip_nep_ritz_eval_dev: a term-operator handle has no matrices to take ||A_k||_F from: set the norms of the backward error with feasthip_set_term_norms";
         return FEASTHIP_ERROR_FPM;
     }

@@ -185,7 +185,7 @@ __global__ __launch_bounds__(FH_BLOCK, 4) void k_spmm(fh_spmm_args a) {
             if (!BIDENT) nb = bval[k0n + l16];
         }
         // FAR GATHER, one row step ahead.  Ingest puts the nonzero with the largest column index first in its row
-        // (fh_api.hip): in an ascending sweep that is the one X row of the step that no workgroup has touched yet -- it
+        // (fh_ingest.hpp): in an ascending sweep that is the one X row of the step that no workgroup has touched yet -- it
         // comes from HBM, the other gathers from L1/L2 -- and a wave that waits for it every step keeps exactly one HBM
         // request in flight (measured: 2.9 us per 4-row step whatever the row length, 2.0-2.5 TB/s algorithmic).  Slot 0 of
         // the NEXT row is therefore gathered while this row is computed: issued after this row's own gathers, so the
@@ -322,7 +322,7 @@ __global__ __launch_bounds__(FH_BLOCK, 4) void k_spmm(fh_spmm_args a) {
 // Locality: XCD group g = blockIdx & 7 owns the row slice g; its workgroups sweep the slice as a moving band of
 // (workgroups per group) x 16 rows, so the X rows a band needs (band + the two stencil planes) stay in that XCD's L2 or,
 // for the far planes of a wide stencil, in the Infinity Cache.  Row order inside a row: the far gather (largest column,
-// first in its row: fh_api.hip ingest) is issued first so that it has the longest time to arrive.
+// first in its row: fh_ingest.hpp) is issued first so that it has the longest time to arrive.
 // ------------------------------------------------------------------------------------
 #ifndef FH_ROW_THREADS
 #define FH_ROW_THREADS 1024
@@ -458,7 +458,7 @@ __global__ __launch_bounds__(FH_ROW_THREADS, FH_ROW_WAVES) void k_spmm_row(fh_sp
 }
 
 // ------------------------------------------------------------------------------------
-// LDS-window SpMM for a matrix that ingest renumbered into row blocks (fh_api.hip: fh_block_partition; complex128 panels).
+// LDS-window SpMM for a matrix that ingest renumbered into row blocks (fh_ingest.hpp: fh_block_partition; complex128 panels).
 // OPT-IN (FH_REORDER=1|2): measured SLOWER than k_spmm on cfg 3 -- 57 us against 33 us per node -- see below.
 //
 // k_spmm gathers every X row a matrix row touches from L1/L2: 8 gathers of 256 B per row and 16-column tile.  Here a

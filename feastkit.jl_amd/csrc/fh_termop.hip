@@ -1,4 +1,4 @@
-// fh_termop.hip -- term-operator handles (feasthip_set_term_operator, h->kind == 5): the split form
+// fh_termop.hip -- term-operator handles (feasthip_set_term_operator, h->kind == FH_KIND_TERM_OPERATOR): the split form
 //     T(z) X = sum_k f_k(z) (A_k X),   k = 0 .. nt-1,   2 <= nt <= 9,
 // on the caller's products A_k X.  The handle is a term handle (fh_poly.hip: the feasthip_nep_* entry points, host tables of
 // the f_k) that holds no matrix: where a term handle with matrices launches k_spmm_terms or the dense product, the callback
@@ -35,7 +35,7 @@
 #include "fh_device.hpp"
 #include "fh_kernels.hpp"
 #include "fh_krylov.hpp"
-#include "../../include/feasthip.h"
+#include "fh_host.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -216,8 +216,7 @@ int fh_term_products(feasthip_ctx* h, int ld, const cplx* X, cplx* W) {
 extern "C" int feasthip_set_term_operator(feasthip_handle h, int64_t N, int nterms, feasthip_apply_fn apply, void* user, int flags,
                                           unsigned identity_mask, int64_t scratch_bytes) {
     const char* what = "feasthip_set_term_operator";
-    if (!h) return FEASTHIP_ERROR_INTERNAL;
-    if (h->poisoned) { h->last_error = "handle poisoned by an earlier device failure: destroy it"; return FEASTHIP_ERROR_INTERNAL; }
+    if (int gate = fh_gate(h)) return gate;
     if (N <= 0 || N > INT32_MAX / FH_MAX_LD) { h->last_error = std::string(what) + ": N out of range"; return FEASTHIP_ERROR_N; }
     if (nterms < 2 || nterms > FH_TERMS_MAX) { h->last_error = std::string(what) + ": nterms must be 2 .. FEASTHIP_POLY_MAX_DEGREE + 1"; return FEASTHIP_ERROR_FPM; }
     const unsigned all = (1u << nterms) - 1u;
@@ -246,13 +245,13 @@ extern "C" int feasthip_set_term_operator(feasthip_handle h, int64_t N, int nter
     const bool krylov = h->solver == FEASTHIP_SOLVER_BICGSTAB || h->solver == FEASTHIP_SOLVER_GMRES || (h->solver == FEASTHIP_SOLVER_COCG && h->op.symmetric);
     if (!krylov || h->shifted || h->block || h->factor_precision != 64) { h->solver = FEASTHIP_SOLVER_GMRES; h->shifted = h->block = 0; h->factor_precision = 64; }
     h->node_kinds.clear();
-    h->kind = 5;
+    h->kind = FH_KIND_TERM_OPERATOR;
     return 0;
 }
 
 extern "C" int feasthip_set_term_norms(feasthip_handle h, const double* norms) {
     if (!h) return FEASTHIP_ERROR_INTERNAL;
-    if (h->kind != 5) { h->last_error = "feasthip_set_term_norms: needs a term-operator handle (feasthip_set_term_operator)"; return FEASTHIP_ERROR_FPM; }
+    if (h->kind != FH_KIND_TERM_OPERATOR) { h->last_error = "feasthip_set_term_norms: needs a term-operator handle (feasthip_set_term_operator)"; return FEASTHIP_ERROR_FPM; }
     if (!norms) { h->last_error = "feasthip_set_term_norms: null argument"; return FEASTHIP_ERROR_FPM; }
     for (int k = 0; k <= h->poly.degree; ++k)
         if (!(norms[k] > 0.0) || !std::isfinite(norms[k])) {

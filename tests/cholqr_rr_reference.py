@@ -1,5 +1,5 @@
 """numpy restatement of the staged rank-revealing Cholesky-QR (FEASTHIP_ORTHO_CHOLQR_RR): fh_cholqr::pivoted_stage
-(csrc/fh_cholqr.hpp), k_pchol_stage (csrc/fh_blockops.hip) and the stage loop of fh_ortho_staged (csrc/fh_api.hip), with the
+(csrc/fh_cholqr.hpp), k_pchol_stage (csrc/fh_blockops.hip) and the stage loop of fh_ortho_staged (csrc/fh_ortho.hip), with the
 same stages, window and stop rule.  The rank rule is that of _feast_qr_compress! (src/core/feast_aux.jl:101-131)."""
 import numpy as np
 

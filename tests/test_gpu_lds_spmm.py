@@ -1,4 +1,4 @@
-"""The opt-in LDS-window SpMM path (ingest renumbering into 128-row blocks + k_spmm_lds, fh_sparse.hip / fh_api.hip;
+"""The opt-in LDS-window SpMM path (ingest renumbering into 128-row blocks + k_spmm_lds, fh_sparse.hip / fh_ingest.hpp;
 FH_LDS_SPMM=1).  The kernel is off by default -- it measured slower than the gather kernels on cfg 3
 -- but it is the north_star's "CSR SpMV staging rows through LDS" and stays correct; the renumbering itself is ON by
 default for wide patterns since round 3 (it feeds the row-per-wave kernel).  A worker process with FH_REORDER=2 pushes
