@@ -64,6 +64,8 @@ SYMBOLS = {
     "feasthip_set_solver": (_i, [_vp, _i, _d, _d, _i, _i, _i, _i]),
     "feasthip_set_node_solver": (_i, [_vp, _i, _vp]),
     "feasthip_direct_plan_bytes": (_i, [_vp, _i, _pi64, _pi64]),
+    "feasthip_set_preconditioner": (_i, [_vp, _i, _vp, _i, _vp]),
+    "feasthip_last_precond_sweep": (_i, [_vp, _pi, _pi, _pi64, _pi64, _pi64, _pi]),
     "feasthip_set_column_mask": (_i, [_vp, _i64, _vp]),
     "feasthip_rayleigh_ritz_dev": (_i, [_vp, _i64, _vp, _d, _d, _i, _vp, _vp, _vp, _vp]),
     "feasthip_contour_apply": (_i, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _ps]),

@@ -12,7 +12,7 @@ import scipy.sparse as sp
 
 from .engine import HipEngine
 from .contour import feast_contour, feast_gcontour
-from .hip_backend import (DIRECT_SOLVERS, ESTIMATE_SEED, check_direct_nodes, check_ortho, check_two_sided, feast_hip_estimate,
+from .hip_backend import (DIRECT_SOLVERS, ESTIMATE_SEED, check_direct_nodes, check_ortho, check_precond, check_two_sided, feast_hip_estimate,
                           feast_hip_general, feast_hip_general_two_sided, feast_hip_hermitian, feast_hip_polynomial, feast_hip_polynomial_projected,
                           POLY_METHODS, POLY_RESIDUALS, POLY_SET_ASIDE, feast_hip_nonlinear, feast_hip_poly_estimate, nep_functions,
                           nep_table)
@@ -260,7 +260,7 @@ def _engine(engine, device):
 def feast(A, B=None, interval=None, *, M0=10, fpm=None, backend="hip", solver="direct", solver_tol=0.0,
           solver_maxiter=None, solver_restart=30, warm_start=None, inner_rtol=None, real_projection=None,
           inner_precision=64, group=None, engine=None, device=0, Q0=None, contour=None, contour_policy=None,
-          keep_factors=False, seed=None, direct_nodes=None, ortho="mgs"):
+          keep_factors=False, seed=None, direct_nodes=None, ortho="mgs", precond=None, precond_shifts=1):
     """feast(A, [B,] (Emin, Emax); M0, fpm, backend=:hip) for real-symmetric / Hermitian
     dense (numpy) or sparse (scipy) matrices.  Real input is complexified and the result is
     real.(q), exactly as feast_sygv!/feast_scsrgv! do (src/dense/feast_dense.jl:362-387).
@@ -283,10 +283,21 @@ def feast(A, B=None, interval=None, *, M0=10, fpm=None, backend="hip", solver="d
     ``ortho``: what orthonormalises a rank-deficient subspace (every loop of an exact solver): "mgs", the column-pivoted
     Gram-Schmidt (default), or "cholqr_rr", the staged rank-revealing Cholesky-QR; same rank rule.  ``stats["ortho"]`` has one
     entry per loop: method used ("cholqr" = the full-rank fast path), stages, fell_back, rank.
+    ``precond="shift"`` (sparse input, ``solver="gmres"``): the GMRES sweeps are preconditioned by the sparse LU of
+    z_p B - A at a few pivot shifts z_p -- one factorisation serves every node of its pivot, so the call holds
+    ``precond_shifts`` factors where ``solver="sparse_direct"`` holds one per node (feasthip_set_preconditioner).
+    ``precond_shifts``: an int k (default 1) -- the contour's nodes in order are cut into k arcs of equal count (+-1), each
+    arc's pivot is its middle node -- or a list of complex pivots off the real axis (every node takes the nearest).  Restarted
+    GMRES under ONE pivot stalls when more eigenvalues lie near the contour than the restart length: raise ``solver_restart``
+    or ``precond_shifts``.  Any other solver, dense input, ``inner_precision=32``, ``group=``, ``direct_nodes=``,
+    ``fpm[14] = 2`` and ``M0="auto"`` raise ValueError.  ``stats["precond"]`` has one entry per loop: pivots, node_pivot,
+    factorizations, substitution_sweeps, lock_steps per node, factor_bytes, fell_back.  The factors go when the call returns
+    (``keep_factors``).
     """
     if isinstance(M0, str):
         if M0 != "auto":
             raise ValueError("M0 must be an integer or 'auto'")
+        check_precond(precond, precond_shifts, auto_m0=True)
         return _feast_auto(feast, A, B, interval, fpm=fpm, backend=backend, solver=solver, solver_tol=solver_tol,
                            solver_maxiter=solver_maxiter, solver_restart=solver_restart, warm_start=warm_start,
                            inner_rtol=inner_rtol, real_projection=real_projection, inner_precision=inner_precision,
@@ -300,6 +311,8 @@ def feast(A, B=None, interval=None, *, M0=10, fpm=None, backend="hip", solver="d
         raise ValueError("Matrix A must be square")
     if B is not None and B.shape != A.shape:
         raise ValueError("Matrix B must match size of A")
+    check_precond(precond, precond_shifts, sparse=sp.issparse(A), solver=solver, inner_precision=inner_precision, group=group,
+                  direct_nodes=direct_nodes, estimate=fpm is not None and int(fpm[14]) == 2)
     _check_direct_nodes_early(direct_nodes, A, solver, fpm, 2, contour)
     check_ortho(ortho)
     eng = _engine(engine, device)
@@ -418,7 +431,8 @@ def feast(A, B=None, interval=None, *, M0=10, fpm=None, backend="hip", solver="d
                                   warm_start=warm_start, inner_rtol=inner_rtol, real_projection=real_projection,
                                   inner_precision=inner_precision, group=group, Q0=Q0, contour=contour,
                                   contour_policy=contour_policy, eps_floor=float(np.sqrt(np.finfo(np.float32).eps)) if single else 0.0,
-                                  abort_check=abort_check, direct_nodes=None if dn_ignored else direct_nodes, ortho=ortho)
+                                  abort_check=abort_check, direct_nodes=None if dn_ignored else direct_nodes, ortho=ortho,
+                                  precond=precond, precond_shifts=precond_shifts)
         if dn_ignored and isinstance(res.stats, dict):
             res.stats["direct_nodes"] = {"ignored": "direct solver in force"}
         if (res.info == 5 and substituted is not None and substituted.get("used") in ("cocg", "bicgstab") and group is None
@@ -488,7 +502,7 @@ def _two_sided_sparse_route(A, B, solver, nodes, engine, device):
 def feast_general(A, B=None, center=0.0, radius=1.0, *, M0=10, fpm=None, backend="hip", solver="direct",
                   solver_tol=0.0, solver_maxiter=500, solver_restart=30, group=None, engine=None, device=0, Q0=None,
                   inner_precision=64, contour=None, keep_factors=False, seed=None, direct_nodes=None, ortho="mgs",
-                  two_sided=False, QL0=None):
+                  two_sided=False, QL0=None, precond=None, precond_shifts=1):
     """feast_general(A, [B,] center, radius; M0, fpm): src/interfaces/feast_interfaces.jl:274-379.
     ``two_sided=True`` (``solver="direct"``; sparse input also ``"sparse_direct"`` / ``"banded"``): the two-sided method -- a
     left subspace from conjugate-transposed solves on the LU factors of the right sweep, oblique projection, both residuals
@@ -504,10 +518,12 @@ def feast_general(A, B=None, center=0.0, radius=1.0, *, M0=10, fpm=None, backend
     solver, ``inner_precision=32``, ``group=`` and ``direct_nodes=`` raise ValueError.
     ``keep_factors``, ``direct_nodes``, ``ortho``: as in feast() (this variant never orthonormalises its subspace, so ``ortho``
     changes nothing it computes).  ``fpm[14] = 2`` and ``M0="auto"``: as in feast(), on the full contour of the
-    circle (the samples are complex; M = round(Re mean))."""
+    circle (the samples are complex; M = round(Re mean)).
+    ``precond``, ``precond_shifts``: as in feast(), on the full contour of the circle; ``two_sided=True`` raises ValueError too."""
     if isinstance(M0, str):
         if M0 != "auto":
             raise ValueError("M0 must be an integer or 'auto'")
+        check_precond(precond, precond_shifts, auto_m0=True)
         return _feast_auto(feast_general, A, B, center, radius, fpm=fpm, backend=backend, solver=solver, solver_tol=solver_tol,
                            solver_maxiter=solver_maxiter, solver_restart=solver_restart, group=group, engine=engine,
                            device=device, Q0=Q0, inner_precision=inner_precision, contour=contour, keep_factors=keep_factors,
@@ -520,6 +536,8 @@ def feast_general(A, B=None, center=0.0, radius=1.0, *, M0=10, fpm=None, backend
         raise ValueError("radius must be positive")
     if two_sided:
         check_two_sided(sp.issparse(A), solver, inner_precision, group, direct_nodes)
+    check_precond(precond, precond_shifts, sparse=sp.issparse(A), solver=solver, inner_precision=inner_precision, group=group,
+                  direct_nodes=direct_nodes, two_sided=two_sided, estimate=fpm is not None and int(fpm[14]) == 2)
     _check_direct_nodes_early(direct_nodes, A, solver, fpm, 8, contour)
     check_ortho(ortho)
     single = _single_precision(A, B)
@@ -575,7 +593,8 @@ def feast_general(A, B=None, center=0.0, radius=1.0, *, M0=10, fpm=None, backend
             res = feast_hip_general(eng, A, B, complex(center), float(radius), M0, fpm, solver=solver, inner_precision=inner_precision,
                                     solver_tol=solver_tol, solver_maxiter=solver_maxiter,
                                     solver_restart=solver_restart, group=group, Q0=Q0, contour=contour, eps_floor=eps_floor,
-                                    direct_nodes=None if dn_ignored else direct_nodes, ortho=ortho)
+                                    direct_nodes=None if dn_ignored else direct_nodes, ortho=ortho, precond=precond,
+                                    precond_shifts=precond_shifts)
         if dn_ignored and isinstance(res.stats, dict):
             res.stats["direct_nodes"] = {"ignored": "direct solver in force"}
         if substituted is not None and isinstance(res.stats, dict):

@@ -9,6 +9,7 @@
 #include "fh_banded.hpp"
 #include "fh_comm.hpp"
 #include "fh_policy.hpp"       // fh_column_failed
+#include "fh_precond.hpp"      // nearest_pivot
 #include "fh_knobs.hpp"
 
 #include <thread>
@@ -893,16 +894,22 @@ static int fh_block_cocg(feasthip_ctx* h, int ld, int m, int nodes, const std::v
 // and the host adds it after the synchronisation of the next cycle start.  (Counting queued steps made the budget left for a
 // column that the restart's true residual reactivates, and spmm_calls, depend on host/device timing.)
 // ---------------------------------------------------------------------------------------
+// Preconditioned (pc != null, feasthip_set_preconditioner; a CSR problem): the same cycles in the variable u = M x, which lives
+// in X; the operator is I + c_e B M^-1 -- one substitution on the pivot factors of the batch's nodes into the T panels, then
+// k_precond_op -- at every cycle start and every step.  u0 = M x0 is one product of the plain operator with the pivot's
+// coefficients (skipped for a zero guess, whose first cycle start needs no substitution either); after the last cycle
+// x = M^-1 u goes back into X and one more plain product forms the true residual b - S_e x, whose norm is the one reported.
 int fh_gmres(feasthip_ctx* h, int ld, int m, int nodes_all, const std::vector<cplx>& z, const cplx* RHS, cplx* X,
-             size_t stride, fh_solve_result& res) {
+             size_t stride, fh_solve_result& res, fh_gmres_precond* pc) {
     const int N = (int)fh_N(h);
     const size_t panel = (size_t)N * ld;
     const int mr = std::max(h->restart, 2);
     int rc;
     cplx *V, *W, *part, *npart;
     res.status.assign(nodes_all, 0);
-    // node batches: the basis costs (mr + 2) panels per node
-    const size_t per_node = (size_t)(mr + 2) * panel * sizeof(cplx);
+    // node batches: the basis costs (mr + 2) panels per node, and one more for T = M^-1 v under the preconditioner
+    const size_t per_node = (size_t)(mr + 2 + (pc ? 1 : 0)) * panel * sizeof(cplx);
+    cplx* T = nullptr;
     // budget: at most 48 GiB and at most half of what the device has free right now (plus what this handle already
     // holds for the basis) -- several ranks may share one card (shm rehearsal layout), and parts with less HBM exist
     size_t budget = (size_t)48 << 30;
@@ -918,7 +925,8 @@ int fh_gmres(feasthip_ctx* h, int ld, int m, int nodes_all, const std::vector<cp
     int nbatch = (int)std::max<size_t>(1, std::min<size_t>((size_t)nodes_all, budget / std::max<size_t>(per_node, 1)));
     // an allocation failure halves the batch before it becomes an error
     for (;;) {
-        if (fh_buf(h, "gm_V", (size_t)nbatch * (mr + 1) * panel, &V) == 0 && fh_buf(h, "gm_W", (size_t)nbatch * panel, &W) == 0) break;
+        if (fh_buf(h, "gm_V", (size_t)nbatch * (mr + 1) * panel, &V) == 0 && fh_buf(h, "gm_W", (size_t)nbatch * panel, &W) == 0 &&
+            (!pc || fh_buf(h, "gm_T", (size_t)nbatch * panel, &T) == 0)) break;
         if (nbatch == 1) return FEASTHIP_ERROR_MEMORY;
         hipGetLastError();                                   // clear the sticky out-of-memory status
         nbatch = (nbatch + 1) / 2;
@@ -958,6 +966,40 @@ int fh_gmres(feasthip_ctx* h, int ld, int m, int nodes_all, const std::vector<cp
         fh_op_call oc;
         oc.m = m; oc.uniform_coef = 1; oc.coefA = dca; oc.coefB = dcb; oc.nodes = nodes; oc.prec = 64;
         oc.partial2 = npart;
+        // preconditioned batch: the slots of its nodes' pivots, c_e = z_e - z_p, and u0 = M x0 in place of the guess
+        std::vector<int> pslots;
+        fh_precond_args pa;
+        memset(&pa, 0, sizeof(pa));
+        // (pc->sweeps counts the substitutions of the cycle starts, of the lock-steps that RAN and the final one: like
+        //  spmm_calls it does not depend on how far ahead of the device the host queued)
+        auto substitute = [&](const cplx* src, size_t src_stride, cplx* dst, size_t dst_stride) -> int {
+            return fh_banded_precond_solve(h, ld, m, pslots, src, src_stride, dst, dst_stride);
+        };
+        auto copy_panels = [&](const cplx* src, size_t src_stride, cplx* dst, size_t dst_stride) -> hipError_t {
+            hipError_t err = hipSuccess;
+            for (int e = 0; e < nodes && err == hipSuccess; ++e)
+                err = hipMemcpyAsync(dst + (size_t)e * dst_stride, src + (size_t)e * src_stride, panel * sizeof(cplx), hipMemcpyDeviceToDevice, h->stream);
+            return err;
+        };
+        if (pc) {
+            if ((rc = fh_buf(h, "gm_T", (size_t)nodes * panel, &T))) return rc;
+            pslots.assign(pc->slot.begin() + e0, pc->slot.begin() + e0 + nodes);
+            std::vector<cplx> ce(nodes);
+            for (int e = 0; e < nodes; ++e) ce[e] = csub(z[e0 + e], pc->zp[e0 + e]);
+            cplx* dce;
+            if ((rc = fh_upload_coefs(h, "gm_cnode", ce, &dce))) return rc;
+            pa.rowptr = h->csr.rowptr; pa.col = h->csr.col; pa.bval = h->csr.bval; pa.N = N; pa.nodes = nodes; pa.m = m;
+            pa.T = T; pa.t_node_stride = panel; pa.Y = W; pa.y_node_stride = panel; pa.cnode = dce;
+            if (!pc->zero_guess) {
+                cplx *dpa, *dpb;
+                if ((rc = fh_upload_shift_coefs(h, "gm_pcoefA", "gm_pcoefB", pc->zp.data() + e0, nodes, ld, &dpa, &dpb))) return rc;
+                fh_op_call uc = oc;
+                uc.coefA = dpa; uc.coefB = dpb; uc.X = Xb; uc.x_stride = stride; uc.Y = W; uc.y_stride = panel; uc.partial2 = nullptr;
+                if (fh_apply_operator(h, ld, uc) < 0) return FEASTHIP_ERROR_INTERNAL;
+                res.op_calls += 1;
+                FH_CHECK(copy_panels(W, panel, Xb, stride));
+            }
+        }
 
         int total_it = 0, first = 1;                             // total_it: the lock-steps that ran
         unsigned tag = 0;
@@ -966,7 +1008,20 @@ int fh_gmres(feasthip_ctx* h, int ld, int m, int nodes_all, const std::vector<cp
         while (true) {
             // true residual r = b - S x (into W), ||r|| per column, activity from the stop test
             oc.X = Xb; oc.x_stride = stride; oc.Y = W; oc.y_stride = panel; oc.Bvec = RHS; oc.b_stride = 0; oc.dot_mode = 3; oc.node_active = nullptr;
-            const int nb_norm = fh_apply_operator(h, ld, oc);
+            int nb_norm;
+            if (pc) {
+                // r = b - u - c B M^-1 u; the zero guess of the first cycle has T = 0 without a substitution
+                if (first && pc->zero_guess) FH_CHECK(hipMemsetAsync(T, 0, (size_t)nodes * panel * sizeof(cplx), h->stream));
+                else if ((rc = substitute(Xb, stride, T, panel))) return rc;
+                else pc->sweeps += 1;
+                pa.V = Xb; pa.v_node_stride = stride; pa.Bvec = RHS; pa.partial2 = npart; pa.node_active = nullptr;
+                fh_prof_begin(h, "precond_op_start");      // (a class of its own: every node of the batch is live here)
+                fh_launch_precond_op(pa, ld, h->csr.is_complex != 0, h->csr.b_identity != 0, h->stream);
+                fh_prof_end(h);
+                nb_norm = fh_spmm_partials(N, ld);
+            } else {
+                nb_norm = fh_apply_operator(h, ld, oc);
+            }
             if (nb_norm < 0) return FEASTHIP_ERROR_INTERNAL;
             res.op_calls += 1;
             fh_launch_gm_start(ga, ld, nb_norm, nodes, first, h->rtol, h->atol, m, h->stream);
@@ -985,7 +1040,17 @@ int fh_gmres(feasthip_ctx* h, int ld, int m, int nodes_all, const std::vector<cp
             for (int k = 0; k < mr && total_it + k < h->maxit; ++k) {
                 oc.X = V + (size_t)k * panel; oc.x_stride = ga.v_node_stride; oc.Y = W; oc.y_stride = panel; oc.Bvec = nullptr;
                 oc.dot_mode = 0; oc.node_active = ga.node_active; oc.partial2 = nullptr;
-                const int nb_w = fh_apply_operator(h, ld, oc);                                 // w = S v_k
+                int nb_w = 0;
+                if (pc) {                                                                      // w = v_k + c B M^-1 v_k
+                    if ((rc = substitute(V + (size_t)k * panel, ga.v_node_stride, T, panel))) return rc;
+                    pa.V = V + (size_t)k * panel; pa.v_node_stride = ga.v_node_stride; pa.Bvec = nullptr; pa.partial2 = nullptr;
+                    pa.node_active = ga.node_active;
+                    fh_prof_begin(h, "precond_op");
+                    fh_launch_precond_op(pa, ld, h->csr.is_complex != 0, h->csr.b_identity != 0, h->stream);
+                    fh_prof_end(h);
+                } else {
+                    nb_w = fh_apply_operator(h, ld, oc);                                       // w = S v_k
+                }
                 oc.partial2 = npart;
                 if (nb_w < 0) return FEASTHIP_ERROR_INTERNAL;
                 fh_prof_begin(h, "gmres_ortho");
@@ -1016,8 +1081,109 @@ int fh_gmres(feasthip_ctx* h, int ld, int m, int nodes_all, const std::vector<cp
             }
             fh_launch_gm_finish_cycle(ga, ld, Xb, stride, ksteps, nblk_vec, nodes, h->d_progress + 1, h->stream);   // x += V y
         }
+        const double worst_before = res.max_rel_res;
         if ((rc = fh_collect_columns(h, ga.iters, ga.status, ga.active, ga.rnorm, ga.r0norm, ga.target, nodes, m, ld, e0, FH_FAIL_TARGET, res)))
             return rc;
+        if (pc) {
+            // x = M^-1 u, then the true residual b - S_e x: its norm replaces the estimate in what the call reports (the
+            // statuses stay those of the last cycle start, which the step counts and the reference are pinned to)
+            if ((rc = substitute(Xb, stride, T, panel))) return rc;
+            pc->sweeps += 1 + total_it;
+            FH_CHECK(copy_panels(T, panel, Xb, stride));
+            oc.X = Xb; oc.x_stride = stride; oc.Y = W; oc.y_stride = panel; oc.Bvec = RHS; oc.b_stride = 0; oc.dot_mode = 0;
+            oc.node_active = nullptr; oc.partial2 = nullptr;
+            if (fh_apply_operator(h, ld, oc) < 0) return FEASTHIP_ERROR_INTERNAL;
+            res.op_calls += 1;
+            cplx *dwork, *ddots;
+            if ((rc = fh_buf(h, "gm_tn_work", (size_t)fh_vec_nblk(N, ld) * ld, &dwork))) return rc;
+            if ((rc = fh_buf(h, "gm_tn_dots", nl, &ddots))) return rc;
+            for (int e = 0; e < nodes; ++e)
+                fh_launch_dot_cols(W + (size_t)e * panel, W + (size_t)e * panel, N, ld, dwork, ddots + (size_t)e * ld, h->stream);
+            std::vector<cplx> dots(nl);
+            std::vector<double> r0(nl);
+            FH_CHECK(hipMemcpyAsync(dots.data(), ddots, nl * sizeof(cplx), hipMemcpyDeviceToHost, h->stream));
+            FH_CHECK(hipMemcpyAsync(r0.data(), ga.r0norm, nl * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+            FH_CHECK(hipStreamSynchronize(h->stream));
+            res.max_rel_res = worst_before;
+            for (int e = 0; e < nodes; ++e)
+                for (int c = 0; c < m; ++c)
+                    if (r0[(size_t)e * ld + c] > 0) res.max_rel_res = std::max(res.max_rel_res, std::sqrt(dots[(size_t)e * ld + c].x) / r0[(size_t)e * ld + c]);
+        }
+    }
+    return 0;
+}
+
+// What a set preconditioner (feasthip_set_preconditioner) cannot go with; checked by every entry point that honours it
+static int fh_check_precond(feasthip_ctx* h, const char* what) {
+    if (h->pc_pivots.empty() || h->kind == FH_KIND_NONE) return 0;
+    const char* why = nullptr;
+    if (h->kind != FH_KIND_CSR) why = "it needs a CSR problem (feasthip_set_csr): a dense, operator, term or polynomial handle has no sparse factors for the pivots";
+    else if (h->solver != FEASTHIP_SOLVER_GMRES) why = "the solver must be FEASTHIP_SOLVER_GMRES (BiCGStab, COCG and the direct solvers do not take it)";
+    else if (h->factor_precision != 64) why = "factor_precision = 32 is not supported: the identity form I + c B M^-1 needs exact (complex128) pivot factors";
+    else if (h->adjoint) why = "the adjoint switch (feasthip_set_adjoint) is not supported";
+    else if (fh_comm_nranks(h) > 1) why = "a communicator with more than one rank is not supported";
+    else if (h->pc_node_pivot.size() != h->zne.size()) why = "it was set for a contour with another node count";
+    else
+        for (int k : h->node_kinds) if (k != 0) { why = "a node-solver setting with a direct node (feasthip_set_node_solver) is not supported"; break; }
+    if (!why) return 0;
+    h->last_error = std::string(what) + " with a preconditioner set (feasthip_set_preconditioner): " + why;
+    return FEASTHIP_ERROR_FPM;
+}
+
+// GMRES over nodes that each name a pivot (pivot[i]: index into h->pc_pivots, -1: unpreconditioned).  The pivots the nodes name
+// are factored through the band / multifrontal cache; then maximal runs of nodes of one kind -- preconditioned, plain, or
+// without factors (pivot not factorable: status 8, a zero panel) -- go to fh_gmres one after the other.  With every node
+// preconditioned, the usual case, that is one call and one lock-step count.  Adds to h->pc_last.
+static int fh_gmres_preconditioned(feasthip_ctx* h, int ld, int m, const std::vector<cplx>& z, const std::vector<int>& pivot, bool zero_guess,
+                                   const cplx* RHS, cplx* X, size_t stride, int64_t* nfact, fh_solve_result& sr) {
+    const int nodes = (int)z.size();
+    const size_t panel = (size_t)fh_N(h) * ld;
+    int rc;
+    std::vector<int> used, where(h->pc_pivots.size(), -1);           // distinct pivots of these nodes, pivot -> position in `used`
+    for (int i = 0; i < nodes; ++i)
+        if (pivot[i] >= 0 && where[pivot[i]] < 0) { where[pivot[i]] = (int)used.size(); used.push_back(pivot[i]); }
+    std::vector<cplx> zp(used.size());
+    for (size_t p = 0; p < used.size(); ++p) zp[p] = h->pc_pivots[used[p]];
+    std::vector<int> slots, pstatus;
+    int64_t nf = 0, slot_bytes = 0;
+    int fell_back = 0;
+    h->pc_last.panels += 1;
+    if (!used.empty()) {
+        if ((rc = fh_banded_precond_factor(h, zp, slots, pstatus, &nf, &fell_back, &slot_bytes))) return rc;
+        h->pc_last.used += 1;
+    }
+    if (nfact) *nfact += nf;
+    h->pc_last.pivots = std::max(h->pc_last.pivots, (int)used.size());
+    h->pc_last.factorizations += nf; h->pc_last.fell_back |= fell_back;
+    h->pc_last.factor_bytes = std::max<int64_t>(h->pc_last.factor_bytes, (int64_t)used.size() * slot_bytes);
+    std::vector<int> kind(nodes, 0);                                 // 0 plain, 1 preconditioned, 2 no factors
+    for (int i = 0; i < nodes; ++i)
+        if (pivot[i] >= 0) kind[i] = pstatus[where[pivot[i]]] == 0 ? 1 : 2;
+    sr.status.assign(nodes, 0);
+    for (int i0 = 0; i0 < nodes;) {
+        int i1 = i0 + 1;
+        while (i1 < nodes && kind[i1] == kind[i0]) ++i1;
+        const int cnt = i1 - i0;
+        if (kind[i0] == 2) {
+            FH_CHECK(hipMemsetAsync(X + (size_t)i0 * stride, 0, ((size_t)(cnt - 1) * stride + panel) * sizeof(cplx), h->stream));
+            for (int i = i0; i < i1; ++i) { sr.status[i] = FEASTHIP_ERROR_LAPACK; sr.node_iters.push_back(0); sr.col_iters.insert(sr.col_iters.end(), m, 0); }
+        } else {
+            const std::vector<cplx> zr(z.begin() + i0, z.begin() + i1);
+            fh_solve_result part;
+            fh_gmres_precond pc;
+            if (kind[i0] == 1) {
+                pc.zero_guess = zero_guess;
+                for (int i = i0; i < i1; ++i) { pc.slot.push_back(slots[where[pivot[i]]]); pc.zp.push_back(h->pc_pivots[pivot[i]]); }
+            }
+            if ((rc = fh_gmres(h, ld, m, cnt, zr, RHS, X + (size_t)i0 * stride, stride, part, kind[i0] == 1 ? &pc : nullptr))) return rc;
+            h->pc_last.sweeps += pc.sweeps;
+            std::copy(part.status.begin(), part.status.end(), sr.status.begin() + i0);
+            sr.node_iters.insert(sr.node_iters.end(), part.node_iters.begin(), part.node_iters.end());
+            sr.col_iters.insert(sr.col_iters.end(), part.col_iters.begin(), part.col_iters.end());
+            sr.iters_sum += part.iters_sum; sr.op_calls += part.op_calls;
+            sr.max_iters = std::max(sr.max_iters, part.max_iters); sr.max_rel_res = std::max(sr.max_rel_res, part.max_rel_res);
+        }
+        i0 = i1;
     }
     return 0;
 }
@@ -1250,7 +1416,7 @@ static int fh_panel_krylov(feasthip_ctx* h, fh_panel_sweep& g, bool want_moments
 }
 
 // GMRES: zero initial guess like Krylov.jl (or the Ritz warm start when given), then the restarted cycles over every node
-static int fh_panel_gmres(feasthip_ctx* h, const fh_panel_sweep& g, fh_solve_result& sr) {
+static int fh_panel_gmres(feasthip_ctx* h, const fh_panel_sweep& g, int64_t* nfact, fh_solve_result& sr) {
     int rc;
     cplx* dz; double* dlam;
     if ((rc = fh_upload_coefs(h, "ca_z", g.z, &dz))) return rc;
@@ -1259,7 +1425,10 @@ static int fh_panel_gmres(feasthip_ctx* h, const fh_panel_sweep& g, fh_solve_res
     memset(&va, 0, sizeof(va));
     va.N = g.N; va.node_stride = g.panel; va.X = g.Y; va.Q = g.Qp; va.lambda = dlam; va.znode = dz; va.prec = 64;
     fh_launch_init_guess(va, g.ld, fh_vec_nblk(g.N, g.ld), g.nodes, h->stream);
-    return fh_gmres(h, g.ld, g.m, g.nodes, g.z, g.Rhs, g.Y, g.panel, sr);
+    if (h->pc_pivots.empty()) return fh_gmres(h, g.ld, g.m, g.nodes, g.z, g.Rhs, g.Y, g.panel, sr);
+    std::vector<int> pivot(g.nodes);
+    for (int i = 0; i < g.nodes; ++i) pivot[i] = h->pc_node_pivot[h->node_ids[g.order[i]]];
+    return fh_gmres_preconditioned(h, g.ld, g.m, g.z, pivot, g.ritz_lambda == nullptr, g.Rhs, g.Y, g.panel, nfact, sr);
 }
 
 // What an iterative sweep leaves in the handle (feasthip_last_node_iterations / _column_iterations) and in the stats
@@ -1385,7 +1554,7 @@ static int fh_contour_apply_panel(feasthip_ctx* h, int64_t m64, const cplx* dQ, 
     fh_solve_result sr;
     if (direct) rc = fh_panel_direct(h, g, &nfact, sr);
     else if (h->solver == FEASTHIP_SOLVER_BICGSTAB || h->solver == FEASTHIP_SOLVER_COCG) rc = fh_panel_krylov(h, g, dzAq || dzSq || mom, &nfact, sr);
-    else rc = fh_panel_gmres(h, g, sr);
+    else rc = fh_panel_gmres(h, g, &nfact, sr);
     if (rc) return rc;
     if (!direct) fh_store_sweep_result(h, sr, m, stats);
     else if (stats) stats->max_rel_residual = sr.max_rel_res;
@@ -1523,6 +1692,8 @@ static int fh_contour_apply_impl(feasthip_ctx* h, int64_t m64, const cplx* dQ, c
     fh_mask_live live(h);
     h->shift_panels = h->shift_used = h->shift_seed_iters = 0; h->shift_seed = -1;      // feasthip_last_shifted_sweep
     h->block_panels = h->block_used = h->block_steps_max = h->block_breakdowns = h->block_passes = 0;   // feasthip_last_block_sweep
+    h->pc_last = {};                                                                                    // feasthip_last_precond_sweep
+    if (int prc = fh_check_precond(h, "contour_apply")) return prc;
     const int nr = fh_comm_nranks(h);
     int64_t c0 = 0, c1 = m64;
     if (h->col_block_hi >= 0) { c0 = std::min(h->col_block_lo, m64); c1 = std::min(std::max(h->col_block_hi, c0), m64); }
@@ -1856,8 +2027,11 @@ extern "C" int feasthip_matmul(feasthip_handle h, int which, int64_t m, const vo
     return 0;
 }
 
+static int fh_shifted_solve_panel(feasthip_ctx* h, double z_re, double z_im, int64_t m64, const void* dX, void* dY, feasthip_stats* stats);
+
 extern "C" int feasthip_shifted_solve_dev(feasthip_handle h, double z_re, double z_im, int64_t m64, const void* dX,
                                           void* dY, feasthip_stats* stats) {
+    if (h) h->pc_last = {};         // feasthip_last_precond_sweep: the panels of this call add to one report
     if (m64 > FH_MAX_LD) {          // independent right-hand sides: 64 at a time (LU factor cached between panels)
         int rc0 = fh_check_problem(h, m64, 1);
         if (rc0) return rc0;
@@ -1868,7 +2042,7 @@ extern "C" int feasthip_shifted_solve_dev(feasthip_handle h, double z_re, double
         for (int64_t c0 = 0; c0 < m64; c0 += FH_MAX_LD) {
             const int64_t mc = std::min<int64_t>(FH_MAX_LD, m64 - c0);
             feasthip_stats st;
-            rc0 = feasthip_shifted_solve_dev(h, z_re, z_im, mc, (const cplx*)dX + c0 * N0, (cplx*)dY + c0 * N0, &st);
+            rc0 = fh_shifted_solve_panel(h, z_re, z_im, mc, (const cplx*)dX + c0 * N0, (cplx*)dY + c0 * N0, &st);
             if (rc0 != 0 && rc0 != FEASTHIP_ERROR_NO_CONVERGENCE && rc0 != FEASTHIP_ERROR_LAPACK) return rc0;
             worst = std::max(worst, rc0);
             tot.krylov_iterations += st.krylov_iterations; tot.spmm_calls += st.spmm_calls; tot.factorizations += st.factorizations;
@@ -1877,12 +2051,17 @@ extern "C" int feasthip_shifted_solve_dev(feasthip_handle h, double z_re, double
         if (stats) *stats = tot;
         return worst;
     }
+    return fh_shifted_solve_panel(h, z_re, z_im, m64, dX, dY, stats);
+}
 
+// one panel (m <= 64) of feasthip_shifted_solve_dev
+static int fh_shifted_solve_panel(feasthip_ctx* h, double z_re, double z_im, int64_t m64, const void* dX, void* dY, feasthip_stats* stats) {
     int rc = fh_check_problem(h, m64);
     if (rc) return rc;
     if (!dX || !dY) { h->last_error = "shifted_solve: null argument"; return FEASTHIP_ERROR_INTERNAL; }
     if ((rc = fh_check_operator_solve(h, "shifted_solve"))) return rc;
     if ((rc = fh_check_adjoint(h, "shifted_solve"))) return rc;
+    if ((rc = fh_check_precond(h, "shifted_solve"))) return rc;
     FH_CHECK(hipSetDevice(h->device));
     const int m = (int)m64, ld = fh_pick_ld(m), N = (int)fh_N(h);
     const size_t panel = (size_t)N * ld;
@@ -1911,11 +2090,15 @@ extern "C" int feasthip_shifted_solve_dev(feasthip_handle h, double z_re, double
         FH_CHECK(hipMemsetAsync(Y, 0, panel * sizeof(cplx), h->stream));
         fh_solve_result sr;
         const int method = h->solver == FEASTHIP_SOLVER_COCG ? 1 : h->solver == FEASTHIP_SOLVER_BICGSTAB ? 0 : -1;      // -1: GMRES
+        int64_t nfact = 0;
         if (method >= 0) rc = fh_krylov(h, method, h->factor_precision, ld, m, 1, z, Rhs, Y, panel, sr, fh_krylov_opts());
-        else rc = fh_gmres(h, ld, m, 1, z, Rhs, Y, panel, sr);
+        else if (!h->pc_pivots.empty()) {             // a single shift takes the nearest pivot
+            const std::vector<int> pivot(1, fh_precond::nearest_pivot(z_re, z_im, &h->pc_pivots[0].x, (int)h->pc_pivots.size()));
+            rc = fh_gmres_preconditioned(h, ld, m, z, pivot, true, Rhs, Y, panel, &nfact, sr);
+        } else rc = fh_gmres(h, ld, m, 1, z, Rhs, Y, panel, sr);
         if (rc) return rc;
         status = sr.status;
-        if (stats) { stats->krylov_iterations = sr.iters_sum; stats->spmm_calls = sr.op_calls; stats->max_rel_residual = sr.max_rel_res; }
+        if (stats) { stats->krylov_iterations = sr.iters_sum; stats->spmm_calls = sr.op_calls; stats->max_rel_residual = sr.max_rel_res; stats->factorizations = nfact; }
     }
     fh_launch_from_panel(Y, ld, N, m, (cplx*)dY, N, h->stream, fh_perm(h));
     FH_CHECK(hipStreamSynchronize(h->stream));

@@ -531,9 +531,8 @@ static int band_solve_batch(feasthip_ctx* h, int ld, int m, const std::vector<in
     return 0;
 }
 
-// Factor (where the cache does not already hold z[q] in slot slots[q]) and solve the nodes listed in `slots`.
-static int band_solve_slots(feasthip_ctx* h, int ld, int m, const std::vector<int>& slots, const std::vector<cplx>& z, const cplx* RHS,
-                            size_t rhs_stride, cplx* Y, size_t stride, std::vector<int>& status, int64_t* nfact) {
+// Factor the nodes listed in `slots` where the cache does not already hold z[q] in slot slots[q].
+static int band_factor_slots(feasthip_ctx* h, const std::vector<int>& slots, const std::vector<cplx>& z, int64_t* nfact) {
     const int nodes = (int)slots.size();
     int rc;
     std::vector<int> need;
@@ -564,6 +563,15 @@ static int band_solve_slots(feasthip_ctx* h, int ld, int m, const std::vector<in
         done += (int64_t)lost.size();
     }
     if (nfact) *nfact = done;
+    return 0;
+}
+
+// Factor (where the cache does not already hold z[q] in slot slots[q]) and solve the nodes listed in `slots`.
+static int band_solve_slots(feasthip_ctx* h, int ld, int m, const std::vector<int>& slots, const std::vector<cplx>& z, const cplx* RHS,
+                            size_t rhs_stride, cplx* Y, size_t stride, std::vector<int>& status, int64_t* nfact) {
+    const int nodes = (int)slots.size();
+    int rc;
+    if ((rc = band_factor_slots(h, slots, z, nfact))) return rc;
     if ((rc = band_solve_batch(h, ld, m, slots, RHS, rhs_stride, Y, stride))) return rc;
     status.assign(nodes, 0);
     for (int e = 0; e < nodes; ++e) if (h->band_valid[slots[e]] != 1) status[e] = FEASTHIP_ERROR_LAPACK;
@@ -580,17 +588,14 @@ int fh_banded_solve_nodes(feasthip_ctx* h, int ld, int m, int nodes, const std::
     return band_solve_slots(h, ld, m, slots, z, RHS, rhs_stride, Y, stride, status, nfact);
 }
 
-// The direct nodes of a per-node sweep (feasthip_set_node_solver): a subset of the local nodes, so the factor slots are
-// mapped by shift instead of by local node -- a node whose z is cached keeps its slot whatever else joined or left the
-// subset, the others take the slots no node of this call holds.  Only as many slots as the subset needs are allocated.
-int fh_banded_solve_subset(feasthip_ctx* h, int ld, int m, const std::vector<cplx>& z, const cplx* RHS, cplx* Y, size_t stride,
-                           std::vector<int>& status, int64_t* nfact) {
-    int rc = band_check(h);
-    if (rc) return rc;
+// slots[d]: the factor slot of shift z[d], mapped by shift (see fh_banded_solve_subset); slots are added as needed
+static int band_match_slots(feasthip_ctx* h, const std::vector<cplx>& z, std::vector<int>& slots) {
     const int nd = (int)z.size();
+    int rc;
     if ((rc = band_ensure_slots(h, std::max(nd, (int)h->band_factors.size())))) return rc;
     const int nslots = (int)h->band_factors.size();
-    std::vector<int> slots(nd, -1), taken(nslots, 0);
+    std::vector<int> taken(nslots, 0);
+    slots.assign(nd, -1);
     for (int d = 0; d < nd; ++d)
         for (int s = 0; s < nslots && h->cache_factors; ++s)
             if (!taken[s] && h->band_valid[s] == 1 && h->band_z[s].x == z[d].x && h->band_z[s].y == z[d].y) { slots[d] = s; taken[s] = 1; break; }
@@ -598,7 +603,43 @@ int fh_banded_solve_subset(feasthip_ctx* h, int ld, int m, const std::vector<cpl
         for (int d = 0; d < nd; ++d)
             for (int s = 0; s < nslots && slots[d] < 0; ++s)
                 if (!taken[s] && (pass == 1 || h->band_valid[s] != 1)) { slots[d] = s; taken[s] = 1; }
+    return 0;
+}
+
+// The direct nodes of a per-node sweep (feasthip_set_node_solver): a subset of the local nodes, so the factor slots are
+// mapped by shift instead of by local node -- a node whose z is cached keeps its slot whatever else joined or left the
+// subset, the others take the slots no node of this call holds.  Only as many slots as the subset needs are allocated.
+int fh_banded_solve_subset(feasthip_ctx* h, int ld, int m, const std::vector<cplx>& z, const cplx* RHS, cplx* Y, size_t stride,
+                           std::vector<int>& status, int64_t* nfact) {
+    int rc = band_check(h);
+    if (rc) return rc;
+    std::vector<int> slots;
+    if ((rc = band_match_slots(h, z, slots))) return rc;
     return band_solve_slots(h, ld, m, slots, z, RHS, 0, Y, stride, status, nfact);
+}
+
+// Shift preconditioner: the pivots' factors through the same cache and the same slot mapping as the direct nodes of a
+// per-node sweep, so a factor a direct node left at a pivot's shift is reused and only as many slots as there are pivots
+// are added.  The shifts in `pivots` are distinct.
+int fh_banded_precond_factor(feasthip_ctx* h, const std::vector<cplx>& pivots, std::vector<int>& slots, std::vector<int>& status,
+                             int64_t* nfact, int* fell_back, int64_t* slot_bytes) {
+    int rc = band_check(h);
+    if (rc) return rc;
+    if ((rc = band_match_slots(h, pivots, slots))) return rc;
+    const int plan0 = h->band_plan;
+    if ((rc = band_factor_slots(h, slots, pivots, nfact))) return rc;
+    if (fell_back) *fell_back = plan0 == 3 && h->band_plan != 3 ? 1 : 0;
+    if (slot_bytes) *slot_bytes = (int64_t)band_slot_bytes(h);
+    status.assign(pivots.size(), 0);
+    for (size_t p = 0; p < pivots.size(); ++p) if (h->band_valid[slots[p]] != 1) status[p] = FEASTHIP_ERROR_LAPACK;
+    return 0;
+}
+
+int fh_banded_precond_solve(feasthip_ctx* h, int ld, int m, const std::vector<int>& slots, const cplx* RHS, size_t rhs_stride, cplx* Y,
+                            size_t stride) {
+    for (int s : slots)
+        if (s < 0 || s >= (int)h->band_factors.size() || h->band_valid[s] != 1) { h->last_error = "internal: preconditioner substitution on a slot without factors"; return FEASTHIP_ERROR_INTERNAL; }
+    return band_solve_batch(h, ld, m, slots, RHS, rhs_stride, Y, stride);
 }
 
 // Device memory `nodes` direct nodes take under the plan in force: the cached factors and pivots, and the buffers that live

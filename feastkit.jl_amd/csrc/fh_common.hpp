@@ -299,6 +299,12 @@ struct feasthip_ctx {
     // feasthip_set_ortho_method / feasthip_last_ortho: what rejected panels take, and what the last orthonormalisation did
     int ortho_method = 0;         // FEASTHIP_ORTHO_MGS | FEASTHIP_ORTHO_CHOLQR_RR
     struct { int panels = 0, used = 0, stages = 0, fell_back = 0, rank = 0; std::vector<int> perm; std::vector<double> rdiag; } ortho_last;
+    // feasthip_set_preconditioner: the pivot shifts, and per CONTOUR node the index of its pivot (-1: unpreconditioned); empty = none
+    std::vector<cplx> pc_pivots;
+    std::vector<int> pc_node_pivot;
+    // feasthip_last_precond_sweep: panels of the last sweep that ran preconditioned, distinct pivots, factorisations done,
+    // substitution sweeps (one per cycle start, per lock-step and per final x = M^-1 u of a batch), factor bytes held, band fallback
+    struct { int panels = 0, used = 0, pivots = 0, fell_back = 0; int64_t factorizations = 0, sweeps = 0, factor_bytes = 0; } pc_last;
     std::vector<int> col_mask;    // feasthip_set_column_mask: columns with 0 are not iterated by the Krylov solvers
     int poisoned = 0;             // a Krylov deadline / queue fault returned with kernels possibly still queued: every later call fails fast
     int mask_live = 0;            // set only while a contour_apply call runs: the mask is one-shot and never reaches shifted_solve

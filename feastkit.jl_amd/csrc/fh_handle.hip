@@ -260,6 +260,19 @@ extern "C" int feasthip_last_block_sweep(feasthip_handle h, int* used, int* node
     return 0;
 }
 
+extern "C" int feasthip_last_precond_sweep(feasthip_handle h, int* used, int* pivots, int64_t* factorizations, int64_t* substitution_sweeps,
+                                           int64_t* factor_bytes, int* fell_back) {
+    if (!h) return FEASTHIP_ERROR_INTERNAL;
+    const bool u = h->pc_last.panels > 0 && h->pc_last.used == h->pc_last.panels;
+    if (used) *used = u ? 1 : 0;
+    if (pivots) *pivots = h->pc_last.pivots;
+    if (factorizations) *factorizations = h->pc_last.factorizations;
+    if (substitution_sweeps) *substitution_sweeps = h->pc_last.sweeps;
+    if (factor_bytes) *factor_bytes = h->pc_last.factor_bytes;
+    if (fell_back) *fell_back = h->pc_last.fell_back;
+    return 0;
+}
+
 extern "C" int feasthip_last_column_iterations(feasthip_handle h, int* out, int n) {
     if (!h || !out) return FEASTHIP_ERROR_INTERNAL;
     for (int e = 0; e < n; ++e) out[e] = e < (int)h->last_col_iters.size() ? h->last_col_iters[e] : 0;

@@ -55,6 +55,24 @@ int fh_spmm_row_grid(int N);
 int fh_spmm_lds_slots(int nblk_rows, int ld);
 void fh_launch_spmm(const fh_spmm_args& a, int ld, bool is_complex, bool bident, int nblk, hipStream_t st);
 
+// ---- shift-preconditioned operator in its identity form (fh_sparse.hip: k_precond_op) -------------------------------------
+// S_e M^-1 = I + c_e B M^-1 with M = z_p B - A, c_e = z_e - z_p.  T_e = M^-1 V_e comes from the substitution; the kernel forms
+//   step:        Y_e = V_e + c_e B T_e                    (Bvec == null)
+//   cycle start: Y_e = Bvec - V_e - c_e B T_e, partial2 = <Y, Y> in the layout of dot mode 3 ([nodes][fh_spmm_partials][LD])
+// on complex128 panels; columns >= m are written as zeros.  It reads B's values only (none when B = I).
+struct fh_precond_args {
+    const int* rowptr; const int* col; const void* bval;
+    int N; int nodes; int m;
+    const cplx* V; size_t v_node_stride;
+    const cplx* T; size_t t_node_stride;
+    cplx* Y; size_t y_node_stride;
+    const cplx* cnode;                        // [nodes] c_e
+    const cplx* Bvec;                         // shared by the nodes, or null
+    cplx* partial2;                           // cycle start only
+    const int* node_active;                   // may be null; an inactive node is skipped (its partial rows are cleared)
+};
+void fh_launch_precond_op(const fh_precond_args& a, int ld, bool is_complex, bool bident, hipStream_t st);
+
 // ---- Krylov vector kernels (BiCGStab and COCG) -------------------------------------------
 struct fh_vec_args {
     int N;

@@ -32,8 +32,17 @@ struct fh_krylov_opts {
 // atol, maxit (and restart) apply.  fh_krylov: BiCGStab (method 0) or COCG (method 1); fh_gmres: restarted GMRES.
 int fh_krylov(feasthip_ctx* h, int method, int prec, int ld, int m, int nodes, const std::vector<cplx>& z, const cplx* RHS,
               cplx* X, size_t stride, fh_solve_result& res, const fh_krylov_opts& opt);
+// Shift preconditioner of a fh_gmres call (feasthip_set_preconditioner): node e runs in the variable u = M_e x with
+// M_e = zp[e] B - A, whose factors sit in slot[e] of the band / multifrontal cache (fh_banded_precond_factor).  zero_guess: X
+// holds zeros (u0 = M x0 is not formed).  sweeps: substitution sweeps the call made (out).
+struct fh_gmres_precond {
+    std::vector<int> slot;
+    std::vector<cplx> zp;
+    bool zero_guess = false;
+    int64_t sweeps = 0;
+};
 int fh_gmres(feasthip_ctx* h, int ld, int m, int nodes_all, const std::vector<cplx>& z, const cplx* RHS, cplx* X, size_t stride,
-             fh_solve_result& res);
+             fh_solve_result& res, fh_gmres_precond* pc = nullptr);
 
 // Y_e = [Bvec -] P(z_e) X_e on a sparse polynomial handle (fh_poly.hip: k_spmm_poly), complex128 panels; the fields are those
 // of fh_spmm_args.  z_e = znode[e * z_stride].  Returns the partial-sum rows per node it wrote (fh_poly_op_nblk).

@@ -212,6 +212,7 @@ extern "C" int feasthip_set_contour(feasthip_handle h, int ne, const double* zne
     }
     h->weight_scale = weight_scale;
     if ((int)h->node_kinds.size() != ne) h->node_kinds.clear();      // feasthip_set_node_solver: kinds of another contour
+    if ((int)h->pc_node_pivot.size() != ne) { h->pc_pivots.clear(); h->pc_node_pivot.clear(); }      // feasthip_set_preconditioner likewise
     h->node_first = 0;
     h->node_count = ne;
     h->node_ids.resize(ne);
@@ -244,6 +245,38 @@ extern "C" int feasthip_set_node_solver(feasthip_handle h, int count, const int*
         for (int e = 0; e < count; ++e)
             if (kinds[e] != 0) { h->last_error = "feasthip_set_node_solver: there is no matrix for a direct node: " FH_TERMOP_TAKES; return FEASTHIP_ERROR_FPM; }
     h->node_kinds.assign(kinds, kinds + count);
+    return 0;
+}
+
+// Only the setting's own shape is checked here; what it cannot go with (solver, handle kind, precision, adjoint, communicator,
+// direct nodes) may change after this call, so the entry points that honour it look at those (fh_api.hip: fh_check_precond)
+extern "C" int feasthip_set_preconditioner(feasthip_handle h, int npivots, const double* pivots, int count, const int* node_pivot) {
+    if (!h) return FEASTHIP_ERROR_INTERNAL;
+    if (npivots == 0) { h->pc_pivots.clear(); h->pc_node_pivot.clear(); return 0; }
+    if (npivots < 0 || !pivots || !node_pivot) { h->last_error = "feasthip_set_preconditioner: npivots < 0 or null arrays"; return FEASTHIP_ERROR_FPM; }
+    if (count != (int)h->zne.size()) {
+        h->last_error = "feasthip_set_preconditioner: count " + std::to_string(count) + " is not the contour's node count " + std::to_string(h->zne.size());
+        return FEASTHIP_ERROR_FPM;
+    }
+    for (int p = 0; p < npivots; ++p) {
+        if (!(pivots[2 * p + 1] != 0.0) || !std::isfinite(pivots[2 * p]) || !std::isfinite(pivots[2 * p + 1])) {
+            h->last_error = "feasthip_set_preconditioner: pivot " + std::to_string(p) + " must be finite with a non-zero imaginary part (z_p B - A is factored without a stop test)";
+            return FEASTHIP_ERROR_FPM;
+        }
+        for (int q = 0; q < p; ++q)
+            if (pivots[2 * q] == pivots[2 * p] && pivots[2 * q + 1] == pivots[2 * p + 1]) {
+                h->last_error = "feasthip_set_preconditioner: pivots " + std::to_string(q) + " and " + std::to_string(p) + " are the same shift";
+                return FEASTHIP_ERROR_FPM;
+            }
+    }
+    for (int e = 0; e < count; ++e)
+        if (node_pivot[e] < -1 || node_pivot[e] >= npivots) {
+            h->last_error = "feasthip_set_preconditioner: node_pivot[" + std::to_string(e) + "] = " + std::to_string(node_pivot[e]) + " (-1 or a pivot index below " + std::to_string(npivots) + ")";
+            return FEASTHIP_ERROR_FPM;
+        }
+    h->pc_pivots.resize(npivots);
+    for (int p = 0; p < npivots; ++p) h->pc_pivots[p] = cmake(pivots[2 * p], pivots[2 * p + 1]);
+    h->pc_node_pivot.assign(node_pivot, node_pivot + count);
     return 0;
 }
 

@@ -307,6 +307,103 @@ __global__ __launch_bounds__(FH_BLOCK, 4) void k_spmm(fh_spmm_args a) {
 }
 
 // ------------------------------------------------------------------------------------
+// Shift-preconditioned operator in its identity form (fh_precond_args, fh_kernels.hpp):
+//     Y_e = V_e + c_e B T_e              one Arnoldi step of the preconditioned GMRES sweep, T_e = M^-1 V_e
+//     Y_e = Bvec - V_e - c_e B T_e       its cycle start, with the <Y, Y> partial rows of dot mode 3
+// for all nodes of a batch in one launch.  Rows and columns are mapped as in k_spmm (one XCD group per 16-column tile and row
+// slice, a wave = 4 rows x 16 columns, the 16 lanes of a row load 16 nonzeros' column index and B value in one access and
+// broadcast them), so the gathered T lines stay in one private L2 and the partial rows are those k_gm_start reads.  It
+// walks the union pattern but loads only B's values; with B = I there is no gather at all: Y = V + c T element-wise over the
+// same rows.  Per row it moves 3 panel rows (V, T once from HBM, Y) against k_spmm's 2, and no A values.
+// ------------------------------------------------------------------------------------
+template <typename VT, int LD, bool BIDENT>
+__global__ __launch_bounds__(FH_BLOCK, 4) void k_precond_op(fh_precond_args a) {
+    constexpr int NT = LD / 16;
+    constexpr int SLICES = 8 / NT;
+    __shared__ cplx red[FH_BLOCK];
+    const int t = threadIdx.x;
+    const int lane = t & 63, wave = t >> 6;
+    const int g = lane >> 4, l16 = lane & 15;
+    const int S = gridDim.x >> 3;
+    const int grp = blockIdx.x & 7, slot = blockIdx.x >> 3;
+    const int ct = grp % NT, slice = grp / NT;
+    const int slice_rows = (a.N + SLICES - 1) / SLICES;
+    const int row_lo = min(a.N, slice * slice_rows);
+    const int row_hi = min(a.N, row_lo + slice_rows);
+    const int band = S * 16;
+    const int c = ct * 16 + l16;
+    const VT* __restrict__ bval = (const VT*)a.bval;
+    const int* __restrict__ rowptr = a.rowptr;
+    const int* __restrict__ colidx = a.col;
+    const int prow = slice * S + slot;
+    const int nprow = SLICES * S;
+    const bool live_col = c < a.m;
+
+    for (int node = 0; node < a.nodes; ++node) {
+        const size_t pbase = ((size_t)node * nprow + prow) * LD + ct * 16;
+        if (a.node_active && a.node_active[node] == 0) {
+            if (a.partial2 && t < 16) a.partial2[pbase + t] = cmake(0, 0);
+            continue;
+        }
+        const cplx* __restrict__ V = a.V + (size_t)node * a.v_node_stride;
+        const cplx* __restrict__ T = a.T + (size_t)node * a.t_node_stride;
+        cplx* __restrict__ Y = a.Y + (size_t)node * a.y_node_stride;
+        const cplx ce = a.cnode[node];
+        double d2 = 0.0;
+        for (int i = row_lo + slot * 16 + wave * 4 + g; i < row_hi; i += band) {
+            cplx acc = cmake(0, 0);
+            if (BIDENT) {
+                acc = T[(size_t)i * LD + c];
+            } else {
+                const int k0 = rowptr[i], k1 = rowptr[i + 1];
+                for (int kb = k0; kb < k1; kb += 16) {
+                    // (slots past the end of the row hold the row's own index and a zero value, as in k_spmm)
+                    const int kk = kb + l16;
+                    const bool in = kk < k1;
+                    const int mycol = in ? colidx[kk] : i;
+                    const VT myb = in ? bval[kk] : fh_vzero(VT());
+                    const int cnt = min(16, k1 - kb);
+#pragma unroll
+                    for (int q0 = 0; q0 < 16; q0 += 8) {
+                        if (q0 >= cnt) break;
+                        cplx xs[8];
+#pragma unroll
+                        for (int q = 0; q < 8; ++q) xs[q] = T[(size_t)fh_bc16(mycol, q0 + q) * LD + c];
+#pragma unroll
+                        for (int q = 0; q < 8; ++q) acc = cadd(acc, vmul(fh_bc16(myb, q0 + q), xs[q]));
+                    }
+                }
+            }
+            cplx y = cadd(fh_ld_nt(V + (size_t)i * LD + c), cmul(ce, acc));
+            if (a.Bvec) y = csub(fh_ld_nt(a.Bvec + (size_t)i * LD + c), y);
+            if (!live_col) y = cmake(0, 0);
+            fh_st_nt(Y + (size_t)i * LD + c, y);
+            d2 += cabs2(y);
+        }
+        if (a.partial2) {
+            red[t] = cmake(d2, 0);
+            __syncthreads();
+            if (t < 16) {
+                cplx s = cmake(0, 0);
+                for (int k = 0; k < 16; ++k) s = cadd(s, red[t + 16 * k]);
+                a.partial2[pbase + t] = s;
+            }
+            __syncthreads();
+        }
+    }
+}
+
+void fh_launch_precond_op(const fh_precond_args& a, int ld, bool is_complex, bool bident, hipStream_t st) {
+    const dim3 grid(fh_spmm_grid(a.N, ld)), block(FH_BLOCK);
+    fh_with_ld(ld, [&](auto L) {
+        constexpr int LD = decltype(L)::value;
+        if (bident) hipLaunchKernelGGL((k_precond_op<double, LD, true>), grid, block, 0, st, a);
+        else if (is_complex) hipLaunchKernelGGL((k_precond_op<cplx, LD, false>), grid, block, 0, st, a);
+        else hipLaunchKernelGGL((k_precond_op<double, LD, false>), grid, block, 0, st, a);
+    });
+}
+
+// ------------------------------------------------------------------------------------
 // Row-per-wave SpMM for full-width panels (LD = 64, real matrix values): one WAVE takes one matrix row, lane = column.
 //
 // Why a second gather kernel.  k_spmm gives every 16-lane group of a wave its own row, so column indices and values live

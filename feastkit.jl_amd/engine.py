@@ -420,6 +420,27 @@ class HipEngine:
         k = np.ascontiguousarray(kinds, dtype=np.int32)
         self._chk(self.lib.feasthip_set_node_solver(self.h, len(k), _np_ptr(k)))
 
+    def set_preconditioner(self, pivots, node_pivot=None):
+        """Shift preconditioner of the GMRES sweep (feasthip_set_preconditioner): ``pivots`` the complex pivot shifts (non-zero
+        imaginary part), ``node_pivot[e]`` per GLOBAL contour node the index of its pivot, -1 = unpreconditioned.
+        ``pivots=None`` (or empty) clears the setting."""
+        if pivots is None or len(pivots) == 0:
+            self._chk(self.lib.feasthip_set_preconditioner(self.h, 0, None, 0, None))
+            return
+        p = np.ascontiguousarray(pivots, dtype=np.complex128)
+        k = np.ascontiguousarray(node_pivot, dtype=np.int32)
+        self._chk(self.lib.feasthip_set_preconditioner(self.h, len(p), _np_ptr(p), len(k), _np_ptr(k)))
+
+    def last_precond_sweep(self):
+        """What the last sweep or shifted solve did under the preconditioner (feasthip_last_precond_sweep): a dict with
+        used, pivots, factorizations, substitution_sweeps, factor_bytes and fell_back."""
+        used, piv, fb = C.c_int(0), C.c_int(0), C.c_int(0)
+        nf, sw, by = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        self._chk(self.lib.feasthip_last_precond_sweep(self.h, C.byref(used), C.byref(piv), C.byref(nf), C.byref(sw), C.byref(by),
+                                                       C.byref(fb)))
+        return {"used": bool(used.value), "pivots": piv.value, "factorizations": nf.value, "substitution_sweeps": sw.value,
+                "factor_bytes": by.value, "fell_back": bool(fb.value)}
+
     # -- device arrays (plumbing) -----------------------------------------------------
     def set_column_mask(self, mask):
         """mask[c] == 0: column c is not iterated by the Krylov solvers (keeps its warm start);

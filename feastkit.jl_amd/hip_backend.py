@@ -467,6 +467,105 @@ def _direct_nodes_scope(engine, direct_nodes, ne, sparse, solver, m, world, stat
     return dn
 
 
+def check_precond(precond, precond_shifts=1, *, sparse=True, solver="gmres", inner_precision=64, group=None, direct_nodes=None,
+                  two_sided=False, estimate=False, auto_m0=False):
+    """Host-only validation of the ``precond`` / ``precond_shifts`` keywords (no device work) -> None, an int k >= 1 or a list
+    of complex pivots.  Everything the shift preconditioner does not go with raises ValueError and names what to use."""
+    if precond is None:
+        return None
+    if precond != "shift":
+        raise ValueError(f"precond must be None or 'shift', not {precond!r}")
+    if not sparse:
+        raise ValueError("precond='shift' needs sparse input (the pivots are factored by the sparse direct solver); dense input takes solver='direct'")
+    if solver != "gmres":
+        raise ValueError(f"precond='shift' needs solver='gmres', not '{solver}' (BiCGStab and COCG run unpreconditioned; use solver='gmres' or drop precond)")
+    if inner_precision != 64:
+        raise ValueError("precond='shift' needs inner_precision=64: the identity form I + c B M^-1 needs exact pivot factors")
+    if two_sided:
+        raise ValueError("precond='shift' has no two-sided form; use two_sided=True with solver='sparse_direct', or drop two_sided")
+    if group is not None:
+        raise ValueError("precond='shift' sweeps on one rank; drop group= or use an unpreconditioned Krylov solver")
+    if direct_nodes is not None:
+        raise ValueError("precond='shift' does not mix with direct_nodes=; use one of them (direct_nodes= goes with solver='cocg' or 'bicgstab')")
+    if estimate:
+        raise ValueError("precond='shift' does not apply to the count estimate (fpm[14] = 2); run the estimate without precond")
+    if auto_m0:
+        raise ValueError("precond='shift' does not go with M0='auto'; estimate first (fpm[14] = 2 without precond), then pass M0")
+    ps = precond_shifts
+    if isinstance(ps, (bool, str, float, np.floating)):
+        raise ValueError("precond_shifts must be an int k >= 1 or a list of complex pivot shifts")
+    if isinstance(ps, (int, np.integer)):
+        if int(ps) < 1:
+            raise ValueError("precond_shifts must be an int k >= 1 or a list of complex pivot shifts")
+        return int(ps)
+    try:
+        piv = [complex(v) for v in ps]
+    except TypeError:
+        raise ValueError("precond_shifts must be an int k >= 1 or a list of complex pivot shifts") from None
+    if not piv:
+        raise ValueError("precond_shifts: the pivot list is empty")
+    if any(p.imag == 0.0 or not np.isfinite(p.real) or not np.isfinite(p.imag) for p in piv):
+        raise ValueError("precond_shifts: every pivot needs a non-zero imaginary part (z_p B - A is factored; on the real axis it may be singular)")
+    if len(set(piv)) != len(piv):
+        raise ValueError("precond_shifts: the pivots must be distinct")
+    return piv
+
+
+def precond_plan(Zne, spec):
+    """(pivot shifts, node -> pivot index) of a checked ``precond_shifts``: the rules of csrc/fh_precond.hpp.  An int k: the
+    nodes in order cut into k arcs [a ne // k, (a + 1) ne // k), each arc's pivot its middle node (of two, the lower one in
+    the first half of the arcs, the upper one in the second: 8 nodes in 2 arcs give nodes 1 and 6).  A list: every node takes
+    its nearest pivot (lowest index on ties)."""
+    ne = len(Zne)
+    if isinstance(spec, int):
+        k = max(1, min(spec, ne))
+        node_pivot, pivots = [0] * ne, []
+        for a in range(k):
+            lo, hi = a * ne // k, (a + 1) * ne // k
+            pivots.append(complex(Zne[lo + (hi - lo - 1) // 2 if 2 * a + 1 <= k else lo + (hi - lo) // 2]))
+            node_pivot[lo:hi] = [a] * (hi - lo)
+        return pivots, node_pivot
+    return list(spec), [int(np.argmin([abs(complex(z) - p) ** 2 for p in spec])) for z in Zne]
+
+
+class _Precond:
+    """The drivers' ``precond`` keyword as a context: the preconditioner is set on the engine for the loops inside (after
+    set_contour, which keeps it only for the same node count) and cleared on every way out.  ``log`` becomes
+    stats["precond"]: one entry per loop."""
+
+    def __init__(self, engine, spec, Zne):
+        self.engine, self.log = engine, []
+        self.pivots, self.node_pivot = precond_plan(Zne, spec)
+        if any(p.imag == 0.0 for p in self.pivots):
+            raise ValueError("precond_shifts: a contour node on the real axis cannot be a pivot; pass the pivots as a list")
+
+    def __enter__(self):
+        self.engine.set_preconditioner(self.pivots, self.node_pivot)
+        return self
+
+    def __exit__(self, *exc):
+        self.engine.set_preconditioner(None)
+        return False
+
+    def record(self, count):
+        last = self.engine.last_precond_sweep()
+        self.log.append({"pivots": list(self.pivots), "node_pivot": list(self.node_pivot), "factorizations": last["factorizations"],
+                         "substitution_sweeps": last["substitution_sweeps"],
+                         "lock_steps": [int(v) for v in self.engine.last_node_iterations(count)],
+                         "factor_bytes": last["factor_bytes"], "fell_back": last["fell_back"], "used": last["used"]})
+
+
+def _precond_scope(engine, precond, precond_shifts, Zne, sparse, solver, stats, inner_precision=64, group=None, direct_nodes=None):
+    """None: nothing changes (a null context whose value is None)."""
+    spec = check_precond(precond, precond_shifts, sparse=sparse, solver=solver, inner_precision=inner_precision, group=group,
+                         direct_nodes=direct_nodes)
+    if spec is None:
+        return contextlib.nullcontext()
+    pc = _Precond(engine, spec, Zne)
+    stats["precond"] = pc.log
+    return pc
+
+
 class _InexactPolicy(_lib.FeastHipPolicy):
     """The inexact mode's host policy under the C ABI (feasthip_policy_*, csrc/fh_policy.hpp); fields are the C struct's.
     hist, reach: fpm[18] and the subspace reach of every loop under contour steering."""
@@ -644,7 +743,7 @@ def feast_hip_hermitian(engine, A, B, Emin, Emax, M0, fpm, *, freeze_guards_afte
                         real_projection=None, group=None, Q0=None, seed=20260515, contour=None, trace=None,
                         preloaded=False, node_assignment="block", inner_precision=64, column_groups=1,
                         spurious_filter=True, contour_policy=None, eps_floor=0.0, abort_check=None, resident_panels=True,
-                        direct_nodes=None, ortho="mgs"):
+                        direct_nodes=None, ortho="mgs", precond=None, precond_shifts=1):
     """Variant A on the :hip engine.  Returns FeastResult (complex Ritz vectors, like
     _feast_dense_complex_hermitian; real-symmetric callers take real.(q) as the reference
     does, src/dense/feast_dense.jl:372-387).
@@ -686,6 +785,9 @@ def feast_hip_hermitian(engine, A, B, Emin, Emax, M0, fpm, *, freeze_guards_afte
       solved by the sparse direct solver inside the Krylov sweep (feasthip_set_node_solver) -- the list in every loop, the k
       slowest nodes of the first loop from the second on, or what feasthip_policy_pick_direct_nodes picks after every loop.
       ``stats["direct_nodes"]`` has one entry per loop; ``stats["node_iterations"]`` shows 0 for a direct node.
+    precond, precond_shifts: None | "shift" (sparse input, solver "gmres"): the GMRES sweeps run preconditioned by the LU
+      factors of z_p B - A at a few pivot shifts (feasthip_set_preconditioner; check_precond, precond_plan).
+      ``stats["precond"]`` has one entry per loop.
     """
     N = A.shape[0]
     feastdefault(fpm)
@@ -760,8 +862,11 @@ def feast_hip_hermitian(engine, A, B, Emin, Emax, M0, fpm, *, freeze_guards_afte
     # one BLAS thread for the whole solve; the `with` releases the process-wide limit on every way out, including an
     # exception from the engine inside the loop (FeastHipError, a poisoned handle)
     import scipy.sparse as _sp
+    if precond is not None and contour_policy is not None:
+        raise ValueError("precond='shift' keeps the contour it planned its pivots on; drop contour_policy=")
     with small_lapack(), _ortho_scope(engine, ortho, stats), \
-            _direct_nodes_scope(engine, direct_nodes, len(Zne), _sp.issparse(A), solver, M0, world, stats, inner_precision) as dn:
+            _direct_nodes_scope(engine, direct_nodes, len(Zne), _sp.issparse(A), solver, M0, world, stats, inner_precision) as dn, \
+            _precond_scope(engine, precond, precond_shifts, Zne, _sp.issparse(A), solver, stats, inner_precision, group, direct_nodes) as pc:
         for loop_idx in range(0, maxloop + 1):
             loop_count = loop_idx
             # -- sweep
@@ -804,6 +909,8 @@ def feast_hip_hermitian(engine, A, B, Emin, Emax, M0, fpm, *, freeze_guards_afte
                                                       "spmm_node_passes": passes})
             if dn is not None:
                 dn.record(loop_idx, st, layout.local_nodes)
+            if pc is not None:
+                pc.record(layout.count)
             layout.rebalance(engine, loop_idx, active, stats)
             # direct: singular shift -> info 8 (src/dense/feast_dense.jl:199-203); reference GMRES failure -> info 5
             # (src/dense/feast_dense.jl:221-225).  Warm-started solves go on past a Krylov failure (5): the next loop
@@ -950,12 +1057,12 @@ def feast_hip_estimate(engine, A, B, Zne, Wne, weight_scale, m, *, general=False
 
 def feast_hip_general(engine, A, B, Emid, r, M0, fpm, *, solver="direct", solver_tol=0.0, solver_maxiter=500,
                       solver_restart=30, group=None, Q0=None, seed=20260515, inner_precision=64, contour=None, eps_floor=0.0,
-                      direct_nodes=None, ortho="mgs", preloaded=False):
+                      direct_nodes=None, ortho="mgs", preloaded=False, precond=None, precond_shifts=1):
     """Variant C (general, full contour, no factor 2, no orthonormalisation, residual
     without B): src/kernel/feast_kernel.jl:752-950 driven as in src/dense/feast_dense.jl:468-584.
     ``preloaded``: the engine holds the problem already (engine.set_operator); A and B are then read for their shape only.
     ``ortho`` is checked and set on the engine for the solve like in the other drivers; this variant never orthonormalises
-    its subspace, so ``stats["ortho"]`` stays empty."""
+    its subspace, so ``stats["ortho"]`` stays empty.  ``precond``, ``precond_shifts``: as in feast_hip_hermitian."""
     N = A.shape[0]
     feastdefault(fpm)
     info = _check_circle_input(N, M0, r)
@@ -978,7 +1085,8 @@ def feast_hip_general(engine, A, B, Emid, r, M0, fpm, *, solver="direct", solver
     epsout, eps_hist = math.inf, []
     import scipy.sparse as _sp
     with _ortho_scope(engine, ortho, stats), \
-            _direct_nodes_scope(engine, direct_nodes, len(Zne), _sp.issparse(A), solver, M0, world, stats, inner_precision) as dn:
+            _direct_nodes_scope(engine, direct_nodes, len(Zne), _sp.issparse(A), solver, M0, world, stats, inner_precision) as dn, \
+            _precond_scope(engine, precond, precond_shifts, Zne, _sp.issparse(A), solver, stats, inner_precision, group, direct_nodes) as pc:
         while True:
             if inner_precision == 32:
                 # inexact FEAST: the complex64 solves are refined only as far as the current outer residual needs
@@ -988,6 +1096,8 @@ def feast_hip_general(engine, A, B, Emid, r, M0, fpm, *, solver="direct", solver
             fail, (dq, status, st) = _sweep(engine, dQ, M0, world, count, stats)
             if dn is not None:
                 dn.record(loop, st)
+            if pc is not None:
+                pc.record(count)
             if fail:
                 return _empty_result(N, FeastError.Feast_ERROR_LAPACK if fail == 8 else FeastError.Feast_ERROR_NO_CONVERGENCE,
                                      loop, complex_lambda=True, stats=stats)

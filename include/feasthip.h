@@ -318,6 +318,36 @@ int  feasthip_set_node_solver(feasthip_handle h, int count, const int* kinds);
  * panels).  A host shim sizes the direct subset of feasthip_set_node_solver with it.                                       */
 int  feasthip_direct_plan_bytes(feasthip_handle h, int nodes, int64_t* factor_bytes, int64_t* transient_bytes);
 
+/* Shift preconditioner of the restarted GMRES sweep (not in the reference, whose iterative branch src/sparse/feast_sparse.jl:164-203
+ * runs unpreconditioned): M = z_p B - A is factored at a few PIVOT shifts z_p off the real axis, and node e, whose pivot is p,
+ * solves in the variable u = M x with the operator
+ *     S_e M^-1 = (z_e B - A)(z_p B - A)^-1 = I + (z_e - z_p) B M^-1,
+ * whose eigenvalues (z_e - lambda)/(z_p - lambda) sit at 1 for every lambda far from the contour.  One factorisation serves
+ * every node of its pivot: the sweep holds npivots factors where FEASTHIP_SOLVER_BANDED holds one per node.
+ * pivots: npivots (re, im) pairs with a non-zero imaginary part; node_pivot[e], indexed by GLOBAL contour node: the pivot of
+ * node e, or -1 for a node that stays unpreconditioned.  npivots == 0 clears the setting; otherwise count must be the
+ * contour's node count (FEASTHIP_ERROR_FPM).  Persistent until cleared; feasthip_set_contour with another node count clears it.
+ * Honoured by feasthip_contour_apply, _dev, _resident and feasthip_shifted_solve[_dev] (a single shift takes the nearest pivot)
+ * for a CSR problem whose solver is FEASTHIP_SOLVER_GMRES with factor_precision = 64.  While it is set, those calls return
+ * FEASTHIP_ERROR_FPM, with the reason in feasthip_last_error, for any other solver, a dense / operator / term / polynomial
+ * handle, factor_precision = 32, the adjoint switch, a communicator with more than one rank, and a node-solver setting with a
+ * direct node.  The identity form needs exact factors, which is why complex64 factors are out: with M~ != M the operator is
+ * S_e M~^-1, not I + c_e B M~^-1.
+ * The pivots are factored through the factor cache of FEASTHIP_SOLVER_BANDED, matched by shift (all three direct plans): a
+ * repeated sweep factors nothing, a factor a direct node left at the same shift is reused, feasthip_release_factors frees them.
+ * A pivot that cannot be factored gives its nodes node_status 8.  The reported residual is the true b - S_e x of x = M^-1 u;
+ * feasthip_stats.spmm_calls counts operator products (the preconditioned operator included), the substitution sweeps are
+ * reported by feasthip_last_precond_sweep.                                                                                    */
+int  feasthip_set_preconditioner(feasthip_handle h, int npivots, const double* pivots /* re,im pairs */, int count,
+                                 const int* node_pivot);
+/* What the last sweep (or shifted solve) did under the preconditioner, summed over its 64-column panels: used = 1 when every
+ * panel ran preconditioned; the distinct pivots it named; the factorisations it made (0 when the cache held them); the
+ * substitution sweeps (one batched M^-1 per cycle start, per lock-step that ran and per final x = M^-1 u); the device memory of the pivot
+ * factors (pivots x bytes_per_node of feasthip_band_plan); fell_back = 1 when the multifrontal LU rejected a pivot and the band
+ * LU took over (a normal outcome).  Any pointer may be null.                                                                  */
+int  feasthip_last_precond_sweep(feasthip_handle h, int* used, int* pivots, int64_t* factorizations, int64_t* substitution_sweeps,
+                                 int64_t* factor_bytes, int* fell_back);
+
 /* ---- host policy of the inexact FEAST mode (no device work; needs no problem and no GPU) -----------------------------
  * What the :hip backend adds to the reference's driver loop when `solver = :direct` on large sparse input is served by the
  * warm-started, inexact Krylov sweeps (not in the reference; DESIGN.md sections 2 and 5): which ellipse ratio fpm[18] to put
