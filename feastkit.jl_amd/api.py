@@ -76,9 +76,9 @@ _DIRECT_FLOPS = float(os.environ.get("FEASTKIT_DIRECT_FLOPS", "4e11"))
 
 
 def _direct_label(eng):
-    """what FEASTHIP_SOLVER_BANDED runs for the problem set on the engine (feasthip_band_plan: 2 = multifrontal)."""
+    """what FEASTHIP_SOLVER_BANDED runs for the problem set on the engine (feasthip_band_plan)."""
     try:
-        return "multifrontal LU on a nested-dissection tree" if eng.band_plan()[3] == 2 else "band LU after reverse Cuthill-McKee"
+        return "multifrontal LU on a nested-dissection tree" if eng.band_plan()[3] == HipEngine.PLAN_MULTIFRONTAL else "band LU after reverse Cuthill-McKee"
     except Exception:
         return "band LU after reverse Cuthill-McKee"
 
@@ -408,7 +408,7 @@ def feast(A, B=None, interval=None, *, M0=10, fpm=None, backend="hip", solver="d
                 plan["t_direct"] = None
                 if _band_direct_fits(eng, A, B, int(fpm[2])):
                     kl, ku, _nb, _blk = eng.band_plan()
-                    if _blk == 2:      # multifrontal plan: measured 0.19 s for cfg 3 (1.05e11 flop per node, 16 nodes)
+                    if _blk == HipEngine.PLAN_MULTIFRONTAL:      # measured 0.19 s for cfg 3 (1.05e11 flop per node, 16 nodes)
                         plan["t_direct"] = 0.08 + eng.direct_plan_flops() * int(fpm[2]) / 1.3e13
                     else:
                         plan["t_direct"] = 0.3 + (N / 128.0) * 1.5e-3 + 8.0 * N * kl * (kl + ku) * int(fpm[2]) / 2e13

@@ -973,7 +973,7 @@ int fh_gmres(feasthip_ctx* h, int ld, int m, int nodes_all, const std::vector<cp
         // (pc->sweeps counts the substitutions of the cycle starts, of the lock-steps that RAN and the final one: like
         //  spmm_calls it does not depend on how far ahead of the device the host queued)
         auto substitute = [&](const cplx* src, size_t src_stride, cplx* dst, size_t dst_stride) -> int {
-            return fh_banded_precond_solve(h, ld, m, pslots, src, src_stride, dst, dst_stride);
+            return fh_direct_solve_slots(h, true, ld, m, pslots, src, src_stride, dst, dst_stride);
         };
         auto copy_panels = [&](const cplx* src, size_t src_stride, cplx* dst, size_t dst_stride) -> hipError_t {
             hipError_t err = hipSuccess;
@@ -1199,19 +1199,15 @@ static bool fh_is_complex_input(feasthip_ctx* h) { return h->kind == FH_KIND_CSR
 // value >= 1 means no refinement at all: plain complex64 solves for the early, inexact FEAST loops), or
 // stops improving; at most 8 steps.
 // The residual is the fp64 dense operator kernel, so the result has fp64 accuracy as long as
-// cond(z_e B - A) * eps32 < 1.  `single`: one shift through fh_dense_lu_solve_single (nodes == 1).
+// cond(z_e B - A) * eps32 < 1.  `single`: one shift through fh_direct_solve_single (nodes == 1).
 static int fh_dense_lu_refined(feasthip_ctx* h, int ld, int m, int nodes, const std::vector<cplx>& z, const cplx* Rhs, cplx* Y,
                                size_t panel, std::vector<int>& status, int64_t* nfact, bool single, double* worst_out, bool banded) {
     const int N = (int)fh_N(h);
     int rc;
     // banded: the same loop over the complex64 band factors of the sparse direct solver (residual = fp64 SpMM)
     auto solve = [&](const cplx* rhs, size_t rhs_stride, cplx* out, int64_t* nf) -> int {
-        if (banded) {
-            if (single) return fh_banded_solve_single(h, ld, m, z[0], rhs, out, &status[0], nf);
-            return fh_banded_solve_nodes(h, ld, m, nodes, z, rhs, rhs_stride, out, panel, status, nf);
-        }
-        if (single) return fh_dense_lu_solve_single(h, ld, m, z[0], rhs, out, &status[0], nf);
-        return fh_dense_lu_solve_nodes(h, ld, m, nodes, z, rhs, rhs_stride, out, panel, status, nf);
+        if (single) return fh_direct_solve_single(h, banded, ld, m, z[0], rhs, out, &status[0], nf);
+        return fh_direct_solve_nodes(h, banded, ld, m, nodes, z, rhs, rhs_stride, out, panel, status, nf);
     };
     if ((rc = solve(Rhs, 0, Y, nfact))) return rc;
     const double tol = std::max(h->rtol, 1e-14);
@@ -1320,8 +1316,7 @@ static int fh_panel_direct(feasthip_ctx* h, const fh_panel_sweep& g, int64_t* nf
     sr.status.assign(g.nodes, 0);
     if (h->factor_precision == 32)
         return fh_dense_lu_refined(h, g.ld, g.m, g.nodes, g.z, g.Rhs, g.Y, g.panel, sr.status, nfact, false, &sr.max_rel_res, banded);
-    if (banded) return fh_banded_solve_nodes(h, g.ld, g.m, g.nodes, g.z, g.Rhs, 0, g.Y, g.panel, sr.status, nfact);
-    return fh_dense_lu_solve_nodes(h, g.ld, g.m, g.nodes, g.z, g.Rhs, 0, g.Y, g.panel, sr.status, nfact);
+    return fh_direct_solve_nodes(h, banded, g.ld, g.m, g.nodes, g.z, g.Rhs, 0, g.Y, g.panel, sr.status, nfact);
 }
 
 // Shared start (sum mode, fp64 panels): the warm start Y0_e = q_c/(z_e - lambda_c) has the residual
@@ -1360,7 +1355,7 @@ static int fh_panel_krylov(feasthip_ctx* h, fh_panel_sweep& g, bool want_moments
     // direct nodes first, on the same stream: sparse direct solves of the shared right-hand side into their own panels
     // (no warm start, no column mask, as the LU path); the factors live in the band / multifrontal cache, matched by z
     std::vector<int> status_d;
-    if (nd && (rc = fh_banded_solve_subset(h, ld, m, zd, g.Rhs, g.Y + (size_t)nk * panel, panel, status_d, nfact))) return rc;
+    if (nd && (rc = fh_direct_solve_subset(h, true, ld, m, zd, g.Rhs, g.Y + (size_t)nk * panel, panel, status_d, nfact))) return rc;
     fh_krylov_opts opt;
     cplx* dz = nullptr; double* dlam = nullptr;
     if (nk && (rc = fh_upload_coefs(h, "ca_z", zk, &dz))) return rc;
@@ -2078,8 +2073,7 @@ static int fh_shifted_solve_panel(feasthip_ctx* h, double z_re, double z_im, int
         int64_t nfact = 0;          // (the factors are cached per quadrature node when z is one, else in one extra slot)
         double worst = 0.0;
         if (h->factor_precision == 32) rc = fh_dense_lu_refined(h, ld, m, 1, z, Rhs, Y, panel, status, &nfact, true, &worst, banded);
-        else if (banded) rc = fh_banded_solve_single(h, ld, m, z[0], Rhs, Y, &status[0], &nfact);
-        else rc = fh_dense_lu_solve_single(h, ld, m, z[0], Rhs, Y, &status[0], &nfact);
+        else rc = fh_direct_solve_single(h, banded, ld, m, z[0], Rhs, Y, &status[0], &nfact);
         if (rc) return rc;
         if (stats) { stats->factorizations = nfact; stats->max_rel_residual = worst; }
     } else {

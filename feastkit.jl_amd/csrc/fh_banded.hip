@@ -182,13 +182,11 @@ __global__ __launch_bounds__(FH_BLOCK) void k_band_solve(cplx* const* ABs, int* 
 #define FH_BAND_NARROW 64
 
 void fh_banded_free(feasthip_ctx* h) {
-    for (void* p : h->band_factors) if (p) hipFree(p);
-    for (int* p : h->band_pivots) if (p) hipFree(p);
-    h->band_factors.clear(); h->band_pivots.clear(); h->band_valid.clear(); h->band_z.clear();
+    h->band_cache.clear(hipFree);
     if (h->band_perm) hipFree(h->band_perm);
     if (h->band_iperm) hipFree(h->band_iperm);
     h->band_perm = nullptr; h->band_iperm = nullptr;
-    h->band_plan = 0; h->band_kl = 0; h->band_ku = 0; h->band_plan_required = 0;
+    h->band_plan = FH_PLAN_NONE; h->band_kl = 0; h->band_ku = 0; h->band_plan_required = 0;
     fh_mf_free(h);
 }
 
@@ -205,14 +203,14 @@ static void band_rcm_order(feasthip_ctx* h, int kl0, int ku0, std::vector<int>& 
     }
 }
 
-// The blocked band plan (band_plan 2) in the order perm / iperm
+// The blocked band plan (FH_PLAN_BAND) in the order perm / iperm
 static int band_take_band_plan(feasthip_ctx* h, const std::vector<int>& perm, const std::vector<int>& iperm, int kl0, int ku0, int kl1, int ku1) {
     const int64_t N = h->csr.N;
     FH_CHECK(hipMalloc((void**)&h->band_perm, N * sizeof(int)));
     FH_CHECK(hipMalloc((void**)&h->band_iperm, N * sizeof(int)));
     FH_CHECK(hipMemcpy(h->band_perm, perm.data(), N * sizeof(int), hipMemcpyHostToDevice));
     FH_CHECK(hipMemcpy(h->band_iperm, iperm.data(), N * sizeof(int), hipMemcpyHostToDevice));
-    h->band_plan = 2; h->band_kl = kl1; h->band_ku = ku1;
+    h->band_plan = FH_PLAN_BAND; h->band_kl = kl1; h->band_ku = ku1;
     if (fh_knob::debug_timing())
         fprintf(stderr, "[feasthip] band plan: stored order kl %d ku %d, band order kl %d ku %d, %.2f GB per node\n", kl0, ku0, kl1, ku1,
                 (double)fh_wband_elems((int)N, kl1, ku1) * sizeof(cplx) / 1e9);
@@ -227,12 +225,12 @@ static int band_make_plan(feasthip_ctx* h) {
     // pivot (band_fall_back) -- stays while the requirement does: dropping it would plan and factor again on every call.
     // A plan made under the requirement goes likewise once the requirement is off: the calls that never asked for an adjoint
     // get the plan (and the bits) they would have got without it.
-    if (h->band_plan && ((h->require_adjoint && h->band_plan != 3 && !(h->band_plan == 2 && h->band_plan_required)) ||
+    if (h->band_plan != FH_PLAN_NONE && ((h->require_adjoint && h->band_plan != FH_PLAN_MF && !(h->band_plan == FH_PLAN_BAND && h->band_plan_required)) ||
                          (!h->require_adjoint && h->band_plan_required))) {
         fh_banded_free(h);
         fh_mf_free_buffers(h);
     }
-    if (h->band_plan) return 0;
+    if (h->band_plan != FH_PLAN_NONE) return 0;
     h->band_plan_required = h->require_adjoint;
     // A sparse polynomial handle (feasthip_set_polynomial_csr) always plans multifrontal -- the mode 1 branch below without the
     // environment switch -- and has no band plan to fall back on: a pattern without a plan is refused here, a rejected pivot in
@@ -249,7 +247,7 @@ static int band_make_plan(feasthip_ctx* h) {
                             " > 16384), and polynomials have no band LU";
             return FEASTHIP_ERROR_FPM;
         }
-        h->band_plan = 3; h->band_kl = 0; h->band_ku = 0;
+        h->band_plan = FH_PLAN_MF; h->band_kl = 0; h->band_ku = 0;
         return 0;
     }
     if (h->kind != FH_KIND_CSR) { h->last_error = "banded LU needs a CSR matrix (feasthip_set_csr)"; return FEASTHIP_ERROR_FPM; }
@@ -260,7 +258,7 @@ static int band_make_plan(feasthip_ctx* h) {
     const bool force_wide = fh_knob::wband() && !h->require_adjoint;     // read per plan: tests switch it (and it keeps the multifrontal plan out)
     const int mf_mode = h->require_adjoint ? 1 : fh_knob::mf();          // 0 never, 1 always (tests, feasthip_require_adjoint), else by predicted work
     if (!force_wide && mf_mode != 1 && kl0 + ku0 <= FH_BAND_NARROW) {
-        h->band_plan = 1; h->band_kl = kl0; h->band_ku = ku0;
+        h->band_plan = FH_PLAN_NARROW; h->band_kl = kl0; h->band_ku = ku0;
         return 0;
     }
     std::vector<int> perm, iperm;
@@ -282,7 +280,7 @@ static int band_make_plan(feasthip_ctx* h) {
                     fprintf(stderr, "[feasthip] multifrontal plan (%.1f ms): %.3e flop and %.2f GB per node, band %.3e flop and %.2f GB -> %s\n",
                             std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(), fh_mf_plan_flops(h),
                             fh_mf_store_bytes(h, 64) / 1e9, band_flops, (double)fh_wband_elems((int)N, kl1, ku1) * sizeof(cplx) / 1e9, take ? "multifrontal" : "band");
-                if (take) { h->band_plan = 3; h->band_kl = kl1; h->band_ku = ku1; return 0; }
+                if (take) { h->band_plan = FH_PLAN_MF; h->band_kl = kl1; h->band_ku = ku1; return 0; }
                 fh_mf_free(h);
             } else {
                 h->last_error.clear();
@@ -294,20 +292,26 @@ static int band_make_plan(feasthip_ctx* h) {
     return band_take_band_plan(h, perm, iperm, kl0, ku0, kl1, ku1);
 }
 
-static size_t band_slot_bytes(feasthip_ctx* h) {
+// One factor slot under the plan in force: the bytes of its factors at precision prec (64 or 32; the narrow plan has
+// complex128 factors only), the ints of its pivots, and the precision feasthip_set_solver's factor_precision gives it
+static size_t band_slot_bytes(feasthip_ctx* h, int prec) {
     const size_t N = (size_t)h->csr.N;
-    if (h->band_plan == 3) return fh_mf_store_bytes(h, h->band_prec);
-    if (h->band_plan == 2) return fh_wband_elems((int)N, h->band_kl, h->band_ku) * (h->band_prec == 32 ? sizeof(cplxf) : sizeof(cplx));
+    if (h->band_plan == FH_PLAN_MF) return fh_mf_store_bytes(h, prec);
+    if (h->band_plan == FH_PLAN_BAND) return fh_wband_elems((int)N, h->band_kl, h->band_ku) * (prec == 32 ? sizeof(cplxf) : sizeof(cplx));
     return ((size_t)2 * h->band_kl + h->band_ku + 1) * N * sizeof(cplx);
+}
+static size_t band_slot_pivot_ints(feasthip_ctx* h) { return h->band_plan == FH_PLAN_MF ? fh_mf_pivot_ints(h) : (size_t)h->csr.N; }
+static int band_slot_prec(feasthip_ctx* h) {
+    return ((h->band_plan == FH_PLAN_BAND || h->band_plan == FH_PLAN_MF) && h->factor_precision == 32) ? 32 : 64;      // the caller refines in fp64
 }
 
 static int band_check(feasthip_ctx* h) {
     int rc = band_make_plan(h);
     if (rc) return rc;
-    if (h->band_plan == 1) {
+    if (h->band_plan == FH_PLAN_NARROW) {
         const size_t lds = (size_t)(2 * h->band_kl + h->band_ku + 1) * sizeof(cplx);
         if (lds > 60000) { h->last_error = "banded LU: internal (narrow plan with a wide band)"; return FEASTHIP_ERROR_INTERNAL; }
-    } else if (h->band_plan == 2 && h->band_kl > 12000) {
+    } else if (h->band_plan == FH_PLAN_BAND && h->band_kl > 12000) {
         h->last_error = "banded LU: band too wide after reordering (kl > 12000); use an iterative solver";
         return FEASTHIP_ERROR_FPM;
     }
@@ -317,21 +321,19 @@ static int band_check(feasthip_ctx* h) {
 // Buffers that live only while `nslots` nodes are factored and swept (multifrontal plan: the work arena and the substitution
 // panels, about the factors' size again; the band plans have none beyond the sweep's own workspace)
 static double band_transient_bytes(feasthip_ctx* h, int prec, int nslots, size_t slot_bytes) {
-    return h->band_plan == 3 ? (double)nslots * ((double)fh_mf_work_bytes(h, prec) + 0.5 * (double)slot_bytes) : 0.0;
+    return h->band_plan == FH_PLAN_MF ? (double)nslots * ((double)fh_mf_work_bytes(h, prec) + 0.5 * (double)slot_bytes) : 0.0;
 }
 
-static int band_ensure_slots(feasthip_ctx* h, int nslots) {
-    const size_t N = (size_t)h->csr.N;
-    // complex64 factors (feasthip_set_solver factor_precision = 32) exist for the blocked plan only; the caller refines in fp64
-    const int prec = (h->band_plan >= 2 && h->factor_precision == 32) ? 32 : 64;
-    if (prec != h->band_prec) {
-        for (void* p : h->band_factors) if (p) hipFree(p);
-        for (int* p : h->band_pivots) if (p) hipFree(p);
-        h->band_factors.clear(); h->band_pivots.clear(); h->band_valid.clear(); h->band_z.clear();
-        h->band_prec = prec;
-    }
-    const size_t bytes = band_slot_bytes(h);
-    const int missing = nslots - (int)h->band_factors.size();
+// At least nslots factor slots under the plan in force (made here if need be), at the precision the handle asks for
+static int band_ensure_slots(feasthip_ctx* h, int nslots, bool keep_count) {
+    int rc = band_check(h);
+    if (rc) return rc;
+    fh_factor_cache& cache = h->band_cache;
+    if (keep_count) nslots = std::max(nslots, cache.size());
+    const int prec = band_slot_prec(h);
+    cache.set_precision(prec, hipFree);
+    const size_t bytes = band_slot_bytes(h, prec);
+    const int had = cache.size(), missing = nslots - had;
     if (missing > 0) {
         size_t free_b = 0, total_b = 0;
         const double transient = band_transient_bytes(h, prec, nslots, bytes);
@@ -342,33 +344,24 @@ static int band_ensure_slots(feasthip_ctx* h, int nslots) {
         }
     }
     const auto t_alloc = std::chrono::steady_clock::now();
-    const int had = (int)h->band_factors.size();
-    struct alloc_report {
-        feasthip_ctx* h; std::chrono::steady_clock::time_point t0; int had; size_t bytes;
-        ~alloc_report() {
-            if ((int)h->band_factors.size() > had && fh_knob::debug_timing())
-                fprintf(stderr, "[feasthip] band factors: %d x %.2f GB allocated in %.1f ms\n", (int)h->band_factors.size() - had, bytes / 1e9,
-                        std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
-        }
-    } report{h, t_alloc, had, bytes};
-    while ((int)h->band_factors.size() < nslots) {
-        void* f = nullptr; int* pv = nullptr;
-        if (hipMalloc(&f, bytes) != hipSuccess) { (void)hipGetLastError(); h->last_error = "hipMalloc(band factor)"; return FEASTHIP_ERROR_MEMORY; }
-        if (hipMalloc((void**)&pv, (h->band_plan == 3 ? fh_mf_pivot_ints(h) : N) * sizeof(int)) != hipSuccess) { (void)hipGetLastError(); hipFree(f); h->last_error = "hipMalloc(band pivots)"; return FEASTHIP_ERROR_MEMORY; }
-        h->band_factors.push_back(f); h->band_pivots.push_back(pv); h->band_valid.push_back(0); h->band_z.push_back(cmake(0, 0));
-    }
+    const auto alloc = [](size_t b) { void* p = nullptr; if (hipMalloc(&p, b) != hipSuccess) { (void)hipGetLastError(); p = nullptr; } return p; };
+    const fh_grow_result got = cache.grow(nslots, bytes, band_slot_pivot_ints(h) * sizeof(int), alloc, hipFree);
+    if (cache.size() > had && fh_knob::debug_timing())
+        fprintf(stderr, "[feasthip] band factors: %d x %.2f GB allocated in %.1f ms\n", cache.size() - had, bytes / 1e9,
+                std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_alloc).count());
+    if (got != FH_GROW_OK) { h->last_error = got == FH_GROW_NO_FACTOR ? "hipMalloc(band factor)" : "hipMalloc(band pivots)"; return FEASTHIP_ERROR_MEMORY; }
     return 0;
 }
 
 // device arrays of per-node pointers for the slots in `which`: storage (narrow) or matrix base (wide), pivots, (wide) perm
 static int band_pointer_arrays(feasthip_ctx* h, const std::vector<int>& which, cplx*** dabs_out, int*** dpvs_out, int*** dperms_out) {
     const int nf = (int)which.size();
-    const size_t off = h->band_plan == 2 ? fh_wband_base_offset((int)h->csr.N, h->band_kl, h->band_ku) : 0;
+    const size_t off = h->band_plan == FH_PLAN_BAND ? fh_wband_base_offset((int)h->csr.N, h->band_kl, h->band_ku) : 0;
     int rc;
     std::vector<cplx*> abs(nf);
     std::vector<int*> pvs(nf), perms(nf, h->band_perm);
-    const size_t esz = (h->band_plan == 2 && h->band_prec == 32) ? sizeof(cplxf) : sizeof(cplx);
-    for (int q = 0; q < nf; ++q) { abs[q] = (cplx*)((char*)h->band_factors[which[q]] + off * esz); pvs[q] = h->band_pivots[which[q]]; }
+    const size_t esz = (h->band_plan == FH_PLAN_BAND && h->band_cache.prec == 32) ? sizeof(cplxf) : sizeof(cplx);
+    for (int q = 0; q < nf; ++q) { abs[q] = (cplx*)((char*)h->band_cache.slots[which[q]].factor + off * esz); pvs[q] = h->band_cache.slots[which[q]].pivots; }
     cplx** dabs;
     int **dpvs, **dperms;
     if ((rc = fh_buf(h, "bd_ptrs", nf, &dabs))) return rc;
@@ -389,10 +382,10 @@ static int mf_nodes_per_call(feasthip_ctx* h) {
 
 // The multifrontal plan rejected a factorisation (fh_mf.hpp: a zero pivot, or a boundary multiplier beyond
 // fh_mf::max_boundary_multiplier): this matrix goes to the blocked band plan for good -- reverse Cuthill-McKee, partial
-// pivoting over the whole band.  Every factor slot is re-made (their size changes; band_valid = 0: a cached node is factored
+// pivoting over the whole band.  Every factor slot is re-made (their size changes; FH_SLOT_EMPTY: a cached node is factored
 // again when it is next used), as many as there were.  A band whose factors do not fit fails here with the reason in last_error.
 static int band_fall_back(feasthip_ctx* h) {
-    const int nslots = (int)h->band_factors.size();
+    const int nslots = h->band_cache.size();
     const int required = h->band_plan_required;
     fh_banded_free(h);
     h->band_plan_required = required;       // the band plan inherits it: band_make_plan keeps such a plan while the requirement is on
@@ -403,8 +396,7 @@ static int band_fall_back(feasthip_ctx* h) {
     std::vector<int> perm, iperm;
     band_rcm_order(h, kl0, ku0, perm, iperm, kl1, ku1);
     int rc = band_take_band_plan(h, perm, iperm, kl0, ku0, kl1, ku1);
-    if (!rc) rc = band_check(h);
-    if (!rc) rc = band_ensure_slots(h, nslots);
+    if (!rc) rc = band_ensure_slots(h, nslots, false);
     if (rc) h->last_error = "multifrontal LU rejected a pivot; its band LU fallback: " + h->last_error;
     return rc;
 }
@@ -417,10 +409,10 @@ static int band_factor_batch(feasthip_ctx* h, const std::vector<int>& which, con
     const auto t_factor = std::chrono::steady_clock::now();
     int rc;
     cplx* dz;
-    if (h->band_plan == 3) {
+    if (h->band_plan == FH_PLAN_MF) {
         std::vector<void*> stores(nf);
         std::vector<int*> pvs(nf);
-        for (int q = 0; q < nf; ++q) { stores[q] = h->band_factors[which[q]]; pvs[q] = h->band_pivots[which[q]]; }
+        for (int q = 0; q < nf; ++q) { stores[q] = h->band_cache.slots[which[q]].factor; pvs[q] = h->band_cache.slots[which[q]].pivots; }
         if ((rc = fh_buf(h, "bd_z", nf, &dz))) return rc;
         FH_CHECK(hipMemcpyAsync(dz, zlist.data(), nf * sizeof(cplx), hipMemcpyHostToDevice, h->stream));
         // (fronts of a group) x (nodes of a call) is a grid dimension: node batches for long contours
@@ -432,7 +424,7 @@ static int band_factor_batch(feasthip_ctx* h, const std::vector<int>& which, con
             const int cnt = std::min(per_call, nf - q0);
             std::vector<int> info_part;
             std::vector<double> mult_part;
-            if ((rc = fh_mf_factor(h, h->band_prec, cnt, stores.data() + q0, pvs.data() + q0, dz + q0, info_part, mult_part))) return rc;
+            if ((rc = fh_mf_factor(h, h->band_cache.prec, cnt, stores.data() + q0, pvs.data() + q0, dz + q0, info_part, mult_part))) return rc;
             for (int q = 0; q < cnt; ++q) {
                 info_out[q0 + q] = info_part[q];
                 worst = std::max(worst, mult_part[q]);
@@ -440,7 +432,7 @@ static int band_factor_batch(feasthip_ctx* h, const std::vector<int>& which, con
             }
         }
         if (fh_knob::debug_timing())
-            fprintf(stderr, "[feasthip] multifrontal LU: %d factorisations (%d-bit) in %.1f ms, largest boundary multiplier %.3g%s\n", nf, h->band_prec,
+            fprintf(stderr, "[feasthip] multifrontal LU: %d factorisations (%d-bit) in %.1f ms, largest boundary multiplier %.3g%s\n", nf, h->band_cache.prec,
                     std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_factor).count(), worst,
                     rejected ? ": rejected, band LU from here" : "");
         if (!rejected) return 0;
@@ -462,13 +454,13 @@ static int band_factor_batch(feasthip_ctx* h, const std::vector<int>& which, con
     if ((rc = fh_buf(h, "bd_info", nf, &dinfo))) return rc;
     FH_CHECK(hipMemcpyAsync(dz, zlist.data(), nf * sizeof(cplx), hipMemcpyHostToDevice, h->stream));
     FH_CHECK(hipMemsetAsync(dinfo, 0, nf * sizeof(int), h->stream));
-    if (h->band_plan == 2) {
+    if (h->band_plan == FH_PLAN_BAND) {
         std::vector<void*> abs(nf);
-        for (int q = 0; q < nf; ++q) abs[q] = h->band_factors[which[q]];
-        if ((rc = fh_wband_factor(h, h->band_prec, nf, abs.data(), (void**)dabs, dpvs, dz, dinfo, h->band_iperm, kl, ku))) return rc;
+        for (int q = 0; q < nf; ++q) abs[q] = h->band_cache.slots[which[q]].factor;
+        if ((rc = fh_wband_factor(h, h->band_cache.prec, nf, abs.data(), (void**)dabs, dpvs, dz, dinfo, h->band_iperm, kl, ku))) return rc;
     } else {
         const size_t ldab = (size_t)2 * kl + ku + 1;
-        for (int q = 0; q < nf; ++q) FH_CHECK(hipMemsetAsync(h->band_factors[which[q]], 0, ldab * N * sizeof(cplx), h->stream));
+        for (int q = 0; q < nf; ++q) FH_CHECK(hipMemsetAsync(h->band_cache.slots[which[q]].factor, 0, ldab * N * sizeof(cplx), h->stream));
         const dim3 grid((N + FH_BLOCK - 1) / FH_BLOCK, nf), block(FH_BLOCK);
         const bool bid = h->csr.b_identity != 0;
         fh_prof_begin(h, "band_form");
@@ -487,7 +479,7 @@ static int band_factor_batch(feasthip_ctx* h, const std::vector<int>& which, con
     FH_CHECK(hipMemcpyAsync(info_out.data(), dinfo, nf * sizeof(int), hipMemcpyDeviceToHost, h->stream));
     FH_CHECK(hipStreamSynchronize(h->stream));
     if (fh_knob::debug_timing())
-        fprintf(stderr, "[feasthip] band LU: %d factorisations (plan %d, kl %d ku %d, %d-bit) in %.1f ms\n", nf, h->band_plan, kl, ku, h->band_prec,
+        fprintf(stderr, "[feasthip] band LU: %d factorisations (plan %d, kl %d ku %d, %d-bit) in %.1f ms\n", nf, (int)h->band_plan, kl, ku, h->band_cache.prec,
                 std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_factor).count());
     return 0;
 }
@@ -496,32 +488,33 @@ static int band_solve_batch(feasthip_ctx* h, int ld, int m, const std::vector<in
     const int nf = (int)slots.size();
     const int N = (int)h->csr.N;
     int rc;
-    if (h->band_plan == 3) {
+    const int prec = h->band_cache.prec;
+    if (h->band_plan == FH_PLAN_MF) {
         std::vector<void*> stores(nf);
         std::vector<int*> pvs(nf);
-        for (int q = 0; q < nf; ++q) { stores[q] = h->band_factors[slots[q]]; pvs[q] = h->band_pivots[slots[q]]; }
+        for (int q = 0; q < nf; ++q) { stores[q] = h->band_cache.slots[slots[q]].factor; pvs[q] = h->band_cache.slots[slots[q]].pivots; }
         const int per_call = mf_nodes_per_call(h);
         for (int q0 = 0; q0 < nf; q0 += per_call) {
             const int cnt = std::min(per_call, nf - q0);
-            rc = h->adjoint ? fh_mf_solve_adjoint(h, h->band_prec, cnt, stores.data() + q0, pvs.data() + q0, RHS + (size_t)q0 * rhs_stride, rhs_stride, Y + (size_t)q0 * stride, stride, ld, m)
-                            : fh_mf_solve(h, h->band_prec, cnt, stores.data() + q0, pvs.data() + q0, RHS + (size_t)q0 * rhs_stride, rhs_stride, Y + (size_t)q0 * stride, stride, ld, m);
+            rc = h->adjoint ? fh_mf_solve_adjoint(h, prec, cnt, stores.data() + q0, pvs.data() + q0, RHS + (size_t)q0 * rhs_stride, rhs_stride, Y + (size_t)q0 * stride, stride, ld, m)
+                            : fh_mf_solve(h, prec, cnt, stores.data() + q0, pvs.data() + q0, RHS + (size_t)q0 * rhs_stride, rhs_stride, Y + (size_t)q0 * stride, stride, ld, m);
             if (rc) return rc;
         }
         return 0;
     }
     // (the API layer lets the adjoint switch through for the multifrontal and the blocked band plan with complex128 factors:
     // fh_banded_adjoint_ready, fh_check_adjoint)
-    if (h->adjoint && (h->band_plan != 2 || h->band_prec == 32)) { h->last_error = "internal: adjoint substitution on the narrow band plan or on complex64 factors"; return FEASTHIP_ERROR_INTERNAL; }
+    if (h->adjoint && (h->band_plan != FH_PLAN_BAND || prec == 32)) { h->last_error = "internal: adjoint substitution on the narrow band plan or on complex64 factors"; return FEASTHIP_ERROR_INTERNAL; }
     cplx** dabs; int** dpvs; int** dperms;
     if ((rc = band_pointer_arrays(h, slots, &dabs, &dpvs, &dperms))) return rc;
-    if (h->band_plan == 2) {
+    if (h->band_plan == FH_PLAN_BAND) {
         void *Yb, *Zb;                               // complex128 or complex64 panels: sized in bytes
         const size_t bstride = (size_t)N * ld;
-        const size_t esz = h->band_prec == 32 ? sizeof(cplxf) : sizeof(cplx);
+        const size_t esz = prec == 32 ? sizeof(cplxf) : sizeof(cplx);
         if ((rc = fh_get_buf(h, "bd_ypanel", (size_t)nf * bstride * esz, &Yb))) return rc;
         if ((rc = fh_get_buf(h, "bd_zpanel", (size_t)nf * bstride * esz, &Zb))) return rc;
         if (h->adjoint) return fh_wband_solve_adjoint(h, nf, (void**)dabs, dpvs, dperms, h->band_perm, RHS, rhs_stride, Y, stride, Yb, Zb, ld, m, h->band_kl, h->band_ku);
-        return fh_wband_solve(h, h->band_prec, nf, (void**)dabs, dpvs, dperms, h->band_perm, RHS, rhs_stride, Y, stride, Yb, Zb, ld, m, h->band_kl, h->band_ku);
+        return fh_wband_solve(h, prec, nf, (void**)dabs, dpvs, dperms, h->band_perm, RHS, rhs_stride, Y, stride, Yb, Zb, ld, m, h->band_kl, h->band_ku);
     }
     fh_prof_begin(h, "band_solve");
     const size_t total = (size_t)N * ld;
@@ -531,92 +524,7 @@ static int band_solve_batch(feasthip_ctx* h, int ld, int m, const std::vector<in
     return 0;
 }
 
-// Factor the nodes listed in `slots` where the cache does not already hold z[q] in slot slots[q].
-static int band_factor_slots(feasthip_ctx* h, const std::vector<int>& slots, const std::vector<cplx>& z, int64_t* nfact) {
-    const int nodes = (int)slots.size();
-    int rc;
-    std::vector<int> need;
-    std::vector<cplx> zl;
-    for (int e = 0; e < nodes; ++e) {
-        const int s = slots[e];
-        const bool ok = h->cache_factors && h->band_valid[s] == 1 && h->band_z[s].x == z[e].x && h->band_z[s].y == z[e].y;
-        if (!ok) { need.push_back(s); zl.push_back(z[e]); h->band_valid[s] = 0; }
-    }
-    std::vector<int> info;
-    if ((rc = band_factor_batch(h, need, zl, info))) return rc;
-    for (size_t q = 0; q < need.size(); ++q) {
-        h->band_z[need[q]] = zl[q];
-        h->band_valid[need[q]] = info[q] == 0 ? 1 : -1;
-    }
-    int64_t done = (int64_t)need.size();
-    // a fallback to the band plan inside the batch re-made every slot: the nodes that were cached are factored again
-    std::vector<int> lost;
-    std::vector<cplx> zlost;
-    for (int e = 0; e < nodes; ++e)
-        if (h->band_valid[slots[e]] == 0) { lost.push_back(slots[e]); zlost.push_back(z[e]); }
-    if (!lost.empty()) {
-        if ((rc = band_factor_batch(h, lost, zlost, info))) return rc;
-        for (size_t q = 0; q < lost.size(); ++q) {
-            h->band_z[lost[q]] = zlost[q];
-            h->band_valid[lost[q]] = info[q] == 0 ? 1 : -1;
-        }
-        done += (int64_t)lost.size();
-    }
-    if (nfact) *nfact = done;
-    return 0;
-}
-
-// Factor (where the cache does not already hold z[q] in slot slots[q]) and solve the nodes listed in `slots`.
-static int band_solve_slots(feasthip_ctx* h, int ld, int m, const std::vector<int>& slots, const std::vector<cplx>& z, const cplx* RHS,
-                            size_t rhs_stride, cplx* Y, size_t stride, std::vector<int>& status, int64_t* nfact) {
-    const int nodes = (int)slots.size();
-    int rc;
-    if ((rc = band_factor_slots(h, slots, z, nfact))) return rc;
-    if ((rc = band_solve_batch(h, ld, m, slots, RHS, rhs_stride, Y, stride))) return rc;
-    status.assign(nodes, 0);
-    for (int e = 0; e < nodes; ++e) if (h->band_valid[slots[e]] != 1) status[e] = FEASTHIP_ERROR_LAPACK;
-    return 0;
-}
-
-int fh_banded_solve_nodes(feasthip_ctx* h, int ld, int m, int nodes, const std::vector<cplx>& z, const cplx* RHS, size_t rhs_stride, cplx* Y,
-                          size_t stride, std::vector<int>& status, int64_t* nfact) {
-    int rc = band_check(h);
-    if (rc) return rc;
-    if ((rc = band_ensure_slots(h, nodes))) return rc;
-    std::vector<int> slots(nodes);
-    for (int e = 0; e < nodes; ++e) slots[e] = e;
-    return band_solve_slots(h, ld, m, slots, z, RHS, rhs_stride, Y, stride, status, nfact);
-}
-
-// slots[d]: the factor slot of shift z[d], mapped by shift (see fh_banded_solve_subset); slots are added as needed
-static int band_match_slots(feasthip_ctx* h, const std::vector<cplx>& z, std::vector<int>& slots) {
-    const int nd = (int)z.size();
-    int rc;
-    if ((rc = band_ensure_slots(h, std::max(nd, (int)h->band_factors.size())))) return rc;
-    const int nslots = (int)h->band_factors.size();
-    std::vector<int> taken(nslots, 0);
-    slots.assign(nd, -1);
-    for (int d = 0; d < nd; ++d)
-        for (int s = 0; s < nslots && h->cache_factors; ++s)
-            if (!taken[s] && h->band_valid[s] == 1 && h->band_z[s].x == z[d].x && h->band_z[s].y == z[d].y) { slots[d] = s; taken[s] = 1; break; }
-    for (int pass = 0; pass < 2; ++pass)          // free slots first, then the cached ones nobody claimed
-        for (int d = 0; d < nd; ++d)
-            for (int s = 0; s < nslots && slots[d] < 0; ++s)
-                if (!taken[s] && (pass == 1 || h->band_valid[s] != 1)) { slots[d] = s; taken[s] = 1; }
-    return 0;
-}
-
-// The direct nodes of a per-node sweep (feasthip_set_node_solver): a subset of the local nodes, so the factor slots are
-// mapped by shift instead of by local node -- a node whose z is cached keeps its slot whatever else joined or left the
-// subset, the others take the slots no node of this call holds.  Only as many slots as the subset needs are allocated.
-int fh_banded_solve_subset(feasthip_ctx* h, int ld, int m, const std::vector<cplx>& z, const cplx* RHS, cplx* Y, size_t stride,
-                           std::vector<int>& status, int64_t* nfact) {
-    int rc = band_check(h);
-    if (rc) return rc;
-    std::vector<int> slots;
-    if ((rc = band_match_slots(h, z, slots))) return rc;
-    return band_solve_slots(h, ld, m, slots, z, RHS, 0, Y, stride, status, nfact);
-}
+const fh_direct_ops& fh_banded_direct_ops() { static const fh_direct_ops ops = {&feasthip_ctx::band_cache, band_ensure_slots, band_factor_batch, band_solve_batch}; return ops; }
 
 // Shift preconditioner: the pivots' factors through the same cache and the same slot mapping as the direct nodes of a
 // per-node sweep, so a factor a direct node left at a pivot's shift is reused and only as many slots as there are pivots
@@ -625,58 +533,26 @@ int fh_banded_precond_factor(feasthip_ctx* h, const std::vector<cplx>& pivots, s
                              int64_t* nfact, int* fell_back, int64_t* slot_bytes) {
     int rc = band_check(h);
     if (rc) return rc;
-    if ((rc = band_match_slots(h, pivots, slots))) return rc;
-    const int plan0 = h->band_plan;
-    if ((rc = band_factor_slots(h, slots, pivots, nfact))) return rc;
-    if (fell_back) *fell_back = plan0 == 3 && h->band_plan != 3 ? 1 : 0;
-    if (slot_bytes) *slot_bytes = (int64_t)band_slot_bytes(h);
-    status.assign(pivots.size(), 0);
-    for (size_t p = 0; p < pivots.size(); ++p) if (h->band_valid[slots[p]] != 1) status[p] = FEASTHIP_ERROR_LAPACK;
+    const fh_direct_plan plan0 = h->band_plan;
+    if ((rc = fh_direct_factor_matched(h, true, pivots, slots, status, nfact))) return rc;
+    if (fell_back) *fell_back = plan0 == FH_PLAN_MF && h->band_plan != FH_PLAN_MF ? 1 : 0;
+    if (slot_bytes) *slot_bytes = (int64_t)band_slot_bytes(h, h->band_cache.prec);
     return 0;
-}
-
-int fh_banded_precond_solve(feasthip_ctx* h, int ld, int m, const std::vector<int>& slots, const cplx* RHS, size_t rhs_stride, cplx* Y,
-                            size_t stride) {
-    for (int s : slots)
-        if (s < 0 || s >= (int)h->band_factors.size() || h->band_valid[s] != 1) { h->last_error = "internal: preconditioner substitution on a slot without factors"; return FEASTHIP_ERROR_INTERNAL; }
-    return band_solve_batch(h, ld, m, slots, RHS, rhs_stride, Y, stride);
 }
 
 // Device memory `nodes` direct nodes take under the plan in force: the cached factors and pivots, and the buffers that live
-// only while they are factored and swept (band_transient_bytes, which
-// band_ensure_slots checks its allocations against).
+// only while they are factored and swept (band_transient_bytes, which band_ensure_slots checks its allocations against).
+// The multifrontal plan is sized at the precision the next factorisation will have (band_slot_prec), the band plan at the
+// precision of the factors the cache holds now -- complex128 before the first factorisation whatever the handle asks for.
 int fh_banded_plan_bytes(feasthip_ctx* h, int nodes, int64_t* factor_bytes, int64_t* transient_bytes) {
     int rc = band_check(h);
-    if (rc && !h->band_plan) return rc;
-    const int prec = (h->band_plan >= 2 && h->factor_precision == 32) ? 32 : 64;
-    const double bytes = (double)(h->band_plan == 3 ? fh_mf_store_bytes(h, prec) : band_slot_bytes(h));
-    const double pivots = (double)(h->band_plan == 3 ? fh_mf_pivot_ints(h) : (size_t)h->csr.N) * sizeof(int);
+    if (rc && h->band_plan == FH_PLAN_NONE) return rc;
+    const int prec = band_slot_prec(h);
+    const double bytes = (double)band_slot_bytes(h, h->band_plan == FH_PLAN_MF ? prec : h->band_cache.prec);
+    const double pivots = (double)band_slot_pivot_ints(h) * sizeof(int);
     if (factor_bytes) *factor_bytes = (int64_t)((double)nodes * (bytes + pivots));
     if (transient_bytes) *transient_bytes = (int64_t)band_transient_bytes(h, prec, nodes, (size_t)bytes);
     return rc;
-}
-
-int fh_banded_solve_single(feasthip_ctx* h, int ld, int m, cplx z, const cplx* RHS, cplx* Y, int* status, int64_t* nfact) {
-    int rc = band_check(h);
-    if (rc) return rc;
-    int slot = h->node_count;           // a shift equal to a local quadrature node reuses that node's factor
-    for (int e = 0; e < h->node_count && e < (int)h->node_ids.size(); ++e) {
-        const cplx ze = h->zne[h->node_ids[e]];
-        if (ze.x == z.x && ze.y == z.y) { slot = e; break; }
-    }
-    if ((rc = band_ensure_slots(h, std::max(slot, h->node_count) + 1))) return rc;
-    std::vector<int> need(1, slot), info;
-    std::vector<cplx> zl(1, z);
-    const bool cached = h->cache_factors && h->band_valid[slot] == 1 && h->band_z[slot].x == z.x && h->band_z[slot].y == z.y;
-    if (!cached) {
-        if ((rc = band_factor_batch(h, need, zl, info))) return rc;
-        h->band_z[slot] = z;
-        h->band_valid[slot] = info[0] == 0 ? 1 : -1;
-        if (nfact) *nfact = 1;
-    }
-    if ((rc = band_solve_batch(h, ld, m, need, RHS, 0, Y, (size_t)h->csr.N * ld))) return rc;
-    *status = h->band_valid[slot] == 1 ? 0 : FEASTHIP_ERROR_LAPACK;
-    return 0;
 }
 
 // The adjoint switch on a CSR handle (fh_api.hip: fh_check_adjoint): the plan is made if need be and must be the multifrontal
@@ -685,8 +561,8 @@ int fh_banded_solve_single(feasthip_ctx* h, int ld, int m, cplx z, const cplx* R
 int fh_banded_adjoint_ready(feasthip_ctx* h) {
     const int rc = band_check(h);
     if (rc) return rc;
-    if (h->band_plan == 3) return 0;
-    if (h->band_plan == 2) {
+    if (h->band_plan == FH_PLAN_MF) return 0;
+    if (h->band_plan == FH_PLAN_BAND) {
         if (h->factor_precision != 32) return 0;
         h->last_error = "the direct plan of this matrix is the blocked band LU (plan 2) with complex64 factors; its adjoint substitution needs complex128 factors";
         return FEASTHIP_ERROR_FPM;
@@ -699,18 +575,19 @@ int fh_banded_adjoint_ready(feasthip_ctx* h) {
 // real flops of ONE node's factorisation under the plan in force (band: 8 N kl (kl + ku); multifrontal: the padded fronts)
 int fh_banded_plan_flops(feasthip_ctx* h, double* flops) {
     int rc = band_check(h);
-    if (rc && !h->band_plan) return rc;
-    if (flops) *flops = h->band_plan == 3 ? fh_mf_plan_flops(h) : 8.0 * (double)h->csr.N * (double)h->band_kl * (double)(h->band_kl + h->band_ku);
+    if (rc && h->band_plan == FH_PLAN_NONE) return rc;
+    if (flops) *flops = h->band_plan == FH_PLAN_MF ? fh_mf_plan_flops(h) : 8.0 * (double)h->csr.N * (double)h->band_kl * (double)(h->band_kl + h->band_ku);
     return rc;
 }
 
-// The band the direct solver would work on, and the device memory one factor takes (feasthip_band_plan)
+// The band the direct solver would work on, and the device memory one factor takes (feasthip_band_plan); the only place that
+// maps the plan to the ABI's `blocked`: 0 the narrow plan, 1 the blocked band LU, 2 multifrontal (kl, ku: the band it replaced)
 int fh_banded_plan(feasthip_ctx* h, int* kl, int* ku, int64_t* bytes_per_node, int* blocked) {
     int rc = band_check(h);
-    if (rc && !h->band_plan) return rc;
+    if (rc && h->band_plan == FH_PLAN_NONE) return rc;
     if (kl) *kl = h->band_kl;
     if (ku) *ku = h->band_ku;
-    if (bytes_per_node) *bytes_per_node = (int64_t)band_slot_bytes(h);
-    if (blocked) *blocked = h->band_plan == 3 ? 2 : (h->band_plan == 2 ? 1 : 0);      // 2: multifrontal (kl, ku: the band it replaced)
+    if (bytes_per_node) *bytes_per_node = (int64_t)band_slot_bytes(h, h->band_cache.prec);
+    if (blocked) *blocked = h->band_plan == FH_PLAN_MF ? 2 : (h->band_plan == FH_PLAN_BAND ? 1 : 0);
     return rc;
 }

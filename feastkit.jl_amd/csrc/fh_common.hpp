@@ -12,6 +12,8 @@
 #include <vector>
 #include <map>
 
+#include "fh_factor_cache.hpp"
+
 struct __attribute__((aligned(16))) cplx { double x, y; };
 
 __host__ __device__ inline cplx cmake(double a, double b) { cplx r; r.x = a; r.y = b; return r; }
@@ -210,6 +212,11 @@ struct fh_comm;   // fh_comm.hip: RCCL (or shared-device) communicator attached 
 // solvers only.
 enum fh_kind { FH_KIND_NONE = 0, FH_KIND_DENSE = 1, FH_KIND_CSR = 2, FH_KIND_POLYNOMIAL = 3, FH_KIND_OPERATOR = 4, FH_KIND_TERM_OPERATOR = 5 };
 
+// Plan of the sparse direct solver (feasthip_ctx::band_plan, made by fh_banded.hip: band_make_plan): NARROW, a band of at most
+// 64 diagonals in stored order (one-workgroup elimination); BAND, the blocked band LU on the dense kernels after reverse
+// Cuthill-McKee; MF, the multifrontal LU on a nested-dissection tree.  The values are what the "plan %d" messages print.
+enum fh_direct_plan { FH_PLAN_NONE = 0, FH_PLAN_NARROW = 1, FH_PLAN_BAND = 2, FH_PLAN_MF = 3 };
+
 struct feasthip_ctx {
     int device = 0;
     fh_comm* comm = nullptr;
@@ -274,28 +281,20 @@ struct feasthip_ctx {
     cplx* rs_R = nullptr;                       // A X - B X diag(lambda) of that step: the next sweep's shared start residual
     std::vector<cplx> rs_R_lambda;              // the lambda it was formed with
 
-    // dense LU cache: per local node factors + pivots
-    std::vector<void*> lu_factors;
-    std::vector<int*> lu_pivots;
-    std::vector<int> lu_valid;
-    std::vector<cplx> lu_z;
-    int lu_prec = 64;             // element type of the cached dense factors: 64 = complex128, 32 = complex64
-    // banded LU (CSR input, FEASTHIP_SOLVER_BANDED): bandwidths of the union pattern, factors per node slot
-    int csr_kl = 0, csr_ku = 0;
+    // LU factors + pivots per local node slot (fh_factor_cache.hpp; the sequences over them: fh_direct.hip): the dense LU's,
+    // and the sparse direct solver's (CSR input, FEASTHIP_SOLVER_BANDED; complex64 factors under FH_PLAN_BAND / FH_PLAN_MF only)
+    fh_factor_cache lu_cache, band_cache;
+    int csr_kl = 0, csr_ku = 0;   // bandwidths of the union pattern
     // pattern of the matrix as stored on the device (ingest order), kept on the host for the band plan of the direct solver
     std::vector<int> host_rowptr, host_col;
-    // band plan (fh_banded.hip): 0 not made, 1 narrow band in stored order (one-workgroup elimination), 2 blocked band LU
-    // on the dense kernels in band order (band_perm[band row] = stored row, band_iperm its inverse; both on the device)
-    int band_plan = 0, band_kl = 0, band_ku = 0;
+    // plan of the sparse direct solver (fh_banded.hip); FH_PLAN_BAND works in band order (band_perm[band row] = stored row,
+    // band_iperm its inverse; both on the device)
+    fh_direct_plan band_plan = FH_PLAN_NONE;
+    int band_kl = 0, band_ku = 0;
     int band_plan_required = 0;   // the plan was made while feasthip_require_adjoint was on (dropped when it is next needed with the requirement off)
-    int band_prec = 64;           // element type of the cached band factors (blocked plan): 64 = complex128, 32 = complex64
     int* band_perm = nullptr;
     int* band_iperm = nullptr;
-    std::vector<void*> band_factors;
-    std::vector<int*> band_pivots;
-    std::vector<int> band_valid;
-    std::vector<cplx> band_z;
-    void* mf = nullptr;           // multifrontal plan of the sparse direct solver (fh_dense.hip: fh_mf_state), band_plan == 3
+    void* mf = nullptr;           // multifrontal plan of the sparse direct solver (fh_dense.hip: fh_mf_state), band_plan == FH_PLAN_MF
     // feasthip_set_ortho_method / feasthip_last_ortho: what rejected panels take, and what the last orthonormalisation did
     int ortho_method = 0;         // FEASTHIP_ORTHO_MGS | FEASTHIP_ORTHO_CHOLQR_RR
     struct { int panels = 0, used = 0, stages = 0, fell_back = 0, rank = 0; std::vector<int> perm; std::vector<double> rdiag; } ortho_last;
@@ -350,6 +349,31 @@ template <typename T> inline int fh_buf(feasthip_ctx* h, const char* name, size_
 void fh_free_bufs(feasthip_ctx* h);
 // frees the matrices, factors and plans of the current problem (any kind) and leaves h->kind = FH_KIND_NONE
 void fh_free_problem(feasthip_ctx* h);
+
+// What a direct solver gives the sequences of fh_direct.hip: its factor cache; at least nslots slots of the handle's factor
+// precision (the sparse solver makes its plan first; keep_count: and no fewer than the cache held, whatever is dropped on the
+// way); the factors of z[q] B - A into slot which[q], info[q] != 0: singular; and Y[q] = (z B - A)^-1 RHS[q] on the factors of
+// slots[q] (rhs_stride 0: one right-hand side panel shared by all; h->adjoint: the conjugate-transposed substitution).
+struct fh_direct_ops {
+    fh_factor_cache feasthip_ctx::* cache;
+    int (*ensure_slots)(feasthip_ctx* h, int nslots, bool keep_count);
+    int (*factor)(feasthip_ctx* h, const std::vector<int>& which, const std::vector<cplx>& z, std::vector<int>& info);
+    int (*solve)(feasthip_ctx* h, int ld, int m, const std::vector<int>& slots, const cplx* RHS, size_t rhs_stride, cplx* Y, size_t stride);
+};
+// fh_direct.hip: the sequences over a factor cache, on the sparse direct solver (banded) or the dense LU.  Factors are reused
+// when h->cache_factors and the slot holds the shift exactly; *nfact: factorisations done; status: 0 or FEASTHIP_ERROR_LAPACK.
+// Every local node, slot e for node e:  Y[e] = (z_e B - A)^-1 RHS_e
+int fh_direct_solve_nodes(feasthip_ctx* h, bool banded, int ld, int m, int nodes, const std::vector<cplx>& z, const cplx* RHS, size_t rhs_stride,
+                          cplx* Y, size_t stride, std::vector<int>& status, int64_t* nfact);
+// One shift, in the slot fh_one_off_slot gives it; *nfact = 1 when it was factored, left alone when the factor was cached
+int fh_direct_solve_single(feasthip_ctx* h, bool banded, int ld, int m, cplx z, const cplx* RHS, cplx* Y, int* status, int64_t* nfact);
+// A subset of the nodes on one shared RHS panel: slots matched by shift (fh_factor_cache::match), only as many as it needs
+int fh_direct_solve_subset(feasthip_ctx* h, bool banded, int ld, int m, const std::vector<cplx>& z, const cplx* RHS, cplx* Y, size_t stride,
+                           std::vector<int>& status, int64_t* nfact);
+// The factors of the distinct shifts z, matched by shift likewise, without a solve: slots[p] and status[p] of shift p ...
+int fh_direct_factor_matched(feasthip_ctx* h, bool banded, const std::vector<cplx>& z, std::vector<int>& slots, std::vector<int>& status, int64_t* nfact);
+// ... and Y_q = (z B - A)^-1 RHS_q with the factors in slots[q] (a slot may be named more than once), q < slots.size()
+int fh_direct_solve_slots(feasthip_ctx* h, bool banded, int ld, int m, const std::vector<int>& slots, const cplx* RHS, size_t rhs_stride, cplx* Y, size_t stride);
 
 // profiling helpers
 void fh_prof_begin(feasthip_ctx* h, const char* cls);

@@ -1603,7 +1603,7 @@ static int lu_factor_batch(feasthip_ctx* h, const std::vector<int>& which, const
     int rc;
     std::vector<T*> lus(nf);
     std::vector<int*> pvs(nf);
-    for (int q = 0; q < nf; ++q) { lus[q] = (T*)h->lu_factors[which[q]]; pvs[q] = h->lu_pivots[which[q]]; }
+    for (int q = 0; q < nf; ++q) { lus[q] = (T*)h->lu_cache.slots[which[q]].factor; pvs[q] = h->lu_cache.slots[which[q]].pivots; }
     T** dlus;
     int** dpvs;
     cplx* dz;
@@ -1841,7 +1841,7 @@ static int lu_solve_batch(feasthip_ctx* h, int ld, int m, const std::vector<int>
     int rc;
     std::vector<T*> lus(nf);
     std::vector<int*> perms(nf);
-    for (int q = 0; q < nf; ++q) { lus[q] = (T*)h->lu_factors[slots[q]]; perms[q] = h->lu_pivots[slots[q]] + N; }
+    for (int q = 0; q < nf; ++q) { lus[q] = (T*)h->lu_cache.slots[slots[q]].factor; perms[q] = h->lu_cache.slots[slots[q]].pivots + N; }
     T** dlus;
     int** dperms;
     T* Z;
@@ -1876,83 +1876,30 @@ static int lu_solve_batch(feasthip_ctx* h, int ld, int m, const std::vector<int>
     return 0;
 }
 
-static int lu_ensure_slots(feasthip_ctx* h, int nslots) {
+static int lu_ensure_slots(feasthip_ctx* h, int nslots, bool keep_count) {
     const size_t N = (size_t)h->dense.N;
-    const int prec = h->factor_precision == 32 ? 32 : 64;
-    if (h->lu_prec != prec) {                       // factor precision changed: drop the cached factors
-        for (void* p : h->lu_factors) if (p) hipFree(p);
-        for (int* p : h->lu_pivots) if (p) hipFree(p);
-        h->lu_factors.clear(); h->lu_pivots.clear(); h->lu_valid.clear(); h->lu_z.clear();
-        h->lu_prec = prec;
-    }
-    const size_t esz = prec == 32 ? sizeof(cplxf) : sizeof(cplx);
-    while ((int)h->lu_factors.size() < nslots) {
-        void* f = nullptr; int* pv = nullptr;
-        // factor, then the inverted diagonal blocks (k_lu_invert_diag); pivots, then the row permutation
-        const size_t nblk = (N + LU_NB - 1) / LU_NB;
-        const size_t nblk128 = (N + SOLVE_KB - 1) / SOLVE_KB;
-        FH_CHECK(hipMalloc(&f, (N * N + nblk * 2 * LU_NB * LU_NB + nblk128 * 2 * SOLVE_KB * SOLVE_KB) * esz));
-        hipError_t e = hipMalloc((void**)&pv, 2 * N * sizeof(int));
-        if (e != hipSuccess) { hipFree(f); h->last_error = "hipMalloc(pivots)"; return FEASTHIP_ERROR_MEMORY; }
-        h->lu_factors.push_back(f); h->lu_pivots.push_back(pv); h->lu_valid.push_back(0); h->lu_z.push_back(cmake(0, 0));
-    }
+    if (keep_count) nslots = std::max(nslots, h->lu_cache.size());
+    h->lu_cache.set_precision(h->factor_precision == 32 ? 32 : 64, hipFree);
+    const size_t esz = h->lu_cache.prec == 32 ? sizeof(cplxf) : sizeof(cplx);
+    // factor, then the inverted diagonal blocks (k_lu_invert_diag); pivots, then the row permutation
+    const size_t nblk = (N + LU_NB - 1) / LU_NB;
+    const size_t nblk128 = (N + SOLVE_KB - 1) / SOLVE_KB;
+    const size_t bytes = (N * N + nblk * 2 * LU_NB * LU_NB + nblk128 * 2 * SOLVE_KB * SOLVE_KB) * esz;
+    hipError_t err = hipSuccess;
+    const auto alloc = [&err](size_t b) { void* p = nullptr; err = hipMalloc(&p, b); return err == hipSuccess ? p : nullptr; };
+    const fh_grow_result got = h->lu_cache.grow(nslots, bytes, 2 * N * sizeof(int), alloc, hipFree);
+    if (got == FH_GROW_NO_PIVOTS) { h->last_error = "hipMalloc(pivots)"; return FEASTHIP_ERROR_MEMORY; }
+    if (got == FH_GROW_NO_FACTOR) { h->last_error = std::string("hipMalloc(dense factor): ") + hipGetErrorString(err); return err == hipErrorOutOfMemory ? FEASTHIP_ERROR_MEMORY : FEASTHIP_ERROR_INTERNAL; }
     return 0;
 }
 
-int fh_dense_lu_solve_nodes(feasthip_ctx* h, int ld, int m, int nodes, const std::vector<cplx>& z, const cplx* RHS,
-                            size_t rhs_stride, cplx* Y, size_t stride, std::vector<int>& status, int64_t* nfact) {
-    int rc = lu_ensure_slots(h, nodes);
-    const bool f32 = h->lu_prec == 32;
-    if (rc) return rc;
-    std::vector<int> need;
-    std::vector<cplx> zl;
-    for (int e = 0; e < nodes; ++e) {
-        bool ok = h->cache_factors && h->lu_valid[e] == 1 && h->lu_z[e].x == z[e].x && h->lu_z[e].y == z[e].y;
-        if (!ok) { need.push_back(e); zl.push_back(z[e]); h->lu_valid[e] = 0; }
-    }
-    std::vector<int> info;
-    if ((rc = f32 ? lu_factor_batch<cplxf>(h, need, zl, info) : lu_factor_batch<cplx>(h, need, zl, info))) return rc;
-    for (size_t q = 0; q < need.size(); ++q) {
-        h->lu_z[need[q]] = zl[q];
-        h->lu_valid[need[q]] = info[q] == 0 ? 1 : -1;   // -1: singular
-    }
-    if (nfact) *nfact = (int64_t)need.size();
-    std::vector<int> slots(nodes);
-    for (int e = 0; e < nodes; ++e) slots[e] = e;
-    if ((rc = f32 ? lu_solve_batch<cplxf>(h, ld, m, slots, RHS, rhs_stride, Y, stride)
-                  : lu_solve_batch<cplx>(h, ld, m, slots, RHS, rhs_stride, Y, stride))) return rc;
-    status.assign(nodes, 0);
-    for (int e = 0; e < nodes; ++e) if (h->lu_valid[e] != 1) status[e] = FEASTHIP_ERROR_LAPACK;
-    return 0;
+static int lu_factor(feasthip_ctx* h, const std::vector<int>& which, const std::vector<cplx>& z, std::vector<int>& info) {
+    return h->lu_cache.prec == 32 ? lu_factor_batch<cplxf>(h, which, z, info) : lu_factor_batch<cplx>(h, which, z, info);
 }
-
-int fh_dense_lu_solve_single(feasthip_ctx* h, int ld, int m, cplx z, const cplx* RHS, cplx* Y, int* status, int64_t* nfact) {
-    // Factor cache for one-off shifts (RCI jobs 10/11, linear_solver callbacks): a shift equal to
-    // a local quadrature node uses that node's slot, so an RCI sweep over the contour keeps one
-    // factorisation per node across refinement loops, as the reference's drivers do
-    // (factor_cache, src/dense/feast_dense.jl:458, 487-497); any other shift shares one extra slot.
-    int slot = h->node_count;
-    for (int e = 0; e < h->node_count && e < (int)h->node_ids.size(); ++e) {
-        const cplx ze = h->zne[h->node_ids[e]];
-        if (ze.x == z.x && ze.y == z.y) { slot = e; break; }
-    }
-    int rc = lu_ensure_slots(h, std::max(slot, h->node_count) + 1);
-    if (rc) return rc;
-    const bool f32 = h->lu_prec == 32;
-    std::vector<int> need(1, slot), info;
-    std::vector<cplx> zl(1, z);
-    bool cached = h->cache_factors && h->lu_valid[slot] == 1 && h->lu_z[slot].x == z.x && h->lu_z[slot].y == z.y;
-    if (!cached) {
-        if ((rc = f32 ? lu_factor_batch<cplxf>(h, need, zl, info) : lu_factor_batch<cplx>(h, need, zl, info))) return rc;
-        h->lu_z[slot] = z;
-        h->lu_valid[slot] = info[0] == 0 ? 1 : -1;
-        if (nfact) *nfact = 1;
-    }
-    if ((rc = f32 ? lu_solve_batch<cplxf>(h, ld, m, need, RHS, 0, Y, (size_t)h->dense.N * ld)
-                  : lu_solve_batch<cplx>(h, ld, m, need, RHS, 0, Y, (size_t)h->dense.N * ld))) return rc;
-    *status = h->lu_valid[slot] == 1 ? 0 : FEASTHIP_ERROR_LAPACK;
-    return 0;
+static int lu_solve(feasthip_ctx* h, int ld, int m, const std::vector<int>& slots, const cplx* RHS, size_t rhs_stride, cplx* Y, size_t stride) {
+    return h->lu_cache.prec == 32 ? lu_solve_batch<cplxf>(h, ld, m, slots, RHS, rhs_stride, Y, stride) : lu_solve_batch<cplx>(h, ld, m, slots, RHS, rhs_stride, Y, stride);
 }
+const fh_direct_ops& fh_dense_direct_ops() { static const fh_direct_ops ops = {&feasthip_ctx::lu_cache, lu_ensure_slots, lu_factor, lu_solve}; return ops; }
 
 // =======================================================================================
 // Blocked band LU on the dense kernels: the sparse DIRECT solver for patterns whose band (after the reverse

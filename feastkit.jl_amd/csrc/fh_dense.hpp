@@ -32,14 +32,7 @@ int fh_poly_form(feasthip_ctx* h, void* const* dlus, const cplx* dz, int nf, int
 // each one a node of the table's contour, matched exactly) -- what the forming kernels of both direct solvers read.
 int fh_poly_term_table(feasthip_ctx* h, const cplx* dz, int nf, const cplx** dF);
 
-// Factor (cached per local node when h->cache_factors) and solve all local nodes:
-//   Y[e] = (z_e B - A)^{-1} RHS     RHS: one shared panel; Y: node-strided panels
-// (h->adjoint: (z_e B - A)^{-H} RHS by conjugate-transposed substitution on the same cached fp64 factors)
-int fh_dense_lu_solve_nodes(feasthip_ctx* h, int ld, int m, int nodes, const std::vector<cplx>& z, const cplx* RHS, size_t rhs_stride,
-                            cplx* Y, size_t stride, std::vector<int>& status, int64_t* nfact);
-// one-off (uncached) solve for a single shift
-int fh_dense_lu_solve_single(feasthip_ctx* h, int ld, int m, cplx z, const cplx* RHS, cplx* Y, int* status,
-                             int64_t* nfact);
+const fh_direct_ops& fh_dense_direct_ops();          // the dense LU's operations for the sequences of fh_direct.hip
 
 // Blocked band LU on the dense kernels (fh_dense.hip, "wide band"): storage per node fh_wband_elems complex128 values, the
 // matrix pointer the kernels take is storage + fh_wband_base_offset.

@@ -172,9 +172,7 @@ void fh_free_problem(feasthip_ctx* h) {
     h->poly = fh_poly();
     h->op = fh_operator();
     h->top = fh_termop();
-    for (void* p : h->lu_factors) if (p) hipFree(p);
-    for (int* p : h->lu_pivots) if (p) hipFree(p);
-    h->lu_factors.clear(); h->lu_pivots.clear(); h->lu_valid.clear(); h->lu_z.clear();
+    h->lu_cache.clear(hipFree);
     fh_banded_free(h);
     h->kind = FH_KIND_NONE;
     h->rs_P = h->rs_basis = h->rs_X = h->rs_R = nullptr;

@@ -221,7 +221,7 @@ __global__ __launch_bounds__(FH_BLOCK) void k_spmm_fan(fh_fan_args a) {
 
 // ---------------------------------------------------------------------------------------
 // RHS_e = R_last + sum_{p < nd} z_e^p D_p for every node in one pass: the nd + 1 panels are read once, ne panels written
-// (stride: what fh_dense_lu_solve_nodes takes as rhs_stride).  D: nd panels of `total` elements one behind the other.
+// (stride: what fh_direct_solve_nodes takes as rhs_stride).  D: nd panels of `total` elements one behind the other.
 // ---------------------------------------------------------------------------------------
 __global__ __launch_bounds__(FH_BLOCK) void k_poly_rhs(const cplx* __restrict__ Rlast, const cplx* __restrict__ D, int nd,
                                                         const cplx* __restrict__ z, int ne, cplx* __restrict__ RHS, size_t stride,
@@ -916,7 +916,7 @@ static int poly_solve_single(feasthip_ctx* h, int ld, int m, cplx z, const cplx*
         if (!rc) *status = st[0];
         return rc;
     }
-    return h->poly.sparse ? fh_banded_solve_single(h, ld, m, z, Rhs, Y, status, nfact) : fh_dense_lu_solve_single(h, ld, m, z, Rhs, Y, status, nfact);
+    return fh_direct_solve_single(h, h->poly.sparse != 0, ld, m, z, Rhs, Y, status, nfact);
 }
 // The same for every contour node, Y_e = P(z_e)^-1 RHS_e (rhs_stride: `panel` for one right-hand side panel per node, 0 for
 // one panel shared by all nodes -- the only form the Krylov drivers take)
@@ -925,8 +925,7 @@ static int poly_solve_nodes(feasthip_ctx* h, int ld, int m, int ne, const cplx* 
         if (rhs_stride != 0) { h->last_error = "internal: a Krylov solver takes one right-hand-side panel shared by the nodes"; return FEASTHIP_ERROR_INTERNAL; }
         return poly_krylov_nodes(h, ld, m, h->zne, RHS, panel, Y, status, it);
     }
-    return h->poly.sparse ? fh_banded_solve_nodes(h, ld, m, ne, h->zne, RHS, rhs_stride, Y, panel, status, nfact)
-                          : fh_dense_lu_solve_nodes(h, ld, m, ne, h->zne, RHS, rhs_stride, Y, panel, status, nfact);
+    return fh_direct_solve_nodes(h, h->poly.sparse != 0, ld, m, ne, h->zne, RHS, rhs_stride, Y, panel, status, nfact);
 }
 
 // The Krylov counts of a call that ran `ne` nodes on m64 columns in 64-column panels: the statistics, and what

@@ -137,12 +137,8 @@ extern "C" int feasthip_release_factors(feasthip_handle h) {
     FH_CHECK(hipSetDevice(h->device));
     FH_CHECK(hipStreamSynchronize(h->stream));
     if (h->side_stream) FH_CHECK(hipStreamSynchronize(h->side_stream));
-    for (void* p : h->lu_factors) if (p) hipFree(p);
-    for (int* p : h->lu_pivots) if (p) hipFree(p);
-    h->lu_factors.clear(); h->lu_pivots.clear(); h->lu_valid.clear(); h->lu_z.clear();
-    for (void* p : h->band_factors) if (p) hipFree(p);
-    for (int* p : h->band_pivots) if (p) hipFree(p);
-    h->band_factors.clear(); h->band_pivots.clear(); h->band_valid.clear(); h->band_z.clear();
+    h->lu_cache.clear(hipFree);
+    h->band_cache.clear(hipFree);
     fh_mf_free_buffers(h);
     return 0;
 }
@@ -217,8 +213,8 @@ extern "C" int feasthip_set_contour(feasthip_handle h, int ne, const double* zne
     h->node_count = ne;
     h->node_ids.resize(ne);
     for (int e = 0; e < ne; ++e) h->node_ids[e] = e;
-    // cached factors stay: slot e is reused only when its shift equals the new z_e exactly (fh_dense_lu_solve_nodes,
-    // fh_banded_solve_nodes), so a repeated solve on the same contour keeps its factorisations and any other contour
+    // cached factors stay: slot e is reused only when its shift equals the new z_e exactly (fh_direct_solve_nodes over
+    // fh_factor_cache::holds), so a repeated solve on the same contour keeps its factorisations and any other contour
     // refactors slot by slot
     return 0;
 }

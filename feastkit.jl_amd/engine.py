@@ -963,6 +963,9 @@ class HipEngine:
         """Drop the cached LU / band factors of the direct solvers (feasthip_release_factors)."""
         self._chk(self.lib.feasthip_release_factors(self.h))
 
+    # `blocked` of band_plan(): the plan of the sparse direct solver
+    PLAN_NARROW, PLAN_BAND, PLAN_MULTIFRONTAL = 0, 1, 2
+
     def band_plan(self):
         """(kl, ku, bytes per node, blocked) of the band the direct sparse solver would eliminate (feasthip_band_plan)."""
         kl, ku, blocked = C.c_int(0), C.c_int(0), C.c_int(0)

@@ -36,6 +36,7 @@ import scipy.linalg as sla
 from . import _lib
 from .contour import (balanced_contour_points, cost_balanced_contour_points, distribute_contour_points, feast_contour,
                       feast_gcontour, feast_inside_gcontour, split_balanced_assignment)
+from .engine import HipEngine
 from .parameters import check_feast_srci_input, feast_tolerance, feastdefault
 from .types import FeastError, FeastResult
 
@@ -1715,7 +1716,7 @@ def feast_hip_general_two_sided(engine, A, B, Emid, r, M0, fpm, *, solver="direc
     def plan_name():
         if not sparse:
             return "dense LU"
-        return ("multifrontal LU on a nested-dissection tree" if engine.band_plan()[3] == 2
+        return ("multifrontal LU on a nested-dissection tree" if engine.band_plan()[3] == HipEngine.PLAN_MULTIFRONTAL
                 else "band LU after reverse Cuthill-McKee")
 
     try:
